@@ -12,6 +12,11 @@ Launch:  python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1 without
                 bench.py --gpus N --steps K --warmup W
          python bench.py --config 64x8                              (BASELINE.json configs[4]: 64 utterances/GPU x 8 GPUs)
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds what takes runs of its own after the
+timed region: the roofline (event-sampled decodes + committed counter figures), the exact-fp32 and reference-golden anchors
+and the CPU baseline.  --dump-outputs DIR writes the mel of the last timed step as DIR/mel.npy (DIR/mel_rank<r>.npy per rank
+when N > 1); the inputs, weights and Philox noise are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -57,13 +62,20 @@ def parse(argv=None):
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 ranks that all use cuda:0 and talk over gloo: exercises the launch / broadcast / sharding / timing path of a "
                          "multi-GPU run on a one-GPU box (RCCL refuses two ranks on one device); the throughput it prints is not a scaling number")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-steps", type=int, default=4, help="diffusion steps timed on the host CPU")
-    ap.add_argument("--profile-steps", type=int, default=2, help="untimed decodes after the timed region whose conv launches are event-sampled")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline, the exact-fp32 and golden anchors and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the mel of the last timed step as DIR/mel.npy (float32; a seeded sample when it exceeds 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-baseline-steps", type=int, default=4, help="diffusion steps timed on the host CPU (--full)")
+    ap.add_argument("--profile-steps", type=int, default=2,
+                    help="untimed decodes after the timed region whose conv launches are event-sampled (--full)")
     ap.add_argument("--no-anchor", action="store_true",
-                    help="skip the untimed anchor legs after the timed region: one decode on an exact-fp32 (v_mfma_f32_32x32x2_f32) handle with "
-                         "the same inputs and noise, and the replay of the reference's 50-step T=1024 golden")
+                    help="--full without the untimed anchor legs after the timed region: one decode on an exact-fp32 (v_mfma_f32_32x32x2_f32) "
+                         "handle with the same inputs and noise, and the replay of the reference's 50-step T=1024 golden")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cb, cg = CONFIGS[a.config] if a.config else (1, 1)
     if a.batch is None:
         a.batch = cb
@@ -242,6 +254,21 @@ def pmc_traffic():
     return None, None, None
 
 
+DUMP_MAX_BYTES = 64_000_000       # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(out, directory, rank, world):
+    """--dump-outputs: this rank's mel of the last timed step as float32 [B, n_feats, T], or, when the ranks' mels together exceed
+    DUMP_MAX_BYTES, a sample of 1/world of that budget per rank at flat indices drawn from a fixed seed (sorted, the same every run)."""
+    mel = out.detach().float().cpu().numpy()
+    cap = DUMP_MAX_BYTES // (4 * world)
+    if mel.size > cap:
+        idx = np.sort(np.random.default_rng(0).choice(mel.size, cap, replace=False))
+        mel = mel.reshape(-1)[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "mel.npy" if world == 1 else f"mel_rank{rank}.npy"), mel)
+
+
 def algorithmic_bytes_per_eval(n_params, Bp, T):
     """the weights once (fp32) + B' * T * 964 B of tensor I/O (x, mu [80, T] and the mask in, the score out)."""
     return 4.0 * n_params + float(Bp) * T * 964.0
@@ -318,22 +345,39 @@ def run_rank(a, rank, local, world, backend="nccl", workload_cls=HipWorkload, de
     slowest, fastest = max_over_ranks(busy, world, device), -max_over_ranks(-busy, world, device)
     median_step = max_over_ranks(float(np.median(per_step)) if per_step else 0.0, world, device)
     assert out is None or torch.isfinite(out).all(), "non-finite decoder output"
-    # per-launch times for the roofline object: separate, untimed decodes with the library's event sampling switched on
-    wl.profile_begin()
-    for _ in range(max(1, min(a.steps, a.profile_steps))):
-        wl.step()
-    wl.sync()
-    prof = wl.profile_end()
-    anchors = {}
-    if rank == 0 and not a.no_anchor and hasattr(wl, "exact_anchor"):
-        anchors["exact_fp32"] = wl.exact_anchor()
-        anchors["golden_mel_l1"] = wl.golden_anchor(cfg)
+    if a.dump_outputs:
+        dump_outputs(out, a.dump_outputs, rank, world)
+    prof, anchors = None, {}
+    if a.full:
+        # per-launch times for the roofline object: separate, untimed decodes with the library's event sampling switched on
+        wl.profile_begin()
+        for _ in range(max(1, min(a.steps, a.profile_steps))):
+            wl.step()
+        wl.sync()
+        prof = wl.profile_end()
+        if rank == 0 and not a.no_anchor and hasattr(wl, "exact_anchor"):
+            anchors["exact_fp32"] = wl.exact_anchor()
+            anchors["golden_mel_l1"] = wl.golden_anchor(cfg)
 
     res = None
     if rank == 0:
         frames_total = world * B * T * a.steps
         value = frames_total / elapsed
         ms_per_step = 1e3 * elapsed / a.steps
+        res = {"metric": "mel-frames/sec @ 50 diffusion steps, 80x1024", "value": value, "unit": "mel-frames/s",
+               "n_gpus": n_ranks, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
+               "ms_per_step_median": 1e3 * median_step, "value_at_median": world * B * T / median_step if median_step > 0 else None,
+               "rccl_ranks": {"backend": backend if world > 1 else None, "world_size": n_ranks, "ranks": ranks},
+               "broadcast_ms": timing.get("broadcast_ms"), "broadcast_bytes": timing.get("bytes"),
+               "rank_busy_s": {"min": fastest, "max": slowest, "note": "each rank's own K steps before the closing barrier"},
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "dtype_note": "fp32 storage and fp32 accumulation everywhere; GEMM products at fp32 accuracy as f16x3 (two fp16 planes per "
+                             "operand, three fp16 MFMA products; per-evaluation error vs fp64 at the fp32 reference's level)",
+               "config": {"workload": f"B={B} utterance(s)/GPU, 80x{T} mel, {N} diffusion steps, text+spk CFG (3 score evals/step), "
+                                      f"full-size decoder (119.1M params, synthetic weights), built-in Philox noise",
+                          "batch_per_gpu": B, "frames": T, "diffusion_steps": N, "parallelism": f"utterance-sharded x{world}"},
+               "rtf": (elapsed / a.steps) / (B * T * HOP / SR)}
+    if res is not None and a.full:
         n_cfg = 3
         flops_step = prof["flops_eval_item"] * n_cfg * B * N
         # dominant kernel: conv_igemm_kernel (every 3x3 / 1x1 / strided / transposed convolution of the U-Net).  Since round 2 its
@@ -373,20 +417,7 @@ def run_rank(a, rank, local, world, backend="nccl", workload_cls=HipWorkload, de
                     "sampled_eval_ms": (prof["eval_ms"] / max(prof["evals"], 1)),
                     # whole_job_tflops is the direct-convolution count of SURVEY.md 8(d) over wall time
                     "whole_job_tflops": flops_step * world / (ms_per_step * 1e-3) / 1e12}
-        res = {"metric": "mel-frames/sec @ 50 diffusion steps, 80x1024", "value": value, "unit": "mel-frames/s",
-               "n_gpus": n_ranks, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
-               "ms_per_step_median": 1e3 * median_step, "value_at_median": world * B * T / median_step if median_step > 0 else None,
-               "rccl_ranks": {"backend": backend if world > 1 else None, "world_size": n_ranks, "ranks": ranks},
-               "broadcast_ms": timing.get("broadcast_ms"), "broadcast_bytes": timing.get("bytes"),
-               "rank_busy_s": {"min": fastest, "max": slowest, "note": "each rank's own K steps before the closing barrier"},
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "dtype_note": "fp32 storage and fp32 accumulation everywhere; GEMM products at fp32 accuracy as f16x3 (two fp16 planes per "
-                             "operand, three fp16 MFMA products; per-evaluation error vs fp64 at the fp32 reference's level)",
-               "config": {"workload": f"B={B} utterance(s)/GPU, 80x{T} mel, {N} diffusion steps, text+spk CFG (3 score evals/step), "
-                                      f"full-size decoder (119.1M params, synthetic weights), built-in Philox noise",
-                          "batch_per_gpu": B, "frames": T, "diffusion_steps": N, "parallelism": f"utterance-sharded x{world}"},
-               "rtf": (elapsed / a.steps) / (B * T * HOP / SR),
-               "roofline": roofline}
+        res["roofline"] = roofline
         for k, v in anchors.items():
             if v is not None:
                 res[k] = v

@@ -215,3 +215,32 @@ def test_bench_refuses_counter_figures_collected_on_another_tree(monkeypatch):
     monkeypatch.setattr(_build, "source_fingerprint", lambda names: "0" * 16)
     per_launch, per_eval, src = bench.pmc_traffic()
     assert per_launch is None and per_eval is None and src["stale"] is True and src["stale_values"]["all_kernels_per_eval"] > 1e10
+
+
+def test_an_up_to_date_library_is_used_without_writing_to_the_tree(tmp_path, monkeypatch):
+    """The tree may be read-only to the account that runs it (built by another): a library newer than every source and header is
+    returned without creating build/ or its lock; a newer source still goes through the locked rebuild."""
+    import os
+    from unitspeech_amd import _build
+    csrc = tmp_path / "pkg" / "csrc"
+    csrc.mkdir(parents=True)
+    for name in ("a.hip", "k.h"):
+        (csrc / name).write_text("//\n")
+    lib = tmp_path / "pkg" / "lib.so"
+    lib.write_bytes(b"")
+    os.utime(csrc / "a.hip", (1000, 1000))
+    os.utime(csrc / "k.h", (1000, 1000))
+    os.utime(lib, (2000, 2000))
+    monkeypatch.setattr(_build, "HERE", str(tmp_path / "pkg"))
+    monkeypatch.setattr(_build, "CSRC", str(csrc))
+    monkeypatch.setattr(_build, "LIB", str(lib))
+    monkeypatch.setattr(_build, "SOURCES", ["a.hip"])
+    monkeypatch.setattr(_build, "HEADERS", ["k.h"])
+    rebuilt = []
+    monkeypatch.setattr(_build, "_build_locked", lambda force, verbose: rebuilt.append(force) or str(lib))
+    assert _build.build_library() == str(lib)
+    assert rebuilt == [] and not (tmp_path / "pkg" / "build").exists()
+    os.utime(csrc / "k.h", (3000, 3000))
+    assert _build.build_library() == str(lib) and rebuilt == [False]
+    assert _build.build_library(force=True) == str(lib) and rebuilt == [False, True]
+    assert os.stat(tmp_path / "pkg" / "build" / ".lock").st_mode & 0o777 == 0o666

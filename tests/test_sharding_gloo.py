@@ -116,7 +116,7 @@ def _bench_worker(rank, world, port, out_dir):
     import bench
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    a = bench.parse(["--gpus", str(world), "--batch", "3", "--frames", "64", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"])
+    a = bench.parse(["--gpus", str(world), "--batch", "3", "--frames", "64", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"])
     a.cfg = CFG
     res = bench.run_rank(a, rank, rank, world, backend="gloo", workload_cls=_FakeWorkload, device=torch.device("cpu"))
     with open(os.path.join(out_dir, f"b{rank}.json"), "w") as f:
@@ -144,6 +144,48 @@ def test_bench_rank_function_two_gloo_ranks(tmp_path):
     assert r0["rank_busy_s"]["min"] < 0.75 * r0["rank_busy_s"]["max"] <= 0.75 * 1e-3 * r0["ms_per_step"] * 4 * 1.01
     assert r0["ms_per_step_median"] >= 40.0 and abs(r0["ms_per_step_median"] - r0["ms_per_step"]) <= 0.25 * r0["ms_per_step"]
     assert r0["roofline"]["algorithmic_bytes_per_eval"] > 0
+
+
+class _CountingWorkload(_FakeWorkload):
+    """_FakeWorkload whose output carries the number of the call that made it; a plain run must not ask for the profile."""
+
+    def step(self):
+        super().step()
+        B, T = self.a.batch, self.a.frames
+        return torch.arange(B * 80 * T, dtype=torch.float32).view(B, 80, T) + 1e6 * self.calls
+
+    def profile_begin(self):
+        raise AssertionError("a plain bench run samples no profile")
+
+
+def test_bench_plain_run_times_its_steps_only_and_dumps_the_last_output(tmp_path, monkeypatch):
+    import bench
+    import pytest
+
+    def run(*extra):
+        a = bench.parse(["--batch", "2", "--frames", "64", "--steps", "3", "--warmup", "2", *extra])
+        a.cfg = CFG
+        made = []
+        res = bench.run_rank(a, 0, 0, 1, backend="gloo", workload_cls=lambda *args: made.append(_CountingWorkload(*args)) or made[0],
+                             device=torch.device("cpu"))
+        return res, made[0]
+
+    res, wl = run("--dump-outputs", str(tmp_path / "a"))
+    assert wl.calls == 2 + 3 and res["steps"] == 3 and res["warmup"] == 2
+    assert res["unit"] == "mel-frames/s" and res["higher_is_better"] is True and res["dtype"] == "f32" and "metric" in res
+    assert res["ms_per_step"] >= 20.0 and abs(res["value"] - 2 * 64 * 3 / (res["ms_per_step"] * 3e-3)) <= 1e-6 * res["value"]
+    assert not {"roofline", "cpu_baseline", "exact_fp32", "golden_mel_l1"} & set(res)
+    mel = np.load(tmp_path / "a" / "mel.npy")
+    assert mel.dtype == np.float32 and mel.shape == (2, 80, 64) and mel.flat[0] == 5e6          # the fifth call: the last timed step
+    # over the size cap: a fixed sample of the same output, identical from run to run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    run("--dump-outputs", str(tmp_path / "b"))
+    run("--dump-outputs", str(tmp_path / "c"))
+    b, c = np.load(tmp_path / "b" / "mel.npy"), np.load(tmp_path / "c" / "mel.npy")
+    assert b.dtype == np.float32 and b.shape == (1000,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.isin(b, mel).all()
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
 
 
 def test_bench_spawns_its_own_ranks_and_refuses_mismatch(monkeypatch):

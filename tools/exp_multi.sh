@@ -1,6 +1,6 @@
 #!/bin/bash
 # several environment variants, interleaved over rounds: tools/exp_multi.sh rounds "<env 1>" "<env 2>" ...  ("-" = defaults)
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --profile-steps 1"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --profile-steps 1"
 n=$1; shift
 for r in $(seq 1 $n); do
   i=0

@@ -1,5 +1,5 @@
 set -e
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --profile-steps 1"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --profile-steps 1"
 $B > gpurun_out/x_base.log 2>&1
 US_TM_1X1=128 $B > gpurun_out/x_1x1_128.log 2>&1
 US_TM_1X1=256 $B > gpurun_out/x_1x1_256.log 2>&1

@@ -11,6 +11,7 @@ The reference never travels to the GPU box; only these data files do.  Re-run wi
 """
 from __future__ import annotations
 
+import contextlib
 import importlib.machinery
 import os
 import random
@@ -85,6 +86,23 @@ class ReplayRandn:
         return d.to(kw.get("dtype", d.dtype))
 
 
+@contextlib.contextmanager
+def correctly_rounded_math():
+    """torch.exp / sqrt / rsqrt rounded once from float64 (NumPy) to the input's dtype, for the schedule tables (G1).  torch computes
+    them through MKL's vector math, whose last bit depends on the code path MKL picks for the CPU (an AMD and an Intel host differ
+    there); the rest of the tables is IEEE + - * / and a sequential cumprod.  The goldens and the test that checks the oracle
+    against them (tests/test_oracle_golden.py) take the three functions from here, so the comparison stays bit-exact on any host."""
+    orig = torch.exp, torch.sqrt, torch.rsqrt
+
+    def once(f):
+        return lambda x: torch.from_numpy(np.asarray(f(x.detach().double().numpy()))).to(x.dtype)
+    torch.exp, torch.sqrt, torch.rsqrt = once(np.exp), once(np.sqrt), once(lambda v: 1.0 / np.sqrt(v))
+    try:
+        yield
+    finally:
+        torch.exp, torch.sqrt, torch.rsqrt = orig
+
+
 def tt(d, dtype=torch.float32):
     return {k: torch.from_numpy(v).to(dtype) for k, v in d.items()}
 
@@ -127,7 +145,8 @@ def main():
     for n in (2, 10, 50):
         inp = tt(synthetic_inputs(TINY, 1, 8, seed=1, n_steps=n))
         # run the reference loop with scales 0 (one cheap estimator call per step) just to build tables
-        run_loop(model, inp, n, 0.0, 0.0)
+        with correctly_rounded_math():
+            run_loop(model, inp, n, 0.0, 0.0)
         names = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_one_minus_alphas_cumprod",
                  "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_variance"]
         save(f"schedule_N{n}", **{k: getattr(model, k) for k in names})

@@ -49,10 +49,19 @@ def _stale(target: str, deps) -> bool:
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 and link the shared library; returns its path.  Serialised across processes by a
-    lock file: the N ranks of a multi-GPU launch all come through here and must not rebuild the same objects side by side."""
+    lock file: the N ranks of a multi-GPU launch all come through here and must not rebuild the same objects side by side.
+    A library newer than every source and header is returned without touching build/: the tree may be read-only to the user
+    who runs it (built by another account)."""
     import fcntl
+    if not force and not _stale(LIB, [os.path.join(CSRC, s) for s in SOURCES] + _headers()):
+        return LIB
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
-    with open(os.path.join(HERE, "build", ".lock"), "w") as lock:
+    path = os.path.join(HERE, "build", ".lock")
+    with open(path, "w") as lock:
+        try:
+            os.chmod(path, 0o666)         # any account sharing this tree can take the lock (another's file is not ours to change)
+        except OSError:
+            pass
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             return _build_locked(force, verbose)
@@ -60,9 +69,13 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
+def _headers():
+    return [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
+
+
 def _build_locked(force: bool, verbose: bool) -> str:
     cc = _hipcc()
-    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
+    hdrs = _headers()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     jobs = []
