@@ -90,12 +90,14 @@ def test_estimator_ragged_lengths_vs_oracle(tiny, T):
     assert out[2].abs().max().item() == 0.0            # fully padded item
 
 
-def _model_with_env(cfg, **env):
-    """A fresh handle created under the given environment (the library reads its tuning switches at us_decoder_create)."""
+def _model_with_env(cfg, exact=False, **env):
+    """A fresh handle created under the given environment (the library reads its tuning switches at us_decoder_create); exact: the
+    exact-fp32 handle (US_CREATE_EXACT_FP32)."""
     old = {k: os.environ.get(k) for k in env}
     os.environ.update({k: str(v) for k, v in env.items()})
     try:
         m = make_model(cfg)
+        m.exact = exact
         with torch.no_grad():      # creates the handle and uploads the weights now, while the environment is in place
             x = torch.zeros(1, 80, 8, device=DEV)
             m.estimator(x, torch.ones(1, 1, 8, device=DEV), x, torch.full((1,), 0.5, device=DEV), torch.zeros(1, 1, cfg.spk_emb_dim, device=DEV))
@@ -119,7 +121,7 @@ def test_winograd_forms_agree_bitwise_and_match_direct_convolution(tiny, T):
     t = torch.tensor([0.21, 0.55, 0.93])
     args = [inp[k].to(DEV) for k in ("z", "mask", "cond")] + [t.to(DEV), inp["spk_emb"].to(DEV)]
     outs = {}
-    for name, env in (("fused", {"US_WINO_FUSE_MIN_WGS": 1}), ("separate", {"US_WINO_FUSE_MIN_WGS": 10 ** 9}),
+    for name, env in (("fused", {"US_WINO_FUSE": 1}), ("separate", {"US_WINO_FUSE": 0}),
                       ("direct", {"US_WINO_MIN_LEVEL": 99}), ("gn_apart", {"US_WINO_FUSE_GN": 0}), ("default", {})):
         m = _model_with_env(TINY, **env)
         with torch.no_grad():
@@ -425,7 +427,7 @@ def test_long_utterance_properties(full):
 
 def test_f16x3_winograd_gemms_match_the_fp32_path(full):
     """Default path: Winograd GEMMs as three fp16 MFMA products of two-plane split operands (fp32 accumulation) against the same
-    GEMMs on the exact-fp32 matrix instruction (US_F16X3=0) and the oracle: same error level, batch composition stays out of the
+    GEMMs on the exact-fp32 matrix instruction (the US_CREATE_EXACT_FP32 handle) and the oracle: same error level, batch composition stays out of the
     result, and the fused / separate output-transform forms still agree bit for bit."""
     _, sd = full
     T = 64
@@ -434,8 +436,8 @@ def test_f16x3_winograd_gemms_match_the_fp32_path(full):
     args = [inp[k].to(DEV) for k in ("z", "mask", "cond")] + [t.to(DEV), inp["spk_emb"].to(DEV)]
     ref = O.estimator_forward(sd, inp["z"], inp["mask"], inp["cond"], t, inp["spk_emb"])
     outs = {}
-    for name, env in (("f16x3", {}), ("fp32", {"US_F16X3": 0}), ("f16x3_fused", {"US_WINO_FUSE_MIN_WGS": 1}),
-                      ("f16x3_separate", {"US_WINO_FUSE_MIN_WGS": 10 ** 9}), ("f16x3_tm64", {"US_F16_TM": 64})):
+    for name, env in (("f16x3", {}), ("fp32", {"exact": True}), ("f16x3_fused", {"US_WINO_FUSE": 1}),
+                      ("f16x3_separate", {"US_WINO_FUSE": 0}), ("f16x3_tm64", {"US_F16_TM": 64})):
         m = _model_with_env(FULL, **env)
         with torch.no_grad():
             outs[name] = m.estimator(*args)

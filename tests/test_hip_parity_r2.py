@@ -172,21 +172,6 @@ def test_strong_attention_evaluation_vs_reference(golden, tag, cfg, Tn):
     assert e <= 2e-6 and e64 <= 2e-6
 
 
-def test_strong_attention_with_128_row_chunks(golden, monkeypatch):
-    """US_ATTN_CHUNK=128: to_qkv on 128-row tiles, one chunk of online-softmax partials per 128 rows (the two-block form of the
-    epilogue in conv_igemm.hip).  Measured slower and off by default; the path is held to the same bar as the default one, on the
-    attention-dominated weights, with ragged lengths (chunks that end inside a tile)."""
-    g = G(golden("estimator_full_attn"))
-    monkeypatch.setenv("US_ATTN_CHUNK", "128")
-    model = make_model(FULL, rezero_g=1.0, qkv_scale=1.0)          # the switch is read when the handle is created
-    inp = G(synthetic_inputs(FULL, 3, 64, seed=2, lengths=[int(v) for v in g["lengths"]]))
-    with torch.no_grad():
-        out = model.estimator(inp["z"].to(DEV), inp["mask"].to(DEV), inp["cond"].to(DEV), g["t"].to(DEV), inp["spk_emb"].to(DEV))
-    e, e64 = l1(out, g["out"]), l1(out, g["out_fp64"])
-    print(f"\n128-row attention chunks: L1 vs reference {e:.3e}, vs fp64 {e64:.3e}")
-    assert e <= 2e-6 and e64 <= 2e-6
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # per-module outputs of the reference (tests/golden/blocks_tiny.npz) through us_debug_block
 # ---------------------------------------------------------------------------------------------------------------
@@ -443,10 +428,9 @@ def test_finetune_graph_replay_matches_eager_iterations(backward):
 
 def test_f16x3_backward_matches_the_exact_fp32_backward_at_a_pretraining_batch():
     """Every parameter gradient of one full-size loss over 8 crops of 176 frames: the default backward (f16x3 GEMMs for forward, data
-    and weight gradients, incoming gradient scaled by an exact power of two) against the exact-fp32 MFMA backward (US_F16X3=0) of the
+    and weight gradients, incoming gradient scaled by an exact power of two) against the exact-fp32 MFMA backward (the US_CREATE_EXACT_FP32 handle) of the
     same weights and draws.  dL/dscore is ~1e-5 here, below fp16's normal range: without the scaling the whole-gradient error is
     1.2e-6 and the median tensor is at 3.7e-6 (tools/grad_accuracy.py)."""
-    import os
     import random
     cfg = FULL
     sd = {k: torch.from_numpy(v) for k, v in synthetic_state_dict(cfg, 0).items()}
@@ -458,27 +442,19 @@ def test_f16x3_backward_matches_the_exact_fp32_backward_at_a_pretraining_batch()
     spk = torch.from_numpy(g.standard_normal((B, 1, cfg.spk_emb_dim), dtype=np.float32)).to(DEV)
     spk = spk / spk.norm(dim=-1, keepdim=True)
 
-    def grads(env, loss_factor=1.0):
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            m = UnitSpeech(cfg.n_feats, cfg.dim, list(cfg.dim_mults), cfg.beta_min, cfg.beta_max, cfg.pe_scale, cfg.spk_emb_dim)
-            m.load_state_dict(sd)
-            m = m.to(DEV).train()
-            random.seed(0); torch.manual_seed(0)
-            loss, _ = m.compute_loss(x0, mask, cond, spk)
-            (loss * loss_factor).backward()
-            torch.cuda.synchronize()
-            return float(loss), {n: p.grad.detach().double().cpu() for n, p in m.named_parameters() if p.grad is not None}
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
+    def grads(exact=False, loss_factor=1.0):
+        m = UnitSpeech(cfg.n_feats, cfg.dim, list(cfg.dim_mults), cfg.beta_min, cfg.beta_max, cfg.pe_scale, cfg.spk_emb_dim)
+        m.load_state_dict(sd)
+        m = m.to(DEV).train()
+        m.exact = exact
+        random.seed(0); torch.manual_seed(0)
+        loss, _ = m.compute_loss(x0, mask, cond, spk)
+        (loss * loss_factor).backward()
+        torch.cuda.synchronize()
+        return float(loss), {n: p.grad.detach().double().cpu() for n, p in m.named_parameters() if p.grad is not None}
 
-    l_ref, ref = grads({"US_F16X3": "0"})
-    l_new, new = grads({})
+    l_ref, ref = grads(exact=True)
+    l_new, new = grads()
     assert len(ref) == 228 and abs(l_ref - l_new) <= 1e-6
     whole = float(torch.sqrt(sum(((new[n] - ref[n]) ** 2).sum() for n in ref)) / torch.sqrt(sum((ref[n] ** 2).sum() for n in ref)))
     per = sorted(float((new[n] - ref[n]).norm() / (ref[n].norm() + 1e-300)) for n in ref)
@@ -489,6 +465,6 @@ def test_f16x3_backward_matches_the_exact_fp32_backward_at_a_pretraining_batch()
     assert whole <= 6e-7 and median <= 1.5e-6 and worst <= 1e-4
     # the factor is taken from the data, so a caller's own (power-of-two) loss scaling changes nothing but the exponent: a summed
     # instead of a mean-reduced loss cannot push the scaled gradients out of fp16's range
-    _, big = grads({}, loss_factor=float(2 ** 17))
+    _, big = grads(loss_factor=float(2 ** 17))
     drift = float(torch.sqrt(sum(((big[n] * 2.0 ** -17 - new[n]) ** 2).sum() for n in new)) / torch.sqrt(sum((new[n] ** 2).sum() for n in new)))
     assert drift <= 3e-7, drift          # two runs differ by the order of their fp32 atomics only

@@ -17,9 +17,6 @@ ap.add_argument("--dim", type=int, default=128)
 ap.add_argument("--wino-min-level", type=int, default=1, help="levels >= this run their 3x3 convs as Winograd (US_WINO_MIN_LEVEL)")
 ap.add_argument("--wino4", default=__import__("os").environ.get("US_WINO4", "0,44,44,24"),
                 help="per-level 4-wide Winograd form of the inference path (US_WINO4): 0 = F(2x2), 44 = F(4x4), 24 = F(2x4)")
-ap.add_argument("--wino-narrow", action="store_true", help="US_WINO_NARROW=1: Winograd also where cout <= dim (the last up level)")
-ap.add_argument("--no-wtotal", action="store_true", help="US_ATTN_WTOTAL=0: q is computed and stored at every level")
-ap.add_argument("--no-split-copy", action="store_true", help="US_SPLIT_COPY=0: res_conv stays the last launch of every ResnetBlock")
 a = ap.parse_args()
 
 F, T, BP = 80, a.frames, a.bp
@@ -57,10 +54,10 @@ def conv(name, l_out_pixels, cin, cout, taps, wino=False, level=0):
 
 
 def resnet(name, l, cin, cout, first=False):
-    wino = l >= WMIN and (cout > a.dim or a.wino_narrow)
+    wino = l >= WMIN and cout > a.dim
     # a block whose successor takes a split copy of its output (direct convolutions: the narrow last up level) runs res_conv FIRST and
     # lets block2's GroupNorm pass add it (decoder.hip, resnet(): split_out)
-    res_first = cin != cout and not first and not wino and not a.no_split_copy
+    res_first = cin != cout and not first and not wino
     if res_first:
         conv(f"{name}.res 1x1 {cin}->{cout} L{l}", npx(l), cin, cout, 1)
     if not first:
@@ -71,7 +68,7 @@ def resnet(name, l, cin, cout, first=False):
 
 
 def attn(name, l, c):
-    if l == 0 and c <= 128 and not a.no_wtotal:
+    if l == 0 and c <= 128:
         # q folded away (decoder.hip, attention(): W_total): to_qkv computes k | v only, the output projection is C x C on x itself
         conv(f"{name}.kv 1x1 {c}->256 L{l}", npx(l), c, 256, 1)
         conv(f"{name}.out 1x1 {c}->{c} L{l} (W_total)", npx(l), c, c, 1)

@@ -1,5 +1,5 @@
 // Micro-benchmark of the implicit-GEMM convolution kernel on synthetic shapes (build: see tools/conv_bench.sh).
-// usage: conv_bench [debug_mask]
+// usage: conv_bench   (environment: CB_CALIBRATE, CB_ONLY, CB_F16, CB_PRESPLIT, CB_TM, CB_SPLITK, CB_STATS, CB_NO_XCDZ, CB_COLD)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -202,11 +202,9 @@ static void calibrate() {
 
 struct Shape { const char* name; int B, H, W, Cin, Cout, taps; int wino = 0; };   // wino: B = 16 frequencies x 3 items, one weight matrix per frequency
 
-int main(int argc, char** argv) {
-  int debug_arg = argc > 1 ? atoi(argv[1]) : 0;
-  const int debug = debug_arg;
+int main() {
   CK(conv_igemm_init());
-  if (debug == 0) calibrate();
+  if (getenv("CB_CALIBRATE")) calibrate();
   Shape shapes[] = {{"L0 3x3 128->128", 3, 80, 1024, 128, 128, 9}, {"L1 3x3 256->256", 3, 40, 512, 256, 256, 9},
                     {"L2 3x3 512->512", 3, 20, 256, 512, 512, 9}, {"L3 3x3 1024->1024", 3, 10, 128, 1024, 1024, 9},
                     {"L3 3x3 2048->512", 3, 10, 128, 2048, 512, 9}, {"L0 1x1 128->384", 3, 80, 1024, 128, 384, 1},
@@ -245,18 +243,14 @@ int main(int argc, char** argv) {
       if (sh.wino || presplit) hipLaunchKernelGGL(to_f16x2_kernel, dim3(4096), dim3(256), 0, 0, in, n_in / 8);
       hipLaunchKernelGGL(to_f16x2_kernel, dim3(4096), dim3(256), 0, 0, w, n_w / 8);
     }
-    const int n_ab = getenv("CB_AB") ? 2 : 1;           // CB_AB=<bit>: every case also with that debug bit set, back to back
-    const int ab_bit = getenv("CB_AB") ? atoi(getenv("CB_AB")) : 0;
-    for (int ab = 0; ab < n_ab; ++ab)
     for (int tm : {0, 256, 128, 64}) {
       if (tm == 0 && !(getenv("CB_TM") && atoi(getenv("CB_TM")) == 0)) continue;
       if (getenv("CB_TM") && atoi(getenv("CB_TM")) != tm) continue;
       if (tm == 256 && !(f16 && sh.wino != 2)) continue;
-      const int debug = debug_arg | ((ab != 0) != (getenv("CB_AB_FIRST") != nullptr) ? ab_bit : 0);
       ConvArgs a; memset(&a, 0, sizeof a);
       a.in = in; a.in_ld = sh.Cin; a.wt = w; a.bias = bias; a.out = out; a.out_ld = sh.Cout; a.zeros = zeros;
       a.B = sh.B; a.Hin = a.Hout = a.Hs = sh.H; a.Win = a.Wout = a.Ws = sh.W; a.Cin = sh.Cin; a.Cout = sh.Cout;
-      a.ostep = 1; a.istride = 1; a.ntaps = sh.taps; a.bk = 32; a.tm = tm; a.omask_bmod = 1; a.debug = debug;
+      a.ostep = 1; a.istride = 1; a.ntaps = sh.taps; a.bk = 32; a.tm = tm; a.omask_bmod = 1;
       a.splitk_ws = skws; a.splitk_ws_floats = skfl;
       a.f16 = f16 ? ((sh.wino || presplit) ? 1 : 2) : 0;
       static double* stats = nullptr;
@@ -335,7 +329,7 @@ int main(int argc, char** argv) {
         CK(hipEventElapsedTime(&ms, e0, e1)); ms /= reps;
       }
       double fl = 2.0 * sh.B * sh.H * sh.W * (double)sh.Cin * sh.Cout * sh.taps * (sh.wino == 2 ? 16 : 1);
-      printf("%-20s tm=%3d %s debug=%d  %8.1f us  %6.1f TFLOP/s\n", sh.name, tm, f16 ? "f16x3" : "fp32 ", debug, ms * 1e3, fl / ms / 1e9);
+      printf("%-20s tm=%3d %s  %8.1f us  %6.1f TFLOP/s\n", sh.name, tm, f16 ? "f16x3" : "fp32 ", ms * 1e3, fl / ms / 1e9);
     }
     CK(hipFree(in)); CK(hipFree(out)); CK(hipFree(w)); CK(hipFree(bias));
   }

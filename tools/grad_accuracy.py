@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Relative error of every parameter gradient of one full-size fine-tune loss (B crops of 176 frames) between the f16x3 backward
-(default) and the exact-fp32 MFMA backward (US_F16X3=0), same weights, same draws: how much the two-plane fp16 operands cost where
+(default) and the exact-fp32 MFMA backward (the US_CREATE_EXACT_FP32 handle), same weights, same draws: how much the two-plane fp16 operands cost where
 gradients are small (a mean-reduced loss puts dL/dy around 1/(B*80*176)).   python tools/grad_accuracy.py [--batch 1]"""
 import argparse
 import os
@@ -28,23 +28,21 @@ spk = torch.from_numpy(g.standard_normal((B, 1, cfg.spk_emb_dim), dtype=np.float
 spk = spk / spk.norm(dim=-1, keepdim=True)
 
 
-def grads(env):
-    os.environ.update(env)
+def grads(exact=False):
     m = UnitSpeech(cfg.n_feats, cfg.dim, list(cfg.dim_mults), cfg.beta_min, cfg.beta_max, cfg.pe_scale, cfg.spk_emb_dim)
     m.load_state_dict(sd)
     m = m.cuda().train()
+    m.exact = exact
     random.seed(0); torch.manual_seed(0)
     loss, _ = m.compute_loss(x0, mask, cond, spk)
     loss.backward()
     torch.cuda.synchronize()
     out = {n: p.grad.detach().double().cpu() for n, p in m.named_parameters() if p.grad is not None}
-    for k in env:
-        os.environ.pop(k)
     return float(loss), out
 
 
-l_ref, ref = grads({"US_F16X3": "0"})
-l_new, new = grads({})
+l_ref, ref = grads(exact=True)
+l_new, new = grads()
 rel = {n: float((new[n] - ref[n]).norm() / (ref[n].norm() + 1e-300)) for n in ref}
 worst = sorted(rel.items(), key=lambda kv: -kv[1])[:8]
 tot = float(torch.sqrt(sum(((new[n] - ref[n]) ** 2).sum() for n in ref)) / torch.sqrt(sum((ref[n] ** 2).sum() for n in ref)))

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // each A tile nt times and each B tile mt times -- share ONE L2 (dealt by x alone they sat on all eight: 342 MB of fabric
   // traffic per launch against 130 MB of operands, rocprofv3 FETCH_SIZE).
   int bt = (int)blockIdx.x, bz = (int)blockIdx.z;
-  const bool xcd_z = a.xcd_z && ((gridDim.x * gridDim.z) & 7u) == 0 && !(a.debug & 256);
+  const bool xcd_z = a.xcd_z && ((gridDim.x * gridDim.z) & 7u) == 0;
   if (xcd_z) {
     const unsigned lin = blockIdx.x + gridDim.x * blockIdx.z;
     const unsigned lp = (lin & 7u) * ((gridDim.x * gridDim.z) >> 3) + (lin >> 3);
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // The grid's x dimension enumerates (row tile, column tile) pairs with the column tile fastest, so the column tiles of one row
   // tile -- which re-read the same A rows -- run back to back on the same XCD (the re-reads used to come from the Infinity Cache:
   // 765 MB of fabric traffic per level-2 Winograd GEMM against 270 MB of operands, rocprofv3 FETCH_SIZE).
-  if (!xcd_z && (gridDim.x & 7u) == 0 && !(a.debug & 256)) bt = (bt & 7) * (int)(gridDim.x >> 3) + (bt >> 3);
+  if (!xcd_z && (gridDim.x & 7u) == 0) bt = (bt & 7) * (int)(gridDim.x >> 3) + (bt >> 3);
   const int bx = bt / a.nt;
   const int ks = a.ksplit > 1 ? bx % a.ksplit : 0;
   const int m0 = (a.ksplit > 1 ? bx / a.ksplit : bx) * TM, n0 = (bt - bx * a.nt) * TN;
@@ -178,23 +178,14 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       const bool ok = mv[j] && (unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win;
       const unsigned off = ((unsigned)(iy * a.Win + ix) * (unsigned)a.in_ld + (unsigned)achunk[j]) * 4u;
       aoff[j] = ok ? off : a_bytes;
-#ifdef US_CONV_ABLATE
-      if (a.debug & 32) aoff[j] = (unsigned)(j * 4096 + lane * 16) & 0xffff;      // every load hits one hot 64 KB window
-#endif
     }
     wtap_bytes = (unsigned)wt_i * (unsigned)nchunk * (unsigned)wrows * (unsigned)(BK * 4);
-#ifdef US_CONV_ABLATE
-    if (a.debug & 32) wtap_bytes = 0;
-#endif
   };
   auto dma = [&](int ch, int buf) {
     float* As = smem + buf * BUF;
     float* Bs = As + TM * BK;
-    unsigned ach = (unsigned)ch * (unsigned)(BK * 4);
-    unsigned wb = wtap_bytes + (unsigned)ch * (unsigned)wrows * (unsigned)(BK * 4);
-#ifdef US_CONV_ABLATE
-    if (a.debug & 32) { ach = 0; wb = 0; }
-#endif
+    const unsigned ach = (unsigned)ch * (unsigned)(BK * 4);
+    const unsigned wb = wtap_bytes + (unsigned)ch * (unsigned)wrows * (unsigned)(BK * 4);
 #pragma unroll
     for (int j = 0; j < IA; ++j) blds16(rsrc_a, aoff[j], ach, As + (wave * IA + j) * RPI * BK);
 #pragma unroll
@@ -204,10 +195,8 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // Two-level accumulation: the MFMA chain (an exact fp32 fma chain) runs over 128 K-elements, then is folded into
   // `total`.  A single chain over K = 9*Cin (up to 18,432) would carry ~0.2*sqrt(K) ulp of rounding error (19 ulp
   // at K = 9,216); chunks of ~sqrt(K) bring it to ~3 ulp, on par with a blocked CPU sgemm.
-#ifndef US_FLUSH_K
-#define US_FLUSH_K 128
-#endif
-  constexpr int kFlushSteps = US_FLUSH_K / BK;
+  constexpr int kFlushK = 128;
+  constexpr int kFlushSteps = kFlushK / BK;
   f32x16 acc[MB][NB], total[MB][NB];
 #pragma unroll
   for (int i = 0; i < MB; ++i)
@@ -222,19 +211,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   const int a_row = (wm * WM + l32) * BK;
   const int b_row = TM * BK + (wn * (32 * NB) + l32) * BK;
 
-#ifndef US_PRIO_MODE
-#define US_PRIO_MODE 0
-#endif
-#if US_PRIO_MODE == 1
-  // static per-workgroup priority: co-resident workgroups that would otherwise march in lockstep (same code, same
-  // barrier cadence, one shared matrix pipe per SIMD) take turns instead
-  {
-    const unsigned hsh = (blockIdx.x * 2654435761u + blockIdx.y * 40503u + blockIdx.z * 7u) >> 13;
-    if ((hsh & 3) == 1) __builtin_amdgcn_s_setprio(1);
-    else if ((hsh & 3) == 2) __builtin_amdgcn_s_setprio(2);
-    else if ((hsh & 3) == 3) __builtin_amdgcn_s_setprio(3);
-  }
-#endif
   constexpr int NY = WINO ? 4 : 1;
   f32x16 Y[NY][MB][NB];       // WINO: the 2x2 output accumulators (dead otherwise)
   if (WINO) {
@@ -331,13 +307,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       // chunk (2 * kgroup + plane) of the row; lane half hh supplies channels 8 * (2 s + hh) .. + 7 of the chunk's 32
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-#ifdef US_ABL_LDS      // timing experiment: half the fragment reads (the lo planes alias the hi planes; results are wrong)
-        if (p == 1 && !ASPLIT) {
-          for (int i = 0; i < MB; ++i) fa[i * 2 + 1] = fa[i * 2];
-          for (int nb = 0; nb < NB; ++nb) fb[nb * 2 + 1] = fb[nb * 2];
-          continue;
-        }
-#endif
         const int co = ((((2 * s_ + hh) << 1) + p) ^ sw) * 4;
         if (!ASPLIT) {
 #pragma unroll
@@ -368,9 +337,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
           fa[i * 2 + 1] = __builtin_bit_cast(f32x4, lo);
         }
       }
-#ifndef US_NO_SCHEDBAR
       __builtin_amdgcn_sched_barrier(0);
-#endif
       return;
     }
     const int co = ((2 * s_ + hh) ^ sw) * 4;
@@ -380,9 +347,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
     for (int nb = 0; nb < NB; ++nb) fb[nb] = *reinterpret_cast<const f32x4*>(base + b_row + nb * 32 * BK + co);
     // keep the reads AHEAD of the MFMAs that follow in program order (hipcc otherwise sinks them behind the
     // MFMA block and waits for them at once, exposing the LDS latency)
-#ifndef US_NO_SCHEDBAR
     __builtin_amdgcn_sched_barrier(0);
-#endif
   };
   // NSTG == 3: the DMA of chunk s+2 is issued from inside the first MFMA block of step s (it has two steps to land), so its
   // issue slots (M0 write + buffer_load per piece) run under executing MFMAs instead of ahead of them with the matrix pipe idle
@@ -391,18 +356,13 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // F16: the pieces of a chunk (IA + IB LDS-DMA instructions per wave) are spread over the step's MFMAs instead of issued back to
   // back: eight waves issuing 48 of them at once fill the CU's one address queue, and the waves (and the MFMAs queued behind their
   // loads) wait there (tools/conv_bench: the burst costs 15 % of the Winograd-domain GEMMs, twice as many instructions 40 %)
-#ifndef US_DMA_SPREAD
-#define US_DMA_SPREAD 1
-#endif
   constexpr int NPIECE = IA + IB;
   constexpr int SLOTS = 6 * MB * NB;                  // F16 MFMAs of a wave per chunk
   constexpr int PSTRIDE = SLOTS / NPIECE > 0 ? SLOTS / NPIECE : 1;
   unsigned pend_ach = 0, pend_wb = 0;
   auto dma_piece = [&](int k) {
     if (!dma_pending) return;
-#ifndef US_NO_SCHEDBAR
     __builtin_amdgcn_sched_barrier(0);
-#endif
     if (k == 0) {
       if (ch_n == 0) {
         if (WINO) setup_freq(tap_n);
@@ -419,18 +379,14 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       if (++ch_n == nchunk) { ch_n = 0; ++tap_n; }
       dma_pending = false;
     }
-#ifndef US_NO_SCHEDBAR
     __builtin_amdgcn_sched_barrier(0);
-#endif
   };
   auto dma_slot = [&](int sidx) {
-    if (US_DMA_SPREAD && F16 && sidx % PSTRIDE == 0 && sidx / PSTRIDE < NPIECE) dma_piece(sidx / PSTRIDE);
+    if (F16 && sidx % PSTRIDE == 0 && sidx / PSTRIDE < NPIECE) dma_piece(sidx / PSTRIDE);
   };
   auto dma_late = [&]() {
     if (NSTG == 3 && dma_pending) {
-#ifndef US_NO_SCHEDBAR
       __builtin_amdgcn_sched_barrier(0);
-#endif
       if (ch_n == 0) {
         if (WINO) setup_freq(tap_n);
         else setup_tap(tap_n);
@@ -438,9 +394,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       dma(ch_n, dma_buf);
       if (++ch_n == nchunk) { ch_n = 0; ++tap_n; }
       dma_pending = false;
-#ifndef US_NO_SCHEDBAR
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
   };
   auto mma = [&](const f32x4* fa, const f32x4* fb, int phase = 0) {      // phase: first / second 16-deep step of the chunk (F16)
@@ -456,17 +410,11 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
           dma_slot(s0);
           total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, total[i][j], 0, 0, 0);
           dma_slot(s0 + 1);
-#ifndef US_EXP_TWO_PRODUCT      // experiment build: drop a_lo * b_hi, i.e. the A operand at fp16 precision
           total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, total[i][j], 0, 0, 0);
-#endif
           dma_slot(s0 + 2);
-          if (!US_DMA_SPREAD && i == 0 && j == 0) dma_late();
         }
       return;
     }
-#if US_PRIO_MODE == 2
-    __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -474,9 +422,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[i][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][j], fb[nb][j], acc[i][nb], 0, 0, 0);
       }
-#if US_PRIO_MODE == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
   };
   auto step_done = [&]() {
     if (two_level && ++since_flush == kFlushSteps) {
@@ -496,8 +441,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   US_LIFE_AT(1);
 #endif
   if (NSTG == 3) {
-    // static priority for the second-dispatched half of an 8-wave workgroup (the arbitration loser of every segment); experiment bit
-    if (NW == 8 && (a.debug & 512) && wave >= 4) __builtin_amdgcn_s_setprio(1);
     // chunk s lives in buffer s % 3.  At step s: wait for this wave's pieces of chunk s (chunk s+1 may stay in flight), barrier
     // (everybody's pieces have landed, and everybody is done reading chunk s-1, whose buffer chunk s+2 is about to overwrite),
     // issue chunk s+2, multiply chunk s.
@@ -514,23 +457,16 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       US_STAMP_AT(st_t1);
       st_wait += st_t1 - st_t0;
 #endif
-#ifdef US_CONV_ABLATE
-      if (!(a.debug & 1024))       // timing ablation: no barrier in the three-buffer loop (races: results are wrong)
-#endif
       __builtin_amdgcn_s_barrier();
 #ifdef US_STAMP
       US_STAMP_AT(st_t2);
       st_bar += st_t2 - st_t1;
 #endif
-#ifdef US_ABL_DMA       // timing experiment: no loads in the loop (stale tiles; results are wrong)
-      if (false) {
-#else
       if (step + 2 < S_run) {
-#endif
         dma_pending = true;
         dma_buf = cur == 0 ? 2 : cur - 1;
         // fp32 MFMA form, and the first step of the deferred loop (whose first MFMA block does not run): all pieces at once
-        if (!F16 || (a.debug & 64) || (US_DMA_SPREAD && step == 0 && !WINO)) dma_late();
+        if (!F16 || (step == 0 && !WINO)) dma_late();
       }
       const float* base = smem + cur * BUF;
       // as in the two-buffer loop, the MFMAs of a chunk's last 16-deep step run after the next barrier, under the first
@@ -579,47 +515,17 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
     }
   } else {
   for (int step = 0; step < S_run; ++step) {
-    const bool has_next = step + 1 < S_run;
-#ifndef US_DMA_SPREAD2
-#define US_DMA_SPREAD2 0       // two-buffer loop: spreading measured within noise either way (three workgroups per CU already interleave)
-#endif
-    if (has_next && US_DMA_SPREAD2 && F16 && step > 0) {
-      dma_pending = true;          // the pieces go out between this step's MFMAs (dma_slot)
-      dma_buf = (step + 1) & 1;
-    } else if (has_next) {
+    // (spreading the DMA pieces over the MFMAs, as the three-buffer loop does, measured within noise here: three workgroups per CU
+    // already interleave)
+    if (step + 1 < S_run) {
       if (ch_n == 0) {
         if (WINO) setup_freq(tap_n);
         else setup_tap(tap_n);
       }
-#ifdef US_CONV_ABLATE
-      if (!(a.debug & 1))
-#endif
       dma(ch_n, (step + 1) & 1);
       if (++ch_n == nchunk) { ch_n = 0; ++tap_n; }
     }
     const float* base = smem + (step & 1) * BUF;
-#ifdef US_CONV_ABLATE      // timing ablations of tools/conv_bench only (results are wrong by construction)
-    if ((a.debug & 2) && step > 0) {
-      mma(fa1, fb1); step_done(); mma(fa0, fb0);
-      if (NS == 4) { mma(fa1, fb1); mma(fa0, fb0); }
-      if (!(a.debug & 4)) __syncthreads();
-      continue;
-    }
-#endif
-#ifdef US_NO_DEFER
-    load_frags(fa0, fb0, base, 0);
-    load_frags(fa1, fb1, base, 1);
-    mma(fa0, fb0);
-    if (NS == 4) {
-      load_frags(fa0, fb0, base, 2);
-      mma(fa1, fb1);
-      load_frags(fa1, fb1, base, 3);
-      mma(fa0, fb0);
-    }
-    mma(fa1, fb1);
-    step_done();
-    if (WINO && (step + 1) % nchunk == 0) fold(step / nchunk);
-#else
     load_frags(fa0, fb0, base, 0);
     if (step > 0) {           // last sub-step of the previous chunk (fragments were read before the barrier)
       mma(fa1, fb1, 0);
@@ -634,17 +540,11 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       load_frags(fa1, fb1, base, 3);
       mma(fa0, fb0);
     }
-#endif
-#ifdef US_CONV_ABLATE
-    if (!(a.debug & 4))
-#endif
     __syncthreads();   // drains this wave's DMA and fragment reads (vmcnt(0), lgkmcnt(0)) and orders every wave's
                        // reads of this buffer before its next overwrite
   }
-#ifndef US_NO_DEFER
   mma(fa1, fb1);
   if (WINO) fold(15);
-#endif
   }   // NSTG == 2
 #ifdef US_LIFE
   US_LIFE_AT(2);
@@ -674,19 +574,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // separate output transform (chosen by launch geometry, i.e. by the batch) agree to fp64 rounding
   typedef typename std::conditional<WINO, double, float>::type stat_t;
   stat_t gsum[NB] = {}, gsq[NB] = {};
-#ifdef US_CONV_ABLATE
-  if (a.debug & 8) {       // timing ablation: no epilogue at all (keep the accumulators alive)
-    float keep = 0.f;
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) keep += acc[i][j][r];
-    if (keep == 1.2345e-30f) a.out[0] = keep;
-    return;
-  }
-#endif
   if (a.ksplit > 1) {
     // raw partial sums into this slice's slab [ks][B][Ms][Cout]; splitk_finish_kernel sums the slices in a fixed order and
     // applies bias / Rezero / residual / mask / GroupNorm sums (deterministic, unlike float atomics)
@@ -711,7 +598,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // wave instruction, 4x fewer memory instructions than the native layout (the epilogue was half the time of the K=128
   // 1x1 convolutions and 11 % of the level-0 3x3s).
   __syncthreads();                                   // every wave is done with the operand buffers
-  if constexpr (!WINO && (MB == 1 || MB == 2) && NB == 2) {
+  if constexpr (!WINO && MB == 1 && NB == 2) {
     if (a.attn_part_ctx && n0 >= a.attn_q_cols) {
       // to_qkv column tiles 1 / 2: this wave's two 32-column blocks are k_h and v_h of head h for 32 of the tile's 64 rows
       // (qkv_src_row).  Linear attention (unitspeech/unitspeech.py:91-92): k = softmax over ALL n positions, ctx = k v^T; here the
@@ -722,8 +609,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       float* xm = smem;                  // [wn][wm][32]  column maxima of each wave
       float* xs = smem + 128;            // [wn][32]      column sums of wave wm = 1
       float* xc = smem + 256;            // [wn][32][32]  ctx of wave wm = 1
-      // (MB = 2: the 128-row tile, ConvArgs::attn_rows = 128 -- each wave holds 64 rows of k_h | v_h as two 32-row blocks; one chunk of
-      // partials per 128 rows: half the hand-offs, half the partials to merge)
       const int mrow0 = m0 + wm * WM + 4 * hh;
       float kmax = -INFINITY;
 #pragma unroll
@@ -883,9 +768,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   }
 #ifdef US_LIFE
   US_LIFE_AT(4);                                         // every store issued
-#ifdef US_LIFE_DRAIN
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the stores have left the wave)
-#endif
   US_LIFE_AT(3);
   if (a.stamp_out && lane == 0) {
     unsigned long long* o = a.stamp_out + ((blockIdx.x + gridDim.x * blockIdx.z) * NW + wave) * 4;
@@ -989,14 +871,9 @@ hipError_t conv_igemm_init() {
   if ((e = set_attr<32, 64, false, true, 2, 2, true>()) != hipSuccess) return e;
   if ((e = set_attr<32, 32, false, true, 2, 2, true>()) != hipSuccess) return e;
   if ((e = set_attr<32, 32, false, true>()) != hipSuccess) return e;
-  if ((e = set_attr<32, 32, true, true>()) != hipSuccess) return e;
   if ((e = set_attr<32, 32, true, true, 2, 3>()) != hipSuccess) return e;
   return set_attr<16, 32, true>();
 }
-
-static int g_tm64_threshold = -1;
-static int g_splitk = -1;
-static int g_f16_tm = -1;      // US_F16_TM: rows per workgroup of the f16x3 GEMMs (128 or 64)
 
 hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   ConvArgs a = a_in;
@@ -1014,16 +891,6 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     if (a.Cout % kGroups != 0 || (cg & (cg - 1)) != 0) return hipErrorInvalidValue;
   }
   if (a.out2 && (a.out2_ld % 4 != 0 || a.wino_out || a.out_split || a.attn_part_ctx)) return hipErrorInvalidValue;
-  if (g_f16_tm < 0) {
-    const char* e = getenv("US_F16_TM");
-    g_f16_tm = e ? atoi(e) : 0;
-  }
-  if (g_tm64_threshold < 0) {
-    const char* e = getenv("US_TM64_THRESHOLD");
-    // measured on MI355X (tools/conv_bench, bench.py): three co-resident 64-row workgroups per CU (136 VGPRs, 48 KB LDS)
-    // hide the per-chunk barrier better than two 128-row ones at every U-Net shape and batch measured (B'=3 and 24)
-    g_tm64_threshold = e ? atoi(e) : (1 << 30);
-  }
   const int Ms = a.Hs * a.Ws;
   int tn = TN;                        // 64: the half-width tile of the Winograd-domain GEMMs (conv_igemm_kernel<.., NB = 1>), chosen below
   int nt = (a.Cout + TN - 1) / TN;
@@ -1032,63 +899,46 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     // f16x3: the weights are pre-split; f16 = 1: so is the A operand (Winograd-domain GEMMs, planes written by the input
     // transforms); f16 = 2: A is a plain fp32 activation tensor, split in the kernel (any tap geometry)
     if (a.bk != 32) return hipErrorInvalidValue;
-    if (a.f16 == 1 && !a.direct_presplit && a.ntaps == 1 && a.istride == 1 && !a.bias && !a.add && !a.splitk_raw) a.splitk_ws = nullptr;    // Winograd-domain GEMMs
-    if (tm == 0 && g_f16_tm > 0) tm = g_f16_tm;
+    if (a.f16 == 1 && !a.direct_presplit && a.ntaps == 1 && a.istride == 1 && !a.bias && !a.add) a.splitk_ws = nullptr;    // Winograd-domain GEMMs
     if (tm == 0) {
       if (a.f16 == 1 && (a.ntaps > 1 || a.direct_presplit)) {
         // a direct convolution whose producer wrote the two-plane form: no split work in the kernel, so the 128-row tile (wave tile
         // 64 x 64, two workgroups per CU) wins over three 64-row ones: +1.4 % end to end with four such convolutions, 256 rows +1.0 %
-        // (US_TM_PRESPLIT overrides).  A function of the item's geometry only, like the rule below.
-        static int tm_pre = -1;
-        if (tm_pre < 0) { const char* e = getenv("US_TM_PRESPLIT"); tm_pre = e ? atoi(e) : 0; }
-        tm = tm_pre > 0 ? tm_pre : ((long long)a.Hs * a.Ws >= 512 ? 128 : 64);
-        static int tm_pre1 = -1;                     // 1x1 with a pre-split input (the folded to_out, K = 128): US_TM_PRESPLIT_1X1
-        if (tm_pre1 < 0) { const char* e = getenv("US_TM_PRESPLIT_1X1"); tm_pre1 = e ? atoi(e) : 64; }
-        if (a.ntaps == 1 && a.nphase <= 1) tm = tm_pre1;
+        // (1x1 with a pre-split input, the folded to_out with K = 128: 64 rows).  A function of the item's geometry only, like the rule below.
+        tm = (a.ntaps == 1 && a.nphase <= 1) || (long long)a.Hs * a.Ws < 512 ? 64 : 128;
       } else if (a.f16 == 1) {
         // Winograd-domain GEMMs (all items of a frequency in one M range).  Round 3's rule (256 rows whenever that leaves 384 workgroups)
         // ignored wave quantisation: a B = 1 level-3 launch of 384 such workgroups is 1.5 per CU, i.e. two rounds for 1.5 rounds of work.
         // Model: the busiest CU runs ceil(workgroups / 256) of them, each costing its rows; the 128-row form (two co-resident workgroups
-        // per CU) wins when that product is smaller (US_TM_MODEL=0: the old rule).  The tile never changes a result: every output element
-        // sums its K chunks in the same order in both forms.
-        static int tm_model = -1;
-        if (tm_model < 0) { const char* e = getenv("US_TM_MODEL"); tm_model = e ? atoi(e) : 15; }
+        // per CU) wins when that product is smaller by a margin.  The tile never changes a result: every output element sums its K chunks
+        // in the same order in both forms.
         const long long per256 = (long long)((a.Hs * a.Ws + 255) / 256) * nt * a.B;
         const long long per128 = (long long)((a.Hs * a.Ws + 127) / 128) * nt * a.B;
         const long long cost256 = ((per256 + 255) / 256) * 256, cost128 = ((per128 + 255) / 256) * 128;
-        // (tm_model = percent by which the 128-row form must undercut the 256-row one: the two-buffer four-wave kernel runs its rows
+        // (kTmModelMargin = percent by which the 128-row form must undercut the 256-row one: the two-buffer four-wave kernel runs its rows
         // slower than the three-buffer eight-wave one)
-        if (tm_model) tm = cost128 * (100 + tm_model) < cost256 * 100 ? 128 : 256;
-        else tm = per256 >= 384 ? 256 : 128;
+        constexpr int kTmModelMargin = 15;
+        tm = cost128 * (100 + kTmModelMargin) < cost256 * 100 ? 128 : 256;
         // ... and 256 rows x 64 columns: half the work per workgroup at the eight-wave kernel's rate per row (each wave keeps one 32-column
         // block: 12 instead of 24 MFMAs per chunk against the same A fragments).  B = 1 level-3 launch, 768 of them: three rounds of half
         // work instead of two of full -- measured 94.5 -> 89.5 us, a third of what the model promises: the half-width kernel runs its work ~15 %
-        // slower.  US_TN64=0 switches it off; the margin (percent) covers the thinner MFMA : LDS-read ratio.
+        // slower.  The margin (percent) covers the thinner MFMA : LDS-read ratio.
         // short K (a level-1 / level-2 frequency of the 4-wide forms is 4 ... 16 chunks): the eight-wave kernel is one workgroup per CU and cannot
         // hide a workgroup's prologue and epilogue behind another's loop; the 128-row kernel has two per CU.  K <= 512: B = 1 +0.6 %, B = 8
-        // +1.3 % (3,792 -> 3,841 frames/s); 64-row tiles no better.  US_WINO_TM_SHORTK = rows where K <= US_WINO_SHORTK (0: the model above).
-        static int tm_short = -1, k_short = -1;
-        if (tm_short < 0) { const char* e = getenv("US_WINO_TM_SHORTK"); tm_short = e ? atoi(e) : 128; }
-        if (k_short < 0) { const char* e = getenv("US_WINO_SHORTK"); k_short = e ? atoi(e) : 512; }
-        if (tm_short > 0 && a.Cin <= k_short) tm = tm_short;
-        static int tn64 = -1;
-        if (tn64 < 0) { const char* e = getenv("US_TN64"); tn64 = e ? atoi(e) : 25; }
-        if (tn64 > 0 && a.Cout % 64 == 0 && a.Cin >= 1024 && a.Hs * a.Ws > 128) {      // (K = 256 ... 512: twice the prologues and epilogues per unit of work cost more than the rounds saved: measured 34 -> 38 us, 102 -> 120 us)
+        // +1.3 % (3,792 -> 3,841 frames/s); 64-row tiles no better.
+        if (a.Cin <= 512) tm = 128;
+        constexpr int kTn64Margin = 25;
+        if (a.Cout % 64 == 0 && a.Cin >= 1024 && a.Hs * a.Ws > 128) {      // (K = 256 ... 512: twice the prologues and epilogues per unit of work cost more than the rounds saved: measured 34 -> 38 us, 102 -> 120 us)
           const long long per64 = (long long)((a.Hs * a.Ws + 255) / 256) * ((a.Cout + 63) / 64) * a.B;
           const long long cost64 = ((per64 + 255) / 256) * 128;
           // against the 256 x 128 form (the 128-row one measured no better than it wherever the model preferred it)
-          if (cost64 * (100 + tn64) < cost256 * 100) { tm = 256; tn = 64; nt = (a.Cout + 63) / 64; }
+          if (cost64 * (100 + kTn64Margin) < cost256 * 100) { tm = 256; tn = 64; nt = (a.Cout + 63) / 64; }
         }
       } else {
         // direct convolutions (A split in the kernel): three co-resident 64-row workgroups per CU beat the larger tiles at every
         // U-Net shape (tools/conv_bench: 272 vs 251 vs 210 TFLOP/s on the level-0 3x3).  Never a function of the batch, so that
         // the split-K slicing below, hence the summation order, does not depend on what an utterance is batched with.
         tm = 64;
-        static int tm_1x1 = -1, tm_taps = -1;        // experiment knobs: US_TM_1X1 / US_TM_TAPS = 64 | 128 | 256
-        if (tm_1x1 < 0) { const char* e = getenv("US_TM_1X1"); tm_1x1 = e ? atoi(e) : 0; }
-        if (tm_taps < 0) { const char* e = getenv("US_TM_TAPS"); tm_taps = e ? atoi(e) : 0; }
-        if (a.ntaps == 1 && a.nphase <= 1 && tm_1x1 > 0 && (long long)a.Hs * a.Ws >= 4 * tm_1x1) tm = tm_1x1;
-        if ((a.ntaps > 1 || a.nphase > 1) && tm_taps > 0 && (long long)a.Hs * a.Ws >= 4 * tm_taps) tm = tm_taps;
       }
     }
   }
@@ -1106,52 +956,33 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   if (a.attn_part_ctx) {
     // to_qkv with the attention reduction in the epilogue: three 128-column tiles, 64-row tiles (one chunk of partials each), one pass
     if (!((a.Cout == 3 * kHidden && a.attn_q_cols == kHidden) || (a.Cout == 2 * kHidden && a.attn_q_cols == 0)) || a.ntaps != 1 || a.istride != 1 || a.ostep != 1 || a.wino_out || a.nphase > 1 || a.bias || a.add || a.alpha ||
-        a.stats || a.f16 == 1 || !a.attn_part_m || !a.attn_part_s || (a.attn_rows != 0 && a.attn_rows != 64 && a.attn_rows != 128) ||
-        a.attn_nchunks != (a.Hs * a.Ws + (a.attn_rows ? a.attn_rows : 64) - 1) / (a.attn_rows ? a.attn_rows : 64))
+        a.stats || a.f16 == 1 || !a.attn_part_m || !a.attn_part_s || a.attn_nchunks != (a.Hs * a.Ws + 63) / 64)
       return hipErrorInvalidValue;
-    tm = a.attn_rows ? a.attn_rows : 64;
+    tm = 64;
     a.splitk_ws = nullptr;
   }
   if (a.nphase > 1) {
     if (a.nphase != 4 || a.ostep != 2 || a.wino_out) return hipErrorInvalidValue;
     a.splitk_ws = nullptr;            // the merged grid is 4x larger already; slabs are per (item, single phase)
   }
-  if (tm == 0) {
-    const long long wgs128 = (long long)((Ms + 127) / 128) * nt * a.B;
-    tm = wgs128 < g_tm64_threshold ? 64 : 128;
-  }
+  // measured on MI355X (tools/conv_bench, bench.py): three co-resident 64-row workgroups per CU (136 VGPRs, 48 KB LDS)
+  // hide the per-chunk barrier better than two 128-row ones at every U-Net shape and batch measured (B'=3 and 24)
+  if (tm == 0) tm = 64;
   // split-K for launches that cannot fill the chip (small images / short utterances / fine-tune crops): slice the
   // taps*Cin/BK chunks over `ksplit` workgroups per tile, partial slabs in `splitk_ws`, summed by splitk_finish_kernel
   const int mt = (Ms + tm - 1) / tm;
   const long long tiles = (long long)mt * nt * a.B;
   const int S_all = a.ntaps * (a.Cin / a.bk);
   a.ksplit = 1;
-  if (g_splitk < 0) {
-    const char* e = getenv("US_SPLITK");
-    g_splitk = e ? atoi(e) : 1;
-  }
   // The slice count depends on the per-item tile count only (never on the batch), so an utterance's result does not depend
   // on what it is batched or sharded with (tests: ...shard_independence).
   const long long tiles_item = a.splitk_by_batch ? tiles : (long long)mt * nt;
-  if (g_splitk && a.splitk_ws && tiles_item < 128 && S_all >= 8 && a.Cout % 4 == 0 && a.out_ld % 4 == 0 && (!a.add || a.add_ld % 4 == 0)) {
+  if (a.splitk_ws && tiles_item < 128 && S_all >= 8 && a.Cout % 4 == 0 && a.out_ld % 4 == 0 && (!a.add || a.add_ld % 4 == 0)) {
     long long k = (256 + tiles_item - 1) / tiles_item;      // aim at >= 256 workgroups per item
     if (k > S_all / 4) k = S_all / 4;                        // at least 4 chunks per slice
     if (k > 512 / tiles_item) k = 512 / tiles_item;          // bounds the slab: k * Ms * Cout <= 512 tiles = 4 Mi floats per item
     if (k > 32) k = 32;
     if (k >= 2 && k * (long long)a.B * Ms * a.Cout <= a.splitk_ws_floats) a.ksplit = (int)k;
-  }
-  if (a.splitk_raw) {
-    // Winograd-domain GEMMs of one fine-tune crop: 16 frequencies x (1 row tile x 8 column tiles) = 128 workgroups walking 32 chunks each
-    // (33 us, 26 such launches per iteration).  Slice K so that the launch is ~3 workgroups per CU; the output transform sums the slabs.
-    a.ksplit = 1;
-    if (g_splitk && a.splitk_ws && !a.wino_out && !a.out_split && !a.stats && !a.add && !a.bias && tiles < 384 && S_all >= 16) {
-      long long k = (768 + tiles - 1) / tiles;
-      if (k > S_all / 4) k = S_all / 4;
-      if (k > 8) k = 8;
-      while (k >= 2 && k * (long long)a.B * Ms * a.Cout > a.splitk_ws_floats) --k;
-      if (k >= 2) a.ksplit = (int)k;
-    }
-    if (a.ksplit_out) *a.ksplit_out = a.ksplit;
   }
   a.nt = nt;
   dim3 grid(mt * a.ksplit * nt, 1, a.B * (a.nphase > 1 ? a.nphase : 1));
@@ -1161,8 +992,7 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     else if (tm == 128) hipLaunchKernelGGL((conv_igemm_kernel<32, 64, false, true, 2, 2, true>), grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL((conv_igemm_kernel<32, 32, false, true, 2, 2, true>), grid, dim3(256), lds, s, a);
   } else if (a.f16) {
-    if (a.wino_out && !(a.debug & 128)) hipLaunchKernelGGL((conv_igemm_kernel<32, 32, true, true, 2, 3>), grid, dim3(256), lds_bytes(32, 64, 3), s, a);
-    else if (a.wino_out) hipLaunchKernelGGL((conv_igemm_kernel<32, 32, true, true>), grid, dim3(256), lds, s, a);
+    if (a.wino_out) hipLaunchKernelGGL((conv_igemm_kernel<32, 32, true, true, 2, 3>), grid, dim3(256), lds_bytes(32, 64, 3), s, a);
     else if (tm == 256 && tn == 64) hipLaunchKernelGGL((conv_igemm_kernel<32, 64, false, true, 4, 3, false, 1>), grid, dim3(512), lds_bytes(32, 256, 3, 64), s, a);
     else if (tm == 256) hipLaunchKernelGGL((conv_igemm_kernel<32, 64, false, true, 4, 3>), grid, dim3(512), lds_bytes(32, 256, 3), s, a);
     else if (tm == 128) hipLaunchKernelGGL((conv_igemm_kernel<32, 64, false, true>), grid, dim3(256), lds, s, a);
@@ -1180,7 +1010,7 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     hipLaunchKernelGGL((conv_igemm_kernel<16, 64, false>), grid, dim3(256), lds, s, a);
   else
     hipLaunchKernelGGL((conv_igemm_kernel<16, 32, false>), grid, dim3(256), lds, s, a);
-  if (a.ksplit > 1 && !a.splitk_raw) {
+  if (a.ksplit > 1) {
     long long total = (long long)Ms * (a.Cout / 4);
     int blocks = (int)((total + 1023) / 1024);
     if (blocks < 1) blocks = 1;

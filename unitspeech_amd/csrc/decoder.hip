@@ -30,7 +30,7 @@ struct DevBuf {
 
 enum class Kind { RAW, CONV_OIHW, CONVT_IOHW };
 
-constexpr int kWtotalMaxC = 256;
+constexpr int kWtotalMaxC = 128;      // attention with q folded away (attention()) where C <= this
 
 struct Slot {
   std::string key;
@@ -114,37 +114,20 @@ struct us_decoder {
   Slot *final_g, *final_b, *final_w1, *final_b1;
   Slot *text_uncon, *spk_uncon, *mlp0_w, *mlp0_b, *mlp2_w, *mlp2_b;
   int n_resnets = 0;
-  bool f16x3 = true;         // US_F16X3=0: every Winograd GEMM on the fp32 matrix instruction.  Default: those with 32-divisible
-  int f16x3_min_level = 0;   // channel counts at levels >= US_F16X3_MIN_LEVEL run as three fp16 MFMA products of split operands
-  bool f16x3_dgrad = true;   // US_F16X3_DGRAD=0: data gradients of the direct convolutions stay on fp32 MFMA
-  bool f16x3_direct = true;  // US_F16X3_DIRECT=0: direct convolutions (1x1, stride 2, transposed, non-Winograd 3x3) stay on fp32 MFMA
-  long long wino_fuse_min_wgs = 400;   // US_WINO_FUSE_MIN_WGS: fused output transform when the launch keeps this many workgroups
-  long long wino_fuse_min_wgs_small = 200;       // US_WINO_FUSE_MIN_WGS_SMALL: ... for matrices of at most
-  long long wino_fuse_small_kn = 512 * 256;      // US_WINO_FUSE_SMALL_KN elements per frequency
+  // Tuning switches, read from the environment by us_decoder_create only: each selects between two production forms that a test compares.
+  int wino_min_level = 1;   // ResnetBlock 3x3 convs at U-Net levels >= this run as Winograd F(2x2,3x3); US_WINO_MIN_LEVEL, 99 = off.  Level 0
+                            // runs direct since the f16x3 kernels: at 80 x T the 4x-expanded V costs more than 2.25x fewer MFMA FLOPs save
+  // F(4x4,3x3) / F(2x4,3x3) Winograd in inference, per U-Net level: 0 = F(2x2) (wino.hip), 44, 24 (wino4.hip); US_WINO4="l0,l1,l2,l3"
+  int wino4_level_form[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int wino_fuse = -1;        // US_WINO_FUSE: Winograd output transform inside the GEMM wherever legal (1), never (0), by launch size (-1, wino_conv)
   bool wino_fuse_gn = true;  // US_WINO_FUSE_GN=0: block1's gn_apply as its own pass
-  bool presplit = true;      // US_PRESPLIT=0: block1's GroupNorm output stays fp32 for the direct block2 convolution (split in the kernel)
-  bool attn_fuse = true;     // US_ATTN_FUSE=0: to_qkv writes q | k | v and attn_ctx_partial_kernel re-reads k, v (the training path's form)
-  bool xcd_z = true;         // US_XCD_Z=0: the Winograd-domain GEMMs dealt to the XCDs by tile only, not by whole frequencies (A/B)
+  int f16_tm = 0;            // US_F16_TM: rows per workgroup of the f16x3 Winograd-domain GEMMs (64, 128, 256; 0: the launcher's rule)
   // parameter-gradient chains of a backward pass on side streams (train_host.inc, BwdCtx); US_WGRAD_STREAM=0: everything on the caller's
   // (measured, fine-tune iteration / pre-training step: 1 side stream 10.29 ms / 61.5 ms, 2: 10.43 / 62.5, 3: 11.7 / 62.9)
   int wgrad_side_streams = 1;
   std::vector<hipStream_t> wgrad_streams;
   std::vector<hipEvent_t> wgrad_events;
-  // attention with q folded away, out = x + g (W_total x + b_o) with W_total = W_out blockdiag(ctx^T) W_q (attention()): bit l = U-Net level l
-  // (C <= kWtotalMaxC only: the projection's K grows from 128 to C); US_ATTN_WTOTAL
-  // (measured at B = 1: level 0 only +0.9 %; level 0 and the 128-channel up level +0.6 %; levels 0-1 incl. the 256-channel one +0.0 %)
-  int attn_wtotal_levels = 0x1;
-  int attn_wtotal_max_c = 128;       // US_ATTN_WTOTAL_MAXC (<= kWtotalMaxC)
-  int attn_chunk_rows = 64;          // US_ATTN_CHUNK: rows per chunk of the to_qkv epilogue's online-softmax partials (64 | 128 = its row tile)
-  bool fuse_final = true;    // US_FUSE_FINAL=0: the final Block's GroupNorm + Mish as its own launch before the 1x1 projection
-  bool wino_narrow = false; // US_WINO_NARROW=1: Winograd also for convolutions with cout <= dim below level 0 (add_resnet)
-  int wino_max_level = 99;  // US_WINO_MAX_LEVEL (experiment): levels beyond it run direct
-  int wino_min_level = 1;   // ResnetBlock 3x3 convs at U-Net levels >= this run as Winograd F(2x2,3x3); US_WINO_MIN_LEVEL, 99 = off.  Level 0
-                            // runs direct since the f16x3 kernels: at 80 x T the 4x-expanded V costs more than 2.25x fewer MFMA FLOPs save
-  // F(4x4,3x3) / F(2x4,3x3) Winograd in inference, per U-Net level: 0 = F(2x2) (wino.hip), 44, 24 (wino4.hip); US_WINO4="l0,l1,l2,l3"
-  int wino4_level_form[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool training = false;    // us_decoder_set_training
-  bool wino_splitk = false; // US_WINO_SPLITK=1: K-sliced Winograd-domain GEMMs in training passes (wino_conv)
   float* zeros = nullptr;   // zero page read by out-of-image convolution taps
   // f16x3 operand range (kernels.h): one device word that every split ORs into when it meets a value beyond the fp16 range, and a
   // pinned host word us_range_status copies it to.  `exact`: the handle was created with US_CREATE_EXACT_FP32 (no f16x3 anywhere).
@@ -252,8 +235,8 @@ struct us_decoder {
     // Winograd F(2x2,3x3) from US_WINO_MIN_LEVEL down -- except where the output is as narrow as level 0 (cout <= dim: the last up
     // level, 512 -> 128 and 128 -> 128 at 40 x T/2).  There the GEMMs have a single column tile, so nothing amortises the 4x-expanded V
     // (503 MB written and read for the 512-channel input at B' = 3) and the direct form is faster: measured 341 -> ~260 us and
-    // 95 -> ~75 us per convolution, transform included (US_WINO_NARROW=1 brings the Winograd form back).
-    if (level >= wino_min_level && level <= wino_max_level && (cout > cfg.dim || wino_narrow)) {
+    // 95 -> ~75 us per convolution, transform included.
+    if (level >= wino_min_level && cout > cfg.dim) {
       if (!r.first) r.c1.w->want_wino = true;
       r.c2.w->want_wino = true;
     }
@@ -429,7 +412,7 @@ void plan(us_decoder* h, Arena& A, int Bp, int T, Buffers& b, bool train = false
   b.splitk_floats = B * ((size_t)4 << 20);  // 4 Mi floats per item: the conv launcher's bound on its split-K slabs
   b.splitk = A.alloc<float>(b.splitk_floats);
   b.weff = A.alloc<float>(B * (size_t)max_c * kHidden);
-  if (!train && h->attn_wtotal_levels) b.wtotal = A.alloc<float>(B * (size_t)kWtotalMaxC * kWtotalMaxC);
+  if (!train) b.wtotal = A.alloc<float>(B * (size_t)kWtotalMaxC * kWtotalMaxC);
   // Winograd scratch, sized from the convolutions that use it: V holds the conv's input channels and M its output channels;
   // the data gradient (training plans) swaps the two
   size_t wv = 0, wm = 0;
@@ -554,7 +537,8 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
     a.set_tap(0, 0, 0, 0);
     a.out = b.wino_m; a.out_ld = N;
     a.B = nf; a.Hin = a.Hs = a.Hout = e.Bp * t4h; a.Wout = t4w; a.ostep = 1;
-    a.xcd_z = e.h->xcd_z && K >= 256 && N >= 256;
+    a.tm = e.h->f16_tm;
+    a.xcd_z = K >= 256 && N >= 256;
     err4 = run_conv(e, a);
     if (err4 != hipSuccess) return err4;
     return launch_wino4_output(form4, b.wino_m, ep.bias, out, out_ld, ep.stats, e.Bp, H, W, N, e.s);
@@ -584,8 +568,9 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
   // A fused workgroup streams its column tile's weights for all 16 frequencies (16 * K * 128 values) for only 64 tiles of rows, four
   // times the weight traffic of the separate form's 256-row tiles: with small matrices (K * N <= 512 * 256) it already pays at about
   // one workgroup per CU, with the 1024-wide ones only when the launch is several waves deep.
-  const long long min_wgs = (long long)K * N <= e.h->wino_fuse_small_kn ? e.h->wino_fuse_min_wgs_small : e.h->wino_fuse_min_wgs;
-  if (fused_wgs >= min_wgs) {
+  constexpr long long kFuseMinWgs = 400, kFuseMinWgsSmall = 200, kFuseSmallKN = 512 * 256;
+  const long long min_wgs = (long long)K * N <= kFuseSmallKN ? kFuseMinWgsSmall : kFuseMinWgs;
+  if (e.h->wino_fuse == 1 || (e.h->wino_fuse < 0 && fused_wgs >= min_wgs)) {
     a.wino_out = 1;
     a.B = e.Bp; a.Hout = H; a.Wout = W; a.ostep = 2;
     a.out = out; a.out_ld = out_ld;
@@ -609,24 +594,18 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
   // GEMM runs over all Bp * th * tw rows at once (no partial tile per item: a level-3 item has only 320 rows)
   a.out = b.wino_m; a.out_ld = N;
   a.B = 16; a.Hin = a.Hs = a.Hout = e.Bp * th; a.Wout = tw; a.ostep = 1;
+  if (f16) a.tm = e.h->f16_tm;
   // whole frequencies per XCD pay where a frequency's workgroups share operand tiles (nt > 1 column tiles re-reading A, K long enough
   // for the shared reads to matter): with 128 input or output channels the same placement measured 2-20 % SLOWER
-  a.xcd_z = e.h->xcd_z && K >= 256 && N >= 256;
-  // training passes (one crop: a frequency's GEMM is a single row tile): K may be sliced, the output transform sums the slabs (ConvArgs::splitk_raw)
-  int ks = 1;
-  // (measured NEGATIVE at one crop: fine-tune iteration 8.57 -> 9.05 ms -- the chains these launches sit on are paced by launch latency, and
-  // 4-6x the workgroups take the chip from the weight-gradient stream beside them -- so it is off unless US_WINO_SPLITK=1)
-  if (e.splitk_by_batch && e.h->wino_splitk && f16) {
-    a.splitk_raw = 1;
-    a.splitk_ws = b.splitk; a.splitk_ws_floats = (long long)b.splitk_floats;
-    a.ksplit_out = &ks;
-  }
+  a.xcd_z = K >= 256 && N >= 256;
+  // (training passes: K-sliced GEMMs whose slabs the output transform sums measured NEGATIVE at one crop, fine-tune iteration 8.57 ->
+  // 9.05 ms -- the chains these launches sit on are paced by launch latency, and 4-6x the workgroups take the chip from the
+  // weight-gradient stream beside them)
   err = run_conv(e, a);
   if (err != hipSuccess) return err;
   WinoOutExtra x{};
   x.add = ep.add; x.add_ld = ep.add_ld;
   if (ep.mask_out) { x.mask = e.mask; x.mask_ld = e.T; x.mask_step = 1 << level; x.mask_bmod = e.Bm; }
-  if (ks > 1) return launch_wino_output(b.splitk, ep.bias, out, out_ld, ep.stats, e.Bp, H, W, N, e.s, &x, ks, 16LL * e.Bp * th * tw * N);
   return launch_wino_output(b.wino_m, ep.bias, out, out_ld, ep.stats, e.Bp, H, W, N, e.s, &x);
 }
 
@@ -750,7 +729,7 @@ hipError_t gn_apply(EvalCtx& e, const float* y, int level, int C, const double* 
 // two-plane fp16 form and the convolution skips its in-kernel split (-15 % on the level-0 3x3 in tools/conv_bench).  `tmp`: a buffer
 // of the activation's size other than the GroupNorm's input (the planes of a channel quad overlap its neighbour's fp32 input).
 inline bool direct_presplit(EvalCtx& e, const ConvW& w, int C, int tmp_ld) {
-  return e.h->presplit && !(w.w->wino.p && e.b->wino_v) && w.w->direct_f16 && C % 8 == 0 && tmp_ld == C;
+  return !(w.w->wino.p && e.b->wino_v) && w.w->direct_f16 && C % 8 == 0 && tmp_ld == C;
 }
 
 // ResnetBlock (unitspeech/unitspeech.py:58-75).  `in` must already be masked.  mask_out: the result is only consumed
@@ -813,14 +792,13 @@ hipError_t resnet(EvalCtx& e, const ResnetW& r, const float* in, int in_ld, floa
 // r2 of a level takes its input (r1's output) a second time in the two-plane form when its block1 convolution is a direct f16x3 one and
 // it has no res_conv (the identity residual reads the fp32 copy); the copy lives in r2's own output buffer, which is free until its end
 inline bool next_takes_split_copy(EvalCtx& e, const ResnetW& r2) {
-  static const bool on = [] { const char* p = getenv("US_SPLIT_COPY"); return !p || atoi(p) != 0; }();
-  return on && e.h->presplit && e.h->f16x3 && e.h->f16x3_direct && !r2.has_res && !r2.first && direct_presplit(e, r2.c1, r2.c1.cin, r2.c1.cin) &&
+  return !e.h->exact && !r2.has_res && !r2.first && direct_presplit(e, r2.c1, r2.c1.cin, r2.c1.cin) &&
          r2.c1.cin == r2.cout;
 }
 
 // a ResnetBlock whose two readers of its input (block1's 3x3, res_conv) are both direct f16x3 convolutions can take that input pre-split
 inline bool resnet_takes_split(EvalCtx& e, const ResnetW& r) {
-  return e.h->presplit && !r.first && r.has_res && !(r.c1.w->wino.p && e.b->wino_v) && r.c1.w->direct_f16 && r.res.w->direct_f16;
+  return !r.first && r.has_res && !(r.c1.w->wino.p && e.b->wino_v) && r.c1.w->direct_f16 && r.res.w->direct_f16;
 }
 
 // Residual(Rezero(LinearAttention)) (unitspeech/unitspeech.py:78-106)
@@ -832,17 +810,15 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
   const int nch = attn_nchunks(n);
   float* qkv = b.QKV[l];
   int q_ld = 3 * kHidden;
-  bool q_split = false;
   int nparts = nch;
-  if (e.h->attn_fuse && at.qkv.w->qkv_rows.p && at.qkv.w->q_raw.p && b.wtotal && ((e.h->attn_wtotal_levels >> l) & 1) && at.dim <= e.h->attn_wtotal_max_c &&
-      at.dim % 32 == 0) {
+  // (measured at B = 1: level 0 only +0.9 %; level 0 and the 128-channel up level +0.6 %; levels 0-1 incl. the 256-channel one +0.0 %)
+  if (at.qkv.w->qkv_rows.p && at.qkv.w->q_raw.p && b.wtotal && l == 0 && at.dim <= kWtotalMaxC && at.dim % 32 == 0) {
     // q folded away: to_qkv computes k | v only, for the n-reduction in its epilogue, and stores nothing; then
     // out = x + g (W_total x + b_o), W_total[b] = W_out blockdiag(ctx[b]^T) W_q: a C x C projection of x per item instead of q = W_q x written
     // ([n][128]), read back and projected with K = 128 (a third less to_qkv work and 2 * n * 128 floats less traffic; worth it where C <= 256)
     const int H = e.h->cfg.n_feats >> l, W = e.T >> l;
-    const int nch64 = (n + e.h->attn_chunk_rows - 1) / e.h->attn_chunk_rows;
+    const int nch64 = (n + 63) / 64;
     ConvArgs a = base_args(e, at.qkv, in, in_ld, H, W, qkv, kHidden, H, W);
-    a.attn_rows = e.h->attn_chunk_rows;
     a.Cout = 2 * kHidden;
     a.wt_rows = 3 * kHidden;
     // rows kHidden.. of every K-chunk of the qkv_src_row-ordered pack (per head k_h | v_h)
@@ -852,7 +828,7 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
     a.attn_part_ctx = b.part_ctx; a.attn_part_m = b.part_m; a.attn_part_s = b.part_s; a.attn_nchunks = nch64;
     a.attn_q_cols = 0;
     CK(run_conv(e, a));
-    const bool f16 = e.h->f16x3 && e.h->f16x3_direct;
+    const bool f16 = !e.h->exact;
     CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nch64, b.ctx, b.colM, b.colS, b.ctx_split, at.out_w->buf.p, nullptr, at.dim,
                          pick_bk(kHidden), f16, e.s));
     const int bkc = pick_bk(at.dim);
@@ -865,23 +841,18 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
     return conv1x1(e, tot, in, in_ld, l, true, out, out_ld, in, in_ld, at.g->buf.p, b.wtotal, (long long)at.dim * at.dim, at.out_b->buf.p,
                    false, out_split);
   }
-  if (e.h->attn_fuse && at.qkv.w->qkv_rows.p) {
+  if (at.qkv.w->qkv_rows.p) {
     // to_qkv with the n-reduction in its epilogue: only q is written ([n][128]); chunks of 64 rows (ConvArgs::attn_part_ctx)
     const int H = e.h->cfg.n_feats >> l, W = e.T >> l;
-    const int nch64 = (n + e.h->attn_chunk_rows - 1) / e.h->attn_chunk_rows;
+    const int nch64 = (n + 63) / 64;
     q_ld = kHidden;
     ConvArgs a = base_args(e, at.qkv, in, in_ld, H, W, qkv, q_ld, H, W);
-    a.attn_rows = e.h->attn_chunk_rows;
     a.wt = at.qkv.w->qkv_rows.p;
     a.ntaps = 1;
     a.set_tap(0, 0, 0, 0);
     a.attn_part_ctx = b.part_ctx; a.attn_part_m = b.part_m; a.attn_part_s = b.part_s; a.attn_nchunks = nch64;
     a.attn_q_cols = kHidden;
-    // q has one reader, the folded to_out convolution below: where that runs as f16x3 it takes q pre-split
-    static int q_split_env = -1;                     // US_Q_SPLIT=0: q stays fp32 (A/B)
-    if (q_split_env < 0) { const char* ev = getenv("US_Q_SPLIT"); q_split_env = ev ? atoi(ev) : 0; }      // measured: -0.4 % (K = 128: not split-bound)
-    q_split = q_split_env && e.h->presplit && e.h->f16x3 && e.h->f16x3_direct && a.f16 == 2;
-    a.out_split = q_split ? 1 : 0;
+    // (q stays fp32: storing it pre-split for the folded to_out convolution below measured -0.4 %, K = 128 is not split-bound)
     CK(run_conv(e, a));
     nparts = nch64;
   } else {
@@ -889,7 +860,7 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
     CK(launch_attn_ctx_partial(qkv, e.Bp, n, b.part_ctx, b.part_m, b.part_s, nch, e.s));
   }
   const int bk = pick_bk(kHidden);
-  const bool f16 = e.h->f16x3 && e.h->f16x3_direct;
+  const bool f16 = !e.h->exact;
   // chunk partials -> ctx (+ the softmax statistics) -> W_eff = W_out blockdiag(ctx^T), two launches
   CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nparts, b.ctx, b.colM, b.colS, b.ctx_split, at.out_w->buf.p, b.weff, at.dim, bk,
                        f16, e.s));
@@ -900,7 +871,7 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
   eff.w = &tmp; eff.b = nullptr;
   // every consumer of an attention output masks it (Downsample / Upsample input, skip concat, mid blocks)
   return conv1x1(e, eff, qkv, q_ld, l, true, out, out_ld, in, in_ld, at.g->buf.p, b.weff, (long long)at.dim * kHidden,
-                 at.out_b->buf.p, q_split, out_split);
+                 at.out_b->buf.p, false, out_split);
 }
 
 int upload_bytes(us_decoder* h, const void* src, size_t nbytes, void* dev, hipStream_t st);
@@ -994,7 +965,7 @@ hipError_t estimator_eval_impl(EvalCtx& e, const float* x, int Bx, const float* 
   //   fin_split     the last Upsample's output: its one reader is the final Block's convolution.
   std::vector<char> hid_split(L, 0), up_split(L, 0);
   bool fin_split = false;
-  if (h->presplit && h->f16x3 && h->f16x3_direct && h->attn_fuse) {
+  if (!h->exact) {
     for (int l = 0; l < L; ++l) {
       auto& d = h->downs[l];
       if (!d.has_ds || !d.ds.conv.w->direct_f16 || h->C[l] % 8 != 0) continue;
@@ -1083,13 +1054,9 @@ hipError_t estimator_eval_impl(EvalCtx& e, const float* x, int Bx, const float* 
   double* stf = next_stats(e);
   const int c0 = h->C[0];
   CK(conv3x3(e, h->final_conv3, fin, fin_ld, 0, b.S1[0], c0, stf, fin_split));
-  if (h->fuse_final) {      // GroupNorm + Mish + mask inside the 1x1 projection: the normalised tensor is never stored
-    CK(launch_final_conv(b.S1[0], c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s, stf,
-                         h->final_g->buf.p, h->final_b->buf.p));
-    return hipSuccess;
-  }
-  CK(gn_apply(e, b.S1[0], 0, c0, stf, h->final_g, h->final_b, nullptr, nullptr, 0, false, false, b.S1[0], c0));
-  CK(launch_final_conv(b.S1[0], c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s));
+  // GroupNorm + Mish + mask inside the 1x1 projection: the normalised tensor is never stored
+  CK(launch_final_conv(b.S1[0], c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s, stf,
+                       h->final_g->buf.p, h->final_b->buf.p));
   return hipSuccess;
 }
 
@@ -1254,9 +1221,13 @@ int us_decoder_create_ex(us_handle* out, const us_config* cfg, unsigned flags) {
   if (hipGetDevice(&h->device) != hipSuccess) { g_last_error = "no HIP device"; return US_EHIP; }
   hipError_t e = conv_igemm_init();
   if (e != hipSuccess) { g_last_error = std::string("conv_igemm_init: ") + hipGetErrorString(e); return US_EHIP; }
+  h->exact = (flags & US_CREATE_EXACT_FP32) != 0;
+  // the environment switches (us_decoder: each selects between two production forms that a test compares)
   if (const char* wl = getenv("US_WINO_MIN_LEVEL")) h->wino_min_level = atoi(wl);
-  if (const char* wl = getenv("US_WINO_MAX_LEVEL")) h->wino_max_level = atoi(wl);
-  if (const char* ws = getenv("US_WINO_SPLITK")) h->wino_splitk = atoi(ws) != 0;
+  if (const char* wf = getenv("US_WINO_FUSE")) h->wino_fuse = atoi(wf) != 0 ? 1 : 0;
+  if (const char* wf = getenv("US_WINO_FUSE_GN")) h->wino_fuse_gn = atoi(wf) != 0;
+  if (const char* wt = getenv("US_F16_TM")) h->f16_tm = atoi(wt) == 64 || atoi(wt) == 128 || atoi(wt) == 256 ? atoi(wt) : 0;
+  if (const char* ws = getenv("US_WGRAD_STREAM")) h->wgrad_side_streams = atoi(ws) < 0 ? 0 : (atoi(ws) > Tape::kSideMax ? Tape::kSideMax : atoi(ws));
   {
     // per-level 4-wide Winograd form of the inference path (wino4.hip), "l0,l1,l2,l3": 0 = F(2x2,3x3), 44 = F(4x4,3x3), 24 = F(2x4,3x3)
     const char* w4 = getenv("US_WINO4");
@@ -1270,28 +1241,9 @@ int us_decoder_create_ex(us_handle* out, const us_config* cfg, unsigned flags) {
       if (comma == std::string::npos) break;
       pos = comma + 1;
     }
-    if (flags & US_CREATE_EXACT_FP32)
+    if (h->exact)
       for (int l = 0; l < 8; ++l) h->wino4_level_form[l] = 0;
   }
-  if (const char* wl = getenv("US_WINO_NARROW")) h->wino_narrow = atoi(wl) != 0;
-  if (const char* wf = getenv("US_WINO_FUSE_MIN_WGS")) h->wino_fuse_min_wgs = atoll(wf);
-  if (const char* wf = getenv("US_WINO_FUSE_MIN_WGS_SMALL")) h->wino_fuse_min_wgs_small = atoll(wf);
-  if (const char* wf = getenv("US_WINO_FUSE_SMALL_KN")) h->wino_fuse_small_kn = atoll(wf);
-  if (const char* wf = getenv("US_F16X3")) h->f16x3 = atoi(wf) != 0;
-  if (const char* wf = getenv("US_F16X3_MIN_LEVEL")) h->f16x3_min_level = atoi(wf);
-  if (const char* wf = getenv("US_F16X3_DIRECT")) h->f16x3_direct = atoi(wf) != 0;
-  if (const char* wf = getenv("US_F16X3_DGRAD")) h->f16x3_dgrad = atoi(wf) != 0;
-  if (const char* wf = getenv("US_WINO_FUSE_GN")) h->wino_fuse_gn = atoi(wf) != 0;
-  if (const char* wf = getenv("US_XCD_Z")) h->xcd_z = atoi(wf) != 0;
-  if (const char* wf = getenv("US_PRESPLIT")) h->presplit = atoi(wf) != 0;
-  if (const char* wf = getenv("US_ATTN_FUSE")) h->attn_fuse = atoi(wf) != 0;
-  if (const char* ff = getenv("US_FUSE_FINAL")) h->fuse_final = atoi(ff) != 0;
-  if (const char* aw = getenv("US_ATTN_WTOTAL")) h->attn_wtotal_levels = atoi(aw);
-  if (const char* ac = getenv("US_ATTN_CHUNK")) h->attn_chunk_rows = atoi(ac) == 128 ? 128 : 64;
-  if (const char* aw = getenv("US_ATTN_WTOTAL_MAXC")) h->attn_wtotal_max_c = atoi(aw) > kWtotalMaxC ? kWtotalMaxC : atoi(aw);
-  if (const char* ws = getenv("US_WGRAD_STREAM")) h->wgrad_side_streams = atoi(ws) < 0 ? 0 : (atoi(ws) > Tape::kSideMax ? Tape::kSideMax : atoi(ws));
-  if (flags & US_CREATE_EXACT_FP32) h->f16x3 = false;
-  h->exact = !h->f16x3;
   h->build();
   if (hipMalloc(reinterpret_cast<void**>(&h->range_flag), 256) != hipSuccess || hipMemset(h->range_flag, 0, 256) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&h->range_host), 256) != hipSuccess ||
@@ -1331,24 +1283,24 @@ int us_decoder_create_ex(us_handle* out, const us_config* cfg, unsigned flags) {
       ok = hipMalloc(reinterpret_cast<void**>(&s->wino.p), s->wino.n * sizeof(float)) == hipSuccess &&
            hipMalloc(reinterpret_cast<void**>(&s->wino_dg.p), s->wino_dg.n * sizeof(float)) == hipSuccess;
     }
-    if (ok && s->dg.p && h->f16x3 && h->f16x3_direct && h->f16x3_dgrad) {
+    if (ok && s->dg.p && !h->exact) {
       const long long kk = s->kind == Kind::CONVT_IOHW ? s->shape[1] : s->shape[0];      // the data-gradient GEMM sums over the output channels
       s->dg_f16 = kk % 32 == 0;
     }
-    if (ok && !s->want_wino && s->kind != Kind::RAW && h->f16x3 && h->f16x3_direct) {
+    if (ok && !s->want_wino && s->kind != Kind::RAW && !h->exact) {
       const long long cin = s->kind == Kind::CONV_OIHW ? s->shape[1] : s->shape[0];
       s->direct_f16 = cin % 32 == 0;
     }
-    if (ok && s->want_wino && h->f16x3 && s->level >= h->f16x3_min_level) {
+    if (ok && s->want_wino && !h->exact) {
       // the forward GEMM sums over Cin, the data-gradient GEMM over Cout: each needs its K in whole 32-channel chunks
       s->wino_f16 = s->shape[1] % 32 == 0;
       s->wino_dg_f16 = s->shape[0] % 32 == 0;
     }
-    // (not for K = Cin < US_WINO4_MIN_K (256): a frequency's GEMM is then four chunks long and the 36 of them run at 100 TFLOP/s; the level-1
+    // (not for K = Cin < 256: a frequency's GEMM is then four chunks long and the 36 of them run at 100 TFLOP/s; the level-1
     // 128 -> 256 convolution took 91 + 25 + 50 us (GEMM, input, output transform) against 92 + 35 in the fused-output F(2x2) form)
-    static const int wino4_min_k = [] { const char* p = getenv("US_WINO4_MIN_K"); return p ? atoi(p) : 256; }();
+    constexpr int kWino4MinK = 256;
     if (ok && s->want_wino && s->wino_f16 && s->level >= 0 && s->level < 8 && wino4_form_ok(h->wino4_level_form[s->level]) && s->shape[0] % 8 == 0 &&
-        s->shape[1] >= wino4_min_k) {
+        s->shape[1] >= kWino4MinK) {
       s->wino4_form = h->wino4_level_form[s->level];
       s->wino4.n = (size_t)wino4_freqs(s->wino4_form) * s->shape[0] * s->shape[1];
       ok = hipMalloc(reinterpret_cast<void**>(&s->wino4.p), s->wino4.n * sizeof(float)) == hipSuccess;

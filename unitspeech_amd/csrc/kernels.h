@@ -118,21 +118,15 @@ struct ConvArgs {
   float* attn_part_ctx;  // [B][attn_nchunks][4][32][32]; non-null selects the mode (single pass, 64-row tiles)
   float* attn_part_m;    // [B][attn_nchunks][128]
   float* attn_part_s;    // [B][attn_nchunks][128]
-  int attn_nchunks;      // ceil(Hs * Ws / attn_rows)
-  int attn_rows;         // rows per chunk = rows per workgroup: 64 (0 means 64) or 128
+  int attn_nchunks;      // ceil(Hs * Ws / 64)
   int attn_q_cols;       // kHidden: column tile 0 is q and is stored; 0: the launch computes k | v only (Cout = 2 * kHidden, nothing stored:
                          // the caller folds W_q into the output projection, launch_attn_wtotal)
   int wt_rows;           // rows per K-chunk of the packed weight when the launch uses only Cout of them (0: Cout)
-  int splitk_raw;        // Winograd-domain GEMMs of a training pass (B = frequencies): the launcher may slice K and leave the raw slabs
-                         // [ks][B][Ms][Cout] in splitk_ws for the output transform to sum in slice order (no finish launch); the slice count
-  int* ksplit_out;       // ... is returned here (host pointer; 1 = `out` was written as usual)
   float* out2;           // optional second output, pixel-indexed like out (ld out2_ld): acc + bias BEFORE alpha / add / mask.  Training keeps
   int out2_ld;           // the Rezero branch's fn(x) this way: the gain's gradient is sum(grad_out * fn(x)) (unitspeech/unitspeech.py:36-43)
 #if defined(US_STAMP) || defined(US_LIFE)
   unsigned long long* stamp_out;   // diagnostic build only: per (workgroup, wave) {cycles at the vmcnt wait, at the barrier, in the body, steps}
 #endif
-  int debug;             // timing ablations for tools/conv_bench (0 in production): 1 = no DMA after the prologue,
-                         // 2 = no fragment reads after the first, 4 = no barriers
   unsigned long long dy_bits, dx_bits, wtap_bits;   // 4 bits per tap: dy+8, dx+8, weight tap index
   void set_tap(int i, int dy, int dx, int wtap) {
     dy_bits |= (unsigned long long)(dy + 8) << (4 * i);
@@ -303,11 +297,10 @@ struct WgradArgs {
   int chunk;             // output pixels per workgroup (multiple of 8)
   int vchunk;            // f16x3 kernel, shared gw (gw_bstride == 0): pixels per workgroup of the range CONCATENATED over the B items
                          // (0 = per-item chunks as above); set by launch_wgrad
-  int exact;             // 1: the exact-fp32 MFMA form (a handle created with US_CREATE_EXACT_FP32), whatever US_WGRAD_F16 says
+  int exact;             // 1: the exact-fp32 MFMA form (a handle created with US_CREATE_EXACT_FP32)
   const float* gy_amax;  // device float: max |gy| over (at least) the pixels and channels this launch reads, taken by launch_wgrad_amax
                          // into a zeroed word; the f16x3 form derives its exact power-of-two scale of the gradient operand from it
   int overwrite;         // 1: gw holds garbage; legal only when every element has exactly one writer (launch_wgrad_single_writer)
-  int div_addr;          // f16x3 kernel: 1 = recompute every DMA row's coordinates by division in every stage (the form until round 4; US_WGRAD_DIV=1)
   unsigned long long dy_bits, dx_bits, wtap_bits;
   void set_tap(int i, int dy, int dx, int wtap) {
     dy_bits |= (unsigned long long)(dy + 8) << (4 * i);
@@ -417,9 +410,8 @@ struct WinoOutExtra {
   const float* add; int add_ld;                          // pixel-indexed like out
   const float* mask; int mask_ld, mask_step, mask_bmod;  // column ox reads mask[ox * mask_step]
 };
-// nslab > 1: M is nslab split-K slabs of the product, slab_stride floats apart, summed here in slab order (ConvArgs::splitk_raw)
 hipError_t launch_wino_output(const float* M, const float* bias, float* out, int out_ld, double* stats, int B, int H, int W, int C,
-                              hipStream_t s, const WinoOutExtra* extra = nullptr, int nslab = 1, long long slab_stride = 0);
+                              hipStream_t s, const WinoOutExtra* extra = nullptr);
 // f16x3 form of launch_wino_pack_weight (bk = 32): dst holds two interleaved fp16 planes per value, same size and row structure
 hipError_t launch_wino_pack_weight_f16(const float* src, float* dst, int Cout, int Cin, hipStream_t s, bool dgrad = false);
 

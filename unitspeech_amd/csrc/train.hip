@@ -383,14 +383,10 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
     // this wave's pieces of stage st have landed; after the barrier everybody's have, and everybody has read the image of st-1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#ifndef US_WGRAD_ABL
-#define US_WGRAD_ABL 0      // timing ablations (wrong results): 1 conversion only at stage 0, 2 no fragment reads / MFMAs, 4 no loads in the loop
-#endif
-    if (st + 1 < nstage && !(US_WGRAD_ABL & 4)) dma(m_lo + (st + 1) * kWgKP16, (st + 1) & 1);      // its buffer was converted at stage st-1
-    if (!(US_WGRAD_ABL & 1) || st == 0) convert(st & 1);
+    if (st + 1 < nstage) dma(m_lo + (st + 1) * kWgKP16, (st + 1) & 1);      // its buffer was converted at stage st-1
+    convert(st & 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (US_WGRAD_ABL & 2) continue;
     half8_t ah[2], al[2], bh[2], bl[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -474,9 +470,7 @@ hipError_t launch_wgrad_amax(const float* g, int ld, long long rows, int C, floa
 }
 
 static bool wgrad_use_lds(const WgradArgs& a) {
-  static int use_lds = -1;
-  if (use_lds < 0) { const char* e = getenv("US_WGRAD_LDS"); use_lds = e ? atoi(e) : 1; }
-  return use_lds && a.Cout % 128 == 0 && a.Cin % 128 == 0 && a.gy_ld % 4 == 0 && a.x_ld % 4 == 0 &&
+  return a.Cout % 128 == 0 && a.Cin % 128 == 0 && a.gy_ld % 4 == 0 && a.x_ld % 4 == 0 &&
          (long long)a.Hout * a.Wout * a.gy_ld * 4 < (1LL << 31) && (long long)a.Hin * a.Win * a.x_ld * 4 < (1LL << 31);
 }
 
@@ -499,22 +493,16 @@ hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s) {
       attr_set = true;
     }
     dim3 g2(a.B * ((Ms + a.chunk - 1) / a.chunk), (a.Cout / 128) * (a.Cin / 128), a.ntaps);
-    static int use_f16 = -1;       // US_WGRAD_F16=0: the exact-fp32 MFMA form
-    if (use_f16 < 0) { const char* e = getenv("US_WGRAD_F16"); use_f16 = e ? atoi(e) : 1; }
-    if (use_f16 && !a.exact) {
+    if (!a.exact) {
       if (!a.gy_amax) return hipErrorInvalidValue;      // the f16x3 form needs the exact maximum of gy (launch_wgrad_amax)
       WgradArgs a2 = a;
-      static int div_addr = -1;      // US_WGRAD_DIV=1: the per-stage division form of the DMA addresses (A/B)
-      if (div_addr < 0) { const char* e = getenv("US_WGRAD_DIV"); div_addr = e ? atoi(e) : 0; }
-      a2.div_addr = div_addr;
-      static int target_wgs = -1;
-      if (target_wgs < 0) { const char* e = getenv("US_WGRAD_WGS"); target_wgs = e ? atoi(e) : 1536; }
+      constexpr long long kTargetWgs = 1536;
       const long long V = (long long)a.B * Ms;
       if (a.B > 1 && a.gw_bstride == 0 && !a.overwrite && (long long)a.B * a.Hout * a.Wout * a.gy_ld * 4 < (1LL << 31) &&
           (long long)a.B * a.Hin * a.Win * a.x_ld * 4 < (1LL << 31) && V < (1LL << 30)) {
         // one pixel range over all items, cut so that ~target workgroups result (never finer than the per-item rule would cut one item)
         const long long others = (long long)g2.y * g2.z;
-        long long nch = (target_wgs + others - 1) / others;
+        long long nch = (kTargetWgs + others - 1) / others;
         if (nch < 1) nch = 1;
         long long vc = (V + nch - 1) / nch;
         if (vc < a.chunk) vc = a.chunk;
@@ -531,7 +519,7 @@ hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s) {
         if (e != hipSuccess) return e;
         attr16_set = true;
       }
-      if (a2.Ws >= kWgKP16 && a2.Ws < 0x8000 && a2.Hs < 0x8000 && !a2.div_addr) hipLaunchKernelGGL(wgrad_f16_kernel<true>, g2, dim3(256), lds16, s, a2);
+      if (a2.Ws >= kWgKP16 && a2.Ws < 0x8000 && a2.Hs < 0x8000) hipLaunchKernelGGL(wgrad_f16_kernel<true>, g2, dim3(256), lds16, s, a2);
       else hipLaunchKernelGGL(wgrad_f16_kernel<false>, g2, dim3(256), lds16, s, a2);
       return hipGetLastError();
     }
@@ -592,8 +580,7 @@ __global__ __launch_bounds__(256) void unpack_wgrad_oihw_kernel(const float* __r
 }
 
 hipError_t launch_unpack_wgrad(const float* src, float* dst, int Cout, int Cin, int taps, bool oihw, hipStream_t s, const float* scale) {
-  static const bool generic = [] { const char* p = getenv("US_UNPACK_GENERIC"); return p && atoi(p) != 0; }();
-  if (!generic && oihw && (taps == 9 || taps == 1) && Cout <= 65535) {
+  if (oihw && (taps == 9 || taps == 1) && Cout <= 65535) {
     const dim3 grid((Cin + 255) / 256, Cout);
     const int vec_ok = (reinterpret_cast<uintptr_t>(dst) & 15) == 0 ? 1 : 0;
     if (taps == 9) hipLaunchKernelGGL(unpack_wgrad_oihw_kernel<9>, grid, dim3(256), 0, s, src, dst, Cout, Cin, scale, vec_ok);
@@ -867,13 +854,10 @@ hipError_t launch_gn_bwd(const GnBwdArgs& a, hipStream_t s) {
   // at 32 crops, 14,080 blocks of a level-0 launch queued 28,000 atomics per address.  Cap the blocks of a launch (all items) instead.
   // (measured: pre-training step at 32 crops 62.1 ms uncapped, 55.1-55.8 for caps of 256 ... 1,024 blocks; one crop: 10.28 -> 10.15 ms
   // per fine-tune iteration at 256)
-  static int target = -1;
-  if (target < 0) { const char* e = getenv("US_GN_BWD_BLOCKS"); target = e ? atoi(e) : 512; }
-  if (target > 0) {
-    if (blocks > target / 2) blocks = target / 2;
-    if ((long long)blocks * a.B > target) blocks = target / a.B;
-    if (blocks < 8) blocks = 8;
-  }
+  constexpr int kTarget = 512;
+  if (blocks > kTarget / 2) blocks = kTarget / 2;
+  if ((long long)blocks * a.B > kTarget) blocks = kTarget / a.B;
+  if (blocks < 8) blocks = 8;
   hipLaunchKernelGGL(gn_bwd_kernel<1>, dim3(blocks, a.B), dim3(256), 0, s, a);
   hipLaunchKernelGGL(gn_bwd_kernel<2>, dim3(blocks, a.B), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -918,57 +902,13 @@ hipError_t launch_attn_bwd_gctx(const float* qkv, const float* gO, int B, int n,
 
 // Per pixel and head: P = exp(k - M)/S;  t[d] = sum_e v[e]*gctx[d][e];  gk[d] = P[d]*(t[d] - cc[d]);  gv[e] = sum_d P[d]*gctx[d][e]
 // with cc[d] = sum_e ctx[d][e]*gctx[d][e].  Writes gk, gv into columns [128,384) of gqkv (ld 384).
-__global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
-                                                          const float* __restrict__ gctx, const float* __restrict__ colM,
-                                                          const float* __restrict__ colS, int n, float* __restrict__ gqkv) {
-  __shared__ float sg[kHeads][kDimHead][kDimHead + 1];    // gctx[h][d][e]
-  __shared__ float sgt[kHeads][kDimHead][kDimHead + 1];   // gctx[h][e][d]^T
-  __shared__ float scc[kHidden];
-  const int b = blockIdx.y;
-  const float* gc = gctx + (long long)b * kHeads * kDimHead * kDimHead;
-  const float* cx = ctx + (long long)b * kHeads * kDimHead * kDimHead;
-  for (int i = threadIdx.x; i < kHeads * kDimHead * kDimHead; i += 256) {
-    int h = i >> 10, d = (i >> 5) & 31, e = i & 31;
-    float v = gc[i];
-    sg[h][d][e] = v;
-    sgt[h][e][d] = v;
-  }
-  if (threadIdx.x < kHidden) {
-    const int h = threadIdx.x >> 5, d = threadIdx.x & 31;
-    float acc = 0.f;
-    for (int e = 0; e < kDimHead; ++e) acc += cx[(h * kDimHead + d) * kDimHead + e] * gc[(h * kDimHead + d) * kDimHead + e];
-    scc[threadIdx.x] = acc;
-  }
-  __syncthreads();
-  const int grp = threadIdx.x >> 5, l = threadIdx.x & 31;     // 8 groups of 32 lanes: 2 pixels x 4 heads per pass
-  const int h = grp & 3;
-  const float M = colM[(long long)b * kHidden + h * kDimHead + l], S = colS[(long long)b * kHidden + h * kDimHead + l];
-  const float cc = scc[h * kDimHead + l];
-  for (long long p = blockIdx.x * 2LL + (grp >> 2); p < n; p += (long long)gridDim.x * 2) {
-    const float* row = qkv + ((long long)b * n + p) * (3 * kHidden);
-    const float kk = row[kHidden + h * kDimHead + l];
-    const float vv = row[2 * kHidden + h * kDimHead + l];
-    const float P = expf(kk - M) / S;
-    float t = 0.f, gv = 0.f;
-#pragma unroll 8
-    for (int j = 0; j < kDimHead; ++j) {
-      float vj = __shfl(vv, j, 32), Pj = __shfl(P, j, 32);
-      t += vj * sg[h][l][j];          // d = l, e = j
-      gv += Pj * sgt[h][l][j];        // e = l, d = j : gctx[j][l]
-    }
-    float* orow = gqkv + ((long long)b * n + p) * (3 * kHidden);
-    orow[kHidden + h * kDimHead + l] = P * (t - cc);
-    orow[2 * kHidden + h * kDimHead + l] = gv;
-  }
-}
-
-// The same on the matrix cores.  Per head the two products are 32 x 32 GEMMs over a block of 32 pixels,
+// On the matrix cores: per head the two products are 32 x 32 GEMMs over a block of 32 pixels,
 //   T^T[d][p] = sum_e gctx[d][e] v[p][e],   GV^T[e][p] = sum_d gctx[d][e] P[p][d],
 // with the pixel on the MFMA's column index: a lane owns one pixel (it loads the pixel's 32 k and 32 v values of the head as eight 16-byte
 // vectors each and feeds v / P as the B operand straight from those registers, element 2j + hh at step j), gctx is the A operand (16 + 16
 // registers per lane, loaded once per workgroup: wave = head), and the results come back with the pixel on the lane and 16 of the head's
 // channels in the registers -- four 16-byte stores per output and pixel.  v_mfma_f32_32x32x2_f32: exact fp32 products and sums, as the
-// shuffle form's fmas (another order).  The shuffle form spent 32 x (2 shuffles + 2 LDS reads + 2 fmas) per pixel and head: 1.1 ms for the
+// earlier shuffle-and-fma form's (another order).  That form spent 32 x (2 shuffles + 2 LDS reads + 2 fmas) per pixel and head: 1.1 ms for the
 // level-0 attention of a pre-training batch.
 __global__ __launch_bounds__(256) void attn_bwd_kv_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                                                const float* __restrict__ gctx, const float* __restrict__ colM,
@@ -1049,17 +989,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_mfma_kernel(const float* __re
 
 hipError_t launch_attn_bwd_kv(const float* qkv, const float* ctx, const float* gctx, const float* colM, const float* colS, int B,
                               int n, float* gqkv, hipStream_t s) {
-  static const bool mfma = [] { const char* e = getenv("US_ATTN_BWD_KV_MFMA"); return !e || atoi(e) != 0; }();
-  if (mfma) {
-    int bm = (n + 31) / 32;                  // 32-pixel blocks of an item; a workgroup's prologue (gctx, cc) wants several of them at a batch
-    const int cap = 1024 / B < 8 ? 8 : 1024 / B;
-    if (bm > cap) bm = cap;
-    hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel, dim3(bm, B), dim3(256), 0, s, qkv, ctx, gctx, colM, colS, n, gqkv);
-    return hipGetLastError();
-  }
-  int bx = (n + 1) / 2;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(attn_bwd_kv_kernel, dim3(bx, B), dim3(256), 0, s, qkv, ctx, gctx, colM, colS, n, gqkv);
+  int bm = (n + 31) / 32;                  // 32-pixel blocks of an item; a workgroup's prologue (gctx, cc) wants several of them at a batch
+  const int cap = 1024 / B < 8 ? 8 : 1024 / B;
+  if (bm > cap) bm = cap;
+  hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel, dim3(bm, B), dim3(256), 0, s, qkv, ctx, gctx, colM, colS, n, gqkv);
   return hipGetLastError();
 }
 

@@ -203,8 +203,7 @@ inline hipError_t resnet_train(EvalCtx& e, Tape& tp, const ResnetW& r, const flo
   const int l = r.level;
   const float* tproj = tp.fb.tproj + tp.fb.tproj_off[r.index];
   CK(conv3x3(e, r.c1, in, in_ld, l, t.y1, r.cout, t.st1));
-  static const bool fuse_h1 = [] { const char* p = getenv("US_TRAIN_FUSE_H1"); return !p || atoi(p) != 0; }();
-  if (fuse_h1 && r.c2.w->wino.p && e.b->wino_v && gn_wino_input_supported(r.cout)) {
+  if (r.c2.w->wino.p && e.b->wino_v && gn_wino_input_supported(r.cout)) {
     // block1's GroupNorm + Mish + time embedding inside block2's Winograd input transform, as in inference (resnet()), with the
     // activation h1 stored from the same pass for the weight gradient: one launch and one read of y1 less per ResnetBlock
     WinoGnArgs g;
@@ -236,7 +235,7 @@ inline hipError_t attention_train(EvalCtx& e, Tape& tp, AttT& t, const float* in
   CK(conv1x1(e, at.qkv, in, in_ld, l, false, t.qkv, 3 * kHidden, nullptr, 0, nullptr, nullptr, 0, nullptr));
   CK(launch_attn_ctx_partial(t.qkv, e.Bp, n, b.part_ctx, b.part_m, b.part_s, nch, e.s));
   const int bk = pick_bk(kHidden);
-  const bool f16 = e.h->f16x3 && e.h->f16x3_direct;
+  const bool f16 = !e.h->exact;
   CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nch, t.ctx, t.colM, t.colS, b.ctx_split, at.out_w->buf.p, t.weff, at.dim, bk, f16,
                        e.s));
   ConvW eff;
@@ -407,15 +406,13 @@ struct BwdCtx {
 };
 
 // Pixels per wgrad workgroup: every workgroup ends with a 64x64 LDS reduction and 4,096 atomics, so the pixel range is
-// split only as far as needed to put ~`US_WGRAD_WGS` (default 1,536) workgroups on the chip: the 1,024-channel layers of a
+// split only as far as needed to put ~1,536 workgroups on the chip (768 at one crop): the 1,024-channel layers of a
 // 176-frame crop (220 pixels, 2,304 tile-taps) take their pixels in one piece, level 0 (14,080 pixels, 36 tile-taps) in ~40.
 inline int wgrad_chunk(int Ms, int cout, int cin, int ntaps, int B) {
   // one crop: 768 (the weight-gradient launches run beside the data-gradient chain on the second stream: 1,536 workgroups each took the
   // chip away from it -- fine-tune iteration 10.14 ms at 1,536, 9.78 at 768, 9.94 at 512, 10.65 at 256); a batch: 1,536 (pre-training
   // step at 32 crops: 56.0 ms at 1,536, 58.1 at 768, 60.1 at 512)
-  static int env_target = -2;
-  if (env_target == -2) { const char* e = getenv("US_WGRAD_WGS"); env_target = e ? atoi(e) : -1; }
-  const int target = env_target > 0 ? env_target : (B == 1 ? 768 : 1536);
+  const int target = B == 1 ? 768 : 1536;
   const long long tt = (long long)((cout + 63) / 64) * ((cin + 63) / 64) * ntaps * B;
   long long nch = (target + tt - 1) / tt;
   if (nch < 1) nch = 1;
@@ -576,10 +573,9 @@ inline hipError_t resnet_backward(BwdCtx& c, const ResT& t, const float* G, int 
   GY = tp.GY2[l];            // block1's gradient in its own buffer: block2's weight-gradient chain may still be reading the first
   // time-embedding projection: h1 = (a1*m + tproj)*m  ->  gtproj[b][c] = sum_p GH (already masked)
   // (no consumer before the MLP backward at the very end: on the second stream, GH marked busy until it has been read)
-  static const bool merge_chains = [] { const char* p = getenv("US_MERGE_CHAINS"); return !p || atoi(p) != 0; }();
   // (one crop only: the event calls weigh where launches are 5-30 us -- fine-tune iteration 9.32 -> 9.26 ms; at 32 crops starting the row
   // sums and block1's weight gradient later costs overlap: pre-training step 55.4 -> 56.2 ms)
-  const bool merged = merge_chains && !r.first && e.Bp == 1;      // the row sums wait for block1's chain below (GH stays untouched until the next block)
+  const bool merged = !r.first && e.Bp == 1;      // the row sums wait for block1's chain below (GH stays untouched until the next block)
   if (!merged) {
     CK(c.wgrad_fork());
     CK(launch_rowsum_per_item(GH, co, e.Bp, n, co, tp.gtproj + tp.fb.tproj_off[r.index], c.ws));
@@ -639,9 +635,8 @@ inline hipError_t attention_backward(BwdCtx& c, const AttT& t, const float* G, i
   const int n = H * W;
   const float* gptr = at.g->buf.p;
   // bias / Rezero gain / to_out weight: parameter gradients only (colsumG and M1 are scratch of this chain) -> second stream
-  static const bool side_attn = [] { const char* p = getenv("US_SIDE_ATTN"); return !p || atoi(p) != 0; }();
-  if (side_attn) CK(c.wgrad_fork());
-  hipStream_t as = side_attn ? c.ws : c.s;
+  CK(c.wgrad_fork());
+  hipStream_t as = c.ws;
   CK(zero_f32(c.colsumG(), (size_t)C, as));
   CK(launch_colsum(G, g_ld, (long long)e.Bp * n, C, nullptr, c.colsumG(), as));
   CK(launch_attn_bwd_bias(c.colsumG(), at.out_b->buf.p, gptr, C, at.out_b->grad, nullptr, as));
@@ -661,7 +656,7 @@ inline hipError_t attention_backward(BwdCtx& c, const AttT& t, const float* G, i
     CK(launch_wgrad(a, as));
   }
   CK(launch_attn_bwd_wout(c.M1(), t.ctx, at.out_w->buf.p, gptr, e.Bp, C, at.out_w->grad, nullptr, as));
-  if (side_attn) CK(c.wgrad_done(G));
+  CK(c.wgrad_done(G));
   // gO = g * G W_o   [n x 128]
   float* gO = tp.GO[l];
   CK(conv_dgrad_s1(c, at.out_w, kHidden, C, 1, G, g_ld, l, gO, kHidden, nullptr, 0, gptr, false, nullptr, 0, 0));
