@@ -289,6 +289,41 @@ int us_clip_adam_step(void* const* p, void* const* g, void* const* m, void* cons
                       const int32_t* blk_tensor, const int64_t* blk_off, int n_tensors, int n_blocks, double lr, double beta1,
                       double beta2, double eps, int step, float max_norm, float* partial, us_stream stream);
 
+/* ---- BigVGAN vocoder (unitspeech/vocoder/models.py:117-191, inference) -----------------------------------------------------
+ * mel [B][num_mels][T] -> waveform [B][1][T * prod(upsample_rates)], exact fp32.  Same conventions as the front-end handles: weights
+ * are loaded one state_dict tensor at a time from DEVICE memory, in the reference's key names of the remove_weight_norm() form
+ * (weight norm folded by the caller), the caller owns the activation scratch (us_vocoder_workspace_bytes),
+ * a forward call allocates nothing and only enqueues on `stream` (graph-capturable), and a call made while another device than the
+ * handle's is current is refused (US_EINVAL).  Activation1d's two 12-tap filters are the state_dict buffers
+ * `<act>.upsample.filter` / `<act>.downsample.lowpass.filter` [1, 1, 12], taken as given.  resblock "2" (AMPBlock2), up-samplers
+ * whose kernel is not a multiple of their rate (or with kernel - rate odd) and rates above 16 are not built: us_vocoder_create
+ * returns US_EINVAL for them. */
+typedef struct us_vocoder* us_vocoder_handle;
+enum { US_VOCODER_SNAKE = 0, US_VOCODER_SNAKEBETA = 1 };
+typedef struct us_vocoder_config {
+  int32_t num_mels;                      /* 80 */
+  int32_t upsample_initial_channel;      /* 1536 (22 kHz / 80-band), 512 (base) */
+  int32_t resblock;                      /* 1 = AMPBlock1 (2 is refused) */
+  int32_t n_up;                          /* len(upsample_rates), <= 8 */
+  int32_t upsample_rates[8];
+  int32_t upsample_kernel_sizes[8];
+  int32_t n_kernels;                     /* len(resblock_kernel_sizes), <= 4 */
+  int32_t resblock_kernel_sizes[4];      /* odd */
+  int32_t resblock_dilation_sizes[4][3];
+  int32_t activation;                    /* US_VOCODER_SNAKE / US_VOCODER_SNAKEBETA */
+  int32_t snake_logscale;                /* 1: alpha / beta are stored as logarithms */
+} us_vocoder_config;
+int us_vocoder_create(us_vocoder_handle* out, const us_vocoder_config* cfg);
+int us_vocoder_destroy(us_vocoder_handle h);
+int us_vocoder_load_weight(us_vocoder_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_vocoder_num_weights(us_vocoder_handle h);
+const char* us_vocoder_weight_key(us_vocoder_handle h, int i);
+const char* us_vocoder_last_error(us_vocoder_handle h);
+size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T);
+/* `BigVGAN.forward(mel)` (:169-191): mel [B][num_mels][T] -> wav [B][1][T * prod(upsample_rates)]. */
+int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
+                       us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

@@ -9,10 +9,14 @@ Two modes:
   --synthetic   no checkpoints / espeak / vocoder are needed: seeded synthetic decoder weights, a deterministic stand-in for
                 the text encoder + duration predictor (same call signatures), output = de-normalised mel saved as .npy.
                 This is the plumbing check of BASELINE.json configs[0] (10 diffusion steps, short text).
+  --hip_vocoder the BigVGAN vocoder on the HIP library (unitspeech_amd.vocoder): with --synthetic it vocodes the mel with seeded
+                weights (config: --vocoder_config, default the 22 kHz / 80-band large generator) and also writes the wav; in the
+                default mode it loads the reference's vocoder checkpoint and config instead of calling the reference's get_vocoder.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import sys
 import time
@@ -46,6 +50,9 @@ def main():
                          "torch's device generator: the stream the committed goldens were drawn from (tests/golden/tts_*.npz: 4242)")
     ap.add_argument("--spk_seed", type=int, default=None,
                     help="--synthetic: the speaker embedding of unitspeech_amd.synthetic_inputs(seed) instead of the --ID-keyed one")
+    ap.add_argument("--hip_vocoder", action="store_true", help="run BigVGAN on the HIP library (with --synthetic: seeded weights, writes the wav)")
+    ap.add_argument("--vocoder_config", type=str, default=None,
+                    help="--synthetic --hip_vocoder: generator config JSON (default: the 22 kHz / 80-band large BigVGAN)")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -79,6 +86,15 @@ def main():
         mel_min, mel_max = torch.tensor(-11.5, device=device), torch.tensor(2.0, device=device)
         phoneme, phoneme_lengths = text_to_ids(args.text, device)
         vocoder = None
+        if args.hip_vocoder:
+            from unitspeech_amd.vocoder import BIGVGAN_22KHZ_80BAND, BigVGAN, synthetic_bigvgan_state_dict
+            h = BIGVGAN_22KHZ_80BAND
+            if args.vocoder_config:
+                with open(args.vocoder_config) as f:
+                    h = json.load(f)
+            vocoder = BigVGAN(h)
+            vocoder.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_bigvgan_state_dict(h, 0).items()})
+            vocoder = vocoder.to(device).eval()
     else:
         if not args.reference_root:
             raise SystemExit("give --reference_root (reference checkout with its checkpoints) or use --synthetic")
@@ -87,6 +103,9 @@ def main():
         from unitspeech.text import cleaned_text_to_sequence, phonemize, symbols           # noqa: E402
         from unitspeech.util import get_phonemizer, get_vocoder, intersperse                # noqa: E402
         root = args.reference_root
+        if args.hip_vocoder:
+            from unitspeech_amd.vocoder import get_vocoder as get_hip_vocoder
+            get_vocoder = get_hip_vocoder                                                  # same arguments, util.py:174-181
         vocoder = get_vocoder(config_path=os.path.join(root, rcfg.vocoder.config_path), checkpoint=os.path.join(root, rcfg.vocoder.ckpt_path),
                               device=device)
         ck = os.path.join(root, rcfg.decoder.checkpoint if args.ID < 0 else f"{rcfg.finetune.finetuned_decoders_path}/{args.ID}.pt")
@@ -135,14 +154,14 @@ def main():
     frames = mel.shape[-1]
     print(f"decoded {frames} mel frames in {dt:.3f} s ({frames / dt:.1f} frames/s, RTF {dt / (frames * 256 / 22050):.3f}), "
           f"{args.diffusion_steps} diffusion steps, finite={bool(torch.isfinite(mel).all())}")
-    if vocoder is None:
+    if args.synthetic:
         out = os.path.splitext(args.generated_sample_path)[0] + ".mel.npy"
         np.save(out, mel.squeeze(0).cpu().numpy())
-        print(f"saved mel-spectrogram to {out} (no vocoder in --synthetic mode)")
-    else:
+        print(f"saved mel-spectrogram to {out}" + ("" if vocoder is not None else " (no vocoder in --synthetic mode without --hip_vocoder)"))
+    if vocoder is not None:
         from scipy.io.wavfile import write
         audio = vocoder.forward(mel).cpu().squeeze().clamp(-1, 1).numpy()
-        write(args.generated_sample_path, 22050, audio)
+        write(args.generated_sample_path, int(vocoder.h.get("sampling_rate", 22050)) if args.hip_vocoder else 22050, audio)
         print(f"saved {args.generated_sample_path}")
 
 

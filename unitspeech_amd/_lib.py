@@ -31,6 +31,15 @@ class us_duration_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("in_channels", "filter_channels", "kernel_size", "spk_emb_dim")]
 
 
+class us_vocoder_config(C.Structure):
+    _fields_ = [("num_mels", C.c_int32), ("upsample_initial_channel", C.c_int32), ("resblock", C.c_int32), ("n_up", C.c_int32),
+                ("upsample_rates", C.c_int32 * 8), ("upsample_kernel_sizes", C.c_int32 * 8), ("n_kernels", C.c_int32),
+                ("resblock_kernel_sizes", C.c_int32 * 4), ("resblock_dilation_sizes", (C.c_int32 * 3) * 4), ("activation", C.c_int32),
+                ("snake_logscale", C.c_int32)]
+
+
+US_VOCODER_SNAKE, US_VOCODER_SNAKEBETA = 0, 1
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -80,6 +89,14 @@ SIGNATURES = {
     "us_frontend_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "us_encoder_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_duration_predictor_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_vocoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_vocoder_config)]),
+    "us_vocoder_destroy": (C.c_int, [C.c_void_p]),
+    "us_vocoder_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "us_vocoder_num_weights": (C.c_int, [C.c_void_p]),
+    "us_vocoder_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "us_vocoder_last_error": (C.c_char_p, [C.c_void_p]),
+    "us_vocoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "us_vocoder_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_debug_block": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1,0 +1,549 @@
+// BigVGAN vocoder, inference (the reference's unitspeech/vocoder/models.py:169-191 `BigVGAN.forward`, :60-69 `AMPBlock1.forward`,
+// activations.py `Snake` / `SnakeBeta`, alias_free_torch/{act,resample,filter}.py `Activation1d`): mel [B][num_mels][T] ->
+// waveform [B][1][T * prod(upsample_rates)], exact fp32 throughout (storage, products and sums).
+//
+// Activations are planar [B][C][T] (time contiguous), the layout the reference's tensors have, so the mel the decoder's
+// finish_mel_kernel writes is taken as it is.  Three kernels do the work:
+//  - vc_conv_kernel: every dense Conv1d (conv_pre, the AMP convolutions) and every ConvTranspose1d (polyphase form, below) as an
+//    implicit GEMM on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): D[co][q] = sum_kk W[co][kk] * X[kk][q] with kk = tap * Cin + ci.
+//    The output channel is the MFMA row and time the column, so each of a lane's 16 results goes to a 32-sample run of one channel
+//    (coalesced stores).  Epilogue: bias, then the residual (`x = xt + x`, models.py:68), then the AMP-block sum (`xs += ...`,
+//    :184-186) and its division by num_kernels (:187) in the reference's order.
+//  - vc_act_kernel: one Activation1d (2x up-sampling, Snake / SnakeBeta, low-pass + 2x down-sampling) reading [C][T] once and
+//    writing [C][T] once.
+//  - vc_post_kernel: conv_post (C -> 1, k = 7) as a per-sample fp32 reduction with the tanh in its epilogue.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/unitspeech_hip.h"
+#include "kernels.h"
+
+namespace us {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// ---- implicit-GEMM convolution --------------------------------------------------------------------------------------------
+// Output step q in [0, Tin) of phase r computes   out[b][co][q * ostride + r] = bias[co] + sum_{j < taps, ci} P_r[j * Cin + ci][co]
+// * in[b][ci][q + off[r] + j * dil]   with in[] = 0 outside [0, Tin).
+//  Conv1d(k, dilation d, padding d (k - 1) / 2):  one phase, ostride 1, taps k, dil d, off -d (k - 1) / 2, P[j * Cin + ci][co] =
+//    W[co][ci][j].
+//  ConvTranspose1d(Cin, Cout, k, stride u, padding p = (k - u) / 2), k = K * u:  y[co][t] = bias[co] + sum_{ci, j} W[ci][co][j] *
+//    x[ci][i] over the (i, j) with i * u - p + j = t.  Write t = q * u + r and (r + p) = a_r * u + b_r (0 <= b_r < u): then j must
+//    be n * u + b_r (n in [0, K)) and i = q + a_r - n.  So phase r is an ordinary convolution with K taps, dil 1, off[r] = a_r -
+//    (K - 1) (tap n' = K - 1 - n reads x[q + off[r] + n']) and P_r[n' * Cin + ci][co] = W[ci][co][(K - 1 - n') * u + b_r]: every one
+//    of its K taps is a real product (none of the zeros of the stride-u dilated input is ever computed), and the u phases
+//    together write each output sample exactly once (t = q * u + r covers [0, Tin * u)).
+// P is packed once at load with its K*Cin rows padded to a multiple of kVcBK and its columns to a multiple of kVcBM (zeros), so
+// the weight tile needs no bounds checks.
+constexpr int kVcBM = 64;     // output channels per workgroup
+constexpr int kVcBN = 128;    // output steps per workgroup
+constexpr int kVcBK = 16;     // reduction slice per LDS stage
+constexpr int kVcMaxPhases = 16;
+
+struct VcConvArgs {
+  const float* in;            // [B][Cin][Tin]
+  const float* w;             // [nph][Kpad][ldw]
+  const float* bias;          // [Cout]
+  const float* res;           // [B][Cout][Tout] added after the bias, or null (may alias out)
+  const float* sum;           // [B][Cout][Tout] running AMP sum the result is added to, or null (may alias out)
+  float* out;                 // [B][Cout][Tout]
+  int Cin, Cout, Tin, Tout;
+  int taps, dil, Kdim, Kpad, ldw;
+  int nph, ostride;
+  float div;                  // > 0: the final value is divided by it (the last AMP block of a level)
+  int off[kVcMaxPhases];
+};
+
+__global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a) {
+  __shared__ float As[2][kVcBK][kVcBM];
+  __shared__ float Bs[2][kVcBK][kVcBN];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int mh = wave & 1, nh = wave >> 1;              // wave tile: 32 channels x 64 steps
+  const int b = blockIdx.z / a.nph, ph = blockIdx.z - b * a.nph;
+  const int m0 = blockIdx.y * kVcBM, n0 = blockIdx.x * kVcBN;
+  const float* __restrict__ in = a.in + (size_t)b * a.Cin * a.Tin;
+  const float* __restrict__ w = a.w + (size_t)ph * a.Kpad * a.ldw;
+  const int off = a.off[ph];
+  // global -> register staging: weights 4 floats per thread (one float4 of row tid / 16), input 8 floats of row tid / 16
+  const int wr = tid >> 4, wc = (tid & 15) * 4;
+  const int xr = tid >> 4, xc = tid & 15;
+  float4 wreg;
+  float xreg[8];
+  auto load = [&](int k0) {
+    wreg = *reinterpret_cast<const float4*>(w + (size_t)(k0 + wr) * a.ldw + m0 + wc);
+    const int kk = k0 + xr;
+    const bool live = kk < a.Kdim;
+    const int j = live ? kk / a.Cin : 0, ci = kk - j * a.Cin;
+    const float* row = in + (size_t)ci * a.Tin;
+    const int t0 = n0 + off + j * a.dil;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int t = t0 + xc + 16 * i;
+      xreg[i] = (live && t >= 0 && t < a.Tin) ? row[t] : 0.f;
+    }
+  };
+  auto store = [&](int buf) {
+    *reinterpret_cast<float4*>(&As[buf][wr][wc]) = wreg;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) Bs[buf][xr][xc + 16 * i] = xreg[i];
+  };
+  f32x16 acc[2];
+#pragma unroll
+  for (int n = 0; n < 2; ++n)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+  const int nk = a.Kpad / kVcBK;
+  load(0);
+  store(0);
+  __syncthreads();
+  const int kl = lane >> 5, cl = lane & 31;
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) load((kt + 1) * kVcBK);
+#pragma unroll
+    for (int s = 0; s < kVcBK / 2; ++s) {
+      const float fa = As[cur][2 * s + kl][mh * 32 + cl];
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        const float fb = Bs[cur][2 * s + kl][nh * 64 + n * 32 + cl];
+        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[n], 0, 0, 0);
+      }
+    }
+    if (kt + 1 < nk) store(cur ^ 1);
+    __syncthreads();
+  }
+  // D layout (32x32 f32 MFMA): column = lane & 31, row = 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
+  float* out = a.out + (size_t)b * a.Cout * a.Tout;        // not __restrict__: res / sum may alias it
+  const size_t bo = (size_t)b * a.Cout * a.Tout;
+#pragma unroll
+  for (int n = 0; n < 2; ++n) {
+    const int q = n0 + nh * 64 + n * 32 + cl;
+    if (q >= a.Tin) continue;
+    const int t = q * a.ostride + ph;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = m0 + mh * 32 + 8 * (r >> 2) + 4 * kl + (r & 3);
+      if (co >= a.Cout) continue;
+      const size_t idx = (size_t)co * a.Tout + t;
+      float v = acc[n][r] + a.bias[co];
+      if (a.res) v = v + a.res[bo + idx];
+      if (a.sum) v = a.sum[bo + idx] + v;
+      if (a.div > 0.f) v = v / a.div;
+      out[idx] = v;
+    }
+  }
+}
+
+// P[ph][kk][co] (zero padded) from a Conv1d weight W[Cout][Cin][k] (u == 0) or a ConvTranspose1d weight W[Cin][Cout][k] (u > 0,
+// k = taps * u, padding p): the packing of the comment above vc_conv_kernel.
+__global__ void vc_pack_kernel(const float* __restrict__ w, float* __restrict__ p, int Cin, int Cout, int k, int u, int pad, int taps,
+                               int Kpad, int ldw, int nph) {
+  const size_t n = (size_t)nph * Kpad * ldw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int co = (int)(i % ldw);
+    const int kk = (int)((i / ldw) % Kpad);
+    const int ph = (int)(i / ((size_t)ldw * Kpad));
+    float v = 0.f;
+    if (co < Cout && kk < taps * Cin) {
+      const int j = kk / Cin, ci = kk - j * Cin;
+      if (u == 0) {
+        v = w[((size_t)co * Cin + ci) * k + j];
+      } else {
+        const int br = (ph + pad) % u;
+        v = w[((size_t)ci * Cout + co) * k + (taps - 1 - j) * u + br];
+      }
+    }
+    p[i] = v;
+  }
+}
+
+// ---- anti-aliased Snake / SnakeBeta (Activation1d with up_ratio = down_ratio = 2, 12-tap filters) ----------------------------
+// UpSample1d (resample.py): pad = 12 / 2 - 1 = 5 samples of replicate padding, conv_transpose with stride 2, times 2, crop 15 / 15.
+// With x(i) = x[clamp(i, 0, T - 1)] that is, for m in [0, 2T):
+//   u[2q]     = 2 * sum_{s < 6} f[2s + 1] * x(q + 2 - s)
+//   u[2q + 1] = 2 * sum_{s < 6} f[2s]     * x(q + 3 - s)
+// then v = act(u), and LowPassFilter1d(stride 2) replicate-pads v by (5, 6):   out[n] = sum_{j < 12} g[j] * v[clamp(2n + j - 5, 0, 2T - 1)].
+// A workgroup makes kActN outputs of one (b, c) row: it stages x(n0 - 6 .. n0 + kActN + 5) and v(clamp(2 n0 - 6 .. 2 n0 + 2 kActN + 5))
+// in LDS; every index those formulas touch lies in those windows.
+constexpr int kActN = 256;
+
+__global__ __launch_bounds__(256) void vc_act_kernel(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ ab,
+                                                     const float* __restrict__ fup, const float* __restrict__ fdown, int C, int T) {
+  __shared__ float xs[kActN + 12];
+  __shared__ float vs[2 * kActN + 12];
+  __shared__ float f[24];
+  const int row = blockIdx.y, c = row % C;
+  const int n0 = blockIdx.x * kActN;
+  const float* __restrict__ xr = x + (size_t)row * T;
+  if (threadIdx.x < 12) {
+    f[threadIdx.x] = fup[threadIdx.x];
+    f[12 + threadIdx.x] = fdown[threadIdx.x];
+  }
+  for (int i = threadIdx.x; i < kActN + 12; i += blockDim.x) xs[i] = xr[min(max(n0 - 6 + i, 0), T - 1)];
+  __syncthreads();
+  const float alpha = ab[c], inv = ab[C + c];
+  for (int i = threadIdx.x; i < 2 * kActN + 12; i += blockDim.x) {
+    const int m = min(max(2 * n0 - 6 + i, 0), 2 * T - 1);
+    const int q = m >> 1, odd = m & 1;
+    const float* xq = xs + (q - n0 + 6) + 2 + odd;        // x(q + 2 + odd - s) = xq[-s]
+    float acc = 0.f;
+#pragma unroll
+    for (int s = 0; s < 6; ++s) acc = fmaf(f[2 * s + 1 - odd], xq[-s], acc);
+    const float uval = 2.f * acc;
+    const float sn = sinf(mul_rn(uval, alpha));
+    vs[i] = add_rn(uval, mul_rn(inv, mul_rn(sn, sn)));    // x + 1 / (beta + 1e-9) * sin(x alpha)^2, each op rounded as in activations.py
+  }
+  __syncthreads();
+  for (int l = threadIdx.x; l < kActN; l += blockDim.x) {
+    if (n0 + l >= T) break;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc = fmaf(f[12 + j], vs[2 * l + j + 1], acc);
+    out[(size_t)row * T + n0 + l] = acc;
+  }
+}
+
+// alpha / beta of one Snake(Beta) module -> ab[0][c] = alpha' (exp(alpha) with snake_logscale), ab[1][c] = 1 / (beta' + 1e-9);
+// `which` 0: from alpha (Snake fills both halves from it), 1: beta (SnakeBeta's second parameter)
+__global__ void vc_snake_param_kernel(const float* __restrict__ p, float* __restrict__ ab, int C, int which, int both, int logscale) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float v = logscale ? expf(p[c]) : p[c];
+  if (which == 0) ab[c] = v;
+  if (which == 1 || both) ab[C + c] = 1.f / (v + 1e-9f);
+}
+
+// ---- conv_post: Conv1d(C, 1, 7, padding 3) + tanh --------------------------------------------------------------------------------
+constexpr int kPostK = 7;
+
+__global__ __launch_bounds__(256) void vc_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      float* __restrict__ out, int C, int T) {
+  extern __shared__ float ws[];
+  for (int i = threadIdx.x; i < C * kPostK; i += blockDim.x) ws[i] = w[i];
+  __syncthreads();
+  const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  const float* __restrict__ xb = x + (size_t)b * C * T;
+  float acc = 0.f;
+  for (int ci = 0; ci < C; ++ci) {
+    const float* xr = xb + (size_t)ci * T;
+#pragma unroll
+    for (int j = 0; j < kPostK; ++j) {
+      const int tt = t + j - kPostK / 2;
+      if (tt >= 0 && tt < T) acc = fmaf(ws[ci * kPostK + j], xr[tt], acc);
+    }
+  }
+  out[(size_t)b * T + t] = tanhf(acc + bias[0]);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+struct VcWeight {
+  std::vector<int64_t> shape;
+  float* dev = nullptr;         // reference layout
+  bool loaded = false;
+  size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
+};
+
+struct VcConv {                 // one Conv1d / ConvTranspose1d in packed form
+  std::string prefix;
+  int cin = 0, cout = 0, k = 0, dil = 1, u = 0, pad = 0;     // u > 0: transposed with stride u
+  int taps = 0, Kpad = 0, ldw = 0, nph = 1;
+  int off[kVcMaxPhases] = {};
+  float* packed = nullptr;
+};
+
+struct VcAct {                  // one Activation1d
+  std::string prefix;
+  int C = 0;
+  float* ab = nullptr;          // [2][C]
+};
+
+}  // namespace
+}  // namespace us
+
+struct us_vocoder {
+  us_vocoder_config cfg{};
+  int device = 0;
+  std::vector<std::string> keys;       // state_dict order (remove_weight_norm form)
+  std::map<std::string, us::VcWeight> w;
+  std::map<std::string, us::VcConv> conv;
+  std::map<std::string, us::VcAct> act;
+  std::string err;
+};
+
+namespace us {
+namespace {
+
+int vc_fail(us_vocoder* h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  set_last_error(msg.c_str());
+  return code;
+}
+int vc_hip(us_vocoder* h, const char* what, hipError_t e) { return vc_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+void vc_key(us_vocoder* h, const std::string& k, std::vector<int64_t> shape) {
+  h->keys.push_back(k);
+  h->w[k].shape = std::move(shape);
+}
+
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+void vc_add_conv(us_vocoder* h, const std::string& p, int cin, int cout, int k, int dil) {
+  vc_key(h, p + ".weight", {cout, cin, k});
+  vc_key(h, p + ".bias", {cout});
+  VcConv& c = h->conv[p];
+  c.prefix = p; c.cin = cin; c.cout = cout; c.k = k; c.dil = dil; c.taps = k;
+  c.Kpad = round_up(k * cin, kVcBK); c.ldw = round_up(cout, kVcBM); c.nph = 1;
+  c.off[0] = -dil * (k - 1) / 2;
+}
+
+void vc_add_up(us_vocoder* h, const std::string& p, int cin, int cout, int k, int u) {
+  vc_key(h, p + ".weight", {cin, cout, k});      // ConvTranspose1d weight layout [in, out, k]
+  vc_key(h, p + ".bias", {cout});
+  VcConv& c = h->conv[p];
+  c.prefix = p; c.cin = cin; c.cout = cout; c.k = k; c.u = u; c.pad = (k - u) / 2;
+  c.taps = k / u; c.Kpad = round_up(c.taps * cin, kVcBK); c.ldw = round_up(cout, kVcBM); c.nph = u;
+  for (int r = 0; r < u; ++r) c.off[r] = (r + c.pad) / u - (c.taps - 1);
+}
+
+void vc_add_act(us_vocoder* h, const std::string& p, int C) {
+  vc_key(h, p + ".act.alpha", {C});
+  if (h->cfg.activation == US_VOCODER_SNAKEBETA) vc_key(h, p + ".act.beta", {C});
+  vc_key(h, p + ".upsample.filter", {1, 1, 12});
+  vc_key(h, p + ".downsample.lowpass.filter", {1, 1, 12});
+  VcAct& a = h->act[p];
+  a.prefix = p; a.C = C;
+}
+
+int channels(const us_vocoder_config& c, int level) { return c.upsample_initial_channel >> level; }   // after up-sampler `level - 1`
+
+// module registration order of models.py:125-165, remove_weight_norm() form
+void vocoder_keys(us_vocoder* h) {
+  const auto& c = h->cfg;
+  vc_add_conv(h, "conv_pre", c.num_mels, c.upsample_initial_channel, 7, 1);
+  for (int i = 0; i < c.n_up; ++i)
+    vc_add_up(h, "ups." + std::to_string(i) + ".0", channels(c, i), channels(c, i + 1), c.upsample_kernel_sizes[i], c.upsample_rates[i]);
+  for (int i = 0; i < c.n_up; ++i)
+    for (int j = 0; j < c.n_kernels; ++j) {
+      const std::string p = "resblocks." + std::to_string(i * c.n_kernels + j);
+      const int ch = channels(c, i + 1), k = c.resblock_kernel_sizes[j];
+      for (int l = 0; l < 3; ++l) vc_add_conv(h, p + ".convs1." + std::to_string(l), ch, ch, k, c.resblock_dilation_sizes[j][l]);
+      for (int l = 0; l < 3; ++l) vc_add_conv(h, p + ".convs2." + std::to_string(l), ch, ch, k, 1);
+      for (int a = 0; a < 6; ++a) vc_add_act(h, p + ".activations." + std::to_string(a), ch);
+    }
+  const int ch = channels(c, c.n_up);
+  vc_add_act(h, "activation_post", ch);
+  vc_key(h, "conv_post.weight", {1, ch, kPostK});
+  vc_key(h, "conv_post.bias", {1});
+}
+
+int vc_device(us_vocoder* h, const char* what) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
+    return vc_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
+                                     std::to_string(h->device) + ")");
+  return US_OK;
+}
+
+long long vc_hop(const us_vocoder_config& c) {
+  long long hop = 1;
+  for (int i = 0; i < c.n_up; ++i) hop *= c.upsample_rates[i];
+  return hop;
+}
+
+// largest C * T of any activation per batch item (conv_pre's output or a level's), in floats
+long long vc_max_ct(const us_vocoder_config& c, int T) {
+  long long m = (long long)c.upsample_initial_channel * T, t = T;
+  for (int i = 0; i < c.n_up; ++i) {
+    t *= c.upsample_rates[i];
+    m = std::max(m, (long long)channels(c, i + 1) * t);
+  }
+  return m;
+}
+
+constexpr int kVcBuffers = 5;      // level input, AMP sum, residual stream, activation output, first-conv output
+
+void conv(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, const float* res, const float* sum, float div,
+          int B, int Tin) {
+  const VcConv& c = h->conv.at(p);
+  VcConvArgs a{};
+  a.in = in; a.w = c.packed; a.bias = h->w.at(p + ".bias").dev; a.res = res; a.sum = sum; a.out = out;
+  a.Cin = c.cin; a.Cout = c.cout; a.Tin = Tin; a.Tout = Tin * c.nph;
+  a.taps = c.taps; a.dil = c.u ? 1 : c.dil; a.Kdim = c.taps * c.cin; a.Kpad = c.Kpad; a.ldw = c.ldw;
+  a.nph = c.nph; a.ostride = c.nph; a.div = div;
+  for (int r = 0; r < c.nph; ++r) a.off[r] = c.off[r];
+  hipLaunchKernelGGL(vc_conv_kernel, dim3((Tin + kVcBN - 1) / kVcBN, (c.cout + kVcBM - 1) / kVcBM, B * c.nph), dim3(256), 0, s, a);
+}
+
+void activation(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, int B, int T) {
+  const VcAct& a = h->act.at(p);
+  hipLaunchKernelGGL(vc_act_kernel, dim3((T + kActN - 1) / kActN, B * a.C), dim3(256), 0, s, in, out, a.ab,
+                     h->w.at(p + ".upsample.filter").dev, h->w.at(p + ".downsample.lowpass.filter").dev, a.C, T);
+}
+
+}  // namespace
+}  // namespace us
+
+extern "C" {
+
+using namespace us;
+
+int us_vocoder_create(us_vocoder_handle* out, const us_vocoder_config* cfg) {
+  if (!out || !cfg) return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: null argument");
+  const auto& c = *cfg;
+  if (c.resblock != 1)
+    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: only resblock \"1\" (AMPBlock1) is built; AMPBlock2 is not");
+  if (c.activation != US_VOCODER_SNAKE && c.activation != US_VOCODER_SNAKEBETA)
+    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: activation must be snake or snakebeta");
+  if (c.num_mels <= 0 || c.num_mels > 4096 || c.upsample_initial_channel <= 0 || c.upsample_initial_channel > 8192 || c.n_up <= 0 ||
+      c.n_up > 8 || c.n_kernels <= 0 || c.n_kernels > 4 || c.snake_logscale < 0 || c.snake_logscale > 1)
+    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: bad num_mels / upsample_initial_channel / number of up-samplers or kernels");
+  if (c.upsample_initial_channel % (1 << c.n_up) != 0)
+    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: upsample_initial_channel must be divisible by 2^len(upsample_rates)");
+  for (int i = 0; i < c.n_up; ++i) {
+    const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
+    if (u <= 0 || u > kVcMaxPhases || k < u || k % u != 0 || (k - u) % 2 != 0)
+      return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: up-sampler " + std::to_string(i) +
+                                             ": rate in [1, 16] and kernel a multiple of the rate with (kernel - rate) even are built");
+  }
+  for (int j = 0; j < c.n_kernels; ++j) {
+    const int k = c.resblock_kernel_sizes[j];
+    if (k <= 0 || k > 31 || k % 2 == 0)
+      return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: resblock kernel sizes must be odd and at most 31");
+    for (int l = 0; l < 3; ++l)
+      if (c.resblock_dilation_sizes[j][l] <= 0 || c.resblock_dilation_sizes[j][l] > 64)
+        return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: resblock dilations must be in [1, 64]");
+  }
+  if ((size_t)(c.upsample_initial_channel >> c.n_up) * kPostK * sizeof(float) > 48 * 1024)
+    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: too many channels at conv_post");
+  auto* h = new us_vocoder();
+  h->cfg = c;
+  (void)hipGetDevice(&h->device);
+  vocoder_keys(h);
+  *out = h;
+  return US_OK;
+}
+
+int us_vocoder_destroy(us_vocoder_handle h) {
+  if (!h) return US_OK;
+  for (auto& kv : h->w)
+    if (kv.second.dev) (void)hipFree(kv.second.dev);
+  for (auto& kv : h->conv)
+    if (kv.second.packed) (void)hipFree(kv.second.packed);
+  for (auto& kv : h->act)
+    if (kv.second.ab) (void)hipFree(kv.second.ab);
+  delete h;
+  return US_OK;
+}
+
+int us_vocoder_num_weights(us_vocoder_handle h) { return h ? (int)h->keys.size() : 0; }
+const char* us_vocoder_weight_key(us_vocoder_handle h, int i) {
+  return (h && i >= 0 && i < (int)h->keys.size()) ? h->keys[i].c_str() : nullptr;
+}
+const char* us_vocoder_last_error(us_vocoder_handle h) { return h ? h->err.c_str() : us_last_error(nullptr); }
+
+int us_vocoder_load_weight(us_vocoder_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
+  if (!h || !key || !data || !shape) return vc_fail(h, US_EINVAL, "us_vocoder_load_weight: null argument");
+  auto it = h->w.find(key);
+  if (it == h->w.end()) return vc_fail(h, US_ENOKEY, std::string("us_vocoder_load_weight: unknown key '") + key + "'");
+  VcWeight& w = it->second;
+  bool same = ndim == (int)w.shape.size();
+  for (int i = 0; same && i < ndim; ++i) same = shape[i] == w.shape[i];
+  if (!same) return vc_fail(h, US_ESHAPE, std::string("us_vocoder_load_weight: shape of '") + key + "' does not match the configuration");
+  int rc = vc_device(h, "us_vocoder_load_weight");
+  if (rc != US_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t n = w.numel();
+  hipError_t e;
+  if (!w.dev && (e = hipMalloc(&w.dev, n * sizeof(float))) != hipSuccess) return vc_hip(h, "hipMalloc(weight)", e);
+  if ((e = hipMemcpyAsync(w.dev, data, n * sizeof(float), hipMemcpyDeviceToDevice, s)) != hipSuccess) return vc_hip(h, "hipMemcpyAsync(weight)", e);
+  const std::string k(key);
+  const auto dot = k.rfind('.');
+  const std::string prefix = k.substr(0, dot), leaf = k.substr(dot + 1);
+  auto ci = h->conv.find(prefix);
+  if (ci != h->conv.end() && leaf == "weight") {
+    VcConv& c = ci->second;
+    const size_t np = (size_t)c.nph * c.Kpad * c.ldw;
+    if (!c.packed && (e = hipMalloc(&c.packed, np * sizeof(float))) != hipSuccess) return vc_hip(h, "hipMalloc(packed weight)", e);
+    hipLaunchKernelGGL(vc_pack_kernel, dim3((unsigned)std::min<size_t>((np + 255) / 256, 4096)), dim3(256), 0, s, w.dev, c.packed, c.cin,
+                       c.cout, c.k, c.u, c.pad, c.taps, c.Kpad, c.ldw, c.nph);
+  }
+  const auto adot = prefix.rfind('.');
+  if (adot != std::string::npos && prefix.substr(adot + 1) == "act" && (leaf == "alpha" || leaf == "beta")) {
+    VcAct& a = h->act.at(prefix.substr(0, adot));
+    if (!a.ab && (e = hipMalloc(&a.ab, 2 * (size_t)a.C * sizeof(float))) != hipSuccess) return vc_hip(h, "hipMalloc(snake parameters)", e);
+    const bool snake = h->cfg.activation == US_VOCODER_SNAKE;
+    hipLaunchKernelGGL(vc_snake_param_kernel, dim3((a.C + 255) / 256), dim3(256), 0, s, w.dev, a.ab, a.C, leaf == "alpha" ? 0 : 1, snake ? 1 : 0,
+                       h->cfg.snake_logscale ? 1 : 0);
+  }
+  if ((e = hipGetLastError()) != hipSuccess) return vc_hip(h, "us_vocoder_load_weight", e);
+  w.loaded = true;
+  return US_OK;
+}
+
+size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T) {
+  if (!h || B <= 0 || T <= 0) return 0;
+  return (size_t)kVcBuffers * (size_t)B * (size_t)vc_max_ct(h->cfg, T) * sizeof(float) + 256;
+}
+
+int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
+                       us_stream stream) {
+  if (!h || !mel || !wav || B <= 0 || T <= 0) return vc_fail(h, US_EINVAL, "us_vocoder_forward: bad argument");
+  const auto& c = h->cfg;
+  const long long hop = vc_hop(c);
+  if (vc_max_ct(c, T) >= (1ll << 31) || (long long)T * hop >= (1ll << 31) || (long long)B * c.upsample_initial_channel > 65535 ||
+      (long long)B * kVcMaxPhases > 65535)
+    return vc_fail(h, US_EINVAL, "us_vocoder_forward: B * channels or T * hop too large");
+  for (const auto& k : h->keys)
+    if (!h->w[k].loaded) return vc_fail(h, US_EWEIGHTS, "us_vocoder_forward: weight '" + k + "' has not been loaded");
+  int rc = vc_device(h, "us_vocoder_forward");
+  if (rc != US_OK) return rc;
+  if (!workspace || workspace_bytes < us_vocoder_workspace_bytes(h, B, T))
+    return vc_fail(h, US_EWORKSPACE, "us_vocoder_forward: workspace too small (us_vocoder_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t slab = (size_t)B * (size_t)vc_max_ct(c, T);
+  float* base = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+  float* X = base;               // level input (the up-sampler's output)
+  float* S = X + slab;           // level output: the AMP-block sum (conv_pre writes here too)
+  float* R = S + slab;           // residual stream x_l of the running AMP block (l = 1, 2)
+  float* A = R + slab;           // Activation1d output
+  float* H = A + slab;           // output of the block's first convolution
+  conv(h, s, "conv_pre", mel, S, nullptr, nullptr, 0.f, B, T);
+  int t = T;
+  for (int i = 0; i < c.n_up; ++i) {
+    conv(h, s, "ups." + std::to_string(i) + ".0", S, X, nullptr, nullptr, 0.f, B, t);
+    t *= c.upsample_rates[i];
+    for (int j = 0; j < c.n_kernels; ++j) {
+      // AMPBlock1.forward (models.py:60-69): x_{l+1} = c2(a2(c1(a1(x_l)))) + x_l, x_0 = the level input
+      const std::string p = "resblocks." + std::to_string(i * c.n_kernels + j);
+      const float* xl = X;
+      for (int l = 0; l < 3; ++l) {
+        const std::string ls = std::to_string(l);
+        activation(h, s, p + ".activations." + std::to_string(2 * l), xl, A, B, t);
+        conv(h, s, p + ".convs1." + ls, A, H, nullptr, nullptr, 0.f, B, t);
+        activation(h, s, p + ".activations." + std::to_string(2 * l + 1), H, A, B, t);
+        if (l < 2) {
+          conv(h, s, p + ".convs2." + ls, A, R, xl, nullptr, 0.f, B, t);
+          xl = R;
+        } else {        // the block's output goes straight into the level sum: xs (+)= x_3, then / num_kernels (:180-187)
+          conv(h, s, p + ".convs2." + ls, A, S, xl, j > 0 ? S : nullptr, j == c.n_kernels - 1 ? (float)c.n_kernels : 0.f, B, t);
+        }
+      }
+    }
+  }
+  activation(h, s, "activation_post", S, A, B, t);
+  const int ch = channels(c, c.n_up);
+  hipLaunchKernelGGL(vc_post_kernel, dim3((t + 255) / 256, B), dim3(256), (size_t)ch * kPostK * sizeof(float), s, A,
+                     h->w["conv_post.weight"].dev, h->w["conv_post.bias"].dev, wav, ch, t);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : vc_hip(h, "us_vocoder_forward", e);
+}
+
+}  // extern "C"
