@@ -194,6 +194,13 @@ int us_pow2_scale(const float* x, size_t n, int target_log2, float* scale_and_in
 int us_finetune_segment(const float* cond_x, const float* y, const float* attn, const int64_t* start, const int64_t* count,
                         float* y_cut, float* cond_y, float* seg_mask, int B, int F, int Lu, int Ly, int segment_size,
                         us_stream stream);
+/* Transpose of us_finetune_segment's alignment (the unit-encoder step, train_STEP2.py:295-297): d_cond_x [B,F,Lu] =
+ * attn_cut d_cond_y, i.e. d_cond_x[b][f][l] = sum_{j < count[b]} attn[b][l][start[b] + j] d_cond_y[b][f][j].  Overwrites d_cond_x. */
+int us_finetune_segment_backward(const float* d_cond_y, const float* attn, const int64_t* start, const int64_t* count, float* d_cond_x, int B,
+                                 int F, int Lu, int Ly, int segment_size, us_stream stream);
+/* Prior loss of train_STEP2.py:302-303: loss[0] (device) = sum(0.5 ((y - mu_y)^2 + log 2 pi) y_mask) / (sum(y_mask) F) over y, mu_y
+ * [B,F,T], y_mask [B,1,T]; d_mu_y (optional) = its gradient w.r.t. mu_y.  One workgroup, fixed summation order: no scratch. */
+int us_prior_loss(const float* y, const float* mu_y, const float* y_mask, float* loss, float* d_mu_y, int B, int F, int T, us_stream stream);
 
 /* ---- conditioning producer of `execute_text_to_speech` (:424-438; the text encoder and duration predictor stay the
  * caller's modules) -----------------------------------------------------------------------------------------------------
@@ -243,6 +250,34 @@ const char* us_frontend_last_error(us_frontend_handle h);
 size_t us_frontend_workspace_bytes(us_frontend_handle h, int B, int L);
 int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x, float* x_mask, int B, int L,
                        void* workspace, size_t workspace_bytes, us_stream stream);
+/* ---- training of the Encoder (encoder.py:253-308 in train mode; csrc/encoder_train.hip) --------------------------------
+ * us_encoder_forward_train: the forward with every Dropout of the reference -- the prenet's three relu_drop (p = 0.5), and in
+ *   each transformer layer the attention probabilities, EncoderModule.drop after attention, the FFN's drop after the ReLU and
+ *   EncoderModule.drop after the FFN (p = p_dropout, 0 <= p_dropout < 1).  p_dropout < 0: no site drops, the prenet's
+ *   included (the reference in eval mode, through which autograd still runs).  Same inputs and outputs as us_encoder_forward.  The
+ *   workspace (us_encoder_train_workspace_bytes) keeps the tape the backward reads; it must stay untouched until then.  The
+ *   tape stores every activation (about 7 C + F floats per symbol and layer) and the attention probabilities (B H L^2 floats
+ *   per layer; stored rather than recomputed), plus the backward's scratch and a gradient slot for every key.
+ * us_encoder_backward: overwrites grads[i] (reference layout of keys[i], device memory) with the gradient of that state_dict
+ *   key, given upstream gradients grad_mu [B,n_feats,L] and / or grad_x [B,n_channels,L] (either may be NULL: zero).  Keys not
+ *   listed are computed into the workspace and dropped.  US_EINVAL when the workspace holds no training forward of this B and L.
+ *   Deterministic: no atomics, fixed summation orders.
+ * Dropout masks are a pure function of (seed, site, flat index of the element in the reference's tensor): Philox4x32-10 keyed by
+ *   the seed, counter (index / 4, site).  Sites: 0, 1, 2 the prenet layers ([B,C,L]); for transformer layer i, 3 + 4i the attention
+ *   probabilities ([B,H,L,L]), 4 + 4i the drop after attention ([B,C,L]), 5 + 4i the FFN's drop ([B,filter_channels,L]), 6 + 4i the
+ *   drop after the FFN ([B,C,L]).
+ * us_encoder_dropout_mask: TEST HOOK.  Writes the scaled keep mask (0 or 1 / (1 - p)) that `site` used for `seed` in a training
+ *   forward with this p_dropout, in the shape listed above: p = 0.5 at the prenet sites and p_dropout elsewhere (all ones for a
+ *   negative p_dropout).  A pure function of its arguments.
+ * us_encoder_tape_release: forget the training forward a workspace holds (call before the memory is freed or reused); a later
+ *   us_encoder_backward on it fails with US_EINVAL. */
+size_t us_encoder_train_workspace_bytes(us_frontend_handle h, int B, int L);
+int us_encoder_forward_train(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x, float* x_mask, int B,
+                             int L, float p_dropout, uint64_t seed, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float* grad_x, int B, int L, const char* const* keys,
+                        float* const* grads, int n_grads, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_encoder_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B, int L, float p_dropout, float* out, us_stream stream);
+int us_encoder_tape_release(us_frontend_handle h, const void* workspace);
 /* `DurationPredictor.forward(x, x_mask, w=None, g=g, reverse=True)` (:47-63): x [B,in_channels,L], x_mask [B,1,L],
  * g [B,1,spk_emb_dim] (NULL iff spk_emb_dim == 0) -> logw [B,1,L]. */
 int us_duration_predictor_forward(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
+#include "frontend.h"
 #include "kernels.h"
 
 namespace us {
@@ -286,29 +287,6 @@ __global__ void fe_pack_conv_kernel(const float* w, float* out, int Cout, int Ci
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-struct Weight {
-  std::vector<int64_t> shape;
-  float* dev = nullptr;        // reference layout
-  float* packed = nullptr;     // conv weights: [K][Cin][Cout]
-  bool loaded = false;
-  size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
-};
-
-}  // namespace
-}  // namespace us
-
-struct us_frontend {
-  int kind = 0;                        // 0: Encoder, 1: DurationPredictor
-  us_encoder_config ec{};
-  us_duration_config dc{};
-  int device = 0;
-  std::vector<std::string> keys;       // state_dict order
-  std::map<std::string, us::Weight> w;
-  std::string err;
-};
-
-namespace us {
-namespace {
 
 int fe_fail(us_frontend* h, int code, const std::string& msg) {
   if (h) h->err = msg;

@@ -290,6 +290,62 @@ __global__ void finish_mel_kernel(const float* __restrict__ x, const float* __re
   }
 }
 
+// transpose of finetune_segment_kernel's cond_y = attn_cut^T cond_x:  d_cond_x[b][f][l] = sum_{j < count[b]} attn[b][l][start[b] + j]
+// * d_cond_y[b][f][j]  (frames of the window past count[b] or past y carry no alignment; summed in j order)
+__global__ __launch_bounds__(256) void finetune_segment_bwd_kernel(const float* __restrict__ d_cond_y, const float* __restrict__ attn,
+                                                                   const long long* __restrict__ start, const long long* __restrict__ count,
+                                                                   float* __restrict__ d_cond_x, int B, int F, int Lu, int Ly, int seg) {
+  const long long total = (long long)B * F * Lu;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int l = (int)(i % Lu);
+    const int f = (int)((i / Lu) % F);
+    const int b = (int)(i / ((long long)Lu * F));
+    const long long s0 = start[b];
+    const long long n = count[b] < seg ? count[b] : seg;
+    const float* ap = attn + ((long long)b * Lu + l) * Ly;
+    const float* gp = d_cond_y + ((long long)b * F + f) * seg;
+    float acc = 0.f;
+    for (long long j = 0; j < n; ++j) {
+      const long long src = s0 + j;
+      if (src >= 0 && src < Ly) acc = __builtin_fmaf(ap[src], gp[j], acc);
+    }
+    d_cond_x[i] = acc;
+  }
+}
+
+// train_STEP2.py:302-303:  loss = sum(0.5 ((y - mu)^2 + log 2 pi) * mask) / (sum(mask) * F),  d_mu = -(y - mu) * mask / (sum(mask) * F).
+// One workgroup: each thread sums a strided slice in order, the 1024 partials meet in a fixed tree (deterministic); then the
+// same workgroup writes d_mu with the denominator it found.
+__global__ __launch_bounds__(1024) void prior_loss_kernel(const float* __restrict__ y, const float* __restrict__ mu, const float* __restrict__ mask,
+                                                          float* __restrict__ loss, float* __restrict__ d_mu, int B, int F, int T) {
+  __shared__ float red[2][1024];
+  const int tid = threadIdx.x;
+  const long long n = (long long)B * F * T, nm = (long long)B * T;
+  const float half_log_2pi = 0.91893853320467274f;
+  float s = 0.f, m = 0.f;
+  for (long long i = tid; i < n; i += 1024) {
+    const long long b = i / ((long long)F * T), t = i % T;
+    const float w = mask[b * T + t];
+    const float d = y[i] - mu[i];
+    s += (0.5f * d * d + half_log_2pi) * w;
+  }
+  for (long long i = tid; i < nm; i += 1024) m += mask[i];
+  red[0][tid] = s;
+  red[1][tid] = m;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+    __syncthreads();
+  }
+  const float denom = red[1][0] * (float)F;
+  if (tid == 0) loss[0] = red[0][0] / denom;
+  if (d_mu)
+    for (long long i = tid; i < n; i += 1024) {
+      const long long b = i / ((long long)F * T), t = i % T;
+      d_mu[i] = -(y[i] - mu[i]) * mask[b * T + t] / denom;
+    }
+}
+
 inline int nblocks(long long total, int cap = 2048) {
   long long b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -403,6 +459,24 @@ int us_finetune_segment(const float* cond_x, const float* y, const float* attn, 
                      seg_mask, B, F, Lu, Ly, segment_size);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : fail("us_finetune_segment", e);
+}
+
+int us_finetune_segment_backward(const float* d_cond_y, const float* attn, const int64_t* start, const int64_t* count, float* d_cond_x, int B,
+                                 int F, int Lu, int Ly, int segment_size, us_stream stream) {
+  if (!d_cond_y || !attn || !start || !count || !d_cond_x || B <= 0 || F <= 0 || Lu <= 0 || Ly <= 0 || segment_size <= 0)
+    return bad("us_finetune_segment_backward: bad argument");
+  hipLaunchKernelGGL(finetune_segment_bwd_kernel, dim3(nblocks((long long)B * F * Lu)), dim3(256), 0, static_cast<hipStream_t>(stream), d_cond_y,
+                     attn, reinterpret_cast<const long long*>(start), reinterpret_cast<const long long*>(count), d_cond_x, B, F, Lu, Ly,
+                     segment_size);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fail("us_finetune_segment_backward", e);
+}
+
+int us_prior_loss(const float* y, const float* mu_y, const float* y_mask, float* loss, float* d_mu_y, int B, int F, int T, us_stream stream) {
+  if (!y || !mu_y || !y_mask || !loss || B <= 0 || F <= 0 || T <= 0) return bad("us_prior_loss: bad argument");
+  hipLaunchKernelGGL(prior_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), y, mu_y, y_mask, loss, d_mu_y, B, F, T);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fail("us_prior_loss", e);
 }
 
 int us_tts_durations(const float* logw, const float* x_mask, float* w_ceil, int64_t* y_lengths, int B, int L, float length_scale,

@@ -7,14 +7,17 @@ signatures and return values -- `Encoder(x, x_lengths) -> (mu_x, x, x_mask)`, `D
 g=spk_emb, reverse=True) -> logw` -- so `UnitSpeech.execute_text_to_speech(phoneme, lengths, spk_emb, text_encoder,
 duration_predictor, ...)` takes them where it takes the reference's modules.
 
-Inference only: the modules must be in eval mode (the reference's Dropouts are then the identity), and the duration
-predictor's training branch (`reverse=False`: the MSE against log durations, :60-61) is not built.  There is no CPU
-fallback: tensors must live on a ROCm device.
+In eval mode the reference's Dropouts are the identity.  `Encoder(..., trainable=True)` in train mode runs the training forward
+of csrc/encoder_train.hip (every Dropout of the reference) through a `torch.autograd.Function` whose backward produces the
+gradient of every parameter; without `trainable=True` train mode is refused, and the duration predictor is inference only (its
+training branch, `reverse=False`: the MSE against log durations, :60-61, is not built).  There is no CPU fallback: tensors must
+live on a ROCm device.
 """
 from __future__ import annotations
 
 import ctypes as C
 import hashlib
+import weakref
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -196,11 +199,13 @@ class _FrontEndModule(torch.nn.Module):
     def _create(self, lib, device):          # overridden
         raise NotImplementedError
 
-    def _sync(self, device: torch.device):
+    def _sync(self, device: torch.device, training_ok: bool = False):
         if device.type != "cuda":
             raise RuntimeError("the HIP front end needs tensors on a ROCm device (no CPU fallback); got " + str(device))
-        if self.training:
-            raise RuntimeError(f"{type(self).__name__} is inference-only (the reference's Dropout layers are not built): call .eval()")
+        if self.training and not training_ok:
+            hint = " or construct it with trainable=True to train it" if isinstance(self, Encoder) else ""
+            raise RuntimeError(f"{type(self).__name__} is inference-only (the reference's Dropout layers are not built): call .eval()"
+                               + hint)
         lib = _lib.load()
         if not self._h or self._device != device:
             self._close()
@@ -255,8 +260,9 @@ class Encoder(_FrontEndModule):
     n_contentvec=0, window_size=None)`."""
 
     def __init__(self, n_vocab, n_feats, n_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout=0.0, n_contentvec=0,
-                 window_size=None):
+                 window_size=None, *, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         if n_contentvec:
             raise NotImplementedError("Encoder(n_contentvec > 0) (a Linear front instead of the Embedding, encoder.py:281) is not built: "
                                       "no configuration of the reference uses it")
@@ -274,11 +280,21 @@ class Encoder(_FrontEndModule):
                                    self.cfg.n_layers, self.cfg.kernel_size, self.cfg.window_size or 0)
         _lib.check(lib.us_encoder_create(C.byref(self._h), C.byref(c)), None, "us_encoder_create")
 
-    @torch.no_grad()
     def forward(self, x, x_lengths):
-        """x [B, L] symbol ids, x_lengths [B] -> (mu_x [B, n_feats, L], x [B, n_channels, L], x_mask [B, 1, L])."""
+        """x [B, L] symbol ids, x_lengths [B] -> (mu_x [B, n_feats, L], x [B, n_channels, L], x_mask [B, 1, L]).
+
+        With trainable=True in train mode: the training forward (dropout p = 0.5 in the prenet, p_dropout elsewhere, seeded from
+        torch's default generator), differentiable with respect to every parameter that requires grad."""
         if x.dim() != 2 or x_lengths.dim() != 1 or x_lengths.shape[0] != x.shape[0]:
             raise ValueError(f"Encoder: expected ids [B, L] and lengths [B], got {tuple(x.shape)} and {tuple(x_lengths.shape)}")
+        if self.training and self.trainable:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            params = list(self.state_dict(keep_vars=True).values())
+            return _EncoderTrain.apply(self, x, x_lengths, seed, float(self.p_dropout), *params)
+        return self._forward_eval(x, x_lengths)
+
+    @torch.no_grad()
+    def _forward_eval(self, x, x_lengths):
         device = x.device
         lib, stream = self._sync(device)
         b, l = x.shape
@@ -293,6 +309,63 @@ class Encoder(_FrontEndModule):
                                         ws.data_ptr(), ws.numel(), stream)
         self._check(lib, rc, "us_encoder_forward")
         return mu_x, h, mask
+
+
+def _release_tape(enc_ref, ptr):
+    enc = enc_ref()
+    if enc is not None and getattr(enc, "_h", None):
+        _lib.load().us_encoder_tape_release(enc._h, ptr)
+
+
+class _EncoderTrain(torch.autograd.Function):
+    """us_encoder_forward_train / us_encoder_backward.  Each call owns its workspace (the tape), kept in ctx until backward.
+    p < 0 runs without any dropout (the reference in eval mode, differentiated)."""
+
+    @staticmethod
+    def forward(ctx, enc, x, x_lengths, seed, p, *params):
+        device = x.device
+        lib, stream = enc._sync(device, training_ok=True)
+        b, l = x.shape
+        ids = x.to(torch.int64).contiguous()
+        lens = x_lengths.to(device=device, dtype=torch.int64).contiguous()
+        mu_x = torch.empty(b, enc.cfg.n_feats, l, device=device)
+        h = torch.empty(b, enc.cfg.n_channels, l, device=device)
+        mask = torch.empty(b, 1, l, device=device)
+        ws = torch.empty(int(lib.us_encoder_train_workspace_bytes(enc._h, b, l)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            rc = lib.us_encoder_forward_train(enc._h, ids.data_ptr(), lens.data_ptr(), mu_x.data_ptr(), h.data_ptr(), mask.data_ptr(), b, l,
+                                              p, seed, ws.data_ptr(), ws.numel(), stream)
+        enc._check(lib, rc, "us_encoder_forward_train")
+        ctx.enc, ctx.ws, ctx.shape = enc, ws, (b, l)
+        ctx.keys = list(enc.state_dict(keep_vars=True).keys())
+        ctx.versions = [(t.data_ptr(), t._version) for t in params]
+        # the handle forgets this tape when the workspace tensor goes (its memory may then hold anything)
+        weakref.finalize(ws, _release_tape, weakref.ref(enc), ws.data_ptr())
+        ctx.mark_non_differentiable(mask)
+        return mu_x, h, mask
+
+    @staticmethod
+    def backward(ctx, g_mu, g_x, _g_mask):
+        enc, ws, (b, l) = ctx.enc, ctx.ws, ctx.shape
+        params = list(enc.state_dict(keep_vars=True).values())
+        if [(t.data_ptr(), t._version) for t in params] != ctx.versions:
+            raise RuntimeError("Encoder backward: a parameter was modified in place after the training forward (the tape holds "
+                               "activations of the old weights); run the forward again")
+        device = ws.device
+        lib, stream = enc._sync(device, training_ok=True)
+        need = ctx.needs_input_grad[5:]
+        shapes = encoder_state_shapes(enc.cfg)
+        grads = [torch.empty(shapes[k], device=device) if n else None for k, n in zip(ctx.keys, need)]
+        sel = [(k, g) for k, g in zip(ctx.keys, grads) if g is not None]
+        keys = (C.c_char_p * max(len(sel), 1))(*[k.encode() for k, _ in sel])
+        ptrs = (C.c_void_p * max(len(sel), 1))(*[g.data_ptr() for _, g in sel])
+        f32 = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+        g_mu, g_x = f32(g_mu), f32(g_x)
+        with torch.cuda.device(device):
+            rc = lib.us_encoder_backward(enc._h, g_mu.data_ptr() if g_mu is not None else None, g_x.data_ptr() if g_x is not None else None,
+                                         b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(), stream)
+        enc._check(lib, rc, "us_encoder_backward")
+        return (None,) * 5 + tuple(grads)
 
 
 class DurationPredictor(_FrontEndModule):
