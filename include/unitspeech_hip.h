@@ -202,6 +202,25 @@ int us_finetune_segment_backward(const float* d_cond_y, const float* attn, const
  * [B,F,T], y_mask [B,1,T]; d_mu_y (optional) = its gradient w.r.t. mu_y.  One workgroup, fixed summation order: no scratch. */
 int us_prior_loss(const float* y, const float* mu_y, const float* y_mask, float* loss, float* d_mu_y, int B, int F, int T, us_stream stream);
 
+/* ---- text-to-speech training step (train_STEP1.py:307-387), csrc/tts_train.hip ------------------------------------------
+ * us_mas_log_prior: the log-prior of monotonic alignment search (:336-342) times maximum_path's mask: log_prior [B,Tx,Ty] =
+ *   (-0.5 sum_f y^2 + sum_f mu_x y - 0.5 sum_f mu_x^2 - 0.5 F log 2 pi) x_mask[b][x] y_mask[b][y] for mu_x [B,F,Tx], y [B,F,Ty],
+ *   x_mask [B,1,Tx], y_mask [B,1,Ty]; masked cells are 0.
+ * us_maximum_path: glow-tts `maximum_path` (:343) over log_prior [B,Tx,Ty] with tx = x_lengths[b], ty = y_lengths[b] (device,
+ *   int64, clamped to [0, Tx] / [0, Ty]): attn [B,Tx,Ty] fp32 0/1 (overwritten), durations [B,Tx] = row sums of attn.  The path is
+ *   bit-identical to the sequential algorithm (fp32 accumulation, -1e9 sentinels, strict comparison in the backtrack), also for
+ *   tx > ty.  Tx <= 1024.  The per-item decision table lives in LDS when it fits (Tx * ceil(Ty / 32) words, 512 x 2048 does);
+ *   otherwise the caller passes us_maximum_path_workspace_bytes of device scratch (0 when every item fits).  No host sync.
+ * us_duration_loss: loss[0] (device) = sum((logw - log(1e-8 + durations) x_mask)^2) / sum(x_lengths) over logw, x_mask [B,1,Tx],
+ *   durations [B,Tx] (:348-349); d_logw (optional) = its gradient w.r.t. logw.  One workgroup, fixed summation order. */
+int us_mas_log_prior(const float* mu_x, const float* y, const float* x_mask, const float* y_mask, float* log_prior, int B, int F, int Tx,
+                     int Ty, us_stream stream);
+size_t us_maximum_path_workspace_bytes(int B, int Tx, int Ty);
+int us_maximum_path(const float* log_prior, const int64_t* x_lengths, const int64_t* y_lengths, float* attn, float* durations, int B, int Tx,
+                    int Ty, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_duration_loss(const float* logw, const float* durations, const float* x_mask, const int64_t* x_lengths, float* loss, float* d_logw,
+                     int B, int Tx, us_stream stream);
+
 /* ---- conditioning producer of `execute_text_to_speech` (:424-438; the text encoder and duration predictor stay the
  * caller's modules) -----------------------------------------------------------------------------------------------------
  * us_tts_durations: w_ceil[B,L] = ceil(exp(logw) * x_mask) * length_scale, y_lengths[B] (int64) = max(sum_l w_ceil, 1).

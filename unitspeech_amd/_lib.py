@@ -97,6 +97,10 @@ SIGNATURES = {
     "us_encoder_tape_release": (C.c_int, [C.c_void_p, C.c_void_p]),
     "us_finetune_segment_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "us_prior_loss": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
+    "us_mas_log_prior": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "us_maximum_path_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "us_maximum_path": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_duration_loss": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.c_void_p]),
     "us_duration_predictor_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_vocoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_vocoder_config)]),
     "us_vocoder_destroy": (C.c_int, [C.c_void_p]),

@@ -87,3 +87,17 @@ def save_finetuned_checkpoint(path: str, decoder, spk_emb: torch.Tensor, mel_min
     out["mel_max"] = torch.as_tensor(mel_max).cpu()
     out["spk_emb"] = spk_emb.detach().cpu()
     torch.save(out, path)
+
+
+def save_pretrained_checkpoint(path: str, decoder, speaker_embeddings, mel_min, mel_max, iteration: int) -> None:
+    """`train_STEP1.py:297-304` (`pretrained_decoder.pt`): {"model": decoder.state_dict(), "spk_emb": the speaker Embedding's
+    state_dict ({"weight": [n_speakers, D]}), "mel_min", "mel_max", "iteration"}, in that order; `load_decoder_checkpoint` reads it
+    back.  `speaker_embeddings` is the `torch.nn.Embedding` (or its state_dict)."""
+    sd = speaker_embeddings.state_dict() if hasattr(speaker_embeddings, "state_dict") else speaker_embeddings
+    out: Dict[str, Any] = {}
+    out["model"] = OrderedDict((k, v.detach().cpu()) for k, v in decoder.state_dict().items())
+    out["spk_emb"] = OrderedDict((k, v.detach().cpu()) for k, v in sd.items())
+    out["mel_min"] = torch.as_tensor(mel_min).cpu()
+    out["mel_max"] = torch.as_tensor(mel_max).cpu()
+    out["iteration"] = int(iteration)
+    torch.save(out, path)

@@ -12,6 +12,10 @@ clip + update for all tensors in three HIP launches (`us_clip_adam_step`, csrc/o
     optimizer.step(max_norm=1)            # == clip_grad_norm_(params, 1) followed by Adam.step()
     optimizer.last_grad_norm              # device scalar: the total norm clip_grad_norm_ would have returned
 
+A parameter group may carry its own clip norm, `{"params": ..., "max_norm": 5.0}`: that group is clipped on its own total norm
+(train_STEP1.py:244-249 clips the text encoder at 5, the duration predictor at 5 and the decoder at 2, then takes one Adam step);
+the group's norm is kept in `last_grad_norms[group_index]`.  A group without the key uses step's `max_norm` argument.
+
 Only what the reference uses is supported: weight_decay=0, amsgrad=False, maximize=False, fp32 parameters on one ROCm device.
 There is no CPU fallback.
 """
@@ -31,6 +35,7 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad))
         self.lib = _lib.load()
         self.last_grad_norm = None
+        self.last_grad_norms = {}  # per group index: device scalar total norm of the group's last clipped step
         self._tables = {}          # per group: cached device tables keyed by the pointer tuple
         self._pinned = {}          # per group: pinned staging ring for the pointer table
 
@@ -101,16 +106,17 @@ class FusedAdam(torch.optim.Optimizer):
             for s in sts:
                 s["step"] += 1
             b1, b2 = group["betas"]
+            mn = group.get("max_norm", max_norm)
             ptrs = tab["ptrs"]
             with torch.cuda.device(dev):
                 rc = self.lib.us_clip_adam_step(ptrs[0].data_ptr(), ptrs[1].data_ptr(), ptrs[2].data_ptr(), ptrs[3].data_ptr(),
                                                 ptrs[4].data_ptr(), tab["blk_tensor"].data_ptr(), tab["blk_off"].data_ptr(), len(ps),
                                                 tab["n_blocks"], float(group["lr"]), float(b1), float(b2), float(group["eps"]), step,
-                                                float(max_norm) if max_norm is not None else 0.0, tab["partial"].data_ptr(),
+                                                float(mn) if mn is not None else 0.0, tab["partial"].data_ptr(),
                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             _lib.check(rc, None, "us_clip_adam_step")
-            if max_norm is not None:
-                self.last_grad_norm = tab["partial"][tab["n_blocks"]]
+            if mn is not None:
+                self.last_grad_norm = self.last_grad_norms[gi] = tab["partial"][tab["n_blocks"]]
             torch._C._increment_version(ps)        # the kernel wrote the parameters in place: let version-keyed caches (the HIP
                                                    # engine's weight sync) see it; takes an ITERABLE of tensors
         return loss

@@ -1,0 +1,117 @@
+"""The alignment side of the text-to-speech training step (`train_STEP1.py`'s `compute_train_step_loss`, :336-349) in library
+launches.
+
+`mas_log_prior` is the Gaussian log-prior between the encoder's mu_x and the mel (:336-342, masked as `maximum_path` masks it),
+`maximum_path` a drop-in for the external `monotonic_align.maximum_path` (:343) that runs on the device and never copies the
+[B, Tx, Ty] table to the host, `align` both in one call with the durations MAS implies, and `duration_loss` the MSE of the log
+durations (:348-349, `util.duration_loss` after `log(1e-8 + sum(attn))`), differentiable in logw.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+
+__all__ = ["mas_log_prior", "maximum_path", "maximum_path_lengths", "align", "duration_loss"]
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _f32(t, dev):
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _i64(t, dev):
+    return t.detach().to(device=dev, dtype=torch.int64).contiguous()
+
+
+@torch.no_grad()
+def mas_log_prior(mu_x, y, x_mask, y_mask):
+    """mu_x [B, F, Tx], y [B, F, Ty], x_mask [B, 1, Tx], y_mask [B, 1, Ty] -> log_prior [B, Tx, Ty] fp32:
+    (-0.5 sum_f y^2 + sum_f mu_x y - 0.5 sum_f mu_x^2 - 0.5 F log 2 pi) x_mask y_mask."""
+    dev = mu_x.device
+    B, F, Tx = mu_x.shape
+    Ty = y.shape[-1]
+    if y.shape[:2] != (B, F) or tuple(x_mask.shape) != (B, 1, Tx) or tuple(y_mask.shape) != (B, 1, Ty):
+        raise ValueError(f"mas_log_prior: mu_x {tuple(mu_x.shape)}, y {tuple(y.shape)}, x_mask {tuple(x_mask.shape)}, "
+                         f"y_mask {tuple(y_mask.shape)} do not agree")
+    mu, yy, xm, ym = _f32(mu_x, dev), _f32(y, dev), _f32(x_mask, dev), _f32(y_mask, dev)
+    out = torch.empty(B, Tx, Ty, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().us_mas_log_prior(mu.data_ptr(), yy.data_ptr(), xm.data_ptr(), ym.data_ptr(), out.data_ptr(), B, F, Tx, Ty, _stream())
+    _lib.check(rc, None, "us_mas_log_prior")
+    return out
+
+
+@torch.no_grad()
+def maximum_path_lengths(log_prior, x_lengths, y_lengths):
+    """log_prior [B, Tx, Ty] with per-item lengths -> (attn [B, Tx, Ty] fp32 0/1, durations [B, Tx] fp32).  With int64 device
+    lengths nothing crosses to or from the host; host lengths are copied to the device first (a synchronous upload)."""
+    dev = log_prior.device
+    B, Tx, Ty = log_prior.shape
+    lp, xl, yl = _f32(log_prior, dev), _i64(x_lengths, dev), _i64(y_lengths, dev)
+    if xl.shape != (B,) or yl.shape != (B,):
+        raise ValueError(f"maximum_path: lengths {tuple(xl.shape)} / {tuple(yl.shape)} must hold {B} values")
+    lib = _lib.load()
+    attn = torch.empty(B, Tx, Ty, device=dev)
+    dur = torch.empty(B, Tx, device=dev)
+    n = int(lib.us_maximum_path_workspace_bytes(B, Tx, Ty))
+    ws = torch.empty(n, dtype=torch.uint8, device=dev) if n else None        # 0 while every item's table fits in LDS
+    with torch.cuda.device(dev):
+        rc = lib.us_maximum_path(lp.data_ptr(), xl.data_ptr(), yl.data_ptr(), attn.data_ptr(), dur.data_ptr(), B, Tx, Ty,
+                                 ws.data_ptr() if n else None, n, _stream())
+    _lib.check(rc, None, "us_maximum_path")
+    return attn, dur
+
+
+@torch.no_grad()
+def maximum_path(value, mask):
+    """Drop-in for `monotonic_align.maximum_path(value, mask)` (train_STEP1.py:343): value, mask [B, Tx, Ty] -> path [B, Tx, Ty]
+    0/1 in value's dtype.  tx / ty are read off the mask's first column / row, as the reference does; the cells the algorithm
+    reads all lie inside the mask, so value is not multiplied by it here."""
+    if value.dim() != 3 or mask.shape != value.shape:
+        raise ValueError(f"maximum_path: value {tuple(value.shape)} and mask {tuple(mask.shape)} must both be [B, Tx, Ty]")
+    tx = mask.sum(1)[:, 0].to(torch.int64)
+    ty = mask.sum(2)[:, 0].to(torch.int64)
+    attn, _ = maximum_path_lengths(value, tx, ty)
+    return attn.to(value.dtype)
+
+
+@torch.no_grad()
+def align(mu_x, y, x_mask, y_mask, x_lengths, y_lengths):
+    """train_STEP1.py:336-345 -> (attn [B, Tx, Ty], durations [B, Tx]): the MAS alignment of the mel to mu_x and its row sums."""
+    return maximum_path_lengths(mas_log_prior(mu_x, y, x_mask, y_mask), x_lengths, y_lengths)
+
+
+class _DurationLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logw, durations, x_mask, x_lengths):
+        dev = logw.device
+        B, Tx = durations.shape
+        if logw.numel() != B * Tx or x_mask.numel() != B * Tx:
+            raise ValueError(f"duration_loss: logw {tuple(logw.shape)}, x_mask {tuple(x_mask.shape)} and durations [B, Tx] = "
+                             f"{(B, Tx)} do not agree")
+        if logw.dtype != torch.float32:
+            raise TypeError(f"duration_loss: logw must be fp32 (the loss and its gradient are computed in fp32), got {logw.dtype}")
+        lw, d, m, xl = _f32(logw, dev), _f32(durations, dev), _f32(x_mask, dev), _i64(x_lengths, dev)
+        loss = torch.empty((), device=dev)
+        d_logw = torch.empty_like(lw)
+        with torch.cuda.device(dev):
+            rc = _lib.load().us_duration_loss(lw.data_ptr(), d.data_ptr(), m.data_ptr(), xl.data_ptr(), loss.data_ptr(), d_logw.data_ptr(),
+                                              B, Tx, _stream())
+        _lib.check(rc, None, "us_duration_loss")
+        ctx.save_for_backward(d_logw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_logw,) = ctx.saved_tensors
+        return d_logw * g, None, None, None
+
+
+def duration_loss(logw, durations, x_mask, x_lengths):
+    """train_STEP1.py:348-349: sum((logw - log(1e-8 + durations) x_mask)^2) / sum(x_lengths) with logw, x_mask [B, 1, Tx] and
+    durations [B, Tx] (the row sums of MAS's attn); differentiable in logw, which must be fp32."""
+    return _DurationLossFn.apply(logw, durations, x_mask, x_lengths)
