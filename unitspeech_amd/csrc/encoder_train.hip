@@ -1,5 +1,6 @@
 // Training side of the text / unit `Encoder` (unitspeech/encoder.py:253-308 in train mode): a forward with every Dropout of
-// the reference, and the backward to every state_dict key.
+// the reference, and the backward to every state_dict key.  The forward's schedule and its embedding, LayerNorm, attention and
+// layout kernels are frontend.hip's (encoder_forward in training mode); this file holds its convolution, the tape and the backward.
 //
 // Layout: activations channel-last [B][L][C] (row = b * L + l), as in frontend.hip.  Every convolution (the prenet's k = 5,
 // the FFN's k = kernel_size, the 1x1 q / k / v / o / proj / proj_m) is one implicit GEMM on the fp32 matrix cores
@@ -33,43 +34,6 @@ namespace us {
 namespace {
 
 typedef float et_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kPrenet = 3, kPrenetK = 5;                 // encoder.py:283-284
-constexpr float kPrenetP = 0.5f;                         // encoder.py:285-286
-constexpr int kSitesPerLayer = 4;
-enum { kSiteAttnP = 0, kSiteAttnOut = 1, kSiteFfnRelu = 2, kSiteFfnOut = 3 };
-
-// ---- dropout stream ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void et_philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-
-struct Drop {
-  unsigned long long seed;
-  int site;          // < 0: no dropout
-  float p, scale;
-};
-
-// the factor element `idx` of a site is multiplied by: 0 or 1 / (1 - p); 1 when p == 0 or there is no site
-__device__ __forceinline__ float et_keep(const Drop& d, unsigned long long idx) {
-  if (d.site < 0 || d.p <= 0.f) return 1.f;
-  uint32_t c[4] = {(uint32_t)(idx >> 2), (uint32_t)(idx >> 34), (uint32_t)d.site, 0u};
-  et_philox(c, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
-  const uint32_t w = c[idx & 3];
-  return (float)(w >> 8) * 5.9604644775390625e-08f >= d.p ? d.scale : 0.f;      // uniform in [0, 1) on a 2^-24 grid
-}
-// flat index of channel-last element (row, c) in the reference's [B][C][L] tensor
-__device__ __forceinline__ unsigned long long et_cf_index(long long row, int c, int C, int L) {
-  const long long b = row / L, l = row - b * L;
-  return ((unsigned long long)b * C + c) * L + l;
-}
 
 // ---- implicit-GEMM convolution on the fp32 matrix cores ----------------------------------------------------------------
 constexpr int kBM = 64, kBN = 64, kBK = 16;
@@ -251,20 +215,7 @@ __global__ void et_colsum_finish_kernel(const float* part, float* out, int N, in
   out[c] = s * scale;
 }
 
-// ---- embedding, mask, layout -------------------------------------------------------------------------------------------
-__global__ void et_embed_kernel(const long long* ids, const long long* lengths, const float* emb, float* x0, long long* ids_tape,
-                                float* mask, int n_vocab, int C, int L, float scale) {
-  const long long row = blockIdx.x;
-  const long long id = ids[row];
-  const bool ok = id >= 0 && id < n_vocab;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) x0[row * C + c] = ok ? mul_rn(emb[id * C + c], scale) : __builtin_nanf("");
-  if (threadIdx.x == 0) {
-    ids_tape[row] = id;
-    const long long b = row / L;
-    mask[row] = (row - b * L) < lengths[b] ? 1.f : 0.f;
-  }
-}
-
+// ---- embedding gradient, layout --------------------------------------------------------------------------------------
 // emb_grad[v][:] = scale * sum over rows (in order) with ids[row] == v of dx0[row][:]
 __global__ __launch_bounds__(256) void et_embed_grad_kernel(const long long* ids, const float* dx0, float* grad, long long rows, int C,
                                                             float scale) {
@@ -285,36 +236,21 @@ __global__ __launch_bounds__(256) void et_embed_grad_kernel(const long long* ids
   }
 }
 
-// channel-last [B][L][C] <-> channel-first [B][C][L], optionally times mask[b][l]
-template <bool kToFirst>
-__global__ void et_transpose_kernel(const float* in, const float* mask, float* out, int L, int C) {
+// channel-first [B][C][L] (the caller's gradients) -> channel-last [B][L][C], optionally times mask[b][l]
+__global__ void et_to_channel_last_kernel(const float* in, const float* mask, float* out, int L, int C) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-    if (kToFirst) {
-      const int l = l0 + r, c = c0 + threadIdx.x;
-      tile[r][threadIdx.x] = (l < L && c < C) ? in[((long long)b * L + l) * C + c] : 0.f;
-    } else {
-      const int c = c0 + r, l = l0 + threadIdx.x;
-      tile[threadIdx.x][r] = (l < L && c < C) ? in[((long long)b * C + c) * L + l] : 0.f;
-    }
+    const int c = c0 + r, l = l0 + threadIdx.x;
+    tile[threadIdx.x][r] = (l < L && c < C) ? in[((long long)b * C + c) * L + l] : 0.f;
   }
   __syncthreads();
   for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-    if (kToFirst) {
-      const int c = c0 + r, l = l0 + threadIdx.x;
-      if (l < L && c < C) {
-        float v = tile[threadIdx.x][r];
-        if (mask) v *= mask[(long long)b * L + l];
-        out[((long long)b * C + c) * L + l] = v;
-      }
-    } else {
-      const int l = l0 + r, c = c0 + threadIdx.x;
-      if (l < L && c < C) {
-        float v = tile[r][threadIdx.x];
-        if (mask) v *= mask[(long long)b * L + l];
-        out[((long long)b * L + l) * C + c] = v;
-      }
+    const int l = l0 + r, c = c0 + threadIdx.x;
+    if (l < L && c < C) {
+      float v = tile[r][threadIdx.x];
+      if (mask) v *= mask[(long long)b * L + l];
+      out[((long long)b * L + l) * C + c] = v;
     }
   }
 }
@@ -337,60 +273,8 @@ __global__ void et_mask_out_kernel(float* out, long long n, Drop d) {
     out[i] = et_keep(d, (unsigned long long)i);
 }
 
-// ---- LayerNorm (eps 1e-4, encoder.py:21-30) ----------------------------------------------------------------------------
+// ---- LayerNorm backward (eps 1e-4, encoder.py:21-30) -------------------------------------------------------------------
 constexpr int kLnPerLane = 16;      // C <= 1024
-struct LnFwdArgs {
-  const float* in;
-  const float* add; Drop add_drop;    // n = in + drop(add) (add may be null)
-  float* sum_out;                     // n is stored here (the backward's LayerNorm input), or null
-  const float* gamma; const float* beta;
-  int relu; Drop out_drop;            // y = drop(relu(LN(n))) (prenet relu_drop)
-  const float* mask;                  // y *= mask[row], or null
-  float* out;
-  int C, L; float eps;
-};
-__global__ __launch_bounds__(64) void et_ln_fwd_kernel(LnFwdArgs a) {
-  const long long row = blockIdx.x;
-  const int lane = threadIdx.x;
-  float v[kLnPerLane];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kLnPerLane; ++i) {
-    const int c = lane + 64 * i;
-    v[i] = 0.f;
-    if (c < a.C) {
-      v[i] = a.in[row * a.C + c];
-      if (a.add) v[i] = add_rn(v[i], a.add[row * a.C + c] * et_keep(a.add_drop, et_cf_index(row, c, a.C, a.L)));
-      if (a.sum_out) a.sum_out[row * a.C + c] = v[i];
-      s += v[i];
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  const float mean = s / (float)a.C;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < kLnPerLane; ++i) {
-    const int c = lane + 64 * i;
-    if (c < a.C) { const float d = sub_rn(v[i], mean); q = __builtin_fmaf(d, d, q); }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  const float rstd = 1.f / sqrtf(add_rn(q / (float)a.C, a.eps));
-  const float m = a.mask ? a.mask[row] : 1.f;
-#pragma unroll
-  for (int i = 0; i < kLnPerLane; ++i) {
-    const int c = lane + 64 * i;
-    if (c < a.C) {
-      float y = add_rn(mul_rn(mul_rn(sub_rn(v[i], mean), rstd), a.gamma[c]), a.beta[c]);
-      if (a.relu) y = y > 0.f ? y : 0.f;
-      if (a.out_drop.site >= 0) y *= et_keep(a.out_drop, et_cf_index(row, c, a.C, a.L));
-      if (a.mask) y *= m;
-      a.out[row * a.C + c] = y;
-    }
-  }
-}
-
 // dx of y = LN(x) for upstream dy; with `gate` (the stored prenet output drop(relu(y))), dy is first taken through the dropout
 // and the ReLU: dy = gate > 0 ? dy * gate_scale : 0.  dyx[row][c] = dy * xhat and dyo[row][c] = dy feed the gamma / beta sums.
 struct LnBwdArgs {
@@ -456,95 +340,7 @@ __global__ __launch_bounds__(64) void et_ln_bwd_kernel(LnBwdArgs a) {
   }
 }
 
-// ---- relative-position self-attention (encoder.py:115-144) --------------------------------------------------------------
-struct AttnArgs {
-  const float* q; const float* k; const float* v;     // [B][L][C], head h owns channels [h * D, (h + 1) * D)
-  const float* rel_k; const float* rel_v;             // [2W+1][D] or null
-  const float* mask;                                  // [B][L]
-  float* P;                                           // [B][H][L][L] softmax probabilities before dropout
-  float* out;                                         // [B][L][C]
-  // backward
-  const float* dO;                                    // [B][L][C] gradient of `out`
-  float* DS;                                          // [B][H][L][L] gradient of the scores (0 where filled with -1e4)
-  float* dq; float* dk; float* dv;                    // [B][L][C]
-  double* rel_part;                                   // [2][B][2W+1][D]
-  int L, C, D, H, W;
-  float sqrt_d;
-  Drop drop;                                          // dropout of p_attn, flat index of [B][H][L][L]
-};
-
-// one (query i, head, item): score[j] = q_i.k_j / sqrt(D) + [|j-i| <= W] q_i.rel_k[j-i+W] / sqrt(D), -1e4 where mask_i mask_j == 0,
-// p = softmax (stored), pd = drop(p); out = sum_j pd[j] v_j + sum_{|d| <= W} pd[i+d] rel_v[d+W]
-__global__ void __launch_bounds__(128) et_attn_fwd_kernel(AttnArgs a) {
-  extern __shared__ float sm[];          // p[L], q[D], red[128]
-  float* p = sm;
-  float* qs = sm + a.L;
-  float* red = qs + a.D;
-  const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const long long base = (long long)b * a.L * a.C + (long long)h * a.D;
-  const long long prow = (((long long)b * a.H + h) * a.L + i) * a.L;
-  for (int d = tid; d < a.D; d += blockDim.x) qs[d] = a.q[base + (long long)i * a.C + d];
-  __syncthreads();
-  const float mi = a.mask[(long long)b * a.L + i];
-  float mx = -INFINITY;
-  for (int j = tid; j < a.L; j += blockDim.x) {
-    const float* kj = a.k + base + (long long)j * a.C;
-    float s = 0.f;
-    for (int d = 0; d < a.D; ++d) s = __builtin_fmaf(qs[d], kj[d], s);
-    s = s / a.sqrt_d;
-    const int off = j - i;
-    if (a.rel_k && off >= -a.W && off <= a.W) {
-      const float* rk = a.rel_k + (long long)(off + a.W) * a.D;
-      float r = 0.f;
-      for (int d = 0; d < a.D; ++d) r = __builtin_fmaf(qs[d], rk[d], r);
-      s = add_rn(s, r / a.sqrt_d);
-    }
-    if (mi * a.mask[(long long)b * a.L + j] == 0.f) s = -1e4f;
-    p[j] = s;
-    mx = fmaxf(mx, s);
-  }
-  red[tid] = mx;
-  __syncthreads();
-  for (int o = 64; o > 0; o >>= 1) {
-    if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
-    __syncthreads();
-  }
-  mx = red[0];
-  __syncthreads();
-  float sum = 0.f;
-  for (int j = tid; j < a.L; j += blockDim.x) {
-    const float e = expf(p[j] - mx);
-    p[j] = e;
-    sum += e;
-  }
-  red[tid] = sum;
-  __syncthreads();
-  for (int o = 64; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  sum = red[0];
-  for (int j = tid; j < a.L; j += blockDim.x) {
-    const float pj = p[j] / sum;
-    a.P[prow + j] = pj;
-    p[j] = pj * et_keep(a.drop, (unsigned long long)(prow + j));
-  }
-  __syncthreads();
-  for (int d = tid; d < a.D; d += blockDim.x) {
-    float o1 = 0.f;
-    for (int j = 0; j < a.L; ++j) o1 = __builtin_fmaf(p[j], a.v[base + (long long)j * a.C + d], o1);
-    if (a.rel_v) {
-      float o2 = 0.f;
-      for (int off = -a.W; off <= a.W; ++off) {
-        const int j = i + off;
-        if (j >= 0 && j < a.L) o2 = __builtin_fmaf(p[j], a.rel_v[(long long)(off + a.W) * a.D + d], o2);
-      }
-      o1 = add_rn(o1, o2);
-    }
-    a.out[base + (long long)i * a.C + d] = o1;
-  }
-}
-
+// ---- relative-position self-attention backward (encoder.py:115-144; AttnArgs and the forward kernel: frontend.h / .hip) ------
 // backward, one (query i, head, item): dpd[j] = dO_i.v_j (+ dO_i.rel_v[j-i+W] in the band), dp = dpd * keep,
 // ds[j] = p[j] (dp[j] - sum_k p[k] dp[k]) (0 where the score was filled: no gradient flows through -1e4); dq_i from ds
 __global__ void __launch_bounds__(128) et_attn_bwd_q_kernel(AttnArgs a) {
@@ -659,12 +455,6 @@ __global__ void et_rel_finish_kernel(const double* part, float* grad_v, float* g
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-int et_fail(us_frontend* h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  set_last_error(msg.c_str());
-  return code;
-}
-
 unsigned et_blocks(long long n, int threads) {
   const long long b = (n + threads - 1) / threads;
   return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -672,7 +462,7 @@ unsigned et_blocks(long long n, int threads) {
 
 // workspace layout of one training forward (the tape) and of its backward, in floats from a 256-byte aligned base
 struct Layout {
-  size_t ids, mask, x0, pc[kPrenet], pa[kPrenet], mu, xf;
+  size_t ids, mask, x0, pc[kPrenetLayers], pa[kPrenetLayers], mu, xf;
   std::vector<size_t> x, q, k, v, at, n1, x1, n2, hd, p;        // per transformer layer
   size_t tape_end;
   size_t g, t, d1, dh, dyx, dyo, dq, dk, dv, ds, wd, wpart, cpart, rpart, arena;
@@ -681,7 +471,7 @@ struct Layout {
 };
 
 size_t conv_numel(const us_encoder_config& c) {      // largest convolution weight
-  size_t m = (size_t)c.n_channels * c.n_channels * kPrenetK;
+  size_t m = (size_t)c.n_channels * c.n_channels * kPrenetKernel;
   m = std::max(m, (size_t)c.filter_channels * c.n_channels * c.kernel_size);
   m = std::max(m, (size_t)c.n_feats * c.n_channels);
   return m;
@@ -702,8 +492,8 @@ Layout et_layout(const us_frontend* h, int B, int L) {
   o.ids = take(2 * rows);
   o.mask = take(rows);
   o.x0 = take(plane);
-  for (int i = 0; i < kPrenet; ++i) o.pc[i] = take(plane);
-  for (int i = 0; i < kPrenet; ++i) o.pa[i] = take(plane);
+  for (int i = 0; i < kPrenetLayers; ++i) o.pc[i] = take(plane);
+  for (int i = 0; i < kPrenetLayers; ++i) o.pa[i] = take(plane);
   for (int i = 0; i < c.n_layers; ++i) {
     o.x.push_back(take(plane)); o.q.push_back(take(plane)); o.k.push_back(take(plane)); o.v.push_back(take(plane));
     o.at.push_back(take(plane)); o.n1.push_back(take(plane)); o.x1.push_back(take(plane)); o.n2.push_back(take(plane));
@@ -741,17 +531,6 @@ struct Ctx {
 
 const float* wdev(us_frontend* h, const std::string& k) { return h->w[k].dev; }
 
-void conv_fwd(const Ctx& x, const std::string& key, const float* in, float* out, bool mask_in, bool relu, bool mask_out,
-              const float* add, Drop drop) {
-  const Weight& w = x.h->w[key + ".weight"];
-  GemmArgs a{};
-  a.in = in; a.mask = x.mask; a.mask_in = mask_in;
-  a.rows = (int)x.rows; a.L = x.L; a.N = (int)w.shape[0]; a.Cin = (int)w.shape[1]; a.K = (int)w.shape[2]; a.pad = a.K / 2;
-  a.w = w.packed; a.bias = wdev(x.h, key + ".bias"); a.add = add; a.out = out; a.relu = relu; a.mask_out = mask_out;
-  a.drop = drop;
-  hipLaunchKernelGGL(et_gemm_kernel<false>, dim3((x.rows + kBM - 1) / kBM, (a.N + kBN - 1) / kBN), dim3(256), 0, x.s, a);
-}
-
 // din = (add + dgrad(dout)) [gated] [* mask]; dW, db of the convolution `key` whose forward input was `in` (read times mask when
 // mask_in); dw / db are the destinations in torch layout
 void conv_bwd(const Ctx& x, const std::string& key, const float* in, bool mask_in, const float* dout, float* din, const float* add,
@@ -783,16 +562,6 @@ void conv_bwd(const Ctx& x, const std::string& key, const float* in, bool mask_i
   hipLaunchKernelGGL(et_gemm_kernel<false>, dim3((x.rows + kBM - 1) / kBM, (Cin + kBN - 1) / kBN), dim3(256), 0, x.s, a);
 }
 
-void ln_fwd(const Ctx& x, const std::string& key, const float* in, const float* add, Drop add_drop, float* sum_out, bool relu,
-            Drop out_drop, const float* mask, float* out) {
-  LnFwdArgs a{};
-  a.in = in; a.add = add; a.add_drop = add_drop; a.sum_out = sum_out;
-  a.gamma = wdev(x.h, key + ".gamma"); a.beta = wdev(x.h, key + ".beta");
-  a.relu = relu; a.out_drop = out_drop; a.mask = mask; a.out = out;
-  a.C = x.h->ec.n_channels; a.L = x.L; a.eps = 1e-4f;
-  hipLaunchKernelGGL(et_ln_fwd_kernel, dim3((unsigned)x.rows), dim3(64), 0, x.s, a);
-}
-
 void ln_bwd(const Ctx& x, const std::string& key, const float* in, const float* dy, const float* gate, float gate_scale, float* dx,
             float* dgamma, float* dbeta) {
   const Layout& l = *x.lay;
@@ -806,14 +575,6 @@ void ln_bwd(const Ctx& x, const std::string& key, const float* in, const float* 
   hipLaunchKernelGGL(et_colsum_kernel, dim3((C + 63) / 64, kColChunks), dim3(256), 0, x.s, x.f(l.dyo), x.f(l.cpart), (int)x.rows, C);
   hipLaunchKernelGGL(et_colsum_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, x.s, x.f(l.cpart), dbeta, C, kColChunks, 1.f);
 }
-
-Drop make_drop(uint64_t seed, int site, float p) {
-  Drop d{};
-  d.seed = seed; d.site = p > 0.f ? site : -1; d.p = p; d.scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  return d;
-}
-Drop no_drop() { return make_drop(0, -1, 0.f); }
-int layer_site(int layer, int which) { return kPrenet + kSitesPerLayer * layer + which; }
 
 AttnArgs attn_args(const Ctx& x, int i) {
   const auto& c = x.h->ec;
@@ -829,22 +590,31 @@ AttnArgs attn_args(const Ctx& x, int i) {
 }
 
 int et_check(us_frontend* h, const char* what, int B, int L) {
-  if (!h || h->kind != 0) return et_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
-  if (B <= 0 || L <= 0 || B > 65535 || L > 65535) return et_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
-  for (const auto& k : h->keys)
-    if (!h->w[k].loaded) return et_fail(h, US_EWEIGHTS, std::string(what) + ": weight '" + k + "' has not been loaded");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
-    return et_fail(h, US_EINVAL, std::string(what) + ": the current device is not the handle's");
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  if (B <= 0 || L <= 0 || B > 65535 || L > 65535) return fe_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
+  const int rc = fe_check(h, what);
+  if (rc != US_OK) return rc;
   const int D = h->ec.n_channels / h->ec.n_heads;
   if (((size_t)2 * L + D + 128) * sizeof(float) > 64 * 1024)
-    return et_fail(h, US_EINVAL, std::string(what) + ": more than ~8000 symbols per utterance");
+    return fe_fail(h, US_EINVAL, std::string(what) + ": more than ~8000 symbols per utterance");
   return US_OK;
 }
 
 float* et_base(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
 
 }  // namespace
+
+void gemm_conv_fwd(us_frontend* h, hipStream_t s, const std::string& key, const float* in, float* out, const float* mask, const float* add,
+                   long long rows, int L, bool mask_in, bool relu, bool mask_out, Drop drop) {
+  const Weight& w = h->w[key + ".weight"];
+  GemmArgs a{};
+  a.in = in; a.mask = mask; a.mask_in = mask_in;
+  a.rows = (int)rows; a.L = L; a.N = (int)w.shape[0]; a.Cin = (int)w.shape[1]; a.K = (int)w.shape[2]; a.pad = a.K / 2;
+  a.w = w.packed; a.bias = wdev(h, key + ".bias"); a.add = add; a.out = out; a.relu = relu; a.mask_out = mask_out;
+  a.drop = drop;
+  hipLaunchKernelGGL(et_gemm_kernel<false>, dim3((rows + kBM - 1) / kBM, (a.N + kBN - 1) / kBN), dim3(256), 0, s, a);
+}
+
 }  // namespace us
 
 extern "C" {
@@ -860,58 +630,29 @@ int us_encoder_forward_train(us_frontend_handle h, const int64_t* ids, const int
                              int B, int L, float p_dropout, uint64_t seed, void* workspace, size_t workspace_bytes, us_stream stream) {
   int rc = et_check(h, "us_encoder_forward_train", B, L);
   if (rc != US_OK) return rc;
-  if (!ids || !lengths || !mu_x || !x_out || !x_mask) return et_fail(h, US_EINVAL, "us_encoder_forward_train: null argument");
-  if (!(p_dropout < 1.f)) return et_fail(h, US_EINVAL, "us_encoder_forward_train: p_dropout must be below 1");
+  if (!ids || !lengths || !mu_x || !x_out || !x_mask) return fe_fail(h, US_EINVAL, "us_encoder_forward_train: null argument");
+  if (!(p_dropout < 1.f)) return fe_fail(h, US_EINVAL, "us_encoder_forward_train: p_dropout must be below 1");
   const bool no_dropout = p_dropout < 0.f;         // the reference in eval mode (autograd still runs): no site drops
   if (!workspace || workspace_bytes < us_encoder_train_workspace_bytes(h, B, L))
-    return et_fail(h, US_EWORKSPACE, "us_encoder_forward_train: workspace too small (us_encoder_train_workspace_bytes)");
+    return fe_fail(h, US_EWORKSPACE, "us_encoder_forward_train: workspace too small (us_encoder_train_workspace_bytes)");
   const auto& c = h->ec;
   const Layout l = et_layout(h, B, L);
   Ctx x{h, static_cast<hipStream_t>(stream), et_base(workspace), &l, B, L, (long long)B * L, nullptr};
   x.mask = x.f(l.mask);
-  const int C = c.n_channels;
-  hipLaunchKernelGGL(et_embed_kernel, dim3((unsigned)x.rows), dim3(C >= 256 ? 256 : 64), 0, x.s, reinterpret_cast<const long long*>(ids),
-                     reinterpret_cast<const long long*>(lengths), wdev(h, "emb.weight"), x.f(l.x0),
-                     reinterpret_cast<long long*>(x.f(l.ids)), x.mask, c.n_vocab, C, L, sqrtf((float)C));
-  // prenet (ConvReluNorm, encoder.py:58-65): c_i = conv(a_{i-1} * mask), a_i = drop(relu(LN(c_i))); (x0 + proj(a_2)) * mask
-  const float* cur = x.f(l.x0);
-  for (int i = 0; i < kPrenet; ++i) {
-    const std::string n = std::to_string(i);
-    conv_fwd(x, "prenet.conv_layers." + n, cur, x.f(l.pc[i]), true, false, false, nullptr, no_drop());
-    ln_fwd(x, "prenet.norm_layers." + n, x.f(l.pc[i]), nullptr, no_drop(), nullptr, true, make_drop(seed, i, no_dropout ? 0.f : kPrenetP),
-           nullptr, x.f(l.pa[i]));
-    cur = x.f(l.pa[i]);
-  }
-  const float p = no_dropout ? 0.f : p_dropout;
-  for (int i = 0; i < c.n_layers; ++i) {
-    float* xin = x.f(l.x[i]);
-    if (i == 0) conv_fwd(x, "prenet.proj", cur, xin, false, false, true, x.f(l.x0), no_drop());
-    const std::string ap = "encoder.attn_layers." + std::to_string(i), n = std::to_string(i);
-    conv_fwd(x, ap + ".conv_q", xin, x.f(l.q[i]), false, false, false, nullptr, no_drop());
-    conv_fwd(x, ap + ".conv_k", xin, x.f(l.k[i]), false, false, false, nullptr, no_drop());
-    conv_fwd(x, ap + ".conv_v", xin, x.f(l.v[i]), false, false, false, nullptr, no_drop());
-    AttnArgs a = attn_args(x, i);
-    a.drop = make_drop(seed, layer_site(i, kSiteAttnP), p);
-    hipLaunchKernelGGL(et_attn_fwd_kernel, dim3(L, c.n_heads, B), dim3(128), ((size_t)L + a.D + 128) * sizeof(float), x.s, a);
-    float* y = x.f(l.g);       // conv_o / conv_2 output: backward scratch, free during the forward
-    conv_fwd(x, ap + ".conv_o", x.f(l.at[i]), y, false, false, false, nullptr, no_drop());
-    ln_fwd(x, "encoder.norm_layers_1." + n, xin, y, make_drop(seed, layer_site(i, kSiteAttnOut), p), x.f(l.n1[i]), false, no_drop(),
-           nullptr, x.f(l.x1[i]));
-    const std::string fp = "encoder.ffn_layers." + n;
-    conv_fwd(x, fp + ".conv_1", x.f(l.x1[i]), x.f(l.hd[i]), true, true, false, nullptr, make_drop(seed, layer_site(i, kSiteFfnRelu), p));
-    conv_fwd(x, fp + ".conv_2", x.f(l.hd[i]), y, true, false, true, nullptr, no_drop());
-    float* next = i + 1 < c.n_layers ? x.f(l.x[i + 1]) : x.f(l.xf);
-    ln_fwd(x, "encoder.norm_layers_2." + n, x.f(l.x1[i]), y, make_drop(seed, layer_site(i, kSiteFfnOut), p), x.f(l.n2[i]), false,
-           no_drop(), x.mask, next);
-  }
-  if (c.n_layers == 0) conv_fwd(x, "prenet.proj", cur, x.f(l.xf), false, false, true, x.f(l.x0), no_drop());
-  conv_fwd(x, "proj_m", x.f(l.xf), x.f(l.mu), false, false, true, nullptr, no_drop());
-  hipLaunchKernelGGL(et_transpose_kernel<true>, dim3((L + 31) / 32, (c.n_feats + 31) / 32, B), dim3(32, 8), 0, x.s, x.f(l.mu), nullptr,
-                     mu_x, L, c.n_feats);
-  hipLaunchKernelGGL(et_transpose_kernel<true>, dim3((L + 31) / 32, (C + 31) / 32, B), dim3(32, 8), 0, x.s, x.f(l.xf), nullptr, x_out, L, C);
+  // the tape: one slot per entry and layer (Layout); conv_o / conv_2's output goes to backward scratch, free during the forward
+  EncoderBufs b{};
+  b.mask = x.mask; b.ids_tape = reinterpret_cast<long long*>(x.f(l.ids)); b.x0 = x.f(l.x0);
+  for (int i = 0; i < kPrenetLayers; ++i) { b.pc[i] = x.f(l.pc[i]); b.pa[i] = x.f(l.pa[i]); }
+  b.y = x.f(l.g); b.xf = x.f(l.xf); b.mu = x.f(l.mu);
+  for (int i = 0; i < c.n_layers; ++i)
+    b.layer.push_back({x.f(l.x[i]), x.f(l.q[i]), x.f(l.k[i]), x.f(l.v[i]), x.f(l.at[i]), x.f(l.n1[i]), x.f(l.x1[i]), x.f(l.hd[i]),
+                       x.f(l.n2[i]), x.f(l.p[i])});
+  EncoderMode m;
+  m.train = true; m.seed = seed; m.p = no_dropout ? 0.f : p_dropout; m.p_prenet = no_dropout ? 0.f : kPrenetP;
+  if ((rc = encoder_forward(h, x.s, b, m, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
   hipError_t e = hipMemcpyAsync(x_mask, x.mask, (size_t)x.rows * sizeof(float), hipMemcpyDeviceToDevice, x.s);
   if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return et_fail(h, US_EHIP, std::string("us_encoder_forward_train: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fe_fail(h, US_EHIP, std::string("us_encoder_forward_train: ") + hipGetErrorString(e));
   EncoderTape t;
   t.B = B; t.L = L; t.p_dropout = p_dropout; t.seed = seed;
   h->tapes[workspace] = t;
@@ -925,8 +666,8 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
   auto it = h->tapes.find(workspace);
   if (!workspace || it == h->tapes.end() || it->second.B != B || it->second.L != L ||
       workspace_bytes < us_encoder_train_workspace_bytes(h, B, L))
-    return et_fail(h, US_EINVAL, "us_encoder_backward: the workspace holds no us_encoder_forward_train of this B and L");
-  if (n_grads < 0 || (n_grads > 0 && (!keys || !grads))) return et_fail(h, US_EINVAL, "us_encoder_backward: bad gradient list");
+    return fe_fail(h, US_EINVAL, "us_encoder_backward: the workspace holds no us_encoder_forward_train of this B and L");
+  if (n_grads < 0 || (n_grads > 0 && (!keys || !grads))) return fe_fail(h, US_EINVAL, "us_encoder_backward: bad gradient list");
   const EncoderTape tape = it->second;
   const auto& c = h->ec;
   const Layout l = et_layout(h, B, L);
@@ -936,8 +677,8 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
   // destinations: the caller's buffer, or a slot of the workspace's arena for a key nobody asked for
   std::map<std::string, float*> dst;
   for (int i = 0; i < n_grads; ++i) {
-    if (!keys[i] || !grads[i]) return et_fail(h, US_EINVAL, "us_encoder_backward: null key or gradient buffer");
-    if (!h->w.count(keys[i])) return et_fail(h, US_ENOKEY, std::string("us_encoder_backward: unknown key '") + keys[i] + "'");
+    if (!keys[i] || !grads[i]) return fe_fail(h, US_EINVAL, "us_encoder_backward: null key or gradient buffer");
+    if (!h->w.count(keys[i])) return fe_fail(h, US_ENOKEY, std::string("us_encoder_backward: unknown key '") + keys[i] + "'");
     dst[keys[i]] = grads[i];
   }
   {
@@ -956,11 +697,11 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
   float* dh = x.f(l.dh);
   // upstream: x = xf (masked), mu = proj_m(xf) * mask
   if (grad_x)
-    hipLaunchKernelGGL(et_transpose_kernel<false>, dim3((L + 31) / 32, (C + 31) / 32, B), dim3(32, 8), 0, x.s, grad_x, x.mask, g, L, C);
+    hipLaunchKernelGGL(et_to_channel_last_kernel, dim3((L + 31) / 32, (C + 31) / 32, B), dim3(32, 8), 0, x.s, grad_x, x.mask, g, L, C);
   else
     (void)hipMemsetAsync(g, 0, (size_t)x.rows * C * sizeof(float), x.s);
   if (grad_mu) {
-    hipLaunchKernelGGL(et_transpose_kernel<false>, dim3((L + 31) / 32, (nf + 31) / 32, B), dim3(32, 8), 0, x.s, grad_mu, x.mask, d1, L, nf);
+    hipLaunchKernelGGL(et_to_channel_last_kernel, dim3((L + 31) / 32, (nf + 31) / 32, B), dim3(32, 8), 0, x.s, grad_mu, x.mask, d1, L, nf);
     conv_bwd(x, "proj_m", x.f(l.xf), false, d1, g, g, nullptr, 1.f, true, G("proj_m.weight"), G("proj_m.bias"));
   } else {
     (void)hipMemsetAsync(G("proj_m.weight"), 0, (size_t)nf * C * sizeof(float), x.s);
@@ -999,9 +740,9 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
     conv_bwd(x, ap + ".conv_v", xin, false, x.f(l.dv), g, g, nullptr, 1.f, true, G(ap + ".conv_v.weight"), G(ap + ".conv_v.bias"));
   }
   // prenet output (x0 + proj(a_2)) * mask: g is its (masked) gradient
-  conv_bwd(x, "prenet.proj", x.f(l.pa[kPrenet - 1]), false, g, t, nullptr, nullptr, 1.f, false, G("prenet.proj.weight"),
+  conv_bwd(x, "prenet.proj", x.f(l.pa[kPrenetLayers - 1]), false, g, t, nullptr, nullptr, 1.f, false, G("prenet.proj.weight"),
            G("prenet.proj.bias"));
-  for (int i = kPrenet - 1; i >= 0; --i) {
+  for (int i = kPrenetLayers - 1; i >= 0; --i) {
     const std::string n = std::to_string(i), cp = "prenet.conv_layers." + n, np = "prenet.norm_layers." + n;
     // t: gradient of a_i;  a_i = drop(relu(LN(c_i))), c_i = conv(in * mask)
     ln_bwd(x, np, x.f(l.pc[i]), t, x.f(l.pa[i]), p_prenet > 0.f ? 1.f / (1.f - p_prenet) : 1.f, d1, G(np + ".gamma"), G(np + ".beta"));
@@ -1011,29 +752,29 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
   hipLaunchKernelGGL(et_embed_grad_kernel, dim3(c.n_vocab), dim3(256), 0, x.s, reinterpret_cast<const long long*>(x.f(l.ids)), g,
                      G("emb.weight"), x.rows, C, sqrtf((float)C));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : et_fail(h, US_EHIP, std::string("us_encoder_backward: ") + hipGetErrorString(e));
+  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_encoder_backward: ") + hipGetErrorString(e));
 }
 
 int us_encoder_tape_release(us_frontend_handle h, const void* workspace) {
-  if (!h || h->kind != 0) return et_fail(h, US_EINVAL, "us_encoder_tape_release: not an encoder handle");
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, "us_encoder_tape_release: not an encoder handle");
   h->tapes.erase(workspace);
   return US_OK;
 }
 
 int us_encoder_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B, int L, float p_dropout, float* out, us_stream stream) {
-  if (!h || h->kind != 0 || !out || B <= 0 || L <= 0) return et_fail(h, US_EINVAL, "us_encoder_dropout_mask: bad argument");
+  if (!h || h->kind != 0 || !out || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_encoder_dropout_mask: bad argument");
   const auto& c = h->ec;
-  if (site < 0 || site >= kPrenet + kSitesPerLayer * c.n_layers) return et_fail(h, US_EINVAL, "us_encoder_dropout_mask: no such site");
+  if (site < 0 || site >= kPrenetLayers + kSitesPerLayer * c.n_layers) return fe_fail(h, US_EINVAL, "us_encoder_dropout_mask: no such site");
   long long n = (long long)B * c.n_channels * L;
-  if (!(p_dropout < 1.f)) return et_fail(h, US_EINVAL, "us_encoder_dropout_mask: p_dropout must be below 1");
+  if (!(p_dropout < 1.f)) return fe_fail(h, US_EINVAL, "us_encoder_dropout_mask: p_dropout must be below 1");
   float p = p_dropout < 0.f ? 0.f : p_dropout;
-  if (site < kPrenet) p = p_dropout < 0.f ? 0.f : kPrenetP;
-  else if ((site - kPrenet) % kSitesPerLayer == kSiteAttnP) n = (long long)B * c.n_heads * L * L;
-  else if ((site - kPrenet) % kSitesPerLayer == kSiteFfnRelu) n = (long long)B * c.filter_channels * L;
+  if (site < kPrenetLayers) p = p_dropout < 0.f ? 0.f : kPrenetP;
+  else if ((site - kPrenetLayers) % kSitesPerLayer == kSiteAttnP) n = (long long)B * c.n_heads * L * L;
+  else if ((site - kPrenetLayers) % kSitesPerLayer == kSiteFfnRelu) n = (long long)B * c.filter_channels * L;
   hipLaunchKernelGGL(et_mask_out_kernel, dim3(et_blocks(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), out, n,
                      make_drop(seed, site, p));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : et_fail(h, US_EHIP, std::string("us_encoder_dropout_mask: ") + hipGetErrorString(e));
+  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_encoder_dropout_mask: ") + hipGetErrorString(e));
 }
 
 }  // extern "C"

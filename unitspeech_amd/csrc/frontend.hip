@@ -1,10 +1,12 @@
 // Conditioning producer of `execute_text_to_speech`: the text / unit `Encoder`
-// (/root/reference/unitspeech/encoder.py:253-308) and the `DurationPredictor` (unitspeech/duration_predictor.py:24-63), inference
-// (eval mode: every Dropout is the identity).
+// (/root/reference/unitspeech/encoder.py:253-308) and the `DurationPredictor` (unitspeech/duration_predictor.py:24-63).  The Encoder's
+// forward is stated once, here, for both of its modes: inference (eval mode: every Dropout is the identity) and the training
+// forward of us_encoder_forward_train, which adds the reference's Dropout sites and stores the tape that the backward
+// (encoder_train.hip) reads.  The kernels take the mode as a template parameter, so the inference instantiations carry none of it.
 //
 // The work is tiny next to the diffusion loop (a 6-layer, 192-channel transformer over a few hundred symbols: ~2 GFLOP per
 // utterance, once, against 60 TFLOP for the 50 decoder evaluations), so the kernels are plain fp32 FMA code with a fixed
-// summation order -- no MFMA, no split reductions -- laid out for coalesced access: activations are kept channel-last
+// summation order -- no MFMA (but for training's convolutions, see encoder_forward), no split reductions -- laid out for coalesced access: activations are kept channel-last
 // [B][L][C] (a symbol's channels contiguous), convolution weights are re-packed once to [tap][Cin][Cout].  What matters
 // here is that the arithmetic follows the reference statement by statement (mask placement, LayerNorm formula and eps,
 // score scaling before the relative term is added, -1e4 fill, two separate value sums), which the goldens of
@@ -27,19 +29,21 @@ namespace {
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
 
-// x[b][l][:] = emb[ids[b][l]][:] * scale   (encoder.py:295; an id outside the table gives NaNs rather than a silent clamp)
-__global__ void fe_embed_kernel(const long long* ids, const float* emb, float* out, int n_vocab, int C, float scale) {
+// x[b][l][:] = emb[ids[b][l]][:] * scale   (encoder.py:295; an id outside the table gives NaNs rather than a silent clamp) and
+// mask[b][l] = l < lengths[b]   (unitspeech/util.py sequence_mask); training keeps the ids for the embedding gradient
+template <bool kTrain>
+__global__ void fe_embed_kernel(const long long* ids, const long long* lengths, const float* emb, float* out, long long* ids_tape,
+                                float* mask, int n_vocab, int C, int L, float scale) {
   const long long row = blockIdx.x;
-  const long long id = ids[row];
+  const unsigned b = blockIdx.x / (unsigned)L;
+  const long long id = ids[row], len = lengths[b];      // both loads in flight together: the mask costs no second round trip
+  if (threadIdx.x == 0) {
+    if (kTrain) ids_tape[row] = id;
+    mask[row] = (long long)(blockIdx.x - b * (unsigned)L) < len ? 1.f : 0.f;
+  }
   const bool ok = id >= 0 && id < n_vocab;
   for (int c = threadIdx.x; c < C; c += blockDim.x)
     out[row * C + c] = ok ? mul_rn(emb[id * C + c], scale) : __builtin_nanf("");
-}
-
-// mask[b][l] = l < lengths[b]   (unitspeech/util.py sequence_mask)
-__global__ void fe_length_mask_kernel(const long long* lengths, float* mask, int L) {
-  const int b = blockIdx.y, l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l < L) mask[(long long)b * L + l] = l < lengths[b] ? 1.f : 0.f;
 }
 
 struct Conv1dArgs {
@@ -117,6 +121,13 @@ __global__ void __launch_bounds__(64 * kConvKg) fe_conv1d_kernel(Conv1dArgs a) {
   }
 }
 
+// what the training forward adds to a LayerNorm
+struct LnTrain {
+  Drop add_drop;        // n = in + drop(add)
+  Drop out_drop;        // y = drop(relu(LN(n))) (prenet relu_drop)
+  float* sum_out;       // n is stored here (the backward's LayerNorm input), or null
+  int L;                // the dropout streams index the reference's [B][C][L] tensor
+};
 struct LnArgs {
   const float* in;      // [rows][C]
   const float* add;     // [rows][C] or null: in + add is normalised (transformer residual)
@@ -124,11 +135,13 @@ struct LnArgs {
   const float* mask;    // [rows] or null: output multiplied by it
   float* out;
   int C; float eps; int relu;
+  LnTrain t;            // read by the kTrain instantiation only
 };
 constexpr int kLnMaxPerLane = 16;      // C <= 1024
 
 // LayerNorm over the channels of one symbol (encoder.py:21-30: mean, mean of squared deviations, (x - mean) * rsqrt(var + eps)
 // * gamma + beta; duration_predictor.py:16-21 is the same arithmetic through F.layer_norm).  One wave per symbol.
+template <bool kTrain>
 __global__ void __launch_bounds__(64) fe_layernorm_kernel(LnArgs a) {
   const long long row = blockIdx.x;
   const int lane = threadIdx.x;
@@ -140,7 +153,12 @@ __global__ void __launch_bounds__(64) fe_layernorm_kernel(LnArgs a) {
     v[i] = 0.f;
     if (c < a.C) {
       v[i] = a.in[row * a.C + c];
-      if (a.add) v[i] = add_rn(v[i], a.add[row * a.C + c]);
+      if (a.add) {
+        float ad = a.add[row * a.C + c];
+        if (kTrain) ad *= et_keep(a.t.add_drop, et_cf_index(row, c, a.C, a.t.L));
+        v[i] = add_rn(v[i], ad);
+      }
+      if (kTrain && a.t.sum_out) a.t.sum_out[row * a.C + c] = v[i];
       s += v[i];
     }
   }
@@ -163,25 +181,19 @@ __global__ void __launch_bounds__(64) fe_layernorm_kernel(LnArgs a) {
     if (c < a.C) {
       float y = add_rn(mul_rn(mul_rn(sub_rn(v[i], mean), rstd), a.gamma[c]), a.beta[c]);
       if (a.relu) y = y > 0.f ? y : 0.f;
+      if (kTrain && a.t.out_drop.site >= 0) y *= et_keep(a.t.out_drop, et_cf_index(row, c, a.C, a.t.L));
       if (a.mask) y *= m;
       a.out[row * a.C + c] = y;
     }
   }
 }
 
-struct AttnArgs {
-  const float* q; const float* k; const float* v;     // [B][L][C], head h owns channels [h * D, (h + 1) * D)
-  const float* rel_k; const float* rel_v;             // [2W+1][D] (heads_share) or null
-  const float* mask;                                  // [B][L]
-  float* out;                                         // [B][L][C]
-  int L, C, D, W;
-  float inv_unused, sqrt_d;
-};
-
 // MultiHeadAttention.attention (encoder.py:115-144) for one (query i, head, item):
 //   score[j] = q_i.k_j / sqrt(D) + [|j-i| <= W] q_i.rel_k[j-i+W] / sqrt(D);  -1e4 where mask_i * mask_j == 0;  softmax over j;
 //   out = sum_j p[j] v_j  +  sum_{|d| <= W, 0 <= i+d < L} p[i+d] rel_v[d+W]
-// (the reference reaches the same terms by zero-padding the 2W+1 embeddings to 2L-1 and skewing, :154-182).
+// (the reference reaches the same terms by zero-padding the 2W+1 embeddings to 2L-1 and skewing, :154-182).  Training stores p
+// (a.P) and goes on with pd = drop(p) in its place.
+template <bool kTrain>
 __global__ void __launch_bounds__(128) fe_rel_attention_kernel(AttnArgs a) {
   extern __shared__ float sm[];          // p[L], q[D], red[128]
   float* p = sm;
@@ -230,7 +242,15 @@ __global__ void __launch_bounds__(128) fe_rel_attention_kernel(AttnArgs a) {
     __syncthreads();
   }
   sum = red[0];
-  for (int j = tid; j < a.L; j += blockDim.x) p[j] = p[j] / sum;
+  const long long prow = (((long long)b * a.H + h) * a.L + i) * a.L;
+  for (int j = tid; j < a.L; j += blockDim.x) {
+    float pj = p[j] / sum;
+    if (kTrain) {
+      a.P[prow + j] = pj;
+      pj *= et_keep(a.drop, (unsigned long long)(prow + j));
+    }
+    p[j] = pj;
+  }
   __syncthreads();
   for (int d = tid; d < a.D; d += blockDim.x) {
     float o1 = 0.f;
@@ -247,7 +267,7 @@ __global__ void __launch_bounds__(128) fe_rel_attention_kernel(AttnArgs a) {
   }
 }
 
-// [B][L][C] -> [B][C][L] (the reference's channel-first tensors), optionally times mask[b][l]; and the reverse
+// [B][L][C] -> [B][C][L] (the reference's channel-first tensors), optionally times mask[b][l]
 __global__ void fe_to_channel_first_kernel(const float* in, const float* mask, float* out, int L, int C) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
@@ -287,12 +307,29 @@ __global__ void fe_pack_conv_kernel(const float* w, float* out, int Cout, int Ci
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
+}  // namespace
 
 int fe_fail(us_frontend* h, int code, const std::string& msg) {
   if (h) h->err = msg;
   set_last_error(msg.c_str());
   return code;
 }
+// the handle is bound to the device that was current at creation: weights live there, launches go to a stream of that device
+static int fe_device(us_frontend* h, const char* what) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
+    return fe_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
+                                     std::to_string(h->device) + ")");
+  return US_OK;
+}
+int fe_check(us_frontend* h, const char* what) {
+  for (const auto& k : h->keys)
+    if (!h->w[k].loaded) return fe_fail(h, US_EWEIGHTS, std::string(what) + ": weight '" + k + "' has not been loaded");
+  return fe_device(h, what);
+}
+
+namespace {
+
 int fe_hip(us_frontend* h, const char* what, hipError_t e) {
   return fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -309,8 +346,6 @@ void add_norm(us_frontend* h, const std::string& p, int c) {
   add_key(h, p + ".gamma", {c});
   add_key(h, p + ".beta", {c});
 }
-
-constexpr int kPrenetLayers = 3, kPrenetKernel = 5;      // encoder.py:283-284
 
 // state_dict of Encoder (module registration order of encoder.py:270-291)
 void encoder_keys(us_frontend* h) {
@@ -352,20 +387,7 @@ size_t fe_scratch_floats(const us_frontend* h, long long rows) {
   if (h->kind == 0) return (size_t)rows * (6 * (size_t)h->ec.n_channels + (size_t)h->ec.filter_channels);      // x, x_org/y, q, k, v, a (C each) + h1 (F)
   return (size_t)rows * ((size_t)(h->dc.in_channels + h->dc.spk_emb_dim) + 2 * (size_t)h->dc.filter_channels);
 }
-// the handle is bound to the device that was current at creation: weights live there, launches go to a stream of that device
-int fe_device(us_frontend* h, const char* what) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
-    return fe_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
-                                     std::to_string(h->device) + ")");
-  return US_OK;
-}
-
-int fe_ready(us_frontend* h, const char* what) {
-  for (const auto& k : h->keys)
-    if (!h->w[k].loaded) return fe_fail(h, US_EWEIGHTS, std::string(what) + ": weight '" + k + "' has not been loaded");
-  return US_OK;
-}
+float* fe_base(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
 
 int conv1d(us_frontend* h, hipStream_t s, const std::string& prefix, const float* in, float* out, const float* mask, const float* add,
            int B, int L, bool mask_in, bool relu, bool mask_out) {
@@ -380,13 +402,15 @@ int conv1d(us_frontend* h, hipStream_t s, const std::string& prefix, const float
   return US_OK;
 }
 
+// train: the training forward's extras (null: inference)
 int layernorm(us_frontend* h, hipStream_t s, const std::string& prefix, const float* in, const float* add, float* out, const float* mask,
-              long long rows, int C, float eps, bool relu) {
+              long long rows, int C, float eps, bool relu, const LnTrain* train = nullptr) {
   if (C > 64 * kLnMaxPerLane) return fe_fail(h, US_EINVAL, "front-end LayerNorm: more than 1024 channels");
   LnArgs a{};
   a.in = in; a.add = add; a.gamma = h->w[prefix + ".gamma"].dev; a.beta = h->w[prefix + ".beta"].dev; a.mask = mask; a.out = out;
   a.C = C; a.eps = eps; a.relu = relu;
-  hipLaunchKernelGGL(fe_layernorm_kernel, dim3((unsigned)rows), dim3(64), 0, s, a);
+  if (train) a.t = *train;
+  hipLaunchKernelGGL(train ? fe_layernorm_kernel<true> : fe_layernorm_kernel<false>, dim3((unsigned)rows), dim3(64), 0, s, a);
   return US_OK;
 }
 
@@ -395,6 +419,70 @@ void to_channel_first(hipStream_t s, const float* in, const float* mask, float* 
 }
 
 }  // namespace
+
+// The Encoder's forward, once for both modes.  The two convolutions stay two: inference runs L of 100-300 and is latency-bound,
+// which the fixed-order fp32 FMA kernel above serves best; training runs B * L of several thousand rows on the MFMA GEMM that
+// its dgrad / wgrad share (they differ in summation order only).  The mode of the call picks, nothing else does.
+int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const int64_t* lengths,
+                    float* mu_x, float* x_out, int B, int L) {
+  const auto& c = h->ec;
+  const int C = c.n_channels, D = C / c.n_heads;
+  const long long rows = (long long)B * L;
+  int rc;
+  auto conv = [&](const std::string& key, const float* in, float* out, const float* add, bool mask_in, bool relu, bool mask_out,
+                  Drop drop = no_drop()) {
+    if (!m.train) return conv1d(h, s, key, in, out, b.mask, add, B, L, mask_in, relu, mask_out);
+    gemm_conv_fwd(h, s, key, in, out, b.mask, add, rows, L, mask_in, relu, mask_out, drop);
+    return (int)US_OK;
+  };
+  auto norm = [&](const std::string& key, const float* in, const float* add, Drop add_drop, float* sum_out, bool relu, Drop out_drop,
+                  const float* mask, float* out) {
+    const LnTrain t{add_drop, out_drop, sum_out, L};
+    return layernorm(h, s, key, in, add, out, mask, rows, C, 1e-4f, relu, m.train ? &t : nullptr);
+  };
+  hipLaunchKernelGGL(m.train ? fe_embed_kernel<true> : fe_embed_kernel<false>, dim3((unsigned)rows), dim3(C >= 256 ? 256 : 64), 0, s,
+                     reinterpret_cast<const long long*>(ids), reinterpret_cast<const long long*>(lengths), h->w["emb.weight"].dev, b.x0,
+                     b.ids_tape, b.mask, c.n_vocab, C, L, sqrtf((float)C));
+  // prenet (ConvReluNorm.forward, encoder.py:58-65): c_i = conv(a_{i-1} * mask), a_i = drop(relu(LN(c_i))); (x0 + proj(a_2)) * mask
+  const float* cur = b.x0;
+  for (int i = 0; i < kPrenetLayers; ++i) {
+    const std::string n = std::to_string(i);
+    if ((rc = conv("prenet.conv_layers." + n, cur, b.pc[i], nullptr, true, false, false)) != US_OK) return rc;
+    if ((rc = norm("prenet.norm_layers." + n, b.pc[i], nullptr, no_drop(), nullptr, true, make_drop(m.seed, i, m.p_prenet), nullptr,
+                   b.pa[i])) != US_OK) return rc;
+    cur = b.pa[i];
+  }
+  if ((rc = conv("prenet.proj", cur, c.n_layers ? b.layer[0].x : b.xf, b.x0, false, false, true)) != US_OK) return rc;
+  // transformer blocks (EncoderModule.forward, :239-250); `x` is masked on entry to every block (LayerNorm 2 writes it masked)
+  for (int i = 0; i < c.n_layers; ++i) {
+    const EncoderBufs::Layer& l = b.layer[i];
+    const std::string n = std::to_string(i), ap = "encoder.attn_layers." + n, fp = "encoder.ffn_layers." + n;
+    if ((rc = conv(ap + ".conv_q", l.x, l.q, nullptr, false, false, false)) != US_OK) return rc;
+    if ((rc = conv(ap + ".conv_k", l.x, l.k, nullptr, false, false, false)) != US_OK) return rc;
+    if ((rc = conv(ap + ".conv_v", l.x, l.v, nullptr, false, false, false)) != US_OK) return rc;
+    AttnArgs a{};
+    a.q = l.q; a.k = l.k; a.v = l.v; a.mask = b.mask; a.P = l.P; a.out = l.at;
+    a.rel_k = c.window_size > 0 ? h->w[ap + ".emb_rel_k"].dev : nullptr;
+    a.rel_v = c.window_size > 0 ? h->w[ap + ".emb_rel_v"].dev : nullptr;
+    a.L = L; a.C = C; a.D = D; a.H = c.n_heads; a.W = c.window_size; a.sqrt_d = sqrtf((float)D);
+    a.drop = make_drop(m.seed, layer_site(i, kSiteAttnP), m.p);
+    hipLaunchKernelGGL(m.train ? fe_rel_attention_kernel<true> : fe_rel_attention_kernel<false>, dim3(L, c.n_heads, B), dim3(128),
+                       ((size_t)L + D + 128) * sizeof(float), s, a);
+    if ((rc = conv(ap + ".conv_o", l.at, b.y, nullptr, false, false, false)) != US_OK) return rc;
+    if ((rc = norm("encoder.norm_layers_1." + n, l.x, b.y, make_drop(m.seed, layer_site(i, kSiteAttnOut), m.p), l.n1, false, no_drop(),
+                   nullptr, l.x1)) != US_OK) return rc;
+    if ((rc = conv(fp + ".conv_1", l.x1, l.hd, nullptr, true, true, false, make_drop(m.seed, layer_site(i, kSiteFfnRelu), m.p))) != US_OK)
+      return rc;
+    if ((rc = conv(fp + ".conv_2", l.hd, b.y, nullptr, true, false, true)) != US_OK) return rc;
+    if ((rc = norm("encoder.norm_layers_2." + n, l.x1, b.y, make_drop(m.seed, layer_site(i, kSiteFfnOut), m.p), l.n2, false, no_drop(),
+                   b.mask, i + 1 < c.n_layers ? b.layer[i + 1].x : b.xf)) != US_OK) return rc;
+  }
+  if ((rc = conv("proj_m", b.xf, b.mu, nullptr, false, false, true)) != US_OK) return rc;
+  to_channel_first(s, b.mu, nullptr, mu_x, B, L, c.n_feats);
+  to_channel_first(s, b.xf, nullptr, x_out, B, L, C);
+  return US_OK;
+}
+
 }  // namespace us
 
 extern "C" {
@@ -482,61 +570,29 @@ int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* 
   if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, "us_encoder_forward: not an encoder handle");
   if (!ids || !lengths || !mu_x || !x_out || !x_mask || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_encoder_forward: bad argument");
   if (B > 65535) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than 65535 items");
-  int rc = fe_ready(h, "us_encoder_forward");
+  int rc = fe_check(h, "us_encoder_forward");
   if (rc != US_OK) return rc;
   const auto& c = h->ec;
-  const int C = c.n_channels, F = c.filter_channels, D = C / c.n_heads;
-  const size_t attn_lds = ((size_t)L + D + 128) * sizeof(float);
-  if (attn_lds > 64 * 1024) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than ~16000 symbols per utterance");
+  const int C = c.n_channels, D = C / c.n_heads;
+  if (((size_t)L + D + 128) * sizeof(float) > 64 * 1024) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than ~16000 symbols per utterance");
   const long long rows = (long long)B * L;
-  if ((rc = fe_device(h, "us_encoder_forward")) != US_OK) return rc;
   if (!workspace || workspace_bytes < us_frontend_workspace_bytes(h, B, L))
     return fe_fail(h, US_EWORKSPACE, "us_encoder_forward: workspace too small (us_frontend_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float* x = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-  float* y = x + rows * C;
-  float* q = y + rows * C;
+  // seven planes (fe_scratch_floats): x_org, then conv_o / conv_2's output once the prenet is done; the running x (both LayerNorms
+  // of a block write it in place); q, k (the prenet ping-pongs in them, proj_m's output lands in q); v; the attention output; h1
+  float* p0 = fe_base(workspace);
+  float* xr = p0 + rows * C;
+  float* q = xr + rows * C;
   float* k = q + rows * C;
   float* v = k + rows * C;
   float* at = v + rows * C;
   float* h1 = at + rows * C;
-  const float* mask = x_mask;      // [B][1][L] == [B][L]
-  hipLaunchKernelGGL(fe_length_mask_kernel, dim3((L + 255) / 256, B), dim3(256), 0, s, reinterpret_cast<const long long*>(lengths), x_mask, L);
-  hipLaunchKernelGGL(fe_embed_kernel, dim3((unsigned)rows), dim3(C >= 256 ? 256 : 64), 0, s, reinterpret_cast<const long long*>(ids),
-                     h->w["emb.weight"].dev, x, c.n_vocab, C, sqrtf((float)C));
-  // prenet (ConvReluNorm.forward, encoder.py:58-65): x_org stays in `x`; q / k ping-pong
-  const float* cur = x;
-  float* pp[2] = {q, k};
-  for (int i = 0; i < kPrenetLayers; ++i) {
-    float* t = pp[i & 1];
-    if ((rc = conv1d(h, s, "prenet.conv_layers." + std::to_string(i), cur, t, mask, nullptr, B, L, true, false, false)) != US_OK) return rc;
-    if ((rc = layernorm(h, s, "prenet.norm_layers." + std::to_string(i), t, nullptr, t, nullptr, rows, C, 1e-4f, true)) != US_OK) return rc;
-    cur = t;
-  }
-  if ((rc = conv1d(h, s, "prenet.proj", cur, y, mask, x, B, L, false, false, true)) != US_OK) return rc;      // (x_org + proj(x)) * x_mask
-  { float* t = x; x = y; y = t; }
-  // transformer blocks (EncoderModule.forward, :239-250); `x` is masked on entry to every block (LayerNorm 2 writes it masked)
-  for (int i = 0; i < c.n_layers; ++i) {
-    const std::string ap = "encoder.attn_layers." + std::to_string(i);
-    if ((rc = conv1d(h, s, ap + ".conv_q", x, q, mask, nullptr, B, L, false, false, false)) != US_OK) return rc;
-    if ((rc = conv1d(h, s, ap + ".conv_k", x, k, mask, nullptr, B, L, false, false, false)) != US_OK) return rc;
-    if ((rc = conv1d(h, s, ap + ".conv_v", x, v, mask, nullptr, B, L, false, false, false)) != US_OK) return rc;
-    AttnArgs a{};
-    a.q = q; a.k = k; a.v = v; a.mask = mask; a.out = at;
-    a.rel_k = c.window_size > 0 ? h->w[ap + ".emb_rel_k"].dev : nullptr;
-    a.rel_v = c.window_size > 0 ? h->w[ap + ".emb_rel_v"].dev : nullptr;
-    a.L = L; a.C = C; a.D = D; a.W = c.window_size; a.sqrt_d = sqrtf((float)D);
-    hipLaunchKernelGGL(fe_rel_attention_kernel, dim3(L, c.n_heads, B), dim3(128), attn_lds, s, a);
-    if ((rc = conv1d(h, s, ap + ".conv_o", at, y, mask, nullptr, B, L, false, false, false)) != US_OK) return rc;
-    if ((rc = layernorm(h, s, "encoder.norm_layers_1." + std::to_string(i), x, y, x, nullptr, rows, C, 1e-4f, false)) != US_OK) return rc;
-    const std::string fp = "encoder.ffn_layers." + std::to_string(i);
-    if ((rc = conv1d(h, s, fp + ".conv_1", x, h1, mask, nullptr, B, L, true, true, false)) != US_OK) return rc;
-    if ((rc = conv1d(h, s, fp + ".conv_2", h1, y, mask, nullptr, B, L, true, false, true)) != US_OK) return rc;
-    if ((rc = layernorm(h, s, "encoder.norm_layers_2." + std::to_string(i), x, y, x, mask, rows, C, 1e-4f, false)) != US_OK) return rc;
-  }
-  if ((rc = conv1d(h, s, "proj_m", x, q, mask, nullptr, B, L, false, false, true)) != US_OK) return rc;
-  to_channel_first(s, q, nullptr, mu_x, B, L, c.n_feats);
-  to_channel_first(s, x, nullptr, x_out, B, L, C);
+  EncoderBufs b{};
+  b.mask = x_mask;      // [B][1][L] == [B][L]
+  b.x0 = p0; b.y = p0; b.xf = xr; b.mu = q;
+  for (int i = 0; i < kPrenetLayers; ++i) b.pc[i] = b.pa[i] = (i & 1) ? k : q;
+  b.layer.assign(c.n_layers, EncoderBufs::Layer{xr, q, k, v, at, nullptr, xr, h1, nullptr, nullptr});
+  if ((rc = encoder_forward(h, static_cast<hipStream_t>(stream), b, EncoderMode{}, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : fe_hip(h, "us_encoder_forward", e);
 }
@@ -548,15 +604,14 @@ int us_duration_predictor_forward(us_frontend_handle h, const float* x, const fl
   if (!x || !x_mask || !logw || B <= 0 || L <= 0 || B > 65535) return fe_fail(h, US_EINVAL, "us_duration_predictor_forward: bad argument");
   if ((c.spk_emb_dim > 0) != (g != nullptr))
     return fe_fail(h, US_EINVAL, "us_duration_predictor_forward: g must be given exactly when the module was built with spk_emb_dim > 0");
-  int rc = fe_ready(h, "us_duration_predictor_forward");
+  int rc = fe_check(h, "us_duration_predictor_forward");
   if (rc != US_OK) return rc;
   const int Cin = c.in_channels + c.spk_emb_dim, F = c.filter_channels;
   const long long rows = (long long)B * L;
-  if ((rc = fe_device(h, "us_duration_predictor_forward")) != US_OK) return rc;
   if (!workspace || workspace_bytes < us_frontend_workspace_bytes(h, B, L))
     return fe_fail(h, US_EWORKSPACE, "us_duration_predictor_forward: workspace too small (us_frontend_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* xin = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+  float* xin = fe_base(workspace);
   float* a1 = xin + rows * Cin;
   float* a2 = a1 + rows * F;
   hipLaunchKernelGGL(fe_gather_concat_kernel, dim3(L, B), dim3(256), 0, s, x, g, xin, L, c.in_channels, c.spk_emb_dim);

@@ -213,7 +213,7 @@ class _FrontEndModule(torch.nn.Module):
                 self._create(lib, device)
             self._device, self._versions = device, {}
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        # the handle allocates its weight store on the CURRENT device and refuses calls made under another one (frontend.hip: fe_device)
+        # the handle allocates its weight store on the CURRENT device and refuses calls made under another one (frontend.hip: fe_check)
         with torch.cuda.device(device):
             for key, t in self.state_dict(keep_vars=True).items():
                 tag = (t.data_ptr(), t._version, t.device)
