@@ -301,6 +301,36 @@ int us_encoder_tape_release(us_frontend_handle h, const void* workspace);
  * g [B,1,spk_emb_dim] (NULL iff spk_emb_dim == 0) -> logw [B,1,L]. */
 int us_duration_predictor_forward(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,
                                   void* workspace, size_t workspace_bytes, us_stream stream);
+/* ---- training of the DurationPredictor (duration_predictor.py:47-63 in train mode; csrc/duration_train.hip) -----------------
+ * The Encoder's training ABI, one for one, on a duration-predictor handle.
+ * us_duration_predictor_forward_train: same inputs and output as us_duration_predictor_forward, with the reference's two Dropouts
+ *   (0 <= p_dropout < 1; 0 draws nothing; p_dropout < 0: the reference in eval mode, differentiated).  The workspace
+ *   (us_duration_predictor_train_workspace_bytes) keeps the tape the backward reads -- the concatenated input, the mask and the two
+ *   convolutions' outputs after the ReLU -- plus the backward's scratch and a gradient slot for every key; it must stay untouched
+ *   until then.
+ * us_duration_predictor_backward: overwrites grads[i] (reference layout of keys[i], device memory) with the gradient of that
+ *   state_dict key, given grad_logw [B,1,L].  All ten keys are available; keys not listed are computed into the workspace and
+ *   dropped.  There is NO gradient for x (the reference detaches it, :48) and NONE for g: conv_1's data gradient is never computed.
+ *   US_EINVAL when the workspace holds no training forward of this B and L (never run, released, or another handle's).
+ *   Deterministic: no atomics, fixed summation orders.
+ * Dropout masks are the Encoder's stream (Philox4x32-10 keyed by the seed, counter (index / 4, site)): site 0 follows norm_1,
+ *   site 1 follows norm_2, flat index of the reference's [B,filter_channels,L] tensor.
+ * us_duration_predictor_dropout_mask: TEST HOOK.  The scaled keep mask (0 or 1 / (1 - p)) [B,filter_channels,L] that `site` used
+ *   for `seed` (all ones for p_dropout <= 0).  A pure function of its arguments.
+ * us_duration_predictor_tape_release: forget the training forward a workspace holds (call before the memory is freed or reused).
+ * us_duration_predictor_mse_loss: the reverse=False branch (:60-62) on its own: loss[0] = sum((logw - log(w + 1e-6) x_mask)^2) /
+ *   sum(x_mask) and, when d_logw is not NULL, d loss / d logw [B,1,L]; logw, w, x_mask [B,1,L].  (us_duration_loss is train_STEP1's
+ *   other statement: epsilon 1e-8 inside the log, divided by sum(x_lengths).) */
+size_t us_duration_predictor_train_workspace_bytes(us_frontend_handle h, int B, int L);
+int us_duration_predictor_forward_train(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,
+                                        float p_dropout, uint64_t seed, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_duration_predictor_backward(us_frontend_handle h, const float* grad_logw, int B, int L, const char* const* keys, float* const* grads,
+                                   int n_grads, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_duration_predictor_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B, int L, float p_dropout, float* out,
+                                       us_stream stream);
+int us_duration_predictor_tape_release(us_frontend_handle h, const void* workspace);
+int us_duration_predictor_mse_loss(const float* logw, const float* w, const float* x_mask, float* loss, float* d_logw, int B, int L,
+                                   us_stream stream);
 
 /* ---- one building block of the score network on its own (parity tests against per-module reference outputs) ---------
  * prefix: the module's state_dict prefix ("estimator.downs.1.1", "estimator.downs.1.2", "estimator.downs.1.3",

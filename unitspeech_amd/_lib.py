@@ -102,6 +102,14 @@ SIGNATURES = {
     "us_maximum_path": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_duration_loss": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.c_void_p]),
     "us_duration_predictor_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_duration_predictor_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "us_duration_predictor_forward_train": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t,
+                                                                        C.c_void_p]),
+    "us_duration_predictor_backward": (C.c_int, [C.c_void_p] * 2 + [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.c_int,
+                                                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_duration_predictor_dropout_mask": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "us_duration_predictor_tape_release": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "us_duration_predictor_mse_loss": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
     "us_vocoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_vocoder_config)]),
     "us_vocoder_destroy": (C.c_int, [C.c_void_p]),
     "us_vocoder_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

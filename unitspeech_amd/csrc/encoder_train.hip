@@ -477,11 +477,6 @@ size_t conv_numel(const us_encoder_config& c) {      // largest convolution weig
   return m;
 }
 
-int wgrad_splits(long long rows) {
-  long long s = rows / 512;
-  return (int)(s < 1 ? 1 : (s > 32 ? 32 : s));
-}
-
 Layout et_layout(const us_frontend* h, int B, int L) {
   const auto& c = h->ec;
   const size_t rows = (size_t)B * L, C = c.n_channels, F = c.filter_channels, H = c.n_heads;
@@ -535,31 +530,13 @@ const float* wdev(us_frontend* h, const std::string& k) { return h->w[k].dev; }
 // mask_in); dw / db are the destinations in torch layout
 void conv_bwd(const Ctx& x, const std::string& key, const float* in, bool mask_in, const float* dout, float* din, const float* add,
               const float* gate, float gate_scale, bool mask_out, float* dw, float* db) {
-  const Weight& w = x.h->w[key + ".weight"];
-  const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], K = (int)w.shape[2];
+  const int Cout = (int)x.h->w[key + ".weight"].shape[0];
   const Layout& l = *x.lay;
-  const long long nw = (long long)Cout * Cin * K;
-  // weight gradient
-  GemmArgs g{};
-  g.in = in; g.mask = x.mask; g.mask_in = mask_in;
-  g.rows = (int)x.rows; g.L = x.L; g.Cin = Cin; g.N = Cout; g.K = K; g.pad = K / 2;
-  g.dout = dout; g.part = x.f(l.wpart); g.splits = l.splits;
-  g.rows_per_split = (int)(((x.rows + l.splits - 1) / l.splits + kBK - 1) / kBK * kBK);
-  g.drop.site = -1;
-  hipLaunchKernelGGL(et_gemm_kernel<true>, dim3((Cin + kBM - 1) / kBM, (Cout + kBN - 1) / kBN, K * l.splits), dim3(256), 0, x.s, g);
-  hipLaunchKernelGGL(et_wgrad_finish_kernel, dim3(et_blocks(nw, 256)), dim3(256), 0, x.s, x.f(l.wpart), dw, l.splits, K, Cin, Cout);
+  gemm_conv_wgrad(x.h, x.s, key, in, x.mask, mask_in, dout, x.rows, x.L, x.f(l.wpart), dw);
   // bias gradient
   hipLaunchKernelGGL(et_colsum_kernel, dim3((Cout + 63) / 64, kColChunks), dim3(256), 0, x.s, dout, x.f(l.cpart), (int)x.rows, Cout);
   hipLaunchKernelGGL(et_colsum_finish_kernel, dim3((Cout + 255) / 256), dim3(256), 0, x.s, x.f(l.cpart), db, Cout, kColChunks, 1.f);
-  if (!din) return;
-  // data gradient: the forward form with the tap-flipped transposed weight
-  hipLaunchKernelGGL(et_pack_dgrad_kernel, dim3(et_blocks(nw, 256)), dim3(256), 0, x.s, w.dev, x.f(l.wd), Cout, Cin, K);
-  GemmArgs a{};
-  a.in = dout; a.mask = x.mask; a.mask_in = 0;
-  a.rows = (int)x.rows; a.L = x.L; a.Cin = Cout; a.N = Cin; a.K = K; a.pad = K / 2;
-  a.w = x.f(l.wd); a.gate = gate; a.gate_scale = gate_scale; a.add = add; a.out = din; a.mask_out = mask_out;
-  a.drop.site = -1;
-  hipLaunchKernelGGL(et_gemm_kernel<false>, dim3((x.rows + kBM - 1) / kBM, (Cin + kBN - 1) / kBN), dim3(256), 0, x.s, a);
+  if (din) gemm_conv_dgrad(x.h, x.s, key, dout, din, x.mask, add, gate, gate_scale, mask_out, x.rows, x.L, x.f(l.wd));
 }
 
 void ln_bwd(const Ctx& x, const std::string& key, const float* in, const float* dy, const float* gate, float gate_scale, float* dx,
@@ -603,6 +580,40 @@ int et_check(us_frontend* h, const char* what, int B, int L) {
 float* et_base(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
 
 }  // namespace
+
+int wgrad_splits(long long rows) {
+  long long s = rows / 512;
+  return (int)(s < 1 ? 1 : (s > 32 ? 32 : s));
+}
+
+void gemm_conv_wgrad(us_frontend* h, hipStream_t s, const std::string& key, const float* in, const float* mask, bool mask_in, const float* dout,
+                     long long rows, int L, float* part, float* dw) {
+  const Weight& w = h->w[key + ".weight"];
+  const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], K = (int)w.shape[2];
+  const int splits = wgrad_splits(rows);
+  GemmArgs g{};
+  g.in = in; g.mask = mask; g.mask_in = mask_in;
+  g.rows = (int)rows; g.L = L; g.Cin = Cin; g.N = Cout; g.K = K; g.pad = K / 2;
+  g.dout = dout; g.part = part; g.splits = splits;
+  g.rows_per_split = (int)(((rows + splits - 1) / splits + kBK - 1) / kBK * kBK);
+  g.drop.site = -1;
+  hipLaunchKernelGGL(et_gemm_kernel<true>, dim3((Cin + kBM - 1) / kBM, (Cout + kBN - 1) / kBN, K * splits), dim3(256), 0, s, g);
+  hipLaunchKernelGGL(et_wgrad_finish_kernel, dim3(et_blocks((long long)Cout * Cin * K, 256)), dim3(256), 0, s, part, dw, splits, K, Cin, Cout);
+}
+
+// the forward form with the tap-flipped transposed weight
+void gemm_conv_dgrad(us_frontend* h, hipStream_t s, const std::string& key, const float* dout, float* din, const float* mask, const float* add,
+                     const float* gate, float gate_scale, bool mask_out, long long rows, int L, float* wd) {
+  const Weight& w = h->w[key + ".weight"];
+  const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], K = (int)w.shape[2];
+  hipLaunchKernelGGL(et_pack_dgrad_kernel, dim3(et_blocks((long long)Cout * Cin * K, 256)), dim3(256), 0, s, w.dev, wd, Cout, Cin, K);
+  GemmArgs a{};
+  a.in = dout; a.mask = mask; a.mask_in = 0;
+  a.rows = (int)rows; a.L = L; a.Cin = Cout; a.N = Cin; a.K = K; a.pad = K / 2;
+  a.w = wd; a.gate = gate; a.gate_scale = gate_scale; a.add = add; a.out = din; a.mask_out = mask_out;
+  a.drop.site = -1;
+  hipLaunchKernelGGL(et_gemm_kernel<false>, dim3((rows + kBM - 1) / kBM, (Cin + kBN - 1) / kBN), dim3(256), 0, s, a);
+}
 
 void gemm_conv_fwd(us_frontend* h, hipStream_t s, const std::string& key, const float* in, float* out, const float* mask, const float* add,
                    long long rows, int L, bool mask_in, bool relu, bool mask_out, Drop drop) {

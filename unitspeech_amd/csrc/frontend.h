@@ -1,6 +1,7 @@
 // Host-side state of a `us_frontend_handle` and what crosses between frontend.hip (the Encoder's forward in both modes, the
-// DurationPredictor) and encoder_train.hip (the MFMA convolution, the Encoder's backward): the dropout stream, the attention
-// arguments, the forward's buffer table and the launchers the two files call in each other.
+// DurationPredictor), encoder_train.hip (the MFMA convolution, the Encoder's backward) and duration_train.hip (the
+// DurationPredictor's training): the dropout stream, the attention arguments, the forward's buffer table and the launchers the
+// files call in each other.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,7 +21,8 @@ struct Weight {
   size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
 };
 
-// what one us_encoder_forward_train left in a caller-owned workspace (keyed by the workspace's base address)
+// what one us_encoder_forward_train / us_duration_predictor_forward_train left in a caller-owned workspace (keyed by the
+// workspace's base address)
 struct EncoderTape {
   int B = 0, L = 0;
   float p_dropout = 0.f;
@@ -144,5 +146,16 @@ int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const E
 // encoder_train.hip: the convolution `key` as an implicit GEMM on the fp32 matrix cores (training forward)
 void gemm_conv_fwd(us_frontend* h, hipStream_t s, const std::string& key, const float* in, float* out, const float* mask, const float* add,
                    long long rows, int L, bool mask_in, bool relu, bool mask_out, Drop drop);
+// encoder_train.hip: the two gradient forms of the same GEMM, on the caller's scratch.
+// dw (torch layout [Cout][Cin][K]) of the convolution `key` whose forward read `in` (times mask when mask_in) and whose output
+// gradient is dout; `part` holds wgrad_splits(rows) * K * Cin * Cout floats, added in a fixed order
+int wgrad_splits(long long rows);
+void gemm_conv_wgrad(us_frontend* h, hipStream_t s, const std::string& key, const float* in, const float* mask, bool mask_in, const float* dout,
+                     long long rows, int L, float* part, float* dw);
+// din = (add + dgrad(dout)) [gate > 0 ? * gate_scale : 0] [* mask]; `wd` holds the K * Cout * Cin floats of the flipped weight
+void gemm_conv_dgrad(us_frontend* h, hipStream_t s, const std::string& key, const float* dout, float* din, const float* mask, const float* add,
+                     const float* gate, float gate_scale, bool mask_out, long long rows, int L, float* wd);
+// frontend.hip: out[b][l] = x[b][:][l] | g[b][:] (channel-first in, channel-last out: the DurationPredictor's cat, :49-50)
+void fe_gather_concat(hipStream_t s, const float* x_cf, const float* g, float* out, int B, int L, int C, int S);
 
 }  // namespace us

@@ -420,6 +420,10 @@ void to_channel_first(hipStream_t s, const float* in, const float* mask, float* 
 
 }  // namespace
 
+void fe_gather_concat(hipStream_t s, const float* x_cf, const float* g, float* out, int B, int L, int C, int S) {
+  hipLaunchKernelGGL(fe_gather_concat_kernel, dim3(L, B), dim3(256), 0, s, x_cf, g, out, L, C, S);
+}
+
 // The Encoder's forward, once for both modes.  The two convolutions stay two: inference runs L of 100-300 and is latency-bound,
 // which the fixed-order fp32 FMA kernel above serves best; training runs B * L of several thousand rows on the MFMA GEMM that
 // its dgrad / wgrad share (they differ in summation order only).  The mode of the call picks, nothing else does.
@@ -614,7 +618,7 @@ int us_duration_predictor_forward(us_frontend_handle h, const float* x, const fl
   float* xin = fe_base(workspace);
   float* a1 = xin + rows * Cin;
   float* a2 = a1 + rows * F;
-  hipLaunchKernelGGL(fe_gather_concat_kernel, dim3(L, B), dim3(256), 0, s, x, g, xin, L, c.in_channels, c.spk_emb_dim);
+  fe_gather_concat(s, x, g, xin, B, L, c.in_channels, c.spk_emb_dim);
   // conv(x * mask) -> relu -> LayerNorm, twice (duration_predictor.py:51-58); proj(x * mask) * mask (:59)
   if ((rc = conv1d(h, s, "conv_1", xin, a1, x_mask, nullptr, B, L, true, true, false)) != US_OK) return rc;
   if ((rc = layernorm(h, s, "norm_1", a1, nullptr, a1, nullptr, rows, F, 1e-5f, false)) != US_OK) return rc;

@@ -9,9 +9,9 @@ duration_predictor, ...)` takes them where it takes the reference's modules.
 
 In eval mode the reference's Dropouts are the identity.  `Encoder(..., trainable=True)` in train mode runs the training forward
 of csrc/encoder_train.hip (every Dropout of the reference) through a `torch.autograd.Function` whose backward produces the
-gradient of every parameter; without `trainable=True` train mode is refused, and the duration predictor is inference only (its
-training branch, `reverse=False`: the MSE against log durations, :60-61, is not built).  There is no CPU fallback: tensors must
-live on a ROCm device.
+gradient of every parameter; `DurationPredictor(..., trainable=True)` does the same through csrc/duration_train.hip, including its
+training branch (`reverse=False`: the MSE against log durations, :60-61).  Without `trainable=True` train mode is refused.  There is
+no CPU fallback: tensors must live on a ROCm device.
 """
 from __future__ import annotations
 
@@ -203,7 +203,7 @@ class _FrontEndModule(torch.nn.Module):
         if device.type != "cuda":
             raise RuntimeError("the HIP front end needs tensors on a ROCm device (no CPU fallback); got " + str(device))
         if self.training and not training_ok:
-            hint = " or construct it with trainable=True to train it" if isinstance(self, Encoder) else ""
+            hint = " or construct it with trainable=True to train it"
             raise RuntimeError(f"{type(self).__name__} is inference-only (the reference's Dropout layers are not built): call .eval()"
                                + hint)
         lib = _lib.load()
@@ -369,10 +369,17 @@ class _EncoderTrain(torch.autograd.Function):
 
 
 class DurationPredictor(_FrontEndModule):
-    """`unitspeech/duration_predictor.py:24` `DurationPredictor(in_channels, filter_channels, kernel_size, p_dropout, spk_emb_dim=0)`."""
+    """`unitspeech/duration_predictor.py:24` `DurationPredictor(in_channels, filter_channels, kernel_size, p_dropout, spk_emb_dim=0)`.
 
-    def __init__(self, in_channels, filter_channels, kernel_size, p_dropout=0.0, spk_emb_dim=0):
+    Without `trainable=True` it is inference only (eval mode, `reverse=True`).  With it, a call made in train mode (both Dropouts at
+    p_dropout, seeded from torch's default generator) or in eval mode with grad enabled (no dropout) is differentiable with respect to
+    every parameter that requires grad: `reverse=True` returns logw, `reverse=False` the loss of :60-62 against `w`.  No gradient leaves
+    through `x` (the reference detaches it) or through `g` (a `g` that requires grad is refused rather than silently given None).
+    In eval mode under `torch.no_grad()` the inference path runs, so its bits are the non-trainable module's."""
+
+    def __init__(self, in_channels, filter_channels, kernel_size, p_dropout=0.0, spk_emb_dim=0, *, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.cfg = DurationPredictorConfig(int(in_channels), int(filter_channels), int(kernel_size), int(spk_emb_dim))
         self.p_dropout = p_dropout
         cin = in_channels + spk_emb_dim
@@ -387,16 +394,32 @@ class DurationPredictor(_FrontEndModule):
         c = _lib.us_duration_config(self.cfg.in_channels, self.cfg.filter_channels, self.cfg.kernel_size, self.cfg.spk_emb_dim)
         _lib.check(lib.us_duration_predictor_create(C.byref(self._h), C.byref(c)), None, "us_duration_predictor_create")
 
-    @torch.no_grad()
     def forward(self, x, x_mask, w=None, g=None, reverse=False):
-        """x [B, in_channels, L], x_mask [B, 1, L], g [B, 1, spk_emb_dim] -> logw [B, 1, L] (reverse=True only)."""
-        if not reverse:
-            raise NotImplementedError("DurationPredictor(reverse=False) (the training loss, duration_predictor.py:60-61) is not built")
+        """x [B, in_channels, L], x_mask [B, 1, L], g [B, 1, spk_emb_dim] -> logw [B, 1, L] (reverse=True), or with w [B, 1, L] the
+        scalar loss sum((logw - log(w + 1e-6) x_mask)^2) / sum(x_mask) (reverse=False, trainable=True only)."""
+        if not reverse and not self.trainable:
+            raise NotImplementedError("DurationPredictor(reverse=False) (the training loss, duration_predictor.py:60-61) needs "
+                                      "trainable=True")
         if x.dim() != 3 or x.shape[1] != self.cfg.in_channels or x_mask.shape != (x.shape[0], 1, x.shape[2]):
             raise ValueError(f"DurationPredictor: expected x [B, {self.cfg.in_channels}, L] and x_mask [B, 1, L], got {tuple(x.shape)} "
                              f"and {tuple(x_mask.shape)}")
         if (g is None) != (self.cfg.spk_emb_dim == 0) or (g is not None and tuple(g.shape) != (x.shape[0], 1, self.cfg.spk_emb_dim)):
             raise ValueError(f"DurationPredictor: g must be [B, 1, {self.cfg.spk_emb_dim}] (None iff spk_emb_dim == 0)")
+        if not reverse and (w is None or w.numel() != x_mask.numel()):
+            raise ValueError("DurationPredictor(reverse=False): w [B, 1, L] (the target durations) is required")
+        if self.trainable and (self.training or torch.is_grad_enabled()):
+            if g is not None and g.requires_grad:
+                raise RuntimeError("DurationPredictor: g requires grad, but this module returns no gradient for g (conv_1's data gradient "
+                                   "is not built); pass g.detach()")
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.training else 0
+            params = list(self.state_dict(keep_vars=True).values())
+            logw = _DurationTrain.apply(self, x, x_mask, g, seed, float(self.p_dropout) if self.training else -1.0, *params)
+        else:
+            logw = self._forward_eval(x, x_mask, g)
+        return logw if reverse else _DurationMseFn.apply(logw, w, x_mask)
+
+    @torch.no_grad()
+    def _forward_eval(self, x, x_mask, g):
         device = x.device
         lib, stream = self._sync(device)
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
@@ -409,3 +432,78 @@ class DurationPredictor(_FrontEndModule):
                                                    logw.data_ptr(), x.shape[0], x.shape[2], ws.data_ptr(), ws.numel(), stream)
         self._check(lib, rc, "us_duration_predictor_forward")
         return logw
+
+
+def _release_duration_tape(dp_ref, ptr):
+    dp = dp_ref()
+    if dp is not None and getattr(dp, "_h", None):
+        _lib.load().us_duration_predictor_tape_release(dp._h, ptr)
+
+
+class _DurationTrain(torch.autograd.Function):
+    """us_duration_predictor_forward_train / us_duration_predictor_backward.  Each call owns its workspace (the tape), kept in ctx
+    until backward.  p < 0 runs without dropout (the reference in eval mode, differentiated)."""
+
+    @staticmethod
+    def forward(ctx, dp, x, x_mask, g, seed, p, *params):
+        device = x.device
+        lib, stream = dp._sync(device, training_ok=True)
+        b, l = x.shape[0], x.shape[2]
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        xs, ms = f32(x), f32(x_mask)
+        gs = f32(g) if g is not None else None
+        logw = torch.empty(b, 1, l, device=device)
+        ws = torch.empty(int(lib.us_duration_predictor_train_workspace_bytes(dp._h, b, l)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            rc = lib.us_duration_predictor_forward_train(dp._h, xs.data_ptr(), ms.data_ptr(), gs.data_ptr() if gs is not None else None,
+                                                         logw.data_ptr(), b, l, p, seed, ws.data_ptr(), ws.numel(), stream)
+        dp._check(lib, rc, "us_duration_predictor_forward_train")
+        ctx.dp, ctx.ws, ctx.shape = dp, ws, (b, l)
+        ctx.keys = list(dp.state_dict(keep_vars=True).keys())
+        ctx.versions = [(t.data_ptr(), t._version) for t in params]
+        weakref.finalize(ws, _release_duration_tape, weakref.ref(dp), ws.data_ptr())
+        return logw
+
+    @staticmethod
+    def backward(ctx, g_logw):
+        dp, ws, (b, l) = ctx.dp, ctx.ws, ctx.shape
+        params = list(dp.state_dict(keep_vars=True).values())
+        if [(t.data_ptr(), t._version) for t in params] != ctx.versions:
+            raise RuntimeError("DurationPredictor backward: a parameter was modified in place after the training forward (the tape holds "
+                               "activations of the old weights); run the forward again")
+        device = ws.device
+        lib, stream = dp._sync(device, training_ok=True)
+        need = ctx.needs_input_grad[6:]
+        shapes = duration_predictor_state_shapes(dp.cfg)
+        grads = [torch.empty(shapes[k], device=device) if n else None for k, n in zip(ctx.keys, need)]
+        sel = [(k, g) for k, g in zip(ctx.keys, grads) if g is not None]
+        keys = (C.c_char_p * max(len(sel), 1))(*[k.encode() for k, _ in sel])
+        ptrs = (C.c_void_p * max(len(sel), 1))(*[g.data_ptr() for _, g in sel])
+        gl = g_logw.detach().to(device=device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(device):
+            rc = lib.us_duration_predictor_backward(dp._h, gl.data_ptr(), b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(), stream)
+        dp._check(lib, rc, "us_duration_predictor_backward")
+        return (None,) * 6 + tuple(grads)
+
+
+class _DurationMseFn(torch.autograd.Function):
+    """us_duration_predictor_mse_loss: duration_predictor.py:60-62, differentiable in logw."""
+
+    @staticmethod
+    def forward(ctx, logw, w, x_mask):
+        device = logw.device
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        lw, ww, m = f32(logw), f32(w), f32(x_mask)
+        loss = torch.empty((), device=device)
+        d_logw = torch.empty_like(lw)
+        with torch.cuda.device(device):
+            rc = _lib.load().us_duration_predictor_mse_loss(lw.data_ptr(), ww.data_ptr(), m.data_ptr(), loss.data_ptr(), d_logw.data_ptr(),
+                                                            lw.shape[0], lw.shape[-1], C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+        _lib.check(rc, None, "us_duration_predictor_mse_loss")
+        ctx.save_for_backward(d_logw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_logw,) = ctx.saved_tensors
+        return d_logw * g, None, None

@@ -5,14 +5,22 @@ launches.
 `maximum_path` a drop-in for the external `monotonic_align.maximum_path` (:343) that runs on the device and never copies the
 [B, Tx, Ty] table to the host, `align` both in one call with the durations MAS implies, and `duration_loss` the MSE of the log
 durations (:348-349, `util.duration_loss` after `log(1e-8 + sum(attn))`), differentiable in logw.
+
+`compute_train_step_loss` assembles the whole iteration (:319-387) from those, the trainable `Encoder` and `DurationPredictor`, the
+crop and prior loss of `unit_encoder_train` and the decoder's `compute_loss`; `random_replace_tensor` is the speaker swap of
+:325-326.
 """
 from __future__ import annotations
 
 import torch
 
-from . import _lib
+from typing import Optional, Sequence
 
-__all__ = ["mas_log_prior", "maximum_path", "maximum_path_lengths", "align", "duration_loss"]
+from . import _lib
+from .unit_encoder_train import align_segment, prior_loss
+
+__all__ = ["mas_log_prior", "maximum_path", "maximum_path_lengths", "align", "duration_loss", "random_replace_tensor",
+           "compute_train_step_loss"]
 
 
 def _stream():
@@ -115,3 +123,40 @@ def duration_loss(logw, durations, x_mask, x_lengths):
     """train_STEP1.py:348-349: sum((logw - log(1e-8 + durations) x_mask)^2) / sum(x_lengths) with logw, x_mask [B, 1, Tx] and
     durations [B, Tx] (the row sums of MAS's attn); differentiable in logw, which must be fp32."""
     return _DurationLossFn.apply(logw, durations, x_mask, x_lengths)
+
+
+def random_replace_tensor(spk_embs, replacement_emb, replace_percentage: float = 0.25):
+    """`util.random_replace_tensor` (train_STEP1.py:325-326): int(replace_percentage * B) items, the first of `torch.randperm(B)` on
+    the default CPU generator, are replaced by `replacement_emb`.  Works on a copy: the caller's tensor is left as it was."""
+    out = spk_embs.clone()
+    n = int(spk_embs.size(0) * replace_percentage)
+    idx = torch.randperm(spk_embs.size(0))[:n]
+    if n:
+        out[idx.to(out.device)] = replacement_emb.detach().to(out).reshape((1,) + tuple(out.shape[1:]))
+    return out
+
+
+def compute_train_step_loss(text_encoder, duration_predictor, decoder, x, x_lengths, y, y_lengths, spk_emb, out_size, *,
+                            spk_uncond: Optional[torch.Tensor] = None, starts: Optional[Sequence[int]] = None,
+                            t: Optional[torch.Tensor] = None, aux: Optional[dict] = None):
+    """`compute_train_step_loss` (train_STEP1.py:319-387) -> (dur_loss, prior_loss, diff_loss).  x [B, Tx] symbol ids, y [B, n_feats,
+    Ty], spk_emb [B, 1, spk_emb_dim]; `spk_uncond` enables the speaker swap, `starts` fixes the crop offsets (else `random.choice`, as
+    the reference), `t` the diffusion times (else `compute_loss` draws them).  Gradients reach the encoder through mu_x (prior and
+    diffusion loss), the predictor through logw only (its input is detached), and every decoder parameter.  The [B, Tx, Ty] table
+    stays on the device.  A dict given as `aux` receives attn, durations, y_mask and mu_y."""
+    if spk_uncond is not None:
+        spk_emb = random_replace_tensor(spk_emb, spk_uncond)
+    mu_x, h, x_mask = text_encoder(x, x_lengths)
+    logw = duration_predictor(h.detach(), x_mask, w=None, g=spk_emb, reverse=True)
+    Ty = y.shape[-1]
+    y_mask = (torch.arange(Ty, device=y.device).unsqueeze(0) < y_lengths.to(y.device).unsqueeze(1)).unsqueeze(1).to(x_mask.dtype)
+    attn, durations = align(mu_x, y, x_mask, y_mask, x_lengths, y_lengths)
+    dur_loss = duration_loss(logw, durations, x_mask, x_lengths)
+    y_seg, seg_mask, mu_y = align_segment(mu_x, y, y_lengths, attn, out_size, starts)
+    if t is None:
+        diff_loss, _ = decoder.compute_loss(y_seg, seg_mask, mu_y, spk_emb=spk_emb)
+    else:
+        diff_loss, _ = decoder.loss_t(y_seg, seg_mask, mu_y, t, spk_emb)
+    if aux is not None:
+        aux.update(attn=attn, durations=durations, y_mask=seg_mask, mu_y=mu_y)
+    return dur_loss, prior_loss(y_seg, mu_y, seg_mask), diff_loss
