@@ -10,7 +10,8 @@
   --features F  the OUTPUTS of the reference's pre-steps (finetune.py:86-128) from a `.pt` (torch.save of a dict) or `.npz` file, so the
                 speaker embedder / unit extractor can run wherever their checkpoints live and the adaptation here:
                   mel        [1, 80, L]   normalised to [-1, 1] as finetune.py:104 leaves it (or raw with "mel_is_normalized": False)
-                  spk_emb    [1, 256] or [1, 1, 256]   (divided by its norm here, :110)
+                  spk_emb    [1, 256] or [1, 1, 256]   (divided by its norm here, :110); or  spk_hidden_states [L, 1, T, C], the
+                             speaker encoder's upstream hidden states (ecapa_tdnn.py:262-264) + --speaker_encoder_checkpoint (:106-110)
                   duration   [1, Lu]      frames per unit (process_unit, :114)
                   cond_x     [1, 80, Lu]  the unit encoder's output (:123); or  unit [1, Lu] int64 + --unit_encoder_checkpoint (:66-79)
                   mel_min, mel_max        scalars (else the decoder checkpoint's, :98-99)
@@ -40,8 +41,9 @@ def load_features(args, cfg, base, device):
     else:
         d = torch.load(path, map_location="cpu")
     d = {k: (torch.as_tensor(v) if not isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+    hip_spk = bool(args.speaker_encoder_checkpoint) and "spk_emb" not in d and "spk_hidden_states" in d
     for k in ("mel", "spk_emb", "duration"):
-        if k not in d:
+        if k not in d and not (k == "spk_emb" and hip_spk):
             raise SystemExit(f"--features {path}: missing `{k}`")
 
     def scalar(name):
@@ -58,10 +60,17 @@ def load_features(args, cfg, base, device):
         raise SystemExit(f"--features: mel must be [1, {cfg.n_feats}, L], got {tuple(mel.shape)}")
     if "mel_is_normalized" in d and not bool(d["mel_is_normalized"]):
         mel = (mel - mel_min) / (mel_max - mel_min) * 2 - 1                      # finetune.py:104
-    spk = d["spk_emb"].float().reshape(1, 1, -1)
-    if spk.shape[-1] != cfg.spk_emb_dim:
-        raise SystemExit(f"--features: spk_emb must have {cfg.spk_emb_dim} elements, got {spk.shape[-1]}")
-    spk = spk / spk.norm()                                                       # :110
+    if hip_spk:
+        from unitspeech_amd.speaker_encoder import load_speaker_encoder_checkpoint
+        hidden = d["spk_hidden_states"].float()
+        spk_embedder = load_speaker_encoder_checkpoint(args.speaker_encoder_checkpoint, device, feat_dim=int(hidden.shape[-1]),
+                                                       emb_dim=cfg.spk_emb_dim)                      # :48-49
+        spk = spk_embedder.embed(hidden.to(device)).reshape(1, 1, -1)                              # :106-110, the norm included
+    else:
+        spk = d["spk_emb"].float().reshape(1, 1, -1)
+        if spk.shape[-1] != cfg.spk_emb_dim:
+            raise SystemExit(f"--features: spk_emb must have {cfg.spk_emb_dim} elements, got {spk.shape[-1]}")
+        spk = spk / spk.norm()                                                   # :110
     duration = d["duration"].float().reshape(1, -1)
     if "cond_x" in d:
         cond_x = d["cond_x"].float()
@@ -101,6 +110,10 @@ def main():
     ap.add_argument("--features", type=str, default=None, help="file with the pre-step tensors of finetune.py:86-128 (see the module docstring)")
     ap.add_argument("--unit_encoder_checkpoint", type=str, default=None, help="--features with `unit` instead of `cond_x`: the unit encoder's "
                                                                               "checkpoint ({'model': state_dict}, finetune.py:77-78)")
+    ap.add_argument("--speaker_encoder_checkpoint", type=str, default=None, help="--features with `spk_hidden_states` instead of `spk_emb`: the "
+                    "speaker encoder's checkpoint ({'model': state_dict}, util.py:183-188); the embedding comes from the HIP ECAPA-TDNN")
+    ap.add_argument("--hip_speaker_encoder", action="store_true", help="--synthetic: spk_emb from the HIP ECAPA-TDNN (seeded weights) on "
+                    "synthetic upstream hidden states instead of a random vector")
     ap.add_argument("--learned_frontend", action="store_true", help="--synthetic: cond_x from the HIP unit encoder (seeded weights) on synthetic units")
     ap.add_argument("--reference_root", type=str, default=None)
     ap.add_argument("--out_dir", type=str, default="checkpoints/inference")
@@ -151,8 +164,16 @@ def main():
             unit = torch.from_numpy(g.integers(0, ec.n_vocab, size=(1, Lu)).astype(np.int64)).to(device)
             cond_x, _, _ = unit_encoder.to(device).eval()(unit, torch.LongTensor([Lu]).to(device))
         duration = torch.full((1, Lu), 3.0, device=device)
-        spk = torch.from_numpy(g.standard_normal((1, 1, cfg.spk_emb_dim), dtype=np.float32)).to(device)
-        spk_emb = spk / spk.norm()
+        if args.hip_speaker_encoder:
+            # finetune.py:106-110: spk_emb is the ECAPA-TDNN's embedding of the reference utterance over its norm; here the HIP module
+            # at the reference's sizes (WavLM-large: 25 hidden states of 1024) with seeded weights on 3 s of seeded hidden states
+            from unitspeech_amd.speaker_encoder import synthetic_speaker_embedder, synthetic_hidden_states
+            spk_embedder = synthetic_speaker_embedder(cfg.spk_emb_dim).to(device)
+            hidden = torch.from_numpy(synthetic_hidden_states(25, 1, 149, 1024, args.ID & 0xffff)).to(device)
+            spk_emb = spk_embedder.embed(hidden).reshape(1, 1, -1)
+        else:
+            spk = torch.from_numpy(g.standard_normal((1, 1, cfg.spk_emb_dim), dtype=np.float32)).to(device)
+            spk_emb = spk / spk.norm()
         mel_min, mel_max = torch.tensor(-11.5), torch.tensor(2.0)
     else:
         if not args.reference_root:

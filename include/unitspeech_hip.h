@@ -408,6 +408,43 @@ size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T);
 int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
                        us_stream stream);
 
+/* ---- ECAPA-TDNN speaker encoder (unitspeech/speaker_encoder/ecapa_tdnn.py:164-287, eval mode) --------------------------------
+ * The upstream model's hidden states [L][B][T][feat_dim] -> embedding [B][emb_dim]: the softmax(feature_weight)-weighted sum of the L
+ * hidden states, InstanceNorm1d, the ECAPA-TDNN trunk (k = 5 convolution, three SE-Res2 blocks with dilations 2 / 3 / 4, the 1536-channel
+ * 1x1 convolution, attentive statistics pooling, BatchNorm1d, Linear) and, on request, the division by the norm (finetune.py:110).  fp32
+ * storage and accumulation, exact fp32 products.  The upstream model itself (WavLM / HuBERT) and the fbank / mfcc extraction are not
+ * part of the library.  Same conventions as the vocoder handle: weights are loaded one state_dict tensor at a time from DEVICE memory
+ * in the reference's key names (every floating-point key except `feature_extract.*`; BatchNorm runs from its running statistics), the
+ * caller owns the activation scratch (us_speaker_workspace_bytes), a forward call allocates nothing and only enqueues on `stream`, and
+ * a call made while another device than the handle's is current is refused (US_EINVAL).  Every reduction has a fixed order: repeated
+ * calls, and batch items alone or together, give the same bits.  SE_Res2Block shortcuts (in_channels != out_channels) do not occur in
+ * the reference's configuration and are refused (US_ENOKEY for a `.shortcut.` key); channels must be a multiple of 8, at most 512. */
+typedef struct us_speaker* us_speaker_handle;
+typedef struct us_speaker_config {
+  int32_t feat_dim;                      /* 1024 (WavLM-large hidden size) */
+  int32_t channels;                      /* 512 */
+  int32_t emb_dim;                       /* 256 */
+  int32_t n_layers;                      /* length of feature_weight: 25 for WavLM-large; 0 = no feature_weight (fbank / mfcc form) */
+  int32_t global_context_att;            /* 0 / 1: AttentiveStatsPool's global context */
+} us_speaker_config;
+enum { US_SPEAKER_STAGE_FEAT = 0, US_SPEAKER_STAGE_LAYER1 = 1, US_SPEAKER_STAGE_BLOCKS = 2, US_SPEAKER_STAGE_POOLING = 3 };
+int us_speaker_create(us_speaker_handle* out, const us_speaker_config* cfg);
+int us_speaker_destroy(us_speaker_handle h);
+int us_speaker_load_weight(us_speaker_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_speaker_num_weights(us_speaker_handle h);
+const char* us_speaker_weight_key(us_speaker_handle h, int i);
+const char* us_speaker_last_error(us_speaker_handle h);
+size_t us_speaker_workspace_bytes(us_speaker_handle h, int B, int T);
+/* `ECAPA_TDNN.forward` from get_feat's input on (:261-287).  hidden_states is [L][B][T][feat_dim] with L = n_layers, or, with L = 0, the
+ * already combined [B][feat_dim][T] (which only gets the InstanceNorm1d).  Any T >= 1; all items of a batch share T (the reference has
+ * no masking).  emb_out [B][emb_dim]; normalize = 1 divides the whole output by its norm (B = 1 only), 0 returns the raw output. */
+int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, int B, int T, float* emb_out, int normalize, void* workspace,
+                       size_t workspace_bytes, us_stream stream);
+/* Debug view of an intermediate the last us_speaker_forward(B, T) left in `workspace`: *data points into it, shape[3] is its extent.
+ * FEAT [B][feat_dim][T] after get_feat, LAYER1 [B][channels][T], BLOCKS [B][3 channels][T] (layer2 | layer3 | layer4 along the
+ * channels, the input of `conv`), POOLING [B][3072][1] (mean | std, before `bn`).  Enqueues nothing. */
+int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

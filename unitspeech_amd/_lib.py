@@ -40,6 +40,11 @@ class us_vocoder_config(C.Structure):
 
 US_VOCODER_SNAKE, US_VOCODER_SNAKEBETA = 0, 1
 
+
+class us_speaker_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("feat_dim", "channels", "emb_dim", "n_layers", "global_context_att")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -118,6 +123,15 @@ SIGNATURES = {
     "us_vocoder_last_error": (C.c_char_p, [C.c_void_p]),
     "us_vocoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "us_vocoder_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_speaker_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_speaker_config)]),
+    "us_speaker_destroy": (C.c_int, [C.c_void_p]),
+    "us_speaker_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "us_speaker_num_weights": (C.c_int, [C.c_void_p]),
+    "us_speaker_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "us_speaker_last_error": (C.c_char_p, [C.c_void_p]),
+    "us_speaker_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "us_speaker_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_speaker_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "us_debug_block": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

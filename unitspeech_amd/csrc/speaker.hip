@@ -1,0 +1,837 @@
+// ECAPA-TDNN speaker encoder, eval-mode forward (the reference's unitspeech/speaker_encoder/ecapa_tdnn.py:248-287 `get_feat` +
+// `forward`, :15-161 the modules they call): the upstream model's hidden states [L][B][T][C] -> embedding [B][emb_dim], fp32
+// storage and fp32 accumulation throughout.
+//
+// Activations are planar [B][C][T] (time contiguous), the layout of the reference's tensors.  The kernels:
+//  - sp_combine_kernel: the softmax-weighted sum over the L hidden states (+ 1e-6), read once and coalesced along C, transposed
+//    through LDS into [B][C][T];  sp_instnorm_kernel: InstanceNorm1d, one wave per (b, c) row.
+//  - sp_conv_kernel: every dense convolution (layer1's k = 5, the 1x1 ones, the pooling's two) as an implicit GEMM on the fp32 matrix
+//    cores (v_mfma_f32_32x32x2_f32, exact fp32 products): D[co][t] = sum_kk W[co][kk] X[kk][t], kk = tap * Cin + ci.  Epilogue: bias,
+//    a per-(b, co) bias (the global-context terms of the pooling), ReLU / tanh, then the eval-mode BatchNorm as one scale and one
+//    shift per channel (it follows the ReLU, so it cannot live in the weights).
+//  - sp_res2_kernel: the seven chained width -> width k = 3 dilated convolutions of a Res2Conv1dReluBn for one time tile, the running
+//    chunk held in LDS with a 7 * dilation halo on either side; plain fp32 FMAs (the vector units have the fp32 matrix cores' rate and
+//    the chunks are 64 channels at most), each lane one time step, the weights wave-uniform.
+//  - sp_rowmean_kernel / sp_se_kernel / sp_scale_res_kernel: SE_Connect and the block residual.
+//  - sp_rowstats_kernel / sp_ctx_bias_kernel: the global-context mean / std and their share of pooling.linear1 as a bias.
+//  - sp_pool_kernel: softmax over T and the weighted mean / std per (b, c) row, `bn` applied;  sp_linear_kernel;  sp_normalize_kernel.
+// Every reduction is a fixed-order tree inside one wave (or a fixed-order loop over waves): no atomics, so a batch item's result
+// does not depend on its neighbours or on the run.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/unitspeech_hip.h"
+#include "kernels.h"
+
+namespace us {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kSpOut = 1536;       // ecapa_tdnn.py:222: channels of `conv` and of the pooling
+constexpr int kSpAtt = 128;        // se_bottleneck_dim and attention_channels (:225-232)
+constexpr int kSpScale = 8;        // Res2 scale
+constexpr int kSpStages = kSpScale - 1;
+constexpr float kBnEps = 1e-5f;
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// ---- feature combine + instance norm (get_feat, :261-271) ------------------------------------------------------------------
+constexpr int kCmbT = 16, kCmbC = 64;
+
+__global__ __launch_bounds__(256) void sp_combine_kernel(const float* __restrict__ h, const float* __restrict__ lw, float* __restrict__ x,
+                                                         int L, int B, int T, int C) {
+  __shared__ float tile[kCmbT][kCmbC + 1];
+  const int tid = threadIdx.x, cl = tid & 63, tr = tid >> 6;
+  const int c0 = blockIdx.x * kCmbC, t0 = blockIdx.y * kCmbT, b = blockIdx.z;
+  const int c = c0 + cl;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  const size_t lstride = (size_t)B * T * C;
+  const float* hb = h + (size_t)b * T * C + c;
+  for (int l = 0; l < L; ++l) {
+    const float wl = lw[l];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int t = t0 + tr + 4 * i;
+      if (t < T && c < C) acc[i] = fmaf(wl, hb[(size_t)l * lstride + (size_t)t * C], acc[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tile[tr + 4 * i][cl] = acc[i] + 1e-6f;
+  __syncthreads();
+  const int cc = tid >> 2, tq = (tid & 3) * 4;
+  if (c0 + cc < C) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = t0 + tq + j;
+      if (t < T) x[((size_t)b * C + c0 + cc) * T + t] = tile[tq + j][cc];
+    }
+  }
+}
+
+__global__ void sp_layer_softmax_kernel(const float* __restrict__ w, float* __restrict__ lw, int L) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float m = w[0];
+  for (int l = 1; l < L; ++l) m = fmaxf(m, w[l]);
+  float s = 0.f;
+  for (int l = 0; l < L; ++l) s += expf(w[l] - m);
+  for (int l = 0; l < L; ++l) lw[l] = expf(w[l] - m) / s;
+}
+
+// InstanceNorm1d without affine: biased variance over T, eps 1e-5.  One wave per row; `out` may be `in`.
+__global__ __launch_bounds__(256) void sp_instnorm_kernel(const float* in, float* out, int rows, int T) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* r = in + (size_t)row * T;
+  float s = 0.f;
+  for (int t = lane; t < T; t += 64) s += r[t];
+  const float mean = wave_sum(s) / (float)T;
+  float v = 0.f;
+  for (int t = lane; t < T; t += 64) {
+    const float d = r[t] - mean;
+    v = fmaf(d, d, v);
+  }
+  const float rs = 1.f / sqrtf(wave_sum(v) / (float)T + 1e-5f);
+  float* o = out + (size_t)row * T;
+  for (int t = lane; t < T; t += 64) o[t] = (r[t] - mean) * rs;
+}
+
+// ---- implicit-GEMM convolution ------------------------------------------------------------------------------------------------
+// out[b][co][t] = post(bias[co] + bias2[b][co] + sum_{j < taps, ci} P[j * Cin + ci][co] * in[b][ci][t + j - taps / 2]), in[] = 0 outside
+// [0, T).  P is packed once with its rows padded to a multiple of kSpBK and its columns to a multiple of kSpBM (zeros).  `in` and `out`
+// carry their own batch strides, so a tensor may be a channel slice of a wider one (the [out2, out3, out4] concatenation is written in
+// place by the three blocks).
+constexpr int kSpBM = 64;      // output channels per workgroup
+constexpr int kSpBN = 64;      // time steps per workgroup
+constexpr int kSpBK = 16;      // reduction slice per LDS stage
+enum { kActNone = 0, kActRelu = 1, kActTanh = 2 };
+
+struct SpConvArgs {
+  const float* in;
+  const float* w;             // [Kpad][ldw]
+  const float* bias;          // [Cout]
+  const float* bias2;         // [B][Cout] or null
+  const float* scale;         // [Cout] or null: applied with shift after the activation
+  const float* shift;
+  float* out;
+  long long in_bs, out_bs;    // floats between batch items
+  int Cin, Cout, T, taps, Kdim, Kpad, ldw, act;
+};
+
+__global__ __launch_bounds__(256) void sp_conv_kernel(SpConvArgs a) {
+  __shared__ float As[2][kSpBK][kSpBM];
+  __shared__ float Bs[2][kSpBK][kSpBN];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int mh = wave & 1, nh = wave >> 1;              // wave tile: 32 channels x 32 steps
+  const int b = blockIdx.z;
+  const int m0 = blockIdx.y * kSpBM, n0 = blockIdx.x * kSpBN;
+  const float* __restrict__ in = a.in + (size_t)b * a.in_bs;
+  const float* __restrict__ w = a.w;
+  const int off = -(a.taps / 2);
+  const int wr = tid >> 4, wc = (tid & 15) * 4;
+  const int xr = tid >> 4, xc = tid & 15;
+  float4 wreg;
+  float xreg[4];
+  auto load = [&](int k0) {
+    wreg = *reinterpret_cast<const float4*>(w + (size_t)(k0 + wr) * a.ldw + m0 + wc);
+    const int kk = k0 + xr;
+    const bool live = kk < a.Kdim;
+    const int j = live ? kk / a.Cin : 0, ci = live ? kk - j * a.Cin : 0;
+    const float* row = in + (size_t)ci * a.T;
+    const int t0 = n0 + off + j;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int t = t0 + xc + 16 * i;
+      xreg[i] = (live && t >= 0 && t < a.T) ? row[t] : 0.f;
+    }
+  };
+  auto store = [&](int buf) {
+    *reinterpret_cast<float4*>(&As[buf][wr][wc]) = wreg;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) Bs[buf][xr][xc + 16 * i] = xreg[i];
+  };
+  f32x16 acc[2];
+#pragma unroll
+  for (int n = 0; n < 2; ++n)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+  const int nk = a.Kpad / kSpBK;
+  load(0);
+  store(0);
+  __syncthreads();
+  const int kl = lane >> 5, cl = lane & 31;
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) load((kt + 1) * kSpBK);
+#pragma unroll
+    for (int s = 0; s < kSpBK / 2; ++s) {          // two accumulators in turn: no MFMA waits on the one before it
+      const float fa = As[cur][2 * s + kl][mh * 32 + cl];
+      const float fb = Bs[cur][2 * s + kl][nh * 32 + cl];
+      acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[s & 1], 0, 0, 0);
+    }
+    if (kt + 1 < nk) store(cur ^ 1);
+    __syncthreads();
+  }
+  // D layout (32x32 f32 MFMA): column = lane & 31, row = 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
+  const int t = n0 + nh * 32 + cl;
+  if (t >= a.T) return;
+  float* __restrict__ out = a.out + (size_t)b * a.out_bs;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int co = m0 + mh * 32 + 8 * (r >> 2) + 4 * kl + (r & 3);
+    if (co >= a.Cout) continue;
+    float v = (acc[0][r] + acc[1][r]) + a.bias[co];
+    if (a.bias2) v += a.bias2[(size_t)b * a.Cout + co];
+    if (a.act == kActRelu) v = fmaxf(v, 0.f);
+    else if (a.act == kActTanh) v = tanhf(v);
+    if (a.scale) v = fmaf(v, a.scale[co], a.shift[co]);
+    out[(size_t)co * a.T + t] = v;
+  }
+}
+
+// P[kk][co] (zero padded), kk = j * Cin + ci, from a Conv1d weight W[Cout][CinTot][k] of which the first Cin input channels are taken
+__global__ void sp_pack_kernel(const float* __restrict__ w, float* __restrict__ p, int Cin, int CinTot, int Cout, int k, int Kpad, int ldw) {
+  const size_t n = (size_t)Kpad * ldw;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int co = (int)(i % ldw), kk = (int)(i / ldw);
+    float v = 0.f;
+    if (co < Cout && kk < k * Cin) {
+      const int j = kk / Cin, ci = kk - j * Cin;
+      v = w[((size_t)co * CinTot + ci) * k + j];
+    }
+    p[i] = v;
+  }
+}
+
+// BatchNorm1d in eval mode as y = x * scale + shift
+__global__ void sp_bnfold_kernel(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ rm, const float* __restrict__ rv,
+                                 float* __restrict__ scale, float* __restrict__ shift, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float s = w[i] / sqrtf(rv[i] + kBnEps);
+  scale[i] = s;
+  shift[i] = b[i] - rm[i] * s;
+}
+
+// ---- Res2Conv1dReluBn (:35-51) --------------------------------------------------------------------------------------------------
+// One workgroup: batch item b, output steps [t0, t0 + TT), all seven stages.  Its LDS window holds kRes2W = TT + 14 * dil positions,
+// position p <-> time t0 - 7 dil + p.  Stage i reads the window S (= stage i - 1's output + split i; split 0 for i = 0) and writes
+// bn(relu(conv(S))) over the WHOLE window, taking S as zero beyond the window's ends: a position within (i + 1) dil of an end is then
+// wrong, which after seven stages still leaves the TT central ones exact.  A position outside [0, T) is forced to zero at every stage
+// (each convolution pads its own input with zeros; the value the previous stage would compute there from zeros is not one).
+// Lane = position, so the weights of a (ci, tap) are wave-uniform: 16 output channels per lane, packed contiguously.
+constexpr int kRes2W = 128;
+constexpr int kRes2Co = 16;
+
+__global__ __launch_bounds__(512) void sp_res2_kernel(const float* __restrict__ y, float* __restrict__ out, const float* __restrict__ wp,
+                                                      const float* __restrict__ bss, int width, int wpad, int T, int dil, int TT) {
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.y, t0 = blockIdx.x * TT, halo = kSpStages * dil, base = t0 - halo;
+  const size_t bo = (size_t)b * kSpScale * width * T;
+  const float* __restrict__ yb = y + bo;
+  float* __restrict__ ob = out + bo;
+  const int half = width * kRes2W;              // the two windows: stage i reads the one at (i & 1) * half and writes the other
+  for (int idx = tid; idx < width * kRes2W; idx += 512) {
+    const int ci = idx / kRes2W, p = idx - ci * kRes2W, t = base + p;
+    lds[idx] = (t >= 0 && t < T) ? yb[(size_t)ci * T + t] : 0.f;
+  }
+  // the eighth split passes through (:47-48)
+  for (int idx = tid; idx < width * TT; idx += 512) {
+    const int ci = idx / TT, t = t0 + idx - ci * TT;
+    if (t < T) ob[(size_t)((kSpScale - 1) * width + ci) * T + t] = yb[(size_t)((kSpScale - 1) * width + ci) * T + t];
+  }
+  __syncthreads();
+  const int p = (wave & 1) * 64 + lane, t = base + p, cog = wave >> 1;
+  const bool inside = t >= 0 && t < T;
+  const bool centre = inside && p >= halo && p < halo + TT;
+  const bool lo = p - dil >= 0, hi = p + dil < kRes2W;
+  for (int i = 0; i < kSpStages; ++i) {
+    const float* __restrict__ cur = lds + (i & 1) * half;
+    float* __restrict__ nxt = lds + ((i & 1) ^ 1) * half;
+    const float* __restrict__ wi = wp + (size_t)i * width * 3 * wpad;
+    const float* __restrict__ bi = bss + (size_t)i * 3 * wpad;
+    for (int co0 = cog * kRes2Co; co0 < width; co0 += 4 * kRes2Co) {
+      float acc[kRes2Co];
+#pragma unroll
+      for (int j = 0; j < kRes2Co; ++j) acc[j] = bi[co0 + j];
+      for (int ci = 0; ci < width; ++ci) {
+        const float* row = cur + ci * kRes2W + p;
+        const float xm = lo ? row[-dil] : 0.f, x0 = row[0], xp = hi ? row[dil] : 0.f;
+        const float* __restrict__ w = wi + (size_t)ci * 3 * wpad + co0;
+#pragma unroll
+        for (int j = 0; j < kRes2Co; ++j) {
+          acc[j] = fmaf(w[j], xm, acc[j]);
+          acc[j] = fmaf(w[wpad + j], x0, acc[j]);
+          acc[j] = fmaf(w[2 * wpad + j], xp, acc[j]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kRes2Co; ++j) {
+        const int co = co0 + j;
+        if (co >= width) break;
+        float v = fmaf(fmaxf(acc[j], 0.f), bi[wpad + co], bi[2 * wpad + co]);
+        v = inside ? v : 0.f;
+        if (centre) ob[(size_t)(i * width + co) * T + t] = v;
+        if (i + 1 < kSpStages) nxt[co * kRes2W + p] = v + (inside ? yb[(size_t)((i + 1) * width + co) * T + t] : 0.f);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// stage i of a block: wp[i][ci][tap][co] (co padded to wpad with zeros) and bss[i][{bias, bn scale, bn shift}][co]
+__global__ void sp_res2_pack_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ bw,
+                                    const float* __restrict__ bb, const float* __restrict__ rm, const float* __restrict__ rv, float* __restrict__ wp,
+                                    float* __restrict__ bss, int width, int wpad) {
+  const int n = width * 3 * wpad;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int co = i % wpad, k = (i / wpad) % 3, ci = i / (3 * wpad);
+    wp[i] = co < width ? w[((size_t)co * width + ci) * 3 + k] : 0.f;
+  }
+  for (int co = blockIdx.x * blockDim.x + threadIdx.x; co < wpad; co += gridDim.x * blockDim.x) {
+    const bool live = co < width;
+    const float s = live ? bw[co] / sqrtf(rv[co] + kBnEps) : 0.f;
+    bss[co] = live ? bias[co] : 0.f;
+    bss[wpad + co] = s;
+    bss[2 * wpad + co] = live ? bb[co] - rm[co] * s : 0.f;
+  }
+}
+
+// ---- SE_Connect (:78-84) and the block residual (:126) --------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sp_rowmean_kernel(const float* __restrict__ in, float* __restrict__ mean, int rows, int T) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* r = in + (size_t)row * T;
+  float s = 0.f;
+  for (int t = lane; t < T; t += 64) s += r[t];
+  s = wave_sum(s);
+  if (lane == 0) mean[row] = s / (float)T;
+}
+
+// s[b][c] = sigmoid(W2 relu(W1 mean[b] + b1) + b2); one workgroup per batch item, one wave per output
+__global__ __launch_bounds__(1024) void sp_se_kernel(const float* __restrict__ mean, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                     const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ s, int ch) {
+  extern __shared__ float sm[];          // mean [ch], hidden [kSpAtt]
+  float* hid = sm + ch;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = threadIdx.x; c < ch; c += 1024) sm[c] = mean[(size_t)b * ch + c];
+  __syncthreads();
+  for (int j = wave; j < kSpAtt; j += 16) {
+    float a = 0.f;
+    for (int c = lane; c < ch; c += 64) a = fmaf(w1[(size_t)j * ch + c], sm[c], a);
+    a = wave_sum(a);
+    if (lane == 0) hid[j] = fmaxf(a + b1[j], 0.f);
+  }
+  __syncthreads();
+  for (int c = wave; c < ch; c += 16) {
+    float a = 0.f;
+    for (int j = lane; j < kSpAtt; j += 64) a = fmaf(w2[(size_t)c * kSpAtt + j], hid[j], a);
+    a = wave_sum(a);
+    if (lane == 0) s[(size_t)b * ch + c] = 1.f / (1.f + expf(-(a + b2[c])));
+  }
+}
+
+__global__ __launch_bounds__(256) void sp_scale_res_kernel(const float* __restrict__ y, const float* __restrict__ s, const float* __restrict__ res,
+                                                           float* __restrict__ out, int ch, int T, long long res_bs, long long out_bs) {
+  const int b = blockIdx.y;
+  const size_t n = (size_t)ch * T;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i / T);
+    out[(size_t)b * out_bs + i] = fmaf(y[(size_t)b * n + i], s[(size_t)b * ch + c], res[(size_t)b * res_bs + i]);
+  }
+}
+
+// ---- AttentiveStatsPool (:145-161) ------------------------------------------------------------------------------------------------
+// global context: ctx[b][0][c] = mean over T, ctx[b][1][c] = sqrt(unbiased var + 1e-10) (torch.var's default; NaN for T = 1 as there)
+__global__ __launch_bounds__(256) void sp_rowstats_kernel(const float* __restrict__ in, float* __restrict__ ctx, int C, int rows, int T) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* r = in + (size_t)row * T;
+  float s = 0.f;
+  for (int t = lane; t < T; t += 64) s += r[t];
+  const float mean = wave_sum(s) / (float)T;
+  float v = 0.f;
+  for (int t = lane; t < T; t += 64) {
+    const float d = r[t] - mean;
+    v = fmaf(d, d, v);
+  }
+  v = wave_sum(v) / (float)(T - 1);
+  if (lane == 0) {
+    const int b = row / C, c = row - b * C;
+    ctx[((size_t)b * 2) * C + c] = mean;
+    ctx[((size_t)b * 2 + 1) * C + c] = sqrtf(v + 1e-10f);
+  }
+}
+
+// the two constant thirds of linear1's input as a bias: bias2[b][j] = sum_c W1[j][C + c] mean[b][c] + W1[j][2 C + c] std[b][c]
+__global__ __launch_bounds__(1024) void sp_ctx_bias_kernel(const float* __restrict__ ctx, const float* __restrict__ w1, float* __restrict__ bias2, int C) {
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* cb = ctx + (size_t)b * 2 * C;
+  for (int j = wave; j < kSpAtt; j += 16) {
+    const float* w = w1 + (size_t)j * 3 * C + C;
+    float a = 0.f;
+    for (int c = lane; c < 2 * C; c += 64) a = fmaf(w[c], cb[c], a);
+    a = wave_sum(a);
+    if (lane == 0) bias2[(size_t)b * kSpAtt + j] = a;
+  }
+}
+
+// one wave per (b, c) row: alpha = softmax_T(e), mean = sum alpha x, std = sqrt(clamp(sum alpha x^2 - mean^2, 1e-9)); raw[b] = [mean | std]
+// and bnd = raw * scale + shift (the eval-mode `bn` of :284)
+__global__ __launch_bounds__(256) void sp_pool_kernel(const float* __restrict__ x, const float* __restrict__ e, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, float* __restrict__ raw, float* __restrict__ bnd, int C,
+                                                      int rows, int T) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + (size_t)row * T;
+  const float* er = e + (size_t)row * T;
+  float m = -INFINITY;
+  for (int t = lane; t < T; t += 64) m = fmaxf(m, er[t]);
+  m = wave_max(m);
+  float se = 0.f, sx = 0.f, sxx = 0.f;
+  for (int t = lane; t < T; t += 64) {
+    const float w = expf(er[t] - m), v = xr[t];
+    se += w;
+    sx = fmaf(w, v, sx);
+    sxx = fmaf(w * v, v, sxx);
+  }
+  se = wave_sum(se);
+  sx = wave_sum(sx);
+  sxx = wave_sum(sxx);
+  if (lane == 0) {
+    const int b = row / C, c = row - b * C;
+    const float mean = sx / se;
+    const float sd = sqrtf(fmaxf(sxx / se - mean * mean, 1e-9f));
+    const size_t o = (size_t)b * 2 * C;
+    raw[o + c] = mean;
+    raw[o + C + c] = sd;
+    bnd[o + c] = fmaf(mean, scale[c], shift[c]);
+    bnd[o + C + c] = fmaf(sd, scale[C + c], shift[C + c]);
+  }
+}
+
+// out[b][j] = bias[j] + sum_i W[j][i] p[b][i]; one wave per output
+__global__ __launch_bounds__(256) void sp_linear_kernel(const float* __restrict__ p, const float* __restrict__ w, const float* __restrict__ bias,
+                                                        float* __restrict__ out, int B, int in_dim, int out_dim) {
+  const int lane = threadIdx.x & 63, o = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (o >= B * out_dim) return;
+  const int b = o / out_dim, j = o - b * out_dim;
+  float a = 0.f;
+  for (int i = lane; i < in_dim; i += 64) a = fmaf(w[(size_t)j * in_dim + i], p[(size_t)b * in_dim + i], a);
+  a = wave_sum(a);
+  if (lane == 0) out[o] = a + bias[j];
+}
+
+// x /= |x| over all n elements (finetune.py:110); one workgroup, the sum of squares in fp64 in a fixed order
+__global__ __launch_bounds__(256) void sp_normalize_kernel(float* __restrict__ x, int n) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)x[i] * (double)x[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  const float norm = (float)sqrt(part[0]);
+  for (int i = threadIdx.x; i < n; i += 256) x[i] = x[i] / norm;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+struct SpWeight {
+  std::vector<int64_t> shape;
+  float* dev = nullptr;         // reference layout
+  bool loaded = false;
+  size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
+};
+
+struct SpConv {                 // one dense Conv1d in packed form
+  int cin = 0, cin_tot = 0, cout = 0, k = 1, Kpad = 0, ldw = 0;
+  float* packed = nullptr;
+};
+
+struct SpBn {                   // one folded BatchNorm1d
+  int n = 0;
+  float* scale = nullptr;       // [2][n]: scale, shift
+};
+
+struct SpRes2 {
+  float* wp = nullptr;          // [7][width][3][wpad]
+  float* bss = nullptr;         // [7][3][wpad]
+};
+
+}  // namespace
+}  // namespace us
+
+struct us_speaker {
+  us_speaker_config cfg{};
+  int device = 0;
+  int width = 0, wpad = 0;
+  std::vector<std::string> keys;       // state_dict order, floating-point entries only
+  std::map<std::string, us::SpWeight> w;
+  std::map<std::string, us::SpConv> conv;
+  std::map<std::string, us::SpBn> bn;
+  std::map<std::string, us::SpRes2> res2;
+  float* lw = nullptr;                 // softmax(feature_weight)
+  bool allocated = false;              // device tensors exist (made by the first load, so creating a handle touches no device)
+  bool dirty = true;                   // a weight changed since the derived forms were made
+  std::string err;
+};
+
+namespace us {
+namespace {
+
+int sp_fail(us_speaker* h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  set_last_error(msg.c_str());
+  return code;
+}
+int sp_hip(us_speaker* h, const char* what, hipError_t e) { return sp_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+int sp_round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+void sp_key(us_speaker* h, const std::string& k, std::vector<int64_t> shape) {
+  h->keys.push_back(k);
+  h->w[k].shape = std::move(shape);
+}
+
+void sp_add_conv(us_speaker* h, const std::string& p, int cin, int cin_tot, int cout, int k) {
+  sp_key(h, p + ".weight", {cout, cin_tot, k});
+  sp_key(h, p + ".bias", {cout});
+  SpConv& c = h->conv[p];
+  c.cin = cin; c.cin_tot = cin_tot; c.cout = cout; c.k = k;
+  c.Kpad = sp_round_up(k * cin, kSpBK); c.ldw = sp_round_up(cout, kSpBM);
+}
+
+void sp_add_bn(us_speaker* h, const std::string& p, int n, bool folded) {
+  sp_key(h, p + ".weight", {n});
+  sp_key(h, p + ".bias", {n});
+  sp_key(h, p + ".running_mean", {n});
+  sp_key(h, p + ".running_var", {n});
+  if (folded) h->bn[p].n = n;
+}
+
+void sp_add_linear(us_speaker* h, const std::string& p, int in, int out) {
+  sp_key(h, p + ".weight", {out, in});
+  sp_key(h, p + ".bias", {out});
+}
+
+// module registration order of ecapa_tdnn.py:206-234 (and :103-106, :27-33 inside a block)
+void speaker_keys(us_speaker* h) {
+  const auto& c = h->cfg;
+  const int ch = c.channels;
+  if (c.n_layers > 0) sp_key(h, "feature_weight", {c.n_layers});
+  sp_add_conv(h, "layer1.conv", c.feat_dim, c.feat_dim, ch, 5);
+  sp_add_bn(h, "layer1.bn", ch, true);
+  for (int l = 2; l <= 4; ++l) {
+    const std::string p = "layer" + std::to_string(l);
+    sp_add_conv(h, p + ".Conv1dReluBn1.conv", ch, ch, ch, 1);
+    sp_add_bn(h, p + ".Conv1dReluBn1.bn", ch, true);
+    for (int i = 0; i < kSpStages; ++i) {
+      const std::string q = p + ".Res2Conv1dReluBn.convs." + std::to_string(i);
+      sp_key(h, q + ".weight", {h->width, h->width, 3});
+      sp_key(h, q + ".bias", {h->width});
+    }
+    for (int i = 0; i < kSpStages; ++i) sp_add_bn(h, p + ".Res2Conv1dReluBn.bns." + std::to_string(i), h->width, false);
+    h->res2[p];
+    sp_add_conv(h, p + ".Conv1dReluBn2.conv", ch, ch, ch, 1);
+    sp_add_bn(h, p + ".Conv1dReluBn2.bn", ch, true);
+    sp_add_linear(h, p + ".SE_Connect.linear1", ch, kSpAtt);
+    sp_add_linear(h, p + ".SE_Connect.linear2", kSpAtt, ch);
+  }
+  sp_add_conv(h, "conv", 3 * ch, 3 * ch, kSpOut, 1);
+  sp_add_conv(h, "pooling.linear1", kSpOut, c.global_context_att ? 3 * kSpOut : kSpOut, kSpAtt, 1);
+  sp_add_conv(h, "pooling.linear2", kSpAtt, kSpAtt, kSpOut, 1);
+  sp_add_bn(h, "bn", 2 * kSpOut, true);
+  sp_add_linear(h, "linear", 2 * kSpOut, c.emb_dim);
+}
+
+int sp_device(us_speaker* h, const char* what) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
+    return sp_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
+                                     std::to_string(h->device) + ")");
+  return US_OK;
+}
+
+// every tensor the forward reads, at once: after the first load neither a load nor a forward allocates
+hipError_t sp_alloc(us_speaker* h) {
+  hipError_t e = hipSuccess;
+  auto alloc = [&](float** p, size_t n) {
+    if (e == hipSuccess && !*p) e = hipMalloc(p, std::max<size_t>(n, 1) * sizeof(float));
+  };
+  for (auto& kv : h->w) alloc(&kv.second.dev, kv.second.numel());
+  for (auto& kv : h->conv) alloc(&kv.second.packed, (size_t)kv.second.Kpad * kv.second.ldw);
+  for (auto& kv : h->bn) alloc(&kv.second.scale, 2 * (size_t)kv.second.n);
+  for (auto& kv : h->res2) {
+    alloc(&kv.second.wp, (size_t)kSpStages * h->width * 3 * h->wpad);
+    alloc(&kv.second.bss, (size_t)kSpStages * 3 * h->wpad);
+  }
+  alloc(&h->lw, 64);
+  h->allocated = e == hipSuccess;
+  return e;
+}
+
+// every derived form (packed GEMM weights, folded BatchNorms, the Res2 stage packs, the layer softmax) from the loaded tensors
+void sp_prepare(us_speaker* h, hipStream_t s) {
+  auto W = [&](const std::string& k) { return h->w.at(k).dev; };
+  for (auto& kv : h->conv) {
+    SpConv& c = kv.second;
+    const size_t np = (size_t)c.Kpad * c.ldw;
+    hipLaunchKernelGGL(sp_pack_kernel, dim3((unsigned)std::min<size_t>((np + 255) / 256, 4096)), dim3(256), 0, s, W(kv.first + ".weight"), c.packed,
+                       c.cin, c.cin_tot, c.cout, c.k, c.Kpad, c.ldw);
+  }
+  for (auto& kv : h->bn) {
+    SpBn& b = kv.second;
+    const std::string& p = kv.first;
+    hipLaunchKernelGGL(sp_bnfold_kernel, dim3((b.n + 255) / 256), dim3(256), 0, s, W(p + ".weight"), W(p + ".bias"), W(p + ".running_mean"),
+                       W(p + ".running_var"), b.scale, b.scale + b.n, b.n);
+  }
+  for (auto& kv : h->res2) {
+    const std::string p = kv.first + ".Res2Conv1dReluBn.";
+    for (int i = 0; i < kSpStages; ++i) {
+      const std::string cv = p + "convs." + std::to_string(i), bn = p + "bns." + std::to_string(i);
+      hipLaunchKernelGGL(sp_res2_pack_kernel, dim3(16), dim3(256), 0, s, W(cv + ".weight"), W(cv + ".bias"), W(bn + ".weight"), W(bn + ".bias"),
+                         W(bn + ".running_mean"), W(bn + ".running_var"), kv.second.wp + (size_t)i * h->width * 3 * h->wpad,
+                         kv.second.bss + (size_t)i * 3 * h->wpad, h->width, h->wpad);
+    }
+  }
+  if (h->cfg.n_layers > 0) hipLaunchKernelGGL(sp_layer_softmax_kernel, dim3(1), dim3(64), 0, s, W("feature_weight"), h->lw, h->cfg.n_layers);
+  h->dirty = false;
+}
+
+size_t sp_pad(size_t n) { return (n + 63) / 64 * 64; }
+
+struct SpPlan {                 // float offsets into the 256-byte aligned workspace
+  size_t x0, o1, cat, a, r, y, big, att, e, mean, s, ctx, b2, praw, pbn, total;
+};
+
+SpPlan sp_plan(const us_speaker_config& c, int B, int T) {
+  SpPlan p{};
+  size_t o = 0;
+  auto take = [&](size_t n) { const size_t at = o; o += sp_pad(n); return at; };
+  const size_t bt = (size_t)B * T, ch = (size_t)c.channels;
+  p.x0 = take(bt * c.feat_dim);
+  p.o1 = take(bt * ch);
+  p.cat = take(bt * 3 * ch);
+  p.a = take(bt * ch);
+  p.r = take(bt * ch);
+  p.y = take(bt * ch);
+  p.big = take(bt * kSpOut);
+  p.att = take(bt * kSpAtt);
+  p.e = take(bt * kSpOut);
+  p.mean = take((size_t)B * ch);
+  p.s = take((size_t)B * ch);
+  p.ctx = take((size_t)B * 2 * kSpOut);
+  p.b2 = take((size_t)B * kSpAtt);
+  p.praw = take((size_t)B * 2 * kSpOut);
+  p.pbn = take((size_t)B * 2 * kSpOut);
+  p.total = o;
+  return p;
+}
+
+float* sp_base(void* workspace) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255)); }
+
+void sp_conv(us_speaker* h, hipStream_t s, const std::string& p, const std::string& bn, int act, const float* in, long long in_bs, float* out,
+             long long out_bs, const float* bias2, int B, int T) {
+  const SpConv& c = h->conv.at(p);
+  SpConvArgs a{};
+  a.in = in; a.w = c.packed; a.bias = h->w.at(p + ".bias").dev; a.bias2 = bias2; a.out = out;
+  if (!bn.empty()) {
+    const SpBn& f = h->bn.at(bn);
+    a.scale = f.scale; a.shift = f.scale + f.n;
+  }
+  a.in_bs = in_bs; a.out_bs = out_bs;
+  a.Cin = c.cin; a.Cout = c.cout; a.T = T; a.taps = c.k; a.Kdim = c.k * c.cin; a.Kpad = c.Kpad; a.ldw = c.ldw; a.act = act;
+  hipLaunchKernelGGL(sp_conv_kernel, dim3((T + kSpBN - 1) / kSpBN, (c.cout + kSpBM - 1) / kSpBM, B), dim3(256), 0, s, a);
+}
+
+}  // namespace
+}  // namespace us
+
+extern "C" {
+
+using namespace us;
+
+int us_speaker_create(us_speaker_handle* out, const us_speaker_config* cfg) {
+  if (!out || !cfg) return sp_fail(nullptr, US_EINVAL, "us_speaker_create: null argument");
+  const auto& c = *cfg;
+  if (c.feat_dim <= 0 || c.feat_dim > 8192 || c.emb_dim <= 0 || c.emb_dim > 8192 || c.n_layers < 0 || c.n_layers > 64 ||
+      c.global_context_att < 0 || c.global_context_att > 1)
+    return sp_fail(nullptr, US_EINVAL, "us_speaker_create: bad feat_dim / emb_dim / n_layers / global_context_att");
+  if (c.channels <= 0 || c.channels % kSpScale != 0 || c.channels > 64 * kSpScale)
+    return sp_fail(nullptr, US_EINVAL, "us_speaker_create: channels must be a multiple of 8, at most 512 (a Res2 chunk of 64 channels "
+                                       "is what the chained kernel holds in LDS)");
+  auto* h = new us_speaker();
+  h->cfg = c;
+  h->width = c.channels / kSpScale;
+  h->wpad = sp_round_up(h->width, kRes2Co);
+  (void)hipGetDevice(&h->device);
+  speaker_keys(h);
+  *out = h;
+  return US_OK;
+}
+
+int us_speaker_destroy(us_speaker_handle h) {
+  if (!h) return US_OK;
+  for (auto& kv : h->w)
+    if (kv.second.dev) (void)hipFree(kv.second.dev);
+  for (auto& kv : h->conv)
+    if (kv.second.packed) (void)hipFree(kv.second.packed);
+  for (auto& kv : h->bn)
+    if (kv.second.scale) (void)hipFree(kv.second.scale);
+  for (auto& kv : h->res2) {
+    if (kv.second.wp) (void)hipFree(kv.second.wp);
+    if (kv.second.bss) (void)hipFree(kv.second.bss);
+  }
+  if (h->lw) (void)hipFree(h->lw);
+  delete h;
+  return US_OK;
+}
+
+int us_speaker_num_weights(us_speaker_handle h) { return h ? (int)h->keys.size() : 0; }
+const char* us_speaker_weight_key(us_speaker_handle h, int i) {
+  return (h && i >= 0 && i < (int)h->keys.size()) ? h->keys[i].c_str() : nullptr;
+}
+const char* us_speaker_last_error(us_speaker_handle h) { return h ? h->err.c_str() : us_last_error(nullptr); }
+
+int us_speaker_load_weight(us_speaker_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
+  if (!h || !key || !data || !shape) return sp_fail(h, US_EINVAL, "us_speaker_load_weight: null argument");
+  const std::string k(key);
+  if (k.find(".shortcut.") != std::string::npos)
+    return sp_fail(h, US_ENOKEY, "us_speaker_load_weight: '" + k + "': SE_Res2Block shortcuts (in_channels != out_channels) are not built");
+  auto it = h->w.find(k);
+  if (it == h->w.end()) return sp_fail(h, US_ENOKEY, "us_speaker_load_weight: unknown key '" + k + "'");
+  SpWeight& w = it->second;
+  bool same = ndim == (int)w.shape.size();
+  for (int i = 0; same && i < ndim; ++i) same = shape[i] == w.shape[i];
+  if (!same) return sp_fail(h, US_ESHAPE, "us_speaker_load_weight: shape of '" + k + "' does not match the configuration");
+  int rc = sp_device(h, "us_speaker_load_weight");
+  if (rc != US_OK) return rc;
+  hipError_t e;
+  if (!h->allocated && (e = sp_alloc(h)) != hipSuccess) return sp_hip(h, "us_speaker_load_weight: hipMalloc", e);
+  e = hipMemcpyAsync(w.dev, data, w.numel() * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return sp_hip(h, "hipMemcpyAsync(weight)", e);
+  w.loaded = true;
+  h->dirty = true;
+  return US_OK;
+}
+
+size_t us_speaker_workspace_bytes(us_speaker_handle h, int B, int T) {
+  if (!h || B <= 0 || T <= 0) return 0;
+  return sp_plan(h->cfg, B, T).total * sizeof(float) + 256;
+}
+
+int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, int B, int T, float* emb_out, int normalize, void* workspace,
+                       size_t workspace_bytes, us_stream stream) {
+  if (!h || !hidden_states || !emb_out || B <= 0 || T <= 0 || L < 0) return sp_fail(h, US_EINVAL, "us_speaker_forward: bad argument");
+  const auto& c = h->cfg;
+  if (L != 0 && L != c.n_layers)
+    return sp_fail(h, US_EINVAL, "us_speaker_forward: L must be the configuration's n_layers (" + std::to_string(c.n_layers) +
+                                     "), or 0 for already combined [B][feat_dim][T] features");
+  if (normalize && B != 1) return sp_fail(h, US_EINVAL, "us_speaker_forward: normalize divides the whole output by its norm and is defined for B = 1");
+  const long long big = std::max<long long>(std::max(c.feat_dim, 3 * c.channels), kSpOut);
+  if ((long long)B * T * big >= (1ll << 31) || B > 65535) return sp_fail(h, US_EINVAL, "us_speaker_forward: B * T * channels too large");
+  for (const auto& k : h->keys)
+    if (!h->w[k].loaded) return sp_fail(h, US_EWEIGHTS, "us_speaker_forward: weight '" + k + "' has not been loaded");
+  int rc = sp_device(h, "us_speaker_forward");
+  if (rc != US_OK) return rc;
+  if (!workspace || workspace_bytes < us_speaker_workspace_bytes(h, B, T))
+    return sp_fail(h, US_EWORKSPACE, "us_speaker_forward: workspace too small (us_speaker_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (h->dirty) sp_prepare(h, s);
+  const SpPlan p = sp_plan(c, B, T);
+  float* base = sp_base(workspace);
+  const int ch = c.channels, F = c.feat_dim;
+  auto W = [&](const std::string& k) { return h->w.at(k).dev; };
+  auto rows_grid = [](long long rows) { return dim3((unsigned)((rows + 3) / 4)); };
+  // get_feat (:261-271)
+  float* X0 = base + p.x0;
+  if (L > 0) {
+    hipLaunchKernelGGL(sp_combine_kernel, dim3((F + kCmbC - 1) / kCmbC, (T + kCmbT - 1) / kCmbT, B), dim3(256), 0, s, hidden_states, h->lw, X0, L,
+                       B, T, F);
+    hipLaunchKernelGGL(sp_instnorm_kernel, rows_grid((long long)B * F), dim3(256), 0, s, X0, X0, B * F, T);
+  } else {
+    hipLaunchKernelGGL(sp_instnorm_kernel, rows_grid((long long)B * F), dim3(256), 0, s, hidden_states, X0, B * F, T);
+  }
+  const long long ct = (long long)ch * T;
+  float* O1 = base + p.o1;
+  float* CAT = base + p.cat;
+  float* A = base + p.a;
+  float* R = base + p.r;
+  float* Y = base + p.y;
+  sp_conv(h, s, "layer1.conv", "layer1.bn", kActRelu, X0, (long long)F * T, O1, ct, nullptr, B, T);
+  static const int dils[3] = {2, 3, 4};                       // :225-227
+  for (int blk = 0; blk < 3; ++blk) {
+    const std::string q = "layer" + std::to_string(blk + 2);
+    const float* in = blk == 0 ? O1 : CAT + (size_t)(blk - 1) * ct;
+    const long long in_bs = blk == 0 ? ct : 3 * ct;
+    sp_conv(h, s, q + ".Conv1dReluBn1.conv", q + ".Conv1dReluBn1.bn", kActRelu, in, in_bs, A, ct, nullptr, B, T);
+    const int dil = dils[blk], TT = kRes2W - 2 * kSpStages * dil;
+    const SpRes2& r2 = h->res2.at(q);
+    hipLaunchKernelGGL(sp_res2_kernel, dim3((T + TT - 1) / TT, B), dim3(512), 2 * (size_t)h->width * kRes2W * sizeof(float), s, A, R, r2.wp,
+                       r2.bss, h->width, h->wpad, T, dil, TT);
+    sp_conv(h, s, q + ".Conv1dReluBn2.conv", q + ".Conv1dReluBn2.bn", kActRelu, R, ct, Y, ct, nullptr, B, T);
+    hipLaunchKernelGGL(sp_rowmean_kernel, rows_grid((long long)B * ch), dim3(256), 0, s, Y, base + p.mean, B * ch, T);
+    hipLaunchKernelGGL(sp_se_kernel, dim3(B), dim3(1024), (size_t)(ch + kSpAtt) * sizeof(float), s, base + p.mean, W(q + ".SE_Connect.linear1.weight"),
+                       W(q + ".SE_Connect.linear1.bias"), W(q + ".SE_Connect.linear2.weight"), W(q + ".SE_Connect.linear2.bias"), base + p.s, ch);
+    hipLaunchKernelGGL(sp_scale_res_kernel, dim3((unsigned)std::min<long long>((ct + 255) / 256, 2048), B), dim3(256), 0, s, Y, base + p.s, in,
+                       CAT + (size_t)blk * ct, ch, T, in_bs, 3 * ct);
+  }
+  float* BIG = base + p.big;
+  sp_conv(h, s, "conv", "", kActRelu, CAT, 3 * ct, BIG, (long long)kSpOut * T, nullptr, B, T);
+  const float* bias2 = nullptr;
+  if (c.global_context_att) {
+    hipLaunchKernelGGL(sp_rowstats_kernel, rows_grid((long long)B * kSpOut), dim3(256), 0, s, BIG, base + p.ctx, kSpOut, B * kSpOut, T);
+    hipLaunchKernelGGL(sp_ctx_bias_kernel, dim3(B), dim3(1024), 0, s, base + p.ctx, W("pooling.linear1.weight"), base + p.b2, kSpOut);
+    bias2 = base + p.b2;
+  }
+  sp_conv(h, s, "pooling.linear1", "", kActTanh, BIG, (long long)kSpOut * T, base + p.att, (long long)kSpAtt * T, bias2, B, T);
+  sp_conv(h, s, "pooling.linear2", "", kActNone, base + p.att, (long long)kSpAtt * T, base + p.e, (long long)kSpOut * T, nullptr, B, T);
+  const SpBn& fb = h->bn.at("bn");
+  hipLaunchKernelGGL(sp_pool_kernel, rows_grid((long long)B * kSpOut), dim3(256), 0, s, BIG, base + p.e, fb.scale, fb.scale + fb.n, base + p.praw,
+                     base + p.pbn, kSpOut, B * kSpOut, T);
+  hipLaunchKernelGGL(sp_linear_kernel, rows_grid((long long)B * c.emb_dim), dim3(256), 0, s, base + p.pbn, W("linear.weight"), W("linear.bias"),
+                     emb_out, B, 2 * kSpOut, c.emb_dim);
+  if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(1), dim3(256), 0, s, emb_out, B * c.emb_dim);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : sp_hip(h, "us_speaker_forward", e);
+}
+
+int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape) {
+  if (!h || !data || !shape || B <= 0 || T <= 0) return sp_fail(h, US_EINVAL, "us_speaker_stage: bad argument");
+  if (!workspace || workspace_bytes < us_speaker_workspace_bytes(h, B, T))
+    return sp_fail(h, US_EWORKSPACE, "us_speaker_stage: workspace too small (us_speaker_workspace_bytes)");
+  const SpPlan p = sp_plan(h->cfg, B, T);
+  const float* base = sp_base(workspace);
+  shape[0] = B;
+  shape[2] = T;
+  switch (stage) {
+    case US_SPEAKER_STAGE_FEAT: *data = base + p.x0; shape[1] = h->cfg.feat_dim; break;
+    case US_SPEAKER_STAGE_LAYER1: *data = base + p.o1; shape[1] = h->cfg.channels; break;
+    case US_SPEAKER_STAGE_BLOCKS: *data = base + p.cat; shape[1] = 3 * h->cfg.channels; break;
+    case US_SPEAKER_STAGE_POOLING: *data = base + p.praw; shape[1] = 2 * kSpOut; shape[2] = 1; break;
+    default: return sp_fail(h, US_EINVAL, "us_speaker_stage: unknown stage");
+  }
+  return US_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,310 @@
+"""ECAPA-TDNN speaker encoder on the HIP library: the upstream model's hidden states -> speaker embedding [B, emb_dim] (inference).
+
+Drop-in for the reference's `unitspeech/speaker_encoder/ecapa_tdnn.py:164-298` `ECAPA_TDNN` / `ECAPA_TDNN_SMALL` from the hidden
+states on: the same constructor arguments, the same module tree and therefore the same `state_dict` keys, shapes and order with
+every `feature_extract.*` key removed (the WavLM / HuBERT upstream and the fbank / mfcc extraction are not part of this library).
+The torch modules below only hold parameters; the arithmetic is `csrc/speaker.hip`.
+
+`forward_features(hidden_states)` is the entry point: `[L, B, T, C]`, a list of L `[B, T, C]`, or an already combined `[B, C, T]`.
+There is no CPU fallback: tensors must live on a ROCm device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import hashlib
+from collections import OrderedDict
+from typing import Dict
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+
+# number of hidden states the s3prl upstreams return (the CNN output plus one per transformer layer): the length of `feature_weight`
+UPSTREAM_LAYERS = {"wavlm_large": 25, "hubert_large_ll60k": 25, "wav2vec2_xlsr": 25, "wav2vec2_large_ll60k": 25,
+                   "wavlm_base_plus": 13, "wavlm_base": 13, "hubert_base": 13, "wav2vec2_base_960": 13}
+OUT_CHANNELS = 1536            # ecapa_tdnn.py:222
+BOTTLENECK = 128               # se_bottleneck_dim and attention_channels (:225-232)
+SCALE = 8
+STAGES = {"feat": 0, "layer1": 1, "blocks": 2, "pooling": 3}
+
+
+class _Conv1dReluBn(nn.Module):
+    def __init__(self, cin, cout, k=1):
+        super().__init__()
+        self.conv = nn.Conv1d(cin, cout, k)
+        self.bn = nn.BatchNorm1d(cout)
+
+
+class _Res2Conv1dReluBn(nn.Module):
+    def __init__(self, channels):
+        super().__init__()
+        w = channels // SCALE
+        self.convs = nn.ModuleList([nn.Conv1d(w, w, 3) for _ in range(SCALE - 1)])
+        self.bns = nn.ModuleList([nn.BatchNorm1d(w) for _ in range(SCALE - 1)])
+
+
+class _SEConnect(nn.Module):
+    def __init__(self, channels):
+        super().__init__()
+        self.linear1 = nn.Linear(channels, BOTTLENECK)
+        self.linear2 = nn.Linear(BOTTLENECK, channels)
+
+
+class _SERes2Block(nn.Module):
+    def __init__(self, channels):
+        super().__init__()
+        self.Conv1dReluBn1 = _Conv1dReluBn(channels, channels)
+        self.Res2Conv1dReluBn = _Res2Conv1dReluBn(channels)
+        self.Conv1dReluBn2 = _Conv1dReluBn(channels, channels)
+        self.SE_Connect = _SEConnect(channels)
+
+
+class _AttentiveStatsPool(nn.Module):
+    def __init__(self, in_dim, global_context_att):
+        super().__init__()
+        self.linear1 = nn.Conv1d(in_dim * 3 if global_context_att else in_dim, BOTTLENECK, 1)
+        self.linear2 = nn.Conv1d(BOTTLENECK, in_dim, 1)
+
+
+class ECAPA_TDNN(nn.Module):
+    """`ECAPA_TDNN(...)` of ecapa_tdnn.py:164.  `feat_num` (not a reference argument) gives the number of hidden states for an upstream
+    `feat_type` this module does not know (the reference asks the upstream itself, :237-246)."""
+
+    def __init__(self, feat_dim=80, channels=512, emb_dim=192, global_context_att=False, feat_type='fbank', sr=16000,
+                 feature_selection="hidden_states", update_extract=False, config_path=None, feat_num=None):
+        super().__init__()
+        if channels <= 0 or channels % SCALE != 0:
+            raise ValueError(f"channels must be a positive multiple of {SCALE}, got {channels}")
+        self.feat_type, self.feature_selection, self.update_extract, self.sr = feat_type, feature_selection, False, sr
+        self.feat_dim, self.emb_dim, self.global_context_att = int(feat_dim), int(emb_dim), bool(global_context_att)
+        if feat_type in ("fbank", "mfcc"):
+            self.feat_num = 0
+        else:
+            if feat_num is None and feat_type not in UPSTREAM_LAYERS:
+                raise ValueError(f"feat_type {feat_type!r}: give feat_num, the number of hidden states the upstream returns")
+            self.feat_num = int(feat_num if feat_num is not None else UPSTREAM_LAYERS[feat_type])
+            self.feature_weight = nn.Parameter(torch.zeros(self.feat_num))
+        self.instance_norm = nn.InstanceNorm1d(feat_dim)
+        self.channels = [channels] * 4 + [OUT_CHANNELS]
+        self.layer1 = _Conv1dReluBn(feat_dim, channels, 5)
+        self.layer2 = _SERes2Block(channels)
+        self.layer3 = _SERes2Block(channels)
+        self.layer4 = _SERes2Block(channels)
+        self.conv = nn.Conv1d(channels * 3, OUT_CHANNELS, 1)
+        self.pooling = _AttentiveStatsPool(OUT_CHANNELS, self.global_context_att)
+        self.bn = nn.BatchNorm1d(OUT_CHANNELS * 2)
+        self.linear = nn.Linear(OUT_CHANNELS * 2, emb_dim)
+        self._h = C.c_void_p()
+        self._device = None
+        self._tags = {}
+        self._ws = None
+        self._src = None
+
+    def config(self) -> dict:
+        return {"feat_dim": self.feat_dim, "channels": self.channels[0], "emb_dim": self.emb_dim,
+                "global_context_att": self.global_context_att, "n_layers": self.feat_num}
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        if any(".shortcut." in k for k in state_dict):
+            raise RuntimeError("ECAPA_TDNN: the state_dict has SE_Res2Block `shortcut` keys (in_channels != out_channels), which this "
+                               "module does not build: every block of the reference's configuration keeps its channel count")
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    # ---- engine ----------------------------------------------------------------------------------------------------------
+
+    def _config_struct(self):
+        c = _lib.us_speaker_config()
+        c.feat_dim, c.channels, c.emb_dim, c.n_layers = self.feat_dim, self.channels[0], self.emb_dim, self.feat_num
+        c.global_context_att = int(self.global_context_att)
+        return c
+
+    def _sources(self):
+        """C-ABI key -> tensor: every floating-point entry of the state_dict (`num_batches_tracked` plays no part in eval mode)."""
+        return OrderedDict((k, t) for k, t in self.state_dict(keep_vars=True).items() if t.is_floating_point())
+
+    def _apply(self, fn, *args, **kwargs):
+        self._src = None                   # .to() / .float() replace the buffers: the cached tensor list is rebuilt
+        return super()._apply(fn, *args, **kwargs)
+
+    def _sync(self, device: torch.device):
+        if device.type != "cuda":
+            raise RuntimeError("the HIP speaker encoder needs tensors on a ROCm device (no CPU fallback); got " + str(device))
+        lib = _lib.load()
+        if not self._h or self._device != device:
+            self._close()
+            with torch.cuda.device(device):
+                c = self._config_struct()
+                _lib.check(lib.us_speaker_create(C.byref(self._h), C.byref(c)), None, "us_speaker_create")
+            self._device, self._tags = device, {}
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        with torch.no_grad(), torch.cuda.device(device):
+            if self._src is None:
+                self._src = list(self._sources().items())
+            for key, p in self._src:
+                tag = (p.data_ptr(), p._version, p.device)
+                if self._tags.get(key) == tag:
+                    continue
+                src = p.detach().to(device=device, dtype=torch.float32).contiguous()
+                shape = (C.c_int64 * src.dim())(*src.shape)
+                rc = lib.us_speaker_load_weight(self._h, key.encode(), src.data_ptr(), shape, src.dim(), stream)
+                self._check(lib, rc, f"us_speaker_load_weight({key})")
+                torch.cuda.current_stream(device).synchronize()        # the temporary must outlive the copy
+                self._tags[key] = tag
+        return lib, stream
+
+    def _check(self, lib, rc, what):
+        if rc != _lib.US_OK:
+            msg = lib.us_speaker_last_error(self._h)
+            raise RuntimeError(f"libunitspeech_hip: {what} failed with {_lib.ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}")
+
+    def _close(self):
+        if getattr(self, "_h", None):
+            _lib.load().us_speaker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self._close()
+        except Exception:
+            pass
+
+    def _input(self, hidden_states):
+        """-> (contiguous fp32 tensor, L, B, T) with L = 0 for the combined [B, C, T] form."""
+        if isinstance(hidden_states, (list, tuple)):
+            hidden_states = torch.stack(list(hidden_states), dim=0)
+        x = hidden_states
+        if x.dim() == 4:
+            if self.feat_num == 0:
+                raise ValueError(f"ECAPA_TDNN(feat_type={self.feat_type!r}) has no feature_weight: give the combined [B, {self.feat_dim}, T]")
+            if x.shape[0] != self.feat_num or x.shape[3] != self.feat_dim or x.shape[1] < 1 or x.shape[2] < 1:
+                raise ValueError(f"ECAPA_TDNN: expected hidden states [{self.feat_num}, B, T, {self.feat_dim}], got {tuple(x.shape)}")
+            L, B, T = x.shape[0], x.shape[1], x.shape[2]
+        elif x.dim() == 3:
+            if x.shape[1] != self.feat_dim or x.shape[0] < 1 or x.shape[2] < 1:
+                raise ValueError(f"ECAPA_TDNN: expected combined features [B, {self.feat_dim}, T], got {tuple(x.shape)}")
+            L, B, T = 0, x.shape[0], x.shape[2]
+        else:
+            raise ValueError(f"ECAPA_TDNN: expected [L, B, T, C] or [B, C, T], got {tuple(x.shape)}")
+        return x.detach().to(dtype=torch.float32).contiguous(), int(L), int(B), int(T)
+
+    @torch.no_grad()
+    def _run(self, hidden_states, normalize: bool):
+        x, L, B, T = self._input(hidden_states)
+        device = x.device
+        lib, stream = self._sync(device)
+        out = torch.empty(B, self.emb_dim, device=device)
+        n = int(lib.us_speaker_workspace_bytes(self._h, B, T))
+        if self._ws is None or self._ws.numel() < n or self._ws.device != device:
+            self._ws = None
+            self._ws = torch.empty(n, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            rc = lib.us_speaker_forward(self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), self._ws.data_ptr(),
+                                        self._ws.numel(), stream)
+        self._check(lib, rc, "us_speaker_forward")
+        self._last = (B, T)
+        return out
+
+    def forward_features(self, hidden_states):
+        """`ECAPA_TDNN.forward` (:274-287) from `get_feat`'s input on: -> [B, emb_dim]."""
+        return self._run(hidden_states, False)
+
+    def embed(self, hidden_states):
+        """finetune.py:106-110: the embedding of one utterance divided by its norm, [1, emb_dim]."""
+        if self._input(hidden_states)[2] != 1:
+            raise ValueError("ECAPA_TDNN.embed: one utterance at a time (the norm is taken over the whole output)")
+        return self._run(hidden_states, True)
+
+    def forward(self, x):
+        raise NotImplementedError("ECAPA_TDNN.forward(wav) needs the upstream feature extractor (WavLM / HuBERT through s3prl, or fbank / mfcc), "
+                                  "which is outside this library: run the upstream and call forward_features(hidden_states)")
+
+    @torch.no_grad()
+    def stage(self, name: str) -> torch.Tensor:
+        """An intermediate of the last forward_features call (a copy): `feat` [B, C, T] after get_feat, `layer1` [B, channels, T],
+        `blocks` [B, 3 channels, T] (layer2, layer3, layer4 along the channels) and `pooling` [B, 3072] before `bn`."""
+        lib = _lib.load()
+        B, T = self._last
+        ptr, shape = C.c_void_p(), (C.c_int64 * 3)()
+        rc = lib.us_speaker_stage(self._h, STAGES[name], B, T, self._ws.data_ptr(), self._ws.numel(), C.byref(ptr), shape)
+        self._check(lib, rc, f"us_speaker_stage({name})")
+        off, n = ptr.value - self._ws.data_ptr(), shape[0] * shape[1] * shape[2]
+        torch.cuda.current_stream(self._ws.device).synchronize()
+        out = self._ws[off:off + 4 * n].view(torch.float32).view(*[s for s in shape]).clone()
+        return out.squeeze(-1) if name == "pooling" else out
+
+
+def ECAPA_TDNN_SMALL(feat_dim, emb_dim=256, feat_type='fbank', sr=16000, feature_selection="hidden_states", update_extract=False,
+                     config_path=None, feat_num=None):
+    return ECAPA_TDNN(feat_dim=feat_dim, channels=512, emb_dim=emb_dim, feat_type=feat_type, sr=sr, feature_selection=feature_selection,
+                      update_extract=update_extract, config_path=config_path, feat_num=feat_num)
+
+
+def load_speaker_encoder_checkpoint(path, device=None, feat_dim=1024, emb_dim=256, feat_type="wavlm_large"):
+    """unitspeech/util.py:183-188 `get_speaker_embedder` on the HIP module: ECAPA_TDNN_SMALL(1024, 256, "wavlm_large"), the
+    checkpoint's {"model": state_dict} without its `feature_extract.*` keys loaded strictly, eval mode."""
+    state_dict = torch.load(path, map_location=lambda storage, loc: storage)
+    model = ECAPA_TDNN_SMALL(feat_dim=feat_dim, emb_dim=emb_dim, feat_type=feat_type, config_path=None)
+    sd = OrderedDict((k, v) for k, v in state_dict["model"].items() if not k.startswith("feature_extract."))
+    model.load_state_dict(sd, strict=True)
+    model = model.eval()
+    return model.to(device) if device is not None else model
+
+
+def _rng(seed: int, name: str) -> np.random.Generator:
+    key = int.from_bytes(hashlib.sha256(f"ecapa/{seed}/{name}".encode()).digest()[:8], "little")
+    return np.random.Generator(np.random.Philox(key=key))
+
+
+def _module(cfg) -> ECAPA_TDNN:
+    n = int(cfg.get("n_layers", 0))
+    return ECAPA_TDNN(feat_dim=cfg["feat_dim"], channels=cfg["channels"], emb_dim=cfg["emb_dim"],
+                      global_context_att=bool(cfg["global_context_att"]), feat_type="upstream" if n else "fbank", feat_num=n or None)
+
+
+def synthetic_ecapa_state_dict(cfg, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Seeded weights in the reference's key order for a config dict (`feat_dim`, `channels`, `emb_dim`, `global_context_att`,
+    `n_layers`).  Convolution and linear weights N(0, 2 / fan_in) (activations keep their scale through the ReLUs), biases 0.05 N(0, 1),
+    `linear.weight` a hundredth of that,
+    BatchNorm weights and running variances uniform in [0.5, 1.5), BatchNorm biases and running means 0.1 N(0, 1), `feature_weight`
+    N(0, 1), `num_batches_tracked` 1000: nothing is left at a value that would hide a wrong formula."""
+    out = OrderedDict()
+    for name, t in _module(cfg).state_dict().items():
+        shape, g = tuple(t.shape), _rng(seed, name)
+        leaf = name.rsplit(".", 1)[-1]
+        is_bn = ".bn." in name or ".bns." in name or name.startswith("bn.")
+        if leaf == "num_batches_tracked":
+            out[name] = np.array(1000, dtype=np.int64)
+            continue
+        if name == "feature_weight":
+            v = g.standard_normal(shape, dtype=np.float32)
+        elif leaf == "running_var" or (is_bn and leaf == "weight"):
+            v = 0.5 + g.random(shape, dtype=np.float32)
+        elif leaf == "running_mean" or (is_bn and leaf == "bias"):
+            v = 0.1 * g.standard_normal(shape, dtype=np.float32)
+        elif leaf == "weight":
+            gain = 0.01 if name == "linear.weight" else 1.0         # the residual stream grows block by block; a trained embedding is O(1)
+            v = g.standard_normal(shape, dtype=np.float32) * np.float32(gain * np.sqrt(2.0 / np.prod(shape[1:])))
+        elif leaf == "bias":
+            v = 0.05 * g.standard_normal(shape, dtype=np.float32)
+        else:
+            raise KeyError(name)
+        out[name] = np.ascontiguousarray(v, dtype=np.float32)
+    return out
+
+
+def synthetic_speaker_embedder(emb_dim: int = 256, seed: int = 0) -> ECAPA_TDNN:
+    """ECAPA_TDNN_SMALL(1024, emb_dim, "wavlm_large") -- what util.get_speaker_embedder builds -- with seeded weights, eval mode."""
+    m = ECAPA_TDNN_SMALL(feat_dim=1024, emb_dim=emb_dim, feat_type="wavlm_large")
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_ecapa_state_dict(m.config(), seed).items()})
+    return m.eval()
+
+
+def synthetic_hidden_states(L: int, B: int, T: int, C_: int, seed: int = 0) -> np.ndarray:
+    """Seeded hidden states [L, B, T, C]: N(0, 1) drawn layer by layer, layer l scaled by (1 + 0.2 l) so the layer weights matter."""
+    g = np.random.Generator(np.random.Philox(key=2000 + seed))
+    x = np.empty((L, B, T, C_), dtype=np.float32)
+    for l in range(L):
+        x[l] = g.standard_normal((B, T, C_), dtype=np.float32) * np.float32(1.0 + 0.2 * l)
+    return x
