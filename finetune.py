@@ -14,6 +14,9 @@
                              speaker encoder's upstream hidden states (ecapa_tdnn.py:262-264) + --speaker_encoder_checkpoint (:106-110)
                   duration   [1, Lu]      frames per unit (process_unit, :114)
                   cond_x     [1, 80, Lu]  the unit encoder's output (:123); or  unit [1, Lu] int64 + --unit_encoder_checkpoint (:66-79)
+                  dense      [T, D]       in place of unit / duration: the unit extractor's dense features (:112), quantised and brought to
+                             the mel rate on the device (unitspeech_amd.units) with the centres of --kmeans_checkpoint (a scikit-learn
+                             KMeans saved with joblib) or `centers` [K, D] in the file; needs --unit_encoder_checkpoint
                   mel_min, mel_max        scalars (else the decoder checkpoint's, :98-99)
 Saves {"model", "spk_emb", "mel_min", "mel_max"} like finetune.py:167-173.
 """
@@ -41,6 +44,18 @@ def load_features(args, cfg, base, device):
     else:
         d = torch.load(path, map_location="cpu")
     d = {k: (torch.as_tensor(v) if not isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+    if "dense" in d and "unit" not in d and "cond_x" not in d:
+        # finetune.py:112-114: KMeans.predict, unique_consecutive and process_unit(encoded, 16000, 256), here in one library call
+        from unitspeech_amd.units import KMeansQuantizer
+        if "centers" not in d and not args.kmeans_checkpoint:
+            raise SystemExit(f"--features {path}: `dense` needs the k-means centres: --kmeans_checkpoint or `centers` in the file")
+        quantizer = KMeansQuantizer.from_centers(d["centers"]) if "centers" in d else KMeansQuantizer(args.kmeans_checkpoint)
+        dense = d["dense"].float().reshape(1, -1, d["dense"].shape[-1]).to(device)
+        unit, duration, n = quantizer.encode(dense, None, 16000, 256)
+        n = int(n[0])
+        if int(quantizer.last_counters[0]):
+            raise SystemExit(f"--features {path}: `dense` has rows with non-finite values")
+        d["unit"], d["duration"] = unit[:, :n].cpu(), duration[:, :n].cpu()
     hip_spk = bool(args.speaker_encoder_checkpoint) and "spk_emb" not in d and "spk_hidden_states" in d
     for k in ("mel", "spk_emb", "duration"):
         if k not in d and not (k == "spk_emb" and hip_spk):
@@ -110,6 +125,10 @@ def main():
     ap.add_argument("--features", type=str, default=None, help="file with the pre-step tensors of finetune.py:86-128 (see the module docstring)")
     ap.add_argument("--unit_encoder_checkpoint", type=str, default=None, help="--features with `unit` instead of `cond_x`: the unit encoder's "
                                                                               "checkpoint ({'model': state_dict}, finetune.py:77-78)")
+    ap.add_argument("--kmeans_checkpoint", type=str, default=None, help="--features with `dense` instead of `unit` / `duration`: the unit "
+                    "extractor's k-means model (scikit-learn KMeans saved with joblib); units and durations come from the HIP unit extraction")
+    ap.add_argument("--hip_units", action="store_true", help="--synthetic --learned_frontend: the units and durations come from the HIP unit "
+                    "extraction (k-means quantiser + process_unit) on synthetic dense features and centres instead of random units")
     ap.add_argument("--speaker_encoder_checkpoint", type=str, default=None, help="--features with `spk_hidden_states` instead of `spk_emb`: the "
                     "speaker encoder's checkpoint ({'model': state_dict}, util.py:183-188); the embedding comes from the HIP ECAPA-TDNN")
     ap.add_argument("--hip_speaker_encoder", action="store_true", help="--synthetic: spk_emb from the HIP ECAPA-TDNN (seeded weights) on "
@@ -162,8 +181,22 @@ def main():
                                    window_size=ec.window_size)
             unit_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_encoder_state_dict(ec, 0).items()})
             unit = torch.from_numpy(g.integers(0, ec.n_vocab, size=(1, Lu)).astype(np.int64)).to(device)
+            duration = torch.full((1, Lu), 3.0, device=device)
+            if args.hip_units:
+                # finetune.py:112-114: the units are the k-means labels of the unit extractor's dense features (50 Hz, 16 kHz audio) brought
+                # to the mel rate by process_unit(encoded, 16000, 256); here seeded centres and features for the L mel frames
+                from unitspeech_amd.units import KMeansQuantizer, synthetic_centers, synthetic_dense
+                centers = synthetic_centers(ec.n_vocab, 768, args.ID & 0xffff)
+                dense = torch.from_numpy(synthetic_dense(centers, L * 256 // 320, args.ID & 0xffff)).to(device)
+                unit, duration, n = KMeansQuantizer.from_centers(centers).encode(dense.unsqueeze(0), None, 16000, 256)
+                Lu = int(n[0])
+                unit, duration = unit[:, :Lu], duration[:, :Lu]
+                print(f"hip units: {dense.shape[0]} dense frames -> {Lu} units over {int(duration.sum())} mel frames")
             cond_x, _, _ = unit_encoder.to(device).eval()(unit, torch.LongTensor([Lu]).to(device))
-        duration = torch.full((1, Lu), 3.0, device=device)
+        else:
+            if args.hip_units:
+                raise SystemExit("--hip_units needs --learned_frontend (the units feed the HIP unit encoder)")
+            duration = torch.full((1, Lu), 3.0, device=device)
         if args.hip_speaker_encoder:
             # finetune.py:106-110: spk_emb is the ECAPA-TDNN's embedding of the reference utterance over its norm; here the HIP module
             # at the reference's sizes (WavLM-large: 25 hidden states of 1024) with seeded weights on 3 s of seeded hidden states

@@ -445,6 +445,41 @@ int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, i
  * channels, the input of `conv`), POOLING [B][3072][1] (mean | std, before `bn`).  Enqueues nothing. */
 int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape);
 
+/* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
+ * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102
+ * `process_unit`) as handle-free device calls.  Every call only enqueues on `stream`, allocates nothing and takes device scratch of
+ * us_units_workspace_bytes(B, Tmax, K, D, Lout) (K = 0: no quantize, Lout = 0: no process).  All integer outputs are exact.
+ * us_units_pack_centers: centres [K][D] fp32 (finite) -> `packed` (us_units_packed_bytes): the GEMM operand, 1/2 |c_k|^2 computed in fp64
+ *   and rounded once to fp32, and max |c_k|.  K in [1, 2048]; D a multiple of 4 in [4, 1024].
+ * us_units_quantize: dense [B][Tmax][D], lengths [B] (device int64) -> units [B][Tmax] int64 = the fp64 argmin over k of
+ *   sum_d (x_d - c_kd)^2 taken over the fp32 inputs, the lower index on exact ties.  Scores come from one fp32 matrix-core GEMM whose
+ *   epilogue keeps (best, second best, index) per row; a row whose gap is at most twice the proven fp32 error bound is re-evaluated over
+ *   all K in fp64 on the device.  Rows t >= lengths[b] get -1; a row with a non-finite feature gets -1.  counters [2] (device int32,
+ *   overwritten): [0] rows with a non-finite feature, [1] rows decided in fp64.
+ * us_units_dedup: run-length encoding per item, `unique_consecutive(return_counts=True)`: units [B][Tmax] with lengths [B] ->
+ *   out_units, out_durations [B][Tmax] (zero beyond n[b]) and n [B], all int64 on the device.  out_units must not alias units.
+ * us_units_process: `process_unit(encoded, sampling_rate, hop_length)` in closed form for runs units / durations [B][Lin] (durations NULL:
+ *   all ones) with n_in [B] valid entries.  With spf = sampling_rate / 50 (integer division, as the reference), run i holds the samples of
+ *   its 50 Hz frames, output frame j covers samples [j hop, (j + 1) hop), there are (sum(durations) spf) / hop of them, and a frame's unit
+ *   is the one with the most samples in it (ties: the smallest unit value, `torch.mode`); the frames are then run-length encoded into
+ *   out_units, out_durations [B][Lout] int64 (zero beyond n_out[b]), duration_f [B][Lout] fp32 (optional: the `duration` us_tts_align and
+ *   generate_path take) and n_out [B] (0 for an input shorter than one hop; -1, and nothing else, for an item with more than Lout output
+ *   frames).  An output frame may span up to 64 frames of the 50 Hz stream: US_EINVAL beyond that.
+ * us_units_encode: us_units_quantize then us_units_process (durations all ones, n_in = lengths) in one call. */
+size_t us_units_packed_bytes(int K, int D);
+int us_units_pack_centers(const float* centers, int K, int D, void* packed, size_t packed_bytes, us_stream stream);
+size_t us_units_workspace_bytes(int B, int Tmax, int K, int D, int Lout);
+int us_units_quantize(const float* dense, const int64_t* lengths, const void* packed, int B, int Tmax, int K, int D, int64_t* units,
+                      int32_t* counters, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_units_dedup(const int64_t* units, const int64_t* lengths, int B, int Tmax, int64_t* out_units, int64_t* out_durations, int64_t* n,
+                   void* workspace, size_t workspace_bytes, us_stream stream);
+int us_units_process(const int64_t* units, const int64_t* durations, const int64_t* n_in, int B, int Lin, int sampling_rate, int hop_length,
+                     int64_t* out_units, int64_t* out_durations, float* duration_f, int64_t* n_out, int Lout, void* workspace,
+                     size_t workspace_bytes, us_stream stream);
+int us_units_encode(const float* dense, const int64_t* lengths, const void* packed, int B, int Tmax, int K, int D, int sampling_rate,
+                    int hop_length, int64_t* out_units, int64_t* out_durations, float* duration_f, int64_t* n_out, int Lout,
+                    int32_t* counters, void* workspace, size_t workspace_bytes, us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 
