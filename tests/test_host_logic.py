@@ -244,3 +244,23 @@ def test_an_up_to_date_library_is_used_without_writing_to_the_tree(tmp_path, mon
     assert _build.build_library() == str(lib) and rebuilt == [False]
     assert _build.build_library(force=True) == str(lib) and rebuilt == [False, True]
     assert os.stat(tmp_path / "pkg" / "build" / ".lock").st_mode & 0o777 == 0o666
+
+
+def test_the_three_handle_modules_share_one_base():
+    """Encoder / DurationPredictor, BigVGAN and ECAPA_TDNN push their weights and report library errors through the one HandleModule."""
+    from unitspeech_amd._handle import HandleModule
+    from unitspeech_amd.encoder import DurationPredictor, Encoder
+    from unitspeech_amd.speaker_encoder import ECAPA_TDNN
+    from unitspeech_amd.vocoder import BigVGAN
+    voc = {"resblock": "1", "upsample_rates": [2], "upsample_kernel_sizes": [4], "upsample_initial_channel": 4, "resblock_kernel_sizes": [3],
+           "resblock_dilation_sizes": [[1, 3, 5]], "activation": "snake", "snake_logscale": False, "num_mels": 4}
+    modules = [Encoder(20, 8, 16, 32, 2, 1, 3, 0.1, window_size=4), DurationPredictor(16, 24, 3, 0.1, spk_emb_dim=12), BigVGAN(voc),
+               ECAPA_TDNN(feat_dim=8, channels=8, emb_dim=4)]
+    assert sorted({m._abi for m in modules}) == ["frontend", "speaker", "vocoder"]
+    for m in modules:
+        assert isinstance(m, HandleModule)
+        for f in ("_sync", "_check", "_close", "_workspace", "__del__"):
+            assert getattr(type(m), f) is getattr(HandleModule, f), (type(m).__name__, f)
+        with pytest.raises(RuntimeError, match=f"the HIP {m._what} needs tensors on a ROCm device"):
+            m.eval()._sync(torch.device("cpu"))
+

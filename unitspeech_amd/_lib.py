@@ -86,12 +86,6 @@ SIGNATURES = {
     "us_tts_align": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p]),
     "us_encoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_encoder_config)]),
     "us_duration_predictor_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_duration_config)]),
-    "us_frontend_destroy": (C.c_int, [C.c_void_p]),
-    "us_frontend_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
-    "us_frontend_num_weights": (C.c_int, [C.c_void_p]),
-    "us_frontend_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "us_frontend_last_error": (C.c_char_p, [C.c_void_p]),
-    "us_frontend_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "us_encoder_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_encoder_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "us_encoder_forward_train": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t,
@@ -116,20 +110,8 @@ SIGNATURES = {
     "us_duration_predictor_tape_release": (C.c_int, [C.c_void_p, C.c_void_p]),
     "us_duration_predictor_mse_loss": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
     "us_vocoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_vocoder_config)]),
-    "us_vocoder_destroy": (C.c_int, [C.c_void_p]),
-    "us_vocoder_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
-    "us_vocoder_num_weights": (C.c_int, [C.c_void_p]),
-    "us_vocoder_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "us_vocoder_last_error": (C.c_char_p, [C.c_void_p]),
-    "us_vocoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "us_vocoder_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_speaker_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_speaker_config)]),
-    "us_speaker_destroy": (C.c_int, [C.c_void_p]),
-    "us_speaker_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
-    "us_speaker_num_weights": (C.c_int, [C.c_void_p]),
-    "us_speaker_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "us_speaker_last_error": (C.c_char_p, [C.c_void_p]),
-    "us_speaker_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "us_speaker_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_speaker_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
@@ -151,6 +133,16 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_last_error": (C.c_char_p, [C.c_void_p]),
 }
+# what the three weight-table handles (csrc/handle.h) share
+for _p in ("frontend", "vocoder", "speaker"):
+    SIGNATURES.update({
+        f"us_{_p}_destroy": (C.c_int, [C.c_void_p]),
+        f"us_{_p}_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+        f"us_{_p}_num_weights": (C.c_int, [C.c_void_p]),
+        f"us_{_p}_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
+        f"us_{_p}_last_error": (C.c_char_p, [C.c_void_p]),
+        f"us_{_p}_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    })
 
 _lock = threading.Lock()
 _lib = None

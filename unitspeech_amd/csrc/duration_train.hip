@@ -298,8 +298,6 @@ DtLayout dt_layout(const us_frontend* h, int B, int L) {
   return o;
 }
 
-float* dt_base(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
-
 int dt_check(us_frontend* h, const char* what, int B, int L) {
   if (!h || h->kind != 1) return fe_fail(h, US_EINVAL, std::string(what) + ": not a duration-predictor handle");
   if (B <= 0 || L <= 0 || B > 65535 || L > 65535) return fe_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
@@ -343,7 +341,7 @@ int us_duration_predictor_forward_train(us_frontend_handle h, const float* x, co
     return fe_fail(h, US_EWORKSPACE, "us_duration_predictor_forward_train: workspace too small (us_duration_predictor_train_workspace_bytes)");
   const DtLayout l = dt_layout(h, B, L);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* base = dt_base(workspace);
+  float* base = ws_align(workspace);
   const long long rows = (long long)B * L;
   const int F = c.filter_channels;
   const float p = p_dropout < 0.f ? 0.f : p_dropout;       // negative: the reference in eval mode (autograd still runs)
@@ -381,7 +379,7 @@ int us_duration_predictor_backward(us_frontend_handle h, const float* grad_logw,
   const EncoderTape tape = it->second;
   const DtLayout l = dt_layout(h, B, L);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* base = dt_base(workspace);
+  float* base = ws_align(workspace);
   const long long rows = (long long)B * L;
   const int F = h->dc.filter_channels;
   // destinations: the caller's buffer, or a slot of the workspace's arena for a key nobody asked for

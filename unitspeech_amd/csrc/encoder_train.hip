@@ -577,8 +577,6 @@ int et_check(us_frontend* h, const char* what, int B, int L) {
   return US_OK;
 }
 
-float* et_base(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
-
 }  // namespace
 
 int wgrad_splits(long long rows) {
@@ -648,7 +646,7 @@ int us_encoder_forward_train(us_frontend_handle h, const int64_t* ids, const int
     return fe_fail(h, US_EWORKSPACE, "us_encoder_forward_train: workspace too small (us_encoder_train_workspace_bytes)");
   const auto& c = h->ec;
   const Layout l = et_layout(h, B, L);
-  Ctx x{h, static_cast<hipStream_t>(stream), et_base(workspace), &l, B, L, (long long)B * L, nullptr};
+  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
   x.mask = x.f(l.mask);
   // the tape: one slot per entry and layer (Layout); conv_o / conv_2's output goes to backward scratch, free during the forward
   EncoderBufs b{};
@@ -682,7 +680,7 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
   const EncoderTape tape = it->second;
   const auto& c = h->ec;
   const Layout l = et_layout(h, B, L);
-  Ctx x{h, static_cast<hipStream_t>(stream), et_base(workspace), &l, B, L, (long long)B * L, nullptr};
+  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
   x.mask = x.f(l.mask);
   const int C = c.n_channels, nf = c.n_feats;
   // destinations: the caller's buffer, or a slot of the workspace's arena for a key nobody asked for

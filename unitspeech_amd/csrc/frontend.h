@@ -10,16 +10,9 @@
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
 
 namespace us {
-
-struct Weight {
-  std::vector<int64_t> shape;
-  float* dev = nullptr;        // reference layout
-  float* packed = nullptr;     // conv weights: [K][Cin][Cout]
-  bool loaded = false;
-  size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
-};
 
 // what one us_encoder_forward_train / us_duration_predictor_forward_train left in a caller-owned workspace (keyed by the
 // workspace's base address)
@@ -31,14 +24,10 @@ struct EncoderTape {
 
 }  // namespace us
 
-struct us_frontend {
+struct us_frontend : us::WeightTable {
   int kind = 0;                        // 0: Encoder, 1: DurationPredictor
   us_encoder_config ec{};
   us_duration_config dc{};
-  int device = 0;
-  std::vector<std::string> keys;       // state_dict order
-  std::map<std::string, us::Weight> w;
-  std::string err;
   std::map<const void*, us::EncoderTape> tapes;   // training forwards whose tape a workspace holds (us_encoder_tape_release)
 };
 
@@ -137,9 +126,9 @@ struct EncoderMode {
   float p = 0.f, p_prenet = 0.f;
 };
 
-int fe_fail(us_frontend* h, int code, const std::string& msg);
-// every weight is loaded and the current device is the handle's (weights live there, launches go to a stream of that device)
-int fe_check(us_frontend* h, const char* what);
+// the table's fail (h may be null) and all_loaded under the names the three front-end files call them by
+inline int fe_fail(us_frontend* h, int code, const std::string& msg) { return WeightTable::fail(h, code, msg); }
+inline int fe_check(us_frontend* h, const char* what) { return h->all_loaded(what); }
 // frontend.hip: embedding -> prenet -> transformer blocks -> proj_m -> mu_x, x_out in the reference's [B][C][L]
 int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const int64_t* lengths,
                     float* mu_x, float* x_out, int B, int L);

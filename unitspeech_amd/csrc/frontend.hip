@@ -307,59 +307,28 @@ __global__ void fe_pack_conv_kernel(const float* w, float* out, int Cout, int Ci
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-}  // namespace
-
-int fe_fail(us_frontend* h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  set_last_error(msg.c_str());
-  return code;
-}
-// the handle is bound to the device that was current at creation: weights live there, launches go to a stream of that device
-static int fe_device(us_frontend* h, const char* what) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
-    return fe_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
-                                     std::to_string(h->device) + ")");
-  return US_OK;
-}
-int fe_check(us_frontend* h, const char* what) {
-  for (const auto& k : h->keys)
-    if (!h->w[k].loaded) return fe_fail(h, US_EWEIGHTS, std::string(what) + ": weight '" + k + "' has not been loaded");
-  return fe_device(h, what);
-}
-
-namespace {
-
-int fe_hip(us_frontend* h, const char* what, hipError_t e) {
-  return fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-void add_key(us_frontend* h, const std::string& k, std::vector<int64_t> shape) {
-  h->keys.push_back(k);
-  h->w[k].shape = std::move(shape);
-}
 void add_conv(us_frontend* h, const std::string& p, int cout, int cin, int k) {
-  add_key(h, p + ".weight", {cout, cin, k});
-  add_key(h, p + ".bias", {cout});
+  h->add(p + ".weight", {cout, cin, k});
+  h->add(p + ".bias", {cout});
 }
 void add_norm(us_frontend* h, const std::string& p, int c) {
-  add_key(h, p + ".gamma", {c});
-  add_key(h, p + ".beta", {c});
+  h->add(p + ".gamma", {c});
+  h->add(p + ".beta", {c});
 }
 
 // state_dict of Encoder (module registration order of encoder.py:270-291)
 void encoder_keys(us_frontend* h) {
   const auto& c = h->ec;
   const int C = c.n_channels, D = C / c.n_heads;
-  add_key(h, "emb.weight", {c.n_vocab, C});
+  h->add("emb.weight", {c.n_vocab, C});
   for (int i = 0; i < kPrenetLayers; ++i) add_conv(h, "prenet.conv_layers." + std::to_string(i), C, C, kPrenetKernel);
   for (int i = 0; i < kPrenetLayers; ++i) add_norm(h, "prenet.norm_layers." + std::to_string(i), C);
   add_conv(h, "prenet.proj", C, C, 1);
   for (int i = 0; i < c.n_layers; ++i) {
     const std::string p = "encoder.attn_layers." + std::to_string(i);
     if (c.window_size > 0) {
-      add_key(h, p + ".emb_rel_k", {1, 2 * c.window_size + 1, D});
-      add_key(h, p + ".emb_rel_v", {1, 2 * c.window_size + 1, D});
+      h->add(p + ".emb_rel_k", {1, 2 * c.window_size + 1, D});
+      h->add(p + ".emb_rel_v", {1, 2 * c.window_size + 1, D});
     }
     for (const char* n : {".conv_q", ".conv_k", ".conv_v", ".conv_o"}) add_conv(h, p + n, C, C, 1);
   }
@@ -387,7 +356,6 @@ size_t fe_scratch_floats(const us_frontend* h, long long rows) {
   if (h->kind == 0) return (size_t)rows * (6 * (size_t)h->ec.n_channels + (size_t)h->ec.filter_channels);      // x, x_org/y, q, k, v, a (C each) + h1 (F)
   return (size_t)rows * ((size_t)(h->dc.in_channels + h->dc.spk_emb_dim) + 2 * (size_t)h->dc.filter_channels);
 }
-float* fe_base(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
 
 int conv1d(us_frontend* h, hipStream_t s, const std::string& prefix, const float* in, float* out, const float* mask, const float* add,
            int B, int L, bool mask_in, bool relu, bool mask_out) {
@@ -525,40 +493,28 @@ int us_duration_predictor_create(us_frontend_handle* out, const us_duration_conf
 
 int us_frontend_destroy(us_frontend_handle h) {
   if (!h) return US_OK;
-  for (auto& kv : h->w) {
-    if (kv.second.dev) (void)hipFree(kv.second.dev);
-    if (kv.second.packed) (void)hipFree(kv.second.packed);
-  }
+  h->free_weights();
   delete h;
   return US_OK;
 }
 
-int us_frontend_num_weights(us_frontend_handle h) { return h ? (int)h->keys.size() : 0; }
-const char* us_frontend_weight_key(us_frontend_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->keys.size()) ? h->keys[i].c_str() : nullptr;
-}
-const char* us_frontend_last_error(us_frontend_handle h) { return h ? h->err.c_str() : us_last_error(nullptr); }
+int us_frontend_num_weights(us_frontend_handle h) { return h ? h->num() : 0; }
+const char* us_frontend_weight_key(us_frontend_handle h, int i) { return h ? h->key(i) : nullptr; }
+const char* us_frontend_last_error(us_frontend_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
 
 int us_frontend_load_weight(us_frontend_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
-  if (!h || !key || !data || !shape) return fe_fail(h, US_EINVAL, "us_frontend_load_weight: null argument");
-  auto it = h->w.find(key);
-  if (it == h->w.end()) return fe_fail(h, US_ENOKEY, std::string("us_frontend_load_weight: unknown key '") + key + "'");
-  Weight& w = it->second;
-  bool same = ndim == (int)w.shape.size();
-  for (int i = 0; same && i < ndim; ++i) same = shape[i] == w.shape[i];
-  if (!same) return fe_fail(h, US_ESHAPE, std::string("us_frontend_load_weight: shape of '") + key + "' does not match the configuration");
-  int rcd = fe_device(h, "us_frontend_load_weight");
-  if (rcd != US_OK) return rcd;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t n = w.numel();
-  hipError_t e;
-  if (!w.dev && (e = hipMalloc(&w.dev, n * sizeof(float))) != hipSuccess) return fe_hip(h, "hipMalloc(weight)", e);
-  if ((e = hipMemcpyAsync(w.dev, data, n * sizeof(float), hipMemcpyDeviceToDevice, s)) != hipSuccess) return fe_hip(h, "hipMemcpyAsync(weight)", e);
+  Weight* wp;
+  const int rc = WeightTable::load(h, "us_frontend_load_weight", key, data, shape, ndim, s, &wp);
+  if (rc != US_OK) return rc;
+  Weight& w = *wp;
   if (ndim == 3) {       // Conv1d weight
-    if (!w.packed && (e = hipMalloc(&w.packed, n * sizeof(float))) != hipSuccess) return fe_hip(h, "hipMalloc(packed weight)", e);
+    const size_t n = w.numel();
+    hipError_t e;
+    if (!w.packed && (e = hipMalloc(&w.packed, n * sizeof(float))) != hipSuccess) return h->hip("hipMalloc(packed weight)", e);
     hipLaunchKernelGGL(fe_pack_conv_kernel, dim3((unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, w.dev, w.packed,
                        (int)shape[0], (int)shape[1], (int)shape[2]);
-    if ((e = hipGetLastError()) != hipSuccess) return fe_hip(h, "fe_pack_conv_kernel", e);
+    if ((e = hipGetLastError()) != hipSuccess) return h->hip("fe_pack_conv_kernel", e);
   }
   w.loaded = true;
   return US_OK;
@@ -584,7 +540,7 @@ int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* 
     return fe_fail(h, US_EWORKSPACE, "us_encoder_forward: workspace too small (us_frontend_workspace_bytes)");
   // seven planes (fe_scratch_floats): x_org, then conv_o / conv_2's output once the prenet is done; the running x (both LayerNorms
   // of a block write it in place); q, k (the prenet ping-pongs in them, proj_m's output lands in q); v; the attention output; h1
-  float* p0 = fe_base(workspace);
+  float* p0 = ws_align(workspace);
   float* xr = p0 + rows * C;
   float* q = xr + rows * C;
   float* k = q + rows * C;
@@ -598,7 +554,7 @@ int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* 
   b.layer.assign(c.n_layers, EncoderBufs::Layer{xr, q, k, v, at, nullptr, xr, h1, nullptr, nullptr});
   if ((rc = encoder_forward(h, static_cast<hipStream_t>(stream), b, EncoderMode{}, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_hip(h, "us_encoder_forward", e);
+  return e == hipSuccess ? US_OK : h->hip("us_encoder_forward", e);
 }
 
 int us_duration_predictor_forward(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,
@@ -615,7 +571,7 @@ int us_duration_predictor_forward(us_frontend_handle h, const float* x, const fl
   if (!workspace || workspace_bytes < us_frontend_workspace_bytes(h, B, L))
     return fe_fail(h, US_EWORKSPACE, "us_duration_predictor_forward: workspace too small (us_frontend_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* xin = fe_base(workspace);
+  float* xin = ws_align(workspace);
   float* a1 = xin + rows * Cin;
   float* a2 = a1 + rows * F;
   fe_gather_concat(s, x, g, xin, B, L, c.in_channels, c.spk_emb_dim);
@@ -626,7 +582,7 @@ int us_duration_predictor_forward(us_frontend_handle h, const float* x, const fl
   if ((rc = layernorm(h, s, "norm_2", a2, nullptr, a2, nullptr, rows, F, 1e-5f, false)) != US_OK) return rc;
   if ((rc = conv1d(h, s, "proj", a2, logw, x_mask, nullptr, B, L, true, false, true)) != US_OK) return rc;      // [B][L][1] == [B][1][L]
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_hip(h, "us_duration_predictor_forward", e);
+  return e == hipSuccess ? US_OK : h->hip("us_duration_predictor_forward", e);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
 #include "kernels.h"
 
 namespace us {
@@ -456,13 +457,6 @@ __global__ __launch_bounds__(256) void sp_normalize_kernel(float* __restrict__ x
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-struct SpWeight {
-  std::vector<int64_t> shape;
-  float* dev = nullptr;         // reference layout
-  bool loaded = false;
-  size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
-};
-
 struct SpConv {                 // one dense Conv1d in packed form
   int cin = 0, cin_tot = 0, cout = 0, k = 1, Kpad = 0, ldw = 0;
   float* packed = nullptr;
@@ -481,64 +475,46 @@ struct SpRes2 {
 }  // namespace
 }  // namespace us
 
-struct us_speaker {
+struct us_speaker : us::WeightTable {      // keys: the floating-point entries only
   us_speaker_config cfg{};
-  int device = 0;
   int width = 0, wpad = 0;
-  std::vector<std::string> keys;       // state_dict order, floating-point entries only
-  std::map<std::string, us::SpWeight> w;
   std::map<std::string, us::SpConv> conv;
   std::map<std::string, us::SpBn> bn;
   std::map<std::string, us::SpRes2> res2;
   float* lw = nullptr;                 // softmax(feature_weight)
   bool allocated = false;              // device tensors exist (made by the first load, so creating a handle touches no device)
   bool dirty = true;                   // a weight changed since the derived forms were made
-  std::string err;
 };
 
 namespace us {
 namespace {
 
-int sp_fail(us_speaker* h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  set_last_error(msg.c_str());
-  return code;
-}
-int sp_hip(us_speaker* h, const char* what, hipError_t e) { return sp_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-int sp_round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-void sp_key(us_speaker* h, const std::string& k, std::vector<int64_t> shape) {
-  h->keys.push_back(k);
-  h->w[k].shape = std::move(shape);
-}
-
 void sp_add_conv(us_speaker* h, const std::string& p, int cin, int cin_tot, int cout, int k) {
-  sp_key(h, p + ".weight", {cout, cin_tot, k});
-  sp_key(h, p + ".bias", {cout});
+  h->add(p + ".weight", {cout, cin_tot, k});
+  h->add(p + ".bias", {cout});
   SpConv& c = h->conv[p];
   c.cin = cin; c.cin_tot = cin_tot; c.cout = cout; c.k = k;
-  c.Kpad = sp_round_up(k * cin, kSpBK); c.ldw = sp_round_up(cout, kSpBM);
+  c.Kpad = round_up(k * cin, kSpBK); c.ldw = round_up(cout, kSpBM);
 }
 
 void sp_add_bn(us_speaker* h, const std::string& p, int n, bool folded) {
-  sp_key(h, p + ".weight", {n});
-  sp_key(h, p + ".bias", {n});
-  sp_key(h, p + ".running_mean", {n});
-  sp_key(h, p + ".running_var", {n});
+  h->add(p + ".weight", {n});
+  h->add(p + ".bias", {n});
+  h->add(p + ".running_mean", {n});
+  h->add(p + ".running_var", {n});
   if (folded) h->bn[p].n = n;
 }
 
 void sp_add_linear(us_speaker* h, const std::string& p, int in, int out) {
-  sp_key(h, p + ".weight", {out, in});
-  sp_key(h, p + ".bias", {out});
+  h->add(p + ".weight", {out, in});
+  h->add(p + ".bias", {out});
 }
 
 // module registration order of ecapa_tdnn.py:206-234 (and :103-106, :27-33 inside a block)
 void speaker_keys(us_speaker* h) {
   const auto& c = h->cfg;
   const int ch = c.channels;
-  if (c.n_layers > 0) sp_key(h, "feature_weight", {c.n_layers});
+  if (c.n_layers > 0) h->add("feature_weight", {c.n_layers});
   sp_add_conv(h, "layer1.conv", c.feat_dim, c.feat_dim, ch, 5);
   sp_add_bn(h, "layer1.bn", ch, true);
   for (int l = 2; l <= 4; ++l) {
@@ -547,8 +523,8 @@ void speaker_keys(us_speaker* h) {
     sp_add_bn(h, p + ".Conv1dReluBn1.bn", ch, true);
     for (int i = 0; i < kSpStages; ++i) {
       const std::string q = p + ".Res2Conv1dReluBn.convs." + std::to_string(i);
-      sp_key(h, q + ".weight", {h->width, h->width, 3});
-      sp_key(h, q + ".bias", {h->width});
+      h->add(q + ".weight", {h->width, h->width, 3});
+      h->add(q + ".bias", {h->width});
     }
     for (int i = 0; i < kSpStages; ++i) sp_add_bn(h, p + ".Res2Conv1dReluBn.bns." + std::to_string(i), h->width, false);
     h->res2[p];
@@ -562,14 +538,6 @@ void speaker_keys(us_speaker* h) {
   sp_add_conv(h, "pooling.linear2", kSpAtt, kSpAtt, kSpOut, 1);
   sp_add_bn(h, "bn", 2 * kSpOut, true);
   sp_add_linear(h, "linear", 2 * kSpOut, c.emb_dim);
-}
-
-int sp_device(us_speaker* h, const char* what) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
-    return sp_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
-                                     std::to_string(h->device) + ")");
-  return US_OK;
 }
 
 // every tensor the forward reads, at once: after the first load neither a load nor a forward allocates
@@ -648,8 +616,6 @@ SpPlan sp_plan(const us_speaker_config& c, int B, int T) {
   return p;
 }
 
-float* sp_base(void* workspace) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255)); }
-
 void sp_conv(us_speaker* h, hipStream_t s, const std::string& p, const std::string& bn, int act, const float* in, long long in_bs, float* out,
              long long out_bs, const float* bias2, int B, int T) {
   const SpConv& c = h->conv.at(p);
@@ -672,18 +638,18 @@ extern "C" {
 using namespace us;
 
 int us_speaker_create(us_speaker_handle* out, const us_speaker_config* cfg) {
-  if (!out || !cfg) return sp_fail(nullptr, US_EINVAL, "us_speaker_create: null argument");
+  if (!out || !cfg) return WeightTable::fail(nullptr, US_EINVAL, "us_speaker_create: null argument");
   const auto& c = *cfg;
   if (c.feat_dim <= 0 || c.feat_dim > 8192 || c.emb_dim <= 0 || c.emb_dim > 8192 || c.n_layers < 0 || c.n_layers > 64 ||
       c.global_context_att < 0 || c.global_context_att > 1)
-    return sp_fail(nullptr, US_EINVAL, "us_speaker_create: bad feat_dim / emb_dim / n_layers / global_context_att");
+    return WeightTable::fail(nullptr, US_EINVAL, "us_speaker_create: bad feat_dim / emb_dim / n_layers / global_context_att");
   if (c.channels <= 0 || c.channels % kSpScale != 0 || c.channels > 64 * kSpScale)
-    return sp_fail(nullptr, US_EINVAL, "us_speaker_create: channels must be a multiple of 8, at most 512 (a Res2 chunk of 64 channels "
-                                       "is what the chained kernel holds in LDS)");
+    return WeightTable::fail(nullptr, US_EINVAL, "us_speaker_create: channels must be a multiple of 8, at most 512 (a Res2 chunk of 64 "
+                                                 "channels is what the chained kernel holds in LDS)");
   auto* h = new us_speaker();
   h->cfg = c;
   h->width = c.channels / kSpScale;
-  h->wpad = sp_round_up(h->width, kRes2Co);
+  h->wpad = round_up(h->width, kRes2Co);
   (void)hipGetDevice(&h->device);
   speaker_keys(h);
   *out = h;
@@ -692,8 +658,7 @@ int us_speaker_create(us_speaker_handle* out, const us_speaker_config* cfg) {
 
 int us_speaker_destroy(us_speaker_handle h) {
   if (!h) return US_OK;
-  for (auto& kv : h->w)
-    if (kv.second.dev) (void)hipFree(kv.second.dev);
+  h->free_weights();
   for (auto& kv : h->conv)
     if (kv.second.packed) (void)hipFree(kv.second.packed);
   for (auto& kv : h->bn)
@@ -707,30 +672,22 @@ int us_speaker_destroy(us_speaker_handle h) {
   return US_OK;
 }
 
-int us_speaker_num_weights(us_speaker_handle h) { return h ? (int)h->keys.size() : 0; }
-const char* us_speaker_weight_key(us_speaker_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->keys.size()) ? h->keys[i].c_str() : nullptr;
-}
-const char* us_speaker_last_error(us_speaker_handle h) { return h ? h->err.c_str() : us_last_error(nullptr); }
+int us_speaker_num_weights(us_speaker_handle h) { return h ? h->num() : 0; }
+const char* us_speaker_weight_key(us_speaker_handle h, int i) { return h ? h->key(i) : nullptr; }
+const char* us_speaker_last_error(us_speaker_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
 
 int us_speaker_load_weight(us_speaker_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
-  if (!h || !key || !data || !shape) return sp_fail(h, US_EINVAL, "us_speaker_load_weight: null argument");
-  const std::string k(key);
-  if (k.find(".shortcut.") != std::string::npos)
-    return sp_fail(h, US_ENOKEY, "us_speaker_load_weight: '" + k + "': SE_Res2Block shortcuts (in_channels != out_channels) are not built");
-  auto it = h->w.find(k);
-  if (it == h->w.end()) return sp_fail(h, US_ENOKEY, "us_speaker_load_weight: unknown key '" + k + "'");
-  SpWeight& w = it->second;
-  bool same = ndim == (int)w.shape.size();
-  for (int i = 0; same && i < ndim; ++i) same = shape[i] == w.shape[i];
-  if (!same) return sp_fail(h, US_ESHAPE, "us_speaker_load_weight: shape of '" + k + "' does not match the configuration");
-  int rc = sp_device(h, "us_speaker_load_weight");
+  // shortcuts are refused by name, before the key lookup (and after the null-argument check, which find() makes)
+  if (h && key && data && shape && std::string(key).find(".shortcut.") != std::string::npos)
+    return h->fail(US_ENOKEY, std::string("us_speaker_load_weight: '") + key +
+                                  "': SE_Res2Block shortcuts (in_channels != out_channels) are not built");
+  Weight* w;
+  int rc = WeightTable::find(h, "us_speaker_load_weight", key, data, shape, ndim, &w);
   if (rc != US_OK) return rc;
   hipError_t e;
-  if (!h->allocated && (e = sp_alloc(h)) != hipSuccess) return sp_hip(h, "us_speaker_load_weight: hipMalloc", e);
-  e = hipMemcpyAsync(w.dev, data, w.numel() * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return sp_hip(h, "hipMemcpyAsync(weight)", e);
-  w.loaded = true;
+  if (!h->allocated && (e = sp_alloc(h)) != hipSuccess) return h->hip("us_speaker_load_weight: hipMalloc", e);
+  if ((rc = h->copy(*w, data, static_cast<hipStream_t>(stream))) != US_OK) return rc;      // sp_alloc made w->dev: no allocation here
+  w->loaded = true;
   h->dirty = true;
   return US_OK;
 }
@@ -742,24 +699,22 @@ size_t us_speaker_workspace_bytes(us_speaker_handle h, int B, int T) {
 
 int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, int B, int T, float* emb_out, int normalize, void* workspace,
                        size_t workspace_bytes, us_stream stream) {
-  if (!h || !hidden_states || !emb_out || B <= 0 || T <= 0 || L < 0) return sp_fail(h, US_EINVAL, "us_speaker_forward: bad argument");
+  if (!h || !hidden_states || !emb_out || B <= 0 || T <= 0 || L < 0) return WeightTable::fail(h, US_EINVAL, "us_speaker_forward: bad argument");
   const auto& c = h->cfg;
   if (L != 0 && L != c.n_layers)
-    return sp_fail(h, US_EINVAL, "us_speaker_forward: L must be the configuration's n_layers (" + std::to_string(c.n_layers) +
-                                     "), or 0 for already combined [B][feat_dim][T] features");
-  if (normalize && B != 1) return sp_fail(h, US_EINVAL, "us_speaker_forward: normalize divides the whole output by its norm and is defined for B = 1");
+    return h->fail(US_EINVAL, "us_speaker_forward: L must be the configuration's n_layers (" + std::to_string(c.n_layers) +
+                                  "), or 0 for already combined [B][feat_dim][T] features");
+  if (normalize && B != 1) return h->fail(US_EINVAL, "us_speaker_forward: normalize divides the whole output by its norm and is defined for B = 1");
   const long long big = std::max<long long>(std::max(c.feat_dim, 3 * c.channels), kSpOut);
-  if ((long long)B * T * big >= (1ll << 31) || B > 65535) return sp_fail(h, US_EINVAL, "us_speaker_forward: B * T * channels too large");
-  for (const auto& k : h->keys)
-    if (!h->w[k].loaded) return sp_fail(h, US_EWEIGHTS, "us_speaker_forward: weight '" + k + "' has not been loaded");
-  int rc = sp_device(h, "us_speaker_forward");
+  if ((long long)B * T * big >= (1ll << 31) || B > 65535) return h->fail(US_EINVAL, "us_speaker_forward: B * T * channels too large");
+  const int rc = h->all_loaded("us_speaker_forward");
   if (rc != US_OK) return rc;
   if (!workspace || workspace_bytes < us_speaker_workspace_bytes(h, B, T))
-    return sp_fail(h, US_EWORKSPACE, "us_speaker_forward: workspace too small (us_speaker_workspace_bytes)");
+    return h->fail(US_EWORKSPACE, "us_speaker_forward: workspace too small (us_speaker_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->dirty) sp_prepare(h, s);
   const SpPlan p = sp_plan(c, B, T);
-  float* base = sp_base(workspace);
+  float* base = ws_align(workspace);
   const int ch = c.channels, F = c.feat_dim;
   auto W = [&](const std::string& k) { return h->w.at(k).dev; };
   auto rows_grid = [](long long rows) { return dim3((unsigned)((rows + 3) / 4)); };
@@ -813,15 +768,15 @@ int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, i
                      emb_out, B, 2 * kSpOut, c.emb_dim);
   if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(1), dim3(256), 0, s, emb_out, B * c.emb_dim);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : sp_hip(h, "us_speaker_forward", e);
+  return e == hipSuccess ? US_OK : h->hip("us_speaker_forward", e);
 }
 
 int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape) {
-  if (!h || !data || !shape || B <= 0 || T <= 0) return sp_fail(h, US_EINVAL, "us_speaker_stage: bad argument");
+  if (!h || !data || !shape || B <= 0 || T <= 0) return WeightTable::fail(h, US_EINVAL, "us_speaker_stage: bad argument");
   if (!workspace || workspace_bytes < us_speaker_workspace_bytes(h, B, T))
-    return sp_fail(h, US_EWORKSPACE, "us_speaker_stage: workspace too small (us_speaker_workspace_bytes)");
+    return h->fail(US_EWORKSPACE, "us_speaker_stage: workspace too small (us_speaker_workspace_bytes)");
   const SpPlan p = sp_plan(h->cfg, B, T);
-  const float* base = sp_base(workspace);
+  const float* base = ws_align(workspace);
   shape[0] = B;
   shape[2] = T;
   switch (stage) {
@@ -829,7 +784,7 @@ int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspa
     case US_SPEAKER_STAGE_LAYER1: *data = base + p.o1; shape[1] = h->cfg.channels; break;
     case US_SPEAKER_STAGE_BLOCKS: *data = base + p.cat; shape[1] = 3 * h->cfg.channels; break;
     case US_SPEAKER_STAGE_POOLING: *data = base + p.praw; shape[1] = 2 * kSpOut; shape[2] = 1; break;
-    default: return sp_fail(h, US_EINVAL, "us_speaker_stage: unknown stage");
+    default: return h->fail(US_EINVAL, "us_speaker_stage: unknown stage");
   }
   return US_OK;
 }

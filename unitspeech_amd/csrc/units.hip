@@ -26,6 +26,7 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
 #include "kernels.h"
 
 namespace us {
@@ -39,8 +40,6 @@ constexpr int kBC = 64;        // centres per tile
 constexpr int kBK = 16;        // reduction slice per LDS stage
 constexpr int kXld = 68;       // row stride of the transposed feature slice: the four k of a float4 land on banks 16 apart
 constexpr int kTargetGroups = 512;   // workgroups wanted before the centres stop being split across workgroups (two per CU)
-
-__host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // ---- pack ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void un_norm_kernel(const float* __restrict__ c, float* __restrict__ hn, float* __restrict__ meta, int K,

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
 #include "kernels.h"
 
 namespace us {
@@ -244,13 +245,6 @@ __global__ __launch_bounds__(256) void vc_post_kernel(const float* __restrict__ 
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-struct VcWeight {
-  std::vector<int64_t> shape;
-  float* dev = nullptr;         // reference layout
-  bool loaded = false;
-  size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
-};
-
 struct VcConv {                 // one Conv1d / ConvTranspose1d in packed form
   std::string prefix;
   int cin = 0, cout = 0, k = 0, dil = 1, u = 0, pad = 0;     // u > 0: transposed with stride u
@@ -268,36 +262,18 @@ struct VcAct {                  // one Activation1d
 }  // namespace
 }  // namespace us
 
-struct us_vocoder {
+struct us_vocoder : us::WeightTable {      // keys: the remove_weight_norm form
   us_vocoder_config cfg{};
-  int device = 0;
-  std::vector<std::string> keys;       // state_dict order (remove_weight_norm form)
-  std::map<std::string, us::VcWeight> w;
   std::map<std::string, us::VcConv> conv;
   std::map<std::string, us::VcAct> act;
-  std::string err;
 };
 
 namespace us {
 namespace {
 
-int vc_fail(us_vocoder* h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  set_last_error(msg.c_str());
-  return code;
-}
-int vc_hip(us_vocoder* h, const char* what, hipError_t e) { return vc_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-void vc_key(us_vocoder* h, const std::string& k, std::vector<int64_t> shape) {
-  h->keys.push_back(k);
-  h->w[k].shape = std::move(shape);
-}
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 void vc_add_conv(us_vocoder* h, const std::string& p, int cin, int cout, int k, int dil) {
-  vc_key(h, p + ".weight", {cout, cin, k});
-  vc_key(h, p + ".bias", {cout});
+  h->add(p + ".weight", {cout, cin, k});
+  h->add(p + ".bias", {cout});
   VcConv& c = h->conv[p];
   c.prefix = p; c.cin = cin; c.cout = cout; c.k = k; c.dil = dil; c.taps = k;
   c.Kpad = round_up(k * cin, kVcBK); c.ldw = round_up(cout, kVcBM); c.nph = 1;
@@ -305,8 +281,8 @@ void vc_add_conv(us_vocoder* h, const std::string& p, int cin, int cout, int k, 
 }
 
 void vc_add_up(us_vocoder* h, const std::string& p, int cin, int cout, int k, int u) {
-  vc_key(h, p + ".weight", {cin, cout, k});      // ConvTranspose1d weight layout [in, out, k]
-  vc_key(h, p + ".bias", {cout});
+  h->add(p + ".weight", {cin, cout, k});      // ConvTranspose1d weight layout [in, out, k]
+  h->add(p + ".bias", {cout});
   VcConv& c = h->conv[p];
   c.prefix = p; c.cin = cin; c.cout = cout; c.k = k; c.u = u; c.pad = (k - u) / 2;
   c.taps = k / u; c.Kpad = round_up(c.taps * cin, kVcBK); c.ldw = round_up(cout, kVcBM); c.nph = u;
@@ -314,10 +290,10 @@ void vc_add_up(us_vocoder* h, const std::string& p, int cin, int cout, int k, in
 }
 
 void vc_add_act(us_vocoder* h, const std::string& p, int C) {
-  vc_key(h, p + ".act.alpha", {C});
-  if (h->cfg.activation == US_VOCODER_SNAKEBETA) vc_key(h, p + ".act.beta", {C});
-  vc_key(h, p + ".upsample.filter", {1, 1, 12});
-  vc_key(h, p + ".downsample.lowpass.filter", {1, 1, 12});
+  h->add(p + ".act.alpha", {C});
+  if (h->cfg.activation == US_VOCODER_SNAKEBETA) h->add(p + ".act.beta", {C});
+  h->add(p + ".upsample.filter", {1, 1, 12});
+  h->add(p + ".downsample.lowpass.filter", {1, 1, 12});
   VcAct& a = h->act[p];
   a.prefix = p; a.C = C;
 }
@@ -340,16 +316,8 @@ void vocoder_keys(us_vocoder* h) {
     }
   const int ch = channels(c, c.n_up);
   vc_add_act(h, "activation_post", ch);
-  vc_key(h, "conv_post.weight", {1, ch, kPostK});
-  vc_key(h, "conv_post.bias", {1});
-}
-
-int vc_device(us_vocoder* h, const char* what) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != h->device)
-    return vc_fail(h, US_EINVAL, std::string(what) + ": the current device (" + std::to_string(dev) + ") is not the handle's (" +
-                                     std::to_string(h->device) + ")");
-  return US_OK;
+  h->add("conv_post.weight", {1, ch, kPostK});
+  h->add("conv_post.bias", {1});
 }
 
 long long vc_hop(const us_vocoder_config& c) {
@@ -396,33 +364,34 @@ extern "C" {
 using namespace us;
 
 int us_vocoder_create(us_vocoder_handle* out, const us_vocoder_config* cfg) {
-  if (!out || !cfg) return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: null argument");
+  if (!out || !cfg) return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: null argument");
   const auto& c = *cfg;
   if (c.resblock != 1)
-    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: only resblock \"1\" (AMPBlock1) is built; AMPBlock2 is not");
+    return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: only resblock \"1\" (AMPBlock1) is built; AMPBlock2 is not");
   if (c.activation != US_VOCODER_SNAKE && c.activation != US_VOCODER_SNAKEBETA)
-    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: activation must be snake or snakebeta");
+    return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: activation must be snake or snakebeta");
   if (c.num_mels <= 0 || c.num_mels > 4096 || c.upsample_initial_channel <= 0 || c.upsample_initial_channel > 8192 || c.n_up <= 0 ||
       c.n_up > 8 || c.n_kernels <= 0 || c.n_kernels > 4 || c.snake_logscale < 0 || c.snake_logscale > 1)
-    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: bad num_mels / upsample_initial_channel / number of up-samplers or kernels");
+    return WeightTable::fail(nullptr, US_EINVAL,
+                             "us_vocoder_create: bad num_mels / upsample_initial_channel / number of up-samplers or kernels");
   if (c.upsample_initial_channel % (1 << c.n_up) != 0)
-    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: upsample_initial_channel must be divisible by 2^len(upsample_rates)");
+    return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: upsample_initial_channel must be divisible by 2^len(upsample_rates)");
   for (int i = 0; i < c.n_up; ++i) {
     const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
     if (u <= 0 || u > kVcMaxPhases || k < u || k % u != 0 || (k - u) % 2 != 0)
-      return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: up-sampler " + std::to_string(i) +
-                                             ": rate in [1, 16] and kernel a multiple of the rate with (kernel - rate) even are built");
+      return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: up-sampler " + std::to_string(i) +
+                                                       ": rate in [1, 16] and kernel a multiple of the rate with (kernel - rate) even are built");
   }
   for (int j = 0; j < c.n_kernels; ++j) {
     const int k = c.resblock_kernel_sizes[j];
     if (k <= 0 || k > 31 || k % 2 == 0)
-      return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: resblock kernel sizes must be odd and at most 31");
+      return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: resblock kernel sizes must be odd and at most 31");
     for (int l = 0; l < 3; ++l)
       if (c.resblock_dilation_sizes[j][l] <= 0 || c.resblock_dilation_sizes[j][l] > 64)
-        return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: resblock dilations must be in [1, 64]");
+        return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: resblock dilations must be in [1, 64]");
   }
   if ((size_t)(c.upsample_initial_channel >> c.n_up) * kPostK * sizeof(float) > 48 * 1024)
-    return vc_fail(nullptr, US_EINVAL, "us_vocoder_create: too many channels at conv_post");
+    return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: too many channels at conv_post");
   auto* h = new us_vocoder();
   h->cfg = c;
   (void)hipGetDevice(&h->device);
@@ -433,8 +402,7 @@ int us_vocoder_create(us_vocoder_handle* out, const us_vocoder_config* cfg) {
 
 int us_vocoder_destroy(us_vocoder_handle h) {
   if (!h) return US_OK;
-  for (auto& kv : h->w)
-    if (kv.second.dev) (void)hipFree(kv.second.dev);
+  h->free_weights();
   for (auto& kv : h->conv)
     if (kv.second.packed) (void)hipFree(kv.second.packed);
   for (auto& kv : h->act)
@@ -443,27 +411,17 @@ int us_vocoder_destroy(us_vocoder_handle h) {
   return US_OK;
 }
 
-int us_vocoder_num_weights(us_vocoder_handle h) { return h ? (int)h->keys.size() : 0; }
-const char* us_vocoder_weight_key(us_vocoder_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->keys.size()) ? h->keys[i].c_str() : nullptr;
-}
-const char* us_vocoder_last_error(us_vocoder_handle h) { return h ? h->err.c_str() : us_last_error(nullptr); }
+int us_vocoder_num_weights(us_vocoder_handle h) { return h ? h->num() : 0; }
+const char* us_vocoder_weight_key(us_vocoder_handle h, int i) { return h ? h->key(i) : nullptr; }
+const char* us_vocoder_last_error(us_vocoder_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
 
 int us_vocoder_load_weight(us_vocoder_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
-  if (!h || !key || !data || !shape) return vc_fail(h, US_EINVAL, "us_vocoder_load_weight: null argument");
-  auto it = h->w.find(key);
-  if (it == h->w.end()) return vc_fail(h, US_ENOKEY, std::string("us_vocoder_load_weight: unknown key '") + key + "'");
-  VcWeight& w = it->second;
-  bool same = ndim == (int)w.shape.size();
-  for (int i = 0; same && i < ndim; ++i) same = shape[i] == w.shape[i];
-  if (!same) return vc_fail(h, US_ESHAPE, std::string("us_vocoder_load_weight: shape of '") + key + "' does not match the configuration");
-  int rc = vc_device(h, "us_vocoder_load_weight");
-  if (rc != US_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t n = w.numel();
+  Weight* wp;
+  const int rc = WeightTable::load(h, "us_vocoder_load_weight", key, data, shape, ndim, s, &wp);
+  if (rc != US_OK) return rc;
+  Weight& w = *wp;
   hipError_t e;
-  if (!w.dev && (e = hipMalloc(&w.dev, n * sizeof(float))) != hipSuccess) return vc_hip(h, "hipMalloc(weight)", e);
-  if ((e = hipMemcpyAsync(w.dev, data, n * sizeof(float), hipMemcpyDeviceToDevice, s)) != hipSuccess) return vc_hip(h, "hipMemcpyAsync(weight)", e);
   const std::string k(key);
   const auto dot = k.rfind('.');
   const std::string prefix = k.substr(0, dot), leaf = k.substr(dot + 1);
@@ -471,19 +429,19 @@ int us_vocoder_load_weight(us_vocoder_handle h, const char* key, const float* da
   if (ci != h->conv.end() && leaf == "weight") {
     VcConv& c = ci->second;
     const size_t np = (size_t)c.nph * c.Kpad * c.ldw;
-    if (!c.packed && (e = hipMalloc(&c.packed, np * sizeof(float))) != hipSuccess) return vc_hip(h, "hipMalloc(packed weight)", e);
+    if (!c.packed && (e = hipMalloc(&c.packed, np * sizeof(float))) != hipSuccess) return h->hip("hipMalloc(packed weight)", e);
     hipLaunchKernelGGL(vc_pack_kernel, dim3((unsigned)std::min<size_t>((np + 255) / 256, 4096)), dim3(256), 0, s, w.dev, c.packed, c.cin,
                        c.cout, c.k, c.u, c.pad, c.taps, c.Kpad, c.ldw, c.nph);
   }
   const auto adot = prefix.rfind('.');
   if (adot != std::string::npos && prefix.substr(adot + 1) == "act" && (leaf == "alpha" || leaf == "beta")) {
     VcAct& a = h->act.at(prefix.substr(0, adot));
-    if (!a.ab && (e = hipMalloc(&a.ab, 2 * (size_t)a.C * sizeof(float))) != hipSuccess) return vc_hip(h, "hipMalloc(snake parameters)", e);
+    if (!a.ab && (e = hipMalloc(&a.ab, 2 * (size_t)a.C * sizeof(float))) != hipSuccess) return h->hip("hipMalloc(snake parameters)", e);
     const bool snake = h->cfg.activation == US_VOCODER_SNAKE;
     hipLaunchKernelGGL(vc_snake_param_kernel, dim3((a.C + 255) / 256), dim3(256), 0, s, w.dev, a.ab, a.C, leaf == "alpha" ? 0 : 1, snake ? 1 : 0,
                        h->cfg.snake_logscale ? 1 : 0);
   }
-  if ((e = hipGetLastError()) != hipSuccess) return vc_hip(h, "us_vocoder_load_weight", e);
+  if ((e = hipGetLastError()) != hipSuccess) return h->hip("us_vocoder_load_weight", e);
   w.loaded = true;
   return US_OK;
 }
@@ -495,22 +453,19 @@ size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T) {
 
 int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
                        us_stream stream) {
-  if (!h || !mel || !wav || B <= 0 || T <= 0) return vc_fail(h, US_EINVAL, "us_vocoder_forward: bad argument");
+  if (!h || !mel || !wav || B <= 0 || T <= 0) return WeightTable::fail(h, US_EINVAL, "us_vocoder_forward: bad argument");
   const auto& c = h->cfg;
   const long long hop = vc_hop(c);
   if (vc_max_ct(c, T) >= (1ll << 31) || (long long)T * hop >= (1ll << 31) || (long long)B * c.upsample_initial_channel > 65535 ||
       (long long)B * kVcMaxPhases > 65535)
-    return vc_fail(h, US_EINVAL, "us_vocoder_forward: B * channels or T * hop too large");
-  for (const auto& k : h->keys)
-    if (!h->w[k].loaded) return vc_fail(h, US_EWEIGHTS, "us_vocoder_forward: weight '" + k + "' has not been loaded");
-  int rc = vc_device(h, "us_vocoder_forward");
+    return h->fail(US_EINVAL, "us_vocoder_forward: B * channels or T * hop too large");
+  const int rc = h->all_loaded("us_vocoder_forward");
   if (rc != US_OK) return rc;
   if (!workspace || workspace_bytes < us_vocoder_workspace_bytes(h, B, T))
-    return vc_fail(h, US_EWORKSPACE, "us_vocoder_forward: workspace too small (us_vocoder_workspace_bytes)");
+    return h->fail(US_EWORKSPACE, "us_vocoder_forward: workspace too small (us_vocoder_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t slab = (size_t)B * (size_t)vc_max_ct(c, T);
-  float* base = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-  float* X = base;               // level input (the up-sampler's output)
+  float* X = ws_align(workspace);     // level input (the up-sampler's output)
   float* S = X + slab;           // level output: the AMP-block sum (conv_pre writes here too)
   float* R = S + slab;           // residual stream x_l of the running AMP block (l = 1, 2)
   float* A = R + slab;           // Activation1d output
@@ -543,7 +498,7 @@ int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B,
   hipLaunchKernelGGL(vc_post_kernel, dim3((t + 255) / 256, B), dim3(256), (size_t)ch * kPostK * sizeof(float), s, A,
                      h->w["conv_post.weight"].dev, h->w["conv_post.bias"].dev, wav, ch, t);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : vc_hip(h, "us_vocoder_forward", e);
+  return e == hipSuccess ? US_OK : h->hip("us_vocoder_forward", e);
 }
 
 }  // extern "C"

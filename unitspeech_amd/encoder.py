@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import HandleModule
 
 PRENET_LAYERS, PRENET_KERNEL = 3, 5            # unitspeech/encoder.py:283-284
 
@@ -188,71 +189,15 @@ class _Transformer(torch.nn.Module):
         self.norm_layers_2 = torch.nn.ModuleList([_NormParams(c) for _ in range(n_layers)])
 
 
-class _FrontEndModule(torch.nn.Module):
-    """Owns one `us_frontend_handle` and pushes parameters whose storage or version changed since the last call."""
+class _FrontEndModule(HandleModule):
+    """Owns one `us_frontend_handle`."""
+    _abi, _what = "frontend", "front end"
 
-    def _init_engine(self):
-        self._h = C.c_void_p()
-        self._device = None
-        self._versions = {}
-
-    def _create(self, lib, device):          # overridden
-        raise NotImplementedError
-
-    def _sync(self, device: torch.device, training_ok: bool = False):
-        if device.type != "cuda":
-            raise RuntimeError("the HIP front end needs tensors on a ROCm device (no CPU fallback); got " + str(device))
+    def _precondition(self, training_ok: bool = False):
         if self.training and not training_ok:
             hint = " or construct it with trainable=True to train it"
             raise RuntimeError(f"{type(self).__name__} is inference-only (the reference's Dropout layers are not built): call .eval()"
                                + hint)
-        lib = _lib.load()
-        if not self._h or self._device != device:
-            self._close()
-            with torch.cuda.device(device):
-                self._create(lib, device)
-            self._device, self._versions = device, {}
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        # the handle allocates its weight store on the CURRENT device and refuses calls made under another one (frontend.hip: fe_check)
-        with torch.cuda.device(device):
-            for key, t in self.state_dict(keep_vars=True).items():
-                tag = (t.data_ptr(), t._version, t.device)
-                if self._versions.get(key) == tag:
-                    continue
-                in_place = t.dtype == torch.float32 and t.device == device and t.is_contiguous()
-                src = t.detach() if in_place else t.detach().to(device=device, dtype=torch.float32).contiguous()
-                shape = (C.c_int64 * src.dim())(*src.shape)
-                rc = lib.us_frontend_load_weight(self._h, key.encode(), src.data_ptr(), shape, src.dim(), stream)
-                self._check(lib, rc, f"us_frontend_load_weight({key})")
-                if not in_place:
-                    torch.cuda.current_stream(device).synchronize()      # the temporary must outlive the copy
-                self._versions[key] = tag
-        return lib, stream
-
-    def _workspace(self, lib, device, B, L):
-        """Caller-owned activation scratch of one forward call (torch's caching allocator: no hipMalloc / hipFree in the call)."""
-        n = int(lib.us_frontend_workspace_bytes(self._h, B, L))
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws.numel() < n or ws.device != device:
-            self._ws = None
-            self._ws = ws = torch.empty(n, dtype=torch.uint8, device=device)
-        return ws
-
-    def _check(self, lib, rc, what):
-        if rc != _lib.US_OK:
-            msg = lib.us_frontend_last_error(self._h)
-            raise RuntimeError(f"libunitspeech_hip: {what} failed with {_lib.ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def _close(self):
-        if getattr(self, "_h", None):
-            _lib.load().us_frontend_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self._close()
-        except Exception:
-            pass
 
 
 class Encoder(_FrontEndModule):
@@ -273,7 +218,6 @@ class Encoder(_FrontEndModule):
         self.prenet = _Prenet(n_channels)
         self.encoder = _Transformer(n_channels, filter_channels, n_heads, n_layers, kernel_size, window_size)
         self.proj_m = _Conv1dParams(n_channels, n_feats, 1)
-        self._init_engine()
 
     def _create(self, lib, device):
         c = _lib.us_encoder_config(self.cfg.n_vocab, self.cfg.n_feats, self.cfg.n_channels, self.cfg.filter_channels, self.cfg.n_heads,
@@ -388,7 +332,6 @@ class DurationPredictor(_FrontEndModule):
         self.conv_2 = _Conv1dParams(filter_channels, filter_channels, kernel_size)
         self.norm_2 = _NormParams(filter_channels)
         self.proj = _Conv1dParams(filter_channels, 1, 1)
-        self._init_engine()
 
     def _create(self, lib, device):
         c = _lib.us_duration_config(self.cfg.in_channels, self.cfg.filter_channels, self.cfg.kernel_size, self.cfg.spk_emb_dim)

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._handle import HandleModule
 
 # number of hidden states the s3prl upstreams return (the CNN output plus one per transformer layer): the length of `feature_weight`
 UPSTREAM_LAYERS = {"wavlm_large": 25, "hubert_large_ll60k": 25, "wav2vec2_xlsr": 25, "wav2vec2_large_ll60k": 25,
@@ -68,9 +69,13 @@ class _AttentiveStatsPool(nn.Module):
         self.linear2 = nn.Conv1d(BOTTLENECK, in_dim, 1)
 
 
-class ECAPA_TDNN(nn.Module):
+class ECAPA_TDNN(HandleModule):
     """`ECAPA_TDNN(...)` of ecapa_tdnn.py:164.  `feat_num` (not a reference argument) gives the number of hidden states for an upstream
     `feat_type` this module does not know (the reference asks the upstream itself, :237-246)."""
+    _abi, _what = "speaker", "speaker encoder"
+    # weights: every floating-point entry of the state_dict (`num_batches_tracked` plays no part in eval mode), ~200 keys against a
+    # forward of a millisecond or two, and no parameter is ever registered anew
+    _cache_sources = True
 
     def __init__(self, feat_dim=80, channels=512, emb_dim=192, global_context_att=False, feat_type='fbank', sr=16000,
                  feature_selection="hidden_states", update_extract=False, config_path=None, feat_num=None):
@@ -96,11 +101,6 @@ class ECAPA_TDNN(nn.Module):
         self.pooling = _AttentiveStatsPool(OUT_CHANNELS, self.global_context_att)
         self.bn = nn.BatchNorm1d(OUT_CHANNELS * 2)
         self.linear = nn.Linear(OUT_CHANNELS * 2, emb_dim)
-        self._h = C.c_void_p()
-        self._device = None
-        self._tags = {}
-        self._ws = None
-        self._src = None
 
     def config(self) -> dict:
         return {"feat_dim": self.feat_dim, "channels": self.channels[0], "emb_dim": self.emb_dim,
@@ -120,55 +120,9 @@ class ECAPA_TDNN(nn.Module):
         c.global_context_att = int(self.global_context_att)
         return c
 
-    def _sources(self):
-        """C-ABI key -> tensor: every floating-point entry of the state_dict (`num_batches_tracked` plays no part in eval mode)."""
-        return OrderedDict((k, t) for k, t in self.state_dict(keep_vars=True).items() if t.is_floating_point())
-
-    def _apply(self, fn, *args, **kwargs):
-        self._src = None                   # .to() / .float() replace the buffers: the cached tensor list is rebuilt
-        return super()._apply(fn, *args, **kwargs)
-
-    def _sync(self, device: torch.device):
-        if device.type != "cuda":
-            raise RuntimeError("the HIP speaker encoder needs tensors on a ROCm device (no CPU fallback); got " + str(device))
-        lib = _lib.load()
-        if not self._h or self._device != device:
-            self._close()
-            with torch.cuda.device(device):
-                c = self._config_struct()
-                _lib.check(lib.us_speaker_create(C.byref(self._h), C.byref(c)), None, "us_speaker_create")
-            self._device, self._tags = device, {}
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        with torch.no_grad(), torch.cuda.device(device):
-            if self._src is None:
-                self._src = list(self._sources().items())
-            for key, p in self._src:
-                tag = (p.data_ptr(), p._version, p.device)
-                if self._tags.get(key) == tag:
-                    continue
-                src = p.detach().to(device=device, dtype=torch.float32).contiguous()
-                shape = (C.c_int64 * src.dim())(*src.shape)
-                rc = lib.us_speaker_load_weight(self._h, key.encode(), src.data_ptr(), shape, src.dim(), stream)
-                self._check(lib, rc, f"us_speaker_load_weight({key})")
-                torch.cuda.current_stream(device).synchronize()        # the temporary must outlive the copy
-                self._tags[key] = tag
-        return lib, stream
-
-    def _check(self, lib, rc, what):
-        if rc != _lib.US_OK:
-            msg = lib.us_speaker_last_error(self._h)
-            raise RuntimeError(f"libunitspeech_hip: {what} failed with {_lib.ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def _close(self):
-        if getattr(self, "_h", None):
-            _lib.load().us_speaker_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self._close()
-        except Exception:
-            pass
+    def _create(self, lib, device):
+        c = self._config_struct()
+        _lib.check(lib.us_speaker_create(C.byref(self._h), C.byref(c)), None, "us_speaker_create")
 
     def _input(self, hidden_states):
         """-> (contiguous fp32 tensor, L, B, T) with L = 0 for the combined [B, C, T] form."""
@@ -195,13 +149,9 @@ class ECAPA_TDNN(nn.Module):
         device = x.device
         lib, stream = self._sync(device)
         out = torch.empty(B, self.emb_dim, device=device)
-        n = int(lib.us_speaker_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < n or self._ws.device != device:
-            self._ws = None
-            self._ws = torch.empty(n, dtype=torch.uint8, device=device)
+        ws = self._workspace(lib, device, B, T)
         with torch.cuda.device(device):
-            rc = lib.us_speaker_forward(self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), self._ws.data_ptr(),
-                                        self._ws.numel(), stream)
+            rc = lib.us_speaker_forward(self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), ws.data_ptr(), ws.numel(), stream)
         self._check(lib, rc, "us_speaker_forward")
         self._last = (B, T)
         return out

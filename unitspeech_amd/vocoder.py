@@ -25,6 +25,7 @@ from torch import nn
 from torch.nn.utils.weight_norm import WeightNorm
 
 from . import _lib
+from ._handle import HandleModule
 
 # configs of the 22 kHz / 80-band BigVGAN generators (hop 256): the large one and the base one
 BIGVGAN_22KHZ_80BAND = {
@@ -126,8 +127,9 @@ def _check_config(h: _H) -> None:
         raise ValueError("1 to 4 resblock kernel sizes, each with 3 dilations (AMPBlock1)")
 
 
-class BigVGAN(nn.Module):
+class BigVGAN(HandleModule):
     """`BigVGAN(h)` of models.py:117; `forward(mel [B, num_mels, T]) -> [B, 1, T * prod(upsample_rates)]`."""
+    _abi, _what = "vocoder", "vocoder"
 
     def __init__(self, h):
         super().__init__()
@@ -146,9 +148,6 @@ class BigVGAN(nn.Module):
         self.activation_post = _Activation1d(ch, h)
         self.conv_post = _wn(nn.Conv1d(ch, 1, 7, 1, padding=3))
         self.hop = int(np.prod(h.upsample_rates))
-        self._h = C.c_void_p()
-        self._device = None
-        self._tags = {}
 
     def remove_weight_norm(self):
         """models.py:193-202: every convolution loses its weight norm (the folded weight becomes the parameter `weight`)."""
@@ -179,62 +178,26 @@ class BigVGAN(nn.Module):
         c.snake_logscale = int(bool(h.snake_logscale))
         return c
 
+    def _create(self, lib, device):
+        c = self._config_struct()
+        _lib.check(lib.us_vocoder_create(C.byref(self._h), C.byref(c)), None, "us_vocoder_create")
+
     def _sources(self):
-        """C-ABI key -> (tensors its value is made from, function making it): folded conv weights, biases, Snake parameters, filters."""
+        """Folded conv weights (made anew while the weight norm is on), biases, Snake parameters, filters."""
         out = OrderedDict()
         for name, m in self.named_modules():
             if isinstance(m, (nn.Conv1d, nn.ConvTranspose1d)):
                 hook = next((hk for hk in m._forward_pre_hooks.values() if isinstance(hk, WeightNorm)), None)
                 if hook is None:
-                    out[name + ".weight"] = ((m.weight,), lambda m=m: m.weight)
+                    out[name + ".weight"] = ((m.weight,), None)
                 else:
                     out[name + ".weight"] = ((getattr(m, hook.name + "_g"), getattr(m, hook.name + "_v")),
                                              lambda m=m, hook=hook: hook.compute_weight(m))
-                out[name + ".bias"] = ((m.bias,), lambda m=m: m.bias)
+                out[name + ".bias"] = ((m.bias,), None)
         for key, t in self.state_dict(keep_vars=True).items():
             if key.endswith((".alpha", ".beta", ".filter")):
-                out[key] = ((t,), lambda t=t: t)
+                out[key] = ((t,), None)
         return out
-
-    def _sync(self, device: torch.device):
-        if device.type != "cuda":
-            raise RuntimeError("the HIP vocoder needs tensors on a ROCm device (no CPU fallback); got " + str(device))
-        lib = _lib.load()
-        if not self._h or self._device != device:
-            self._close()
-            with torch.cuda.device(device):
-                c = self._config_struct()
-                _lib.check(lib.us_vocoder_create(C.byref(self._h), C.byref(c)), None, "us_vocoder_create")
-            self._device, self._tags = device, {}
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        with torch.no_grad(), torch.cuda.device(device):
-            for key, (parts, make) in self._sources().items():
-                tag = tuple((p.data_ptr(), p._version, p.device) for p in parts)
-                if self._tags.get(key) == tag:
-                    continue
-                src = make().detach().to(device=device, dtype=torch.float32).contiguous()
-                shape = (C.c_int64 * src.dim())(*src.shape)
-                rc = lib.us_vocoder_load_weight(self._h, key.encode(), src.data_ptr(), shape, src.dim(), stream)
-                self._check(lib, rc, f"us_vocoder_load_weight({key})")
-                torch.cuda.current_stream(device).synchronize()        # the temporary must outlive the copy
-                self._tags[key] = tag
-        return lib, stream
-
-    def _check(self, lib, rc, what):
-        if rc != _lib.US_OK:
-            msg = lib.us_vocoder_last_error(self._h)
-            raise RuntimeError(f"libunitspeech_hip: {what} failed with {_lib.ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}")
-
-    def _close(self):
-        if getattr(self, "_h", None):
-            _lib.load().us_vocoder_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self._close()
-        except Exception:
-            pass
 
     @torch.no_grad()
     def forward(self, x):
@@ -245,11 +208,7 @@ class BigVGAN(nn.Module):
         b, _, t = x.shape
         mel = x.detach().to(dtype=torch.float32).contiguous()
         wav = torch.empty(b, 1, t * self.hop, device=device)
-        n = int(lib.us_vocoder_workspace_bytes(self._h, b, t))
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws.numel() < n or ws.device != device:
-            self._ws = None
-            self._ws = ws = torch.empty(n, dtype=torch.uint8, device=device)
+        ws = self._workspace(lib, device, b, t)
         with torch.cuda.device(device):
             rc = lib.us_vocoder_forward(self._h, mel.data_ptr(), wav.data_ptr(), b, t, ws.data_ptr(), ws.numel(), stream)
         self._check(lib, rc, "us_vocoder_forward")
