@@ -86,10 +86,10 @@ def test_repeated_runs_and_batch_items_are_bit_identical():
         assert torch.equal(batch[i:i + 1], m.forward_features(hid[:, i:i + 1].contiguous())), i
 
 
-@pytest.mark.parametrize("T", [1, 2, 9, 57, 1499])
-@pytest.mark.parametrize("size", ["tiny", "full"])
+@pytest.mark.parametrize("size,T", [("tiny", T) for T in (1, 2, 9, 57, 65, 1499)] + [("full", T) for T in (1, 2, 9, 57, 1499)])
 def test_edge_lengths_match_the_torch_restatement(golden, size, T):
-    """T = 1, 2, 9 are shorter than the dilated receptive fields (every halo path); 1499 is a 30 s clip.  Bar: the goldens' absolute
+    """T = 1, 2, 9 are shorter than the dilated receptive fields (every halo path); 65 puts exactly one step into a second 64-step tile of
+    the convolution's loader; 1499 is a 30 s clip.  Bar: the goldens' absolute
     2e-5, or 1e-5 of the largest embedding entry where that is larger (the fp32 floor of the reference itself is 2e-6 at |emb| ~ 1)."""
     cfg = json.loads(str(golden("speaker_tiny")["config"])) if size == "tiny" else FULL
     sd = {k: torch.from_numpy(v) for k, v in synthetic_ecapa_state_dict(cfg, 3).items()}

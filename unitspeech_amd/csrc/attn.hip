@@ -12,7 +12,6 @@
 
 namespace us {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kChunk = 128;

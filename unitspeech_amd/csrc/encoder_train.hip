@@ -33,8 +33,6 @@
 namespace us {
 namespace {
 
-typedef float et_f32x16 __attribute__((ext_vector_type(16)));
-
 // ---- implicit-GEMM convolution on the fp32 matrix cores ----------------------------------------------------------------
 constexpr int kBM = 64, kBN = 64, kBK = 16;
 
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
       Bs[buf][e >> 6][e & 63] = breg[i];
     }
   };
-  et_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int kl = lane >> 5, cl = lane & 31;
@@ -145,12 +143,11 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
     __syncthreads();
     cur ^= 1;
   }
-  // D layout (32x32 f32 MFMA): column = lane & 31, row = 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
   const int n = n0 + wn + cl;
   if (n >= a.N) return;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = m0 + wm + 8 * (r >> 2) + 4 * kl + (r & 3);
+    const int m = m0 + wm + mfma32_row(r, kl);
     if (kWgrad) {
       if (m < a.Cin) a.part[(((long long)split * a.K + tap) * a.Cin + m) * a.N + n] = acc[r];
       continue;

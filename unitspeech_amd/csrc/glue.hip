@@ -17,17 +17,6 @@ namespace us {
 
 namespace {
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // cumulative noise of `get_noise(t, beta_min, beta_max, cumulative=True)` (:204-209) in the reference's fp32 order:
 // beta_min * t + (0.5 * (beta_max - beta_min)) * t^2, the bracket being a Python double rounded to fp32 once
 __device__ __forceinline__ float cum_noise(float t, float beta_min, float half_delta) {
@@ -70,7 +59,7 @@ __global__ __launch_bounds__(256) void diffusion_loss_partial_kernel(const float
   {
     float ms = 0.f;
     for (int i = threadIdx.x; i < B * T; i += 256) ms += mask[i];
-    double w = wsum((double)ms);
+    double w = wave_sum_d((double)ms);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
     __syncthreads();
     if (threadIdx.x == 0) s_den = (float)(red[0] + red[1] + red[2] + red[3]) * (float)F;
@@ -87,7 +76,7 @@ __global__ __launch_bounds__(256) void diffusion_loss_partial_kernel(const float
     acc += (double)mul_rn(r, r);
     if (dscore) dscore[i] = 2.f * r * sd / den;
   }
-  acc = wsum(acc);
+  acc = wave_sum_d(acc);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void diffusion_loss_partial_kernel(const float
 __global__ __launch_bounds__(64) void diffusion_loss_final_kernel(const double* __restrict__ partial, int n, float* __restrict__ loss) {
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += 64) acc += partial[i];
-  acc = wsum(acc);
+  acc = wave_sum_d(acc);
   if (threadIdx.x == 0) loss[0] = (float)acc / (float)partial[n];
 }
 
@@ -179,8 +168,8 @@ __global__ __launch_bounds__(256) void first_conv_dgrad_kernel(const float* __re
         a1 = fmaf(g, w[C + co], a1);
       }
     }
-    a0 = wsum(a0);
-    a1 = wsum(a1);
+    a0 = wave_sum(a0);
+    a1 = wave_sum(a1);
     if (lane == 0) {
       const float m = mask[(long long)b * T + tt];
       if (gmu) gmu[p] = a0 * m;
@@ -201,7 +190,7 @@ __global__ __launch_bounds__(64) void tts_durations_kernel(const float* __restri
     w_ceil[(long long)b * L + l] = w;
     acc += w;                       // whole frame counts: exact in fp32 in any order (below 2^24)
   }
-  acc = wsum(acc);
+  acc = wave_sum(acc);
   if (threadIdx.x == 0) y_lengths[b] = (long long)fmaxf(acc, 1.f);
 }
 

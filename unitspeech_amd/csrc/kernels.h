@@ -24,6 +24,27 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
 #pragma clang fp contract(off)
   return a - b;
 }
+// The accumulator of a v_mfma_f32_32x32x2_f32 and its D layout: register r of a lane holds column lane & 31 and row mfma32_row(r,
+// lane >> 5), ascending in r.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ int mfma32_row(int r, int kl) { return 8 * (r >> 2) + 4 * kl + (r & 3); }
+// one value per lane -> the whole wave's sum / maximum in every lane, by a fixed butterfly (the same bits in every run)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+double wave_sum(double) = delete;      // a double takes wave_sum_d: no quiet rounding to float
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
 #endif
 
 // ---- f16x3 operand range ---------------------------------------------------------------------------------------------

@@ -13,17 +13,6 @@ static thread_local unsigned* t_range_flag = nullptr;
 unsigned* current_range_flag() { return t_range_flag; }
 void set_range_flag(unsigned* p) { t_range_flag = p; }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // Mish (unitspeech/unitspeech.py:13-15): x*tanh(softplus(x)), softplus threshold 20.
 // tanh(log(1+w)) = ((1+w)^2-1)/((1+w)^2+1) = w(w+2)/(w(w+2)+2) with w = e^x: one exp, one divide, no cancellation.
 // v_exp_f32 / v_rcp_f32 forms (about 1 ulp each): the library expf and IEEE division made the GroupNorm+Mish pass

@@ -27,30 +27,18 @@
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
+#include "conv1d_planar.h"
 #include "handle.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kSpOut = 1536;       // ecapa_tdnn.py:222: channels of `conv` and of the pooling
 constexpr int kSpAtt = 128;        // se_bottleneck_dim and attention_channels (:225-232)
 constexpr int kSpScale = 8;        // Res2 scale
 constexpr int kSpStages = kSpScale - 1;
 constexpr float kBnEps = 1e-5f;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 // ---- feature combine + instance norm (get_feat, :261-271) ------------------------------------------------------------------
 constexpr int kCmbT = 16, kCmbC = 64;
@@ -114,12 +102,11 @@ __global__ __launch_bounds__(256) void sp_instnorm_kernel(const float* in, float
 
 // ---- implicit-GEMM convolution ------------------------------------------------------------------------------------------------
 // out[b][co][t] = post(bias[co] + bias2[b][co] + sum_{j < taps, ci} P[j * Cin + ci][co] * in[b][ci][t + j - taps / 2]), in[] = 0 outside
-// [0, T).  P is packed once with its rows padded to a multiple of kSpBK and its columns to a multiple of kSpBM (zeros).  `in` and `out`
-// carry their own batch strides, so a tensor may be a channel slice of a wider one (the [out2, out3, out4] concatenation is written in
-// place by the three blocks).
-constexpr int kSpBM = 64;      // output channels per workgroup
+// [0, T): the main loop and the pack P are conv1d_planar.h's.  64 steps per workgroup: a wave's tile is 32 channels x 32 steps,
+// planar_conv_mainloop<1, 2> (one sub-tile, two accumulator chains taking the K slice's products in turn).  `in` and `out` carry their
+// own batch strides, so a tensor may be a channel slice of a wider one (the [out2, out3, out4] concatenation is written in place by the
+// three blocks).
 constexpr int kSpBN = 64;      // time steps per workgroup
-constexpr int kSpBK = 16;      // reduction slice per LDS stage
 enum { kActNone = 0, kActRelu = 1, kActTanh = 2 };
 
 struct SpConvArgs {
@@ -131,91 +118,29 @@ struct SpConvArgs {
   const float* shift;
   float* out;
   long long in_bs, out_bs;    // floats between batch items
-  int Cin, Cout, T, taps, Kdim, Kpad, ldw, act;
+  int Cin, Cout, T, off, Kdim, Kpad, ldw, act;
 };
 
 __global__ __launch_bounds__(256) void sp_conv_kernel(SpConvArgs a) {
-  __shared__ float As[2][kSpBK][kSpBM];
-  __shared__ float Bs[2][kSpBK][kSpBN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int mh = wave & 1, nh = wave >> 1;              // wave tile: 32 channels x 32 steps
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
   const int b = blockIdx.z;
-  const int m0 = blockIdx.y * kSpBM, n0 = blockIdx.x * kSpBN;
-  const float* __restrict__ in = a.in + (size_t)b * a.in_bs;
-  const float* __restrict__ w = a.w;
-  const int off = -(a.taps / 2);
-  const int wr = tid >> 4, wc = (tid & 15) * 4;
-  const int xr = tid >> 4, xc = tid & 15;
-  float4 wreg;
-  float xreg[4];
-  auto load = [&](int k0) {
-    wreg = *reinterpret_cast<const float4*>(w + (size_t)(k0 + wr) * a.ldw + m0 + wc);
-    const int kk = k0 + xr;
-    const bool live = kk < a.Kdim;
-    const int j = live ? kk / a.Cin : 0, ci = live ? kk - j * a.Cin : 0;
-    const float* row = in + (size_t)ci * a.T;
-    const int t0 = n0 + off + j;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int t = t0 + xc + 16 * i;
-      xreg[i] = (live && t >= 0 && t < a.T) ? row[t] : 0.f;
-    }
-  };
-  auto store = [&](int buf) {
-    *reinterpret_cast<float4*>(&As[buf][wr][wc]) = wreg;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) Bs[buf][xr][xc + 16 * i] = xreg[i];
-  };
-  f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-  const int nk = a.Kpad / kSpBK;
-  load(0);
-  store(0);
-  __syncthreads();
-  const int kl = lane >> 5, cl = lane & 31;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * kSpBK);
-#pragma unroll
-    for (int s = 0; s < kSpBK / 2; ++s) {          // two accumulators in turn: no MFMA waits on the one before it
-      const float fa = As[cur][2 * s + kl][mh * 32 + cl];
-      const float fb = Bs[cur][2 * s + kl][nh * 32 + cl];
-      acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[s & 1], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(cur ^ 1);
-    __syncthreads();
-  }
-  // D layout (32x32 f32 MFMA): column = lane & 31, row = 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
+  const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kSpBN;
+  f32x16 acc[1][2];
+  planar_conv_mainloop<1, 2>({a.in + (size_t)b * a.in_bs, a.w, a.Cin, a.T, 1, a.off, a.Kdim, a.Kpad, a.ldw, m0, n0}, acc);
   const int t = n0 + nh * 32 + cl;
   if (t >= a.T) return;
   float* __restrict__ out = a.out + (size_t)b * a.out_bs;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int co = m0 + mh * 32 + 8 * (r >> 2) + 4 * kl + (r & 3);
+    const int co = m0 + mh * 32 + mfma32_row(r, kl);
     if (co >= a.Cout) continue;
-    float v = (acc[0][r] + acc[1][r]) + a.bias[co];
+    float v = (acc[0][0][r] + acc[0][1][r]) + a.bias[co];
     if (a.bias2) v += a.bias2[(size_t)b * a.Cout + co];
     if (a.act == kActRelu) v = fmaxf(v, 0.f);
     else if (a.act == kActTanh) v = tanhf(v);
     if (a.scale) v = fmaf(v, a.scale[co], a.shift[co]);
     out[(size_t)co * a.T + t] = v;
-  }
-}
-
-// P[kk][co] (zero padded), kk = j * Cin + ci, from a Conv1d weight W[Cout][CinTot][k] of which the first Cin input channels are taken
-__global__ void sp_pack_kernel(const float* __restrict__ w, float* __restrict__ p, int Cin, int CinTot, int Cout, int k, int Kpad, int ldw) {
-  const size_t n = (size_t)Kpad * ldw;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int co = (int)(i % ldw), kk = (int)(i / ldw);
-    float v = 0.f;
-    if (co < Cout && kk < k * Cin) {
-      const int j = kk / Cin, ci = kk - j * Cin;
-      v = w[((size_t)co * CinTot + ci) * k + j];
-    }
-    p[i] = v;
   }
 }
 
@@ -457,11 +382,6 @@ __global__ __launch_bounds__(256) void sp_normalize_kernel(float* __restrict__ x
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-struct SpConv {                 // one dense Conv1d in packed form
-  int cin = 0, cin_tot = 0, cout = 0, k = 1, Kpad = 0, ldw = 0;
-  float* packed = nullptr;
-};
-
 struct SpBn {                   // one folded BatchNorm1d
   int n = 0;
   float* scale = nullptr;       // [2][n]: scale, shift
@@ -478,7 +398,7 @@ struct SpRes2 {
 struct us_speaker : us::WeightTable {      // keys: the floating-point entries only
   us_speaker_config cfg{};
   int width = 0, wpad = 0;
-  std::map<std::string, us::SpConv> conv;
+  std::map<std::string, us::PlanarConv> conv;
   std::map<std::string, us::SpBn> bn;
   std::map<std::string, us::SpRes2> res2;
   float* lw = nullptr;                 // softmax(feature_weight)
@@ -492,9 +412,7 @@ namespace {
 void sp_add_conv(us_speaker* h, const std::string& p, int cin, int cin_tot, int cout, int k) {
   h->add(p + ".weight", {cout, cin_tot, k});
   h->add(p + ".bias", {cout});
-  SpConv& c = h->conv[p];
-  c.cin = cin; c.cin_tot = cin_tot; c.cout = cout; c.k = k;
-  c.Kpad = round_up(k * cin, kSpBK); c.ldw = round_up(cout, kSpBM);
+  h->conv[p].conv(cin, cin_tot, cout, k, 1);
 }
 
 void sp_add_bn(us_speaker* h, const std::string& p, int n, bool folded) {
@@ -547,7 +465,7 @@ hipError_t sp_alloc(us_speaker* h) {
     if (e == hipSuccess && !*p) e = hipMalloc(p, std::max<size_t>(n, 1) * sizeof(float));
   };
   for (auto& kv : h->w) alloc(&kv.second.dev, kv.second.numel());
-  for (auto& kv : h->conv) alloc(&kv.second.packed, (size_t)kv.second.Kpad * kv.second.ldw);
+  for (auto& kv : h->conv) alloc(&kv.second.packed, kv.second.packed_floats());
   for (auto& kv : h->bn) alloc(&kv.second.scale, 2 * (size_t)kv.second.n);
   for (auto& kv : h->res2) {
     alloc(&kv.second.wp, (size_t)kSpStages * h->width * 3 * h->wpad);
@@ -561,12 +479,7 @@ hipError_t sp_alloc(us_speaker* h) {
 // every derived form (packed GEMM weights, folded BatchNorms, the Res2 stage packs, the layer softmax) from the loaded tensors
 void sp_prepare(us_speaker* h, hipStream_t s) {
   auto W = [&](const std::string& k) { return h->w.at(k).dev; };
-  for (auto& kv : h->conv) {
-    SpConv& c = kv.second;
-    const size_t np = (size_t)c.Kpad * c.ldw;
-    hipLaunchKernelGGL(sp_pack_kernel, dim3((unsigned)std::min<size_t>((np + 255) / 256, 4096)), dim3(256), 0, s, W(kv.first + ".weight"), c.packed,
-                       c.cin, c.cin_tot, c.cout, c.k, c.Kpad, c.ldw);
-  }
+  for (auto& kv : h->conv) kv.second.pack(W(kv.first + ".weight"), s);
   for (auto& kv : h->bn) {
     SpBn& b = kv.second;
     const std::string& p = kv.first;
@@ -618,7 +531,7 @@ SpPlan sp_plan(const us_speaker_config& c, int B, int T) {
 
 void sp_conv(us_speaker* h, hipStream_t s, const std::string& p, const std::string& bn, int act, const float* in, long long in_bs, float* out,
              long long out_bs, const float* bias2, int B, int T) {
-  const SpConv& c = h->conv.at(p);
+  const PlanarConv& c = h->conv.at(p);
   SpConvArgs a{};
   a.in = in; a.w = c.packed; a.bias = h->w.at(p + ".bias").dev; a.bias2 = bias2; a.out = out;
   if (!bn.empty()) {
@@ -626,8 +539,8 @@ void sp_conv(us_speaker* h, hipStream_t s, const std::string& p, const std::stri
     a.scale = f.scale; a.shift = f.scale + f.n;
   }
   a.in_bs = in_bs; a.out_bs = out_bs;
-  a.Cin = c.cin; a.Cout = c.cout; a.T = T; a.taps = c.k; a.Kdim = c.k * c.cin; a.Kpad = c.Kpad; a.ldw = c.ldw; a.act = act;
-  hipLaunchKernelGGL(sp_conv_kernel, dim3((T + kSpBN - 1) / kSpBN, (c.cout + kSpBM - 1) / kSpBM, B), dim3(256), 0, s, a);
+  a.Cin = c.cin; a.Cout = c.cout; a.T = T; a.off = c.off[0]; a.Kdim = c.Kdim(); a.Kpad = c.Kpad; a.ldw = c.ldw; a.act = act;
+  hipLaunchKernelGGL(sp_conv_kernel, dim3((T + kSpBN - 1) / kSpBN, (c.cout + kPcBM - 1) / kPcBM, B), dim3(256), 0, s, a);
 }
 
 }  // namespace
@@ -659,8 +572,7 @@ int us_speaker_create(us_speaker_handle* out, const us_speaker_config* cfg) {
 int us_speaker_destroy(us_speaker_handle h) {
   if (!h) return US_OK;
   h->free_weights();
-  for (auto& kv : h->conv)
-    if (kv.second.packed) (void)hipFree(kv.second.packed);
+  for (auto& kv : h->conv) kv.second.release();
   for (auto& kv : h->bn)
     if (kv.second.scale) (void)hipFree(kv.second.scale);
   for (auto& kv : h->res2) {

@@ -9,14 +9,7 @@
 
 namespace us {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // d/dz [ z * tanh(softplus(z)) ]  (softplus threshold 20 as in the forward)
 // v_exp_f32 / v_rcp_f32 forms (about 1 ulp each), as mish_f of the forward (ops.hip): with the library expf and two IEEE divisions the
@@ -1024,7 +1017,7 @@ __global__ __launch_bounds__(256) void attn_bwd_wout_kernel(const float* __restr
     atomicAdd(&gwout[i], acc * g[0]);
   }
   if (!gg) return;         // the gain's gradient comes from launch_dot_partial (fixed-order fp64 sum of grad_out * fn(x)), not from M1
-  dot = wsum(dot);
+  dot = wave_sum(dot);
   __shared__ float s_dot[4];                  // one atomic per block on the single gain-gradient word
   if ((threadIdx.x & 63) == 0) s_dot[threadIdx.x >> 6] = dot;
   __syncthreads();
@@ -1046,7 +1039,7 @@ __global__ void attn_bwd_bias_kernel(const float* __restrict__ colsumG, const fl
     atomicAdd(&gbout[c], g[0] * colsumG[c]);
   }
   if (!gg) return;
-  dot = wsum(dot);
+  dot = wave_sum(dot);
   if ((threadIdx.x & 63) == 0) atomicAdd(gg, dot);
 }
 
@@ -1058,14 +1051,9 @@ __global__ void attn_bwd_bias_kernel(const float* __restrict__ colsumG, const fl
 // (tests/golden/grads_full_8x176_fp64.npz).  Here: every block sums its fixed share of the products in fp64 (a float product is exact in
 // a double), writes ONE partial, and reduce_finalize_kernel adds the partials in index order.  No atomics, no dependence on arrival order.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wsum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 __device__ __forceinline__ void block_partial_store(double v, double* dst) {      // 256 threads; every thread calls
   __shared__ double s_p[4];
-  v = wsum_d(v);
+  v = wave_sum_d(v);
   if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) *dst = (s_p[0] + s_p[1]) + (s_p[2] + s_p[3]);
@@ -1121,7 +1109,7 @@ __global__ __launch_bounds__(64) void reduce_finalize_kernel(RedJobs jobs) {
   const double* p = jobs.p[j];
   double acc = 0.0;
   for (int i = threadIdx.x; i < jobs.n[j]; i += 64) acc += p[i];
-  acc = wsum_d(acc);
+  acc = wave_sum_d(acc);
   if (threadIdx.x == 0) {
     const double sc = jobs.scale[j] ? (double)jobs.scale[j][0] : 1.0;
     jobs.dst[j][0] += (float)(acc * sc);

@@ -32,8 +32,6 @@
 namespace us {
 namespace {
 
-typedef float tt_f32x16 __attribute__((ext_vector_type(16)));
-
 // ---- log-prior GEMM ----------------------------------------------------------------------------------------------------
 // Workgroup tile 64 (x) x 64 (y), four waves of 32 x 32.  Operands come straight from global memory (F = 80: a 32 x 32 tile reads
 // 20 KB of operands for 40 MFMAs; L2 serves the repeats): A(x, f) = mu_x[b][f][x], B(f, y) = y[b][f][y], both lane-contiguous.
@@ -47,7 +45,7 @@ __global__ __launch_bounds__(256) void mas_log_prior_kernel(const float* __restr
   const int y = blockIdx.x * 64 + (wave >> 1) * 32 + cl;
   const float* mb = mu + (size_t)b * F * Tx;
   const float* yb = yv + (size_t)b * F * Ty;
-  tt_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   float sa = 0.f, sb = 0.f;          // sum over the f of this lane's parity of mu^2 (row x) and y^2 (column y)
@@ -62,10 +60,10 @@ __global__ __launch_bounds__(256) void mas_log_prior_kernel(const float* __restr
   sa += __shfl_xor(sa, 32);
   sb += __shfl_xor(sb, 32);
   const float ysq = -0.5f * sb, ym = y < Ty ? y_mask[(size_t)b * Ty + y] : 0.f;
-  // D layout: column = lane & 31, row = 8 (r >> 2) + 4 (lane >> 5) + (r & 3); the row's mu^2 sum lives in lane `row`
+  // the MFMA column is y, the MFMA row x; the row's mu^2 sum lives in lane `row`
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int ri = 8 * (r >> 2) + 4 * kl + (r & 3);
+    const int ri = mfma32_row(r, kl);
     const float msq = -0.5f * __shfl(sa, ri);
     const int xr = blockIdx.y * 64 + (wave & 1) * 32 + ri;
     if (xr >= Tx || y >= Ty) continue;                          // after the shuffle: every lane takes part in it

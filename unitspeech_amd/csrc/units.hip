@@ -32,8 +32,6 @@
 namespace us {
 namespace {
 
-typedef float un_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kMaxK = 2048, kMaxD = 1024, kMaxSpan = 64;
 constexpr int kBR = 64;        // rows per workgroup
 constexpr int kBC = 64;        // centres per tile
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(256) void un_score_kernel(const float* __restrict__
       Xs[buf][xk + 2][xr] = xreg.z;
       Xs[buf][xk + 3][xr] = xreg.w;
     };
-    un_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -158,10 +156,10 @@ __global__ __launch_bounds__(256) void un_score_kernel(const float* __restrict__
       if (kt + 1 < nk) store(cur ^ 1);
       __syncthreads();
     }
-    // D layout (32x32 f32 MFMA): column (row of X) = lane & 31, row (centre) = 8 (r >> 2) + 4 (lane >> 5) + (r & 3), ascending in r
+    // the MFMA column is the row of X, the MFMA row the centre: a lane meets its centres in ascending order
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int c = c0 + ch * 32 + 8 * (r >> 2) + 4 * kl + (r & 3);
+      const int c = c0 + ch * 32 + mfma32_row(r, kl);
       const float s = hn[c] - (acc[0][r] + acc[1][r]);
       if (s < best.b1) {
         best.b2 = best.b1;

@@ -21,31 +21,19 @@
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
+#include "conv1d_planar.h"
 #include "handle.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ---- implicit-GEMM convolution --------------------------------------------------------------------------------------------
 // Output step q in [0, Tin) of phase r computes   out[b][co][q * ostride + r] = bias[co] + sum_{j < taps, ci} P_r[j * Cin + ci][co]
-// * in[b][ci][q + off[r] + j * dil]   with in[] = 0 outside [0, Tin).
-//  Conv1d(k, dilation d, padding d (k - 1) / 2):  one phase, ostride 1, taps k, dil d, off -d (k - 1) / 2, P[j * Cin + ci][co] =
-//    W[co][ci][j].
-//  ConvTranspose1d(Cin, Cout, k, stride u, padding p = (k - u) / 2), k = K * u:  y[co][t] = bias[co] + sum_{ci, j} W[ci][co][j] *
-//    x[ci][i] over the (i, j) with i * u - p + j = t.  Write t = q * u + r and (r + p) = a_r * u + b_r (0 <= b_r < u): then j must
-//    be n * u + b_r (n in [0, K)) and i = q + a_r - n.  So phase r is an ordinary convolution with K taps, dil 1, off[r] = a_r -
-//    (K - 1) (tap n' = K - 1 - n reads x[q + off[r] + n']) and P_r[n' * Cin + ci][co] = W[ci][co][(K - 1 - n') * u + b_r]: every one
-//    of its K taps is a real product (none of the zeros of the stride-u dilated input is ever computed), and the u phases
-//    together write each output sample exactly once (t = q * u + r covers [0, Tin * u)).
-// P is packed once at load with its K*Cin rows padded to a multiple of kVcBK and its columns to a multiple of kVcBM (zeros), so
-// the weight tile needs no bounds checks.
-constexpr int kVcBM = 64;     // output channels per workgroup
+// * in[b][ci][q + off[r] + j * dil]   with in[] = 0 outside [0, Tin): the main loop, the pack P and the polyphase form of a
+// ConvTranspose1d are conv1d_planar.h's.  128 steps per workgroup: a wave's tile is 32 channels x 64 steps, planar_conv_mainloop<2, 1>
+// (two 32-step sub-tiles, one accumulator chain each).
 constexpr int kVcBN = 128;    // output steps per workgroup
-constexpr int kVcBK = 16;     // reduction slice per LDS stage
-constexpr int kVcMaxPhases = 16;
 
 struct VcConvArgs {
   const float* in;            // [B][Cin][Tin]
@@ -55,71 +43,21 @@ struct VcConvArgs {
   const float* sum;           // [B][Cout][Tout] running AMP sum the result is added to, or null (may alias out)
   float* out;                 // [B][Cout][Tout]
   int Cin, Cout, Tin, Tout;
-  int taps, dil, Kdim, Kpad, ldw;
+  int dil, Kdim, Kpad, ldw;
   int nph, ostride;
   float div;                  // > 0: the final value is divided by it (the last AMP block of a level)
-  int off[kVcMaxPhases];
+  int off[kPcMaxPhases];
 };
 
 __global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a) {
-  __shared__ float As[2][kVcBK][kVcBM];
-  __shared__ float Bs[2][kVcBK][kVcBN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int mh = wave & 1, nh = wave >> 1;              // wave tile: 32 channels x 64 steps
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
   const int b = blockIdx.z / a.nph, ph = blockIdx.z - b * a.nph;
-  const int m0 = blockIdx.y * kVcBM, n0 = blockIdx.x * kVcBN;
-  const float* __restrict__ in = a.in + (size_t)b * a.Cin * a.Tin;
-  const float* __restrict__ w = a.w + (size_t)ph * a.Kpad * a.ldw;
-  const int off = a.off[ph];
-  // global -> register staging: weights 4 floats per thread (one float4 of row tid / 16), input 8 floats of row tid / 16
-  const int wr = tid >> 4, wc = (tid & 15) * 4;
-  const int xr = tid >> 4, xc = tid & 15;
-  float4 wreg;
-  float xreg[8];
-  auto load = [&](int k0) {
-    wreg = *reinterpret_cast<const float4*>(w + (size_t)(k0 + wr) * a.ldw + m0 + wc);
-    const int kk = k0 + xr;
-    const bool live = kk < a.Kdim;
-    const int j = live ? kk / a.Cin : 0, ci = kk - j * a.Cin;
-    const float* row = in + (size_t)ci * a.Tin;
-    const int t0 = n0 + off + j * a.dil;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int t = t0 + xc + 16 * i;
-      xreg[i] = (live && t >= 0 && t < a.Tin) ? row[t] : 0.f;
-    }
-  };
-  auto store = [&](int buf) {
-    *reinterpret_cast<float4*>(&As[buf][wr][wc]) = wreg;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) Bs[buf][xr][xc + 16 * i] = xreg[i];
-  };
-  f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-  const int nk = a.Kpad / kVcBK;
-  load(0);
-  store(0);
-  __syncthreads();
-  const int kl = lane >> 5, cl = lane & 31;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * kVcBK);
-#pragma unroll
-    for (int s = 0; s < kVcBK / 2; ++s) {
-      const float fa = As[cur][2 * s + kl][mh * 32 + cl];
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        const float fb = Bs[cur][2 * s + kl][nh * 64 + n * 32 + cl];
-        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[n], 0, 0, 0);
-      }
-    }
-    if (kt + 1 < nk) store(cur ^ 1);
-    __syncthreads();
-  }
-  // D layout (32x32 f32 MFMA): column = lane & 31, row = 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
+  const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kVcBN;
+  f32x16 acc[2][1];
+  planar_conv_mainloop<2, 1>({a.in + (size_t)b * a.Cin * a.Tin, a.w + (size_t)ph * a.Kpad * a.ldw, a.Cin, a.Tin, a.dil, a.off[ph], a.Kdim,
+                              a.Kpad, a.ldw, m0, n0},
+                             acc);
   float* out = a.out + (size_t)b * a.Cout * a.Tout;        // not __restrict__: res / sum may alias it
   const size_t bo = (size_t)b * a.Cout * a.Tout;
 #pragma unroll
@@ -129,38 +67,15 @@ __global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a) {
     const int t = q * a.ostride + ph;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = m0 + mh * 32 + 8 * (r >> 2) + 4 * kl + (r & 3);
+      const int co = m0 + mh * 32 + mfma32_row(r, kl);
       if (co >= a.Cout) continue;
       const size_t idx = (size_t)co * a.Tout + t;
-      float v = acc[n][r] + a.bias[co];
+      float v = acc[n][0][r] + a.bias[co];
       if (a.res) v = v + a.res[bo + idx];
       if (a.sum) v = a.sum[bo + idx] + v;
       if (a.div > 0.f) v = v / a.div;
       out[idx] = v;
     }
-  }
-}
-
-// P[ph][kk][co] (zero padded) from a Conv1d weight W[Cout][Cin][k] (u == 0) or a ConvTranspose1d weight W[Cin][Cout][k] (u > 0,
-// k = taps * u, padding p): the packing of the comment above vc_conv_kernel.
-__global__ void vc_pack_kernel(const float* __restrict__ w, float* __restrict__ p, int Cin, int Cout, int k, int u, int pad, int taps,
-                               int Kpad, int ldw, int nph) {
-  const size_t n = (size_t)nph * Kpad * ldw;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int co = (int)(i % ldw);
-    const int kk = (int)((i / ldw) % Kpad);
-    const int ph = (int)(i / ((size_t)ldw * Kpad));
-    float v = 0.f;
-    if (co < Cout && kk < taps * Cin) {
-      const int j = kk / Cin, ci = kk - j * Cin;
-      if (u == 0) {
-        v = w[((size_t)co * Cin + ci) * k + j];
-      } else {
-        const int br = (ph + pad) % u;
-        v = w[((size_t)ci * Cout + co) * k + (taps - 1 - j) * u + br];
-      }
-    }
-    p[i] = v;
   }
 }
 
@@ -245,14 +160,6 @@ __global__ __launch_bounds__(256) void vc_post_kernel(const float* __restrict__ 
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-struct VcConv {                 // one Conv1d / ConvTranspose1d in packed form
-  std::string prefix;
-  int cin = 0, cout = 0, k = 0, dil = 1, u = 0, pad = 0;     // u > 0: transposed with stride u
-  int taps = 0, Kpad = 0, ldw = 0, nph = 1;
-  int off[kVcMaxPhases] = {};
-  float* packed = nullptr;
-};
-
 struct VcAct {                  // one Activation1d
   std::string prefix;
   int C = 0;
@@ -264,7 +171,7 @@ struct VcAct {                  // one Activation1d
 
 struct us_vocoder : us::WeightTable {      // keys: the remove_weight_norm form
   us_vocoder_config cfg{};
-  std::map<std::string, us::VcConv> conv;
+  std::map<std::string, us::PlanarConv> conv;
   std::map<std::string, us::VcAct> act;
 };
 
@@ -274,19 +181,13 @@ namespace {
 void vc_add_conv(us_vocoder* h, const std::string& p, int cin, int cout, int k, int dil) {
   h->add(p + ".weight", {cout, cin, k});
   h->add(p + ".bias", {cout});
-  VcConv& c = h->conv[p];
-  c.prefix = p; c.cin = cin; c.cout = cout; c.k = k; c.dil = dil; c.taps = k;
-  c.Kpad = round_up(k * cin, kVcBK); c.ldw = round_up(cout, kVcBM); c.nph = 1;
-  c.off[0] = -dil * (k - 1) / 2;
+  h->conv[p].conv(cin, cin, cout, k, dil);
 }
 
 void vc_add_up(us_vocoder* h, const std::string& p, int cin, int cout, int k, int u) {
   h->add(p + ".weight", {cin, cout, k});      // ConvTranspose1d weight layout [in, out, k]
   h->add(p + ".bias", {cout});
-  VcConv& c = h->conv[p];
-  c.prefix = p; c.cin = cin; c.cout = cout; c.k = k; c.u = u; c.pad = (k - u) / 2;
-  c.taps = k / u; c.Kpad = round_up(c.taps * cin, kVcBK); c.ldw = round_up(cout, kVcBM); c.nph = u;
-  for (int r = 0; r < u; ++r) c.off[r] = (r + c.pad) / u - (c.taps - 1);
+  h->conv[p].transposed(cin, cout, k, u);
 }
 
 void vc_add_act(us_vocoder* h, const std::string& p, int C) {
@@ -340,14 +241,14 @@ constexpr int kVcBuffers = 5;      // level input, AMP sum, residual stream, act
 
 void conv(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, const float* res, const float* sum, float div,
           int B, int Tin) {
-  const VcConv& c = h->conv.at(p);
+  const PlanarConv& c = h->conv.at(p);
   VcConvArgs a{};
   a.in = in; a.w = c.packed; a.bias = h->w.at(p + ".bias").dev; a.res = res; a.sum = sum; a.out = out;
   a.Cin = c.cin; a.Cout = c.cout; a.Tin = Tin; a.Tout = Tin * c.nph;
-  a.taps = c.taps; a.dil = c.u ? 1 : c.dil; a.Kdim = c.taps * c.cin; a.Kpad = c.Kpad; a.ldw = c.ldw;
+  a.dil = c.dil; a.Kdim = c.Kdim(); a.Kpad = c.Kpad; a.ldw = c.ldw;
   a.nph = c.nph; a.ostride = c.nph; a.div = div;
   for (int r = 0; r < c.nph; ++r) a.off[r] = c.off[r];
-  hipLaunchKernelGGL(vc_conv_kernel, dim3((Tin + kVcBN - 1) / kVcBN, (c.cout + kVcBM - 1) / kVcBM, B * c.nph), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(vc_conv_kernel, dim3((Tin + kVcBN - 1) / kVcBN, (c.cout + kPcBM - 1) / kPcBM, B * c.nph), dim3(256), 0, s, a);
 }
 
 void activation(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, int B, int T) {
@@ -378,7 +279,7 @@ int us_vocoder_create(us_vocoder_handle* out, const us_vocoder_config* cfg) {
     return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: upsample_initial_channel must be divisible by 2^len(upsample_rates)");
   for (int i = 0; i < c.n_up; ++i) {
     const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
-    if (u <= 0 || u > kVcMaxPhases || k < u || k % u != 0 || (k - u) % 2 != 0)
+    if (u <= 0 || u > kPcMaxPhases || k < u || k % u != 0 || (k - u) % 2 != 0)
       return WeightTable::fail(nullptr, US_EINVAL, "us_vocoder_create: up-sampler " + std::to_string(i) +
                                                        ": rate in [1, 16] and kernel a multiple of the rate with (kernel - rate) even are built");
   }
@@ -403,8 +304,7 @@ int us_vocoder_create(us_vocoder_handle* out, const us_vocoder_config* cfg) {
 int us_vocoder_destroy(us_vocoder_handle h) {
   if (!h) return US_OK;
   h->free_weights();
-  for (auto& kv : h->conv)
-    if (kv.second.packed) (void)hipFree(kv.second.packed);
+  for (auto& kv : h->conv) kv.second.release();
   for (auto& kv : h->act)
     if (kv.second.ab) (void)hipFree(kv.second.ab);
   delete h;
@@ -427,11 +327,9 @@ int us_vocoder_load_weight(us_vocoder_handle h, const char* key, const float* da
   const std::string prefix = k.substr(0, dot), leaf = k.substr(dot + 1);
   auto ci = h->conv.find(prefix);
   if (ci != h->conv.end() && leaf == "weight") {
-    VcConv& c = ci->second;
-    const size_t np = (size_t)c.nph * c.Kpad * c.ldw;
-    if (!c.packed && (e = hipMalloc(&c.packed, np * sizeof(float))) != hipSuccess) return h->hip("hipMalloc(packed weight)", e);
-    hipLaunchKernelGGL(vc_pack_kernel, dim3((unsigned)std::min<size_t>((np + 255) / 256, 4096)), dim3(256), 0, s, w.dev, c.packed, c.cin,
-                       c.cout, c.k, c.u, c.pad, c.taps, c.Kpad, c.ldw, c.nph);
+    PlanarConv& c = ci->second;
+    if (!c.packed && (e = hipMalloc(&c.packed, c.packed_floats() * sizeof(float))) != hipSuccess) return h->hip("hipMalloc(packed weight)", e);
+    c.pack(w.dev, s);
   }
   const auto adot = prefix.rfind('.');
   if (adot != std::string::npos && prefix.substr(adot + 1) == "act" && (leaf == "alpha" || leaf == "beta")) {
@@ -457,7 +355,7 @@ int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B,
   const auto& c = h->cfg;
   const long long hop = vc_hop(c);
   if (vc_max_ct(c, T) >= (1ll << 31) || (long long)T * hop >= (1ll << 31) || (long long)B * c.upsample_initial_channel > 65535 ||
-      (long long)B * kVcMaxPhases > 65535)
+      (long long)B * kPcMaxPhases > 65535)
     return h->fail(US_EINVAL, "us_vocoder_forward: B * channels or T * hop too large");
   const int rc = h->all_loaded("us_vocoder_forward");
   if (rc != US_OK) return rc;
