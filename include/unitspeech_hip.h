@@ -407,6 +407,16 @@ size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T);
 /* `BigVGAN.forward(mel)` (:169-191): mel [B][num_mels][T] -> wav [B][1][T * prod(upsample_rates)]. */
 int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
                        us_stream stream);
+/* One layer of the vocoder on its own, through the launch the forward uses (layer-level parity tests).  prefix names
+ *  - a convolution: "conv_pre", "ups.<i>.0", "resblocks.<n>.convs1.<l>", "resblocks.<n>.convs2.<l>": in [B][Cin][Tin] -> out
+ *    [B][Cout][Tin * rate] (rate 1 for a Conv1d) = conv(in) + bias, then + res, then sum + that, then / div, each only when given
+ *    (res, sum null and div 0 otherwise; res and sum are [B][Cout][Tout] and either may be `out` itself, as in the forward);
+ *  - an Activation1d: "resblocks.<n>.activations.<a>", "activation_post": in, out [B][C][Tin];
+ *  - "conv_post": in [B][C][Tin] -> out [B][1][Tin], tanh included.
+ * res, sum and div are refused (US_EINVAL) for the last two kinds; an unknown prefix is US_ENOKEY; us_vocoder_forward's size limits
+ * apply to the layer's own tensors.  Needs every weight loaded; takes no workspace. */
+int us_vocoder_debug_layer(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div, float* out,
+                           int B, int Tin, us_stream stream);
 
 /* ---- ECAPA-TDNN speaker encoder (unitspeech/speaker_encoder/ecapa_tdnn.py:164-287, eval mode) --------------------------------
  * The upstream model's hidden states [L][B][T][feat_dim] -> embedding [B][emb_dim]: the softmax(feature_weight)-weighted sum of the L
@@ -444,6 +454,16 @@ int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, i
  * FEAT [B][feat_dim][T] after get_feat, LAYER1 [B][channels][T], BLOCKS [B][3 channels][T] (layer2 | layer3 | layer4 along the
  * channels, the input of `conv`), POOLING [B][3072][1] (mean | std, before `bn`).  Enqueues nothing. */
 int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape);
+/* One dense convolution of the speaker encoder on its own, through the launch the forward uses (layer-level parity tests).  prefix:
+ * "layer1.conv", "layer<l>.Conv1dReluBn<1|2>.conv", "conv", "pooling.linear1" (which reads the first 1536 of its weight's input
+ * channels), "pooling.linear2".  out[b][co][t] = bn(act(conv(in)[b][co][t] + bias[co] + bias2[b][co])): act one of US_SPEAKER_ACT_*;
+ * bias2 [B][Cout] or null; bn_prefix null or "" for none, else a BatchNorm the forward folds ("layer1.bn", "layer<l>.Conv1dReluBn<1|2>.bn",
+ * "bn") with at least Cout channels, of which the first Cout are applied as one scale and one shift.  in / out are [B][C][T] with
+ * in_bs / out_bs floats between batch items (>= C * T), so either may be a channel slice of a wider tensor.  An unknown prefix or
+ * bn_prefix is US_ENOKEY.  Needs every weight loaded; takes no workspace. */
+enum { US_SPEAKER_ACT_NONE = 0, US_SPEAKER_ACT_RELU = 1, US_SPEAKER_ACT_TANH = 2 };
+int us_speaker_debug_conv(us_speaker_handle h, const char* prefix, const char* bn_prefix, int act, const float* in, int64_t in_bs, float* out,
+                          int64_t out_bs, const float* bias2, int B, int T, us_stream stream);
 
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102

@@ -140,3 +140,43 @@ def test_library_key_list_and_refusals():
         assert lib.us_speaker_create(C.byref(h), C.byref(bad)) == -1, field
     assert b"multiple of 8" in lib.us_speaker_last_error(None) or b"bad" in lib.us_speaker_last_error(None)
     assert C.sizeof(_lib.us_speaker_config) == 5 * 4
+
+
+def test_debug_conv_refuses_bad_arguments_before_any_device_work():
+    """us_speaker_debug_conv: null and non-positive arguments, an unknown activation, convolution or BatchNorm, a BatchNorm with fewer
+    channels than the convolution, batch strides shorter than the tensors, sizes past the kernel's limits, and (last) weights that were
+    never loaded."""
+    lib = _lib.load()
+    h = C.c_void_p()
+    c = ECAPA_TDNN(feat_dim=13, channels=40, emb_dim=7, global_context_att=True, feat_type="wavlm_large", feat_num=2)._config_struct()
+    assert lib.us_speaker_create(C.byref(h), C.byref(c)) == 0
+    p = 4096                     # never dereferenced: every call below is refused on the host
+    EINVAL, ENOKEY, EWEIGHTS = -1, -2, -4
+    call = lib.us_speaker_debug_conv
+    T = 9
+    ok = dict(h=h, prefix=b"layer1.conv", bn=b"layer1.bn", act=1, x=p, in_bs=13 * T, out=p, out_bs=40 * T, bias2=None, B=2, T=T)
+
+    def run(**kw):
+        a = dict(ok, **kw)
+        return call(a["h"], a["prefix"], a["bn"], a["act"], a["x"], a["in_bs"], a["out"], a["out_bs"], a["bias2"], a["B"], a["T"], None)
+
+    for kw in (dict(h=None), dict(prefix=None), dict(x=None), dict(out=None), dict(B=0), dict(T=0), dict(T=-3), dict(act=3), dict(act=-1)):
+        assert run(**kw) == EINVAL, kw
+    for bad in (b"", b"layer1", b"layer1.conv.weight", b"layer2.Res2Conv1dReluBn.convs.0", b"layer5.Conv1dReluBn1.conv", b"linear"):
+        assert run(prefix=bad) == ENOKEY, bad
+    for bad in (b"layer1", b"layer2.Res2Conv1dReluBn.bns.0", b"bn.weight"):
+        assert run(bn=bad) == ENOKEY, bad
+        assert bad in lib.us_speaker_last_error(h)
+    assert run(prefix=b"conv", bn=b"layer1.bn", in_bs=120 * T, out_bs=1536 * T) == EINVAL          # 40 BatchNorm channels for 1536
+    assert b"fewer channels" in lib.us_speaker_last_error(h)
+    assert run(in_bs=13 * T - 1) == EINVAL and run(out_bs=40 * T - 1) == EINVAL
+    assert b"stride" in lib.us_speaker_last_error(h)
+    assert run(prefix=b"pooling.linear1", bn=None, in_bs=1536 * T - 1, out_bs=128 * T) == EINVAL   # Cin is 1536 of the weight's 4608
+    assert run(B=65536) == EINVAL
+    big = 1 << 26
+    assert run(T=big, in_bs=13 * big, out_bs=40 * big) == EINVAL                                  # 40 * 2^26 >= 2^31
+    # everything in order: the next check is the weights
+    assert run() == EWEIGHTS and run(bn=None, act=0) == EWEIGHTS and run(bn=b"") == EWEIGHTS
+    assert run(in_bs=100 * T, out_bs=120 * T) == EWEIGHTS                                         # channel slices of wider tensors
+    assert run(prefix=b"pooling.linear1", bn=b"bn", act=2, in_bs=1536 * T, out_bs=128 * T, bias2=p) == EWEIGHTS
+    lib.us_speaker_destroy(h)

@@ -108,6 +108,46 @@ def test_library_refuses_shapes_it_does_not_implement():
     assert lib.us_vocoder_create(C.byref(h), C.byref(bad)) == -1
 
 
+def test_debug_layer_refuses_bad_arguments_before_any_device_work():
+    """us_vocoder_debug_layer: null and non-positive arguments, an unknown prefix, an epilogue operand on a layer that has no epilogue,
+    sizes past the forward's limits, and (last, so everything above is checked first) weights that were never loaded."""
+    import ctypes as C
+
+    from unitspeech_amd import _lib
+    lib = _lib.load()
+    m = BigVGAN(dict(BIGVGAN_22KHZ_80BAND, upsample_initial_channel=16, upsample_rates=[3, 2], upsample_kernel_sizes=[9, 4],
+                     resblock_kernel_sizes=[3], resblock_dilation_sizes=[[1, 3, 5]]))
+    h = C.c_void_p()
+    c = m._config_struct()
+    assert lib.us_vocoder_create(C.byref(h), C.byref(c)) == 0
+    p = 4096                     # never dereferenced: every call below is refused on the host
+    EINVAL, ENOKEY, EWEIGHTS = -1, -2, -4
+    call = lib.us_vocoder_debug_layer
+    assert call(None, b"conv_pre", p, None, None, 0.0, p, 1, 4, None) == EINVAL
+    assert call(h, None, p, None, None, 0.0, p, 1, 4, None) == EINVAL
+    assert call(h, b"conv_pre", None, None, None, 0.0, p, 1, 4, None) == EINVAL
+    assert call(h, b"conv_pre", p, None, None, 0.0, None, 1, 4, None) == EINVAL
+    assert call(h, b"conv_pre", p, None, None, 0.0, p, 0, 4, None) == EINVAL
+    assert call(h, b"conv_pre", p, None, None, 0.0, p, 1, 0, None) == EINVAL
+    assert call(h, b"conv_pre", p, None, None, -1.0, p, 1, 4, None) == EINVAL
+    assert call(h, b"conv_pre", p, None, None, float("nan"), p, 1, 4, None) == EINVAL
+    for bad in (b"", b"conv_pre.weight", b"ups.2.0", b"ups.0", b"resblocks.2.convs1.0", b"resblocks.0.convs1.3", b"resblocks.0.activations.6"):
+        assert call(h, bad, p, None, None, 0.0, p, 1, 4, None) == ENOKEY, bad
+        assert bad in lib.us_vocoder_last_error(h)
+    for layer in (b"resblocks.1.activations.5", b"activation_post", b"conv_post"):
+        assert call(h, layer, p, p, None, 0.0, p, 1, 4, None) == EINVAL, layer
+        assert call(h, layer, p, None, p, 0.0, p, 1, 4, None) == EINVAL, layer
+        assert call(h, layer, p, None, None, 2.0, p, 1, 4, None) == EINVAL, layer
+        assert b"epilogue" in lib.us_vocoder_last_error(h)
+    assert call(h, b"conv_pre", p, None, None, 0.0, p, 4096, 4, None) == EINVAL           # B * channels past a grid dimension
+    assert call(h, b"ups.0.0", p, None, None, 0.0, p, 1, 1 << 27, None) == EINVAL         # Cout * Tin * rate = 8 * 3 * 2^27 >= 2^31
+    assert call(h, b"ups.0.0", p, None, None, 0.0, p, 1, 1 << 26, None) == EWEIGHTS       # within the limits: next check
+    for layer in (b"conv_pre", b"ups.1.0", b"resblocks.1.convs2.2", b"resblocks.0.activations.0", b"activation_post", b"conv_post"):
+        assert call(h, layer, p, None, None, 0.0, p, 1, 4, None) == EWEIGHTS, layer
+    assert call(h, b"resblocks.0.convs2.2", p, p, p, 1.0, p, 1, 4, None) == EWEIGHTS      # a convolution takes the epilogue operands
+    lib.us_vocoder_destroy(h)
+
+
 def test_flops_per_frame_of_the_two_22khz_generators():
     from unitspeech_amd.vocoder import BIGVGAN_BASE_22KHZ_80BAND
     assert 1.80e9 < bigvgan_flops(BIGVGAN_22KHZ_80BAND, 1024) / 1024 < 1.86e9           # torch.utils.flop_counter: 1.83 G

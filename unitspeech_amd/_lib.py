@@ -39,6 +39,7 @@ class us_vocoder_config(C.Structure):
 
 
 US_VOCODER_SNAKE, US_VOCODER_SNAKEBETA = 0, 1
+US_SPEAKER_ACT_NONE, US_SPEAKER_ACT_RELU, US_SPEAKER_ACT_TANH = 0, 1, 2
 
 
 class us_speaker_config(C.Structure):
@@ -111,9 +112,13 @@ SIGNATURES = {
     "us_duration_predictor_mse_loss": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
     "us_vocoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_vocoder_config)]),
     "us_vocoder_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_vocoder_debug_layer": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p]),
     "us_speaker_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_speaker_config)]),
     "us_speaker_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_speaker_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "us_speaker_debug_conv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),

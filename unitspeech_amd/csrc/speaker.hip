@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void sp_instnorm_kernel(const float* in, float
 // own batch strides, so a tensor may be a channel slice of a wider one (the [out2, out3, out4] concatenation is written in place by the
 // three blocks).
 constexpr int kSpBN = 64;      // time steps per workgroup
-enum { kActNone = 0, kActRelu = 1, kActTanh = 2 };
+enum { kActNone = US_SPEAKER_ACT_NONE, kActRelu = US_SPEAKER_ACT_RELU, kActTanh = US_SPEAKER_ACT_TANH };
 
 struct SpConvArgs {
   const float* in;
@@ -344,7 +344,11 @@ __global__ __launch_bounds__(256) void sp_pool_kernel(const float* __restrict__ 
   if (lane == 0) {
     const int b = row / C, c = row - b * C;
     const float mean = sx / se;
-    const float sd = sqrtf(fmaxf(sxx / se - mean * mean, 1e-9f));
+    // mean^2 rounded on its own, as the reference's `mean ** 2`: contracted into an fma the difference keeps the rounding error of
+    // sxx / se, and at T = 1 (sxx / se = round(x^2), mean = x) that error, up to 6e-8 x^2, takes the place of the exact 0 the clamp is for
+    // (the clamp keeps a NaN, as torch.clamp does and fmaxf does not: with the global context and T = 1 the reference's std is NaN)
+    const float var = sxx / se - mul_rn(mean, mean);
+    const float sd = sqrtf(var < 1e-9f ? 1e-9f : var);
     const size_t o = (size_t)b * 2 * C;
     raw[o + c] = mean;
     raw[o + C + c] = sd;
@@ -681,6 +685,32 @@ int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, i
   if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(1), dim3(256), 0, s, emb_out, B * c.emb_dim);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_speaker_forward", e);
+}
+
+int us_speaker_debug_conv(us_speaker_handle h, const char* prefix, const char* bn_prefix, int act, const float* in, int64_t in_bs, float* out,
+                          int64_t out_bs, const float* bias2, int B, int T, us_stream stream) {
+  if (!h || !prefix || !in || !out || B <= 0 || T <= 0 || (act != kActNone && act != kActRelu && act != kActTanh))
+    return WeightTable::fail(h, US_EINVAL, "us_speaker_debug_conv: bad argument");
+  const std::string p(prefix), bn(bn_prefix ? bn_prefix : "");
+  const auto ci = h->conv.find(p);
+  if (ci == h->conv.end()) return h->fail(US_ENOKEY, "us_speaker_debug_conv: unknown convolution '" + p + "'");
+  const PlanarConv& c = ci->second;
+  if (!bn.empty()) {
+    const auto bi = h->bn.find(bn);
+    if (bi == h->bn.end()) return h->fail(US_ENOKEY, "us_speaker_debug_conv: unknown folded BatchNorm '" + bn + "'");
+    if (bi->second.n < c.cout) return h->fail(US_EINVAL, "us_speaker_debug_conv: BatchNorm '" + bn + "' has fewer channels than '" + p + "'");
+  }
+  if ((long long)std::max(c.cin, c.cout) * T >= (1ll << 31) || B > 65535)
+    return h->fail(US_EINVAL, "us_speaker_debug_conv: B or channels * T too large");
+  if (in_bs < (long long)c.cin * T || out_bs < (long long)c.cout * T)
+    return h->fail(US_EINVAL, "us_speaker_debug_conv: a batch stride is shorter than the tensor (in_bs >= Cin * T, out_bs >= Cout * T)");
+  const int rc = h->all_loaded("us_speaker_debug_conv");
+  if (rc != US_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (h->dirty) sp_prepare(h, s);
+  sp_conv(h, s, p, bn, act, in, in_bs, out, out_bs, bias2, B, T);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip("us_speaker_debug_conv", e);
 }
 
 int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape) {

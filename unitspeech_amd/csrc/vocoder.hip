@@ -257,6 +257,12 @@ void activation(us_vocoder* h, hipStream_t s, const std::string& p, const float*
                      h->w.at(p + ".upsample.filter").dev, h->w.at(p + ".downsample.lowpass.filter").dev, a.C, T);
 }
 
+void post(us_vocoder* h, hipStream_t s, const float* in, float* out, int B, int T) {
+  const int ch = channels(h->cfg, h->cfg.n_up);
+  hipLaunchKernelGGL(vc_post_kernel, dim3((T + 255) / 256, B), dim3(256), (size_t)ch * kPostK * sizeof(float), s, in,
+                     h->w.at("conv_post.weight").dev, h->w.at("conv_post.bias").dev, out, ch, T);
+}
+
 }  // namespace
 }  // namespace us
 
@@ -392,11 +398,40 @@ int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B,
     }
   }
   activation(h, s, "activation_post", S, A, B, t);
-  const int ch = channels(c, c.n_up);
-  hipLaunchKernelGGL(vc_post_kernel, dim3((t + 255) / 256, B), dim3(256), (size_t)ch * kPostK * sizeof(float), s, A,
-                     h->w["conv_post.weight"].dev, h->w["conv_post.bias"].dev, wav, ch, t);
+  post(h, s, A, wav, B, t);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_vocoder_forward", e);
+}
+
+int us_vocoder_debug_layer(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div, float* out,
+                           int B, int Tin, us_stream stream) {
+  if (!h || !prefix || !in || !out || B <= 0 || Tin <= 0 || !(div >= 0.f))
+    return WeightTable::fail(h, US_EINVAL, "us_vocoder_debug_layer: bad argument");
+  const std::string p(prefix);
+  const auto ci = h->conv.find(p);
+  const bool is_act = h->act.count(p) != 0, is_post = p == "conv_post";
+  if (ci == h->conv.end() && !is_act && !is_post) return h->fail(US_ENOKEY, "us_vocoder_debug_layer: unknown layer '" + p + "'");
+  if (ci == h->conv.end() && (res || sum || div != 0.f))
+    return h->fail(US_EINVAL, "us_vocoder_debug_layer: res / sum / div belong to a convolution's epilogue; '" + p + "' is not one");
+  // the largest C * T this layer reads or writes, under us_vocoder_forward's limits
+  long long ct;
+  if (ci != h->conv.end())
+    ct = std::max((long long)ci->second.cin * Tin, (long long)ci->second.cout * Tin * ci->second.nph);
+  else
+    ct = (long long)(is_act ? h->act.at(p).C : channels(h->cfg, h->cfg.n_up)) * Tin;
+  if (ct >= (1ll << 31) || (long long)B * h->cfg.upsample_initial_channel > 65535 || (long long)B * kPcMaxPhases > 65535)
+    return h->fail(US_EINVAL, "us_vocoder_debug_layer: B * channels or C * T too large");
+  const int rc = h->all_loaded("us_vocoder_debug_layer");
+  if (rc != US_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (ci != h->conv.end())
+    conv(h, s, p, in, out, res, sum, div, B, Tin);
+  else if (is_act)
+    activation(h, s, p, in, out, B, Tin);
+  else
+    post(h, s, in, out, B, Tin);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip("us_vocoder_debug_layer", e);
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@ OUT_CHANNELS = 1536            # ecapa_tdnn.py:222
 BOTTLENECK = 128               # se_bottleneck_dim and attention_channels (:225-232)
 SCALE = 8
 STAGES = {"feat": 0, "layer1": 1, "blocks": 2, "pooling": 3}
+ACTS = {None: _lib.US_SPEAKER_ACT_NONE, "none": _lib.US_SPEAKER_ACT_NONE, "relu": _lib.US_SPEAKER_ACT_RELU, "tanh": _lib.US_SPEAKER_ACT_TANH}
 
 
 class _Conv1dReluBn(nn.Module):
@@ -165,6 +166,38 @@ class ECAPA_TDNN(HandleModule):
         if self._input(hidden_states)[2] != 1:
             raise ValueError("ECAPA_TDNN.embed: one utterance at a time (the norm is taken over the whole output)")
         return self._run(hidden_states, True)
+
+    @torch.no_grad()
+    def debug_conv(self, prefix, x, bn_prefix=None, act=None, bias2=None, out=None):
+        """One dense convolution alone through the launch `forward_features` uses (us_speaker_debug_conv): `layer1.conv`,
+        `layer<l>.Conv1dReluBn<1|2>.conv`, `conv`, `pooling.linear1` (the first 1536 input channels of its weight) or `pooling.linear2`;
+        -> bn(act(conv(x) + bias + bias2)).  x [B, Cin, T] and `out` [B, Cout, T] are fp32 with time contiguous and channels T apart, and
+        may be channel slices of wider tensors (their batch strides are passed on); bias2 [B, Cout]."""
+        device = x.device
+        lib, stream = self._sync(device)
+        mod = self.get_submodule(prefix)
+        cin = OUT_CHANNELS if prefix == "pooling.linear1" else mod.in_channels
+        cout = mod.out_channels
+        if x.dim() != 3 or x.shape[1] != cin or x.shape[2] < 1:
+            raise ValueError(f"ECAPA_TDNN.debug_conv({prefix}): expected [B, {cin}, T], got {tuple(x.shape)}")
+        b, _, t = x.shape
+        if out is None:
+            out = torch.empty(b, cout, t, device=device)
+        for name, v, c in (("x", x, cin), ("out", out, cout)):
+            if tuple(v.shape) != (b, c, t) or v.dtype != torch.float32 or v.device != device or (t > 1 and v.stride(2) != 1) or \
+                    (c > 1 and v.stride(1) != t) or (b > 1 and v.stride(0) < c * t):
+                raise ValueError(f"ECAPA_TDNN.debug_conv({prefix}): {name} must be fp32 [{b}, {c}, {t}] on {device}, time contiguous, channels "
+                                 f"{t} apart")
+        if bias2 is not None:
+            bias2 = bias2.detach().to(device=device, dtype=torch.float32).contiguous()
+            if tuple(bias2.shape) != (b, cout):
+                raise ValueError(f"ECAPA_TDNN.debug_conv({prefix}): bias2 must be [{b}, {cout}]")
+        bs = lambda v, c: int(v.stride(0)) if b > 1 else c * t
+        with torch.cuda.device(device):
+            rc = lib.us_speaker_debug_conv(self._h, prefix.encode(), bn_prefix.encode() if bn_prefix else None, ACTS[act], x.data_ptr(),
+                                           bs(x, cin), out.data_ptr(), bs(out, cout), None if bias2 is None else bias2.data_ptr(), b, t, stream)
+        self._check(lib, rc, f"us_speaker_debug_conv({prefix})")
+        return out
 
     def forward(self, x):
         raise NotImplementedError("ECAPA_TDNN.forward(wav) needs the upstream feature extractor (WavLM / HuBERT through s3prl, or fbank / mfcc), "

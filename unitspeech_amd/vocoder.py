@@ -215,6 +215,44 @@ class BigVGAN(HandleModule):
         return wav
 
 
+    @torch.no_grad()
+    def debug_layer(self, prefix, x, res=None, sum=None, div=0.0, out=None):
+        """One layer alone through the launch `forward` uses (us_vocoder_debug_layer): a convolution (`conv_pre`, `ups.<i>.0`,
+        `resblocks.<n>.convs1|convs2.<l>`; with its epilogue's `res`, `sum` and `div`), an Activation1d (`resblocks.<n>.activations.<a>`,
+        `activation_post`) or `conv_post` (tanh included).  x [B, C, Tin] -> [B, Cout, Tout]; `out`, `res` and `sum` are contiguous fp32
+        tensors of that shape on x's device and may share storage, as they do in the forward."""
+        device = x.device
+        lib, stream = self._sync(device)
+        try:
+            mod = self.get_submodule(prefix)
+        except AttributeError:
+            mod = None
+        if isinstance(mod, nn.ConvTranspose1d):
+            cin, cout, rate = mod.in_channels, mod.out_channels, mod.stride[0]
+        elif isinstance(mod, nn.Conv1d):
+            cin, cout, rate = mod.in_channels, mod.out_channels, 1
+        elif isinstance(mod, _Activation1d):
+            cin = cout = mod.act.alpha.shape[0]
+            rate = 1
+        else:
+            cin, cout, rate = x.shape[1], 1, 1           # not a layer: the library names the refusal
+        if x.dim() != 3 or x.shape[1] != cin or x.shape[2] < 1:
+            raise ValueError(f"BigVGAN.debug_layer({prefix}): expected [B, {cin}, T], got {tuple(x.shape)}")
+        b, _, t = x.shape
+        shape = (b, cout, t * rate)
+        x = x.detach().to(dtype=torch.float32).contiguous()
+        if out is None:
+            out = torch.empty(shape, device=device)
+        for name, v in (("out", out), ("res", res), ("sum", sum)):
+            if v is not None and (tuple(v.shape) != shape or v.dtype != torch.float32 or v.device != device or not v.is_contiguous()):
+                raise ValueError(f"BigVGAN.debug_layer({prefix}): {name} must be a contiguous fp32 {shape} on {device}")
+        ptr = lambda v: None if v is None else v.data_ptr()
+        with torch.cuda.device(device):
+            rc = lib.us_vocoder_debug_layer(self._h, prefix.encode(), x.data_ptr(), ptr(res), ptr(sum), float(div), out.data_ptr(), b, t, stream)
+        self._check(lib, rc, f"us_vocoder_debug_layer({prefix})")
+        return out
+
+
 def get_vocoder(config_path, checkpoint, device):
     """unitspeech/util.py:174-181 on the HIP vocoder: config JSON, checkpoint["generator"], to(device), eval, remove_weight_norm."""
     with open(config_path) as f:
