@@ -6,10 +6,14 @@
   default       the reference's pre-steps (speaker embedder, unit extractor, unit encoder, mel extraction; finetune.py:47-128)
                 come from a checkout of the reference given with --reference_root and stay on the stock PyTorch path.
   --synthetic   seeded synthetic decoder weights and a synthetic (mel, units, durations, speaker embedding) tuple: runs the
-                fine-tuning loop itself (BASELINE.json configs[3]) without any downloaded model.
+                fine-tuning loop itself (BASELINE.json configs[3]) without any downloaded model.  --hip_mel takes the mel from a seeded
+                waveform through the HIP mel front end instead of random numbers.
   --features F  the OUTPUTS of the reference's pre-steps (finetune.py:86-128) from a `.pt` (torch.save of a dict) or `.npz` file, so the
                 speaker embedder / unit extractor can run wherever their checkpoints live and the adaptation here:
-                  mel        [1, 80, L]   normalised to [-1, 1] as finetune.py:104 leaves it (or raw with "mel_is_normalized": False)
+                  mel        [1, 80, L]   normalised to [-1, 1] as finetune.py:104 leaves it (or raw with "mel_is_normalized": False); or
+                             wav [T] or [1, T], the reference utterance at the decoder's sampling rate (`wav_sampling_rate`, when given,
+                             must say so: resampling is not part of the library): the mel of :86-104 is then computed on the device
+                             (unitspeech_amd.mel) and normalised with mel_min / mel_max
                   spk_emb    [1, 256] or [1, 1, 256]   (divided by its norm here, :110); or  spk_hidden_states [L, 1, T, C], the
                              speaker encoder's upstream hidden states (ecapa_tdnn.py:262-264) + --speaker_encoder_checkpoint (:106-110)
                   duration   [1, Lu]      frames per unit (process_unit, :114)
@@ -35,6 +39,10 @@ from unitspeech_amd.checkpoint import build_decoder, infer_config, load_decoder_
 from unitspeech_amd.util import fix_len_compatibility, generate_path, sequence_mask
 
 
+SAMPLING_RATE = 22050
+MEL_ARGS = (1024, 80, SAMPLING_RATE, 256, 1024, 0, 8000)          # finetune.py:86-96: n_fft, num_mels, sampling_rate, hop, win, fmin, fmax
+
+
 def load_features(args, cfg, base, device):
     """--features: (mel, cond_x, duration, spk_emb, mel_min, mel_max) on `device` from the file the reference's pre-steps were saved to."""
     path = args.features
@@ -57,9 +65,10 @@ def load_features(args, cfg, base, device):
             raise SystemExit(f"--features {path}: `dense` has rows with non-finite values")
         d["unit"], d["duration"] = unit[:, :n].cpu(), duration[:, :n].cpu()
     hip_spk = bool(args.speaker_encoder_checkpoint) and "spk_emb" not in d and "spk_hidden_states" in d
+    hip_mel = "mel" not in d and "wav" in d
     for k in ("mel", "spk_emb", "duration"):
-        if k not in d and not (k == "spk_emb" and hip_spk):
-            raise SystemExit(f"--features {path}: missing `{k}`")
+        if k not in d and not (k == "spk_emb" and hip_spk) and not (k == "mel" and hip_mel):
+            raise SystemExit(f"--features {path}: missing `{k}`" + (" (or `wav`)" if k == "mel" else ""))
 
     def scalar(name):
         if name in d:
@@ -68,12 +77,23 @@ def load_features(args, cfg, base, device):
             return getattr(base, name).float().reshape(())
         raise SystemExit(f"--features {path}: no `{name}` in the file and no decoder checkpoint to take it from (finetune.py:98-99)")
     mel_min, mel_max = scalar("mel_min"), scalar("mel_max")
-    mel = d["mel"].float()
+    if hip_mel:
+        # finetune.py:86-104: mel_spectrogram(wav, 1024, 80, 22050, 256, 1024, 0, 8000, center=False), then the normalisation
+        from unitspeech_amd.mel import MelSpectrogram
+        if "wav_sampling_rate" in d and int(d["wav_sampling_rate"]) != SAMPLING_RATE:
+            raise SystemExit(f"--features {path}: `wav` is at {int(d['wav_sampling_rate'])} Hz, the decoder's mel is defined at {SAMPLING_RATE} Hz; "
+                             "resample it first (the library has no resampler)")
+        wav = d["wav"].float()
+        if wav.dim() not in (1, 2) or (wav.dim() == 2 and wav.shape[0] != 1):
+            raise SystemExit(f"--features: wav must be [T] or [1, T], got {tuple(wav.shape)}")
+        mel = MelSpectrogram(*MEL_ARGS).to(device)(wav.reshape(1, -1).to(device), mel_min=mel_min, mel_max=mel_max).cpu()
+    else:
+        mel = d["mel"].float()
     if mel.dim() == 2:
         mel = mel.unsqueeze(0)
     if mel.dim() != 3 or mel.shape[0] != 1 or mel.shape[1] != cfg.n_feats:
         raise SystemExit(f"--features: mel must be [1, {cfg.n_feats}, L], got {tuple(mel.shape)}")
-    if "mel_is_normalized" in d and not bool(d["mel_is_normalized"]):
+    if not hip_mel and "mel_is_normalized" in d and not bool(d["mel_is_normalized"]):
         mel = (mel - mel_min) / (mel_max - mel_min) * 2 - 1                      # finetune.py:104
     if hip_spk:
         from unitspeech_amd.speaker_encoder import load_speaker_encoder_checkpoint
@@ -133,6 +153,8 @@ def main():
                     "speaker encoder's checkpoint ({'model': state_dict}, util.py:183-188); the embedding comes from the HIP ECAPA-TDNN")
     ap.add_argument("--hip_speaker_encoder", action="store_true", help="--synthetic: spk_emb from the HIP ECAPA-TDNN (seeded weights) on "
                     "synthetic upstream hidden states instead of a random vector")
+    ap.add_argument("--hip_mel", action="store_true", help="--synthetic: the mel comes from the HIP mel front end on a seeded waveform (normalised "
+                    "with mel_min / mel_max) instead of random numbers")
     ap.add_argument("--learned_frontend", action="store_true", help="--synthetic: cond_x from the HIP unit encoder (seeded weights) on synthetic units")
     ap.add_argument("--reference_root", type=str, default=None)
     ap.add_argument("--out_dir", type=str, default="checkpoints/inference")
@@ -171,6 +193,12 @@ def main():
         L = 600
         Lu = L // 3
         mel = torch.from_numpy(g.standard_normal((1, cfg.n_feats, L), dtype=np.float32)).clamp(-1, 1).to(device)
+        if args.hip_mel:
+            # finetune.py:86-104: the mel of the reference utterance and its normalisation; here L frames of a seeded waveform
+            from unitspeech_amd.mel import MelSpectrogram, synthetic_waveform
+            wav = torch.from_numpy(synthetic_waveform(L * MEL_ARGS[3], args.ID & 0xffff, SAMPLING_RATE)).to(device)
+            mel = MelSpectrogram(*MEL_ARGS).to(device)(wav, mel_min=-11.5, mel_max=2.0)
+            print(f"hip mel: {wav.numel()} samples -> {mel.shape[-1]} frames in [{float(mel.min()):.3f}, {float(mel.max()):.3f}]")
         cond_x = (torch.from_numpy(g.standard_normal((1, cfg.n_feats, Lu), dtype=np.float32)) * 0.5).to(device)
         if args.learned_frontend:
             # finetune.py:66-78,122-123: cond_x is the (frozen, eval-mode) unit encoder's output for the utterance's unit sequence;
@@ -208,6 +236,8 @@ def main():
             spk = torch.from_numpy(g.standard_normal((1, 1, cfg.spk_emb_dim), dtype=np.float32)).to(device)
             spk_emb = spk / spk.norm()
         mel_min, mel_max = torch.tensor(-11.5), torch.tensor(2.0)
+    elif args.hip_mel:
+        raise SystemExit("--hip_mel needs --synthetic (with --features, put `wav` in the file)")
     else:
         if not args.reference_root:
             raise SystemExit("give --features (the pre-step tensors), --reference_root (reference checkout with its checkpoints) or use --synthetic")

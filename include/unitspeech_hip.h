@@ -465,6 +465,45 @@ enum { US_SPEAKER_ACT_NONE = 0, US_SPEAKER_ACT_RELU = 1, US_SPEAKER_ACT_TANH = 2
 int us_speaker_debug_conv(us_speaker_handle h, const char* prefix, const char* bn_prefix, int act, const float* in, int64_t in_bs, float* out,
                           int64_t out_bs, const float* bias2, int B, int T, us_stream stream);
 
+/* ---- mel-spectrogram front end (unitspeech/vocoder/meldataset.py:51-74 with center=False; finetune.py:104), csrc/mel.hip --------
+ * Waveform [B][Tmax] -> log-mel [B][num_mels][Tmax / hop]: reflect padding by (n_fft - hop) / 2, the windowed DFT as a convolution
+ * with n_fft / hop taps over the de-interleaved waveform, sqrt(re^2 + im^2 + 1e-9), the mel projection, log(max(x, 1e-5)) and,
+ * on request, the normalisation (m - mel_min) / (mel_max - mel_min) * 2 - 1 with every operation rounded on its own.  fp32 storage and
+ * accumulation, exact fp32 products on the matrix cores.  Same conventions as the vocoder handle: the two weights are loaded from
+ * DEVICE memory and taken as given, "mel_basis" [num_mels][n_fft / 2 + 1] (the filter bank) and "window" [win] (centred in n_fft
+ * samples when shorter, as torch.stft does); loading mel_basis synchronises the stream once (the host learns how many bins have a
+ * non-zero column: only those are computed).  The caller owns the scratch (us_mel_workspace_bytes); us_mel_forward and us_mel_minmax
+ * allocate nothing and only enqueue on `stream` (graph-capturable: lengths are read on the host during the call), and a call made
+ * while another device than the handle's is current is refused (US_EINVAL).  An item's frames depend on its own samples only and every
+ * sum has a fixed order: an item alone or in a batch, and repeated calls, give the same bits.
+ * us_mel_create returns US_EINVAL when hop does not divide n_fft, n_fft - hop is odd, win > n_fft or n_fft > 4096. */
+typedef struct us_mel* us_mel_handle;
+typedef struct us_mel_config {
+  int32_t n_fft;                         /* 1024 */
+  int32_t hop;                           /* 256 */
+  int32_t win;                           /* 1024 */
+  int32_t num_mels;                      /* 80 */
+} us_mel_config;
+int us_mel_create(us_mel_handle* out, const us_mel_config* cfg);
+int us_mel_destroy(us_mel_handle h);
+int us_mel_load_weight(us_mel_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_mel_num_weights(us_mel_handle h);
+const char* us_mel_weight_key(us_mel_handle h, int i);
+const char* us_mel_last_error(us_mel_handle h);
+/* frames of a waveform of T samples: T / hop */
+int us_mel_frames(us_mel_handle h, int T);
+size_t us_mel_workspace_bytes(us_mel_handle h, int B, int Tmax);
+/* wav [B][Tmax] (device); lengths: HOST int64 [B], the samples of each item, or NULL for Tmax each.  A length must be above
+ * (n_fft - hop) / 2 (the reflection needs it) and at most Tmax, else US_EINVAL; samples at or past an item's length are never read.
+ * mel_min / mel_max: device, n_norm values each with n_norm = 0 (no normalisation; both may be NULL), 1 (one range for all bands) or
+ * num_mels (one per band).  out [B][num_mels][Tmax / hop]: item b has lengths[b] / hop frames, the ones past them are pad_value. */
+int us_mel_forward(us_mel_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, const float* mel_min, const float* mel_max,
+                   int n_norm, float pad_value, float* out, void* workspace, size_t workspace_bytes, us_stream stream);
+/* out[0][m] = min, out[1][m] = max of mel[b][m][t] over b < B, t < lengths_frames[b] (HOST int64 [B] in [0, F], or NULL for F each):
+ * the inner loop of preprocessing/process_mel_normalization.py.  mel [B][num_mels][F] and out [2][num_mels] on the device.  Exact in
+ * any order; a NaN is skipped (fminf / fmaxf); +inf / -inf when there is no valid frame. */
+int us_mel_minmax(us_mel_handle h, const float* mel, const int64_t* lengths_frames, int B, int F, float* out, us_stream stream);
+
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102
  * `process_unit`) as handle-free device calls.  Every call only enqueues on `stream`, allocates nothing and takes device scratch of

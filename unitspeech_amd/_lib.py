@@ -46,6 +46,10 @@ class us_speaker_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("feat_dim", "channels", "emb_dim", "n_layers", "global_context_att")]
 
 
+class us_mel_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "num_mels")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -119,6 +123,11 @@ SIGNATURES = {
     "us_speaker_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "us_speaker_debug_conv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_int, C.c_int, C.c_void_p]),
+    "us_mel_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_mel_config)]),
+    "us_mel_frames": (C.c_int, [C.c_void_p, C.c_int]),
+    "us_mel_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_mel_minmax": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
@@ -138,8 +147,8 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_last_error": (C.c_char_p, [C.c_void_p]),
 }
-# what the three weight-table handles (csrc/handle.h) share
-for _p in ("frontend", "vocoder", "speaker"):
+# what the four weight-table handles (csrc/handle.h) share
+for _p in ("frontend", "vocoder", "speaker", "mel"):
     SIGNATURES.update({
         f"us_{_p}_destroy": (C.c_int, [C.c_void_p]),
         f"us_{_p}_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
