@@ -297,6 +297,39 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
                         float* const* grads, int n_grads, void* workspace, size_t workspace_bytes, us_stream stream);
 int us_encoder_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B, int L, float p_dropout, float* out, us_stream stream);
 int us_encoder_tape_release(us_frontend_handle h, const void* workspace);
+/* TEST HOOKS: one launch group of the Encoder's training forward / backward alone, through the host function the forward or the
+ * backward calls, for kernel-level parity tests (tests/test_encoder_train_kernels_gpu.py).  Activations are channel-last
+ * [B][L][C] (row = b * L + l), as the kernels see them; mask is [B][L].  All work goes on `stream`; scratch is the caller's
+ * workspace of us_encoder_debug_workspace_bytes(h, B, L) bytes (one size serves every hook); nothing is allocated.  A bad
+ * argument is US_EINVAL and an unknown key or layer US_ENOKEY, both before any launch; every weight must be loaded.
+ * us_encoder_debug_conv: the Conv1d `key` ("prenet.conv_layers.0", "encoder.ffn_layers.1.conv_2", "proj_m", ...), Cout x Cin x K.
+ *   US_ENCODER_CONV_FWD:   out [B][L][Cout] = (add + drop(relu(conv(in [* mask]) + bias))) [* mask]: in [B][L][Cin]; the flags pick
+ *     the input mask, the ReLU and the output mask; add [B][L][Cout] or NULL; drop_site >= 0 applies that site's keep mask for
+ *     (seed, p_dropout) (us_encoder_dropout_mask with the same p; the site's channel count must be Cout), < 0 none.
+ *   US_ENCODER_CONV_WGRAD: dw [Cout][Cin][K] (torch layout) and db [Cout] from in [B][L][Cin] (read times mask with MASK_IN) and
+ *     the output gradient dout [B][L][Cout].
+ *   US_ENCODER_CONV_DGRAD: out [B][L][Cin] = (add + dgrad(dout)) [gate > 0 ? * gate_scale : 0] [* mask]: gate [B][L][Cin] or NULL.
+ *   Operands a mode does not take must be NULL / 0.
+ * us_encoder_debug_ln_bwd: backward of the LayerNorm `key` ("prenet.norm_layers.0", "encoder.norm_layers_1.2", ...) over
+ *   n_channels: x (its input), dy, and optionally gate with gate_scale (dy is first taken as gate > 0 ? dy * gate_scale : 0: the
+ *   prenet's ReLU and dropout) -> dx [B][L][C], dgamma [C], dbeta [C].
+ * us_encoder_debug_attention: the attention of transformer layer `layer` in its training form on the caller's q, k, v [B][L][C]:
+ *   out [B][L][C] and P [B][H][L][L] (the probabilities before dropout); the keep mask is that of site 3 + 4 * layer for
+ *   (seed, p_dropout), p_dropout in [0, 1).  With dO [B][L][C] also the backward: DS [B][H][L][L], dq, dk, dv [B][L][C] and the
+ *   gradients of emb_rel_k / emb_rel_v [2W+1][D] (NULL when window_size is 0); without dO all of these are NULL.
+ * us_encoder_debug_embed_grad: grad [n_vocab][C] of emb.weight from ids [B][L] and the gradient dx0 [B][L][C] of emb(ids) * sqrt(C). */
+enum { US_ENCODER_CONV_FWD = 0, US_ENCODER_CONV_WGRAD = 1, US_ENCODER_CONV_DGRAD = 2 };
+enum { US_ENCODER_CONV_MASK_IN = 1, US_ENCODER_CONV_RELU = 2, US_ENCODER_CONV_MASK_OUT = 4 };
+size_t us_encoder_debug_workspace_bytes(us_frontend_handle h, int B, int L);
+int us_encoder_debug_conv(us_frontend_handle h, const char* key, int mode, const float* in, const float* dout, const float* mask,
+                          const float* add, const float* gate, float gate_scale, unsigned flags, int drop_site, float p_dropout, uint64_t seed,
+                          float* out, float* dw, float* db, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_encoder_debug_ln_bwd(us_frontend_handle h, const char* key, const float* x, const float* dy, const float* gate, float gate_scale,
+                            float* dx, float* dgamma, float* dbeta, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_encoder_debug_attention(us_frontend_handle h, int layer, const float* q, const float* k, const float* v, const float* mask, float p_dropout,
+                               uint64_t seed, float* out, float* P, const float* dO, float* DS, float* dq, float* dk, float* dv,
+                               float* grad_rel_k, float* grad_rel_v, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_encoder_debug_embed_grad(us_frontend_handle h, const int64_t* ids, const float* dx0, float* grad, int B, int L, us_stream stream);
 /* `DurationPredictor.forward(x, x_mask, w=None, g=g, reverse=True)` (:47-63): x [B,in_channels,L], x_mask [B,1,L],
  * g [B,1,spk_emb_dim] (NULL iff spk_emb_dim == 0) -> logw [B,1,L]. */
 int us_duration_predictor_forward(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,

@@ -112,6 +112,96 @@ def test_c_abi_new_entry_points_refuse_bad_arguments_without_device_work():
         lib.us_frontend_destroy(h)
 
 
+ODD = EncoderConfig(n_vocab=30, n_feats=17, n_channels=40, filter_channels=72, n_heads=2, n_layers=2, kernel_size=5, window_size=4)
+
+
+def test_c_abi_debug_entry_points_refuse_bad_arguments_without_device_work():
+    """us_encoder_debug_*: a null handle or operand, an unknown mode / flag / dropout site, an operand the mode does not take
+    (US_EINVAL) and an unknown key or layer (US_ENOKEY) are all refused before the weights are even looked at (US_EWEIGHTS: none
+    is loaded here), so no launch can have happened."""
+    lib = _lib.load()
+    for s in ("us_encoder_debug_workspace_bytes", "us_encoder_debug_conv", "us_encoder_debug_ln_bwd", "us_encoder_debug_attention",
+              "us_encoder_debug_embed_grad"):
+        assert s in _lib.SIGNATURES and hasattr(lib, s)
+    conv, ln, att, emb = lib.us_encoder_debug_conv, lib.us_encoder_debug_ln_bwd, lib.us_encoder_debug_attention, lib.us_encoder_debug_embed_grad
+    p = 4096                                   # a non-null address that must never be read
+    assert lib.us_encoder_debug_workspace_bytes(None, 1, 1) == 0
+    assert conv(None, b"proj_m", 0, p, None, None, None, None, 1.0, 0, -1, 0.0, 0, p, None, None, 1, 1, p, 1 << 30, None) == -1
+    assert ln(None, b"prenet.norm_layers.0", p, p, None, 1.0, p, p, p, 1, 1, p, 1 << 30, None) == -1
+    assert att(None, 0, p, p, p, p, 0.0, 0, p, p, None, None, None, None, None, None, None, 1, 1, p, 1 << 30, None) == -1
+    assert emb(None, p, p, p, 1, 1, None) == -1
+    h = C.c_void_p()
+    c = _lib.us_encoder_config(ODD.n_vocab, ODD.n_feats, ODD.n_channels, ODD.filter_channels, ODD.n_heads, ODD.n_layers, ODD.kernel_size,
+                               ODD.window_size)
+    assert lib.us_encoder_create(C.byref(h), C.byref(c)) == 0
+    d = lib.us_frontend_destroy
+    try:
+        small = lib.us_encoder_debug_workspace_bytes(h, 1, 8)
+        assert 0 < small < lib.us_encoder_debug_workspace_bytes(h, 2, 8) < lib.us_encoder_debug_workspace_bytes(h, 64, 400)
+        assert lib.us_encoder_debug_workspace_bytes(h, 0, 8) == 0
+        fwd = lambda key, mode=0, x=p, dout=None, mask=None, add=None, gate=None, flags=0, site=-1, pd=0.0, out=p, dw=None, db=None, B=1, L=8: \
+            conv(h, key, mode, x, dout, mask, add, gate, 1.0, flags, site, pd, 0, out, dw, db, B, L, p, 1 << 30, None)
+        assert fwd(None) == -1 and fwd(b"proj_m", mode=3) == -1 and fwd(b"proj_m", flags=8) == -1
+        assert fwd(b"proj_m", x=None) == -1 and fwd(b"proj_m", out=None) == -1 and fwd(b"proj_m", dout=p) == -1
+        assert fwd(b"proj_m", flags=1) == -1                                   # a mask flag without a mask
+        assert fwd(b"proj_m", site=3 + 4 * ODD.n_layers, pd=0.1) == -1 and fwd(b"proj_m", site=0, pd=1.0) == -1
+        assert fwd(b"proj_m", mode=1, dout=p, out=None, dw=p) == -1            # wgrad without db
+        assert fwd(b"proj_m", mode=1, dout=p, out=None, dw=p, db=p, add=p) == -1
+        assert fwd(b"proj_m", mode=2, x=None, dout=p, site=0, pd=0.1) == -1     # only the forward drops
+        assert fwd(b"proj_m", mode=2, x=p, dout=p) == -1
+        assert fwd(b"proj_m", B=0) == -1 and fwd(b"proj_m", L=70000) == -1
+        assert fwd(b"proj_n") == -2 and fwd(b"emb") == -2 and fwd(b"prenet.norm_layers.0") == -2
+        assert fwd(b"proj_m") == -4 and fwd(b"proj_m", mode=1, dout=p, out=None, dw=p, db=p) == -4          # only the weights are missing
+        assert fwd(b"encoder.ffn_layers.1.conv_2", mode=2, x=None, dout=p, gate=p, add=p, mask=p, flags=4) == -4
+        lnc = lambda key, x=p, dy=p, dx=p, dg=p, db=p: ln(h, key, x, dy, None, 1.0, dx, dg, db, 1, 8, p, 1 << 30, None)
+        assert lnc(None) == -1 and lnc(b"prenet.norm_layers.0", x=None) == -1 and lnc(b"prenet.norm_layers.0", db=None) == -1
+        assert lnc(b"prenet.norm_layers.3") == -2 and lnc(b"proj_m") == -2
+        assert lnc(b"encoder.norm_layers_2.1") == -4
+        ac = lambda layer=0, q=p, P=p, pd=0.0, dO=None, DS=None, rest=None, gk=None: \
+            att(h, layer, q, p, p, p, pd, 0, p, P, dO, DS, rest, rest, rest, gk, gk, 1, 8, p, 1 << 30, None)
+        assert ac(q=None) == -1 and ac(P=None) == -1 and ac(pd=1.0) == -1 and ac(pd=-0.5) == -1
+        assert ac(DS=p) == -1 and ac(dO=p) == -1 and ac(dO=p, DS=p, rest=p) == -1       # a half-given backward
+        assert ac(layer=ODD.n_layers) == -2 and ac(layer=-1) == -2
+        assert ac() == -4 and ac(dO=p, DS=p, rest=p, gk=p) == -4
+        assert emb(h, None, p, p, 1, 8, None) == -1 and emb(h, p, p, None, 1, 8, None) == -1 and emb(h, p, p, p, 1, 0, None) == -1
+        assert emb(h, p, p, p, 1, 8, None) == -4
+    finally:
+        d(h)
+
+
+def test_the_odd_configuration_constructs_and_ends_reductions_inside_a_slice():
+    """The configuration tests/test_encoder_train_kernels_gpu.py adds to TINY and FULL: K * Cin is no multiple of the GEMM's
+    16-wide reduction slice for the prenet and the FFN convolutions, N and Cin are no multiples of the 64-wide tile, D = 20."""
+    sd = synthetic_encoder_state_dict(ODD, 0)
+    assert list(sd) == list(encoder_state_shapes(ODD))
+    Encoder(ODD.n_vocab, ODD.n_feats, ODD.n_channels, ODD.filter_channels, ODD.n_heads, ODD.n_layers, ODD.kernel_size, 0.1,
+            window_size=ODD.window_size, trainable=True).load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    for key in ("prenet.conv_layers.0", "encoder.ffn_layers.0.conv_1", "encoder.ffn_layers.0.conv_2", "proj_m"):
+        cout, cin, k = sd[key + ".weight"].shape
+        assert (k * cin) % 16 != 0 and cin % 64 != 0 and cout % 64 != 0, key
+    assert ODD.n_channels // ODD.n_heads == 20
+    ids, lens = torch.randint(0, ODD.n_vocab, (2, 7)), torch.LongTensor([7, 3])
+    mu_x, _, _ = ET.encoder_forward({k: torch.from_numpy(v).double() for k, v in sd.items()}, ODD.n_heads, ids, lens)
+    assert mu_x.shape == (2, 17, 7) and bool(torch.isfinite(mu_x).all())
+
+
+def wgrad_split_geometry(rows):
+    """(splits, rows_per_split) of gemm_conv_wgrad (csrc/encoder_train.hip: wgrad_splits, and the round-up to the 16-row slice)."""
+    s = min(max(rows // 512, 1), 32)
+    return s, (-(-rows // s) + 15) // 16 * 16
+
+
+def test_no_row_count_leaves_the_weight_gradient_an_empty_last_split():
+    """splits * rows_per_split never passes rows by a whole split for rows <= 20,000 (below the cap of 32 it would take
+    512 < 16 (splits - 1), above it rows <= 15,872 < 32 * 512), so an EMPTY last split does not occur and the GPU tests cannot
+    run one; the shapes they do run (a short last split at 1030 rows, the cap at 16,500) are checked here too."""
+    for rows in range(1, 20001):
+        s, per = wgrad_split_geometry(rows)
+        assert (s - 1) * per < rows, rows
+    assert wgrad_split_geometry(1030) == (2, 528) and wgrad_split_geometry(12800) == (25, 512) and wgrad_split_geometry(16500) == (32, 528)
+    assert wgrad_split_geometry(1024) == (2, 512) and wgrad_split_geometry(65) == (1, 80)
+
+
 def test_train_mode_needs_trainable_and_says_so():
     enc = Encoder(20, 8, 16, 32, 2, 2, 3, 0.1, window_size=4).train()
     assert enc.trainable is False

@@ -41,19 +41,29 @@ def band(emb: torch.Tensor, L: int) -> torch.Tensor:
 
 
 def encoder_forward(sd: Dict[str, torch.Tensor], n_heads: int, ids: torch.Tensor, lengths: torch.Tensor,
-                    masks: Optional[Dict[int, torch.Tensor]] = None):
-    """-> (mu_x [B, n_feats, L], x [B, C, L], x_mask [B, 1, L]); differentiable in every tensor of sd."""
+                    masks: Optional[Dict[int, torch.Tensor]] = None, tape: Optional[Dict[str, torch.Tensor]] = None):
+    """-> (mu_x [B, n_feats, L], x [B, C, L], x_mask [B, 1, L]); differentiable in every tensor of sd.
+
+    With `tape` (a dict), the intermediates a kernel-level test needs are stored in it under the names below, each with its
+    gradient retained: after a backward, `tape[name].grad` is the operand the corresponding backward launch reads."""
     masks = masks or {}
+
+    def keep(name, t):
+        if tape is not None:
+            if t.requires_grad:
+                t.retain_grad()
+            tape[name] = t
+        return t
     drop = lambda t, site: t * masks[site].to(t.dtype) if site in masks else t
     emb = sd["emb.weight"]
     C = emb.shape[1]
     L = ids.shape[1]
-    x = (emb[ids] * math.sqrt(C)).transpose(1, 2)
+    x = keep("x0", (emb[ids] * math.sqrt(C)).transpose(1, 2))              # [B, C, L]
     x_mask = (torch.arange(L, device=ids.device).view(1, L) < lengths.view(-1, 1)).unsqueeze(1).to(x.dtype)
     # prenet (ConvReluNorm)
     x_org, h = x, x
     for i in range(PRENET_LAYERS):
-        h = conv(h * x_mask, sd, f"prenet.conv_layers.{i}")
+        h = keep(f"prenet.{i}.conv", conv(keep(f"prenet.{i}.in", h * x_mask), sd, f"prenet.conv_layers.{i}"))
         h = layer_norm(h, sd[f"prenet.norm_layers.{i}.gamma"], sd[f"prenet.norm_layers.{i}.beta"])
         h = drop(torch.relu(h), i)
     x = (x_org + conv(h, sd, "prenet.proj")) * x_mask
@@ -64,10 +74,10 @@ def encoder_forward(sd: Dict[str, torch.Tensor], n_heads: int, ids: torch.Tensor
     B = ids.shape[0]
     for i in range(n_layers):
         ap, site = f"encoder.attn_layers.{i}", 3 + 4 * i
-        x = x * x_mask
-        q = conv(x, sd, ap + ".conv_q").view(B, n_heads, D, L).transpose(2, 3)
-        k = conv(x, sd, ap + ".conv_k").view(B, n_heads, D, L).transpose(2, 3)
-        v = conv(x, sd, ap + ".conv_v").view(B, n_heads, D, L).transpose(2, 3)
+        x = keep(f"layer.{i}.x", x * x_mask)
+        q = keep(f"layer.{i}.q", conv(x, sd, ap + ".conv_q")).view(B, n_heads, D, L).transpose(2, 3)      # kept as [B, C, L]
+        k = keep(f"layer.{i}.k", conv(x, sd, ap + ".conv_k")).view(B, n_heads, D, L).transpose(2, 3)
+        v = keep(f"layer.{i}.v", conv(x, sd, ap + ".conv_v")).view(B, n_heads, D, L).transpose(2, 3)
         scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(D)
         rel = ap + ".emb_rel_k" in sd
         if rel:
@@ -77,7 +87,7 @@ def encoder_forward(sd: Dict[str, torch.Tensor], n_heads: int, ids: torch.Tensor
         out = torch.matmul(p, v)
         if rel:
             out = out + torch.einsum("bhij,ijd->bhid", p, band(sd[ap + ".emb_rel_v"], L))
-        y = conv(out.transpose(2, 3).reshape(B, C, L), sd, ap + ".conv_o")
+        y = conv(keep(f"layer.{i}.attn", out.transpose(2, 3).reshape(B, C, L)), sd, ap + ".conv_o")
         x = layer_norm(x + drop(y, site + 1), sd[f"encoder.norm_layers_1.{i}.gamma"], sd[f"encoder.norm_layers_1.{i}.beta"])
         fp = f"encoder.ffn_layers.{i}"
         y = drop(torch.relu(conv(x * x_mask, sd, fp + ".conv_1")), site + 2)

@@ -14,6 +14,8 @@ US_OK = 0
 US_CREATE_EXACT_FP32 = 1
 US_RANGE_ACT, US_RANGE_WEIGHT = 1, 2
 US_BACKWARD_GRADS_ZEROED, US_BACKWARD_KEEP_TAPE = 1, 2
+US_ENCODER_CONV_FWD, US_ENCODER_CONV_WGRAD, US_ENCODER_CONV_DGRAD = 0, 1, 2
+US_ENCODER_CONV_MASK_IN, US_ENCODER_CONV_RELU, US_ENCODER_CONV_MASK_OUT = 1, 2, 4
 ERRORS = {-1: "EINVAL", -2: "ENOKEY", -3: "ESHAPE", -4: "EWEIGHTS", -5: "EWORKSPACE", -6: "EHIP"}
 
 
@@ -99,6 +101,14 @@ SIGNATURES = {
                                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_encoder_dropout_mask": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_encoder_tape_release": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "us_encoder_debug_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "us_encoder_debug_conv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_uint, C.c_int, C.c_float, C.c_uint64]
+                              + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_encoder_debug_ln_bwd": (C.c_int, [C.c_void_p, C.c_char_p] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 3
+                                + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_encoder_debug_attention": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_float, C.c_uint64] + [C.c_void_p] * 9
+                                   + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_encoder_debug_embed_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     "us_finetune_segment_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "us_prior_loss": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
     "us_mas_log_prior": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),

@@ -500,7 +500,7 @@ Layout et_layout(const us_frontend* h, int B, int L) {
   o.splits = wgrad_splits((long long)rows);
   o.wd = take(conv_numel(c));
   o.wpart = take((size_t)o.splits * conv_numel(c));
-  o.cpart = take((size_t)kColChunks * std::max(C, F));
+  o.cpart = take((size_t)kColChunks * std::max(std::max(C, F), (size_t)c.n_feats));
   const size_t nw = 2 * (size_t)c.window_size + 1, D = C / H;
   o.rpart = take(4 * (size_t)B * nw * D);      // doubles
   size_t params = 0;
@@ -561,6 +561,41 @@ AttnArgs attn_args(const Ctx& x, int i) {
   a.L = x.L; a.C = c.n_channels; a.H = c.n_heads; a.D = c.n_channels / c.n_heads; a.W = c.window_size;
   a.sqrt_d = sqrtf((float)a.D);
   return a;
+}
+
+// DS, dq, dk, dv of one layer's attention for upstream a.dO (a.P and a.drop as the forward left them), and the gradients of the
+// relative embeddings the heads share
+void attn_bwd(hipStream_t s, const AttnArgs& a, int B, float* grad_rel_v, float* grad_rel_k) {
+  hipLaunchKernelGGL(et_attn_bwd_q_kernel, dim3(a.L, a.H, B), dim3(128), ((size_t)a.L + a.D + 128) * sizeof(float), s, a);
+  hipLaunchKernelGGL(et_attn_bwd_kv_kernel, dim3(a.L, a.H, B), dim3(128), (size_t)2 * a.L * sizeof(float), s, a);
+  if (a.W > 0) {
+    const int nw = 2 * a.W + 1, ne = nw * a.D;
+    hipLaunchKernelGGL(et_attn_bwd_rel_kernel, dim3(nw, B), dim3(128), 0, s, a);
+    hipLaunchKernelGGL(et_rel_finish_kernel, dim3((ne + 255) / 256), dim3(256), 0, s, a.rel_part, grad_rel_v, grad_rel_k, B, ne, 1.f / a.sqrt_d);
+  }
+}
+
+// emb.weight's gradient from the gradient dx0 of emb(ids) * sqrt(C)
+void embed_grad(hipStream_t s, const long long* ids, const float* dx0, float* grad, long long rows, int n_vocab, int C) {
+  hipLaunchKernelGGL(et_embed_grad_kernel, dim3(n_vocab), dim3(256), 0, s, ids, dx0, grad, rows, C, sqrtf((float)C));
+}
+
+// scratch of the us_encoder_debug_* entry points: the backward's own slots (conv_bwd, ln_bwd and attn_bwd read them from a Layout)
+Layout et_debug_layout(const us_frontend* h, int B, int L) {
+  const auto& c = h->ec;
+  const size_t rows = (size_t)B * L, C = c.n_channels, F = c.filter_channels;
+  Layout o{};
+  size_t at = 0;
+  auto take = [&](size_t n) { const size_t r = at; at += (n + 63) / 64 * 64; return r; };
+  o.splits = wgrad_splits((long long)rows);
+  o.wd = take(conv_numel(c));
+  o.wpart = take((size_t)o.splits * conv_numel(c));
+  o.cpart = take((size_t)kColChunks * std::max(std::max(C, F), (size_t)c.n_feats));
+  o.dyx = take(rows * C);
+  o.dyo = take(rows * C);
+  o.rpart = take(4 * (size_t)B * (2 * (size_t)c.window_size + 1) * (C / c.n_heads));      // doubles
+  o.total = at;
+  return o;
 }
 
 int et_check(us_frontend* h, const char* what, int B, int L) {
@@ -731,14 +766,7 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
     AttnArgs a = attn_args(x, i);
     a.drop = make_drop(seed, layer_site(i, kSiteAttnP), p);
     a.dO = dh; a.DS = x.f(l.ds); a.dq = x.f(l.dq); a.dk = x.f(l.dk); a.dv = x.f(l.dv); a.rel_part = reinterpret_cast<double*>(x.f(l.rpart));
-    hipLaunchKernelGGL(et_attn_bwd_q_kernel, dim3(L, c.n_heads, B), dim3(128), ((size_t)L + a.D + 128) * sizeof(float), x.s, a);
-    hipLaunchKernelGGL(et_attn_bwd_kv_kernel, dim3(L, c.n_heads, B), dim3(128), (size_t)2 * L * sizeof(float), x.s, a);
-    if (c.window_size > 0) {
-      const int nw = 2 * c.window_size + 1, ne = nw * a.D;
-      hipLaunchKernelGGL(et_attn_bwd_rel_kernel, dim3(nw, B), dim3(128), 0, x.s, a);
-      hipLaunchKernelGGL(et_rel_finish_kernel, dim3((ne + 255) / 256), dim3(256), 0, x.s, reinterpret_cast<const double*>(x.f(l.rpart)), G(ap + ".emb_rel_v"),
-                         G(ap + ".emb_rel_k"), B, ne, 1.f / a.sqrt_d);
-    }
+    attn_bwd(x.s, a, B, c.window_size > 0 ? G(ap + ".emb_rel_v") : nullptr, c.window_size > 0 ? G(ap + ".emb_rel_k") : nullptr);
     // the block's input x (masked on entry): residual + q / k / v data gradients, then the entry mask
     const float* xin = x.f(l.x[i]);
     conv_bwd(x, ap + ".conv_q", xin, false, x.f(l.dq), g, g, nullptr, 1.f, false, G(ap + ".conv_q.weight"), G(ap + ".conv_q.bias"));
@@ -755,8 +783,7 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
     if (i > 0) conv_bwd(x, cp, x.f(l.pa[i - 1]), true, d1, t, nullptr, nullptr, 1.f, true, G(cp + ".weight"), G(cp + ".bias"));
     else conv_bwd(x, cp, x.f(l.x0), true, d1, g, g, nullptr, 1.f, true, G(cp + ".weight"), G(cp + ".bias"));
   }
-  hipLaunchKernelGGL(et_embed_grad_kernel, dim3(c.n_vocab), dim3(256), 0, x.s, reinterpret_cast<const long long*>(x.f(l.ids)), g,
-                     G("emb.weight"), x.rows, C, sqrtf((float)C));
+  embed_grad(x.s, reinterpret_cast<const long long*>(x.f(l.ids)), g, G("emb.weight"), x.rows, c.n_vocab, C);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_encoder_backward: ") + hipGetErrorString(e));
 }
@@ -781,6 +808,125 @@ int us_encoder_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B
                      make_drop(seed, site, p));
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_encoder_dropout_mask: ") + hipGetErrorString(e));
+}
+
+// ---- one launch group alone, for kernel-level parity tests (tests/test_encoder_train_kernels_gpu.py) ---------------------------
+namespace {
+
+// what every debug entry point checks before anything else; `lay` receives the scratch layout
+int et_debug_check(us_frontend* h, const char* what, int B, int L, void* workspace, size_t workspace_bytes, Layout* lay) {
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  if (B <= 0 || L <= 0 || B > 65535 || L > 65535 || (long long)B * L > 0x7fffffffLL / 1024)
+    return fe_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
+  const int D = h->ec.n_channels / h->ec.n_heads;
+  if (((size_t)2 * L + D + 128) * sizeof(float) > 64 * 1024)
+    return fe_fail(h, US_EINVAL, std::string(what) + ": more than ~8000 symbols per utterance");
+  const int rc = fe_check(h, what);
+  if (rc != US_OK) return rc;
+  if (lay) {
+    *lay = et_debug_layout(h, B, L);
+    if (!workspace || workspace_bytes < lay->total * sizeof(float) + 256)
+      return fe_fail(h, US_EWORKSPACE, std::string(what) + ": workspace too small (us_encoder_debug_workspace_bytes)");
+  }
+  return US_OK;
+}
+
+}  // namespace
+
+size_t us_encoder_debug_workspace_bytes(us_frontend_handle h, int B, int L) {
+  if (!h || h->kind != 0 || B <= 0 || L <= 0) return 0;
+  return et_debug_layout(h, B, L).total * sizeof(float) + 256;
+}
+
+int us_encoder_debug_conv(us_frontend_handle h, const char* key, int mode, const float* in, const float* dout, const float* mask,
+                          const float* add, const float* gate, float gate_scale, unsigned flags, int drop_site, float p_dropout, uint64_t seed,
+                          float* out, float* dw, float* db, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
+  const char* what = "us_encoder_debug_conv";
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  if (!key || mode < US_ENCODER_CONV_FWD || mode > US_ENCODER_CONV_DGRAD || (flags & ~7u))
+    return fe_fail(h, US_EINVAL, std::string(what) + ": null key, unknown mode or unknown flag");
+  const bool mask_in = flags & US_ENCODER_CONV_MASK_IN, relu = flags & US_ENCODER_CONV_RELU, mask_out = flags & US_ENCODER_CONV_MASK_OUT;
+  const bool fwd = mode == US_ENCODER_CONV_FWD, wgrad = mode == US_ENCODER_CONV_WGRAD, dgrad = mode == US_ENCODER_CONV_DGRAD;
+  if ((fwd && (!in || !out || dout || gate || dw || db)) || (wgrad && (!in || !dout || !dw || !db || out || add || gate || relu || mask_out)) ||
+      (dgrad && (!dout || !out || in || dw || db || relu || mask_in)) || ((mask_in || mask_out) && !mask))
+    return fe_fail(h, US_EINVAL, std::string(what) + ": an operand this mode needs is null, or one it does not take is given");
+  const auto& c = h->ec;
+  if (fwd && drop_site >= 0 && (drop_site >= kPrenetLayers + kSitesPerLayer * c.n_layers || !(p_dropout >= 0.f && p_dropout < 1.f)))
+    return fe_fail(h, US_EINVAL, std::string(what) + ": no such dropout site, or p_dropout outside [0, 1)");
+  if (!fwd && drop_site >= 0) return fe_fail(h, US_EINVAL, std::string(what) + ": only the forward has a dropout site");
+  const std::string k(key);
+  auto wi = h->w.find(k + ".weight");
+  if (wi == h->w.end() || wi->second.shape.size() != 3 || !h->w.count(k + ".bias"))
+    return fe_fail(h, US_ENOKEY, std::string(what) + ": unknown convolution '" + k + "'");
+  Layout l;
+  const int rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l);
+  if (rc != US_OK) return rc;
+  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, const_cast<float*>(mask)};
+  if (fwd) gemm_conv_fwd(h, x.s, k, in, out, mask, add, x.rows, L, mask_in, relu, mask_out, drop_site >= 0 ? make_drop(seed, drop_site, p_dropout) : no_drop());
+  else if (wgrad) conv_bwd(x, k, in, mask_in, dout, nullptr, nullptr, nullptr, 1.f, false, dw, db);
+  else gemm_conv_dgrad(h, x.s, k, dout, out, mask, add, gate, gate_scale, mask_out, x.rows, L, x.f(l.wd));
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+int us_encoder_debug_ln_bwd(us_frontend_handle h, const char* key, const float* x_in, const float* dy, const float* gate, float gate_scale,
+                            float* dx, float* dgamma, float* dbeta, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
+  const char* what = "us_encoder_debug_ln_bwd";
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  if (!key || !x_in || !dy || !dx || !dgamma || !dbeta) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
+  const std::string k(key);
+  if (!h->w.count(k + ".gamma") || !h->w.count(k + ".beta")) return fe_fail(h, US_ENOKEY, std::string(what) + ": unknown LayerNorm '" + k + "'");
+  Layout l;
+  const int rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l);
+  if (rc != US_OK) return rc;
+  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
+  ln_bwd(x, k, x_in, dy, gate, gate_scale, dx, dgamma, dbeta);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+int us_encoder_debug_attention(us_frontend_handle h, int layer, const float* q, const float* k, const float* v, const float* mask, float p_dropout,
+                               uint64_t seed, float* out, float* P, const float* dO, float* DS, float* dq, float* dk, float* dv,
+                               float* grad_rel_k, float* grad_rel_v, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
+  const char* what = "us_encoder_debug_attention";
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  const auto& c = h->ec;
+  if (!q || !k || !v || !mask || !out || !P || !(p_dropout >= 0.f && p_dropout < 1.f))
+    return fe_fail(h, US_EINVAL, std::string(what) + ": null argument, or p_dropout outside [0, 1)");
+  const bool rel = c.window_size > 0;
+  if (dO ? (!DS || !dq || !dk || !dv || (rel && (!grad_rel_k || !grad_rel_v))) : (DS || dq || dk || dv || grad_rel_k || grad_rel_v))
+    return fe_fail(h, US_EINVAL, std::string(what) + ": the backward takes dO and every gradient buffer, the forward alone none of them");
+  if (layer < 0 || layer >= c.n_layers) return fe_fail(h, US_ENOKEY, std::string(what) + ": no attention layer " + std::to_string(layer));
+  Layout l;
+  const int rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l);
+  if (rc != US_OK) return rc;
+  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, const_cast<float*>(mask)};
+  const std::string ap = "encoder.attn_layers." + std::to_string(layer);
+  AttnArgs a{};
+  a.q = q; a.k = k; a.v = v; a.mask = mask; a.P = P; a.out = out;
+  a.rel_k = rel ? wdev(h, ap + ".emb_rel_k") : nullptr;
+  a.rel_v = rel ? wdev(h, ap + ".emb_rel_v") : nullptr;
+  a.L = L; a.C = c.n_channels; a.H = c.n_heads; a.D = c.n_channels / c.n_heads; a.W = c.window_size;
+  a.sqrt_d = sqrtf((float)a.D);
+  a.drop = make_drop(seed, layer_site(layer, kSiteAttnP), p_dropout);
+  rel_attention_fwd(x.s, a, B, true);
+  if (dO) {
+    a.dO = dO; a.DS = DS; a.dq = dq; a.dk = dk; a.dv = dv; a.rel_part = reinterpret_cast<double*>(x.f(l.rpart));
+    attn_bwd(x.s, a, B, grad_rel_v, grad_rel_k);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+int us_encoder_debug_embed_grad(us_frontend_handle h, const int64_t* ids, const float* dx0, float* grad, int B, int L, us_stream stream) {
+  const char* what = "us_encoder_debug_embed_grad";
+  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  if (!ids || !dx0 || !grad) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
+  const int rc = et_debug_check(h, what, B, L, nullptr, 0, nullptr);
+  if (rc != US_OK) return rc;
+  embed_grad(static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(ids), dx0, grad, (long long)B * L, h->ec.n_vocab, h->ec.n_channels);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 }  // extern "C"

@@ -144,6 +144,8 @@ void gemm_conv_wgrad(us_frontend* h, hipStream_t s, const std::string& key, cons
 // din = (add + dgrad(dout)) [gate > 0 ? * gate_scale : 0] [* mask]; `wd` holds the K * Cout * Cin floats of the flipped weight
 void gemm_conv_dgrad(us_frontend* h, hipStream_t s, const std::string& key, const float* dout, float* din, const float* mask, const float* add,
                      const float* gate, float gate_scale, bool mask_out, long long rows, int L, float* wd);
+// frontend.hip: the attention of one layer for B items (training: a.P is stored and a.drop applied)
+void rel_attention_fwd(hipStream_t s, const AttnArgs& a, int B, bool train);
 // frontend.hip: out[b][l] = x[b][:][l] | g[b][:] (channel-first in, channel-last out: the DurationPredictor's cat, :49-50)
 void fe_gather_concat(hipStream_t s, const float* x_cf, const float* g, float* out, int B, int L, int C, int S);
 

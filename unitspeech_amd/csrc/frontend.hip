@@ -388,6 +388,11 @@ void to_channel_first(hipStream_t s, const float* in, const float* mask, float* 
 
 }  // namespace
 
+void rel_attention_fwd(hipStream_t s, const AttnArgs& a, int B, bool train) {
+  hipLaunchKernelGGL(train ? fe_rel_attention_kernel<true> : fe_rel_attention_kernel<false>, dim3(a.L, a.H, B), dim3(128),
+                     ((size_t)a.L + a.D + 128) * sizeof(float), s, a);
+}
+
 void fe_gather_concat(hipStream_t s, const float* x_cf, const float* g, float* out, int B, int L, int C, int S) {
   hipLaunchKernelGGL(fe_gather_concat_kernel, dim3(L, B), dim3(256), 0, s, x_cf, g, out, L, C, S);
 }
@@ -438,8 +443,7 @@ int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const E
     a.rel_v = c.window_size > 0 ? h->w[ap + ".emb_rel_v"].dev : nullptr;
     a.L = L; a.C = C; a.D = D; a.H = c.n_heads; a.W = c.window_size; a.sqrt_d = sqrtf((float)D);
     a.drop = make_drop(m.seed, layer_site(i, kSiteAttnP), m.p);
-    hipLaunchKernelGGL(m.train ? fe_rel_attention_kernel<true> : fe_rel_attention_kernel<false>, dim3(L, c.n_heads, B), dim3(128),
-                       ((size_t)L + D + 128) * sizeof(float), s, a);
+    rel_attention_fwd(s, a, B, m.train);
     if ((rc = conv(ap + ".conv_o", l.at, b.y, nullptr, false, false, false)) != US_OK) return rc;
     if ((rc = norm("encoder.norm_layers_1." + n, l.x, b.y, make_drop(m.seed, layer_site(i, kSiteAttnOut), m.p), l.n1, false, no_drop(),
                    nullptr, l.x1)) != US_OK) return rc;

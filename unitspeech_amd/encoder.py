@@ -255,6 +255,104 @@ class Encoder(_FrontEndModule):
         return mu_x, h, mask
 
 
+    # ---- one launch group alone (the us_encoder_debug_* test hooks), for tests/test_encoder_train_kernels_gpu.py ---------------
+    # Tensors are contiguous fp32 on the module's device, channel-last [B, L, C] as the kernels see them; mask is [B, L].
+
+    def _debug(self, ref, b, l):
+        lib, stream = self._sync(ref.device, training_ok=True)
+        n = int(lib.us_encoder_debug_workspace_bytes(self._h, b, l))
+        ws = self._dbg_ws = getattr(self, "_dbg_ws", None)
+        if ws is None or ws.numel() < n or ws.device != ref.device:
+            self._dbg_ws = None
+            ws = self._dbg_ws = torch.empty(n, dtype=torch.uint8, device=ref.device)
+        return lib, stream, ws
+
+    @staticmethod
+    def _ptr(t, shape, name):
+        if t is None:
+            return None
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or t.device.type != "cuda":
+            raise ValueError(f"Encoder debug hook: {name} must be a contiguous fp32 {tuple(shape)} on the device, got {tuple(t.shape)} {t.dtype}")
+        return t.data_ptr()
+
+    @torch.no_grad()
+    def debug_conv(self, key, mode, x=None, dout=None, mask=None, add=None, gate=None, gate_scale=1.0, mask_in=False, relu=False,
+                   mask_out=False, drop_site=-1, p_dropout=0.0, seed=0):
+        """The convolution `key` alone (us_encoder_debug_conv).  mode "fwd": x [B, L, Cin] -> out [B, L, Cout]; "wgrad": x, dout
+        [B, L, Cout] -> (dw [Cout, Cin, K], db [Cout]); "dgrad": dout -> din [B, L, Cin] (with add, gate / gate_scale, mask_out)."""
+        cout, cin, k = encoder_state_shapes(self.cfg)[key + ".weight"] if key + ".weight" in encoder_state_shapes(self.cfg) else (0, 0, 0)
+        ref = x if x is not None else dout
+        b, l = ref.shape[:2]
+        lib, stream, ws = self._debug(ref, b, l)
+        dev = ref.device
+        m = {"fwd": _lib.US_ENCODER_CONV_FWD, "wgrad": _lib.US_ENCODER_CONV_WGRAD, "dgrad": _lib.US_ENCODER_CONV_DGRAD}[mode]
+        flags = (_lib.US_ENCODER_CONV_MASK_IN if mask_in else 0) | (_lib.US_ENCODER_CONV_RELU if relu else 0) | \
+            (_lib.US_ENCODER_CONV_MASK_OUT if mask_out else 0)
+        out = dw = db = None
+        if mode == "wgrad":
+            dw, db = torch.empty(cout, cin, k, device=dev), torch.empty(cout, device=dev)
+        else:
+            out = torch.empty(b, l, cout if mode == "fwd" else cin, device=dev)
+        P = self._ptr
+        with torch.cuda.device(dev):
+            rc = lib.us_encoder_debug_conv(self._h, key.encode(), m, P(x, (b, l, cin), "x"), P(dout, (b, l, cout), "dout"), P(mask, (b, l), "mask"),
+                                           P(add, (b, l, cout if mode == "fwd" else cin), "add"), P(gate, (b, l, cin), "gate"), float(gate_scale),
+                                           flags, int(drop_site), float(p_dropout), int(seed), P(out, out.shape, "out") if out is not None else None,
+                                           P(dw, (cout, cin, k), "dw"), P(db, (cout,), "db"), b, l, ws.data_ptr(), ws.numel(), stream)
+        self._check(lib, rc, f"us_encoder_debug_conv({key}, {mode})")
+        return (dw, db) if mode == "wgrad" else out
+
+    @torch.no_grad()
+    def debug_ln_bwd(self, key, x, dy, gate=None, gate_scale=1.0):
+        """Backward of the LayerNorm `key` alone (us_encoder_debug_ln_bwd): x, dy [B, L, C] -> (dx, dgamma, dbeta)."""
+        b, l, c = x.shape
+        lib, stream, ws = self._debug(x, b, l)
+        dx, dg, db = torch.empty_like(x), torch.empty(c, device=x.device), torch.empty(c, device=x.device)
+        P, sh = self._ptr, (b, l, self.cfg.n_channels)
+        with torch.cuda.device(x.device):
+            rc = lib.us_encoder_debug_ln_bwd(self._h, key.encode(), P(x, sh, "x"), P(dy, sh, "dy"), P(gate, sh, "gate"), float(gate_scale),
+                                             dx.data_ptr(), dg.data_ptr(), db.data_ptr(), b, l, ws.data_ptr(), ws.numel(), stream)
+        self._check(lib, rc, f"us_encoder_debug_ln_bwd({key})")
+        return dx, dg, db
+
+    @torch.no_grad()
+    def debug_attention(self, layer, q, k, v, mask, p_dropout=0.0, seed=0, dO=None):
+        """The attention of transformer layer `layer` alone, training form (us_encoder_debug_attention): q, k, v [B, L, C] ->
+        {"out", "P"}, and with dO also {"DS", "dq", "dk", "dv", "emb_rel_k", "emb_rel_v"} (the last two only with a window)."""
+        b, l, c = q.shape
+        lib, stream, ws = self._debug(q, b, l)
+        dev, h, d, w = q.device, self.cfg.n_heads, self.cfg.n_channels // self.cfg.n_heads, self.cfg.window_size or 0
+        r = {"out": torch.empty(b, l, c, device=dev), "P": torch.empty(b, h, l, l, device=dev)}
+        if dO is not None:
+            r.update(DS=torch.empty(b, h, l, l, device=dev), dq=torch.empty(b, l, c, device=dev), dk=torch.empty(b, l, c, device=dev),
+                     dv=torch.empty(b, l, c, device=dev))
+            if w:
+                r.update(emb_rel_k=torch.empty(1, 2 * w + 1, d, device=dev), emb_rel_v=torch.empty(1, 2 * w + 1, d, device=dev))
+        P, sh = self._ptr, (b, l, self.cfg.n_channels)
+        opt = lambda n: r[n].data_ptr() if n in r else None
+        with torch.cuda.device(dev):
+            rc = lib.us_encoder_debug_attention(self._h, int(layer), P(q, sh, "q"), P(k, sh, "k"), P(v, sh, "v"), P(mask, (b, l), "mask"),
+                                                float(p_dropout), int(seed), r["out"].data_ptr(), r["P"].data_ptr(), P(dO, sh, "dO"), opt("DS"),
+                                                opt("dq"), opt("dk"), opt("dv"), opt("emb_rel_k"), opt("emb_rel_v"), b, l, ws.data_ptr(),
+                                                ws.numel(), stream)
+        self._check(lib, rc, f"us_encoder_debug_attention({layer})")
+        return r
+
+    @torch.no_grad()
+    def debug_embed_grad(self, ids, dx0):
+        """emb.weight's gradient alone (us_encoder_debug_embed_grad): ids [B, L] int64, dx0 [B, L, C] -> [n_vocab, C]."""
+        b, l = ids.shape
+        lib, stream = self._sync(dx0.device, training_ok=True)
+        if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.device != dx0.device:
+            raise ValueError("Encoder.debug_embed_grad: ids must be contiguous int64 on the device")
+        grad = torch.empty(self.cfg.n_vocab, self.cfg.n_channels, device=dx0.device)
+        with torch.cuda.device(dx0.device):
+            rc = lib.us_encoder_debug_embed_grad(self._h, ids.data_ptr(), self._ptr(dx0, (b, l, self.cfg.n_channels), "dx0"), grad.data_ptr(),
+                                                 b, l, stream)
+        self._check(lib, rc, "us_encoder_debug_embed_grad")
+        return grad
+
+
 def _release_tape(enc_ref, ptr):
     enc = enc_ref()
     if enc is not None and getattr(enc, "_h", None):
