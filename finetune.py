@@ -12,8 +12,9 @@
                 speaker embedder / unit extractor can run wherever their checkpoints live and the adaptation here:
                   mel        [1, 80, L]   normalised to [-1, 1] as finetune.py:104 leaves it (or raw with "mel_is_normalized": False); or
                              wav [T] or [1, T], the reference utterance at the decoder's sampling rate (`wav_sampling_rate`, when given,
-                             must say so: resampling is not part of the library): the mel of :86-104 is then computed on the device
-                             (unitspeech_amd.mel) and normalised with mel_min / mel_max
+                             must say so, unless --hip_resample is given: the waveform is then brought to 22050 Hz on the device,
+                             unitspeech_amd.resample): the mel of :86-104 is then computed on the device (unitspeech_amd.mel) and
+                             normalised with mel_min / mel_max
                   spk_emb    [1, 256] or [1, 1, 256]   (divided by its norm here, :110); or  spk_hidden_states [L, 1, T, C], the
                              speaker encoder's upstream hidden states (ecapa_tdnn.py:262-264) + --speaker_encoder_checkpoint (:106-110)
                   duration   [1, Lu]      frames per unit (process_unit, :114)
@@ -80,13 +81,18 @@ def load_features(args, cfg, base, device):
     if hip_mel:
         # finetune.py:86-104: mel_spectrogram(wav, 1024, 80, 22050, 256, 1024, 0, 8000, center=False), then the normalisation
         from unitspeech_amd.mel import MelSpectrogram
-        if "wav_sampling_rate" in d and int(d["wav_sampling_rate"]) != SAMPLING_RATE:
-            raise SystemExit(f"--features {path}: `wav` is at {int(d['wav_sampling_rate'])} Hz, the decoder's mel is defined at {SAMPLING_RATE} Hz; "
-                             "resample it first (the library has no resampler)")
+        rate = int(d["wav_sampling_rate"]) if "wav_sampling_rate" in d else SAMPLING_RATE
+        if rate != SAMPLING_RATE and not getattr(args, "hip_resample", False):
+            raise SystemExit(f"--features {path}: `wav` is at {rate} Hz, the decoder's mel is defined at {SAMPLING_RATE} Hz; "
+                             "resample it first, or pass --hip_resample to have the library do it on the device")
         wav = d["wav"].float()
         if wav.dim() not in (1, 2) or (wav.dim() == 2 and wav.shape[0] != 1):
             raise SystemExit(f"--features: wav must be [T] or [1, T], got {tuple(wav.shape)}")
-        mel = MelSpectrogram(*MEL_ARGS).to(device)(wav.reshape(1, -1).to(device), mel_min=mel_min, mel_max=mel_max).cpu()
+        wav = wav.reshape(1, -1).to(device)
+        if rate != SAMPLING_RATE:
+            from unitspeech_amd.resample import Resample
+            wav = Resample(rate, SAMPLING_RATE).to(device)(wav)                  # data.py:75, torchaudio.transforms.Resample(sr, 22050)
+        mel = MelSpectrogram(*MEL_ARGS).to(device)(wav, mel_min=mel_min, mel_max=mel_max).cpu()
     else:
         mel = d["mel"].float()
     if mel.dim() == 2:
@@ -155,6 +161,8 @@ def main():
                     "synthetic upstream hidden states instead of a random vector")
     ap.add_argument("--hip_mel", action="store_true", help="--synthetic: the mel comes from the HIP mel front end on a seeded waveform (normalised "
                     "with mel_min / mel_max) instead of random numbers")
+    ap.add_argument("--hip_resample", action="store_true", help="--features with `wav` at another `wav_sampling_rate` than 22050: resample it "
+                    "on the device (the HIP sinc resampler, torchaudio.transforms.Resample's arithmetic) before the mel")
     ap.add_argument("--learned_frontend", action="store_true", help="--synthetic: cond_x from the HIP unit encoder (seeded weights) on synthetic units")
     ap.add_argument("--reference_root", type=str, default=None)
     ap.add_argument("--out_dir", type=str, default="checkpoints/inference")

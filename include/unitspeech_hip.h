@@ -537,6 +537,38 @@ int us_mel_forward(us_mel_handle h, const float* wav, const int64_t* lengths, in
  * any order; a NaN is skipped (fminf / fmaxf); +inf / -inf when there is no valid frame. */
 int us_mel_minmax(us_mel_handle h, const float* mel, const int64_t* lengths_frames, int B, int F, float* out, us_stream stream);
 
+/* ---- sinc resampler (torchaudio.transforms.Resample, as called at finetune.py:113 and data.py:75,193), csrc/resample.hip ----------
+ * Waveform [B][Tmax] -> [B][us_resample_out_length(h, Tmax)].  With orig_freq and new_freq the two rates divided by their gcd and
+ * K = orig_freq + 2 width, output sample i = q * new_freq + c of an item of len samples is
+ *   out[i] = sum_{k < K} kernel[c][0][k] * y[q * orig_freq + k - width],  y = 0 outside [0, len),  i < ceil(new_freq * len / orig_freq):
+ * torchaudio's strided convolution with its buffer "kernel" [new_freq][1][K], the one weight, loaded from DEVICE memory and taken as
+ * given.  fp32 storage and accumulation, exact fp32 products on the matrix cores, the K products of an output added in sample order.
+ * Same conventions as the mel handle: the caller owns the scratch (us_resample_workspace_bytes); us_resample_forward allocates nothing
+ * and only enqueues on `stream` (lengths are read on the host during the call), a call made while another device than the handle's is
+ * current is refused (US_EINVAL), and an item alone or in a batch, and repeated calls, give the same bits.
+ * us_resample_create touches no device and returns US_EINVAL for a non-positive rate, rates with a common divisor, a rate above 4096,
+ * a negative width or a width above 2^16.  (The fields are not called `orig` and `new`: the latter is a C++ keyword.) */
+typedef struct us_resample* us_resample_handle;
+typedef struct us_resample_config {
+  int32_t orig_freq;                     /* 441 for 22050 -> 16000 */
+  int32_t new_freq;                      /* 320 */
+  int32_t width;                         /* 9: ceil(lowpass_filter_width * orig_freq / (rolloff * min(orig_freq, new_freq))) */
+} us_resample_config;
+int us_resample_create(us_resample_handle* out, const us_resample_config* cfg);
+int us_resample_destroy(us_resample_handle h);
+int us_resample_load_weight(us_resample_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_resample_num_weights(us_resample_handle h);
+const char* us_resample_weight_key(us_resample_handle h, int i);
+const char* us_resample_last_error(us_resample_handle h);
+/* samples of the output for T input samples: (new_freq * T + orig_freq - 1) / orig_freq in 64-bit integers (0 for T < 1) */
+int64_t us_resample_out_length(us_resample_handle h, int64_t T);
+size_t us_resample_workspace_bytes(us_resample_handle h, int B, int Tmax);
+/* wav [B][Tmax] (device); lengths: HOST int64 [B], the samples of each item in [1, Tmax], or NULL for Tmax each; Tmax at most 2^30.
+ * Samples at or past an item's length are never read.  out [B][us_resample_out_length(h, Tmax)]: item b has
+ * us_resample_out_length(h, lengths[b]) samples, the ones past them are 0; nothing past the row is written. */
+int us_resample_forward(us_resample_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, float* out, void* workspace,
+                        size_t workspace_bytes, us_stream stream);
+
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102
  * `process_unit`) as handle-free device calls.  Every call only enqueues on `stream`, allocates nothing and takes device scratch of

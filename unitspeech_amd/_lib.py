@@ -52,6 +52,10 @@ class us_mel_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "num_mels")]
 
 
+class us_resample_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("orig_freq", "new_freq", "width")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -138,6 +142,10 @@ SIGNATURES = {
     "us_mel_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_mel_minmax": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "us_resample_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_resample_config)]),
+    "us_resample_out_length": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "us_resample_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
@@ -157,8 +165,8 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_last_error": (C.c_char_p, [C.c_void_p]),
 }
-# what the four weight-table handles (csrc/handle.h) share
-for _p in ("frontend", "vocoder", "speaker", "mel"):
+# what the five weight-table handles (csrc/handle.h) share
+for _p in ("frontend", "vocoder", "speaker", "mel", "resample"):
     SIGNATURES.update({
         f"us_{_p}_destroy": (C.c_int, [C.c_void_p]),
         f"us_{_p}_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
