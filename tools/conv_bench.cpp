@@ -1,5 +1,7 @@
 // Micro-benchmark of the implicit-GEMM convolution kernel on synthetic shapes (build: see tools/conv_bench.sh).
 // usage: conv_bench   (environment: CB_CALIBRATE, CB_ONLY, CB_F16, CB_PRESPLIT, CB_TM, CB_SPLITK, CB_STATS, CB_NO_XCDZ, CB_COLD)
+// The "S" shapes (wino = 3, with CB_F16) are the 4-wide forms' separate GEMMs as the decoder launches them: each runs on the general kernel and,
+// where the rule routes it, on wino_stream_kernel; the two outputs are compared bit for bit.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -201,6 +203,7 @@ static void calibrate() {
 }
 
 struct Shape { const char* name; int B, H, W, Cin, Cout, taps; int wino = 0; };   // wino: B = 16 frequencies x 3 items, one weight matrix per frequency
+                                                                                  // wino = 3: B frequencies, H x W rows each, no bias (wino_conv's 4-wide branch)
 
 int main() {
   CK(conv_igemm_init());
@@ -223,6 +226,11 @@ int main() {
                     {"G3 gemm 1024->1024", 16, 15, 64, 1024, 1024, 1, 1}, {"G3 gemm 2048->512", 16, 15, 64, 2048, 512, 1, 1},
                     {"G3 gemm 512->512", 16, 15, 64, 512, 512, 1, 1},
                     {"H3 gemm 1024->1024", 24, 15, 32, 1024, 1024, 1, 1}, {"H2 gemm 512->512", 36, 15, 64, 512, 512, 1, 1}, {"G0 gemm 128->128", 16, 120, 512, 128, 128, 1, 1},
+                    // F(4x4) / F(2x4) at B' = 3: rows per frequency = 3 items x tiles
+                    {"S1 W44 256->256", 36, 30, 128, 256, 256, 1, 3},
+                    {"S2 W44 256->256", 36, 15, 64, 256, 256, 1, 3}, {"S2 W44 256->512", 36, 15, 64, 256, 512, 1, 3},
+                    {"S2 W44 512->512", 36, 15, 64, 512, 512, 1, 3}, {"S3 W24 512->512", 24, 15, 32, 512, 512, 1, 3},
+                    {"S1 W44 ragged 340 rows", 36, 20, 17, 256, 256, 1, 3}, {"S2 W44 ragged 50 rows", 36, 10, 5, 256, 512, 1, 3},
                     // wino = 2: output transform fused (B = items, H x W = tile grid, output 2H x 2W)
                     {"F0 fused 128->128", 3, 40, 512, 128, 128, 1, 2}, {"F1 fused 256->256", 3, 20, 256, 256, 256, 1, 2},
                     {"F1 fused 512->256", 3, 20, 256, 512, 256, 1, 2}, {"F2 fused 512->512 B24", 24, 10, 128, 512, 512, 1, 2},
@@ -233,7 +241,8 @@ int main() {
   for (auto& sh : shapes) {
     if (getenv("CB_ONLY") && !strstr(sh.name, getenv("CB_ONLY"))) continue;
     size_t n_in = (size_t)sh.B * sh.H * sh.W * sh.Cin * (sh.wino == 2 ? 16 : 1), n_out = (size_t)sh.B * sh.H * sh.W * sh.Cout * (sh.wino == 2 ? 4 : 1);
-    size_t n_w = (size_t)sh.taps * sh.Cin * sh.Cout * (sh.wino == 1 ? sh.B / std::max(sh.B / 16, 1) : (sh.wino ? 16 : 1));
+    size_t n_w = (size_t)sh.taps * sh.Cin * sh.Cout * (sh.wino == 1 ? sh.B / std::max(sh.B / 16, 1) : (sh.wino == 3 ? sh.B : (sh.wino ? 16 : 1)));
+    if (sh.wino == 3 && !getenv("CB_F16")) continue;
     float *in, *out, *w, *bias;
     CK(hipMalloc(&in, n_in * 4)); CK(hipMalloc(&out, n_out * 4)); CK(hipMalloc(&w, n_w * 4)); CK(hipMalloc(&bias, sh.Cout * 4));
     CK(launch_fill_normal(in, n_in, 1, 1, 0)); CK(launch_fill_normal(w, n_w, 1, 2, 0)); CK(launch_fill_normal(bias, sh.Cout, 1, 3, 0));
@@ -243,9 +252,11 @@ int main() {
       if (sh.wino || presplit) hipLaunchKernelGGL(to_f16x2_kernel, dim3(4096), dim3(256), 0, 0, in, n_in / 8);
       hipLaunchKernelGGL(to_f16x2_kernel, dim3(4096), dim3(256), 0, 0, w, n_w / 8);
     }
+    std::vector<float> ref_out;         // wino = 3: the general kernel's output, compared with the streaming kernel's
+    for (int stream : {0, 1})
     for (int tm : {0, 256, 128, 64}) {
-      if (tm == 0 && !(getenv("CB_TM") && atoi(getenv("CB_TM")) == 0)) continue;
-      if (getenv("CB_TM") && atoi(getenv("CB_TM")) != tm) continue;
+      if (sh.wino == 3 ? tm != 0 : (stream != 0 || (tm == 0 && !(getenv("CB_TM") && atoi(getenv("CB_TM")) == 0)))) continue;
+      if (sh.wino != 3 && getenv("CB_TM") && atoi(getenv("CB_TM")) != tm) continue;
       if (tm == 256 && !(f16 && sh.wino != 2)) continue;
       ConvArgs a; memset(&a, 0, sizeof a);
       a.in = in; a.in_ld = sh.Cin; a.wt = w; a.bias = bias; a.out = out; a.out_ld = sh.Cout; a.zeros = zeros;
@@ -258,6 +269,10 @@ int main() {
       if (getenv("CB_STATS") && sh.wino != 1) a.stats = stats;
       if (sh.wino == 1 && !getenv("CB_NO_XCDZ")) a.xcd_z = 1;
       if (sh.wino == 1) { a.wt_bstride = (long long)sh.Cin * sh.Cout; a.wt_bdiv = sh.B / 16; a.splitk_ws = nullptr; }
+      if (sh.wino == 3) {
+        a.wt_bstride = (long long)sh.Cin * sh.Cout; a.splitk_ws = nullptr; a.bias = nullptr; a.xcd_z = sh.Cin >= 256 && sh.Cout >= 256;
+        a.Hin = a.Hs = a.Hout = sh.H; a.wino_stream = stream;
+      }
       if (sh.wino == 2) { a.wt_bstride = (long long)sh.Cin * sh.Cout; a.wino_out = 1; a.ostep = 2; a.Hout = 2 * sh.H; a.Wout = 2 * sh.W; a.splitk_ws = nullptr; }
       if (sh.taps == 9) { for (int ky = 0; ky < 3; ++ky) for (int kx = 0; kx < 3; ++kx) a.set_tap(ky * 3 + kx, ky - 1, kx - 1, ky * 3 + kx); }
       else a.set_tap(0, 0, 0, 0);
@@ -329,6 +344,17 @@ int main() {
         CK(hipEventElapsedTime(&ms, e0, e1)); ms /= reps;
       }
       double fl = 2.0 * sh.B * sh.H * sh.W * (double)sh.Cin * sh.Cout * sh.taps * (sh.wino == 2 ? 16 : 1);
+      if (sh.wino == 3) {
+        std::vector<float> h(n_out);
+        CK(hipMemcpy(h.data(), out, n_out * 4, hipMemcpyDeviceToHost));
+        const double gb = ((double)n_in + n_out + n_w) * 4e-9;
+        double asum = 0; for (float v : h) asum += v < 0 ? -v : v;
+        printf("%-24s %s  %8.1f us  %6.1f TFLOP/s  %5.2f TB/s  mean|M| %.4f", sh.name, stream ? "stream " : "general", ms * 1e3, fl / ms / 1e9, gb / ms, asum / n_out);
+        if (!stream) { ref_out.swap(h); printf("\n"); }
+        else printf("  %s\n", memcmp(ref_out.data(), h.data(), n_out * 4) == 0 ? "bit-identical" : "DIFFERS");
+        CK(hipMemset(out, 0xff, n_out * 4));       // the next variant must write every element itself
+        continue;
+      }
       printf("%-20s tm=%3d %s  %8.1f us  %6.1f TFLOP/s\n", sh.name, tm, f16 ? "f16x3" : "fp32 ", ms * 1e3, fl / ms / 1e9);
     }
     CK(hipFree(in)); CK(hipFree(out)); CK(hipFree(w)); CK(hipFree(bias));

@@ -1,5 +1,5 @@
 #!/bin/bash
-# builds and runs the conv micro-benchmark on the GPU box: tools/conv_bench.sh | f16 [filter] | life [filter] | diag [filter]
+# builds and runs the conv micro-benchmark on the GPU box: tools/conv_bench.sh | f16 [filter] | stream [filter] | life [filter] | diag [filter]
 set -e
 cd "$(dirname "$0")/.."
 hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/conv_bench.cpp unitspeech_amd/csrc/conv_igemm.hip unitspeech_amd/csrc/ops.hip -o /tmp/conv_bench
@@ -8,6 +8,11 @@ if [ "$1" = f16 ]; then
   CB_CALIBRATE=1 CB_ONLY="(none)" /tmp/conv_bench | grep "calibration"
   CB_ONLY="${2:-G}" CB_F16=1 /tmp/conv_bench
   CB_ONLY="${2:-G}" /tmp/conv_bench
+  exit 0
+fi
+if [ "$1" = stream ]; then
+  # the 4-wide forms' separate GEMMs on the general and on the streaming kernel, outputs compared: tools/conv_bench.sh stream [shape filter]
+  CB_ONLY="${2:-S}" CB_F16=1 /tmp/conv_bench
   exit 0
 fi
 if [ "$1" = life ]; then

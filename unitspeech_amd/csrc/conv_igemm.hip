@@ -31,6 +31,7 @@ namespace us {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TN = 128;      // columns per workgroup of the NB = 2 instantiations (host-side sizing)
 
@@ -847,6 +848,170 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs a) {
   }
 }
 
+// Winograd-domain GEMMs with short K (256), streamed: M_f [rows][N] = V_f [rows][K] * U_f, both operands in the two-plane fp16 form, M in
+// fp32.  The general loop above runs these at half the rate the chip streams at: eight steps of K = 256 are a prologue and an epilogue as long
+// as the loop, with a barrier and six LDS-DMA pieces per wave for every 12 MFMAs.  Here a workgroup of 8 waves (one per CU, two per SIMD) owns one
+// frequency, one group of 256 output columns and a contiguous range of 32-row tiles.  Wave w keeps the B fragments of columns 32 w .. 32 w + 31 for
+// the WHOLE of K in registers (K / 16 steps x 2 planes x 16 bytes per lane: 128 VGPRs at K = 256), loaded once, straight from the
+// [K/32][N][32] pack (a lane's 8 channels of one plane are one 16-byte piece there).  Only the A tiles (32 rows x K * 4 bytes) go through LDS, NBUF
+// buffers deep, with ONE counted vmcnt wait and ONE barrier per row tile: K / 64 DMA pieces per wave for 3 K / 16 MFMAs.
+// LDS image of a tile: 16-byte slot (row, c) sits at row * K/4 + (c ^ (row & 15)); K/4 is a multiple of 16, so the 16 rows of a ds_read_b128 lane
+// group ({0-3,12-15,20-27} / {4-11,16-19,28-31}: all 16 residues of row & 15) hit the 16 distinct slots of the 256-byte bank window.  The swizzle is
+// applied on the source side of the DMA (the image must be lane-linear) and again by the reads.
+// Summation order per output element is the general kernel's (ascending 16-deep steps, acc = hi hi, total = hi lo + lo hi, one final fma, same
+// lane-half convention), so M is bit-identical to conv_igemm_kernel<32, 64, false, true>'s.
+// vmcnt: loads, LDS-DMA and stores retire in issue order.  Every iteration issues exactly K/64 pieces (rows or tiles beyond the tensor read zeros
+// through the descriptor) and 4 buffer stores (rows beyond the tensor are dropped by the descriptor), so the count behind tile j's pieces is known.
+template <int K, int NBUF>
+__global__ __launch_bounds__(512) void wino_stream_kernel(ConvArgs a, int rows, int rgroups, int total_wgs) {
+  constexpr int CPRK = K / 4;             // 16-byte slots per A row
+  constexpr int TILE_F = 32 * K;          // floats per A tile
+  constexpr int P = K / 64;               // DMA pieces per wave and tile (32 * CPRK slots / 64 lanes / 8 waves)
+  constexpr int NSTEP = K / 16;           // 16-deep MFMA steps
+  constexpr int PSTRIDE = NSTEP / P;      // one piece every PSTRIDE steps
+  static_assert(K == 128 || K == 256, "the B fragments of the whole K live in registers");      // (only K = 256 is instantiated: no 4-wide pack has K < 256)
+  static_assert(NBUF >= 3 && (NBUF - 2) * P + 4 * (NBUF - 1) <= 63, "counted vmcnt waits");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l32 = lane & 31, hh = lane >> 5;
+  // Workgroups are dealt round-robin over the 8 XCDs; XCD k takes the k-th contiguous eighth of the (frequency, column group, row group) range, so
+  // the workgroups of a frequency share one L2 for U_f (and, with two column groups, for the A tiles both read).  gridDim.x is a multiple of 8.
+  const unsigned per = gridDim.x >> 3;
+  const unsigned lp = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+  if (lp >= (unsigned)total_wgs) return;
+  const int ncg = a.Cout >> 8;
+  const int rg = (int)(lp % (unsigned)rgroups);
+  const int fc = (int)(lp / (unsigned)rgroups);
+  const int f = fc / ncg, cg = fc - f * ncg;
+  const int ntile = (rows + 31) >> 5;
+  const int t_lo = ntile * rg / rgroups, t_hi = ntile * (rg + 1) / rgroups;      // ntile < 2^17 (host: rows * K * 4 < 2^31), rgroups <= 256
+  if (t_hi <= t_lo) return;
+
+  // ---- B fragments: this wave's 32 columns, all of K ----
+  const int ncol = cg * 256 + wave * 32;
+  const int wrows = a.wt_rows ? a.wt_rows : a.Cout;
+  const float* wl = a.wt + (long long)f * a.wt_bstride + (long long)(ncol + l32) * 32 + hh * 8;
+  f32x4 bf[NSTEP][2];
+#pragma unroll
+  for (int s = 0; s < NSTEP; ++s)
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+      bf[s][p] = *reinterpret_cast<const f32x4*>(wl + (long long)(s >> 1) * wrows * 32 + (s & 1) * 16 + p * 4);
+
+  // ---- A tiles: DMA source bookkeeping (this lane feeds slot 64 * (wave * P + j) + lane of the image) ----
+  const unsigned a_bytes = (unsigned)rows * (unsigned)(K * 4);              // < 2^31 (host-checked)
+  const unsigned o_bytes = (unsigned)rows * (unsigned)a.Cout * 4u;          // < 2^31 (host-checked)
+  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (long long)f * rows * K), 0, (int)a_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_o =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (long long)f * rows * a.Cout), 0, (int)o_bytes, 0x00020000);
+  int arow[P];
+  unsigned aoff[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const int slot = (wave * P + j) * 64 + lane;
+    const int r = slot / CPRK, pos = slot % CPRK;
+    arow[j] = r;
+    aoff[j] = (unsigned)r * (unsigned)(K * 4) + (unsigned)((pos ^ (r & 15)) * 16);
+  }
+  // the whole offset travels in the per-lane register: that is the one the descriptor's range check sees
+  auto dma_piece = [&](int tile, int buf, int j) {
+    const int m = tile * 32 + arow[j];
+    const unsigned off = (tile < t_hi && m < rows) ? (unsigned)tile * (unsigned)(32 * K * 4) + aoff[j] : a_bytes;
+    blds16(rsrc_a, off, 0u, smem + buf * TILE_F + (wave * P + j) * 256);
+  };
+
+  // fragment reads: row l32, slot 4 s + 2 hh + p
+  const int xr = l32 & 15;
+  const int a_row = l32 * K;
+  float* tr = smem + NBUF * TILE_F + wave * (32 * 36);     // per-wave turn-round patch, 32 rows x (32 + 4 pad) floats
+  const int trow = lane >> 3, tc4 = (lane & 7) * 4;
+
+#pragma unroll
+  for (int i = 0; i < NBUF - 1; ++i)
+#pragma unroll
+    for (int j = 0; j < P; ++j) dma_piece(t_lo + i, i, j);
+
+  int cur = 0;
+  for (int t = t_lo; t < t_hi; ++t) {
+    // tile t's pieces were followed by those of tiles t+1 .. t+NBUF-2 and by the stores of the min(t - t_lo, NBUF - 1) tiles before this one
+    const int nst = t - t_lo < NBUF - 1 ? t - t_lo : NBUF - 1;
+    if (nst == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * P) : "memory");
+    else if (nst == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * P + 4) : "memory");
+    else if (nst == 2 || NBUF == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * P + 8) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * P + 12) : "memory");
+    __builtin_amdgcn_s_barrier();       // everybody's pieces of tile t have landed; everybody is done reading tile t-1, whose buffer tile t+NBUF-1 takes
+    const int nbuf = cur == 0 ? NBUF - 1 : cur - 1;
+    const float* base = smem + cur * TILE_F + a_row;
+    f32x16 acc, total;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; total[r] = 0.f; }
+    f32x4 fa[2][2];
+    auto load_frags = [&](f32x4* fr, int s) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) fr[p] = *reinterpret_cast<const f32x4*>(base + ((4 * s + 2 * hh + p) ^ xr) * 4);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    load_frags(fa[0], 0);
+#pragma unroll
+    for (int s = 0; s < NSTEP; ++s) {
+      if (s + 1 < NSTEP) load_frags(fa[(s + 1) & 1], s + 1);
+      const half8 ah = __builtin_bit_cast(half8, fa[s & 1][0]), al = __builtin_bit_cast(half8, fa[s & 1][1]);
+      const half8 bh = __builtin_bit_cast(half8, bf[s][0]), bl = __builtin_bit_cast(half8, bf[s][1]);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+      if (s % PSTRIDE == 0) {         // the next tile's pieces go out under executing MFMAs, not in a burst
+        __builtin_amdgcn_sched_barrier(0);
+        dma_piece(t + NBUF - 1, nbuf, s / PSTRIDE);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      total = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, total, 0, 0, 0);
+      total = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, total, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = __builtin_fmaf(total[r], 0x1p-11f, acc[r]);
+    // C/D layout of the 32x32 block: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); turned round so that a lane stores 16 bytes
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * hh) * 36 + l32] = acc[r];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int dr = trow + 8 * k;
+      const int m = t * 32 + dr;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(tr + dr * 36 + tc4);
+      const unsigned off = m < rows ? ((unsigned)m * (unsigned)a.Cout + (unsigned)(ncol + tc4)) * 4u : o_bytes;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_o, (int)off, 0, 0);
+    }
+    cur = cur == NBUF - 1 ? 0 : cur + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the zero-filled pieces of the tiles beyond t_hi are still landing in this workgroup's LDS
+}
+
+template <int K, int NBUF>
+static constexpr int stream_lds_bytes() { return (NBUF * 32 * K + 8 * 32 * 36) * (int)sizeof(float); }
+
+// Does a launch qualify for wino_stream_kernel?  A function of K, N and the form only (the sizes below merely keep 32-bit offsets in range).
+static bool wino_stream_route(const ConvArgs& a) {
+  if (!a.wino_stream || a.f16 != 1 || a.ntaps != 1 || a.direct_presplit || a.istride != 1 || a.tm != 0) return false;
+  if (a.bias || a.add || a.stats || a.omask || a.alpha || a.out2 || a.out_split || a.wino_out || a.attn_part_ctx || a.nphase > 1) return false;
+  if (a.Cin != 256 || a.Cout % 256 != 0 || a.in_ld != a.Cin || a.out_ld != a.Cout || a.wt_bdiv > 1) return false;
+  if (a.ostep != 1 || a.oy0 != 0 || a.ox0 != 0 || a.Hs != a.Hout || a.Ws != a.Wout || a.Hin != a.Hs || a.Win != a.Ws) return false;
+  if ((a.dy_bits & 15) != 8 || (a.dx_bits & 15) != 8 || (a.wtap_bits & 15) != 0) return false;
+  const long long rows = (long long)a.Hs * a.Ws;
+  return rows * a.Cin * 4 < (1LL << 31) && rows * a.Cout * 4 < (1LL << 31);
+}
+
+static hipError_t launch_wino_stream(const ConvArgs& a, hipStream_t s) {
+  const int rows = a.Hs * a.Ws, ntile = (rows + 31) / 32;
+  const int pairs = a.B * (a.Cout / 256);
+  // about one workgroup per CU (each takes a whole CU's LDS); the row-group count follows the batch, which does not touch the summation order
+  int rgroups = 256 / pairs;
+  if (rgroups < 1) rgroups = 1;
+  if (rgroups > ntile) rgroups = ntile;
+  const int total = pairs * rgroups;
+  const dim3 grid(((total + 7) / 8) * 8);
+  hipLaunchKernelGGL((wino_stream_kernel<256, 3>), grid, dim3(512), (stream_lds_bytes<256, 3>()), s, a, rows, rgroups, total);
+  return hipGetLastError();
+}
+
 static size_t lds_bytes(int bk, int tm, int nstg = 2, int tn = TN) { return (size_t)nstg * (tm + tn) * bk * sizeof(float); }
 
 template <int BK, int WM, bool WINO, bool F16 = false, int NWM = 2, int NSTG = 2, bool ASPLIT = false>
@@ -871,6 +1036,8 @@ hipError_t conv_igemm_init() {
   if ((e = set_attr<32, 32, false, true, 2, 2, true>()) != hipSuccess) return e;
   if ((e = set_attr<32, 32, false, true>()) != hipSuccess) return e;
   if ((e = set_attr<32, 32, true, true, 2, 3>()) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_stream_kernel<256, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               stream_lds_bytes<256, 3>())) != hipSuccess) return e;
   return set_attr<16, 32, true>();
 }
 
@@ -890,6 +1057,8 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     if (a.Cout % kGroups != 0 || (cg & (cg - 1)) != 0) return hipErrorInvalidValue;
   }
   if (a.out2 && (a.out2_ld % 4 != 0 || a.wino_out || a.out_split || a.attn_part_ctx)) return hipErrorInvalidValue;
+  // short-K Winograd-domain GEMMs of the 4-wide forms: the streaming kernel (same bits; US_WINO_STREAM, a non-zero US_F16_TM keeps this path)
+  if (wino_stream_route(a)) return launch_wino_stream(a, s);
   const int Ms = a.Hs * a.Ws;
   int tn = TN;                        // 64: the half-width tile of the Winograd-domain GEMMs (conv_igemm_kernel<.., NB = 1>), chosen below
   int nt = (a.Cout + TN - 1) / TN;

@@ -121,6 +121,7 @@ struct us_decoder {
   int wino4_level_form[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int wino_fuse = -1;        // US_WINO_FUSE: Winograd output transform inside the GEMM wherever legal (1), never (0), by launch size (-1, wino_conv)
   bool wino_fuse_gn = true;  // US_WINO_FUSE_GN=0: block1's gn_apply as its own pass
+  bool wino_stream = true;   // US_WINO_STREAM=0: the 4-wide forms' K = 256 GEMMs on the general kernel instead of wino_stream_kernel (same bits)
   int f16_tm = 0;            // US_F16_TM: rows per workgroup of the f16x3 Winograd-domain GEMMs (64, 128, 256; 0: the launcher's rule)
   // parameter-gradient chains of a backward pass on side streams (train_host.inc, BwdCtx); US_WGRAD_STREAM=0: everything on the caller's
   // (measured, fine-tune iteration / pre-training step: 1 side stream 10.29 ms / 61.5 ms, 2: 10.43 / 62.5, 3: 11.7 / 62.9)
@@ -538,6 +539,7 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
     a.out = b.wino_m; a.out_ld = N;
     a.B = nf; a.Hin = a.Hs = a.Hout = e.Bp * t4h; a.Wout = t4w; a.ostep = 1;
     a.tm = e.h->f16_tm;
+    a.wino_stream = e.h->wino_stream ? 1 : 0;
     a.xcd_z = K >= 256 && N >= 256;
     err4 = run_conv(e, a);
     if (err4 != hipSuccess) return err4;
@@ -1226,6 +1228,7 @@ int us_decoder_create_ex(us_handle* out, const us_config* cfg, unsigned flags) {
   if (const char* wl = getenv("US_WINO_MIN_LEVEL")) h->wino_min_level = atoi(wl);
   if (const char* wf = getenv("US_WINO_FUSE")) h->wino_fuse = atoi(wf) != 0 ? 1 : 0;
   if (const char* wf = getenv("US_WINO_FUSE_GN")) h->wino_fuse_gn = atoi(wf) != 0;
+  if (const char* ws = getenv("US_WINO_STREAM")) h->wino_stream = atoi(ws) != 0;
   if (const char* wt = getenv("US_F16_TM")) h->f16_tm = atoi(wt) == 64 || atoi(wt) == 128 || atoi(wt) == 256 ? atoi(wt) : 0;
   if (const char* ws = getenv("US_WGRAD_STREAM")) h->wgrad_side_streams = atoi(ws) < 0 ? 0 : (atoi(ws) > Tape::kSideMax ? Tape::kSideMax : atoi(ws));
   {

@@ -127,6 +127,8 @@ struct ConvArgs {
   float* splitk_ws;      // optional scratch for split-K partial slabs (splitk_ws_floats floats); null disables split-K
   long long splitk_ws_floats;
   unsigned* range_flag;  // set by the launcher (current_range_flag()): where an in-kernel f16x3 split reports an operand beyond the fp16 range
+  int wino_stream;       // 1: a separate-form Winograd-domain GEMM (f16 = 1) with K = 256 and N a multiple of 256 may run on
+                         // wino_stream_kernel (conv_igemm.hip: weights in registers, A tiles streamed; same bits).  us_decoder::wino_stream
   int direct_presplit;   // f16 = 1 on a DIRECT convolution (its producer stored the input with out_split), as opposed to a Winograd-domain
                          // GEMM: the tile follows the direct rule (a function of the item's geometry only, never of the batch)
   int out_split;         // 1: the stored tensor is the two-plane fp16 form (per 8 channels 8 hi | 8 lo, same bytes as fp32; Cout, out_ld and
