@@ -7,7 +7,8 @@
                 come from a checkout of the reference given with --reference_root and stay on the stock PyTorch path.
   --synthetic   seeded synthetic decoder weights and a synthetic (mel, units, durations, speaker embedding) tuple: runs the
                 fine-tuning loop itself (BASELINE.json configs[3]) without any downloaded model.  --hip_mel takes the mel from a seeded
-                waveform through the HIP mel front end instead of random numbers.
+                waveform through the HIP mel front end instead of random numbers; --hip_hubert (with --hip_units) takes the dense features
+                from the HIP HuBERT encoder (seeded base-size weights) on a seeded waveform, resampled 22050 -> 16000 with --hip_resample.
   --features F  the OUTPUTS of the reference's pre-steps (finetune.py:86-128) from a `.pt` (torch.save of a dict) or `.npz` file, so the
                 speaker embedder / unit extractor can run wherever their checkpoints live and the adaptation here:
                   mel        [1, 80, L]   normalised to [-1, 1] as finetune.py:104 leaves it (or raw with "mel_is_normalized": False); or
@@ -22,6 +23,10 @@
                   dense      [T, D]       in place of unit / duration: the unit extractor's dense features (:112), quantised and brought to
                              the mel rate on the device (unitspeech_amd.units) with the centres of --kmeans_checkpoint (a scikit-learn
                              KMeans saved with joblib) or `centers` [K, D] in the file; needs --unit_encoder_checkpoint
+                  wav                     also in place of dense / unit / duration, with --hubert_checkpoint (a HuBERT-base checkpoint in
+                             transformers' or fairseq's layout; --hubert_layer, default 11) and --kmeans_checkpoint: the waveform is
+                             brought to 16 kHz on the device (:113), the HIP HuBERT encoder (unitspeech_amd.hubert) gives the dense features
+                             and the units come from them as above
                   mel_min, mel_max        scalars (else the decoder checkpoint's, :98-99)
 Saves {"model", "spk_emb", "mel_min", "mel_max"} like finetune.py:167-173.
 """
@@ -53,6 +58,16 @@ def load_features(args, cfg, base, device):
     else:
         d = torch.load(path, map_location="cpu")
     d = {k: (torch.as_tensor(v) if not isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+    if "wav" in d and getattr(args, "hubert_checkpoint", None) and not any(k in d for k in ("dense", "unit", "cond_x")):
+        # finetune.py:112-113: the unit extractor's dense model on the utterance at 16 kHz
+        from unitspeech_amd.hubert import HubertFeatureReader, load_hubert_checkpoint
+        from unitspeech_amd.resample import Resample
+        rate = int(d["wav_sampling_rate"]) if "wav_sampling_rate" in d else SAMPLING_RATE
+        wav16 = d["wav"].float().reshape(1, -1).to(device)
+        if rate != 16000:
+            wav16 = Resample(rate, 16000).to(device)(wav16)                     # :113, torchaudio.transforms.Resample(22050, 16000)
+        hubert, normalize = load_hubert_checkpoint(args.hubert_checkpoint)
+        d["dense"] = HubertFeatureReader(hubert, layer=args.hubert_layer, normalize=normalize).to(device)(wav16[0]).cpu()
     if "dense" in d and "unit" not in d and "cond_x" not in d:
         # finetune.py:112-114: KMeans.predict, unique_consecutive and process_unit(encoded, 16000, 256), here in one library call
         from unitspeech_amd.units import KMeansQuantizer
@@ -155,6 +170,11 @@ def main():
                     "extractor's k-means model (scikit-learn KMeans saved with joblib); units and durations come from the HIP unit extraction")
     ap.add_argument("--hip_units", action="store_true", help="--synthetic --learned_frontend: the units and durations come from the HIP unit "
                     "extraction (k-means quantiser + process_unit) on synthetic dense features and centres instead of random units")
+    ap.add_argument("--hip_hubert", action="store_true", help="--synthetic --learned_frontend --hip_units: the dense features come from the HIP "
+                    "HuBERT encoder (seeded base-size weights) on a seeded waveform (at 22050 Hz and resampled on the device with --hip_resample)")
+    ap.add_argument("--hubert_checkpoint", type=str, default=None, help="--features with `wav` instead of `dense` / `unit`: a HuBERT-base checkpoint "
+                    "(transformers' state_dict or fairseq's {'model': ...}) for the HIP HuBERT encoder; needs --kmeans_checkpoint or `centers`")
+    ap.add_argument("--hubert_layer", type=int, default=11, help="the encoder layer whose output is quantised (the reference's mHuBERT units: 11)")
     ap.add_argument("--speaker_encoder_checkpoint", type=str, default=None, help="--features with `spk_hidden_states` instead of `spk_emb`: the "
                     "speaker encoder's checkpoint ({'model': state_dict}, util.py:183-188); the embedding comes from the HIP ECAPA-TDNN")
     ap.add_argument("--hip_speaker_encoder", action="store_true", help="--synthetic: spk_emb from the HIP ECAPA-TDNN (seeded weights) on "
@@ -218,12 +238,33 @@ def main():
             unit_encoder.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_encoder_state_dict(ec, 0).items()})
             unit = torch.from_numpy(g.integers(0, ec.n_vocab, size=(1, Lu)).astype(np.int64)).to(device)
             duration = torch.full((1, Lu), 3.0, device=device)
+            if args.hip_hubert and not args.hip_units:
+                raise SystemExit("--hip_hubert needs --hip_units (its features feed the unit quantiser)")
             if args.hip_units:
                 # finetune.py:112-114: the units are the k-means labels of the unit extractor's dense features (50 Hz, 16 kHz audio) brought
                 # to the mel rate by process_unit(encoded, 16000, 256); here seeded centres and features for the L mel frames
                 from unitspeech_amd.units import KMeansQuantizer, synthetic_centers, synthetic_dense
                 centers = synthetic_centers(ec.n_vocab, 768, args.ID & 0xffff)
-                dense = torch.from_numpy(synthetic_dense(centers, L * 256 // 320, args.ID & 0xffff)).to(device)
+                if args.hip_hubert:
+                    # finetune.py:112-113: the dense features are the unit extractor's HuBERT on the utterance at 16 kHz; here seeded base-size
+                    # weights on a seeded waveform of L * 256 // 320 frames
+                    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+                    from hubert_torch import base_config, synthetic_hubert_state_dict
+                    from unitspeech_amd.hubert import HubertFeatureReader, HubertModel
+                    from unitspeech_amd.mel import synthetic_waveform
+                    n16 = 400 + 320 * (L * 256 // 320 - 1)
+                    if args.hip_resample:
+                        from unitspeech_amd.resample import Resample
+                        n22 = -(-n16 * 441 // 320)
+                        wav16 = Resample(SAMPLING_RATE, 16000).to(device)(torch.from_numpy(synthetic_waveform(n22, args.ID & 0xffff, SAMPLING_RATE)).to(device))[:n16]
+                    else:
+                        wav16 = torch.from_numpy(synthetic_waveform(n16, args.ID & 0xffff, 16000)).to(device)
+                    hubert = HubertModel.base()
+                    hubert.load_state_dict(synthetic_hubert_state_dict(base_config(), args.ID & 0xffff))
+                    dense = HubertFeatureReader(hubert, layer=args.hubert_layer).to(device)(wav16)
+                    print(f"hip hubert: {wav16.numel()} samples at 16 kHz -> {dense.shape[0]} frames of {dense.shape[1]} (layer {args.hubert_layer})")
+                else:
+                    dense = torch.from_numpy(synthetic_dense(centers, L * 256 // 320, args.ID & 0xffff)).to(device)
                 unit, duration, n = KMeansQuantizer.from_centers(centers).encode(dense.unsqueeze(0), None, 16000, 256)
                 Lu = int(n[0])
                 unit, duration = unit[:, :Lu], duration[:, :Lu]
@@ -232,6 +273,8 @@ def main():
         else:
             if args.hip_units:
                 raise SystemExit("--hip_units needs --learned_frontend (the units feed the HIP unit encoder)")
+            if args.hip_hubert:
+                raise SystemExit("--hip_hubert needs --learned_frontend --hip_units (its features feed the unit quantiser)")
             duration = torch.full((1, Lu), 3.0, device=device)
         if args.hip_speaker_encoder:
             # finetune.py:106-110: spk_emb is the ECAPA-TDNN's embedding of the reference utterance over its norm; here the HIP module
@@ -251,7 +294,8 @@ def main():
             raise SystemExit("give --features (the pre-step tensors), --reference_root (reference checkout with its checkpoints) or use --synthetic")
         raise SystemExit("running the pre-steps here needs the reference's WavLM/ECAPA speaker embedder, mHuBERT unit extractor and unit "
                          "encoder checkpoints (finetune.py:47-128), none of which are available offline; run the pre-steps with the "
-                         "reference, save their tensors and pass the file with --features")
+                         "reference, save their tensors and pass the file with --features (the unit extractor itself runs here: `wav` with "
+                         "--hubert_checkpoint and --kmeans_checkpoint)")
     decoder = decoder.to(device).train()
     # finetune.py:81 uses torch.optim.Adam; FusedAdam is the same update (clip + Adam) in three HIP launches
     opt = (torch.optim.Adam if args.torch_optimizer else FusedAdam)(decoder.parameters(), lr=args.learning_rate)

@@ -569,6 +569,57 @@ size_t us_resample_workspace_bytes(us_resample_handle h, int B, int Tmax);
 int us_resample_forward(us_resample_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, float* out, void* workspace,
                         size_t workspace_bytes, us_stream stream);
 
+/* ---- HuBERT encoder (the unit extractor's dense model, textless/data/hubert_feature_reader.py, and the ContentVec extractor of
+ * scripts/voice_conversion.py:46-68), csrc/hubert.hip ---------------------------------------------------------------------------------
+ * 16 kHz waveform [B][Tmax] with per-item lengths -> the encoder's state after n layers, [B][F][H] with F = us_hubert_frames(h, Tmax):
+ * transformers.HubertModel with the group-norm feature extractor and post-LN layers (hidden_states[n]; fairseq's output_layer = n), eval
+ * mode.  Weights go in by transformers' state_dict keys, except that the positional convolution's weight-norm pair is given folded as
+ * "encoder.pos_conv_embed.conv.weight" = g v / |v| [H][H / groups][k] and masked_spec_embed is not taken.  fp32 storage, exact fp32
+ * products on the matrix cores.  Same conventions as the other weight-table handles: us_hubert_create touches no device, the caller owns
+ * the scratch (us_hubert_workspace_bytes, 0 for B < 1 or a Tmax below the receptive field), us_hubert_forward allocates nothing and only
+ * enqueues on `stream` (lengths are read on the host during the call), a call made while another device than the handle's is current is
+ * refused (US_EINVAL), and an item alone or in a batch, and repeated calls, give the same bits.
+ * us_hubert_create returns US_EINVAL for feat_extract_norm other than US_HUBERT_NORM_GROUP, do_stable_layer_norm, a hidden size the heads
+ * do not divide, a head dimension above 64 or not a multiple of 4, a hidden size the positional groups do not divide, more than
+ * US_HUBERT_MAX_CONV extractor layers, more than 16 taps in layer 0 or a stride above 4 in a later layer. */
+#define US_HUBERT_MAX_CONV 8
+enum { US_HUBERT_NORM_GROUP = 0, US_HUBERT_NORM_LAYER = 1 };
+typedef struct us_hubert* us_hubert_handle;
+typedef struct us_hubert_config {
+  int32_t n_conv;                            /* 7 */
+  int32_t conv_dim[US_HUBERT_MAX_CONV];      /* 512 x 7 */
+  int32_t conv_kernel[US_HUBERT_MAX_CONV];   /* 10, 3, 3, 3, 3, 2, 2 */
+  int32_t conv_stride[US_HUBERT_MAX_CONV];   /* 5, 2, 2, 2, 2, 2, 2 */
+  int32_t hidden_size;                       /* 768 */
+  int32_t n_heads;                           /* 12 */
+  int32_t intermediate_size;                 /* 3072 */
+  int32_t n_layers;                          /* 12 */
+  int32_t pos_conv_kernel;                   /* 128; padding k / 2, an even k drops the last output step */
+  int32_t pos_conv_groups;                   /* 16 */
+  int32_t feat_extract_norm;                 /* US_HUBERT_NORM_GROUP */
+  int32_t do_stable_layer_norm;              /* 0 */
+  float layer_norm_eps;                      /* 1e-5 */
+} us_hubert_config;
+int us_hubert_create(us_hubert_handle* out, const us_hubert_config* cfg);
+int us_hubert_destroy(us_hubert_handle h);
+int us_hubert_load_weight(us_hubert_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_hubert_num_weights(us_hubert_handle h);
+const char* us_hubert_weight_key(us_hubert_handle h, int i);
+const char* us_hubert_last_error(us_hubert_handle h);
+/* frames of a T-sample item: floor((L - k) / s) + 1 through the extractor's layers (320 samples per frame, 400 for the first, with the
+ * base values); US_EINVAL (negative) when T is shorter than the receptive field */
+int us_hubert_frames(us_hubert_handle h, int64_t T);
+size_t us_hubert_workspace_bytes(us_hubert_handle h, int B, int Tmax);
+/* wav [B][Tmax] (device); lengths: HOST int64 [B], the samples of each item, at least the receptive field (else US_EINVAL) and at most
+ * Tmax, or NULL for Tmax each.  Item b's rows are what the model gives for its own samples alone: the group norm's statistics run over its
+ * own steps, the positional convolution sees zeros past its last frame, attention runs over its own frames (this is not the behaviour of
+ * transformers' attention_mask); samples at or past its length are never read.
+ * normalize: the reader's F.layer_norm(x, x.shape) first, per item over its own samples.  n_layers_out in [0, n_layers]: stop after that
+ * many layers.  out [B][F][H]; hidden_states: NULL, or [B][n_layers_out + 1][F][H] receiving the state after 0 .. n_layers_out layers.  Rows
+ * at and past an item's frames are 0; nothing past the tensors is written. */
+int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out, float* out,
+                      float* hidden_states, void* workspace, size_t workspace_bytes, us_stream stream);
+
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102
  * `process_unit`) as handle-free device calls.  Every call only enqueues on `stream`, allocates nothing and takes device scratch of

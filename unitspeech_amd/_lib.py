@@ -56,6 +56,16 @@ class us_resample_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("orig_freq", "new_freq", "width")]
 
 
+US_HUBERT_MAX_CONV = 8
+US_HUBERT_NORM_GROUP, US_HUBERT_NORM_LAYER = 0, 1
+
+
+class us_hubert_config(C.Structure):
+    _fields_ = ([("n_conv", C.c_int32)] + [(n, C.c_int32 * US_HUBERT_MAX_CONV) for n in ("conv_dim", "conv_kernel", "conv_stride")] +
+                [(n, C.c_int32) for n in ("hidden_size", "n_heads", "intermediate_size", "n_layers", "pos_conv_kernel", "pos_conv_groups",
+                                          "feat_extract_norm", "do_stable_layer_norm")] + [("layer_norm_eps", C.c_float)])
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -146,6 +156,10 @@ SIGNATURES = {
     "us_resample_out_length": (C.c_int64, [C.c_void_p, C.c_int64]),
     "us_resample_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    "us_hubert_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_hubert_config)]),
+    "us_hubert_frames": (C.c_int, [C.c_void_p, C.c_int64]),
+    "us_hubert_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
@@ -165,8 +179,8 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_last_error": (C.c_char_p, [C.c_void_p]),
 }
-# what the five weight-table handles (csrc/handle.h) share
-for _p in ("frontend", "vocoder", "speaker", "mel", "resample"):
+# what the six weight-table handles (csrc/handle.h) share
+for _p in ("frontend", "vocoder", "speaker", "mel", "resample", "hubert"):
     SIGNATURES.update({
         f"us_{_p}_destroy": (C.c_int, [C.c_void_p]),
         f"us_{_p}_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

@@ -40,7 +40,9 @@ struct PlanarConvTile {       // what one workgroup of 256 threads multiplies
 // [32 mh, +32) and the NSUB 32-step sub-tiles from step 32 NSUB nh on.  Sub-tile n accumulates into acc[n][0 .. NCHAIN): MFMA s of
 // a K slice goes to chain s % NCHAIN, so with two chains no MFMA waits on the one before it, and the caller adds the chains up.
 // K slices of kPcBK are double-buffered in LDS: the next slice's global loads are in flight while this one is multiplied.
-template <int NSUB, int NCHAIN>
+// STRIDE > 1 is the strided convolution D[co][q] = sum P[j * Cin + ci][co] * in[ci][STRIDE * q + off + j * dil] (the HuBERT extractor); the
+// default multiplies by a compile-time 1, so every other instantiation's code is what it was.
+template <int NSUB, int NCHAIN, int STRIDE = 1>
 __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f32x16 (&acc)[NSUB][NCHAIN]) {
   constexpr int BN = 64 * NSUB, NX = BN / 16;
   __shared__ float As[2][kPcBK][kPcBM];
@@ -60,10 +62,10 @@ __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f3
     const bool live = kk < g.Kdim;
     const int j = live ? kk / g.Cin : 0, ci = live ? kk - j * g.Cin : 0;
     const float* row = in + (size_t)ci * g.T;
-    const int t0 = g.n0 + g.off + j * g.dil;
+    const int t0 = g.n0 * STRIDE + g.off + j * g.dil;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-      const int t = t0 + xc + 16 * i;
+      const int t = t0 + (xc + 16 * i) * STRIDE;
       xreg[i] = (live && t >= 0 && t < g.T) ? row[t] : 0.f;
     }
   };
