@@ -8,7 +8,8 @@
   --synthetic   seeded synthetic decoder weights and a synthetic (mel, units, durations, speaker embedding) tuple: runs the
                 fine-tuning loop itself (BASELINE.json configs[3]) without any downloaded model.  --hip_mel takes the mel from a seeded
                 waveform through the HIP mel front end instead of random numbers; --hip_hubert (with --hip_units) takes the dense features
-                from the HIP HuBERT encoder (seeded base-size weights) on a seeded waveform, resampled 22050 -> 16000 with --hip_resample.
+                from the HIP HuBERT encoder (seeded base-size weights) on a seeded waveform, resampled 22050 -> 16000 with --hip_resample;
+                --hip_wavlm takes spk_emb from the HIP WavLM-large (seeded) in front of the seeded HIP ECAPA-TDNN on that waveform.
   --features F  the OUTPUTS of the reference's pre-steps (finetune.py:86-128) from a `.pt` (torch.save of a dict) or `.npz` file, so the
                 speaker embedder / unit extractor can run wherever their checkpoints live and the adaptation here:
                   mel        [1, 80, L]   normalised to [-1, 1] as finetune.py:104 leaves it (or raw with "mel_is_normalized": False); or
@@ -18,6 +19,8 @@
                              normalised with mel_min / mel_max
                   spk_emb    [1, 256] or [1, 1, 256]   (divided by its norm here, :110); or  spk_hidden_states [L, 1, T, C], the
                              speaker encoder's upstream hidden states (ecapa_tdnn.py:262-264) + --speaker_encoder_checkpoint (:106-110)
+                             or  wav with --hip_wavlm + --speaker_encoder_path, the reference's whole embedder checkpoint: the waveform
+                             is brought to 16 kHz on the device and WavLM and the ECAPA-TDNN both run on HIP (:113-117)
                   duration   [1, Lu]      frames per unit (process_unit, :114)
                   cond_x     [1, 80, Lu]  the unit encoder's output (:123); or  unit [1, Lu] int64 + --unit_encoder_checkpoint (:66-79)
                   dense      [T, D]       in place of unit / duration: the unit extractor's dense features (:112), quantised and brought to
@@ -81,9 +84,12 @@ def load_features(args, cfg, base, device):
             raise SystemExit(f"--features {path}: `dense` has rows with non-finite values")
         d["unit"], d["duration"] = unit[:, :n].cpu(), duration[:, :n].cpu()
     hip_spk = bool(args.speaker_encoder_checkpoint) and "spk_emb" not in d and "spk_hidden_states" in d
+    hip_wavlm = getattr(args, "hip_wavlm", False) and bool(getattr(args, "speaker_encoder_path", None)) and "spk_emb" not in d and "wav" in d
+    if getattr(args, "hip_wavlm", False) and not hip_wavlm and "spk_emb" not in d:
+        raise SystemExit(f"--features {path}: --hip_wavlm needs `wav` in the file and --speaker_encoder_path (the whole embedder's checkpoint)")
     hip_mel = "mel" not in d and "wav" in d
     for k in ("mel", "spk_emb", "duration"):
-        if k not in d and not (k == "spk_emb" and hip_spk) and not (k == "mel" and hip_mel):
+        if k not in d and not (k == "spk_emb" and (hip_spk or hip_wavlm)) and not (k == "mel" and hip_mel):
             raise SystemExit(f"--features {path}: missing `{k}`" + (" (or `wav`)" if k == "mel" else ""))
 
     def scalar(name):
@@ -116,7 +122,18 @@ def load_features(args, cfg, base, device):
         raise SystemExit(f"--features: mel must be [1, {cfg.n_feats}, L], got {tuple(mel.shape)}")
     if not hip_mel and "mel_is_normalized" in d and not bool(d["mel_is_normalized"]):
         mel = (mel - mel_min) / (mel_max - mel_min) * 2 - 1                      # finetune.py:104
-    if hip_spk:
+    if hip_wavlm:
+        # finetune.py:113-117: the utterance at 16 kHz through the whole speaker embedder (WavLM, then the ECAPA-TDNN), over its norm
+        from unitspeech_amd.resample import Resample
+        from unitspeech_amd.speaker_encoder import load_speaker_embedder_checkpoint
+        rate = int(d["wav_sampling_rate"]) if "wav_sampling_rate" in d else SAMPLING_RATE
+        wav16 = d["wav"].float().reshape(1, -1).to(device)
+        if rate != 16000:
+            wav16 = Resample(rate, 16000).to(device)(wav16)
+        spk = load_speaker_embedder_checkpoint(args.speaker_encoder_path, device).embed_wav(wav16).reshape(1, 1, -1)
+        if spk.shape[-1] != cfg.spk_emb_dim:
+            raise SystemExit(f"--speaker_encoder_path: the embedder gives {spk.shape[-1]} elements, the decoder takes {cfg.spk_emb_dim}")
+    elif hip_spk:
         from unitspeech_amd.speaker_encoder import load_speaker_encoder_checkpoint
         hidden = d["spk_hidden_states"].float()
         spk_embedder = load_speaker_encoder_checkpoint(args.speaker_encoder_checkpoint, device, feat_dim=int(hidden.shape[-1]),
@@ -179,6 +196,13 @@ def main():
                     "speaker encoder's checkpoint ({'model': state_dict}, util.py:183-188); the embedding comes from the HIP ECAPA-TDNN")
     ap.add_argument("--hip_speaker_encoder", action="store_true", help="--synthetic: spk_emb from the HIP ECAPA-TDNN (seeded weights) on "
                     "synthetic upstream hidden states instead of a random vector")
+    ap.add_argument("--hip_wavlm", action="store_true", help="--synthetic: spk_emb from the HIP WavLM-large (seeded weights drawn on the device) in "
+                    "front of the seeded HIP ECAPA-TDNN, on a seeded waveform (at 22050 Hz and resampled on the device with --hip_resample); "
+                    "--features with `wav`: spk_emb from the whole embedder of --speaker_encoder_path")
+    ap.add_argument("--speaker_encoder_path", type=str, default=None, help="--features with `wav` and --hip_wavlm: the reference's speaker "
+                    "embedder checkpoint ({'model': state_dict} with its feature_extract.* keys); WavLM and the ECAPA-TDNN both run on HIP")
+    ap.add_argument("--wavlm_layers", type=int, default=24, help="--synthetic --hip_wavlm: encoder layers of the seeded WavLM (the trunk then "
+                    "takes that many + 1 hidden states); for short test runs")
     ap.add_argument("--hip_mel", action="store_true", help="--synthetic: the mel comes from the HIP mel front end on a seeded waveform (normalised "
                     "with mel_min / mel_max) instead of random numbers")
     ap.add_argument("--hip_resample", action="store_true", help="--features with `wav` at another `wav_sampling_rate` than 22050: resample it "
@@ -276,7 +300,33 @@ def main():
             if args.hip_hubert:
                 raise SystemExit("--hip_hubert needs --learned_frontend --hip_units (its features feed the unit quantiser)")
             duration = torch.full((1, Lu), 3.0, device=device)
-        if args.hip_speaker_encoder:
+        if args.hip_wavlm:
+            # finetune.py:113-117: spk_emb is the embedder's output for the reference utterance at 16 kHz over its norm: WavLM-large, every
+            # hidden state into the ECAPA-TDNN.  Here both at the reference's sizes with seeded weights on a seeded waveform.
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+            from wavlm_torch import large_config, synthetic_wavlm_state_dict
+            from unitspeech_amd.mel import synthetic_waveform
+            from unitspeech_amd.speaker_encoder import ECAPA_TDNN_SMALL, synthetic_ecapa_state_dict
+            from unitspeech_amd.wavlm import WavLMModel
+            if not 0 <= args.wavlm_layers <= 24:
+                raise SystemExit("--wavlm_layers must be between 0 and 24")
+            n16 = 400 + 320 * (L * 256 // 320 - 1)
+            if args.hip_resample:
+                from unitspeech_amd.resample import Resample
+                n22 = -(-n16 * 441 // 320)
+                wav16 = Resample(SAMPLING_RATE, 16000).to(device)(torch.from_numpy(synthetic_waveform(n22, args.ID & 0xffff, SAMPLING_RATE)).to(device))[:n16]
+            else:
+                wav16 = torch.from_numpy(synthetic_waveform(n16, args.ID & 0xffff, 16000)).to(device)
+            wcfg = dict(large_config(), num_hidden_layers=args.wavlm_layers)
+            wavlm = WavLMModel(**wcfg)
+            wavlm.load_state_dict(synthetic_wavlm_state_dict(wcfg, args.ID & 0xffff, device=device), assign=True)      # drawn on the device: no 1.2 GB upload
+            spk_embedder = ECAPA_TDNN_SMALL(feat_dim=1024, emb_dim=cfg.spk_emb_dim, feat_type="wavlm_large", feat_num=args.wavlm_layers + 1)
+            spk_embedder.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_ecapa_state_dict(spk_embedder.config(), 0).items()})
+            spk_embedder = spk_embedder.eval().attach_upstream(wavlm.eval(), normalize=True).to(device)
+            spk_emb = spk_embedder.embed_wav(wav16.reshape(1, -1)).reshape(1, 1, -1)
+            print(f"hip wavlm: {wav16.numel()} samples at 16 kHz -> {args.wavlm_layers + 1} hidden states of {wavlm.frames(wav16.numel())} x 1024 -> "
+                  f"spk_emb {spk_emb.shape[-1]}")
+        elif args.hip_speaker_encoder:
             # finetune.py:106-110: spk_emb is the ECAPA-TDNN's embedding of the reference utterance over its norm; here the HIP module
             # at the reference's sizes (WavLM-large: 25 hidden states of 1024) with seeded weights on 3 s of seeded hidden states
             from unitspeech_amd.speaker_encoder import synthetic_speaker_embedder, synthetic_hidden_states
@@ -287,6 +337,8 @@ def main():
             spk = torch.from_numpy(g.standard_normal((1, 1, cfg.spk_emb_dim), dtype=np.float32)).to(device)
             spk_emb = spk / spk.norm()
         mel_min, mel_max = torch.tensor(-11.5), torch.tensor(2.0)
+    elif args.hip_wavlm:
+        raise SystemExit("--hip_wavlm needs --synthetic (or --features with `wav` and --speaker_encoder_path)")
     elif args.hip_mel:
         raise SystemExit("--hip_mel needs --synthetic (with --features, put `wav` in the file)")
     else:

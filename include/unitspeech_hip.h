@@ -620,6 +620,55 @@ size_t us_hubert_workspace_bytes(us_hubert_handle h, int B, int Tmax);
 int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out, float* out,
                       float* hidden_states, void* workspace, size_t workspace_bytes, us_stream stream);
 
+/* ---- WavLM encoder (the upstream of the speaker embedder, ECAPA_TDNN_SMALL(feat_type="wavlm_large")), csrc/hubert.hip ---------------------
+ * transformers.WavLMModel in eval mode, in both published forms: feat_extract_norm = US_HUBERT_NORM_LAYER with do_stable_layer_norm = 1 and
+ * conv_bias = 1 (WavLM-large: every extractor layer is conv + bias, LayerNorm over channels, GELU; the encoder is pre-LN, so hidden state
+ * i < L is the un-normalised input of layer i and hidden state L is encoder.layer_norm of the stream), or US_HUBERT_NORM_GROUP with 0 and 0
+ * (WavLM-base and base-plus: HuBERT's schedule).  Any other combination of the three is US_EINVAL, as are the geometries us_hubert_create
+ * refuses, an odd num_buckets or one outside [4, 4096], and a max_bucket_distance not above num_buckets / 4.
+ * Attention adds WavLM's gated relative position bias: score = q.k d^-1/2 + gate[q] * rel_attn_embed[bucket(k - q)][head], with the gate
+ * a (b gru_rel_pos_const[head] - 1) + 2, a and b the sigmoids of the two sums of four of gru_rel_pos_linear(x_head), x the attention's
+ * input.  The delta -> bucket map is made on the host at create; from layer 0's rel_attn_embed a per-head table over delta in [-D, D] is
+ * formed, D the first saturated distance (778 at the default 320 / 800), and larger distances are clamped: no [F][F] array exists.
+ * Weights go in by transformers' state_dict keys (positional convolution folded, masked_spec_embed not taken), as for us_hubert_*, whose
+ * conventions and per-item semantics hold here too. */
+typedef struct us_wavlm* us_wavlm_handle;
+typedef struct us_wavlm_config {
+  int32_t n_conv;                            /* 7 */
+  int32_t conv_dim[US_HUBERT_MAX_CONV];      /* 512 x 7 */
+  int32_t conv_kernel[US_HUBERT_MAX_CONV];   /* 10, 3, 3, 3, 3, 2, 2 */
+  int32_t conv_stride[US_HUBERT_MAX_CONV];   /* 5, 2, 2, 2, 2, 2, 2 */
+  int32_t hidden_size;                       /* 1024 */
+  int32_t n_heads;                           /* 16 */
+  int32_t intermediate_size;                 /* 4096 */
+  int32_t n_layers;                          /* 24 */
+  int32_t pos_conv_kernel;                   /* 128 */
+  int32_t pos_conv_groups;                   /* 16 */
+  int32_t feat_extract_norm;                 /* US_HUBERT_NORM_LAYER */
+  int32_t do_stable_layer_norm;              /* 1 */
+  float layer_norm_eps;                      /* 1e-5 */
+  int32_t conv_bias;                         /* 1 */
+  int32_t num_buckets;                       /* 320 */
+  int32_t max_bucket_distance;               /* 800 */
+} us_wavlm_config;
+int us_wavlm_create(us_wavlm_handle* out, const us_wavlm_config* cfg);
+int us_wavlm_destroy(us_wavlm_handle h);
+int us_wavlm_load_weight(us_wavlm_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_wavlm_num_weights(us_wavlm_handle h);
+const char* us_wavlm_weight_key(us_wavlm_handle h, int i);
+const char* us_wavlm_last_error(us_wavlm_handle h);
+int us_wavlm_frames(us_wavlm_handle h, int64_t T);
+size_t us_wavlm_workspace_bytes(us_wavlm_handle h, int B, int Tmax);
+/* the bucket of delta = key - query in the handle's host map (|delta| beyond the first saturated distance is clamped to it) */
+int us_wavlm_position_bucket(us_wavlm_handle h, int64_t delta);
+/* The arguments and per-item semantics of us_hubert_forward.  hidden_states (or NULL): state l of item b is written at
+ * hidden_states + b * hs_item_stride + l * hs_layer_stride (floats), [F][H] each: ((n_layers_out + 1) F H, F H) is [B][n + 1][F][H],
+ * transformers' order, and (F H, B F H) is [n + 1][B][F][H], what us_speaker_forward reads.  Strides under which two states would overlap
+ * are US_EINVAL. */
+int us_wavlm_forward(us_wavlm_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out, float* out,
+                     float* hidden_states, int64_t hs_item_stride, int64_t hs_layer_stride, void* workspace, size_t workspace_bytes,
+                     us_stream stream);
+
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102
  * `process_unit`) as handle-free device calls.  Every call only enqueues on `stream`, allocates nothing and takes device scratch of

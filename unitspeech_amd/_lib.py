@@ -66,6 +66,10 @@ class us_hubert_config(C.Structure):
                                           "feat_extract_norm", "do_stable_layer_norm")] + [("layer_norm_eps", C.c_float)])
 
 
+class us_wavlm_config(C.Structure):
+    _fields_ = us_hubert_config._fields_ + [(n, C.c_int32) for n in ("conv_bias", "num_buckets", "max_bucket_distance")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -160,6 +164,11 @@ SIGNATURES = {
     "us_hubert_frames": (C.c_int, [C.c_void_p, C.c_int64]),
     "us_hubert_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_wavlm_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_wavlm_config)]),
+    "us_wavlm_frames": (C.c_int, [C.c_void_p, C.c_int64]),
+    "us_wavlm_position_bucket": (C.c_int, [C.c_void_p, C.c_int64]),
+    "us_wavlm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
@@ -179,8 +188,8 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_last_error": (C.c_char_p, [C.c_void_p]),
 }
-# what the six weight-table handles (csrc/handle.h) share
-for _p in ("frontend", "vocoder", "speaker", "mel", "resample", "hubert"):
+# what the seven weight-table handles (csrc/handle.h) share
+for _p in ("frontend", "vocoder", "speaker", "mel", "resample", "hubert", "wavlm"):
     SIGNATURES.update({
         f"us_{_p}_destroy": (C.c_int, [C.c_void_p]),
         f"us_{_p}_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

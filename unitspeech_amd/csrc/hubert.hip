@@ -16,6 +16,14 @@
 //  - hb_attn_kernel<DT>: softmax(Q^T K) V per (item, head, 64-query tile) with an online softmax: key / value tiles of 64 streamed through
 //    LDS, running maximum and sum in registers, scores of keys at or past the item's frames set to -inf, tiles without a live key skipped.
 // Every reduction has a fixed order and no tile depends on the batch: an item alone or in a batch, and repeated calls, give the same bits.
+//
+// The WavLM encoder (transformers.WavLMModel; us_wavlm_*) runs on the same kernels and host schedule.  Its large form has a layer-norm extractor
+// (every layer: convolution + bias, hb_ln_kernel over the channels with GELU) and a pre-LN encoder (x + attn(LN(x)), h + ffn(LN(h)), the residual
+// added in the GEMM's epilogue; hidden state i < L is the un-normalised stream, copied channel-last by hb_export_kernel, hidden state L is
+// encoder.layer_norm of it); its base form is HuBERT's schedule.  Both add the gated relative position bias in attention:
+//  - wl_gate_kernel: gate[item][head][frame] from gru_rel_pos_linear of the head's own channels of the attention's input.
+//  - wl_table_kernel (once per weight load): table[head][delta + D] = rel_attn_embed[bucket(delta)][head] over delta in [-D, D], D the first
+//    saturated distance of the host-made bucket map; wl_attn_kernel<DT> adds gate[q] * table[head][clamp(key - q)] to each score.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,9 +89,9 @@ __global__ __launch_bounds__(1024) void hb_wavstats_kernel(const float* __restri
   }
 }
 
-// ---- extractor layer 0: out[b][c][q] = sum_j w[c][j] * x[b][s q + j], x = (wav - mean) * rstd; 0 at and past the item's steps -------------------
+// ---- extractor layer 0: out[b][c][q] = (bias[c] +) sum_j w[c][j] * x[b][s q + j], x = (wav - mean) * rstd; 0 at and past the item's steps ------
 __global__ __launch_bounds__(256) void hb_conv0_kernel(const float* __restrict__ wav, const float* __restrict__ stats, const float* __restrict__ w,
-                                                       float* __restrict__ out, HbLens lens, int Tmax, int C, int T1) {
+                                                       const float* __restrict__ bias, float* __restrict__ out, HbLens lens, int Tmax, int C, int T1) {
   const int b = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
   if (q >= T1) return;
   const int k = lens.k[0], s = lens.s[0];
@@ -100,7 +108,7 @@ __global__ __launch_bounds__(256) void hb_conv0_kernel(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < kHbMaxK0; ++j)
       if (j < k) a = fmaf(wc[j], xr[j], a);
-    o[(size_t)c * T1] = a;
+    o[(size_t)c * T1] = bias && live ? a + bias[c] : a;
   }
 }
 
@@ -169,13 +177,14 @@ __global__ __launch_bounds__(256) void hb_gemm_kernel(HbGemmArgs a, HbLens lens)
 // ---- LayerNorm over the channel axis of a planar tensor, residual in front ---------------------------------------------------------------------
 // y[c][t] = ((x[c][t] + res[c][t]) - mean_t) * rstd_t * gamma[c] + beta[c] for t below the item's frames, 0 past them.  A workgroup is 32
 // columns (tid & 31) x 32 channel slices (tid >> 5): slice s adds up channels s, s + 32, ... in order, the 32 partials of a column are then
-// added in slice order.  e1 / e2 (optional): the same values channel-last, [T][C] per item, written 32 x 32 through LDS.
+// added in slice order.  e1 / e2 (optional): the same values channel-last, [T][C] per item, written 32 x 32 through LDS.  gelu: GELU
+// after the affine (the layer-norm extractor's layers).
 constexpr int kLnCols = 32, kLnSlices = 32;
 
 __global__ __launch_bounds__(1024) void hb_ln_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ e1,
                                                      float* __restrict__ e2, long long e1_bs, long long e2_bs, HbLens lens, int level, int C,
-                                                     int T, float eps) {
+                                                     int T, float eps, int gelu) {
   __shared__ float red[kLnSlices][kLnCols];
   __shared__ float tile[kLnCols][kLnSlices + 1];
   const int col = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -211,7 +220,10 @@ __global__ __launch_bounds__(1024) void hb_ln_kernel(const float* __restrict__ x
   for (int c0 = 0; c0 < C; c0 += kLnSlices) {
     const int c = c0 + sl;
     float o = 0.f;
-    if (live && c < C) o = fmaf((at(c) - mean) * rs, gamma[c], beta[c]);
+    if (live && c < C) {
+      o = fmaf((at(c) - mean) * rs, gamma[c], beta[c]);
+      if (gelu) o = hb_gelu(o);
+    }
     if (y && in && c < C) y[bo + (size_t)c * T + t] = o;
     if (e1 || e2) {
       __syncthreads();
@@ -227,6 +239,52 @@ __global__ __launch_bounds__(1024) void hb_ln_kernel(const float* __restrict__ x
   }
 }
 
+// ---- the channel-last copy of a planar tensor (the pre-LN encoder's un-normalised hidden states), 32 x 32 through LDS --------------------------
+// e1 / e2 [T][C] per item from x [C][T]; x already holds 0 past the item's frames.  grid: (time tiles, channel tiles, items)
+__global__ __launch_bounds__(1024) void hb_export_kernel(const float* __restrict__ x, float* __restrict__ e1, float* __restrict__ e2, long long e1_bs,
+                                                         long long e2_bs, int C, int T) {
+  __shared__ float tile[kLnCols][kLnSlices + 1];
+  const int col = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int b = blockIdx.z, t0 = blockIdx.x * kLnCols, c0 = blockIdx.y * kLnSlices;
+  tile[col][sl] = (t0 + col < T && c0 + sl < C) ? x[(size_t)b * C * T + (size_t)(c0 + sl) * T + t0 + col] : 0.f;
+  __syncthreads();
+  if (t0 + sl < T && c0 + col < C) {
+    const float q = tile[sl][col];
+    const size_t i = (size_t)(t0 + sl) * C + c0 + col;
+    if (e1) e1[(size_t)b * e1_bs + i] = q;
+    if (e2) e2[(size_t)b * e2_bs + i] = q;
+  }
+}
+
+// ---- WavLM's gate of the relative position bias, per (item, head, frame) ---------------------------------------------------------------------
+// p = w x_head + bias (8 values from the head's own d channels of the attention's input x [H][F]), a = sigmoid(p0 + p1 + p2 + p3),
+// b = sigmoid(p4 + .. + p7), gate = a (b cst[head] - 1) + 2.  One frame per lane, the channels in index order.  grid: (frame tiles, heads, items)
+__global__ __launch_bounds__(256) void wl_gate_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const float* __restrict__ cst, float* __restrict__ gate, int H, int d, int F) {
+  const int b = blockIdx.z, head = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= F) return;
+  const float* xr = x + ((size_t)b * H + (size_t)head * d) * F + t;
+  float p[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) p[j] = bias[j];
+#pragma unroll 8
+  for (int c = 0; c < d; ++c) {
+    const float v = xr[(size_t)c * F];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = fmaf(w[j * d + c], v, p[j]);
+  }
+  const float ga = 1.f / (1.f + expf(-(((p[0] + p[1]) + p[2]) + p[3])));
+  const float gb = 1.f / (1.f + expf(-(((p[4] + p[5]) + p[6]) + p[7])));
+  gate[((size_t)b * gridDim.y + head) * F + t] = fmaf(ga, fmaf(gb, cst[head], -1.f), 2.f);
+}
+
+// table[h][i] = rel_attn_embed[bucket[i]][h] for i = delta + D in [0, 2 D]
+__global__ __launch_bounds__(256) void wl_table_kernel(const float* __restrict__ emb, const int* __restrict__ bucket, float* __restrict__ table,
+                                                       int heads, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+  if (i < n) table[(size_t)h * n + i] = emb[(size_t)bucket[i] * heads + h];
+}
+
 // ---- attention ---------------------------------------------------------------------------------------------------------------------------------
 // qkv [3 H][F] planar per item (q already scaled); head h owns rows [h d, (h + 1) d) of each third.  A workgroup is 64 queries of one (item,
 // head), a wave 16 of them.  Per key tile of 64 (through LDS, K as [c][key] with rows of 80 floats, V with rows of 68: both conflict-free
@@ -235,13 +293,16 @@ __global__ __launch_bounds__(1024) void hb_ln_kernel(const float* __restrict__ x
 //   O^T[c][q]  += sum_key V[c][key] P^T[key][q]:  a lane's accumulator register r of key block ks IS P^T[16 ks + 4 (l >> 4) + r][q = l & 15],
 //                 the B operand of a k-step whose four keys are {16 ks + 4 g + r : g = l >> 4}; A reads V at those same keys (one float4).
 // So the probabilities never leave their registers.  The head dimension is padded to 16 DT with zero rows (d = 20: DT = 2).
+// BIAS (WavLM): the score gets + gate[q] * table[head][clamp(key - q, -D, D) + D] before the masking and the running maximum.  The 127
+// differences a 64 x 64 tile can hold are staged per key tile in two more rows of Ks; the gate is one register per lane.
 constexpr int kAtQ = 64, kAtK = 64, kAtKs = 80, kAtVs = 68;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int DT>
-__global__ __launch_bounds__(256) void hb_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out, HbLens lens, int level, int H, int d,
-                                                      int F, long long qkv_bs, long long out_bs) {
-  __shared__ float Ks[16 * DT][kAtKs];
+template <int DT, bool BIAS>
+__device__ __forceinline__ void hb_attn_body(const float* __restrict__ qkv, float* __restrict__ out, HbLens lens, int level, int H, int d,
+                                             int F, long long qkv_bs, long long out_bs, const float* __restrict__ gate,
+                                             const float* __restrict__ table, int D) {
+  __shared__ float Ks[16 * DT + (BIAS ? 2 : 0)][kAtKs];
   __shared__ __attribute__((aligned(16))) float Vs[16 * DT][kAtVs];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
   const int b = blockIdx.z, head = blockIdx.y, qt0 = blockIdx.x * kAtQ;
@@ -264,6 +325,10 @@ __global__ __launch_bounds__(256) void hb_attn_kernel(const float* __restrict__ 
     const int c = 4 * s + lg;
     qr[s] = (c < d && tq < n) ? Q[(size_t)c * F + tq] : 0.f;
   }
+  float* Bs = &Ks[16 * DT][0];                       // BIAS: table[key - query] for key - query = k0 - qt0 - 63 + i, i < 127
+  const float* __restrict__ tab = BIAS ? table + (size_t)head * (2 * D + 1) + D : nullptr;
+  const float gq = BIAS && tq < n ? gate[((size_t)b * gridDim.y + head) * F + tq] : 0.f;
+  const int bq = 63 - (wave * 16 + li) + lg * 4;
   f32x4 o[DT];
 #pragma unroll
   for (int ct = 0; ct < DT; ++ct) o[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -278,6 +343,7 @@ __global__ __launch_bounds__(256) void hb_attn_kernel(const float* __restrict__ 
       Ks[r][lane] = ok ? K[(size_t)r * F + key] : 0.f;
       Vs[r][lane] = ok ? V[(size_t)r * F + key] : 0.f;
     }
+    if (BIAS && tid < 127) Bs[tid] = tab[max(-D, min(D, k0 - qt0 - 63 + tid))];
     __syncthreads();
     f32x4 s[4];
 #pragma unroll
@@ -291,6 +357,7 @@ __global__ __launch_bounds__(256) void hb_attn_kernel(const float* __restrict__ 
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
+        if (BIAS) s[ks][r] = fmaf(gq, Bs[bq + ks * 16 + r], s[ks][r]);
         if (k0 + ks * 16 + lg * 4 + r >= n) s[ks][r] = -INFINITY;
         mx = fmaxf(mx, s[ks][r]);
       }
@@ -334,47 +401,79 @@ __global__ __launch_bounds__(256) void hb_attn_kernel(const float* __restrict__ 
     }
 }
 
+template <int DT>
+__global__ __launch_bounds__(256) void hb_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out, HbLens lens, int level, int H, int d,
+                                                      int F, long long qkv_bs, long long out_bs) {
+  hb_attn_body<DT, false>(qkv, out, lens, level, H, d, F, qkv_bs, out_bs, nullptr, nullptr, 0);
+}
+
+// the bias variant is held to four waves per SIMD (hb_attn_kernel<4>'s occupancy): left alone it takes 119 + 16 registers at DT = 4 and runs three
+template <int DT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void wl_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                                                                HbLens lens, int level, int H, int d, int F,
+                                                                                                long long qkv_bs, long long out_bs,
+                                                                                                const float* __restrict__ gate,
+                                                                                                const float* __restrict__ table, int D) {
+  hb_attn_body<DT, true>(qkv, out, lens, level, H, d, F, qkv_bs, out_bs, gate, table, D);
+}
+
 struct HbLayer {
   PlanarConv qkv, out, ff1, ff2;
   float* qkv_w = nullptr;     // [3 H][H]: q | k | v
   float* qkv_b = nullptr;     // [3 H]
 };
 
+// what us_hubert and us_wavlm share: the configuration, the weight table and the packed GEMM operands
+struct HbModel : WeightTable {
+  us_hubert_config cfg{};
+  const char* abi = "us_hubert";           // the prefix of the entry points' names in messages
+  int d = 0, cg = 0;                       // head dimension; channels per positional-convolution group
+  std::vector<PlanarConv> ext;             // extractor layers 1 .. n_conv - 1 (index i - 1)
+  PlanarConv proj, pos;                    // pos: one group's geometry, `packed` holds all groups
+  std::vector<HbLayer> layers;
+  bool allocated = false;                  // device tensors exist (made by the first load, so creating a handle touches no device)
+  bool dirty = true;                       // a weight changed since the derived forms were made
+  // WavLM only
+  bool wavlm = false;
+  int conv_bias = 0, num_buckets = 0, max_distance = 0;
+  int D = 0;                               // the first saturated distance: bucket(delta) is constant for |delta| >= D on either side
+  std::vector<int> bucket;                 // bucket(delta) for delta = i - D, i in [0, 2 D]
+  int* bucket_dev = nullptr;
+  float* table = nullptr;                  // [heads][2 D + 1]: rel_attn_embed[bucket(delta)][head]
+  bool layer_ext() const { return cfg.feat_extract_norm == US_HUBERT_NORM_LAYER; }
+  bool pre_ln() const { return cfg.do_stable_layer_norm != 0; }
+};
+
 }  // namespace
 }  // namespace us
 
-struct us_hubert : us::WeightTable {
-  us_hubert_config cfg{};
-  int d = 0, cg = 0;                       // head dimension; channels per positional-convolution group
-  std::vector<us::PlanarConv> ext;         // extractor layers 1 .. n_conv - 1 (index i - 1)
-  us::PlanarConv proj, pos;                // pos: one group's geometry, `packed` holds all groups
-  std::vector<us::HbLayer> layers;
-  bool allocated = false;                  // device tensors exist (made by the first load, so creating a handle touches no device)
-  bool dirty = true;                       // a weight changed since the derived forms were made
-};
+struct us_hubert : us::HbModel {};
+struct us_wavlm : us::HbModel {};
 
 namespace us {
 namespace {
 
 std::string hb_conv_key(int i) { return "feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight"; }
+std::string hb_conv_prefix(int i) { return "feature_extractor.conv_layers." + std::to_string(i) + "."; }
 std::string hb_layer_key(int i) { return "encoder.layers." + std::to_string(i) + "."; }
 
-void hb_add_affine(us_hubert* h, const std::string& p, int n) {
+void hb_add_affine(HbModel* h, const std::string& p, int n) {
   h->add(p + ".weight", {n});
   h->add(p + ".bias", {n});
 }
-void hb_add_linear(us_hubert* h, const std::string& p, int out, int in) {
+void hb_add_linear(HbModel* h, const std::string& p, int out, int in) {
   h->add(p + ".weight", {out, in});
   h->add(p + ".bias", {out});
 }
 
-// transformers.HubertModel's registration order (the positional convolution's weight in its folded form: g v / |v|)
-void hubert_keys(us_hubert* h) {
+// transformers.HubertModel's / WavLMModel's registration order (the positional convolution's weight in its folded form: g v / |v|)
+void hubert_keys(HbModel* h) {
   const auto& c = h->cfg;
   const int H = c.hidden_size, I = c.intermediate_size, Cl = c.conv_dim[c.n_conv - 1];
   for (int i = 0; i < c.n_conv; ++i) {
     h->add(hb_conv_key(i), {c.conv_dim[i], i ? c.conv_dim[i - 1] : 1, c.conv_kernel[i]});
-    if (i == 0) hb_add_affine(h, "feature_extractor.conv_layers.0.layer_norm", c.conv_dim[0]);
+    if (h->conv_bias) h->add(hb_conv_prefix(i) + "conv.bias", {c.conv_dim[i]});
+    if (i == 0 || h->layer_ext()) hb_add_affine(h, hb_conv_prefix(i) + "layer_norm", c.conv_dim[i]);
   }
   hb_add_affine(h, "feature_projection.layer_norm", Cl);
   hb_add_linear(h, "feature_projection.projection", H, Cl);
@@ -383,7 +482,12 @@ void hubert_keys(us_hubert* h) {
   hb_add_affine(h, "encoder.layer_norm", H);
   for (int i = 0; i < c.n_layers; ++i) {
     const std::string p = hb_layer_key(i);
+    if (h->wavlm) h->add(p + "attention.gru_rel_pos_const", {1, c.n_heads, 1, 1});
     for (const char* n : {"k_proj", "v_proj", "q_proj", "out_proj"}) hb_add_linear(h, p + "attention." + n, H, H);
+    if (h->wavlm) {
+      hb_add_linear(h, p + "attention.gru_rel_pos_linear", 8, h->d);
+      if (i == 0) h->add(p + "attention.rel_attn_embed.weight", {h->num_buckets, c.n_heads});
+    }
     hb_add_affine(h, p + "layer_norm", H);
     hb_add_linear(h, p + "feed_forward.intermediate_dense", I, H);
     hb_add_linear(h, p + "feed_forward.output_dense", H, I);
@@ -391,7 +495,7 @@ void hubert_keys(us_hubert* h) {
   }
 }
 
-void hb_geometry(us_hubert* h) {
+void hb_geometry(HbModel* h) {
   const auto& c = h->cfg;
   const int H = c.hidden_size, I = c.intermediate_size;
   h->ext.resize(c.n_conv - 1);
@@ -411,8 +515,28 @@ void hb_geometry(us_hubert* h) {
   }
 }
 
+// WavLM's T5-style bucket of delta = key - query: num_buckets / 2 per sign, exact below num_buckets / 4, logarithmic up to max_distance,
+// clamped to the last bucket from there
+int wl_bucket(int num_buckets, int max_distance, long long delta) {
+  const int nb = num_buckets / 2, max_exact = nb / 2;
+  const int r = delta > 0 ? nb : 0;
+  const long long a = delta < 0 ? -delta : delta;
+  if (a < max_exact) return r + (int)a;
+  const double v = std::log((double)a / max_exact) / std::log((double)max_distance / max_exact) * (nb - max_exact);
+  return r + (int)std::min<long long>(max_exact + (long long)v, nb - 1);
+}
+
+// the delta -> bucket map over [-D, D], D the first distance whose bucket is the last one (at most max_distance)
+void wl_bucket_map(HbModel* h) {
+  int D = 0;
+  while (D < h->max_distance && wl_bucket(h->num_buckets, h->max_distance, -D) != h->num_buckets / 2 - 1) ++D;
+  h->D = D;
+  h->bucket.resize(2 * D + 1);
+  for (int i = 0; i <= 2 * D; ++i) h->bucket[i] = wl_bucket(h->num_buckets, h->max_distance, i - D);
+}
+
 // every tensor the forward reads, at once: after the first load neither a load nor a forward allocates
-hipError_t hb_alloc(us_hubert* h) {
+hipError_t hb_alloc(HbModel* h) {
   hipError_t e = hipSuccess;
   auto alloc = [&](float** p, size_t n) {
     if (e == hipSuccess && !*p) e = hipMalloc(p, std::max<size_t>(n, 1) * sizeof(float));
@@ -430,12 +554,18 @@ hipError_t hb_alloc(us_hubert* h) {
     alloc(&l.qkv_w, 3 * H * H);
     alloc(&l.qkv_b, 3 * H);
   }
+  if (h->wavlm) {
+    const size_t n = h->bucket.size();
+    alloc(&h->table, n * h->cfg.n_heads);
+    if (e == hipSuccess && !h->bucket_dev) e = hipMalloc(&h->bucket_dev, n * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(h->bucket_dev, h->bucket.data(), n * sizeof(int), hipMemcpyHostToDevice);
+  }
   h->allocated = e == hipSuccess;
   return e;
 }
 
-// the packed GEMM weights (and the q | k | v concatenation) from the loaded tensors
-hipError_t hb_prepare(us_hubert* h, hipStream_t s) {
+// the packed GEMM weights (and the q | k | v concatenation, and WavLM's per-head bias table) from the loaded tensors
+hipError_t hb_prepare(HbModel* h, hipStream_t s) {
   auto W = [&](const std::string& k) { return h->w.at(k).dev; };
   const auto& c = h->cfg;
   const size_t H = (size_t)c.hidden_size;
@@ -460,6 +590,11 @@ hipError_t hb_prepare(us_hubert* h, hipStream_t s) {
     l.ff1.pack(W(hb_layer_key(i) + "feed_forward.intermediate_dense.weight"), s);
     l.ff2.pack(W(hb_layer_key(i) + "feed_forward.output_dense.weight"), s);
   }
+  if (h->wavlm && c.n_layers > 0) {
+    const int n = 2 * h->D + 1;
+    hipLaunchKernelGGL(wl_table_kernel, dim3((n + 255) / 256, c.n_heads), dim3(256), 0, s, W("encoder.layers.0.attention.rel_attn_embed.weight"),
+                       h->bucket_dev, h->table, c.n_heads, n);
+  }
   h->dirty = false;
   return hipGetLastError();
 }
@@ -482,10 +617,11 @@ long long hb_receptive_field(const us_hubert_config& c) {
 size_t hb_pad(size_t n) { return (n + 63) / 64 * 64; }
 
 struct HbPlan {                 // float offsets into the 256-byte aligned workspace
-  size_t stats, a, b, x0, p, x, x1, y, qkv, att, ff, total;
+  size_t stats, a, b, x0, p, x, x1, y, qkv, att, ff, gate, total;
 };
 
-HbPlan hb_plan(const us_hubert_config& c, int B, int Tmax) {
+HbPlan hb_plan(const HbModel* h, int B, int Tmax) {
+  const us_hubert_config& c = h->cfg;
   HbPlan p{};
   size_t o = 0;
   auto take = [&](size_t n) { const size_t at = o; o += hb_pad(n); return at; };
@@ -495,6 +631,7 @@ HbPlan hb_plan(const us_hubert_config& c, int B, int Tmax) {
     const size_t n = (size_t)B * ch * (size_t)hb_steps(c, Tmax, std::min(i + 1, c.n_conv));
     (i % 2 == 0 ? ea : eb) = std::max(i % 2 == 0 ? ea : eb, n);
   }
+  if (h->layer_ext()) ea = eb = std::max(ea, eb);       // every layer is a convolution into one and a LayerNorm into the other
   const size_t bf = (size_t)B * (size_t)hb_steps(c, Tmax, c.n_conv), H = (size_t)c.hidden_size;
   p.stats = take(2 * (size_t)B);
   p.a = take(ea);
@@ -507,6 +644,7 @@ HbPlan hb_plan(const us_hubert_config& c, int B, int Tmax) {
   p.qkv = take(bf * 3 * H);
   p.att = take(bf * H);
   p.ff = take(bf * (size_t)c.intermediate_size);
+  p.gate = take(h->wavlm ? bf * (size_t)c.n_heads : 0);
   p.total = o;
   return p;
 }
@@ -537,10 +675,22 @@ void hb_gemm(hipStream_t s, const HbGemm& g, const HbLens& lens, int nb) {
   }
 }
 
-void hb_attn(hipStream_t s, const float* qkv, float* out, const HbLens& lens, int level, int H, int heads, int d, int F, int nb) {
+// gate / table: null for plain attention (HuBERT), else WavLM's gated relative position bias
+void hb_attn(hipStream_t s, const float* qkv, float* out, const HbLens& lens, int level, int H, int heads, int d, int F, int nb, const float* gate,
+             const float* table, int D) {
   const dim3 grid((F + kAtQ - 1) / kAtQ, heads, nb);
   const long long qb = 3ll * H * F, ob = (long long)H * F;
-  switch ((d + 15) / 16) {
+  const int dt = (d + 15) / 16;
+  if (gate) {
+    switch (dt) {
+      case 1: hipLaunchKernelGGL(wl_attn_kernel<1>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob, gate, table, D); break;
+      case 2: hipLaunchKernelGGL(wl_attn_kernel<2>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob, gate, table, D); break;
+      case 3: hipLaunchKernelGGL(wl_attn_kernel<3>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob, gate, table, D); break;
+      default: hipLaunchKernelGGL(wl_attn_kernel<4>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob, gate, table, D); break;
+    }
+    return;
+  }
+  switch (dt) {
     case 1: hipLaunchKernelGGL(hb_attn_kernel<1>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob); break;
     case 2: hipLaunchKernelGGL(hb_attn_kernel<2>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob); break;
     case 3: hipLaunchKernelGGL(hb_attn_kernel<3>, grid, dim3(256), 0, s, qkv, out, lens, level, H, d, F, qb, ob); break;
@@ -548,47 +698,35 @@ void hb_attn(hipStream_t s, const float* qkv, float* out, const HbLens& lens, in
   }
 }
 
-}  // namespace
-}  // namespace us
-
-extern "C" {
-
-using namespace us;
-
-int us_hubert_create(us_hubert_handle* out, const us_hubert_config* cfg) {
-  if (!out || !cfg) return WeightTable::fail(nullptr, US_EINVAL, "us_hubert_create: null argument");
-  const auto& c = *cfg;
-  auto bad = [](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, "us_hubert_create: " + m); };
-  if (c.feat_extract_norm != US_HUBERT_NORM_GROUP) return bad("only the group-norm feature extractor (feat_extract_norm = \"group\") is built");
-  if (c.do_stable_layer_norm) return bad("the pre-LN encoder (do_stable_layer_norm) is not built");
-  if (c.n_conv < 1 || c.n_conv > kHbMaxConv) return bad("1 to 8 feature-extractor layers");
+// the checks us_hubert_create and us_wavlm_create share; "" when the geometry is built
+std::string hb_check_geometry(const us_hubert_config& c) {
+  if (c.n_conv < 1 || c.n_conv > kHbMaxConv) return "1 to 8 feature-extractor layers";
   for (int i = 0; i < c.n_conv; ++i) {
     if (c.conv_dim[i] < 1 || c.conv_dim[i] > 8192 || c.conv_kernel[i] < 1 || c.conv_kernel[i] > 64 || c.conv_stride[i] < 1)
-      return bad("bad conv_dim / conv_kernel / conv_stride at layer " + std::to_string(i));
+      return "bad conv_dim / conv_kernel / conv_stride at layer " + std::to_string(i);
     if (i == 0 ? c.conv_kernel[0] > kHbMaxK0 || c.conv_stride[0] > 64 : c.conv_stride[i] > 4)
-      return bad("layer 0 takes at most 16 taps, the others a stride of at most 4");
+      return "layer 0 takes at most 16 taps, the others a stride of at most 4";
   }
   if (c.hidden_size < 1 || c.hidden_size > 8192 || c.intermediate_size < 1 || c.intermediate_size > 32768 || c.n_layers < 0 || c.n_layers > 64)
-    return bad("bad hidden_size / intermediate_size / n_layers");
-  if (c.n_heads < 1 || c.hidden_size % c.n_heads != 0) return bad("hidden_size must be divisible by the number of heads");
+    return "bad hidden_size / intermediate_size / n_layers";
+  if (c.n_heads < 1 || c.hidden_size % c.n_heads != 0) return "hidden_size must be divisible by the number of heads";
   const int d = c.hidden_size / c.n_heads;
-  if (d > 64 || d % 4 != 0) return bad("the head dimension must be a multiple of 4, at most 64 (got " + std::to_string(d) + ")");
-  if (c.pos_conv_groups < 1 || c.hidden_size % c.pos_conv_groups != 0) return bad("hidden_size must be divisible by the positional convolution's groups");
-  if (c.pos_conv_kernel < 1 || c.pos_conv_kernel > 1024) return bad("bad positional convolution kernel");
-  if (!(c.layer_norm_eps > 0.f)) return bad("layer_norm_eps must be positive");
-  auto* h = new us_hubert();
-  h->cfg = c;
-  h->d = d;
-  h->cg = c.hidden_size / c.pos_conv_groups;
+  if (d > 64 || d % 4 != 0) return "the head dimension must be a multiple of 4, at most 64 (got " + std::to_string(d) + ")";
+  if (c.pos_conv_groups < 1 || c.hidden_size % c.pos_conv_groups != 0) return "hidden_size must be divisible by the positional convolution's groups";
+  if (c.pos_conv_kernel < 1 || c.pos_conv_kernel > 1024) return "bad positional convolution kernel";
+  if (!(c.layer_norm_eps > 0.f)) return "layer_norm_eps must be positive";
+  return "";
+}
+
+void hb_init(HbModel* h) {
+  h->d = h->cfg.hidden_size / h->cfg.n_heads;
+  h->cg = h->cfg.hidden_size / h->cfg.pos_conv_groups;
   (void)hipGetDevice(&h->device);
   hubert_keys(h);
   hb_geometry(h);
-  *out = h;
-  return US_OK;
 }
 
-int us_hubert_destroy(us_hubert_handle h) {
-  if (!h) return US_OK;
+void hb_release(HbModel* h) {
   h->free_weights();
   for (auto& c : h->ext) c.release();
   h->proj.release();
@@ -601,53 +739,50 @@ int us_hubert_destroy(us_hubert_handle h) {
     if (l.qkv_w) (void)hipFree(l.qkv_w);
     if (l.qkv_b) (void)hipFree(l.qkv_b);
   }
-  delete h;
-  return US_OK;
+  if (h->bucket_dev) (void)hipFree(h->bucket_dev);
+  if (h->table) (void)hipFree(h->table);
 }
 
-int us_hubert_num_weights(us_hubert_handle h) { return h ? h->num() : 0; }
-const char* us_hubert_weight_key(us_hubert_handle h, int i) { return h ? h->key(i) : nullptr; }
-const char* us_hubert_last_error(us_hubert_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
-
-int us_hubert_load_weight(us_hubert_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
+int hb_load_weight(HbModel* h, const char* what, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
   Weight* w;
-  int rc = WeightTable::find(h, "us_hubert_load_weight", key, data, shape, ndim, &w);
+  int rc = WeightTable::find(h, what, key, data, shape, ndim, &w);
   if (rc != US_OK) return rc;
   hipError_t e;
-  if (!h->allocated && (e = hb_alloc(h)) != hipSuccess) return h->hip("us_hubert_load_weight: hipMalloc", e);
+  if (!h->allocated && (e = hb_alloc(h)) != hipSuccess) return h->hip((std::string(what) + ": hipMalloc").c_str(), e);
   if ((rc = h->copy(*w, data, static_cast<hipStream_t>(stream))) != US_OK) return rc;      // hb_alloc made w->dev: no allocation here
   w->loaded = true;
   h->dirty = true;
   return US_OK;
 }
 
-int us_hubert_frames(us_hubert_handle h, int64_t T) {
-  if (!h) return WeightTable::fail(nullptr, US_EINVAL, "us_hubert_frames: null handle");
+int hb_frames(HbModel* h, const char* what, int64_t T) {
+  if (!h) return WeightTable::fail(nullptr, US_EINVAL, std::string(what) + ": null handle");
   const long long f = T > 0 ? hb_steps(h->cfg, T, h->cfg.n_conv) : 0;
   if (f < 1 || f >= (1ll << 31))
-    return h->fail(US_EINVAL, "us_hubert_frames: " + std::to_string((long long)T) + " samples are fewer than the receptive field (" +
+    return h->fail(US_EINVAL, std::string(what) + ": " + std::to_string((long long)T) + " samples are fewer than the receptive field (" +
                                   std::to_string(hb_receptive_field(h->cfg)) + "), or too many");
   return (int)f;
 }
 
-size_t us_hubert_workspace_bytes(us_hubert_handle h, int B, int Tmax) {
+size_t hb_workspace_bytes(HbModel* h, int B, int Tmax) {
   if (!h || B <= 0 || Tmax <= 0 || hb_steps(h->cfg, Tmax, h->cfg.n_conv) < 1) return 0;
-  return hb_plan(h->cfg, B, Tmax).total * sizeof(float) + 256;
+  return hb_plan(h, B, Tmax).total * sizeof(float) + 256;
 }
 
-int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out, float* out,
-                      float* hidden_states, void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (!h || !wav || !out || B <= 0 || Tmax <= 0) return WeightTable::fail(h, US_EINVAL, "us_hubert_forward: bad argument");
+// hidden state l of item b starts at hidden_states + b * hs_bs + l * hs_ls (floats)
+int hb_forward(HbModel* h, const std::string& what, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out,
+               float* out, float* hidden_states, long long hs_bs, long long hs_ls, void* workspace, size_t workspace_bytes, us_stream stream) {
+  if (!h || !wav || !out || B <= 0 || Tmax <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
   const auto& c = h->cfg;
   if (n_layers_out < 0 || n_layers_out > c.n_layers)
-    return h->fail(US_EINVAL, "us_hubert_forward: n_layers_out must be between 0 and the configuration's " + std::to_string(c.n_layers) + " layers");
+    return h->fail(US_EINVAL, what + ": n_layers_out must be between 0 and the configuration's " + std::to_string(c.n_layers) + " layers");
   const long long field = hb_receptive_field(c);
   if (Tmax < field)
-    return h->fail(US_EINVAL, "us_hubert_forward: Tmax = " + std::to_string(Tmax) + " is shorter than the receptive field (" + std::to_string(field) +
+    return h->fail(US_EINVAL, what + ": Tmax = " + std::to_string(Tmax) + " is shorter than the receptive field (" + std::to_string(field) +
                                   " samples)");
   for (int b = 0; lengths && b < B; ++b)
     if (lengths[b] < field || lengths[b] > Tmax)
-      return h->fail(US_EINVAL, "us_hubert_forward: lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
+      return h->fail(US_EINVAL, what + ": lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
                                     " must be at least the receptive field (" + std::to_string(field) + " samples) and at most Tmax");
   const int H = c.hidden_size, I = c.intermediate_size, nl = c.n_conv;
   int Tl[kHbMaxConv + 1];                 // buffer widths: the steps of a Tmax-sample item after each layer
@@ -659,21 +794,28 @@ int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengt
   }
   const int F = Tl[nl];
   big = std::max(big, (long long)std::max(3 * H, I) * F);
-  if (big >= (1ll << 31)) return h->fail(US_EINVAL, "us_hubert_forward: channels * steps of one item too large");
-  const int rc = h->all_loaded("us_hubert_forward");
+  if (big >= (1ll << 31)) return h->fail(US_EINVAL, what + ": channels * steps of one item too large");
+  const size_t fh = (size_t)F * H;
+  if (hidden_states) {
+    const long long f = (long long)fh, n1 = n_layers_out + 1;
+    const bool items_outer = hs_ls >= f && hs_bs >= n1 * hs_ls, layers_outer = hs_bs >= f && hs_ls >= (long long)B * hs_bs;
+    if (!items_outer && !layers_outer)
+      return h->fail(US_EINVAL, what + ": the hidden states' item and layer strides must describe [B][n + 1][F][H] or [n + 1][B][F][H] without overlap");
+  }
+  const int rc = h->all_loaded(what.c_str());
   if (rc != US_OK) return rc;
-  if (!workspace || workspace_bytes < us_hubert_workspace_bytes(h, B, Tmax))
-    return h->fail(US_EWORKSPACE, "us_hubert_forward: workspace too small (us_hubert_workspace_bytes)");
+  if (!workspace || workspace_bytes < hb_workspace_bytes(h, B, Tmax))
+    return h->fail(US_EWORKSPACE, what + ": workspace too small (" + h->abi + "_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->dirty) {
     const hipError_t e = hb_prepare(h, s);
-    if (e != hipSuccess) return h->hip("us_hubert_forward: preparing the weights", e);
+    if (e != hipSuccess) return h->hip((what + ": preparing the weights").c_str(), e);
   }
-  const HbPlan p = hb_plan(c, B, Tmax);
+  const HbPlan p = hb_plan(h, B, Tmax);
   float* base = ws_align(workspace);
   auto W = [&](const std::string& k) { return h->w.at(k).dev; };
-  const size_t fh = (size_t)F * H;
-  const long long hs_bs = (long long)(n_layers_out + 1) * F * H;
+  auto Wopt = [&](const std::string& k) { return h->conv_bias ? h->w.at(k).dev : nullptr; };
+  const bool pre_ln = h->pre_ln();
   for (int b0 = 0; b0 < B; b0 += kHbItems) {
     const int nb = std::min(kHbItems, B - b0);
     HbLens lens{};
@@ -688,26 +830,54 @@ int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengt
       stats = base + p.stats + 2 * (size_t)b0;
       hipLaunchKernelGGL(hb_wavstats_kernel, dim3(nb), dim3(1024), 0, s, x, stats, lens, Tmax);
     }
+    // LayerNorm over the channels of a planar [C][T] tensor of the items at hand; e1 / e2: channel-last copies
+    auto ln_launch = [&](const float* in, const float* res, const std::string& key, float* y, float* e1, float* e2, long long e1_bs, int level, int C,
+                         int T, float eps, int gelu) {
+      hipLaunchKernelGGL(hb_ln_kernel, dim3((T + kLnCols - 1) / kLnCols, nb), dim3(1024), 0, s, in, res, W(key + ".weight"), W(key + ".bias"), y, e1, e2,
+                         e1_bs, (long long)fh, lens, level, C, T, eps, gelu);
+    };
     // the feature extractor
     float* eb[2] = {base + p.a, base + p.b};
     float* cur = eb[0] + (size_t)b0 * c.conv_dim[0] * Tl[1];
-    hipLaunchKernelGGL(hb_conv0_kernel, dim3((Tl[1] + 255) / 256, nb), dim3(256), 0, s, x, stats, W(hb_conv_key(0)), cur, lens, Tmax, c.conv_dim[0],
-                       Tl[1]);
-    hipLaunchKernelGGL(hb_gn_gelu_kernel, dim3(c.conv_dim[0], nb), dim3(256), 0, s, cur, W("feature_extractor.conv_layers.0.layer_norm.weight"),
-                       W("feature_extractor.conv_layers.0.layer_norm.bias"), lens, c.conv_dim[0], Tl[1]);
-    for (int i = 1; i < nl; ++i) {
-      float* nxt = eb[i & 1] + (size_t)b0 * c.conv_dim[i] * Tl[i + 1];
-      HbGemm g{&h->ext[i - 1], cur, nullptr, nullptr, nxt, Tl[i], Tl[i + 1]};
-      g.stride = c.conv_stride[i]; g.gelu = 1; g.level = i + 1;
-      hb_gemm(s, g, lens, nb);
-      cur = nxt;
-    }
-    // the feature projection
+    const float* feat;                    // the feature projection's normalised input
     const int Cl = c.conv_dim[nl - 1];
-    float* nrm = eb[nl & 1] + (size_t)b0 * Cl * F;
-    hipLaunchKernelGGL(hb_ln_kernel, dim3((F + kLnCols - 1) / kLnCols, nb), dim3(1024), 0, s, cur, (const float*)nullptr,
-                       W("feature_projection.layer_norm.weight"), W("feature_projection.layer_norm.bias"), nrm, (float*)nullptr, (float*)nullptr, 0ll,
-                       0ll, lens, nl, Cl, F, c.layer_norm_eps);
+    hipLaunchKernelGGL(hb_conv0_kernel, dim3((Tl[1] + 255) / 256, nb), dim3(256), 0, s, x, stats, W(hb_conv_key(0)), Wopt(hb_conv_prefix(0) + "conv.bias"),
+                       cur, lens, Tmax, c.conv_dim[0], Tl[1]);
+    if (h->layer_ext()) {                 // conv (+ bias) into one buffer, LayerNorm over channels + GELU into the other
+      int at = 0;                         // the buffer `cur` lies in
+      auto other = [&](int ch, int T) {
+        at ^= 1;
+        return eb[at] + (size_t)b0 * ch * T;
+      };
+      for (int i = 0; i < nl; ++i) {
+        if (i > 0) {
+          float* nxt = other(c.conv_dim[i], Tl[i + 1]);
+          HbGemm g{&h->ext[i - 1], cur, Wopt(hb_conv_prefix(i) + "conv.bias"), nullptr, nxt, Tl[i], Tl[i + 1]};
+          g.stride = c.conv_stride[i]; g.level = i + 1;
+          hb_gemm(s, g, lens, nb);
+          cur = nxt;
+        }
+        float* nrm = other(c.conv_dim[i], Tl[i + 1]);
+        ln_launch(cur, nullptr, hb_conv_prefix(i) + "layer_norm", nrm, nullptr, nullptr, 0ll, i + 1, c.conv_dim[i], Tl[i + 1], 1e-5f, 1);
+        cur = nrm;
+      }
+      float* nrm = other(Cl, F);
+      ln_launch(cur, nullptr, "feature_projection.layer_norm", nrm, nullptr, nullptr, 0ll, nl, Cl, F, c.layer_norm_eps, 0);
+      feat = nrm;
+    } else {
+      hipLaunchKernelGGL(hb_gn_gelu_kernel, dim3(c.conv_dim[0], nb), dim3(256), 0, s, cur, W("feature_extractor.conv_layers.0.layer_norm.weight"),
+                         W("feature_extractor.conv_layers.0.layer_norm.bias"), lens, c.conv_dim[0], Tl[1]);
+      for (int i = 1; i < nl; ++i) {
+        float* nxt = eb[i & 1] + (size_t)b0 * c.conv_dim[i] * Tl[i + 1];
+        HbGemm g{&h->ext[i - 1], cur, Wopt(hb_conv_prefix(i) + "conv.bias"), nullptr, nxt, Tl[i], Tl[i + 1]};
+        g.stride = c.conv_stride[i]; g.gelu = 1; g.level = i + 1;
+        hb_gemm(s, g, lens, nb);
+        cur = nxt;
+      }
+      float* nrm = eb[nl & 1] + (size_t)b0 * Cl * F;
+      ln_launch(cur, nullptr, "feature_projection.layer_norm", nrm, nullptr, nullptr, 0ll, nl, Cl, F, c.layer_norm_eps, 0);
+      feat = nrm;
+    }
     float* X0 = base + p.x0 + b0 * fh;
     float* P = base + p.p + b0 * fh;
     float* X = base + p.x + b0 * fh;
@@ -716,34 +886,80 @@ int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengt
     float* QKV = base + p.qkv + 3 * b0 * fh;
     float* ATT = base + p.att + b0 * fh;
     float* FF = base + p.ff + (size_t)b0 * F * I;
+    float* G = h->wavlm ? base + p.gate + (size_t)b0 * c.n_heads * F : nullptr;
     {
-      HbGemm g{&h->proj, nrm, W("feature_projection.projection.bias"), nullptr, X0, F, F};
+      HbGemm g{&h->proj, feat, W("feature_projection.projection.bias"), nullptr, X0, F, F};
       g.level = nl;
       hb_gemm(s, g, lens, nb);
     }
-    // x + gelu(pos_conv(x)), then the encoder's LayerNorm
+    // x + gelu(pos_conv(x))
     {
       HbGemm g{&h->pos, X0, W("encoder.pos_conv_embed.conv.bias"), X0, P, F, F};
       g.groups = c.pos_conv_groups; g.gelu = 1; g.level = nl;
       hb_gemm(s, g, lens, nb);
     }
+    // layer >= 0: the encoder's state after that many layers, which goes to its hidden_states slot and, when it is the last one asked for, to out
+    auto slot = [&](int layer) { return layer >= 0 && hidden_states ? hidden_states + (size_t)b0 * hs_bs + (size_t)layer * hs_ls : nullptr; };
+    auto result = [&](int layer) { return layer == n_layers_out ? out + b0 * fh : nullptr; };
     auto ln = [&](const float* in, const float* res, const std::string& key, float* y, int layer) {
-      // layer >= 0: the encoder's state after that many layers, which goes to its hidden_states slot and, when it is the last one asked for, to out
-      float* e1 = layer >= 0 && hidden_states ? hidden_states + (size_t)b0 * hs_bs + (size_t)layer * fh : nullptr;
-      float* e2 = layer == n_layers_out ? out + b0 * fh : nullptr;
-      hipLaunchKernelGGL(hb_ln_kernel, dim3((F + kLnCols - 1) / kLnCols, nb), dim3(1024), 0, s, in, res, W(key + ".weight"), W(key + ".bias"), y, e1, e2,
-                         hs_bs, (long long)fh, lens, nl, H, F, c.layer_norm_eps);
+      ln_launch(in, res, key, y, slot(layer), result(layer), hs_bs, nl, H, F, c.layer_norm_eps, 0);
     };
+    auto attention = [&](const float* in, const HbLayer& l, const std::string& q) {          // in -> ATT
+      if (h->wavlm)
+        hipLaunchKernelGGL(wl_gate_kernel, dim3((F + 255) / 256, c.n_heads, nb), dim3(256), 0, s, in, W(q + "attention.gru_rel_pos_linear.weight"),
+                           W(q + "attention.gru_rel_pos_linear.bias"), W(q + "attention.gru_rel_pos_const"), G, H, h->d, F);
+      HbGemm g{&l.qkv, in, l.qkv_b, nullptr, QKV, F, F};
+      g.nscale = H; g.scale = 1.f / sqrtf((float)h->d); g.level = nl;
+      hb_gemm(s, g, lens, nb);
+      hb_attn(s, QKV, ATT, lens, nl, H, c.n_heads, h->d, F, nb, G, h->table, h->D);
+    };
+    if (pre_ln) {
+      // the residual stream stays un-normalised: x + attn(LN(x)), then h + ffn(LN(h)), the residual added in the GEMM's epilogue.  Hidden state
+      // i < L is the stream before layer i (a transposing copy), hidden state L is encoder.layer_norm of it.
+      float* S = P;                       // the stream
+      float* S2 = X;                      // the buffer the next stream is written to
+      auto export_stream = [&](int layer) {
+        float* e1 = slot(layer);
+        float* e2 = result(layer);
+        if (e1 || e2)
+          hipLaunchKernelGGL(hb_export_kernel, dim3((F + kLnCols - 1) / kLnCols, (H + kLnSlices - 1) / kLnSlices, nb), dim3(1024), 0, s, S, e1, e2, hs_bs,
+                             (long long)fh, H, F);
+      };
+      for (int i = 0; i < n_layers_out; ++i) {
+        const HbLayer& l = h->layers[i];
+        const std::string q = hb_layer_key(i);
+        export_stream(i);
+        ln_launch(S, nullptr, q + "layer_norm", X1, nullptr, nullptr, 0ll, nl, H, F, c.layer_norm_eps, 0);
+        attention(X1, l, q);
+        {
+          HbGemm g{&l.out, ATT, W(q + "attention.out_proj.bias"), S, Y, F, F};
+          g.level = nl;
+          hb_gemm(s, g, lens, nb);
+        }
+        ln_launch(Y, nullptr, q + "final_layer_norm", X1, nullptr, nullptr, 0ll, nl, H, F, c.layer_norm_eps, 0);
+        {
+          HbGemm g{&l.ff1, X1, W(q + "feed_forward.intermediate_dense.bias"), nullptr, FF, F, F};
+          g.gelu = 1; g.level = nl;
+          hb_gemm(s, g, lens, nb);
+        }
+        {
+          HbGemm g{&l.ff2, FF, W(q + "feed_forward.output_dense.bias"), Y, S2, F, F};
+          g.level = nl;
+          hb_gemm(s, g, lens, nb);
+        }
+        std::swap(S, S2);
+      }
+      if (n_layers_out == c.n_layers)
+        ln(S, nullptr, "encoder.layer_norm", nullptr, n_layers_out);
+      else
+        export_stream(n_layers_out);
+      continue;
+    }
     ln(P, nullptr, "encoder.layer_norm", X, 0);
     for (int i = 0; i < n_layers_out; ++i) {
       const HbLayer& l = h->layers[i];
       const std::string q = hb_layer_key(i);
-      {
-        HbGemm g{&l.qkv, X, l.qkv_b, nullptr, QKV, F, F};
-        g.nscale = H; g.scale = 1.f / sqrtf((float)h->d); g.level = nl;
-        hb_gemm(s, g, lens, nb);
-      }
-      hb_attn(s, QKV, ATT, lens, nl, H, c.n_heads, h->d, F, nb);
+      attention(X, l, q);
       {
         HbGemm g{&l.out, ATT, W(q + "attention.out_proj.bias"), nullptr, Y, F, F};
         g.level = nl;
@@ -764,7 +980,123 @@ int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengt
     }
   }
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : h->hip("us_hubert_forward", e);
+  return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
+}
+
+}  // namespace
+}  // namespace us
+
+extern "C" {
+
+using namespace us;
+
+int us_hubert_create(us_hubert_handle* out, const us_hubert_config* cfg) {
+  if (!out || !cfg) return WeightTable::fail(nullptr, US_EINVAL, "us_hubert_create: null argument");
+  const auto& c = *cfg;
+  auto bad = [](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, "us_hubert_create: " + m); };
+  if (c.feat_extract_norm != US_HUBERT_NORM_GROUP) return bad("only the group-norm feature extractor (feat_extract_norm = \"group\") is built");
+  if (c.do_stable_layer_norm) return bad("the pre-LN encoder (do_stable_layer_norm) is not built");
+  const std::string m = hb_check_geometry(c);
+  if (!m.empty()) return bad(m);
+  auto* h = new us_hubert();
+  h->cfg = c;
+  hb_init(h);
+  *out = h;
+  return US_OK;
+}
+
+int us_hubert_destroy(us_hubert_handle h) {
+  if (!h) return US_OK;
+  hb_release(h);
+  delete h;
+  return US_OK;
+}
+
+int us_hubert_num_weights(us_hubert_handle h) { return h ? h->num() : 0; }
+const char* us_hubert_weight_key(us_hubert_handle h, int i) { return h ? h->key(i) : nullptr; }
+const char* us_hubert_last_error(us_hubert_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
+
+int us_hubert_load_weight(us_hubert_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
+  return hb_load_weight(h, "us_hubert_load_weight", key, data, shape, ndim, stream);
+}
+
+int us_hubert_frames(us_hubert_handle h, int64_t T) { return hb_frames(h, "us_hubert_frames", T); }
+
+size_t us_hubert_workspace_bytes(us_hubert_handle h, int B, int Tmax) { return hb_workspace_bytes(h, B, Tmax); }
+
+int us_hubert_forward(us_hubert_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out, float* out,
+                      float* hidden_states, void* workspace, size_t workspace_bytes, us_stream stream) {
+  long long fh = 0;
+  if (h && Tmax > 0) fh = std::max(0ll, hb_steps(h->cfg, Tmax, h->cfg.n_conv)) * h->cfg.hidden_size;
+  return hb_forward(h, "us_hubert_forward", wav, lengths, B, Tmax, normalize, n_layers_out, out, hidden_states,
+                    (long long)(std::max(n_layers_out, 0) + 1) * fh, fh, workspace, workspace_bytes, stream);
+}
+
+int us_wavlm_create(us_wavlm_handle* out, const us_wavlm_config* cfg) {
+  if (!out || !cfg) return WeightTable::fail(nullptr, US_EINVAL, "us_wavlm_create: null argument");
+  auto bad = [](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, "us_wavlm_create: " + m); };
+  us_hubert_config c{};
+  c.n_conv = cfg->n_conv;
+  for (int i = 0; i < US_HUBERT_MAX_CONV; ++i) {
+    c.conv_dim[i] = cfg->conv_dim[i];
+    c.conv_kernel[i] = cfg->conv_kernel[i];
+    c.conv_stride[i] = cfg->conv_stride[i];
+  }
+  c.hidden_size = cfg->hidden_size; c.n_heads = cfg->n_heads; c.intermediate_size = cfg->intermediate_size; c.n_layers = cfg->n_layers;
+  c.pos_conv_kernel = cfg->pos_conv_kernel; c.pos_conv_groups = cfg->pos_conv_groups;
+  c.feat_extract_norm = cfg->feat_extract_norm; c.do_stable_layer_norm = cfg->do_stable_layer_norm ? 1 : 0; c.layer_norm_eps = cfg->layer_norm_eps;
+  const bool large = c.feat_extract_norm == US_HUBERT_NORM_LAYER && c.do_stable_layer_norm && cfg->conv_bias;
+  const bool base = c.feat_extract_norm == US_HUBERT_NORM_GROUP && !c.do_stable_layer_norm && !cfg->conv_bias;
+  if (!large && !base)
+    return bad("feat_extract_norm, do_stable_layer_norm and conv_bias must be (layer, 1, 1), WavLM-large's form, or (group, 0, 0), WavLM-base's");
+  const std::string m = hb_check_geometry(c);
+  if (!m.empty()) return bad(m);
+  if (cfg->num_buckets < 4 || cfg->num_buckets > 4096 || cfg->num_buckets % 2 != 0) return bad("num_buckets must be even, from 4 to 4096");
+  if (cfg->max_bucket_distance <= cfg->num_buckets / 4 || cfg->max_bucket_distance > (1 << 20))
+    return bad("max_bucket_distance must be above num_buckets / 4 and at most 2^20");
+  auto* h = new us_wavlm();
+  h->cfg = c;
+  h->abi = "us_wavlm";
+  h->wavlm = true;
+  h->conv_bias = cfg->conv_bias ? 1 : 0;
+  h->num_buckets = cfg->num_buckets;
+  h->max_distance = cfg->max_bucket_distance;
+  wl_bucket_map(h);
+  hb_init(h);
+  *out = h;
+  return US_OK;
+}
+
+int us_wavlm_destroy(us_wavlm_handle h) {
+  if (!h) return US_OK;
+  hb_release(h);
+  delete h;
+  return US_OK;
+}
+
+int us_wavlm_num_weights(us_wavlm_handle h) { return h ? h->num() : 0; }
+const char* us_wavlm_weight_key(us_wavlm_handle h, int i) { return h ? h->key(i) : nullptr; }
+const char* us_wavlm_last_error(us_wavlm_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
+
+int us_wavlm_load_weight(us_wavlm_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
+  return hb_load_weight(h, "us_wavlm_load_weight", key, data, shape, ndim, stream);
+}
+
+int us_wavlm_frames(us_wavlm_handle h, int64_t T) { return hb_frames(h, "us_wavlm_frames", T); }
+
+size_t us_wavlm_workspace_bytes(us_wavlm_handle h, int B, int Tmax) { return hb_workspace_bytes(h, B, Tmax); }
+
+int us_wavlm_position_bucket(us_wavlm_handle h, int64_t delta) {
+  if (!h) return WeightTable::fail(nullptr, US_EINVAL, "us_wavlm_position_bucket: null handle");
+  const long long D = h->D;
+  return h->bucket[(size_t)(std::max<long long>(-D, std::min<long long>(D, delta)) + D)];
+}
+
+int us_wavlm_forward(us_wavlm_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, int normalize, int n_layers_out, float* out,
+                     float* hidden_states, int64_t hs_item_stride, int64_t hs_layer_stride, void* workspace, size_t workspace_bytes,
+                     us_stream stream) {
+  return hb_forward(h, "us_wavlm_forward", wav, lengths, B, Tmax, normalize, n_layers_out, out, hidden_states, hs_item_stride, hs_layer_stride,
+                    workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 
 Drop-in for the reference's `unitspeech/speaker_encoder/ecapa_tdnn.py:164-298` `ECAPA_TDNN` / `ECAPA_TDNN_SMALL` from the hidden
 states on: the same constructor arguments, the same module tree and therefore the same `state_dict` keys, shapes and order with
-every `feature_extract.*` key removed (the WavLM / HuBERT upstream and the fbank / mfcc extraction are not part of this library).
+every `feature_extract.*` key removed (the fbank / mfcc extraction is not part of this library; a WavLM upstream is `wavlm.WavLMModel`,
+put in front with `attach_upstream`, after which `forward(wav)` is the reference's).
 The torch modules below only hold parameters; the arithmetic is `csrc/speaker.hip`.
 
 `forward_features(hidden_states)` is the entry point: `[L, B, T, C]`, a list of L `[B, T, C]`, or an already combined `[B, C, T]`.
@@ -199,9 +200,48 @@ class ECAPA_TDNN(HandleModule):
         self._check(lib, rc, f"us_speaker_debug_conv({prefix})")
         return out
 
-    def forward(self, x):
-        raise NotImplementedError("ECAPA_TDNN.forward(wav) needs the upstream feature extractor (WavLM / HuBERT through s3prl, or fbank / mfcc), "
-                                  "which is outside this library: run the upstream and call forward_features(hidden_states)")
+    # ---- the upstream in front (get_feat, :248-272) ------------------------------------------------------------------------------
+
+    def attach_upstream(self, wavlm, normalize=True):
+        """Put a `wavlm.WavLMModel` in front: `forward(wav [B, T])` then runs it and the trunk on all its hidden states, which the
+        library writes as [L + 1, B, F, H] (`get_feat` + `forward`, :248-287).  `normalize`: s3prl's wavlm_large applies
+        `F.layer_norm(wav, wav.shape)` to each waveform first.  The upstream is not a submodule: its parameters stay out of
+        `state_dict()`, as `feature_extract.*` does in this module's checkpoints; `.to()` and `.cuda()` move it along."""
+        n = wavlm.config["num_hidden_layers"] + 1
+        if n != self.feat_num or wavlm.config["hidden_size"] != self.feat_dim:
+            raise ValueError(f"ECAPA_TDNN.attach_upstream: the upstream gives {n} hidden states of width {wavlm.config['hidden_size']}, the trunk "
+                             f"takes {self.feat_num} of width {self.feat_dim}")
+        object.__setattr__(self, "_upstream", wavlm.eval())
+        self._upstream_normalize = bool(normalize)
+        return self
+
+    @property
+    def upstream(self):
+        return self.__dict__.get("_upstream")
+
+    def _apply(self, fn, *args, **kwargs):
+        if self.upstream is not None:
+            self.upstream._apply(fn, *args, **kwargs)
+        return super()._apply(fn, *args, **kwargs)
+
+    def _hidden_states(self, wav, lengths=None):
+        _, hs = self.upstream(wav, lengths, output_hidden_states=True, normalize=self._upstream_normalize, layers_first=True)
+        return hs
+
+    def forward(self, x, lengths=None):
+        if self.upstream is None:
+            raise NotImplementedError("ECAPA_TDNN.forward(wav) needs the upstream feature extractor (WavLM / HuBERT through s3prl, or fbank / mfcc), "
+                                      "which is outside this library: run the upstream and call forward_features(hidden_states)")
+        return self._run(self._hidden_states(x, lengths), False)
+
+    def embed_wav(self, wav):
+        """finetune.py:113-117: the embedding of one 16 kHz utterance [1, T] divided by its norm, [1, emb_dim]."""
+        if self.upstream is None:
+            raise NotImplementedError("ECAPA_TDNN.embed_wav needs an upstream: attach_upstream(WavLMModel), or run the upstream and call "
+                                      "embed(hidden_states)")
+        if wav.dim() != 2 or wav.shape[0] != 1:
+            raise ValueError("ECAPA_TDNN.embed_wav: one utterance [1, T] at a time (the norm is taken over the whole output)")
+        return self._run(self._hidden_states(wav), True)
 
     @torch.no_grad()
     def stage(self, name: str) -> torch.Tensor:
@@ -232,6 +272,31 @@ def load_speaker_encoder_checkpoint(path, device=None, feat_dim=1024, emb_dim=25
     sd = OrderedDict((k, v) for k, v in state_dict["model"].items() if not k.startswith("feature_extract."))
     model.load_state_dict(sd, strict=True)
     model = model.eval()
+    return model.to(device) if device is not None else model
+
+
+def load_speaker_embedder_checkpoint(path, device=None, feat_type="wavlm_large", **wavlm_config):
+    """The reference's whole speaker embedder from its {"model": state_dict} file: the trunk from the keys outside `feature_extract.*`, as
+    `load_speaker_encoder_checkpoint` loads it (sizes from the tensor shapes), and a `WavLMModel` from the `feature_extract.model.*`
+    keys through `from_fairseq_wavlm_state_dict`, its sizes read from the shapes too (`wavlm.wavlm_config_from_state_dict`; keywords
+    override), attached with s3prl's waveform normalisation when the extractor is the layer-norm form.  Eval mode."""
+    from .wavlm import WavLMModel, from_fairseq_wavlm_state_dict, wavlm_config_from_state_dict
+    sd = torch.load(path, map_location=lambda storage, loc: storage)["model"]
+    pre = "feature_extract.model."
+    up = OrderedDict((k[len(pre):], v) for k, v in sd.items() if k.startswith(pre))
+    if not up:
+        raise ValueError(f"{path} holds no `feature_extract.*` keys, so there is no upstream to load: use load_speaker_encoder_checkpoint "
+                         "and forward_features(hidden_states)")
+    up = from_fairseq_wavlm_state_dict(up)
+    cfg = wavlm_config_from_state_dict(up, **wavlm_config)
+    wavlm = WavLMModel(**cfg)
+    wavlm.load_state_dict(up)
+    trunk = OrderedDict((k, v) for k, v in sd.items() if not k.startswith("feature_extract."))
+    model = ECAPA_TDNN(feat_dim=int(trunk["layer1.conv.weight"].shape[1]), channels=int(trunk["layer1.conv.weight"].shape[0]),
+                       emb_dim=int(trunk["linear.weight"].shape[0]), feat_type=feat_type, feat_num=int(trunk["feature_weight"].shape[0]),
+                       global_context_att=int(trunk["pooling.linear1.weight"].shape[1]) == 3 * OUT_CHANNELS)
+    model.load_state_dict(trunk, strict=True)
+    model = model.eval().attach_upstream(wavlm, normalize=cfg["feat_extract_norm"] == "layer")
     return model.to(device) if device is not None else model
 
 
