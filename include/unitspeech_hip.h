@@ -479,11 +479,23 @@ const char* us_speaker_weight_key(us_speaker_handle h, int i);
 const char* us_speaker_last_error(us_speaker_handle h);
 size_t us_speaker_workspace_bytes(us_speaker_handle h, int B, int T);
 /* `ECAPA_TDNN.forward` from get_feat's input on (:261-287).  hidden_states is [L][B][T][feat_dim] with L = n_layers, or, with L = 0, the
- * already combined [B][feat_dim][T] (which only gets the InstanceNorm1d).  Any T >= 1; all items of a batch share T (the reference has
- * no masking).  emb_out [B][emb_dim]; normalize = 1 divides the whole output by its norm (B = 1 only), 0 returns the raw output. */
+ * already combined [B][feat_dim][T] (which only gets the InstanceNorm1d).  Any T >= 1; every item of the batch has T steps (the
+ * reference has no masking; us_speaker_forward_lengths is the call for items of different lengths).  emb_out [B][emb_dim]; normalize = 1
+ * divides the whole output by its norm (B = 1 only), 0 returns the raw output. */
 int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, int B, int T, float* emb_out, int normalize, void* workspace,
                        size_t workspace_bytes, us_stream stream);
-/* Debug view of an intermediate the last us_speaker_forward(B, T) left in `workspace`: *data points into it, shape[3] is its extent.
+/* The same forward on a ragged batch: hidden_states is [L][B][Tmax][feat_dim] (or, with L = 0, [B][feat_dim][Tmax]) and item b is valid on
+ * its first lengths[b] steps.  `lengths` is a HOST array of B values in [1, Tmax]; they travel to the kernels as arguments, 32 items per
+ * launch group, so the call still allocates nothing, copies nothing and only enqueues on `stream`.  Nothing at or past an item's end is
+ * read into any result (it may hold anything, NaN included): the instance norm, the SE means, the global context and the attentive pooling
+ * run over lengths[b] steps, the dilated convolutions see zeros past the end as they do past T, and row b of emb_out has exactly the bits
+ * us_speaker_forward gives for that item alone at T = lengths[b].  normalize = 1 divides each row by its own norm (any B).  The
+ * workspace is us_speaker_workspace_bytes(h, B, Tmax); afterwards us_speaker_stage(B, Tmax) shows [B][C][Tmax] tensors of which only each
+ * item's first lengths[b] steps are defined.  A null `lengths`, or a lengths[b] outside [1, Tmax] (the message names b), is US_EINVAL
+ * before anything is enqueued. */
+int us_speaker_forward_lengths(us_speaker_handle h, const float* hidden_states, int L, int B, int Tmax, const int64_t* lengths, float* emb_out,
+                               int normalize, void* workspace, size_t workspace_bytes, us_stream stream);
+/* Debug view of an intermediate the last us_speaker_forward(B, T) or us_speaker_forward_lengths(B, Tmax) left in `workspace`: *data points into it, shape[3] is its extent.
  * FEAT [B][feat_dim][T] after get_feat, LAYER1 [B][channels][T], BLOCKS [B][3 channels][T] (layer2 | layer3 | layer4 along the
  * channels, the input of `conv`), POOLING [B][3072][1] (mean | std, before `bn`).  Enqueues nothing. */
 int us_speaker_stage(us_speaker_handle h, int stage, int B, int T, void* workspace, size_t workspace_bytes, const float** data, int64_t* shape);

@@ -17,6 +17,12 @@
 //  - sp_pool_kernel: softmax over T and the weighted mean / std per (b, c) row, `bn` applied;  sp_linear_kernel;  sp_normalize_kernel.
 // Every reduction is a fixed-order tree inside one wave (or a fixed-order loop over waves): no atomics, so a batch item's result
 // does not depend on its neighbours or on the run.
+//
+// Ragged batches (us_speaker_forward_lengths): every kernel that looks along time is a template over how it learns an item's length.
+// SpSameT is the uniform call: the length is the row stride T, and the instantiation is the kernel as it was.  SpLens carries the
+// lengths of up to kSpItems items as a kernel argument (one scalar load per workgroup, indexed by the block's item): item b is then a
+// tensor of lens.n[b] steps stored with row stride T, the time tiles start where they start when the item runs alone, and every sum
+// runs over the same terms in the same order, so the item's result has the bits of the uniform call on the item alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,14 +46,48 @@ constexpr int kSpScale = 8;        // Res2 scale
 constexpr int kSpStages = kSpScale - 1;
 constexpr float kBnEps = 1e-5f;
 
+// ---- how a kernel learns the valid steps of batch item b (rows are T apart either way) -------------------------------------------
+constexpr int kSpItems = 32;       // batch items per launch of the ragged form: their lengths travel as kernel arguments
+
+struct SpSameT {                   // us_speaker_forward: every item has T steps
+  static constexpr bool ragged = false;
+  __device__ __forceinline__ int operator()(int, int T) const { return T; }
+};
+
+struct SpLens {                    // us_speaker_forward_lengths: item b of the launch has n[b] steps, 1 <= n[b] <= T
+  static constexpr bool ragged = true;
+  int n[kSpItems];
+  __device__ __forceinline__ int operator()(int b, int) const { return n[b]; }
+};
+
+// The (b, c) row of a one-wave-per-row kernel and its valid steps; false: the wave has no row.  Uniform: rows are numbered through the
+// whole batch, four per workgroup.  Ragged: blockIdx.y is the item (its length a scalar load), blockIdx.x * 4 + wave the channel.
+template <class LN>
+__device__ __forceinline__ bool sp_row(const LN& lens, int C, int rows, int T, int& row, int& n) {
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (LN::ragged) {
+    if (w >= C) return false;
+    row = blockIdx.y * C + w;
+    n = lens(blockIdx.y, T);
+    return true;
+  }
+  row = w;
+  n = T;
+  return w < rows;
+}
+
 // ---- feature combine + instance norm (get_feat, :261-271) ------------------------------------------------------------------
 constexpr int kCmbT = 16, kCmbC = 64;
 
+// B: the items of the whole tensor h (its layer stride), of which this launch takes gridDim.z from h on
+template <class LN>
 __global__ __launch_bounds__(256) void sp_combine_kernel(const float* __restrict__ h, const float* __restrict__ lw, float* __restrict__ x,
-                                                         int L, int B, int T, int C) {
+                                                         int L, int B, int T, int C, LN lens) {
   __shared__ float tile[kCmbT][kCmbC + 1];
   const int tid = threadIdx.x, cl = tid & 63, tr = tid >> 6;
   const int c0 = blockIdx.x * kCmbC, t0 = blockIdx.y * kCmbT, b = blockIdx.z;
+  const int n = lens(b, T);
+  if (LN::ragged && t0 >= n) return;
   const int c = c0 + cl;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const size_t lstride = (size_t)B * T * C;
@@ -57,7 +97,7 @@ __global__ __launch_bounds__(256) void sp_combine_kernel(const float* __restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int t = t0 + tr + 4 * i;
-      if (t < T && c < C) acc[i] = fmaf(wl, hb[(size_t)l * lstride + (size_t)t * C], acc[i]);
+      if (t < n && c < C) acc[i] = fmaf(wl, hb[(size_t)l * lstride + (size_t)t * C], acc[i]);
     }
   }
 #pragma unroll
@@ -68,7 +108,7 @@ __global__ __launch_bounds__(256) void sp_combine_kernel(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int t = t0 + tq + j;
-      if (t < T) x[((size_t)b * C + c0 + cc) * T + t] = tile[tq + j][cc];
+      if (t < n) x[((size_t)b * C + c0 + cc) * T + t] = tile[tq + j][cc];
     }
   }
 }
@@ -82,22 +122,27 @@ __global__ void sp_layer_softmax_kernel(const float* __restrict__ w, float* __re
   for (int l = 0; l < L; ++l) lw[l] = expf(w[l] - m) / s;
 }
 
-// InstanceNorm1d without affine: biased variance over T, eps 1e-5.  One wave per row; `out` may be `in`.
-__global__ __launch_bounds__(256) void sp_instnorm_kernel(const float* in, float* out, int rows, int T) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+// InstanceNorm1d without affine: biased variance over the item's n steps, eps 1e-5.  One wave per row; `out` may be `in`.  The ragged form
+// writes zeros on [n, T): layer1.conv (k = 5) then reads past an item's end the zeros it pads with when the item runs alone.
+template <class LN>
+__global__ __launch_bounds__(256) void sp_instnorm_kernel(const float* in, float* out, int C, int rows, int T, LN lens) {
+  const int lane = threadIdx.x & 63;
+  int row, n;
+  if (!sp_row(lens, C, rows, T, row, n)) return;
   const float* r = in + (size_t)row * T;
   float s = 0.f;
-  for (int t = lane; t < T; t += 64) s += r[t];
-  const float mean = wave_sum(s) / (float)T;
+  for (int t = lane; t < n; t += 64) s += r[t];
+  const float mean = wave_sum(s) / (float)n;
   float v = 0.f;
-  for (int t = lane; t < T; t += 64) {
+  for (int t = lane; t < n; t += 64) {
     const float d = r[t] - mean;
     v = fmaf(d, d, v);
   }
-  const float rs = 1.f / sqrtf(wave_sum(v) / (float)T + 1e-5f);
+  const float rs = 1.f / sqrtf(wave_sum(v) / (float)n + 1e-5f);
   float* o = out + (size_t)row * T;
-  for (int t = lane; t < T; t += 64) o[t] = (r[t] - mean) * rs;
+  for (int t = lane; t < n; t += 64) o[t] = (r[t] - mean) * rs;
+  if (LN::ragged)
+    for (int t = n + lane; t < T; t += 64) o[t] = 0.f;
 }
 
 // ---- implicit-GEMM convolution ------------------------------------------------------------------------------------------------
@@ -121,15 +166,21 @@ struct SpConvArgs {
   int Cin, Cout, T, off, Kdim, Kpad, ldw, act;
 };
 
-__global__ __launch_bounds__(256) void sp_conv_kernel(SpConvArgs a) {
+// Ragged: a workgroup whose 64 steps all lie at or past the item's end returns before the first barrier, and no step at or past it is
+// stored.  The loader still reads columns up to the row's T: a k = 1 output column depends on its own input column alone, so whatever
+// lies past the end stays in columns that are never stored, and layer1's k = 5 reads the zeros sp_instnorm_kernel wrote there.
+template <class LN>
+__global__ __launch_bounds__(256) void sp_conv_kernel(SpConvArgs a, LN lens) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
   const int b = blockIdx.z;
   const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kSpBN;
+  const int n = lens(b, a.T);
+  if (LN::ragged && n0 >= n) return;
   f32x16 acc[1][2];
   planar_conv_mainloop<1, 2>({a.in + (size_t)b * a.in_bs, a.w, a.Cin, a.T, 1, a.off, a.Kdim, a.Kpad, a.ldw, m0, n0}, acc);
   const int t = n0 + nh * 32 + cl;
-  if (t >= a.T) return;
+  if (t >= n) return;
   float* __restrict__ out = a.out + (size_t)b * a.out_bs;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -159,33 +210,37 @@ __global__ void sp_bnfold_kernel(const float* __restrict__ w, const float* __res
 // position p <-> time t0 - 7 dil + p.  Stage i reads the window S (= stage i - 1's output + split i; split 0 for i = 0) and writes
 // bn(relu(conv(S))) over the WHOLE window, taking S as zero beyond the window's ends: a position within (i + 1) dil of an end is then
 // wrong, which after seven stages still leaves the TT central ones exact.  A position outside [0, T) is forced to zero at every stage
-// (each convolution pads its own input with zeros; the value the previous stage would compute there from zeros is not one).
+// (each convolution pads its own input with zeros; the value the previous stage would compute there from zeros is not one).  Ragged: the
+// item's end n takes the place of T in `inside` and in every read, rows stay T apart, and a tile that starts at or past n returns at once.
 // Lane = position, so the weights of a (ci, tap) are wave-uniform: 16 output channels per lane, packed contiguously.
 constexpr int kRes2W = 128;
 constexpr int kRes2Co = 16;
 
+template <class LN>
 __global__ __launch_bounds__(512) void sp_res2_kernel(const float* __restrict__ y, float* __restrict__ out, const float* __restrict__ wp,
-                                                      const float* __restrict__ bss, int width, int wpad, int T, int dil, int TT) {
+                                                      const float* __restrict__ bss, int width, int wpad, int T, int dil, int TT, LN lens) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y, t0 = blockIdx.x * TT, halo = kSpStages * dil, base = t0 - halo;
+  const int n = lens(b, T);
+  if (LN::ragged && t0 >= n) return;
   const size_t bo = (size_t)b * kSpScale * width * T;
   const float* __restrict__ yb = y + bo;
   float* __restrict__ ob = out + bo;
   const int half = width * kRes2W;              // the two windows: stage i reads the one at (i & 1) * half and writes the other
   for (int idx = tid; idx < width * kRes2W; idx += 512) {
     const int ci = idx / kRes2W, p = idx - ci * kRes2W, t = base + p;
-    lds[idx] = (t >= 0 && t < T) ? yb[(size_t)ci * T + t] : 0.f;
+    lds[idx] = (t >= 0 && t < n) ? yb[(size_t)ci * T + t] : 0.f;
   }
   // the eighth split passes through (:47-48)
   for (int idx = tid; idx < width * TT; idx += 512) {
     const int ci = idx / TT, t = t0 + idx - ci * TT;
-    if (t < T) ob[(size_t)((kSpScale - 1) * width + ci) * T + t] = yb[(size_t)((kSpScale - 1) * width + ci) * T + t];
+    if (t < n) ob[(size_t)((kSpScale - 1) * width + ci) * T + t] = yb[(size_t)((kSpScale - 1) * width + ci) * T + t];
   }
   __syncthreads();
   const int p = (wave & 1) * 64 + lane, t = base + p, cog = wave >> 1;
-  const bool inside = t >= 0 && t < T;
+  const bool inside = t >= 0 && t < n;
   const bool centre = inside && p >= halo && p < halo + TT;
   const bool lo = p - dil >= 0, hi = p + dil < kRes2W;
   for (int i = 0; i < kSpStages; ++i) {
@@ -241,14 +296,16 @@ __global__ void sp_res2_pack_kernel(const float* __restrict__ w, const float* __
 }
 
 // ---- SE_Connect (:78-84) and the block residual (:126) --------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sp_rowmean_kernel(const float* __restrict__ in, float* __restrict__ mean, int rows, int T) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+template <class LN>
+__global__ __launch_bounds__(256) void sp_rowmean_kernel(const float* __restrict__ in, float* __restrict__ mean, int C, int rows, int T, LN lens) {
+  const int lane = threadIdx.x & 63;
+  int row, n;
+  if (!sp_row(lens, C, rows, T, row, n)) return;
   const float* r = in + (size_t)row * T;
   float s = 0.f;
-  for (int t = lane; t < T; t += 64) s += r[t];
+  for (int t = lane; t < n; t += 64) s += r[t];
   s = wave_sum(s);
-  if (lane == 0) mean[row] = s / (float)T;
+  if (lane == 0) mean[row] = s / (float)n;
 }
 
 // s[b][c] = sigmoid(W2 relu(W1 mean[b] + b1) + b2); one workgroup per batch item, one wave per output
@@ -274,31 +331,37 @@ __global__ __launch_bounds__(1024) void sp_se_kernel(const float* __restrict__ m
   }
 }
 
+// Ragged: the loop runs over the item's ch * n valid elements only, so the workgroups past them (the grid is sized for T) have no turn
+template <class LN>
 __global__ __launch_bounds__(256) void sp_scale_res_kernel(const float* __restrict__ y, const float* __restrict__ s, const float* __restrict__ res,
-                                                           float* __restrict__ out, int ch, int T, long long res_bs, long long out_bs) {
+                                                           float* __restrict__ out, int ch, int T, long long res_bs, long long out_bs, LN lens) {
   const int b = blockIdx.y;
-  const size_t n = (size_t)ch * T;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i / T);
-    out[(size_t)b * out_bs + i] = fmaf(y[(size_t)b * n + i], s[(size_t)b * ch + c], res[(size_t)b * res_bs + i]);
+  const int len = lens(b, T);
+  const size_t n = (size_t)ch * T, live = (size_t)ch * len;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < live; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i / len);
+    const size_t j = LN::ragged ? (size_t)c * T + (i - (size_t)c * len) : i;
+    out[(size_t)b * out_bs + j] = fmaf(y[(size_t)b * n + j], s[(size_t)b * ch + c], res[(size_t)b * res_bs + j]);
   }
 }
 
 // ---- AttentiveStatsPool (:145-161) ------------------------------------------------------------------------------------------------
 // global context: ctx[b][0][c] = mean over T, ctx[b][1][c] = sqrt(unbiased var + 1e-10) (torch.var's default; NaN for T = 1 as there)
-__global__ __launch_bounds__(256) void sp_rowstats_kernel(const float* __restrict__ in, float* __restrict__ ctx, int C, int rows, int T) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+template <class LN>
+__global__ __launch_bounds__(256) void sp_rowstats_kernel(const float* __restrict__ in, float* __restrict__ ctx, int C, int rows, int T, LN lens) {
+  const int lane = threadIdx.x & 63;
+  int row, n;
+  if (!sp_row(lens, C, rows, T, row, n)) return;
   const float* r = in + (size_t)row * T;
   float s = 0.f;
-  for (int t = lane; t < T; t += 64) s += r[t];
-  const float mean = wave_sum(s) / (float)T;
+  for (int t = lane; t < n; t += 64) s += r[t];
+  const float mean = wave_sum(s) / (float)n;
   float v = 0.f;
-  for (int t = lane; t < T; t += 64) {
+  for (int t = lane; t < n; t += 64) {
     const float d = r[t] - mean;
     v = fmaf(d, d, v);
   }
-  v = wave_sum(v) / (float)(T - 1);
+  v = wave_sum(v) / (float)(n - 1);
   if (lane == 0) {
     const int b = row / C, c = row - b * C;
     ctx[((size_t)b * 2) * C + c] = mean;
@@ -321,18 +384,20 @@ __global__ __launch_bounds__(1024) void sp_ctx_bias_kernel(const float* __restri
 
 // one wave per (b, c) row: alpha = softmax_T(e), mean = sum alpha x, std = sqrt(clamp(sum alpha x^2 - mean^2, 1e-9)); raw[b] = [mean | std]
 // and bnd = raw * scale + shift (the eval-mode `bn` of :284)
+template <class LN>
 __global__ __launch_bounds__(256) void sp_pool_kernel(const float* __restrict__ x, const float* __restrict__ e, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, float* __restrict__ raw, float* __restrict__ bnd, int C,
-                                                      int rows, int T) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+                                                      int rows, int T, LN lens) {
+  const int lane = threadIdx.x & 63;
+  int row, n;
+  if (!sp_row(lens, C, rows, T, row, n)) return;
   const float* xr = x + (size_t)row * T;
   const float* er = e + (size_t)row * T;
   float m = -INFINITY;
-  for (int t = lane; t < T; t += 64) m = fmaxf(m, er[t]);
+  for (int t = lane; t < n; t += 64) m = fmaxf(m, er[t]);
   m = wave_max(m);
   float se = 0.f, sx = 0.f, sxx = 0.f;
-  for (int t = lane; t < T; t += 64) {
+  for (int t = lane; t < n; t += 64) {
     const float w = expf(er[t] - m), v = xr[t];
     se += w;
     sx = fmaf(w, v, sx);
@@ -369,9 +434,10 @@ __global__ __launch_bounds__(256) void sp_linear_kernel(const float* __restrict_
   if (lane == 0) out[o] = a + bias[j];
 }
 
-// x /= |x| over all n elements (finetune.py:110); one workgroup, the sum of squares in fp64 in a fixed order
+// x /= |x| over the n elements of row blockIdx.x (finetune.py:110); one workgroup per row, the sum of squares in fp64 in a fixed order
 __global__ __launch_bounds__(256) void sp_normalize_kernel(float* __restrict__ x, int n) {
   __shared__ double part[256];
+  x += (size_t)blockIdx.x * n;
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += (double)x[i] * (double)x[i];
   part[threadIdx.x] = s;
@@ -533,8 +599,9 @@ SpPlan sp_plan(const us_speaker_config& c, int B, int T) {
   return p;
 }
 
+template <class LN>
 void sp_conv(us_speaker* h, hipStream_t s, const std::string& p, const std::string& bn, int act, const float* in, long long in_bs, float* out,
-             long long out_bs, const float* bias2, int B, int T) {
+             long long out_bs, const float* bias2, int B, int T, const LN& lens) {
   const PlanarConv& c = h->conv.at(p);
   SpConvArgs a{};
   a.in = in; a.w = c.packed; a.bias = h->w.at(p + ".bias").dev; a.bias2 = bias2; a.out = out;
@@ -544,7 +611,98 @@ void sp_conv(us_speaker* h, hipStream_t s, const std::string& p, const std::stri
   }
   a.in_bs = in_bs; a.out_bs = out_bs;
   a.Cin = c.cin; a.Cout = c.cout; a.T = T; a.off = c.off[0]; a.Kdim = c.Kdim(); a.Kpad = c.Kpad; a.ldw = c.ldw; a.act = act;
-  hipLaunchKernelGGL(sp_conv_kernel, dim3((T + kSpBN - 1) / kSpBN, (c.cout + kPcBM - 1) / kPcBM, B), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((sp_conv_kernel<LN>), dim3((T + kSpBN - 1) / kSpBN, (c.cout + kPcBM - 1) / kPcBM, B), dim3(256), 0, s, a, lens);
+}
+
+// One wave per (b, c) row: the uniform form numbers the rows through the batch, the ragged one puts the item on blockIdx.y (sp_row)
+template <class LN>
+dim3 sp_rows_grid(int nb, int C) {
+  return LN::ragged ? dim3((unsigned)((C + 3) / 4), (unsigned)nb) : dim3((unsigned)(((long long)nb * C + 3) / 4));
+}
+
+// The forward of the nb items from item b0 on, of a batch of B items with rows T apart: every launch of `ECAPA_TDNN.forward` from
+// get_feat's input on.  The uniform call makes one pass over the whole batch (b0 = 0, nb = B); the ragged one makes a pass per kSpItems
+// items, `lens` holding theirs.
+template <class LN>
+void sp_run(us_speaker* h, hipStream_t s, const float* hidden_states, int L, int B, int T, int b0, int nb, const LN& lens, float* base,
+            const SpPlan& p, float* emb_out) {
+  const auto& c = h->cfg;
+  const int ch = c.channels, F = c.feat_dim;
+  const long long ct = (long long)ch * T;
+  const size_t o = (size_t)b0;                                  // every buffer is [B][...]: this pass works on its items' part
+  auto W = [&](const std::string& k) { return h->w.at(k).dev; };
+  // get_feat (:261-271)
+  float* X0 = base + p.x0 + o * F * T;
+  if (L > 0) {
+    hipLaunchKernelGGL((sp_combine_kernel<LN>), dim3((F + kCmbC - 1) / kCmbC, (T + kCmbT - 1) / kCmbT, nb), dim3(256), 0, s,
+                       hidden_states + o * T * F, h->lw, X0, L, B, T, F, lens);
+    hipLaunchKernelGGL((sp_instnorm_kernel<LN>), sp_rows_grid<LN>(nb, F), dim3(256), 0, s, X0, X0, F, nb * F, T, lens);
+  } else {
+    hipLaunchKernelGGL((sp_instnorm_kernel<LN>), sp_rows_grid<LN>(nb, F), dim3(256), 0, s, hidden_states + o * F * T, X0, F, nb * F, T, lens);
+  }
+  float* O1 = base + p.o1 + o * ct;
+  float* CAT = base + p.cat + o * 3 * ct;
+  float* A = base + p.a + o * ct;
+  float* R = base + p.r + o * ct;
+  float* Y = base + p.y + o * ct;
+  float* MEAN = base + p.mean + o * ch;
+  float* S = base + p.s + o * ch;
+  sp_conv(h, s, "layer1.conv", "layer1.bn", kActRelu, X0, (long long)F * T, O1, ct, nullptr, nb, T, lens);
+  static const int dils[3] = {2, 3, 4};                       // :225-227
+  for (int blk = 0; blk < 3; ++blk) {
+    const std::string q = "layer" + std::to_string(blk + 2);
+    const float* in = blk == 0 ? O1 : CAT + (size_t)(blk - 1) * ct;
+    const long long in_bs = blk == 0 ? ct : 3 * ct;
+    sp_conv(h, s, q + ".Conv1dReluBn1.conv", q + ".Conv1dReluBn1.bn", kActRelu, in, in_bs, A, ct, nullptr, nb, T, lens);
+    const int dil = dils[blk], TT = kRes2W - 2 * kSpStages * dil;
+    const SpRes2& r2 = h->res2.at(q);
+    hipLaunchKernelGGL((sp_res2_kernel<LN>), dim3((T + TT - 1) / TT, nb), dim3(512), 2 * (size_t)h->width * kRes2W * sizeof(float), s, A, R, r2.wp,
+                       r2.bss, h->width, h->wpad, T, dil, TT, lens);
+    sp_conv(h, s, q + ".Conv1dReluBn2.conv", q + ".Conv1dReluBn2.bn", kActRelu, R, ct, Y, ct, nullptr, nb, T, lens);
+    hipLaunchKernelGGL((sp_rowmean_kernel<LN>), sp_rows_grid<LN>(nb, ch), dim3(256), 0, s, Y, MEAN, ch, nb * ch, T, lens);
+    hipLaunchKernelGGL(sp_se_kernel, dim3(nb), dim3(1024), (size_t)(ch + kSpAtt) * sizeof(float), s, MEAN, W(q + ".SE_Connect.linear1.weight"),
+                       W(q + ".SE_Connect.linear1.bias"), W(q + ".SE_Connect.linear2.weight"), W(q + ".SE_Connect.linear2.bias"), S, ch);
+    hipLaunchKernelGGL((sp_scale_res_kernel<LN>), dim3((unsigned)std::min<long long>((ct + 255) / 256, 2048), nb), dim3(256), 0, s, Y, S, in,
+                       CAT + (size_t)blk * ct, ch, T, in_bs, 3 * ct, lens);
+  }
+  const long long bt = (long long)kSpOut * T, at = (long long)kSpAtt * T;
+  float* BIG = base + p.big + o * bt;
+  float* ATT = base + p.att + o * at;
+  float* E = base + p.e + o * bt;
+  float* CTX = base + p.ctx + o * 2 * kSpOut;
+  float* B2 = base + p.b2 + o * kSpAtt;
+  float* PRAW = base + p.praw + o * 2 * kSpOut;
+  float* PBN = base + p.pbn + o * 2 * kSpOut;
+  sp_conv(h, s, "conv", "", kActRelu, CAT, 3 * ct, BIG, bt, nullptr, nb, T, lens);
+  const float* bias2 = nullptr;
+  if (c.global_context_att) {
+    hipLaunchKernelGGL((sp_rowstats_kernel<LN>), sp_rows_grid<LN>(nb, kSpOut), dim3(256), 0, s, BIG, CTX, kSpOut, nb * kSpOut, T, lens);
+    hipLaunchKernelGGL(sp_ctx_bias_kernel, dim3(nb), dim3(1024), 0, s, CTX, W("pooling.linear1.weight"), B2, kSpOut);
+    bias2 = B2;
+  }
+  sp_conv(h, s, "pooling.linear1", "", kActTanh, BIG, bt, ATT, at, bias2, nb, T, lens);
+  sp_conv(h, s, "pooling.linear2", "", kActNone, ATT, at, E, bt, nullptr, nb, T, lens);
+  const SpBn& fb = h->bn.at("bn");
+  hipLaunchKernelGGL((sp_pool_kernel<LN>), sp_rows_grid<LN>(nb, kSpOut), dim3(256), 0, s, BIG, E, fb.scale, fb.scale + fb.n, PRAW, PBN, kSpOut,
+                     nb * kSpOut, T, lens);
+  hipLaunchKernelGGL(sp_linear_kernel, dim3((unsigned)(((long long)nb * c.emb_dim + 3) / 4)), dim3(256), 0, s, PBN, W("linear.weight"),
+                     W("linear.bias"), emb_out + o * c.emb_dim, nb, 2 * kSpOut, c.emb_dim);
+}
+
+// what the two forward entry points check alike; US_OK: `s` has the derived weight forms enqueued
+int sp_forward_checks(us_speaker* h, const std::string& what, int L, int B, int T, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  const auto& c = h->cfg;
+  if (L != 0 && L != c.n_layers)
+    return h->fail(US_EINVAL, what + ": L must be the configuration's n_layers (" + std::to_string(c.n_layers) +
+                                  "), or 0 for already combined [B][feat_dim][T] features");
+  const long long big = std::max<long long>(std::max(c.feat_dim, 3 * c.channels), kSpOut);
+  if ((long long)B * T * big >= (1ll << 31) || B > 65535) return h->fail(US_EINVAL, what + ": B * T * channels too large");
+  const int rc = h->all_loaded(what.c_str());
+  if (rc != US_OK) return rc;
+  if (!workspace || workspace_bytes < us_speaker_workspace_bytes(h, B, T))
+    return h->fail(US_EWORKSPACE, what + ": workspace too small (us_speaker_workspace_bytes)");
+  if (h->dirty) sp_prepare(h, s);
+  return US_OK;
 }
 
 }  // namespace
@@ -616,75 +774,39 @@ size_t us_speaker_workspace_bytes(us_speaker_handle h, int B, int T) {
 int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, int B, int T, float* emb_out, int normalize, void* workspace,
                        size_t workspace_bytes, us_stream stream) {
   if (!h || !hidden_states || !emb_out || B <= 0 || T <= 0 || L < 0) return WeightTable::fail(h, US_EINVAL, "us_speaker_forward: bad argument");
-  const auto& c = h->cfg;
-  if (L != 0 && L != c.n_layers)
-    return h->fail(US_EINVAL, "us_speaker_forward: L must be the configuration's n_layers (" + std::to_string(c.n_layers) +
-                                  "), or 0 for already combined [B][feat_dim][T] features");
   if (normalize && B != 1) return h->fail(US_EINVAL, "us_speaker_forward: normalize divides the whole output by its norm and is defined for B = 1");
-  const long long big = std::max<long long>(std::max(c.feat_dim, 3 * c.channels), kSpOut);
-  if ((long long)B * T * big >= (1ll << 31) || B > 65535) return h->fail(US_EINVAL, "us_speaker_forward: B * T * channels too large");
-  const int rc = h->all_loaded("us_speaker_forward");
-  if (rc != US_OK) return rc;
-  if (!workspace || workspace_bytes < us_speaker_workspace_bytes(h, B, T))
-    return h->fail(US_EWORKSPACE, "us_speaker_forward: workspace too small (us_speaker_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->dirty) sp_prepare(h, s);
-  const SpPlan p = sp_plan(c, B, T);
-  float* base = ws_align(workspace);
-  const int ch = c.channels, F = c.feat_dim;
-  auto W = [&](const std::string& k) { return h->w.at(k).dev; };
-  auto rows_grid = [](long long rows) { return dim3((unsigned)((rows + 3) / 4)); };
-  // get_feat (:261-271)
-  float* X0 = base + p.x0;
-  if (L > 0) {
-    hipLaunchKernelGGL(sp_combine_kernel, dim3((F + kCmbC - 1) / kCmbC, (T + kCmbT - 1) / kCmbT, B), dim3(256), 0, s, hidden_states, h->lw, X0, L,
-                       B, T, F);
-    hipLaunchKernelGGL(sp_instnorm_kernel, rows_grid((long long)B * F), dim3(256), 0, s, X0, X0, B * F, T);
-  } else {
-    hipLaunchKernelGGL(sp_instnorm_kernel, rows_grid((long long)B * F), dim3(256), 0, s, hidden_states, X0, B * F, T);
-  }
-  const long long ct = (long long)ch * T;
-  float* O1 = base + p.o1;
-  float* CAT = base + p.cat;
-  float* A = base + p.a;
-  float* R = base + p.r;
-  float* Y = base + p.y;
-  sp_conv(h, s, "layer1.conv", "layer1.bn", kActRelu, X0, (long long)F * T, O1, ct, nullptr, B, T);
-  static const int dils[3] = {2, 3, 4};                       // :225-227
-  for (int blk = 0; blk < 3; ++blk) {
-    const std::string q = "layer" + std::to_string(blk + 2);
-    const float* in = blk == 0 ? O1 : CAT + (size_t)(blk - 1) * ct;
-    const long long in_bs = blk == 0 ? ct : 3 * ct;
-    sp_conv(h, s, q + ".Conv1dReluBn1.conv", q + ".Conv1dReluBn1.bn", kActRelu, in, in_bs, A, ct, nullptr, B, T);
-    const int dil = dils[blk], TT = kRes2W - 2 * kSpStages * dil;
-    const SpRes2& r2 = h->res2.at(q);
-    hipLaunchKernelGGL(sp_res2_kernel, dim3((T + TT - 1) / TT, B), dim3(512), 2 * (size_t)h->width * kRes2W * sizeof(float), s, A, R, r2.wp,
-                       r2.bss, h->width, h->wpad, T, dil, TT);
-    sp_conv(h, s, q + ".Conv1dReluBn2.conv", q + ".Conv1dReluBn2.bn", kActRelu, R, ct, Y, ct, nullptr, B, T);
-    hipLaunchKernelGGL(sp_rowmean_kernel, rows_grid((long long)B * ch), dim3(256), 0, s, Y, base + p.mean, B * ch, T);
-    hipLaunchKernelGGL(sp_se_kernel, dim3(B), dim3(1024), (size_t)(ch + kSpAtt) * sizeof(float), s, base + p.mean, W(q + ".SE_Connect.linear1.weight"),
-                       W(q + ".SE_Connect.linear1.bias"), W(q + ".SE_Connect.linear2.weight"), W(q + ".SE_Connect.linear2.bias"), base + p.s, ch);
-    hipLaunchKernelGGL(sp_scale_res_kernel, dim3((unsigned)std::min<long long>((ct + 255) / 256, 2048), B), dim3(256), 0, s, Y, base + p.s, in,
-                       CAT + (size_t)blk * ct, ch, T, in_bs, 3 * ct);
-  }
-  float* BIG = base + p.big;
-  sp_conv(h, s, "conv", "", kActRelu, CAT, 3 * ct, BIG, (long long)kSpOut * T, nullptr, B, T);
-  const float* bias2 = nullptr;
-  if (c.global_context_att) {
-    hipLaunchKernelGGL(sp_rowstats_kernel, rows_grid((long long)B * kSpOut), dim3(256), 0, s, BIG, base + p.ctx, kSpOut, B * kSpOut, T);
-    hipLaunchKernelGGL(sp_ctx_bias_kernel, dim3(B), dim3(1024), 0, s, base + p.ctx, W("pooling.linear1.weight"), base + p.b2, kSpOut);
-    bias2 = base + p.b2;
-  }
-  sp_conv(h, s, "pooling.linear1", "", kActTanh, BIG, (long long)kSpOut * T, base + p.att, (long long)kSpAtt * T, bias2, B, T);
-  sp_conv(h, s, "pooling.linear2", "", kActNone, base + p.att, (long long)kSpAtt * T, base + p.e, (long long)kSpOut * T, nullptr, B, T);
-  const SpBn& fb = h->bn.at("bn");
-  hipLaunchKernelGGL(sp_pool_kernel, rows_grid((long long)B * kSpOut), dim3(256), 0, s, BIG, base + p.e, fb.scale, fb.scale + fb.n, base + p.praw,
-                     base + p.pbn, kSpOut, B * kSpOut, T);
-  hipLaunchKernelGGL(sp_linear_kernel, rows_grid((long long)B * c.emb_dim), dim3(256), 0, s, base + p.pbn, W("linear.weight"), W("linear.bias"),
-                     emb_out, B, 2 * kSpOut, c.emb_dim);
-  if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(1), dim3(256), 0, s, emb_out, B * c.emb_dim);
+  const int rc = sp_forward_checks(h, "us_speaker_forward", L, B, T, workspace, workspace_bytes, s);
+  if (rc != US_OK) return rc;
+  sp_run(h, s, hidden_states, L, B, T, 0, B, SpSameT{}, ws_align(workspace), sp_plan(h->cfg, B, T), emb_out);
+  if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(1), dim3(256), 0, s, emb_out, B * h->cfg.emb_dim);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_speaker_forward", e);
+}
+
+int us_speaker_forward_lengths(us_speaker_handle h, const float* hidden_states, int L, int B, int Tmax, const int64_t* lengths, float* emb_out,
+                               int normalize, void* workspace, size_t workspace_bytes, us_stream stream) {
+  if (!h || !hidden_states || !emb_out || B <= 0 || Tmax <= 0 || L < 0)
+    return WeightTable::fail(h, US_EINVAL, "us_speaker_forward_lengths: bad argument");
+  if (!lengths) return h->fail(US_EINVAL, "us_speaker_forward_lengths: lengths is null (B host values in [1, Tmax]; us_speaker_forward is the uniform call)");
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 1 || lengths[b] > Tmax)
+      return h->fail(US_EINVAL, "us_speaker_forward_lengths: lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
+                                    " must be at least 1 and at most Tmax = " + std::to_string(Tmax));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = sp_forward_checks(h, "us_speaker_forward_lengths", L, B, Tmax, workspace, workspace_bytes, s);
+  if (rc != US_OK) return rc;
+  const SpPlan p = sp_plan(h->cfg, B, Tmax);
+  float* base = ws_align(workspace);
+  for (int b0 = 0; b0 < B; b0 += kSpItems) {
+    const int nb = std::min(kSpItems, B - b0);
+    SpLens lens{};
+    for (int i = 0; i < kSpItems; ++i) lens.n[i] = i < nb ? (int)lengths[b0 + i] : 1;
+    sp_run(h, s, hidden_states, L, B, Tmax, b0, nb, lens, base, p, emb_out);
+  }
+  if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(B), dim3(256), 0, s, emb_out, h->cfg.emb_dim);      // each row by its own norm
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip("us_speaker_forward_lengths", e);
 }
 
 int us_speaker_debug_conv(us_speaker_handle h, const char* prefix, const char* bn_prefix, int act, const float* in, int64_t in_bs, float* out,
@@ -708,7 +830,7 @@ int us_speaker_debug_conv(us_speaker_handle h, const char* prefix, const char* b
   if (rc != US_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->dirty) sp_prepare(h, s);
-  sp_conv(h, s, p, bn, act, in, in_bs, out, out_bs, bias2, B, T);
+  sp_conv(h, s, p, bn, act, in, in_bs, out, out_bs, bias2, B, T, SpSameT{});
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_speaker_debug_conv", e);
 }

@@ -7,6 +7,8 @@ put in front with `attach_upstream`, after which `forward(wav)` is the reference
 The torch modules below only hold parameters; the arithmetic is `csrc/speaker.hip`.
 
 `forward_features(hidden_states)` is the entry point: `[L, B, T, C]`, a list of L `[B, T, C]`, or an already combined `[B, C, T]`.
+With `lengths` (valid frames per item) the batch is ragged: nothing past an item's end reaches its embedding, and each row has the
+bits the item gives when it runs alone (`us_speaker_forward_lengths`).
 There is no CPU fallback: tensors must live on a ROCm device.
 """
 from __future__ import annotations
@@ -145,28 +147,46 @@ class ECAPA_TDNN(HandleModule):
             raise ValueError(f"ECAPA_TDNN: expected [L, B, T, C] or [B, C, T], got {tuple(x.shape)}")
         return x.detach().to(dtype=torch.float32).contiguous(), int(L), int(B), int(T)
 
+    @staticmethod
+    def _lengths(lengths, B, what):
+        """-> the B per-item lengths as Python ints (the library checks their range and names the item)."""
+        v = [int(i) for i in (lengths.reshape(-1).tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
+        if len(v) != B:
+            raise ValueError(f"ECAPA_TDNN.{what}: {len(v)} lengths for {B} items" + (f" (item {len(v)} has none)" if len(v) < B else ""))
+        return v
+
     @torch.no_grad()
-    def _run(self, hidden_states, normalize: bool):
+    def _run(self, hidden_states, normalize: bool, lengths=None, what="forward_features"):
         x, L, B, T = self._input(hidden_states)
+        if lengths is not None:
+            lengths = self._lengths(lengths, B, what)
         device = x.device
         lib, stream = self._sync(device)
         out = torch.empty(B, self.emb_dim, device=device)
         ws = self._workspace(lib, device, B, T)
         with torch.cuda.device(device):
-            rc = lib.us_speaker_forward(self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), ws.data_ptr(), ws.numel(), stream)
-        self._check(lib, rc, "us_speaker_forward")
+            if lengths is None:
+                rc = lib.us_speaker_forward(self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), ws.data_ptr(), ws.numel(), stream)
+            else:
+                rc = lib.us_speaker_forward_lengths(self._h, x.data_ptr(), L, B, T, (C.c_int64 * B)(*lengths), out.data_ptr(), int(normalize),
+                                                    ws.data_ptr(), ws.numel(), stream)
+        self._check(lib, rc, "us_speaker_forward" if lengths is None else "us_speaker_forward_lengths")
         self._last = (B, T)
         return out
 
-    def forward_features(self, hidden_states):
-        """`ECAPA_TDNN.forward` (:274-287) from `get_feat`'s input on: -> [B, emb_dim]."""
-        return self._run(hidden_states, False)
+    def forward_features(self, hidden_states, lengths=None):
+        """`ECAPA_TDNN.forward` (:274-287) from `get_feat`'s input on: -> [B, emb_dim].  `lengths` (B values in [1, T], a list or a tensor):
+        item b is valid on its first lengths[b] frames of the padded T, whatever lies past them (NaN included) is never used, and row b
+        has the bits of `forward_features` on that item alone."""
+        return self._run(hidden_states, False, lengths)
 
-    def embed(self, hidden_states):
-        """finetune.py:106-110: the embedding of one utterance divided by its norm, [1, emb_dim]."""
-        if self._input(hidden_states)[2] != 1:
-            raise ValueError("ECAPA_TDNN.embed: one utterance at a time (the norm is taken over the whole output)")
-        return self._run(hidden_states, True)
+    def embed(self, hidden_states, lengths=None):
+        """finetune.py:106-110: the embedding of one utterance divided by its norm, [1, emb_dim].  With `lengths`: a ragged batch, each row
+        divided by its own norm, [B, emb_dim]."""
+        if lengths is None and self._input(hidden_states)[2] != 1:
+            raise ValueError("ECAPA_TDNN.embed: one utterance at a time (the norm is taken over the whole output): item 1 is one too many; "
+                             "give `lengths` for a batch, which divides each row by its own norm")
+        return self._run(hidden_states, True, lengths, "embed")
 
     @torch.no_grad()
     def debug_conv(self, prefix, x, bn_prefix=None, act=None, bias2=None, out=None):
@@ -228,25 +248,39 @@ class ECAPA_TDNN(HandleModule):
         _, hs = self.upstream(wav, lengths, output_hidden_states=True, normalize=self._upstream_normalize, layers_first=True)
         return hs
 
+    def _frames(self, wav, lengths):
+        """samples per item -> the upstream's frames per item (None stays None)"""
+        if lengths is None:
+            return None
+        return [self.upstream.frames(n) for n in self._lengths(lengths, wav.shape[0], "forward")]
+
     def forward(self, x, lengths=None):
+        """`ECAPA_TDNN.forward(wav)` (:248-287): wav [B, T] at 16 kHz -> [B, emb_dim].  `lengths` are samples per item: the upstream runs
+        ragged and the trunk runs over `upstream.frames(lengths[b])` frames of item b, so row b is what the item gives alone.  (Before the
+        trunk took lengths, this call ran it over all frames of the padded batch, and the padded frames entered the statistics of the
+        shorter items; no caller relied on those numbers.)"""
         if self.upstream is None:
             raise NotImplementedError("ECAPA_TDNN.forward(wav) needs the upstream feature extractor (WavLM / HuBERT through s3prl, or fbank / mfcc), "
                                       "which is outside this library: run the upstream and call forward_features(hidden_states)")
-        return self._run(self._hidden_states(x, lengths), False)
+        return self._run(self._hidden_states(x, lengths), False, self._frames(x, lengths), "forward")
 
-    def embed_wav(self, wav):
-        """finetune.py:113-117: the embedding of one 16 kHz utterance [1, T] divided by its norm, [1, emb_dim]."""
+    def embed_wav(self, wav, lengths=None):
+        """finetune.py:113-117: the embedding of one 16 kHz utterance [1, T] divided by its norm, [1, emb_dim].  With `lengths` (samples per
+        item): a padded batch [B, T], each row divided by its own norm."""
         if self.upstream is None:
             raise NotImplementedError("ECAPA_TDNN.embed_wav needs an upstream: attach_upstream(WavLMModel), or run the upstream and call "
                                       "embed(hidden_states)")
-        if wav.dim() != 2 or wav.shape[0] != 1:
-            raise ValueError("ECAPA_TDNN.embed_wav: one utterance [1, T] at a time (the norm is taken over the whole output)")
-        return self._run(self._hidden_states(wav), True)
+        if wav.dim() != 2 or (lengths is None and wav.shape[0] != 1):
+            raise ValueError("ECAPA_TDNN.embed_wav: one utterance [1, T] at a time (the norm is taken over the whole output), or a padded "
+                             "batch [B, T] with `lengths`")
+        return self._run(self._hidden_states(wav, lengths), True, self._frames(wav, lengths), "embed_wav")
 
     @torch.no_grad()
     def stage(self, name: str) -> torch.Tensor:
         """An intermediate of the last forward_features call (a copy): `feat` [B, C, T] after get_feat, `layer1` [B, channels, T],
-        `blocks` [B, 3 channels, T] (layer2, layer3, layer4 along the channels) and `pooling` [B, 3072] before `bn`."""
+        `blocks` [B, 3 channels, T] (layer2, layer3, layer4 along the channels) and `pooling` [B, 3072] before `bn`.  After a call with
+        `lengths`, T is the padded length and only the first lengths[b] frames of item b are defined (`feat` is 0 past them, the others hold
+        whatever the workspace held)."""
         lib = _lib.load()
         B, T = self._last
         ptr, shape = C.c_void_p(), (C.c_int64 * 3)()
