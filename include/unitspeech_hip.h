@@ -440,6 +440,14 @@ size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T);
 /* `BigVGAN.forward(mel)` (:169-191): mel [B][num_mels][T] -> wav [B][1][T * prod(upsample_rates)]. */
 int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
                        us_stream stream);
+/* The same on a ragged batch: mel [B][num_mels][Tmax], of which item b is valid on its first lengths[b] frames; `lengths` is a HOST
+ * array of B values in [1, Tmax] (null or a value outside that range: US_EINVAL naming the item, before anything is enqueued).  wav
+ * [B][1][Tmax * hop]: item b's first lengths[b] * hop samples have exactly the bits us_vocoder_forward gives for that item alone at
+ * T = lengths[b], and the samples past them are 0.0f.  Nothing at or past an item's end is read: the mel there and the whole workspace
+ * may hold anything, NaN included.  Workspace: us_vocoder_workspace_bytes(h, B, Tmax).  Allocates nothing, copies nothing, only enqueues
+ * (the lengths travel as kernel arguments, 32 items per launch), and B is not bound by us_vocoder_forward's B * channels <= 65535. */
+int us_vocoder_forward_lengths(us_vocoder_handle h, const float* mel, const int64_t* lengths, float* wav, int B, int Tmax,
+                               void* workspace, size_t workspace_bytes, us_stream stream);
 /* One layer of the vocoder on its own, through the launch the forward uses (layer-level parity tests).  prefix names
  *  - a convolution: "conv_pre", "ups.<i>.0", "resblocks.<n>.convs1.<l>", "resblocks.<n>.convs2.<l>": in [B][Cin][Tin] -> out
  *    [B][Cout][Tin * rate] (rate 1 for a Conv1d) = conv(in) + bias, then + res, then sum + that, then / div, each only when given
@@ -450,6 +458,11 @@ int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B,
  * apply to the layer's own tensors.  Needs every weight loaded; takes no workspace. */
 int us_vocoder_debug_layer(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div, float* out,
                            int B, int Tin, us_stream stream);
+/* us_vocoder_debug_layer on a ragged batch, through the launches us_vocoder_forward_lengths uses: rows are Tin_max (Tin_max * rate for
+ * the output of an up-sampler) apart and item b has lengths[b] input steps (HOST array, B values in [1, Tin_max]).  A convolution or an
+ * Activation1d leaves `out` untouched at and past an item's end; "conv_post" writes 0.0f there. */
+int us_vocoder_debug_layer_lengths(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div,
+                                   float* out, int B, int Tin_max, const int64_t* lengths, us_stream stream);
 
 /* ---- ECAPA-TDNN speaker encoder (unitspeech/speaker_encoder/ecapa_tdnn.py:164-287, eval mode) --------------------------------
  * The upstream model's hidden states [L][B][T][feat_dim] -> embedding [B][emb_dim]: the softmax(feature_weight)-weighted sum of the L

@@ -146,6 +146,10 @@ SIGNATURES = {
     "us_vocoder_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_vocoder_debug_layer": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p]),
+    "us_vocoder_forward_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
+    "us_vocoder_debug_layer_lengths": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int,
+                                                 C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
     "us_speaker_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_speaker_config)]),
     "us_speaker_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_speaker_forward_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_int, C.c_void_p,

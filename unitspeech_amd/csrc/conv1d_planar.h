@@ -34,6 +34,7 @@ struct PlanarConvTile {       // what one workgroup of 256 threads multiplies
   int Cin, T, dil, off;
   int Kdim, Kpad, ldw;        // Kdim = taps * Cin live rows of w
   int m0, n0;                 // first output channel and first output step
+  int n = 0;                  // valid steps of every row (rows stay T apart): read by the VALID main loop only, in[] = 0 outside [0, n)
 };
 
 // The main loop.  The workgroup's tile is kPcBM channels x 64 NSUB steps; wave (mh, nh) = (wave & 1, wave >> 1) owns channels
@@ -42,7 +43,9 @@ struct PlanarConvTile {       // what one workgroup of 256 threads multiplies
 // K slices of kPcBK are double-buffered in LDS: the next slice's global loads are in flight while this one is multiplied.
 // STRIDE > 1 is the strided convolution D[co][q] = sum P[j * Cin + ci][co] * in[ci][STRIDE * q + off + j * dil] (the HuBERT extractor); the
 // default multiplies by a compile-time 1, so every other instantiation's code is what it was.
-template <int NSUB, int NCHAIN, int STRIDE = 1>
+// VALID bounds the input loads by the tile's valid length g.n instead of its row stride g.T (a ragged batch item: n steps stored T apart, so
+// nothing at or past an item's end is ever read and no producer has to write zeros there); the default never looks at g.n.
+template <int NSUB, int NCHAIN, int STRIDE = 1, bool VALID = false>
 __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f32x16 (&acc)[NSUB][NCHAIN]) {
   constexpr int BN = 64 * NSUB, NX = BN / 16;
   __shared__ float As[2][kPcBK][kPcBM];
@@ -63,10 +66,11 @@ __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f3
     const int j = live ? kk / g.Cin : 0, ci = live ? kk - j * g.Cin : 0;
     const float* row = in + (size_t)ci * g.T;
     const int t0 = g.n0 * STRIDE + g.off + j * g.dil;
+    const int end = VALID ? g.n : g.T;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
       const int t = t0 + (xc + 16 * i) * STRIDE;
-      xreg[i] = (live && t >= 0 && t < g.T) ? row[t] : 0.f;
+      xreg[i] = (live && t >= 0 && t < end) ? row[t] : 0.f;
     }
   };
   auto store = [&](int buf) {

@@ -12,10 +12,19 @@
 //  - vc_act_kernel: one Activation1d (2x up-sampling, Snake / SnakeBeta, low-pass + 2x down-sampling) reading [C][T] once and
 //    writing [C][T] once.
 //  - vc_post_kernel: conv_post (C -> 1, k = 7) as a per-sample fp32 reduction with the tanh in its epilogue.
+//
+// Ragged batches (us_vocoder_forward_lengths): each of the three kernels is a template over how it learns an item's length.  VcSameT is
+// the uniform call: the length is the row stride, and the instantiation is the kernel as it was.  VcLens carries the lengths of up to
+// kVcItems items as a kernel argument (one scalar load per workgroup, indexed by the block's item): item b is then a tensor of lens.n[b]
+// steps stored with the padded row stride.  Every read along time is bounded or clamped by the item's own length, so nothing at or past
+// an item's end is read and nothing there is written (conv_post alone writes zeros over the padded tail of the waveform); the time
+// tiles start where they start when the item runs alone and BigVGAN has no reduction along time, so the item's samples have the bits of
+// the uniform call on the item alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <map>
 #include <string>
 #include <vector>
@@ -35,6 +44,20 @@ namespace {
 // (two 32-step sub-tiles, one accumulator chain each).
 constexpr int kVcBN = 128;    // output steps per workgroup
 
+// ---- how a kernel learns the valid steps of batch item b (rows are the padded length apart either way) ---------------------------
+constexpr int kVcItems = 32;  // batch items per launch of the ragged form: their lengths travel as kernel arguments
+
+struct VcSameT {              // us_vocoder_forward: every item has T steps
+  static constexpr bool ragged = false;
+  __device__ __forceinline__ int operator()(int, int T) const { return T; }
+};
+
+struct VcLens {               // us_vocoder_forward_lengths: item b of the launch has n[b] steps at this level, 1 <= n[b] <= T
+  static constexpr bool ragged = true;
+  int n[kVcItems];
+  __device__ __forceinline__ int operator()(int b, int) const { return n[b]; }
+};
+
 struct VcConvArgs {
   const float* in;            // [B][Cin][Tin]
   const float* w;             // [nph][Kpad][ldw]
@@ -49,21 +72,30 @@ struct VcConvArgs {
   int off[kPcMaxPhases];
 };
 
-__global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a) {
+// Uniform grid: (time tiles, channel tiles, B * phases).  Ragged grid: (time tiles, channel tiles * phases, items of the launch), so the
+// batch is not capped by a grid dimension.  Ragged: Tin / Tout are the padded row strides and item b has n = lens.n[b] input steps; the
+// main loop takes in[] as zero at or past n, a workgroup whose 128 steps all lie at or past n returns before its first barrier (the
+// test is workgroup-uniform), and no step at or past n is stored.
+template <class LN>
+__global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a, LN lens) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
-  const int b = blockIdx.z / a.nph, ph = blockIdx.z - b * a.nph;
-  const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kVcBN;
+  const int b = LN::ragged ? blockIdx.z : blockIdx.z / a.nph;
+  const int mt = LN::ragged ? blockIdx.y / a.nph : blockIdx.y;
+  const int ph = LN::ragged ? blockIdx.y - mt * a.nph : blockIdx.z - b * a.nph;
+  const int m0 = mt * kPcBM, n0 = blockIdx.x * kVcBN;
+  const int nv = lens(b, a.Tin);
+  if (LN::ragged && n0 >= nv) return;
   f32x16 acc[2][1];
-  planar_conv_mainloop<2, 1>({a.in + (size_t)b * a.Cin * a.Tin, a.w + (size_t)ph * a.Kpad * a.ldw, a.Cin, a.Tin, a.dil, a.off[ph], a.Kdim,
-                              a.Kpad, a.ldw, m0, n0},
-                             acc);
+  planar_conv_mainloop<2, 1, 1, LN::ragged>({a.in + (size_t)b * a.Cin * a.Tin, a.w + (size_t)ph * a.Kpad * a.ldw, a.Cin, a.Tin, a.dil,
+                                             a.off[ph], a.Kdim, a.Kpad, a.ldw, m0, n0, nv},
+                                            acc);
   float* out = a.out + (size_t)b * a.Cout * a.Tout;        // not __restrict__: res / sum may alias it
   const size_t bo = (size_t)b * a.Cout * a.Tout;
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     const int q = n0 + nh * 64 + n * 32 + cl;
-    if (q >= a.Tin) continue;
+    if (q >= nv) continue;
     const int t = q * a.ostride + ph;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -87,16 +119,22 @@ __global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a) {
 // then v = act(u), and LowPassFilter1d(stride 2) replicate-pads v by (5, 6):   out[n] = sum_{j < 12} g[j] * v[clamp(2n + j - 5, 0, 2T - 1)].
 // A workgroup makes kActN outputs of one (b, c) row: it stages x(n0 - 6 .. n0 + kActN + 5) and v(clamp(2 n0 - 6 .. 2 n0 + 2 kActN + 5))
 // in LDS; every index those formulas touch lies in those windows.
+// Uniform grid: (tiles, B * C).  Ragged grid: (tiles, C, items of the launch); T is the padded row stride and the item's n takes its place
+// in both replicate clamps (the sequence's last sample is the item's, not the padding's) and in the store bound; a tile at or past n returns.
 constexpr int kActN = 256;
 
+template <class LN>
 __global__ __launch_bounds__(256) void vc_act_kernel(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ ab,
-                                                     const float* __restrict__ fup, const float* __restrict__ fdown, int C, int T) {
+                                                     const float* __restrict__ fup, const float* __restrict__ fdown, int C, int Trow, LN lens) {
   __shared__ float xs[kActN + 12];
   __shared__ float vs[2 * kActN + 12];
   __shared__ float f[24];
-  const int row = blockIdx.y, c = row % C;
+  const int row = LN::ragged ? blockIdx.z * C + blockIdx.y : blockIdx.y;
+  const int c = LN::ragged ? blockIdx.y : row % C;
   const int n0 = blockIdx.x * kActN;
-  const float* __restrict__ xr = x + (size_t)row * T;
+  const int T = lens(LN::ragged ? blockIdx.z : 0, Trow);
+  if (LN::ragged && n0 >= T) return;
+  const float* __restrict__ xr = x + (size_t)row * Trow;
   if (threadIdx.x < 12) {
     f[threadIdx.x] = fup[threadIdx.x];
     f[12 + threadIdx.x] = fdown[threadIdx.x];
@@ -121,7 +159,7 @@ __global__ __launch_bounds__(256) void vc_act_kernel(const float* __restrict__ x
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 12; ++j) acc = fmaf(f[12 + j], vs[2 * l + j + 1], acc);
-    out[(size_t)row * T + n0 + l] = acc;
+    out[(size_t)row * Trow + n0 + l] = acc;
   }
 }
 
@@ -138,24 +176,32 @@ __global__ void vc_snake_param_kernel(const float* __restrict__ p, float* __rest
 // ---- conv_post: Conv1d(C, 1, 7, padding 3) + tanh --------------------------------------------------------------------------------
 constexpr int kPostK = 7;
 
+// Ragged: Trow is the padded row stride, the item's n takes T's place in the zero padding, and the samples on [n, Trow) are written as
+// 0.0f, so the whole returned waveform is defined.
+template <class LN>
 __global__ __launch_bounds__(256) void vc_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                      float* __restrict__ out, int C, int T) {
+                                                      float* __restrict__ out, int C, int Trow, LN lens) {
   extern __shared__ float ws[];
   for (int i = threadIdx.x; i < C * kPostK; i += blockDim.x) ws[i] = w[i];
   __syncthreads();
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
-  const float* __restrict__ xb = x + (size_t)b * C * T;
+  if (t >= Trow) return;
+  const int T = lens(b, Trow);
+  if (LN::ragged && t >= T) {
+    out[(size_t)b * Trow + t] = 0.f;
+    return;
+  }
+  const float* __restrict__ xb = x + (size_t)b * C * Trow;
   float acc = 0.f;
   for (int ci = 0; ci < C; ++ci) {
-    const float* xr = xb + (size_t)ci * T;
+    const float* xr = xb + (size_t)ci * Trow;
 #pragma unroll
     for (int j = 0; j < kPostK; ++j) {
       const int tt = t + j - kPostK / 2;
       if (tt >= 0 && tt < T) acc = fmaf(ws[ci * kPostK + j], xr[tt], acc);
     }
   }
-  out[(size_t)b * T + t] = tanhf(acc + bias[0]);
+  out[(size_t)b * Trow + t] = tanhf(acc + bias[0]);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -239,8 +285,24 @@ long long vc_max_ct(const us_vocoder_config& c, int T) {
 
 constexpr int kVcBuffers = 5;      // level input, AMP sum, residual stream, activation output, first-conv output
 
+// Ragged launches: `lengths` (host, or null for the uniform call) counts item b's steps in units of which this level has `rate` each; one
+// launch per kVcItems items, its time tiles covering the longest of them.
+template <class F>
+void vc_groups(int B, const int64_t* lengths, long long rate, F&& launch) {
+  for (int b0 = 0; b0 < B; b0 += kVcItems) {
+    const int nb = std::min(kVcItems, B - b0);
+    VcLens lens{};
+    int longest = 1;
+    for (int i = 0; i < kVcItems; ++i) {
+      lens.n[i] = i < nb ? (int)(lengths[b0 + i] * rate) : 1;
+      longest = std::max(longest, lens.n[i]);
+    }
+    launch(b0, nb, longest, lens);
+  }
+}
+
 void conv(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, const float* res, const float* sum, float div,
-          int B, int Tin) {
+          int B, int Tin, const int64_t* lengths = nullptr, long long rate = 1) {
   const PlanarConv& c = h->conv.at(p);
   VcConvArgs a{};
   a.in = in; a.w = c.packed; a.bias = h->w.at(p + ".bias").dev; a.res = res; a.sum = sum; a.out = out;
@@ -248,19 +310,115 @@ void conv(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, f
   a.dil = c.dil; a.Kdim = c.Kdim(); a.Kpad = c.Kpad; a.ldw = c.ldw;
   a.nph = c.nph; a.ostride = c.nph; a.div = div;
   for (int r = 0; r < c.nph; ++r) a.off[r] = c.off[r];
-  hipLaunchKernelGGL(vc_conv_kernel, dim3((Tin + kVcBN - 1) / kVcBN, (c.cout + kPcBM - 1) / kPcBM, B * c.nph), dim3(256), 0, s, a);
+  const int mt = (c.cout + kPcBM - 1) / kPcBM;
+  if (!lengths) {
+    hipLaunchKernelGGL(vc_conv_kernel<VcSameT>, dim3((Tin + kVcBN - 1) / kVcBN, mt, B * c.nph), dim3(256), 0, s, a, VcSameT{});
+    return;
+  }
+  vc_groups(B, lengths, rate, [&](int b0, int nb, int longest, const VcLens& lens) {
+    VcConvArgs g = a;
+    const size_t io = (size_t)b0 * c.cin * Tin, oo = (size_t)b0 * c.cout * a.Tout;
+    g.in = in + io; g.out = out + oo;
+    if (res) g.res = res + oo;
+    if (sum) g.sum = sum + oo;
+    hipLaunchKernelGGL(vc_conv_kernel<VcLens>, dim3((longest + kVcBN - 1) / kVcBN, mt * c.nph, nb), dim3(256), 0, s, g, lens);
+  });
 }
 
-void activation(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, int B, int T) {
+void activation(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, int B, int T,
+                const int64_t* lengths = nullptr, long long rate = 1) {
   const VcAct& a = h->act.at(p);
-  hipLaunchKernelGGL(vc_act_kernel, dim3((T + kActN - 1) / kActN, B * a.C), dim3(256), 0, s, in, out, a.ab,
-                     h->w.at(p + ".upsample.filter").dev, h->w.at(p + ".downsample.lowpass.filter").dev, a.C, T);
+  const float* fup = h->w.at(p + ".upsample.filter").dev;
+  const float* fdown = h->w.at(p + ".downsample.lowpass.filter").dev;
+  if (!lengths) {
+    hipLaunchKernelGGL(vc_act_kernel<VcSameT>, dim3((T + kActN - 1) / kActN, B * a.C), dim3(256), 0, s, in, out, a.ab, fup, fdown, a.C, T,
+                       VcSameT{});
+    return;
+  }
+  vc_groups(B, lengths, rate, [&](int b0, int nb, int longest, const VcLens& lens) {
+    const size_t o = (size_t)b0 * a.C * T;
+    hipLaunchKernelGGL(vc_act_kernel<VcLens>, dim3((longest + kActN - 1) / kActN, a.C, nb), dim3(256), 0, s, in + o, out + o, a.ab, fup,
+                       fdown, a.C, T, lens);
+  });
 }
 
-void post(us_vocoder* h, hipStream_t s, const float* in, float* out, int B, int T) {
+void post(us_vocoder* h, hipStream_t s, const float* in, float* out, int B, int T, const int64_t* lengths = nullptr, long long rate = 1) {
   const int ch = channels(h->cfg, h->cfg.n_up);
-  hipLaunchKernelGGL(vc_post_kernel, dim3((T + 255) / 256, B), dim3(256), (size_t)ch * kPostK * sizeof(float), s, in,
-                     h->w.at("conv_post.weight").dev, h->w.at("conv_post.bias").dev, out, ch, T);
+  const size_t lds = (size_t)ch * kPostK * sizeof(float);
+  const float* w = h->w.at("conv_post.weight").dev;
+  const float* bias = h->w.at("conv_post.bias").dev;
+  if (!lengths) {
+    hipLaunchKernelGGL(vc_post_kernel<VcSameT>, dim3((T + 255) / 256, B), dim3(256), lds, s, in, w, bias, out, ch, T, VcSameT{});
+    return;
+  }
+  // every tile of the padded row is launched: the ones past an item's end write its zeros
+  vc_groups(B, lengths, rate, [&](int b0, int nb, int, const VcLens& lens) {
+    hipLaunchKernelGGL(vc_post_kernel<VcLens>, dim3((T + 255) / 256, nb), dim3(256), lds, s, in + (size_t)b0 * ch * T, w, bias,
+                       out + (size_t)b0 * T, ch, T, lens);
+  });
+}
+
+// null, or a refusal that names the first item whose length is outside [1, Tmax]
+std::string vc_bad_length(const char* what, const int64_t* lengths, int B, int Tmax, const char* tname) {
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 1 || lengths[b] > Tmax)
+      return std::string(what) + ": lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
+             " must be at least 1 and at most " + tname + " = " + std::to_string(Tmax);
+  return std::string();
+}
+
+// BigVGAN.forward (models.py:169-191); lengths null: every item has T frames
+int vc_forward(us_vocoder* h, const char* what, const float* mel, const int64_t* lengths, float* wav, int B, int T, void* workspace,
+               size_t workspace_bytes, us_stream stream) {
+  const std::string name(what);
+  const auto& c = h->cfg;
+  const long long hop = vc_hop(c);
+  if (vc_max_ct(c, T) >= (1ll << 31) || (long long)T * hop >= (1ll << 31))
+    return h->fail(US_EINVAL, name + ": B * channels or T * hop too large");
+  // the uniform launches number the (item, channel) and (item, phase) pairs along one grid dimension; the ragged ones give the item its own
+  if (!lengths && ((long long)B * c.upsample_initial_channel > 65535 || (long long)B * kPcMaxPhases > 65535))
+    return h->fail(US_EINVAL, name + ": B * channels or T * hop too large");
+  const int rc = h->all_loaded(what);
+  if (rc != US_OK) return rc;
+  if (!workspace || workspace_bytes < us_vocoder_workspace_bytes(h, B, T))
+    return h->fail(US_EWORKSPACE, name + ": workspace too small (us_vocoder_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t slab = (size_t)B * (size_t)vc_max_ct(c, T);
+  float* X = ws_align(workspace);     // level input (the up-sampler's output)
+  float* S = X + slab;           // level output: the AMP-block sum (conv_pre writes here too)
+  float* R = S + slab;           // residual stream x_l of the running AMP block (l = 1, 2)
+  float* A = R + slab;           // Activation1d output
+  float* H = A + slab;           // output of the block's first convolution
+  const int64_t* ln = lengths;
+  conv(h, s, "conv_pre", mel, S, nullptr, nullptr, 0.f, B, T, ln, 1);
+  int t = T;
+  long long r = 1;                    // steps per mel frame at this level
+  for (int i = 0; i < c.n_up; ++i) {
+    conv(h, s, "ups." + std::to_string(i) + ".0", S, X, nullptr, nullptr, 0.f, B, t, ln, r);
+    t *= c.upsample_rates[i];
+    r *= c.upsample_rates[i];
+    for (int j = 0; j < c.n_kernels; ++j) {
+      // AMPBlock1.forward (models.py:60-69): x_{l+1} = c2(a2(c1(a1(x_l)))) + x_l, x_0 = the level input
+      const std::string p = "resblocks." + std::to_string(i * c.n_kernels + j);
+      const float* xl = X;
+      for (int l = 0; l < 3; ++l) {
+        const std::string ls = std::to_string(l);
+        activation(h, s, p + ".activations." + std::to_string(2 * l), xl, A, B, t, ln, r);
+        conv(h, s, p + ".convs1." + ls, A, H, nullptr, nullptr, 0.f, B, t, ln, r);
+        activation(h, s, p + ".activations." + std::to_string(2 * l + 1), H, A, B, t, ln, r);
+        if (l < 2) {
+          conv(h, s, p + ".convs2." + ls, A, R, xl, nullptr, 0.f, B, t, ln, r);
+          xl = R;
+        } else {        // the block's output goes straight into the level sum: xs (+)= x_3, then / num_kernels (:180-187)
+          conv(h, s, p + ".convs2." + ls, A, S, xl, j > 0 ? S : nullptr, j == c.n_kernels - 1 ? (float)c.n_kernels : 0.f, B, t, ln, r);
+        }
+      }
+    }
+  }
+  activation(h, s, "activation_post", S, A, B, t, ln, r);
+  post(h, s, A, wav, B, t, ln, r);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip(what, e);
 }
 
 }  // namespace
@@ -358,80 +516,74 @@ size_t us_vocoder_workspace_bytes(us_vocoder_handle h, int B, int T) {
 int us_vocoder_forward(us_vocoder_handle h, const float* mel, float* wav, int B, int T, void* workspace, size_t workspace_bytes,
                        us_stream stream) {
   if (!h || !mel || !wav || B <= 0 || T <= 0) return WeightTable::fail(h, US_EINVAL, "us_vocoder_forward: bad argument");
-  const auto& c = h->cfg;
-  const long long hop = vc_hop(c);
-  if (vc_max_ct(c, T) >= (1ll << 31) || (long long)T * hop >= (1ll << 31) || (long long)B * c.upsample_initial_channel > 65535 ||
-      (long long)B * kPcMaxPhases > 65535)
-    return h->fail(US_EINVAL, "us_vocoder_forward: B * channels or T * hop too large");
-  const int rc = h->all_loaded("us_vocoder_forward");
-  if (rc != US_OK) return rc;
-  if (!workspace || workspace_bytes < us_vocoder_workspace_bytes(h, B, T))
-    return h->fail(US_EWORKSPACE, "us_vocoder_forward: workspace too small (us_vocoder_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t slab = (size_t)B * (size_t)vc_max_ct(c, T);
-  float* X = ws_align(workspace);     // level input (the up-sampler's output)
-  float* S = X + slab;           // level output: the AMP-block sum (conv_pre writes here too)
-  float* R = S + slab;           // residual stream x_l of the running AMP block (l = 1, 2)
-  float* A = R + slab;           // Activation1d output
-  float* H = A + slab;           // output of the block's first convolution
-  conv(h, s, "conv_pre", mel, S, nullptr, nullptr, 0.f, B, T);
-  int t = T;
-  for (int i = 0; i < c.n_up; ++i) {
-    conv(h, s, "ups." + std::to_string(i) + ".0", S, X, nullptr, nullptr, 0.f, B, t);
-    t *= c.upsample_rates[i];
-    for (int j = 0; j < c.n_kernels; ++j) {
-      // AMPBlock1.forward (models.py:60-69): x_{l+1} = c2(a2(c1(a1(x_l)))) + x_l, x_0 = the level input
-      const std::string p = "resblocks." + std::to_string(i * c.n_kernels + j);
-      const float* xl = X;
-      for (int l = 0; l < 3; ++l) {
-        const std::string ls = std::to_string(l);
-        activation(h, s, p + ".activations." + std::to_string(2 * l), xl, A, B, t);
-        conv(h, s, p + ".convs1." + ls, A, H, nullptr, nullptr, 0.f, B, t);
-        activation(h, s, p + ".activations." + std::to_string(2 * l + 1), H, A, B, t);
-        if (l < 2) {
-          conv(h, s, p + ".convs2." + ls, A, R, xl, nullptr, 0.f, B, t);
-          xl = R;
-        } else {        // the block's output goes straight into the level sum: xs (+)= x_3, then / num_kernels (:180-187)
-          conv(h, s, p + ".convs2." + ls, A, S, xl, j > 0 ? S : nullptr, j == c.n_kernels - 1 ? (float)c.n_kernels : 0.f, B, t);
-        }
-      }
-    }
-  }
-  activation(h, s, "activation_post", S, A, B, t);
-  post(h, s, A, wav, B, t);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : h->hip("us_vocoder_forward", e);
+  return vc_forward(h, "us_vocoder_forward", mel, nullptr, wav, B, T, workspace, workspace_bytes, stream);
 }
 
-int us_vocoder_debug_layer(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div, float* out,
-                           int B, int Tin, us_stream stream) {
-  if (!h || !prefix || !in || !out || B <= 0 || Tin <= 0 || !(div >= 0.f))
-    return WeightTable::fail(h, US_EINVAL, "us_vocoder_debug_layer: bad argument");
-  const std::string p(prefix);
+int us_vocoder_forward_lengths(us_vocoder_handle h, const float* mel, const int64_t* lengths, float* wav, int B, int Tmax, void* workspace,
+                               size_t workspace_bytes, us_stream stream) {
+  if (!h || !mel || !wav || B <= 0 || Tmax <= 0) return WeightTable::fail(h, US_EINVAL, "us_vocoder_forward_lengths: bad argument");
+  if (!lengths)
+    return h->fail(US_EINVAL, "us_vocoder_forward_lengths: lengths is null (B host values in [1, Tmax]; us_vocoder_forward is the uniform call)");
+  const std::string bad = vc_bad_length("us_vocoder_forward_lengths", lengths, B, Tmax, "Tmax");
+  if (!bad.empty()) return h->fail(US_EINVAL, bad);
+  return vc_forward(h, "us_vocoder_forward_lengths", mel, lengths, wav, B, Tmax, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+namespace us {
+namespace {
+
+// one layer alone; lengths null: every item has Tin steps
+int vc_debug_layer(us_vocoder* h, const char* what, const char* prefix, const float* in, const float* res, const float* sum, float div,
+                   float* out, int B, int Tin, const int64_t* lengths, us_stream stream) {
+  const std::string name(what), p(prefix);
   const auto ci = h->conv.find(p);
   const bool is_act = h->act.count(p) != 0, is_post = p == "conv_post";
-  if (ci == h->conv.end() && !is_act && !is_post) return h->fail(US_ENOKEY, "us_vocoder_debug_layer: unknown layer '" + p + "'");
+  if (ci == h->conv.end() && !is_act && !is_post) return h->fail(US_ENOKEY, name + ": unknown layer '" + p + "'");
   if (ci == h->conv.end() && (res || sum || div != 0.f))
-    return h->fail(US_EINVAL, "us_vocoder_debug_layer: res / sum / div belong to a convolution's epilogue; '" + p + "' is not one");
+    return h->fail(US_EINVAL, name + ": res / sum / div belong to a convolution's epilogue; '" + p + "' is not one");
   // the largest C * T this layer reads or writes, under us_vocoder_forward's limits
   long long ct;
   if (ci != h->conv.end())
     ct = std::max((long long)ci->second.cin * Tin, (long long)ci->second.cout * Tin * ci->second.nph);
   else
     ct = (long long)(is_act ? h->act.at(p).C : channels(h->cfg, h->cfg.n_up)) * Tin;
-  if (ct >= (1ll << 31) || (long long)B * h->cfg.upsample_initial_channel > 65535 || (long long)B * kPcMaxPhases > 65535)
-    return h->fail(US_EINVAL, "us_vocoder_debug_layer: B * channels or C * T too large");
-  const int rc = h->all_loaded("us_vocoder_debug_layer");
+  if (ct >= (1ll << 31) || (!lengths && ((long long)B * h->cfg.upsample_initial_channel > 65535 || (long long)B * kPcMaxPhases > 65535)))
+    return h->fail(US_EINVAL, name + ": B * channels or C * T too large");
+  const int rc = h->all_loaded(what);
   if (rc != US_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (ci != h->conv.end())
-    conv(h, s, p, in, out, res, sum, div, B, Tin);
+    conv(h, s, p, in, out, res, sum, div, B, Tin, lengths, 1);
   else if (is_act)
-    activation(h, s, p, in, out, B, Tin);
+    activation(h, s, p, in, out, B, Tin, lengths, 1);
   else
-    post(h, s, in, out, B, Tin);
+    post(h, s, in, out, B, Tin, lengths, 1);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : h->hip("us_vocoder_debug_layer", e);
+  return e == hipSuccess ? US_OK : h->hip(what, e);
+}
+
+}  // namespace
+}  // namespace us
+
+extern "C" {
+
+int us_vocoder_debug_layer(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div, float* out,
+                           int B, int Tin, us_stream stream) {
+  if (!h || !prefix || !in || !out || B <= 0 || Tin <= 0 || !(div >= 0.f))
+    return WeightTable::fail(h, US_EINVAL, "us_vocoder_debug_layer: bad argument");
+  return vc_debug_layer(h, "us_vocoder_debug_layer", prefix, in, res, sum, div, out, B, Tin, nullptr, stream);
+}
+
+int us_vocoder_debug_layer_lengths(us_vocoder_handle h, const char* prefix, const float* in, const float* res, const float* sum, float div,
+                                   float* out, int B, int Tin_max, const int64_t* lengths, us_stream stream) {
+  if (!h || !prefix || !in || !out || B <= 0 || Tin_max <= 0 || !(div >= 0.f))
+    return WeightTable::fail(h, US_EINVAL, "us_vocoder_debug_layer_lengths: bad argument");
+  if (!lengths) return h->fail(US_EINVAL, "us_vocoder_debug_layer_lengths: lengths is null (B host values in [1, Tin_max])");
+  const std::string bad = vc_bad_length("us_vocoder_debug_layer_lengths", lengths, B, Tin_max, "Tin_max");
+  if (!bad.empty()) return h->fail(US_EINVAL, bad);
+  return vc_debug_layer(h, "us_vocoder_debug_layer_lengths", prefix, in, res, sum, div, out, B, Tin_max, lengths, stream);
 }
 
 }  // extern "C"

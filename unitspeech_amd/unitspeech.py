@@ -859,14 +859,16 @@ class UnitSpeech(BaseModule):
     @torch.no_grad()
     def execute_text_to_speech(self, phoneme, phoneme_lengths, spk_emb, text_encoder, duration_predictor,
                                num_downsamplings_in_unet, diffusion_steps=50, length_scale=1.0, text_gradient_scale=1.0,
-                               spk_gradient_scale=1.0, *, mel_range=None, **sampler_kw):
+                               spk_gradient_scale=1.0, *, mel_range=None, return_lengths=False, **sampler_kw):
         """`execute_text_to_speech`, unitspeech/unitspeech.py:413-450.  The text encoder and the duration predictor are the
         caller's modules (:421-422); everything between them and the sampler runs in the library: `us_tts_durations`
         (ceil(exp(logw) * x_mask) * length_scale and the frame counts, :424-427), one host read of the longest utterance
         (:428, as in the reference) and `us_tts_align` (`generate_path` + attn^T cond_x + `sequence_mask`, :431-438).
         Returns (encoder_outputs, decoder_outputs, attn) cropped as the reference crops them (its `attn[:, :, :y_max_length]`
         acts on the symbol axis of the 4-D path, :450).  mel_range=(mel_min, mel_max): decoder_outputs de-normalised for the
-        vocoder (inference.py:140)."""
+        vocoder (inference.py:140).  return_lengths=True: a fourth result, `y_lengths` (int64 [B] on the device), the frames of each
+        item: with B > 1 the outputs are cropped to the longest item, and a shorter one holds past its own end the image of masked
+        zeros, which is not silence (`BigVGAN.forward(mel, lengths=y_lengths)` vocodes each item over its own frames)."""
         lib = _lib.load()
         cond_x, x, x_mask = text_encoder(phoneme, phoneme_lengths)
         logw = duration_predictor(x, x_mask, w=None, g=spk_emb, reverse=True)
@@ -890,4 +892,5 @@ class UnitSpeech(BaseModule):
         z = torch.randn_like(cond_y, device=dev)                                    # RNG draw #0 of the reference (:441)
         dec = self.forward(z, y_mask, cond_y, spk_emb, n_timesteps=diffusion_steps, text_gradient_scale=text_gradient_scale,
                            spk_gradient_scale=spk_gradient_scale, mel_range=mel_range, **sampler_kw)
-        return cond_y[:, :, :y_max_length], dec[:, :, :y_max_length], attn[:, :, :y_max_length]
+        out = (cond_y[:, :, :y_max_length], dec[:, :, :y_max_length], attn[:, :, :y_max_length])
+        return out + (y_lengths,) if return_lengths else out

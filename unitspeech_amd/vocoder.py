@@ -1,4 +1,5 @@
-"""BigVGAN vocoder on the HIP library: mel [B, num_mels, T] -> waveform [B, 1, T * hop] (inference).
+"""BigVGAN vocoder on the HIP library: mel [B, num_mels, T] -> waveform [B, 1, T * hop] (inference).  With `lengths` (valid frames per
+item) the batch is ragged: nothing past an item's end reaches its samples, and each item has the bits it has when it runs alone.
 
 Drop-in for the reference's `unitspeech/vocoder/models.py:117-191` `BigVGAN(h)`: the same constructor argument (an `AttrDict`
 or a plain dict of the JSON config), the same module tree and therefore the same `state_dict` keys, shapes and order, in both
@@ -199,28 +200,63 @@ class BigVGAN(HandleModule):
                 out[key] = ((t,), None)
         return out
 
+    @staticmethod
+    def _lengths(lengths, B, what):
+        """-> the B per-item lengths as Python ints (the library checks their range and names the item).  A device tensor is read back
+        here: one synchronisation."""
+        if isinstance(lengths, (torch.Tensor, np.ndarray)):
+            if isinstance(lengths, torch.Tensor):
+                integer = not (lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool)
+            else:
+                integer = lengths.dtype.kind in "iu"
+            if not integer:
+                raise ValueError(f"BigVGAN.{what}: lengths must be integers, got dtype {lengths.dtype}")
+            lengths = lengths.reshape(-1).tolist()
+        v = []
+        for i, n in enumerate(lengths):
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+                raise ValueError(f"BigVGAN.{what}: lengths must be integers, item {i} has {n!r}")
+            v.append(int(n))
+        if len(v) != B:
+            raise ValueError(f"BigVGAN.{what}: {len(v)} lengths for {B} items" + (f" (item {len(v)} has none)" if len(v) < B else ""))
+        return v
+
     @torch.no_grad()
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """mel [B, num_mels, T] -> [B, 1, T * hop].  `lengths` (B frame counts in [1, T]: a list, a host tensor or a device tensor, which
+        costs one synchronisation to read): the batch is ragged, item b is valid on its first lengths[b] frames and whatever lies past
+        them (NaN included) is never read; `out[b, :, :lengths[b] * hop]` has the bits of `forward(x[b:b+1, :, :lengths[b]])` and the
+        samples past it are zeros (`us_vocoder_forward_lengths`)."""
         if x.dim() != 3 or x.shape[1] != self.h.num_mels or x.shape[2] < 1:
             raise ValueError(f"BigVGAN: expected mel [B, {self.h.num_mels}, T], got {tuple(x.shape)}")
+        b, _, t = x.shape
+        if lengths is not None:
+            lengths = self._lengths(lengths, b, "forward")
         device = x.device
         lib, stream = self._sync(device)
-        b, _, t = x.shape
         mel = x.detach().to(dtype=torch.float32).contiguous()
         wav = torch.empty(b, 1, t * self.hop, device=device)
         ws = self._workspace(lib, device, b, t)
         with torch.cuda.device(device):
-            rc = lib.us_vocoder_forward(self._h, mel.data_ptr(), wav.data_ptr(), b, t, ws.data_ptr(), ws.numel(), stream)
-        self._check(lib, rc, "us_vocoder_forward")
+            if lengths is None:
+                rc = lib.us_vocoder_forward(self._h, mel.data_ptr(), wav.data_ptr(), b, t, ws.data_ptr(), ws.numel(), stream)
+            else:
+                rc = lib.us_vocoder_forward_lengths(self._h, mel.data_ptr(), (C.c_int64 * b)(*lengths), wav.data_ptr(), b, t, ws.data_ptr(),
+                                                    ws.numel(), stream)
+        self._check(lib, rc, "us_vocoder_forward" if lengths is None else "us_vocoder_forward_lengths")
         return wav
 
 
     @torch.no_grad()
-    def debug_layer(self, prefix, x, res=None, sum=None, div=0.0, out=None):
+    def debug_layer(self, prefix, x, res=None, sum=None, div=0.0, out=None, lengths=None):
         """One layer alone through the launch `forward` uses (us_vocoder_debug_layer): a convolution (`conv_pre`, `ups.<i>.0`,
         `resblocks.<n>.convs1|convs2.<l>`; with its epilogue's `res`, `sum` and `div`), an Activation1d (`resblocks.<n>.activations.<a>`,
         `activation_post`) or `conv_post` (tanh included).  x [B, C, Tin] -> [B, Cout, Tout]; `out`, `res` and `sum` are contiguous fp32
-        tensors of that shape on x's device and may share storage, as they do in the forward."""
+        tensors of that shape on x's device and may share storage, as they do in the forward.  `lengths` (B input-step counts in [1, Tin],
+        as `forward` takes them): the ragged launch (us_vocoder_debug_layer_lengths); a convolution or an Activation1d then leaves `out`
+        as it was at and past an item's end (give `out` to define it there), and `conv_post` writes zeros there."""
+        if lengths is not None:
+            lengths = self._lengths(lengths, x.shape[0] if x.dim() == 3 else -1, "debug_layer")
         device = x.device
         lib, stream = self._sync(device)
         try:
@@ -248,8 +284,12 @@ class BigVGAN(HandleModule):
                 raise ValueError(f"BigVGAN.debug_layer({prefix}): {name} must be a contiguous fp32 {shape} on {device}")
         ptr = lambda v: None if v is None else v.data_ptr()
         with torch.cuda.device(device):
-            rc = lib.us_vocoder_debug_layer(self._h, prefix.encode(), x.data_ptr(), ptr(res), ptr(sum), float(div), out.data_ptr(), b, t, stream)
-        self._check(lib, rc, f"us_vocoder_debug_layer({prefix})")
+            if lengths is None:
+                rc = lib.us_vocoder_debug_layer(self._h, prefix.encode(), x.data_ptr(), ptr(res), ptr(sum), float(div), out.data_ptr(), b, t, stream)
+            else:
+                rc = lib.us_vocoder_debug_layer_lengths(self._h, prefix.encode(), x.data_ptr(), ptr(res), ptr(sum), float(div), out.data_ptr(), b, t,
+                                                        (C.c_int64 * b)(*lengths), stream)
+        self._check(lib, rc, f"us_vocoder_debug_layer({prefix})" if lengths is None else f"us_vocoder_debug_layer_lengths({prefix})")
         return out
 
 
