@@ -1,5 +1,6 @@
-// The planar Conv1d implicit GEMM on v_mfma_f32_32x32x2_f32 that the vocoder and the speaker encoder share (vc_conv_kernel,
-// sp_conv_kernel): the main loop, the weight pack and the host-side description of a layer.
+// The planar Conv1d implicit GEMM on v_mfma_f32_32x32x2_f32 that the vocoder, the speaker encoder, HuBERT / WavLM, the mel front end and the
+// resampler share (vc_conv_kernel, sp_conv_kernel, hb_gemm_kernel, mel_dft_kernel, mel_proj_kernel, rs_gemm_kernel): the main loop, the lane
+// map (PLANAR_*) its epilogues read, the fold in front of the last three, the weight pack and the host-side description of a layer.
 //
 // Activations are planar [B][C][T] (time contiguous).  Output step q of one batch item and one phase:
 //   D[co][q] = sum_{j < taps, ci < Cin} P[j * Cin + ci][co] * in[ci][q + off + j * dil],   in[] = 0 outside [0, T),
@@ -37,9 +38,23 @@ struct PlanarConvTile {       // what one workgroup of 256 threads multiplies
   int n = 0;                  // valid steps of every row (rows stay T apart): read by the VALID main loop only, in[] = 0 outside [0, n)
 };
 
-// The main loop.  The workgroup's tile is kPcBM channels x 64 NSUB steps; wave (mh, nh) = (wave & 1, wave >> 1) owns channels
-// [32 mh, +32) and the NSUB 32-step sub-tiles from step 32 NSUB nh on.  Sub-tile n accumulates into acc[n][0 .. NCHAIN): MFMA s of
-// a K slice goes to chain s % NCHAIN, so with two chains no MFMA waits on the one before it, and the caller adds the chains up.
+// A thread's place in the 256-thread tile, written once: wave (mh, nh) = (wave & 1, wave >> 1) owns channels [32 mh, +32) and the NSUB 32-step
+// sub-tiles from step 32 NSUB nh on; inside a sub-tile the lane feeds K row kl and column cl of an MFMA and holds, in register r of the
+// accumulator, row mfma32_row(r, kl) of column cl.  The main loop's LDS reads and every epilogue take the channel and the step from these, so
+// the two agree.  They are macros, not functions: the expressions then reach the optimiser inside the kernel, as the lines they replace did
+// (inline functions are optimised on their own first, and every epilogue then compiled to other instructions).  PLANAR_STEP(NSUB, n0, n) and
+// n0 + PLANAR_COL(NSUB, n) are the same number; the first keeps the wave's and the sub-tile's offsets apart, as the vocoder wrote it.
+#define PLANAR_LANE(tid)                          \
+  const int lane = (tid) & 63, wave = (tid) >> 6; \
+  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31
+#define PLANAR_ROW(r) (mh * 32 + mfma32_row(r, kl))                   /* within the tile: the channel of accumulator register r */
+#define PLANAR_COL(NSUB, n) ((nh * (NSUB) + (n)) * 32 + cl)           /* within the tile: the step of sub-tile n */
+#define PLANAR_CHANNEL(m0, r) ((m0) + mh * 32 + mfma32_row(r, kl))    /* in the tensor, for a tile that starts at channel m0 ... */
+#define PLANAR_STEP(NSUB, n0, n) ((n0) + nh * ((NSUB) * 32) + (n) * 32 + cl) /* ... and step n0 */
+
+// The main loop.  The workgroup's tile is kPcBM channels x 64 NSUB steps, shared out among the waves as PLANAR_LANE says.  Sub-tile n
+// accumulates into acc[n][0 .. NCHAIN): MFMA s of a K slice goes to chain s % NCHAIN, so with two chains no MFMA waits on the one before it,
+// and the caller adds the chains up.
 // K slices of kPcBK are double-buffered in LDS: the next slice's global loads are in flight while this one is multiplied.
 // STRIDE > 1 is the strided convolution D[co][q] = sum P[j * Cin + ci][co] * in[ci][STRIDE * q + off + j * dil] (the HuBERT extractor); the
 // default multiplies by a compile-time 1, so every other instantiation's code is what it was.
@@ -50,8 +65,8 @@ __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f3
   constexpr int BN = 64 * NSUB, NX = BN / 16;
   __shared__ float As[2][kPcBK][kPcBM];
   __shared__ float Bs[2][kPcBK][BN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int mh = wave & 1, nh = wave >> 1;
+  const int tid = threadIdx.x;
+  PLANAR_LANE(tid);
   const float* __restrict__ in = g.in;
   const float* __restrict__ w = g.w;
   // global -> register staging: weights 4 floats per thread (one float4 of row tid / 16), input NX floats of row tid / 16
@@ -88,7 +103,6 @@ __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f3
   load(0);
   store(0);
   __syncthreads();
-  const int kl = lane >> 5, cl = lane & 31;
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < nk) load((kt + 1) * kPcBK);
@@ -97,12 +111,33 @@ __device__ __forceinline__ void planar_conv_mainloop(const PlanarConvTile& g, f3
       const float fa = As[cur][2 * s + kl][mh * 32 + cl];
 #pragma unroll
       for (int n = 0; n < NSUB; ++n) {
-        const float fb = Bs[cur][2 * s + kl][(nh * NSUB + n) * 32 + cl];
+        const float fb = Bs[cur][2 * s + kl][PLANAR_COL(NSUB, n)];
         acc[n][s % NCHAIN] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[n][s % NCHAIN], 0, 0, 0);
       }
     }
     if (kt + 1 < nk) store(cur ^ 1);
     __syncthreads();
+  }
+}
+
+// The fold in front of a convolution whose input is a strided view of a waveform (mel.hip, resample.hip): rows wav[b][Tmax] of lens.n[b] valid
+// samples -> x[b][ci][q] = src(w, len, q, ci) for ci < C, q < Q, where w and len are item b's row and length and src gives 0.f where the
+// element is padding or (q, ci) lies outside the tensor.  One workgroup of 256 threads per 64 ci x 64 q of one item (blockIdx: q tile, ci tile,
+// item).  w is read along ci and x written along q: transposed through LDS so that both are coalesced.
+template <class Lens, class Src>
+__device__ __forceinline__ void planar_fold_tile(const float* __restrict__ wav, float* __restrict__ x, const Lens& lens, int Tmax, int C, int Q,
+                                                 Src&& src) {
+  __shared__ float tile[64][65];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
+  const long long len = lens.n[b];
+  const float* __restrict__ w = wav + (size_t)b * Tmax;
+  for (int r = wave; r < 64; r += 4) tile[r][lane] = src(w, len, q0 + r, c0 + lane);
+  __syncthreads();
+  float* __restrict__ xb = x + (size_t)b * C * Q;
+  for (int r = wave; r < 64; r += 4) {
+    const int ci = c0 + r, q = q0 + lane;
+    if (ci < C && q < Q) xb[(size_t)ci * Q + q] = tile[lane][r];
   }
 }
 

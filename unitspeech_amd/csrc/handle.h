@@ -1,5 +1,5 @@
 // The host plumbing every handle that takes its weights by state_dict key shares (us_frontend, us_vocoder, us_speaker, us_mel, us_resample, us_hubert, us_wavlm): the weight
-// table with its error reporting, device binding and load_weight prefix, and the two small helpers that came with each copy.  The
+// table with its error reporting, device binding and load_weight prefix, and the small workspace helpers that came with each copy.  The
 // decoder's handle (deferred raw copies and a flush) is a different design and does not use this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -100,5 +100,14 @@ struct WeightTable {
 inline float* ws_align(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }
 
 constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// every buffer of a workspace takes a multiple of 64 floats, so each starts on a 256-byte boundary
+constexpr size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
+
+// float offsets into the aligned workspace, handed out in order: take(n) is where a buffer of n floats starts, `total` what all of them need
+struct WsTake {
+  size_t total = 0;
+  size_t operator()(size_t n) { const size_t at = total; total += pad64(n); return at; }
+};
 
 }  // namespace us

@@ -35,19 +35,20 @@
 #include "../../include/unitspeech_hip.h"
 #include "conv1d_planar.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
-constexpr int kHbItems = 32;        // batch items per launch: their lengths travel as kernel arguments (the caller's are on the host)
+constexpr int kHbItems = 32;        // batch items per launch (item_lens.h)
 constexpr int kHbMaxConv = US_HUBERT_MAX_CONV;
 constexpr int kHbMaxK0 = 16;        // taps of layer 0 held in registers
 
-struct HbLens {
-  int n[kHbItems];                  // samples per item
+struct HbLens : ItemLens<kHbItems> {                // n[]: samples per item
   int k[kHbMaxConv], s[kHbMaxConv];
 };
+static_assert(sizeof(HbLens) == (kHbItems + 2 * kHbMaxConv) * sizeof(int), "n[], k[], s[] in this order: a kernel's argument segment");
 
 // item b's valid length after `level` extractor layers (0: samples)
 __device__ __forceinline__ int hb_len(const HbLens& L, int b, int level) {
@@ -148,21 +149,20 @@ struct HbGemmArgs {
 
 template <int STRIDE>
 __global__ __launch_bounds__(256) void hb_gemm_kernel(HbGemmArgs a, HbLens lens) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
+  PLANAR_LANE(threadIdx.x);
   const int b = blockIdx.z, grp = blockIdx.y / a.mtiles, mt = blockIdx.y - grp * a.mtiles;
   const int m0 = mt * kPcBM, n0 = blockIdx.x * 64;
   f32x16 acc[1][2];
   planar_conv_mainloop<1, 2, STRIDE>({a.in + (size_t)b * a.in_bs + (size_t)grp * a.Cin * a.Tin, a.w + (size_t)grp * a.Kpad * a.ldw, a.Cin, a.Tin, 1,
                                       a.off, a.Kdim, a.Kpad, a.ldw, m0, n0},
                                      acc);
-  const int t = n0 + nh * 32 + cl;
+  const int t = PLANAR_STEP(1, n0, 0);
   if (t >= a.Tout) return;
   const bool live = t < hb_len(lens, b, a.level);
   float* __restrict__ out = a.out + (size_t)b * a.out_bs;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int cg = m0 + mh * 32 + mfma32_row(r, kl);
+    const int cg = PLANAR_CHANNEL(m0, r);
     if (cg >= a.Cout) continue;
     const int co = grp * a.Cout + cg;
     float v = acc[0][0][r] + acc[0][1][r];
@@ -614,8 +614,6 @@ long long hb_receptive_field(const us_hubert_config& c) {
   return n;
 }
 
-size_t hb_pad(size_t n) { return (n + 63) / 64 * 64; }
-
 struct HbPlan {                 // float offsets into the 256-byte aligned workspace
   size_t stats, a, b, x0, p, x, x1, y, qkv, att, ff, gate, total;
 };
@@ -623,8 +621,7 @@ struct HbPlan {                 // float offsets into the 256-byte aligned works
 HbPlan hb_plan(const HbModel* h, int B, int Tmax) {
   const us_hubert_config& c = h->cfg;
   HbPlan p{};
-  size_t o = 0;
-  auto take = [&](size_t n) { const size_t at = o; o += hb_pad(n); return at; };
+  WsTake take;
   size_t ea = 0, eb = 0;        // the extractor's two buffers: layer i writes a (i even) or b (i odd); the projection's LayerNorm takes the other
   for (int i = 0; i <= c.n_conv; ++i) {
     const int ch = c.conv_dim[std::min(i, c.n_conv - 1)];
@@ -645,7 +642,7 @@ HbPlan hb_plan(const HbModel* h, int B, int Tmax) {
   p.att = take(bf * H);
   p.ff = take(bf * (size_t)c.intermediate_size);
   p.gate = take(h->wavlm ? bf * (size_t)c.n_heads : 0);
-  p.total = o;
+  p.total = take.total;
   return p;
 }
 
@@ -780,10 +777,8 @@ int hb_forward(HbModel* h, const std::string& what, const float* wav, const int6
   if (Tmax < field)
     return h->fail(US_EINVAL, what + ": Tmax = " + std::to_string(Tmax) + " is shorter than the receptive field (" + std::to_string(field) +
                                   " samples)");
-  for (int b = 0; lengths && b < B; ++b)
-    if (lengths[b] < field || lengths[b] > Tmax)
-      return h->fail(US_EINVAL, what + ": lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
-                                    " must be at least the receptive field (" + std::to_string(field) + " samples) and at most Tmax");
+  const std::string bad = bad_length(what.c_str(), lengths, B, field, Tmax);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad + " must be at least the receptive field (" + std::to_string(field) + " samples) and at most Tmax");
   const int H = c.hidden_size, I = c.intermediate_size, nl = c.n_conv;
   int Tl[kHbMaxConv + 1];                 // buffer widths: the steps of a Tmax-sample item after each layer
   Tl[0] = Tmax;
@@ -816,10 +811,8 @@ int hb_forward(HbModel* h, const std::string& what, const float* wav, const int6
   auto W = [&](const std::string& k) { return h->w.at(k).dev; };
   auto Wopt = [&](const std::string& k) { return h->conv_bias ? h->w.at(k).dev : nullptr; };
   const bool pre_ln = h->pre_ln();
-  for (int b0 = 0; b0 < B; b0 += kHbItems) {
-    const int nb = std::min(kHbItems, B - b0);
-    HbLens lens{};
-    for (int i = 0; i < kHbItems; ++i) lens.n[i] = i < nb ? (lengths ? (int)lengths[b0 + i] : Tmax) : (int)field;
+  for_item_groups<kHbItems>(B, [&](int b) { return lengths ? lengths[b] : Tmax; }, [&](int b0, int nb, const ItemLens<kHbItems>& items, int) {
+    HbLens lens{items, {}, {}};
     for (int i = 0; i < kHbMaxConv; ++i) {
       lens.k[i] = i < nl ? c.conv_kernel[i] : 1;
       lens.s[i] = i < nl ? c.conv_stride[i] : 1;
@@ -953,7 +946,7 @@ int hb_forward(HbModel* h, const std::string& what, const float* wav, const int6
         ln(S, nullptr, "encoder.layer_norm", nullptr, n_layers_out);
       else
         export_stream(n_layers_out);
-      continue;
+      return;
     }
     ln(P, nullptr, "encoder.layer_norm", X, 0);
     for (int i = 0; i < n_layers_out; ++i) {
@@ -978,7 +971,7 @@ int hb_forward(HbModel* h, const std::string& what, const float* wav, const int6
       }
       ln(Y, X1, q + "final_layer_norm", X, i + 1);
     }
-  }
+  });
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
 }

@@ -28,6 +28,7 @@
 #include "../../include/unitspeech_hip.h"
 #include "conv1d_planar.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
@@ -39,25 +40,15 @@ namespace {
 // the partial sums of window x twiddle x signal stay small (emulated on the CPU in fp32: 0.4 of the reference's own fp32 error on
 // integrated noise with one chain, 9 times it with two interleaved ones).
 constexpr int kMelBN = 128;
-constexpr int kMelItems = 64;       // batch items per launch: their lengths travel as kernel arguments (the caller's are on the host)
+constexpr int kMelItems = 64;       // batch items per launch (item_lens.h): samples (mel_frame_kernel) or frames (mel_proj_kernel, mel_minmax_kernel)
 constexpr int kMelMaxFft = 4096;
 constexpr int kMelMaxMels = 1024;
 
-struct MelLens {
-  int n[kMelItems];                 // samples (mel_frame_kernel) or frames (mel_proj_kernel, mel_minmax_kernel) of each item
-};
-
 // X[b][ci][q] = y_pad[q * hop + ci]; y_pad[i] = wav[reflect(i - p)] for i < len + 2 p, 0 beyond.  len > p, so a reflected index
 // stays inside [0, len): nothing at or past wav[b][len] is read.  One workgroup: 64 ci x 64 q.
-__global__ __launch_bounds__(256) void mel_frame_kernel(const float* __restrict__ wav, float* __restrict__ x, MelLens lens, int Tmax, int hop, int p,
-                                                        int Q) {
-  __shared__ float tile[64][65];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
-  const long long len = lens.n[b];
-  const float* __restrict__ w = wav + (size_t)b * Tmax;
-  for (int r = wave; r < 64; r += 4) {
-    const int q = q0 + r, ci = c0 + lane;
+__global__ __launch_bounds__(256) void mel_frame_kernel(const float* __restrict__ wav, float* __restrict__ x, ItemLens<kMelItems> lens, int Tmax,
+                                                        int hop, int p, int Q) {
+  planar_fold_tile(wav, x, lens, Tmax, hop, Q, [=](const float* __restrict__ w, long long len, int q, int ci) {
     float v = 0.f;
     const long long i = (long long)q * hop + ci;
     if (q < Q && ci < hop && i < len + 2 * p) {
@@ -65,14 +56,8 @@ __global__ __launch_bounds__(256) void mel_frame_kernel(const float* __restrict_
       s = s < 0 ? -s : (s >= len ? 2 * (len - 1) - s : s);
       v = w[s];
     }
-    tile[r][lane] = v;
-  }
-  __syncthreads();
-  float* __restrict__ xb = x + (size_t)b * hop * Q;
-  for (int r = wave; r < 64; r += 4) {
-    const int ci = c0 + r, q = q0 + lane;
-    if (ci < hop && q < Q) xb[(size_t)ci * Q + q] = tile[lane][r];
-  }
+    return v;
+  });
 }
 
 // P[n][2 f + part] = round_fp32(w[n] * (cos, -sin)(2 pi (f n mod n_fft) / n_fft)) for n < n_fft, f < live, zero in the padding; w is the
@@ -124,8 +109,7 @@ struct MelDftArgs {
 };
 
 __global__ __launch_bounds__(256) void mel_dft_kernel(MelDftArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
+  PLANAR_LANE(threadIdx.x);
   const int b = blockIdx.z;
   const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kMelBN;
   f32x16 acc[2][1];
@@ -133,11 +117,11 @@ __global__ __launch_bounds__(256) void mel_dft_kernel(MelDftArgs a) {
   float* __restrict__ mag = a.mag + (size_t)b * a.live * a.F;
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
-    const int t = n0 + (nh * 2 + n) * 32 + cl;
+    const int t = n0 + PLANAR_COL(2, n);
     if (t >= a.F) continue;
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
-      const int f = (m0 + mh * 32 + mfma32_row(r, kl)) >> 1;      // rows (r, r + 1) are (2 f, 2 f + 1)
+      const int f = PLANAR_CHANNEL(m0, r) >> 1;                            // rows (r, r + 1) are (2 f, 2 f + 1)
       if (f >= a.live) continue;
       const float re = acc[n][0][r], im = acc[n][0][r + 1];
       mag[(size_t)f * a.F + t] = sqrtf(re * re + im * im + 1e-9f);    // meldataset.py:69
@@ -151,14 +135,13 @@ struct MelProjArgs {
   const float* mel_min;       // n_norm values (1: one for all bands), or null
   const float* mel_max;
   float* out;                 // [B][num_mels][F]
-  MelLens frames;
+  ItemLens<kMelItems> frames;
   float pad_value;
   int n_norm, num_mels, F, live, Kpad, ldw;
 };
 
 __global__ __launch_bounds__(256) void mel_proj_kernel(MelProjArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
+  PLANAR_LANE(threadIdx.x);
   const int b = blockIdx.z;
   const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kMelBN;
   f32x16 acc[2][1];
@@ -166,12 +149,12 @@ __global__ __launch_bounds__(256) void mel_proj_kernel(MelProjArgs a) {
   float* __restrict__ out = a.out + (size_t)b * a.num_mels * a.F;
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
-    const int t = n0 + (nh * 2 + n) * 32 + cl;
+    const int t = n0 + PLANAR_COL(2, n);
     if (t >= a.F) continue;
     const bool valid = t < a.frames.n[b];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = m0 + mh * 32 + mfma32_row(r, kl);
+      const int co = PLANAR_CHANNEL(m0, r);
       if (co >= a.num_mels) continue;
       float v = a.pad_value;
       if (valid) {
@@ -190,8 +173,8 @@ __global__ __launch_bounds__(256) void mel_proj_kernel(MelProjArgs a) {
 
 // out[0][m] = min, out[1][m] = max of mel[b][m][t] over t < frames[b] of the launch's items; `merge` folds in what out already holds
 // (the next kMelItems items of a larger batch).  One workgroup per band.  +inf / -inf when no item has a frame.
-__global__ __launch_bounds__(256) void mel_minmax_kernel(const float* __restrict__ mel, MelLens frames, int B, int num_mels, int F,
-                                                         float* __restrict__ out, int merge) {
+__global__ __launch_bounds__(256) void mel_minmax_kernel(const float* __restrict__ mel, ItemLens<kMelItems> frames, int B, int num_mels,
+                                                         int F, float* __restrict__ out, int merge) {
   __shared__ float smin[4], smax[4];
   const int m = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float lo = INFINITY, hi = -INFINITY;
@@ -261,15 +244,10 @@ void mel_pack(us_mel* h, hipStream_t s) {
                      h->bins, h->live, h->proj_Kpad, h->proj_ldw);
 }
 
-size_t mel_pad64(size_t n) { return (n + 63) / 64 * 64; }
-
-// item lengths of a call: every one in (pad, Tmax]; NULL = all Tmax
+// item lengths of a call: every one in (lo, hi]; NULL = all hi
 int mel_check_lengths(us_mel* h, const char* what, const int64_t* lengths, int B, long long lo, long long hi) {
-  for (int b = 0; lengths && b < B; ++b)
-    if (lengths[b] <= lo || lengths[b] > hi)
-      return h->fail(US_EINVAL, std::string(what) + ": lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
-                                    " is outside (" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
-  return US_OK;
+  const std::string bad = bad_length(what, lengths, B, lo + 1, hi);
+  return bad.empty() ? US_OK : h->fail(US_EINVAL, bad + " is outside (" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
 }
 
 }  // namespace
@@ -344,7 +322,7 @@ int us_mel_frames(us_mel_handle h, int T) { return (h && T > 0) ? T / h->cfg.hop
 size_t us_mel_workspace_bytes(us_mel_handle h, int B, int Tmax) {
   if (!h || B <= 0 || Tmax <= 0) return 0;
   const size_t F = (size_t)(Tmax / h->cfg.hop), Q = F + h->taps - 1;
-  return (mel_pad64((size_t)B * h->cfg.hop * Q) + mel_pad64((size_t)B * h->bins * F)) * sizeof(float) + 256;
+  return (pad64((size_t)B * h->cfg.hop * Q) + pad64((size_t)B * h->bins * F)) * sizeof(float) + 256;
 }
 
 int us_mel_forward(us_mel_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, const float* mel_min, const float* mel_max,
@@ -365,15 +343,9 @@ int us_mel_forward(us_mel_handle h, const float* wav, const int64_t* lengths, in
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int F = Tmax / c.hop, Q = F + h->taps - 1, live = h->live;
   float* X = ws_align(workspace);
-  float* MAG = X + mel_pad64((size_t)B * c.hop * Q);
+  float* MAG = X + pad64((size_t)B * c.hop * Q);
   const unsigned tiles = (unsigned)((F + kMelBN - 1) / kMelBN);
-  for (int b0 = 0; b0 < B; b0 += kMelItems) {
-    const int nb = std::min(kMelItems, B - b0);
-    MelLens samples{}, frames{};
-    for (int i = 0; i < nb; ++i) {
-      samples.n[i] = lengths ? (int)lengths[b0 + i] : Tmax;
-      frames.n[i] = samples.n[i] / c.hop;
-    }
+  for_item_groups<kMelItems>(B, [&](int b) { return lengths ? lengths[b] : Tmax; }, [&](int b0, int nb, const ItemLens<kMelItems>& samples, int) {
     float* Xb = X + (size_t)b0 * c.hop * Q;
     float* Mb = MAG + (size_t)b0 * live * F;
     hipLaunchKernelGGL(mel_frame_kernel, dim3((unsigned)((Q + 63) / 64), (unsigned)((c.hop + 63) / 64), (unsigned)nb), dim3(256), 0, s,
@@ -382,10 +354,11 @@ int us_mel_forward(us_mel_handle h, const float* wav, const int64_t* lengths, in
     hipLaunchKernelGGL(mel_dft_kernel, dim3(tiles, (unsigned)(h->dft_ldw / kPcBM), (unsigned)nb), dim3(256), 0, s, d);
     MelProjArgs p{};
     p.mag = Mb; p.w = h->proj; p.mel_min = mel_min; p.mel_max = mel_max; p.out = out + (size_t)b0 * c.num_mels * F;
-    p.frames = frames; p.pad_value = pad_value; p.n_norm = n_norm; p.num_mels = c.num_mels; p.F = F; p.live = live;
+    for (int i = 0; i < kMelItems; ++i) p.frames.n[i] = samples.n[i] / c.hop;
+    p.pad_value = pad_value; p.n_norm = n_norm; p.num_mels = c.num_mels; p.F = F; p.live = live;
     p.Kpad = h->proj_Kpad; p.ldw = h->proj_ldw;
     hipLaunchKernelGGL(mel_proj_kernel, dim3(tiles, (unsigned)(h->proj_ldw / kPcBM), (unsigned)nb), dim3(256), 0, s, p);
-  }
+  });
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_mel_forward", e);
 }
@@ -397,12 +370,9 @@ int us_mel_minmax(us_mel_handle h, const float* mel, const int64_t* lengths_fram
   if ((rc = h->on_device("us_mel_minmax")) != US_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int M = h->cfg.num_mels;
-  for (int b0 = 0; b0 < B; b0 += kMelItems) {
-    const int nb = std::min(kMelItems, B - b0);
-    MelLens frames{};
-    for (int i = 0; i < nb; ++i) frames.n[i] = lengths_frames ? (int)lengths_frames[b0 + i] : F;
+  for_item_groups<kMelItems>(B, [&](int b) { return lengths_frames ? lengths_frames[b] : F; }, [&](int b0, int nb, const ItemLens<kMelItems>& frames, int) {
     hipLaunchKernelGGL(mel_minmax_kernel, dim3((unsigned)M), dim3(256), 0, s, mel + (size_t)b0 * M * F, frames, nb, M, F, out, b0 > 0 ? 1 : 0);
-  }
+  });
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_mel_minmax", e);
 }

@@ -36,38 +36,23 @@
 #include "../../include/unitspeech_hip.h"
 #include "conv1d_planar.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
 constexpr int kRsBN = 128;          // frames per workgroup (planar_conv_mainloop<2, 1>)
-constexpr int kRsItems = 64;        // batch items per launch: their lengths travel as kernel arguments (the caller's are on the host)
+constexpr int kRsItems = 64;        // batch items per launch (item_lens.h): the samples of each
 constexpr int kRsMaxRate = 4096;
 
-struct RsLens {
-  int n[kRsItems];                  // samples of each item
-};
-
 // X[b][ci][q] = y_b[q * orig + ci - width], 0 outside [0, len_b).  One workgroup: 64 ci x 64 q.
-__global__ __launch_bounds__(256) void rs_fold_kernel(const float* __restrict__ wav, float* __restrict__ x, RsLens lens, int Tmax, int orig, int width,
-                                                      int Q) {
-  __shared__ float tile[64][65];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
-  const long long len = lens.n[b];
-  const float* __restrict__ w = wav + (size_t)b * Tmax;
-  for (int r = wave; r < 64; r += 4) {
-    const int q = q0 + r, ci = c0 + lane;
+__global__ __launch_bounds__(256) void rs_fold_kernel(const float* __restrict__ wav, float* __restrict__ x, ItemLens<kRsItems> lens, int Tmax,
+                                                      int orig, int width, int Q) {
+  planar_fold_tile(wav, x, lens, Tmax, orig, Q, [=](const float* __restrict__ w, long long len, int q, int ci) {
     const long long s = (long long)q * orig + ci - width;
-    tile[r][lane] = (q < Q && ci < orig && s >= 0 && s < len) ? w[s] : 0.f;
-  }
-  __syncthreads();
-  float* __restrict__ xb = x + (size_t)b * orig * Q;
-  for (int r = wave; r < 64; r += 4) {
-    const int ci = c0 + r, q = q0 + lane;
-    if (ci < orig && q < Q) xb[(size_t)ci * Q + q] = tile[lane][r];
-  }
+    return (q < Q && ci < orig && s >= 0 && s < len) ? w[s] : 0.f;
+  });
 }
 
 // P[k][c] = kernel[c][0][k] for k < K, c < nw, zero in the padding
@@ -83,15 +68,14 @@ struct RsGemmArgs {
   const float* x;             // [B][orig][Q]
   const float* w;             // [Kpad][ldw]
   float* out;                 // [B][out_ld]
-  RsLens samples;
+  ItemLens<kRsItems> samples;
   long long out_ld;           // ceil(nw * Tmax / orig)
   int orig, nw, Q, Kdim, Kpad, ldw;
 };
 
 __global__ __launch_bounds__(256) void rs_gemm_kernel(RsGemmArgs a) {
   __shared__ float stage[64][65];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
+  PLANAR_LANE(threadIdx.x);
   const int b = blockIdx.z;
   const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kRsBN;
   f32x16 acc[2][1];
@@ -102,9 +86,9 @@ __global__ __launch_bounds__(256) void rs_gemm_kernel(RsGemmArgs a) {
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     if (n) __syncthreads();                        // pass 0's reads are done
-    // pass n: sub-tile n of every wave.  Staging row 32 nh + cl is frame n0 + (2 nh + n) * 32 + cl.
+    // pass n: sub-tile n of every wave.  Staging row PLANAR_COL(1, 0) = 32 nh + cl is frame n0 + PLANAR_COL(2, n) = n0 + (2 nh + n) * 32 + cl.
 #pragma unroll
-    for (int r = 0; r < 16; ++r) stage[nh * 32 + cl][mh * 32 + mfma32_row(r, kl)] = acc[n][0][r];
+    for (int r = 0; r < 16; ++r) stage[PLANAR_COL(1, 0)][PLANAR_ROW(r)] = acc[n][0][r];
     __syncthreads();
     for (int e = threadIdx.x; e < 64 * live; e += 256) {
       const int j = e / live, c = e - j * live;
@@ -127,7 +111,6 @@ struct us_resample : us::WeightTable {
 namespace us {
 namespace {
 
-size_t rs_pad64(size_t n) { return (n + 63) / 64 * 64; }
 long long rs_out_length(const us_resample* h, long long T) { return ((long long)h->cfg.new_freq * T + h->cfg.orig_freq - 1) / h->cfg.orig_freq; }
 // frames the GEMM computes for rows of Tmax samples, and the columns of X they read
 long long rs_frames(const us_resample* h, long long Tmax) { return (rs_out_length(h, Tmax) + h->cfg.new_freq - 1) / h->cfg.new_freq; }
@@ -197,7 +180,7 @@ int64_t us_resample_out_length(us_resample_handle h, int64_t T) { return (h && T
 size_t us_resample_workspace_bytes(us_resample_handle h, int B, int Tmax) {
   if (!h || B <= 0 || Tmax <= 0) return 0;
   const size_t Q = (size_t)rs_frames(h, Tmax) + h->taps - 1;
-  return rs_pad64((size_t)B * h->cfg.orig_freq * Q) * sizeof(float) + 256;
+  return pad64((size_t)B * h->cfg.orig_freq * Q) * sizeof(float) + 256;
 }
 
 int us_resample_forward(us_resample_handle h, const float* wav, const int64_t* lengths, int B, int Tmax, float* out, void* workspace,
@@ -206,10 +189,8 @@ int us_resample_forward(us_resample_handle h, const float* wav, const int64_t* l
   const auto& c = h->cfg;
   // q * orig + ci, q * new + c and new * len stay far inside 64 bits, the frame count inside 32
   if (Tmax < 1 || Tmax > (1 << 30)) return h->fail(US_EINVAL, "us_resample_forward: Tmax must be in [1, 2^30]");
-  for (int b = 0; lengths && b < B; ++b)
-    if (lengths[b] < 1 || lengths[b] > Tmax)
-      return h->fail(US_EINVAL, "us_resample_forward: lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
-                                    " is outside [1, " + std::to_string(Tmax) + "]");
+  const std::string bad = bad_length("us_resample_forward", lengths, B, 1, Tmax);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad + " is outside [1, " + std::to_string(Tmax) + "]");
   int rc = h->all_loaded("us_resample_forward");
   if (rc != US_OK) return rc;
   if (!workspace || workspace_bytes < us_resample_workspace_bytes(h, B, Tmax))
@@ -219,17 +200,16 @@ int us_resample_forward(us_resample_handle h, const float* wav, const int64_t* l
   const int F = (int)rs_frames(h, Tmax), Q = F + h->taps - 1;
   float* X = ws_align(workspace);
   const unsigned tiles = (unsigned)((F + kRsBN - 1) / kRsBN);
-  for (int b0 = 0; b0 < B; b0 += kRsItems) {
-    const int nb = std::min(kRsItems, B - b0);
+  for_item_groups<kRsItems>(B, [&](int b) { return lengths ? lengths[b] : Tmax; }, [&](int b0, int nb, const ItemLens<kRsItems>& samples, int) {
     RsGemmArgs g{};
-    for (int i = 0; i < nb; ++i) g.samples.n[i] = lengths ? (int)lengths[b0 + i] : Tmax;
+    g.samples = samples;
     float* Xb = X + (size_t)b0 * c.orig_freq * Q;
     hipLaunchKernelGGL(rs_fold_kernel, dim3((unsigned)((Q + 63) / 64), (unsigned)((c.orig_freq + 63) / 64), (unsigned)nb), dim3(256), 0, s,
-                       wav + (size_t)b0 * Tmax, Xb, g.samples, Tmax, c.orig_freq, c.width, Q);
+                       wav + (size_t)b0 * Tmax, Xb, samples, Tmax, c.orig_freq, c.width, Q);
     g.x = Xb; g.w = h->packed; g.out = out + (size_t)b0 * out_ld; g.out_ld = out_ld;
     g.orig = c.orig_freq; g.nw = c.new_freq; g.Q = Q; g.Kdim = h->K; g.Kpad = h->Kpad; g.ldw = h->ldw;
     hipLaunchKernelGGL(rs_gemm_kernel, dim3(tiles, (unsigned)(h->ldw / kPcBM), (unsigned)nb), dim3(256), 0, s, g);
-  }
+  });
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_resample_forward", e);
 }

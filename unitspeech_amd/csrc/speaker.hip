@@ -18,11 +18,10 @@
 // Every reduction is a fixed-order tree inside one wave (or a fixed-order loop over waves): no atomics, so a batch item's result
 // does not depend on its neighbours or on the run.
 //
-// Ragged batches (us_speaker_forward_lengths): every kernel that looks along time is a template over how it learns an item's length.
-// SpSameT is the uniform call: the length is the row stride T, and the instantiation is the kernel as it was.  SpLens carries the
-// lengths of up to kSpItems items as a kernel argument (one scalar load per workgroup, indexed by the block's item): item b is then a
-// tensor of lens.n[b] steps stored with row stride T, the time tiles start where they start when the item runs alone, and every sum
-// runs over the same terms in the same order, so the item's result has the bits of the uniform call on the item alone.
+// Ragged batches (us_speaker_forward_lengths): every kernel that looks along time is a template over how it learns an item's length, SameT
+// or ItemLens<kSpItems> (item_lens.h; an item's length is at least 1 and at most T).  The time tiles start where they start when the item
+// runs alone, and every sum runs over the same terms in the same order, so the item's result has the bits of the uniform call on the item
+// alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +34,7 @@
 #include "../../include/unitspeech_hip.h"
 #include "conv1d_planar.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
@@ -46,19 +46,7 @@ constexpr int kSpScale = 8;        // Res2 scale
 constexpr int kSpStages = kSpScale - 1;
 constexpr float kBnEps = 1e-5f;
 
-// ---- how a kernel learns the valid steps of batch item b (rows are T apart either way) -------------------------------------------
-constexpr int kSpItems = 32;       // batch items per launch of the ragged form: their lengths travel as kernel arguments
-
-struct SpSameT {                   // us_speaker_forward: every item has T steps
-  static constexpr bool ragged = false;
-  __device__ __forceinline__ int operator()(int, int T) const { return T; }
-};
-
-struct SpLens {                    // us_speaker_forward_lengths: item b of the launch has n[b] steps, 1 <= n[b] <= T
-  static constexpr bool ragged = true;
-  int n[kSpItems];
-  __device__ __forceinline__ int operator()(int b, int) const { return n[b]; }
-};
+constexpr int kSpItems = 32;       // batch items per launch of the ragged form (item_lens.h)
 
 // The (b, c) row of a one-wave-per-row kernel and its valid steps; false: the wave has no row.  Uniform: rows are numbered through the
 // whole batch, four per workgroup.  Ragged: blockIdx.y is the item (its length a scalar load), blockIdx.x * 4 + wave the channel.
@@ -171,20 +159,19 @@ struct SpConvArgs {
 // lies past the end stays in columns that are never stored, and layer1's k = 5 reads the zeros sp_instnorm_kernel wrote there.
 template <class LN>
 __global__ __launch_bounds__(256) void sp_conv_kernel(SpConvArgs a, LN lens) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
+  PLANAR_LANE(threadIdx.x);
   const int b = blockIdx.z;
   const int m0 = blockIdx.y * kPcBM, n0 = blockIdx.x * kSpBN;
   const int n = lens(b, a.T);
   if (LN::ragged && n0 >= n) return;
   f32x16 acc[1][2];
   planar_conv_mainloop<1, 2>({a.in + (size_t)b * a.in_bs, a.w, a.Cin, a.T, 1, a.off, a.Kdim, a.Kpad, a.ldw, m0, n0}, acc);
-  const int t = n0 + nh * 32 + cl;
+  const int t = PLANAR_STEP(1, n0, 0);
   if (t >= n) return;
   float* __restrict__ out = a.out + (size_t)b * a.out_bs;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int co = m0 + mh * 32 + mfma32_row(r, kl);
+    const int co = PLANAR_CHANNEL(m0, r);
     if (co >= a.Cout) continue;
     float v = (acc[0][0][r] + acc[0][1][r]) + a.bias[co];
     if (a.bias2) v += a.bias2[(size_t)b * a.Cout + co];
@@ -569,16 +556,13 @@ void sp_prepare(us_speaker* h, hipStream_t s) {
   h->dirty = false;
 }
 
-size_t sp_pad(size_t n) { return (n + 63) / 64 * 64; }
-
 struct SpPlan {                 // float offsets into the 256-byte aligned workspace
   size_t x0, o1, cat, a, r, y, big, att, e, mean, s, ctx, b2, praw, pbn, total;
 };
 
 SpPlan sp_plan(const us_speaker_config& c, int B, int T) {
   SpPlan p{};
-  size_t o = 0;
-  auto take = [&](size_t n) { const size_t at = o; o += sp_pad(n); return at; };
+  WsTake take;
   const size_t bt = (size_t)B * T, ch = (size_t)c.channels;
   p.x0 = take(bt * c.feat_dim);
   p.o1 = take(bt * ch);
@@ -595,7 +579,7 @@ SpPlan sp_plan(const us_speaker_config& c, int B, int T) {
   p.b2 = take((size_t)B * kSpAtt);
   p.praw = take((size_t)B * 2 * kSpOut);
   p.pbn = take((size_t)B * 2 * kSpOut);
-  p.total = o;
+  p.total = take.total;
   return p;
 }
 
@@ -778,7 +762,7 @@ int us_speaker_forward(us_speaker_handle h, const float* hidden_states, int L, i
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rc = sp_forward_checks(h, "us_speaker_forward", L, B, T, workspace, workspace_bytes, s);
   if (rc != US_OK) return rc;
-  sp_run(h, s, hidden_states, L, B, T, 0, B, SpSameT{}, ws_align(workspace), sp_plan(h->cfg, B, T), emb_out);
+  sp_run(h, s, hidden_states, L, B, T, 0, B, SameT{}, ws_align(workspace), sp_plan(h->cfg, B, T), emb_out);
   if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(1), dim3(256), 0, s, emb_out, B * h->cfg.emb_dim);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_speaker_forward", e);
@@ -789,21 +773,16 @@ int us_speaker_forward_lengths(us_speaker_handle h, const float* hidden_states, 
   if (!h || !hidden_states || !emb_out || B <= 0 || Tmax <= 0 || L < 0)
     return WeightTable::fail(h, US_EINVAL, "us_speaker_forward_lengths: bad argument");
   if (!lengths) return h->fail(US_EINVAL, "us_speaker_forward_lengths: lengths is null (B host values in [1, Tmax]; us_speaker_forward is the uniform call)");
-  for (int b = 0; b < B; ++b)
-    if (lengths[b] < 1 || lengths[b] > Tmax)
-      return h->fail(US_EINVAL, "us_speaker_forward_lengths: lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
-                                    " must be at least 1 and at most Tmax = " + std::to_string(Tmax));
+  const std::string bad = bad_length("us_speaker_forward_lengths", lengths, B, 1, Tmax);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad + " must be at least 1 and at most Tmax = " + std::to_string(Tmax));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rc = sp_forward_checks(h, "us_speaker_forward_lengths", L, B, Tmax, workspace, workspace_bytes, s);
   if (rc != US_OK) return rc;
   const SpPlan p = sp_plan(h->cfg, B, Tmax);
   float* base = ws_align(workspace);
-  for (int b0 = 0; b0 < B; b0 += kSpItems) {
-    const int nb = std::min(kSpItems, B - b0);
-    SpLens lens{};
-    for (int i = 0; i < kSpItems; ++i) lens.n[i] = i < nb ? (int)lengths[b0 + i] : 1;
+  for_item_groups<kSpItems>(B, [&](int b) { return lengths[b]; }, [&](int b0, int nb, const ItemLens<kSpItems>& lens, int) {
     sp_run(h, s, hidden_states, L, B, Tmax, b0, nb, lens, base, p, emb_out);
-  }
+  });
   if (normalize) hipLaunchKernelGGL(sp_normalize_kernel, dim3(B), dim3(256), 0, s, emb_out, h->cfg.emb_dim);      // each row by its own norm
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_speaker_forward_lengths", e);
@@ -830,7 +809,7 @@ int us_speaker_debug_conv(us_speaker_handle h, const char* prefix, const char* b
   if (rc != US_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->dirty) sp_prepare(h, s);
-  sp_conv(h, s, p, bn, act, in, in_bs, out, out_bs, bias2, B, T, SpSameT{});
+  sp_conv(h, s, p, bn, act, in, in_bs, out, out_bs, bias2, B, T, SameT{});
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip("us_speaker_debug_conv", e);
 }

@@ -13,13 +13,11 @@
 //    writing [C][T] once.
 //  - vc_post_kernel: conv_post (C -> 1, k = 7) as a per-sample fp32 reduction with the tanh in its epilogue.
 //
-// Ragged batches (us_vocoder_forward_lengths): each of the three kernels is a template over how it learns an item's length.  VcSameT is
-// the uniform call: the length is the row stride, and the instantiation is the kernel as it was.  VcLens carries the lengths of up to
-// kVcItems items as a kernel argument (one scalar load per workgroup, indexed by the block's item): item b is then a tensor of lens.n[b]
-// steps stored with the padded row stride.  Every read along time is bounded or clamped by the item's own length, so nothing at or past
-// an item's end is read and nothing there is written (conv_post alone writes zeros over the padded tail of the waveform); the time
-// tiles start where they start when the item runs alone and BigVGAN has no reduction along time, so the item's samples have the bits of
-// the uniform call on the item alone.
+// Ragged batches (us_vocoder_forward_lengths): each of the three kernels is a template over how it learns an item's length, SameT or
+// ItemLens<kVcItems> (item_lens.h; an item's length is at least 1 and at most the padded row stride).  Every read along time is bounded or
+// clamped by the item's own length, so nothing at or past an item's end is read and nothing there is written (conv_post alone writes zeros
+// over the padded tail of the waveform); the time tiles start where they start when the item runs alone and BigVGAN has no reduction along
+// time, so the item's samples have the bits of the uniform call on the item alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +30,7 @@
 #include "../../include/unitspeech_hip.h"
 #include "conv1d_planar.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
@@ -44,19 +43,7 @@ namespace {
 // (two 32-step sub-tiles, one accumulator chain each).
 constexpr int kVcBN = 128;    // output steps per workgroup
 
-// ---- how a kernel learns the valid steps of batch item b (rows are the padded length apart either way) ---------------------------
-constexpr int kVcItems = 32;  // batch items per launch of the ragged form: their lengths travel as kernel arguments
-
-struct VcSameT {              // us_vocoder_forward: every item has T steps
-  static constexpr bool ragged = false;
-  __device__ __forceinline__ int operator()(int, int T) const { return T; }
-};
-
-struct VcLens {               // us_vocoder_forward_lengths: item b of the launch has n[b] steps at this level, 1 <= n[b] <= T
-  static constexpr bool ragged = true;
-  int n[kVcItems];
-  __device__ __forceinline__ int operator()(int b, int) const { return n[b]; }
-};
+constexpr int kVcItems = 32;  // batch items per launch of the ragged form (item_lens.h)
 
 struct VcConvArgs {
   const float* in;            // [B][Cin][Tin]
@@ -78,8 +65,7 @@ struct VcConvArgs {
 // test is workgroup-uniform), and no step at or past n is stored.
 template <class LN>
 __global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a, LN lens) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int mh = wave & 1, nh = wave >> 1, kl = lane >> 5, cl = lane & 31;
+  PLANAR_LANE(threadIdx.x);
   const int b = LN::ragged ? blockIdx.z : blockIdx.z / a.nph;
   const int mt = LN::ragged ? blockIdx.y / a.nph : blockIdx.y;
   const int ph = LN::ragged ? blockIdx.y - mt * a.nph : blockIdx.z - b * a.nph;
@@ -94,12 +80,12 @@ __global__ __launch_bounds__(256) void vc_conv_kernel(VcConvArgs a, LN lens) {
   const size_t bo = (size_t)b * a.Cout * a.Tout;
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
-    const int q = n0 + nh * 64 + n * 32 + cl;
+    const int q = PLANAR_STEP(2, n0, n);
     if (q >= nv) continue;
     const int t = q * a.ostride + ph;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = m0 + mh * 32 + mfma32_row(r, kl);
+      const int co = PLANAR_CHANNEL(m0, r);
       if (co >= a.Cout) continue;
       const size_t idx = (size_t)co * a.Tout + t;
       float v = acc[n][0][r] + a.bias[co];
@@ -285,22 +271,7 @@ long long vc_max_ct(const us_vocoder_config& c, int T) {
 
 constexpr int kVcBuffers = 5;      // level input, AMP sum, residual stream, activation output, first-conv output
 
-// Ragged launches: `lengths` (host, or null for the uniform call) counts item b's steps in units of which this level has `rate` each; one
-// launch per kVcItems items, its time tiles covering the longest of them.
-template <class F>
-void vc_groups(int B, const int64_t* lengths, long long rate, F&& launch) {
-  for (int b0 = 0; b0 < B; b0 += kVcItems) {
-    const int nb = std::min(kVcItems, B - b0);
-    VcLens lens{};
-    int longest = 1;
-    for (int i = 0; i < kVcItems; ++i) {
-      lens.n[i] = i < nb ? (int)(lengths[b0 + i] * rate) : 1;
-      longest = std::max(longest, lens.n[i]);
-    }
-    launch(b0, nb, longest, lens);
-  }
-}
-
+// Ragged launches: `lengths` counts item b's steps in units of which this level has `rate` each; the time tiles cover the group's longest item
 void conv(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, float* out, const float* res, const float* sum, float div,
           int B, int Tin, const int64_t* lengths = nullptr, long long rate = 1) {
   const PlanarConv& c = h->conv.at(p);
@@ -312,16 +283,16 @@ void conv(us_vocoder* h, hipStream_t s, const std::string& p, const float* in, f
   for (int r = 0; r < c.nph; ++r) a.off[r] = c.off[r];
   const int mt = (c.cout + kPcBM - 1) / kPcBM;
   if (!lengths) {
-    hipLaunchKernelGGL(vc_conv_kernel<VcSameT>, dim3((Tin + kVcBN - 1) / kVcBN, mt, B * c.nph), dim3(256), 0, s, a, VcSameT{});
+    hipLaunchKernelGGL(vc_conv_kernel<SameT>, dim3((Tin + kVcBN - 1) / kVcBN, mt, B * c.nph), dim3(256), 0, s, a, SameT{});
     return;
   }
-  vc_groups(B, lengths, rate, [&](int b0, int nb, int longest, const VcLens& lens) {
+  for_item_groups<kVcItems>(B, [&](int b) { return lengths[b] * rate; }, [&](int b0, int nb, const ItemLens<kVcItems>& lens, int longest) {
     VcConvArgs g = a;
     const size_t io = (size_t)b0 * c.cin * Tin, oo = (size_t)b0 * c.cout * a.Tout;
     g.in = in + io; g.out = out + oo;
     if (res) g.res = res + oo;
     if (sum) g.sum = sum + oo;
-    hipLaunchKernelGGL(vc_conv_kernel<VcLens>, dim3((longest + kVcBN - 1) / kVcBN, mt * c.nph, nb), dim3(256), 0, s, g, lens);
+    hipLaunchKernelGGL(vc_conv_kernel<ItemLens<kVcItems>>, dim3((longest + kVcBN - 1) / kVcBN, mt * c.nph, nb), dim3(256), 0, s, g, lens);
   });
 }
 
@@ -331,13 +302,13 @@ void activation(us_vocoder* h, hipStream_t s, const std::string& p, const float*
   const float* fup = h->w.at(p + ".upsample.filter").dev;
   const float* fdown = h->w.at(p + ".downsample.lowpass.filter").dev;
   if (!lengths) {
-    hipLaunchKernelGGL(vc_act_kernel<VcSameT>, dim3((T + kActN - 1) / kActN, B * a.C), dim3(256), 0, s, in, out, a.ab, fup, fdown, a.C, T,
-                       VcSameT{});
+    hipLaunchKernelGGL(vc_act_kernel<SameT>, dim3((T + kActN - 1) / kActN, B * a.C), dim3(256), 0, s, in, out, a.ab, fup, fdown, a.C, T,
+                       SameT{});
     return;
   }
-  vc_groups(B, lengths, rate, [&](int b0, int nb, int longest, const VcLens& lens) {
+  for_item_groups<kVcItems>(B, [&](int b) { return lengths[b] * rate; }, [&](int b0, int nb, const ItemLens<kVcItems>& lens, int longest) {
     const size_t o = (size_t)b0 * a.C * T;
-    hipLaunchKernelGGL(vc_act_kernel<VcLens>, dim3((longest + kActN - 1) / kActN, a.C, nb), dim3(256), 0, s, in + o, out + o, a.ab, fup,
+    hipLaunchKernelGGL(vc_act_kernel<ItemLens<kVcItems>>, dim3((longest + kActN - 1) / kActN, a.C, nb), dim3(256), 0, s, in + o, out + o, a.ab, fup,
                        fdown, a.C, T, lens);
   });
 }
@@ -348,23 +319,20 @@ void post(us_vocoder* h, hipStream_t s, const float* in, float* out, int B, int 
   const float* w = h->w.at("conv_post.weight").dev;
   const float* bias = h->w.at("conv_post.bias").dev;
   if (!lengths) {
-    hipLaunchKernelGGL(vc_post_kernel<VcSameT>, dim3((T + 255) / 256, B), dim3(256), lds, s, in, w, bias, out, ch, T, VcSameT{});
+    hipLaunchKernelGGL(vc_post_kernel<SameT>, dim3((T + 255) / 256, B), dim3(256), lds, s, in, w, bias, out, ch, T, SameT{});
     return;
   }
   // every tile of the padded row is launched: the ones past an item's end write its zeros
-  vc_groups(B, lengths, rate, [&](int b0, int nb, int, const VcLens& lens) {
-    hipLaunchKernelGGL(vc_post_kernel<VcLens>, dim3((T + 255) / 256, nb), dim3(256), lds, s, in + (size_t)b0 * ch * T, w, bias,
+  for_item_groups<kVcItems>(B, [&](int b) { return lengths[b] * rate; }, [&](int b0, int nb, const ItemLens<kVcItems>& lens, int) {
+    hipLaunchKernelGGL(vc_post_kernel<ItemLens<kVcItems>>, dim3((T + 255) / 256, nb), dim3(256), lds, s, in + (size_t)b0 * ch * T, w, bias,
                        out + (size_t)b0 * T, ch, T, lens);
   });
 }
 
-// null, or a refusal that names the first item whose length is outside [1, Tmax]
+// "", or a refusal that names the first item whose length is outside [1, Tmax]
 std::string vc_bad_length(const char* what, const int64_t* lengths, int B, int Tmax, const char* tname) {
-  for (int b = 0; b < B; ++b)
-    if (lengths[b] < 1 || lengths[b] > Tmax)
-      return std::string(what) + ": lengths[" + std::to_string(b) + "] = " + std::to_string((long long)lengths[b]) +
-             " must be at least 1 and at most " + tname + " = " + std::to_string(Tmax);
-  return std::string();
+  const std::string bad = bad_length(what, lengths, B, 1, Tmax);
+  return bad.empty() ? bad : bad + " must be at least 1 and at most " + tname + " = " + std::to_string(Tmax);
 }
 
 // BigVGAN.forward (models.py:169-191); lengths null: every item has T frames
