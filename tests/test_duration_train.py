@@ -108,6 +108,35 @@ def test_c_abi_refuses_bad_arguments_without_device_work():
         assert lib.us_duration_predictor_tape_release(h, None) == 0
         assert lib.us_duration_predictor_tape_release(e, None) == -1
         assert lib.us_encoder_tape_release(h, None) == -1                               # unchanged: Encoder handles only
+        # the sentences themselves, whole
+        err = lambda hh: lib.us_frontend_last_error(hh).decode()
+        p = 4096                                   # a non-null address that must never be read
+        fwd = lambda hh, B=1, L=8: lib.us_duration_predictor_forward_train(hh, None, None, None, None, B, L, 0.1, 0, None, 0, None)
+        bwd = lambda hh, B=1, L=8: lib.us_duration_predictor_backward(hh, None, B, L, None, None, 0, None, 0, None)
+        msk = lambda hh, site=0, pd=0.1, out=p: lib.us_duration_predictor_dropout_mask(hh, 0, site, 1, 8, pd, out, None)
+        assert fwd(h) == -4 and err(h) == "us_duration_predictor_forward_train: weight 'conv_1.weight' has not been loaded"
+        assert bwd(h) == -4 and err(h) == "us_duration_predictor_backward: weight 'conv_1.weight' has not been loaded"
+        for B, L in ((0, 8), (1, 0), (65536, 8), (1, 65536)):
+            assert fwd(h, B, L) == -1 and err(h) == "us_duration_predictor_forward_train: bad B or L"
+            assert bwd(h, B, L) == -1 and err(h) == "us_duration_predictor_backward: bad B or L"
+        for site in (2, -1):
+            assert msk(h, site=site) == -1 and err(h) == "us_duration_predictor_dropout_mask: no such site"
+        for pd in (1.0, float("nan")):
+            assert msk(h, pd=pd) == -1 and err(h) == "us_duration_predictor_dropout_mask: p_dropout must be below 1"
+        assert msk(h, out=None) == -1 and err(h) == "us_duration_predictor_dropout_mask: bad argument"
+        for hh in (e, None):                       # an Encoder handle, and none at all (the sentence is then the library's last error)
+            assert fwd(hh) == -1 and err(hh) == "us_duration_predictor_forward_train: not a duration-predictor handle"
+            assert bwd(hh) == -1 and err(hh) == "us_duration_predictor_backward: not a duration-predictor handle"
+            assert lib.us_duration_predictor_tape_release(hh, None) == -1
+            assert err(hh) == "us_duration_predictor_tape_release: not a duration-predictor handle"
+            assert msk(hh) == -1 and err(hh) == "us_duration_predictor_dropout_mask: bad argument"
+            assert lib.us_duration_predictor_forward(hh, None, None, None, None, 1, 8, None, 0, None) == -1
+            assert err(hh) == "us_duration_predictor_forward: not a duration-predictor handle"
+            assert lib.us_duration_predictor_train_workspace_bytes(hh, 1, 8) == 0
+        assert lib.us_encoder_tape_release(h, None) == -1 and err(h) == "us_encoder_tape_release: not an encoder handle"
+        # workspace sizes in bytes, as the library gave them before the layout took its offsets from handle.h's WsTake
+        for (B, L), want in {(1, 8): 135680, (3, 19): 165376, (4, 60): 273664}.items():
+            assert lib.us_duration_predictor_train_workspace_bytes(h, B, L) == want, (B, L)
     finally:
         lib.us_frontend_destroy(h)
         lib.us_frontend_destroy(e)

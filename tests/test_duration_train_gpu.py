@@ -195,16 +195,30 @@ def test_a_stale_or_released_tape_is_refused():
     n = int(lib.us_duration_predictor_train_workspace_bytes(dp._h, B, L))
     ws, logw, gl = torch.empty(n, dtype=torch.uint8, device="cuda"), torch.empty(B, 1, L).cuda(), torch.ones(B, 1, L).cuda()
     bwd = lambda w, b=B: lib.us_duration_predictor_backward(dp._h, gl.data_ptr(), b, L, None, None, 0, w.data_ptr(), n, None)
-    assert bwd(ws) == -1                                                 # never run
+    err = lambda h: lib.us_frontend_last_error(h).decode()
+    no_tape = "us_duration_predictor_backward: the workspace holds no us_duration_predictor_forward_train of this B and L"
+    assert bwd(ws) == -1 and err(dp._h) == no_tape                       # never run
     assert lib.us_duration_predictor_forward_train(dp._h, x.data_ptr(), m.data_ptr(), g.data_ptr(), logw.data_ptr(), B, L, 0.0, 0,
                                                    ws.data_ptr(), n, None) == 0
     assert bwd(ws) == 0
-    assert bwd(ws, 1) == -1                                              # another B
+    assert bwd(ws, 1) == -1 and err(dp._h) == no_tape                    # another B
     other = make(TINY, 0.0).train()
     other._sync(torch.device("cuda"), training_ok=True)
     assert lib.us_duration_predictor_backward(other._h, gl.data_ptr(), B, L, None, None, 0, ws.data_ptr(), n, None) == -1      # foreign
+    assert err(other._h) == no_tape
+    # the gradient list's refusals, as whole sentences; every one returns before anything is launched
+    gb = torch.empty(1, device="cuda")
+    keys, ptrs = (C.c_char_p * 1)(b"proj.bias"), (C.c_void_p * 1)(gb.data_ptr())
+    lst = lambda k=keys, q=ptrs, nk=1, gp=gl.data_ptr(): lib.us_duration_predictor_backward(dp._h, gp, B, L, k, q, nk, ws.data_ptr(), n, None)
+    assert lst(gp=None) == -1 and err(dp._h) == "us_duration_predictor_backward: null grad_logw"
+    for bad in (dict(nk=-1), dict(k=None), dict(q=None)):
+        assert lst(**bad) == -1 and err(dp._h) == "us_duration_predictor_backward: bad gradient list", bad
+    for bad in (dict(k=(C.c_char_p * 1)(None)), dict(q=(C.c_void_p * 1)(None))):
+        assert lst(**bad) == -1 and err(dp._h) == "us_duration_predictor_backward: null key or gradient buffer", bad
+    assert lst(k=(C.c_char_p * 1)(b"nope")) == -2 and err(dp._h) == "us_duration_predictor_backward: unknown key 'nope'"
+    assert lst() == 0                                                    # the refusals left the tape alone
     assert lib.us_duration_predictor_tape_release(dp._h, ws.data_ptr()) == 0
-    assert bwd(ws) == -1                                                 # released
+    assert bwd(ws) == -1 and err(dp._h) == no_tape                       # released
     torch.cuda.synchronize()
     # the module releases a call's tape with its workspace
     out = dp(x, m, g=g, reverse=True)

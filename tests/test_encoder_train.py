@@ -108,6 +108,42 @@ def test_c_abi_new_entry_points_refuse_bad_arguments_without_device_work():
         assert lib.us_encoder_forward_train(h, None, None, None, None, None, 1, 8, 0.1, 0, None, 0, None) == -4
         assert lib.us_encoder_dropout_mask(h, 0, 3 + 4 * TINY.n_layers, 1, 8, 0.1, None, None) == -1
         assert lib.us_encoder_tape_release(h, None) == 0
+        # the sentences themselves, whole
+        err = lambda hh: lib.us_frontend_last_error(hh).decode()
+        p = 4096                                   # a non-null address that must never be read
+        fwd = lambda hh, B=1, L=8: lib.us_encoder_forward_train(hh, None, None, None, None, None, B, L, 0.1, 0, None, 0, None)
+        bwd = lambda hh, B=1, L=8: lib.us_encoder_backward(hh, None, None, B, L, None, None, 0, None, 0, None)
+        msk = lambda hh, site=0, pd=0.1, out=p: lib.us_encoder_dropout_mask(hh, 0, site, 1, 8, pd, out, None)
+        assert fwd(h) == -4 and err(h) == "us_encoder_forward_train: weight 'emb.weight' has not been loaded"
+        assert bwd(h) == -4 and err(h) == "us_encoder_backward: weight 'emb.weight' has not been loaded"
+        assert fwd(h, L=9000) == -4 and err(h) == "us_encoder_forward_train: weight 'emb.weight' has not been loaded"   # before the LDS bound
+        for B, L in ((0, 8), (1, 0), (65536, 8), (1, 65536)):
+            assert fwd(h, B, L) == -1 and err(h) == "us_encoder_forward_train: bad B or L"
+            assert bwd(h, B, L) == -1 and err(h) == "us_encoder_backward: bad B or L"
+        assert msk(h, site=3 + 4 * TINY.n_layers) == -1 and err(h) == "us_encoder_dropout_mask: no such site"
+        assert msk(h, site=-1) == -1 and err(h) == "us_encoder_dropout_mask: no such site"
+        assert msk(h, pd=1.0) == -1 and err(h) == "us_encoder_dropout_mask: p_dropout must be below 1"
+        assert msk(h, pd=float("nan")) == -1 and err(h) == "us_encoder_dropout_mask: p_dropout must be below 1"
+        assert msk(h, out=None) == -1 and err(h) == "us_encoder_dropout_mask: bad argument"
+        # a DurationPredictor handle, and none at all (the sentence is then the library's last error)
+        d = C.c_void_p()
+        dc = _lib.us_duration_config(16, 24, 3, 12)
+        assert lib.us_duration_predictor_create(C.byref(d), C.byref(dc)) == 0
+        try:
+            for hh in (d, None):
+                assert fwd(hh) == -1 and err(hh) == "us_encoder_forward_train: not an encoder handle"
+                assert bwd(hh) == -1 and err(hh) == "us_encoder_backward: not an encoder handle"
+                assert lib.us_encoder_tape_release(hh, None) == -1 and err(hh) == "us_encoder_tape_release: not an encoder handle"
+                assert msk(hh) == -1 and err(hh) == "us_encoder_dropout_mask: bad argument"
+                assert lib.us_encoder_forward(hh, None, None, None, None, None, 1, 8, None, 0, None) == -1
+                assert err(hh) == "us_encoder_forward: not an encoder handle"
+                assert lib.us_encoder_train_workspace_bytes(hh, 1, 8) == 0 and lib.us_encoder_debug_workspace_bytes(hh, 1, 8) == 0
+        finally:
+            lib.us_frontend_destroy(d)
+        # workspace sizes in bytes, as the library gave them before the layouts took their offsets from handle.h's WsTake
+        sizes = {(1, 8): (322304, 70144), (3, 19): (603648, 87552), (4, 60): (1848832, 136448)}
+        for (B, L), want in sizes.items():
+            assert (lib.us_encoder_train_workspace_bytes(h, B, L), lib.us_encoder_debug_workspace_bytes(h, B, L)) == want, (B, L)
     finally:
         lib.us_frontend_destroy(h)
 
@@ -165,6 +201,33 @@ def test_c_abi_debug_entry_points_refuse_bad_arguments_without_device_work():
         assert ac() == -4 and ac(dO=p, DS=p, rest=p, gk=p) == -4
         assert emb(h, None, p, p, 1, 8, None) == -1 and emb(h, p, p, None, 1, 8, None) == -1 and emb(h, p, p, p, 1, 0, None) == -1
         assert emb(h, p, p, p, 1, 8, None) == -4
+        # the sentences themselves, whole
+        err = lambda hh: lib.us_frontend_last_error(hh).decode()
+        lnb = lambda B=1, L=8: ln(h, b"prenet.norm_layers.0", p, p, None, 1.0, p, p, p, B, L, p, 1 << 30, None)
+        acb = lambda B=1, L=8: att(h, 0, p, p, p, p, 0.0, 0, p, p, None, None, None, None, None, None, None, B, L, p, 1 << 30, None)
+        calls = {"us_encoder_debug_conv": lambda B=1, L=8: fwd(b"proj_m", B=B, L=L), "us_encoder_debug_ln_bwd": lnb,
+                 "us_encoder_debug_attention": acb, "us_encoder_debug_embed_grad": lambda B=1, L=8: emb(h, p, p, p, B, L, None)}
+        for name, call in calls.items():
+            for B, L in ((0, 8), (1, 0), (65536, 8), (1, 65536), (65535, 33)):          # the last: B * L * 1024 passes 2^31
+                assert call(B, L) == -1 and err(h) == name + ": bad B or L", (name, B, L)
+            assert call(1, 9000) == -1 and err(h) == name + ": more than ~8000 symbols per utterance"     # before the weights
+            assert call() == -4 and err(h) == name + ": weight 'emb.weight' has not been loaded"
+        assert fwd(b"proj_m", mode=1, dout=p, out=None, dw=p, db=p) == -4
+        small_ws = conv(h, b"proj_m", 0, p, None, None, None, None, 1.0, 0, -1, 0.0, 0, p, None, None, 1, 8, p, 16, None)
+        assert small_ws == -4                      # the workspace is looked at after the weights
+        dp = C.c_void_p()
+        dc = _lib.us_duration_config(16, 24, 3, 12)
+        assert lib.us_duration_predictor_create(C.byref(dp), C.byref(dc)) == 0
+        try:
+            for hh in (dp, None):
+                wrong = {"us_encoder_debug_conv": lambda: conv(hh, b"proj_m", 0, p, None, None, None, None, 1.0, 0, -1, 0.0, 0, p, None, None, 1, 8, p, 1 << 30, None),
+                         "us_encoder_debug_ln_bwd": lambda: ln(hh, b"prenet.norm_layers.0", p, p, None, 1.0, p, p, p, 1, 8, p, 1 << 30, None),
+                         "us_encoder_debug_attention": lambda: att(hh, 0, p, p, p, p, 0.0, 0, p, p, None, None, None, None, None, None, None, 1, 8, p, 1 << 30, None),
+                         "us_encoder_debug_embed_grad": lambda: emb(hh, p, p, p, 1, 8, None)}
+                for name, call in wrong.items():
+                    assert call() == -1 and err(hh) == name + ": not an encoder handle", name
+        finally:
+            d(dp)
     finally:
         d(h)
 

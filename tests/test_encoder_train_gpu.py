@@ -256,6 +256,32 @@ def test_stale_tapes_and_in_place_weight_changes_are_refused():
     assert lib.us_encoder_backward(enc._h, out[0].data_ptr(), None, 2, 8, keys, ptrs, 1, ws.data_ptr(), n, s) == -1   # other L
     assert lib.us_encoder_tape_release(enc._h, ws.data_ptr()) == 0
     assert lib.us_encoder_backward(enc._h, out[0].data_ptr(), None, 2, 9, keys, ptrs, 1, ws.data_ptr(), n, s) == -1   # released
+    # the refusals that lie behind loaded weights, as whole sentences; every one returns before anything is launched
+    err = lambda h: lib.us_frontend_last_error(h).decode()
+    B, L = 2, 7
+    ids, lens = ids[:, :L].contiguous(), torch.LongTensor([7, 4]).cuda()
+    n = int(lib.us_encoder_train_workspace_bytes(enc._h, B, L))
+    ws = torch.empty(n, dtype=torch.uint8, device="cuda")
+    out = [torch.empty(B, cfg.n_feats, L, device="cuda"), torch.empty(B, cfg.n_channels, L, device="cuda"), torch.empty(B, 1, L, device="cuda")]
+    gmu = torch.ones(B, cfg.n_feats, L, device="cuda")
+    bwd = lambda h, b=B, k=keys, q=ptrs, nk=1: lib.us_encoder_backward(h, gmu.data_ptr(), None, b, L, k, q, nk, ws.data_ptr(), n, s)
+    no_tape = "us_encoder_backward: the workspace holds no us_encoder_forward_train of this B and L"
+    assert bwd(enc._h) == -1 and err(enc._h) == no_tape                                         # never run
+    assert lib.us_encoder_forward_train(enc._h, ids.data_ptr(), lens.data_ptr(), *[o.data_ptr() for o in out], B, L, 0.1, 1, ws.data_ptr(), n, s) == 0
+    assert bwd(enc._h, b=1) == -1 and err(enc._h) == no_tape                                    # another B
+    other = make(cfg)
+    other._sync(torch.device("cuda"), training_ok=True)
+    assert bwd(other._h) == -1 and err(other._h) == no_tape                                     # another handle's tape
+    assert bwd(enc._h, nk=-1) == -1 and err(enc._h) == "us_encoder_backward: bad gradient list"
+    assert bwd(enc._h, k=None) == -1 and err(enc._h) == "us_encoder_backward: bad gradient list"
+    assert bwd(enc._h, q=None) == -1 and err(enc._h) == "us_encoder_backward: bad gradient list"
+    assert bwd(enc._h, k=(C.c_char_p * 1)(None)) == -1 and err(enc._h) == "us_encoder_backward: null key or gradient buffer"
+    assert bwd(enc._h, q=(C.c_void_p * 1)(None)) == -1 and err(enc._h) == "us_encoder_backward: null key or gradient buffer"
+    assert bwd(enc._h, k=(C.c_char_p * 1)(b"nope")) == -2 and err(enc._h) == "us_encoder_backward: unknown key 'nope'"
+    assert bwd(enc._h) == 0                                                                     # the refusals left the tape alone
+    assert lib.us_encoder_tape_release(enc._h, ws.data_ptr()) == 0
+    assert bwd(enc._h) == -1 and err(enc._h) == no_tape                                         # released
+    torch.cuda.synchronize()
 
 
 def test_prior_loss_and_segment_backward_match_torch():

@@ -265,11 +265,6 @@ __global__ __launch_bounds__(256) void dt_mse_loss_kernel(const float* __restric
     d_logw[i] = (float)(2.0 * ((double)logw[i] - (double)(logf(w[i] + 1e-6f) * mask[i])) / den);
 }
 
-__global__ void dt_mask_out_kernel(float* out, long long n, Drop d) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    out[i] = et_keep(d, (unsigned long long)i);
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 // workspace of one training forward (the tape) and of its backward, in floats from a 256-byte aligned base
@@ -282,26 +277,22 @@ DtLayout dt_layout(const us_frontend* h, int B, int L) {
   const auto& c = h->dc;
   const size_t rows = (size_t)B * L, F = c.filter_channels, Cin = (size_t)c.in_channels + c.spk_emb_dim, K = c.kernel_size;
   DtLayout o{};
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t r = at; at += (n + 63) / 64 * 64; return r; };
+  WsTake take;
   o.xin = take(rows * Cin); o.mask = take(rows); o.r1 = take(rows * F); o.h1 = take(rows * F); o.r2 = take(rows * F);
-  o.tape_end = at;
+  o.tape_end = take.total;
   o.dc = take(rows * F); o.dh = take(rows * F);
   o.wd = take(F * F * K);
   o.wpart = take((size_t)wgrad_splits((long long)rows) * F * std::max(F, Cin) * K);
   o.part = take((size_t)kDtChunks * kDtSums * F);
   o.part_b = take(kDtChunks);
-  size_t params = 0;
-  for (const auto& kv : h->w) params += kv.second.numel();
-  o.arena = take(params);
-  o.total = at;
+  o.arena = take(h->total_numel());
+  o.total = take.total;
   return o;
 }
 
 int dt_check(us_frontend* h, const char* what, int B, int L) {
-  if (!h || h->kind != 1) return fe_fail(h, US_EINVAL, std::string(what) + ": not a duration-predictor handle");
-  if (B <= 0 || L <= 0 || B > 65535 || L > 65535) return fe_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
-  return fe_check(h, what);
+  const int rc = fe_accept(h, kDuration, what, B, L);
+  return rc != US_OK ? rc : h->all_loaded(what);
 }
 
 template <bool kHead>
@@ -324,7 +315,7 @@ extern "C" {
 using namespace us;
 
 size_t us_duration_predictor_train_workspace_bytes(us_frontend_handle h, int B, int L) {
-  if (!h || h->kind != 1 || B <= 0 || L <= 0) return 0;
+  if (!h || h->kind != kDuration || B <= 0 || L <= 0) return 0;
   return dt_layout(h, B, L).total * sizeof(float) + 256;
 }
 
@@ -347,7 +338,7 @@ int us_duration_predictor_forward_train(us_frontend_handle h, const float* x, co
   const float p = p_dropout < 0.f ? 0.f : p_dropout;       // negative: the reference in eval mode (autograd still runs)
   float* mask = base + l.mask;
   hipError_t e = hipMemcpyAsync(mask, x_mask, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return fe_fail(h, US_EHIP, std::string("us_duration_predictor_forward_train: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return h->hip("us_duration_predictor_forward_train", e);
   fe_gather_concat(s, x, g, base + l.xin, B, L, c.in_channels, c.spk_emb_dim);
   gemm_conv_fwd(h, s, "conv_1", base + l.xin, base + l.r1, mask, nullptr, rows, L, true, true, false, no_drop());
   DtFwdArgs a{};
@@ -358,11 +349,8 @@ int us_duration_predictor_forward_train(us_frontend_handle h, const float* x, co
   a.r = base + l.r2; a.gamma = h->w["norm_2.gamma"].dev; a.beta = h->w["norm_2.beta"].dev; a.out = logw;      // [B][L][1] == [B][1][L]
   a.pw = h->w["proj.weight"].dev; a.pb = h->w["proj.bias"].dev; a.drop = make_drop(seed, 1, p);
   dt_norm_fwd<true>(s, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fe_fail(h, US_EHIP, std::string("us_duration_predictor_forward_train: ") + hipGetErrorString(e));
-  EncoderTape t;
-  t.B = B; t.L = L; t.p_dropout = p_dropout; t.seed = seed;
-  h->tapes[workspace] = t;
+  if ((rc = fe_launched(h, "us_duration_predictor_forward_train")) != US_OK) return rc;
+  h->tapes[workspace] = EncoderTape{B, L, p_dropout, seed};
   return US_OK;
 }
 
@@ -370,32 +358,17 @@ int us_duration_predictor_backward(us_frontend_handle h, const float* grad_logw,
                                    int n_grads, void* workspace, size_t workspace_bytes, us_stream stream) {
   int rc = dt_check(h, "us_duration_predictor_backward", B, L);
   if (rc != US_OK) return rc;
-  auto it = h->tapes.find(workspace);
-  if (!workspace || it == h->tapes.end() || it->second.B != B || it->second.L != L ||
-      workspace_bytes < us_duration_predictor_train_workspace_bytes(h, B, L))
-    return fe_fail(h, US_EINVAL, "us_duration_predictor_backward: the workspace holds no us_duration_predictor_forward_train of this B and L");
+  EncoderTape tape;
+  if ((rc = fe_tape(h, "us_duration_predictor_backward", "us_duration_predictor_forward_train", B, L, workspace, workspace_bytes,
+                    us_duration_predictor_train_workspace_bytes(h, B, L), &tape)) != US_OK) return rc;
   if (!grad_logw) return fe_fail(h, US_EINVAL, "us_duration_predictor_backward: null grad_logw");
-  if (n_grads < 0 || (n_grads > 0 && (!keys || !grads))) return fe_fail(h, US_EINVAL, "us_duration_predictor_backward: bad gradient list");
-  const EncoderTape tape = it->second;
   const DtLayout l = dt_layout(h, B, L);
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* base = ws_align(workspace);
   const long long rows = (long long)B * L;
   const int F = h->dc.filter_channels;
-  // destinations: the caller's buffer, or a slot of the workspace's arena for a key nobody asked for
   std::map<std::string, float*> dst;
-  for (int i = 0; i < n_grads; ++i) {
-    if (!keys[i] || !grads[i]) return fe_fail(h, US_EINVAL, "us_duration_predictor_backward: null key or gradient buffer");
-    if (!h->w.count(keys[i])) return fe_fail(h, US_ENOKEY, std::string("us_duration_predictor_backward: unknown key '") + keys[i] + "'");
-    dst[keys[i]] = grads[i];
-  }
-  {
-    size_t at = l.arena;
-    for (const auto& k : h->keys) {
-      if (!dst.count(k)) dst[k] = base + at;
-      at += h->w[k].numel();
-    }
-  }
+  if ((rc = fe_grad_table(h, "us_duration_predictor_backward", keys, grads, n_grads, base + l.arena, &dst)) != US_OK) return rc;
   auto G = [&](const char* k) { return dst.at(k); };
   const float p = tape.p_dropout < 0.f ? 0.f : tape.p_dropout;
   float* mask = base + l.mask;
@@ -422,27 +395,20 @@ int us_duration_predictor_backward(us_frontend_handle h, const float* grad_logw,
   hipLaunchKernelGGL(dt_sum_kernel, dim3(sum_blocks), dim3(256), 0, s, q);
   // conv_1: weight gradient only (x is detached by the reference and g gets no gradient: the data gradient is never computed)
   gemm_conv_wgrad(h, s, "conv_1", base + l.xin, mask, true, dc, rows, L, base + l.wpart, G("conv_1.weight"));
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_duration_predictor_backward: ") + hipGetErrorString(e));
+  return fe_launched(h, "us_duration_predictor_backward");
 }
 
 int us_duration_predictor_tape_release(us_frontend_handle h, const void* workspace) {
-  if (!h || h->kind != 1) return fe_fail(h, US_EINVAL, "us_duration_predictor_tape_release: not a duration-predictor handle");
-  h->tapes.erase(workspace);
-  return US_OK;
+  return fe_tape_release(h, kDuration, "us_duration_predictor_tape_release", workspace);
 }
 
 int us_duration_predictor_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B, int L, float p_dropout, float* out,
                                        us_stream stream) {
-  if (!h || h->kind != 1 || !out || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_duration_predictor_dropout_mask: bad argument");
+  if (!h || h->kind != kDuration || !out || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_duration_predictor_dropout_mask: bad argument");
   if (site < 0 || site > 1) return fe_fail(h, US_EINVAL, "us_duration_predictor_dropout_mask: no such site");
   if (!(p_dropout < 1.f)) return fe_fail(h, US_EINVAL, "us_duration_predictor_dropout_mask: p_dropout must be below 1");
-  const long long n = (long long)B * h->dc.filter_channels * L;
-  const long long blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(dt_mask_out_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), out, n,
-                     make_drop(seed, site, p_dropout < 0.f ? 0.f : p_dropout));
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_duration_predictor_dropout_mask: ") + hipGetErrorString(e));
+  return fe_keep_mask(h, "us_duration_predictor_dropout_mask", static_cast<hipStream_t>(stream), out, (long long)B * h->dc.filter_channels * L,
+                      make_drop(seed, site, p_dropout < 0.f ? 0.f : p_dropout));
 }
 
 int us_duration_predictor_mse_loss(const float* logw, const float* w, const float* x_mask, float* loss, float* d_logw, int B, int L,

@@ -264,12 +264,6 @@ __global__ void et_drop_mask_kernel(const float* in, const float* mask, float* o
   }
 }
 
-// the scaled keep mask of one site, in the reference's layout (test hook of us_encoder_dropout_mask)
-__global__ void et_mask_out_kernel(float* out, long long n, Drop d) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    out[i] = et_keep(d, (unsigned long long)i);
-}
-
 // ---- LayerNorm backward (eps 1e-4, encoder.py:21-30) -------------------------------------------------------------------
 constexpr int kLnPerLane = 16;      // C <= 1024
 // dx of y = LN(x) for upstream dy; with `gate` (the stored prenet output drop(relu(y))), dy is first taken through the dropout
@@ -479,8 +473,7 @@ Layout et_layout(const us_frontend* h, int B, int L) {
   const size_t rows = (size_t)B * L, C = c.n_channels, F = c.filter_channels, H = c.n_heads;
   const size_t plane = rows * C, att = (size_t)B * H * L * L;
   Layout o{};
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t r = at; at += (n + 63) / 64 * 64; return r; };
+  WsTake take;
   o.ids = take(2 * rows);
   o.mask = take(rows);
   o.x0 = take(plane);
@@ -493,7 +486,7 @@ Layout et_layout(const us_frontend* h, int B, int L) {
   }
   o.xf = take(plane);
   o.mu = take(rows * c.n_feats);
-  o.tape_end = at;
+  o.tape_end = take.total;
   const size_t wide = rows * std::max(std::max(C, F), (size_t)c.n_feats);
   o.g = take(plane); o.t = take(plane); o.d1 = take(wide); o.dh = take(wide); o.dyx = take(plane); o.dyo = take(plane);
   o.dq = take(plane); o.dk = take(plane); o.dv = take(plane); o.ds = take(att);
@@ -503,10 +496,8 @@ Layout et_layout(const us_frontend* h, int B, int L) {
   o.cpart = take((size_t)kColChunks * std::max(std::max(C, F), (size_t)c.n_feats));
   const size_t nw = 2 * (size_t)c.window_size + 1, D = C / H;
   o.rpart = take(4 * (size_t)B * nw * D);      // doubles
-  size_t params = 0;
-  for (const auto& kv : h->w) params += kv.second.numel();
-  o.arena = take(params);
-  o.total = at;
+  o.arena = take(h->total_numel());
+  o.total = take.total;
   return o;
 }
 
@@ -585,8 +576,7 @@ Layout et_debug_layout(const us_frontend* h, int B, int L) {
   const auto& c = h->ec;
   const size_t rows = (size_t)B * L, C = c.n_channels, F = c.filter_channels;
   Layout o{};
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t r = at; at += (n + 63) / 64 * 64; return r; };
+  WsTake take;
   o.splits = wgrad_splits((long long)rows);
   o.wd = take(conv_numel(c));
   o.wpart = take((size_t)o.splits * conv_numel(c));
@@ -594,19 +584,22 @@ Layout et_debug_layout(const us_frontend* h, int B, int L) {
   o.dyx = take(rows * C);
   o.dyo = take(rows * C);
   o.rpart = take(4 * (size_t)B * (2 * (size_t)c.window_size + 1) * (C / c.n_heads));      // doubles
-  o.total = at;
+  o.total = take.total;
   return o;
 }
 
-int et_check(us_frontend* h, const char* what, int B, int L) {
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
-  if (B <= 0 || L <= 0 || B > 65535 || L > 65535) return fe_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
-  const int rc = fe_check(h, what);
-  if (rc != US_OK) return rc;
+// the attention backward keeps two rows of L and one of D in LDS
+int et_lds_bound(us_frontend* h, const char* what, int L) {
   const int D = h->ec.n_channels / h->ec.n_heads;
   if (((size_t)2 * L + D + 128) * sizeof(float) > 64 * 1024)
-    return fe_fail(h, US_EINVAL, std::string(what) + ": more than ~8000 symbols per utterance");
+    return h->fail(US_EINVAL, std::string(what) + ": more than ~8000 symbols per utterance");
   return US_OK;
+}
+
+int et_check(us_frontend* h, const char* what, int B, int L) {
+  int rc = fe_accept(h, kEncoder, what, B, L);
+  if (rc == US_OK) rc = h->all_loaded(what);
+  return rc != US_OK ? rc : et_lds_bound(h, what, L);
 }
 
 }  // namespace
@@ -663,7 +656,7 @@ extern "C" {
 using namespace us;
 
 size_t us_encoder_train_workspace_bytes(us_frontend_handle h, int B, int L) {
-  if (!h || h->kind != 0 || B <= 0 || L <= 0) return 0;
+  if (!h || h->kind != kEncoder || B <= 0 || L <= 0) return 0;
   return et_layout(h, B, L).total * sizeof(float) + 256;
 }
 
@@ -693,10 +686,8 @@ int us_encoder_forward_train(us_frontend_handle h, const int64_t* ids, const int
   if ((rc = encoder_forward(h, x.s, b, m, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
   hipError_t e = hipMemcpyAsync(x_mask, x.mask, (size_t)x.rows * sizeof(float), hipMemcpyDeviceToDevice, x.s);
   if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return fe_fail(h, US_EHIP, std::string("us_encoder_forward_train: ") + hipGetErrorString(e));
-  EncoderTape t;
-  t.B = B; t.L = L; t.p_dropout = p_dropout; t.seed = seed;
-  h->tapes[workspace] = t;
+  if (e != hipSuccess) return h->hip("us_encoder_forward_train", e);
+  h->tapes[workspace] = EncoderTape{B, L, p_dropout, seed};
   return US_OK;
 }
 
@@ -704,31 +695,16 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
                         float* const* grads, int n_grads, void* workspace, size_t workspace_bytes, us_stream stream) {
   int rc = et_check(h, "us_encoder_backward", B, L);
   if (rc != US_OK) return rc;
-  auto it = h->tapes.find(workspace);
-  if (!workspace || it == h->tapes.end() || it->second.B != B || it->second.L != L ||
-      workspace_bytes < us_encoder_train_workspace_bytes(h, B, L))
-    return fe_fail(h, US_EINVAL, "us_encoder_backward: the workspace holds no us_encoder_forward_train of this B and L");
-  if (n_grads < 0 || (n_grads > 0 && (!keys || !grads))) return fe_fail(h, US_EINVAL, "us_encoder_backward: bad gradient list");
-  const EncoderTape tape = it->second;
+  EncoderTape tape;
+  if ((rc = fe_tape(h, "us_encoder_backward", "us_encoder_forward_train", B, L, workspace, workspace_bytes,
+                    us_encoder_train_workspace_bytes(h, B, L), &tape)) != US_OK) return rc;
   const auto& c = h->ec;
   const Layout l = et_layout(h, B, L);
   Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
   x.mask = x.f(l.mask);
   const int C = c.n_channels, nf = c.n_feats;
-  // destinations: the caller's buffer, or a slot of the workspace's arena for a key nobody asked for
   std::map<std::string, float*> dst;
-  for (int i = 0; i < n_grads; ++i) {
-    if (!keys[i] || !grads[i]) return fe_fail(h, US_EINVAL, "us_encoder_backward: null key or gradient buffer");
-    if (!h->w.count(keys[i])) return fe_fail(h, US_ENOKEY, std::string("us_encoder_backward: unknown key '") + keys[i] + "'");
-    dst[keys[i]] = grads[i];
-  }
-  {
-    size_t at = l.arena;
-    for (const auto& k : h->keys) {
-      if (!dst.count(k)) dst[k] = x.f(at);
-      at += h->w[k].numel();
-    }
-  }
+  if ((rc = fe_grad_table(h, "us_encoder_backward", keys, grads, n_grads, x.f(l.arena), &dst)) != US_OK) return rc;
   auto G = [&](const std::string& k) { return dst.at(k); };
   const float p = tape.p_dropout < 0.f ? 0.f : tape.p_dropout, p_prenet = tape.p_dropout < 0.f ? 0.f : kPrenetP;
   const uint64_t seed = tape.seed;
@@ -784,18 +760,15 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
     else conv_bwd(x, cp, x.f(l.x0), true, d1, g, g, nullptr, 1.f, true, G(cp + ".weight"), G(cp + ".bias"));
   }
   embed_grad(x.s, reinterpret_cast<const long long*>(x.f(l.ids)), g, G("emb.weight"), x.rows, c.n_vocab, C);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_encoder_backward: ") + hipGetErrorString(e));
+  return fe_launched(h, "us_encoder_backward");
 }
 
 int us_encoder_tape_release(us_frontend_handle h, const void* workspace) {
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, "us_encoder_tape_release: not an encoder handle");
-  h->tapes.erase(workspace);
-  return US_OK;
+  return fe_tape_release(h, kEncoder, "us_encoder_tape_release", workspace);
 }
 
 int us_encoder_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B, int L, float p_dropout, float* out, us_stream stream) {
-  if (!h || h->kind != 0 || !out || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_encoder_dropout_mask: bad argument");
+  if (!h || h->kind != kEncoder || !out || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_encoder_dropout_mask: bad argument");
   const auto& c = h->ec;
   if (site < 0 || site >= kPrenetLayers + kSitesPerLayer * c.n_layers) return fe_fail(h, US_EINVAL, "us_encoder_dropout_mask: no such site");
   long long n = (long long)B * c.n_channels * L;
@@ -804,10 +777,7 @@ int us_encoder_dropout_mask(us_frontend_handle h, uint64_t seed, int site, int B
   if (site < kPrenetLayers) p = p_dropout < 0.f ? 0.f : kPrenetP;
   else if ((site - kPrenetLayers) % kSitesPerLayer == kSiteAttnP) n = (long long)B * c.n_heads * L * L;
   else if ((site - kPrenetLayers) % kSitesPerLayer == kSiteFfnRelu) n = (long long)B * c.filter_channels * L;
-  hipLaunchKernelGGL(et_mask_out_kernel, dim3(et_blocks(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), out, n,
-                     make_drop(seed, site, p));
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string("us_encoder_dropout_mask: ") + hipGetErrorString(e));
+  return fe_keep_mask(h, "us_encoder_dropout_mask", static_cast<hipStream_t>(stream), out, n, make_drop(seed, site, p));
 }
 
 // ---- one launch group alone, for kernel-level parity tests (tests/test_encoder_train_kernels_gpu.py) ---------------------------
@@ -815,18 +785,14 @@ namespace {
 
 // what every debug entry point checks before anything else; `lay` receives the scratch layout
 int et_debug_check(us_frontend* h, const char* what, int B, int L, void* workspace, size_t workspace_bytes, Layout* lay) {
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
-  if (B <= 0 || L <= 0 || B > 65535 || L > 65535 || (long long)B * L > 0x7fffffffLL / 1024)
-    return fe_fail(h, US_EINVAL, std::string(what) + ": bad B or L");
-  const int D = h->ec.n_channels / h->ec.n_heads;
-  if (((size_t)2 * L + D + 128) * sizeof(float) > 64 * 1024)
-    return fe_fail(h, US_EINVAL, std::string(what) + ": more than ~8000 symbols per utterance");
-  const int rc = fe_check(h, what);
+  int rc = fe_accept(h, kEncoder, what, B, L);
   if (rc != US_OK) return rc;
+  if ((long long)B * L > 0x7fffffffLL / 1024) return h->fail(US_EINVAL, std::string(what) + ": bad B or L");
+  if ((rc = et_lds_bound(h, what, L)) != US_OK || (rc = h->all_loaded(what)) != US_OK) return rc;
   if (lay) {
     *lay = et_debug_layout(h, B, L);
     if (!workspace || workspace_bytes < lay->total * sizeof(float) + 256)
-      return fe_fail(h, US_EWORKSPACE, std::string(what) + ": workspace too small (us_encoder_debug_workspace_bytes)");
+      return h->fail(US_EWORKSPACE, std::string(what) + ": workspace too small (us_encoder_debug_workspace_bytes)");
   }
   return US_OK;
 }
@@ -834,7 +800,7 @@ int et_debug_check(us_frontend* h, const char* what, int B, int L, void* workspa
 }  // namespace
 
 size_t us_encoder_debug_workspace_bytes(us_frontend_handle h, int B, int L) {
-  if (!h || h->kind != 0 || B <= 0 || L <= 0) return 0;
+  if (!h || h->kind != kEncoder || B <= 0 || L <= 0) return 0;
   return et_debug_layout(h, B, L).total * sizeof(float) + 256;
 }
 
@@ -842,7 +808,8 @@ int us_encoder_debug_conv(us_frontend_handle h, const char* key, int mode, const
                           const float* add, const float* gate, float gate_scale, unsigned flags, int drop_site, float p_dropout, uint64_t seed,
                           float* out, float* dw, float* db, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
   const char* what = "us_encoder_debug_conv";
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  int rc = fe_accept(h, kEncoder, what);
+  if (rc != US_OK) return rc;
   if (!key || mode < US_ENCODER_CONV_FWD || mode > US_ENCODER_CONV_DGRAD || (flags & ~7u))
     return fe_fail(h, US_EINVAL, std::string(what) + ": null key, unknown mode or unknown flag");
   const bool mask_in = flags & US_ENCODER_CONV_MASK_IN, relu = flags & US_ENCODER_CONV_RELU, mask_out = flags & US_ENCODER_CONV_MASK_OUT;
@@ -859,37 +826,35 @@ int us_encoder_debug_conv(us_frontend_handle h, const char* key, int mode, const
   if (wi == h->w.end() || wi->second.shape.size() != 3 || !h->w.count(k + ".bias"))
     return fe_fail(h, US_ENOKEY, std::string(what) + ": unknown convolution '" + k + "'");
   Layout l;
-  const int rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l);
-  if (rc != US_OK) return rc;
+  if ((rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l)) != US_OK) return rc;
   Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, const_cast<float*>(mask)};
   if (fwd) gemm_conv_fwd(h, x.s, k, in, out, mask, add, x.rows, L, mask_in, relu, mask_out, drop_site >= 0 ? make_drop(seed, drop_site, p_dropout) : no_drop());
   else if (wgrad) conv_bwd(x, k, in, mask_in, dout, nullptr, nullptr, nullptr, 1.f, false, dw, db);
   else gemm_conv_dgrad(h, x.s, k, dout, out, mask, add, gate, gate_scale, mask_out, x.rows, L, x.f(l.wd));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return fe_launched(h, what);
 }
 
 int us_encoder_debug_ln_bwd(us_frontend_handle h, const char* key, const float* x_in, const float* dy, const float* gate, float gate_scale,
                             float* dx, float* dgamma, float* dbeta, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
   const char* what = "us_encoder_debug_ln_bwd";
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  int rc = fe_accept(h, kEncoder, what);
+  if (rc != US_OK) return rc;
   if (!key || !x_in || !dy || !dx || !dgamma || !dbeta) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
   const std::string k(key);
   if (!h->w.count(k + ".gamma") || !h->w.count(k + ".beta")) return fe_fail(h, US_ENOKEY, std::string(what) + ": unknown LayerNorm '" + k + "'");
   Layout l;
-  const int rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l);
-  if (rc != US_OK) return rc;
+  if ((rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l)) != US_OK) return rc;
   Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
   ln_bwd(x, k, x_in, dy, gate, gate_scale, dx, dgamma, dbeta);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return fe_launched(h, what);
 }
 
 int us_encoder_debug_attention(us_frontend_handle h, int layer, const float* q, const float* k, const float* v, const float* mask, float p_dropout,
                                uint64_t seed, float* out, float* P, const float* dO, float* DS, float* dq, float* dk, float* dv,
                                float* grad_rel_k, float* grad_rel_v, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
   const char* what = "us_encoder_debug_attention";
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
+  int rc = fe_accept(h, kEncoder, what);
+  if (rc != US_OK) return rc;
   const auto& c = h->ec;
   if (!q || !k || !v || !mask || !out || !P || !(p_dropout >= 0.f && p_dropout < 1.f))
     return fe_fail(h, US_EINVAL, std::string(what) + ": null argument, or p_dropout outside [0, 1)");
@@ -898,8 +863,7 @@ int us_encoder_debug_attention(us_frontend_handle h, int layer, const float* q, 
     return fe_fail(h, US_EINVAL, std::string(what) + ": the backward takes dO and every gradient buffer, the forward alone none of them");
   if (layer < 0 || layer >= c.n_layers) return fe_fail(h, US_ENOKEY, std::string(what) + ": no attention layer " + std::to_string(layer));
   Layout l;
-  const int rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l);
-  if (rc != US_OK) return rc;
+  if ((rc = et_debug_check(h, what, B, L, workspace, workspace_bytes, &l)) != US_OK) return rc;
   Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, const_cast<float*>(mask)};
   const std::string ap = "encoder.attn_layers." + std::to_string(layer);
   AttnArgs a{};
@@ -914,19 +878,17 @@ int us_encoder_debug_attention(us_frontend_handle h, int layer, const float* q, 
     a.dO = dO; a.DS = DS; a.dq = dq; a.dk = dk; a.dv = dv; a.rel_part = reinterpret_cast<double*>(x.f(l.rpart));
     attn_bwd(x.s, a, B, grad_rel_v, grad_rel_k);
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return fe_launched(h, what);
 }
 
 int us_encoder_debug_embed_grad(us_frontend_handle h, const int64_t* ids, const float* dx0, float* grad, int B, int L, us_stream stream) {
   const char* what = "us_encoder_debug_embed_grad";
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, std::string(what) + ": not an encoder handle");
-  if (!ids || !dx0 || !grad) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
-  const int rc = et_debug_check(h, what, B, L, nullptr, 0, nullptr);
+  int rc = fe_accept(h, kEncoder, what);
   if (rc != US_OK) return rc;
+  if (!ids || !dx0 || !grad) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
+  if ((rc = et_debug_check(h, what, B, L, nullptr, 0, nullptr)) != US_OK) return rc;
   embed_grad(static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(ids), dx0, grad, (long long)B * L, h->ec.n_vocab, h->ec.n_channels);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fe_fail(h, US_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+  return fe_launched(h, what);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Host-side state of a `us_frontend_handle` and what crosses between frontend.hip (the Encoder's forward in both modes, the
 // DurationPredictor), encoder_train.hip (the MFMA convolution, the Encoder's backward) and duration_train.hip (the
-// DurationPredictor's training): the dropout stream, the attention arguments, the forward's buffer table and the launchers the
-// files call in each other.
+// DurationPredictor's training): the dropout stream, the attention arguments, the forward's buffer table, the launchers the
+// files call in each other, and the host logic the two trainable modules share (the entry check, the tape, the gradient table).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,11 +21,12 @@ struct EncoderTape {
   float p_dropout = 0.f;
   uint64_t seed = 0;
 };
+enum { kEncoder = 0, kDuration = 1 };      // us_frontend::kind
 
 }  // namespace us
 
 struct us_frontend : us::WeightTable {
-  int kind = 0;                        // 0: Encoder, 1: DurationPredictor
+  int kind = us::kEncoder;
   us_encoder_config ec{};
   us_duration_config dc{};
   std::map<const void*, us::EncoderTape> tapes;   // training forwards whose tape a workspace holds (us_encoder_tape_release)
@@ -126,9 +127,26 @@ struct EncoderMode {
   float p = 0.f, p_prenet = 0.f;
 };
 
-// the table's fail (h may be null) and all_loaded under the names the three front-end files call them by
+// the table's fail under the name the three front-end files call it by (h may be null)
 inline int fe_fail(us_frontend* h, int code, const std::string& msg) { return WeightTable::fail(h, code, msg); }
-inline int fe_check(us_frontend* h, const char* what) { return h->all_loaded(what); }
+// how an entry point `what` ends once everything is enqueued: a launch's error is the call's
+inline int fe_launched(us_frontend* h, const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip(what, e);
+}
+// ---- frontend.hip: what the entry points of the two modules share --------------------------------------------------------
+// how an entry point opens: h is a handle of `kind` (not null after this) and B, L are in 1..65535 (they become grid dimensions)
+int fe_accept(us_frontend* h, int kind, const char* what, int B = 1, int L = 1);
+// where a backward writes each key's gradient: the caller's buffer for keys[i], for a key nobody asked for its slot of `arena`
+// (total_numel() floats that end a training workspace: every key's gradient in state_dict order, unpadded)
+int fe_grad_table(us_frontend* h, const char* what, const char* const* keys, float* const* grads, int n_grads, float* arena,
+                  std::map<std::string, float*>* dst);
+// *out = the tape the training forward `fwd` left in `workspace` (of `need` bytes) for this B and L
+int fe_tape(us_frontend* h, const char* what, const char* fwd, int B, int L, const void* workspace, size_t have, size_t need,
+            EncoderTape* out);
+int fe_tape_release(us_frontend* h, int kind, const char* what, const void* workspace);
+// out[i] = the factor element i of site d.site is multiplied by, in the reference's layout (the *_dropout_mask test hooks)
+int fe_keep_mask(us_frontend* h, const char* what, hipStream_t s, float* out, long long n, Drop d);
 // frontend.hip: embedding -> prenet -> transformer blocks -> proj_m -> mu_x, x_out in the reference's [B][C][L]
 int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const int64_t* lengths,
                     float* mu_x, float* x_out, int B, int L);

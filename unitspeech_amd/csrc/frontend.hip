@@ -294,6 +294,12 @@ __global__ void fe_gather_concat_kernel(const float* x_cf, const float* g, float
   for (int s = threadIdx.x; s < S; s += blockDim.x) o[C + s] = g[(long long)b * S + s];
 }
 
+// the scaled keep mask of one site, in the reference's layout (fe_keep_mask)
+__global__ void fe_keep_mask_kernel(float* out, long long n, Drop d) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    out[i] = et_keep(d, (unsigned long long)i);
+}
+
 // w[co][ci][k] (torch Conv1d) -> [k][ci][co]
 __global__ void fe_pack_conv_kernel(const float* w, float* out, int Cout, int Cin, int K) {
   const long long n = (long long)Cout * Cin * K;
@@ -353,7 +359,7 @@ void duration_keys(us_frontend* h) {
 
 // activation scratch of one forward call, in floats (the caller owns it: us_frontend_workspace_bytes)
 size_t fe_scratch_floats(const us_frontend* h, long long rows) {
-  if (h->kind == 0) return (size_t)rows * (6 * (size_t)h->ec.n_channels + (size_t)h->ec.filter_channels);      // x, x_org/y, q, k, v, a (C each) + h1 (F)
+  if (h->kind == kEncoder) return (size_t)rows * (6 * (size_t)h->ec.n_channels + (size_t)h->ec.filter_channels);      // x, x_org/y, q, k, v, a (C each) + h1 (F)
   return (size_t)rows * ((size_t)(h->dc.in_channels + h->dc.spk_emb_dim) + 2 * (size_t)h->dc.filter_channels);
 }
 
@@ -395,6 +401,49 @@ void rel_attention_fwd(hipStream_t s, const AttnArgs& a, int B, bool train) {
 
 void fe_gather_concat(hipStream_t s, const float* x_cf, const float* g, float* out, int B, int L, int C, int S) {
   hipLaunchKernelGGL(fe_gather_concat_kernel, dim3(L, B), dim3(256), 0, s, x_cf, g, out, L, C, S);
+}
+
+int fe_accept(us_frontend* h, int kind, const char* what, int B, int L) {
+  if (!h || h->kind != kind)
+    return fe_fail(h, US_EINVAL, std::string(what) + (kind == kEncoder ? ": not an encoder handle" : ": not a duration-predictor handle"));
+  if (B <= 0 || L <= 0 || B > 65535 || L > 65535) return h->fail(US_EINVAL, std::string(what) + ": bad B or L");
+  return US_OK;
+}
+
+int fe_grad_table(us_frontend* h, const char* what, const char* const* keys, float* const* grads, int n_grads, float* arena,
+                  std::map<std::string, float*>* dst) {
+  if (n_grads < 0 || (n_grads > 0 && (!keys || !grads))) return h->fail(US_EINVAL, std::string(what) + ": bad gradient list");
+  for (int i = 0; i < n_grads; ++i) {
+    if (!keys[i] || !grads[i]) return h->fail(US_EINVAL, std::string(what) + ": null key or gradient buffer");
+    if (!h->w.count(keys[i])) return h->fail(US_ENOKEY, std::string(what) + ": unknown key '" + keys[i] + "'");
+    (*dst)[keys[i]] = grads[i];
+  }
+  for (const auto& k : h->keys) {
+    if (!dst->count(k)) (*dst)[k] = arena;
+    arena += h->w[k].numel();
+  }
+  return US_OK;
+}
+
+int fe_tape(us_frontend* h, const char* what, const char* fwd, int B, int L, const void* workspace, size_t have, size_t need,
+            EncoderTape* out) {
+  auto it = h->tapes.find(workspace);
+  if (!workspace || it == h->tapes.end() || it->second.B != B || it->second.L != L || have < need)
+    return h->fail(US_EINVAL, std::string(what) + ": the workspace holds no " + fwd + " of this B and L");
+  *out = it->second;
+  return US_OK;
+}
+
+int fe_tape_release(us_frontend* h, int kind, const char* what, const void* workspace) {
+  const int rc = fe_accept(h, kind, what);
+  if (rc == US_OK) h->tapes.erase(workspace);
+  return rc;
+}
+
+int fe_keep_mask(us_frontend* h, const char* what, hipStream_t s, float* out, long long n, Drop d) {
+  const long long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(fe_keep_mask_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, out, n, d);
+  return fe_launched(h, what);
 }
 
 // The Encoder's forward, once for both modes.  The two convolutions stay two: inference runs L of 100-300 and is latency-bound,
@@ -474,7 +523,7 @@ int us_encoder_create(us_frontend_handle* out, const us_encoder_config* cfg) {
   if (c.n_channels > 1024 || c.filter_channels > 1024)
     return fe_fail(nullptr, US_EINVAL, "us_encoder_create: more than 1024 channels");
   auto* h = new us_frontend();
-  h->kind = 0; h->ec = c;
+  h->kind = kEncoder; h->ec = c;
   (void)hipGetDevice(&h->device);
   encoder_keys(h);
   *out = h;
@@ -488,7 +537,7 @@ int us_duration_predictor_create(us_frontend_handle* out, const us_duration_conf
       c.filter_channels > 1024 || c.in_channels + c.spk_emb_dim > 1024)
     return fe_fail(nullptr, US_EINVAL, "us_duration_predictor_create: bad configuration");
   auto* h = new us_frontend();
-  h->kind = 1; h->dc = c;
+  h->kind = kDuration; h->dc = c;
   (void)hipGetDevice(&h->device);
   duration_keys(h);
   *out = h;
@@ -531,11 +580,11 @@ size_t us_frontend_workspace_bytes(us_frontend_handle h, int B, int L) {
 
 int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x_out, float* x_mask, int B,
                        int L, void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (!h || h->kind != 0) return fe_fail(h, US_EINVAL, "us_encoder_forward: not an encoder handle");
+  int rc = fe_accept(h, kEncoder, "us_encoder_forward");
+  if (rc != US_OK) return rc;
   if (!ids || !lengths || !mu_x || !x_out || !x_mask || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_encoder_forward: bad argument");
   if (B > 65535) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than 65535 items");
-  int rc = fe_check(h, "us_encoder_forward");
-  if (rc != US_OK) return rc;
+  if ((rc = h->all_loaded("us_encoder_forward")) != US_OK) return rc;
   const auto& c = h->ec;
   const int C = c.n_channels, D = C / c.n_heads;
   if (((size_t)L + D + 128) * sizeof(float) > 64 * 1024) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than ~16000 symbols per utterance");
@@ -557,19 +606,18 @@ int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* 
   for (int i = 0; i < kPrenetLayers; ++i) b.pc[i] = b.pa[i] = (i & 1) ? k : q;
   b.layer.assign(c.n_layers, EncoderBufs::Layer{xr, q, k, v, at, nullptr, xr, h1, nullptr, nullptr});
   if ((rc = encoder_forward(h, static_cast<hipStream_t>(stream), b, EncoderMode{}, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : h->hip("us_encoder_forward", e);
+  return fe_launched(h, "us_encoder_forward");
 }
 
 int us_duration_predictor_forward(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,
                                   void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (!h || h->kind != 1) return fe_fail(h, US_EINVAL, "us_duration_predictor_forward: not a duration-predictor handle");
+  int rc = fe_accept(h, kDuration, "us_duration_predictor_forward");
+  if (rc != US_OK) return rc;
   const auto& c = h->dc;
   if (!x || !x_mask || !logw || B <= 0 || L <= 0 || B > 65535) return fe_fail(h, US_EINVAL, "us_duration_predictor_forward: bad argument");
   if ((c.spk_emb_dim > 0) != (g != nullptr))
     return fe_fail(h, US_EINVAL, "us_duration_predictor_forward: g must be given exactly when the module was built with spk_emb_dim > 0");
-  int rc = fe_check(h, "us_duration_predictor_forward");
-  if (rc != US_OK) return rc;
+  if ((rc = h->all_loaded("us_duration_predictor_forward")) != US_OK) return rc;
   const int Cin = c.in_channels + c.spk_emb_dim, F = c.filter_channels;
   const long long rows = (long long)B * L;
   if (!workspace || workspace_bytes < us_frontend_workspace_bytes(h, B, L))
@@ -585,8 +633,7 @@ int us_duration_predictor_forward(us_frontend_handle h, const float* x, const fl
   if ((rc = conv1d(h, s, "conv_2", a1, a2, x_mask, nullptr, B, L, true, true, false)) != US_OK) return rc;
   if ((rc = layernorm(h, s, "norm_2", a2, nullptr, a2, nullptr, rows, F, 1e-5f, false)) != US_OK) return rc;
   if ((rc = conv1d(h, s, "proj", a2, logw, x_mask, nullptr, B, L, true, false, true)) != US_OK) return rc;      // [B][L][1] == [B][1][L]
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : h->hip("us_duration_predictor_forward", e);
+  return fe_launched(h, "us_duration_predictor_forward");
 }
 
 }  // extern "C"

@@ -58,6 +58,7 @@ struct WeightTable {
   }
 
   int num() const { return (int)keys.size(); }
+  size_t total_numel() const { size_t n = 0; for (const auto& kv : w) n += kv.second.numel(); return n; }      // floats of all weights
   const char* key(int i) const { return (i >= 0 && i < num()) ? keys[i].c_str() : nullptr; }
   const char* last_error() const { return err.c_str(); }
 

@@ -203,6 +203,7 @@ class _FrontEndModule(HandleModule):
 class Encoder(_FrontEndModule):
     """`unitspeech/encoder.py:253` `Encoder(n_vocab, n_feats, n_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout,
     n_contentvec=0, window_size=None)`."""
+    _train_abi = "encoder"                     # us_{_train_abi}_forward_train, _backward, _train_workspace_bytes, _tape_release
 
     def __init__(self, n_vocab, n_feats, n_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout=0.0, n_contentvec=0,
                  window_size=None, *, trainable=False):
@@ -237,22 +238,22 @@ class Encoder(_FrontEndModule):
             return _EncoderTrain.apply(self, x, x_lengths, seed, float(self.p_dropout), *params)
         return self._forward_eval(x, x_lengths)
 
+    def _operands(self, x, x_lengths):
+        """What either forward hands to the library: [ids, lengths] as contiguous int64 on x's device, and the (mu_x, x, x_mask) it fills."""
+        (b, l), dev = x.shape, x.device
+        ins = [x.to(torch.int64).contiguous(), x_lengths.to(device=dev, dtype=torch.int64).contiguous()]
+        return ins, (torch.empty(b, self.cfg.n_feats, l, device=dev), torch.empty(b, self.cfg.n_channels, l, device=dev),
+                     torch.empty(b, 1, l, device=dev))
+
     @torch.no_grad()
     def _forward_eval(self, x, x_lengths):
-        device = x.device
-        lib, stream = self._sync(device)
-        b, l = x.shape
-        ids = x.to(torch.int64).contiguous()
-        lens = x_lengths.to(device=device, dtype=torch.int64).contiguous()
-        mu_x = torch.empty(b, self.cfg.n_feats, l, device=device)
-        h = torch.empty(b, self.cfg.n_channels, l, device=device)
-        mask = torch.empty(b, 1, l, device=device)
-        ws = self._workspace(lib, device, b, l)
-        with torch.cuda.device(device):
-            rc = lib.us_encoder_forward(self._h, ids.data_ptr(), lens.data_ptr(), mu_x.data_ptr(), h.data_ptr(), mask.data_ptr(), b, l,
-                                        ws.data_ptr(), ws.numel(), stream)
+        lib, stream = self._sync(x.device)
+        ins, outs = self._operands(x, x_lengths)
+        ws = self._workspace(lib, x.device, *x.shape)
+        with torch.cuda.device(x.device):
+            rc = lib.us_encoder_forward(self._h, *_ptrs(ins + list(outs)), *x.shape, ws.data_ptr(), ws.numel(), stream)
         self._check(lib, rc, "us_encoder_forward")
-        return mu_x, h, mask
+        return outs
 
 
     # ---- one launch group alone (the us_encoder_debug_* test hooks), for tests/test_encoder_train_kernels_gpu.py ---------------
@@ -353,61 +354,75 @@ class Encoder(_FrontEndModule):
         return grad
 
 
-def _release_tape(enc_ref, ptr):
-    enc = enc_ref()
-    if enc is not None and getattr(enc, "_h", None):
-        _lib.load().us_encoder_tape_release(enc._h, ptr)
+def _ptrs(tensors):
+    return [None if t is None else t.data_ptr() for t in tensors]
+
+
+def _f32(t, device):
+    return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+# ---- the autograd bridge of the two trainable modules ----------------------------------------------------------------------
+# Each training forward owns its workspace, which is the tape: ctx keeps it until backward.  The two C ABIs end alike:
+# us_{abi}_forward_train(h, operands..., B, L, p, seed, ws, bytes, stream), us_{abi}_backward(h, upstream..., B, L, keys, grads, n, ws,
+# bytes, stream).
+
+def _release_tape(mod_ref, ptr):
+    mod = mod_ref()
+    if mod is not None and getattr(mod, "_h", None):
+        getattr(_lib.load(), f"us_{mod._train_abi}_tape_release")(mod._h, ptr)
+
+
+def _tape_forward(ctx, mod, operands, b, l, p, seed, params):
+    """Run mod's training forward on `operands` (tensors on the device, or None) into a workspace of its own, kept in ctx as the tape."""
+    device = operands[0].device
+    lib, stream = mod._sync(device, training_ok=True)
+    abi = mod._train_abi
+    ws = torch.empty(int(getattr(lib, f"us_{abi}_train_workspace_bytes")(mod._h, b, l)), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        rc = getattr(lib, f"us_{abi}_forward_train")(mod._h, *_ptrs(operands), b, l, p, seed, ws.data_ptr(), ws.numel(), stream)
+    mod._check(lib, rc, f"us_{abi}_forward_train")
+    ctx.mod, ctx.ws, ctx.shape = mod, ws, (b, l)
+    ctx.versions = [(t.data_ptr(), t._version) for t in params]
+    # the handle forgets this tape when the workspace tensor goes (its memory may then hold anything)
+    weakref.finalize(ws, _release_tape, weakref.ref(mod), ws.data_ptr())
+
+
+def _tape_backward(ctx, upstream, n_inputs):
+    """mod's backward from the tape in ctx for the `upstream` gradients (None: zero); what autograd's backward returns: None for
+    the n_inputs inputs in front of the parameters, then the gradient of every parameter that requires one."""
+    mod, ws, (b, l) = ctx.mod, ctx.ws, ctx.shape
+    sd = mod.state_dict(keep_vars=True)
+    if [(t.data_ptr(), t._version) for t in sd.values()] != ctx.versions:
+        raise RuntimeError(f"{type(mod).__name__} backward: a parameter was modified in place after the training forward (the tape holds "
+                           "activations of the old weights); run the forward again")
+    device = ws.device
+    lib, stream = mod._sync(device, training_ok=True)
+    grads = [torch.empty(t.shape, device=device) if n else None for t, n in zip(sd.values(), ctx.needs_input_grad[n_inputs:])]
+    sel = [(k, g) for k, g in zip(sd, grads) if g is not None]
+    keys = (C.c_char_p * max(len(sel), 1))(*[k.encode() for k, _ in sel])
+    ptrs = (C.c_void_p * max(len(sel), 1))(*[g.data_ptr() for _, g in sel])
+    upstream = [_f32(t, device) for t in upstream]
+    with torch.cuda.device(device):
+        rc = getattr(lib, f"us_{mod._train_abi}_backward")(mod._h, *_ptrs(upstream), b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(),
+                                                          stream)
+    mod._check(lib, rc, f"us_{mod._train_abi}_backward")
+    return (None,) * n_inputs + tuple(grads)
 
 
 class _EncoderTrain(torch.autograd.Function):
-    """us_encoder_forward_train / us_encoder_backward.  Each call owns its workspace (the tape), kept in ctx until backward.
-    p < 0 runs without any dropout (the reference in eval mode, differentiated)."""
+    """us_encoder_forward_train / us_encoder_backward.  p < 0 runs without any dropout (the reference in eval mode, differentiated)."""
 
     @staticmethod
     def forward(ctx, enc, x, x_lengths, seed, p, *params):
-        device = x.device
-        lib, stream = enc._sync(device, training_ok=True)
-        b, l = x.shape
-        ids = x.to(torch.int64).contiguous()
-        lens = x_lengths.to(device=device, dtype=torch.int64).contiguous()
-        mu_x = torch.empty(b, enc.cfg.n_feats, l, device=device)
-        h = torch.empty(b, enc.cfg.n_channels, l, device=device)
-        mask = torch.empty(b, 1, l, device=device)
-        ws = torch.empty(int(lib.us_encoder_train_workspace_bytes(enc._h, b, l)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            rc = lib.us_encoder_forward_train(enc._h, ids.data_ptr(), lens.data_ptr(), mu_x.data_ptr(), h.data_ptr(), mask.data_ptr(), b, l,
-                                              p, seed, ws.data_ptr(), ws.numel(), stream)
-        enc._check(lib, rc, "us_encoder_forward_train")
-        ctx.enc, ctx.ws, ctx.shape = enc, ws, (b, l)
-        ctx.keys = list(enc.state_dict(keep_vars=True).keys())
-        ctx.versions = [(t.data_ptr(), t._version) for t in params]
-        # the handle forgets this tape when the workspace tensor goes (its memory may then hold anything)
-        weakref.finalize(ws, _release_tape, weakref.ref(enc), ws.data_ptr())
-        ctx.mark_non_differentiable(mask)
-        return mu_x, h, mask
+        ins, outs = enc._operands(x, x_lengths)
+        _tape_forward(ctx, enc, ins + list(outs), *x.shape, p, seed, params)
+        ctx.mark_non_differentiable(outs[2])
+        return outs
 
     @staticmethod
     def backward(ctx, g_mu, g_x, _g_mask):
-        enc, ws, (b, l) = ctx.enc, ctx.ws, ctx.shape
-        params = list(enc.state_dict(keep_vars=True).values())
-        if [(t.data_ptr(), t._version) for t in params] != ctx.versions:
-            raise RuntimeError("Encoder backward: a parameter was modified in place after the training forward (the tape holds "
-                               "activations of the old weights); run the forward again")
-        device = ws.device
-        lib, stream = enc._sync(device, training_ok=True)
-        need = ctx.needs_input_grad[5:]
-        shapes = encoder_state_shapes(enc.cfg)
-        grads = [torch.empty(shapes[k], device=device) if n else None for k, n in zip(ctx.keys, need)]
-        sel = [(k, g) for k, g in zip(ctx.keys, grads) if g is not None]
-        keys = (C.c_char_p * max(len(sel), 1))(*[k.encode() for k, _ in sel])
-        ptrs = (C.c_void_p * max(len(sel), 1))(*[g.data_ptr() for _, g in sel])
-        f32 = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
-        g_mu, g_x = f32(g_mu), f32(g_x)
-        with torch.cuda.device(device):
-            rc = lib.us_encoder_backward(enc._h, g_mu.data_ptr() if g_mu is not None else None, g_x.data_ptr() if g_x is not None else None,
-                                         b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(), stream)
-        enc._check(lib, rc, "us_encoder_backward")
-        return (None,) * 5 + tuple(grads)
+        return _tape_backward(ctx, (g_mu, g_x), 5)
 
 
 class DurationPredictor(_FrontEndModule):
@@ -418,6 +433,8 @@ class DurationPredictor(_FrontEndModule):
     every parameter that requires grad: `reverse=True` returns logw, `reverse=False` the loss of :60-62 against `w`.  No gradient leaves
     through `x` (the reference detaches it) or through `g` (a `g` that requires grad is refused rather than silently given None).
     In eval mode under `torch.no_grad()` the inference path runs, so its bits are the non-trainable module's."""
+
+    _train_abi = "duration_predictor"
 
     def __init__(self, in_channels, filter_channels, kernel_size, p_dropout=0.0, spk_emb_dim=0, *, trainable=False):
         super().__init__()
@@ -459,72 +476,35 @@ class DurationPredictor(_FrontEndModule):
             logw = self._forward_eval(x, x_mask, g)
         return logw if reverse else _DurationMseFn.apply(logw, w, x_mask)
 
+    def _operands(self, x, x_mask, g):
+        """What either forward hands to the library: [x, x_mask, g] as contiguous fp32 on x's device (g None without a speaker
+        embedding), and the logw [B, 1, L] it fills."""
+        return [_f32(t, x.device) for t in (x, x_mask, g)], torch.empty(x.shape[0], 1, x.shape[2], device=x.device)
+
     @torch.no_grad()
     def _forward_eval(self, x, x_mask, g):
-        device = x.device
-        lib, stream = self._sync(device)
-        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-        xs, ms = f32(x), f32(x_mask)
-        gs = f32(g) if g is not None else None
-        logw = torch.empty(x.shape[0], 1, x.shape[2], device=device)
-        ws = self._workspace(lib, device, x.shape[0], x.shape[2])
-        with torch.cuda.device(device):
-            rc = lib.us_duration_predictor_forward(self._h, xs.data_ptr(), ms.data_ptr(), gs.data_ptr() if gs is not None else None,
-                                                   logw.data_ptr(), x.shape[0], x.shape[2], ws.data_ptr(), ws.numel(), stream)
+        lib, stream = self._sync(x.device)
+        ins, logw = self._operands(x, x_mask, g)
+        ws = self._workspace(lib, x.device, x.shape[0], x.shape[2])
+        with torch.cuda.device(x.device):
+            rc = lib.us_duration_predictor_forward(self._h, *_ptrs(ins + [logw]), x.shape[0], x.shape[2], ws.data_ptr(), ws.numel(), stream)
         self._check(lib, rc, "us_duration_predictor_forward")
         return logw
 
 
-def _release_duration_tape(dp_ref, ptr):
-    dp = dp_ref()
-    if dp is not None and getattr(dp, "_h", None):
-        _lib.load().us_duration_predictor_tape_release(dp._h, ptr)
-
-
 class _DurationTrain(torch.autograd.Function):
-    """us_duration_predictor_forward_train / us_duration_predictor_backward.  Each call owns its workspace (the tape), kept in ctx
-    until backward.  p < 0 runs without dropout (the reference in eval mode, differentiated)."""
+    """us_duration_predictor_forward_train / us_duration_predictor_backward.  p < 0 runs without dropout (the reference in eval
+    mode, differentiated)."""
 
     @staticmethod
     def forward(ctx, dp, x, x_mask, g, seed, p, *params):
-        device = x.device
-        lib, stream = dp._sync(device, training_ok=True)
-        b, l = x.shape[0], x.shape[2]
-        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-        xs, ms = f32(x), f32(x_mask)
-        gs = f32(g) if g is not None else None
-        logw = torch.empty(b, 1, l, device=device)
-        ws = torch.empty(int(lib.us_duration_predictor_train_workspace_bytes(dp._h, b, l)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            rc = lib.us_duration_predictor_forward_train(dp._h, xs.data_ptr(), ms.data_ptr(), gs.data_ptr() if gs is not None else None,
-                                                         logw.data_ptr(), b, l, p, seed, ws.data_ptr(), ws.numel(), stream)
-        dp._check(lib, rc, "us_duration_predictor_forward_train")
-        ctx.dp, ctx.ws, ctx.shape = dp, ws, (b, l)
-        ctx.keys = list(dp.state_dict(keep_vars=True).keys())
-        ctx.versions = [(t.data_ptr(), t._version) for t in params]
-        weakref.finalize(ws, _release_duration_tape, weakref.ref(dp), ws.data_ptr())
+        ins, logw = dp._operands(x, x_mask, g)
+        _tape_forward(ctx, dp, ins + [logw], x.shape[0], x.shape[2], p, seed, params)
         return logw
 
     @staticmethod
     def backward(ctx, g_logw):
-        dp, ws, (b, l) = ctx.dp, ctx.ws, ctx.shape
-        params = list(dp.state_dict(keep_vars=True).values())
-        if [(t.data_ptr(), t._version) for t in params] != ctx.versions:
-            raise RuntimeError("DurationPredictor backward: a parameter was modified in place after the training forward (the tape holds "
-                               "activations of the old weights); run the forward again")
-        device = ws.device
-        lib, stream = dp._sync(device, training_ok=True)
-        need = ctx.needs_input_grad[6:]
-        shapes = duration_predictor_state_shapes(dp.cfg)
-        grads = [torch.empty(shapes[k], device=device) if n else None for k, n in zip(ctx.keys, need)]
-        sel = [(k, g) for k, g in zip(ctx.keys, grads) if g is not None]
-        keys = (C.c_char_p * max(len(sel), 1))(*[k.encode() for k, _ in sel])
-        ptrs = (C.c_void_p * max(len(sel), 1))(*[g.data_ptr() for _, g in sel])
-        gl = g_logw.detach().to(device=device, dtype=torch.float32).contiguous()
-        with torch.cuda.device(device):
-            rc = lib.us_duration_predictor_backward(dp._h, gl.data_ptr(), b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(), stream)
-        dp._check(lib, rc, "us_duration_predictor_backward")
-        return (None,) * 6 + tuple(grads)
+        return _tape_backward(ctx, (g_logw,), 6)
 
 
 class _DurationMseFn(torch.autograd.Function):
