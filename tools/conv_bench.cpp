@@ -1,5 +1,8 @@
 // Micro-benchmark of the implicit-GEMM convolution kernel on synthetic shapes (build: see tools/conv_bench.sh).
-// usage: conv_bench   (environment: CB_CALIBRATE, CB_ONLY, CB_F16, CB_PRESPLIT, CB_TM, CB_SPLITK, CB_STATS, CB_NO_XCDZ, CB_COLD)
+// usage: conv_bench   (environment: CB_CALIBRATE, CB_ONLY, CB_F16, CB_PRESPLIT, CB_TM, CB_SPLITK, CB_STATS, CB_NO_XCDZ, CB_COLD, CB_XFORM)
+// CB_XFORM: instead of the convolutions, the memory passes that write the two-plane fp16 form at the decode's B' = 3 shapes -- the 4-wide
+// Winograd input transforms (plain and GroupNorm form) and gn_apply's out_split / out2 -- with 8-byte and with lane-paired 16-byte stores,
+// outputs compared byte for byte, and the output transforms over the same bytes as the reference rate.
 // The "S" shapes (wino = 3, with CB_F16) are the 4-wide forms' separate GEMMs as the decoder launches them: each runs on the general kernel and,
 // where the rule routes it, on wino_stream_kernel; the two outputs are compared bit for bit.
 #include <hip/hip_runtime.h>
@@ -202,12 +205,99 @@ static void calibrate() {
   }
 }
 
+// ---- CB_XFORM -------------------------------------------------------------------------------------------------------------------------
+template <class F> static float time_us(F&& launch) {      // warm, ten launches back to back
+  hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  for (int i = 0; i < 3; ++i) CK(launch());
+  CK(hipEventRecord(e0, 0));
+  for (int i = 0; i < 10; ++i) CK(launch());
+  CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+  float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+  CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
+  return ms * 100.f;
+}
+
+static void xform_bench() {
+  struct X { const char* name; int level, C, H, W, form; };
+  const X xs[] = {{"L1 C=256  40x512 F(4x4)", 1, 256, 40, 512, 44}, {"L2 C=512  20x256 F(4x4)", 2, 512, 20, 256, 44},
+                  {"L3 C=1024 10x128 F(2x4)", 3, 1024, 10, 128, 24}, {"L3 C=512  10x128 F(2x4)", 3, 512, 10, 128, 24}};
+  const int B = 3;
+  double* stats; CK(hipMalloc(&stats, (size_t)B * kGroups * kStatStride * 8));
+  float *gamma, *beta, *temb, *mask;
+  CK(hipMalloc(&gamma, 1024 * 4)); CK(hipMalloc(&beta, 1024 * 4)); CK(hipMalloc(&temb, (size_t)B * 1024 * 4)); CK(hipMalloc(&mask, (size_t)B * 1024 * 4));
+  CK(launch_fill_normal(gamma, 1024, 1, 11, 0)); CK(launch_fill_normal(beta, 1024, 1, 12, 0)); CK(launch_fill_normal(temb, (size_t)B * 1024, 1, 13, 0));
+  {
+    std::vector<float> hm((size_t)B * 1024, 1.f);          // item 1: the last 96 frames padded, item 2: all but 64
+    for (int t = 1024 - 96; t < 1024; ++t) hm[1024 + t] = 0.f;
+    for (int t = 64; t < 1024; ++t) hm[2048 + t] = 0.f;
+    CK(hipMemcpy(mask, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+  }
+  printf("%-26s %-6s %-8s %9s %7s  %s\n", "shape", "form", "stores", "us", "TB/s", "V against the 8-byte arm");
+  for (const X& x : xs) {
+    int th, tw; wino4_tiles(x.form, x.H, x.W, &th, &tw);
+    const int nf = wino4_freqs(x.form);
+    const size_t n_x = (size_t)B * x.H * x.W * x.C, n_v = (size_t)nf * B * th * tw * x.C;
+    float *in, *V, *M, *out, *bias;
+    CK(hipMalloc(&in, n_x * 4)); CK(hipMalloc(&V, n_v * 4)); CK(hipMalloc(&M, n_v * 4)); CK(hipMalloc(&out, n_x * 4)); CK(hipMalloc(&bias, x.C * 4));
+    CK(launch_fill_normal(in, n_x, 1, 1, 0)); CK(launch_fill_normal(M, n_v, 1, 2, 0)); CK(launch_fill_normal(bias, x.C, 1, 3, 0));
+    CK(hipMemset(stats, 0, (size_t)B * kGroups * kStatStride * 8));
+    CK(launch_gn_stats(in, x.C, B, x.H * x.W, x.C, stats, 0));
+    WinoGnArgs g; memset(&g, 0, sizeof g);
+    g.stats = stats; g.gamma = gamma; g.beta = beta; g.temb = temb; g.mask = mask; g.mask_ld = 1024; g.mask_step = 1 << x.level; g.mask_bmod = B;
+    const double tb = ((double)n_x + n_v) * 4e-12;
+    for (int gn : {0, 1}) {
+      std::vector<float> ref(n_v), got(n_v);
+      for (int s16 : {0, 1}) {
+        CK(hipMemset(V, 0xff, n_v * 4));                  // every byte must be written by the arm itself
+        const float us = time_us([&] { return launch_wino4_input(x.form, in, x.C, V, B, x.H, x.W, x.C, gn ? &g : nullptr, 0, s16 != 0); });
+        CK(hipMemcpy((s16 ? got : ref).data(), V, n_v * 4, hipMemcpyDeviceToHost));
+        printf("%-26s %-6s %-8s %9.1f %7.2f  %s\n", x.name, gn ? "GN" : "plain", s16 ? "16-byte" : "8-byte", us, tb / (us * 1e-6),
+               s16 ? (memcmp(ref.data(), got.data(), n_v * 4) == 0 ? "bit-identical" : "DIFFERS") : "");
+      }
+    }
+    CK(hipMemset(stats, 0, (size_t)B * kGroups * kStatStride * 8));
+    const float us = time_us([&] { return launch_wino4_output(x.form, M, bias, out, x.C, stats, B, x.H, x.W, x.C, 0); });
+    printf("%-26s %-6s %-8s %9.1f %7.2f  (M + Y: the reference rate)\n", x.name, "output", "16-byte", us, tb / (us * 1e-6));
+    CK(hipFree(in)); CK(hipFree(V)); CK(hipFree(M)); CK(hipFree(out)); CK(hipFree(bias));
+  }
+  {
+    // gn_apply at level 0: block1's form (out_split, time embedding, post-mask) and block2's form (fp32 out + two-plane copy, residual)
+    const int C = 128, H = 80, W = 1024;
+    const size_t n = (size_t)B * H * W * C;
+    float *y, *res, *out, *out2;
+    CK(hipMalloc(&y, n * 4)); CK(hipMalloc(&res, n * 4)); CK(hipMalloc(&out, n * 4)); CK(hipMalloc(&out2, n * 4));
+    CK(launch_fill_normal(y, n, 1, 4, 0)); CK(launch_fill_normal(res, n, 1, 5, 0));
+    CK(hipMemset(stats, 0, (size_t)B * kGroups * kStatStride * 8));
+    CK(launch_gn_stats(y, C, B, H * W, C, stats, 0));
+    for (int form : {0, 1}) {
+      GnApplyArgs a; memset(&a, 0, sizeof a);
+      a.y = y; a.y_ld = C; a.stats = stats; a.gamma = gamma; a.beta = beta; a.mask = mask; a.mask_ld = 1024; a.mask_step = 1; a.mask_bmod = B;
+      a.out = out; a.out_ld = C; a.B = B; a.H = H; a.W = W; a.C = C;
+      if (form == 0) { a.temb = temb; a.temb_ld = C; a.post_mask = 1; a.out_split = 1; }
+      else { a.res = res; a.res_ld = C; a.post_mask = 1; a.out2 = out2; a.out2_ld = C; }
+      const double tb = (double)n * (form == 0 ? 2 : 4) * 4e-12;
+      std::vector<float> ref(n), got(n);
+      for (int s16 : {0, 1}) {
+        a.store16 = s16;
+        float* split = form == 0 ? out : out2;
+        CK(hipMemset(split, 0xff, n * 4));
+        const float us = time_us([&] { return launch_gn_apply(a, 0); });
+        CK(hipMemcpy((s16 ? got : ref).data(), split, n * 4, hipMemcpyDeviceToHost));
+        printf("%-26s %-6s %-8s %9.1f %7.2f  %s\n", "L0 C=128 80x1024 gn_apply", form == 0 ? "split" : "+out2", s16 ? "16-byte" : "8-byte", us, tb / (us * 1e-6),
+               s16 ? (memcmp(ref.data(), got.data(), n * 4) == 0 ? "bit-identical" : "DIFFERS") : "");
+      }
+    }
+    CK(hipFree(y)); CK(hipFree(res)); CK(hipFree(out)); CK(hipFree(out2));
+  }
+}
+
 struct Shape { const char* name; int B, H, W, Cin, Cout, taps; int wino = 0; };   // wino: B = 16 frequencies x 3 items, one weight matrix per frequency
                                                                                   // wino = 3: B frequencies, H x W rows each, no bias (wino_conv's 4-wide branch)
 
 int main() {
   CK(conv_igemm_init());
   if (getenv("CB_CALIBRATE")) calibrate();
+  if (getenv("CB_XFORM")) { xform_bench(); return 0; }
   Shape shapes[] = {{"L0 3x3 128->128", 3, 80, 1024, 128, 128, 9}, {"L1 3x3 256->256", 3, 40, 512, 256, 256, 9},
                     {"L2 3x3 512->512", 3, 20, 256, 512, 512, 9}, {"L3 3x3 1024->1024", 3, 10, 128, 1024, 1024, 9},
                     {"L3 3x3 2048->512", 3, 10, 128, 2048, 512, 9}, {"L0 1x1 128->384", 3, 80, 1024, 128, 384, 1},

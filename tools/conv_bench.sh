@@ -1,8 +1,14 @@
 #!/bin/bash
-# builds and runs the conv micro-benchmark on the GPU box: tools/conv_bench.sh | f16 [filter] | stream [filter] | life [filter] | diag [filter]
+# builds and runs the conv micro-benchmark on the GPU box: tools/conv_bench.sh | f16 [filter] | stream [filter] | life [filter] | diag [filter] | xform
 set -e
 cd "$(dirname "$0")/.."
-hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/conv_bench.cpp unitspeech_amd/csrc/conv_igemm.hip unitspeech_amd/csrc/ops.hip -o /tmp/conv_bench
+SRC="tools/conv_bench.cpp unitspeech_amd/csrc/conv_igemm.hip unitspeech_amd/csrc/ops.hip unitspeech_amd/csrc/wino4.hip unitspeech_amd/csrc/wino.hip"
+hipcc --offload-arch=gfx950 -O3 -std=c++17 $SRC -o /tmp/conv_bench
+if [ "$1" = xform ]; then
+  # the passes that write the two-plane fp16 form, 8-byte against lane-paired 16-byte stores, at the decode's B' = 3 shapes
+  CB_XFORM=1 /tmp/conv_bench
+  exit 0
+fi
 if [ "$1" = f16 ]; then
   # f16x3 GEMM forms on the Winograd-domain shapes: tools/conv_bench.sh f16 [shape filter]
   CB_CALIBRATE=1 CB_ONLY="(none)" /tmp/conv_bench | grep "calibration"
@@ -17,13 +23,13 @@ if [ "$1" = stream ]; then
 fi
 if [ "$1" = life ]; then
   # workgroup lifetimes of the production tile choice (100 MHz stamps; -DUS_LIFE): tools/conv_bench.sh life [shape filter]
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -DUS_LIFE tools/conv_bench.cpp unitspeech_amd/csrc/conv_igemm.hip unitspeech_amd/csrc/ops.hip -o /tmp/cb_life
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -DUS_LIFE $SRC -o /tmp/cb_life
   for tm in ${LIFE_TMS:-0 256 128}; do echo "== CB_TM=$tm"; CB_ONLY="${2:-H3}" CB_F16=1 CB_TM=$tm /tmp/cb_life | grep "TFLOP\|life\|times"; done
   exit 0
 fi
 if [ "$1" = diag ]; then
   # where the three-buffer f16x3 GEMM spends a step: s_memtime stamps (-DUS_STAMP): tools/conv_bench.sh diag [shape filter]
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -DUS_STAMP tools/conv_bench.cpp unitspeech_amd/csrc/conv_igemm.hip unitspeech_amd/csrc/ops.hip -o /tmp/cb_stamp
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -DUS_STAMP $SRC -o /tmp/cb_stamp
   for b in conv_bench cb_stamp; do
     echo "== build: $b (stamp: cycles per step)"
     CB_ONLY="${2:-G3 gemm 1024}" CB_F16=1 CB_TM=256 /tmp/$b | grep "TFLOP\|stamps"

@@ -122,6 +122,9 @@ struct us_decoder {
   int wino_fuse = -1;        // US_WINO_FUSE: Winograd output transform inside the GEMM wherever legal (1), never (0), by launch size (-1, wino_conv)
   bool wino_fuse_gn = true;  // US_WINO_FUSE_GN=0: block1's gn_apply as its own pass
   bool wino_stream = true;   // US_WINO_STREAM=0: the 4-wide forms' K = 256 GEMMs on the general kernel instead of wino_stream_kernel (same bits)
+  bool split_store16 = true; // US_SPLIT_STORE16=0: the memory passes that produce the two-plane fp16 form (Winograd input transforms, gn_apply) write it
+                             // with 8-byte stores per lane instead of lane-paired 16-byte ones (same bits).  The convolution epilogue's out_split
+                             // keeps its 8-byte stores either way
   int f16_tm = 0;            // US_F16_TM: rows per workgroup of the f16x3 Winograd-domain GEMMs (64, 128, 256; 0: the launcher's rule)
   // parameter-gradient chains of a backward pass on side streams (train_host.inc, BwdCtx); US_WGRAD_STREAM=0: everything on the caller's
   // (measured, fine-tune iteration / pre-training step: 1 side stream 10.29 ms / 61.5 ms, 2: 10.43 / 62.5, 3: 11.7 / 62.9)
@@ -522,7 +525,7 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
     int t4h, t4w;
     wino4_tiles(form4, H, W, &t4h, &t4w);
     const int nf = wino4_freqs(form4);
-    hipError_t err4 = launch_wino4_input(form4, in, in_ld, b.wino_v, e.Bp, H, W, K, gn, e.s);
+    hipError_t err4 = launch_wino4_input(form4, in, in_ld, b.wino_v, e.Bp, H, W, K, gn, e.s, e.h->split_store16);
     if (err4 != hipSuccess) return err4;
     ConvArgs a;
     memset(&a, 0, sizeof a);
@@ -549,7 +552,7 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
   // gn: `in` is block1's raw conv output (ld == K); its GroupNorm + Mish + time embedding are evaluated inside the transform
   // f16: U is in the f16x3 form and V is written the same way (two interleaved fp16 planes per value, same bytes and strides)
   hipError_t err = gn ? (in_ld == K ? launch_gn_wino_input(in, b.wino_v, e.Bp, H, W, K, *gn, e.s, f16) : hipErrorInvalidValue)
-                      : launch_wino_input(in, in_ld, b.wino_v, e.Bp, H, W, K, e.s, f16);
+                      : launch_wino_input(in, in_ld, b.wino_v, e.Bp, H, W, K, e.s, f16, e.h->split_store16);
   if (err != hipSuccess) return err;
   ConvArgs a;
   memset(&a, 0, sizeof a);
@@ -715,6 +718,7 @@ hipError_t gn_apply(EvalCtx& e, const float* y, int level, int C, const double* 
   a.res = res; a.res_ld = res_ld; a.res_masked = res_masked ? 1 : 0;
   a.post_mask = post_mask ? 1 : 0;
   a.out_split = out_split ? 1 : 0;
+  a.store16 = e.h->split_store16 ? 1 : 0;
   a.out = out; a.out_ld = out_ld;
   a.out2 = split_copy; a.out2_ld = C;
   a.B = e.Bp; a.H = e.h->cfg.n_feats >> level; a.W = e.T >> level; a.C = C;
@@ -1011,6 +1015,7 @@ hipError_t estimator_eval_impl(EvalCtx& e, const float* x, int Bx, const float* 
         ga.mask = e.mask; ga.mask_ld = e.T; ga.mask_step = 1; ga.mask_bmod = e.Bm;
         ga.res2_in = b.in2; ga.res2_w = r.res.w->buf.p; ga.res2_b = r.res.b->buf.p;
         ga.post_mask = 1;
+        ga.store16 = e.h->split_store16 ? 1 : 0;
         ga.out = b.P[0]; ga.out_ld = c;
         if (r2_copy) { ga.out2 = b.Q[0]; ga.out2_ld = c; }
         ga.B = e.Bp; ga.H = F; ga.W = T; ga.C = c;
@@ -1229,6 +1234,7 @@ int us_decoder_create_ex(us_handle* out, const us_config* cfg, unsigned flags) {
   if (const char* wf = getenv("US_WINO_FUSE")) h->wino_fuse = atoi(wf) != 0 ? 1 : 0;
   if (const char* wf = getenv("US_WINO_FUSE_GN")) h->wino_fuse_gn = atoi(wf) != 0;
   if (const char* ws = getenv("US_WINO_STREAM")) h->wino_stream = atoi(ws) != 0;
+  if (const char* ss = getenv("US_SPLIT_STORE16")) h->split_store16 = atoi(ss) != 0;
   if (const char* wt = getenv("US_F16_TM")) h->f16_tm = atoi(wt) == 64 || atoi(wt) == 128 || atoi(wt) == 256 ? atoi(wt) : 0;
   if (const char* ws = getenv("US_WGRAD_STREAM")) h->wgrad_side_streams = atoi(ws) < 0 ? 0 : (atoi(ws) > Tape::kSideMax ? Tape::kSideMax : atoi(ws));
   {

@@ -232,6 +232,8 @@ struct GnApplyArgs {
   float* out; int out_ld;
   float* out2; int out2_ld;                                // optional second copy of the result in the two-plane form (out stays fp32): a tensor
                                                            // read both as a residual (fp32) and by a direct f16x3 convolution (pre-split)
+  int store16;                                             // out_split / out2 written by lane pairs in whole 16-byte pieces (store_split_pair16,
+                                                           // pack_f16.h) where the launch meets its preconditions; 0: 8-byte pieces.  Same bytes.
   int B, H, W, C;
 };
 hipError_t launch_gn_apply(const GnApplyArgs& a, hipStream_t s);
@@ -415,7 +417,8 @@ hipError_t launch_wino_pack_weight(const float* src, float* dst, int Cout, int C
 // x: [B][H][W][x_ld] (C channels) -> V: [16][B][th][tw][C], th = ceil(H/2), tw = ceil(W/2); zero padding outside the image
 // split = true: V is written as two interleaved fp16 planes per value (same bytes; C % 8 == 0) for the f16x3 GEMM
 // (conv_igemm_kernel<.., F16 = true>)
-hipError_t launch_wino_input(const float* x, int x_ld, float* V, int B, int H, int W, int C, hipStream_t s, bool split = false);
+// store16 (split only): lane pairs write whole 16-byte pieces of the planes (store_split_pair16, pack_f16.h); same bytes
+hipError_t launch_wino_input(const float* x, int x_ld, float* V, int B, int H, int W, int C, hipStream_t s, bool split = false, bool store16 = true);
 // V of d = (mish(GroupNorm(y)) * mask + temb) * mask, y a raw conv output [B][H][W][C] (ld = C): block1's gn_apply of a
 // ResnetBlock folded into the input transform of its second convolution (C a multiple of 32)
 struct WinoGnArgs {
@@ -446,7 +449,9 @@ bool wino4_form_ok(int form);
 int wino4_freqs(int form);
 void wino4_tiles(int form, int H, int W, int* th, int* tw);
 // gn (optional): x is block1's raw conv output (ld == C) and d = (mish(GroupNorm(x)) * mask + temb) * mask is evaluated on the fly (h_out unsupported)
-hipError_t launch_wino4_input(int form, const float* x, int x_ld, float* V, int B, int H, int W, int C, const WinoGnArgs* gn, hipStream_t s);
+// store16: lane pairs write V in whole 16-byte pieces (store_split_pair16, pack_f16.h); false: every lane its own two 8-byte pieces.  Same bytes.
+hipError_t launch_wino4_input(int form, const float* x, int x_ld, float* V, int B, int H, int W, int C, const WinoGnArgs* gn, hipStream_t s,
+                              bool store16 = true);
 hipError_t launch_wino4_output(int form, const float* M, const float* bias, float* out, int out_ld, double* stats, int B, int H, int W, int C,
                                hipStream_t s);
 hipError_t launch_wino4_pack_weight(int form, const float* src, float* dst, int Cout, int Cin, hipStream_t s);

@@ -3,6 +3,7 @@
 // All of them are streaming passes with 16-byte coalesced accesses along the channel (pixel-major layout) or
 // the time axis (planar [B][F][T] boundary tensors); reductions use wave64 shuffles.
 #include "kernels.h"
+#include "pack_f16.h"
 
 namespace us {
 
@@ -207,6 +208,7 @@ hipError_t launch_gn_stats(const float* y, int ld, int B, int n, int C, double* 
 // GroupNorm apply + Mish + mask (+ time-embedding addend) (+ masked residual)
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
+  typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
   // A thread owns one channel quad for its whole life (C/4 divides 256 or is a multiple of it for every width of the
   // U-Net), so the per-channel scale/shift are folded once: z = y*sc + sh with sc = rstd*gamma, sh = beta - mean*sc.
   const int b = blockIdx.y;
@@ -285,9 +287,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
       o += a.res_masked ? rr * m : rr;
     }
     if (a.post_mask) o *= m;
-    if (a.out_split) {
+    if (a.out_split || o2b) {
       // hi = fp16(x), lo = fp16((x - hi) * 2^11); a value beyond the fp16 range is reported, not clamped (kernels.h)
-      typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
       half4_t hi, lo;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -296,26 +297,20 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
         hi[k] = h;
         lo[k] = l;
       }
-      _Float16* oh = reinterpret_cast<_Float16*>(ob + p * a.out_ld) + 2 * (c & ~7) + (c & 7);
-      *reinterpret_cast<half4_t*>(oh) = hi;
-      *reinterpret_cast<half4_t*>(oh + 8) = lo;
-    } else {
-      *reinterpret_cast<f32x4*>(ob + p * a.out_ld + c) = o;
+      const int co = 2 * (c & ~7) + (c & 7);      // the hi quad in halves; lo 8 halves further
+      auto store_planes = [&](float* row) {
+        _Float16* oh = reinterpret_cast<_Float16*>(row) + co;
+        if (a.store16) {      // lanes 2k, 2k + 1 hold quads c, c + 4 of pixel p (i has the lane's parity, C / 4 is even: launcher)
+          store_split_pair16(oh, hi, lo);
+        } else {
+          *reinterpret_cast<half4_t*>(oh) = hi;
+          *reinterpret_cast<half4_t*>(oh + 8) = lo;
+        }
+      };
+      if (a.out_split) store_planes(ob + p * a.out_ld);
+      if (o2b) store_planes(o2b + p * a.out2_ld);
     }
-    if (o2b) {
-      typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-      half4_t hi, lo;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        us_half h, l;
-        split_f16x3(o[k], h, l, over);
-        hi[k] = h;
-        lo[k] = l;
-      }
-      _Float16* oh = reinterpret_cast<_Float16*>(o2b + p * a.out2_ld) + 2 * (c & ~7) + (c & 7);
-      *reinterpret_cast<half4_t*>(oh) = hi;
-      *reinterpret_cast<half4_t*>(oh + 8) = lo;
-    }
+    if (!a.out_split) *reinterpret_cast<f32x4*>(ob + p * a.out_ld + c) = o;
     if (fixed_quad) {
       p += rpi;
       w += wstep;
@@ -332,6 +327,9 @@ hipError_t launch_gn_apply(const GnApplyArgs& a_in, hipStream_t s) {
     return hipErrorInvalidValue;
   if (a.out_split && (a.C % 8 != 0 || a.out_ld % 8 != 0 || a.out == a.y)) return hipErrorInvalidValue;
   if (a.out2 && (a.C % 8 != 0 || a.out2_ld % 8 != 0 || a.out2 == a.y || a.out2 == a.out || a.out2 == a.res)) return hipErrorInvalidValue;
+  // 16-byte stores of the two-plane form: an even quad count per pixel puts quads c, c + 4 of one pixel on lanes 2k, 2k + 1 (256-thread blocks,
+  // a grid stride that is a multiple of 256) and makes `total` even, so a pair leaves the loop together
+  if (a.C % 8 != 0 || !(a.out_split || a.out2)) a.store16 = 0;
   long long total = (long long)a.H * a.W * (a.C / 4);
   int blocks = (int)((total + 256 * 4 - 1) / (256 * 4));
   if (blocks < 1) blocks = 1;

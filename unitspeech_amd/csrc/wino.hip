@@ -27,7 +27,9 @@ __device__ __forceinline__ void split_f16(const f32x4& v, half4& hi, half4& lo, 
     lo[k] = l;
   }
 }
-template <bool SPLIT>
+// S16 (SPLIT only): the lane pair (2k, 2k + 1) holds channel quads c, c + 4 of one tile and writes them as two whole 16-byte pieces
+// (store_split_pair16, pack_f16.h) instead of four 8-byte ones; same bytes.
+template <bool SPLIT, bool S16 = false>
 __device__ __forceinline__ void store_v(float* __restrict__ V, long long idx, const f32x4& v, bool& over) {
   if (!SPLIT) {
     *reinterpret_cast<f32x4*>(V + idx) = v;
@@ -36,13 +38,18 @@ __device__ __forceinline__ void store_v(float* __restrict__ V, long long idx, co
     half4 hi, lo;
     split_f16(v, hi, lo, over);
     const long long o = 2 * (idx & ~7LL) + (idx & 7);
-    *reinterpret_cast<half4*>(vh + o) = hi;
-    *reinterpret_cast<half4*>(vh + o + 8) = lo;
+    if (S16) {
+      store_split_pair16(vh + o, hi, lo);
+    } else {
+      *reinterpret_cast<half4*>(vh + o) = hi;
+      *reinterpret_cast<half4*>(vh + o + 8) = lo;
+    }
   }
 }
 
 // one thread = one (tile, channel quad); grid (blocks, B)
-template <bool SPLIT>
+// S16: i has the lane's parity (256-thread blocks, an even grid stride) and C % 8 == 0 makes per_item even: a lane pair shares its tile and its fate
+template <bool SPLIT, bool S16 = false>
 __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, int x_ld, float* __restrict__ V, int B, int H, int W,
                                                          int C, unsigned* range_flag) {
   bool over = false;
@@ -83,23 +90,26 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
     for (int r = 0; r < 4; ++r) {
       // columns: v = t B
       f32x4 v0 = tt[r][0] - tt[r][2], v1 = tt[r][1] + tt[r][2], v2 = tt[r][2] - tt[r][1], v3 = tt[r][1] - tt[r][3];
-      store_v<SPLIT>(V, vi + (long long)(r * 4 + 0) * plane, v0, over);
-      store_v<SPLIT>(V, vi + (long long)(r * 4 + 1) * plane, v1, over);
-      store_v<SPLIT>(V, vi + (long long)(r * 4 + 2) * plane, v2, over);
-      store_v<SPLIT>(V, vi + (long long)(r * 4 + 3) * plane, v3, over);
+      store_v<SPLIT, S16>(V, vi + (long long)(r * 4 + 0) * plane, v0, over);
+      store_v<SPLIT, S16>(V, vi + (long long)(r * 4 + 1) * plane, v1, over);
+      store_v<SPLIT, S16>(V, vi + (long long)(r * 4 + 2) * plane, v2, over);
+      store_v<SPLIT, S16>(V, vi + (long long)(r * 4 + 3) * plane, v3, over);
     }
   }
   if (SPLIT) range_report(range_flag, over, kRangeAct);
 }
 
-hipError_t launch_wino_input(const float* x, int x_ld, float* V, int B, int H, int W, int C, hipStream_t s, bool split) {
+hipError_t launch_wino_input(const float* x, int x_ld, float* V, int B, int H, int W, int C, hipStream_t s, bool split, bool store16) {
   if (C % 4 != 0 || x_ld % 4 != 0) return hipErrorInvalidValue;
   const long long per_item = (long long)((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
   if (per_item >= (1LL << 31)) return hipErrorInvalidValue;
   int blocks = (int)((per_item + 255) / 256);
   if (blocks < 1) blocks = 1;
   if (blocks > 4096) blocks = 4096;
-  if (split) hipLaunchKernelGGL(wino_input_kernel<true>, dim3(blocks, B), dim3(256), 0, s, x, x_ld, V, B, H, W, C, current_range_flag());
+  // (the lane pairs of the 16-byte stores need an even quad count per tile; otherwise every lane keeps its own 8-byte pieces)
+  if (split && store16 && C % 8 == 0)
+    hipLaunchKernelGGL((wino_input_kernel<true, true>), dim3(blocks, B), dim3(256), 0, s, x, x_ld, V, B, H, W, C, current_range_flag());
+  else if (split) hipLaunchKernelGGL(wino_input_kernel<true>, dim3(blocks, B), dim3(256), 0, s, x, x_ld, V, B, H, W, C, current_range_flag());
   else hipLaunchKernelGGL(wino_input_kernel<false>, dim3(blocks, B), dim3(256), 0, s, x, x_ld, V, B, H, W, C, (unsigned*)nullptr);
   return hipGetLastError();
 }

@@ -93,7 +93,10 @@ template <> struct Bt<2> {
 // 72 stores with 64-bit address arithmetic each, a branch per pixel, a full IEEE division inside every Mish.  Now: pixels come through a
 // buffer descriptor (an offset beyond it reads zeros: no branches, the padding for free), V is addressed as uniform plane base + one
 // 32-bit offset, the Mish reciprocal is v_rcp_f32, and the range check is a running maximum instead of a compare per value.
-template <int MH, int MW, bool GN>
+// S16: a lane pair writes its two channel quads as whole 16-byte pieces (store_split_pair16, pack_f16.h) instead of four 8-byte ones:
+// 36 store instructions per F(4x4) tile instead of 72.  i has the lane's parity (256-thread blocks, an even grid stride) and per_item is even
+// (C % 8 == 0), so a pair always holds quads c, c + 4 of one tile and leaves the loop together.
+template <int MH, int MW, bool GN, bool S16>
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ x, int x_ld, float* __restrict__ V, int B, int H, int W,
                                                           int C, WinoGnArgs g, unsigned* range_flag) {
   constexpr int NH = Coef<MH>::N, NW = Coef<MW>::N;
@@ -186,8 +189,13 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
           lo[k] = (us_half)((xv - (float)h) * 2048.f);
         }
         _Float16* pf = vb + (long long)(ii * NW + j) * plane_h;      // uniform: a scalar base per frequency
-        *reinterpret_cast<half4w*>(pf + ho) = hi;
-        *reinterpret_cast<half4w*>(pf + ho + 8) = lo;
+        if (S16) {
+          store_split_pair16(pf + ho, hi, lo);       // (per frequency, in front of its store: nothing stays live across frequencies)
+          __builtin_amdgcn_sched_barrier(0);
+        } else {
+          *reinterpret_cast<half4w*>(pf + ho) = hi;
+          *reinterpret_cast<half4w*>(pf + ho + 8) = lo;
+        }
       }
     }
   }
@@ -362,7 +370,22 @@ void wino4_tiles(int form, int H, int W, int* th, int* tw) {
   *tw = (W + mw - 1) / mw;
 }
 
-hipError_t launch_wino4_input(int form, const float* x, int x_ld, float* V, int B, int H, int W, int C, const WinoGnArgs* gn, hipStream_t s) {
+namespace {
+template <int MH, int MW>
+void launch_input(bool gn, bool store16, dim3 grid, hipStream_t s, const float* x, int x_ld, float* V, int B, int H, int W, int C, const WinoGnArgs& g,
+                  unsigned* rf) {
+  if (gn) {
+    if (store16) hipLaunchKernelGGL((wino4_input_kernel<MH, MW, true, true>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
+    else hipLaunchKernelGGL((wino4_input_kernel<MH, MW, true, false>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
+  } else {
+    if (store16) hipLaunchKernelGGL((wino4_input_kernel<MH, MW, false, true>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
+    else hipLaunchKernelGGL((wino4_input_kernel<MH, MW, false, false>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
+  }
+}
+}  // namespace
+
+hipError_t launch_wino4_input(int form, const float* x, int x_ld, float* V, int B, int H, int W, int C, const WinoGnArgs* gn, hipStream_t s,
+                              bool store16) {
   if (!wino4_form_ok(form) || C % 8 != 0 || x_ld % 4 != 0 || B > 65535) return hipErrorInvalidValue;
   // 32-bit byte offsets inside one item (buffer descriptor) and 32-bit element offsets inside one (frequency, item) plane of V
   if ((long long)H * W * x_ld * 4 >= (1LL << 31) || (long long)H * W * C >= (1LL << 30)) return hipErrorInvalidValue;
@@ -376,13 +399,10 @@ hipError_t launch_wino4_input(int form, const float* x, int x_ld, float* V, int 
   wino4_tiles(form, H, W, &th, &tw);
   const dim3 grid(grid_for((long long)th * tw * (C / 4)), B);
   unsigned* rf = current_range_flag();
-  if (form == 44) {
-    if (gn) hipLaunchKernelGGL((wino4_input_kernel<4, 4, true>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
-    else hipLaunchKernelGGL((wino4_input_kernel<4, 4, false>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
-  } else {
-    if (gn) hipLaunchKernelGGL((wino4_input_kernel<2, 4, true>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
-    else hipLaunchKernelGGL((wino4_input_kernel<2, 4, false>), grid, dim3(256), 0, s, x, x_ld, V, B, H, W, C, g, rf);
-  }
+  // store16: C % 8 == 0 (checked above) makes the quad count per tile even, so lanes 2k, 2k + 1 of the 256-thread blocks hold quads c, c + 4
+  // of one tile and per_item is even: the lane-pair preconditions of store_split_pair16 hold for every launch that gets here
+  if (form == 44) launch_input<4, 4>(gn != nullptr, store16, grid, s, x, x_ld, V, B, H, W, C, g, rf);
+  else launch_input<2, 4>(gn != nullptr, store16, grid, s, x, x_ld, V, B, H, W, C, g, rf);
   return hipGetLastError();
 }
 
