@@ -231,14 +231,24 @@ int us_tts_durations(const float* logw, const float* x_mask, float* w_ceil, int6
                      float length_scale, us_stream stream);
 int us_tts_align(const float* cond_x, const float* w_ceil, const float* x_mask, const int64_t* y_lengths, float* cond_y,
                  float* attn, float* y_mask, int B, int F, int L, int Tp, us_stream stream);
+/* ---- mel-rate alignment of voice conversion (scripts/voice_conversion.py:22-33), the counterpart of us_tts_align --------
+ * us_vc_align: cond_y [B,F,Tp] = F.interpolate(cond_x[b, :, :x_lengths[b]], size=y_lengths[b], mode='linear') per item, each as
+ *   if it were alone (never from the padded L), zeros on [y_lengths[b], Tp); y_mask [B,Tp] = t < y_lengths[b].  cond_x [B,F,L];
+ *   x_lengths, y_lengths [B] int64 on the device, which the caller has validated: 1 <= x_lengths[b] <= L, 1 <= y_lengths[b] <= Tp
+ *   (values outside are clamped, so nothing is read out of bounds).  The source coordinate is evaluated exactly in integers:
+ *   num = max((2t + 1) Lx - Ly, 0), i0 = num / (2 Ly), lambda = (num mod 2 Ly) / (2 Ly), out = (1 - lambda) x[i0] + lambda x[i1].
+ *   One launch, no host sync. */
+int us_vc_align(const float* cond_x, const int64_t* x_lengths, const int64_t* y_lengths, float* cond_y, float* y_mask, int B, int F,
+                int L, int Tp, us_stream stream);
 
 /* ---- the two learned modules of the conditioning producer, inference -------------------------------
  * `Encoder` (unitspeech/encoder.py:253-308; text encoder and unit encoder are two instances) and `DurationPredictor`
  * (unitspeech/duration_predictor.py:24-63, reverse=True).  Same conventions as the decoder handle: the caller owns the
  * activation scratch (us_frontend_workspace_bytes), nothing is allocated or freed by a forward call, and a call made while
- * another device than the handle's is current is refused (US_EINVAL).  Dropout is the identity (eval mode); `n_contentvec > 0`
- * (encoder.py:281: a Linear instead of the Embedding) and `heads_share=False` are not built -- no configuration of the
- * reference uses them (conf/hydra_config.py:85-116). */
+ * another device than the handle's is current is refused (US_EINVAL).  Dropout is the identity (eval mode).  `n_contentvec > 0`
+ * (encoder.py:279-283: a Linear(n_contentvec -> n_channels, bias=False) instead of the Embedding; checkpoints/voice-conversion.json
+ * sets 768) is a handle kind of its own, us_encoder_create_contentvec below; `heads_share=False` is not built -- no
+ * configuration of the reference uses it (conf/hydra_config.py:85-116). */
 typedef struct us_frontend* us_frontend_handle;
 typedef struct us_encoder_config {
   int32_t n_vocab;          /* len(symbols) + 1 (text) / n_units (unit encoder) */
@@ -269,6 +279,28 @@ const char* us_frontend_last_error(us_frontend_handle h);
 size_t us_frontend_workspace_bytes(us_frontend_handle h, int B, int L);
 int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x, float* x_mask, int B, int L,
                        void* workspace, size_t workspace_bytes, us_stream stream);
+/* The Encoder with a Linear front (the ContentVec encoder of voice conversion).  us_encoder_create_contentvec: cfg as for
+ * us_encoder_create (cfg->n_vocab is ignored), 1 <= n_contentvec <= 1024 else US_EINVAL; the key table is the reference's, with
+ * emb.weight [n_channels, n_contentvec] (Linear layout) and every other key unchanged.
+ * us_encoder_forward_features: feats [B,L,n_contentvec] fp32 in place of the ids; outputs and workspace as us_encoder_forward.
+ *   x0 = (feats . emb.weight^T) * sqrt(n_channels) runs on the fp32 matrix cores, reduction order fixed and independent of B and L;
+ *   rows at or past lengths[b] are NOT READ (they may hold anything, NaN included) and give zeros.  The convolutions run on the
+ *   fp32 FMA kernel of us_encoder_forward (measured faster than the matrix-core GEMM at L = 499 and 1499).  An id handle here, or a
+ *   ContentVec handle in us_encoder_forward / us_encoder_forward_train / us_encoder_backward, is US_EINVAL.
+ * us_encoder_forward_features_train / us_encoder_backward_features: us_encoder_forward_train / us_encoder_backward for such a
+ *   handle (same schedule, tape, workspace size, dropout sites and gradient table).  The backward takes feats again (the tape does
+ *   not copy them) and produces emb.weight's gradient [n_channels, n_contentvec] = sqrt(n_channels) * sum over valid rows of
+ *   dx0[row][c] * feats[row][k] with the split weight-gradient GEMM, partial sums added in a fixed order; there is no gradient
+ *   with respect to feats. */
+int us_encoder_create_contentvec(us_frontend_handle* out, const us_encoder_config* cfg, int32_t n_contentvec);
+int us_encoder_forward_features(us_frontend_handle h, const float* feats, const int64_t* lengths, float* mu_x, float* x, float* x_mask,
+                                int B, int L, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_encoder_forward_features_train(us_frontend_handle h, const float* feats, const int64_t* lengths, float* mu_x, float* x,
+                                      float* x_mask, int B, int L, float p_dropout, uint64_t seed, void* workspace,
+                                      size_t workspace_bytes, us_stream stream);
+int us_encoder_backward_features(us_frontend_handle h, const float* feats, const float* grad_mu, const float* grad_x, int B, int L,
+                                 const char* const* keys, float* const* grads, int n_grads, void* workspace, size_t workspace_bytes,
+                                 us_stream stream);
 /* ---- training of the Encoder (encoder.py:253-308 in train mode; csrc/encoder_train.hip) --------------------------------
  * us_encoder_forward_train: the forward with every Dropout of the reference -- the prenet's three relu_drop (p = 0.5), and in
  *   each transformer layer the attention probabilities, EncoderModule.drop after attention, the FFN's drop after the ReLU and

@@ -44,6 +44,10 @@ def encoder_forward(sd: Dict[str, torch.Tensor], n_heads: int, ids: torch.Tensor
                     masks: Optional[Dict[int, torch.Tensor]] = None, tape: Optional[Dict[str, torch.Tensor]] = None):
     """-> (mu_x [B, n_feats, L], x [B, C, L], x_mask [B, 1, L]); differentiable in every tensor of sd.
 
+    `ids` [B, L] of an integer dtype are symbols for the Embedding front; a floating-point `ids` [B, L, n_contentvec] holds
+    features for the Linear front (encoder.py:279-280, `emb.weight` [C, n_contentvec]).  Feature rows at or past an item's length
+    count as zeros whatever they hold (the library does not read them).
+
     With `tape` (a dict), the intermediates a kernel-level test needs are stored in it under the names below, each with its
     gradient retained: after a backward, `tape[name].grad` is the operand the corresponding backward launch reads."""
     masks = masks or {}
@@ -56,10 +60,16 @@ def encoder_forward(sd: Dict[str, torch.Tensor], n_heads: int, ids: torch.Tensor
         return t
     drop = lambda t, site: t * masks[site].to(t.dtype) if site in masks else t
     emb = sd["emb.weight"]
-    C = emb.shape[1]
     L = ids.shape[1]
-    x = keep("x0", (emb[ids] * math.sqrt(C)).transpose(1, 2))              # [B, C, L]
-    x_mask = (torch.arange(L, device=ids.device).view(1, L) < lengths.view(-1, 1)).unsqueeze(1).to(x.dtype)
+    valid = torch.arange(L, device=ids.device).view(1, L) < lengths.view(-1, 1)
+    if ids.is_floating_point():
+        C = emb.shape[0]
+        feats = torch.where(valid.unsqueeze(-1), ids.to(emb.dtype), torch.zeros((), dtype=emb.dtype, device=ids.device))
+        x = keep("x0", (F.linear(feats, emb) * math.sqrt(C)).transpose(1, 2))
+    else:
+        C = emb.shape[1]
+        x = keep("x0", (emb[ids] * math.sqrt(C)).transpose(1, 2))              # [B, C, L]
+    x_mask = valid.unsqueeze(1).to(x.dtype)
     # prenet (ConvReluNorm)
     x_org, h = x, x
     for i in range(PRENET_LAYERS):

@@ -109,7 +109,14 @@ SIGNATURES = {
     "us_finetune_segment": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_void_p]),
     "us_tts_durations": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "us_tts_align": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p]),
+    "us_vc_align": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "us_encoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_encoder_config)]),
+    "us_encoder_create_contentvec": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_encoder_config), C.c_int32]),
+    "us_encoder_forward_features": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_encoder_forward_features_train": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t,
+                                                                      C.c_void_p]),
+    "us_encoder_backward_features": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.c_int,
+                                                                 C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_duration_predictor_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_duration_config)]),
     "us_encoder_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_encoder_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

@@ -54,13 +54,20 @@ struct GemmArgs {
   const float* dout;      // [rows][N]
   float* part;            // [S][K][Cin][N]
   int rows_per_split, splits;
+  // the Linear front of a ContentVec handle (kFront; K = 1, no bias): a row at or past its item's length is not read (it may
+  // hold anything, NaN included) and counts as zeros
+  const long long* lengths;   // [B], forward: which rows are read; the forward also writes mask_w[row] = row's frame < lengths[b]
+  float* mask_w;              // [rows]
+  float scale;                // forward: out = product * scale, rounded separately (encoder.py:295)
 };
 
 // Workgroup tile 64 x 64 of D, four waves of 32 x 32 (one 32x32x2 MFMA accumulator each), reduction slices of 16 staged in LDS
 // through registers (the next slice is loaded while the current one is multiplied).
 //   forward / dgrad:  D[row][n],  A(row, r = tap * Cin + ci) = in[row + tap - pad][ci],  B(r, n) = w[r][n]
 //   wgrad:            D[ci][co] of tap blockIdx.z / splits,  A(ci, row) = in[row + tap - pad][ci],  B(row, co) = dout[row][co]
-template <bool kWgrad>
+//   front (kFront): the forward form at K = 1 on in = feats, w = emb.weight packed [Cin][N]; its wgrad reads mask (the tape's) for
+//   the rows it may read
+template <bool kWgrad, bool kFront = false>
 __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
   __shared__ float As[2][kBK][kBM + 4];
   __shared__ float Bs[2][kBK][kBN + 4];
@@ -89,8 +96,12 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
           const int b = row / a.L, t = row - b * a.L, tt = t + tap - a.pad;
           if (tt >= 0 && tt < a.L) {
             const long long src = (long long)row + tap - a.pad;
-            v = a.in[src * a.Cin + ci];
-            if (a.mask_in) v *= a.mask[src];
+            if (kFront) {
+              if (a.mask[src] != 0.f) v = a.in[src * a.Cin + ci];
+            } else {
+              v = a.in[src * a.Cin + ci];
+              if (a.mask_in) v *= a.mask[src];
+            }
           }
         }
       } else {
@@ -101,8 +112,12 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
           const int b = row / a.L, t = row - b * a.L, tt = t + tp - a.pad;
           if (tt >= 0 && tt < a.L) {
             const long long src = (long long)row + tp - a.pad;
-            v = a.in[src * a.Cin + ci];
-            if (a.mask_in) v *= a.mask[src];
+            if (kFront) {
+              if (t < a.lengths[b]) v = a.in[src * a.Cin + ci];
+            } else {
+              v = a.in[src * a.Cin + ci];
+              if (a.mask_in) v *= a.mask[src];
+            }
           }
         }
       }
@@ -143,6 +158,10 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
     __syncthreads();
     cur ^= 1;
   }
+  if (kFront && !kWgrad && blockIdx.y == 0 && tid < kBM && m0 + tid < a.rows) {      // x_mask, by the first column of workgroups
+    const int row = m0 + tid, b = row / a.L;
+    a.mask_w[row] = (long long)(row - b * a.L) < a.lengths[b] ? 1.f : 0.f;
+  }
   const int n = n0 + wn + cl;
   if (n >= a.N) return;
 #pragma unroll
@@ -154,6 +173,10 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
     }
     if (m >= a.rows) continue;
     const long long o = (long long)m * a.N + n;
+    if (kFront) {      // product first, then the scale; a row past its length summed zeros
+      a.out[o] = mul_rn(acc[r], a.scale);
+      continue;
+    }
     float v = acc[r];
     if (a.bias) v += a.bias[n];
     if (a.relu) v = v > 0.f ? v : 0.f;
@@ -165,8 +188,8 @@ __global__ __launch_bounds__(256) void et_gemm_kernel(GemmArgs a) {
   }
 }
 
-// grad[co][ci][tap] (torch layout) = sum over splits, in order, of part[s][tap][ci][co]
-__global__ void et_wgrad_finish_kernel(const float* part, float* grad, int S, int K, int Cin, int Cout) {
+// grad[co][ci][tap] (torch layout) = scale * sum over splits, in order, of part[s][tap][ci][co]
+__global__ void et_wgrad_finish_kernel(const float* part, float* grad, int S, int K, int Cin, int Cout, float scale) {
   const long long n = (long long)Cout * Cin * K;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int k = (int)(i % K);
@@ -174,7 +197,7 @@ __global__ void et_wgrad_finish_kernel(const float* part, float* grad, int S, in
     const int ci = (int)(r % Cin), co = (int)(r / Cin);
     float s = 0.f;
     for (int sp = 0; sp < S; ++sp) s += part[(((long long)sp * K + k) * Cin + ci) * Cout + co];
-    grad[i] = s;
+    grad[i] = mul_rn(s, scale);
   }
 }
 
@@ -461,8 +484,10 @@ struct Layout {
   size_t total;
 };
 
-size_t conv_numel(const us_encoder_config& c) {      // largest convolution weight
+size_t conv_numel(const us_frontend* h) {      // largest convolution weight (the Linear front counts as one)
+  const us_encoder_config& c = h->ec;
   size_t m = (size_t)c.n_channels * c.n_channels * kPrenetKernel;
+  m = std::max(m, (size_t)c.n_channels * h->n_contentvec);
   m = std::max(m, (size_t)c.filter_channels * c.n_channels * c.kernel_size);
   m = std::max(m, (size_t)c.n_feats * c.n_channels);
   return m;
@@ -491,8 +516,8 @@ Layout et_layout(const us_frontend* h, int B, int L) {
   o.g = take(plane); o.t = take(plane); o.d1 = take(wide); o.dh = take(wide); o.dyx = take(plane); o.dyo = take(plane);
   o.dq = take(plane); o.dk = take(plane); o.dv = take(plane); o.ds = take(att);
   o.splits = wgrad_splits((long long)rows);
-  o.wd = take(conv_numel(c));
-  o.wpart = take((size_t)o.splits * conv_numel(c));
+  o.wd = take(conv_numel(h));
+  o.wpart = take((size_t)o.splits * conv_numel(h));
   o.cpart = take((size_t)kColChunks * std::max(std::max(C, F), (size_t)c.n_feats));
   const size_t nw = 2 * (size_t)c.window_size + 1, D = C / H;
   o.rpart = take(4 * (size_t)B * nw * D);      // doubles
@@ -578,8 +603,8 @@ Layout et_debug_layout(const us_frontend* h, int B, int L) {
   Layout o{};
   WsTake take;
   o.splits = wgrad_splits((long long)rows);
-  o.wd = take(conv_numel(c));
-  o.wpart = take((size_t)o.splits * conv_numel(c));
+  o.wd = take(conv_numel(h));
+  o.wpart = take((size_t)o.splits * conv_numel(h));
   o.cpart = take((size_t)kColChunks * std::max(std::max(C, F), (size_t)c.n_feats));
   o.dyx = take(rows * C);
   o.dyo = take(rows * C);
@@ -596,10 +621,45 @@ int et_lds_bound(us_frontend* h, const char* what, int L) {
   return US_OK;
 }
 
-int et_check(us_frontend* h, const char* what, int B, int L) {
+// features: the entry point is one of the *_features ones (the handle must be a ContentVec one, and the other way round)
+int et_check(us_frontend* h, const char* what, bool features, int B, int L) {
   int rc = fe_accept(h, kEncoder, what, B, L);
+  if (rc == US_OK) rc = fe_front(h, what, features);
   if (rc == US_OK) rc = h->all_loaded(what);
   return rc != US_OK ? rc : et_lds_bound(h, what, L);
+}
+
+// us_encoder_forward_train (ids; feats null) and us_encoder_forward_features_train (feats; ids null)
+int et_forward_train(us_frontend* h, const char* what, bool features, const int64_t* ids, const float* feats, const int64_t* lengths, float* mu_x,
+                     float* x_out, float* x_mask, int B, int L, float p_dropout, uint64_t seed, void* workspace, size_t workspace_bytes,
+                     us_stream stream) {
+  int rc = et_check(h, what, features, B, L);
+  if (rc != US_OK) return rc;
+  if ((features ? !feats : !ids) || !lengths || !mu_x || !x_out || !x_mask) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
+  if (!(p_dropout < 1.f)) return fe_fail(h, US_EINVAL, std::string(what) + ": p_dropout must be below 1");
+  const bool no_dropout = p_dropout < 0.f;         // the reference in eval mode (autograd still runs): no site drops
+  if (!workspace || workspace_bytes < us_encoder_train_workspace_bytes(h, B, L))
+    return fe_fail(h, US_EWORKSPACE, std::string(what) + ": workspace too small (us_encoder_train_workspace_bytes)");
+  const auto& c = h->ec;
+  const Layout l = et_layout(h, B, L);
+  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
+  x.mask = x.f(l.mask);
+  // the tape: one slot per entry and layer (Layout); conv_o / conv_2's output goes to backward scratch, free during the forward
+  EncoderBufs b{};
+  b.mask = x.mask; b.ids_tape = reinterpret_cast<long long*>(x.f(l.ids)); b.x0 = x.f(l.x0);
+  for (int i = 0; i < kPrenetLayers; ++i) { b.pc[i] = x.f(l.pc[i]); b.pa[i] = x.f(l.pa[i]); }
+  b.y = x.f(l.g); b.xf = x.f(l.xf); b.mu = x.f(l.mu);
+  for (int i = 0; i < c.n_layers; ++i)
+    b.layer.push_back({x.f(l.x[i]), x.f(l.q[i]), x.f(l.k[i]), x.f(l.v[i]), x.f(l.at[i]), x.f(l.n1[i]), x.f(l.x1[i]), x.f(l.hd[i]),
+                       x.f(l.n2[i]), x.f(l.p[i])});
+  EncoderMode m;
+  m.train = m.gemm = true; m.seed = seed; m.p = no_dropout ? 0.f : p_dropout; m.p_prenet = no_dropout ? 0.f : kPrenetP;
+  if ((rc = encoder_forward(h, x.s, b, m, ids, feats, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
+  hipError_t e = hipMemcpyAsync(x_mask, x.mask, (size_t)x.rows * sizeof(float), hipMemcpyDeviceToDevice, x.s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return h->hip(what, e);
+  h->tapes[workspace] = EncoderTape{B, L, p_dropout, seed};
+  return US_OK;
 }
 
 }  // namespace
@@ -621,7 +681,35 @@ void gemm_conv_wgrad(us_frontend* h, hipStream_t s, const std::string& key, cons
   g.rows_per_split = (int)(((rows + splits - 1) / splits + kBK - 1) / kBK * kBK);
   g.drop.site = -1;
   hipLaunchKernelGGL(et_gemm_kernel<true>, dim3((Cin + kBM - 1) / kBM, (Cout + kBN - 1) / kBN, K * splits), dim3(256), 0, s, g);
-  hipLaunchKernelGGL(et_wgrad_finish_kernel, dim3(et_blocks((long long)Cout * Cin * K, 256)), dim3(256), 0, s, part, dw, splits, K, Cin, Cout);
+  hipLaunchKernelGGL(et_wgrad_finish_kernel, dim3(et_blocks((long long)Cout * Cin * K, 256)), dim3(256), 0, s, part, dw, splits, K, Cin, Cout, 1.f);
+}
+
+// emb.weight's gradient of a ContentVec handle: dw [C][n_contentvec] = sqrt(C) * sum over valid rows of dx0[row][c] * feats[row][k],
+// the split wgrad GEMM at K = 1 (rows whose mask is 0 are not read)
+void gemm_front_wgrad(us_frontend* h, hipStream_t s, const float* feats, const float* mask, const float* dx0, long long rows, int L,
+                      float* part, float* dw) {
+  const int C = h->ec.n_channels, Cin = h->n_contentvec;
+  const int splits = wgrad_splits(rows);
+  GemmArgs g{};
+  g.in = feats; g.mask = mask;
+  g.rows = (int)rows; g.L = L; g.Cin = Cin; g.N = C; g.K = 1; g.pad = 0;
+  g.dout = dx0; g.part = part; g.splits = splits;
+  g.rows_per_split = (int)(((rows + splits - 1) / splits + kBK - 1) / kBK * kBK);
+  g.drop.site = -1;
+  hipLaunchKernelGGL((et_gemm_kernel<true, true>), dim3((Cin + kBM - 1) / kBM, (C + kBN - 1) / kBN, splits), dim3(256), 0, s, g);
+  hipLaunchKernelGGL(et_wgrad_finish_kernel, dim3(et_blocks((long long)C * Cin, 256)), dim3(256), 0, s, part, dw, splits, 1, Cin, C,
+                     sqrtf((float)C));
+}
+
+// x0 [rows][C] = (feats [rows][n_contentvec] . emb.weight^T) * sqrt(C) with zeros at rows past their item's length, and x_mask
+void gemm_front_fwd(us_frontend* h, hipStream_t s, const float* feats, const int64_t* lengths, float* x0, float* mask, long long rows, int L) {
+  const Weight& w = h->w["emb.weight"];
+  GemmArgs a{};
+  a.in = feats; a.lengths = reinterpret_cast<const long long*>(lengths); a.mask_w = mask;
+  a.rows = (int)rows; a.L = L; a.N = (int)w.shape[0]; a.Cin = (int)w.shape[1]; a.K = 1; a.pad = 0;
+  a.w = w.packed; a.out = x0; a.scale = sqrtf((float)a.N);
+  a.drop.site = -1;
+  hipLaunchKernelGGL((et_gemm_kernel<false, true>), dim3((rows + kBM - 1) / kBM, (a.N + kBN - 1) / kBN), dim3(256), 0, s, a);
 }
 
 // the forward form with the tap-flipped transposed weight
@@ -662,49 +750,35 @@ size_t us_encoder_train_workspace_bytes(us_frontend_handle h, int B, int L) {
 
 int us_encoder_forward_train(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x_out, float* x_mask,
                              int B, int L, float p_dropout, uint64_t seed, void* workspace, size_t workspace_bytes, us_stream stream) {
-  int rc = et_check(h, "us_encoder_forward_train", B, L);
-  if (rc != US_OK) return rc;
-  if (!ids || !lengths || !mu_x || !x_out || !x_mask) return fe_fail(h, US_EINVAL, "us_encoder_forward_train: null argument");
-  if (!(p_dropout < 1.f)) return fe_fail(h, US_EINVAL, "us_encoder_forward_train: p_dropout must be below 1");
-  const bool no_dropout = p_dropout < 0.f;         // the reference in eval mode (autograd still runs): no site drops
-  if (!workspace || workspace_bytes < us_encoder_train_workspace_bytes(h, B, L))
-    return fe_fail(h, US_EWORKSPACE, "us_encoder_forward_train: workspace too small (us_encoder_train_workspace_bytes)");
-  const auto& c = h->ec;
-  const Layout l = et_layout(h, B, L);
-  Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
-  x.mask = x.f(l.mask);
-  // the tape: one slot per entry and layer (Layout); conv_o / conv_2's output goes to backward scratch, free during the forward
-  EncoderBufs b{};
-  b.mask = x.mask; b.ids_tape = reinterpret_cast<long long*>(x.f(l.ids)); b.x0 = x.f(l.x0);
-  for (int i = 0; i < kPrenetLayers; ++i) { b.pc[i] = x.f(l.pc[i]); b.pa[i] = x.f(l.pa[i]); }
-  b.y = x.f(l.g); b.xf = x.f(l.xf); b.mu = x.f(l.mu);
-  for (int i = 0; i < c.n_layers; ++i)
-    b.layer.push_back({x.f(l.x[i]), x.f(l.q[i]), x.f(l.k[i]), x.f(l.v[i]), x.f(l.at[i]), x.f(l.n1[i]), x.f(l.x1[i]), x.f(l.hd[i]),
-                       x.f(l.n2[i]), x.f(l.p[i])});
-  EncoderMode m;
-  m.train = true; m.seed = seed; m.p = no_dropout ? 0.f : p_dropout; m.p_prenet = no_dropout ? 0.f : kPrenetP;
-  if ((rc = encoder_forward(h, x.s, b, m, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
-  hipError_t e = hipMemcpyAsync(x_mask, x.mask, (size_t)x.rows * sizeof(float), hipMemcpyDeviceToDevice, x.s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return h->hip("us_encoder_forward_train", e);
-  h->tapes[workspace] = EncoderTape{B, L, p_dropout, seed};
-  return US_OK;
+  return et_forward_train(h, "us_encoder_forward_train", false, ids, nullptr, lengths, mu_x, x_out, x_mask, B, L, p_dropout, seed, workspace,
+                          workspace_bytes, stream);
 }
 
-int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float* grad_x, int B, int L, const char* const* keys,
-                        float* const* grads, int n_grads, void* workspace, size_t workspace_bytes, us_stream stream) {
-  int rc = et_check(h, "us_encoder_backward", B, L);
+int us_encoder_forward_features_train(us_frontend_handle h, const float* feats, const int64_t* lengths, float* mu_x, float* x_out,
+                                      float* x_mask, int B, int L, float p_dropout, uint64_t seed, void* workspace, size_t workspace_bytes,
+                                      us_stream stream) {
+  return et_forward_train(h, "us_encoder_forward_features_train", true, nullptr, feats, lengths, mu_x, x_out, x_mask, B, L, p_dropout, seed,
+                          workspace, workspace_bytes, stream);
+}
+
+namespace {
+
+// us_encoder_backward (feats null: the ids are on the tape) and us_encoder_backward_features (the caller passes feats again)
+int et_backward(us_frontend* h, const char* what, const char* fwd, bool features, const float* feats, const float* grad_mu,
+                const float* grad_x, int B, int L, const char* const* keys, float* const* grads, int n_grads, void* workspace,
+                size_t workspace_bytes, us_stream stream) {
+  int rc = et_check(h, what, features, B, L);
   if (rc != US_OK) return rc;
+  if (features && !feats) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
   EncoderTape tape;
-  if ((rc = fe_tape(h, "us_encoder_backward", "us_encoder_forward_train", B, L, workspace, workspace_bytes,
-                    us_encoder_train_workspace_bytes(h, B, L), &tape)) != US_OK) return rc;
+  if ((rc = fe_tape(h, what, fwd, B, L, workspace, workspace_bytes, us_encoder_train_workspace_bytes(h, B, L), &tape)) != US_OK) return rc;
   const auto& c = h->ec;
   const Layout l = et_layout(h, B, L);
   Ctx x{h, static_cast<hipStream_t>(stream), ws_align(workspace), &l, B, L, (long long)B * L, nullptr};
   x.mask = x.f(l.mask);
   const int C = c.n_channels, nf = c.n_feats;
   std::map<std::string, float*> dst;
-  if ((rc = fe_grad_table(h, "us_encoder_backward", keys, grads, n_grads, x.f(l.arena), &dst)) != US_OK) return rc;
+  if ((rc = fe_grad_table(h, what, keys, grads, n_grads, x.f(l.arena), &dst)) != US_OK) return rc;
   auto G = [&](const std::string& k) { return dst.at(k); };
   const float p = tape.p_dropout < 0.f ? 0.f : tape.p_dropout, p_prenet = tape.p_dropout < 0.f ? 0.f : kPrenetP;
   const uint64_t seed = tape.seed;
@@ -759,8 +833,25 @@ int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float*
     if (i > 0) conv_bwd(x, cp, x.f(l.pa[i - 1]), true, d1, t, nullptr, nullptr, 1.f, true, G(cp + ".weight"), G(cp + ".bias"));
     else conv_bwd(x, cp, x.f(l.x0), true, d1, g, g, nullptr, 1.f, true, G(cp + ".weight"), G(cp + ".bias"));
   }
-  embed_grad(x.s, reinterpret_cast<const long long*>(x.f(l.ids)), g, G("emb.weight"), x.rows, c.n_vocab, C);
-  return fe_launched(h, "us_encoder_backward");
+  // g: the (masked) gradient of x0
+  if (features) gemm_front_wgrad(h, x.s, feats, x.mask, g, x.rows, L, x.f(l.wpart), G("emb.weight"));
+  else embed_grad(x.s, reinterpret_cast<const long long*>(x.f(l.ids)), g, G("emb.weight"), x.rows, c.n_vocab, C);
+  return fe_launched(h, what);
+}
+
+}  // namespace
+
+int us_encoder_backward(us_frontend_handle h, const float* grad_mu, const float* grad_x, int B, int L, const char* const* keys,
+                        float* const* grads, int n_grads, void* workspace, size_t workspace_bytes, us_stream stream) {
+  return et_backward(h, "us_encoder_backward", "us_encoder_forward_train", false, nullptr, grad_mu, grad_x, B, L, keys, grads, n_grads,
+                     workspace, workspace_bytes, stream);
+}
+
+int us_encoder_backward_features(us_frontend_handle h, const float* feats, const float* grad_mu, const float* grad_x, int B, int L,
+                                 const char* const* keys, float* const* grads, int n_grads, void* workspace, size_t workspace_bytes,
+                                 us_stream stream) {
+  return et_backward(h, "us_encoder_backward_features", "us_encoder_forward_features_train", true, feats, grad_mu, grad_x, B, L, keys,
+                     grads, n_grads, workspace, workspace_bytes, stream);
 }
 
 int us_encoder_tape_release(us_frontend_handle h, const void* workspace) {
@@ -886,6 +977,7 @@ int us_encoder_debug_embed_grad(us_frontend_handle h, const int64_t* ids, const 
   int rc = fe_accept(h, kEncoder, what);
   if (rc != US_OK) return rc;
   if (!ids || !dx0 || !grad) return fe_fail(h, US_EINVAL, std::string(what) + ": null argument");
+  if ((rc = fe_front(h, what, false)) != US_OK) return rc;
   if ((rc = et_debug_check(h, what, B, L, nullptr, 0, nullptr)) != US_OK) return rc;
   embed_grad(static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(ids), dx0, grad, (long long)B * L, h->ec.n_vocab, h->ec.n_channels);
   return fe_launched(h, what);

@@ -28,6 +28,7 @@ enum { kEncoder = 0, kDuration = 1 };      // us_frontend::kind
 struct us_frontend : us::WeightTable {
   int kind = us::kEncoder;
   us_encoder_config ec{};
+  int n_contentvec = 0;                           // > 0: a ContentVec handle, emb is Linear(n_contentvec -> n_channels, bias=False)
   us_duration_config dc{};
   std::map<const void*, us::EncoderTape> tapes;   // training forwards whose tape a workspace holds (us_encoder_tape_release)
 };
@@ -100,9 +101,9 @@ struct AttnArgs {
 // The buffers encoder_forward walks, channel-last [B][L][C] unless noted.  Inference points them into seven planes that it
 // reuses (entries alias, LayerNorm runs in place); training gives every entry its own slot of the tape.
 struct EncoderBufs {
-  float* mask;                 // [B][L], written by the embedding kernel
-  long long* ids_tape;         // training: the ids, kept for the embedding gradient
-  float* x0;                   // emb(ids) * sqrt(C)
+  float* mask;                 // [B][L], written by the embedding kernel (the front GEMM of a ContentVec handle)
+  long long* ids_tape;         // training: the ids, kept for the embedding gradient (a ContentVec handle keeps nothing)
+  float* x0;                   // emb(ids) * sqrt(C) / emb(feats) * sqrt(C)
   float* pc[kPrenetLayers];    // prenet conv_i output
   float* pa[kPrenetLayers];    // prenet relu_drop(LayerNorm(pc[i]))
   float* y;                    // conv_o / conv_2 output, dead after the LayerNorm that adds it
@@ -119,10 +120,11 @@ struct EncoderBufs {
   };
   std::vector<Layer> layer;    // n_layers entries
 };
-// inference: eval mode, fe_conv1d_kernel.  training: the reference's Dropout sites at p / p_prenet (0: nothing is drawn), the
-// training entries of EncoderBufs stored, convolutions on the MFMA GEMM of encoder_train.hip
+// train: the reference's Dropout sites at p / p_prenet (0: nothing is drawn) and the training entries of EncoderBufs stored; else
+// eval mode.  gemm: the convolutions run on the MFMA GEMM of encoder_train.hip, else on fe_conv1d_kernel.  The entry point sets
+// it and B or L never do: training does; inference does not, for either kind of handle (frontend.hip, encoder_forward)
 struct EncoderMode {
-  bool train = false;
+  bool train = false, gemm = false;
   uint64_t seed = 0;
   float p = 0.f, p_prenet = 0.f;
 };
@@ -148,8 +150,16 @@ int fe_tape_release(us_frontend* h, int kind, const char* what, const void* work
 // out[i] = the factor element i of site d.site is multiplied by, in the reference's layout (the *_dropout_mask test hooks)
 int fe_keep_mask(us_frontend* h, const char* what, hipStream_t s, float* out, long long n, Drop d);
 // frontend.hip: embedding -> prenet -> transformer blocks -> proj_m -> mu_x, x_out in the reference's [B][C][L]
-int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const int64_t* lengths,
-                    float* mu_x, float* x_out, int B, int L);
+// (ids for an id handle, feats [B][L][n_contentvec] for a ContentVec handle; the other is null)
+int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const float* feats,
+                    const int64_t* lengths, float* mu_x, float* x_out, int B, int L);
+// the handle's front is the one the entry point `what` is for (features: one of the *_features entry points)
+int fe_front(us_frontend* h, const char* what, bool features);
+// encoder_train.hip: the Linear front as a K = 1 GEMM: x0 = (feats . emb.weight^T) * sqrt(C) and x_mask; rows past an item's
+// length are not read and give zeros.  gemm_front_wgrad: emb.weight's gradient [C][n_contentvec] from dx0 over the rows mask keeps
+void gemm_front_fwd(us_frontend* h, hipStream_t s, const float* feats, const int64_t* lengths, float* x0, float* mask, long long rows, int L);
+void gemm_front_wgrad(us_frontend* h, hipStream_t s, const float* feats, const float* mask, const float* dx0, long long rows, int L,
+                      float* part, float* dw);
 // encoder_train.hip: the convolution `key` as an implicit GEMM on the fp32 matrix cores (training forward)
 void gemm_conv_fwd(us_frontend* h, hipStream_t s, const std::string& key, const float* in, float* out, const float* mask, const float* add,
                    long long rows, int L, bool mask_in, bool relu, bool mask_out, Drop drop);

@@ -326,7 +326,8 @@ void add_norm(us_frontend* h, const std::string& p, int c) {
 void encoder_keys(us_frontend* h) {
   const auto& c = h->ec;
   const int C = c.n_channels, D = C / c.n_heads;
-  h->add("emb.weight", {c.n_vocab, C});
+  if (h->n_contentvec > 0) h->add("emb.weight", {C, h->n_contentvec});      // Linear layout [out][in], encoder.py:280
+  else h->add("emb.weight", {c.n_vocab, C});
   for (int i = 0; i < kPrenetLayers; ++i) add_conv(h, "prenet.conv_layers." + std::to_string(i), C, C, kPrenetKernel);
   for (int i = 0; i < kPrenetLayers; ++i) add_norm(h, "prenet.norm_layers." + std::to_string(i), C);
   add_conv(h, "prenet.proj", C, C, 1);
@@ -410,6 +411,12 @@ int fe_accept(us_frontend* h, int kind, const char* what, int B, int L) {
   return US_OK;
 }
 
+int fe_front(us_frontend* h, const char* what, bool features) {
+  if ((h->n_contentvec > 0) == features) return US_OK;
+  return h->fail(US_EINVAL, std::string(what) + (features ? ": not a ContentVec handle (us_encoder_create_contentvec)"
+                                                            : ": a ContentVec handle takes features (the us_encoder_*_features entry points)"));
+}
+
 int fe_grad_table(us_frontend* h, const char* what, const char* const* keys, float* const* grads, int n_grads, float* arena,
                   std::map<std::string, float*>* dst) {
   if (n_grads < 0 || (n_grads > 0 && (!keys || !grads))) return h->fail(US_EINVAL, std::string(what) + ": bad gradient list");
@@ -446,18 +453,21 @@ int fe_keep_mask(us_frontend* h, const char* what, hipStream_t s, float* out, lo
   return fe_launched(h, what);
 }
 
-// The Encoder's forward, once for both modes.  The two convolutions stay two: inference runs L of 100-300 and is latency-bound,
-// which the fixed-order fp32 FMA kernel above serves best; training runs B * L of several thousand rows on the MFMA GEMM that
-// its dgrad / wgrad share (they differ in summation order only).  The mode of the call picks, nothing else does.
-int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const int64_t* lengths,
-                    float* mu_x, float* x_out, int B, int L) {
+// The Encoder's forward, once for both modes and both fronts.  The two convolutions stay two: inference is latency-bound, which
+// the fixed-order fp32 FMA kernel above serves best; training runs B * L of several thousand rows on the MFMA GEMM that its
+// dgrad / wgrad share (they differ in summation order only).  m.gemm picks, and the entry point sets it, never B or L.  The
+// inference of a ContentVec handle runs L of 500-1500 (50 frames per second of source audio) and was measured on both: the whole
+// encoder at B = 1, L = 499 takes 1.19 ms on the FMA kernel and 3.30 ms on the GEMM (24 workgroups of 64 x 64 on 256 CUs), at
+// B = 8 3.9 against 4.9 ms, at L = 1499 2.95 against 4.74 ms, so it keeps the FMA kernel as the id handle does.
+int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const EncoderMode& m, const int64_t* ids, const float* feats,
+                    const int64_t* lengths, float* mu_x, float* x_out, int B, int L) {
   const auto& c = h->ec;
   const int C = c.n_channels, D = C / c.n_heads;
   const long long rows = (long long)B * L;
   int rc;
   auto conv = [&](const std::string& key, const float* in, float* out, const float* add, bool mask_in, bool relu, bool mask_out,
                   Drop drop = no_drop()) {
-    if (!m.train) return conv1d(h, s, key, in, out, b.mask, add, B, L, mask_in, relu, mask_out);
+    if (!m.gemm) return conv1d(h, s, key, in, out, b.mask, add, B, L, mask_in, relu, mask_out);
     gemm_conv_fwd(h, s, key, in, out, b.mask, add, rows, L, mask_in, relu, mask_out, drop);
     return (int)US_OK;
   };
@@ -466,9 +476,12 @@ int encoder_forward(us_frontend* h, hipStream_t s, const EncoderBufs& b, const E
     const LnTrain t{add_drop, out_drop, sum_out, L};
     return layernorm(h, s, key, in, add, out, mask, rows, C, 1e-4f, relu, m.train ? &t : nullptr);
   };
-  hipLaunchKernelGGL(m.train ? fe_embed_kernel<true> : fe_embed_kernel<false>, dim3((unsigned)rows), dim3(C >= 256 ? 256 : 64), 0, s,
-                     reinterpret_cast<const long long*>(ids), reinterpret_cast<const long long*>(lengths), h->w["emb.weight"].dev, b.x0,
-                     b.ids_tape, b.mask, c.n_vocab, C, L, sqrtf((float)C));
+  if (feats)
+    gemm_front_fwd(h, s, feats, lengths, b.x0, b.mask, rows, L);
+  else
+    hipLaunchKernelGGL(m.train ? fe_embed_kernel<true> : fe_embed_kernel<false>, dim3((unsigned)rows), dim3(C >= 256 ? 256 : 64), 0, s,
+                       reinterpret_cast<const long long*>(ids), reinterpret_cast<const long long*>(lengths), h->w["emb.weight"].dev, b.x0,
+                       b.ids_tape, b.mask, c.n_vocab, C, L, sqrtf((float)C));
   // prenet (ConvReluNorm.forward, encoder.py:58-65): c_i = conv(a_{i-1} * mask), a_i = drop(relu(LN(c_i))); (x0 + proj(a_2)) * mask
   const float* cur = b.x0;
   for (int i = 0; i < kPrenetLayers; ++i) {
@@ -514,20 +527,34 @@ extern "C" {
 
 using namespace us;
 
-int us_encoder_create(us_frontend_handle* out, const us_encoder_config* cfg) {
+namespace {
+
+// us_encoder_create (n_contentvec == 0) and us_encoder_create_contentvec
+int encoder_create(us_frontend_handle* out, const us_encoder_config* cfg, int n_contentvec) {
   if (!out || !cfg) return fe_fail(nullptr, US_EINVAL, "us_encoder_create: null argument");
-  const auto& c = *cfg;
+  us_encoder_config c = *cfg;
+  if (n_contentvec > 0) c.n_vocab = 1;      // ignored: there is no table
   if (c.n_vocab <= 0 || c.n_feats <= 0 || c.n_channels <= 0 || c.filter_channels <= 0 || c.n_heads <= 0 || c.n_layers < 0 ||
       c.kernel_size <= 0 || c.kernel_size % 2 == 0 || c.window_size < 0 || c.n_channels % c.n_heads != 0)
     return fe_fail(nullptr, US_EINVAL, "us_encoder_create: bad configuration (odd kernel_size, n_channels divisible by n_heads)");
   if (c.n_channels > 1024 || c.filter_channels > 1024)
     return fe_fail(nullptr, US_EINVAL, "us_encoder_create: more than 1024 channels");
   auto* h = new us_frontend();
-  h->kind = kEncoder; h->ec = c;
+  h->kind = kEncoder; h->ec = c; h->n_contentvec = n_contentvec;
   (void)hipGetDevice(&h->device);
   encoder_keys(h);
   *out = h;
   return US_OK;
+}
+
+}  // namespace
+
+int us_encoder_create(us_frontend_handle* out, const us_encoder_config* cfg) { return encoder_create(out, cfg, 0); }
+
+int us_encoder_create_contentvec(us_frontend_handle* out, const us_encoder_config* cfg, int32_t n_contentvec) {
+  if (n_contentvec < 1 || n_contentvec > 1024)
+    return fe_fail(nullptr, US_EINVAL, "us_encoder_create_contentvec: n_contentvec must be in 1..1024");
+  return encoder_create(out, cfg, n_contentvec);
 }
 
 int us_duration_predictor_create(us_frontend_handle* out, const us_duration_config* cfg) {
@@ -561,12 +588,13 @@ int us_frontend_load_weight(us_frontend_handle h, const char* key, const float* 
   const int rc = WeightTable::load(h, "us_frontend_load_weight", key, data, shape, ndim, s, &wp);
   if (rc != US_OK) return rc;
   Weight& w = *wp;
-  if (ndim == 3) {       // Conv1d weight
+  const bool front = h->kind == kEncoder && h->n_contentvec > 0 && ndim == 2;      // emb.weight [C][n_contentvec]: a K = 1 convolution
+  if (ndim == 3 || front) {       // Conv1d weight
     const size_t n = w.numel();
     hipError_t e;
     if (!w.packed && (e = hipMalloc(&w.packed, n * sizeof(float))) != hipSuccess) return h->hip("hipMalloc(packed weight)", e);
     hipLaunchKernelGGL(fe_pack_conv_kernel, dim3((unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, w.dev, w.packed,
-                       (int)shape[0], (int)shape[1], (int)shape[2]);
+                       (int)shape[0], (int)shape[1], front ? 1 : (int)shape[2]);
     if ((e = hipGetLastError()) != hipSuccess) return h->hip("fe_pack_conv_kernel", e);
   }
   w.loaded = true;
@@ -578,19 +606,24 @@ size_t us_frontend_workspace_bytes(us_frontend_handle h, int B, int L) {
   return fe_scratch_floats(h, (long long)B * L) * sizeof(float) + 256;
 }
 
-int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x_out, float* x_mask, int B,
-                       int L, void* workspace, size_t workspace_bytes, us_stream stream) {
-  int rc = fe_accept(h, kEncoder, "us_encoder_forward");
+namespace {
+
+// us_encoder_forward (ids; feats null) and us_encoder_forward_features (feats; ids null)
+int encoder_infer(us_frontend* h, const std::string& what, bool features, const int64_t* ids, const float* feats, const int64_t* lengths, float* mu_x,
+                  float* x_out, float* x_mask, int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
+  int rc = fe_accept(h, kEncoder, what.c_str());
   if (rc != US_OK) return rc;
-  if (!ids || !lengths || !mu_x || !x_out || !x_mask || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, "us_encoder_forward: bad argument");
-  if (B > 65535) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than 65535 items");
-  if ((rc = h->all_loaded("us_encoder_forward")) != US_OK) return rc;
+  if ((rc = fe_front(h, what.c_str(), features)) != US_OK) return rc;
+  if ((features ? !feats : !ids) || !lengths || !mu_x || !x_out || !x_mask || B <= 0 || L <= 0) return fe_fail(h, US_EINVAL, what + ": bad argument");
+  if (B > 65535) return fe_fail(h, US_EINVAL, what + ": more than 65535 items");
+  if (features && (long long)B * L > 0x7fffffffLL / 1024) return fe_fail(h, US_EINVAL, what + ": B * L too large");
+  if ((rc = h->all_loaded(what.c_str())) != US_OK) return rc;
   const auto& c = h->ec;
   const int C = c.n_channels, D = C / c.n_heads;
-  if (((size_t)L + D + 128) * sizeof(float) > 64 * 1024) return fe_fail(h, US_EINVAL, "us_encoder_forward: more than ~16000 symbols per utterance");
+  if (((size_t)L + D + 128) * sizeof(float) > 64 * 1024) return fe_fail(h, US_EINVAL, what + ": more than ~16000 symbols per utterance");
   const long long rows = (long long)B * L;
   if (!workspace || workspace_bytes < us_frontend_workspace_bytes(h, B, L))
-    return fe_fail(h, US_EWORKSPACE, "us_encoder_forward: workspace too small (us_frontend_workspace_bytes)");
+    return fe_fail(h, US_EWORKSPACE, what + ": workspace too small (us_frontend_workspace_bytes)");
   // seven planes (fe_scratch_floats): x_org, then conv_o / conv_2's output once the prenet is done; the running x (both LayerNorms
   // of a block write it in place); q, k (the prenet ping-pongs in them, proj_m's output lands in q); v; the attention output; h1
   float* p0 = ws_align(workspace);
@@ -605,8 +638,23 @@ int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* 
   b.x0 = p0; b.y = p0; b.xf = xr; b.mu = q;
   for (int i = 0; i < kPrenetLayers; ++i) b.pc[i] = b.pa[i] = (i & 1) ? k : q;
   b.layer.assign(c.n_layers, EncoderBufs::Layer{xr, q, k, v, at, nullptr, xr, h1, nullptr, nullptr});
-  if ((rc = encoder_forward(h, static_cast<hipStream_t>(stream), b, EncoderMode{}, ids, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
-  return fe_launched(h, "us_encoder_forward");
+  EncoderMode m;
+  m.gemm = false;      // either kind of handle: measured, see encoder_forward
+  if ((rc = encoder_forward(h, static_cast<hipStream_t>(stream), b, m, ids, feats, lengths, mu_x, x_out, B, L)) != US_OK) return rc;
+  return fe_launched(h, what.c_str());
+}
+
+}  // namespace
+
+int us_encoder_forward(us_frontend_handle h, const int64_t* ids, const int64_t* lengths, float* mu_x, float* x_out, float* x_mask, int B,
+                       int L, void* workspace, size_t workspace_bytes, us_stream stream) {
+  return encoder_infer(h, "us_encoder_forward", false, ids, nullptr, lengths, mu_x, x_out, x_mask, B, L, workspace, workspace_bytes, stream);
+}
+
+int us_encoder_forward_features(us_frontend_handle h, const float* feats, const int64_t* lengths, float* mu_x, float* x_out, float* x_mask,
+                                int B, int L, void* workspace, size_t workspace_bytes, us_stream stream) {
+  return encoder_infer(h, "us_encoder_forward_features", true, nullptr, feats, lengths, mu_x, x_out, x_mask, B, L, workspace, workspace_bytes,
+                       stream);
 }
 
 int us_duration_predictor_forward(us_frontend_handle h, const float* x, const float* x_mask, const float* g, float* logw, int B, int L,

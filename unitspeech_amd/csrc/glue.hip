@@ -226,6 +226,36 @@ __global__ __launch_bounds__(256) void tts_align_kernel(const float* __restrict_
     for (int l = 0; l < L; ++l) attn[((long long)b * L + l) * Tp + t] = (l == sym) ? 1.f : 0.f;
 }
 
+// Voice conversion's mel-rate alignment (scripts/voice_conversion.py:22-33): F.interpolate(mode='linear', align_corners=False) of
+// item b from its own x_lengths[b] frames to its own y_lengths[b] frames, zeros on [y_lengths[b], Tp), y_mask[b][t] = t < y_lengths[b].
+// The source coordinate max((t + 0.5) Lx / Ly - 0.5, 0) = num / (2 Ly) with num = max((2t + 1) Lx - Ly, 0) is split exactly in
+// integers: i0 = num / (2 Ly), lambda = (num mod 2 Ly) / (2 Ly); so the result does not depend on how fp32 would round the coordinate,
+// nor on the padded L or on the other items.  Lengths are the caller's to validate; they are clamped here so that no read leaves cond_x.
+__global__ __launch_bounds__(256) void vc_align_kernel(const float* __restrict__ cond_x, const long long* __restrict__ x_lengths,
+                                                       const long long* __restrict__ y_lengths, float* __restrict__ cond_y,
+                                                       float* __restrict__ y_mask, int F, int L, int Tp) {
+  const int b = blockIdx.y;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= Tp) return;
+  const long long Lx = min(max(x_lengths[b], 1LL), (long long)L), Ly = min(max(y_lengths[b], 1LL), (long long)Tp);
+  const bool live = t < Ly;
+  if (y_mask) y_mask[(long long)b * Tp + t] = live ? 1.f : 0.f;
+  int i0 = 0, i1 = 0;
+  float lam = 0.f;
+  if (live) {
+    const long long num = max((2LL * t + 1) * Lx - Ly, 0LL), den = 2 * Ly;
+    const long long q = min(num / den, Lx - 1);
+    i0 = (int)q;
+    i1 = i0 + (q < Lx - 1 ? 1 : 0);
+    lam = (float)(num - q * den) / (float)den;
+  }
+  const float w0 = 1.f - lam;
+  for (int f = 0; f < F; ++f) {
+    const float* x = cond_x + ((long long)b * F + f) * L;
+    cond_y[((long long)b * F + f) * Tp + t] = live ? add_rn(mul_rn(w0, x[i0]), mul_rn(lam, x[i1])) : 0.f;
+  }
+}
+
 // `fine_tune` crop (:458-486): y_cut[b][:, j] = y[b][:, start_b + j], cond_y[b][:, j] = (sum_l attn[b][l][start_b + j] *
 // cond_x[b][:, l]) * mask, mask[b][j] = j < n_b, for j < segment; zeros beyond n_b.  attn is the caller's dense [B][Lu][Ly] matrix.
 __global__ __launch_bounds__(256) void finetune_segment_kernel(const float* __restrict__ cond_x, const float* __restrict__ y,
@@ -485,6 +515,16 @@ int us_tts_align(const float* cond_x, const float* w_ceil, const float* x_mask, 
                      cond_x, w_ceil, x_mask, reinterpret_cast<const long long*>(y_lengths), cond_y, attn, y_mask, F, L, Tp);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : fail("us_tts_align", e);
+}
+
+int us_vc_align(const float* cond_x, const int64_t* x_lengths, const int64_t* y_lengths, float* cond_y, float* y_mask, int B, int F, int L,
+                int Tp, us_stream stream) {
+  if (!cond_x || !x_lengths || !y_lengths || !cond_y || !y_mask || B <= 0 || B > 65535 || F <= 0 || L <= 0 || Tp <= 0)
+    return bad("us_vc_align: bad argument");
+  hipLaunchKernelGGL(vc_align_kernel, dim3((Tp + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), cond_x,
+                     reinterpret_cast<const long long*>(x_lengths), reinterpret_cast<const long long*>(y_lengths), cond_y, y_mask, F, L, Tp);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : fail("us_vc_align", e);
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@ class EncoderConfig:
     n_layers: int = 6
     kernel_size: int = 3
     window_size: Optional[int] = 4
+    n_contentvec: int = 0          # > 0: emb is Linear(n_contentvec -> n_channels, bias=False) (checkpoints/voice-conversion.json: 768)
 
 
 @dataclass(frozen=True)
@@ -57,7 +58,7 @@ def encoder_state_shapes(cfg: EncoderConfig) -> "OrderedDict[str, Tuple[int, ...
     """state_dict keys and shapes in the reference module's registration order (unitspeech/encoder.py:270-291)."""
     c, d = cfg.n_channels, cfg.n_channels // cfg.n_heads
     sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-    sh["emb.weight"] = (cfg.n_vocab, c)
+    sh["emb.weight"] = (c, cfg.n_contentvec) if cfg.n_contentvec else (cfg.n_vocab, c)      # Linear [out, in] / Embedding
     for i in range(PRENET_LAYERS):
         sh[f"prenet.conv_layers.{i}.weight"] = (c, c, PRENET_KERNEL)
         sh[f"prenet.conv_layers.{i}.bias"] = (c,)
@@ -98,7 +99,7 @@ def duration_predictor_state_shapes(cfg: DurationPredictorConfig) -> "OrderedDic
                         ("proj.weight", (1, f, 1)), ("proj.bias", (1,))])
 
 
-def _synthetic(shapes, seed: int, tag: str) -> Dict[str, np.ndarray]:
+def _synthetic(shapes, seed: int, tag: str, linear_front: bool = False) -> Dict[str, np.ndarray]:
     """Seeded weights from (seed, tensor name) with NumPy's Philox stream, like params.synthetic_state_dict: every tensor is
     non-trivial (the reference initialises `prenet.proj` to zero, which would hide the whole prenet from a parity test)."""
     out = OrderedDict()
@@ -111,7 +112,7 @@ def _synthetic(shapes, seed: int, tag: str) -> Dict[str, np.ndarray]:
         elif name.endswith(("beta", "bias")):
             v = 0.1 * z
         elif name == "emb.weight":
-            v = z * shape[1] ** -0.5                       # encoder.py:284
+            v = z * (shape[0] if linear_front else shape[1]) ** -0.5      # n_channels ** -0.5 for either front, encoder.py:283
         elif "emb_rel" in name:
             v = z * shape[2] ** -0.5                       # :88-92
         else:                                             # Conv1d [out, in, k]
@@ -121,7 +122,7 @@ def _synthetic(shapes, seed: int, tag: str) -> Dict[str, np.ndarray]:
 
 
 def synthetic_encoder_state_dict(cfg: EncoderConfig, seed: int = 0) -> Dict[str, np.ndarray]:
-    return _synthetic(encoder_state_shapes(cfg), seed, "encoder")
+    return _synthetic(encoder_state_shapes(cfg), seed, "encoder", bool(cfg.n_contentvec))
 
 
 def synthetic_duration_predictor_state_dict(cfg: DurationPredictorConfig, seed: int = 0) -> Dict[str, np.ndarray]:
@@ -210,8 +211,8 @@ class Encoder(_FrontEndModule):
         super().__init__()
         self.trainable = bool(trainable)
         if n_contentvec:
-            raise NotImplementedError("Encoder(n_contentvec > 0) (a Linear front instead of the Embedding, encoder.py:281) is not built: "
-                                      "no configuration of the reference uses it")
+            raise NotImplementedError("Encoder(n_contentvec > 0) (a Linear front instead of the Embedding, encoder.py:281) is a class of "
+                                      "its own here: use ContentVecEncoder")
         self.cfg = EncoderConfig(int(n_vocab), int(n_feats), int(n_channels), int(filter_channels), int(n_heads), int(n_layers),
                                  int(kernel_size), int(window_size) if window_size else None)
         self.p_dropout = p_dropout
@@ -354,6 +355,70 @@ class Encoder(_FrontEndModule):
         return grad
 
 
+class _LinearParams(torch.nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(cout, cin).normal_(0, cout ** -0.5))      # encoder.py:280,283
+
+
+class ContentVecEncoder(_FrontEndModule):
+    """`unitspeech/encoder.py:253` `Encoder(..., n_contentvec=768, ...)`: the Encoder whose front is `Linear(n_contentvec ->
+    n_channels, bias=False)` (:279-280), as `scripts/voice_conversion.py` builds it from checkpoints/voice-conversion.json.  Same
+    argument list and `state_dict` as the reference (`contentvec_encoder.pt`'s ["model"] loads strictly); `n_vocab` is accepted and
+    unused.  `forward(feats [B, L, n_contentvec], lengths [B]) -> (mu_x, x, x_mask)`.  Rows of `feats` at or past an item's length
+    are never read.  `trainable=True`: as `Encoder`, differentiable with respect to every parameter (not to `feats`)."""
+    _train_abi = "encoder"
+    _train_forward, _train_backward = "us_encoder_forward_features_train", "us_encoder_backward_features"
+
+    def __init__(self, n_vocab, n_feats, n_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout=0.0, n_contentvec=768,
+                 window_size=None, *, trainable=False):
+        super().__init__()
+        self.trainable = bool(trainable)
+        if not 1 <= int(n_contentvec) <= 1024:
+            raise ValueError(f"ContentVecEncoder: n_contentvec must be in 1..1024, got {n_contentvec}")
+        self.cfg = EncoderConfig(int(n_vocab), int(n_feats), int(n_channels), int(filter_channels), int(n_heads), int(n_layers),
+                                 int(kernel_size), int(window_size) if window_size else None, int(n_contentvec))
+        self.p_dropout = p_dropout
+        self.emb = _LinearParams(n_contentvec, n_channels)
+        self.prenet = _Prenet(n_channels)
+        self.encoder = _Transformer(n_channels, filter_channels, n_heads, n_layers, kernel_size, window_size)
+        self.proj_m = _Conv1dParams(n_channels, n_feats, 1)
+
+    def _create(self, lib, device):
+        c = _lib.us_encoder_config(1, self.cfg.n_feats, self.cfg.n_channels, self.cfg.filter_channels, self.cfg.n_heads, self.cfg.n_layers,
+                                   self.cfg.kernel_size, self.cfg.window_size or 0)
+        _lib.check(lib.us_encoder_create_contentvec(C.byref(self._h), C.byref(c), self.cfg.n_contentvec), None,
+                   "us_encoder_create_contentvec")
+
+    def forward(self, feats, lengths):
+        """feats [B, L, n_contentvec], lengths [B] -> (mu_x [B, n_feats, L], x [B, n_channels, L], x_mask [B, 1, L])."""
+        if feats.dim() != 3 or feats.shape[2] != self.cfg.n_contentvec or lengths.dim() != 1 or lengths.shape[0] != feats.shape[0]:
+            raise ValueError(f"ContentVecEncoder: expected features [B, L, {self.cfg.n_contentvec}] and lengths [B], got "
+                             f"{tuple(feats.shape)} and {tuple(lengths.shape)}")
+        if self.training and self.trainable:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            params = list(self.state_dict(keep_vars=True).values())
+            return _ContentVecEncoderTrain.apply(self, feats, lengths, seed, float(self.p_dropout), *params)
+        return self._forward_eval(feats, lengths)
+
+    def _operands(self, feats, lengths):
+        (b, l, _), dev = feats.shape, feats.device
+        ins = [_f32(feats, dev), lengths.to(device=dev, dtype=torch.int64).contiguous()]
+        return ins, (torch.empty(b, self.cfg.n_feats, l, device=dev), torch.empty(b, self.cfg.n_channels, l, device=dev),
+                     torch.empty(b, 1, l, device=dev))
+
+    @torch.no_grad()
+    def _forward_eval(self, feats, lengths):
+        lib, stream = self._sync(feats.device)
+        ins, outs = self._operands(feats, lengths)
+        b, l = feats.shape[:2]
+        ws = self._workspace(lib, feats.device, b, l)
+        with torch.cuda.device(feats.device):
+            rc = lib.us_encoder_forward_features(self._h, *_ptrs(ins + list(outs)), b, l, ws.data_ptr(), ws.numel(), stream)
+        self._check(lib, rc, "us_encoder_forward_features")
+        return outs
+
+
 def _ptrs(tensors):
     return [None if t is None else t.data_ptr() for t in tensors]
 
@@ -380,8 +445,9 @@ def _tape_forward(ctx, mod, operands, b, l, p, seed, params):
     abi = mod._train_abi
     ws = torch.empty(int(getattr(lib, f"us_{abi}_train_workspace_bytes")(mod._h, b, l)), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        rc = getattr(lib, f"us_{abi}_forward_train")(mod._h, *_ptrs(operands), b, l, p, seed, ws.data_ptr(), ws.numel(), stream)
-    mod._check(lib, rc, f"us_{abi}_forward_train")
+        name = getattr(mod, "_train_forward", f"us_{abi}_forward_train")
+        rc = getattr(lib, name)(mod._h, *_ptrs(operands), b, l, p, seed, ws.data_ptr(), ws.numel(), stream)
+    mod._check(lib, rc, name)
     ctx.mod, ctx.ws, ctx.shape = mod, ws, (b, l)
     ctx.versions = [(t.data_ptr(), t._version) for t in params]
     # the handle forgets this tape when the workspace tensor goes (its memory may then hold anything)
@@ -404,9 +470,9 @@ def _tape_backward(ctx, upstream, n_inputs):
     ptrs = (C.c_void_p * max(len(sel), 1))(*[g.data_ptr() for _, g in sel])
     upstream = [_f32(t, device) for t in upstream]
     with torch.cuda.device(device):
-        rc = getattr(lib, f"us_{mod._train_abi}_backward")(mod._h, *_ptrs(upstream), b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(),
-                                                          stream)
-    mod._check(lib, rc, f"us_{mod._train_abi}_backward")
+        name = getattr(mod, "_train_backward", f"us_{mod._train_abi}_backward")
+        rc = getattr(lib, name)(mod._h, *_ptrs(upstream), b, l, keys, ptrs, len(sel), ws.data_ptr(), ws.numel(), stream)
+    mod._check(lib, rc, name)
     return (None,) * n_inputs + tuple(grads)
 
 
@@ -423,6 +489,23 @@ class _EncoderTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_mu, g_x, _g_mask):
         return _tape_backward(ctx, (g_mu, g_x), 5)
+
+
+class _ContentVecEncoderTrain(torch.autograd.Function):
+    """us_encoder_forward_features_train / us_encoder_backward_features.  The backward is handed the features again (the tape does
+    not copy them); no gradient is returned for them."""
+
+    @staticmethod
+    def forward(ctx, enc, feats, lengths, seed, p, *params):
+        ins, outs = enc._operands(feats, lengths)
+        _tape_forward(ctx, enc, ins + list(outs), *feats.shape[:2], p, seed, params)
+        ctx.feats = ins[0]
+        ctx.mark_non_differentiable(outs[2])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_mu, g_x, _g_mask):
+        return _tape_backward(ctx, (ctx.feats, g_mu, g_x), 5)
 
 
 class DurationPredictor(_FrontEndModule):

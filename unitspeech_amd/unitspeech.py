@@ -894,3 +894,54 @@ class UnitSpeech(BaseModule):
                            spk_gradient_scale=spk_gradient_scale, mel_range=mel_range, **sampler_kw)
         out = (cond_y[:, :, :y_max_length], dec[:, :, :y_max_length], attn[:, :, :y_max_length])
         return out + (y_lengths,) if return_lengths else out
+
+    @torch.no_grad()
+    def execute_voice_conversion(self, contentvec, contentvec_lengths, mel_lengths, spk_emb, contentvec_encoder, num_downsamplings_in_unet,
+                                 diffusion_steps=50, text_gradient_scale=1.0, spk_gradient_scale=1.0, *, mel_range=None,
+                                 return_lengths=False, **sampler_kw):
+        """`voice_conversion` of the reference's scripts/voice_conversion.py:19-43 for a batch.  contentvec [B, L, n_contentvec] and
+        contentvec_lengths [B] go through the caller's `contentvec_encoder` (:22); `vc_align` takes its output from each item's
+        ContentVec frames to that item's `mel_lengths[b]` mel frames (F.interpolate mode='linear', the zero pad to the U-Net's length
+        multiple and y_mask, :26-33); then z = randn_like(cond_y) and the sampler, the reference's RNG order (:35-41).  Every item gets
+        the B = 1 schedule, as everywhere in this library.  Returns (cond_y, decoder_outputs) cropped to the longest item;
+        mel_range=(mel_min, mel_max): decoder_outputs de-normalised for the vocoder (:114); return_lengths=True: a third result,
+        `y_lengths` (int64 [B] on the device) for `BigVGAN.forward(mel, lengths=y_lengths)`."""
+        cond_x, _, _ = contentvec_encoder(contentvec, contentvec_lengths)
+        y_max_length = max(_length_list(mel_lengths))
+        Tp = fix_len_compatibility(y_max_length, num_downsamplings_in_unet)
+        cond_y, y_mask, y_lengths = vc_align(cond_x, contentvec_lengths, mel_lengths, Tp)
+        z = torch.randn_like(cond_y, device=cond_y.device)                           # the reference's first draw (:35)
+        dec = self.forward(z, y_mask, cond_y, spk_emb, n_timesteps=diffusion_steps, text_gradient_scale=text_gradient_scale,
+                           spk_gradient_scale=spk_gradient_scale, mel_range=mel_range, **sampler_kw)
+        out = (cond_y[:, :, :y_max_length], dec[:, :, :y_max_length])
+        return out + (y_lengths,) if return_lengths else out
+
+
+def _length_list(lengths):
+    """Per-item lengths (a tensor on any device, or a sequence of ints) as a list of Python ints."""
+    return [int(v) for v in (lengths.cpu().tolist() if torch.is_tensor(lengths) else lengths)]
+
+
+def vc_align(cond_x, x_lengths, y_lengths, Tp):
+    """`us_vc_align`: cond_x [B, F, L] -> (cond_y [B, F, Tp], y_mask [B, 1, Tp], y_lengths int64 [B] on the device).  Item b is
+    interpolated linearly (F.interpolate mode='linear', align_corners=False) from its own x_lengths[b] frames to its own
+    y_lengths[b] frames, as if it were alone; zeros fill [y_lengths[b], Tp).  Lengths are validated on the host, before any launch:
+    a call is refused unless 1 <= x_lengths[b] <= L and 1 <= y_lengths[b] <= Tp."""
+    dev = cond_x.device
+    if dev.type != "cuda":
+        raise RuntimeError("the HIP decoder needs tensors on a ROCm device (no CPU fallback); got " + str(dev))
+    if cond_x.dim() != 3:
+        raise ValueError(f"vc_align: expected cond_x [B, F, L], got {tuple(cond_x.shape)}")
+    B, F, L = cond_x.shape
+    xl, yl, Tp = _length_list(x_lengths), _length_list(y_lengths), int(Tp)
+    if len(xl) != B or len(yl) != B or Tp < 1 or any(not 1 <= n <= L for n in xl) or any(not 1 <= n <= Tp for n in yl):
+        raise ValueError(f"vc_align: x_lengths {xl} must hold {B} values in [1, {L}] and y_lengths {yl} {B} values in [1, {Tp}]")
+    cx = _f32c(cond_x, dev)
+    meta = torch.tensor([xl, yl], dtype=torch.int64).to(dev)
+    cond_y = torch.empty(B, F, Tp, dtype=torch.float32, device=dev)
+    y_mask = torch.empty(B, 1, Tp, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().us_vc_align(_dev_ptr(cx), _dev_ptr(meta[0]), _dev_ptr(meta[1]), _dev_ptr(cond_y), _dev_ptr(y_mask), B, F, L, Tp,
+                                     _stream())
+    _lib.check(rc, None, "us_vc_align")
+    return cond_y, y_mask, meta[1]
