@@ -96,8 +96,10 @@ for u in range(L - 1):
     conv(f"ups.{u}.up 4x4s2T {co} L{l}->L{l-1} (4 phases, one launch)", npx(l), co, co, 16)
 conv("final 3x3 128->128 L0", npx(0), C[0], C[0], 9, wino=0 >= WMIN)
 
-# (the short-K GEMMs of the 4-wide forms run on wino_stream_kernel unless US_WINO_STREAM=0: the same launch slots)
-rows = [r for r in csv.DictReader(open(a.trace)) if "conv_igemm" in r["Kernel_Name"] or "wino_stream_kernel" in r["Kernel_Name"]]
+# (the short-K GEMMs of the 4-wide forms run on wino_stream_kernel unless US_WINO_STREAM=0, the routed long-K ones on wino_persist_kernel unless
+# US_WINO_PERSIST=0: the same launch slots)
+CONV_KERNELS = ("conv_igemm", "wino_stream_kernel", "wino_persist_kernel")
+rows = [r for r in csv.DictReader(open(a.trace)) if any(k in r["Kernel_Name"] for k in CONV_KERNELS)]
 n = len(seq)
 assert len(rows) % n == 0, (len(rows), n)
 evals = len(rows) // n

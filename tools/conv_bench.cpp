@@ -5,6 +5,8 @@
 // outputs compared byte for byte, and the output transforms over the same bytes as the reference rate.
 // The "S" shapes (wino = 3, with CB_F16) are the 4-wide forms' separate GEMMs as the decoder launches them: each runs on the general kernel and,
 // where the rule routes it, on wino_stream_kernel; the two outputs are compared bit for bit.
+// CB_PERSIST (with CB_F16) compares the general kernel with wino_persist_kernel (CB_PERSIST_WGS workgroups, default one per CU) instead, bit
+// for bit: on the two K = 512 "S" shapes and on the "P" shapes, the other K >= 512 GEMMs of the 4-wide forms at B' = 3.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -321,6 +323,10 @@ int main() {
                     {"S2 W44 256->256", 36, 15, 64, 256, 256, 1, 3}, {"S2 W44 256->512", 36, 15, 64, 256, 512, 1, 3},
                     {"S2 W44 512->512", 36, 15, 64, 512, 512, 1, 3}, {"S3 W24 512->512", 24, 15, 32, 512, 512, 1, 3},
                     {"S1 W44 ragged 340 rows", 36, 20, 17, 256, 256, 1, 3}, {"S2 W44 ragged 50 rows", 36, 10, 5, 256, 512, 1, 3},
+                    // the other K >= 512 launches of the decode (level 2: 36 frequencies x 960 rows, level 3: 24 x 480) and two ragged ones
+                    {"P2 W44 1024->256", 36, 15, 64, 1024, 256, 1, 3}, {"P3 W24 512->1024", 24, 15, 32, 512, 1024, 1, 3},
+                    {"P3 W24 1024->1024", 24, 15, 32, 1024, 1024, 1, 3}, {"P3 W24 2048->512", 24, 15, 32, 2048, 512, 1, 3},
+                    {"P3 W24 ragged 180 rows", 24, 9, 20, 1024, 1024, 1, 3}, {"P2 W44 ragged 50 rows", 36, 10, 5, 512, 512, 1, 3},
                     // wino = 2: output transform fused (B = items, H x W = tile grid, output 2H x 2W)
                     {"F0 fused 128->128", 3, 40, 512, 128, 128, 1, 2}, {"F1 fused 256->256", 3, 20, 256, 256, 256, 1, 2},
                     {"F1 fused 512->256", 3, 20, 256, 512, 256, 1, 2}, {"F2 fused 512->512 B24", 24, 10, 128, 512, 512, 1, 2},
@@ -343,8 +349,17 @@ int main() {
       hipLaunchKernelGGL(to_f16x2_kernel, dim3(4096), dim3(256), 0, 0, w, n_w / 8);
     }
     std::vector<float> ref_out;         // wino = 3: the general kernel's output, compared with the streaming kernel's
+    const bool persist_mode = getenv("CB_PERSIST") != nullptr;     // wino = 3: general against persistent instead of general against streaming
+    int persist_wgs = 0;
+    if (persist_mode) {
+      CK(hipDeviceGetAttribute(&persist_wgs, hipDeviceAttributeMultiprocessorCount, 0));
+      if (getenv("CB_PERSIST_WGS") && atoi(getenv("CB_PERSIST_WGS")) > 0) persist_wgs = atoi(getenv("CB_PERSIST_WGS"));
+    }
     for (int stream : {0, 1})
     for (int tm : {0, 256, 128, 64}) {
+#ifdef US_LIFE
+      if (sh.wino == 3 && stream) continue;      // workgroup lives are stamped by the general kernel only
+#endif
       if (sh.wino == 3 ? tm != 0 : (stream != 0 || (tm == 0 && !(getenv("CB_TM") && atoi(getenv("CB_TM")) == 0)))) continue;
       if (sh.wino != 3 && getenv("CB_TM") && atoi(getenv("CB_TM")) != tm) continue;
       if (tm == 256 && !(f16 && sh.wino != 2)) continue;
@@ -361,7 +376,9 @@ int main() {
       if (sh.wino == 1) { a.wt_bstride = (long long)sh.Cin * sh.Cout; a.wt_bdiv = sh.B / 16; a.splitk_ws = nullptr; }
       if (sh.wino == 3) {
         a.wt_bstride = (long long)sh.Cin * sh.Cout; a.splitk_ws = nullptr; a.bias = nullptr; a.xcd_z = sh.Cin >= 256 && sh.Cout >= 256;
-        a.Hin = a.Hs = a.Hout = sh.H; a.wino_stream = stream;
+        a.Hin = a.Hs = a.Hout = sh.H;
+        if (persist_mode) a.wino_persist = stream ? persist_wgs : 0;
+        else a.wino_stream = stream;
       }
       if (sh.wino == 2) { a.wt_bstride = (long long)sh.Cin * sh.Cout; a.wino_out = 1; a.ostep = 2; a.Hout = 2 * sh.H; a.Wout = 2 * sh.W; a.splitk_ws = nullptr; }
       if (sh.taps == 9) { for (int ky = 0; ky < 3; ++ky) for (int kx = 0; kx < 3; ++kx) a.set_tap(ky * 3 + kx, ky - 1, kx - 1, ky * 3 + kx); }
@@ -439,7 +456,7 @@ int main() {
         CK(hipMemcpy(h.data(), out, n_out * 4, hipMemcpyDeviceToHost));
         const double gb = ((double)n_in + n_out + n_w) * 4e-9;
         double asum = 0; for (float v : h) asum += v < 0 ? -v : v;
-        printf("%-24s %s  %8.1f us  %6.1f TFLOP/s  %5.2f TB/s  mean|M| %.4f", sh.name, stream ? "stream " : "general", ms * 1e3, fl / ms / 1e9, gb / ms, asum / n_out);
+        printf("%-24s %s  %8.1f us  %6.1f TFLOP/s  %5.2f TB/s  mean|M| %.4f", sh.name, stream ? (persist_mode ? "persist" : "stream ") : "general", ms * 1e3, fl / ms / 1e9, gb / ms, asum / n_out);
         if (!stream) { ref_out.swap(h); printf("\n"); }
         else printf("  %s\n", memcmp(ref_out.data(), h.data(), n_out * 4) == 0 ? "bit-identical" : "DIFFERS");
         CK(hipMemset(out, 0xff, n_out * 4));       // the next variant must write every element itself

@@ -5,6 +5,12 @@ import re
 import subprocess
 import sys
 
+# dynamic LDS the launchers ask for (the compiler reports only static LDS: 0 for these), bytes per workgroup
+DYNAMIC_LDS = {
+    "wino_stream_kernel<256, 3>": (3 * 32 * 256 + 8 * 32 * 36) * 4,
+    "wino_persist_kernel<64, 1>": (3 * (256 + 64) * 32 + 8 * 32 * 36) * 4,      # 256 x 64 tiles
+}
+
 
 def main():
     src = sys.argv[1]
@@ -16,17 +22,19 @@ def main():
         sys.exit(r.returncode)
     rows, cur = [], None
     for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
+        m = re.search(r"remark:(?: \S+:\d+:\d+:)? Function Name: (\S+)", line)
         if m:
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
             cur = {"name": name}
             rows.append(cur)
             continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        m = re.search(r"remark:(?: \S+:\d+:\d+:)?\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
     print(f"{'VGPR':>5} {'AGPR':>5} {'spill':>6} {'scratch':>8} {'occ':>4} {'LDS':>7}  kernel")
     for c in rows:
+        if not c.get("LDS Size"):
+            c["LDS Size"] = next((v for k, v in DYNAMIC_LDS.items() if k in c["name"]), 0)
         print(f"{c.get('VGPRs', 0):5d} {c.get('AGPRs', 0):5d} {c.get('VGPRs Spill', 0):6d} {c.get('ScratchSize', 0):8d} "
               f"{c.get('Occupancy', 0):4d} {c.get('LDS Size', 0):7d}  {c['name'][:150]}")
 

@@ -1012,6 +1012,236 @@ static hipError_t launch_wino_stream(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// Winograd-domain GEMMs with long K (>= 512), persistent: M_f [rows][N] = V_f [rows][K] * U_f, both operands in the two-plane fp16 form, M dense in
+// fp32.  The general loop runs these as rounds of short-lived workgroups (K / 32 = 16 ... 64 steps each): every workgroup fills its pipeline cold, and
+// the workgroups of a round end together, so their store burst runs while no matrix pipe has work.  Here a bounded grid of workgroups (one per CU,
+// 8 waves as 4 (M) x 2 (N), 512 threads) walks its share of the work items (frequency, row tile, column tile; column tile fastest) back to
+// back, and the three-buffer chunk rotation does NOT restart per item: chunk g of the workgroup's whole sequence lives in buffer g % 3, and at step g
+// the pieces of chunk g + 2 are issued -- during the last two steps of item t those are the first two chunks of item t + 1 -- so item t's epilogue
+// (acc + 2^-11 total, a per-wave LDS patch outside the operand buffers, 16-byte row stores) runs with the next item's loads in flight and its stores
+// drain under the next item's MFMAs.  No state is shared between workgroups.
+// Tile: TM = 4 WM rows x TN = 64 NB columns (WM = 64, NB = 1: 256 x 64, the form the general launcher picks for K >= 1024; WM = 32, NB = 2: 128 x 128).
+// Same bits as conv_igemm_kernel<32, .., false, true, ..>: ascending 32-channel chunks, two 16-deep steps each, acc = hi hi, total = hi lo then lo hi,
+// one final fma, the same MFMA and lane-half convention, the same LDS image and swizzle.
+// vmcnt: loads, LDS-DMA and stores retire in issue order.  Every step issues exactly P = IA + IB pieces and every item exactly NST = 4 MB NB stores (a
+// row beyond the tensor, and every piece of the item after the workgroup's last, gets an offset beyond its descriptor: the load returns zeros, the
+// store is dropped).  Issue order around the start of item t >= 1 (n = K / 32):
+//   step (t-1, n-1): P pieces of chunk (t, 1)
+//   step (t, 0):     the first pieces of chunk (t, 2) | NST stores of item t-1 | the other pieces of chunk (t, 2)
+//   step (t, 1):     P pieces of chunk (t, 3)
+// so behind the pieces of the chunk that step (t, c) is about to read there are P younger operations, except at c = 1 of every item but the
+// workgroup's first, where there are P + NST.  The wait also retires this wave's fragment reads (lgkmcnt(0)) before the barrier, so that the buffer
+// of chunk g - 1, which chunk g + 2 overwrites after the barrier, has no read in flight from any wave.
+template <int WM, int NB>
+__global__ __launch_bounds__(512) void wino_persist_kernel(ConvArgs a, int rows, int mt, int total_items) {
+  constexpr int BK = 32, NWM = 4, NW = 2 * NWM;
+  constexpr int MB = WM / 32, TM = NWM * WM, TN = 64 * NB;
+  constexpr int IA = TM / 8 / NW, IB = TN / 8 / NW;      // a wave-wide piece covers 8 rows of 128 bytes
+  constexpr int P = IA + IB;
+  constexpr int NST = 4 * MB * NB;                       // stores per wave and item
+  constexpr int BUF = (TM + TN) * BK;                    // floats per operand buffer
+  constexpr int SLOTS = 6 * MB * NB;                     // MFMAs of a wave per chunk
+  constexpr int PSTRIDE = SLOTS / P;
+  static_assert(MB >= 1 && IA >= 1 && IB >= 1 && PSTRIDE >= 1 && (P - 1) * PSTRIDE < SLOTS && P + NST <= 63, "piece slots and counted waits");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l32 = lane & 31, hh = lane >> 5;
+
+  // ---- this workgroup's items: the workgroups with the same id % 8 (dealt to one XCD) own one contiguous share of the range, and workgroup j of the
+  // gx in that group takes items j, j + gx, j + 2 gx, ... of the share.  At any time the group is therefore inside gx consecutive items -- with 32
+  // workgroups per XCD about one frequency, as in a round of the general kernel -- so a B tile is fetched into the XCD's L2 once for all the row
+  // tiles that use it.  (Contiguous per-workgroup ranges were built first: the group then streams every frequency of its share at once, U twice
+  // from beyond L2; the same launches measured 4 us slower in the decode) ----
+  const int K = a.Cin, nchunk = K / BK, nt = a.Cout / TN;
+  const long long G = gridDim.x, id = blockIdx.x;
+  const long long ng = G < 8 ? G : 8, gx = (G - (id & 7) + 7) >> 3;
+  const long long g_lo = total_items * (id & 7) / ng;
+  const int it_lo = (int)(g_lo + (id >> 3)), it_hi = (int)(total_items * ((id & 7) + 1) / ng), it_step = (int)gx;
+  if (it_hi <= it_lo) return;
+  const int n_items = (it_hi - it_lo + it_step - 1) / it_step;
+
+  // ---- DMA source bookkeeping: this lane feeds LDS position (row = 8 * piece + lane / 8, 16-byte slot lane % 8) ----
+  const unsigned a_bytes = (unsigned)rows * (unsigned)K * 4u;               // < 2^31 (host-checked), like the two below
+  const unsigned b_bytes = (unsigned)a.Cout * (unsigned)K * 4u;
+  const unsigned o_bytes = (unsigned)rows * (unsigned)a.Cout * 4u;
+  const int lrow = lane >> 3, lpos = lane & 7;
+  __amdgpu_buffer_rsrc_t rsrc_a, rsrc_b;
+  unsigned aoff[IA], boff[IB];
+  auto setup_item = [&](int it) {
+    const bool ok = it < it_hi;              // the item after the last: valid descriptors, every offset out of range
+    const int itc = ok ? it : it_lo;
+    const int f = itc / (mt * nt), rem = itc - f * (mt * nt);
+    const int rt = rem / nt, ct = rem - rt * nt;
+    rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (long long)f * rows * K), 0, (int)a_bytes, 0x00020000);
+    rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)(a.wt + (long long)f * a.wt_bstride), 0, (int)b_bytes, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < IA; ++j) {
+      const int r = (wave * IA + j) * 8 + lrow;
+      const int m = rt * TM + r;
+      aoff[j] = (ok && m < rows) ? (unsigned)m * (unsigned)(K * 4) + (unsigned)((lpos ^ ((r >> 1) & 7)) * 16) : a_bytes;
+    }
+#pragma unroll
+    for (int j = 0; j < IB; ++j) {
+      const int r = (wave * IB + j) * 8 + lrow;
+      const int n = ct * TN + r;             // < Cout: Cout is a multiple of TN (host-checked)
+      boff[j] = ok ? (unsigned)n * (unsigned)(BK * 4) + (unsigned)((lpos ^ ((r >> 1) & 7)) * 16) : b_bytes;
+    }
+  };
+  int it_issue = it_lo, ch_issue = 0;        // the chunk the next pieces belong to
+  unsigned pend_ach = 0, pend_wb = 0;
+  int dma_buf = 0;
+  auto dma_piece = [&](int k) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (k == 0) {
+      if (ch_issue == nchunk) { ch_issue = 0; setup_item(it_issue += it_step); }
+      pend_ach = (unsigned)ch_issue * (unsigned)(BK * 4);
+      pend_wb = (unsigned)ch_issue * (unsigned)a.Cout * (unsigned)(BK * 4);
+    }
+    float* As = smem + dma_buf * BUF;
+    float* Bs = As + TM * BK;
+    if (k < IA) blds16(rsrc_a, aoff[k < IA ? k : 0], pend_ach, As + (wave * IA + k) * 8 * BK);
+    else blds16(rsrc_b, boff[k < IA ? 0 : k - IA], pend_wb, Bs + (wave * IB + (k - IA)) * 8 * BK);
+    if (k == P - 1) ++ch_issue;
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  f32x16 acc[MB][NB], total[MB][NB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; total[i][j][r] = 0.f; }
+
+  // fragment reads: row R, 16-byte chunk ((2 s + hh) * 2 + plane) ^ swz(R); swz depends on the lane only (WM is a multiple of 16)
+  const int sw = (l32 >> 1) & 7;
+  const int a_row = (wm * WM + l32) * BK;
+  const int b_row = TM * BK + (wn * (32 * NB) + l32) * BK;
+  f32x4 fa0[MB * 2], fb0[NB * 2], fa1[MB * 2], fb1[NB * 2];
+  auto load_frags = [&](f32x4* fa, f32x4* fb, const float* base, int s_) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int co = ((((2 * s_ + hh) << 1) + p) ^ sw) * 4;
+#pragma unroll
+      for (int i = 0; i < MB; ++i) fa[i * 2 + p] = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + co);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) fb[nb * 2 + p] = *reinterpret_cast<const f32x4*>(base + b_row + nb * 32 * BK + co);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // phase 0 / 1: first / second half of a step's MFMAs (the piece slots); phase -1: no pieces
+  auto mma = [&](const f32x4* fa, const f32x4* fb, int phase) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const half8 ah = __builtin_bit_cast(half8, fa[i * 2]), al = __builtin_bit_cast(half8, fa[i * 2 + 1]);
+        const half8 bh = __builtin_bit_cast(half8, fb[j * 2]), bl = __builtin_bit_cast(half8, fb[j * 2 + 1]);
+        const int s0 = phase * (SLOTS / 2) + (i * NB + j) * 3;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i][j], 0, 0, 0);
+        if (phase >= 0 && s0 % PSTRIDE == 0 && s0 / PSTRIDE < P) dma_piece(s0 / PSTRIDE);
+        total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, total[i][j], 0, 0, 0);
+        if (phase >= 0 && (s0 + 1) % PSTRIDE == 0 && (s0 + 1) / PSTRIDE < P) dma_piece((s0 + 1) / PSTRIDE);
+        total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, total[i][j], 0, 0, 0);
+        if (phase >= 0 && (s0 + 2) % PSTRIDE == 0 && (s0 + 2) / PSTRIDE < P) dma_piece((s0 + 2) / PSTRIDE);
+      }
+  };
+  // item `it` is complete in acc / total: store it and clear the accumulators.  C/D layout of a 32x32 block: col = lane & 31,
+  // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); turned round through the wave's patch so that a lane stores 16 bytes
+  float* tr = smem + 3 * BUF + wave * (32 * 36);
+  const int trow = lane >> 3, tc4 = (lane & 7) * 4;
+  auto store_item = [&](int it) {
+    const int f = it / (mt * nt), rem = it - f * (mt * nt);
+    const int rt = rem / nt, ct = rem - rt * nt;
+    const __amdgpu_buffer_rsrc_t rsrc_o =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (long long)f * rows * a.Cout), 0, (int)o_bytes, 0x00020000);
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const int m_base = rt * TM + wm * WM + mb * 32, ncol = ct * TN + wn * (32 * NB) + nb * 32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          tr[((r & 3) + 8 * (r >> 2) + 4 * hh) * 36 + l32] = __builtin_fmaf(total[mb][nb][r], 0x1p-11f, acc[mb][nb][r]);
+          acc[mb][nb][r] = 0.f;
+          total[mb][nb][r] = 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int dr = trow + 8 * k;
+          const int m = m_base + dr;
+          f32x4 v = *reinterpret_cast<const f32x4*>(tr + dr * 36 + tc4);
+          v = v + f32x4{0.f, 0.f, 0.f, 0.f};      // the general epilogue adds its (absent) bias: a -0 becomes +0 there, so it does here
+          const unsigned off = m < rows ? ((unsigned)m * (unsigned)a.Cout + (unsigned)(ncol + tc4)) * 4u : o_bytes;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_o, (int)off, 0, 0);
+        }
+      }
+  };
+
+  // ---- prologue: chunks 0 and 1 of the first item, all pieces at once ----
+  setup_item(it_lo);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    dma_buf = c;
+#pragma unroll
+    for (int k = 0; k < P; ++k) dma_piece(k);
+  }
+
+  const int nsteps = n_items * nchunk;
+  int cur = 0, c = 0, it = it_lo;
+  for (int g = 0; g < nsteps; ++g) {
+    if (c == 1 && it != it_lo) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(P + NST) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(P) : "memory");
+    __builtin_amdgcn_s_barrier();       // everybody's pieces of chunk g have landed; nobody has a read of chunk g-1 in flight
+    dma_buf = cur == 0 ? 2 : cur - 1;   // (g + 2) % 3
+    const float* base = smem + cur * BUF;
+    load_frags(fa0, fb0, base, 0);
+    if (g > 0) {
+      mma(fa1, fb1, 0);                 // the second 16-deep step of chunk g-1, deferred across the barrier: it covers the reads above
+      if (c == 0) store_item(it - it_step);   // ... which completed an item
+    } else {
+#pragma unroll
+      for (int k = 0; k < P; ++k)
+        if (k * PSTRIDE < SLOTS / 2) dma_piece(k);
+    }
+    load_frags(fa1, fb1, base, 1);
+    mma(fa0, fb0, 1);
+    cur = cur == 2 ? 0 : cur + 1;
+    if (++c == nchunk) { c = 0; it += it_step; }
+  }
+  mma(fa1, fb1, -1);
+  store_item(it - it_step);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the zero-filled pieces of the item beyond it_hi are still landing in this workgroup's LDS
+}
+
+template <int WM, int NB>
+static constexpr int persist_lds_bytes() { return (3 * (4 * WM + 64 * NB) * 32 + 8 * 32 * 36) * (int)sizeof(float); }
+
+// Does a launch qualify for wino_persist_kernel?  A function of K, N and the form only (the sizes below merely keep 32-bit offsets in range).
+static bool wino_persist_route(const ConvArgs& a) {
+  if (a.wino_persist <= 0 || a.f16 != 1 || a.ntaps != 1 || a.direct_presplit || a.istride != 1 || a.tm != 0) return false;
+  if (a.bias || a.add || a.stats || a.omask || a.alpha || a.out2 || a.out_split || a.wino_out || a.attn_part_ctx || a.nphase > 1) return false;
+  if (a.Cin < 512 || a.Cin % 32 != 0 || a.in_ld != a.Cin || a.out_ld != a.Cout || a.wt_bdiv > 1 || a.wt_rows != 0) return false;
+  if (a.Cout % 64 != 0) return false;
+  if (a.ostep != 1 || a.oy0 != 0 || a.ox0 != 0 || a.Hs != a.Hout || a.Ws != a.Wout || a.Hin != a.Hs || a.Win != a.Ws) return false;
+  if ((a.dy_bits & 15) != 8 || (a.dx_bits & 15) != 8 || (a.wtap_bits & 15) != 0) return false;
+  const long long rows = (long long)a.Hs * a.Ws;
+  return rows * a.Cin * 4 < (1LL << 31) && rows * a.Cout * 4 < (1LL << 31) && (long long)a.Cin * a.Cout * 4 < (1LL << 31) &&
+         (long long)a.B * ((rows + 255) / 256) * (a.Cout / 64) < (1LL << 27);
+}
+
+static hipError_t launch_wino_persist(const ConvArgs& a, hipStream_t s) {
+  const int rows = a.Hs * a.Ws;
+  const int wgs = a.wino_persist;            // CUs x one co-resident workgroup, or US_WINO_PERSIST_WGS
+  // 256 x 64 tiles at every K.  The 128 x 128 instantiation <32, 2> (the general launcher's tile for K = 512) was built and measured too: slower
+  // than this one at K = 512 (level 2, 512 -> 512: 78.7 against 64.7 us warm), so only one form is compiled in.
+  const int mt = (rows + 255) / 256;
+  hipLaunchKernelGGL((wino_persist_kernel<64, 1>), dim3(wgs), dim3(512), (persist_lds_bytes<64, 1>()), s, a, rows, mt, a.B * mt * (a.Cout / 64));
+  return hipGetLastError();
+}
+
 static size_t lds_bytes(int bk, int tm, int nstg = 2, int tn = TN) { return (size_t)nstg * (tm + tn) * bk * sizeof(float); }
 
 template <int BK, int WM, bool WINO, bool F16 = false, int NWM = 2, int NSTG = 2, bool ASPLIT = false>
@@ -1038,6 +1268,8 @@ hipError_t conv_igemm_init() {
   if ((e = set_attr<32, 32, true, true, 2, 3>()) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_stream_kernel<256, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                stream_lds_bytes<256, 3>())) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_persist_kernel<64, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               persist_lds_bytes<64, 1>())) != hipSuccess) return e;
   return set_attr<16, 32, true>();
 }
 
@@ -1059,6 +1291,8 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   if (a.out2 && (a.out2_ld % 4 != 0 || a.wino_out || a.out_split || a.attn_part_ctx)) return hipErrorInvalidValue;
   // short-K Winograd-domain GEMMs of the 4-wide forms: the streaming kernel (same bits; US_WINO_STREAM, a non-zero US_F16_TM keeps this path)
   if (wino_stream_route(a)) return launch_wino_stream(a, s);
+  // long-K Winograd-domain GEMMs of the 4-wide forms: the persistent kernel (same bits; US_WINO_PERSIST, a non-zero US_F16_TM keeps this path)
+  if (wino_persist_route(a)) return launch_wino_persist(a, s);
   const int Ms = a.Hs * a.Ws;
   int tn = TN;                        // 64: the half-width tile of the Winograd-domain GEMMs (conv_igemm_kernel<.., NB = 1>), chosen below
   int nt = (a.Cout + TN - 1) / TN;

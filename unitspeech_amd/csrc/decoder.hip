@@ -121,6 +121,8 @@ struct us_decoder {
   int wino4_level_form[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int wino_fuse = -1;        // US_WINO_FUSE: Winograd output transform inside the GEMM wherever legal (1), never (0), by launch size (-1, wino_conv)
   bool wino_fuse_gn = true;  // US_WINO_FUSE_GN=0: block1's gn_apply as its own pass
+  bool wino_persist = true;  // US_WINO_PERSIST=0: the 4-wide forms' K >= 512 GEMMs on the general kernel instead of wino_persist_kernel (same bits)
+  int wino_persist_wgs = 256;  // its grid: the device's CU count, or US_WINO_PERSIST_WGS
   bool wino_stream = true;   // US_WINO_STREAM=0: the 4-wide forms' K = 256 GEMMs on the general kernel instead of wino_stream_kernel (same bits)
   bool split_store16 = true; // US_SPLIT_STORE16=0: the memory passes that produce the two-plane fp16 form (Winograd input transforms, gn_apply) write it
                              // with 8-byte stores per lane instead of lane-paired 16-byte ones (same bits).  The convolution epilogue's out_split
@@ -543,6 +545,11 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
     a.B = nf; a.Hin = a.Hs = a.Hout = e.Bp * t4h; a.Wout = t4w; a.ostep = 1;
     a.tm = e.h->f16_tm;
     a.wino_stream = e.h->wino_stream ? 1 : 0;
+    // long K on the persistent kernel where it measured faster in the decode (a function of K, N and the form only): K = 1024, and
+    // K = 512 except the F(2x4) form's 512 -> 512 (1.5 items per workgroup at B' = 3: nothing to carry a pipeline into; measured null).  K = 2048
+    // (its 192 full-width tiles are one round of the general kernel; measured slower) stays where it was.
+    const bool persist_gain = K == 1024 || (K == 512 && !(form4 == 24 && N == 512));
+    a.wino_persist = e.h->wino_persist && persist_gain ? e.h->wino_persist_wgs : 0;
     a.xcd_z = K >= 256 && N >= 256;
     err4 = run_conv(e, a);
     if (err4 != hipSuccess) return err4;
@@ -1234,6 +1241,14 @@ int us_decoder_create_ex(us_handle* out, const us_config* cfg, unsigned flags) {
   if (const char* wf = getenv("US_WINO_FUSE")) h->wino_fuse = atoi(wf) != 0 ? 1 : 0;
   if (const char* wf = getenv("US_WINO_FUSE_GN")) h->wino_fuse_gn = atoi(wf) != 0;
   if (const char* ws = getenv("US_WINO_STREAM")) h->wino_stream = atoi(ws) != 0;
+  if (const char* wp = getenv("US_WINO_PERSIST")) h->wino_persist = atoi(wp) != 0;
+  {
+    // the persistent kernel's grid: one workgroup per CU (each takes a CU's LDS); US_WINO_PERSIST_WGS overrides it (tests, tuning)
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) cus = 256;
+    h->wino_persist_wgs = cus;
+    if (const char* wg = getenv("US_WINO_PERSIST_WGS")) { if (atoi(wg) > 0 && atoi(wg) <= 65536) h->wino_persist_wgs = atoi(wg); }
+  }
   if (const char* ss = getenv("US_SPLIT_STORE16")) h->split_store16 = atoi(ss) != 0;
   if (const char* wt = getenv("US_F16_TM")) h->f16_tm = atoi(wt) == 64 || atoi(wt) == 128 || atoi(wt) == 256 ? atoi(wt) : 0;
   if (const char* ws = getenv("US_WGRAD_STREAM")) h->wgrad_side_streams = atoi(ws) < 0 ? 0 : (atoi(ws) > Tape::kSideMax ? Tape::kSideMax : atoi(ws));

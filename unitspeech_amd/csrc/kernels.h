@@ -160,6 +160,9 @@ struct ConvArgs {
   // (grid z = B * 4), each with its own tap table; oy0 / ox0 / dy_bits / dx_bits / wtap_bits above are then unused.  One
   // 4x larger grid instead of four sub-wave ones back to back.
   int nphase;
+  int wino_persist;      // > 0: a separate-form Winograd-domain GEMM (f16 = 1) with K >= 512 may run on wino_persist_kernel (conv_igemm.hip:
+                         // persistent workgroups, the pipeline carried across tiles; same bits) with this many workgroups:
+                         // us_decoder::wino_persist / wino_persist_wgs.  (Placed here it takes nphase's padding: no other member moves.)
   unsigned long long ph_dy[4], ph_dx[4], ph_wtap[4];
   void set_phase_tap(int ph, int i, int dy, int dx, int wtap) {
     ph_dy[ph] |= (unsigned long long)(dy + 8) << (4 * i);
