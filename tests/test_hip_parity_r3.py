@@ -35,8 +35,7 @@ def l1(a, b):
     return (a.double().cpu() - b.double().cpu()).abs().mean().item()
 
 
-def build(sd_np, exact=False, train=False):
-    cfg = FULL
+def build(sd_np, exact=False, train=False, cfg=FULL):
     m = UnitSpeech(cfg.n_feats, cfg.dim, list(cfg.dim_mults), cfg.beta_min, cfg.beta_max, cfg.pe_scale, cfg.spk_emb_dim)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd_np.items()}, strict=True)
     m.exact = exact
@@ -299,8 +298,8 @@ class _ReplayRandn:
         return d.to(device=kw.get("device", d.device), dtype=kw.get("dtype", d.dtype))
 
 
-def _hip_grads(sd_np, x0, mask, cond, spk, t, z, exact=False, loss_factor=1.0):
-    m = build(sd_np, exact=exact, train=True)
+def _hip_grads(sd_np, x0, mask, cond, spk, t, z, exact=False, loss_factor=1.0, cfg=FULL):
+    m = build(sd_np, exact=exact, train=True, cfg=cfg)
     with _ReplayRandn([z.to(DEV)]):
         loss, _ = m.loss_t(x0.to(DEV), mask.to(DEV), cond.to(DEV), t.to(DEV), spk.to(DEV))
     (loss * loss_factor).backward()
@@ -381,6 +380,48 @@ def test_pretraining_batch_loss_and_every_gradient_vs_oracle_autograd(sd_np):
             worst = max(worst, (float((mine - g64).norm() / (g64.norm() + 1e-300)), n))
         print(f"  {tag} vs the reference's fp64 autograd: worst tensor {worst[1]} {worst[0]:.2e}")
         assert worst[0] <= 1e-4, worst
+
+
+@pytest.mark.parametrize("dim_mults,n_grads", [((1,), 60), ((1, 2), 116)])
+def test_one_and_two_level_unets_vs_oracle(dim_mults, n_grads):
+    """The U-Net walk at the depths every other test leaves out (they all run four levels): one level has no Downsample, Upsample or concat
+    buffer and mid_block2 feeds the final block; two levels have one of each and mid_block2 writes into the concat buffer.  Estimator,
+    sampler, and the training loss with every gradient, against the CPU oracle (which takes the depth from the state dict), at the bars of
+    test_estimator_ragged_lengths_vs_oracle, test_loop_minimum_sizes_vs_oracle and
+    test_pretraining_batch_loss_and_every_gradient_vs_oracle_autograd."""
+    from unitspeech_amd.params import param_shapes
+    cfg = DecoderConfig(dim=16, dim_mults=dim_mults)
+    sd_np, T = synthetic_state_dict(cfg, 0), 8
+    sd = O.to_torch(sd_np)
+    model = build(sd_np, cfg=cfg)
+    # inference: a full, a partly and a fully padded item, three diffusion times
+    inp = G(synthetic_inputs(cfg, 3, T, seed=11, n_steps=2, lengths=[8, 5, 0]))
+    t = torch.tensor([0.37, 0.9, 0.05])
+    with torch.no_grad():
+        out = model.estimator(inp["z"].to(DEV), inp["mask"].to(DEV), inp["cond"].to(DEV), t.to(DEV), inp["spk_emb"].to(DEV))
+    e_est = l1(out, O.estimator_forward(sd, inp["z"], inp["mask"], inp["cond"], t, inp["spk_emb"]))
+    dec = model(inp["z"].to(DEV), inp["mask"].to(DEV), inp["cond"].to(DEV), inp["spk_emb"].to(DEV), 2, 1.0, 1.0, noise=inp["noise"].to(DEV))
+    e_dec = l1(dec, O.reverse_diffusion(sd, inp["z"], inp["mask"], inp["cond"], inp["spk_emb"], 2, 1.0, 1.0, noise=inp["noise"]))
+    print(f"\n{len(dim_mults)} level(s): estimator L1 vs oracle {e_est:.3e}, 2-step decode L1 vs oracle {e_dec:.3e}")
+    assert tuple(out.shape) == (3, cfg.n_feats, T) and e_est <= 2e-6
+    assert out[2].abs().max().item() == 0.0            # fully padded item
+    assert e_dec <= 1e-4
+    # training: no empty item, so that no gradient tensor has zero norm
+    tr = G(synthetic_inputs(cfg, 2, T, seed=12, n_steps=1, lengths=[8, 5]))
+    x0, mask, cond, spk, z, tt = tr["z"].clamp(-1, 1), tr["mask"], tr["cond"], tr["spk_emb"], tr["noise"][0], torch.tensor([0.3, 0.8])
+    leaf = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    loss_ref, _ = O.loss_t(leaf, x0, mask, cond, tt, spk, z, cfg.n_feats, cfg.beta_min, cfg.beta_max, cfg.pe_scale)
+    loss_ref.backward()
+    ref = {k: v.grad.detach().double() for k, v in leaf.items() if v.grad is not None and k.startswith("estimator.")}
+    assert len(ref) == n_grads == len([k for k in param_shapes(cfg) if k.startswith("estimator.")])
+    assert all(float(g.norm()) > 0 for g in ref.values())
+    for tag, exact in (("f16x3", False), ("exact-fp32", True)):
+        loss, got = _hip_grads(sd_np, x0, mask, cond, spk, tt, z, exact=exact, cfg=cfg)
+        assert set(ref) <= set(got)                     # no tensor is skipped
+        _, median, worst = _rel({k: got[k] for k in ref}, ref)
+        print(f"  {tag}: loss {loss:.7f} (oracle {float(loss_ref):.7f}), gradient tensors vs oracle autograd: median {median:.2e}, worst {worst:.2e}")
+        assert abs(loss - float(loss_ref)) <= 2e-6 * max(1.0, abs(float(loss_ref)))
+        assert worst <= 1e-4
 
 
 def test_weight_gradient_chains_on_the_second_stream_give_the_gradients_of_the_one_stream_backward(sd_np, monkeypatch):

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
@@ -327,6 +328,21 @@ struct us_decoder {
 
 namespace {
 
+// every ResnetBlock in execution order: downs (r1, r2 per level), mid1, mid2, ups (r1, r2 per level).  fn returns nothing, or a
+// hipError_t: then the first failure is returned and the blocks after it are not visited
+template <typename Fn>
+auto for_each_resnet(us_decoder* h, Fn&& fn) {
+  if constexpr (std::is_void<decltype(fn(h->mid1))>::value) {
+    for (auto& d : h->downs) { fn(d.r1); fn(d.r2); }
+    fn(h->mid1); fn(h->mid2);
+    for (auto& u : h->ups) { fn(u.r1); fn(u.r2); }
+  } else {
+    hipError_t err = hipSuccess;
+    for_each_resnet(h, [&](const ResnetW& r) { if (err == hipSuccess) err = fn(r); });
+    return err;
+  }
+}
+
 // enqueue the deferred RAW-tensor copies (us_decoder_load_weight) as one launch; called by every entry point that computes
 int flush_copies(us_decoder* h, hipStream_t st);
 
@@ -360,20 +376,86 @@ struct Buffers {
   float *in2, *posemb, *mlp_h, *temb, *tproj;
   std::vector<size_t> tproj_off;   // per resnet, in floats
   int tproj_ld = 0;
-  double* stats;                   // [n_gn][Bp][8][2][kStatSlots]
-  size_t stats_count = 0;
-  std::vector<float*> D, P, Q, S1, S2, QKV, CAT;
-  float* U0;
-  float *part_ctx, *part_m, *part_s, *ctx, *weff, *colM, *colS, *ctx_split;
-  float* wtotal = nullptr;         // [Bp][C][C] W_out blockdiag(ctx^T) W_q of the levels whose attention folds q away (attention())
+  float *part_ctx, *part_m, *part_s, *ctx_split;
   float *wino_v = nullptr, *wino_m = nullptr;   // Winograd-domain input / product tensors [16][Bp][tiles][C]
   float* splitk = nullptr;         // split-K slab scratch of the conv kernel
   size_t splitk_floats = 0;
   bool tproj_ready = false;        // true when tproj already holds this evaluation's time projections
+  // inference plans only (plan()): per-level activations the placement table aliases its entries onto, and the attention's per-item operands
+  std::vector<float*> D, P, Q, S1, S2, QKV;
+  float* U0 = nullptr;
+  float *ctx = nullptr, *weff = nullptr, *colM = nullptr, *colS = nullptr;
+  float* wtotal = nullptr;         // [Bp][C][C] W_out blockdiag(ctx^T) W_q of the levels whose attention folds q away (attention())
 };
 
-void plan(us_decoder* h, Arena& A, int Bp, int T, Buffers& b, bool train = false) {
-  const int L = h->cfg.n_mults, F = h->cfg.n_feats;
+// ---- placement table: where each ResnetBlock, attention and resample of the U-Net walk (unet_forward) reads and writes.  An inference
+// plan aliases the entries onto the per-level scratch of Buffers (plan()); a training plan gives every entry a slot of its own on the
+// tape (plan_train()).  A null tensor is one the plan does not keep.  `x` / `x_ld` are recorded by the walk (the backward reads them).
+struct ResT {
+  const ResnetW* w = nullptr;
+  const float* x = nullptr; int x_ld = 0;
+  float *y1 = nullptr, *y2 = nullptr;   // block1's / block2's raw convolution output
+  float* h1 = nullptr;                  // block1's activation; null (not kept): it goes in place over y1, or as fp16 planes into `out`
+  float* r0 = nullptr;                  // first block: res_conv's output; null (not kept): the block's last GroupNorm pass re-evaluates it
+  float* r_early = nullptr;             // scratch of a res_conv that has to run before block2's GroupNorm pass (resnet(): split_out)
+  float* out = nullptr; int out_ld = 0;
+  double *st1 = nullptr, *st2 = nullptr;
+};
+struct AttT {
+  const AttnW* w = nullptr;
+  const float* x = nullptr; int x_ld = 0;
+  float *qkv = nullptr, *ctx = nullptr, *colM = nullptr, *colS = nullptr, *weff = nullptr, *out = nullptr;
+  int out_ld = 0;
+  float* o_pre = nullptr;           // fn(x) of the Rezero wrapper, [B][n][dim]: to_out's result before gain and residual (ConvArgs::out2); null: not kept
+};
+struct CvT {
+  const ConvW* w = nullptr; int level = 0;
+  const float* x = nullptr; int x_ld = 0;
+  float* out = nullptr; int out_ld = 0;
+};
+struct Places {
+  std::vector<ResT> res;            // indexed by ResnetW::index
+  std::vector<AttT> att;            // execution order: downs[0..L-1], mid, ups[0..L-2]
+  std::vector<CvT> downs, ups;      // downs[l]: Downsample of level l; ups[u]: Upsample of h->ups[u]
+  std::vector<float*> CAT;          // [l >= 1]: the skip concat (what arrives from level l + 1 | level l's attention output), 2 * C[l] wide
+  float* fin_y = nullptr;           // final Block: raw convolution output
+  float* fin_h = nullptr;           // ... and its activation; null (not kept): GroupNorm + Mish run inside the 1x1 projection
+  const float* fin_x = nullptr; int fin_ld = 0; double* fin_st = nullptr;
+  double* stats = nullptr;          // st1 / st2 of every ResnetBlock and fin_st, [2 * n_resnets + 1][Bp][8][2][kStatSlots]: zeroed once per forward
+  size_t stats_count = 0;
+};
+
+// every entry's weights and GroupNorm statistics; the tensors are the caller's to place
+void init_places(us_decoder* h, Arena& A, int Bp, Places& p) {
+  const int L = h->cfg.n_mults;
+  const size_t st_block = (size_t)Bp * kGroups * kStatStride;
+  p.stats_count = (size_t)(2 * h->n_resnets + 1) * st_block;
+  p.stats = A.alloc<double>(p.stats_count);
+  p.res.assign(h->n_resnets, ResT());
+  for_each_resnet(h, [&](const ResnetW& r) {
+    ResT& t = p.res[r.index];
+    t.w = &r;
+    t.st1 = p.stats + (size_t)(2 * r.index) * st_block;
+    t.st2 = t.st1 + st_block;
+  });
+  p.fin_st = p.stats + (size_t)(2 * h->n_resnets) * st_block;
+  p.att.assign(2 * L, AttT());
+  p.downs.assign(L - 1, CvT());
+  p.ups.assign(L - 1, CvT());
+  p.CAT.assign(L, nullptr);
+  for (int l = 0; l < L; ++l) p.att[l].w = &h->downs[l].a;
+  p.att[L].w = &h->mid_attn;
+  for (int u = 0; u < L - 1; ++u) {
+    p.att[L + 1 + u].w = &h->ups[u].a;
+    p.downs[u].w = &h->downs[u].ds.conv; p.downs[u].level = u;
+    p.ups[u].w = &h->ups[u].us.conv; p.ups[u].level = h->ups[u].us.level;
+  }
+}
+
+// The scratch every plan needs: stacked input, time embedding, attention partials, split-K slabs, Winograd-domain tensors.  train: the
+// plan of a training step (F(2x2) only; the data gradient runs through the same V / M with a convolution's channel counts swapped)
+void plan_shared(us_decoder* h, Arena& A, int Bp, int T, Buffers& b, bool train) {
+  const int F = h->cfg.n_feats;
   const size_t B = (size_t)Bp;
   b.in2 = A.alloc<float>(B * F * T * 2);
   b.posemb = A.alloc<float>(B * h->cfg.dim);
@@ -382,45 +464,16 @@ void plan(us_decoder* h, Arena& A, int Bp, int T, Buffers& b, bool train = false
   // per-resnet time projections, one row block per resnet
   b.tproj_off.assign(h->n_resnets, 0);
   size_t toff = 0;
-  auto reg = [&](const ResnetW& r) { b.tproj_off[r.index] = toff; toff += B * r.cout; };
-  for (auto& d : h->downs) { reg(d.r1); reg(d.r2); }
-  reg(h->mid1); reg(h->mid2);
-  for (auto& u : h->ups) { reg(u.r1); reg(u.r2); }
+  for_each_resnet(h, [&](const ResnetW& r) { b.tproj_off[r.index] = toff; toff += B * r.cout; });
   b.tproj = A.alloc<float>(toff);
-  b.stats_count = (size_t)(2 * h->n_resnets + 1) * B * kGroups * kStatStride;
-  b.stats = A.alloc<double>(b.stats_count);
-  b.D.assign(L, nullptr); b.P.assign(L, nullptr); b.Q.assign(L, nullptr); b.S1.assign(L, nullptr);
-  b.S2.assign(L, nullptr); b.QKV.assign(L, nullptr); b.CAT.assign(L, nullptr);
-  size_t max_n = 0;
-  int max_c = 0;
-  for (int l = 0; l < L; ++l) {
-    size_t n = (size_t)(F >> l) * (T >> l);
-    size_t c = h->C[l];
-    if (n > max_n) max_n = n;
-    if ((int)c > max_c) max_c = (int)c;
-    if (l > 0) b.D[l] = A.alloc<float>(B * n * h->C[l - 1]);
-    b.P[l] = A.alloc<float>(B * n * c);
-    b.Q[l] = A.alloc<float>(B * n * c);
-    b.S1[l] = A.alloc<float>(B * n * c);
-    b.S2[l] = A.alloc<float>(B * n * c);
-    b.QKV[l] = A.alloc<float>(B * n * 3 * kHidden);
-    if (l > 0) b.CAT[l] = A.alloc<float>(B * n * 2 * c);
-  }
-  b.U0 = A.alloc<float>(B * (size_t)F * T * h->C[0]);
-  size_t nch = (max_n + 63) / 64;        // 64-row chunks of the fused to_qkv epilogue (the separate kernel's are 128 rows)
+  const size_t nch = ((size_t)F * T + 63) / 64;        // level 0's 64-row chunks of the fused to_qkv epilogue (the separate kernel's are 128 rows)
   b.part_ctx = A.alloc<float>(B * nch * kHeads * kDimHead * kDimHead);
   b.part_m = A.alloc<float>(B * nch * kHidden);
   b.part_s = A.alloc<float>(B * nch * kHidden);
-  b.ctx = A.alloc<float>(B * kHeads * kDimHead * kDimHead);
-  b.colM = A.alloc<float>(B * kHidden);
-  b.colS = A.alloc<float>(B * kHidden);
   b.ctx_split = A.alloc<float>(attn_merge_scratch_floats(Bp));
   b.splitk_floats = B * ((size_t)4 << 20);  // 4 Mi floats per item: the conv launcher's bound on its split-K slabs
   b.splitk = A.alloc<float>(b.splitk_floats);
-  b.weff = A.alloc<float>(B * (size_t)max_c * kHidden);
-  if (!train) b.wtotal = A.alloc<float>(B * (size_t)kWtotalMaxC * kWtotalMaxC);
-  // Winograd scratch, sized from the convolutions that use it: V holds the conv's input channels and M its output channels;
-  // the data gradient (training plans) swaps the two
+  // Winograd scratch, sized from the convolutions that use it: V holds the conv's input channels and M its output channels
   size_t wv = 0, wm = 0;
   auto need = [&](const ConvW& c, int l) {
     if (!c.w || !c.w->want_wino) return;
@@ -437,12 +490,72 @@ void plan(us_decoder* h, Arena& A, int Bp, int T, Buffers& b, bool train = false
       wm = std::max(wm, f4 * c.cout);
     }
   };
-  auto need_r = [&](const ResnetW& r) { need(r.c1, r.level); need(r.c2, r.level); };
-  for (auto& d : h->downs) { need_r(d.r1); need_r(d.r2); }
-  need_r(h->mid1); need_r(h->mid2);
-  for (auto& u : h->ups) { need_r(u.r1); need_r(u.r2); }
+  for_each_resnet(h, [&](const ResnetW& r) { need(r.c1, r.level); need(r.c2, r.level); });
   need(h->final_conv3, 0);
   if (wv) { b.wino_v = A.alloc<float>(wv); b.wino_m = A.alloc<float>(wm); }
+}
+
+// Inference plan: per-level activations, and a placement table that aliases onto them.  At level l a ResnetBlock works in S1 / S2, r1
+// writes P and r2 writes Q; the down path's attention writes the second half of the level's concat buffer (level 0, whose skip is never
+// popped: P[0]), the up path's P; a Downsample writes D of the level below, an Upsample the first half of the concat buffer above (U0 at the top).
+void plan(us_decoder* h, Arena& A, int Bp, int T, Buffers& b, Places& p) {
+  const int L = h->cfg.n_mults, F = h->cfg.n_feats;
+  const size_t B = (size_t)Bp;
+  init_places(h, A, Bp, p);
+  b.D.assign(L, nullptr); b.P.assign(L, nullptr); b.Q.assign(L, nullptr); b.S1.assign(L, nullptr);
+  b.S2.assign(L, nullptr); b.QKV.assign(L, nullptr);
+  int max_c = 0;
+  for (int l = 0; l < L; ++l) {
+    size_t n = (size_t)(F >> l) * (T >> l);
+    size_t c = h->C[l];
+    if ((int)c > max_c) max_c = (int)c;
+    if (l > 0) b.D[l] = A.alloc<float>(B * n * h->C[l - 1]);
+    b.P[l] = A.alloc<float>(B * n * c);
+    b.Q[l] = A.alloc<float>(B * n * c);
+    b.S1[l] = A.alloc<float>(B * n * c);
+    b.S2[l] = A.alloc<float>(B * n * c);
+    b.QKV[l] = A.alloc<float>(B * n * 3 * kHidden);
+    if (l > 0) p.CAT[l] = A.alloc<float>(B * n * 2 * c);
+  }
+  b.U0 = A.alloc<float>(B * (size_t)F * T * h->C[0]);
+  b.ctx = A.alloc<float>(B * kHeads * kDimHead * kDimHead);
+  b.colM = A.alloc<float>(B * kHidden);
+  b.colS = A.alloc<float>(B * kHidden);
+  b.weff = A.alloc<float>(B * (size_t)max_c * kHidden);
+  b.wtotal = A.alloc<float>(B * (size_t)kWtotalMaxC * kWtotalMaxC);
+  plan_shared(h, A, Bp, T, b, false);
+  auto res = [&](const ResnetW& r, float* out, int out_ld) {
+    ResT& t = p.res[r.index];
+    t.y1 = b.S1[r.level]; t.y2 = b.S2[r.level];
+    t.r_early = b.QKV[r.level];      // the level's attention scratch: free while a ResnetBlock runs
+    t.out = out; t.out_ld = out_ld;
+  };
+  auto att = [&](AttT& t, float* out, int out_ld) {
+    t.qkv = b.QKV[t.w->level]; t.ctx = b.ctx; t.colM = b.colM; t.colS = b.colS; t.weff = b.weff;
+    t.out = out; t.out_ld = out_ld;
+  };
+  for (int l = 0; l < L; ++l) {
+    const int c = h->C[l];
+    res(h->downs[l].r1, b.P[l], c);
+    res(h->downs[l].r2, b.Q[l], c);
+    if (l == 0) att(p.att[0], b.P[0], c);
+    else att(p.att[l], p.CAT[l] + c, 2 * c);
+    if (l < L - 1) { p.downs[l].out = b.D[l + 1]; p.downs[l].out_ld = c; }
+  }
+  const int lm = L - 1, cm = h->C[lm];
+  res(h->mid1, b.P[lm], cm);
+  att(p.att[L], b.Q[lm], cm);
+  if (L > 1) res(h->mid2, p.CAT[lm], 2 * cm);
+  else res(h->mid2, b.P[lm], cm);
+  for (int u = 0; u < L - 1; ++u) {
+    const int l = h->ups[u].r1.level, co = h->ups[u].r1.cout;
+    res(h->ups[u].r1, b.P[l], co);
+    res(h->ups[u].r2, b.Q[l], co);
+    att(p.att[L + 1 + u], b.P[l], co);
+    if (l - 1 >= 1) { p.ups[u].out = p.CAT[l - 1]; p.ups[u].out_ld = 2 * h->C[l - 1]; }
+    else { p.ups[u].out = b.U0; p.ups[u].out_ld = h->C[0]; }
+  }
+  p.fin_y = b.S1[0];
 }
 
 // ---- one estimator evaluation -------------------------------------------------------------------------
@@ -453,15 +566,11 @@ struct EvalCtx {
   int Bp, T;
   const float* mask;   // [Bm][T]
   int Bm;
-  int gn_slot = 0;
   int splitk_by_batch = 0;   // training contexts: see ConvArgs::splitk_by_batch
-  bool infer = false;        // an inference evaluation: the 4-wide Winograd forms (wino4.hip) may serve its 3x3 convolutions
+  // THE mode flag.  true: an inference evaluation, which may use the forms no backward can follow -- the 4-wide Winograd forms (wino4.hip),
+  // two-plane fp16 hand-offs between layers, to_qkv's reduction epilogue and q-folding.  false: a training step (forward or backward)
+  bool infer = false;
 };
-
-double* next_stats(EvalCtx& e) {
-  double* p = e.b->stats + (size_t)(e.gn_slot++) * e.Bp * kGroups * kStatStride;
-  return p;
-}
 
 // frame mask of the OUTPUT tensor (at `level_out` resolution) applied by the epilogue
 void set_omask(EvalCtx& e, ConvArgs& a, int level_out) {
@@ -491,15 +600,24 @@ ConvArgs base_args(EvalCtx& e, const ConvW& w, const float* in, int in_ld, int H
   return a;
 }
 
+// `in` already holds the two-plane fp16 form (its producer stored it with out_split): an f16x3 convolution then skips its in-kernel split
+inline bool take_presplit(ConvArgs& a) {
+  if (a.f16 != 2) return false;
+  a.f16 = 1;
+  a.direct_presplit = 1;
+  return true;
+}
+
 // every implicit-GEMM launch goes through here so the sampled evaluation can bracket it with HIP events
-hipError_t run_conv(EvalCtx& e, const ConvArgs& a) {
+// flops: the launch's count where the geometry in `a` does not give it (wino_conv's GEMM with the output transform inside)
+hipError_t run_conv(EvalCtx& e, const ConvArgs& a, double flops = 0) {
   us_decoder* h = e.h;
   if (!h->prof_active) return launch_conv_igemm(a, e.s);
   us_decoder::ProfRec r;
   r.a = h->prof_event();
   r.b = h->prof_event();
   r.kind = 0;
-  r.flops = 2.0 * a.B * (double)a.Hs * a.Ws * a.Cout * (double)a.Cin * a.ntaps * (a.nphase > 1 ? a.nphase : 1);
+  r.flops = flops > 0 ? flops : 2.0 * a.B * (double)a.Hs * a.Ws * a.Cout * (double)a.Cin * a.ntaps * (a.nphase > 1 ? a.nphase : 1);
   r.f16 = a.f16 ? 1 : 0;
   (void)hipEventRecord(r.a, e.s);
   hipError_t err = launch_conv_igemm(a, e.s);
@@ -521,6 +639,22 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
                      const WinoEpi& ep, const WinoGnArgs* gn = nullptr, bool f16 = false, int form4 = 0, const float* U4 = nullptr) {
   const int H = e.h->cfg.n_feats >> level, W = e.T >> level;
   Buffers& b = *e.b;
+  // one frequency's GEMM M_f = V_f U_f over th x tw tiles per item, K input and N output channels; the caller sets the output side
+  auto gemm_args = [&](const float* Uf, int bkf, bool f16f, int th, int tw) {
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.f16 = f16f ? 1 : 0;
+    a.in = b.wino_v; a.in_ld = K;
+    a.wt = Uf; a.wt_bstride = (long long)N * K;
+    a.Hin = th; a.Win = tw; a.Cin = K; a.Cout = N;
+    a.Hs = th; a.Ws = tw; a.istride = 1;
+    a.bk = bkf;
+    a.omask_bmod = 1;
+    a.zeros = e.h->zeros;
+    a.ntaps = 1;
+    a.set_tap(0, 0, 0, 0);
+    return a;
+  };
   if (form4 && U4 && e.infer && !ep.add && !ep.mask_out && !(gn && gn->h_out) && (!gn || in_ld == K) &&
       (long long)H * W * in_ld * 4 < (1LL << 31) && (long long)H * W * K < (1LL << 30)) {       // (launch_wino4_input's 32-bit offsets; else F(2x2))
     // F(4x4,3x3) / F(2x4,3x3): input transform (+ block1's GroupNorm), one GEMM over all items per frequency, output transform
@@ -529,18 +663,7 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
     const int nf = wino4_freqs(form4);
     hipError_t err4 = launch_wino4_input(form4, in, in_ld, b.wino_v, e.Bp, H, W, K, gn, e.s, e.h->split_store16);
     if (err4 != hipSuccess) return err4;
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.f16 = 1;
-    a.in = b.wino_v; a.in_ld = K;
-    a.wt = U4; a.wt_bstride = (long long)N * K;
-    a.Hin = t4h; a.Win = t4w; a.Cin = K; a.Cout = N;
-    a.Hs = t4h; a.Ws = t4w; a.istride = 1;
-    a.bk = 32;
-    a.omask_bmod = 1;
-    a.zeros = e.h->zeros;
-    a.ntaps = 1;
-    a.set_tap(0, 0, 0, 0);
+    ConvArgs a = gemm_args(U4, 32, true, t4h, t4w);
     a.out = b.wino_m; a.out_ld = N;
     a.B = nf; a.Hin = a.Hs = a.Hout = e.Bp * t4h; a.Wout = t4w; a.ostep = 1;
     a.tm = e.h->f16_tm;
@@ -561,18 +684,7 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
   hipError_t err = gn ? (in_ld == K ? launch_gn_wino_input(in, b.wino_v, e.Bp, H, W, K, *gn, e.s, f16) : hipErrorInvalidValue)
                       : launch_wino_input(in, in_ld, b.wino_v, e.Bp, H, W, K, e.s, f16, e.h->split_store16);
   if (err != hipSuccess) return err;
-  ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.f16 = f16 ? 1 : 0;
-  a.in = b.wino_v; a.in_ld = K;
-  a.wt = U; a.wt_bstride = (long long)N * K;
-  a.Hin = th; a.Win = tw; a.Cin = K; a.Cout = N;
-  a.Hs = th; a.Ws = tw; a.istride = 1;
-  a.bk = bk;
-  a.omask_bmod = 1;
-  a.zeros = e.h->zeros;
-  a.ntaps = 1;
-  a.set_tap(0, 0, 0, 0);
+  ConvArgs a = gemm_args(U, bk, f16, th, tw);
   // Output transform inside the GEMM kernel (one workgroup walks the 16 frequencies of its tile) when that still leaves
   // enough workgroups for the chip; otherwise 16x more, shorter workgroups and a separate transform pass.  Both forms add in
   // the same order, so the choice (which depends on the batch) does not change a single bit of the result.
@@ -590,17 +702,7 @@ hipError_t wino_conv(EvalCtx& e, const float* in, int in_ld, const float* U, int
     a.stats = ep.stats;
     a.add = ep.add; a.add_ld = ep.add_ld;
     if (ep.mask_out) set_omask(e, a, level);
-    us_decoder* h = e.h;
-    if (!h->prof_active) return launch_conv_igemm(a, e.s);
-    us_decoder::ProfRec r;
-    r.a = h->prof_event(); r.b = h->prof_event(); r.kind = 0;
-    r.flops = 2.0 * 16 * e.Bp * (double)th * tw * N * (double)K;
-    r.f16 = a.f16 ? 1 : 0;
-    (void)hipEventRecord(r.a, e.s);
-    err = launch_conv_igemm(a, e.s);
-    (void)hipEventRecord(r.b, e.s);
-    h->prof_pending.push_back(r);
-    return err;
+    return run_conv(e, a, 2.0 * 16 * e.Bp * (double)th * tw * N * (double)K);
   }
   // separate form: the items of one frequency are contiguous in V and in M, and a 1x1 tap never leaves its row, so a frequency's
   // GEMM runs over all Bp * th * tw rows at once (no partial tile per item: a level-3 item has only 320 rows)
@@ -637,11 +739,7 @@ hipError_t conv3x3(EvalCtx& e, const ConvW& w, const float* in, int in_ld, int l
   if (w.w->wino.p && e.b->wino_v) return in_split ? hipErrorInvalidValue : conv3x3_wino(e, w, in, in_ld, level, out, out_ld, stats);
   const int H = e.h->cfg.n_feats >> level, W = e.T >> level;
   ConvArgs a = base_args(e, w, in, in_ld, H, W, out, out_ld, H, W);
-  if (in_split) {
-    if (a.f16 != 2) return hipErrorInvalidValue;
-    a.f16 = 1;
-    a.direct_presplit = 1;
-  }
+  if (in_split && !take_presplit(a)) return hipErrorInvalidValue;
   a.ntaps = 9;
   for (int ky = 0; ky < 3; ++ky)
     for (int kx = 0; kx < 3; ++kx) a.set_tap(ky * 3 + kx, ky - 1, kx - 1, ky * 3 + kx);
@@ -656,11 +754,7 @@ hipError_t conv1x1(EvalCtx& e, const ConvW& w, const float* in, int in_ld, int l
   const int H = e.h->cfg.n_feats >> level, W = e.T >> level;
   ConvArgs a = base_args(e, w, in, in_ld, H, W, out, out_ld, H, W);
   a.out2 = out2; a.out2_ld = out2_ld;
-  if (in_split) {
-    if (a.f16 != 2) return hipErrorInvalidValue;
-    a.f16 = 1;
-    a.direct_presplit = 1;
-  }
+  if (in_split && !take_presplit(a)) return hipErrorInvalidValue;
   a.out_split = out_split ? 1 : 0;
   a.ntaps = 1;
   a.set_tap(0, 0, 0, 0);
@@ -673,11 +767,7 @@ hipError_t conv1x1(EvalCtx& e, const ConvW& w, const float* in, int in_ld, int l
 hipError_t conv_down(EvalCtx& e, const ConvW& w, const float* in, int in_ld, int level, float* out, int out_ld, bool in_split = false) {
   const int H = e.h->cfg.n_feats >> level, W = e.T >> level;
   ConvArgs a = base_args(e, w, in, in_ld, H, W, out, out_ld, H / 2, W / 2);
-  if (in_split) {
-    if (a.f16 != 2) return hipErrorInvalidValue;
-    a.f16 = 1;
-    a.direct_presplit = 1;
-  }
+  if (in_split && !take_presplit(a)) return hipErrorInvalidValue;
   a.ntaps = 9;
   a.istride = 2;
   for (int ky = 0; ky < 3; ++ky)
@@ -695,11 +785,7 @@ hipError_t conv_up(EvalCtx& e, const ConvW& w, const float* in, int in_ld, int l
   static const int DY[2][2] = {{0, -1}, {0, 1}};
   // all four output phases in one launch (ConvArgs::nphase)
   ConvArgs a = base_args(e, w, in, in_ld, H, W, out, out_ld, 2 * H, 2 * W);
-  if (in_split) {
-    if (a.f16 != 2) return hipErrorInvalidValue;
-    a.f16 = 1;
-    a.direct_presplit = 1;
-  }
+  if (in_split && !take_presplit(a)) return hipErrorInvalidValue;
   a.out_split = out_split ? 1 : 0;
   a.Hs = H; a.Ws = W; a.ostep = 2;
   a.ntaps = 4;
@@ -745,68 +831,96 @@ inline bool direct_presplit(EvalCtx& e, const ConvW& w, int C, int tmp_ld) {
   return !(w.w->wino.p && e.b->wino_v) && w.w->direct_f16 && C % 8 == 0 && tmp_ld == C;
 }
 
+// The middle of a ResnetBlock: block1's GroupNorm + Mish + time embedding (pre-masked for block2's `x * mask`, :54) over y1, then block2's
+// convolution into y2.  The activation h1 between them is stored only where the plan keeps it (training: block2's weight gradient reads it).
+hipError_t resnet_mid(EvalCtx& e, ResT& t) {
+  const ResnetW& r = *t.w;
+  const int l = r.level;
+  const float* tproj = e.b->tproj + e.b->tproj_off[r.index];
+  // GroupNorm inside block2's Winograd input transform (one launch and one read of y1 less).  Inference: unless US_WINO_FUSE_GN=0.  Training:
+  // always, the switch being an inference A/B -- except in the first block, whose training form has always been the plain pass
+  const bool fuse_gn = e.infer ? e.h->wino_fuse_gn : !r.first;
+  if (r.c2.w->wino.p && e.b->wino_v && fuse_gn && gn_wino_input_supported(r.cout)) {
+    WinoGnArgs g{};
+    g.stats = t.st1; g.gamma = r.g1->buf.p; g.beta = r.b1->buf.p; g.temb = tproj;
+    g.mask = e.mask; g.mask_ld = e.T; g.mask_step = 1 << l; g.mask_bmod = e.Bm;
+    g.h_out = t.h1;
+    return conv3x3_wino(e, r.c2, t.y1, r.cout, l, t.y2, r.cout, t.st2, &g);
+  }
+  // h1 has ONE consumer in inference, block2's convolution: where that is a direct f16x3 one (level 0), gn_apply writes the two-plane fp16
+  // form into `out`, free until the block's end, and the convolution skips its in-kernel split; otherwise h1 goes in place over y1
+  const bool planes = e.infer && direct_presplit(e, r.c2, r.cout, t.out_ld) && t.out != t.x;
+  float* h1 = t.h1 ? t.h1 : planes ? t.out : t.y1;
+  CK(gn_apply(e, t.y1, l, r.cout, t.st1, r.g1, r.b1, tproj, nullptr, 0, false, true, h1, r.cout, planes));
+  return conv3x3(e, r.c2, h1, r.cout, l, t.y2, r.cout, t.st2, planes);
+}
+
 // ResnetBlock (unitspeech/unitspeech.py:58-75).  `in` must already be masked.  mask_out: the result is only consumed
 // through `x * mask` (next ResnetBlock / concat), so the mask is applied to what is stored; false when the consumer
 // is the attention, which reads the raw tensor (padded frames included, :91).
+// The two-plane fp16 hand-offs (inference only, decided by unet_forward):
 // in_split: `in` is in the two-plane fp16 form (only legal when block1's convolution and res_conv are direct f16x3 convolutions: resnet_takes_split())
 // split_out: the block also stores its result in the two-plane form there (ld = cout), for the next block's `in_copy`;
 // in_copy: the input once more in the two-plane form (ld = cin): block1's direct f16x3 convolution reads it without the in-kernel split
 // while the identity residual keeps reading the fp32 `in` (next_takes_split_copy()).
-hipError_t resnet(EvalCtx& e, const ResnetW& r, const float* in, int in_ld, float* out, int out_ld, bool mask_out, bool in_split = false,
-                  float* split_out = nullptr, const float* in_copy = nullptr) {
-  Buffers& b = *e.b;
+hipError_t resnet(EvalCtx& e, ResT& t, const float* in, int in_ld, bool mask_out, bool in_split = false, float* split_out = nullptr,
+                  const float* in_copy = nullptr) {
+  const ResnetW& r = *t.w;
   const int l = r.level;
-  float* S1 = b.S1[l];
-  float* S2 = b.S2[l];
-  const float* tproj = b.tproj + b.tproj_off[r.index];
-  double* st1 = next_stats(e);
-  double* st2 = next_stats(e);
+  t.x = in; t.x_ld = in_ld;
   if (in_split && !r.has_res) return hipErrorInvalidValue;      // the identity residual would need the fp32 tensor
   if (in_copy && (in_split || r.has_res)) return hipErrorInvalidValue;
-  if (split_out && (out_ld != r.cout || split_out == out)) return hipErrorInvalidValue;
+  if (split_out && (t.out_ld != r.cout || split_out == t.out)) return hipErrorInvalidValue;
   // with a split copy to write, res_conv runs first into a spare buffer and block2's GroupNorm pass -- the last writer then -- adds it
   // (the same two fp32 operands, (conv + bias) + h, as when the convolution's epilogue adds h) and stores both forms
   float* R = nullptr;
   if (split_out && r.has_res) {
-    if (r.cout > 3 * kHidden) return hipErrorInvalidValue;
-    R = b.QKV[l];                                                // the level's attention scratch: free while a ResnetBlock runs
+    if (r.cout > 3 * kHidden || !t.r_early) return hipErrorInvalidValue;
+    R = t.r_early;
     CK(conv1x1(e, r.res, in, in_ld, l, false, R, r.cout, nullptr, 0, nullptr, nullptr, 0, nullptr, in_split));
   }
-  if (in_copy) CK(conv3x3(e, r.c1, in_copy, r.c1.cin, l, S1, r.cout, st1, true));
-  else CK(conv3x3(e, r.c1, in, in_ld, l, S1, r.cout, st1, in_split));
-  if (r.c2.w->wino.p && b.wino_v && e.h->wino_fuse_gn && gn_wino_input_supported(r.cout)) {
-    // block1's GroupNorm + Mish + time embedding (pre-masked for block2's `x * mask`, :54) evaluated inside the Winograd input
-    // transform of block2's conv: h1 is never written
-    WinoGnArgs g{};
-    g.stats = st1; g.gamma = r.g1->buf.p; g.beta = r.b1->buf.p; g.temb = tproj;
-    g.mask = e.mask; g.mask_ld = e.T; g.mask_step = 1 << l; g.mask_bmod = e.Bm;
-    CK(conv3x3_wino(e, r.c2, S1, r.cout, l, S2, r.cout, st2, &g));
-  } else {
-    // block1 output + time embedding, pre-masked for block2's `x * mask` (:54)
-    if (direct_presplit(e, r.c2, r.cout, out_ld) && out != in) {
-      CK(gn_apply(e, S1, l, r.cout, st1, r.g1, r.b1, tproj, nullptr, 0, false, true, out, r.cout, true));      // `out` is free until the end
-      CK(conv3x3(e, r.c2, out, r.cout, l, S2, r.cout, st2, true));
-    } else {
-      CK(gn_apply(e, S1, l, r.cout, st1, r.g1, r.b1, tproj, nullptr, 0, false, true, S1, r.cout));
-      CK(conv3x3(e, r.c2, S1, r.cout, l, S2, r.cout, st2));
-    }
-  }
+  if (in_copy) CK(conv3x3(e, r.c1, in_copy, r.c1.cin, l, t.y1, r.cout, t.st1, true));
+  else CK(conv3x3(e, r.c1, in, in_ld, l, t.y1, r.cout, t.st1, in_split));
+  CK(resnet_mid(e, t));
   if (R) {
-    CK(gn_apply(e, S2, l, r.cout, st2, r.g2, r.b2, nullptr, R, r.cout, false, mask_out, out, out_ld, false, split_out));
+    CK(gn_apply(e, t.y2, l, r.cout, t.st2, r.g2, r.b2, nullptr, R, r.cout, false, mask_out, t.out, t.out_ld, false, split_out));
   } else if (r.has_res) {
-    CK(gn_apply(e, S2, l, r.cout, st2, r.g2, r.b2, nullptr, nullptr, 0, false, false, out, out_ld));
-    CK(conv1x1(e, r.res, in, in_ld, l, mask_out, out, out_ld, out, out_ld, nullptr, nullptr, 0, nullptr, in_split));
+    CK(gn_apply(e, t.y2, l, r.cout, t.st2, r.g2, r.b2, nullptr, nullptr, 0, false, false, t.out, t.out_ld));
+    CK(conv1x1(e, r.res, in, in_ld, l, mask_out, t.out, t.out_ld, t.out, t.out_ld, nullptr, nullptr, 0, nullptr, in_split));
   } else {
-    CK(gn_apply(e, S2, l, r.cout, st2, r.g2, r.b2, nullptr, in, in_ld, false, mask_out, out, out_ld, false, split_out));
+    CK(gn_apply(e, t.y2, l, r.cout, t.st2, r.g2, r.b2, nullptr, in, in_ld, false, mask_out, t.out, t.out_ld, false, split_out));
   }
   return hipSuccess;
+}
+
+// The first ResnetBlock: its 2-channel convolutions (block1's 3x3 and res_conv) run on the direct kernel, from the stacked input.
+// split_out: as in resnet().  What differs between the plans is only what becomes of res_conv's output r0.
+hipError_t resnet_first(EvalCtx& e, ResT& t, float* split_out) {
+  const ResnetW& r = *t.w;
+  const int F = e.h->cfg.n_feats, c = r.cout;
+  t.x = e.b->in2; t.x_ld = 2;
+  CK(launch_first_conv(e.b->in2, r.c1.w->buf.p, r.c1.b->buf.p, r.res.w->buf.p, r.res.b->buf.p, t.y1, t.r0, t.st1, e.Bp, F, e.T, c, e.s));
+  CK(resnet_mid(e, t));
+  // kept (training: the backward's res_conv gradients want the stored sum's operands): the ordinary GroupNorm pass adds it
+  if (t.r0) return gn_apply(e, t.y2, 0, c, t.st2, r.g2, r.b2, nullptr, t.r0, c, false, true, t.out, t.out_ld);
+  // not kept: block2's GroupNorm pass re-evaluates the 1x1 res_conv from the two input channels
+  GnApplyArgs ga;
+  memset(&ga, 0, sizeof ga);
+  ga.y = t.y2; ga.y_ld = c; ga.stats = t.st2; ga.gamma = r.g2->buf.p; ga.beta = r.b2->buf.p;
+  ga.mask = e.mask; ga.mask_ld = e.T; ga.mask_step = 1; ga.mask_bmod = e.Bm;
+  ga.res2_in = e.b->in2; ga.res2_w = r.res.w->buf.p; ga.res2_b = r.res.b->buf.p;
+  ga.post_mask = 1;
+  ga.store16 = e.h->split_store16 ? 1 : 0;
+  ga.out = t.out; ga.out_ld = t.out_ld;
+  if (split_out) { ga.out2 = split_out; ga.out2_ld = c; }
+  ga.B = e.Bp; ga.H = F; ga.W = e.T; ga.C = c;
+  return launch_gn_apply(ga, e.s);
 }
 
 // r2 of a level takes its input (r1's output) a second time in the two-plane form when its block1 convolution is a direct f16x3 one and
 // it has no res_conv (the identity residual reads the fp32 copy); the copy lives in r2's own output buffer, which is free until its end
 inline bool next_takes_split_copy(EvalCtx& e, const ResnetW& r2) {
-  return !e.h->exact && !r2.has_res && !r2.first && direct_presplit(e, r2.c1, r2.c1.cin, r2.c1.cin) &&
-         r2.c1.cin == r2.cout;
+  return !r2.has_res && !r2.first && direct_presplit(e, r2.c1, r2.c1.cin, r2.c1.cin) && r2.c1.cin == r2.cout;
 }
 
 // a ResnetBlock whose two readers of its input (block1's 3x3, res_conv) are both direct f16x3 convolutions can take that input pre-split
@@ -816,22 +930,23 @@ inline bool resnet_takes_split(EvalCtx& e, const ResnetW& r) {
 
 // Residual(Rezero(LinearAttention)) (unitspeech/unitspeech.py:78-106)
 // out_split: store the result in the two-plane fp16 form (every consumer is a direct f16x3 convolution)
-hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, float* out, int out_ld, bool out_split = false) {
+hipError_t attention(EvalCtx& e, AttT& t, const float* in, int in_ld, bool out_split = false) {
+  const AttnW& at = *t.w;
   Buffers& b = *e.b;
+  t.x = in; t.x_ld = in_ld;
   const int l = at.level;
-  const int n = (e.h->cfg.n_feats >> l) * (e.T >> l);
-  const int nch = attn_nchunks(n);
-  float* qkv = b.QKV[l];
-  int q_ld = 3 * kHidden;
-  int nparts = nch;
+  const int H = e.h->cfg.n_feats >> l, W = e.T >> l, n = H * W;
+  const int nch64 = (n + 63) / 64;
+  const bool f16 = !e.h->exact;
+  // to_qkv with the n-reduction in its epilogue (ConvArgs::attn_part_ctx, chunks of 64 rows) stores q at most: inference only, the backward
+  // reads q, k and v
+  const bool qkv_epilogue = e.infer && at.qkv.w->qkv_rows.p;
   // (measured at B = 1: level 0 only +0.9 %; level 0 and the 128-channel up level +0.6 %; levels 0-1 incl. the 256-channel one +0.0 %)
-  if (at.qkv.w->qkv_rows.p && at.qkv.w->q_raw.p && b.wtotal && l == 0 && at.dim <= kWtotalMaxC && at.dim % 32 == 0) {
+  if (qkv_epilogue && at.qkv.w->q_raw.p && b.wtotal && l == 0 && at.dim <= kWtotalMaxC && at.dim % 32 == 0) {
     // q folded away: to_qkv computes k | v only, for the n-reduction in its epilogue, and stores nothing; then
     // out = x + g (W_total x + b_o), W_total[b] = W_out blockdiag(ctx[b]^T) W_q: a C x C projection of x per item instead of q = W_q x written
     // ([n][128]), read back and projected with K = 128 (a third less to_qkv work and 2 * n * 128 floats less traffic; worth it where C <= 256)
-    const int H = e.h->cfg.n_feats >> l, W = e.T >> l;
-    const int nch64 = (n + 63) / 64;
-    ConvArgs a = base_args(e, at.qkv, in, in_ld, H, W, qkv, kHidden, H, W);
+    ConvArgs a = base_args(e, at.qkv, in, in_ld, H, W, t.qkv, kHidden, H, W);
     a.Cout = 2 * kHidden;
     a.wt_rows = 3 * kHidden;
     // rows kHidden.. of every K-chunk of the qkv_src_row-ordered pack (per head k_h | v_h)
@@ -841,25 +956,24 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
     a.attn_part_ctx = b.part_ctx; a.attn_part_m = b.part_m; a.attn_part_s = b.part_s; a.attn_nchunks = nch64;
     a.attn_q_cols = 0;
     CK(run_conv(e, a));
-    const bool f16 = !e.h->exact;
-    CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nch64, b.ctx, b.colM, b.colS, b.ctx_split, at.out_w->buf.p, nullptr, at.dim,
+    CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nch64, t.ctx, t.colM, t.colS, b.ctx_split, at.out_w->buf.p, nullptr, at.dim,
                          pick_bk(kHidden), f16, e.s));
     const int bkc = pick_bk(at.dim);
-    CK(launch_attn_wtotal(b.ctx, at.out_w->buf.p, at.qkv.w->q_raw.p, b.wtotal, e.Bp, at.dim, bkc, f16, e.s));
+    CK(launch_attn_wtotal(t.ctx, at.out_w->buf.p, at.qkv.w->q_raw.p, b.wtotal, e.Bp, at.dim, bkc, f16, e.s));
     ConvW tot;
     tot.cin = at.dim; tot.cout = at.dim;
     Slot tmp;             // only .bk / .buf / .direct_f16 are read by base_args
     tmp.bk = bkc; tmp.buf.p = b.wtotal; tmp.direct_f16 = f16;
     tot.w = &tmp; tot.b = nullptr;
-    return conv1x1(e, tot, in, in_ld, l, true, out, out_ld, in, in_ld, at.g->buf.p, b.wtotal, (long long)at.dim * at.dim, at.out_b->buf.p,
+    return conv1x1(e, tot, in, in_ld, l, true, t.out, t.out_ld, in, in_ld, at.g->buf.p, b.wtotal, (long long)at.dim * at.dim, at.out_b->buf.p,
                    false, out_split);
   }
-  if (at.qkv.w->qkv_rows.p) {
-    // to_qkv with the n-reduction in its epilogue: only q is written ([n][128]); chunks of 64 rows (ConvArgs::attn_part_ctx)
-    const int H = e.h->cfg.n_feats >> l, W = e.T >> l;
-    const int nch64 = (n + 63) / 64;
+  int q_ld = 3 * kHidden, nparts = attn_nchunks(n);
+  if (qkv_epilogue) {
+    // only q is written ([n][128])
     q_ld = kHidden;
-    ConvArgs a = base_args(e, at.qkv, in, in_ld, H, W, qkv, q_ld, H, W);
+    nparts = nch64;
+    ConvArgs a = base_args(e, at.qkv, in, in_ld, H, W, t.qkv, q_ld, H, W);
     a.wt = at.qkv.w->qkv_rows.p;
     a.ntaps = 1;
     a.set_tap(0, 0, 0, 0);
@@ -867,24 +981,22 @@ hipError_t attention(EvalCtx& e, const AttnW& at, const float* in, int in_ld, fl
     a.attn_q_cols = kHidden;
     // (q stays fp32: storing it pre-split for the folded to_out convolution below measured -0.4 %, K = 128 is not split-bound)
     CK(run_conv(e, a));
-    nparts = nch64;
   } else {
-    CK(conv1x1(e, at.qkv, in, in_ld, l, false, qkv, 3 * kHidden, nullptr, 0, nullptr, nullptr, 0, nullptr));
-    CK(launch_attn_ctx_partial(qkv, e.Bp, n, b.part_ctx, b.part_m, b.part_s, nch, e.s));
+    CK(conv1x1(e, at.qkv, in, in_ld, l, false, t.qkv, 3 * kHidden, nullptr, 0, nullptr, nullptr, 0, nullptr));
+    CK(launch_attn_ctx_partial(t.qkv, e.Bp, n, b.part_ctx, b.part_m, b.part_s, nparts, e.s));
   }
   const int bk = pick_bk(kHidden);
-  const bool f16 = !e.h->exact;
   // chunk partials -> ctx (+ the softmax statistics) -> W_eff = W_out blockdiag(ctx^T), two launches
-  CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nparts, b.ctx, b.colM, b.colS, b.ctx_split, at.out_w->buf.p, b.weff, at.dim, bk,
+  CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nparts, t.ctx, t.colM, t.colS, b.ctx_split, at.out_w->buf.p, t.weff, at.dim, bk,
                        f16, e.s));
   ConvW eff;
   eff.cin = kHidden; eff.cout = at.dim;
   Slot tmp;             // only .bk / .buf / .direct_f16 are read by base_args
-  tmp.bk = bk; tmp.buf.p = b.weff; tmp.direct_f16 = f16;
+  tmp.bk = bk; tmp.buf.p = t.weff; tmp.direct_f16 = f16;
   eff.w = &tmp; eff.b = nullptr;
   // every consumer of an attention output masks it (Downsample / Upsample input, skip concat, mid blocks)
-  return conv1x1(e, eff, qkv, q_ld, l, true, out, out_ld, in, in_ld, at.g->buf.p, b.weff, (long long)at.dim * kHidden,
-                 at.out_b->buf.p, false, out_split);
+  return conv1x1(e, eff, t.qkv, q_ld, l, true, t.out, t.out_ld, in, in_ld, at.g->buf.p, t.weff, (long long)at.dim * kHidden,
+                 at.out_b->buf.p, false, out_split, t.o_pre, t.o_pre ? at.dim : 0);
 }
 
 int upload_bytes(us_decoder* h, const void* src, size_t nbytes, void* dev, hipStream_t st);
@@ -902,20 +1014,26 @@ inline int proj_jobs(us_decoder* h, std::vector<LinJob>& jobs, std::vector<const
     blocks.push_back(&r);
     o0 += r.cout;
   };
-  for (auto& d : h->downs) { add(d.r1); add(d.r2); }
-  add(h->mid1); add(h->mid2);
-  for (auto& u : h->ups) { add(u.r1); add(u.r2); }
+  for_each_resnet(h, add);
   return o0;
+}
+
+// temb = cat(mlp(SinusoidalPosEmb(t)), spk) for `rows` time values (unitspeech.py:165-168); spk: [spk_rows][S], repeated down the rows
+// (null: the time half only)
+hipError_t temb_chain(us_decoder* h, const float* t, int rows, const float* spk, int spk_rows, float* posemb, float* mlp_h, float* temb,
+                      hipStream_t s) {
+  const int dim = h->cfg.dim, S = h->cfg.spk_emb_dim, td = dim + S;
+  CK(launch_pos_emb(t, posemb, rows, dim, h->cfg.pe_scale, s));
+  CK(launch_linear(posemb, dim, h->mlp0_w->buf.p, h->mlp0_b->buf.p, mlp_h, 4 * dim, rows, dim, 4 * dim, false, s));
+  CK(launch_linear(mlp_h, 4 * dim, h->mlp2_w->buf.p, h->mlp2_b->buf.p, temb, td, rows, 4 * dim, dim, true, s));
+  return spk ? launch_copy_rows(spk, S, spk_rows, temb + dim, td, rows, S, s) : hipSuccess;
 }
 
 hipError_t time_embedding(EvalCtx& e, const float* t, const float* spk) {
   us_decoder* h = e.h;
   Buffers& b = *e.b;
-  const int dim = h->cfg.dim, S = h->cfg.spk_emb_dim, td = dim + S;
-  CK(launch_pos_emb(t, b.posemb, e.Bp, dim, h->cfg.pe_scale, e.s));
-  CK(launch_linear(b.posemb, dim, h->mlp0_w->buf.p, h->mlp0_b->buf.p, b.mlp_h, 4 * dim, e.Bp, dim, 4 * dim, false, e.s));
-  CK(launch_linear(b.mlp_h, 4 * dim, h->mlp2_w->buf.p, h->mlp2_b->buf.p, b.temb, td, e.Bp, 4 * dim, dim, true, e.s));
-  CK(launch_copy_rows(spk, S, e.Bp, b.temb + dim, td, e.Bp, S, e.s));
+  const int td = h->cfg.dim + h->cfg.spk_emb_dim;
+  CK(temb_chain(h, t, e.Bp, spk, e.Bp, b.posemb, b.mlp_h, b.temb, e.s));
   // the 22 projections mlp(temb) of the ResnetBlocks (unitspeech.py:61,72) share their input: one launch from a job table
   std::vector<LinJob> jobs;
   std::vector<const ResnetW*> blocks;
@@ -925,60 +1043,34 @@ hipError_t time_embedding(EvalCtx& e, const float* t, const float* spk) {
     if (upload_bytes(h, jobs.data(), jobs.size() * sizeof(LinJob), h->lin_tab_dev, e.s) != US_OK) return hipErrorUnknown;
     return launch_linear_multi(h->lin_tab_dev, (int)jobs.size(), total, b.temb, td, e.Bp, td, true, e.s);
   }
-  auto proj = [&](const ResnetW& r) {
+  return for_each_resnet(h, [&](const ResnetW& r) {
     return launch_linear(b.temb, td, r.mlp_w->buf.p, r.mlp_b->buf.p, b.tproj + b.tproj_off[r.index], r.cout, e.Bp, td, r.cout, true,
                          e.s);
-  };
-  for (auto& d : h->downs) { CK(proj(d.r1)); CK(proj(d.r2)); }
-  CK(proj(h->mid1)); CK(proj(h->mid2));
-  for (auto& u : h->ups) { CK(proj(u.r1)); CK(proj(u.r2)); }
-  return hipSuccess;
+  });
 }
 
-// x: [Bx][F][T]; mu: [Bmu][F][T]; items b' < n_text_uncond use text_uncon instead of mu; spk: [Bp][S]; t: [Bp]
-hipError_t estimator_eval_impl(EvalCtx& e, const float* x, int Bx, const float* mu, int Bmu, int n_text_uncond, const float* t,
-                               const float* spk, float* out);
-
-// `sample` marks the evaluation whose launches are bracketed with events when profiling is enabled
-hipError_t estimator_eval(EvalCtx& e, const float* x, int Bx, const float* mu, int Bmu, int n_text_uncond, const float* t,
-                          const float* spk, float* out, bool sample = false) {
-  us_decoder* h = e.h;
-  if (!(h->prof_enabled && sample)) return estimator_eval_impl(e, x, Bx, mu, Bmu, n_text_uncond, t, spk, out);
-  us_decoder::ProfRec r;
-  r.a = h->prof_event();
-  r.b = h->prof_event();
-  r.kind = 1;
-  r.flops = 0;
-  (void)hipEventRecord(r.a, e.s);
-  h->prof_active = true;
-  hipError_t err = estimator_eval_impl(e, x, Bx, mu, Bmu, n_text_uncond, t, spk, out);
-  h->prof_active = false;
-  (void)hipEventRecord(r.b, e.s);
-  h->prof_pending.push_back(r);
-  return err;
-}
-
-hipError_t estimator_eval_impl(EvalCtx& e, const float* x, int Bx, const float* mu, int Bmu, int n_text_uncond, const float* t,
-                               const float* spk, float* out) {
+// The U-Net of `GradLogPEstimator2d.forward` (unitspeech.py:170-201) over a placement table: every launch of an inference evaluation
+// and of a training forward between the time embedding and the result.
+// x: [Bx][F][T]; mu: [Bmu][F][T]; items b' < n_text_uncond use text_uncon instead of mu; out: [Bp][F][T]
+hipError_t unet_forward(EvalCtx& e, Places& p, const float* x, int Bx, const float* mu, int Bmu, int n_text_uncond, float* out) {
   us_decoder* h = e.h;
   Buffers& b = *e.b;
   const int L = h->cfg.n_mults, F = h->cfg.n_feats, T = e.T;
-  e.gn_slot = 0;
-  CK(hipMemsetAsync(b.stats, 0, b.stats_count * sizeof(double), e.s));
-  if (!b.tproj_ready) CK(time_embedding(e, t, spk));
   CK(launch_stack_inputs(x, Bx, mu, Bmu, n_text_uncond, h->text_uncon->buf.p, e.mask, e.Bm, b.in2, e.Bp, F, T, e.s));
 
   // Tensors that only direct f16x3 convolutions read are stored in the two-plane fp16 form by their producer's epilogue (no split work
-  // in the consumers, which then run the 128-row tile):
+  // in the consumers, which then run the 128-row tile).  Inference only: a training step keeps every tensor in fp32 for its backward.
   //   hid_split[l]  level l's attention output.  Level 0: its one reader is the Downsample (the level-0 skip is never popped,
   //                 unitspeech.py:180,190-192).  Deeper: the Downsample plus the up path's first ResnetBlock (the concat's second half),
   //                 which qualifies where that block runs direct (resnet_takes_split: the narrow last up level); the concat's first
   //                 half, the Upsample output of the level below, is then stored the same way.
   //   up_split[l]   the up path's attention output at level l: its one reader is the Upsample.
   //   fin_split     the last Upsample's output: its one reader is the final Block's convolution.
+  //   r2_copy       r1's output once more, for r2's block1 (next_takes_split_copy)
+  const bool planes = e.infer && !h->exact;
   std::vector<char> hid_split(L, 0), up_split(L, 0);
   bool fin_split = false;
-  if (!h->exact) {
+  if (planes) {
     for (int l = 0; l < L; ++l) {
       auto& d = h->downs[l];
       if (!d.has_ds || !d.ds.conv.w->direct_f16 || h->C[l] % 8 != 0) continue;
@@ -988,90 +1080,79 @@ hipError_t estimator_eval_impl(EvalCtx& e, const float* x, int Bx, const float* 
     for (int u = 0; u < L - 1; ++u) up_split[h->ups[u].r1.level] = h->ups[u].us.conv.w->direct_f16 ? 1 : 0;
     fin_split = L > 1 && !(h->final_conv3.w->wino.p && b.wino_v) && h->final_conv3.w->direct_f16 && h->ups[L - 2].us.conv.w->direct_f16;
   }
+  // r1, r2 and the attention of one level; `cat_split`: r1 reads the concat buffer in the two-plane form.  Returns the attention's entry
+  auto level = [&](const ResnetW& w1, const ResnetW& w2, AttT& at, const float* in, int in_ld, bool cat_split, bool att_split) {
+    ResT &r1 = p.res[w1.index], &r2 = p.res[w2.index];
+    float* copy = planes && next_takes_split_copy(e, w2) ? r2.out : nullptr;
+    CK(w1.first ? resnet_first(e, r1, copy) : resnet(e, r1, in, in_ld, true, cat_split, copy));
+    CK(resnet(e, r2, r1.out, r1.out_ld, false, false, nullptr, copy));
+    return attention(e, at, r2.out, r2.out_ld, att_split);
+  };
   const float* cur = nullptr;
   int cur_ld = 0;
   for (int l = 0; l < L; ++l) {
     auto& d = h->downs[l];
-    const int c = h->C[l];
-    const bool r2_copy = next_takes_split_copy(e, d.r2);
-    if (l == 0) {
-      // first ResnetBlock: 2-channel convs on the direct kernel
-      const ResnetW& r = d.r1;
-      double* st1 = next_stats(e);
-      double* st2 = next_stats(e);
-      // (the block's 1x1 res_conv output is not stored: its GroupNorm pass below re-evaluates it from the two input channels)
-      CK(launch_first_conv(b.in2, r.c1.w->buf.p, r.c1.b->buf.p, r.res.w->buf.p, r.res.b->buf.p, b.S1[0], nullptr, st1, e.Bp, F, T, c, e.s));
-      if (r.c2.w->wino.p && b.wino_v && h->wino_fuse_gn && gn_wino_input_supported(c)) {
-        WinoGnArgs g{};     // as in resnet(): block1's GroupNorm + Mish + time embedding inside block2's input transform
-        g.stats = st1; g.gamma = r.g1->buf.p; g.beta = r.b1->buf.p; g.temb = b.tproj + b.tproj_off[r.index];
-        g.mask = e.mask; g.mask_ld = e.T; g.mask_step = 1; g.mask_bmod = e.Bm;
-        CK(conv3x3_wino(e, r.c2, b.S1[0], c, 0, b.S2[0], c, st2, &g));
-      } else {
-        if (direct_presplit(e, r.c2, c, c)) {      // as in resnet(): P[0], this block's output buffer, holds the two-plane form meanwhile
-          CK(gn_apply(e, b.S1[0], 0, c, st1, r.g1, r.b1, b.tproj + b.tproj_off[r.index], nullptr, 0, false, true, b.P[0], c, true));
-          CK(conv3x3(e, r.c2, b.P[0], c, 0, b.S2[0], c, st2, true));
-        } else {
-          CK(gn_apply(e, b.S1[0], 0, c, st1, r.g1, r.b1, b.tproj + b.tproj_off[r.index], nullptr, 0, false, true, b.S1[0], c));
-          CK(conv3x3(e, r.c2, b.S1[0], c, 0, b.S2[0], c, st2));
-        }
-      }
-      {
-        GnApplyArgs ga;
-        memset(&ga, 0, sizeof ga);
-        ga.y = b.S2[0]; ga.y_ld = c; ga.stats = st2; ga.gamma = r.g2->buf.p; ga.beta = r.b2->buf.p;
-        ga.mask = e.mask; ga.mask_ld = e.T; ga.mask_step = 1; ga.mask_bmod = e.Bm;
-        ga.res2_in = b.in2; ga.res2_w = r.res.w->buf.p; ga.res2_b = r.res.b->buf.p;
-        ga.post_mask = 1;
-        ga.store16 = e.h->split_store16 ? 1 : 0;
-        ga.out = b.P[0]; ga.out_ld = c;
-        if (r2_copy) { ga.out2 = b.Q[0]; ga.out2_ld = c; }
-        ga.B = e.Bp; ga.H = F; ga.W = T; ga.C = c;
-        CK(launch_gn_apply(ga, e.s));
-      }
-    } else {
-      CK(resnet(e, d.r1, cur, cur_ld, b.P[l], c, true, false, r2_copy ? b.Q[l] : nullptr));
-    }
-    CK(resnet(e, d.r2, b.P[l], c, b.Q[l], c, false, false, nullptr, r2_copy ? b.Q[l] : nullptr));
-    float* hid = l == 0 ? b.P[0] : b.CAT[l] + c;
-    int hid_ld = l == 0 ? c : 2 * c;
-    CK(attention(e, d.a, b.Q[l], c, hid, hid_ld, hid_split[l]));
+    AttT& at = p.att[l];
+    CK(level(d.r1, d.r2, at, cur, cur_ld, false, hid_split[l]));
+    cur = at.out; cur_ld = at.out_ld;
     if (d.has_ds) {
-      CK(conv_down(e, d.ds.conv, hid, hid_ld, l, b.D[l + 1], c, hid_split[l]));
-      cur = b.D[l + 1];
-      cur_ld = c;
-    } else {
-      cur = hid;
-      cur_ld = hid_ld;
+      CvT& c = p.downs[l];
+      c.x = cur; c.x_ld = cur_ld;
+      CK(conv_down(e, *c.w, cur, cur_ld, l, c.out, c.out_ld, hid_split[l]));
+      cur = c.out; cur_ld = c.out_ld;
     }
   }
-  const int lm = L - 1, cm = h->C[lm];
-  CK(resnet(e, h->mid1, cur, cur_ld, b.P[lm], cm, false));
-  CK(attention(e, h->mid_attn, b.P[lm], cm, b.Q[lm], cm));
-  float* xcat = L > 1 ? b.CAT[lm] : b.P[lm];
-  CK(resnet(e, h->mid2, b.Q[lm], cm, xcat, L > 1 ? 2 * cm : cm, true));
-  const float* fin = xcat;
-  int fin_ld = cm;
+  ResT &m1 = p.res[h->mid1.index], &m2 = p.res[h->mid2.index];
+  CK(resnet(e, m1, cur, cur_ld, false));
+  CK(attention(e, p.att[L], m1.out, m1.out_ld));
+  CK(resnet(e, m2, p.att[L].out, p.att[L].out_ld, true));       // into the first half of the deepest concat buffer (L == 1: a buffer of its own)
+  const float* fin = m2.out;
+  int fin_ld = m2.out_ld;
   for (int u = 0; u < L - 1; ++u) {
     auto& up = h->ups[u];
-    const int l = up.r1.level, co = up.r1.cout;
-    const bool r2_copy = next_takes_split_copy(e, up.r2);
-    CK(resnet(e, up.r1, b.CAT[l], 2 * h->C[l], b.P[l], co, true, l <= L - 2 && hid_split[l], r2_copy ? b.Q[l] : nullptr));
-    CK(resnet(e, up.r2, b.P[l], co, b.Q[l], co, false, false, nullptr, r2_copy ? b.Q[l] : nullptr));
-    CK(attention(e, up.a, b.Q[l], co, b.P[l], co, up_split[l]));
-    float* dst = (l - 1 >= 1) ? b.CAT[l - 1] : b.U0;
-    int dst_ld = (l - 1 >= 1) ? 2 * h->C[l - 1] : h->C[0];
-    CK(conv_up(e, up.us.conv, b.P[l], co, l, dst, dst_ld, up_split[l], (l - 1 >= 1) ? hid_split[l - 1] != 0 : fin_split));
-    fin = dst;
-    fin_ld = dst_ld;
+    const int l = up.r1.level;
+    AttT& at = p.att[L + 1 + u];
+    CK(level(up.r1, up.r2, at, p.CAT[l], 2 * h->C[l], l <= L - 2 && hid_split[l], up_split[l]));
+    CvT& c = p.ups[u];
+    c.x = at.out; c.x_ld = at.out_ld;
+    CK(conv_up(e, *c.w, at.out, at.out_ld, l, c.out, c.out_ld, up_split[l], (l - 1 >= 1) ? hid_split[l - 1] != 0 : fin_split));
+    fin = c.out; fin_ld = c.out_ld;
   }
   // final Block + 1x1 projection (unitspeech/unitspeech.py:198-201)
-  double* stf = next_stats(e);
   const int c0 = h->C[0];
-  CK(conv3x3(e, h->final_conv3, fin, fin_ld, 0, b.S1[0], c0, stf, fin_split));
-  // GroupNorm + Mish + mask inside the 1x1 projection: the normalised tensor is never stored
-  CK(launch_final_conv(b.S1[0], c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s, stf,
-                       h->final_g->buf.p, h->final_b->buf.p));
-  return hipSuccess;
+  p.fin_x = fin; p.fin_ld = fin_ld;
+  CK(conv3x3(e, h->final_conv3, fin, fin_ld, 0, p.fin_y, c0, p.fin_st, fin_split));
+  // fin_h not kept: GroupNorm + Mish + mask inside the 1x1 projection, the normalised tensor is never stored
+  if (!p.fin_h)
+    return launch_final_conv(p.fin_y, c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s, p.fin_st,
+                             h->final_g->buf.p, h->final_b->buf.p);
+  CK(gn_apply(e, p.fin_y, 0, c0, p.fin_st, h->final_g, h->final_b, nullptr, nullptr, 0, false, false, p.fin_h, c0));
+  return launch_final_conv(p.fin_h, c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s);
+}
+
+// One inference evaluation.  t: [Bp], spk: [Bp][S] (unused when the sampler has the time projections ready).
+// `sample` marks the evaluation whose launches are bracketed with events when profiling is enabled
+hipError_t estimator_eval(EvalCtx& e, Places& p, const float* x, int Bx, const float* mu, int Bmu, int n_text_uncond, const float* t,
+                          const float* spk, float* out, bool sample = false) {
+  us_decoder* h = e.h;
+  auto run = [&]() -> hipError_t {
+    CK(hipMemsetAsync(p.stats, 0, p.stats_count * sizeof(double), e.s));
+    if (!e.b->tproj_ready) CK(time_embedding(e, t, spk));
+    return unet_forward(e, p, x, Bx, mu, Bmu, n_text_uncond, out);
+  };
+  if (!(h->prof_enabled && sample)) return run();
+  us_decoder::ProfRec r;
+  r.a = h->prof_event();
+  r.b = h->prof_event();
+  r.kind = 1;
+  r.flops = 0;
+  (void)hipEventRecord(r.a, e.s);
+  h->prof_active = true;
+  hipError_t err = run();
+  h->prof_active = false;
+  (void)hipEventRecord(r.b, e.s);
+  h->prof_pending.push_back(r);
+  return err;
 }
 
 // ---- time / speaker projections for a block of diffusion steps ------------------------------------------------
@@ -1081,9 +1162,7 @@ constexpr int kTimeBlock = 64;
 
 inline size_t sum_res_cout(us_decoder* h) {
   size_t c = 0;
-  for (auto& d : h->downs) c += d.r1.cout + d.r2.cout;
-  c += h->mid1.cout + h->mid2.cout;
-  for (auto& u : h->ups) c += u.r1.cout + u.r2.cout;
+  for_each_resnet(h, [&](const ResnetW& r) { c += r.cout; });
   return c;
 }
 inline size_t time_block_floats(us_decoder* h, int Bp) {
@@ -1107,21 +1186,14 @@ inline void plan_time_block(us_decoder* h, Arena& A, int Bp, TimeBlock& tb) {
 // starting at ns * tproj_off[r] (tproj_off from plan()): step i's rows sit at + (i-i0)*Bp*cout_r.
 inline hipError_t compute_time_block(EvalCtx& e, TimeBlock& tb, const float* coef_host, int i0, int ns, const float* spk_cfg) {
   us_decoder* h = e.h;
-  const int dim = h->cfg.dim, S = h->cfg.spk_emb_dim, td = dim + S;
+  const int td = h->cfg.dim + h->cfg.spk_emb_dim;
   const int rows = ns * e.Bp;
   for (int i = 0; i < ns; ++i) CK(launch_fill(tb.t_all + (size_t)i * e.Bp, coef_host[(size_t)(i0 + i) * 8 + 6], e.Bp, e.s));
-  CK(launch_pos_emb(tb.t_all, tb.posemb, rows, dim, h->cfg.pe_scale, e.s));
-  CK(launch_linear(tb.posemb, dim, h->mlp0_w->buf.p, h->mlp0_b->buf.p, tb.mlp_h, 4 * dim, rows, dim, 4 * dim, false, e.s));
-  CK(launch_linear(tb.mlp_h, 4 * dim, h->mlp2_w->buf.p, h->mlp2_b->buf.p, tb.temb, td, rows, 4 * dim, dim, true, e.s));
-  CK(launch_copy_rows(spk_cfg, S, e.Bp, tb.temb + dim, td, rows, S, e.s));
-  auto proj = [&](const ResnetW& r) {
+  CK(temb_chain(h, tb.t_all, rows, spk_cfg, e.Bp, tb.posemb, tb.mlp_h, tb.temb, e.s));
+  return for_each_resnet(h, [&](const ResnetW& r) {
     return launch_linear(tb.temb, td, r.mlp_w->buf.p, r.mlp_b->buf.p, tb.tproj + (size_t)ns * e.b->tproj_off[r.index], r.cout, rows, td,
                          r.cout, true, e.s);
-  };
-  for (auto& d : h->downs) { CK(proj(d.r1)); CK(proj(d.r2)); }
-  CK(proj(h->mid1)); CK(proj(h->mid2));
-  for (auto& u : h->ups) { CK(proj(u.r1)); CK(proj(u.r2)); }
-  return hipSuccess;
+  });
 }
 
 #include "train_host.inc"
@@ -1485,7 +1557,8 @@ size_t us_workspace_bytes(us_handle h, int Bp, int T) {
   if (!h || Bp <= 0 || T <= 0) return 0;
   Arena A(nullptr, 0);
   Buffers b;
-  plan(h, A, Bp, T, b);
+  Places pl;
+  plan(h, A, Bp, T, b, pl);
   return A.off + 256;
 }
 
@@ -1510,11 +1583,12 @@ int us_estimator_forward(us_handle h, const float* x, const float* mask, const f
     return h->fail(US_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, us_workspace_bytes(h, Bp, T));
   Arena A(workspace, workspace_bytes);
   Buffers b;
-  plan(h, A, Bp, T, b);
+  Places pl;
+  plan(h, A, Bp, T, b, pl);
   EvalCtx e{h, static_cast<hipStream_t>(stream), &b, Bp, T, mask, Bp};
   e.infer = true;
   RangeScope range_scope(h->range_flag);
-  US_HIP(h, estimator_eval(e, x, Bp, mu, Bp, 0, t, spk, out, true));
+  US_HIP(h, estimator_eval(e, pl, x, Bp, mu, Bp, 0, t, spk, out, true));
   return US_OK;
 }
 
@@ -1615,6 +1689,7 @@ int us_reverse_diffusion(us_handle h, const float* z, const float* mask, const f
   TimeBlock tblock;
   plan_time_block(h, A, mbs * n_cfg, tblock);
   Buffers bufs;
+  Places places;
   const size_t est_off = (A.off + 255) & ~size_t(255);
   if (use_s) US_HIP(h, launch_l2_normalize(h->spk_uncon->buf.p, spk_un, S, s));     // :358
 
@@ -1622,7 +1697,7 @@ int us_reverse_diffusion(us_handle h, const float* z, const float* mask, const f
     const int mb = (B - b0) < mbs ? (B - b0) : mbs;
     const int Bp = mb * n_cfg;
     Arena AE(static_cast<char*>(workspace) + est_off, workspace_bytes - est_off);
-    plan(h, AE, Bp, T, bufs);
+    plan(h, AE, Bp, T, bufs, places);
     const float* z_b = z + (size_t)b0 * FT;
     const float* cond_b = cond + (size_t)b0 * FT;
     const float* mask_b = mask + (size_t)b0 * T;
@@ -1638,9 +1713,7 @@ int us_reverse_diffusion(us_handle h, const float* z, const float* mask, const f
     e.infer = true;
     const std::vector<size_t> base_off = bufs.tproj_off;     // per-resnet offsets of ONE evaluation (plan())
     std::vector<int> couts(h->n_resnets, 0);
-    for (auto& d : h->downs) { couts[d.r1.index] = d.r1.cout; couts[d.r2.index] = d.r2.cout; }
-    couts[h->mid1.index] = h->mid1.cout; couts[h->mid2.index] = h->mid2.cout;
-    for (auto& u : h->ups) { couts[u.r1.index] = u.r1.cout; couts[u.r2.index] = u.r2.cout; }
+    for_each_resnet(h, [&](const ResnetW& r) { couts[r.index] = r.cout; });
     float* eval_tproj = bufs.tproj;
     int blk0 = 0, blk_n = 0;
     for (int i = 0; i < N; ++i) {
@@ -1656,7 +1729,7 @@ int us_reverse_diffusion(us_handle h, const float* z, const float* mask, const f
       for (int r = 0; r < h->n_resnets; ++r)
         bufs.tproj_off[r] = (size_t)blk_n * base_off[r] + (size_t)(i - blk0) * Bp * couts[r];
       bufs.tproj_ready = true;
-      US_HIP(h, estimator_eval(e, xt, mb, cond_b, mb, n_text_uncond, tbuf, spk_cfg, score, i == N / 2));
+      US_HIP(h, estimator_eval(e, places, xt, mb, cond_b, mb, n_text_uncond, tbuf, spk_cfg, score, i == N / 2));
       SamplerArgs sa;
       memset(&sa, 0, sizeof sa);
       sa.xt = xt; sa.score = score; sa.mask = mask_b; sa.out = xt;
@@ -1699,13 +1772,14 @@ double us_estimator_flops(us_handle h, int T) {
     conv(n, kHidden, a.dim, 1);
     fl += 2.0 * 2.0 * n * kHeads * kDimHead * kDimHead;   // the two einsums
   };
+  for_each_resnet(h, res);      // (every term is an integer far below 2^53: the sum does not depend on its order)
   for (auto& d : h->downs) {
-    res(d.r1); res(d.r2); att(d.a);
+    att(d.a);
     if (d.has_ds) conv(npx(d.ds.level + 1), d.ds.dim, d.ds.dim, 9);
   }
-  res(h->mid1); att(h->mid_attn); res(h->mid2);
+  att(h->mid_attn);
   for (auto& u : h->ups) {
-    res(u.r1); res(u.r2); att(u.a);
+    att(u.a);
     conv(npx(u.us.level), u.us.dim, u.us.dim, 16);      // transposed 4x4: 16 MACs per INPUT pixel per channel pair
   }
   conv(npx(0), h->cfg.dim, h->cfg.dim, 9);
@@ -1773,53 +1847,50 @@ int us_debug_block(us_handle h, int kind, const char* prefix, int level, const f
   hipStream_t s = static_cast<hipStream_t>(stream);
   Arena A(workspace, workspace_bytes);
   Buffers b;
-  plan(h, A, B, T, b);
+  Places pl;
+  plan(h, A, B, T, b, pl);
   EvalCtx e{h, s, &b, B, T, mask, B};
   e.infer = true;
   RangeScope range_scope(h->range_flag);
-  US_HIP(h, hipMemsetAsync(b.stats, 0, b.stats_count * sizeof(double), s));
-  std::vector<const ResnetW*> rs;
-  std::vector<const AttnW*> as;
-  for (auto& d : h->downs) { rs.push_back(&d.r1); rs.push_back(&d.r2); as.push_back(&d.a); }
-  rs.push_back(&h->mid1); rs.push_back(&h->mid2); as.push_back(&h->mid_attn);
-  for (auto& u : h->ups) { rs.push_back(&u.r1); rs.push_back(&u.r2); as.push_back(&u.a); }
+  US_HIP(h, hipMemsetAsync(pl.stats, 0, pl.stats_count * sizeof(double), s));
   if (kind == US_DEBUG_TEMB) {
     // x = t [B]; out [B][2 * dim] = SinusoidalPosEmb(t) | mlp(SinusoidalPosEmb(t))  (unitspeech.py:109-121,133-134,165-166), by the launches
     // time_embedding() makes
     const int dim = h->cfg.dim;
-    US_HIP(h, launch_pos_emb(x, b.posemb, B, dim, h->cfg.pe_scale, s));
-    US_HIP(h, launch_linear(b.posemb, dim, h->mlp0_w->buf.p, h->mlp0_b->buf.p, b.mlp_h, 4 * dim, B, dim, 4 * dim, false, s));
-    US_HIP(h, launch_linear(b.mlp_h, 4 * dim, h->mlp2_w->buf.p, h->mlp2_b->buf.p, b.temb, dim + h->cfg.spk_emb_dim, B, 4 * dim, dim, true, s));
+    US_HIP(h, temb_chain(h, x, B, nullptr, 0, b.posemb, b.mlp_h, b.temb, s));
     US_HIP(h, launch_copy_rows(b.posemb, dim, B, out, 2 * dim, B, dim, s));
     US_HIP(h, launch_copy_rows(b.temb, dim + h->cfg.spk_emb_dim, B, out + dim, 2 * dim, B, dim, s));
     return US_OK;
   }
   if (kind == US_DEBUG_BLOCK || kind == US_DEBUG_RESNET) {
-    for (const ResnetW* r0 : rs) {
-      if (r0->mlp_w->key != p + ".mlp.1.weight") continue;
-      if (r0->first) return h->fail(US_EINVAL, "the 2-channel first block has no stand-alone entry");
-      ResnetW r = *r0;
+    for (ResT t : pl.res) {
+      if (t.w->mlp_w->key != p + ".mlp.1.weight") continue;
+      if (t.w->first) return h->fail(US_EINVAL, "the 2-channel first block has no stand-alone entry");
+      ResnetW r = *t.w;
       r.level = level;                   // geometry (H, W, mask stride) of the requested level; the weights are the module's own
+      t.w = &r;
+      t.y1 = b.S1[level]; t.y2 = b.S2[level]; t.r_early = b.QKV[level]; t.out = out; t.out_ld = r.cout;
       if (kind == US_DEBUG_BLOCK) {      // Block = block1 of that ResnetBlock: Mish(GroupNorm(conv(x))) * mask, x pre-masked (:46-55)
-        double* st = next_stats(e);
-        US_HIP(h, conv3x3(e, r.c1, x, r.cin, level, b.S1[level], r.cout, st));
-        US_HIP(h, gn_apply(e, b.S1[level], level, r.cout, st, r.g1, r.b1, nullptr, nullptr, 0, false, false, out, r.cout));
+        US_HIP(h, conv3x3(e, r.c1, x, r.cin, level, t.y1, r.cout, t.st1));
+        US_HIP(h, gn_apply(e, t.y1, level, r.cout, t.st1, r.g1, r.b1, nullptr, nullptr, 0, false, false, out, r.cout));
         return US_OK;
       }
       if (!temb) return h->fail(US_EINVAL, "ResnetBlock needs temb");
       const int td = h->cfg.dim + h->cfg.spk_emb_dim;
       US_HIP(h, launch_linear(temb, td, r.mlp_w->buf.p, r.mlp_b->buf.p, b.tproj + b.tproj_off[r.index], r.cout, B, td, r.cout, true, s));
-      US_HIP(h, resnet(e, r, x, r.cin, out, r.cout, false));
+      US_HIP(h, resnet(e, t, x, r.cin, false));
       return US_OK;
     }
     return h->fail(US_ENOKEY, "no ResnetBlock '%s'", prefix);
   }
   if (kind == US_DEBUG_ATTENTION) {
-    for (const AttnW* a0 : as) {
-      if (a0->g->key != p + ".fn.g") continue;
-      AttnW a = *a0;
+    for (AttT t : pl.att) {
+      if (t.w->g->key != p + ".fn.g") continue;
+      AttnW a = *t.w;
       a.level = level;
-      US_HIP(h, attention(e, a, x, a.dim, out, a.dim));
+      t.w = &a;
+      t.qkv = b.QKV[level]; t.out = out; t.out_ld = a.dim;
+      US_HIP(h, attention(e, t, x, a.dim));
       return US_OK;
     }
     return h->fail(US_ENOKEY, "no attention '%s'", prefix);

@@ -1,5 +1,5 @@
-// Included by decoder.hip inside its anonymous namespace: training-mode forward (keeps every tensor the backward
-// needs) and the backward pass of `GradLogPEstimator2d` (reference: autograd through unitspeech/unitspeech.py:164-201,
+// Included by decoder.hip inside its anonymous namespace: the tape (the placement table of a training forward, which keeps every
+// tensor the backward needs) and the backward pass of `GradLogPEstimator2d` (reference: autograd through unitspeech/unitspeech.py:164-201,
 // driven by `loss.backward()` at finetune.py:163).  Gradient conventions:
 //   * a tensor that is stored pre-multiplied by the frame mask has a gradient that is masked too (its producer's
 //     backward would multiply by the mask anyway), so data-gradient GEMMs of such tensors apply the mask in their epilogue;
@@ -18,38 +18,13 @@ inline hipError_t zero_f32(float* p, size_t n, hipStream_t s) {
 }
 inline hipError_t zero_f64(double* p, size_t n, hipStream_t s) { return zero_f32(reinterpret_cast<float*>(p), 2 * n, s); }
 
-struct ResT {
-  const ResnetW* w = nullptr;
-  const float* x = nullptr; int x_ld = 0;
-  float *y1 = nullptr, *h1 = nullptr, *y2 = nullptr, *out = nullptr, *r0 = nullptr;
-  int out_ld = 0;
-  double *st1 = nullptr, *st2 = nullptr;
-  bool mask_out = false;
-};
-struct AttT {
-  const AttnW* w = nullptr;
-  const float* x = nullptr; int x_ld = 0;
-  float *qkv = nullptr, *ctx = nullptr, *colM = nullptr, *colS = nullptr, *weff = nullptr, *out = nullptr;
-  int out_ld = 0;
-  float* o_pre = nullptr;           // fn(x) of the Rezero wrapper, [B][n][dim]: to_out's result before gain and residual (ConvArgs::out2)
-};
-struct CvT {
-  const ConvW* w = nullptr; int level = 0;
-  const float* x = nullptr; int x_ld = 0;
-  float* out = nullptr; int out_ld = 0;
-};
-
-struct Tape {
+// The placement table of a training step, every entry a slot of its own that lives until the backward, and the backward's scratch
+struct Tape : Places {
   int Bp = 0, T = 0;
   bool forward_done = false;
   const float* mask = nullptr; int Bm = 0;   // library-owned copy inside the workspace (the caller's tensor may be gone by backward)
   float* mask_copy = nullptr;
   Buffers fb;                       // forward scratch that is not saved per layer (time embedding, attention partials, in2)
-  std::vector<ResT> res;            // indexed by ResnetW::index
-  std::vector<AttT> att;            // execution order: downs[0..L-1], mid, ups[0..L-2]
-  std::vector<CvT> downs, ups;
-  std::vector<float*> CAT;
-  float *fin_y = nullptr, *fin_h = nullptr; const float* fin_x = nullptr; int fin_ld = 0; double* fin_st = nullptr;
   // backward scratch
   std::vector<float*> GA, GB, GY, GY2, GH, GQKV, GO, GCAT;
   // scratch of the parameter-gradient chains, one set per side stream of the backward pass (BwdCtx): packed weight gradient, the
@@ -62,8 +37,6 @@ struct Tape {
   size_t zero_floats = 0;
   double* gsum = nullptr;           // one [B][8][2] block per GroupNorm backward, zeroed together
   int gsum_next = 0;
-  double* stats_all = nullptr;      // st1 / st2 of every ResnetBlock and fin_st, contiguous: one zero-fill per forward
-  size_t stats_all_count = 0;
   size_t wscratch_floats = 0;
   // optional input gradients of the current backward call (caller-owned, planar [Bp][F][T] / [Bp][S]; null = not wanted)
   float *grad_x = nullptr, *grad_mu = nullptr, *grad_spk = nullptr;
@@ -79,75 +52,56 @@ inline void plan_train(us_decoder* h, Arena& A, int Bp, int T, Tape& tp) {
   const int L = h->cfg.n_mults, F = h->cfg.n_feats;
   const size_t B = (size_t)Bp;
   tp.Bp = Bp; tp.T = T;
-  plan(h, A, Bp, T, tp.fb, true);       // reuse the inference plan for in2 / temb / tproj / stats / attention partial buffers
+  // of the forward's scratch only what no layer keeps; the backward reads fb.in2 / posemb / mlp_h / temb / tproj_off and runs its
+  // convolutions through fb.splitk and fb.wino_v / wino_m
+  plan_shared(h, A, Bp, T, tp.fb, true);
+  init_places(h, A, Bp, tp);
   auto npx = [&](int l) { return (size_t)(F >> l) * (T >> l); };
-  tp.res.assign(h->n_resnets, ResT());
-  tp.CAT.assign(L, nullptr);
-  const size_t st_block = B * kGroups * kStatStride;
-  tp.stats_all_count = (size_t)(2 * h->n_resnets + 1) * st_block;
-  tp.stats_all = A.alloc<double>(tp.stats_all_count);
   for (int l = 1; l < L; ++l) tp.CAT[l] = A.alloc<float>(B * npx(l) * 2 * h->C[l]);
-  auto plan_res = [&](const ResnetW& r) {
+  // out: null = a slot of its own, `ld` wide
+  auto plan_res = [&](const ResnetW& r, float* out, int ld) {
     ResT& t = tp.res[r.index];
-    t.w = &r;
     const size_t n = npx(r.level);
     t.y1 = A.alloc<float>(B * n * r.cout);
     t.h1 = A.alloc<float>(B * n * r.cout);
     t.y2 = A.alloc<float>(B * n * r.cout);
     if (r.first) t.r0 = A.alloc<float>(B * n * r.cout);
-    t.st1 = tp.stats_all + (size_t)(2 * r.index) * st_block;
-    t.st2 = tp.stats_all + (size_t)(2 * r.index + 1) * st_block;
+    t.out = out ? out : A.alloc<float>(B * n * ld); t.out_ld = ld;
   };
-  auto plan_att = [&](const AttnW& a) {
-    AttT t;
-    t.w = &a;
-    const size_t n = npx(a.level);
+  auto plan_att = [&](AttT& t, float* out, int ld) {
+    const size_t n = npx(t.w->level);
     t.qkv = A.alloc<float>(B * n * 3 * kHidden);
     t.ctx = A.alloc<float>(B * kHeads * kDimHead * kDimHead);
     t.colM = A.alloc<float>(B * kHidden);
     t.colS = A.alloc<float>(B * kHidden);
-    t.weff = A.alloc<float>(B * (size_t)a.dim * kHidden);
-    t.o_pre = A.alloc<float>(B * n * (size_t)a.dim);
-    tp.att.push_back(t);
+    t.weff = A.alloc<float>(B * (size_t)t.w->dim * kHidden);
+    t.o_pre = A.alloc<float>(B * n * (size_t)t.w->dim);
+    t.out = out ? out : A.alloc<float>(B * n * ld); t.out_ld = ld;
   };
-  tp.att.clear(); tp.downs.clear(); tp.ups.clear();
-  // outputs that are not part of a concat buffer
   for (int l = 0; l < L; ++l) {
     auto& d = h->downs[l];
-    plan_res(d.r1); plan_res(d.r2); plan_att(d.a);
-    const size_t n = npx(l);
-    tp.res[d.r1.index].out = A.alloc<float>(B * n * h->C[l]); tp.res[d.r1.index].out_ld = h->C[l];
-    tp.res[d.r2.index].out = A.alloc<float>(B * n * h->C[l]); tp.res[d.r2.index].out_ld = h->C[l];
-    AttT& at = tp.att.back();
-    if (l == 0) { at.out = A.alloc<float>(B * n * h->C[0]); at.out_ld = h->C[0]; }
-    else { at.out = tp.CAT[l] + h->C[l]; at.out_ld = 2 * h->C[l]; }
-    if (d.has_ds) {
-      CvT c; c.w = &d.ds.conv; c.level = l;
-      c.out = A.alloc<float>(B * npx(l + 1) * h->C[l]); c.out_ld = h->C[l];
-      tp.downs.push_back(c);
-    }
+    const int c = h->C[l];
+    plan_res(d.r1, nullptr, c); plan_res(d.r2, nullptr, c);
+    if (l == 0) plan_att(tp.att[0], nullptr, c);
+    else plan_att(tp.att[l], tp.CAT[l] + c, 2 * c);
+    if (d.has_ds) { tp.downs[l].out = A.alloc<float>(B * npx(l + 1) * c); tp.downs[l].out_ld = c; }
   }
   const int lm = L - 1, cm = h->C[lm];
-  plan_res(h->mid1); plan_att(h->mid_attn); plan_res(h->mid2);
-  tp.res[h->mid1.index].out = A.alloc<float>(B * npx(lm) * cm); tp.res[h->mid1.index].out_ld = cm;
-  tp.att.back().out = A.alloc<float>(B * npx(lm) * cm); tp.att.back().out_ld = cm;
-  if (L > 1) { tp.res[h->mid2.index].out = tp.CAT[lm]; tp.res[h->mid2.index].out_ld = 2 * cm; }
-  else { tp.res[h->mid2.index].out = A.alloc<float>(B * npx(lm) * cm); tp.res[h->mid2.index].out_ld = cm; }
+  plan_res(h->mid1, nullptr, cm);
+  plan_att(tp.att[L], nullptr, cm);
+  if (L > 1) plan_res(h->mid2, tp.CAT[lm], 2 * cm);
+  else plan_res(h->mid2, nullptr, cm);
   for (int u = 0; u < L - 1; ++u) {
     auto& up = h->ups[u];
     const int l = up.r1.level, co = up.r1.cout;
-    plan_res(up.r1); plan_res(up.r2); plan_att(up.a);
-    tp.res[up.r1.index].out = A.alloc<float>(B * npx(l) * co); tp.res[up.r1.index].out_ld = co;
-    tp.res[up.r2.index].out = A.alloc<float>(B * npx(l) * co); tp.res[up.r2.index].out_ld = co;
-    tp.att.back().out = A.alloc<float>(B * npx(l) * co); tp.att.back().out_ld = co;
-    CvT c; c.w = &up.us.conv; c.level = l;
+    plan_res(up.r1, nullptr, co); plan_res(up.r2, nullptr, co);
+    plan_att(tp.att[L + 1 + u], nullptr, co);
+    CvT& c = tp.ups[u];
     if (l - 1 >= 1) { c.out = tp.CAT[l - 1]; c.out_ld = 2 * h->C[l - 1]; }
     else { c.out = A.alloc<float>(B * npx(0) * h->C[0]); c.out_ld = h->C[0]; }
-    tp.ups.push_back(c);
   }
   tp.fin_y = A.alloc<float>(B * npx(0) * h->C[0]);
   tp.fin_h = A.alloc<float>(B * npx(0) * h->C[0]);
-  tp.fin_st = tp.stats_all + (size_t)(2 * h->n_resnets) * st_block;
 
   // ---- backward scratch ----
   tp.GA.assign(L, nullptr); tp.GB.assign(L, nullptr); tp.GY.assign(L, nullptr); tp.GY2.assign(L, nullptr); tp.GH.assign(L, nullptr);
@@ -196,127 +150,17 @@ inline void plan_train(us_decoder* h, Arena& A, int Bp, int T, Tape& tp) {
   tp.gscaled = A.alloc<float>(B * (size_t)F * T);
 }
 
-// ---- training forward ---------------------------------------------------------------------------------------
-inline hipError_t resnet_train(EvalCtx& e, Tape& tp, const ResnetW& r, const float* in, int in_ld, bool mask_out) {
-  ResT& t = tp.res[r.index];
-  t.x = in; t.x_ld = in_ld; t.mask_out = mask_out;
-  const int l = r.level;
-  const float* tproj = tp.fb.tproj + tp.fb.tproj_off[r.index];
-  CK(conv3x3(e, r.c1, in, in_ld, l, t.y1, r.cout, t.st1));
-  if (r.c2.w->wino.p && e.b->wino_v && gn_wino_input_supported(r.cout)) {
-    // block1's GroupNorm + Mish + time embedding inside block2's Winograd input transform, as in inference (resnet()), with the
-    // activation h1 stored from the same pass for the weight gradient: one launch and one read of y1 less per ResnetBlock
-    WinoGnArgs g;
-    memset(&g, 0, sizeof g);
-    g.stats = t.st1; g.gamma = r.g1->buf.p; g.beta = r.b1->buf.p; g.temb = tproj;
-    g.mask = e.mask; g.mask_ld = e.T; g.mask_step = 1 << l; g.mask_bmod = e.Bm;
-    g.h_out = t.h1;
-    CK(conv3x3_wino(e, r.c2, t.y1, r.cout, l, t.y2, r.cout, t.st2, &g));
-  } else {
-    CK(gn_apply(e, t.y1, l, r.cout, t.st1, r.g1, r.b1, tproj, nullptr, 0, false, true, t.h1, r.cout));
-    CK(conv3x3(e, r.c2, t.h1, r.cout, l, t.y2, r.cout, t.st2));
-  }
-  if (r.has_res) {
-    CK(gn_apply(e, t.y2, l, r.cout, t.st2, r.g2, r.b2, nullptr, nullptr, 0, false, false, t.out, t.out_ld));
-    CK(conv1x1(e, r.res, in, in_ld, l, mask_out, t.out, t.out_ld, t.out, t.out_ld, nullptr, nullptr, 0, nullptr));
-  } else {
-    CK(gn_apply(e, t.y2, l, r.cout, t.st2, r.g2, r.b2, nullptr, in, in_ld, false, mask_out, t.out, t.out_ld));
-  }
-  return hipSuccess;
-}
-
-inline hipError_t attention_train(EvalCtx& e, Tape& tp, AttT& t, const float* in, int in_ld) {
-  const AttnW& at = *t.w;
-  Buffers& b = tp.fb;
-  t.x = in; t.x_ld = in_ld;
-  const int l = at.level;
-  const int n = (e.h->cfg.n_feats >> l) * (e.T >> l);
-  const int nch = attn_nchunks(n);
-  CK(conv1x1(e, at.qkv, in, in_ld, l, false, t.qkv, 3 * kHidden, nullptr, 0, nullptr, nullptr, 0, nullptr));
-  CK(launch_attn_ctx_partial(t.qkv, e.Bp, n, b.part_ctx, b.part_m, b.part_s, nch, e.s));
-  const int bk = pick_bk(kHidden);
-  const bool f16 = !e.h->exact;
-  CK(launch_attn_merge(b.part_ctx, b.part_m, b.part_s, e.Bp, nch, t.ctx, t.colM, t.colS, b.ctx_split, at.out_w->buf.p, t.weff, at.dim, bk, f16,
-                       e.s));
-  ConvW eff;
-  eff.cin = kHidden; eff.cout = at.dim;
-  Slot tmp;
-  tmp.bk = bk; tmp.buf.p = t.weff; tmp.direct_f16 = f16;
-  eff.w = &tmp; eff.b = nullptr;
-  return conv1x1(e, eff, t.qkv, 3 * kHidden, l, true, t.out, t.out_ld, in, in_ld, at.g->buf.p, t.weff, (long long)at.dim * kHidden,
-                 at.out_b->buf.p, false, false, t.o_pre, at.dim);
-}
-
+// ---- training forward: the walk of unet_forward over the tape ---------------------------------------------------------------
 inline hipError_t train_forward(us_decoder* h, Tape& tp, hipStream_t s, const float* x, const float* mu, const float* mask, const float* t,
                                 const float* spk, float* out) {
-  const int L = h->cfg.n_mults, F = h->cfg.n_feats, T = tp.T, Bp = tp.Bp;
+  const int T = tp.T, Bp = tp.Bp;
   CK(hipMemcpyAsync(tp.mask_copy, mask, sizeof(float) * (size_t)Bp * T, hipMemcpyDeviceToDevice, s));
-  mask = tp.mask_copy;
-  EvalCtx e{h, s, &tp.fb, Bp, T, mask, Bp};
+  tp.mask = tp.mask_copy; tp.Bm = Bp;
+  EvalCtx e{h, s, &tp.fb, Bp, T, tp.mask, Bp};
   e.splitk_by_batch = 1;
-  tp.mask = mask; tp.Bm = Bp;
-  CK(zero_f64(tp.stats_all, tp.stats_all_count, s));     // every GroupNorm's partial sums of this forward
+  CK(zero_f64(tp.stats, tp.stats_count, s));     // every GroupNorm's partial sums of this forward
   CK(time_embedding(e, t, spk));
-  CK(launch_stack_inputs(x, Bp, mu, Bp, 0, h->text_uncon->buf.p, mask, Bp, tp.fb.in2, Bp, F, T, s));
-  const float* cur = nullptr;
-  int cur_ld = 0;
-  size_t ai = 0, di = 0;
-  for (int l = 0; l < L; ++l) {
-    auto& d = h->downs[l];
-    const int c = h->C[l];
-    if (l == 0) {
-      const ResnetW& r = d.r1;
-      ResT& rt = tp.res[r.index];
-      rt.x = tp.fb.in2; rt.x_ld = 2; rt.mask_out = true;
-      CK(launch_first_conv(tp.fb.in2, r.c1.w->buf.p, r.c1.b->buf.p, r.res.w->buf.p, r.res.b->buf.p, rt.y1, rt.r0, rt.st1, Bp, F, T, c, s));
-      CK(gn_apply(e, rt.y1, 0, c, rt.st1, r.g1, r.b1, tp.fb.tproj + tp.fb.tproj_off[r.index], nullptr, 0, false, true, rt.h1, c));
-      CK(conv3x3(e, r.c2, rt.h1, c, 0, rt.y2, c, rt.st2));
-      CK(gn_apply(e, rt.y2, 0, c, rt.st2, r.g2, r.b2, nullptr, rt.r0, c, false, true, rt.out, rt.out_ld));
-    } else {
-      CK(resnet_train(e, tp, d.r1, cur, cur_ld, true));
-    }
-    ResT& r1t = tp.res[d.r1.index];
-    CK(resnet_train(e, tp, d.r2, r1t.out, r1t.out_ld, false));
-    ResT& r2t = tp.res[d.r2.index];
-    AttT& at = tp.att[ai++];
-    CK(attention_train(e, tp, at, r2t.out, r2t.out_ld));
-    if (d.has_ds) {
-      CvT& c = tp.downs[di++];
-      c.x = at.out; c.x_ld = at.out_ld;
-      CK(conv_down(e, *c.w, at.out, at.out_ld, l, c.out, c.out_ld));
-      cur = c.out; cur_ld = c.out_ld;
-    } else {
-      cur = at.out; cur_ld = at.out_ld;
-    }
-  }
-  CK(resnet_train(e, tp, h->mid1, cur, cur_ld, false));
-  {
-    ResT& m1 = tp.res[h->mid1.index];
-    AttT& at = tp.att[ai++];
-    CK(attention_train(e, tp, at, m1.out, m1.out_ld));
-    CK(resnet_train(e, tp, h->mid2, at.out, at.out_ld, true));
-  }
-  const float* fin = tp.res[h->mid2.index].out;
-  int fin_ld = tp.res[h->mid2.index].out_ld;
-  for (int u = 0; u < L - 1; ++u) {
-    auto& up = h->ups[u];
-    const int l = up.r1.level;
-    CK(resnet_train(e, tp, up.r1, tp.CAT[l], 2 * h->C[l], true));
-    ResT& r1t = tp.res[up.r1.index];
-    CK(resnet_train(e, tp, up.r2, r1t.out, r1t.out_ld, false));
-    ResT& r2t = tp.res[up.r2.index];
-    AttT& at = tp.att[ai++];
-    CK(attention_train(e, tp, at, r2t.out, r2t.out_ld));
-    CvT& c = tp.ups[u];
-    c.x = at.out; c.x_ld = at.out_ld;
-    CK(conv_up(e, *c.w, at.out, at.out_ld, l, c.out, c.out_ld));
-    fin = c.out; fin_ld = c.out_ld;
-  }
-  const int c0 = h->C[0];
-  tp.fin_x = fin; tp.fin_ld = fin_ld;
-  CK(conv3x3(e, h->final_conv3, fin, fin_ld, 0, tp.fin_y, c0, tp.fin_st));
-  CK(gn_apply(e, tp.fin_y, 0, c0, tp.fin_st, h->final_g, h->final_b, nullptr, nullptr, 0, false, false, tp.fin_h, c0));
-  CK(launch_final_conv(tp.fin_h, c0, h->final_w1->buf.p, h->final_b1->buf.p, mask, T, Bp, out, Bp, F, T, c0, s));
+  CK(unet_forward(e, tp, x, Bp, mu, Bp, 0, out));
   tp.forward_done = true;
   return hipSuccess;
 }
@@ -906,9 +750,7 @@ inline hipError_t train_backward_body(us_decoder* h, Tape& tp, BwdCtx& c, EvalCt
       if (upload_bytes(h, jobs.data(), jobs.size() * sizeof(LinJob), h->lin_tab_bwd_dev, s) != US_OK) return hipErrorUnknown;
       CK(launch_linear_bwd_multi(h->lin_tab_bwd_dev, (int)jobs.size(), total, tp.fb.temb, td, Bp, td, true, tp.gtemb, td, s));
     } else {
-      for (auto& d : h->downs) { CK(proj_bwd(d.r1)); CK(proj_bwd(d.r2)); }
-      CK(proj_bwd(h->mid1)); CK(proj_bwd(h->mid2));
-      for (auto& u : h->ups) { CK(proj_bwd(u.r1)); CK(proj_bwd(u.r2)); }
+      CK(for_each_resnet(h, proj_bwd));
     }
   }
   CK(launch_mul_mish_grad(tp.gtemb, td, tp.fb.temb, td, Bp, td, s));       // mish'(temb), shared by the 22 projections
