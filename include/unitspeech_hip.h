@@ -761,6 +761,41 @@ int us_units_encode(const float* dense, const int64_t* lengths, const void* pack
                     int hop_length, int64_t* out_units, int64_t* out_durations, float* duration_f, int64_t* n_out, int Lout,
                     int32_t* counters, void* workspace, size_t workspace_bytes, us_stream stream);
 
+/* ---- fitting the unit codebook, csrc/units_fit.hip -----------------------------------------------------------------------------------
+ * The half of a k-means iteration that us_units_quantize does not do, as handle-free device calls that only enqueue on `stream` and
+ * allocate nothing.  K in [1, 2048], D a multiple of 4 in [4, 1024], at most 2^24 rows per call; the two size functions return 0 for
+ * anything else and the calls return US_EINVAL.  No float atomics anywhere: every output has the same bits on every run.
+ * us_units_fit_workspace_bytes(rows, K, D): device scratch of one us_units_fit_accumulate or us_units_fit_seed_step call.
+ * us_units_fit_state_bytes(K, D): the state that accumulate calls add into: fp64 sums [K][D], int64 counts [K], the fp64 inertia, rows used
+ *   and rows skipped.  us_units_fit_state_clear zeroes it; us_units_fit_update leaves it cleared.
+ * us_units_fit_accumulate: labels [rows] (device int64, as us_units_quantize writes them: -1 or anything outside [0, K) is a skipped row),
+ *   dense [rows][D] fp32 and the centres [K][D] the labels were taken against -> state += {sum of the rows of every centre, their number,
+ *   sum_rows sum_d (x_d - c_label,d)^2, rows used, rows skipped}.  An inverted index (per-chunk histograms, an exclusive scan, a stable
+ *   scatter of row numbers) gives every centre its rows in ascending order; each row is read once and added in fp64 in that order, lists
+ *   longer than 512 rows in pieces of 512 whose partial sums are added in piece order.  The sums depend on how the rows were split into
+ *   calls (in the last fp64 bits) and on nothing else.
+ * us_units_fit_update: mode US_UNITS_FIT_LLOYD: c_k = fp32(sum_k / count_k), totals_out[k] = count_k (totals may be NULL);
+ *   US_UNITS_FIT_MINIBATCH: c_k = fp32((c_k total_k + sum_k) / (total_k + count_k)), totals_out[k] = totals_in[k] + count_k (scikit-learn's
+ *   MiniBatchKMeans.partial_fit with reassignment_ratio = 0).  A centre with count_k = 0 keeps its value.  centers_out may be centers_in and
+ *   totals_out may be totals_in.  record (device, 40 bytes): {fp64 inertia, fp64 shift2 = sum (c_new - c_old)^2 over the fp32 values,
+ *   int64 empty centres, int64 rows used, int64 rows skipped}.
+ * us_units_fit_seed_step: step `step` in [0, K) of plain D^2 k-means++ over dense [B][Tmax][D] with lengths [B] (device int64); a row at or
+ *   beyond lengths[b] or with a non-finite feature is never chosen.  Step 0 initialises mind [B Tmax] (device fp64, the caller's) and takes
+ *   valid row floor(u n_valid); step j >= 1 sets mind_i = min(mind_i, sum_d (x_id - c_d)^2) for centre j - 1 (fp64, d ascending), takes a
+ *   fixed-order blocked inclusive scan P and picks the smallest valid i with P_i > u P_last, or valid row floor(u n_valid) when P_last = 0.
+ *   u in [0, 1) comes from the caller.  centers [K][D] row `step` and picked[step] (device int64: the row index, -1 without a valid row)
+ *   are written; steps must be called in order with the same buffers. */
+enum { US_UNITS_FIT_LLOYD = 0, US_UNITS_FIT_MINIBATCH = 1 };
+size_t us_units_fit_workspace_bytes(int64_t rows, int K, int D);
+size_t us_units_fit_state_bytes(int K, int D);
+int us_units_fit_state_clear(void* state, size_t state_bytes, int K, int D, us_stream stream);
+int us_units_fit_accumulate(const float* dense, const int64_t* labels, const float* centers, int64_t rows, int K, int D, void* state,
+                            size_t state_bytes, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_units_fit_update(int mode, const float* centers_in, float* centers_out, const int64_t* totals_in, int64_t* totals_out, int K, int D,
+                        void* state, size_t state_bytes, void* record, us_stream stream);
+int us_units_fit_seed_step(const float* dense, const int64_t* lengths, int B, int Tmax, int K, int D, int step, double u, double* mind,
+                           float* centers, int64_t* picked, void* workspace, size_t workspace_bytes, us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

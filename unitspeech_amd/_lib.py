@@ -191,6 +191,13 @@ SIGNATURES = {
     "us_units_process": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_encode": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                                                          C.c_void_p]),
+    "us_units_fit_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "us_units_fit_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "us_units_fit_state_clear": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "us_units_fit_accumulate": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
+    "us_units_fit_update": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "us_units_fit_seed_step": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "us_debug_block": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -458,4 +458,8 @@ hipError_t launch_wino4_input(int form, const float* x, int x_ld, float* V, int 
 hipError_t launch_wino4_output(int form, const float* M, const float* bias, float* out, int out_ld, double* stats, int B, int H, int W, int C,
                                hipStream_t s);
 hipError_t launch_wino4_pack_weight(int form, const float* src, float* dst, int Cout, int Cin, hipStream_t s);
+
+// ---- codebook fit (units_fit.hip) --------------------------------------------------------------------------------------------------------
+// Like units.hip, self-contained behind its C entry points (us_units_fit_*): nothing of it is launched from another source.  Its limits and
+// the layouts of its state and workspace are host arithmetic in units_fit_layout.h.
 }  // namespace us
