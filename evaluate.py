@@ -1,0 +1,227 @@
+#!/usr/bin/env python3
+"""Scoring synthesised speech on the HIP library: the counterpart of the reference's evaluation/ (transcribe every sample, compare with
+its text by character and word error rate, compare its speaker embedding with the reference recording's).
+
+    python evaluate.py --filelist LIST --ctc_path CTC.pt --vocab_path vocab.json [--config_path config.json]
+                       [--speaker_encoder_path EMBEDDER.pt] [--batch 16] [--out RESULT.json]
+    python evaluate.py --synthetic 12 --batch 4
+
+LIST holds one `wav|transcript[|reference_wav]` line per sample.  CTC.pt is a `torch.save`d state dict of `transformers.HubertForCTC` or
+`Wav2Vec2ForCTC` in the base form (the class is taken from the keys; nothing is fetched by name; the base size unless --config_path
+names the model's config.json) and vocab.json its tokenizer's vocabulary.  The wavs are read with `voice_conversion.read_wav`,
+resampled to 16 kHz by the library's `Resample`, sorted by length and transcribed in ragged batches of --batch (`transcribe_ids`: encoder, CTC head, greedy collapse; an item has the ids it has alone).  The
+transcripts are brought to the vocabulary by `normalize_text`; CER and WER are `unitspeech_amd.asr.error_rates` (corpus rates: sum of
+distances over sum of reference lengths).  With --speaker_encoder_path and the third column, SECS is the cosine similarity of
+`ECAPA_TDNN.embed_wav` between each wav and its reference.  One line per file, then the corpus line; --out writes all of it as JSON.
+
+--synthetic N runs without files: a seeded tiny CTC model, N seeded waveforms, and as transcripts the model's own decodings with a known
+number of edits applied (characters appended, or cut from the end): the distance of each pair is then exactly that number, so the CER
+printed must equal the `expected_cer` printed next to it.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+MIN_SAMPLES_16K = 400            # the receptive field of the feature extractor: one frame
+SYNTHETIC_RATE = 22050
+SYNTHETIC_EDITS = 2              # per utterance
+TINY = dict(conv_dim=[24] * 7, conv_kernel=[10, 3, 3, 3, 3, 2, 2], conv_stride=[5, 2, 2, 2, 2, 2, 2], hidden_size=40, num_attention_heads=2,
+            intermediate_size=72, num_hidden_layers=2, num_conv_pos_embeddings=16, num_conv_pos_embedding_groups=4, layer_norm_eps=1e-5)
+TINY_VOCAB = {"<pad>": 0, "|": 1, **{c: i + 2 for i, c in enumerate("abcdefghij")}}
+
+
+def parse_filelist(text: str):
+    """`wav|transcript[|reference_wav]` lines -> [(wav, transcript, reference_wav or None)]; blank lines are skipped."""
+    out = []
+    for no, line in enumerate(text.splitlines(), start=1):
+        line = line.strip()
+        if not line:
+            continue
+        parts = line.split("|")
+        if len(parts) not in (2, 3) or not parts[0]:
+            raise ValueError(f"file list line {no}: expected `wav|transcript[|reference_wav]`, got {line!r}")
+        out.append((parts[0], parts[1], parts[2] if len(parts) == 3 and parts[2] else None))
+    return out
+
+
+def plan_batches(lengths, max_batch: int):
+    """Indices into `lengths`, sorted by length (ties in index order) and cut into batches of at most `max_batch`."""
+    if max_batch < 1:
+        raise ValueError("--batch must be at least 1")
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    return [order[i:i + max_batch] for i in range(0, len(order), max_batch)]
+
+
+def apply_edits(text: str, edits: int, cut: bool, letter: str = "a"):
+    """A string at Levenshtein distance exactly `edits` from `text`: `edits` characters cut from its end (when asked, and when that leaves
+    a longer, tidy string) or `edits` letters appended: the lengths then differ by `edits`, which no alignment can beat."""
+    if cut and len(text) > 2 * edits and not text[:-edits].endswith(" "):
+        return text[:-edits]
+    return text + letter * edits
+
+
+@torch.no_grad()
+def to_16k(wav, rate, device, resamplers):
+    from unitspeech_amd.resample import Resample
+    wav = torch.as_tensor(wav).float().to(device)
+    if rate == 16000:
+        return wav
+    if rate not in resamplers:
+        resamplers[rate] = Resample(rate, 16000).to(device)
+    return resamplers[rate](wav)
+
+
+def padded_batch(wavs16, idx):
+    n = [int(wavs16[i].shape[0]) for i in idx]
+    x = torch.zeros(len(idx), max(n), device=wavs16[idx[0]].device)
+    for b, i in enumerate(idx):
+        x[b, :n[b]] = wavs16[i]
+    return x, n
+
+
+@torch.no_grad()
+def transcribe_all(model, vocabulary, wavs16, max_batch):
+    """16 kHz waveforms [T_i] on the device -> their transcripts, in the order given; one read back per batch, of the tokens."""
+    texts = [None] * len(wavs16)
+    batches = plan_batches([int(w.shape[0]) for w in wavs16], max_batch)
+    for idx in batches:
+        x, n = padded_batch(wavs16, idx)
+        tokens, count = model.transcribe_ids(x, n)
+        for i, t in zip(idx, vocabulary.decode(tokens.cpu(), count.cpu())):
+            texts[i] = t
+    return texts, batches
+
+
+@torch.no_grad()
+def similarities(embedder, wavs16, refs16, max_batch):
+    """Cosine similarity of `embed_wav` (unit norm) between wavs16[i] and refs16[i] (None: no reference) -> list of float or None."""
+    pairs = [i for i, r in enumerate(refs16) if r is not None]
+    emb = {}
+    for which, src in (("wav", wavs16), ("ref", refs16)):
+        for idx in plan_batches([int(src[i].shape[0]) for i in pairs], max_batch):
+            idx = [pairs[j] for j in idx]
+            x, n = padded_batch(src, idx)
+            e = embedder.embed_wav(x, n).cpu()
+            for b, i in enumerate(idx):
+                emb[which, i] = e[b]
+    return [float((emb["wav", i] * emb["ref", i]).sum()) if r is not None else None for i, r in enumerate(refs16)]
+
+
+def synthetic_model(device, seed: int = 0):
+    """A seeded tiny `HubertForCTC` over TINY_VOCAB (the head drawn with unit scale, so that the ids vary) and its vocabulary."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from hubert_torch import synthetic_hubert_state_dict
+    from unitspeech_amd.asr import CTCVocabulary, HubertForCTC
+    V = len(TINY_VOCAB)
+    model = HubertForCTC(vocab_size=V, pad_token_id=0, **TINY)
+    sd = {"hubert." + k: v for k, v in synthetic_hubert_state_dict(TINY, seed).items()}
+    g = np.random.Generator(np.random.Philox(key=9000 + seed))
+    sd["lm_head.weight"] = torch.from_numpy(g.standard_normal((V, TINY["hidden_size"]), dtype=np.float32))
+    sd["lm_head.bias"] = torch.from_numpy(0.1 * g.standard_normal(V, dtype=np.float32))
+    model.load_state_dict(sd)
+    return model.to(device).eval(), CTCVocabulary(TINY_VOCAB)
+
+
+def synthetic_waves(n: int, seed: int = 0):
+    from unitspeech_amd.mel import synthetic_waveform
+    if n < 1:
+        raise ValueError("--synthetic N: N must be at least 1")
+    g = np.random.Generator(np.random.Philox(key=7000 + seed))
+    lens = g.integers(int(0.4 * SYNTHETIC_RATE), int(1.6 * SYNTHETIC_RATE), size=n)
+    return [(f"synthetic_{i:04d}", synthetic_waveform(int(lens[i]), seed * 1000 + i, SYNTHETIC_RATE), SYNTHETIC_RATE) for i in range(n)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--filelist", default=None, help="`wav|transcript[|reference_wav]` lines")
+    ap.add_argument("--ctc_path", default=None, help="state dict of a HubertForCTC / Wav2Vec2ForCTC (base form)")
+    ap.add_argument("--vocab_path", default=None, help="the tokenizer's vocab.json")
+    ap.add_argument("--config_path", default=None, help="the model's config.json, when it is not the base size")
+    ap.add_argument("--blank", default="<pad>")
+    ap.add_argument("--word_delimiter", default="|")
+    ap.add_argument("--normalize", action="store_true", help="zero mean, unit variance per waveform (a feature extractor with do_normalize)")
+    ap.add_argument("--speaker_encoder_path", default=None, help="the whole speaker embedder's checkpoint: adds SECS against the third column")
+    ap.add_argument("--batch", type=int, default=16, help="most files in one call")
+    ap.add_argument("--out", default=None, help="JSON file for the result")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded waveforms through a seeded tiny model")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("no ROCm device: the HIP recogniser has no CPU fallback")
+    from unitspeech_amd.asr import CTCVocabulary, error_rates, load_ctc_checkpoint, normalize_text
+    device = torch.device(args.device)
+    resamplers, embedder = {}, None
+    if args.synthetic:
+        model, vocabulary = synthetic_model(device, args.seed)
+        items = synthetic_waves(args.synthetic, args.seed)
+        transcripts, references = None, [None] * len(items)
+    else:
+        if not args.filelist or not args.ctc_path or not args.vocab_path:
+            raise SystemExit("give --filelist, --ctc_path and --vocab_path, or --synthetic N")
+        from voice_conversion import read_wav
+        with open(args.filelist, encoding="utf-8") as f:
+            entries = parse_filelist(f.read())
+        if not entries:
+            raise SystemExit(f"{args.filelist}: no files")
+        vocabulary = CTCVocabulary(args.vocab_path, args.blank, args.word_delimiter)
+        config = {}
+        if args.config_path:
+            with open(args.config_path, encoding="utf-8") as f:
+                config = {k: v for k, v in json.load(f).items() if k not in ("vocab_size", "pad_token_id")}
+        model = load_ctc_checkpoint(args.ctc_path, pad_token_id=vocabulary.blank_id, **config).to(device)
+        items = [(path,) + read_wav(path) for path, _, _ in entries]
+        transcripts = [normalize_text(text, vocabulary) for _, text, _ in entries]
+        references = [ref for _, _, ref in entries]
+        if args.speaker_encoder_path and any(references):
+            from unitspeech_amd.speaker_encoder import load_speaker_embedder_checkpoint
+            embedder = load_speaker_embedder_checkpoint(args.speaker_encoder_path, device)
+    wavs16 = []
+    for name, wav, rate in items:
+        w = to_16k(wav, rate, device, resamplers)
+        if w.shape[0] < MIN_SAMPLES_16K:
+            raise SystemExit(f"{name}: {w.shape[0]} samples at 16 kHz are fewer than the receptive field ({MIN_SAMPLES_16K})")
+        wavs16.append(w)
+    model.pad_token_id = vocabulary.blank_id
+    if args.normalize:
+        wavs16 = [(w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7) for w in wavs16]
+    hyps, batches = transcribe_all(model, vocabulary, wavs16, args.batch)
+    result = {}
+    if args.synthetic:
+        transcripts = [apply_edits(h, SYNTHETIC_EDITS, cut=bool(i & 1)) for i, h in enumerate(hyps)]
+        result["expected_cer"] = SYNTHETIC_EDITS * len(hyps) / sum(len(t) for t in transcripts)
+    rates = error_rates(hyps, transcripts, device)
+    secs = [None] * len(items)
+    if embedder is not None:
+        from voice_conversion import read_wav
+        refs16 = [to_16k(*read_wav(r), device, resamplers) if r else None for r in references]
+        secs = similarities(embedder, wavs16, refs16, args.batch)
+    files = []
+    for (name, _, _), h, t, p, s in zip(items, hyps, transcripts, rates["per_utterance"], secs):
+        rec = dict(file=name, hypothesis=h, reference=t, **p)
+        if s is not None:
+            rec["secs"] = s
+        files.append(rec)
+        print(f"{name}: CER {p['cer']:.4f} ({p['char_distance']}/{p['chars']})  WER {p['wer']:.4f} ({p['word_distance']}/{p['words']})"
+              + (f"  SECS {s:.4f}" if s is not None else "") + f"  | {h!r} <- {t!r}")
+    result.update(cer=rates["cer"], wer=rates["wer"], files=len(files), batches=len(batches), per_file=files)
+    have = [s for s in secs if s is not None]
+    if have:
+        result["secs"] = float(np.mean(have))
+    print(json.dumps({k: v for k, v in result.items() if k != "per_file"}))
+    if args.out:
+        with open(args.out, "w", encoding="utf-8") as f:
+            json.dump(result, f, ensure_ascii=False, indent=1)
+
+
+if __name__ == "__main__":
+    main()

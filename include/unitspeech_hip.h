@@ -796,6 +796,31 @@ int us_units_fit_update(int mode, const float* centers_in, float* centers_out, c
 int us_units_fit_seed_step(const float* dense, const int64_t* lengths, int B, int Tmax, int K, int D, int step, double u, double* mind,
                            float* centers, int64_t* picked, void* workspace, size_t workspace_bytes, us_stream stream);
 
+/* ---- the recogniser's end: CTC head, greedy decoding, edit distance, csrc/ctc.hip ------------------------------------------------------
+ * What scoring synthesised speech by CER / WER needs after the encoder (us_hubert_forward), as handle-free device calls that only
+ * enqueue on `stream`, allocate nothing and need no scratch.  V in [2, 2048], H a multiple of 4 in [4, 1024], B <= 65535 and at most 2^24
+ * rows per call; us_ctc_packed_bytes returns 0 for anything else and the calls return US_EINVAL.
+ * us_ctc_pack_head: `lm_head` weight [V][H] and bias [V] (NULL: zeros) -> `packed` (us_ctc_packed_bytes): the GEMM operand and the bias.
+ * us_ctc_logits: hidden [B][Tmax][H], lengths [B] (device int64, frames per item; NULL: all Tmax) -> logits [B][Tmax][V] =
+ *   hidden . weight^T + bias in fp32 on the matrix cores, a row's products added in a fixed order that does not depend on where the row
+ *   lies (an item has the same bits alone and in a batch); log_probs [B][Tmax][V] (optional) = log_softmax over V; ids [B][Tmax] int64
+ *   (optional) = the argmax of the logits as written, the lower index on ties (finite logits).  Rows t >= lengths[b] get logits 0,
+ *   log_probs 0 and ids -1, and their features are not read.
+ * us_ctc_collapse: greedy CTC decoding per item over ids [B][Tmax] with lengths [B] (NULL: all Tmax): equal neighbours are merged,
+ *   then `blank` is dropped -> tokens [B][Tmax] and first_frame [B][Tmax] (optional: the frame at which each kept token's run starts),
+ *   zero beyond n[b], and n [B], all int64 on the device.  tokens and first_frame must not alias ids.
+ * us_edit_distance: Levenshtein distance (unit costs) of P pairs hyp [P][Lh] / ref [P][Lr] with n_hyp, n_ref [P] valid tokens (clamped to
+ *   [0, Lh] and [0, Lr]) -> dist [P], exact, all int64 on the device.  Lh and Lr at most 4096, else US_EINVAL; P = 0 does nothing.  Only
+ *   the distance: substitution / deletion / insertion counts depend on which optimal alignment is taken. */
+size_t us_ctc_packed_bytes(int V, int H);
+int us_ctc_pack_head(const float* weight, const float* bias, int V, int H, void* packed, size_t packed_bytes, us_stream stream);
+int us_ctc_logits(const float* hidden, const int64_t* lengths, const void* packed, int B, int Tmax, int V, int H, float* logits,
+                  float* log_probs, int64_t* ids, us_stream stream);
+int us_ctc_collapse(const int64_t* ids, const int64_t* lengths, int B, int Tmax, int64_t blank, int64_t* tokens, int64_t* first_frame,
+                    int64_t* n, us_stream stream);
+int us_edit_distance(const int64_t* hyp, const int64_t* n_hyp, int Lh, const int64_t* ref, const int64_t* n_ref, int Lr, int P, int64_t* dist,
+                     us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

@@ -198,6 +198,11 @@ SIGNATURES = {
                                           C.c_void_p]),
     "us_units_fit_update": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "us_units_fit_seed_step": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "us_ctc_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "us_ctc_pack_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_ctc_logits": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 4),
+    "us_ctc_collapse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "us_edit_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "us_debug_block": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
