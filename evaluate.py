@@ -3,7 +3,7 @@
 its text by character and word error rate, compare its speaker embedding with the reference recording's).
 
     python evaluate.py --filelist LIST --ctc_path CTC.pt --vocab_path vocab.json [--config_path config.json]
-                       [--speaker_encoder_path EMBEDDER.pt] [--batch 16] [--out RESULT.json]
+                       [--speaker_encoder_path EMBEDDER.pt] [--batch 16] [--timestamps] [--out RESULT.json]
     python evaluate.py --synthetic 12 --batch 4
 
 LIST holds one `wav|transcript[|reference_wav]` line per sample.  CTC.pt is a `torch.save`d state dict of `transformers.HubertForCTC` or
@@ -13,6 +13,8 @@ resampled to 16 kHz by the library's `Resample`, sorted by length and transcribe
 transcripts are brought to the vocabulary by `normalize_text`; CER and WER are `unitspeech_amd.asr.error_rates` (corpus rates: sum of
 distances over sum of reference lengths).  With --speaker_encoder_path and the third column, SECS is the cosine similarity of
 `ECAPA_TDNN.embed_wav` between each wav and its reference.  One line per file, then the corpus line; --out writes all of it as JSON.
+--timestamps adds `word_times` to each file's record: the reference text's words with start and end in seconds (20 ms frames), from the forced
+alignment of the text to the recogniser's log-probabilities (`align`); null for a text that is empty or longer than its audio allows.
 
 --synthetic N runs without files: a seeded tiny CTC model, N seeded waveforms, and as transcripts the model's own decodings with a known
 number of edits applied (characters appended, or cut from the end): the distance of each pair is then exactly that number, so the CER
@@ -116,6 +118,41 @@ def similarities(embedder, wavs16, refs16, max_batch):
     return [float((emb["wav", i] * emb["ref", i]).sum()) if r is not None else None for i, r in enumerate(refs16)]
 
 
+FRAME_SECONDS = 0.02             # one encoder frame: 320 samples at 16 kHz
+
+
+def word_spans(text: str):
+    """[(word, first character index, one past its last)] of a normalised transcript, whose characters are its tokens one for one."""
+    spans, i = [], 0
+    for w in text.split(" "):
+        if w:
+            spans.append((w, i, i + len(w)))
+        i += len(w) + 1
+    return spans
+
+
+@torch.no_grad()
+def word_timestamps(model, vocabulary, wavs16, transcripts, batches):
+    """Per file the reference transcript's words with start and end in seconds, from the forced alignment of the transcript to the
+    head's log-probabilities (`align`); None for a file whose transcript is empty or does not fit its frames."""
+    out = [None] * len(wavs16)
+    for idx in batches:
+        x, n = padded_batch(wavs16, idx)
+        ids = [vocabulary.encode(transcripts[i]) for i in idx]
+        tg = torch.zeros(len(idx), max(1, max(len(t) for t in ids)), dtype=torch.int64)
+        for b, t in enumerate(ids):
+            tg[b, :len(t)] = torch.tensor(t, dtype=torch.int64)
+            tg[b, len(t):] = (vocabulary.blank_id + 1) % len(vocabulary)
+        _, score, start, frames = model.align(x, n, tg.to(x.device), torch.tensor([len(t) for t in ids], dtype=torch.int64).to(x.device))
+        score, start, frames = score.cpu(), start.cpu(), frames.cpu()
+        for b, i in enumerate(idx):
+            if not ids[b] or not np.isfinite(float(score[b])):
+                continue
+            out[i] = [{"word": w, "start": round(float(start[b, a]) * FRAME_SECONDS, 2),
+                       "end": round(float(start[b, e - 1] + frames[b, e - 1]) * FRAME_SECONDS, 2)} for w, a, e in word_spans(transcripts[i])]
+    return out
+
+
 def synthetic_model(device, seed: int = 0):
     """A seeded tiny `HubertForCTC` over TINY_VOCAB (the head drawn with unit scale, so that the ids vary) and its vocabulary."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -152,6 +189,7 @@ def main(argv=None):
     ap.add_argument("--speaker_encoder_path", default=None, help="the whole speaker embedder's checkpoint: adds SECS against the third column")
     ap.add_argument("--batch", type=int, default=16, help="most files in one call")
     ap.add_argument("--out", default=None, help="JSON file for the result")
+    ap.add_argument("--timestamps", action="store_true", help="per-word start and end times of the reference text (forced alignment)")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded waveforms through a seeded tiny model")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
@@ -205,11 +243,14 @@ def main(argv=None):
         from voice_conversion import read_wav
         refs16 = [to_16k(*read_wav(r), device, resamplers) if r else None for r in references]
         secs = similarities(embedder, wavs16, refs16, args.batch)
+    words = word_timestamps(model, vocabulary, wavs16, transcripts, batches) if args.timestamps else None
     files = []
-    for (name, _, _), h, t, p, s in zip(items, hyps, transcripts, rates["per_utterance"], secs):
+    for k, ((name, _, _), h, t, p, s) in enumerate(zip(items, hyps, transcripts, rates["per_utterance"], secs)):
         rec = dict(file=name, hypothesis=h, reference=t, **p)
         if s is not None:
             rec["secs"] = s
+        if words is not None:
+            rec["word_times"] = words[k]
         files.append(rec)
         print(f"{name}: CER {p['cer']:.4f} ({p['char_distance']}/{p['chars']})  WER {p['wer']:.4f} ({p['word_distance']}/{p['words']})"
               + (f"  SECS {s:.4f}" if s is not None else "") + f"  | {h!r} <- {t!r}")

@@ -821,6 +821,49 @@ int us_ctc_collapse(const int64_t* ids, const int64_t* lengths, int B, int Tmax,
 int us_edit_distance(const int64_t* hyp, const int64_t* n_hyp, int Lh, const int64_t* ref, const int64_t* n_ref, int Lr, int P, int64_t* dist,
                      us_stream stream);
 
+/* ---- fitting the CTC head: loss, gradient, the head's backward pass, forced alignment, csrc/ctc_train.hip -----------------------------
+ * Handle-free device calls like the ones above: they allocate nothing and only enqueue on `stream`.  Scratch is the caller's, at least
+ * what the matching *_workspace_bytes host function returns (0 for sizes the call refuses); it may hold anything and is reusable as soon
+ * as the call's work on the stream is done.  B <= 65535, at most 2^24 rows (B * Tmax) per call, V in [2, 2048], blank in [0, V).  A target
+ * holds at most 1024 tokens: Lmax > 1024 is US_EINVAL.  frame_lengths [B] (NULL: all Tmax), targets [B][Lmax] and target_lengths [B] are
+ * device int64; lengths are clamped to [0, Tmax] and [0, Lmax].  The extended label sequence of an item with L tokens has S = 2 L + 1
+ * states (blank, token 0, blank, ..., blank).
+ * us_ctc_loss: logits [B][Tmax][V] fp32 (the log-softmax over V is taken inside) -> loss [B] = -log p(target | logits), and, when
+ *   grad_logits [B][Tmax][V] is not NULL, d(sum_b grad_out[b] loss[b]) / d logits = grad_out[b] * (softmax - occupancy); grad_out [B] device
+ *   fp32, NULL: ones.  with_grad of the workspace size says whether grad_logits will be given.  stage = US_CTC_WHOLE is the complete call.
+ *   A training step that learns grad_out only after the loss splits it: US_CTC_FORWARD (grad_logits NULL, workspace sized with_grad = 1)
+ *   writes the loss and leaves alpha in the workspace; US_CTC_BACKWARD (grad_logits given), with the same arguments and that untouched
+ *   workspace, runs the backward sweep alone and may be repeated.  The two give the bits of the whole call.  Rows t >= frame_lengths[b]
+ *   get gradient 0 and are not read.  An item has the same loss and gradient bits alone and inside any batch, and from run to run: the occupancy of a
+ *   vocabulary entry that occurs several times in the target is added in ascending target position, the blank's in a fixed tree over the
+ *   states; there are no float atomics.  An infeasible item (fewer frames than L + the number of adjacent equal target pairs) gets loss
+ *   +inf (0 when zero_infinity != 0) and gradient 0 -- torch.nn.functional.ctc_loss writes NaN gradients there unless zero_infinity is set.
+ *   L = 0 is valid (the all-blank path); so is T = 0 with L = 0 (loss 0).  A target outside [0, V) or equal to the blank makes its item's
+ *   loss NaN and its gradient 0; nothing is read out of bounds.
+ * us_ctc_head_backward: grad_logits [B][Tmax][V], hidden [B][Tmax][H] (H a multiple of 4 in [4, 1024]), lengths as in us_ctc_logits ->
+ *   d_weight [V][H] = sum over live rows of g[row][v] hidden[row][h], d_bias [V] = sum of g[row][v], and, when d_hidden is not NULL,
+ *   d_hidden [B][Tmax][H] = g . weight (weight [V][H] as given to us_ctc_pack_head; needed only then).  Both products run on the fp32 matrix
+ *   cores.  Rows t >= lengths[b] are not read, contribute nothing and get d_hidden 0.  The sum over rows is taken per chunk of rows into
+ *   the workspace and the chunks are then added in order: the same bits in every run (the chunking depends on B * Tmax).
+ * us_ctc_forced_align: scores [B][Tmax][V] fp32 (log-probabilities, or any additive score) -> the best path through the states: path
+ *   [B][Tmax] int64 = the vocabulary entry emitted at each frame, blank included, -1 at t >= frame_lengths[b]; score [B] = the sum of the
+ *   path's scores, added in frame order in fp32; start [B][Lmax] and frames [B][Lmax] int64 = the first frame of each target token and the
+ *   number of frames on it (0 beyond target_lengths[b]).  Tie rule: among equal predecessors staying in s wins over s - 1, and s - 1 over
+ *   s - 2; of the two end states the last label wins over the final blank.  An infeasible item gets score -inf, a path of -1 and frames 0;
+ *   a target outside [0, V) or equal to the blank gives score NaN and the same. */
+enum { US_CTC_WHOLE = 0, US_CTC_FORWARD = 1, US_CTC_BACKWARD = 2 };
+size_t us_ctc_loss_workspace_bytes(int B, int Tmax, int Lmax, int with_grad);
+int us_ctc_loss(const float* logits, const int64_t* frame_lengths, const int64_t* targets, const int64_t* target_lengths, const float* grad_out,
+                int B, int Tmax, int V, int Lmax, int64_t blank, int zero_infinity, int stage, float* loss, float* grad_logits, void* workspace,
+                size_t workspace_bytes, us_stream stream);
+size_t us_ctc_head_backward_workspace_bytes(int B, int Tmax, int V, int H);
+int us_ctc_head_backward(const float* grad_logits, const float* hidden, const int64_t* lengths, const float* weight, int B, int Tmax, int V,
+                         int H, float* d_weight, float* d_bias, float* d_hidden, void* workspace, size_t workspace_bytes, us_stream stream);
+size_t us_ctc_align_workspace_bytes(int B, int Tmax, int Lmax);
+int us_ctc_forced_align(const float* scores, const int64_t* frame_lengths, const int64_t* targets, const int64_t* target_lengths, int B, int Tmax,
+                        int V, int Lmax, int64_t blank, int64_t* path, float* score, int64_t* start, int64_t* frames, void* workspace,
+                        size_t workspace_bytes, us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

@@ -56,6 +56,7 @@ class us_resample_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("orig_freq", "new_freq", "width")]
 
 
+US_CTC_WHOLE, US_CTC_FORWARD, US_CTC_BACKWARD = 0, 1, 2
 US_HUBERT_MAX_CONV = 8
 US_HUBERT_NORM_GROUP, US_HUBERT_NORM_LAYER = 0, 1
 
@@ -203,6 +204,13 @@ SIGNATURES = {
     "us_ctc_logits": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 4),
     "us_ctc_collapse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "us_edit_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "us_ctc_loss_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "us_ctc_loss": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                              C.c_void_p]),
+    "us_ctc_head_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "us_ctc_head_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "us_ctc_align_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "us_ctc_forced_align": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "us_debug_block": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -6,6 +6,8 @@
                                   adapter), with exactly their `state_dict` keys, around the library's `HubertModel`
   CTCVocabulary, normalize_text   HF's `vocab.json`; ids -> text, text -> ids, and the reference text brought to the vocabulary
   edit_distance, error_rates      Levenshtein distance per pair on the device; corpus and per-utterance CER / WER
+  ctc_loss, forced_align          fitting the head on frozen features (csrc/ctc_train.hip): the CTC loss, differentiable in the logits, and
+                                  the best alignment of a transcript to the frames; `CTCHead(..., trainable=True)` is the head that trains
 
 The recogniser's contract is HF's: ids are the argmax of the fp32 logits (the lower index on ties).  Nothing is read back to the host
 between the encoder, the head and the collapse.  There is no CPU fallback: a tensor that is not on a GPU raises.
@@ -23,9 +25,10 @@ from . import _lib
 from .hubert import _BASE, HubertModel
 
 __all__ = ["CTCHead", "HubertForCTC", "Wav2Vec2ForCTC", "load_ctc_checkpoint", "CTCVocabulary", "normalize_text", "edit_distance",
-           "error_rates"]
+           "error_rates", "ctc_loss", "forced_align"]
 
 MAX_V, MAX_H, MAX_TOKENS = 2048, 1024, 4096
+MAX_TARGET = 1024                 # tokens per target of ctc_loss / forced_align
 
 
 def _stream():
@@ -75,17 +78,21 @@ class CTCHead(torch.nn.Module):
     """`lm_head`: `weight` [V, H] and `bias` [V].  V in [2, 2048], H a multiple of 4 up to 1024.
 
     `forward(features [B, F, H], frame_lengths=None)` -> logits [B, F, V] (`log_probs=True`: `(logits, log_probs)`); rows at or beyond
-    frame_lengths[b] are 0.  `decode(...)` -> `(tokens [B, F], n [B])`, greedy."""
+    frame_lengths[b] are 0.  `decode(...)` -> `(tokens [B, F], n [B])`, greedy.
 
-    def __init__(self, hidden_size: int, vocab_size: int):
+    `trainable=True` (the `Encoder(..., trainable=True)` convention): the two parameters require grad, and `forward` with gradients
+    enabled records `us_ctc_head_backward` as the logits' backward; the features get a gradient only when they require one."""
+
+    def __init__(self, hidden_size: int, vocab_size: int, trainable: bool = False):
         super().__init__()
         H, V = int(hidden_size), int(vocab_size)
         if not 2 <= V <= MAX_V:
             raise ValueError(f"CTCHead: vocab_size = {V}; the library takes 2 to {MAX_V}")
         if H % 4 or not 4 <= H <= MAX_H:
             raise ValueError(f"CTCHead: hidden_size = {H}; the library takes a multiple of 4 up to {MAX_H}")
-        self.weight = torch.nn.Parameter(torch.zeros(V, H), requires_grad=False)
-        self.bias = torch.nn.Parameter(torch.zeros(V), requires_grad=False)
+        self.trainable = bool(trainable)
+        self.weight = torch.nn.Parameter(torch.zeros(V, H), requires_grad=self.trainable)
+        self.bias = torch.nn.Parameter(torch.zeros(V), requires_grad=self.trainable)
         self._packed, self._tag = None, None
 
     def packed(self, dev):
@@ -125,7 +132,10 @@ class CTCHead(torch.nn.Module):
         return logits, lp, out_ids, lens
 
     def forward(self, features, frame_lengths=None, log_probs: bool = False):
-        logits, lp, _, _ = self._run(features, frame_lengths, log_probs, False)
+        if self.trainable and torch.is_grad_enabled() and (self.weight.requires_grad or self.bias.requires_grad or features.requires_grad):
+            logits, lp = _HeadFn.apply(self, features, frame_lengths, log_probs, self.weight, self.bias)   # lp carries no gradient
+        else:
+            logits, lp, _, _ = self._run(features, frame_lengths, log_probs, False)
         return (logits, lp) if log_probs else logits
 
     def argmax(self, features, frame_lengths=None):
@@ -140,10 +150,150 @@ class CTCHead(torch.nn.Module):
         return out + (lp,) if log_probs else out
 
 
+class _HeadFn(torch.autograd.Function):
+    """logits = us_ctc_logits(features) with us_ctc_head_backward as its backward (dW, db, and dX when the features require grad)."""
+
+    @staticmethod
+    def forward(ctx, head, features, frame_lengths, log_probs, weight, bias):
+        logits, lp, _, lens = head._run(features, frame_lengths, log_probs, False)
+        ctx.save_for_backward(features, weight)
+        ctx.lens = lens
+        if lp is not None:
+            ctx.mark_non_differentiable(lp)
+        return logits, lp
+
+    @staticmethod
+    def backward(ctx, g, _):
+        features, weight = ctx.saved_tensors
+        dev = g.device
+        B, F, V = g.shape
+        H = weight.shape[1]
+        g = g.detach().to(torch.float32).contiguous()
+        x = features.detach().to(torch.float32).contiguous()
+        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        dw, db = torch.empty(V, H, device=dev), torch.empty(V, device=dev)
+        dx = torch.empty(B, F, H, device=dev) if ctx.needs_input_grad[1] else None
+        lib = _lib.load()
+        n = int(lib.us_ctc_head_backward_workspace_bytes(B, F, V, H))
+        ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.us_ctc_head_backward(g.data_ptr(), x.data_ptr(), None if ctx.lens is None else ctx.lens.data_ptr(), w.data_ptr(), B, F, V, H,
+                                          dw.data_ptr(), db.data_ptr(), None if dx is None else dx.data_ptr(), ws.data_ptr(), n, _stream())
+        _lib.check(rc, None, "us_ctc_head_backward")
+        return (None, None if dx is None else dx.to(features.dtype), None, None, dw.to(weight.dtype) if ctx.needs_input_grad[4] else None,
+                db if ctx.needs_input_grad[5] else None)
+
+
+def _sequences(what, x, targets, frame_lengths, target_lengths):
+    """The checked device arguments of a loss / alignment call: x [B, T, V] fp32, targets [B, Lmax] int64 and the two length vectors."""
+    _need_gpu(x, what)
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"{what}: expected a non-empty [B, T, V], got {tuple(x.shape)}")
+    dev = x.device
+    B = x.shape[0]
+    tg = _i64(targets, dev)
+    if tg.dim() != 2 or tg.shape[0] != B:
+        raise ValueError(f"{what}: targets {tuple(tg.shape)} must be [{B}, Lmax]")
+    if target_lengths is None:
+        raise ValueError(f"{what}: target_lengths is needed")
+    return x.detach().to(torch.float32).contiguous(), tg, _lengths(frame_lengths, B, dev, what), _lengths(target_lengths, B, dev, what)
+
+
+def _ctc_loss_call(x, tg, fl, tl, blank, zero_infinity, stage=_lib.US_CTC_WHOLE, grad_out=None, ws=None, with_grad=False):
+    """One us_ctc_loss call -> (loss, grad_logits or None, workspace).  US_CTC_FORWARD leaves alpha in the workspace it returns;
+    US_CTC_BACKWARD takes that workspace and `grad_out` and runs the backward sweep alone; US_CTC_WHOLE with `with_grad` does both at once."""
+    dev = x.device
+    B, T, V = x.shape
+    Lmax = int(tg.shape[1])
+    lib = _lib.load()
+    with_grad = bool(with_grad) or stage == _lib.US_CTC_BACKWARD
+    n = int(lib.us_ctc_loss_workspace_bytes(B, T, Lmax, int(with_grad or stage == _lib.US_CTC_FORWARD)))
+    if ws is None:
+        ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    loss = torch.empty(B, device=dev)
+    grad = torch.empty(B, T, V, device=dev) if with_grad else None
+    with torch.cuda.device(dev):
+        rc = lib.us_ctc_loss(x.data_ptr(), None if fl is None else fl.data_ptr(), tg.data_ptr() if Lmax else None, tl.data_ptr(),
+                             None if grad_out is None else grad_out.data_ptr(), B, T, V, Lmax, int(blank), int(bool(zero_infinity)), stage,
+                             loss.data_ptr(), None if grad is None else grad.data_ptr(), ws.data_ptr(), n, _stream())
+    _lib.check(rc, None, "us_ctc_loss")
+    return loss, grad, ws
+
+
+class _CTCLossFn(torch.autograd.Function):
+    """The per-item losses.  The forward keeps alpha in the call's workspace; the backward runs the backward sweep alone on it, with the
+    incoming per-item gradient as `grad_out`, so the scaled gradient is written by the kernel itself."""
+
+    @staticmethod
+    def forward(ctx, logits, tg, fl, tl, blank, zero_infinity):
+        x = logits.detach().to(torch.float32).contiguous()
+        loss, _, ws = _ctc_loss_call(x, tg, fl, tl, blank, zero_infinity, _lib.US_CTC_FORWARD)
+        ctx.save_for_backward(x)
+        ctx.args = (tg, fl, tl, blank, zero_infinity, ws)
+        ctx.dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        (x,) = ctx.saved_tensors
+        tg, fl, tl, blank, zero_infinity, ws = ctx.args
+        go = go.detach().to(torch.float32).contiguous()
+        _, grad, _ = _ctc_loss_call(x, tg, fl, tl, blank, zero_infinity, _lib.US_CTC_BACKWARD, go, ws)
+        return grad.to(ctx.dtype), None, None, None, None, None
+
+
+def ctc_loss(logits, targets, frame_lengths, target_lengths, blank: int = 0, reduction: str = "mean", zero_infinity: bool = False):
+    """The CTC loss of logits [B, T, V] (batch-first; the log-softmax is taken inside) against targets [B, Lmax] int64, with frame_lengths
+    [B] (None: all T) and target_lengths [B]; at most 1024 tokens per target.  Differentiable in `logits`.
+
+    `reduction`: "none" -> [B]; "sum"; "mean" as torch has it: each item divided by its target length (clamped to 1), then the average.
+    An infeasible item has loss +inf (0 with `zero_infinity`) and a ZERO gradient, where torch writes NaN gradients unless
+    `zero_infinity` is set.  An item has the same loss and gradient bits alone and in any batch."""
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError(f"ctc_loss: reduction = {reduction!r}; expected 'none', 'sum' or 'mean'")
+    _, tg, fl, tl = _sequences("ctc_loss", logits, targets, frame_lengths, target_lengths)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        loss = _CTCLossFn.apply(logits, tg, fl, tl, int(blank), bool(zero_infinity))
+    else:
+        loss = _ctc_loss_call(logits.detach().to(torch.float32).contiguous(), tg, fl, tl, blank, zero_infinity)[0]
+    if reduction == "none":
+        return loss
+    if reduction == "sum":
+        return loss.sum()
+    return (loss / tl.clamp(min=1).to(loss.dtype)).mean()
+
+
+@torch.no_grad()
+def forced_align(scores, targets, frame_lengths, target_lengths, blank: int = 0):
+    """The best alignment of targets [B, Lmax] to the frames of scores [B, T, V] (log-probabilities, or any additive score) ->
+    (path [B, T] int64: the entry emitted at each frame, blank included, -1 beyond the item's frames; score [B]: the path's summed score;
+    start [B, Lmax], frames [B, Lmax] int64: the first frame of each target token and the number of frames on it).
+
+    Ties: staying in a state wins over advancing by one, that over skipping a blank; the last label wins over the final blank as the end.
+    An infeasible item has score -inf, a path of -1 and frames 0."""
+    x, tg, fl, tl = _sequences("forced_align", scores, targets, frame_lengths, target_lengths)
+    dev = x.device
+    B, T, V = x.shape
+    Lmax = int(tg.shape[1])
+    lib = _lib.load()
+    n = int(lib.us_ctc_align_workspace_bytes(B, T, Lmax))
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    path = torch.empty(B, T, dtype=torch.int64, device=dev)
+    score = torch.empty(B, device=dev)
+    start = torch.empty(B, Lmax, dtype=torch.int64, device=dev)
+    frames = torch.empty(B, Lmax, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.us_ctc_forced_align(x.data_ptr(), None if fl is None else fl.data_ptr(), tg.data_ptr() if Lmax else None, tl.data_ptr(), B, T, V,
+                                     Lmax, int(blank), path.data_ptr(), score.data_ptr(), start.data_ptr() if Lmax else None,
+                                     frames.data_ptr() if Lmax else None, ws.data_ptr(), n, _stream())
+    _lib.check(rc, None, "us_ctc_forced_align")
+    return path, score, start, frames
+
+
 class _EncoderForCTC(torch.nn.Module):
     _prefix = ""
 
-    def __init__(self, vocab_size: int = 32, pad_token_id: int = 0, add_adapter: bool = False, **config):
+    def __init__(self, vocab_size: int = 32, pad_token_id: int = 0, add_adapter: bool = False, trainable: bool = False, **config):
         super().__init__()
         if add_adapter:
             raise ValueError(f"{type(self).__name__}: the adapter (add_adapter=True) is not built")
@@ -151,7 +301,7 @@ class _EncoderForCTC(torch.nn.Module):
         if not 0 <= int(pad_token_id) < int(vocab_size):
             raise ValueError(f"{type(self).__name__}: pad_token_id {pad_token_id} is not in the vocabulary of {vocab_size}")
         self.add_module(self._prefix, encoder)
-        self.lm_head = CTCHead(encoder.config["hidden_size"], vocab_size)
+        self.lm_head = CTCHead(encoder.config["hidden_size"], vocab_size, trainable=trainable)
         self.vocab_size, self.pad_token_id = int(vocab_size), int(pad_token_id)
 
     @classmethod
@@ -193,6 +343,21 @@ class _EncoderForCTC(torch.nn.Module):
         greedy collapse with `pad_token_id` as the blank, with no read back in between."""
         v, frames = self._frames(wav, lengths)
         return self.lm_head.decode(self.encoder(wav, v, normalize=normalize), frames, self.pad_token_id, first_frame)
+
+    def loss(self, wav, lengths, targets, target_lengths, normalize: bool = False, reduction: str = "mean", zero_infinity: bool = False):
+        """The CTC loss of the transcripts targets [B, Lmax] int64 (target_lengths [B]) with `pad_token_id` as the blank.  The encoder is
+        frozen (it runs without gradients); a head built with `trainable=True` gets its gradients from `.backward()`."""
+        v, frames = self._frames(wav, lengths)
+        with torch.no_grad():
+            features = self.encoder(wav, v, normalize=normalize)
+        return ctc_loss(self.lm_head(features, frames), targets, frames, target_lengths, self.pad_token_id, reduction, zero_infinity)
+
+    @torch.no_grad()
+    def align(self, wav, lengths, targets, target_lengths, normalize: bool = False):
+        """-> `forced_align`'s (path, score, start, frames) of the transcripts on the head's log-probabilities, in frames of 20 ms."""
+        v, frames = self._frames(wav, lengths)
+        _, lp = self.lm_head(self.encoder(wav, v, normalize=normalize), frames, log_probs=True)
+        return forced_align(lp, targets, frames, target_lengths, self.pad_token_id)
 
 
 class HubertForCTC(_EncoderForCTC):
