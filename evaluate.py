@@ -15,6 +15,10 @@ distances over sum of reference lengths).  With --speaker_encoder_path and the t
 `ECAPA_TDNN.embed_wav` between each wav and its reference.  One line per file, then the corpus line; --out writes all of it as JSON.
 --timestamps adds `word_times` to each file's record: the reference text's words with start and end in seconds (20 ms frames), from the forced
 alignment of the text to the recogniser's log-probabilities (`align`); null for a text that is empty or longer than its audio allows.
+--sv56 [--ndb N] first brings every loaded sample to N dB active speech level (ITU-T P.56, default -26) on the device, in length-sorted
+ragged batches at the file's own rate and by the reference's int16 route (`unitspeech_amd.level.normalize_level(..., via_int16=True,
+out_int16=True)`), before the recogniser and the speaker encoder see it: the reference notebook's "with sv56" row.  The reference
+recordings of the third column are left as they are.
 
 --synthetic N runs without files: a seeded tiny CTC model, N seeded waveforms, and as transcripts the model's own decodings with a known
 number of edits applied (characters appended, or cut from the end): the distance of each pair is then exactly that number, so the CER
@@ -80,6 +84,25 @@ def to_16k(wav, rate, device, resamplers):
     if rate not in resamplers:
         resamplers[rate] = Resample(rate, 16000).to(device)
     return resamplers[rate](wav)
+
+
+@torch.no_grad()
+def normalize_items(items, ndb, max_batch, device):
+    """[(name, waveform, rate)] -> the same with every waveform brought to `ndb` dB active speech level as the int16 file the reference's
+    sv56 step leaves would read back (s / 32768, fp32, on the device), and per item (level_db, gain, clipped)."""
+    from unitspeech_amd.level import normalize_level
+    out, levels = list(items), [None] * len(items)
+    for rate in sorted({r for _, _, r in items}):
+        group = [i for i, it in enumerate(items) if it[2] == rate]
+        for batch in plan_batches([len(items[i][1]) for i in group], max_batch):
+            idx = [group[j] for j in batch]
+            x, n = padded_batch([torch.as_tensor(items[i][1]).float().to(device) for i in idx], list(range(len(idx))))
+            y, lv = normalize_level(x, rate, ndb, lengths=n, via_int16=True, out_int16=True)
+            y = y.to(torch.float32) / 32768.0
+            for b, (i, level, gain, clipped) in enumerate(zip(idx, lv.level_db.tolist(), lv.gain.tolist(), lv.clipped.tolist())):
+                out[i] = (items[i][0], y[b, :n[b]].clone(), rate)
+                levels[i] = (level, gain, clipped)
+    return out, levels
 
 
 def padded_batch(wavs16, idx):
@@ -190,6 +213,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16, help="most files in one call")
     ap.add_argument("--out", default=None, help="JSON file for the result")
     ap.add_argument("--timestamps", action="store_true", help="per-word start and end times of the reference text (forced alignment)")
+    ap.add_argument("--sv56", action="store_true", help="normalise every sample's active speech level before it is scored")
+    ap.add_argument("--ndb", type=float, default=-26.0, help="--sv56: the target level in dB relative to full scale")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded waveforms through a seeded tiny model")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
@@ -223,6 +248,10 @@ def main(argv=None):
         if args.speaker_encoder_path and any(references):
             from unitspeech_amd.speaker_encoder import load_speaker_embedder_checkpoint
             embedder = load_speaker_embedder_checkpoint(args.speaker_encoder_path, device)
+    if args.sv56:
+        items, levels = normalize_items(items, args.ndb, args.batch, device)
+        for (name, _, _), (level, gain, clipped) in zip(items, levels):
+            print(f"{name}: sv56 level {level:.2f} dB, gain {gain:.4f}, {clipped} clipped samples")
     wavs16 = []
     for name, wav, rate in items:
         w = to_16k(wav, rate, device, resamplers)

@@ -864,6 +864,37 @@ int us_ctc_forced_align(const float* scores, const int64_t* frame_lengths, const
                         int V, int Lmax, int64_t blank, int64_t* path, float* score, int64_t* start, int64_t* frames, void* workspace,
                         size_t workspace_bytes, us_stream stream);
 
+/* ---- active speech level and gain normalisation: ITU-T P.56 method B, what `sv56` does, csrc/level.hip ---------------------------------
+ * Handle-free device calls like the ones above: they allocate nothing, only enqueue on `stream`, and nothing is read back between
+ * measuring and applying.  Scratch is the caller's, at least us_level_workspace_bytes(B, Tmax) (0 for what the calls refuse); it may hold
+ * anything, and the two calls may share it.  B in [1, 65535], Tmax in [1, 2^30], sample_rate > 0, dtypes US_LEVEL_F32 (samples in units of
+ * full scale) or US_LEVEL_I16 (s / 32768); anything else is US_EINVAL.  wav [B][Tmax]; lengths [B] device int64, clamped to [0, Tmax],
+ * NULL: every item has Tmax samples; samples at or past an item's length are never read.  quantize_input != 0 (fp32 input only) first
+ * takes the reference's route to int16, trunc(x * 32767) with the product in fp32, held to the int16 range.
+ * The measurement, all in fp64: g = exp(-1 / (0.03 f)); p[k] = g p[k-1] + (1-g) |x[k]|, q[k] = g q[k-1] + (1-g) p[k] from p = q = 0;
+ * thresholds c[j] = 2^(j-15), j = 0..14; a[j] = the number of k with k - last_j(k) <= I = floor(0.2 f + 0.5), last_j(k) the last index <= k
+ * with q >= c[j] (nothing is counted before the first); A[j] = 10 log10(sum x^2 / a[j] + 1e-20) (a[j] = 0 taken as 1e-20), D[j] = A[j] -
+ * 20 log10 c[j]; the level is A interpolated linearly at D = 15.9 dB on the first segment [j-1, j] with D[j] <= 15.9; -100 when a[0] = 0,
+ * D[0] < 15.9 or there is no such segment.  An item is cut into chunks of us_level_chunk() samples from its own start and the chunks are
+ * combined in order by separate launches (no workgroup waits for another): an item has the same bits alone, inside any batch and from
+ * run to run.
+ * us_level_measure: -> stats [B][8] fp64 = level_db, activity = 10^((rms_db - level_db) / 10) (0 at level -100), rms_db = 10 log10(sum x^2
+ *   / n + 1e-20), peak = max |x|, mean, max, min, n; counts [B][15] int64 = a (optional).  An item of length 0: level -100, activity 0,
+ *   rms_db -100, the rest 0.  An item with a non-finite sample: level, activity, rms_db and peak NaN, counts 0.
+ * us_level_apply: wav, in_dtype, quantize_input and lengths as given to us_level_measure, stats as it wrote them -> out [B][Tmax] of
+ *   out_dtype: factor = 10^((ndb - level_db) / 20), or 1 when the level is -100 or NaN (such an item comes back unchanged).  fp32 out =
+ *   x * factor computed in fp64 and rounded once, not clamped; int16 out = x * factor * 32768 rounded half away from zero and saturated
+ *   to [-32768, 32767], a saturated sample counting as clipped.  Samples at or past an item's length are written as 0, nothing past the
+ *   row.  gain [B] fp64 = factor and clipped [B] int64 (both optional).  16-byte loads and stores when wav and out are 16-byte aligned and
+ *   Tmax is a multiple of 8, single samples otherwise, with the same values.  out must not overlap wav. */
+enum { US_LEVEL_F32 = 0, US_LEVEL_I16 = 1 };
+int us_level_chunk(void);
+size_t us_level_workspace_bytes(int B, int Tmax);
+int us_level_measure(const void* wav, int in_dtype, int quantize_input, const int64_t* lengths, int B, int Tmax, int sample_rate, double* stats,
+                     int64_t* counts, void* workspace, size_t workspace_bytes, us_stream stream);
+int us_level_apply(const void* wav, int in_dtype, int quantize_input, const int64_t* lengths, int B, int Tmax, const double* stats, double ndb,
+                   void* out, int out_dtype, double* gain, int64_t* clipped, void* workspace, size_t workspace_bytes, us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

@@ -12,6 +12,8 @@ Two modes:
   --hip_vocoder the BigVGAN vocoder on the HIP library (unitspeech_amd.vocoder): with --synthetic it vocodes the mel with seeded
                 weights (config: --vocoder_config, default the 22 kHz / 80-band large generator) and also writes the wav; in the
                 default mode it loads the reference's vocoder checkpoint and config instead of calling the reference's get_vocoder.
+  --sv56        wherever a wav is written it first goes the reference's way to int16 and through the active-speech-level normalisation
+                (ITU-T P.56, unitspeech_amd.level) to --ndb dB (default -26), as the reference's sv56_inplace.py step does.
 """
 from __future__ import annotations
 
@@ -53,6 +55,9 @@ def main():
     ap.add_argument("--hip_vocoder", action="store_true", help="run BigVGAN on the HIP library (with --synthetic: seeded weights, writes the wav)")
     ap.add_argument("--vocoder_config", type=str, default=None,
                     help="--synthetic --hip_vocoder: generator config JSON (default: the 22 kHz / 80-band large BigVGAN)")
+    ap.add_argument("--sv56", action="store_true",
+                    help="bring the written wav to --ndb dB active speech level (unitspeech_amd.level, the reference's sv56 step) and write int16")
+    ap.add_argument("--ndb", type=float, default=-26.0, help="--sv56: the target level in dB relative to full scale")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -160,8 +165,17 @@ def main():
         print(f"saved mel-spectrogram to {out}" + ("" if vocoder is not None else " (no vocoder in --synthetic mode without --hip_vocoder)"))
     if vocoder is not None:
         from scipy.io.wavfile import write
-        audio = vocoder.forward(mel).cpu().squeeze().clamp(-1, 1).numpy()
-        write(args.generated_sample_path, int(vocoder.h.get("sampling_rate", 22050)) if args.hip_vocoder else 22050, audio)
+        rate = int(vocoder.h.get("sampling_rate", 22050)) if args.hip_vocoder else 22050
+        if args.sv56:
+            # the reference's write + sv56_inplace.py: the float waveform goes to int16 by truncation, then to the target level, on the device
+            from unitspeech_amd.level import normalize_level
+            audio, info = normalize_level(vocoder.forward(mel).reshape(-1).clamp(-1, 1), rate, args.ndb, via_int16=True, out_int16=True)
+            audio = audio.cpu().numpy()
+            print(f"sv56: level {float(info.level_db[0]):.2f} dB -> {args.ndb:g} dB, gain {float(info.gain[0]):.4f}, "
+                  f"{int(info.clipped[0])} clipped samples")
+        else:
+            audio = vocoder.forward(mel).cpu().squeeze().clamp(-1, 1).numpy()
+        write(args.generated_sample_path, rate, audio)
         print(f"saved {args.generated_sample_path}")
 
 

@@ -13,6 +13,10 @@ a shorter item holds no silence past its own end, so the vocoder takes each item
 vocoded alone.  Written to DIR: `<name>.wav` (float32, the vocoder's sampling rate, clamped to [-1, 1], `y_lengths[b] * hop` samples) and,
 with --dump_mel, `<name>.mel.npy`, the item's [num_mels, y_lengths[b]] slice of the de-normalised mel.
 
+--sv56 [--ndb N] brings each utterance to N dB active speech level (ITU-T P.56, default -26; the reference's sv56 step) on the device: the
+batch goes from the vocoder's output and lengths through `unitspeech_amd.level.normalize_level(..., via_int16=True, out_int16=True)` in one
+call, and `<name>.wav` is then int16.  --keep_raw with --sv56 also writes `<name>.raw.wav`, the int16 before the normalisation.
+
 --synthetic N runs without checkpoints or a phonemiser, on the stand-ins of `inference.py --synthetic --hip_vocoder`: N seeded sentences
 of seeded lengths, seeded decoder weights, the closed-form text encoder / duration predictor (`unitspeech_amd.frontend`) and a seeded
 BigVGAN (the 22 kHz / 80-band base generator unless --vocoder_config names another).
@@ -95,9 +99,10 @@ def pad_ids(ids, device):
 
 @torch.no_grad()
 def synthesize(decoder, text_encoder, duration_predictor, vocoder, ids, spk_emb, mel_range, n_down, max_batch, max_padded_frames,
-               frames_per_symbol=6, **tts_kw):
+               frames_per_symbol=6, sv56_ndb=None, keep_raw=False, rate=22050, **tts_kw):
     """ids: one id list per utterance -> ([(wav [n * hop] on the host, clamped; mel [num_mels, n] on the host)] in the order given, the
-    batches as `plan_batches` cut them)."""
+    batches as `plan_batches` cut them).  With `sv56_ndb` the wav is the int16 of the level normalisation and a third entry follows:
+    (level_db, gain, clipped, the un-normalised int16 wav or None)."""
     device = spk_emb.device
     batches = plan_batches([len(v) for v in ids], max_batch, max_padded_frames, frames_per_symbol)
     out = [None] * len(ids)
@@ -108,10 +113,22 @@ def synthesize(decoder, text_encoder, duration_predictor, vocoder, ids, spk_emb,
             phoneme=phoneme, phoneme_lengths=phoneme_lengths, spk_emb=spk, text_encoder=text_encoder, duration_predictor=duration_predictor,
             num_downsamplings_in_unet=n_down, mel_range=mel_range, return_lengths=True, **tts_kw)
         frames = y_lengths.tolist()                                   # one read for the vocoder's launch and the crops below
-        wav = vocoder.forward(mel, lengths=frames).clamp(-1, 1).cpu()
+        wav = vocoder.forward(mel, lengths=frames).clamp(-1, 1)
+        if sv56_ndb is not None:
+            from unitspeech_amd.level import normalize_level
+            n = y_lengths * vocoder.hop                                  # stays on the device: nothing is read back before the gain is applied
+            norm, info = normalize_level(wav, rate, sv56_ndb, lengths=n, via_int16=True, out_int16=True)
+            raw = (wav * 32767).to(torch.int16).cpu() if keep_raw else None
+            norm, level, gain, clipped = norm.cpu(), info.level_db.tolist(), info.gain.tolist(), info.clipped.tolist()
+        wav = wav.cpu()
         mel = mel.cpu()
         for b, i in enumerate(idx):
-            out[i] = (wav[b, 0, :frames[b] * vocoder.hop].clone(), mel[b, :, :frames[b]].clone())
+            n = frames[b] * vocoder.hop
+            if sv56_ndb is None:
+                out[i] = (wav[b, 0, :n].clone(), mel[b, :, :frames[b]].clone())
+            else:
+                out[i] = (norm[b, 0, :n].clone(), mel[b, :, :frames[b]].clone(),
+                          (level[b], gain[b], clipped[b], None if raw is None else raw[b, 0, :n].clone()))
     return out, batches
 
 
@@ -123,6 +140,9 @@ def main():
     ap.add_argument("--max_padded_frames", type=int, default=16384, help="most mel frames in one padded batch, as estimated from the symbols")
     ap.add_argument("--frames_per_symbol", type=int, default=6, help="the estimate's frames per symbol")
     ap.add_argument("--dump_mel", action="store_true", help="also write <name>.mel.npy")
+    ap.add_argument("--sv56", action="store_true", help="normalise each utterance's active speech level on the device; <name>.wav is int16")
+    ap.add_argument("--ndb", type=float, default=-26.0, help="--sv56: the target level in dB relative to full scale")
+    ap.add_argument("--keep_raw", action="store_true", help="--sv56: also write <name>.raw.wav, the int16 before the normalisation")
     ap.add_argument("--ID", type=int, default=-10, help="the speaker ID (a fine-tuned decoder of the reference checkout when >= 0)")
     ap.add_argument("--text_gradient_scale", type=float, default=1.0)
     ap.add_argument("--spk_gradient_scale", type=float, default=1.0)
@@ -192,17 +212,24 @@ def main():
         phonemizer = get_phonemizer(rcfg.inference.language)
         ids = [intersperse(cleaned_text_to_sequence(phonemize(text, phonemizer)), len(symbols)) for _, text in items]
     results, batches = synthesize(decoder, text_encoder, duration_predictor, vocoder, ids, spk_emb.reshape(1, 1, -1), mel_range, n_down, args.batch,
-                                  args.max_padded_frames, args.frames_per_symbol, diffusion_steps=args.diffusion_steps,
+                                  args.max_padded_frames, args.frames_per_symbol, sv56_ndb=args.ndb if args.sv56 else None,
+                                  keep_raw=args.keep_raw, rate=int(vocoder.h.get("sampling_rate", 22050)), diffusion_steps=args.diffusion_steps,
                                   length_scale=args.length_scale, text_gradient_scale=args.text_gradient_scale,
                                   spk_gradient_scale=args.spk_gradient_scale)
     from scipy.io.wavfile import write
     os.makedirs(args.out, exist_ok=True)
     rate = int(vocoder.h.get("sampling_rate", 22050))
-    for (name, _), (wav, mel) in zip(items, results):
+    for (name, _), res in zip(items, results):
+        wav, mel = res[0], res[1]
         write(os.path.join(args.out, f"{name}.wav"), rate, wav.numpy())
         if args.dump_mel:
             np.save(os.path.join(args.out, f"{name}.mel.npy"), mel.numpy())
-    frames = [int(mel.shape[1]) for _, mel in results]
+        if args.sv56:
+            level, gain, clipped, raw = res[2]
+            if raw is not None:
+                write(os.path.join(args.out, f"{name}.raw.wav"), rate, raw.numpy())
+            print(f"{name}: level {level:.2f} dB, gain {gain:.4f}, {clipped} clipped samples")
+    frames = [int(res[1].shape[1]) for res in results]
     padded = sum(len(b) * max(frames[i] for i in b) for b in batches)
     print(f"{len(items)} utterances in {len(batches)} batches ({sum(frames)} mel frames, {padded} padded, "
           f"{sum(frames) * vocoder.hop / rate:.1f} s of audio) -> {args.out}")

@@ -57,6 +57,7 @@ class us_resample_config(C.Structure):
 
 
 US_CTC_WHOLE, US_CTC_FORWARD, US_CTC_BACKWARD = 0, 1, 2
+US_LEVEL_F32, US_LEVEL_I16 = 0, 1
 US_HUBERT_MAX_CONV = 8
 US_HUBERT_NORM_GROUP, US_HUBERT_NORM_LAYER = 0, 1
 
@@ -211,6 +212,12 @@ SIGNATURES = {
     "us_ctc_head_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "us_ctc_align_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "us_ctc_forced_align": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "us_level_chunk": (C.c_int, []),
+    "us_level_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "us_level_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
+    "us_level_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_debug_block": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

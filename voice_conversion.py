@@ -17,6 +17,10 @@ The flags are the reference's, plus: --contentvec_path, a local state dict in `t
 --out DIR for several sources (--source_path may be given more than once; the outputs are DIR/<source name>.wav).  The source is read
 with scipy.io.wavfile (PCM or float wav; several channels are averaged) and resampled by the library's own `Resample`, not by librosa.
 
+--sv56 [--ndb N] brings each converted waveform to N dB active speech level (ITU-T P.56, default -26; the reference's sv56 step): the batch
+goes from the vocoder's output and lengths through `unitspeech_amd.level.normalize_level(..., via_int16=True, out_int16=True)` in one call
+and the wavs are int16.  --keep_raw with --sv56 also writes `<name>.raw.wav`, the int16 before the normalisation.
+
 --synthetic N needs no files: N seeded waveforms of different lengths (`unitspeech_amd.mel.synthetic_waveform`) in length-sorted batches
 of K through seeded weights of every module (HuBERT-base, the voice-conversion.json encoder, the decoder, the base BigVGAN).
 """
@@ -89,8 +93,10 @@ class Pipeline:
         return self._resamplers[key]
 
     @torch.no_grad()
-    def convert(self, waves, rate, **vc_kw):
-        """waves: float32 arrays sampled at `rate` -> ([waveform [mel_length * hop] on the host per source], a dict of the batch's counts)."""
+    def convert(self, waves, rate, sv56_ndb=None, keep_raw=False, **vc_kw):
+        """waves: float32 arrays sampled at `rate` -> ([waveform [mel_length * hop] on the host per source], a dict of the batch's counts).
+        With `sv56_ndb` the waveforms are the int16 of the level normalisation and the dict also holds level_db, gain, clipped and, with
+        `keep_raw`, raw: the int16 waveforms before it."""
         B, lens = len(waves), [len(w) for w in waves]
         wav = torch.zeros(B, max(lens))
         for b, w in enumerate(waves):
@@ -110,9 +116,20 @@ class Pipeline:
         _, mel, _ = self.decoder.execute_voice_conversion(
             feats, torch.tensor(cv_lengths, dtype=torch.long, device=self.device), mel_lengths, spk, self.encoder, self.n_down,
             mel_range=self.mel_range, return_lengths=True, **vc_kw)
-        audio = self.vocoder.forward(mel, lengths=mel_lengths).clamp(-1, 1).cpu()
+        audio = self.vocoder.forward(mel, lengths=mel_lengths).clamp(-1, 1)
+        extra = {}
+        if sv56_ndb is not None:
+            from unitspeech_amd.level import normalize_level
+            samples = [n * self.vocoder.hop for n in mel_lengths]
+            norm, lv = normalize_level(audio, self.sampling_rate, sv56_ndb, lengths=samples, via_int16=True, out_int16=True)
+            extra = dict(level_db=lv.level_db.tolist(), gain=lv.gain.tolist(), clipped=lv.clipped.tolist())
+            if keep_raw:
+                raw = (audio * 32767).to(torch.int16).cpu()
+                extra["raw"] = [raw[b, 0, :samples[b]].clone() for b in range(B)]
+            audio = norm
+        audio = audio.cpu()
         out = [audio[b, 0, :mel_lengths[b] * self.vocoder.hop].clone() for b in range(B)]
-        return out, dict(sources=B, contentvec_frames=cv_lengths, mel_frames=mel_lengths, samples=[int(o.numel()) for o in out])
+        return out, dict(sources=B, contentvec_frames=cv_lengths, mel_frames=mel_lengths, samples=[int(o.numel()) for o in out], **extra)
 
 
 def build_synthetic(device, seed):
@@ -182,6 +199,9 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded sources through seeded weights; needs no files")
     ap.add_argument("--batch", type=int, default=8, metavar="K", help="most sources in one batch")
     ap.add_argument("--out", default=None, metavar="DIR", help="directory for <name>.wav (several sources, --synthetic)")
+    ap.add_argument("--sv56", action="store_true", help="normalise each converted waveform's active speech level on the device; the wavs are int16")
+    ap.add_argument("--ndb", type=float, default=-26.0, help="--sv56: the target level in dB relative to full scale")
+    ap.add_argument("--keep_raw", action="store_true", help="--sv56: also write <name>.raw.wav, the int16 before the normalisation")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -208,13 +228,18 @@ def main():
         group = [i for i, it in enumerate(items) if it[2] == rate]
         for batch in plan_batches([len(items[i][1]) for i in group], args.batch):
             idx = [group[j] for j in batch]
-            out, info = pipe.convert([items[i][1] for i in idx], rate, diffusion_steps=args.diffusion_step,
+            out, info = pipe.convert([items[i][1] for i in idx], rate, sv56_ndb=args.ndb if args.sv56 else None,
+                                     keep_raw=args.sv56 and args.keep_raw, diffusion_steps=args.diffusion_step,
                                      text_gradient_scale=args.text_gradient_scale, spk_gradient_scale=args.spk_gradient_scale)
-            for i, wav in zip(idx, out):
+            for k, (i, wav) in enumerate(zip(idx, out)):
                 path = os.path.join(args.out, items[i][0] + ".wav") if args.out else args.generated_sample_path
                 if os.path.dirname(path):
                     os.makedirs(os.path.dirname(path), exist_ok=True)
                 write(path, pipe.sampling_rate, wav.numpy())
+                if "raw" in info:
+                    write(os.path.splitext(path)[0] + ".raw.wav", pipe.sampling_rate, info["raw"][k].numpy())
+                if args.sv56:
+                    print(f"{items[i][0]}: level {info['level_db'][k]:.2f} dB, gain {info['gain'][k]:.4f}, {info['clipped'][k]} clipped samples")
             print(f"batch of {info['sources']} sources: contentvec frames {info['contentvec_frames']}, mel frames {info['mel_frames']}, "
                   f"samples written {info['samples']}", flush=True)
 
