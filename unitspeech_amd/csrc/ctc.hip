@@ -2,15 +2,14 @@
 // that allocate nothing, need no scratch and only enqueue on the stream.
 //
 //   us_ctc_pack_head   weight [V][H], bias [V] -> the GEMM operand P[Hpad][Vpad] (h-major, zero padded) followed by bias[Vpad].
-//   us_ctc_logits      logits[b][t][v] = hidden[b][t] . weight[v] + bias[v] on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: an fp32 fma
-//                      chain, the products of un_score_kernel in units.hip).  The rows are the MFMA's A operand, so a row's index lands on
-//                      the accumulator registers and the vocabulary on the lanes: the stores are coalesced along V.  A row's H products are
+//   us_ctc_logits      logits[b][t][v] = hidden[b][t] . weight[v] + bias[v] on the fp32 matrix cores (the tile loop of dense_tile.h,
+//                      shared with the unit scorer).  The rows are the MFMA's A operand, so a row's index lands on the accumulator registers and the vocabulary on the lanes: the stores are coalesced along V.  A row's H products are
 //                      added in one fixed order (two interleaved chains over ascending h, one addition, then the bias) wherever the row
 //                      lies, so an item has the same bits alone and in a ragged batch.  A second kernel, one wave per row, reads the
 //                      written logits: ids = their argmax (the lower index on ties), log_probs = (x - max) - logf(sum expf(x - max)).
 //                      Rows at or beyond lengths[b] get logits 0, log_probs 0 and ids -1.
 //   us_ctc_collapse    greedy CTC decoding per item: a frame is kept when it differs from the frame before it and is not the blank.
-//                      One workgroup per item, an LDS scan over chunk counts (un_dedup_kernel's scheme), any Tmax.
+//                      One workgroup per item, an LDS scan over chunk counts (block_scan256, as the units' run-length encoding), any Tmax.
 //   us_edit_distance   Levenshtein distance with unit costs, one workgroup per pair, anti-diagonal sweep over three rolling diagonals
 //                      of int32 in LDS (indexed by the hypothesis position), one barrier per diagonal.
 #include <hip/hip_runtime.h>
@@ -19,17 +18,16 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "ctc_limits.h"
+#include "dense_tile.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
-constexpr int kMaxV = 2048, kMaxH = 1024, kMaxTokens = 4096;
-constexpr int kBR = 64;        // rows per workgroup
-constexpr int kBC = 64;        // vocabulary entries per workgroup
-constexpr int kBK = 16;        // reduction slice per LDS stage
-constexpr int kXld = 68;       // row stride of the transposed feature slice (un_score_kernel's padding)
+constexpr int kMaxTokens = 4096;
 
 __global__ __launch_bounds__(256) void ctc_pack_kernel(const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ p, int V,
                                                        int H, int Vpad, int Hpad) {
@@ -45,69 +43,42 @@ __global__ __launch_bounds__(256) void ctc_pack_kernel(const float* __restrict__
   }
 }
 
-__device__ __forceinline__ int item_len(const long long* __restrict__ lengths, int b, int Tmax) {
-  return lengths ? (int)min((long long)Tmax, max(0LL, lengths[b])) : Tmax;
-}
-
 // Workgroup: 64 rows x 64 vocabulary entries, four waves of 32 x 32.  Both operands go through LDS k-major (two stages); the rows are
 // transposed on the way in.
 __global__ __launch_bounds__(256) void ctc_logits_kernel(const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ bias,
                                                          const long long* __restrict__ lengths, float* __restrict__ out, int rows, int Tmax,
                                                          int V, int H, int Hpad, int Vpad) {
-  __shared__ float Ws[2][kBK][kBC];
-  __shared__ float Xs[2][kBK][kXld];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ float Ws[2][kDtBK][kDtTile];
+  __shared__ float Xs[2][kDtBK][kDtLdT];
+  const int tid = threadIdx.x;
+  DENSE_LANE(tid);
+  DENSE_STAGE_K(tid);                                    // weight slice: 16 k x 64 entries, one float4 per thread
+  DENSE_STAGE_T(tid);                                    // feature slice: 64 rows x 16 k, one float4 per thread
   const int vh = wave & 1, rh = wave >> 1;
-  const int kl = lane >> 5, cl = lane & 31;
-  const int r0 = blockIdx.x * kBR, c0 = blockIdx.y * kBC;
-  const int pr = tid >> 4, pc = (tid & 15) * 4;          // weight slice: 16 k x 64 entries, one float4 per thread
-  const int xr = tid >> 2, xk = (tid & 3) * 4;           // feature slice: 64 rows x 16 k, one float4 per thread
-  bool xlive = r0 + xr < rows;
-  if (xlive) {                                           // a padding row is never read: what lies there may be anything
-    const int b = (r0 + xr) / Tmax;
-    xlive = (r0 + xr) - b * Tmax < item_len(lengths, b, Tmax);
-  }
-  const float* __restrict__ xrow = X + (size_t)(xlive ? r0 + xr : 0) * H;
-  const int nk = Hpad / kBK;
+  const int r0 = blockIdx.x * kDtTile, c0 = blockIdx.y * kDtTile;
+  const bool xlive = row_live(lengths, r0 + tr, rows, Tmax);   // a padding row is never read: what lies there may be anything
+  const float* __restrict__ xrow = X + (size_t)(xlive ? r0 + tr : 0) * H;
   float4 wreg, xreg;
   auto load = [&](int k0) {
-    wreg = *reinterpret_cast<const float4*>(P + (size_t)(k0 + pr) * Vpad + c0 + pc);
-    xreg = (xlive && k0 + xk < H) ? *reinterpret_cast<const float4*>(xrow + k0 + xk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    wreg = *reinterpret_cast<const float4*>(P + (size_t)(k0 + sk) * Vpad + c0 + sc);
+    xreg = (xlive && k0 + tk < H) ? *reinterpret_cast<const float4*>(xrow + k0 + tk) : make_float4(0.f, 0.f, 0.f, 0.f);
   };
   auto store = [&](int buf) {
-    *reinterpret_cast<float4*>(&Ws[buf][pr][pc]) = wreg;
-    Xs[buf][xk + 0][xr] = xreg.x;
-    Xs[buf][xk + 1][xr] = xreg.y;
-    Xs[buf][xk + 2][xr] = xreg.z;
-    Xs[buf][xk + 3][xr] = xreg.w;
+    *reinterpret_cast<float4*>(&Ws[buf][sk][sc]) = wreg;
+    Xs[buf][tk + 0][tr] = xreg.x;
+    Xs[buf][tk + 1][tr] = xreg.y;
+    Xs[buf][tk + 2][tr] = xreg.z;
+    Xs[buf][tk + 3][tr] = xreg.w;
   };
   f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-  load(0);
-  store(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * kBK);
-#pragma unroll
-    for (int s = 0; s < kBK / 2; ++s) {                  // two accumulators in turn: no MFMA waits on the one before it
-      const float fa = Xs[cur][2 * s + kl][rh * 32 + cl];
-      const float fb = Ws[cur][2 * s + kl][vh * 32 + cl];
-      acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[s & 1], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(cur ^ 1);
-    __syncthreads();
-  }
+  dense_tile_mainloop(Xs, Ws, rh, vh, Hpad / kDtBK, acc, load, store);
   // the MFMA row is the row of X, the MFMA column the vocabulary entry: 32 lanes store 32 neighbouring floats
-  const int v = c0 + vh * 32 + cl;
+  const int v = c0 + DENSE_AT(vh);
   if (v >= V) return;
   const float bv = bias[v];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = r0 + rh * 32 + mfma32_row(r, kl);
+    const int row = r0 + DENSE_ROW(rh, r);
     if (row >= rows) continue;
     const int b = row / Tmax;
     const bool live = row - b * Tmax < item_len(lengths, b, Tmax);
@@ -177,14 +148,7 @@ __global__ __launch_bounds__(256) void ctc_collapse_kernel(const long long* __re
   const int t0 = min(len, tid * chunk), t1 = min(len, t0 + chunk);
   int cnt = 0;
   for (int t = t0; t < t1; ++t) cnt += (u[t] != blank && (t == 0 || u[t] != u[t - 1])) ? 1 : 0;
-  scan[tid] = cnt;
-  __syncthreads();
-  for (int s = 1; s < 256; s <<= 1) {
-    const int v = tid >= s ? scan[tid - s] : 0;
-    __syncthreads();
-    scan[tid] += v;
-    __syncthreads();
-  }
+  block_scan256(scan, cnt);
   const int n = scan[255];
   int pos = scan[tid] - cnt;
   for (int t = t0; t < t1; ++t) {
@@ -209,7 +173,7 @@ __global__ __launch_bounds__(256) void edit_distance_kernel(const long long* __r
   extern __shared__ int diag[];
   const int p = blockIdx.x, tid = threadIdx.x;
   const int cap = Lh + 1;
-  const int n = (int)min((long long)Lh, max(0LL, n_hyp[p])), m = (int)min((long long)Lr, max(0LL, n_ref[p]));
+  const int n = item_len(n_hyp, p, Lh), m = item_len(n_ref, p, Lr);
   const long long* __restrict__ a = hyp + (size_t)p * Lh;
   const long long* __restrict__ c = ref + (size_t)p * Lr;
   int* cur = diag;
@@ -237,23 +201,6 @@ __global__ __launch_bounds__(256) void edit_distance_kernel(const long long* __r
   if (tid == 0) dist[p] = p1[n];
 }
 
-int ctc_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  set_last_error(buf);
-  return US_EHIP;
-}
-int ctc_bad(const char* msg) {
-  set_last_error(msg);
-  return US_EINVAL;
-}
-const char* head_error(int V, int H) {
-  if (V < 2 || V > kMaxV) return "V must be in [2, 2048]";
-  if (H < 4 || H > kMaxH || H % 4) return "H must be a multiple of 4 in [4, 1024]";
-  return nullptr;
-}
-bool rows_ok(int B, int T) { return B > 0 && T > 0 && B <= 65535 && (long long)B * T <= (1LL << 24); }
-
 }  // namespace
 }  // namespace us
 
@@ -263,20 +210,20 @@ extern "C" {
 
 size_t us_ctc_packed_bytes(int V, int H) {
   if (head_error(V, H)) return 0;
-  return ((size_t)round_up(H, kBK) * round_up(V, kBC) + round_up(V, kBC)) * sizeof(float);
+  return ((size_t)round_up(H, kDtBK) * round_up(V, kDtTile) + round_up(V, kDtTile)) * sizeof(float);
 }
 
 int us_ctc_pack_head(const float* weight, const float* bias, int V, int H, void* packed, size_t packed_bytes, us_stream stream) {
   if (const char* m = head_error(V, H)) {
     char buf[128];
     snprintf(buf, sizeof buf, "us_ctc_pack_head: %s (V = %d, H = %d)", m, V, H);
-    return ctc_bad(buf);
+    return bad_arg(buf);
   }
-  if (!weight || !packed || packed_bytes < us_ctc_packed_bytes(V, H)) return ctc_bad("us_ctc_pack_head: bad argument");
+  if (!weight || !packed || packed_bytes < us_ctc_packed_bytes(V, H)) return bad_arg("us_ctc_pack_head: bad argument");
   hipLaunchKernelGGL(ctc_pack_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), weight, bias, static_cast<float*>(packed), V, H,
-                     round_up(V, kBC), round_up(H, kBK));
+                     round_up(V, kDtTile), round_up(H, kDtBK));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : ctc_fail("us_ctc_pack_head", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_ctc_pack_head", e);
 }
 
 int us_ctc_logits(const float* hidden, const int64_t* lengths, const void* packed, int B, int Tmax, int V, int H, float* logits,
@@ -284,30 +231,30 @@ int us_ctc_logits(const float* hidden, const int64_t* lengths, const void* packe
   if (const char* m = head_error(V, H)) {
     char buf[128];
     snprintf(buf, sizeof buf, "us_ctc_logits: %s (V = %d, H = %d)", m, V, H);
-    return ctc_bad(buf);
+    return bad_arg(buf);
   }
-  if (!hidden || !packed || !logits || !rows_ok(B, Tmax)) return ctc_bad("us_ctc_logits: bad argument");
-  const int rows = B * Tmax, Vpad = round_up(V, kBC), Hpad = round_up(H, kBK);
+  if (!hidden || !packed || !logits || !rows_ok(B, Tmax)) return bad_arg("us_ctc_logits: bad argument");
+  const int rows = B * Tmax, Vpad = round_up(V, kDtTile), Hpad = round_up(H, kDtBK);
   const float* P = static_cast<const float*>(packed);
   const long long* lens = reinterpret_cast<const long long*>(lengths);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(ctc_logits_kernel, dim3((rows + kBR - 1) / kBR, Vpad / kBC), dim3(256), 0, s, hidden, P, P + (size_t)Hpad * Vpad, lens,
+  hipLaunchKernelGGL(ctc_logits_kernel, dim3((rows + kDtTile - 1) / kDtTile, Vpad / kDtTile), dim3(256), 0, s, hidden, P, P + (size_t)Hpad * Vpad, lens,
                      logits, rows, Tmax, V, H, Hpad, Vpad);
   if (log_probs || ids)
     hipLaunchKernelGGL(ctc_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, lens, log_probs, reinterpret_cast<long long*>(ids), rows,
                        Tmax, V);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : ctc_fail("us_ctc_logits", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_ctc_logits", e);
 }
 
 int us_ctc_collapse(const int64_t* ids, const int64_t* lengths, int B, int Tmax, int64_t blank, int64_t* tokens, int64_t* first_frame,
                     int64_t* n, us_stream stream) {
-  if (!ids || !tokens || !n || !rows_ok(B, Tmax) || ids == tokens || ids == first_frame) return ctc_bad("us_ctc_collapse: bad argument");
+  if (!ids || !tokens || !n || !rows_ok(B, Tmax) || ids == tokens || ids == first_frame) return bad_arg("us_ctc_collapse: bad argument");
   hipLaunchKernelGGL(ctc_collapse_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(ids),
                      reinterpret_cast<const long long*>(lengths), (long long)blank, reinterpret_cast<long long*>(tokens),
                      reinterpret_cast<long long*>(first_frame), reinterpret_cast<long long*>(n), Tmax);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : ctc_fail("us_ctc_collapse", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_ctc_collapse", e);
 }
 
 int us_edit_distance(const int64_t* hyp, const int64_t* n_hyp, int Lh, const int64_t* ref, const int64_t* n_ref, int Lr, int P, int64_t* dist,
@@ -315,17 +262,17 @@ int us_edit_distance(const int64_t* hyp, const int64_t* n_hyp, int Lh, const int
   if (Lh < 0 || Lr < 0 || Lh > kMaxTokens || Lr > kMaxTokens) {
     char buf[160];
     snprintf(buf, sizeof buf, "us_edit_distance: a sequence holds at most %d tokens (Lh = %d, Lr = %d)", kMaxTokens, Lh, Lr);
-    return ctc_bad(buf);
+    return bad_arg(buf);
   }
-  if (P < 0 || P > (1 << 24)) return ctc_bad("us_edit_distance: P must be in [0, 2^24]");
+  if (P < 0 || P > (1 << 24)) return bad_arg("us_edit_distance: P must be in [0, 2^24]");
   if (P == 0) return US_OK;
-  if (!n_hyp || !n_ref || !dist || (Lh > 0 && !hyp) || (Lr > 0 && !ref)) return ctc_bad("us_edit_distance: bad argument");
+  if (!n_hyp || !n_ref || !dist || (Lh > 0 && !hyp) || (Lr > 0 && !ref)) return bad_arg("us_edit_distance: bad argument");
   const size_t lds = 3 * (size_t)(Lh + 1) * sizeof(int);       // at most 49164 bytes: within the 64 KB a kernel gets unasked
   hipLaunchKernelGGL(edit_distance_kernel, dim3(P), dim3(256), lds, static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(hyp),
                      reinterpret_cast<const long long*>(n_hyp), Lh, reinterpret_cast<const long long*>(ref),
                      reinterpret_cast<const long long*>(n_ref), Lr, reinterpret_cast<long long*>(dist));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : ctc_fail("us_edit_distance", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_edit_distance", e);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 //                          the wave, then the four waves in order.  No float atomics, nothing depends on the batch.
 //                          `stage` lets a training step run the two sweeps as two calls around the moment it learns grad_out
 //                          (US_CTC_FORWARD leaves alpha and the log-likelihoods in the workspace, US_CTC_BACKWARD resumes from them).
-//   us_ctc_head_backward   dW = g^T x and dX = g W on the fp32 matrix cores (v_mfma_f32_32x32x2_f32), db in plain fp32.  The rows are cut
+//   us_ctc_head_backward   dW = g^T x and dX = g W on the fp32 matrix cores (the tile loop of dense_tile.h), db in plain fp32.  The rows are cut
 //                          into chunks whose partial dW / db go to the workspace; a second kernel adds them in chunk order.
 //   us_ctc_forced_align    Viterbi over the same states in fp32 (best predecessor + score, so the path's own sum in frame order has the
 //                          same bits), a 2-bit back-pointer per (t, s) packed per thread into one word per frame, then one thread of
@@ -27,24 +27,21 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "ctc_limits.h"
+#include "dense_tile.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
-constexpr int kMaxV = 2048, kMaxH = 1024;
-constexpr int kMaxL = 1024;                      // tokens per target
+constexpr int kMaxL = 1024;                     // tokens per target
 constexpr int kNT = 256;                         // threads per item
 constexpr int kMaxS = 2 * kMaxL + 1;
 constexpr int kNJ = (kMaxS + kNT - 1) / kNT;     // states per thread: 9
 constexpr int kNV = kMaxV / kNT;                 // vocabulary entries per thread: 8
 constexpr int kWalk = 16;                        // frames of back-pointers staged per step of the backtrace
-constexpr int kBK = 16, kTile = 64, kXld = 68;   // the GEMM tiles of ctc.hip
-
-__device__ __forceinline__ int clamp_len(const long long* __restrict__ lengths, int b, int hi) {
-  return lengths ? (int)min((long long)hi, max(0LL, lengths[b])) : hi;
-}
 
 // ---- row statistics ---------------------------------------------------------------------------------------------------------------
 // stat[row] = (max, log sum exp(x - max)); rows at or beyond the item's frames are not written and never read.
@@ -54,7 +51,7 @@ __global__ __launch_bounds__(256) void ctc_rowstat_kernel(const float* __restric
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int b = row / Tmax;
-  if (row - b * Tmax >= clamp_len(lengths, b, Tmax)) return;
+  if (row - b * Tmax >= item_len(lengths, b, Tmax)) return;
   const float* __restrict__ x = logits + (size_t)row * V;
   float xv[kMaxV / 64];
   float best = -INFINITY;
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(kNT) void ctc_loss_kernel(const float* __restrict__
   __shared__ int nxt[GRAD ? kMaxL : 1];                         // the next position with the same entry, or -1
   __shared__ int head[GRAD ? kMaxV : 1];                        // the first position of an entry, or -1
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int T = clamp_len(frame_lengths, b, Tmax), L = clamp_len(target_lengths, b, Lmax), S = 2 * L + 1;
+  const int T = item_len(frame_lengths, b, Tmax), L = item_len(target_lengths, b, Lmax), S = 2 * L + 1;
   const int Smax = 2 * Lmax + 1;
   const long long* __restrict__ tg = targets + (size_t)b * Lmax;
   const float* __restrict__ x = logits + (size_t)b * Tmax * V;
@@ -305,7 +302,7 @@ __global__ __launch_bounds__(kNT) void ctc_align_kernel(const float* __restrict_
   __shared__ unsigned bp[kWalk * kNT];
   __shared__ int tgs[kMaxL], first[kMaxL], count[kMaxL];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int T = clamp_len(frame_lengths, b, Tmax), L = clamp_len(target_lengths, b, Lmax), S = 2 * L + 1;
+  const int T = item_len(frame_lengths, b, Tmax), L = item_len(target_lengths, b, Lmax), S = 2 * L + 1;
   const int W = align_words(Lmax);
   const long long* __restrict__ tg = targets + (size_t)b * Lmax;
   const float* __restrict__ x = scores + (size_t)b * Tmax * V;
@@ -411,72 +408,48 @@ __global__ __launch_bounds__(kNT) void ctc_align_kernel(const float* __restrict_
 }
 
 // ---- the head's backward pass ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool row_live(const long long* __restrict__ lengths, int row, int rows, int Tmax) {
-  if (row >= rows) return false;
-  const int b = row / Tmax;
-  return row - b * Tmax < clamp_len(lengths, b, Tmax);
-}
-
 // part_w[chunk][V][H] = sum over the chunk's live rows of g[row][v] x[row][h] (the MFMA's M is the vocabulary, its N the hidden index: the
 // lanes store along h); part_b[chunk][V] = the column sums of g, added in row order by the workgroups of the first h tile.
 __global__ __launch_bounds__(256) void ctc_head_dw_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                           const long long* __restrict__ lengths, float* __restrict__ part_w,
                                                           float* __restrict__ part_b, int rows, int Tmax, int V, int H, int chunk) {
-  __shared__ float Gs[2][kBK][kTile];
-  __shared__ float Xs[2][kBK][kTile];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ float Gs[2][kDtBK][kDtTile];
+  __shared__ float Xs[2][kDtBK][kDtTile];
+  const int tid = threadIdx.x;
+  DENSE_LANE(tid);
+  DENSE_STAGE_K(tid);                                    // both slices: 16 rows x 64 columns, four neighbouring columns per thread
   const int hh = wave & 1, vh = wave >> 1;
-  const int kl = lane >> 5, cl = lane & 31;
   const int r0 = blockIdx.x * chunk, r1 = min(rows, r0 + chunk);
-  const int c0 = blockIdx.y * kTile, h0 = blockIdx.z * kTile;
-  const int kr = tid >> 4, kc = (tid & 15) * 4;          // both slices: 16 rows x 64 columns, four neighbouring columns per thread
-  const int nk = (r1 - r0 + kBK - 1) / kBK;
+  const int c0 = blockIdx.y * kDtTile, h0 = blockIdx.z * kDtTile;
   float greg[4];
   float4 xreg;
   auto load = [&](int k0) {
-    const int row = r0 + k0 + kr;
+    const int row = r0 + k0 + sk;
     const bool live = row < r1 && row_live(lengths, row, rows, Tmax);   // a dead row's features may hold anything: they are not read
 #pragma unroll
-    for (int i = 0; i < 4; ++i) greg[i] = (live && c0 + kc + i < V) ? g[(size_t)row * V + c0 + kc + i] : 0.f;
-    xreg = (live && h0 + kc < H) ? *reinterpret_cast<const float4*>(x + (size_t)row * H + h0 + kc) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = 0; i < 4; ++i) greg[i] = (live && c0 + sc + i < V) ? g[(size_t)row * V + c0 + sc + i] : 0.f;   // V need not be a multiple of 4
+    xreg = (live && h0 + sc < H) ? *reinterpret_cast<const float4*>(x + (size_t)row * H + h0 + sc) : make_float4(0.f, 0.f, 0.f, 0.f);
   };
   auto store = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) Gs[buf][kr][kc + i] = greg[i];
-    *reinterpret_cast<float4*>(&Xs[buf][kr][kc]) = xreg;
+    for (int i = 0; i < 4; ++i) Gs[buf][sk][sc + i] = greg[i];
+    *reinterpret_cast<float4*>(&Xs[buf][sk][sc]) = xreg;
   };
   f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
   float bsum = 0.f;
-  load(0);
-  store(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * kBK);
+  dense_tile_mainloop(Gs, Xs, vh, hh, (r1 - r0 + kDtBK - 1) / kDtBK, acc, load, store, DenseNoHook{}, [&](int cur) {
+    if (blockIdx.z == 0 && tid < kDtTile) {
 #pragma unroll
-    for (int s = 0; s < kBK / 2; ++s) {
-      const float fa = Gs[cur][2 * s + kl][vh * 32 + cl];
-      const float fb = Xs[cur][2 * s + kl][hh * 32 + cl];
-      acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[s & 1], 0, 0, 0);
+      for (int k = 0; k < kDtBK; ++k) bsum += Gs[cur][k][tid];
     }
-    if (blockIdx.z == 0 && tid < kTile) {
-#pragma unroll
-      for (int k = 0; k < kBK; ++k) bsum += Gs[cur][k][tid];
-    }
-    if (kt + 1 < nk) store(cur ^ 1);
-    __syncthreads();
-  }
-  if (blockIdx.z == 0 && tid < kTile && c0 + tid < V) part_b[(size_t)blockIdx.x * V + c0 + tid] = bsum;
-  const int h = h0 + hh * 32 + cl;
+  });
+  if (blockIdx.z == 0 && tid < kDtTile && c0 + tid < V) part_b[(size_t)blockIdx.x * V + c0 + tid] = bsum;
+  const int h = h0 + DENSE_AT(hh);
   if (h >= H) return;
   float* __restrict__ pw = part_w + (size_t)blockIdx.x * V * H;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int v = c0 + vh * 32 + mfma32_row(r, kl);
+    const int v = c0 + DENSE_ROW(vh, r);
     if (v < V) pw[(size_t)v * H + h] = acc[0][r] + acc[1][r];
   }
 }
@@ -497,74 +470,44 @@ __global__ __launch_bounds__(256) void ctc_head_sum_kernel(const float* __restri
     db[i - nw] = s;
 }
 
-// dX[row][h] = sum over v of g[row][v] W[v][h]: the rows are the MFMA's M (transposed into LDS on the way in, as ctc_logits_kernel does
-// with the features), h its N.  A row at or beyond its item's frames gets 0.
+// dX[row][h] = sum over v of g[row][v] W[v][h]: the rows are the MFMA's M (a row-major operand of dense_tile.h, transposed into LDS
+// on the way in), h its N.  A row at or beyond its item's frames gets 0.
 __global__ __launch_bounds__(256) void ctc_head_dx_kernel(const float* __restrict__ g, const float* __restrict__ w,
                                                           const long long* __restrict__ lengths, float* __restrict__ dx, int rows, int Tmax,
                                                           int V, int H) {
-  __shared__ float Ws[2][kBK][kTile];
-  __shared__ float Gt[2][kBK][kXld];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ float Ws[2][kDtBK][kDtTile];
+  __shared__ float Gt[2][kDtBK][kDtLdT];
+  const int tid = threadIdx.x;
+  DENSE_LANE(tid);
+  DENSE_STAGE_K(tid);                                    // weight slice: 16 entries x 64 hidden, one float4 per thread
+  DENSE_STAGE_T(tid);                                    // gradient slice: 64 rows x 16 entries, four neighbouring entries per thread
   const int hh = wave & 1, rh = wave >> 1;
-  const int kl = lane >> 5, cl = lane & 31;
-  const int r0 = blockIdx.x * kTile, h0 = blockIdx.y * kTile;
-  const int pr = tid >> 4, pc = (tid & 15) * 4;          // weight slice: 16 entries x 64 hidden, one float4 per thread
-  const int gr = tid >> 2, gk = (tid & 3) * 4;           // gradient slice: 64 rows x 16 entries, four neighbouring entries per thread
-  const bool glive = row_live(lengths, r0 + gr, rows, Tmax);
-  const float* __restrict__ grow = g + (size_t)(glive ? r0 + gr : 0) * V;
-  const int nk = (V + kBK - 1) / kBK;
+  const int r0 = blockIdx.x * kDtTile, h0 = blockIdx.y * kDtTile;
+  const bool glive = row_live(lengths, r0 + tr, rows, Tmax);
+  const float* __restrict__ grow = g + (size_t)(glive ? r0 + tr : 0) * V;
   float4 wreg;
   float greg[4];
   auto load = [&](int k0) {
-    wreg = (k0 + pr < V && h0 + pc < H) ? *reinterpret_cast<const float4*>(w + (size_t)(k0 + pr) * H + h0 + pc) : make_float4(0.f, 0.f, 0.f, 0.f);
+    wreg = (k0 + sk < V && h0 + sc < H) ? *reinterpret_cast<const float4*>(w + (size_t)(k0 + sk) * H + h0 + sc) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) greg[i] = (glive && k0 + gk + i < V) ? grow[k0 + gk + i] : 0.f;
+    for (int i = 0; i < 4; ++i) greg[i] = (glive && k0 + tk + i < V) ? grow[k0 + tk + i] : 0.f;   // V need not be a multiple of 4
   };
   auto store = [&](int buf) {
-    *reinterpret_cast<float4*>(&Ws[buf][pr][pc]) = wreg;
+    *reinterpret_cast<float4*>(&Ws[buf][sk][sc]) = wreg;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) Gt[buf][gk + i][gr] = greg[i];
+    for (int i = 0; i < 4; ++i) Gt[buf][tk + i][tr] = greg[i];
   };
   f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-  load(0);
-  store(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * kBK);
-#pragma unroll
-    for (int s = 0; s < kBK / 2; ++s) {
-      const float fa = Gt[cur][2 * s + kl][rh * 32 + cl];
-      const float fb = Ws[cur][2 * s + kl][hh * 32 + cl];
-      acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[s & 1], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(cur ^ 1);
-    __syncthreads();
-  }
-  const int h = h0 + hh * 32 + cl;
+  dense_tile_mainloop(Gt, Ws, rh, hh, (V + kDtBK - 1) / kDtBK, acc, load, store);
+  const int h = h0 + DENSE_AT(hh);
   if (h >= H) return;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = r0 + rh * 32 + mfma32_row(r, kl);
+    const int row = r0 + DENSE_ROW(rh, r);
     if (row < rows) dx[(size_t)row * H + h] = acc[0][r] + acc[1][r];       // a dead row's operand was all zeros
   }
 }
 
-int train_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  set_last_error(buf);
-  return US_EHIP;
-}
-int train_bad(const char* msg) {
-  set_last_error(msg);
-  return US_EINVAL;
-}
-bool rows_ok(int B, int T) { return B > 0 && T > 0 && B <= 65535 && (long long)B * T <= (1LL << 24); }
 // "" or why the sizes of a loss / alignment call are refused
 const char* seq_error(int B, int Tmax, int V, int Lmax, long long blank, char* buf, size_t n, const char* what) {
   if (Lmax < 0 || Lmax > kMaxL) {
@@ -588,7 +531,7 @@ const char* seq_error(int B, int Tmax, int V, int Lmax, long long blank, char* b
 size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 size_t stat_bytes(int B, int Tmax) { return align256((size_t)B * Tmax * sizeof(float2)); }
 size_t ll_bytes(int B) { return align256((size_t)B * sizeof(double)); }
-int head_chunk(int rows) { return std::max(kTile, round_up((rows + 63) / 64, kBK)); }     // at most 64 chunks
+int head_chunk(int rows) { return std::max(kDtTile, round_up((rows + 63) / 64, kDtBK)); }     // at most 64 chunks
 
 }  // namespace
 }  // namespace us
@@ -606,12 +549,12 @@ int us_ctc_loss(const float* logits, const int64_t* frame_lengths, const int64_t
                 int B, int Tmax, int V, int Lmax, int64_t blank, int zero_infinity, int stage, float* loss, float* grad_logits, void* workspace,
                 size_t workspace_bytes, us_stream stream) {
   char buf[192];
-  if (const char* m = seq_error(B, Tmax, V, Lmax, blank, buf, sizeof buf, "us_ctc_loss")) return train_bad(m);
+  if (const char* m = seq_error(B, Tmax, V, Lmax, blank, buf, sizeof buf, "us_ctc_loss")) return bad_arg(m);
   if (stage < US_CTC_WHOLE || stage > US_CTC_BACKWARD || (stage == US_CTC_FORWARD && grad_logits) || (stage == US_CTC_BACKWARD && !grad_logits))
-    return train_bad("us_ctc_loss: stage must be US_CTC_WHOLE, US_CTC_FORWARD (without grad_logits) or US_CTC_BACKWARD (with grad_logits)");
+    return bad_arg("us_ctc_loss: stage must be US_CTC_WHOLE, US_CTC_FORWARD (without grad_logits) or US_CTC_BACKWARD (with grad_logits)");
   if (!logits || !target_lengths || !loss || (Lmax > 0 && !targets) || !workspace ||
       workspace_bytes < us_ctc_loss_workspace_bytes(B, Tmax, Lmax, grad_logits != nullptr || stage != US_CTC_WHOLE))
-    return train_bad("us_ctc_loss: bad argument");
+    return bad_arg("us_ctc_loss: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = B * Tmax;
   float2* stat = static_cast<float2*>(workspace);
@@ -635,7 +578,7 @@ int us_ctc_loss(const float* logits, const int64_t* frame_lengths, const int64_t
   else
     launch(ctc_loss_kernel<true, false, false>);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : train_fail("us_ctc_loss", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_ctc_loss", e);
 }
 
 size_t us_ctc_align_workspace_bytes(int B, int Tmax, int Lmax) {
@@ -647,38 +590,38 @@ int us_ctc_forced_align(const float* scores, const int64_t* frame_lengths, const
                         int V, int Lmax, int64_t blank, int64_t* path, float* score, int64_t* start, int64_t* frames, void* workspace,
                         size_t workspace_bytes, us_stream stream) {
   char buf[192];
-  if (const char* m = seq_error(B, Tmax, V, Lmax, blank, buf, sizeof buf, "us_ctc_forced_align")) return train_bad(m);
+  if (const char* m = seq_error(B, Tmax, V, Lmax, blank, buf, sizeof buf, "us_ctc_forced_align")) return bad_arg(m);
   if (!scores || !target_lengths || !path || !score || (Lmax > 0 && (!targets || !start || !frames)) || !workspace ||
       workspace_bytes < us_ctc_align_workspace_bytes(B, Tmax, Lmax))
-    return train_bad("us_ctc_forced_align: bad argument");
+    return bad_arg("us_ctc_forced_align: bad argument");
   hipLaunchKernelGGL(ctc_align_kernel, dim3(B), dim3(kNT), 0, static_cast<hipStream_t>(stream), scores,
                      reinterpret_cast<const long long*>(frame_lengths), reinterpret_cast<const long long*>(targets),
                      reinterpret_cast<const long long*>(target_lengths), reinterpret_cast<long long*>(path), score,
                      reinterpret_cast<long long*>(start), reinterpret_cast<long long*>(frames), static_cast<unsigned*>(workspace), Tmax, V,
                      Lmax, (int)blank);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : train_fail("us_ctc_forced_align", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_ctc_forced_align", e);
 }
 
 size_t us_ctc_head_backward_workspace_bytes(int B, int Tmax, int V, int H) {
-  if (!rows_ok(B, Tmax) || V < 2 || V > kMaxV || H < 4 || H > kMaxH || H % 4) return 0;
+  if (!rows_ok(B, Tmax) || head_error(V, H)) return 0;
   const int rows = B * Tmax, chunk = head_chunk(rows), nchunks = (rows + chunk - 1) / chunk;
   return (size_t)nchunks * ((size_t)V * H + V) * sizeof(float);
 }
 
 int us_ctc_head_backward(const float* grad_logits, const float* hidden, const int64_t* lengths, const float* weight, int B, int Tmax, int V,
                          int H, float* d_weight, float* d_bias, float* d_hidden, void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (V < 2 || V > kMaxV || H < 4 || H > kMaxH || H % 4) {
+  if (head_error(V, H)) {
     char buf[160];
     snprintf(buf, sizeof buf, "us_ctc_head_backward: V must be in [2, %d] and H a multiple of 4 in [4, %d] (V = %d, H = %d)", kMaxV, kMaxH, V, H);
-    return train_bad(buf);
+    return bad_arg(buf);
   }
   if (!grad_logits || !hidden || !d_weight || !d_bias || (d_hidden && !weight) || !rows_ok(B, Tmax) || !workspace ||
       workspace_bytes < us_ctc_head_backward_workspace_bytes(B, Tmax, V, H))
-    return train_bad("us_ctc_head_backward: bad argument");
+    return bad_arg("us_ctc_head_backward: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = B * Tmax, chunk = head_chunk(rows), nchunks = (rows + chunk - 1) / chunk;
-  const int vt = (V + kTile - 1) / kTile, ht = (H + kTile - 1) / kTile;
+  const int vt = (V + kDtTile - 1) / kDtTile, ht = (H + kDtTile - 1) / kDtTile;
   const long long* lens = reinterpret_cast<const long long*>(lengths);
   float* part_w = static_cast<float*>(workspace);
   float* part_b = part_w + (size_t)nchunks * V * H;
@@ -688,10 +631,10 @@ int us_ctc_head_backward(const float* grad_logits, const float* hidden, const in
   hipLaunchKernelGGL(ctc_head_sum_kernel, dim3((unsigned)((nw + V + 255) / 256)), dim3(256), 0, s, part_w, part_b, d_weight, d_bias, nw, V,
                      nchunks);
   if (d_hidden)
-    hipLaunchKernelGGL(ctc_head_dx_kernel, dim3((rows + kTile - 1) / kTile, ht), dim3(256), 0, s, grad_logits, weight, lens, d_hidden, rows, Tmax,
+    hipLaunchKernelGGL(ctc_head_dx_kernel, dim3((rows + kDtTile - 1) / kDtTile, ht), dim3(256), 0, s, grad_logits, weight, lens, d_hidden, rows, Tmax,
                        V, H);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : train_fail("us_ctc_head_backward", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_ctc_head_backward", e);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
 #include "kernels.h"
 
 namespace us {
@@ -406,16 +407,6 @@ hipError_t launch_scale(const float* x, const float* scalar_dev, float* out, lon
 using namespace us;
 
 namespace {
-int fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  us::set_last_error(buf);
-  return US_EHIP;
-}
-int bad(const char* msg) {
-  us::set_last_error(msg);
-  return US_EINVAL;
-}
 inline float half_delta(float beta_min, float beta_max) { return (float)(0.5 * ((double)beta_max - (double)beta_min)); }
 }  // namespace
 
@@ -423,11 +414,11 @@ extern "C" {
 
 int us_forward_diffusion(const float* x0, const float* mask, const float* t, const float* z, float* xt, float* z_masked, int B, int F, int T,
                          float beta_min, float beta_max, us_stream stream) {
-  if (!x0 || !mask || !t || !xt || (z && !z_masked) || B <= 0 || F <= 0 || T <= 0) return bad("us_forward_diffusion: bad argument");
+  if (!x0 || !mask || !t || !xt || (z && !z_masked) || B <= 0 || F <= 0 || T <= 0) return bad_arg("us_forward_diffusion: bad argument");
   hipLaunchKernelGGL(forward_diffusion_kernel, dim3(nblocks((long long)B * F * T)), dim3(256), 0, static_cast<hipStream_t>(stream), x0,
                      mask, t, z, xt, z_masked, B, F, T, beta_min, half_delta(beta_min, beta_max));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_forward_diffusion", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_forward_diffusion", e);
 }
 
 size_t us_diffusion_loss_scratch_bytes(int B, int F, int T) {
@@ -436,95 +427,95 @@ size_t us_diffusion_loss_scratch_bytes(int B, int F, int T) {
 
 int us_diffusion_loss(const float* score, const float* z_masked, const float* t, const float* mask, float* loss, float* dscore, int B, int F,
                       int T, float beta_min, float beta_max, void* scratch, size_t scratch_bytes, us_stream stream) {
-  if (!score || !z_masked || !t || !mask || !loss || !scratch || B <= 0 || F <= 0 || T <= 0) return bad("us_diffusion_loss: bad argument");
-  if (scratch_bytes < us_diffusion_loss_scratch_bytes(B, F, T)) return bad("us_diffusion_loss: scratch too small");
+  if (!score || !z_masked || !t || !mask || !loss || !scratch || B <= 0 || F <= 0 || T <= 0) return bad_arg("us_diffusion_loss: bad argument");
+  if (scratch_bytes < us_diffusion_loss_scratch_bytes(B, F, T)) return bad_arg("us_diffusion_loss: scratch too small");
   const int nb = nblocks((long long)B * F * T, 512);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(diffusion_loss_partial_kernel, dim3(nb), dim3(256), 0, s, score, z_masked, t, mask, dscore, static_cast<double*>(scratch),
                      B, F, T, beta_min, half_delta(beta_min, beta_max));
   hipLaunchKernelGGL(diffusion_loss_final_kernel, dim3(1), dim3(64), 0, s, static_cast<const double*>(scratch), nb, loss);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_diffusion_loss", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_diffusion_loss", e);
 }
 
 int us_scale(const float* x, const float* scalar_dev, float* out, size_t n, us_stream stream) {
-  if (!x || !scalar_dev || !out) return bad("us_scale: null argument");
+  if (!x || !scalar_dev || !out) return bad_arg("us_scale: null argument");
   if (n == 0) return US_OK;
   hipLaunchKernelGGL(scale_by_scalar_kernel, dim3(nblocks((long long)n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, scalar_dev, out,
                      (long long)n);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_scale", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_scale", e);
 }
 
 int us_pow2_scale(const float* x, size_t n, int target_log2, float* scale_and_inverse, us_stream stream) {
-  if (!x || !scale_and_inverse || n == 0 || target_log2 < -100 || target_log2 > 100) return bad("us_pow2_scale: bad argument");
+  if (!x || !scale_and_inverse || n == 0 || target_log2 < -100 || target_log2 > 100) return bad_arg("us_pow2_scale: bad argument");
   hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), x, (long long)n, target_log2, scale_and_inverse);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_pow2_scale", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_pow2_scale", e);
 }
 
 int us_mul_mask(const float* x, const float* mask, float* out, int B, int F, int T, us_stream stream) {
-  if (!x || !mask || !out || B <= 0 || F <= 0 || T <= 0) return bad("us_mul_mask: bad argument");
+  if (!x || !mask || !out || B <= 0 || F <= 0 || T <= 0) return bad_arg("us_mul_mask: bad argument");
   hipError_t e = launch_mul_mask(x, mask, out, B, F, T, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? US_OK : fail("us_mul_mask", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_mul_mask", e);
 }
 
 int us_finetune_segment(const float* cond_x, const float* y, const float* attn, const int64_t* start, const int64_t* count, float* y_cut,
                         float* cond_y, float* seg_mask, int B, int F, int Lu, int Ly, int segment_size, us_stream stream) {
   if (!cond_x || !y || !attn || !start || !count || !y_cut || !cond_y || !seg_mask || B <= 0 || F <= 0 || Lu <= 0 || Ly <= 0 || segment_size <= 0)
-    return bad("us_finetune_segment: bad argument");
+    return bad_arg("us_finetune_segment: bad argument");
   hipLaunchKernelGGL(finetune_segment_kernel, dim3(nblocks((long long)B * F * segment_size)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      cond_x, y, attn, reinterpret_cast<const long long*>(start), reinterpret_cast<const long long*>(count), y_cut, cond_y,
                      seg_mask, B, F, Lu, Ly, segment_size);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_finetune_segment", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_finetune_segment", e);
 }
 
 int us_finetune_segment_backward(const float* d_cond_y, const float* attn, const int64_t* start, const int64_t* count, float* d_cond_x, int B,
                                  int F, int Lu, int Ly, int segment_size, us_stream stream) {
   if (!d_cond_y || !attn || !start || !count || !d_cond_x || B <= 0 || F <= 0 || Lu <= 0 || Ly <= 0 || segment_size <= 0)
-    return bad("us_finetune_segment_backward: bad argument");
+    return bad_arg("us_finetune_segment_backward: bad argument");
   hipLaunchKernelGGL(finetune_segment_bwd_kernel, dim3(nblocks((long long)B * F * Lu)), dim3(256), 0, static_cast<hipStream_t>(stream), d_cond_y,
                      attn, reinterpret_cast<const long long*>(start), reinterpret_cast<const long long*>(count), d_cond_x, B, F, Lu, Ly,
                      segment_size);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_finetune_segment_backward", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_finetune_segment_backward", e);
 }
 
 int us_prior_loss(const float* y, const float* mu_y, const float* y_mask, float* loss, float* d_mu_y, int B, int F, int T, us_stream stream) {
-  if (!y || !mu_y || !y_mask || !loss || B <= 0 || F <= 0 || T <= 0) return bad("us_prior_loss: bad argument");
+  if (!y || !mu_y || !y_mask || !loss || B <= 0 || F <= 0 || T <= 0) return bad_arg("us_prior_loss: bad argument");
   hipLaunchKernelGGL(prior_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), y, mu_y, y_mask, loss, d_mu_y, B, F, T);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_prior_loss", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_prior_loss", e);
 }
 
 int us_tts_durations(const float* logw, const float* x_mask, float* w_ceil, int64_t* y_lengths, int B, int L, float length_scale,
                      us_stream stream) {
-  if (!logw || !x_mask || !w_ceil || !y_lengths || B <= 0 || L <= 0) return bad("us_tts_durations: bad argument");
+  if (!logw || !x_mask || !w_ceil || !y_lengths || B <= 0 || L <= 0) return bad_arg("us_tts_durations: bad argument");
   hipLaunchKernelGGL(tts_durations_kernel, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), logw, x_mask, w_ceil,
                      reinterpret_cast<long long*>(y_lengths), L, length_scale);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_tts_durations", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_tts_durations", e);
 }
 
 int us_tts_align(const float* cond_x, const float* w_ceil, const float* x_mask, const int64_t* y_lengths, float* cond_y, float* attn,
                  float* y_mask, int B, int F, int L, int Tp, us_stream stream) {
-  if (!cond_x || !w_ceil || !x_mask || !y_lengths || !cond_y || B <= 0 || F <= 0 || L <= 0 || Tp <= 0) return bad("us_tts_align: bad argument");
-  if ((size_t)L * sizeof(float) > 60000) return bad("us_tts_align: more than 15000 symbols per utterance");
+  if (!cond_x || !w_ceil || !x_mask || !y_lengths || !cond_y || B <= 0 || F <= 0 || L <= 0 || Tp <= 0) return bad_arg("us_tts_align: bad argument");
+  if ((size_t)L * sizeof(float) > 60000) return bad_arg("us_tts_align: more than 15000 symbols per utterance");
   hipLaunchKernelGGL(tts_align_kernel, dim3((Tp + 255) / 256, B), dim3(256), (size_t)L * sizeof(float), static_cast<hipStream_t>(stream),
                      cond_x, w_ceil, x_mask, reinterpret_cast<const long long*>(y_lengths), cond_y, attn, y_mask, F, L, Tp);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_tts_align", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_tts_align", e);
 }
 
 int us_vc_align(const float* cond_x, const int64_t* x_lengths, const int64_t* y_lengths, float* cond_y, float* y_mask, int B, int F, int L,
                 int Tp, us_stream stream) {
   if (!cond_x || !x_lengths || !y_lengths || !cond_y || !y_mask || B <= 0 || B > 65535 || F <= 0 || L <= 0 || Tp <= 0)
-    return bad("us_vc_align: bad argument");
+    return bad_arg("us_vc_align: bad argument");
   hipLaunchKernelGGL(vc_align_kernel, dim3((Tp + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), cond_x,
                      reinterpret_cast<const long long*>(x_lengths), reinterpret_cast<const long long*>(y_lengths), cond_y, y_mask, F, L, Tp);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : fail("us_vc_align", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_vc_align", e);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <map>
 #include <string>
 #include <vector>
@@ -96,6 +97,20 @@ struct WeightTable {
     }
   }
 };
+
+// What the handle-free entry points (glue, units, units_fit, ctc, ctc_train, level, tts_train) answer: a HIP error by name, a refused argument,
+// and the batch a launch of one workgroup per item or per 64 rows takes: B in [1, 65535], T > 0, B * T <= 2^24.
+inline int hip_fail(const char* what, hipError_t e) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+  set_last_error(buf);
+  return US_EHIP;
+}
+inline int bad_arg(const char* msg) {
+  set_last_error(msg);
+  return US_EINVAL;
+}
+constexpr bool rows_ok(int B, int T) { return B > 0 && T > 0 && B <= 65535 && (long long)B * T <= (1LL << 24); }
 
 // a caller-owned workspace starts at its first 256-byte boundary (the *_workspace_bytes functions include the slack)
 inline float* ws_align(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255)); }

@@ -7,6 +7,7 @@
 // workgroup, indexed by the block's item): item b is then a tensor of lens.n[b] steps stored with row stride T.  The item is a grid dimension
 // of the launch, so no grid dimension caps the batch, and more than N items are a launch (or a pass of launches) per N: for_item_groups.
 // A kernel without a uniform form (mel, resample, HuBERT / WavLM) is no template: it takes the carrier alone and reads lens.n[b].
+// The handle-free calls (units, ctc, ctc_train, level, tts_train) take the lengths as a device array of int64 instead: item_len, row_live.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,17 @@ template <int N> struct ItemLens {      // item b of the launch has n[b] steps; 
   __device__ __forceinline__ int operator()(int b, int) const { return n[b]; }
 };
 static_assert(sizeof(ItemLens<32>) == 32 * sizeof(int) && sizeof(ItemLens<64>) == 64 * sizeof(int), "N ints at offset 0: a kernel's argument segment");
+
+// Valid steps of item b from a device array: lengths[b] clamped to [0, cap]; a null array is "every item has cap steps".
+__device__ __forceinline__ int item_len(const long long* __restrict__ lengths, int b, int cap) {
+  return lengths ? (int)min((long long)cap, max(0LL, lengths[b])) : cap;
+}
+// whether row (= b * Tmax + t) of a [B][Tmax] batch flattened to `rows` rows exists and lies inside its item
+__device__ __forceinline__ bool row_live(const long long* __restrict__ lengths, int row, int rows, int Tmax) {
+  if (row >= rows) return false;
+  const int b = row / Tmax;
+  return row - b * Tmax < item_len(lengths, b, Tmax);
+}
 
 // The batch in groups of N items: launch(b0, nb, lens, longest) for the nb <= N items from b0 on, lens.n[i] = len(b0 + i) and longest the
 // largest of them.  The item is a grid dimension of size nb, so the entries past nb are never read; they hold 1.

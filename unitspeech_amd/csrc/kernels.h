@@ -45,6 +45,19 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
+// One value per thread of a 256-thread workgroup -> the inclusive sums in the caller's scan[] (Hillis-Steele, exact for the integer
+// types it is used with).  Where an earlier use of scan[] may still be read, the caller puts a barrier in front.
+template <class T> __device__ __forceinline__ void block_scan256(T (&scan)[256], T v) {
+  const int tid = threadIdx.x;
+  scan[tid] = v;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const T a = tid >= o ? scan[tid - o] : 0;
+    __syncthreads();
+    scan[tid] += a;
+    __syncthreads();
+  }
+}
 #endif
 
 // ---- f16x3 operand range ---------------------------------------------------------------------------------------------

@@ -23,6 +23,8 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
@@ -84,10 +86,6 @@ __device__ __forceinline__ Map block_scan(const Map& mine, double h, Map* wave_t
     total = map_then(total, wave_tot[w], h);
   }
   return map_then(pre, exc, h);
-}
-
-__device__ __forceinline__ int item_len(const long long* __restrict__ lengths, int b, int Tmax) {
-  return lengths ? (int)min((long long)Tmax, max(0LL, lengths[b])) : Tmax;
 }
 
 // The reference's float -> int16 route: an fp32 product truncated toward zero, held to the int16 range.
@@ -541,16 +539,6 @@ __global__ __launch_bounds__(64) void level_gain_kernel(int nch, const double* _
   }
 }
 
-int level_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  set_last_error(buf);
-  return US_EHIP;
-}
-int level_bad(const char* msg) {
-  set_last_error(msg);
-  return US_EINVAL;
-}
 bool dtype_ok(int d) { return d == US_LEVEL_F32 || d == US_LEVEL_I16; }
 bool shape_ok(int B, int Tmax) { return B >= 1 && B <= 65535 && Tmax >= 1 && Tmax <= (1 << 30); }
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
@@ -570,10 +558,10 @@ size_t us_level_workspace_bytes(int B, int Tmax) { return shape_ok(B, Tmax) ? wo
 
 int us_level_measure(const void* wav, int in_dtype, int quantize_input, const int64_t* lengths, int B, int Tmax, int sample_rate, double* stats,
                      int64_t* counts, void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (sample_rate <= 0) return level_bad("us_level_measure: the sample rate must be positive");
-  if (!shape_ok(B, Tmax)) return level_bad("us_level_measure: B must be in [1, 65535] and Tmax in [1, 2^30]");
-  if (!dtype_ok(in_dtype)) return level_bad("us_level_measure: in_dtype must be US_LEVEL_F32 or US_LEVEL_I16");
-  if (!wav || !stats || !workspace) return level_bad("us_level_measure: bad argument");
+  if (sample_rate <= 0) return bad_arg("us_level_measure: the sample rate must be positive");
+  if (!shape_ok(B, Tmax)) return bad_arg("us_level_measure: B must be in [1, 65535] and Tmax in [1, 2^30]");
+  if (!dtype_ok(in_dtype)) return bad_arg("us_level_measure: in_dtype must be US_LEVEL_F32 or US_LEVEL_I16");
+  if (!wav || !stats || !workspace) return bad_arg("us_level_measure: bad argument");
   if (workspace_bytes < work_bytes(B, Tmax)) {
     set_last_error("us_level_measure: the workspace is smaller than us_level_workspace_bytes");
     return US_EWORKSPACE;
@@ -602,14 +590,14 @@ int us_level_measure(const void* wav, int in_dtype, int quantize_input, const in
   hipLaunchKernelGGL(level_final_kernel, dim3(B), dim3(64), 0, s, lens, Tmax, nch, hang, w.totals, w.tuples, stats,
                      reinterpret_cast<long long*>(counts));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : level_fail("us_level_measure", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_level_measure", e);
 }
 
 int us_level_apply(const void* wav, int in_dtype, int quantize_input, const int64_t* lengths, int B, int Tmax, const double* stats, double ndb,
                    void* out, int out_dtype, double* gain, int64_t* clipped, void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (!shape_ok(B, Tmax)) return level_bad("us_level_apply: B must be in [1, 65535] and Tmax in [1, 2^30]");
-  if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return level_bad("us_level_apply: a dtype must be US_LEVEL_F32 or US_LEVEL_I16");
-  if (!wav || !stats || !out || !workspace || !std::isfinite(ndb)) return level_bad("us_level_apply: bad argument");
+  if (!shape_ok(B, Tmax)) return bad_arg("us_level_apply: B must be in [1, 65535] and Tmax in [1, 2^30]");
+  if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return bad_arg("us_level_apply: a dtype must be US_LEVEL_F32 or US_LEVEL_I16");
+  if (!wav || !stats || !out || !workspace || !std::isfinite(ndb)) return bad_arg("us_level_apply: bad argument");
   if (workspace_bytes < work_bytes(B, Tmax)) {
     set_last_error("us_level_apply: the workspace is smaller than us_level_workspace_bytes");
     return US_EWORKSPACE;
@@ -635,7 +623,7 @@ int us_level_apply(const void* wav, int in_dtype, int quantize_input, const int6
                        ndb, static_cast<short*>(out), w.clipped);
   hipLaunchKernelGGL(level_gain_kernel, dim3(B), dim3(64), 0, s, nch, stats, ndb, w.clipped, gain, reinterpret_cast<long long*>(clipped));
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : level_fail("us_level_apply", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_level_apply", e);
 }
 
 }  // extern "C"

@@ -27,6 +27,8 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
@@ -89,8 +91,7 @@ __global__ __launch_bounds__(1024) void maximum_path_kernel(const float* __restr
   __shared__ unsigned table_lds[kTableWords];
   const int b = blockIdx.x;
   const int x = threadIdx.x, lane = x & 63, w = x >> 6;
-  const int tx = (int)min((long long)Tx, max(0LL, x_lengths[b]));
-  const int ty = (int)min((long long)Ty, max(0LL, y_lengths[b]));
+  const int tx = item_len(x_lengths, b, Tx), ty = item_len(y_lengths, b, Ty);
   if (tx == 0 || ty == 0) return;
   const int W = (ty + 31) >> 5;                                // words per row of the bit table
   const bool in_lds = (long long)tx * W <= kTableWords;
@@ -199,16 +200,6 @@ __global__ __launch_bounds__(256) void duration_loss_kernel(const float* __restr
   for (int i = threadIdx.x; i < n; i += 256) d_logw[i] = 2.f * (logw[i] - logf(1e-8f + dur[i]) * x_mask[i]) / len;
 }
 
-int tt_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  set_last_error(buf);
-  return US_EHIP;
-}
-int tt_bad(const char* msg) {
-  set_last_error(msg);
-  return US_EINVAL;
-}
 size_t table_words(int Tx, int Ty) { return (size_t)Tx * ((Ty + 31) / 32); }
 
 }  // namespace
@@ -221,12 +212,12 @@ extern "C" {
 int us_mas_log_prior(const float* mu_x, const float* y, const float* x_mask, const float* y_mask, float* log_prior, int B, int F, int Tx,
                      int Ty, us_stream stream) {
   if (!mu_x || !y || !x_mask || !y_mask || !log_prior || B <= 0 || F <= 0 || Tx <= 0 || Ty <= 0 || B > 65535)
-    return tt_bad("us_mas_log_prior: bad argument");
+    return bad_arg("us_mas_log_prior: bad argument");
   const float cst = (float)(-0.5 * std::log(2.0 * M_PI) * F);  // a Python double added to an fp32 tensor (:338)
   hipLaunchKernelGGL(mas_log_prior_kernel, dim3((Ty + 63) / 64, (Tx + 63) / 64, B), dim3(256), 0, static_cast<hipStream_t>(stream), mu_x, y,
                      x_mask, y_mask, log_prior, F, Tx, Ty, cst);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : tt_fail("us_mas_log_prior", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_mas_log_prior", e);
 }
 
 size_t us_maximum_path_workspace_bytes(int B, int Tx, int Ty) {
@@ -237,8 +228,8 @@ size_t us_maximum_path_workspace_bytes(int B, int Tx, int Ty) {
 int us_maximum_path(const float* log_prior, const int64_t* x_lengths, const int64_t* y_lengths, float* attn, float* durations, int B, int Tx,
                     int Ty, void* workspace, size_t workspace_bytes, us_stream stream) {
   if (!log_prior || !x_lengths || !y_lengths || !attn || !durations || B <= 0 || Tx <= 0 || Ty <= 0)
-    return tt_bad("us_maximum_path: bad argument");
-  if (Tx > 64 * kMaxWaves) return tt_bad("us_maximum_path: more than 1024 symbols per utterance");
+    return bad_arg("us_maximum_path: bad argument");
+  if (Tx > 64 * kMaxWaves) return bad_arg("us_maximum_path: more than 1024 symbols per utterance");
   const size_t need = us_maximum_path_workspace_bytes(B, Tx, Ty);
   if (need && (!workspace || workspace_bytes < need)) {
     set_last_error("us_maximum_path: workspace too small (us_maximum_path_workspace_bytes)");
@@ -247,21 +238,21 @@ int us_maximum_path(const float* log_prior, const int64_t* x_lengths, const int6
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(attn, 0, (size_t)B * Tx * Ty * sizeof(float), s);
   if (e == hipSuccess) e = hipMemsetAsync(durations, 0, (size_t)B * Tx * sizeof(float), s);
-  if (e != hipSuccess) return tt_fail("us_maximum_path", e);
+  if (e != hipSuccess) return hip_fail("us_maximum_path", e);
   const int threads = 64 * ((Tx + 63) / 64);
   hipLaunchKernelGGL(maximum_path_kernel, dim3(B), dim3(threads), 0, s, log_prior, reinterpret_cast<const long long*>(x_lengths),
                      reinterpret_cast<const long long*>(y_lengths), attn, durations, static_cast<unsigned*>(workspace), Tx, Ty);
   e = hipGetLastError();
-  return e == hipSuccess ? US_OK : tt_fail("us_maximum_path", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_maximum_path", e);
 }
 
 int us_duration_loss(const float* logw, const float* durations, const float* x_mask, const int64_t* x_lengths, float* loss, float* d_logw,
                      int B, int Tx, us_stream stream) {
-  if (!logw || !durations || !x_mask || !x_lengths || !loss || B <= 0 || Tx <= 0) return tt_bad("us_duration_loss: bad argument");
+  if (!logw || !durations || !x_mask || !x_lengths || !loss || B <= 0 || Tx <= 0) return bad_arg("us_duration_loss: bad argument");
   hipLaunchKernelGGL(duration_loss_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), logw, durations, x_mask,
                      reinterpret_cast<const long long*>(x_lengths), loss, d_logw, B, B * Tx);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : tt_fail("us_duration_loss", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_duration_loss", e);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 //   us_units_pack_centers  centres [K, D] -> the GEMM operand P[Dpad][Kpad] (d-major, zero padded), h[k] = fp32(1/2 |c_k|^2 in fp64)
 //                          (+inf on the padding, which therefore never wins) and C = max_k |c_k| rounded up.
 //   us_units_quantize      units[b][t] = argmin_k |x - c_k|^2 = argmin_k (h[k] - x . c_k).  The products run on the fp32 matrix cores
-//                          (v_mfma_f32_32x32x2_f32: an fp32 fma chain); the epilogue keeps (best, second best, index) per row and the
+//                          (the tile loop of dense_tile.h: fp32 fma chains); the epilogue keeps (best, second best, index) per row and the
 //                          [T, K] scores never reach memory.  A row whose gap is not above twice the proven fp32 error bound E is
 //                          flagged, and a second kernel takes the fp64 argmin of sum_d (x_d - c_kd)^2 over all K for the flagged rows
 //                          (compacted list in workspace, length read on the device).  So every row gets the fp64 argmin with the lower
@@ -26,17 +26,15 @@
 #include <cstdio>
 
 #include "../../include/unitspeech_hip.h"
+#include "dense_tile.h"
 #include "handle.h"
+#include "item_lens.h"
 #include "kernels.h"
 
 namespace us {
 namespace {
 
 constexpr int kMaxK = 2048, kMaxD = 1024, kMaxSpan = 64;
-constexpr int kBR = 64;        // rows per workgroup
-constexpr int kBC = 64;        // centres per tile
-constexpr int kBK = 16;        // reduction slice per LDS stage
-constexpr int kXld = 68;       // row stride of the transposed feature slice: the four k of a float4 land on banks 16 apart
 constexpr int kTargetGroups = 512;   // workgroups wanted before the centres stop being split across workgroups (two per CU)
 
 // ---- pack ---------------------------------------------------------------------------------------------------------------
@@ -104,62 +102,45 @@ __device__ __forceinline__ Best merge(const Best a, const Best o) {
 __global__ __launch_bounds__(256) void un_score_kernel(const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ hn,
                                                        float4* __restrict__ part, float* __restrict__ xsq, int rows, int D, int Dpad, int Kpad,
                                                        int ntiles, int tps, int nsplit) {
-  __shared__ float Cs[2][kBK][kBC];
-  __shared__ float Xs[2][kBK][kXld];
+  __shared__ float Cs[2][kDtBK][kDtTile];
+  __shared__ float Xs[2][kDtBK][kDtLdT];
   __shared__ float4 join[2][32];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
+  DENSE_LANE(tid);
+  DENSE_STAGE_K(tid);                                    // centre slice: 16 k x 64 centres, one float4 per thread
+  DENSE_STAGE_T(tid);                                    // feature slice: 64 rows x 16 k, one float4 per thread
   const int ch = wave & 1, rh = wave >> 1;
-  const int kl = lane >> 5, cl = lane & 31;
-  const int r0 = blockIdx.x * kBR, split = blockIdx.y;
-  const int pr = tid >> 4, pc = (tid & 15) * 4;          // centre slice: 16 k x 64 centres, one float4 per thread
-  const int xr = tid >> 2, xk = (tid & 3) * 4;           // feature slice: 64 rows x 16 k, one float4 per thread
-  const bool xlive = r0 + xr < rows;
-  const float* __restrict__ xrow = X + (size_t)(xlive ? r0 + xr : 0) * D;
-  const int nk = Dpad / kBK;
+  const int r0 = blockIdx.x * kDtTile, split = blockIdx.y;
+  const bool xlive = r0 + tr < rows;
+  const float* __restrict__ xrow = X + (size_t)(xlive ? r0 + tr : 0) * D;
+  const int nk = Dpad / kDtBK;
   Best best{INFINITY, INFINITY, 0x7fffffff};
   float sx = 0.f;
   const int t_begin = split * tps, t_end = min(ntiles, t_begin + tps);
   for (int tile = t_begin; tile < t_end; ++tile) {
-    const int c0 = tile * kBC;
+    const int c0 = tile * kDtTile;
     float4 creg, xreg;
     auto load = [&](int k0) {
-      creg = *reinterpret_cast<const float4*>(P + (size_t)(k0 + pr) * Kpad + c0 + pc);
-      xreg = (xlive && k0 + xk < D) ? *reinterpret_cast<const float4*>(xrow + k0 + xk) : make_float4(0.f, 0.f, 0.f, 0.f);
+      creg = *reinterpret_cast<const float4*>(P + (size_t)(k0 + sk) * Kpad + c0 + sc);
+      xreg = (xlive && k0 + tk < D) ? *reinterpret_cast<const float4*>(xrow + k0 + tk) : make_float4(0.f, 0.f, 0.f, 0.f);
     };
     auto store = [&](int buf) {
-      *reinterpret_cast<float4*>(&Cs[buf][pr][pc]) = creg;
-      Xs[buf][xk + 0][xr] = xreg.x;
-      Xs[buf][xk + 1][xr] = xreg.y;
-      Xs[buf][xk + 2][xr] = xreg.z;
-      Xs[buf][xk + 3][xr] = xreg.w;
+      *reinterpret_cast<float4*>(&Cs[buf][sk][sc]) = creg;
+      Xs[buf][tk + 0][tr] = xreg.x;
+      Xs[buf][tk + 1][tr] = xreg.y;
+      Xs[buf][tk + 2][tr] = xreg.z;
+      Xs[buf][tk + 3][tr] = xreg.w;
     };
     f32x16 acc[2];
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-    __syncthreads();                                     // the tile before this one is done with both buffers
-    load(0);
-    store(0);
-    __syncthreads();
     const bool first = tile == t_begin;
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) load((kt + 1) * kBK);
-#pragma unroll
-      for (int s = 0; s < kBK / 2; ++s) {                // two accumulators in turn: no MFMA waits on the one before it
-        const float fa = Cs[cur][2 * s + kl][ch * 32 + cl];
-        const float fb = Xs[cur][2 * s + kl][rh * 32 + cl];
-        if (first) sx = fmaf(fb, fb, sx);
-        acc[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[s & 1], 0, 0, 0);
-      }
-      if (kt + 1 < nk) store(cur ^ 1);
-      __syncthreads();
-    }
+    __syncthreads();                                     // the tile before this one is done with both buffers
+    dense_tile_mainloop(Cs, Xs, ch, rh, nk, acc, load, store, [&](float, float fb) {
+      if (first) sx = fmaf(fb, fb, sx);                  // |x|^2 of the lane's row: the first tile sees every k once
+    });
     // the MFMA column is the row of X, the MFMA row the centre: a lane meets its centres in ascending order
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int c = c0 + ch * 32 + mfma32_row(r, kl);
+      const int c = c0 + DENSE_ROW(ch, r);
       const float s = hn[c] - (acc[0][r] + acc[1][r]);
       if (s < best.b1) {
         best.b2 = best.b1;
@@ -184,7 +165,7 @@ __global__ __launch_bounds__(256) void un_score_kernel(const float* __restrict__
     o.b2 = j.y;
     o.i1 = __float_as_int(j.z);
     best = merge(best, o);
-    const int row = r0 + rh * 32 + cl;
+    const int row = r0 + DENSE_AT(rh);
     if (row < rows) {
       part[(size_t)row * nsplit + split] = make_float4(best.b1, best.b2, __int_as_float(best.i1), 0.f);
       if (split == 0) xsq[row] = sx;
@@ -287,14 +268,7 @@ __device__ void rle_block(const long long* __restrict__ u, int len, long long* _
   int cnt = 0;
   for (int t = t0; t < t1; ++t) cnt += (t == 0 || u[t] != u[t - 1]) ? 1 : 0;
   __syncthreads();                                       // scan[] may still be read by a previous use
-  scan[tid] = cnt;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int v = tid >= o ? scan[tid - o] : 0;
-    __syncthreads();
-    scan[tid] += v;
-    __syncthreads();
-  }
+  block_scan256(scan, cnt);
   const int n = scan[255];
   int pos = scan[tid] - cnt;
   for (int t = t0; t < t1; ++t) {
@@ -319,14 +293,12 @@ __device__ void rle_block(const long long* __restrict__ u, int len, long long* _
   if (tid == 0) n_out[0] = n;
 }
 
-__device__ __forceinline__ int clamp_len(long long v, int cap) { return (int)min((long long)cap, max(0LL, v)); }
-
 __global__ __launch_bounds__(256) void un_dedup_kernel(const long long* __restrict__ units, const long long* __restrict__ lengths,
                                                        long long* __restrict__ out_u, long long* __restrict__ out_d,
                                                        long long* __restrict__ n_out, int* __restrict__ starts, int Tmax) {
   const int b = blockIdx.x;
   const size_t o = (size_t)b * Tmax;
-  rle_block(units + o, clamp_len(lengths[b], Tmax), out_u + o, out_d + o, nullptr, n_out + b, starts + o, Tmax);
+  rle_block(units + o, item_len(lengths, b, Tmax), out_u + o, out_d + o, nullptr, n_out + b, starts + o, Tmax);
 }
 
 // ---- process_unit ------------------------------------------------------------------------------------------------------------
@@ -345,19 +317,12 @@ __global__ __launch_bounds__(256) void un_process_kernel(const long long* __rest
   const long long* __restrict__ dur = durations ? durations + (size_t)b * Lin : nullptr;
   long long* __restrict__ cum = cum_ws + (size_t)b * Lin;
   long long* __restrict__ fr = frames_ws + (size_t)b * Lout;
-  const int n = clamp_len(n_in[b], Lin);
+  const int n = item_len(n_in, b, Lin);
   const int chunk = (n + 255) / 256;
   const int i0 = min(n, tid * chunk), i1 = min(n, i0 + chunk);
   long long s = 0;
   for (int i = i0; i < i1; ++i) s += dur ? max(0LL, dur[i]) : 1LL;
-  scan[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const long long v = tid >= o ? scan[tid - o] : 0;
-    __syncthreads();
-    scan[tid] += v;
-    __syncthreads();
-  }
+  block_scan256(scan, s);
   const long long total = scan[255];
   long long run = scan[tid] - s;
   for (int i = i0; i < i1; ++i) {
@@ -407,16 +372,6 @@ __global__ __launch_bounds__(256) void un_process_kernel(const long long* __rest
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-int un_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  set_last_error(buf);
-  return US_EHIP;
-}
-int un_bad(const char* msg) {
-  set_last_error(msg);
-  return US_EINVAL;
-}
 const char* shape_error(int K, int D) {
   if (K < 1 || K > kMaxK) return "K must be in [1, 2048]";
   if (D < 4 || D > kMaxD || D % 4) return "D must be a multiple of 4 in [4, 1024]";
@@ -429,8 +384,8 @@ struct Split {
 };
 Split split_for(int rows, int K) {
   Split s;
-  s.ntiles = round_up(K, kBC) / kBC;
-  const int groups = (rows + kBR - 1) / kBR;
+  s.ntiles = round_up(K, kDtTile) / kDtTile;
+  const int groups = (rows + kDtTile - 1) / kDtTile;
   int want = (kTargetGroups + groups - 1) / groups;
   want = want < 1 ? 1 : (want > s.ntiles ? s.ntiles : want);
   s.tps = (s.ntiles + want - 1) / want;
@@ -463,7 +418,6 @@ Layout layout(int B, int Tmax, int K, int Lout) {
   l.total = o;
   return l;
 }
-bool size_ok(int B, int T) { return B > 0 && T > 0 && B <= 65535 && (long long)B * T <= (1LL << 24); }
 
 }  // namespace
 }  // namespace us
@@ -474,28 +428,28 @@ extern "C" {
 
 size_t us_units_packed_bytes(int K, int D) {
   if (shape_error(K, D)) return 0;
-  return ((size_t)round_up(D, kBK) * round_up(K, kBC) + round_up(K, kBC) + 4) * sizeof(float);
+  return ((size_t)round_up(D, kDtBK) * round_up(K, kDtTile) + round_up(K, kDtTile) + 4) * sizeof(float);
 }
 
 int us_units_pack_centers(const float* centers, int K, int D, void* packed, size_t packed_bytes, us_stream stream) {
   if (const char* m = shape_error(K, D)) {
     char buf[128];
     snprintf(buf, sizeof buf, "us_units_pack_centers: %s (K = %d, D = %d)", m, K, D);
-    return un_bad(buf);
+    return bad_arg(buf);
   }
-  if (!centers || !packed || packed_bytes < us_units_packed_bytes(K, D)) return un_bad("us_units_pack_centers: bad argument");
-  const int Kpad = round_up(K, kBC), Dpad = round_up(D, kBK);
+  if (!centers || !packed || packed_bytes < us_units_packed_bytes(K, D)) return bad_arg("us_units_pack_centers: bad argument");
+  const int Kpad = round_up(K, kDtTile), Dpad = round_up(D, kDtBK);
   float* P = static_cast<float*>(packed);
   float* hn = P + (size_t)Dpad * Kpad;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(un_norm_kernel, dim3(1), dim3(1024), 0, s, centers, hn, hn + Kpad, K, D, Kpad);
   hipLaunchKernelGGL(un_transpose_kernel, dim3(512), dim3(256), 0, s, centers, P, K, D, Kpad, Dpad);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : un_fail("us_units_pack_centers", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_pack_centers", e);
 }
 
 size_t us_units_workspace_bytes(int B, int Tmax, int K, int D, int Lout) {
-  if (!size_ok(B, Tmax) || Lout < 0 || K < 0 || (K > 0 && shape_error(K, D)) || (Lout > 0 && !size_ok(B, Lout))) return 0;
+  if (!rows_ok(B, Tmax) || Lout < 0 || K < 0 || (K > 0 && shape_error(K, D)) || (Lout > 0 && !rows_ok(B, Lout))) return 0;
   return layout(B, Tmax, K, Lout).total;
 }
 
@@ -504,15 +458,15 @@ int us_units_quantize(const float* dense, const int64_t* lengths, const void* pa
   if (const char* m = shape_error(K, D)) {
     char buf[128];
     snprintf(buf, sizeof buf, "us_units_quantize: %s (K = %d, D = %d)", m, K, D);
-    return un_bad(buf);
+    return bad_arg(buf);
   }
-  if (!dense || !lengths || !packed || !units || !counters || !size_ok(B, Tmax)) return un_bad("us_units_quantize: bad argument");
+  if (!dense || !lengths || !packed || !units || !counters || !rows_ok(B, Tmax)) return bad_arg("us_units_quantize: bad argument");
   const Layout l = layout(B, Tmax, K, 0);
   if (!workspace || workspace_bytes < l.total) {
     set_last_error("us_units_quantize: workspace too small (us_units_workspace_bytes)");
     return US_EWORKSPACE;
   }
-  const int rows = B * Tmax, Kpad = round_up(K, kBC), Dpad = round_up(D, kBK);
+  const int rows = B * Tmax, Kpad = round_up(K, kDtTile), Dpad = round_up(D, kDtBK);
   const Split sp = split_for(rows, K);
   const float* P = static_cast<const float*>(packed);
   const float* hn = P + (size_t)Dpad * Kpad;
@@ -522,21 +476,21 @@ int us_units_quantize(const float* dense, const int64_t* lengths, const void* pa
   int* list = reinterpret_cast<int*>(ws + l.list);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), s);
-  if (e != hipSuccess) return un_fail("us_units_quantize", e);
-  hipLaunchKernelGGL(un_score_kernel, dim3((rows + kBR - 1) / kBR, sp.nsplit), dim3(256), 0, s, dense, P, hn, part, xsq, rows, D, Dpad, Kpad,
+  if (e != hipSuccess) return hip_fail("us_units_quantize", e);
+  hipLaunchKernelGGL(un_score_kernel, dim3((rows + kDtTile - 1) / kDtTile, sp.nsplit), dim3(256), 0, s, dense, P, hn, part, xsq, rows, D, Dpad, Kpad,
                      sp.ntiles, sp.tps, sp.nsplit);
   hipLaunchKernelGGL(un_decide_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, part, xsq, hn + Kpad,
                      reinterpret_cast<const long long*>(lengths), reinterpret_cast<long long*>(units), list, counters, rows, Tmax, D, sp.nsplit);
   hipLaunchKernelGGL(un_exact_kernel, dim3(rows < 2048 ? rows : 2048), dim3(256), 0, s, dense, P, list, counters,
                      reinterpret_cast<long long*>(units), K, D, Kpad);
   e = hipGetLastError();
-  return e == hipSuccess ? US_OK : un_fail("us_units_quantize", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_quantize", e);
 }
 
 int us_units_dedup(const int64_t* units, const int64_t* lengths, int B, int Tmax, int64_t* out_units, int64_t* out_durations, int64_t* n,
                    void* workspace, size_t workspace_bytes, us_stream stream) {
-  if (!units || !lengths || !out_units || !out_durations || !n || !size_ok(B, Tmax) || units == out_units)
-    return un_bad("us_units_dedup: bad argument");
+  if (!units || !lengths || !out_units || !out_durations || !n || !rows_ok(B, Tmax) || units == out_units)
+    return bad_arg("us_units_dedup: bad argument");
   const Layout l = layout(B, Tmax, 0, 0);
   if (!workspace || workspace_bytes < l.total) {
     set_last_error("us_units_dedup: workspace too small (us_units_workspace_bytes)");
@@ -547,7 +501,7 @@ int us_units_dedup(const int64_t* units, const int64_t* lengths, int B, int Tmax
                      reinterpret_cast<long long*>(out_durations), reinterpret_cast<long long*>(n),
                      reinterpret_cast<int*>(static_cast<char*>(workspace) + l.starts), Tmax);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : un_fail("us_units_dedup", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_dedup", e);
 }
 
 static int process_at(const int64_t* units, const int64_t* durations, const int64_t* n_in, int B, int Lin, int sampling_rate, int hop_length,
@@ -559,7 +513,7 @@ static int process_at(const int64_t* units, const int64_t* durations, const int6
                      reinterpret_cast<long long*>(n_out), reinterpret_cast<long long*>(ws + l.cum), reinterpret_cast<long long*>(ws + l.frames),
                      reinterpret_cast<int*>(ws + l.starts), Lin, Lout, (long long)(sampling_rate / 50), (long long)hop_length);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : un_fail("us_units_process", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_process", e);
 }
 
 static const char* rate_error(int sampling_rate, int hop_length) {
@@ -575,10 +529,10 @@ int us_units_process(const int64_t* units, const int64_t* durations, const int64
   if (const char* m = rate_error(sampling_rate, hop_length)) {
     char buf[160];
     snprintf(buf, sizeof buf, "us_units_process: %s (sampling_rate = %d, hop_length = %d)", m, sampling_rate, hop_length);
-    return un_bad(buf);
+    return bad_arg(buf);
   }
-  if (!units || !n_in || !out_units || !out_durations || !n_out || !size_ok(B, Lin) || !size_ok(B, Lout))
-    return un_bad("us_units_process: bad argument");
+  if (!units || !n_in || !out_units || !out_durations || !n_out || !rows_ok(B, Lin) || !rows_ok(B, Lout))
+    return bad_arg("us_units_process: bad argument");
   const Layout l = layout(B, Lin, 0, Lout);
   if (!workspace || workspace_bytes < l.total) {
     set_last_error("us_units_process: workspace too small (us_units_workspace_bytes)");
@@ -594,10 +548,10 @@ int us_units_encode(const float* dense, const int64_t* lengths, const void* pack
   if (const char* m = rate_error(sampling_rate, hop_length)) {
     char buf[160];
     snprintf(buf, sizeof buf, "us_units_encode: %s (sampling_rate = %d, hop_length = %d)", m, sampling_rate, hop_length);
-    return un_bad(buf);
+    return bad_arg(buf);
   }
-  if (shape_error(K, D) || !size_ok(B, Tmax) || !size_ok(B, Lout) || !out_units || !out_durations || !n_out)
-    return un_bad("us_units_encode: bad argument");
+  if (shape_error(K, D) || !rows_ok(B, Tmax) || !rows_ok(B, Lout) || !out_units || !out_durations || !n_out)
+    return bad_arg("us_units_encode: bad argument");
   const Layout l = layout(B, Tmax, K, Lout);
   if (!workspace || workspace_bytes < l.total) {
     set_last_error("us_units_encode: workspace too small (us_units_workspace_bytes)");

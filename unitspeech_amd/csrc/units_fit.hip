@@ -592,21 +592,11 @@ __global__ __launch_bounds__(256) void uf_seed_row_kernel(const float* __restric
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-int uf_fail(const char* what, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-  set_last_error(buf);
-  return US_EHIP;
-}
 int uf_bad(const char* what, int64_t rows, int K, int D) {
   char buf[256];
   snprintf(buf, sizeof buf, "%s: K must be in [1, 2048], D a multiple of 4 in [4, 1024], rows in [1, 2^24] (K = %d, D = %d, rows = %lld)", what,
            K, D, (long long)rows);
   set_last_error(buf);
-  return US_EINVAL;
-}
-int uf_arg(const char* msg) {
-  set_last_error(msg);
   return US_EINVAL;
 }
 int uf_small(const char* msg) {
@@ -636,13 +626,13 @@ int us_units_fit_state_clear(void* state, size_t state_bytes, int K, int D, us_s
   const size_t n = state_layout(K, D).total;
   if (!state || state_bytes < n) return uf_small("us_units_fit_state_clear: state too small (us_units_fit_state_bytes)");
   hipError_t e = hipMemsetAsync(state, 0, n, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? US_OK : uf_fail("us_units_fit_state_clear", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_fit_state_clear", e);
 }
 
 int us_units_fit_accumulate(const float* dense, const int64_t* labels, const float* centers, int64_t rows, int K, int D, void* state,
                             size_t state_bytes, void* workspace, size_t workspace_bytes, us_stream stream) {
   if (!shape_ok(K, D) || !rows_ok(rows)) return uf_bad("us_units_fit_accumulate", rows, K, D);
-  if (!dense || !labels || !centers) return uf_arg("us_units_fit_accumulate: bad argument");
+  if (!dense || !labels || !centers) return bad_arg("us_units_fit_accumulate: bad argument");
   const StateLayout sl = state_layout(K, D);
   const WorkLayout wl = work_layout(rows, K, D);
   if (!state || state_bytes < sl.total) return uf_small("us_units_fit_accumulate: state too small (us_units_fit_state_bytes)");
@@ -676,15 +666,15 @@ int us_units_fit_accumulate(const float* dense, const int64_t* labels, const flo
   hipLaunchKernelGGL(uf_reduce_kernel, dim3(K + 1, (D + 255) / 256), dim3(256), 0, s, part, pin, offs, cstart, skip, reinterpret_cast<double*>(st + sl.sums),
                      reinterpret_cast<long long*>(st + sl.counts), reinterpret_cast<long long*>(st + sl.scalars), K, D, dm.nchunks, items);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : uf_fail("us_units_fit_accumulate", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_fit_accumulate", e);
 }
 
 int us_units_fit_update(int mode, const float* centers_in, float* centers_out, const int64_t* totals_in, int64_t* totals_out, int K, int D,
                         void* state, size_t state_bytes, void* record, us_stream stream) {
   if (!shape_ok(K, D)) return uf_bad("us_units_fit_update", 1, K, D);
-  if (mode != US_UNITS_FIT_LLOYD && mode != US_UNITS_FIT_MINIBATCH) return uf_arg("us_units_fit_update: mode must be US_UNITS_FIT_LLOYD or US_UNITS_FIT_MINIBATCH");
+  if (mode != US_UNITS_FIT_LLOYD && mode != US_UNITS_FIT_MINIBATCH) return bad_arg("us_units_fit_update: mode must be US_UNITS_FIT_LLOYD or US_UNITS_FIT_MINIBATCH");
   if (!centers_in || !centers_out || !record || (mode == US_UNITS_FIT_MINIBATCH && (!totals_in || !totals_out)))
-    return uf_arg("us_units_fit_update: bad argument");
+    return bad_arg("us_units_fit_update: bad argument");
   const StateLayout sl = state_layout(K, D);
   if (!state || state_bytes < sl.total) return uf_small("us_units_fit_update: state too small (us_units_fit_state_bytes)");
   char* st = static_cast<char*>(state);
@@ -698,7 +688,7 @@ int us_units_fit_update(int mode, const float* centers_in, float* centers_out, c
                      reinterpret_cast<const double*>(st + sl.shift), reinterpret_cast<long long*>(st + sl.scalars),
                      reinterpret_cast<long long*>(record), K, mb);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : uf_fail("us_units_fit_update", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_fit_update", e);
 }
 
 int us_units_fit_seed_step(const float* dense, const int64_t* lengths, int B, int Tmax, int K, int D, int step, double u, double* mind,
@@ -706,7 +696,7 @@ int us_units_fit_seed_step(const float* dense, const int64_t* lengths, int B, in
   const int64_t rows = (int64_t)B * Tmax;
   if (!shape_ok(K, D) || B < 1 || Tmax < 1 || !rows_ok(rows)) return uf_bad("us_units_fit_seed_step", rows, K, D);
   if (!dense || !lengths || !mind || !centers || !picked || step < 0 || step >= K || !(u >= 0.0 && u < 1.0))
-    return uf_arg("us_units_fit_seed_step: bad argument (step in [0, K), u in [0, 1))");
+    return bad_arg("us_units_fit_seed_step: bad argument (step in [0, K), u in [0, 1))");
   const WorkLayout wl = work_layout(rows, K, D);
   if (!workspace || workspace_bytes < wl.total) return uf_small("us_units_fit_seed_step: workspace too small (us_units_fit_workspace_bytes)");
   char* ws = static_cast<char*>(workspace);
@@ -721,7 +711,7 @@ int us_units_fit_seed_step(const float* dense, const int64_t* lengths, int B, in
   hipLaunchKernelGGL(uf_seed_block_kernel, dim3(1), dim3(256), 0, s, bsum, bcnt, sel, nb, first, u);
   hipLaunchKernelGGL(uf_seed_row_kernel, dim3(1), dim3(256), 0, s, dense, mind, sel, centers, reinterpret_cast<long long*>(picked), n, D, step);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : uf_fail("us_units_fit_seed_step", e);
+  return e == hipSuccess ? US_OK : hip_fail("us_units_fit_seed_step", e);
 }
 
 }  // extern "C"
