@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void skeleton_kernel(const float* __restric
     float* buf = lds + ((s + 1) & 1) * 6144;
     if (FLAGS & 4) {
       if (BUF) {
-        __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g, 0, 0x7fffffff, 0x00020000);
+        __amdgpu_buffer_rsrc_t rsrc = raw_buffer(g, 0x7fffffffu);
         const int voff = (blockIdx.x * 256 + threadIdx.x) * 16;
 #pragma unroll
         for (int j = 0; j < PIECES; ++j)

@@ -12,8 +12,6 @@
 
 namespace us {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kChunk = 128;
 constexpr int kQkvLd = 3 * kHidden;
 
@@ -61,7 +59,7 @@ __global__ __launch_bounds__(256) void attn_ctx_partial_kernel(const float* __re
   float* pc = part_ctx + (blk * kHeads + h) * (kDimHead * kDimHead);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    int d = (r & 3) + 8 * (r >> 2) + 4 * hh;
+    int d = mfma32_row(r, hh);
     pc[d * kDimHead + c] = acc[r];
   }
   if (hh == 0) {
@@ -367,8 +365,7 @@ __global__ __launch_bounds__(256) void attn_wtotal_kernel(const float* __restric
   }
   float* base = wtotal + (long long)b * C * C;
   if (f16) {
-    typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-    half4_t hi, lo;
+    half4 hi, lo;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       us_half h_, l_;
@@ -378,8 +375,8 @@ __global__ __launch_bounds__(256) void attn_wtotal_kernel(const float* __restric
     }
     // piece (k tile, n, group of 8 k) = 8 hi | 8 lo halves; this thread owns half of each plane
     _Float16* d = reinterpret_cast<_Float16*>(base) + (((long long)blockIdx.x * C + n) * 4 + (g8 >> 1)) * 16 + (g8 & 1) * 4;
-    *reinterpret_cast<half4_t*>(d) = hi;
-    *reinterpret_cast<half4_t*>(d + 8) = lo;
+    *reinterpret_cast<half4*>(d) = hi;
+    *reinterpret_cast<half4*>(d + 8) = lo;
     range_report(range_flag, over, kRangeWeight);
   } else {
 #pragma unroll

@@ -13,10 +13,8 @@
 // (`buffer_load_dwordx4 ... offen lds`: SGPR buffer descriptor + 32-bit per-lane byte offset; no staging registers, no
 // ds_write): the A rows are gathered per tap through per-lane offsets, out-of-image taps get an offset beyond the descriptor's
 // range and read zeros; the B rows come from weights pre-packed as [tap][Cin/BK][Cout][BK] so a tile row is one
-// contiguous BK*4-byte line.  The LDS image is lane-linear as the DMA requires; bank conflicts of the
-// ds_read_b128 fragment reads are removed by an XOR swizzle applied on the SOURCE side (lane `pos` of a row
-// fetches 16-byte chunk pos ^ swz(row)) and again on the read side, swz(row) = (row / (64/BK)) % (BK/4): the 16
-// rows of a ds_read_b128 lane group then hit 16 distinct 16-byte slots of the 256-byte bank window.
+// contiguous BK*4-byte line.  The LDS image is lane-linear as the DMA requires; bank conflicts of the ds_read_b128
+// fragment reads are removed by an XOR swizzle on the SOURCE side and again on the read side (chunk_slot, f16x3_tile.h).
 // Two LDS buffers; the DMA for chunk s+1 is issued before the MFMAs of chunk s; one barrier per chunk.
 //
 // Inputs are expected to be already multiplied by the frame mask by their producer (every consumer of such a
@@ -25,25 +23,12 @@
 // BOTH operands, so the pairs (j, 4+j) are summed by instruction j; the K-sum is complete, only its order differs.
 #include <type_traits>
 #include "kernels.h"
+#include "f16x3_tile.h"
 #include "pack_f16.h"
 
 namespace us {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TN = 128;      // columns per workgroup of the NB = 2 instantiations (host-side sizing)
-
-// One wave-wide LDS-DMA piece: 64 lanes x 16 bytes, lane l lands at lds_dst + 16*l.  `buffer_load_dwordx4 ... offen lds`
-// (SGPR descriptor + 32-bit per-lane byte offset + scalar offset) instead of `global_load_lds_dwordx4` (64-bit per-lane
-// address): measured on MI355X in the kernel's own skeleton (tools/conv_bench), 6 pieces per 32 MFMAs cost 15 % of the
-// MFMA rate as global_load_lds and nothing as buffer loads.  A lane whose offset is >= num_records reads zeros
-// (raw-buffer range check), which implements the zero padding of out-of-image taps.
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff_bytes, unsigned soff_bytes, float* lds_dst_wave_uniform) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst_wave_uniform, 16, (int)voff_bytes,
-                                           (int)soff_bytes, 0, 0);
-}
 
 // WINO = true: Winograd-domain GEMMs with the output transform in registers.  `in` is V [16][B][th][tw][Cin], `wt` the 16
 // per-frequency matrices (wt_bstride apart); the workgroup runs its [TM tiles x TN channels] GEMM for the frequencies
@@ -52,18 +37,12 @@ __device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned vof
 // output position (oy0, ox0) = (r, q) of the 2x2 tile with ostep = 2.  Saves the [16][B][tiles][Cout] round trip through
 // HBM and the output-transform pass, for 16x fewer (16x longer) workgroups: used where those still fill the chip.
 //
-// F16 = true ("f16x3"): the same GEMM at fp32 accuracy on the fp16 matrix cores (v_mfma_f32_32x32x16_f16, 16x the fp32 MFMA
-// rate per instruction).  Both operands arrive as TWO fp16 planes per value, x ~= hi + lo * 2^-11 with hi = fp16(x) and
-// lo = fp16((x - hi) * 2^11) (22 significant bits; written by the Winograd input transforms / at weight load), stored
-// interleaved so that a row of 32 channels is still 128 bytes: [8 x hi][8 x lo] per group of 8 channels.  The DMA, the LDS image
-// and its swizzle are therefore byte-for-byte those of the fp32 kernel; only the fragment reads (one 16-byte chunk = 8
-// channels of one plane = one MFMA operand) and the MFMAs differ.  Three products per 16-deep step,
-//   C_hh += a_hi b_hi;   C_x += a_hi b_lo + a_lo b_hi;   C = C_hh + 2^-11 C_x        (a_lo b_lo ~ 2^-22 is dropped),
-// i.e. 16/3 = 5.3x the fp32 MFMA rate; fp16 products are exact in the fp32 accumulator, so the error is the fp32 accumulation's
-// (measured: mean error of a K = 1,152 GEMM 3.40e-7 of mean|C| against 3.38e-7 for an fp32 sgemm).  The scaled lo plane is a
-// normal fp16 whenever hi is, so no operand scaling is needed for |x| in [6e-5, 65504]; smaller values lose nothing that matters
-// (absolute error floor 1.5e-11); a larger one is never clamped: it turns into an infinity and sets the handle's range word
-// (kernels.h: split_f16x3 / range_report), which the caller answers by re-running on the exact-fp32 path.
+// F16 = true ("f16x3", DESIGN 4.0 / 4.0f): the same GEMM at fp32 accuracy on the fp16 matrix cores (v_mfma_f32_32x32x16_f16, 16x the fp32 MFMA
+// rate per instruction).  Both operands arrive as TWO fp16 planes per value (kernels.h: x ~= hi + lo * 2^-11; written by the Winograd input
+// transforms / at weight load), interleaved [8 x hi][8 x lo] per 8 channels, so a row of 32 channels is still 128 bytes: the DMA, the LDS image
+// and its swizzle are byte-for-byte those of the fp32 kernel; only the fragment reads (f16x3_read_frags: one 16-byte piece = 8 channels of one
+// plane = one MFMA operand) and the MFMAs (f16x3_step: three products per 16-deep step, 16/3 = 5.3x the fp32 MFMA rate; f16x3_close) differ.
+// The error is the fp32 accumulation's; a value beyond the fp16 range is never clamped but reported (kernels.h: split_f16x3 / range_report).
 //
 // NWM = waves along M (2: 256 threads, 4: 512 threads = two waves per SIMD); NSTG = LDS operand buffers.  NSTG = 3 is the f16x3
 // GEMMs' pipeline: their 32-channel step is 24 MFMAs of 32 cycles per wave instead of 32 of 64, too short to cover the latency
@@ -89,7 +68,6 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   constexpr int IA = TM / RPI / NW;  // DMA instructions per wave for the A tile
   constexpr int IB = TN / RPI / NW;  // ... for the B tile
   static_assert(NSTG == 2 || NSTG == 3, "two or three operand buffers");
-  constexpr int SWZ_DIV = 64 / BK;   // rows per 256-byte bank window
   constexpr int BUF = (TM + TN) * BK;  // floats per LDS buffer
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
     const int mc = mv[j] ? m : 0;
     my[j] = mc / a.Ws;
     mx[j] = mc - my[j] * a.Ws;
-    achunk[j] = (lpos ^ ((r / SWZ_DIV) % CPR)) * 4;   // source chunk (floats) for this LDS slot
+    achunk[j] = chunk_slot(r, lpos, BK) * 4;   // source chunk (floats) for this LDS slot
   }
   unsigned boff[IB];    // byte offset of this lane's B source inside a [Cout][BK] slab
 #pragma unroll
@@ -156,14 +134,13 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
     const int r = (wave * IB + j) * RPI + lrow;
     int n = n0 + r;
     n = n < a.Cout ? n : a.Cout - 1;                  // clamp: columns >= Cout are never stored
-    boff[j] = (unsigned)(n * BK + (lpos ^ ((r / SWZ_DIV) % CPR)) * 4) * 4u;
+    boff[j] = (unsigned)(n * BK + chunk_slot(r, lpos, BK) * 4) * 4u;
   }
   // buffer descriptors: A = this item's activation tensor (range-checked), B = this item's packed weights
   const unsigned a_bytes = (unsigned)a.Hin * (unsigned)a.Win * (unsigned)a.in_ld * 4u;     // < 2^31 (host-checked)
   const long long a_item = (long long)a.Hin * a.Win * a.in_ld;
-  __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (long long)b * a_item), 0, (int)a_bytes, 0x00020000);
-  __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.wt + (WINO ? 0LL : (long long)(a.wt_bdiv > 1 ? b / a.wt_bdiv : b) * a.wt_bstride)), 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t rsrc_a = raw_buffer(a.in + (long long)b * a_item, a_bytes);
+  __amdgpu_buffer_rsrc_t rsrc_b = raw_buffer(a.wt + (WINO ? 0LL : (long long)(a.wt_bdiv > 1 ? b / a.wt_bdiv : b) * a.wt_bstride), 0x7fffffffu);
 
   unsigned aoff[IA];    // per-lane byte offset of the current tap's source row chunk (>= a_bytes: reads zeros)
   unsigned wtap_bytes = 0;
@@ -207,7 +184,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   int since_flush = 0;
 
   // fragment read offsets (floats): row R, 16-byte chunk (2s+hh) ^ swz(R); swz only depends on the lane
-  const int sw = (l32 / SWZ_DIV) % CPR;
+  const int sw = chunk_swz(l32, BK);
   const int a_row = (wm * WM + l32) * BK;
   const int b_row = TM * BK + (wn * (32 * NB) + l32) * BK;
 
@@ -227,8 +204,8 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   // is in flight while the previous frequency's last chunk is multiplied), so a K = Cin of 128 does not drain the pipeline
   // 16 times per workgroup.
   auto setup_freq = [&](int f) {
-    rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + ((long long)f * a.B + b) * a_item), 0, (int)a_bytes, 0x00020000);
-    rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)(a.wt + (long long)f * a.wt_bstride), 0, 0x7fffffff, 0x00020000);
+    rsrc_a = raw_buffer(a.in + ((long long)f * a.B + b) * a_item, a_bytes);
+    rsrc_b = raw_buffer(a.wt + (long long)f * a.wt_bstride, 0x7fffffffu);
   };
   // a frequency whose K = Cin fits one accumulation chain never touches `total`; F16: `acc` is C_hh and `total` is C_x
   const bool two_level = !F16 && (!WINO || nchunk > kFlushSteps);
@@ -245,7 +222,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < NB; ++j)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { acc[i][j][r] = __builtin_fmaf(total[i][j][r], 0x1p-11f, acc[i][j][r]); total[i][j][r] = 0.f; }
+          for (int r = 0; r < 16; ++r) { acc[i][j][r] = f16x3_close(acc[i][j][r], total[i][j][r]); total[i][j][r] = 0.f; }
     }
     if (two_level) {
 #pragma unroll
@@ -304,23 +281,13 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
   float amax = 0.f;                       // ASPLIT: largest magnitude this wave split (range report after the loop)
   auto load_frags = [&](f32x4* fa, f32x4* fb, const float* base, int s_) {
     if (F16) {
-      // chunk (2 * kgroup + plane) of the row; lane half hh supplies channels 8 * (2 s + hh) .. + 7 of the chunk's 32
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int co = ((((2 * s_ + hh) << 1) + p) ^ sw) * 4;
-        if (!ASPLIT) {
-#pragma unroll
-          for (int i = 0; i < MB; ++i) fa[i * 2 + p] = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + co);
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) fb[nb * 2 + p] = *reinterpret_cast<const f32x4*>(base + b_row + nb * 32 * BK + co);
-      }
+      f16x3_read_frags<ASPLIT ? 0 : MB, NB>(fa, fb, base + a_row, base + b_row, s_, hh, sw);
       if (ASPLIT) {
         // fp32 row: the same 8 channels are two 16-byte chunks of 4 floats; split them here
 #pragma unroll
         for (int i = 0; i < MB; ++i) {
-          const f32x4 v0 = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + ((((2 * s_ + hh) << 1)) ^ sw) * 4);
-          const f32x4 v1 = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + ((((2 * s_ + hh) << 1) + 1) ^ sw) * 4);
+          const f32x4 v0 = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + (f16x3_piece(s_, hh, 0) ^ sw) * 4);
+          const f32x4 v1 = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + (f16x3_piece(s_, hh, 1) ^ sw) * 4);
           half8 hi, lo;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
@@ -403,15 +370,8 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       for (int i = 0; i < MB; ++i)
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-          const half8 ah = __builtin_bit_cast(half8, fa[i * 2]), al = __builtin_bit_cast(half8, fa[i * 2 + 1]);
-          const half8 bh = __builtin_bit_cast(half8, fb[j * 2]), bl = __builtin_bit_cast(half8, fb[j * 2 + 1]);
           const int s0 = phase * (SLOTS / 2) + (i * NB + j) * 3;
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i][j], 0, 0, 0);
-          dma_slot(s0);
-          total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, total[i][j], 0, 0, 0);
-          dma_slot(s0 + 1);
-          total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, total[i][j], 0, 0, 0);
-          dma_slot(s0 + 2);
+          f16x3_step(acc[i][j], total[i][j], fa[i * 2], fa[i * 2 + 1], fb[j * 2], fb[j * 2 + 1], [&](int m) { dma_slot(s0 + m); });
         }
       return;
     }
@@ -557,14 +517,14 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       for (int j = 0; j < NB; ++j) {
         if (F16) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_fmaf(total[i][j][r], 0x1p-11f, acc[i][j][r]);
+          for (int r = 0; r < 16; ++r) acc[i][j][r] = f16x3_close(acc[i][j][r], total[i][j][r]);
         } else {
           acc[i][j] += total[i][j];
         }
       }
   }
 
-  // ---- epilogue: C/D layout of the 32x32 block: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) ----
+  // ---- epilogue: C/D layout of the 32x32 block: col = lane & 31, row = mfma32_row(reg, lane >> 5) ----
   const bool dense = (a.ostep == 1 && a_oy0 == 0 && a_ox0 == 0 && a.Hs == a.Hout && a.Ws == a.Wout);
   const float alpha = a.alpha ? *a.alpha : 1.f;
   float* out_b = a.out + (long long)b * a.Hout * a.Wout * a.out_ld;
@@ -582,7 +542,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * WM + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int m = m0 + wm * WM + mb * 32 + mfma32_row(r, hh);
         if (m < Ms) {
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb) {
@@ -593,10 +553,9 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       }
     return;
   }
-  // Each 32x32 accumulator block (column on the lane, rows in registers) is turned around through a private LDS patch
-  // so that a lane owns 4 consecutive channels of one pixel: 16-byte stores / residual loads, 8 pixel rows x 128 bytes per
-  // wave instruction, 4x fewer memory instructions than the native layout (the epilogue was half the time of the K=128
-  // 1x1 convolutions and 11 % of the level-0 3x3s).
+  // Each 32x32 accumulator block is turned round (turn_round, f16x3_tile.h) so that a lane owns 4 consecutive channels of one
+  // pixel: 16-byte stores / residual loads, 4x fewer memory instructions than the native layout (the epilogue was half the time of
+  // the K=128 1x1 convolutions and 11 % of the level-0 3x3s).
   __syncthreads();                                   // every wave is done with the operand buffers
   if constexpr (!WINO && MB == 1 && NB == 2) {
     if (a.attn_part_ctx && n0 >= a.attn_q_cols) {
@@ -615,7 +574,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const bool ok = mrow0 + mb * 32 + (r & 3) + 8 * (r >> 2) < Ms;
+          const bool ok = mrow0 + mb * 32 + mfma32_row(r, 0) < Ms;
           kmax = fmaxf(kmax, ok ? acc[mb][0][r] : -INFINITY);
         }
       kmax = fmaxf(kmax, __shfl_xor(kmax, 32));
@@ -630,7 +589,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const bool ok = mrow0 + mb * 32 + (r & 3) + 8 * (r >> 2) < Ms;
+          const bool ok = mrow0 + mb * 32 + mfma32_row(r, 0) < Ms;
           const float p = ok ? expf(acc[mb][0][r] - mcol) : 0.f;
           const float v = ok ? acc[mb][1][r] : 0.f;
           ssum += p;
@@ -640,7 +599,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       if (wm == 1) {
         if (hh == 0) xs[wn * 32 + l32] = ssum;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) xc[wn * 1024 + ((r & 3) + 8 * (r >> 2) + 4 * hh) * 32 + l32] = ctx[r];
+        for (int r = 0; r < 16; ++r) xc[wn * 1024 + mfma32_row(r, hh) * 32 + l32] = ctx[r];
       }
       __syncthreads();
       if (wm == 0) {
@@ -648,7 +607,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
         float* pc = a.attn_part_ctx + (blk * kHeads + h) * (kDimHead * kDimHead);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int d = (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int d = mfma32_row(r, hh);
           pc[d * kDimHead + l32] = ctx[r] + xc[wn * 1024 + d * 32 + l32];
         }
         if (hh == 0) {
@@ -659,9 +618,10 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
       return;
     }
   }
-  float* tr = smem + wave * (32 * 36);               // 32 rows x (32 + 4 pad) floats per wave
+  float* tr = smem + wave * kTurnFloats;
+  float* tr_w = tr + turn_write_at(0, lane);          // this lane's column in its half's first row; register r is mfma32_row(r, 0) rows further
   const bool need_xy = !dense || om_b != nullptr;
-  const int trow = lane >> 3, tc4 = (lane & 7) * 4;  // read-back role: row trow + 8k, channels tc4..tc4+3
+  const int tc4 = turn_read_col(lane);               // read-back role: channels tc4..tc4+3 of four rows
   // WINO with an odd image height / width: the last tile row / column has output positions outside the image
   const bool edge = WINO && (((a.Hout | a.Wout) & 1) != 0);
   // bias of this wave's two 32-column blocks, loaded ONCE: a global load inside the block loop would make every block wait
@@ -688,13 +648,13 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const int ncol = n0 + wn * (32 * NB) + nb * 32;
+      // (own loops over the shared patch indices, not turn_round: under its functors every instantiation grew ~40 instructions per block)
       {   // GroupNorm sums in the native layout (this lane's column, its 16 rows)
         const int n = ncol + l32;
         const float bv = bias_col[nb];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int dr = (r & 3) + 8 * (r >> 2) + 4 * hh;
-          const int m = m_base + dr;
+          const int m = m_base + mfma32_row(r, hh);
           const float v = A[mb][nb][r] + bv;
           bool ok = m < Ms && n < a.Cout;
           if (edge) {
@@ -702,16 +662,16 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
             ok = ok && (oy0 + 2 * yy < a.Hout) && (ox0 + 2 * xx < a.Wout);
           }
           if (ok) { gsum[nb] += (stat_t)v; gsq[nb] += (stat_t)(v * v); }
-          tr[dr * 36 + l32] = A[mb][nb][r];
+          tr_w[mfma32_row(r, 0) * kTurnLd] = A[mb][nb][r];
         }
       }
       const int n = ncol + tc4;
       const f32x4 b4 = bias_quad[nb];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const int dr = trow + 8 * k;
+        const int dr = turn_read_row(k, lane);
         const int m = m_base + dr;
-        f32x4 v = *reinterpret_cast<const f32x4*>(tr + dr * 36 + tc4);
+        f32x4 v = *reinterpret_cast<const f32x4*>(tr + dr * kTurnLd + tc4);
         if (m < Ms && n < a.Cout) {
           int yy = yb, xx = xb + dr;
           if (need_xy) while (xx >= a.Ws) { xx -= a.Ws; ++yy; }
@@ -725,8 +685,7 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
           if (add_b) v += *reinterpret_cast<const f32x4*>(add_b + pix * a.add_ld + n);
           if (om_b) v *= om_b[ox * a.omask_step];
           if (a.out_split) {
-            typedef _Float16 half4o __attribute__((ext_vector_type(4)));
-            half4o hi, lo;
+            half4 hi, lo;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               us_half h_, l_;
@@ -735,8 +694,8 @@ __global__ __launch_bounds__(NWM * 128, 2) void conv_igemm_kernel(ConvArgs a) {
               lo[q] = l_;
             }
             _Float16* oh = reinterpret_cast<_Float16*>(out_b + pix * a.out_ld) + 2 * (n & ~7) + (n & 7);
-            *reinterpret_cast<half4o*>(oh) = hi;
-            *reinterpret_cast<half4o*>(oh + 8) = lo;
+            *reinterpret_cast<half4*>(oh) = hi;
+            *reinterpret_cast<half4*>(oh + 8) = lo;
           } else {
             *reinterpret_cast<f32x4*>(out_b + pix * a.out_ld + n) = v;
           }
@@ -848,18 +807,12 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs a) {
   }
 }
 
-// Winograd-domain GEMMs with short K (256), streamed: M_f [rows][N] = V_f [rows][K] * U_f, both operands in the two-plane fp16 form, M in
-// fp32.  The general loop above runs these at half the rate the chip streams at: eight steps of K = 256 are a prologue and an epilogue as long
-// as the loop, with a barrier and six LDS-DMA pieces per wave for every 12 MFMAs.  Here a workgroup of 8 waves (one per CU, two per SIMD) owns one
-// frequency, one group of 256 output columns and a contiguous range of 32-row tiles.  Wave w keeps the B fragments of columns 32 w .. 32 w + 31 for
-// the WHOLE of K in registers (K / 16 steps x 2 planes x 16 bytes per lane: 128 VGPRs at K = 256), loaded once, straight from the
-// [K/32][N][32] pack (a lane's 8 channels of one plane are one 16-byte piece there).  Only the A tiles (32 rows x K * 4 bytes) go through LDS, NBUF
-// buffers deep, with ONE counted vmcnt wait and ONE barrier per row tile: K / 64 DMA pieces per wave for 3 K / 16 MFMAs.
-// LDS image of a tile: 16-byte slot (row, c) sits at row * K/4 + (c ^ (row & 15)); K/4 is a multiple of 16, so the 16 rows of a ds_read_b128 lane
-// group ({0-3,12-15,20-27} / {4-11,16-19,28-31}: all 16 residues of row & 15) hit the 16 distinct slots of the 256-byte bank window.  The swizzle is
-// applied on the source side of the DMA (the image must be lane-linear) and again by the reads.
-// Summation order per output element is the general kernel's (ascending 16-deep steps, acc = hi hi, total = hi lo + lo hi, one final fma, same
-// lane-half convention), so M is bit-identical to conv_igemm_kernel<32, 64, false, true>'s.
+// Winograd-domain GEMMs with short K (256), streamed: M_f [rows][N] = V_f [rows][K] * U_f, both operands in the two-plane fp16 form,
+// M in fp32.  A workgroup of 8 waves (one per CU, two per SIMD) owns one frequency, one group of 256 output columns and a contiguous range of
+// 32-row tiles.  Wave w keeps the B fragments of columns 32 w .. 32 w + 31 for the WHOLE of K in registers (128 VGPRs at K = 256), loaded once,
+// straight from the [K/32][N][32] pack.  Only the A tiles go through LDS (the stream image of f16x3_tile.h), NBUF buffers deep, with ONE counted
+// vmcnt wait and ONE barrier per row tile: K / 64 DMA pieces per wave for 3 K / 16 MFMAs.  Products and close are f16x3_step / f16x3_close, as
+// in every f16x3 kernel, so M is bit-identical to conv_igemm_kernel<32, 64, false, true>'s.
 // vmcnt: loads, LDS-DMA and stores retire in issue order.  Every iteration issues exactly K/64 pieces (rows or tiles beyond the tensor read zeros
 // through the descriptor) and 4 buffer stores (rows beyond the tensor are dropped by the descriptor), so the count behind tile j's pieces is known.
 template <int K, int NBUF>
@@ -902,9 +855,8 @@ __global__ __launch_bounds__(512) void wino_stream_kernel(ConvArgs a, int rows, 
   // ---- A tiles: DMA source bookkeeping (this lane feeds slot 64 * (wave * P + j) + lane of the image) ----
   const unsigned a_bytes = (unsigned)rows * (unsigned)(K * 4);              // < 2^31 (host-checked)
   const unsigned o_bytes = (unsigned)rows * (unsigned)a.Cout * 4u;          // < 2^31 (host-checked)
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (long long)f * rows * K), 0, (int)a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_o =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (long long)f * rows * a.Cout), 0, (int)o_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = raw_buffer(a.in + (long long)f * rows * K, a_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_o = raw_buffer(a.out + (long long)f * rows * a.Cout, o_bytes);
   int arow[P];
   unsigned aoff[P];
 #pragma unroll
@@ -912,7 +864,7 @@ __global__ __launch_bounds__(512) void wino_stream_kernel(ConvArgs a, int rows, 
     const int slot = (wave * P + j) * 64 + lane;
     const int r = slot / CPRK, pos = slot % CPRK;
     arow[j] = r;
-    aoff[j] = (unsigned)r * (unsigned)(K * 4) + (unsigned)((pos ^ (r & 15)) * 16);
+    aoff[j] = (unsigned)r * (unsigned)(K * 4) + (unsigned)(stream_slot(r, pos) * 16);
   }
   // the whole offset travels in the per-lane register: that is the one the descriptor's range check sees
   auto dma_piece = [&](int tile, int buf, int j) {
@@ -921,11 +873,9 @@ __global__ __launch_bounds__(512) void wino_stream_kernel(ConvArgs a, int rows, 
     blds16(rsrc_a, off, 0u, smem + buf * TILE_F + (wave * P + j) * 256);
   };
 
-  // fragment reads: row l32, slot 4 s + 2 hh + p
-  const int xr = l32 & 15;
+  const int xr = stream_swz(l32);
   const int a_row = l32 * K;
-  float* tr = smem + NBUF * TILE_F + wave * (32 * 36);     // per-wave turn-round patch, 32 rows x (32 + 4 pad) floats
-  const int trow = lane >> 3, tc4 = (lane & 7) * 4;
+  float* tr = smem + NBUF * TILE_F + wave * kTurnFloats;   // per-wave turn-round patch
 
 #pragma unroll
   for (int i = 0; i < NBUF - 1; ++i)
@@ -949,44 +899,35 @@ __global__ __launch_bounds__(512) void wino_stream_kernel(ConvArgs a, int rows, 
     f32x4 fa[2][2];
     auto load_frags = [&](f32x4* fr, int s) {
 #pragma unroll
-      for (int p = 0; p < 2; ++p) fr[p] = *reinterpret_cast<const f32x4*>(base + ((4 * s + 2 * hh + p) ^ xr) * 4);
+      for (int p = 0; p < 2; ++p) fr[p] = *reinterpret_cast<const f32x4*>(base + (f16x3_piece(s, hh, p) ^ xr) * 4);
       __builtin_amdgcn_sched_barrier(0);
     };
     load_frags(fa[0], 0);
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
       if (s + 1 < NSTEP) load_frags(fa[(s + 1) & 1], s + 1);
-      const half8 ah = __builtin_bit_cast(half8, fa[s & 1][0]), al = __builtin_bit_cast(half8, fa[s & 1][1]);
-      const half8 bh = __builtin_bit_cast(half8, bf[s][0]), bl = __builtin_bit_cast(half8, bf[s][1]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-      if (s % PSTRIDE == 0) {         // the next tile's pieces go out under executing MFMAs, not in a burst
-        __builtin_amdgcn_sched_barrier(0);
-        dma_piece(t + NBUF - 1, nbuf, s / PSTRIDE);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      total = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, total, 0, 0, 0);
-      total = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, total, 0, 0, 0);
+      f16x3_step(acc, total, fa[s & 1][0], fa[s & 1][1], bf[s][0], bf[s][1], [&](int m) {
+        if (m == 0 && s % PSTRIDE == 0) {         // the next tile's pieces go out under executing MFMAs, not in a burst
+          __builtin_amdgcn_sched_barrier(0);
+          dma_piece(t + NBUF - 1, nbuf, s / PSTRIDE);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      });
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = __builtin_fmaf(total[r], 0x1p-11f, acc[r]);
-    // C/D layout of the 32x32 block: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); turned round so that a lane stores 16 bytes
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * hh) * 36 + l32] = acc[r];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int dr = trow + 8 * k;
+    for (int r = 0; r < 16; ++r) acc[r] = f16x3_close(acc[r], total[r]);
+    turn_round(tr, lane, [&](int r) { return acc[r]; }, [&](int dr, int tc4, f32x4 v) {
       const int m = t * 32 + dr;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(tr + dr * 36 + tc4);
       const unsigned off = m < rows ? ((unsigned)m * (unsigned)a.Cout + (unsigned)(ncol + tc4)) * 4u : o_bytes;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_o, (int)off, 0, 0);
-    }
+    });
     cur = cur == NBUF - 1 ? 0 : cur + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the zero-filled pieces of the tiles beyond t_hi are still landing in this workgroup's LDS
 }
 
 template <int K, int NBUF>
-static constexpr int stream_lds_bytes() { return (NBUF * 32 * K + 8 * 32 * 36) * (int)sizeof(float); }
+static constexpr int stream_lds_bytes() { return NBUF * 32 * K * (int)sizeof(float) + turn_bytes(8); }
 
 // Does a launch qualify for wino_stream_kernel?  A function of K, N and the form only (the sizes below merely keep 32-bit offsets in range).
 static bool wino_stream_route(const ConvArgs& a) {
@@ -1012,17 +953,14 @@ static hipError_t launch_wino_stream(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// Winograd-domain GEMMs with long K (>= 512), persistent: M_f [rows][N] = V_f [rows][K] * U_f, both operands in the two-plane fp16 form, M dense in
-// fp32.  The general loop runs these as rounds of short-lived workgroups (K / 32 = 16 ... 64 steps each): every workgroup fills its pipeline cold, and
-// the workgroups of a round end together, so their store burst runs while no matrix pipe has work.  Here a bounded grid of workgroups (one per CU,
-// 8 waves as 4 (M) x 2 (N), 512 threads) walks its share of the work items (frequency, row tile, column tile; column tile fastest) back to
-// back, and the three-buffer chunk rotation does NOT restart per item: chunk g of the workgroup's whole sequence lives in buffer g % 3, and at step g
-// the pieces of chunk g + 2 are issued -- during the last two steps of item t those are the first two chunks of item t + 1 -- so item t's epilogue
-// (acc + 2^-11 total, a per-wave LDS patch outside the operand buffers, 16-byte row stores) runs with the next item's loads in flight and its stores
-// drain under the next item's MFMAs.  No state is shared between workgroups.
+// Winograd-domain GEMMs with long K (>= 512), persistent: M_f [rows][N] = V_f [rows][K] * U_f, both operands in the two-plane fp16
+// form, M dense in fp32.  A bounded grid of workgroups (one per CU, 8 waves as 4 (M) x 2 (N)) walks its share of the work items (frequency, row
+// tile, column tile; column tile fastest) back to back, and the three-buffer chunk rotation does NOT restart per item: chunk g of the
+// workgroup's whole sequence lives in buffer g % 3 and at step g the pieces of chunk g + 2 are issued, so item t's epilogue (close, turn-round
+// through a per-wave patch outside the operand buffers, 16-byte row stores) runs with the next item's loads in flight.  No shared state.
 // Tile: TM = 4 WM rows x TN = 64 NB columns (WM = 64, NB = 1: 256 x 64, the form the general launcher picks for K >= 1024; WM = 32, NB = 2: 128 x 128).
-// Same bits as conv_igemm_kernel<32, .., false, true, ..>: ascending 32-channel chunks, two 16-deep steps each, acc = hi hi, total = hi lo then lo hi,
-// one final fma, the same MFMA and lane-half convention, the same LDS image and swizzle.
+// Same bits as conv_igemm_kernel<32, .., false, true, ..>: ascending 32-channel chunks, two 16-deep steps each, f16x3_step and f16x3_close, the
+// same chunk image (f16x3_tile.h).
 // vmcnt: loads, LDS-DMA and stores retire in issue order.  Every step issues exactly P = IA + IB pieces and every item exactly NST = 4 MB NB stores (a
 // row beyond the tensor, and every piece of the item after the workgroup's last, gets an offset beyond its descriptor: the load returns zeros, the
 // store is dropped).  Issue order around the start of item t >= 1 (n = K / 32):
@@ -1074,19 +1012,19 @@ __global__ __launch_bounds__(512) void wino_persist_kernel(ConvArgs a, int rows,
     const int itc = ok ? it : it_lo;
     const int f = itc / (mt * nt), rem = itc - f * (mt * nt);
     const int rt = rem / nt, ct = rem - rt * nt;
-    rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (long long)f * rows * K), 0, (int)a_bytes, 0x00020000);
-    rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void*)(a.wt + (long long)f * a.wt_bstride), 0, (int)b_bytes, 0x00020000);
+    rsrc_a = raw_buffer(a.in + (long long)f * rows * K, a_bytes);
+    rsrc_b = raw_buffer(a.wt + (long long)f * a.wt_bstride, b_bytes);
 #pragma unroll
     for (int j = 0; j < IA; ++j) {
       const int r = (wave * IA + j) * 8 + lrow;
       const int m = rt * TM + r;
-      aoff[j] = (ok && m < rows) ? (unsigned)m * (unsigned)(K * 4) + (unsigned)((lpos ^ ((r >> 1) & 7)) * 16) : a_bytes;
+      aoff[j] = (ok && m < rows) ? (unsigned)m * (unsigned)(K * 4) + (unsigned)(chunk_slot(r, lpos) * 16) : a_bytes;
     }
 #pragma unroll
     for (int j = 0; j < IB; ++j) {
       const int r = (wave * IB + j) * 8 + lrow;
       const int n = ct * TN + r;             // < Cout: Cout is a multiple of TN (host-checked)
-      boff[j] = ok ? (unsigned)n * (unsigned)(BK * 4) + (unsigned)((lpos ^ ((r >> 1) & 7)) * 16) : b_bytes;
+      boff[j] = ok ? (unsigned)n * (unsigned)(BK * 4) + (unsigned)(chunk_slot(r, lpos) * 16) : b_bytes;
     }
   };
   int it_issue = it_lo, ch_issue = 0;        // the chunk the next pieces belong to
@@ -1116,19 +1054,12 @@ __global__ __launch_bounds__(512) void wino_persist_kernel(ConvArgs a, int rows,
       for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; total[i][j][r] = 0.f; }
 
   // fragment reads: row R, 16-byte chunk ((2 s + hh) * 2 + plane) ^ swz(R); swz depends on the lane only (WM is a multiple of 16)
-  const int sw = (l32 >> 1) & 7;
+  const int sw = chunk_swz(l32);
   const int a_row = (wm * WM + l32) * BK;
   const int b_row = TM * BK + (wn * (32 * NB) + l32) * BK;
   f32x4 fa0[MB * 2], fb0[NB * 2], fa1[MB * 2], fb1[NB * 2];
   auto load_frags = [&](f32x4* fa, f32x4* fb, const float* base, int s_) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int co = ((((2 * s_ + hh) << 1) + p) ^ sw) * 4;
-#pragma unroll
-      for (int i = 0; i < MB; ++i) fa[i * 2 + p] = *reinterpret_cast<const f32x4*>(base + a_row + i * 32 * BK + co);
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) fb[nb * 2 + p] = *reinterpret_cast<const f32x4*>(base + b_row + nb * 32 * BK + co);
-    }
+    f16x3_read_frags<MB, NB>(fa, fb, base + a_row, base + b_row, s_, hh, sw);
     __builtin_amdgcn_sched_barrier(0);
   };
   // phase 0 / 1: first / second half of a step's MFMAs (the piece slots); phase -1: no pieces
@@ -1137,46 +1068,34 @@ __global__ __launch_bounds__(512) void wino_persist_kernel(ConvArgs a, int rows,
     for (int i = 0; i < MB; ++i)
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
-        const half8 ah = __builtin_bit_cast(half8, fa[i * 2]), al = __builtin_bit_cast(half8, fa[i * 2 + 1]);
-        const half8 bh = __builtin_bit_cast(half8, fb[j * 2]), bl = __builtin_bit_cast(half8, fb[j * 2 + 1]);
         const int s0 = phase * (SLOTS / 2) + (i * NB + j) * 3;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i][j], 0, 0, 0);
-        if (phase >= 0 && s0 % PSTRIDE == 0 && s0 / PSTRIDE < P) dma_piece(s0 / PSTRIDE);
-        total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, total[i][j], 0, 0, 0);
-        if (phase >= 0 && (s0 + 1) % PSTRIDE == 0 && (s0 + 1) / PSTRIDE < P) dma_piece((s0 + 1) / PSTRIDE);
-        total[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, total[i][j], 0, 0, 0);
-        if (phase >= 0 && (s0 + 2) % PSTRIDE == 0 && (s0 + 2) / PSTRIDE < P) dma_piece((s0 + 2) / PSTRIDE);
+        f16x3_step(acc[i][j], total[i][j], fa[i * 2], fa[i * 2 + 1], fb[j * 2], fb[j * 2 + 1], [&](int m) {
+          if (phase >= 0 && (s0 + m) % PSTRIDE == 0 && (s0 + m) / PSTRIDE < P) dma_piece((s0 + m) / PSTRIDE);
+        });
       }
   };
-  // item `it` is complete in acc / total: store it and clear the accumulators.  C/D layout of a 32x32 block: col = lane & 31,
-  // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); turned round through the wave's patch so that a lane stores 16 bytes
-  float* tr = smem + 3 * BUF + wave * (32 * 36);
-  const int trow = lane >> 3, tc4 = (lane & 7) * 4;
+  // item `it` is complete in acc / total: close it, store it through the wave's patch (outside the operand buffers) and clear the accumulators
+  float* tr = smem + 3 * BUF + wave * kTurnFloats;
   auto store_item = [&](int it) {
     const int f = it / (mt * nt), rem = it - f * (mt * nt);
     const int rt = rem / nt, ct = rem - rt * nt;
-    const __amdgpu_buffer_rsrc_t rsrc_o =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (long long)f * rows * a.Cout), 0, (int)o_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_o = raw_buffer(a.out + (long long)f * rows * a.Cout, o_bytes);
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const int m_base = rt * TM + wm * WM + mb * 32, ncol = ct * TN + wn * (32 * NB) + nb * 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          tr[((r & 3) + 8 * (r >> 2) + 4 * hh) * 36 + l32] = __builtin_fmaf(total[mb][nb][r], 0x1p-11f, acc[mb][nb][r]);
+        turn_round(tr, lane, [&](int r) {
+          const float v = f16x3_close(acc[mb][nb][r], total[mb][nb][r]);
           acc[mb][nb][r] = 0.f;
           total[mb][nb][r] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int dr = trow + 8 * k;
+          return v;
+        }, [&](int dr, int tc4, f32x4 v) {
           const int m = m_base + dr;
-          f32x4 v = *reinterpret_cast<const f32x4*>(tr + dr * 36 + tc4);
           v = v + f32x4{0.f, 0.f, 0.f, 0.f};      // the general epilogue adds its (absent) bias: a -0 becomes +0 there, so it does here
           const unsigned off = m < rows ? ((unsigned)m * (unsigned)a.Cout + (unsigned)(ncol + tc4)) * 4u : o_bytes;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc_o, (int)off, 0, 0);
-        }
+        });
       }
   };
 
@@ -1217,7 +1136,7 @@ __global__ __launch_bounds__(512) void wino_persist_kernel(ConvArgs a, int rows,
 }
 
 template <int WM, int NB>
-static constexpr int persist_lds_bytes() { return (3 * (4 * WM + 64 * NB) * 32 + 8 * 32 * 36) * (int)sizeof(float); }
+static constexpr int persist_lds_bytes() { return 3 * (4 * WM + 64 * NB) * 32 * (int)sizeof(float) + turn_bytes(8); }
 
 // Does a launch qualify for wino_persist_kernel?  A function of K, N and the form only (the sizes below merely keep 32-bit offsets in range).
 static bool wino_persist_route(const ConvArgs& a) {

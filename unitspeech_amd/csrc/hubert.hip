@@ -296,7 +296,6 @@ __global__ __launch_bounds__(256) void wl_table_kernel(const float* __restrict__
 // BIAS (WavLM): the score gets + gate[q] * table[head][clamp(key - q, -D, D) + D] before the masking and the running maximum.  The 127
 // differences a 64 x 64 tile can hold are staged per key tile in two more rows of Ks; the gate is one register per lane.
 constexpr int kAtQ = 64, kAtK = 64, kAtKs = 80, kAtVs = 68;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int DT, bool BIAS>
 __device__ __forceinline__ void hb_attn_body(const float* __restrict__ qkv, float* __restrict__ out, HbLens lens, int level, int H, int d,

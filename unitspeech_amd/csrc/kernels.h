@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mfma_layout.h"
 
 namespace us {
 
@@ -24,10 +25,25 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
 #pragma clang fp contract(off)
   return a - b;
 }
-// The accumulator of a v_mfma_f32_32x32x2_f32 and its D layout: register r of a lane holds column lane & 31 and row mfma32_row(r,
-// lane >> 5), ascending in r.
+// The accumulator of a 32x32 MFMA (row layout: mfma32_row, mfma_layout.h) and the vectors the kernels move, defined here and nowhere else.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ int mfma32_row(int r, int kl) { return 8 * (r >> 2) + 4 * kl + (r & 3); }
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+// Raw buffer descriptor over `bytes` bytes at p (wave-uniform): a lane whose byte offset is >= bytes reads zeros and its store is dropped (the
+// kernels' zero padding and row guards).  kRawBufferFlags, the fourth word: DATA_FORMAT = 32-bit (bit 17), no stride, swizzle or index.
+constexpr int kRawBufferFlags = 0x00020000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_buffer(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, kRawBufferFlags);
+}
+// One wave-wide LDS-DMA piece: 64 lanes x 16 bytes, lane l lands at lds_dst + 16*l.  `buffer_load_dwordx4 ... offen lds` (descriptor + 32-bit
+// per-lane byte offset + scalar offset), not `global_load_lds_dwordx4` (64-bit per-lane address): in the conv kernel's own skeleton
+// (tools/conv_bench) 6 pieces per 32 MFMAs cost 15 % of the MFMA rate as global_load_lds and nothing as buffer loads.
+__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff_bytes, unsigned soff_bytes, float* lds_dst_wave_uniform) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst_wave_uniform, 16, (int)voff_bytes,
+                                           (int)soff_bytes, 0, 0);
+}
 // one value per lane -> the whole wave's sum / maximum in every lane, by a fixed butterfly (the same bits in every run)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -7,7 +7,6 @@
 
 namespace us {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // f16x3 range word of the handle whose entry point runs on this host thread (kernels.h)
 static thread_local unsigned* t_range_flag = nullptr;
@@ -208,7 +207,6 @@ hipError_t launch_gn_stats(const float* y, int ld, int B, int n, int C, double* 
 // GroupNorm apply + Mish + mask (+ time-embedding addend) (+ masked residual)
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
-  typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
   // A thread owns one channel quad for its whole life (C/4 divides 256 or is a multiple of it for every width of the
   // U-Net), so the per-channel scale/shift are folded once: z = y*sc + sh with sc = rstd*gamma, sh = beta - mean*sc.
   const int b = blockIdx.y;
@@ -289,7 +287,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
     if (a.post_mask) o *= m;
     if (a.out_split || o2b) {
       // hi = fp16(x), lo = fp16((x - hi) * 2^11); a value beyond the fp16 range is reported, not clamped (kernels.h)
-      half4_t hi, lo;
+      half4 hi, lo;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         us_half h, l;
@@ -303,8 +301,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
         if (a.store16) {      // lanes 2k, 2k + 1 hold quads c, c + 4 of pixel p (i has the lane's parity, C / 4 is even: launcher)
           store_split_pair16(oh, hi, lo);
         } else {
-          *reinterpret_cast<half4_t*>(oh) = hi;
-          *reinterpret_cast<half4_t*>(oh + 8) = lo;
+          *reinterpret_cast<half4*>(oh) = hi;
+          *reinterpret_cast<half4*>(oh + 8) = lo;
         }
       };
       if (a.out_split) store_planes(ob + p * a.out_ld);
@@ -554,7 +552,6 @@ hipError_t launch_scale_table(const CopyEnt* tab_dev, int n_entries, const float
 
 // 16-byte stores, four per thread: the weight-gradient scratch of a 1024-channel layer is 38 MB per zero-fill
 __global__ __launch_bounds__(256) void fill4_kernel(float* __restrict__ dst, float value, int n) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   const f32x4 v = {value, value, value, value};
   const int q = n >> 2;
   f32x4* d4 = reinterpret_cast<f32x4*>(dst);

@@ -7,11 +7,12 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/unitspeech_hip.h"
+#include "kernels.h"
 
 namespace {
 
 constexpr int kChunk = 4096;      // elements per block (16 per thread)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using us::f32x4;
 
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* const* __restrict__ g, const int64_t* __restrict__ numel,
                                                     const int32_t* __restrict__ blk_tensor, const int64_t* __restrict__ blk_off,

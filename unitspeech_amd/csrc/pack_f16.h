@@ -7,9 +7,6 @@
 
 namespace us {
 
-typedef _Float16 pk_half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pk_half4 __attribute__((ext_vector_type(4)));
-
 // One channel quad of a two-plane tensor (per 8 channels: 8 hi | 8 lo) written with ONE 16-byte store instead of two 8-byte ones.
 // Lanes 2k and 2k + 1 hold quads c (c % 8 == 0) and c + 4 of the same pixel / tile: the even lane hands its lo quad to the odd lane and
 // takes that lane's hi quad (a DPP quad_perm [1,0,3,2] move of two dwords), then stores hi[c..c+7] at the 8-group's base while the odd
@@ -17,19 +14,19 @@ typedef _Float16 pk_half4 __attribute__((ext_vector_type(4)));
 // instruction covers 1 KB of whole lines instead of 2 KB in 16-byte pieces at a 32-byte stride.
 // p: where THIS lane's hi quad goes (8-group base + 0 for the even, + 4 halves for the odd lane).  Preconditions (host-checked by every
 // launcher that selects this path): C % 8 == 0; the quad's parity (c / 4) & 1 equals the lane's; both lanes of a pair are active together.
-__device__ __forceinline__ void store_split_pair16(_Float16* p, pk_half4 hi, pk_half4 lo) {
+__device__ __forceinline__ void store_split_pair16(_Float16* p, half4 hi, half4 lo) {
   typedef int pk_int2 __attribute__((ext_vector_type(2)));
   const bool odd = (threadIdx.x & 1) != 0;
   const pk_int2 send = __builtin_bit_cast(pk_int2, odd ? hi : lo);
   pk_int2 got;
   got[0] = __builtin_amdgcn_mov_dpp(send[0], 0xB1, 0xF, 0xF, true);        // 0xB1: quad_perm [1,0,3,2]
   got[1] = __builtin_amdgcn_mov_dpp(send[1], 0xB1, 0xF, 0xF, true);
-  const pk_half4 other = __builtin_bit_cast(pk_half4, got);
-  const pk_half4 first = odd ? other : hi, second = odd ? lo : other;
-  pk_half8 v;
+  const half4 other = __builtin_bit_cast(half4, got);
+  const half4 first = odd ? other : hi, second = odd ? lo : other;
+  half8 v;
 #pragma unroll
   for (int k = 0; k < 4; ++k) { v[k] = first[k]; v[4 + k] = second[k]; }
-  *reinterpret_cast<pk_half8*>(p + (odd ? 4 : 0)) = v;
+  *reinterpret_cast<half8*>(p + (odd ? 4 : 0)) = v;
 }
 
 // U as two interleaved fp16 planes, dst (halves) [f][K/32][N][4 groups x (8 hi | 8 lo)], K = Cin, N = Cout (forward) or K = Cout,
@@ -45,7 +42,7 @@ __device__ __forceinline__ void wino_pack_f16_body(const float* __restrict__ src
     const long long rn = i >> 2;                            // (k / 32) * N + n
     const int n = (int)(rn % N), kc = (int)(rn / N);
     const int k0 = kc * 32 + g4 * 8;
-    pk_half8 hi[16], lo[16];
+    half8 hi[16], lo[16];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
       const int k = k0 + kk;
@@ -77,8 +74,8 @@ __device__ __forceinline__ void wino_pack_f16_body(const float* __restrict__ src
     _Float16* d = dst + (rn * 32 + g4 * 8) * 2;
 #pragma unroll
     for (int f = 0; f < 16; ++f) {
-      *reinterpret_cast<pk_half8*>(d + f * fstride) = hi[f];
-      *reinterpret_cast<pk_half8*>(d + f * fstride + 8) = lo[f];
+      *reinterpret_cast<half8*>(d + f * fstride) = hi[f];
+      *reinterpret_cast<half8*>(d + f * fstride + 8) = lo[f];
     }
   }
 }
@@ -103,7 +100,7 @@ __device__ __forceinline__ void conv_pack_f16_body(const float* __restrict__ src
     const int ch = (int)(t % nchunk);
     const int tap = (int)(t / nchunk);
     const int ky = tap / KW, kx = tap % KW;
-    pk_half8 hi, lo;
+    half8 hi, lo;
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
       const int ci = ch * 32 + g4 * 8 + kk;
@@ -114,8 +111,8 @@ __device__ __forceinline__ void conv_pack_f16_body(const float* __restrict__ src
       lo[kk] = l;
     }
     _Float16* d = dst + i * 16;
-    *reinterpret_cast<pk_half8*>(d) = hi;
-    *reinterpret_cast<pk_half8*>(d + 8) = lo;
+    *reinterpret_cast<half8*>(d) = hi;
+    *reinterpret_cast<half8*>(d + 8) = lo;
   }
 }
 

@@ -6,10 +6,9 @@
 // (reduction over pixels, both operands pixel-major so MFMA fragments are plain coalesced row loads), GroupNorm+Mish
 // backward, the linear-attention backward pieces, column sums (bias gradients) and the small dense layers.
 #include "kernels.h"
+#include "f16x3_tile.h"
 
 namespace us {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // d/dz [ z * tanh(softplus(z)) ]  (softplus threshold 20 as in the forward)
 // v_exp_f32 / v_rcp_f32 forms (about 1 ulp each), as mish_f of the forward (ops.hip): with the library expf and two IEEE divisions the
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            int row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh, col = j * 32 + l32;
+            int row = i * 32 + mfma32_row(r, hh), col = j * 32 + l32;
             if (w == 0) red[row * 64 + col] = acc[i][j][r];
             else red[row * 64 + col] += acc[i][j][r];
           }
@@ -125,9 +124,6 @@ __device__ __forceinline__ WgIdx wgrad_index() {
 }
 
 constexpr int kWgKP = 32;
-__device__ __forceinline__ void wg_blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff_bytes, float* lds_dst_wave_uniform) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst_wave_uniform, 16, (int)voff_bytes, 0, 0, 0);
-}
 
 __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float wsm[];      // 2 stages x (A [32][128] + B [32][128])
@@ -151,9 +147,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(WgradArgs a) {
   const unsigned gy_bytes = (unsigned)a.Hout * (unsigned)a.Wout * (unsigned)a.gy_ld * 4u;
   const unsigned x_bytes = (unsigned)a.Hin * (unsigned)a.Win * (unsigned)a.x_ld * 4u;
   const __amdgpu_buffer_rsrc_t rsrc_g =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.gy + (long long)b * a.Hout * a.Wout * a.gy_ld), 0, (int)gy_bytes, 0x00020000);
+      raw_buffer(a.gy + (long long)b * a.Hout * a.Wout * a.gy_ld, gy_bytes);
   const __amdgpu_buffer_rsrc_t rsrc_x =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + (long long)b * a.Hin * a.Win * a.x_ld), 0, (int)x_bytes, 0x00020000);
+      raw_buffer(a.x + (long long)b * a.Hin * a.Win * a.x_ld, x_bytes);
 
   // this lane's DMA role: instruction j of this wave covers stage rows wave*8 + 2j + (lane>>5), channels (lane&31)*4..+3
   const int lrow = lane >> 5, lch = (lane & 31) * 4;
@@ -172,8 +168,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(WgradArgs a) {
         if ((unsigned)iy < (unsigned)a.Hin && (unsigned)ix < (unsigned)a.Win)
           xoff = ((unsigned)(iy * a.Win + ix) * (unsigned)a.x_ld + (unsigned)(ci0 + lch)) * 4u;
       }
-      wg_blds16(rsrc_g, goff, As + r * 128);
-      wg_blds16(rsrc_x, xoff, Bs + r * 128);
+      blds16(rsrc_g, goff, 0u, As + r * 128);
+      blds16(rsrc_x, xoff, 0u, Bs + r * 128);
     }
   };
 
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(WgradArgs a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int co = co0 + wm * 64 + i * 32 + mfma32_row(0, hh) + mfma32_row(r, 0);      // the lane half's first row, register r further down
         const int ci = ci0 + wn * 64 + j * 32 + l32;
         float* dst = gw + (long long)co * a.Cin + ci;
         if (single) *dst = a.overwrite ? acc[i][j][r] : *dst + acc[i][j][r];
@@ -228,9 +224,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(WgradArgs a) {
 // ONCE into the fragment image (per channel 64 bytes: hi plane of the 16 pixels, lo plane; 16-byte chunks XOR-swizzled by
 // (channel >> 2) & 3 so that both the converting writes and the fragment reads spread over the banks) and every wave reads its
 // fragments from there with ds_read_b128: each value is split once per workgroup, not once per wave that uses it.
-// The gradient operand is scaled by an exact, per-launch power of two (below).  hi = fp16(v), lo = fp16((v - hi) * 2^11);
-// C = C_hh + 2^-11 C_x as in conv_igemm.hip.
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+// The gradient operand is scaled by an exact, per-launch power of two (below).  hi = fp16(v), lo = fp16((v - hi) * 2^11); products
+// and close are f16x3_step / f16x3_close (f16x3_tile.h), as in conv_igemm.hip.
 constexpr int kWgKP16 = 16;
 
 template <bool CARRIED>
@@ -264,9 +259,9 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
   const unsigned gy_bytes = vmode ? gy_item * (unsigned)a.B : gy_item;      // vmode: one descriptor over all items (< 2^31 bytes, host-checked)
   const unsigned x_bytes = vmode ? x_item * (unsigned)a.B : x_item;
   const float* gy_b = a.gy + (long long)b * a.Hout * a.Wout * a.gy_ld;
-  const __amdgpu_buffer_rsrc_t rsrc_g = __builtin_amdgcn_make_buffer_rsrc((void*)gy_b, 0, (int)gy_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_g = raw_buffer(gy_b, gy_bytes);
   const __amdgpu_buffer_rsrc_t rsrc_x =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + (long long)b * a.Hin * a.Win * a.x_ld), 0, (int)x_bytes, 0x00020000);
+      raw_buffer(a.x + (long long)b * a.Hin * a.Win * a.x_ld, x_bytes);
 
   // ---- scale of the gradient operand.  Gradients are small (a mean-reduced loss puts dL/dy around 1e-5, below fp16's normal range), so
   // gy is multiplied by the power of two that brings the largest magnitude of the WHOLE tensor (a.gy_amax, taken exactly by
@@ -331,8 +326,8 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
             xoff = (unsigned)bi * x_item + ((unsigned)(iy * a.Win + ix) * (unsigned)a.x_ld + (unsigned)(ci0 + lch)) * 4u;
         }
       }
-      wg_blds16(rsrc_g, goff, As + r * 128);
-      wg_blds16(rsrc_x, xoff, Bs + r * 128);
+      blds16(rsrc_g, goff, 0u, As + r * 128);
+      blds16(rsrc_x, xoff, 0u, Bs + r * 128);
     }
   };
   // conversion role: unit u = (operand, channel, pixel octet); thread t takes (operand 0, channel t & 127, octet t >> 7) and the same
@@ -344,7 +339,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
     for (int op = 0; op < 2; ++op) {
       const float* src = wsm + buf * RAW + op * (kWgKP16 * 128) + (cv_o * 8) * 128 + cv_c;
       const float sc = op == 0 ? g_scale : 1.f;
-      half8_t hi, lo;
+      half8 hi, lo;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         // no clamp: the scaled gradient cannot leave the fp16 range (exact maximum above); an ACTIVATION beyond it becomes an infinity
@@ -355,8 +350,8 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
         lo[k] = (_Float16)((v - (float)h) * 2048.f);
       }
       float* row = cimg + (op * 128 + cv_c) * 16;
-      *reinterpret_cast<half8_t*>(row + ((cv_o ^ cv_sw) << 2)) = hi;
-      *reinterpret_cast<half8_t*>(row + (((2 + cv_o) ^ cv_sw) << 2)) = lo;
+      *reinterpret_cast<half8*>(row + ((cv_o ^ cv_sw) << 2)) = hi;
+      *reinterpret_cast<half8*>(row + (((2 + cv_o) ^ cv_sw) << 2)) = lo;
     }
   };
 
@@ -380,26 +375,22 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
     convert(st & 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    half8_t ah[2], al[2], bh[2], bl[2];
+    half8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int ca = wm * 64 + i * 32 + l32, cb = wn * 64 + i * 32 + l32;
       const float* ra = cimg + ca * 16;
       const float* rb = cimg + (128 + cb) * 16;
       const int sa = (ca >> 2) & 3, sb = (cb >> 2) & 3;
-      ah[i] = *reinterpret_cast<const half8_t*>(ra + ((hh ^ sa) << 2));
-      al[i] = *reinterpret_cast<const half8_t*>(ra + (((2 + hh) ^ sa) << 2));
-      bh[i] = *reinterpret_cast<const half8_t*>(rb + ((hh ^ sb) << 2));
-      bl[i] = *reinterpret_cast<const half8_t*>(rb + (((2 + hh) ^ sb) << 2));
+      ah[i] = *reinterpret_cast<const half8*>(ra + ((hh ^ sa) << 2));
+      al[i] = *reinterpret_cast<const half8*>(ra + (((2 + hh) ^ sa) << 2));
+      bh[i] = *reinterpret_cast<const half8*>(rb + ((hh ^ sb) << 2));
+      bl[i] = *reinterpret_cast<const half8*>(rb + (((2 + hh) ^ sb) << 2));
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], accx[i][j], 0, 0, 0);
-        accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], accx[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < 2; ++j) f16x3_step(acc[i][j], accx[i][j], ah[i], al[i], bh[j], bl[j]);
   }
   float* gw = a.gw + (long long)b * a.gw_bstride + (long long)wt_i * a.Cout * a.Cin;
   const bool single = vmode ? gridDim.x == 1 : (chunks_per_item == 1 && (a.B == 1 || a.gw_bstride != 0));    // the only writer of these elements
@@ -409,10 +400,10 @@ __global__ __launch_bounds__(256, 3) void wgrad_f16_kernel(WgradArgs a) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = co0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int co = co0 + wm * 64 + i * 32 + mfma32_row(0, hh) + mfma32_row(r, 0);      // the lane half's first row, register r further down
         const int ci = ci0 + wn * 64 + j * 32 + l32;
         float* dst = gw + (long long)co * a.Cin + ci;
-        const float v = __builtin_fmaf(accx[i][j][r], 0x1p-11f, acc[i][j][r]) * g_unscale;
+        const float v = f16x3_close(acc[i][j][r], accx[i][j][r]) * g_unscale;
         if (single) *dst = a.overwrite ? v : *dst + v;
         else atomicAdd(dst, v);
       }
@@ -883,7 +874,7 @@ __global__ __launch_bounds__(256) void attn_bwd_gctx_kernel(const float* __restr
   float* out = gctx + ((long long)b * kHeads + h) * (kDimHead * kDimHead);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    int d = (r & 3) + 8 * (r >> 2) + 4 * hh;
+    int d = mfma32_row(r, hh);
     atomicAdd(&out[d * kDimHead + c], acc[r]);
   }
 }

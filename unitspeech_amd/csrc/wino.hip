@@ -9,15 +9,12 @@
 
 namespace us {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---- f16x3 storage of V (conv_igemm_kernel<.., F16 = true>) -----------------------------------------------------------------
 // SPLIT = true: every value is kept as two fp16 planes, v ~= hi + lo * 2^-11 with hi = fp16(v), lo = fp16((v - hi) * 2^11), interleaved
 // per group of 8 channels as [8 x hi][8 x lo] so that a pixel row keeps its fp32 byte length (C * 4).  `idx` is the fp32 element
 // index of a channel quad (c % 4 == 0): its hi quad sits at half index 2 * (idx - idx % 8) + idx % 8, its lo quad 8 halves further.
 // A Winograd-domain value beyond the fp16 range (|v| >= 65520; V = B^T d B reaches 4x the activation) is reported through `over`
 // (kernels.h: split_f16x3), never clamped; the GEMM's fp32 accumulation carries the same error as an fp32 GEMM.
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split_f16(const f32x4& v, half4& hi, half4& lo, bool& over) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {

@@ -18,9 +18,6 @@
 
 namespace us {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half4w __attribute__((ext_vector_type(4)));
-
 namespace {
 
 template <int M> struct Coef;
@@ -106,7 +103,7 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
   const unsigned per_item = (unsigned)th * tw * C4;
   const long long plane_h = 2LL * B * th * tw * C;             // halves per frequency
   const unsigned item_bytes = (unsigned)H * W * x_ld * 4u;     // < 2^31 (host-checked)
-  __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (long long)b * H * W * x_ld), 0, (int)item_bytes, 0x00020000);
+  __amdgpu_buffer_rsrc_t rx = raw_buffer(x + (long long)b * H * W * x_ld, item_bytes);
   const float* mb = GN ? g.mask + (long long)(b % g.mask_bmod) * g.mask_ld : nullptr;
   const int cg = C / kGroups;
   _Float16* vb = reinterpret_cast<_Float16*>(V) + 2LL * (long long)b * th * tw * C;
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
       Bt<MH>::apply(col, vv);
 #pragma unroll
       for (int ii = 0; ii < NH; ++ii) {
-        half4w hi, lo;
+        half4 hi, lo;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float xv = vv[ii][k];
@@ -193,8 +190,8 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
           store_split_pair16(pf + ho, hi, lo);       // (per frequency, in front of its store: nothing stays live across frequencies)
           __builtin_amdgcn_sched_barrier(0);
         } else {
-          *reinterpret_cast<half4w*>(pf + ho) = hi;
-          *reinterpret_cast<half4w*>(pf + ho + 8) = lo;
+          *reinterpret_cast<half4*>(pf + ho) = hi;
+          *reinterpret_cast<half4*>(pf + ho + 8) = lo;
         }
       }
     }
@@ -332,7 +329,7 @@ __global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict
     for (int fi = 0; fi < NH; ++fi)
 #pragma unroll
       for (int fj = 0; fj < NW; ++fj) {
-        pk_half8 hi, lo;
+        half8 hi, lo;
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk) {
           double u = 0.0;
@@ -348,8 +345,8 @@ __global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict
           hi[kk] = h;
           lo[kk] = l;
         }
-        *reinterpret_cast<pk_half8*>(d + (long long)(fi * NW + fj) * fstride) = hi;
-        *reinterpret_cast<pk_half8*>(d + (long long)(fi * NW + fj) * fstride + 8) = lo;
+        *reinterpret_cast<half8*>(d + (long long)(fi * NW + fj) * fstride) = hi;
+        *reinterpret_cast<half8*>(d + (long long)(fi * NW + fj) * fstride + 8) = lo;
       }
   }
   range_report(range_flag, over, kRangeWeight);
