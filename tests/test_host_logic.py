@@ -264,3 +264,59 @@ def test_the_three_handle_modules_share_one_base():
         with pytest.raises(RuntimeError, match=f"the HIP {m._what} needs tensors on a ROCm device"):
             m.eval()._sync(torch.device("cpu"))
 
+
+
+@pytest.mark.parametrize("lengths", [[3, 5, 7], np.array([3, 5, 7], dtype=np.int64), torch.tensor([3, 5, 7], dtype=torch.int32),
+                                     torch.tensor([[3], [5], [7]])], ids=["list", "np_int64", "int32_tensor", "Bx1_tensor"])
+def test_host_lengths_takes_lists_arrays_and_tensors_of_any_shape(lengths):
+    import ctypes
+    from unitspeech_amd._args import c_lengths, host_lengths
+    for strict in (False, True):
+        v = host_lengths(lengths, 3, "X.forward", integers_only=strict)
+        assert v == [3, 5, 7] and all(type(n) is int for n in v)
+    assert list(c_lengths(v)) == [3, 5, 7] and c_lengths(v)._type_ is ctypes.c_int64
+    assert host_lengths(None, 3, "X.forward") is None and c_lengths(None) is None
+
+
+def test_host_lengths_refuses_a_wrong_count_both_ways():
+    from unitspeech_amd._args import host_lengths
+    with pytest.raises(ValueError) as e:
+        host_lengths([3, 5], 3, "X.forward")
+    assert str(e.value) == "X.forward: 2 lengths for 3 items (item 2 has none)"
+    with pytest.raises(ValueError) as e:
+        host_lengths(torch.tensor([3, 5, 7, 9]), 3, "X.forward")
+    assert str(e.value) == "X.forward: 4 lengths for 3 items"
+
+
+def test_host_lengths_integers_only_is_the_vocoders_refusal():
+    from unitspeech_amd._args import host_lengths
+    with pytest.raises(ValueError) as e:
+        host_lengths(torch.tensor([3.0, 5.5]), 2, "BigVGAN.forward", integers_only=True)
+    assert str(e.value) == "BigVGAN.forward: lengths must be integers, got dtype torch.float32"
+    with pytest.raises(ValueError) as e:
+        host_lengths([3, True], 2, "BigVGAN.forward", integers_only=True)
+    assert str(e.value) == "BigVGAN.forward: lengths must be integers, item 1 has True"
+    with pytest.raises(ValueError) as e:
+        host_lengths([2.0, 3], 2, "BigVGAN.forward", integers_only=True)
+    assert str(e.value) == "BigVGAN.forward: lengths must be integers, item 0 has 2.0"
+    assert host_lengths(torch.tensor([3.0, 5.5]), 2, "Resample") == [3, 5]          # without the flag: int(), as every other wrapper had it
+
+
+def test_device_lengths_of_none_is_none():
+    from unitspeech_amd._args import device_lengths
+    assert device_lengths(None, 3, torch.device("cpu"), "X") is None
+
+
+@pytest.mark.parametrize("name", ["HubertModel", "WavLMModel"])
+def test_waveform_encoders_refuse_training_mode_under_their_own_name(name):
+    from unitspeech_amd._wav_encoder import _WaveformEncoder
+    from unitspeech_amd.hubert import HubertModel
+    from unitspeech_amd.wavlm import WavLMModel
+    cls = {"HubertModel": HubertModel, "WavLMModel": WavLMModel}[name]
+    m = cls(hidden_size=8, num_hidden_layers=1, num_attention_heads=2, intermediate_size=16, conv_dim=(4, 4), conv_kernel=(4, 2),
+            conv_stride=(2, 2), num_conv_pos_embeddings=4, num_conv_pos_embedding_groups=2, num_buckets=8)
+    assert type(m)._precondition is _WaveformEncoder._precondition and not issubclass(WavLMModel, HubertModel)
+    m.eval()._precondition()
+    with pytest.raises(RuntimeError) as e:
+        m.train()._precondition()
+    assert str(e.value) == f"{name} is inference-only (dropout, time masking and the backward pass are not built): call .eval()"

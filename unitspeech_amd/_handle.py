@@ -1,6 +1,7 @@
 """`HandleModule`: a torch module whose arithmetic lives behind one opaque handle of the HIP library that takes its weights by
 state_dict key (csrc/handle.h: us_frontend, us_vocoder, us_speaker, us_mel, us_resample, us_hubert, us_wavlm).  It owns the handle, pushes the weights whose storage or version
-changed since the last call, and keeps the caller-owned workspace."""
+changed since the last call, keeps the caller-owned workspace, and makes the library calls of a forward (`_call`: the handle's device
+current, the return code checked under the symbol's name).  Per-item lengths reach those calls through `_args`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -96,6 +97,12 @@ class HandleModule(torch.nn.Module):
             self._ws = None
             self._ws = ws = torch.empty(n, dtype=torch.uint8, device=device)
         return ws
+
+    def _call(self, lib, device, name, *args):
+        """us_{_abi}_{name}(*args) with `device` current; a refusal is raised under the symbol's full name."""
+        with torch.cuda.device(device):
+            rc = self._fn(lib, name)(*args)
+        self._check(lib, rc, f"us_{self._abi}_{name}")
 
     def _check(self, lib, rc, what):
         if rc != _lib.US_OK:

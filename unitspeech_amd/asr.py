@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import device_lengths, host_lengths, i64 as _i64, need_gpu as _need_gpu, stream as _stream
 from .hubert import _BASE, HubertModel
 
 __all__ = ["CTCHead", "HubertForCTC", "Wav2Vec2ForCTC", "load_ctc_checkpoint", "CTCVocabulary", "normalize_text", "edit_distance",
@@ -31,39 +32,17 @@ MAX_V, MAX_H, MAX_TOKENS = 2048, 1024, 4096
 MAX_TARGET = 1024                 # tokens per target of ctc_loss / forced_align
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _need_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: the tensor is on {t.device}; the recogniser runs on the GPU only (there is no CPU fallback)")
-
-
-def _i64(t, dev):
-    return torch.as_tensor(t).detach().to(device=dev, dtype=torch.int64).contiguous()
-
-
-def _lengths(lengths, B, dev, what):
-    if lengths is None:
-        return None
-    lens = _i64(lengths, dev)
-    if lens.shape != (B,):
-        raise ValueError(f"{what}: lengths {tuple(lens.shape)} must hold {B} values")
-    return lens
-
-
 @torch.no_grad()
 def ctc_collapse(ids, lengths=None, blank: int = 0, first_frame: bool = False):
     """ids [B, Tmax] int64 with lengths [B] (frames; None: all) -> (tokens [B, Tmax], n [B]) and, when asked, first_frame [B, Tmax]:
     equal neighbours merged, then `blank` dropped; zero beyond n[b]."""
-    _need_gpu(ids, "ctc_collapse")
+    _need_gpu(ids, "ctc_collapse", "the recogniser")
     dev = ids.device
     u = _i64(ids, dev)
     if u.dim() != 2 or u.numel() == 0:
         raise ValueError(f"ctc_collapse: ids must be a non-empty [B, Tmax], got {tuple(u.shape)}")
     B, T = u.shape
-    lens = _lengths(lengths, B, dev, "ctc_collapse")
+    lens = device_lengths(lengths, B, dev, "ctc_collapse")
     tokens = torch.empty(B, T, dtype=torch.int64, device=dev)
     ff = torch.empty(B, T, dtype=torch.int64, device=dev) if first_frame else None
     n = torch.empty(B, dtype=torch.int64, device=dev)
@@ -113,14 +92,14 @@ class CTCHead(torch.nn.Module):
 
     @torch.no_grad()
     def _run(self, features, frame_lengths, log_probs, ids):
-        _need_gpu(features, "CTCHead")
+        _need_gpu(features, "CTCHead", "the recogniser")
         V, H = self.weight.shape
         if features.dim() != 3 or features.shape[-1] != H or features.numel() == 0:
             raise ValueError(f"CTCHead: features must be a non-empty [B, F, {H}], got {tuple(features.shape)}")
         dev = features.device
         x = features.detach().to(torch.float32).contiguous()
         B, F = x.shape[:2]
-        lens = _lengths(frame_lengths, B, dev, "CTCHead")
+        lens = device_lengths(frame_lengths, B, dev, "CTCHead")
         logits = torch.empty(B, F, V, device=dev)
         lp = torch.empty(B, F, V, device=dev) if log_probs else None
         out_ids = torch.empty(B, F, dtype=torch.int64, device=dev) if ids else None
@@ -186,7 +165,7 @@ class _HeadFn(torch.autograd.Function):
 
 def _sequences(what, x, targets, frame_lengths, target_lengths):
     """The checked device arguments of a loss / alignment call: x [B, T, V] fp32, targets [B, Lmax] int64 and the two length vectors."""
-    _need_gpu(x, what)
+    _need_gpu(x, what, "the recogniser")
     if x.dim() != 3 or x.numel() == 0:
         raise ValueError(f"{what}: expected a non-empty [B, T, V], got {tuple(x.shape)}")
     dev = x.device
@@ -196,7 +175,8 @@ def _sequences(what, x, targets, frame_lengths, target_lengths):
         raise ValueError(f"{what}: targets {tuple(tg.shape)} must be [{B}, Lmax]")
     if target_lengths is None:
         raise ValueError(f"{what}: target_lengths is needed")
-    return x.detach().to(torch.float32).contiguous(), tg, _lengths(frame_lengths, B, dev, what), _lengths(target_lengths, B, dev, what)
+    return (x.detach().to(torch.float32).contiguous(), tg, device_lengths(frame_lengths, B, dev, what),
+            device_lengths(target_lengths, B, dev, what))
 
 
 def _ctc_loss_call(x, tg, fl, tl, blank, zero_infinity, stage=_lib.US_CTC_WHOLE, grad_out=None, ws=None, with_grad=False):
@@ -326,9 +306,9 @@ class _EncoderForCTC(torch.nn.Module):
         return self.lm_head.load_state_dict(head, strict=strict, **kw)
 
     def _frames(self, wav, lengths):
-        if lengths is None:
+        v = host_lengths(lengths, wav.shape[0], type(self).__name__)
+        if v is None:
             return None, None
-        v = [int(i) for i in (lengths.reshape(-1).tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
         return v, torch.tensor([self.encoder.frames(n) for n in v], dtype=torch.int64).to(wav.device, non_blocking=True)
 
     @torch.no_grad()
@@ -459,13 +439,13 @@ def edit_distance(hyp, ref, n_hyp, n_ref):
     """hyp [P, Lh], ref [P, Lr] int64 with n_hyp, n_ref [P] valid tokens, on the device -> the Levenshtein distance (unit costs) of each
     pair, [P] int64 on the device, exact.  At most 4096 tokens per sequence.  Substitution / deletion / insertion counts are not given:
     they depend on which optimal alignment is taken."""
-    _need_gpu(hyp, "edit_distance")
+    _need_gpu(hyp, "edit_distance", "the recogniser")
     dev = hyp.device
     a, b = _i64(hyp, dev), _i64(ref, dev)
     if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
         raise ValueError(f"edit_distance: hyp and ref must be [P, Lh] and [P, Lr], got {tuple(a.shape)} and {tuple(b.shape)}")
     P = int(a.shape[0])
-    na, nb = _lengths(n_hyp, P, dev, "edit_distance"), _lengths(n_ref, P, dev, "edit_distance")
+    na, nb = device_lengths(n_hyp, P, dev, "edit_distance"), device_lengths(n_ref, P, dev, "edit_distance")
     if na is None or nb is None:
         raise ValueError("edit_distance: n_hyp and n_ref are needed")
     dist = torch.empty(P, dtype=torch.int64, device=dev)

@@ -8,33 +8,17 @@ arithmetic is `csrc/hubert.hip`; there is no CPU fallback and no training.
 """
 from __future__ import annotations
 
-import ctypes as C
-import re
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import _lib
-from ._handle import HandleModule
+from ._wav_encoder import _WaveformEncoder, rename_fairseq
 
 _BASE = dict(conv_dim=(512,) * 7, conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), hidden_size=768, num_attention_heads=12,
              intermediate_size=3072, num_hidden_layers=12, num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16, layer_norm_eps=1e-5)
-_POS = "encoder.pos_conv_embed.conv."
 
 
-def _set(root, key, tensor):
-    """Register `tensor` as a parameter under the dotted `key`, making plain container modules on the way."""
-    *path, leaf = key.split(".")
-    m = root
-    for p in path:
-        if p not in m._modules:
-            m.add_module(p, torch.nn.Module())
-        m = m._modules[p]
-    m.register_parameter(leaf, torch.nn.Parameter(tensor, requires_grad=False))
-
-
-class HubertModel(HandleModule):
+class HubertModel(_WaveformEncoder):
     """`forward(wav [B, T], lengths=None, output_layer=None, output_hidden_states=False)` -> [B, F, H] on wav's device.
 
     The constructor takes the fields of transformers' `HubertConfig` by keyword (others, such as the dropouts, are accepted and unused in
@@ -42,155 +26,34 @@ class HubertModel(HandleModule):
     samples alone (not HF's attention_mask behaviour), rows past its frames are 0.  `output_layer` n stops after n layers (HF's
     `hidden_states[n]`, fairseq's `output_layer`); with `output_hidden_states` the result is `(out, hidden_states [B, n + 1, F, H])`."""
     _abi, _what = "hubert", "HuBERT encoder"
-    _cache_sources = True
+    _ignored_prefixes = ("final_proj.",)           # HubertModelWithFinalProj's head
 
     def __init__(self, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, conv_dim=_BASE["conv_dim"],
                  conv_stride=_BASE["conv_stride"], conv_kernel=_BASE["conv_kernel"], num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16,
                  layer_norm_eps=1e-5, feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False, feat_proj_layer_norm=True,
                  hidden_act="gelu", feat_extract_activation="gelu", mask_time_prob=0.05, mask_feature_prob=0.0, **unused):
-        super().__init__()
         if feat_extract_norm != "group":
             raise ValueError("HubertModel: only the group-norm feature extractor (feat_extract_norm='group') is built")
         if do_stable_layer_norm:
             raise ValueError("HubertModel: the pre-LN encoder (do_stable_layer_norm=True) is not built")
         if conv_bias or not feat_proj_layer_norm or hidden_act != "gelu" or feat_extract_activation != "gelu":
             raise ValueError("HubertModel: conv_bias=False, feat_proj_layer_norm=True and GELU activations are what is built")
-        if not (len(conv_dim) == len(conv_kernel) == len(conv_stride)) or not 1 <= len(conv_dim) <= _lib.US_HUBERT_MAX_CONV:
-            raise ValueError(f"HubertModel: conv_dim, conv_kernel and conv_stride need the same length, at most {_lib.US_HUBERT_MAX_CONV}")
-        self.config = dict(conv_dim=[int(v) for v in conv_dim], conv_kernel=[int(v) for v in conv_kernel], conv_stride=[int(v) for v in conv_stride],
-                           hidden_size=int(hidden_size), num_attention_heads=int(num_attention_heads), intermediate_size=int(intermediate_size),
-                           num_hidden_layers=int(num_hidden_layers), num_conv_pos_embeddings=int(num_conv_pos_embeddings),
-                           num_conv_pos_embedding_groups=int(num_conv_pos_embedding_groups), layer_norm_eps=float(layer_norm_eps))
-        c = self.config
-        H, I = c["hidden_size"], c["intermediate_size"]
-        if H % c["num_attention_heads"] or H % c["num_conv_pos_embedding_groups"]:
-            raise ValueError("HubertModel: hidden_size must be divisible by the heads and by the positional convolution's groups")
-
-        def affine(p, n):
-            _set(self, p + ".weight", torch.ones(n))
-            _set(self, p + ".bias", torch.zeros(n))
-
-        def linear(p, o, i):
-            _set(self, p + ".weight", torch.zeros(o, i))
-            _set(self, p + ".bias", torch.zeros(o))
-
-        if mask_time_prob > 0.0 or mask_feature_prob > 0.0:             # HF registers it under this condition; unused in eval
-            _set(self, "masked_spec_embed", torch.zeros(H))
-        cin = 1
-        for i, (ch, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
-            _set(self, f"feature_extractor.conv_layers.{i}.conv.weight", torch.zeros(ch, cin, k))
-            if i == 0:
-                affine("feature_extractor.conv_layers.0.layer_norm", ch)
-            cin = ch
-        affine("feature_projection.layer_norm", cin)
-        linear("feature_projection.projection", H, cin)
-        kp, g = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
-        _set(self, _POS + "bias", torch.zeros(H))
-        _set(self, _POS + "parametrizations.weight.original0", torch.ones(1, 1, kp))
-        _set(self, _POS + "parametrizations.weight.original1", torch.ones(H, H // g, kp))
-        affine("encoder.layer_norm", H)
-        for i in range(c["num_hidden_layers"]):
-            p = f"encoder.layers.{i}."
-            for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-                linear(p + "attention." + n, H, H)
-            affine(p + "layer_norm", H)
-            linear(p + "feed_forward.intermediate_dense", I, H)
-            linear(p + "feed_forward.output_dense", H, I)
-            affine(p + "final_layer_norm", H)
+        super().__init__(dict(conv_dim=conv_dim, conv_kernel=conv_kernel, conv_stride=conv_stride, hidden_size=hidden_size,
+                              num_attention_heads=num_attention_heads, intermediate_size=intermediate_size, num_hidden_layers=num_hidden_layers,
+                              num_conv_pos_embeddings=num_conv_pos_embeddings, num_conv_pos_embedding_groups=num_conv_pos_embedding_groups,
+                              layer_norm_eps=layer_norm_eps),
+                         masked_spec_embed=mask_time_prob > 0.0 or mask_feature_prob > 0.0)         # HF registers it under this condition
 
     @classmethod
     def base(cls, **overrides):
         """HuBERT-base: facebook/hubert-base-ls960, mHuBERT, ContentVec."""
         return cls(**dict(_BASE, **overrides))
 
-    # ---- checkpoints ---------------------------------------------------------------------------------------------------------
+    def _hidden_layout(self, B, n1, F, H):
+        return (B, n1, F, H), ()                 # us_hubert_forward: item-major, no strides
 
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        """HF's keys; also the older `...conv.weight_g` / `weight_v` spelling of the positional convolution (how content-vec-best is stored);
-        `final_proj.*` (HubertModelWithFinalProj) is ignored, and a checkpoint without `masked_spec_embed` keeps the module's."""
-        sd = OrderedDict()
-        for k, v in state_dict.items():
-            if k.startswith("final_proj."):
-                continue
-            if k == _POS + "weight_g":
-                k = _POS + "parametrizations.weight.original0"
-            elif k == _POS + "weight_v":
-                k = _POS + "parametrizations.weight.original1"
-            sd[k] = v
-        if hasattr(self, "masked_spec_embed"):
-            sd.setdefault("masked_spec_embed", self.masked_spec_embed.detach())
-        else:
-            sd.pop("masked_spec_embed", None)
-        return super().load_state_dict(sd, strict=strict, **kw)
-
-    # ---- engine ----------------------------------------------------------------------------------------------------------------
-
-    def _config_struct(self):
-        c = self.config
-        s = _lib.us_hubert_config()
-        s.n_conv = len(c["conv_dim"])
-        for i in range(s.n_conv):
-            s.conv_dim[i], s.conv_kernel[i], s.conv_stride[i] = c["conv_dim"][i], c["conv_kernel"][i], c["conv_stride"][i]
-        s.hidden_size, s.n_heads, s.intermediate_size, s.n_layers = (c["hidden_size"], c["num_attention_heads"], c["intermediate_size"],
-                                                                     c["num_hidden_layers"])
-        s.pos_conv_kernel, s.pos_conv_groups = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
-        s.feat_extract_norm, s.do_stable_layer_norm, s.layer_norm_eps = _lib.US_HUBERT_NORM_GROUP, 0, c["layer_norm_eps"]
-        return s
-
-    def _create(self, lib, device):
-        s = self._config_struct()
-        _lib.check(lib.us_hubert_create(C.byref(self._h), C.byref(s)), None, "us_hubert_create")
-
-    def _sources(self):
-        """Every parameter under its own key, except masked_spec_embed (unused in eval) and the positional convolution's weight-norm pair,
-        which goes in folded: weight = g * v / |v|, the norm over dims 0 and 1 (torch's `_weight_norm(v, g, dim=2)`)."""
-        out = OrderedDict()
-        sd = self.state_dict(keep_vars=True)
-        for k, t in sd.items():
-            if k == "masked_spec_embed" or k.startswith(_POS + "parametrizations."):
-                continue
-            out[k] = ((t,), None)
-        g, v = sd[_POS + "parametrizations.weight.original0"], sd[_POS + "parametrizations.weight.original1"]
-        out[_POS + "weight"] = ((g, v), lambda: torch._weight_norm(v.detach().float(), g.detach().float(), 2))
-        return out
-
-    def _precondition(self):
-        if self.training:
-            raise RuntimeError("HubertModel is inference-only (dropout, time masking and the backward pass are not built): call .eval()")
-
-    def frames(self, n: int) -> int:
-        """Frames of an n-sample item (0: shorter than the receptive field)."""
-        for k, s in zip(self.config["conv_kernel"], self.config["conv_stride"]):
-            n = (n - k) // s + 1 if n >= k else 0
-        return n
-
-    @torch.no_grad()
     def forward(self, wav, lengths=None, output_layer=None, output_hidden_states=False, normalize=False):
-        if wav.dim() != 2 or wav.shape[0] < 1:
-            raise ValueError(f"HubertModel: expected a waveform [B, T], got {tuple(wav.shape)}")
-        device = wav.device
-        lib, stream = self._sync(device)
-        x = wav.detach().to(dtype=torch.float32).contiguous()
-        B, T = int(x.shape[0]), int(x.shape[1])
-        L = self.config["num_hidden_layers"]
-        n = L if output_layer is None else int(output_layer)
-        lens = None
-        if lengths is not None:
-            v = [int(i) for i in (lengths.reshape(-1).tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-            if len(v) != B:
-                raise ValueError(f"HubertModel: {len(v)} lengths for {B} waveforms")
-            lens = (C.c_int64 * B)(*v)
-        F, H = self.frames(T), self.config["hidden_size"]
-        if F < 1:                                # the library's own refusal, with its message
-            self._check(lib, min(int(lib.us_hubert_frames(self._h, T)), -1), "us_hubert_frames")
-        out = torch.empty(B, F, H, device=device)
-        hs = torch.empty(B, max(n, 0) + 1, F, H, device=device) if output_hidden_states else None
-        ws = self._workspace(lib, device, B, T)
-        with torch.cuda.device(device):
-            rc = lib.us_hubert_forward(self._h, x.data_ptr(), lens, B, T, int(bool(normalize)), n, out.data_ptr(),
-                                       hs.data_ptr() if hs is not None else None, ws.data_ptr(), ws.numel(), stream)
-        self._check(lib, rc, "us_hubert_forward")
-        return (out, hs) if output_hidden_states else out
+        return self._encode(wav, lengths, output_layer, output_hidden_states, normalize)
 
 
 class HubertFeatureReader(torch.nn.Module):
@@ -249,14 +112,7 @@ def from_fairseq_state_dict(sd):
     """A fairseq HuBERT checkpoint's `model` dictionary under `HubertModel`'s (transformers') key names.  `mask_emb`, `label_embs_concat`
     and `final_proj.*` (masking and the pre-training heads, unused in eval) are dropped.  fairseq is not available where this library is
     developed: the mapping is tested on a hand-made dictionary of the right names and shapes only."""
-    out = OrderedDict()
-    for k, v in sd.items():
-        if k in ("mask_emb", "label_embs_concat") or k.startswith("final_proj."):
-            continue
-        for pat, rep in _FAIRSEQ:
-            k = re.sub(pat, rep, k)
-        out[k] = v
-    return out
+    return rename_fairseq(sd, _FAIRSEQ)
 
 
 def load_hubert_checkpoint(path, **config):

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import device_lengths, stream as _stream
 
 __all__ = ["active_speech_level", "normalize_level", "sv56"]
 
@@ -30,10 +31,6 @@ MAX_B, MAX_T = 65535, 1 << 30
 def chunk() -> int:
     """The number of samples of a chunk: an item is cut into chunks of this size from its own start."""
     return int(_lib.load().us_level_chunk())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _rows(wav, what):
@@ -59,15 +56,6 @@ def _rows(wav, what):
     if B > MAX_B or T > MAX_T:
         raise ValueError(f"{what}: at most {MAX_B} items of {MAX_T} samples, got {B} x {T}")
     return x.contiguous(), code
-
-
-def _lengths(lengths, B, dev, what):
-    if lengths is None:
-        return None
-    lens = torch.as_tensor(lengths).detach().to(device=dev, dtype=torch.int64).contiguous()
-    if lens.shape != (B,):
-        raise ValueError(f"{what}: lengths {tuple(lens.shape)} must hold {B} values")
-    return lens
 
 
 def _sample_rate(sample_rate, what):
@@ -103,7 +91,7 @@ def active_speech_level(wav, sample_rate, lengths=None):
     -> SpeechLevel(level_db [B], activity [B], rms_db [B], peak [B] in fp64, counts [B, 15] int64), all on the device.  level_db is -100
     where there is no measurable speech and NaN for an item with a non-finite sample."""
     x, code = _rows(wav, "active_speech_level")
-    lens = _lengths(lengths, x.shape[0], x.device, "active_speech_level")
+    lens = device_lengths(lengths, x.shape[0], x.device, "active_speech_level")
     stats, counts, _, _ = _measure(x, code, False, lens, _sample_rate(sample_rate, "active_speech_level"))
     return _level(stats, counts)
 
@@ -120,7 +108,7 @@ def normalize_level(wav, sample_rate, ndb: float = -26.0, lengths=None, via_int1
     x, code = _rows(wav, "normalize_level")
     B, T = x.shape
     dev = x.device
-    lens = _lengths(lengths, B, dev, "normalize_level")
+    lens = device_lengths(lengths, B, dev, "normalize_level")
     quantize = bool(via_int16) and code == _lib.US_LEVEL_F32
     stats, counts, ws, n = _measure(x, code, quantize, lens, _sample_rate(sample_rate, "normalize_level"))
     out = torch.empty(B, T, dtype=torch.int16 if out_int16 else torch.float32, device=dev)

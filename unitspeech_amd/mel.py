@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import c_lengths, host_lengths
 from ._handle import HandleModule
 
 
@@ -73,15 +74,6 @@ class MelSpectrogram(HandleModule):
         c.n_fft, c.hop, c.win, c.num_mels = self.n_fft, self.hop_size, self.win_size, self.num_mels
         _lib.check(lib.us_mel_create(C.byref(self._h), C.byref(c)), None, "us_mel_create")
 
-    @staticmethod
-    def _host_lengths(lengths, B, what):
-        if lengths is None:
-            return None
-        v = [int(x) for x in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-        if len(v) != B:
-            raise ValueError(f"{what}: {len(v)} lengths for a batch of {B}")
-        return (C.c_int64 * B)(*v)
-
     def _range(self, v, device, name):
         if not isinstance(v, torch.Tensor):
             v = torch.tensor(v, dtype=torch.float32)
@@ -102,7 +94,7 @@ class MelSpectrogram(HandleModule):
         lib, stream = self._sync(device)
         x = wav.detach().to(dtype=torch.float32).contiguous()
         B, T = int(x.shape[0]), int(x.shape[1])
-        lens = self._host_lengths(lengths, B, "MelSpectrogram")
+        lens = c_lengths(host_lengths(lengths, B, "MelSpectrogram"))
         n_norm, mn, mx = 0, None, None
         if mel_min is not None:
             mn, mx = self._range(mel_min, device, "mel_min"), self._range(mel_max, device, "mel_max")
@@ -111,10 +103,8 @@ class MelSpectrogram(HandleModule):
             n_norm = mn.numel()
         out = torch.empty(B, self.num_mels, T // self.hop_size, device=device)
         ws = self._workspace(lib, device, B, T)
-        with torch.cuda.device(device):
-            rc = lib.us_mel_forward(self._h, x.data_ptr(), lens, B, T, None if mn is None else mn.data_ptr(), None if mx is None else mx.data_ptr(),
-                                    n_norm, float(pad_value), out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        self._check(lib, rc, "us_mel_forward")
+        self._call(lib, device, "forward", self._h, x.data_ptr(), lens, B, T, None if mn is None else mn.data_ptr(),
+                   None if mx is None else mx.data_ptr(), n_norm, float(pad_value), out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         return out
 
     @torch.no_grad()
@@ -127,11 +117,9 @@ class MelSpectrogram(HandleModule):
         lib, stream = self._sync(device)
         x = mel.detach().to(dtype=torch.float32).contiguous()
         B, F = int(x.shape[0]), int(x.shape[2])
-        lens = self._host_lengths(frame_lengths, B, "MelSpectrogram.minmax")
+        lens = c_lengths(host_lengths(frame_lengths, B, "MelSpectrogram.minmax"))
         out = torch.empty(2, self.num_mels, device=device)
-        with torch.cuda.device(device):
-            rc = lib.us_mel_minmax(self._h, x.data_ptr(), lens, B, F, out.data_ptr(), stream)
-        self._check(lib, rc, "us_mel_minmax")
+        self._call(lib, device, "minmax", self._h, x.data_ptr(), lens, B, F, out.data_ptr(), stream)
         return out[0], out[1]
 
 

@@ -12,10 +12,10 @@ import ctypes as C
 import math
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._args import c_lengths, host_lengths
 from ._handle import HandleModule
 
 _KAISER_BETA = 14.769656459379492
@@ -87,17 +87,10 @@ class Resample(HandleModule):
         shape = waveform.shape
         x = waveform.detach().to(dtype=torch.float32).reshape(-1, shape[-1]).contiguous()
         B, T = int(x.shape[0]), int(x.shape[1])
-        lens = None
-        if lengths is not None:
-            v = [int(n) for n in (lengths.reshape(-1).tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-            if len(v) != B:
-                raise ValueError(f"Resample: {len(v)} lengths for {B} waveforms")
-            lens = (C.c_int64 * B)(*v)
+        lens = c_lengths(host_lengths(lengths, B, "Resample"))
         out = torch.empty(B, self.out_length(T), device=device)
         ws = self._workspace(lib, device, B, T)
-        with torch.cuda.device(device):
-            rc = lib.us_resample_forward(self._h, x.data_ptr(), lens, B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        self._check(lib, rc, "us_resample_forward")
+        self._call(lib, device, "forward", self._h, x.data_ptr(), lens, B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         return out.reshape(shape[:-1] + (out.shape[-1],))
 
 

@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._args import c_lengths, host_lengths
 from ._handle import HandleModule
 
 # number of hidden states the s3prl upstreams return (the CNN output plus one per transformer layer): the length of `feature_weight`
@@ -147,30 +148,19 @@ class ECAPA_TDNN(HandleModule):
             raise ValueError(f"ECAPA_TDNN: expected [L, B, T, C] or [B, C, T], got {tuple(x.shape)}")
         return x.detach().to(dtype=torch.float32).contiguous(), int(L), int(B), int(T)
 
-    @staticmethod
-    def _lengths(lengths, B, what):
-        """-> the B per-item lengths as Python ints (the library checks their range and names the item)."""
-        v = [int(i) for i in (lengths.reshape(-1).tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-        if len(v) != B:
-            raise ValueError(f"ECAPA_TDNN.{what}: {len(v)} lengths for {B} items" + (f" (item {len(v)} has none)" if len(v) < B else ""))
-        return v
-
     @torch.no_grad()
     def _run(self, hidden_states, normalize: bool, lengths=None, what="forward_features"):
         x, L, B, T = self._input(hidden_states)
-        if lengths is not None:
-            lengths = self._lengths(lengths, B, what)
+        lengths = host_lengths(lengths, B, "ECAPA_TDNN." + what)
         device = x.device
         lib, stream = self._sync(device)
         out = torch.empty(B, self.emb_dim, device=device)
         ws = self._workspace(lib, device, B, T)
-        with torch.cuda.device(device):
-            if lengths is None:
-                rc = lib.us_speaker_forward(self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), ws.data_ptr(), ws.numel(), stream)
-            else:
-                rc = lib.us_speaker_forward_lengths(self._h, x.data_ptr(), L, B, T, (C.c_int64 * B)(*lengths), out.data_ptr(), int(normalize),
-                                                    ws.data_ptr(), ws.numel(), stream)
-        self._check(lib, rc, "us_speaker_forward" if lengths is None else "us_speaker_forward_lengths")
+        if lengths is None:
+            self._call(lib, device, "forward", self._h, x.data_ptr(), L, B, T, out.data_ptr(), int(normalize), ws.data_ptr(), ws.numel(), stream)
+        else:
+            self._call(lib, device, "forward_lengths", self._h, x.data_ptr(), L, B, T, c_lengths(lengths), out.data_ptr(), int(normalize),
+                       ws.data_ptr(), ws.numel(), stream)
         self._last = (B, T)
         return out
 
@@ -250,9 +240,8 @@ class ECAPA_TDNN(HandleModule):
 
     def _frames(self, wav, lengths):
         """samples per item -> the upstream's frames per item (None stays None)"""
-        if lengths is None:
-            return None
-        return [self.upstream.frames(n) for n in self._lengths(lengths, wav.shape[0], "forward")]
+        v = host_lengths(lengths, wav.shape[0], "ECAPA_TDNN.forward")
+        return None if v is None else [self.upstream.frames(n) for n in v]
 
     def forward(self, x, lengths=None):
         """`ECAPA_TDNN.forward(wav)` (:248-287): wav [B, T] at 16 kHz -> [B, emb_dim].  `lengths` are samples per item: the upstream runs

@@ -17,22 +17,15 @@ import torch
 from typing import Optional, Sequence
 
 from . import _lib
+from ._args import i64 as _i64, stream as _stream
 from .unit_encoder_train import align_segment, prior_loss
 
 __all__ = ["mas_log_prior", "maximum_path", "maximum_path_lengths", "align", "duration_loss", "random_replace_tensor",
            "compute_train_step_loss"]
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _f32(t, dev):
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _i64(t, dev):
-    return t.detach().to(device=dev, dtype=torch.int64).contiguous()
 
 
 @torch.no_grad()

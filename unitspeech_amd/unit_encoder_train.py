@@ -15,12 +15,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._args import stream as _stream
 
 __all__ = ["prior_loss", "align_segment", "duration_path", "compute_train_step_loss"]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _f32(t, dev):

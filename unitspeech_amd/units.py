@@ -27,24 +27,12 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._args import i64 as _i64, need_gpu as _need_gpu, stream as _stream
 
 __all__ = ["KMeansQuantizer", "SpeechEncoder", "process_unit", "process_units_batch", "dedup_units", "lloyd_step", "kmeans_plusplus"]
 
 MAX_K, MAX_D, MAX_SPAN = 2048, 1024, 64
 MAX_ROWS = 1 << 24                         # rows of one library call; more go in as a list of chunks
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _need_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: the tensor is on {t.device}; the unit extraction runs on the GPU only (there is no CPU fallback)")
-
-
-def _i64(t, dev):
-    return torch.as_tensor(t).detach().to(device=dev, dtype=torch.int64).contiguous()
 
 
 def _workspace(lib, dev, B, Tmax, K, D, Lout):
@@ -151,7 +139,7 @@ class KMeansQuantizer(torch.nn.Module):
         return self._packed
 
     def _dense(self, dense, lengths):
-        _need_gpu(dense, "KMeansQuantizer")
+        _need_gpu(dense, "KMeansQuantizer", "the unit extraction")
         K, D = self.centers.shape
         if dense.dim() != 3 or dense.shape[-1] != D:
             raise ValueError(f"KMeansQuantizer: features must be [B, T, {D}], got {tuple(dense.shape)}")
@@ -323,7 +311,7 @@ class KMeansQuantizer(torch.nn.Module):
 def dedup_units(units, lengths=None):
     """units [B, Tmax] int64 with lengths [B] -> (units, durations [B, Tmax] int64, zero padded, n [B] int64): per item
     `torch.unique_consecutive(return_counts=True)`, without a host synchronisation."""
-    _need_gpu(units, "dedup_units")
+    _need_gpu(units, "dedup_units", "the unit extraction")
     dev = units.device
     u = _i64(units, dev)
     B, T = u.shape
@@ -349,7 +337,7 @@ def process_units_batch(units, durations, n_in, sampling_rate, hop_length, max_f
     needed when durations are given (Lin otherwise).  Returns (unit [B, Lu] int64, duration [B, Lu] int64, duration as fp32,
     unit_lengths [B] int64); entries beyond unit_lengths[b] are 0, and unit_lengths[b] is -1 for an item with more than max_frames."""
     sampling_rate, hop_length, spf = _check_rates(sampling_rate, hop_length)
-    _need_gpu(units, "process_units_batch")
+    _need_gpu(units, "process_units_batch", "the unit extraction")
     dev = units.device
     u = _i64(units, dev)
     B, Lin = u.shape
@@ -383,7 +371,7 @@ def process_unit(encoded, sampling_rate, hop_length):
     "dense" [T, D] (its T bounds the output); without it the sum of the durations is read first.  An input shorter than one hop gives
     two empty tensors (the reference raises an IndexError there)."""
     units, durations = encoded["units"], encoded["durations"]
-    _need_gpu(units, "process_unit")
+    _need_gpu(units, "process_unit", "the unit extraction")
     if units.dim() != 1 or durations.shape != units.shape:
         raise ValueError(f"process_unit: units {tuple(units.shape)} and durations {tuple(durations.shape)} must be 1-D and agree")
     dense = encoded.get("dense") if hasattr(encoded, "get") else None
@@ -427,7 +415,7 @@ def _fit_chunks(dense, lengths, K, what, D=None, need_rows=True):
         raise ValueError(f"{what}: n_clusters = {K} is larger than the {total} rows")
     out, dev = [], None
     for x, l in zip(xs, ls):
-        _need_gpu(x, what)
+        _need_gpu(x, what, "the unit extraction")
         dev = x.device if dev is None else dev
         if x.device != dev:
             raise RuntimeError(f"{what}: the chunks are on {dev} and {x.device}")

@@ -19,6 +19,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._args import stream as _stream
 from .util import fix_len_compatibility, generate_path, sequence_mask
 
 
@@ -107,10 +108,6 @@ class SinusoidalPosEmb(_Fused):
 # -------------------------------------------------------------------------------------------------
 def _dev_ptr(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(t.data_ptr())
-
-
-def _stream() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _f32c(t: torch.Tensor, device) -> torch.Tensor:

@@ -26,6 +26,7 @@ from torch import nn
 from torch.nn.utils.weight_norm import WeightNorm
 
 from . import _lib
+from ._args import c_lengths, host_lengths
 from ._handle import HandleModule
 
 # configs of the 22 kHz / 80-band BigVGAN generators (hop 256): the large one and the base one
@@ -200,27 +201,6 @@ class BigVGAN(HandleModule):
                 out[key] = ((t,), None)
         return out
 
-    @staticmethod
-    def _lengths(lengths, B, what):
-        """-> the B per-item lengths as Python ints (the library checks their range and names the item).  A device tensor is read back
-        here: one synchronisation."""
-        if isinstance(lengths, (torch.Tensor, np.ndarray)):
-            if isinstance(lengths, torch.Tensor):
-                integer = not (lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool)
-            else:
-                integer = lengths.dtype.kind in "iu"
-            if not integer:
-                raise ValueError(f"BigVGAN.{what}: lengths must be integers, got dtype {lengths.dtype}")
-            lengths = lengths.reshape(-1).tolist()
-        v = []
-        for i, n in enumerate(lengths):
-            if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-                raise ValueError(f"BigVGAN.{what}: lengths must be integers, item {i} has {n!r}")
-            v.append(int(n))
-        if len(v) != B:
-            raise ValueError(f"BigVGAN.{what}: {len(v)} lengths for {B} items" + (f" (item {len(v)} has none)" if len(v) < B else ""))
-        return v
-
     @torch.no_grad()
     def forward(self, x, lengths=None):
         """mel [B, num_mels, T] -> [B, 1, T * hop].  `lengths` (B frame counts in [1, T]: a list, a host tensor or a device tensor, which
@@ -230,20 +210,17 @@ class BigVGAN(HandleModule):
         if x.dim() != 3 or x.shape[1] != self.h.num_mels or x.shape[2] < 1:
             raise ValueError(f"BigVGAN: expected mel [B, {self.h.num_mels}, T], got {tuple(x.shape)}")
         b, _, t = x.shape
-        if lengths is not None:
-            lengths = self._lengths(lengths, b, "forward")
+        lengths = host_lengths(lengths, b, "BigVGAN.forward", integers_only=True)
         device = x.device
         lib, stream = self._sync(device)
         mel = x.detach().to(dtype=torch.float32).contiguous()
         wav = torch.empty(b, 1, t * self.hop, device=device)
         ws = self._workspace(lib, device, b, t)
-        with torch.cuda.device(device):
-            if lengths is None:
-                rc = lib.us_vocoder_forward(self._h, mel.data_ptr(), wav.data_ptr(), b, t, ws.data_ptr(), ws.numel(), stream)
-            else:
-                rc = lib.us_vocoder_forward_lengths(self._h, mel.data_ptr(), (C.c_int64 * b)(*lengths), wav.data_ptr(), b, t, ws.data_ptr(),
-                                                    ws.numel(), stream)
-        self._check(lib, rc, "us_vocoder_forward" if lengths is None else "us_vocoder_forward_lengths")
+        if lengths is None:
+            self._call(lib, device, "forward", self._h, mel.data_ptr(), wav.data_ptr(), b, t, ws.data_ptr(), ws.numel(), stream)
+        else:
+            self._call(lib, device, "forward_lengths", self._h, mel.data_ptr(), c_lengths(lengths), wav.data_ptr(), b, t, ws.data_ptr(),
+                       ws.numel(), stream)
         return wav
 
 
@@ -255,8 +232,7 @@ class BigVGAN(HandleModule):
         tensors of that shape on x's device and may share storage, as they do in the forward.  `lengths` (B input-step counts in [1, Tin],
         as `forward` takes them): the ragged launch (us_vocoder_debug_layer_lengths); a convolution or an Activation1d then leaves `out`
         as it was at and past an item's end (give `out` to define it there), and `conv_post` writes zeros there."""
-        if lengths is not None:
-            lengths = self._lengths(lengths, x.shape[0] if x.dim() == 3 else -1, "debug_layer")
+        lengths = host_lengths(lengths, x.shape[0] if x.dim() == 3 else -1, "BigVGAN.debug_layer", integers_only=True)
         device = x.device
         lib, stream = self._sync(device)
         try:
@@ -288,7 +264,7 @@ class BigVGAN(HandleModule):
                 rc = lib.us_vocoder_debug_layer(self._h, prefix.encode(), x.data_ptr(), ptr(res), ptr(sum), float(div), out.data_ptr(), b, t, stream)
             else:
                 rc = lib.us_vocoder_debug_layer_lengths(self._h, prefix.encode(), x.data_ptr(), ptr(res), ptr(sum), float(div), out.data_ptr(), b, t,
-                                                        (C.c_int64 * b)(*lengths), stream)
+                                                        c_lengths(lengths), stream)
         self._check(lib, rc, f"us_vocoder_debug_layer({prefix})" if lengths is None else f"us_vocoder_debug_layer_lengths({prefix})")
         return out
 
