@@ -8,7 +8,7 @@ its text by character and word error rate, compare its speaker embedding with th
 
 LIST holds one `wav|transcript[|reference_wav]` line per sample.  CTC.pt is a `torch.save`d state dict of `transformers.HubertForCTC` or
 `Wav2Vec2ForCTC` in the base form (the class is taken from the keys; nothing is fetched by name; the base size unless --config_path
-names the model's config.json) and vocab.json its tokenizer's vocabulary.  The wavs are read with `voice_conversion.read_wav`,
+names the model's config.json) and vocab.json its tokenizer's vocabulary.  The wavs are read with `unitspeech_amd.audio.read_wav`,
 resampled to 16 kHz by the library's `Resample`, sorted by length and transcribed in ragged batches of --batch (`transcribe_ids`: encoder, CTC head, greedy collapse; an item has the ids it has alone).  The
 transcripts are brought to the vocabulary by `normalize_text`; CER and WER are `unitspeech_amd.asr.error_rates` (corpus rates: sum of
 distances over sum of reference lengths).  With --speaker_encoder_path and the third column, SECS is the cosine similarity of
@@ -36,6 +36,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from unitspeech_amd.audio import read_wav, to_16k  # noqa: E402
+from unitspeech_amd.batching import pad_batch, plan_batches  # noqa: E402
 
 MIN_SAMPLES_16K = 400            # the receptive field of the feature extractor: one frame
 SYNTHETIC_RATE = 22050
@@ -59,31 +61,12 @@ def parse_filelist(text: str):
     return out
 
 
-def plan_batches(lengths, max_batch: int):
-    """Indices into `lengths`, sorted by length (ties in index order) and cut into batches of at most `max_batch`."""
-    if max_batch < 1:
-        raise ValueError("--batch must be at least 1")
-    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
-    return [order[i:i + max_batch] for i in range(0, len(order), max_batch)]
-
-
 def apply_edits(text: str, edits: int, cut: bool, letter: str = "a"):
     """A string at Levenshtein distance exactly `edits` from `text`: `edits` characters cut from its end (when asked, and when that leaves
     a longer, tidy string) or `edits` letters appended: the lengths then differ by `edits`, which no alignment can beat."""
     if cut and len(text) > 2 * edits and not text[:-edits].endswith(" "):
         return text[:-edits]
     return text + letter * edits
-
-
-@torch.no_grad()
-def to_16k(wav, rate, device, resamplers):
-    from unitspeech_amd.resample import Resample
-    wav = torch.as_tensor(wav).float().to(device)
-    if rate == 16000:
-        return wav
-    if rate not in resamplers:
-        resamplers[rate] = Resample(rate, 16000).to(device)
-    return resamplers[rate](wav)
 
 
 @torch.no_grad()
@@ -96,7 +79,7 @@ def normalize_items(items, ndb, max_batch, device):
         group = [i for i, it in enumerate(items) if it[2] == rate]
         for batch in plan_batches([len(items[i][1]) for i in group], max_batch):
             idx = [group[j] for j in batch]
-            x, n = padded_batch([torch.as_tensor(items[i][1]).float().to(device) for i in idx], list(range(len(idx))))
+            x, n = pad_batch([torch.as_tensor(items[i][1]).float().to(device) for i in idx])
             y, lv = normalize_level(x, rate, ndb, lengths=n, via_int16=True, out_int16=True)
             y = y.to(torch.float32) / 32768.0
             for b, (i, level, gain, clipped) in enumerate(zip(idx, lv.level_db.tolist(), lv.gain.tolist(), lv.clipped.tolist())):
@@ -106,11 +89,8 @@ def normalize_items(items, ndb, max_batch, device):
 
 
 def padded_batch(wavs16, idx):
-    n = [int(wavs16[i].shape[0]) for i in idx]
-    x = torch.zeros(len(idx), max(n), device=wavs16[idx[0]].device)
-    for b, i in enumerate(idx):
-        x[b, :n[b]] = wavs16[i]
-    return x, n
+    """`pad_batch` of the items of `wavs16` that `idx` names."""
+    return pad_batch([wavs16[i] for i in idx])
 
 
 @torch.no_grad()
@@ -231,7 +211,6 @@ def main(argv=None):
     else:
         if not args.filelist or not args.ctc_path or not args.vocab_path:
             raise SystemExit("give --filelist, --ctc_path and --vocab_path, or --synthetic N")
-        from voice_conversion import read_wav
         with open(args.filelist, encoding="utf-8") as f:
             entries = parse_filelist(f.read())
         if not entries:
@@ -269,7 +248,6 @@ def main(argv=None):
     rates = error_rates(hyps, transcripts, device)
     secs = [None] * len(items)
     if embedder is not None:
-        from voice_conversion import read_wav
         refs16 = [to_16k(*read_wav(r), device, resamplers) if r else None for r in references]
         secs = similarities(embedder, wavs16, refs16, args.batch)
     words = word_timestamps(model, vocabulary, wavs16, transcripts, batches) if args.timestamps else None

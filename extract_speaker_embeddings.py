@@ -32,6 +32,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from unitspeech_amd.audio import load_tensor_file, to_16k  # noqa: E402
+from unitspeech_amd.batching import pad_batch, plan_batches  # noqa: E402
 
 MIN_SAMPLES_16K = 400            # the receptive field of the wav2vec2-family feature extractor: one frame
 SYNTHETIC_RATE = 22050
@@ -55,28 +57,6 @@ def parse_filelist(text: str):
             raise ValueError(f"file list line {no}: expected `path|text|speaker`, got {line!r}")
         out.append((parts[0], "|".join(parts[1:-1]), parts[-1]))
     return out
-
-
-def plan_batches(lengths, max_batch: int, max_padded_samples: int):
-    """Cut utterances of the given lengths into batches: -> a list of lists of indices into `lengths`.  The utterances are sorted by length
-    (ties in index order) and taken in that order; a batch is closed when one more would make it larger than `max_batch` items or its
-    padded size (items x its longest) larger than `max_padded_samples`.  Every index appears exactly once; an utterance that alone is
-    longer than `max_padded_samples` gets a batch of its own."""
-    if max_batch < 1 or max_padded_samples < 1:
-        raise ValueError("plan_batches: max_batch and max_padded_samples must be at least 1")
-    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
-    batches, cur = [], []
-    for i in order:
-        n = int(lengths[i])                      # ascending: the newcomer is the longest of the batch it joins
-        if n < 1:
-            raise ValueError(f"plan_batches: utterance {i} has length {n}")
-        if cur and (len(cur) + 1 > max_batch or (len(cur) + 1) * n > max_padded_samples):
-            batches.append(cur)
-            cur = []
-        cur.append(i)
-    if cur:
-        batches.append(cur)
-    return batches
 
 
 def speaker_means(rows, speakers):
@@ -128,11 +108,7 @@ def synthetic_embedder(device, seed: int = 0):
 
 def load_utterance(path: str):
     """-> (waveform [T] fp32 on the host, sampling rate) from a `.pt` / `.npz` file with `wav` and optionally `wav_sampling_rate`."""
-    if path.endswith(".npz"):
-        with np.load(path) as f:
-            d = {k: torch.from_numpy(np.asarray(f[k])) for k in f.files}
-    else:
-        d = torch.load(path, map_location="cpu")
+    d = load_tensor_file(path)
     if not isinstance(d, dict) or "wav" not in d:
         raise SystemExit(f"{path}: expected a dict with `wav` (and `wav_sampling_rate` unless it is {SYNTHETIC_RATE} Hz)")
     wav = torch.as_tensor(d["wav"]).float()
@@ -142,28 +118,13 @@ def load_utterance(path: str):
 
 
 @torch.no_grad()
-def to_16k(wav, rate, device, resamplers):
-    """One utterance [T] at `rate` -> [T'] at 16 kHz on `device` (preprocessing/utils.py:8-14)."""
-    from unitspeech_amd.resample import Resample
-    wav = wav.to(device)
-    if rate == 16000:
-        return wav
-    if rate not in resamplers:
-        resamplers[rate] = Resample(rate, 16000).to(device)
-    return resamplers[rate](wav)
-
-
-@torch.no_grad()
 def embed_all(embedder, wavs16, max_batch, max_padded_samples):
     """wavs16: 16 kHz waveforms [T_i] on the device -> their embeddings [emb_dim], on the host, in the order given."""
     lens = [int(w.shape[0]) for w in wavs16]
     rows = [None] * len(wavs16)
     batches = plan_batches(lens, max_batch, max_padded_samples)
     for idx in batches:
-        n = [lens[i] for i in idx]
-        x = torch.zeros(len(idx), max(n), device=wavs16[idx[0]].device)
-        for b, i in enumerate(idx):
-            x[b, :n[b]] = wavs16[i]
+        x, n = pad_batch([wavs16[i] for i in idx])
         emb = embedder(x, n).cpu()
         for b, i in enumerate(idx):
             rows[i] = emb[b]

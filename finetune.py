@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 from unitspeech_amd import DecoderConfig, FusedAdam, UnitSpeech, synthetic_state_dict
+from unitspeech_amd.audio import load_tensor_file
 from unitspeech_amd.checkpoint import build_decoder, infer_config, load_decoder_checkpoint, save_finetuned_checkpoint
 from unitspeech_amd.util import fix_len_compatibility, generate_path, sequence_mask
 
@@ -55,12 +56,7 @@ MEL_ARGS = (1024, 80, SAMPLING_RATE, 256, 1024, 0, 8000)          # finetune.py:
 def load_features(args, cfg, base, device):
     """--features: (mel, cond_x, duration, spk_emb, mel_min, mel_max) on `device` from the file the reference's pre-steps were saved to."""
     path = args.features
-    if path.endswith(".npz"):
-        with np.load(path) as f:
-            d = {k: torch.from_numpy(np.asarray(f[k])) for k in f.files}
-    else:
-        d = torch.load(path, map_location="cpu")
-    d = {k: (torch.as_tensor(v) if not isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+    d = {k: (torch.as_tensor(v) if not isinstance(v, torch.Tensor) else v) for k, v in load_tensor_file(path).items()}
     if "wav" in d and getattr(args, "hubert_checkpoint", None) and not any(k in d for k in ("dense", "unit", "cond_x")):
         # finetune.py:112-113: the unit extractor's dense model on the utterance at 16 kHz
         from unitspeech_amd.hubert import HubertFeatureReader, load_hubert_checkpoint

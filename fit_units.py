@@ -31,6 +31,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from unitspeech_amd.audio import read_wav, to_16k  # noqa: E402
+from unitspeech_amd.batching import pad_batch  # noqa: E402
 from unitspeech_amd.units import KMeansQuantizer, synthetic_centers, synthetic_dense  # noqa: E402
 
 
@@ -52,8 +54,6 @@ def load_features(path):
 def hubert_chunks(args, device):
     """-> ([features [B, Fmax, D]], [frames [B]]): one ragged batch of --wav_batch waveforms per chunk."""
     from unitspeech_amd.hubert import load_hubert_checkpoint
-    from unitspeech_amd.resample import Resample
-    from voice_conversion import read_wav
     if not args.hubert_checkpoint:
         raise SystemExit("--wav_list needs --hubert_checkpoint")
     hubert, normalize = load_hubert_checkpoint(args.hubert_checkpoint)
@@ -64,22 +64,14 @@ def hubert_chunks(args, device):
     for s in range(0, len(paths), args.wav_batch):
         wavs = []
         for p in paths[s:s + args.wav_batch]:
-            wav, rate = read_wav(p)
-            wav = torch.from_numpy(wav).to(device)
-            if rate != 16000:
-                if rate not in resamplers:
-                    resamplers[rate] = Resample(rate, 16000).to(device)
-                wav = resamplers[rate](wav)
+            wav = to_16k(*read_wav(p), device, resamplers)
             if hubert.frames(wav.numel()) < 1:
                 print(f"skipping {p}: shorter than one frame")
                 continue
             wavs.append(wav)
         if not wavs:
             continue
-        n = [w.numel() for w in wavs]
-        batch = torch.zeros(len(wavs), max(n), device=device)
-        for i, w in enumerate(wavs):
-            batch[i, :n[i]] = w
+        batch, n = pad_batch(wavs)
         xs.append(hubert(batch, lengths=n, output_layer=args.hubert_layer, normalize=normalize))
         ls.append(torch.tensor([hubert.frames(v) for v in n], dtype=torch.int64, device=device))
     if not xs:

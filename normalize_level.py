@@ -25,26 +25,15 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from unitspeech_amd.audio import read_wav  # noqa: E402
+from unitspeech_amd.batching import pad_batch, plan_batches  # noqa: E402
 
 SYNTHETIC_RATE = 22050
 
 
 def read_samples(path):
     """-> (int16 or float32 mono samples, sampling rate): int16 stays int16, everything else becomes float32 in units of full scale."""
-    from scipy.io import wavfile
-    rate, data = wavfile.read(path)
-    if data.ndim == 2 and data.shape[1] == 1:
-        data = data[:, 0]
-    if data.dtype == np.int16 and data.ndim == 1:
-        return np.ascontiguousarray(data), int(rate)
-    if data.dtype.kind == "i":
-        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
-    elif data.dtype.kind == "u":
-        data = (data.astype(np.float32) - 128.0) / 128.0
-    data = data.astype(np.float32)
-    if data.ndim == 2:
-        data = data.mean(axis=1)
-    return np.ascontiguousarray(data), int(rate)
+    return read_wav(path, keep_int16=True)
 
 
 def synthetic_items(n: int, seed: int = 0):
@@ -61,14 +50,6 @@ def synthetic_items(n: int, seed: int = 0):
     return out
 
 
-def plan_batches(lengths, max_batch: int):
-    """Indices into `lengths`, sorted by length (ties in index order) and cut into batches of at most `max_batch`."""
-    if max_batch < 1:
-        raise ValueError("--batch must be at least 1")
-    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
-    return [order[i:i + max_batch] for i in range(0, len(order), max_batch)]
-
-
 @torch.no_grad()
 def normalize_items(items, ndb, max_batch, device):
     """[(name, int16 or float32 samples, rate)] -> [(int16 samples, level_db, gain, clipped)] in the order given.  A batch holds items of one
@@ -76,19 +57,15 @@ def normalize_items(items, ndb, max_batch, device):
     from unitspeech_amd.level import normalize_level
     out = [None] * len(items)
     for key in sorted({(r, w.dtype == np.int16) for _, w, r in items}):
-        rate, is_i16 = key
         group = [i for i, (_, w, r) in enumerate(items) if (r, w.dtype == np.int16) == key]
         for batch in plan_batches([len(items[i][1]) for i in group], max_batch):
             idx = [group[j] for j in batch]
-            n = [len(items[i][1]) for i in idx]
+            x, n = pad_batch([items[i][1] for i in idx])
             if max(n) == 0:
                 for i in idx:
                     out[i] = (np.zeros(0, dtype=np.int16), -100.0, 1.0, 0)
                 continue
-            x = torch.zeros(len(idx), max(n), dtype=torch.int16 if is_i16 else torch.float32)
-            for b, i in enumerate(idx):
-                x[b, :n[b]] = torch.from_numpy(items[i][1])
-            y, lv = normalize_level(x.to(device), rate, ndb, lengths=n, via_int16=True, out_int16=True)
+            y, lv = normalize_level(x.to(device), key[0], ndb, lengths=n, via_int16=True, out_int16=True)
             y = y.cpu().numpy()
             for b, (i, level, gain, clipped) in enumerate(zip(idx, lv.level_db.tolist(), lv.gain.tolist(), lv.clipped.tolist())):
                 out[i] = (y[b, :n[b]].copy(), level, gain, clipped)

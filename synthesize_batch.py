@@ -33,7 +33,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-from extract_speaker_embeddings import plan_batches as _plan  # noqa: E402
+from unitspeech_amd.batching import pad_batch, plan_batches as _plan  # noqa: E402
 
 WORDS = ("buna", "ziua", "the", "quick", "brown", "fox", "jumps", "over", "lazy", "dog", "speech", "unit", "voice", "mel", "wave", "north",
          "wind", "and", "sun", "were", "disputing", "which", "was", "stronger")
@@ -90,10 +90,7 @@ def synthetic_vocoder(device, seed: int = 0, config=None):
 
 def pad_ids(ids, device):
     """A list of id lists -> (phoneme [B, Lmax] int64 padded with 0, phoneme_lengths [B]) on `device`."""
-    lens = [len(v) for v in ids]
-    x = torch.zeros(len(ids), max(lens), dtype=torch.long)
-    for b, v in enumerate(ids):
-        x[b, :lens[b]] = torch.as_tensor(v, dtype=torch.long)
+    x, lens = pad_batch([torch.as_tensor(v, dtype=torch.long) for v in ids])
     return x.to(device), torch.tensor(lens, dtype=torch.long, device=device)
 
 

@@ -30,6 +30,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import evaluate  # noqa: E402
+from unitspeech_amd.audio import read_wav, to_16k  # noqa: E402
+from unitspeech_amd.batching import pad_batch, plan_batches  # noqa: E402
 
 
 def encoder_state_dict(sd, prefix_out: str):
@@ -72,7 +74,7 @@ def synthetic_task(n, seed, device):
     teacher, vocabulary = evaluate.synthetic_model(device, seed)
     items = evaluate.synthetic_waves(n, seed)
     resamplers = {}
-    wavs16 = [evaluate.to_16k(w, r, device, resamplers) for _, w, r in items]
+    wavs16 = [to_16k(w, r, device, resamplers) for _, w, r in items]
     transcripts, _ = evaluate.transcribe_all(teacher, vocabulary, wavs16, n)
     model = HubertForCTC(vocab_size=len(vocabulary), pad_token_id=vocabulary.blank_id, trainable=True, **evaluate.TINY)
     sd = {k: v for k, v in teacher.state_dict().items() if not k.startswith("lm_head.")}
@@ -118,7 +120,6 @@ def main(argv=None):
     else:
         if not args.filelist or not args.vocab_path or not args.encoder_path:
             raise SystemExit("give --filelist, --vocab_path and --encoder_path, or --synthetic N")
-        from voice_conversion import read_wav
         with open(args.filelist, encoding="utf-8") as f:
             entries = evaluate.parse_filelist(f.read())
         if not entries:
@@ -126,7 +127,7 @@ def main(argv=None):
         vocabulary = CTCVocabulary(args.vocab_path, args.blank, args.word_delimiter)
         model = build_model(args, vocabulary, device)
         resamplers = {}
-        wavs16 = [evaluate.to_16k(*read_wav(path), device, resamplers) for path, _, _ in entries]
+        wavs16 = [to_16k(*read_wav(path), device, resamplers) for path, _, _ in entries]
         transcripts = [normalize_text(text, vocabulary) for _, text, _ in entries]
     for i, w in enumerate(wavs16):
         if w.shape[0] < evaluate.MIN_SAMPLES_16K:
@@ -139,7 +140,7 @@ def main(argv=None):
         opt = FusedAdam(params, lr=args.lr)
     else:
         opt = torch.optim.Adam(params, lr=args.lr)
-    batches = evaluate.plan_batches([int(w.shape[0]) for w in wavs16], args.batch)
+    batches = plan_batches([int(w.shape[0]) for w in wavs16], args.batch)
     history, steps = [], 0
     for epoch in range(args.epochs):
         total = torch.zeros((), device=device)
@@ -147,7 +148,7 @@ def main(argv=None):
         for idx in batches:
             if args.steps and steps >= args.steps:
                 break
-            x, n = evaluate.padded_batch(wavs16, idx)
+            x, n = pad_batch([wavs16[i] for i in idx])
             tg, tl = encode_targets([transcripts[i] for i in idx], vocabulary, device)
             opt.zero_grad(set_to_none=True)
             loss = model.loss(x, n, tg, tl, reduction="mean", zero_infinity=True)

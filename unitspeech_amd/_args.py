@@ -1,5 +1,6 @@
 """Batch arguments on their way into the HIP library: per-item lengths as host integers (`host_lengths`, `c_lengths`) or as a device
-int64 tensor (`device_lengths`), and the small conversions every wrapper around a plain library function needs."""
+int64 tensor (`device_lengths`), the small conversions every wrapper around a plain library function needs (`f32`, `i64`), and the call
+of such a function itself (`call`)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,10 +8,29 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _lib
+
 
 def stream():
     """The current stream of the current device as a `hipStream_t` argument (a pointer whether or not the function declares its types)."""
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def call(dev, name, *args):
+    """The plain (handle-free) library function `name` with `dev` current: a tensor goes in as its `data_ptr()`, None as a null
+    pointer, everything else as it is, and the current stream of `dev` is appended.  A refusal is raised under the symbol's name."""
+    tensor = torch.Tensor
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), name)(*[a.data_ptr() if isinstance(a, tensor) else a for a in args], stream())
+    if rc != _lib.US_OK:
+        _lib.check(rc, what=name)
+
+
+def f32(t, dev, detach=True):
+    """-> `t` as a contiguous fp32 tensor on `dev` (None stays None); `detach=False` keeps it in the autograd graph."""
+    if t is None:
+        return None
+    return (t.detach() if detach else t).to(device=dev, dtype=torch.float32).contiguous()
 
 
 def i64(t, dev):

@@ -247,6 +247,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     """dlopen the in-tree library, building it first when absent or older than any of its sources (a cheap mtime check; with
     no hipcc on the machine an existing library is used as it is)."""
     global _lib
+    if _lib is not None:                 # every call of a plain function comes through here: no lock once the library is loaded
+        return _lib
     with _lock:
         if _lib is not None:
             return _lib

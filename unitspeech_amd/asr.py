@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._args import device_lengths, host_lengths, i64 as _i64, need_gpu as _need_gpu, stream as _stream
+from ._args import call as _call, device_lengths, f32 as _f32, host_lengths, i64 as _i64, need_gpu as _need_gpu
 from .hubert import _BASE, HubertModel
 
 __all__ = ["CTCHead", "HubertForCTC", "Wav2Vec2ForCTC", "load_ctc_checkpoint", "CTCVocabulary", "normalize_text", "edit_distance",
@@ -46,10 +46,7 @@ def ctc_collapse(ids, lengths=None, blank: int = 0, first_frame: bool = False):
     tokens = torch.empty(B, T, dtype=torch.int64, device=dev)
     ff = torch.empty(B, T, dtype=torch.int64, device=dev) if first_frame else None
     n = torch.empty(B, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().us_ctc_collapse(u.data_ptr(), None if lens is None else lens.data_ptr(), B, T, int(blank), tokens.data_ptr(),
-                                         None if ff is None else ff.data_ptr(), n.data_ptr(), _stream())
-    _lib.check(rc, None, "us_ctc_collapse")
+    _call(dev, "us_ctc_collapse", u, lens, B, T, int(blank), tokens, ff, n)
     return (tokens, n, ff) if first_frame else (tokens, n)
 
 
@@ -78,15 +75,11 @@ class CTCHead(torch.nn.Module):
         """The head in the library's operand form on `dev`, packed again when a parameter's storage or version changed."""
         tag = tuple((p.data_ptr(), p._version, p.device) for p in (self.weight, self.bias)) + (dev,)
         if self._packed is None or self._tag != tag:
-            lib = _lib.load()
             V, H = self.weight.shape
-            w = self.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-            b = self.bias.detach().to(device=dev, dtype=torch.float32).contiguous()
-            n = int(lib.us_ctc_packed_bytes(V, H))
+            n = int(_lib.load().us_ctc_packed_bytes(V, H))
             buf = torch.empty(n, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.us_ctc_pack_head(w.data_ptr(), b.data_ptr(), V, H, buf.data_ptr(), n, _stream())
-            _lib.check(rc, None, "us_ctc_pack_head")          # w and b are read on the stream their memory would be reused on
+            # w and b are read on the stream their memory would be reused on
+            _call(dev, "us_ctc_pack_head", _f32(self.weight, dev), _f32(self.bias, dev), V, H, buf, n)
             self._packed, self._tag = buf, tag
         return self._packed
 
@@ -103,11 +96,7 @@ class CTCHead(torch.nn.Module):
         logits = torch.empty(B, F, V, device=dev)
         lp = torch.empty(B, F, V, device=dev) if log_probs else None
         out_ids = torch.empty(B, F, dtype=torch.int64, device=dev) if ids else None
-        with torch.cuda.device(dev):
-            rc = _lib.load().us_ctc_logits(x.data_ptr(), None if lens is None else lens.data_ptr(), self.packed(dev).data_ptr(), B, F, V, H,
-                                           logits.data_ptr(), None if lp is None else lp.data_ptr(),
-                                           None if out_ids is None else out_ids.data_ptr(), _stream())
-        _lib.check(rc, None, "us_ctc_logits")
+        _call(dev, "us_ctc_logits", x, lens, self.packed(dev), B, F, V, H, logits, lp, out_ids)
         return logits, lp, out_ids, lens
 
     def forward(self, features, frame_lengths=None, log_probs: bool = False):
@@ -149,16 +138,12 @@ class _HeadFn(torch.autograd.Function):
         H = weight.shape[1]
         g = g.detach().to(torch.float32).contiguous()
         x = features.detach().to(torch.float32).contiguous()
-        w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        w = _f32(weight, dev)
         dw, db = torch.empty(V, H, device=dev), torch.empty(V, device=dev)
         dx = torch.empty(B, F, H, device=dev) if ctx.needs_input_grad[1] else None
-        lib = _lib.load()
-        n = int(lib.us_ctc_head_backward_workspace_bytes(B, F, V, H))
+        n = int(_lib.load().us_ctc_head_backward_workspace_bytes(B, F, V, H))
         ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.us_ctc_head_backward(g.data_ptr(), x.data_ptr(), None if ctx.lens is None else ctx.lens.data_ptr(), w.data_ptr(), B, F, V, H,
-                                          dw.data_ptr(), db.data_ptr(), None if dx is None else dx.data_ptr(), ws.data_ptr(), n, _stream())
-        _lib.check(rc, None, "us_ctc_head_backward")
+        _call(dev, "us_ctc_head_backward", g, x, ctx.lens, w, B, F, V, H, dw, db, dx, ws, n)
         return (None, None if dx is None else dx.to(features.dtype), None, None, dw.to(weight.dtype) if ctx.needs_input_grad[4] else None,
                 db if ctx.needs_input_grad[5] else None)
 
@@ -185,18 +170,14 @@ def _ctc_loss_call(x, tg, fl, tl, blank, zero_infinity, stage=_lib.US_CTC_WHOLE,
     dev = x.device
     B, T, V = x.shape
     Lmax = int(tg.shape[1])
-    lib = _lib.load()
     with_grad = bool(with_grad) or stage == _lib.US_CTC_BACKWARD
-    n = int(lib.us_ctc_loss_workspace_bytes(B, T, Lmax, int(with_grad or stage == _lib.US_CTC_FORWARD)))
+    n = int(_lib.load().us_ctc_loss_workspace_bytes(B, T, Lmax, int(with_grad or stage == _lib.US_CTC_FORWARD)))
     if ws is None:
         ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     loss = torch.empty(B, device=dev)
     grad = torch.empty(B, T, V, device=dev) if with_grad else None
-    with torch.cuda.device(dev):
-        rc = lib.us_ctc_loss(x.data_ptr(), None if fl is None else fl.data_ptr(), tg.data_ptr() if Lmax else None, tl.data_ptr(),
-                             None if grad_out is None else grad_out.data_ptr(), B, T, V, Lmax, int(blank), int(bool(zero_infinity)), stage,
-                             loss.data_ptr(), None if grad is None else grad.data_ptr(), ws.data_ptr(), n, _stream())
-    _lib.check(rc, None, "us_ctc_loss")
+    _call(dev, "us_ctc_loss", x, fl, tg if Lmax else None, tl, grad_out, B, T, V, Lmax, int(blank), int(bool(zero_infinity)), stage, loss, grad,
+          ws, n)
     return loss, grad, ws
 
 
@@ -255,18 +236,14 @@ def forced_align(scores, targets, frame_lengths, target_lengths, blank: int = 0)
     dev = x.device
     B, T, V = x.shape
     Lmax = int(tg.shape[1])
-    lib = _lib.load()
-    n = int(lib.us_ctc_align_workspace_bytes(B, T, Lmax))
+    n = int(_lib.load().us_ctc_align_workspace_bytes(B, T, Lmax))
     ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     path = torch.empty(B, T, dtype=torch.int64, device=dev)
     score = torch.empty(B, device=dev)
     start = torch.empty(B, Lmax, dtype=torch.int64, device=dev)
     frames = torch.empty(B, Lmax, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.us_ctc_forced_align(x.data_ptr(), None if fl is None else fl.data_ptr(), tg.data_ptr() if Lmax else None, tl.data_ptr(), B, T, V,
-                                     Lmax, int(blank), path.data_ptr(), score.data_ptr(), start.data_ptr() if Lmax else None,
-                                     frames.data_ptr() if Lmax else None, ws.data_ptr(), n, _stream())
-    _lib.check(rc, None, "us_ctc_forced_align")
+    _call(dev, "us_ctc_forced_align", x, fl, tg if Lmax else None, tl, B, T, V, Lmax, int(blank), path, score, start if Lmax else None,
+          frames if Lmax else None, ws, n)
     return path, score, start, frames
 
 
@@ -449,10 +426,7 @@ def edit_distance(hyp, ref, n_hyp, n_ref):
     if na is None or nb is None:
         raise ValueError("edit_distance: n_hyp and n_ref are needed")
     dist = torch.empty(P, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().us_edit_distance(a.data_ptr(), na.data_ptr(), int(a.shape[1]), b.data_ptr(), nb.data_ptr(), int(b.shape[1]), P,
-                                          dist.data_ptr(), _stream())
-    _lib.check(rc, None, "us_edit_distance")
+    _call(dev, "us_edit_distance", a, na, int(a.shape[1]), b, nb, int(b.shape[1]), P, dist)
     return dist
 
 

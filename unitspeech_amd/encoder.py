@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import call as _call, f32 as _f32
 from ._handle import HandleModule
 
 PRENET_LAYERS, PRENET_KERNEL = 3, 5            # unitspeech/encoder.py:283-284
@@ -423,10 +424,6 @@ def _ptrs(tensors):
     return [None if t is None else t.data_ptr() for t in tensors]
 
 
-def _f32(t, device):
-    return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
 # ---- the autograd bridge of the two trainable modules ----------------------------------------------------------------------
 # Each training forward owns its workspace, which is the tape: ctx keeps it until backward.  The two C ABIs end alike:
 # us_{abi}_forward_train(h, operands..., B, L, p, seed, ws, bytes, stream), us_{abi}_backward(h, upstream..., B, L, keys, grads, n, ws,
@@ -596,14 +593,10 @@ class _DurationMseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logw, w, x_mask):
         device = logw.device
-        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-        lw, ww, m = f32(logw), f32(w), f32(x_mask)
+        lw, ww, m = _f32(logw, device), _f32(w, device), _f32(x_mask, device)
         loss = torch.empty((), device=device)
         d_logw = torch.empty_like(lw)
-        with torch.cuda.device(device):
-            rc = _lib.load().us_duration_predictor_mse_loss(lw.data_ptr(), ww.data_ptr(), m.data_ptr(), loss.data_ptr(), d_logw.data_ptr(),
-                                                            lw.shape[0], lw.shape[-1], C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-        _lib.check(rc, None, "us_duration_predictor_mse_loss")
+        _call(device, "us_duration_predictor_mse_loss", lw, ww, m, loss, d_logw, lw.shape[0], lw.shape[-1])
         ctx.save_for_backward(d_logw)
         return loss
 

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._args import device_lengths, stream as _stream
+from ._args import call as _call, device_lengths
 
 __all__ = ["active_speech_level", "normalize_level", "sv56"]
 
@@ -67,17 +67,13 @@ def _sample_rate(sample_rate, what):
 
 def _measure(x, code, quantize, lens, sr):
     """-> (stats [B, 8] fp64, counts [B, 15] int64, the workspace, its size)."""
-    lib = _lib.load()
     B, T = x.shape
     dev = x.device
-    n = int(lib.us_level_workspace_bytes(B, T))
+    n = int(_lib.load().us_level_workspace_bytes(B, T))
     ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     stats = torch.empty(B, 8, dtype=torch.float64, device=dev)
     counts = torch.empty(B, 15, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.us_level_measure(x.data_ptr(), code, int(quantize), None if lens is None else lens.data_ptr(), B, T, sr, stats.data_ptr(),
-                                  counts.data_ptr(), ws.data_ptr(), n, _stream())
-    _lib.check(rc, None, "us_level_measure")
+    _call(dev, "us_level_measure", x, code, int(quantize), lens, B, T, sr, stats, counts, ws, n)
     return stats, counts, ws, n
 
 
@@ -114,11 +110,8 @@ def normalize_level(wav, sample_rate, ndb: float = -26.0, lengths=None, via_int1
     out = torch.empty(B, T, dtype=torch.int16 if out_int16 else torch.float32, device=dev)
     gain = torch.empty(B, dtype=torch.float64, device=dev)
     clipped = torch.empty(B, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().us_level_apply(x.data_ptr(), code, int(quantize), None if lens is None else lens.data_ptr(), B, T, stats.data_ptr(),
-                                        float(ndb), out.data_ptr(), _lib.US_LEVEL_I16 if out_int16 else _lib.US_LEVEL_F32, gain.data_ptr(),
-                                        clipped.data_ptr(), ws.data_ptr(), n, _stream())
-    _lib.check(rc, None, "us_level_apply")
+    _call(dev, "us_level_apply", x, code, int(quantize), lens, B, T, stats, float(ndb), out, _lib.US_LEVEL_I16 if out_int16 else _lib.US_LEVEL_F32,
+          gain, clipped, ws, n)
     shape = tuple(wav.shape)
     return out.reshape(shape), LevelInfo(stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3], counts, gain, clipped)
 

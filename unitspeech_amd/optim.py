@@ -19,11 +19,10 @@ the group's norm is kept in `last_grad_norms[group_index]`.  A group without the
 Only what the reference uses is supported: weight_decay=0, amsgrad=False, maximize=False, fp32 parameters on one ROCm device.
 There is no CPU fallback.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._args import call as _call
 
 _CHUNK = 4096
 
@@ -108,13 +107,8 @@ class FusedAdam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             mn = group.get("max_norm", max_norm)
             ptrs = tab["ptrs"]
-            with torch.cuda.device(dev):
-                rc = self.lib.us_clip_adam_step(ptrs[0].data_ptr(), ptrs[1].data_ptr(), ptrs[2].data_ptr(), ptrs[3].data_ptr(),
-                                                ptrs[4].data_ptr(), tab["blk_tensor"].data_ptr(), tab["blk_off"].data_ptr(), len(ps),
-                                                tab["n_blocks"], float(group["lr"]), float(b1), float(b2), float(group["eps"]), step,
-                                                float(mn) if mn is not None else 0.0, tab["partial"].data_ptr(),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            _lib.check(rc, None, "us_clip_adam_step")
+            _call(dev, "us_clip_adam_step", *ptrs, tab["blk_tensor"], tab["blk_off"], len(ps), tab["n_blocks"], float(group["lr"]), float(b1),
+                  float(b2), float(group["eps"]), step, float(mn) if mn is not None else 0.0, tab["partial"])
             if mn is not None:
                 self.last_grad_norm = self.last_grad_norms[gi] = tab["partial"][tab["n_blocks"]]
             torch._C._increment_version(ps)        # the kernel wrote the parameters in place: let version-keyed caches (the HIP

@@ -17,15 +17,11 @@ import torch
 from typing import Optional, Sequence
 
 from . import _lib
-from ._args import i64 as _i64, stream as _stream
+from ._args import call as _call, f32 as _f32, i64 as _i64
 from .unit_encoder_train import align_segment, prior_loss
 
 __all__ = ["mas_log_prior", "maximum_path", "maximum_path_lengths", "align", "duration_loss", "random_replace_tensor",
            "compute_train_step_loss"]
-
-
-def _f32(t, dev):
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
 @torch.no_grad()
@@ -40,9 +36,7 @@ def mas_log_prior(mu_x, y, x_mask, y_mask):
                          f"y_mask {tuple(y_mask.shape)} do not agree")
     mu, yy, xm, ym = _f32(mu_x, dev), _f32(y, dev), _f32(x_mask, dev), _f32(y_mask, dev)
     out = torch.empty(B, Tx, Ty, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().us_mas_log_prior(mu.data_ptr(), yy.data_ptr(), xm.data_ptr(), ym.data_ptr(), out.data_ptr(), B, F, Tx, Ty, _stream())
-    _lib.check(rc, None, "us_mas_log_prior")
+    _call(dev, "us_mas_log_prior", mu, yy, xm, ym, out, B, F, Tx, Ty)
     return out
 
 
@@ -55,15 +49,11 @@ def maximum_path_lengths(log_prior, x_lengths, y_lengths):
     lp, xl, yl = _f32(log_prior, dev), _i64(x_lengths, dev), _i64(y_lengths, dev)
     if xl.shape != (B,) or yl.shape != (B,):
         raise ValueError(f"maximum_path: lengths {tuple(xl.shape)} / {tuple(yl.shape)} must hold {B} values")
-    lib = _lib.load()
     attn = torch.empty(B, Tx, Ty, device=dev)
     dur = torch.empty(B, Tx, device=dev)
-    n = int(lib.us_maximum_path_workspace_bytes(B, Tx, Ty))
+    n = int(_lib.load().us_maximum_path_workspace_bytes(B, Tx, Ty))
     ws = torch.empty(n, dtype=torch.uint8, device=dev) if n else None        # 0 while every item's table fits in LDS
-    with torch.cuda.device(dev):
-        rc = lib.us_maximum_path(lp.data_ptr(), xl.data_ptr(), yl.data_ptr(), attn.data_ptr(), dur.data_ptr(), B, Tx, Ty,
-                                 ws.data_ptr() if n else None, n, _stream())
-    _lib.check(rc, None, "us_maximum_path")
+    _call(dev, "us_maximum_path", lp, xl, yl, attn, dur, B, Tx, Ty, ws, n)
     return attn, dur
 
 
@@ -99,10 +89,7 @@ class _DurationLossFn(torch.autograd.Function):
         lw, d, m, xl = _f32(logw, dev), _f32(durations, dev), _f32(x_mask, dev), _i64(x_lengths, dev)
         loss = torch.empty((), device=dev)
         d_logw = torch.empty_like(lw)
-        with torch.cuda.device(dev):
-            rc = _lib.load().us_duration_loss(lw.data_ptr(), d.data_ptr(), m.data_ptr(), xl.data_ptr(), loss.data_ptr(), d_logw.data_ptr(),
-                                              B, Tx, _stream())
-        _lib.check(rc, None, "us_duration_loss")
+        _call(dev, "us_duration_loss", lw, d, m, xl, loss, d_logw, B, Tx)
         ctx.save_for_backward(d_logw)
         return loss
 

@@ -14,14 +14,9 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
-from ._args import stream as _stream
+from ._args import call as _call, f32 as _f32
 
 __all__ = ["prior_loss", "align_segment", "duration_path", "compute_train_step_loss"]
-
-
-def _f32(t, dev):
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
 class _PriorLossFn(torch.autograd.Function):
@@ -32,9 +27,7 @@ class _PriorLossFn(torch.autograd.Function):
         yy, mu, m = _f32(y, dev), _f32(mu_y, dev), _f32(y_mask, dev)
         loss = torch.empty((), device=dev)
         d_mu = torch.empty_like(mu)
-        with torch.cuda.device(dev):
-            rc = _lib.load().us_prior_loss(yy.data_ptr(), mu.data_ptr(), m.data_ptr(), loss.data_ptr(), d_mu.data_ptr(), B, F, T, _stream())
-        _lib.check(rc, None, "us_prior_loss")
+        _call(dev, "us_prior_loss", yy, mu, m, loss, d_mu, B, F, T)
         ctx.save_for_backward(d_mu)
         return loss
 
@@ -59,10 +52,7 @@ class _SegmentAlignFn(torch.autograd.Function):
         y_cut = torch.empty(B, F, segment_size, device=dev)
         mu_y = torch.empty_like(y_cut)
         seg_mask = torch.empty(B, 1, segment_size, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().us_finetune_segment(cx.data_ptr(), yy.data_ptr(), at.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(),
-                                                 y_cut.data_ptr(), mu_y.data_ptr(), seg_mask.data_ptr(), B, F, Lu, Ly, segment_size, _stream())
-        _lib.check(rc, None, "us_finetune_segment")
+        _call(dev, "us_finetune_segment", cx, yy, at, meta[0], meta[1], y_cut, mu_y, seg_mask, B, F, Lu, Ly, segment_size)
         ctx.save_for_backward(at, meta)
         ctx.dims = (B, F, Lu, Ly, segment_size)
         ctx.mark_non_differentiable(y_cut, seg_mask)
@@ -76,10 +66,7 @@ class _SegmentAlignFn(torch.autograd.Function):
             return (None,) * 5
         g = _f32(g_mu, at.device)
         d_cx = torch.empty(B, F, Lu, device=at.device)
-        with torch.cuda.device(at.device):
-            rc = _lib.load().us_finetune_segment_backward(g.data_ptr(), at.data_ptr(), meta[0].data_ptr(), meta[1].data_ptr(), d_cx.data_ptr(),
-                                                          B, F, Lu, Ly, S, _stream())
-        _lib.check(rc, None, "us_finetune_segment_backward")
+        _call(at.device, "us_finetune_segment_backward", g, at, meta[0], meta[1], d_cx, B, F, Lu, Ly, S)
         return d_cx, None, None, None, None
 
 
@@ -93,10 +80,7 @@ def duration_path(durations, x_mask, y_lengths, T):
     dummy_x = torch.zeros(B, 1, L, device=dev)
     dummy_y = torch.empty(B, 1, T, device=dev)
     attn = torch.empty(B, L, T, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().us_tts_align(dummy_x.data_ptr(), w.data_ptr(), xm.data_ptr(), yl.data_ptr(), dummy_y.data_ptr(), attn.data_ptr(), None,
-                                      B, 1, L, T, _stream())
-    _lib.check(rc, None, "us_tts_align")
+    _call(dev, "us_tts_align", dummy_x, w, xm, yl, dummy_y, attn, None, B, 1, L, T)
     return attn
 
 

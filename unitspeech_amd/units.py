@@ -27,7 +27,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._args import i64 as _i64, need_gpu as _need_gpu, stream as _stream
+from ._args import call as _call, i64 as _i64, need_gpu as _need_gpu
 
 __all__ = ["KMeansQuantizer", "SpeechEncoder", "process_unit", "process_units_batch", "dedup_units", "lloyd_step", "kmeans_plusplus"]
 
@@ -35,8 +35,8 @@ MAX_K, MAX_D, MAX_SPAN = 2048, 1024, 64
 MAX_ROWS = 1 << 24                         # rows of one library call; more go in as a list of chunks
 
 
-def _workspace(lib, dev, B, Tmax, K, D, Lout):
-    n = int(lib.us_units_workspace_bytes(B, Tmax, K, D, Lout))
+def _workspace(dev, B, Tmax, K, D, Lout):
+    n = int(_lib.load().us_units_workspace_bytes(B, Tmax, K, D, Lout))
     if n == 0:
         raise ValueError(f"unit extraction: unsupported sizes B = {B}, T = {Tmax}, K = {K}, D = {D}, output frames = {Lout}")
     return torch.empty(n, dtype=torch.uint8, device=dev), n
@@ -127,14 +127,10 @@ class KMeansQuantizer(torch.nn.Module):
     def packed(self, dev):
         """The centres in the library's operand form on `dev` (packed once per device placement)."""
         if self._packed is None or self._packed.device != dev:
-            lib = _lib.load()
             K, D = self.centers.shape
-            c = self.centers.to(dev)
-            n = int(lib.us_units_packed_bytes(K, D))
+            n = int(_lib.load().us_units_packed_bytes(K, D))
             buf = torch.empty(n, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.us_units_pack_centers(c.data_ptr(), K, D, buf.data_ptr(), n, _stream())
-            _lib.check(rc, None, "us_units_pack_centers")
+            _call(dev, "us_units_pack_centers", self.centers.to(dev), K, D, buf, n)
             self._packed = buf
         return self._packed
 
@@ -159,13 +155,9 @@ class KMeansQuantizer(torch.nn.Module):
         units = torch.empty(B, T, dtype=torch.int64, device=dev)
         if B * T == 0:
             return units
-        lib = _lib.load()
-        ws, n = _workspace(lib, dev, B, T, K, D, 0)
+        ws, n = _workspace(dev, B, T, K, D, 0)
         self.last_counters = torch.empty(2, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.us_units_quantize(x.data_ptr(), lens.data_ptr(), self.packed(dev).data_ptr(), B, T, K, D, units.data_ptr(),
-                                       self.last_counters.data_ptr(), ws.data_ptr(), n, _stream())
-        _lib.check(rc, None, "us_units_quantize")
+        _call(dev, "us_units_quantize", x, lens, self.packed(dev), B, T, K, D, units, self.last_counters, ws, n)
         return units
 
     def forward(self, x):
@@ -182,18 +174,14 @@ class KMeansQuantizer(torch.nn.Module):
         sampling_rate, hop_length, spf = _check_rates(sampling_rate, hop_length)
         x, lens, B, T, K, D, dev = self._dense(dense, lengths)
         Lout = max(1, T * spf // hop_length)
-        lib = _lib.load()
-        ws, n = _workspace(lib, dev, B, T, K, D, Lout)
+        ws, n = _workspace(dev, B, T, K, D, Lout)
         unit = torch.empty(B, Lout, dtype=torch.int64, device=dev)
         dur = torch.empty(B, Lout, dtype=torch.int64, device=dev)
         dur_f = torch.empty(B, Lout, dtype=torch.float32, device=dev)
         n_out = torch.empty(B, dtype=torch.int64, device=dev)
         self.last_counters = torch.empty(2, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.us_units_encode(x.data_ptr(), lens.data_ptr(), self.packed(dev).data_ptr(), B, T, K, D, sampling_rate, hop_length,
-                                     unit.data_ptr(), dur.data_ptr(), dur_f.data_ptr(), n_out.data_ptr(), Lout,
-                                     self.last_counters.data_ptr(), ws.data_ptr(), n, _stream())
-        _lib.check(rc, None, "us_units_encode")
+        _call(dev, "us_units_encode", x, lens, self.packed(dev), B, T, K, D, sampling_rate, hop_length, unit, dur, dur_f, n_out, Lout,
+              self.last_counters, ws, n)
         return unit, dur_f, n_out
 
     # ---- fitting the centres (csrc/units_fit.hip) ---------------------------------------------------------------------------------
@@ -321,12 +309,8 @@ def dedup_units(units, lengths=None):
     n_out = torch.zeros(B, dtype=torch.int64, device=dev)
     if B * T == 0:
         return out_u, out_d, n_out
-    lib = _lib.load()
-    ws, n = _workspace(lib, dev, B, T, 0, 0, 0)
-    with torch.cuda.device(dev):
-        rc = lib.us_units_dedup(u.data_ptr(), lens.data_ptr(), B, T, out_u.data_ptr(), out_d.data_ptr(), n_out.data_ptr(), ws.data_ptr(), n,
-                                _stream())
-    _lib.check(rc, None, "us_units_dedup")
+    ws, n = _workspace(dev, B, T, 0, 0, 0)
+    _call(dev, "us_units_dedup", u, lens, B, T, out_u, out_d, n_out, ws, n)
     return out_u, out_d, n_out
 
 
@@ -355,12 +339,8 @@ def process_units_batch(units, durations, n_in, sampling_rate, hop_length, max_f
     n_out = torch.zeros(B, dtype=torch.int64, device=dev)
     if B * Lin == 0:
         return unit, dur, dur_f, n_out
-    lib = _lib.load()
-    ws, n = _workspace(lib, dev, B, Lin, 0, 0, Lout)
-    with torch.cuda.device(dev):
-        rc = lib.us_units_process(u.data_ptr(), d.data_ptr() if d is not None else None, lens.data_ptr(), B, Lin, sampling_rate, hop_length,
-                                  unit.data_ptr(), dur.data_ptr(), dur_f.data_ptr(), n_out.data_ptr(), Lout, ws.data_ptr(), n, _stream())
-    _lib.check(rc, None, "us_units_process")
+    ws, n = _workspace(dev, B, Lin, 0, 0, Lout)
+    _call(dev, "us_units_process", u, d, lens, B, Lin, sampling_rate, hop_length, unit, dur, dur_f, n_out, Lout, ws, n)
     return unit, dur, dur_f, n_out
 
 
@@ -484,18 +464,11 @@ class _FitState:
     def accumulate(self, x, labels, centers):
         rows = x.shape[0] * x.shape[1]
         ws = self.workspace(rows)
-        with torch.cuda.device(self.dev):
-            rc = self.lib.us_units_fit_accumulate(x.data_ptr(), labels.data_ptr(), centers.data_ptr(), rows, self.K, self.D, self.state.data_ptr(),
-                                                  self.nstate, ws.data_ptr(), ws.numel(), _stream())
-        _lib.check(rc, None, "us_units_fit_accumulate")
+        _call(self.dev, "us_units_fit_accumulate", x, labels, centers, rows, self.K, self.D, self.state, self.nstate, ws, ws.numel())
 
     def update(self, mode, centers_in, centers_out, totals_in, totals_out):
-        with torch.cuda.device(self.dev):
-            rc = self.lib.us_units_fit_update(mode, centers_in.data_ptr(), centers_out.data_ptr(),
-                                              None if totals_in is None else totals_in.data_ptr(),
-                                              None if totals_out is None else totals_out.data_ptr(), self.K, self.D, self.state.data_ptr(),
-                                              self.nstate, self.record.data_ptr(), _stream())
-        _lib.check(rc, None, "us_units_fit_update")
+        _call(self.dev, "us_units_fit_update", mode, centers_in, centers_out, totals_in, totals_out, self.K, self.D, self.state, self.nstate,
+              self.record)
         import numpy as np
         raw = self.record.cpu().numpy().tobytes()                  # the one read-back of an iteration
         f, i = np.frombuffer(raw, dtype="<f8"), np.frombuffer(raw, dtype="<i8")
@@ -510,19 +483,15 @@ def seed_uniforms(K: int, seed: int):
 
 def _seed_pp(x, lens, K, seed):
     dev, (B, T, D) = x.device, x.shape
-    lib = _lib.load()
-    n = int(lib.us_units_fit_workspace_bytes(B * T, K, D))
+    n = int(_lib.load().us_units_fit_workspace_bytes(B * T, K, D))
     if n == 0:
         raise ValueError(f"kmeans_plusplus: unsupported sizes rows = {B * T}, K = {K}, D = {D}")
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     mind = torch.empty(B * T, dtype=torch.float64, device=dev)
     centers = torch.zeros(K, D, dtype=torch.float32, device=dev)
     picked = torch.full((K,), -1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        for j, u in enumerate(seed_uniforms(K, seed)):
-            rc = lib.us_units_fit_seed_step(x.data_ptr(), lens.data_ptr(), B, T, K, D, j, float(u), mind.data_ptr(), centers.data_ptr(),
-                                            picked.data_ptr(), ws.data_ptr(), n, _stream())
-            _lib.check(rc, None, "us_units_fit_seed_step")
+    for j, u in enumerate(seed_uniforms(K, seed)):
+        _call(dev, "us_units_fit_seed_step", x, lens, B, T, K, D, j, float(u), mind, centers, picked, ws, n)
     return centers, picked
 
 

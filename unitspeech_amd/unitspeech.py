@@ -19,7 +19,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._args import stream as _stream
+from ._args import call as _call, stream as _stream
 from .util import fix_len_compatibility, generate_path, sequence_mask
 
 
@@ -382,14 +382,11 @@ class _ForwardDiffusionFn(torch.autograd.Function):
     """`forward_diffusion` (unitspeech/unitspeech.py:376-384) on the HIP library; z is the caller's gaussian draw."""
 
     @staticmethod
-    def forward(ctx, lib, x0, mask, t, z, beta_min, beta_max):
+    def forward(ctx, x0, mask, t, z, beta_min, beta_max):
         B, F, T = x0.shape
         xt, zm = torch.empty_like(x0), torch.empty_like(x0)
-        with torch.cuda.device(x0.device):
-            rc = lib.us_forward_diffusion(_dev_ptr(x0), _dev_ptr(mask), _dev_ptr(t), _dev_ptr(z), _dev_ptr(xt), _dev_ptr(zm), B, F, T,
-                                          beta_min, beta_max, _stream())
-        _lib.check(rc, None, "us_forward_diffusion")
-        ctx.lib, ctx.betas = lib, (beta_min, beta_max)
+        _call(x0.device, "us_forward_diffusion", x0, mask, t, z, xt, zm, B, F, T, beta_min, beta_max)
+        ctx.betas = (beta_min, beta_max)
         ctx.save_for_backward(mask, t)
         ctx.mark_non_differentiable(zm)
         return xt, zm
@@ -400,49 +397,40 @@ class _ForwardDiffusionFn(torch.autograd.Function):
         g = _f32c(g_xt, g_xt.device)
         B, F, T = g.shape
         out = torch.empty_like(g)
-        with torch.cuda.device(g.device):      # d xt / d x0 = exp(-c/2) * mask: the same kernel without the noise term
-            rc = ctx.lib.us_forward_diffusion(_dev_ptr(g), _dev_ptr(mask), _dev_ptr(t), None, _dev_ptr(out), None, B, F, T,
-                                              ctx.betas[0], ctx.betas[1], _stream())
-        _lib.check(rc, None, "us_forward_diffusion (backward)")
-        return None, out, None, None, None, None, None
+        # d xt / d x0 = exp(-c/2) * mask: the same kernel without the noise term
+        _call(g.device, "us_forward_diffusion", g, mask, t, None, out, None, B, F, T, *ctx.betas)
+        return out, None, None, None, None, None
 
 
 class _MulMaskFn(torch.autograd.Function):
     """`cond * mask` (:400) on [B, F, T]."""
 
     @staticmethod
-    def forward(ctx, lib, x, mask):
+    def forward(ctx, x, mask):
         B, F, T = x.shape
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            rc = lib.us_mul_mask(_dev_ptr(x), _dev_ptr(mask), _dev_ptr(out), B, F, T, _stream())
-        _lib.check(rc, None, "us_mul_mask")
-        ctx.lib = lib
+        _call(x.device, "us_mul_mask", x, mask, out, B, F, T)
         ctx.save_for_backward(mask)
         return out
 
     @staticmethod
     def backward(ctx, g):
         (mask,) = ctx.saved_tensors
-        return None, _MulMaskFn.apply(ctx.lib, _f32c(g, g.device), mask), None
+        return _MulMaskFn.apply(_f32c(g, g.device), mask), None
 
 
 class _DiffusionLossFn(torch.autograd.Function):
     """Score-matching objective of `loss_t` (:403-404) with its gradient w.r.t. the score, one fused pass."""
 
     @staticmethod
-    def forward(ctx, lib, score, zm, t, mask, beta_min, beta_max):
+    def forward(ctx, score, zm, t, mask, beta_min, beta_max):
         B, F, T = score.shape
         dev = score.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dscore = torch.empty_like(score)
-        nb = int(lib.us_diffusion_loss_scratch_bytes(B, F, T))
+        nb = int(_lib.load().us_diffusion_loss_scratch_bytes(B, F, T))
         scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.us_diffusion_loss(_dev_ptr(score), _dev_ptr(zm), _dev_ptr(t), _dev_ptr(mask), _dev_ptr(loss), _dev_ptr(dscore), B, F, T,
-                                       beta_min, beta_max, _dev_ptr(scratch), nb, _stream())
-        _lib.check(rc, None, "us_diffusion_loss")
-        ctx.lib = lib
+        _call(dev, "us_diffusion_loss", score, zm, t, mask, loss, dscore, B, F, T, beta_min, beta_max, scratch, nb)
         ctx.save_for_backward(dscore)
         return loss.view(())
 
@@ -451,10 +439,8 @@ class _DiffusionLossFn(torch.autograd.Function):
         (dscore,) = ctx.saved_tensors
         out = torch.empty_like(dscore)
         gs = _f32c(g.reshape(1), dscore.device)
-        with torch.cuda.device(dscore.device):
-            rc = ctx.lib.us_scale(_dev_ptr(dscore), _dev_ptr(gs), _dev_ptr(out), dscore.numel(), _stream())
-        _lib.check(rc, None, "us_scale")
-        return None, out, None, None, None, None, None
+        _call(dscore.device, "us_scale", dscore, gs, out, dscore.numel())
+        return out, None, None, None, None, None
 
 
 def _run_checked(eng, run, exact_engine, range_check, what):
@@ -788,19 +774,19 @@ class UnitSpeech(BaseModule):
         if dev.type != "cuda":
             raise RuntimeError("the HIP decoder needs tensors on a ROCm device (no CPU fallback); got " + str(dev))
         z = torch.randn(x0.shape, dtype=x0.dtype, device=dev, requires_grad=False)
-        return _ForwardDiffusionFn.apply(_lib.load(), _f32c(x0, dev), _f32c(mask, dev), _f32c(t, dev), _f32c(z, dev),
-                                         float(self.beta_min), float(self.beta_max))
+        return _ForwardDiffusionFn.apply(_f32c(x0, dev), _f32c(mask, dev), _f32c(t, dev), _f32c(z, dev), float(self.beta_min),
+                                         float(self.beta_max))
 
     def loss_t(self, x0, mask, cond, t, spk_emb):
         """`loss_t`, unitspeech/unitspeech.py:393-405: noising, conditioning mask, score network, objective -- four calls into
         the library, differentiable w.r.t. the decoder parameters and w.r.t. x0 / cond / spk_emb."""
-        lib, dev = _lib.load(), x0.device
+        dev = x0.device
         B, F, T = x0.shape
         _check_shapes(B, F, T, self.spk_uncon.shape[-1], cond=cond, mask=mask, spk_emb=spk_emb, t=t)
         mask_, t_ = _f32c(mask, dev), _f32c(t, dev)
         xt, z_masked = self.forward_diffusion(x0, mask_, t_)
-        score = self.estimator(xt, mask_, _MulMaskFn.apply(lib, _f32c(cond, dev), mask_), t_, spk_emb)
-        loss = _DiffusionLossFn.apply(lib, score, z_masked, t_, mask_, float(self.beta_min), float(self.beta_max))
+        score = self.estimator(xt, mask_, _MulMaskFn.apply(_f32c(cond, dev), mask_), t_, spk_emb)
+        loss = _DiffusionLossFn.apply(score, z_masked, t_, mask_, float(self.beta_min), float(self.beta_max))
         return loss, xt
 
     def compute_loss(self, x0, mask, cond, spk_emb=None, offset=1e-5):
@@ -840,11 +826,7 @@ class UnitSpeech(BaseModule):
                     tuple(seg_mask.shape) != (B, 1, segment_size):
                 raise ValueError("fine_tune_segment: `out` tensors have the wrong shapes")
         cx, yy, at = _f32c(cond_x, dev), _f32c(y, dev), _f32c(attn, dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().us_finetune_segment(_dev_ptr(cx), _dev_ptr(yy), _dev_ptr(at), _dev_ptr(meta[0]), _dev_ptr(meta[1]),
-                                                 _dev_ptr(y_seg), _dev_ptr(cond_y), _dev_ptr(seg_mask), B, n_feats, Lu, Ly,
-                                                 int(segment_size), _stream())
-        _lib.check(rc, None, "us_finetune_segment")
+        _call(dev, "us_finetune_segment", cx, yy, at, meta[0], meta[1], y_seg, cond_y, seg_mask, B, n_feats, Lu, Ly, int(segment_size))
         return y_seg, seg_mask, cond_y
 
     def fine_tune(self, cond_x, y, y_mask, y_lengths, y_max_length, attn, spk_emb, segment_size, n_feats):
@@ -866,7 +848,6 @@ class UnitSpeech(BaseModule):
         vocoder (inference.py:140).  return_lengths=True: a fourth result, `y_lengths` (int64 [B] on the device), the frames of each
         item: with B > 1 the outputs are cropped to the longest item, and a shorter one holds past its own end the image of masked
         zeros, which is not silence (`BigVGAN.forward(mel, lengths=y_lengths)` vocodes each item over its own frames)."""
-        lib = _lib.load()
         cond_x, x, x_mask = text_encoder(phoneme, phoneme_lengths)
         logw = duration_predictor(x, x_mask, w=None, g=spk_emb, reverse=True)
         dev = cond_x.device
@@ -874,18 +855,13 @@ class UnitSpeech(BaseModule):
         cx, lw, xm = _f32c(cond_x, dev), _f32c(logw, dev).reshape(B, L), _f32c(x_mask, dev).reshape(B, L)
         w_ceil = torch.empty(B, L, dtype=torch.float32, device=dev)
         y_lengths = torch.empty(B, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.us_tts_durations(_dev_ptr(lw), _dev_ptr(xm), _dev_ptr(w_ceil), _dev_ptr(y_lengths), B, L, float(length_scale), _stream())
-        _lib.check(rc, None, "us_tts_durations")
+        _call(dev, "us_tts_durations", lw, xm, w_ceil, y_lengths, B, L, float(length_scale))
         y_max_length = int(y_lengths.max())                                        # host sync, :428
         Tp = fix_len_compatibility(y_max_length, num_downsamplings_in_unet)
         cond_y = torch.empty(B, F, Tp, dtype=torch.float32, device=dev)
         attn = torch.empty(B, 1, L, Tp, dtype=torch.float32, device=dev)
         y_mask = torch.empty(B, 1, Tp, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.us_tts_align(_dev_ptr(cx), _dev_ptr(w_ceil), _dev_ptr(xm), _dev_ptr(y_lengths), _dev_ptr(cond_y), _dev_ptr(attn),
-                                  _dev_ptr(y_mask), B, F, L, Tp, _stream())
-        _lib.check(rc, None, "us_tts_align")
+        _call(dev, "us_tts_align", cx, w_ceil, xm, y_lengths, cond_y, attn, y_mask, B, F, L, Tp)
         z = torch.randn_like(cond_y, device=dev)                                    # RNG draw #0 of the reference (:441)
         dec = self.forward(z, y_mask, cond_y, spk_emb, n_timesteps=diffusion_steps, text_gradient_scale=text_gradient_scale,
                            spk_gradient_scale=spk_gradient_scale, mel_range=mel_range, **sampler_kw)
@@ -937,8 +913,5 @@ def vc_align(cond_x, x_lengths, y_lengths, Tp):
     meta = torch.tensor([xl, yl], dtype=torch.int64).to(dev)
     cond_y = torch.empty(B, F, Tp, dtype=torch.float32, device=dev)
     y_mask = torch.empty(B, 1, Tp, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().us_vc_align(_dev_ptr(cx), _dev_ptr(meta[0]), _dev_ptr(meta[1]), _dev_ptr(cond_y), _dev_ptr(y_mask), B, F, L, Tp,
-                                     _stream())
-    _lib.check(rc, None, "us_vc_align")
+    _call(dev, "us_vc_align", cx, meta[0], meta[1], cond_y, y_mask, B, F, L, Tp)
     return cond_y, y_mask, meta[1]

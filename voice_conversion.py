@@ -36,24 +36,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from unitspeech_amd.audio import read_wav  # noqa: E402
+from unitspeech_amd.batching import pad_batch, plan_batches  # noqa: E402
 
 VC_ENCODER = dict(n_channels=192, filter_channels=768, n_layers=6, kernel_size=3, p_dropout=0.1, n_heads=2, window_size=4,
                   n_contentvec=768)                     # unitspeech/checkpoints/voice-conversion.json "encoder"
 SAMPLING_RATE, HOP = 22050, 256
-
-
-def read_wav(path):
-    """-> (float32 mono waveform in [-1, 1], sampling rate) with scipy.io.wavfile."""
-    from scipy.io import wavfile
-    rate, data = wavfile.read(path)
-    if data.dtype.kind == "i":
-        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
-    elif data.dtype.kind == "u":
-        data = (data.astype(np.float32) - 128.0) / 128.0
-    data = data.astype(np.float32)
-    if data.ndim == 2:
-        data = data.mean(axis=1)
-    return np.ascontiguousarray(data), int(rate)
 
 
 def synthetic_sources(n: int, seed: int = 0):
@@ -67,14 +55,6 @@ def synthetic_sources(n: int, seed: int = 0):
         samples = int(g.integers(int(0.6 * SAMPLING_RATE), int(1.5 * SAMPLING_RATE))) + i
         out.append((f"synthetic_{i:04d}", synthetic_waveform(samples, seed * 1000 + i, SAMPLING_RATE)))
     return out
-
-
-def plan_batches(lengths, max_batch: int):
-    """Indices into `lengths`, sorted by length (ties in index order) and cut into batches of at most `max_batch`."""
-    if max_batch < 1:
-        raise ValueError("--batch must be at least 1")
-    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
-    return [order[i:i + max_batch] for i in range(0, len(order), max_batch)]
 
 
 class Pipeline:
@@ -97,10 +77,8 @@ class Pipeline:
         """waves: float32 arrays sampled at `rate` -> ([waveform [mel_length * hop] on the host per source], a dict of the batch's counts).
         With `sv56_ndb` the waveforms are the int16 of the level normalisation and the dict also holds level_db, gain, clipped and, with
         `keep_raw`, raw: the int16 waveforms before it."""
-        B, lens = len(waves), [len(w) for w in waves]
-        wav = torch.zeros(B, max(lens))
-        for b, w in enumerate(waves):
-            wav[b, :lens[b]] = torch.from_numpy(w)
+        B = len(waves)
+        wav, lens = pad_batch(waves)
         wav = wav.to(self.device)
         if rate != self.sampling_rate:
             r = self.resampler(rate, self.sampling_rate)
