@@ -5,6 +5,8 @@ its text by character and word error rate, compare its speaker embedding with th
     python evaluate.py --filelist LIST --ctc_path CTC.pt --vocab_path vocab.json [--config_path config.json]
                        [--speaker_encoder_path EMBEDDER.pt] [--batch 16] [--timestamps] [--out RESULT.json]
     python evaluate.py --synthetic 12 --batch 4
+    python evaluate.py --filelist LIST --recogniser whisper --whisper_checkpoint DIR [--language ro]
+    python evaluate.py --synthetic 6 --batch 4 --recogniser whisper
 
 LIST holds one `wav|transcript[|reference_wav]` line per sample.  CTC.pt is a `torch.save`d state dict of `transformers.HubertForCTC` or
 `Wav2Vec2ForCTC` in the base form (the class is taken from the keys; nothing is fetched by name; the base size unless --config_path
@@ -19,6 +21,13 @@ alignment of the text to the recogniser's log-probabilities (`align`); null for 
 ragged batches at the file's own rate and by the reference's int16 route (`unitspeech_amd.level.normalize_level(..., via_int16=True,
 out_int16=True)`), before the recogniser and the speaker encoder see it: the reference notebook's "with sv56" row.  The reference
 recordings of the third column are left as they are.
+
+--recogniser whisper transcribes with `unitspeech_amd.whisper.WhisperForConditionalGeneration` instead, as the reference's notebook does
+(`whisper.load_model("medium")`, `pad_or_trim`, `log_mel_spectrogram`, `decode` with default options: greedy, no timestamps).  DIR holds
+`config.json`, the weights (`pytorch_model.bin`, or `model.safetensors` where that package imports), `vocab.json` and `added_tokens.json`
+(and `generation_config.json` for the suppression lists).  The prompt is <|startoftranscript|>, the language, <|transcribe|>,
+<|notimestamps|>; without --language the language is detected per file.  The same length-sorted batches feed it; hypotheses and references are
+brought to lower-case letters, digits, apostrophes and single spaces before scoring.  Files longer than 30 s are refused.
 
 --synthetic N runs without files: a seeded tiny CTC model, N seeded waveforms, and as transcripts the model's own decodings with a known
 number of edits applied (characters appended, or cut from the end): the distance of each pair is then exactly that number, so the CER
@@ -171,6 +180,30 @@ def synthetic_model(device, seed: int = 0):
     return model.to(device).eval(), CTCVocabulary(TINY_VOCAB)
 
 
+TINY_WHISPER = dict(d_model=64, encoder_attention_heads=2, decoder_attention_heads=2, encoder_layers=2, decoder_layers=2, encoder_ffn_dim=128,
+                    decoder_ffn_dim=128, num_mel_bins=80, max_source_positions=1500, max_target_positions=32, vocab_size=36)
+
+
+def synthetic_whisper(device, seed: int = 0):
+    """A seeded tiny Whisper over the letters, the space and the special tokens, and its vocabulary."""
+    from unitspeech_amd.whisper import WhisperForConditionalGeneration, WhisperVocabulary, synthetic_whisper_state_dict
+    vocab = {**{c: i for i, c in enumerate("abcdefghijklmnopqrstuvwxyz")}, "\u0120": 26}          # GPT-2's spelling of the space
+    added = {t: 27 + i for i, t in enumerate(("<|endoftext|>", "<|startoftranscript|>", "<|ro|>", "<|en|>", "<|transcribe|>", "<|notimestamps|>"))}
+    vocabulary = WhisperVocabulary(vocab, added)
+    model = WhisperForConditionalGeneration(**TINY_WHISPER, eos_token_id=vocabulary.end_id, suppress_tokens=sorted(added.values())[1:])
+    model.load_state_dict(synthetic_whisper_state_dict(TINY_WHISPER, seed))
+    return model.to(device).eval(), vocabulary
+
+
+def whisper_prompt(model, vocabulary, language):
+    """The notebook's default options: transcribe, no timestamps; the language given, or detected among the vocabulary's."""
+    model.prompt_ids = [vocabulary.start_id, vocabulary.language_id(language) if language else None, vocabulary.transcribe_id,
+                        vocabulary.notimestamps_id]
+    model.language_ids = vocabulary.language_ids()
+    if model.eos_token_id is None:
+        model.eos_token_id = vocabulary.end_id
+
+
 def synthetic_waves(n: int, seed: int = 0):
     from unitspeech_amd.mel import synthetic_waveform
     if n < 1:
@@ -186,6 +219,9 @@ def main(argv=None):
     ap.add_argument("--ctc_path", default=None, help="state dict of a HubertForCTC / Wav2Vec2ForCTC (base form)")
     ap.add_argument("--vocab_path", default=None, help="the tokenizer's vocab.json")
     ap.add_argument("--config_path", default=None, help="the model's config.json, when it is not the base size")
+    ap.add_argument("--recogniser", choices=("ctc", "whisper"), default="ctc")
+    ap.add_argument("--whisper_checkpoint", default=None, help="--recogniser whisper: directory with config.json, weights, vocab.json, added_tokens.json")
+    ap.add_argument("--language", default=None, help="--recogniser whisper: the language token's name (ro); detected per file when absent")
     ap.add_argument("--blank", default="<pad>")
     ap.add_argument("--word_delimiter", default="|")
     ap.add_argument("--normalize", action="store_true", help="zero mean, unit variance per waveform (a feature extractor with do_normalize)")
@@ -204,23 +240,34 @@ def main(argv=None):
     from unitspeech_amd.asr import CTCVocabulary, error_rates, load_ctc_checkpoint, normalize_text
     device = torch.device(args.device)
     resamplers, embedder = {}, None
+    whisper = args.recogniser == "whisper"
+    if whisper and (args.timestamps or args.normalize):
+        raise SystemExit("--timestamps and --normalize belong to the CTC recogniser")
     if args.synthetic:
-        model, vocabulary = synthetic_model(device, args.seed)
+        model, vocabulary = synthetic_whisper(device, args.seed) if whisper else synthetic_model(device, args.seed)
         items = synthetic_waves(args.synthetic, args.seed)
         transcripts, references = None, [None] * len(items)
     else:
-        if not args.filelist or not args.ctc_path or not args.vocab_path:
+        if whisper and not (args.filelist and args.whisper_checkpoint):
+            raise SystemExit("--recogniser whisper: give --filelist and --whisper_checkpoint, or --synthetic N")
+        if not whisper and (not args.filelist or not args.ctc_path or not args.vocab_path):
             raise SystemExit("give --filelist, --ctc_path and --vocab_path, or --synthetic N")
         with open(args.filelist, encoding="utf-8") as f:
             entries = parse_filelist(f.read())
         if not entries:
             raise SystemExit(f"{args.filelist}: no files")
-        vocabulary = CTCVocabulary(args.vocab_path, args.blank, args.word_delimiter)
-        config = {}
-        if args.config_path:
-            with open(args.config_path, encoding="utf-8") as f:
-                config = {k: v for k, v in json.load(f).items() if k not in ("vocab_size", "pad_token_id")}
-        model = load_ctc_checkpoint(args.ctc_path, pad_token_id=vocabulary.blank_id, **config).to(device)
+        if whisper:
+            from unitspeech_amd.whisper import WhisperVocabulary, load_whisper_checkpoint
+            added = os.path.join(args.whisper_checkpoint, "added_tokens.json")
+            vocabulary = WhisperVocabulary(os.path.join(args.whisper_checkpoint, "vocab.json"), added if os.path.exists(added) else None)
+            model = load_whisper_checkpoint(args.whisper_checkpoint).to(device)
+        else:
+            vocabulary = CTCVocabulary(args.vocab_path, args.blank, args.word_delimiter)
+            config = {}
+            if args.config_path:
+                with open(args.config_path, encoding="utf-8") as f:
+                    config = {k: v for k, v in json.load(f).items() if k not in ("vocab_size", "pad_token_id")}
+            model = load_ctc_checkpoint(args.ctc_path, pad_token_id=vocabulary.blank_id, **config).to(device)
         items = [(path,) + read_wav(path) for path, _, _ in entries]
         transcripts = [normalize_text(text, vocabulary) for _, text, _ in entries]
         references = [ref for _, _, ref in entries]
@@ -237,10 +284,15 @@ def main(argv=None):
         if w.shape[0] < MIN_SAMPLES_16K:
             raise SystemExit(f"{name}: {w.shape[0]} samples at 16 kHz are fewer than the receptive field ({MIN_SAMPLES_16K})")
         wavs16.append(w)
-    model.pad_token_id = vocabulary.blank_id
+    if whisper:
+        whisper_prompt(model, vocabulary, args.language)
+    else:
+        model.pad_token_id = vocabulary.blank_id
     if args.normalize:
         wavs16 = [(w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7) for w in wavs16]
     hyps, batches = transcribe_all(model, vocabulary, wavs16, args.batch)
+    if whisper:
+        hyps = [normalize_text(h, vocabulary) for h in hyps]
     result = {}
     if args.synthetic:
         transcripts = [apply_edits(h, SYNTHETIC_EDITS, cut=bool(i & 1)) for i, h in enumerate(hyps)]

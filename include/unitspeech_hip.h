@@ -726,6 +726,57 @@ int us_wavlm_forward(us_wavlm_handle h, const float* wav, const int64_t* lengths
                      float* hidden_states, int64_t hs_item_stride, int64_t hs_layer_stride, void* workspace, size_t workspace_bytes,
                      us_stream stream);
 
+/* ---- Whisper recogniser (transformers.WhisperForConditionalGeneration, eval mode), csrc/whisper.hip + the encoder schedule in csrc/hubert.hip --
+ * log-mel features [B][n_mels][2 S] (S = max_source_positions) -> encoder hidden states, teacher-forced logits, or greedy token ids.  fp32
+ * storage and exact-fp32 products on the matrix cores.  The model, as transformers computes it:
+ *   encoder stem: GELU(conv1) (k 3, padding 1), GELU(conv2) (k 3, stride 2, padding 1), + embed_positions; the input has exactly 2 S frames;
+ *   encoder layers, then layer_norm: x += out_proj(attn(LN(x))) with q scaled by d_head^-1/2 and k_proj without bias, x += fc2(GELU(fc1(LN(x))));
+ *     GELU is the erf form, LayerNorm's eps is 1e-5;
+ *   decoder input: embed_tokens[id] + embed_positions[pos];
+ *   decoder layers: pre-LN causal self-attention, pre-LN cross-attention over the encoder's output, pre-LN MLP;
+ *   decoder end: layer_norm, then logits = h . embed_tokens^T.
+ * Weights go in by the state_dict keys model.encoder.* and model.decoder.* (us_whisper_weight_key lists them); proj_out.weight is the tied
+ * model.decoder.embed_tokens.weight and is not taken.  Same conventions as the other weight-table handles: us_whisper_create touches no
+ * device, the caller owns the scratch (us_whisper_workspace_bytes(h, B), 0 for B outside [1, 65535]), the computing calls allocate nothing and
+ * enqueue on `stream` (us_whisper_generate also waits for the stream every 8 steps, to read how many items still run), a call made while
+ * another device than the handle's is current is refused (US_EINVAL), and an item alone or in a batch, and repeated calls, give the same bits
+ * (logits and tokens).
+ * us_whisper_create returns US_EINVAL for a d_model the heads do not divide, a head dimension above 64 or not a multiple of 4, a decoder
+ * feed-forward size that is no multiple of 4, and max_source_positions or max_target_positions above 2048.
+ * Not built: the timestamp-token rules (callers put <|notimestamps|> in the prompt), beam search, temperature fallback, fp16 weights. */
+typedef struct us_whisper* us_whisper_handle;
+typedef struct us_whisper_config {
+  int32_t n_mels;
+  int32_t d_model;
+  int32_t encoder_layers, encoder_heads, encoder_ffn;
+  int32_t decoder_layers, decoder_heads, decoder_ffn;
+  int32_t max_source_positions;      /* S */
+  int32_t max_target_positions;
+  int32_t vocab_size;
+} us_whisper_config;
+int us_whisper_create(us_whisper_handle* out, const us_whisper_config* cfg);
+int us_whisper_destroy(us_whisper_handle h);
+int us_whisper_load_weight(us_whisper_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream);
+int us_whisper_num_weights(us_whisper_handle h);
+const char* us_whisper_weight_key(us_whisper_handle h, int i);
+const char* us_whisper_last_error(us_whisper_handle h);
+size_t us_whisper_workspace_bytes(us_whisper_handle h, int B);
+/* features [B][n_mels][T] (device), T = 2 S else US_EINVAL -> out [B][S][d_model], the encoder's last hidden state */
+int us_whisper_encode(us_whisper_handle h, const float* features, int B, int T, float* out, void* workspace, size_t workspace_bytes,
+                      us_stream stream);
+/* teacher forcing: ids HOST int64 [B][N], 1 <= N <= max_target_positions, every id in [0, vocab_size) else US_EINVAL -> logits
+ * [B][N][vocab_size] (device), row t the distribution of the token after ids[.][0 .. t].  The positions are walked one by one through the
+ * kernels of us_whisper_generate, so these are the bits the greedy loop sees. */
+int us_whisper_decoder_logits(us_whisper_handle h, const float* features, int B, int T, const int64_t* ids, int N, float* logits,
+                              void* workspace, size_t workspace_bytes, us_stream stream);
+/* greedy decoding: prompt HOST int64 [B][P] (P >= 1, teacher-forced), at most max_new tokens per item with P + max_new <=
+ * max_target_positions, ended by eos.  suppress / begin_suppress: device bytes [vocab_size] or NULL, non-zero = the token is never chosen /
+ * not chosen at the first generated position.  -> tokens [B][max_new] int64 (device), eos at and after an item's end, and n [B] int64, the
+ * tokens in front of it.  The token is torch.argmax's: the lower index on an exact tie. */
+int us_whisper_generate(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P, int max_new, int64_t eos,
+                        const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* tokens, int64_t* n, void* workspace,
+                        size_t workspace_bytes, us_stream stream);
+
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102
  * `process_unit`) as handle-free device calls.  Every call only enqueues on `stream`, allocates nothing and takes device scratch of

@@ -1,5 +1,5 @@
 """`HandleModule`: a torch module whose arithmetic lives behind one opaque handle of the HIP library that takes its weights by
-state_dict key (csrc/handle.h: us_frontend, us_vocoder, us_speaker, us_mel, us_resample, us_hubert, us_wavlm).  It owns the handle, pushes the weights whose storage or version
+state_dict key (csrc/handle.h: us_frontend, us_vocoder, us_speaker, us_mel, us_resample, us_hubert, us_wavlm, us_whisper).  It owns the handle, pushes the weights whose storage or version
 changed since the last call, keeps the caller-owned workspace, and makes the library calls of a forward (`_call`: the handle's device
 current, the return code checked under the symbol's name).  Per-item lengths reach those calls through `_args`."""
 from __future__ import annotations
@@ -13,7 +13,7 @@ from . import _lib
 
 
 class HandleModule(torch.nn.Module):
-    _abi = ""                  # "frontend" / "vocoder" / "speaker" / "mel" / "resample" / "hubert" / "wavlm": us_{_abi}_load_weight, _last_error, _destroy, _workspace_bytes
+    _abi = ""                  # "frontend" / "vocoder" / "speaker" / "mel" / "resample" / "hubert" / "wavlm" / "whisper": us_{_abi}_load_weight, _last_error, _destroy, _workspace_bytes
     _what = ""                 # how the module calls itself when it refuses a device
     _cache_sources = False     # True: _sources() is walked once, and again after .to() / .float() (for a module whose parameters
                                # are never registered anew; state_dict() of a few hundred entries is not free next to a short forward)

@@ -72,6 +72,11 @@ class us_wavlm_config(C.Structure):
     _fields_ = us_hubert_config._fields_ + [(n, C.c_int32) for n in ("conv_bias", "num_buckets", "max_bucket_distance")]
 
 
+class us_whisper_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "d_model", "encoder_layers", "encoder_heads", "encoder_ffn", "decoder_layers", "decoder_heads",
+                                         "decoder_ffn", "max_source_positions", "max_target_positions", "vocab_size")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -184,6 +189,13 @@ SIGNATURES = {
     "us_wavlm_position_bucket": (C.c_int, [C.c_void_p, C.c_int64]),
     "us_wavlm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_whisper_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_whisper_config)]),
+    "us_whisper_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "us_whisper_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_whisper_decoder_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_void_p]),
+    "us_whisper_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
@@ -228,16 +240,16 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "us_last_error": (C.c_char_p, [C.c_void_p]),
 }
-# what the seven weight-table handles (csrc/handle.h) share
-for _p in ("frontend", "vocoder", "speaker", "mel", "resample", "hubert", "wavlm"):
+# what the eight weight-table handles (csrc/handle.h) share; us_whisper_workspace_bytes takes the batch alone and stands above
+for _p in ("frontend", "vocoder", "speaker", "mel", "resample", "hubert", "wavlm", "whisper"):
     SIGNATURES.update({
         f"us_{_p}_destroy": (C.c_int, [C.c_void_p]),
         f"us_{_p}_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
         f"us_{_p}_num_weights": (C.c_int, [C.c_void_p]),
         f"us_{_p}_weight_key": (C.c_char_p, [C.c_void_p, C.c_int]),
         f"us_{_p}_last_error": (C.c_char_p, [C.c_void_p]),
-        f"us_{_p}_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     })
+    SIGNATURES.setdefault(f"us_{_p}_workspace_bytes", (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]))
 
 _lock = threading.Lock()
 _lib = None

@@ -1,4 +1,4 @@
-// The host plumbing every handle that takes its weights by state_dict key shares (us_frontend, us_vocoder, us_speaker, us_mel, us_resample, us_hubert, us_wavlm): the weight
+// The host plumbing every handle that takes its weights by state_dict key shares (us_frontend, us_vocoder, us_speaker, us_mel, us_resample, us_hubert, us_wavlm, us_whisper): the weight
 // table with its error reporting, device binding and load_weight prefix, and the small workspace helpers that came with each copy.  The
 // decoder's handle (deferred raw copies and a flush) is a different design and does not use this.
 #pragma once

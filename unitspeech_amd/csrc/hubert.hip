@@ -37,6 +37,7 @@
 #include "handle.h"
 #include "item_lens.h"
 #include "kernels.h"
+#include "whisper_encoder.h"
 
 namespace us {
 namespace {
@@ -651,6 +652,7 @@ struct HbGemm {                 // one launch of hb_gemm_kernel
   float* out;
   int Tin, Tout, stride = 1, groups = 1, gelu = 0, nscale = 0, level = 0;
   float scale = 1.f;
+  long long res_bs = -1;        // the residual's item stride when it is not the output's (0: one tensor for every item)
 };
 
 void hb_gemm(hipStream_t s, const HbGemm& g, const HbLens& lens, int nb) {
@@ -659,6 +661,7 @@ void hb_gemm(hipStream_t s, const HbGemm& g, const HbLens& lens, int nb) {
   a.in = g.in; a.w = c.packed; a.bias = g.bias; a.res = g.res; a.out = g.out;
   a.in_bs = (long long)c.cin * g.groups * g.Tin;
   a.out_bs = a.res_bs = (long long)c.cout * g.groups * g.Tout;
+  if (g.res_bs >= 0) a.res_bs = g.res_bs;
   a.Cin = c.cin; a.Cout = c.cout; a.Tin = g.Tin; a.Tout = g.Tout; a.off = c.off[0]; a.Kdim = c.Kdim(); a.Kpad = c.Kpad; a.ldw = c.ldw;
   a.gelu = g.gelu; a.nscale = g.nscale; a.scale = g.scale; a.level = g.level;
   a.mtiles = (c.cout + kPcBM - 1) / kPcBM;
@@ -976,6 +979,236 @@ int hb_forward(HbModel* h, const std::string& what, const float* wav, const int6
 }
 
 }  // namespace
+
+// ---- Whisper's encoder (whisper_encoder.h; us_whisper_* in whisper.hip) on the kernels above -----------------------------------------------------
+// GELU(conv1) (k 3, padding 1), GELU(conv2) (k 3, stride 2, padding 1) + embed_positions in the GEMM's epilogue, WavLM-large's pre-LN layer
+// schedule without the relative position bias, encoder.layer_norm.  Every item has S frames: the length carrier holds S (2 S for conv1).
+struct WhEncoder {
+  WhEncGeometry g{};
+  PlanarConv conv1, conv2;
+  std::vector<HbLayer> layers;
+  std::vector<PlanarConv> cross;      // per decoder layer: [k_proj | v_proj] of the encoder's output
+  std::vector<float*> cross_w, cross_b;
+  float* pos = nullptr;               // embed_positions as a planar [d_model][S] tensor
+};
+
+namespace {
+std::string wh_enc_key(int i) { return "model.encoder.layers." + std::to_string(i) + "."; }
+std::string wh_cross_key(int i) { return "model.decoder.layers." + std::to_string(i) + ".encoder_attn."; }
+
+HbLens wh_lens(int n) {
+  HbLens l{};
+  for (int i = 0; i < kHbItems; ++i) l.n[i] = n;
+  for (int i = 0; i < kHbMaxConv; ++i) l.k[i] = l.s[i] = 1;
+  return l;
+}
+}  // namespace
+
+WhEncoder* wh_encoder_new(const WhEncGeometry& g) {
+  auto* e = new WhEncoder();
+  e->g = g;
+  const int H = g.d_model;
+  e->conv1.conv(g.n_mels, g.n_mels, H, 3, 1);
+  e->conv2.conv(H, H, H, 3, 1);
+  e->layers.resize(g.layers);
+  for (auto& l : e->layers) {
+    l.qkv.conv(H, H, 3 * H, 1, 1);
+    l.out.conv(H, H, H, 1, 1);
+    l.ff1.conv(H, H, g.ffn, 1, 1);
+    l.ff2.conv(g.ffn, g.ffn, H, 1, 1);
+  }
+  e->cross.resize(g.dec_layers);
+  for (auto& c : e->cross) c.conv(H, H, 2 * H, 1, 1);
+  e->cross_w.assign(g.dec_layers, nullptr);
+  e->cross_b.assign(g.dec_layers, nullptr);
+  return e;
+}
+
+void wh_encoder_free(WhEncoder* e) {
+  if (!e) return;
+  e->conv1.release();
+  e->conv2.release();
+  for (auto& l : e->layers) {
+    l.qkv.release();
+    l.out.release();
+    l.ff1.release();
+    l.ff2.release();
+    if (l.qkv_w) (void)hipFree(l.qkv_w);
+    if (l.qkv_b) (void)hipFree(l.qkv_b);
+  }
+  for (auto& c : e->cross) c.release();
+  for (float* p : e->cross_w)
+    if (p) (void)hipFree(p);
+  for (float* p : e->cross_b)
+    if (p) (void)hipFree(p);
+  if (e->pos) (void)hipFree(e->pos);
+  delete e;
+}
+
+hipError_t wh_encoder_alloc(WhEncoder* e) {
+  hipError_t err = hipSuccess;
+  auto alloc = [&](float** p, size_t n) {
+    if (err == hipSuccess && !*p) err = hipMalloc(p, std::max<size_t>(n, 1) * sizeof(float));
+  };
+  const size_t H = (size_t)e->g.d_model;
+  alloc(&e->conv1.packed, e->conv1.packed_floats());
+  alloc(&e->conv2.packed, e->conv2.packed_floats());
+  alloc(&e->pos, H * e->g.S);
+  for (auto& l : e->layers) {
+    alloc(&l.qkv.packed, l.qkv.packed_floats());
+    alloc(&l.out.packed, l.out.packed_floats());
+    alloc(&l.ff1.packed, l.ff1.packed_floats());
+    alloc(&l.ff2.packed, l.ff2.packed_floats());
+    alloc(&l.qkv_w, 3 * H * H);
+    alloc(&l.qkv_b, 3 * H);
+  }
+  for (int i = 0; i < e->g.dec_layers; ++i) {
+    alloc(&e->cross[i].packed, e->cross[i].packed_floats());
+    alloc(&e->cross_w[i], 2 * H * H);
+    alloc(&e->cross_b[i], 2 * H);
+  }
+  return err;
+}
+
+hipError_t wh_encoder_prepare(WhEncoder* e, WeightTable& t, hipStream_t s) {
+  auto W = [&](const std::string& k) { return t.w.at(k).dev; };
+  const size_t H = (size_t)e->g.d_model, S = (size_t)e->g.S;
+  hipError_t err = hipSuccess;
+  auto copy = [&](float* dst, const float* src, size_t n) {
+    if (err == hipSuccess) err = src ? hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s) : hipMemsetAsync(dst, 0, n * sizeof(float), s);
+  };
+  e->conv1.pack(W("model.encoder.conv1.weight"), s);
+  e->conv2.pack(W("model.encoder.conv2.weight"), s);
+  // embed_positions [S][H] read as a planar [C = S][T = H] tensor: its channel-last copy is [H][S]
+  hipLaunchKernelGGL(hb_export_kernel, dim3((unsigned)((H + kLnCols - 1) / kLnCols), (unsigned)((S + kLnSlices - 1) / kLnSlices), 1), dim3(1024), 0, s,
+                     W("model.encoder.embed_positions.weight"), e->pos, (float*)nullptr, 0ll, 0ll, (int)S, (int)H);
+  for (int i = 0; i < e->g.layers; ++i) {
+    HbLayer& l = e->layers[i];
+    const std::string a = wh_enc_key(i) + "self_attn.";
+    copy(l.qkv_w, W(a + "q_proj.weight"), H * H);
+    copy(l.qkv_w + H * H, W(a + "k_proj.weight"), H * H);
+    copy(l.qkv_w + 2 * H * H, W(a + "v_proj.weight"), H * H);
+    copy(l.qkv_b, W(a + "q_proj.bias"), H);
+    copy(l.qkv_b + H, nullptr, H);
+    copy(l.qkv_b + 2 * H, W(a + "v_proj.bias"), H);
+    if (err != hipSuccess) return err;
+    l.qkv.pack(l.qkv_w, s);
+    l.out.pack(W(a + "out_proj.weight"), s);
+    l.ff1.pack(W(wh_enc_key(i) + "fc1.weight"), s);
+    l.ff2.pack(W(wh_enc_key(i) + "fc2.weight"), s);
+  }
+  for (int i = 0; i < e->g.dec_layers; ++i) {
+    const std::string a = wh_cross_key(i);
+    copy(e->cross_w[i], W(a + "k_proj.weight"), H * H);
+    copy(e->cross_w[i] + H * H, W(a + "v_proj.weight"), H * H);
+    copy(e->cross_b[i], nullptr, H);
+    copy(e->cross_b[i] + H, W(a + "v_proj.bias"), H);
+    if (err != hipSuccess) return err;
+    e->cross[i].pack(e->cross_w[i], s);
+  }
+  return hipGetLastError();
+}
+
+namespace {
+struct WhEncPlan {
+  size_t c1, x, x2, x1, y, qkv, att, ff, total;
+};
+WhEncPlan wh_enc_plan(const WhEncGeometry& g, int B) {
+  WhEncPlan p{};
+  WsTake take;
+  const size_t bs = (size_t)B * g.S, H = (size_t)g.d_model;
+  p.c1 = take(2 * bs * H);
+  p.x = take(bs * H);
+  p.x2 = take(bs * H);
+  p.x1 = take(bs * H);
+  p.y = take(bs * H);
+  p.qkv = take(3 * bs * H);
+  p.att = take(bs * H);
+  p.ff = take(bs * (size_t)g.ffn);
+  p.total = take.total;
+  return p;
+}
+}  // namespace
+
+size_t wh_encoder_ws_floats(const WhEncoder* e, int B) { return wh_enc_plan(e->g, B).total; }
+
+hipError_t wh_encoder_forward(WhEncoder* e, WeightTable& t, const float* feats, int B, float* planar, float* out, float* ws, hipStream_t s) {
+  auto W = [&](const std::string& k) { return t.w.at(k).dev; };
+  const WhEncGeometry& g = e->g;
+  const int H = g.d_model, S = g.S, I = g.ffn, d = H / g.heads;
+  const size_t sh = (size_t)S * H;
+  const WhEncPlan p = wh_enc_plan(g, B);
+  const HbLens lens = wh_lens(S), lens2 = wh_lens(2 * S);
+  for (int b0 = 0; b0 < B; b0 += kHbItems) {
+    const int nb = std::min(kHbItems, B - b0);
+    float* C1 = ws + p.c1 + 2 * b0 * sh;
+    float* X = ws + p.x + b0 * sh;
+    float* X2 = ws + p.x2 + b0 * sh;
+    float* X1 = ws + p.x1 + b0 * sh;
+    float* Y = ws + p.y + b0 * sh;
+    float* QKV = ws + p.qkv + 3 * b0 * sh;
+    float* ATT = ws + p.att + b0 * sh;
+    float* FF = ws + p.ff + (size_t)b0 * S * I;
+    auto ln_launch = [&](const float* in, const std::string& key, float* y, float* e2) {
+      hipLaunchKernelGGL(hb_ln_kernel, dim3((S + kLnCols - 1) / kLnCols, nb), dim3(1024), 0, s, in, (const float*)nullptr, W(key + ".weight"),
+                         W(key + ".bias"), y, (float*)nullptr, e2, 0ll, (long long)sh, lens, 0, H, S, 1e-5f, 0);
+    };
+    {
+      HbGemm c{&e->conv1, feats + (size_t)b0 * g.n_mels * 2 * S, W("model.encoder.conv1.bias"), nullptr, C1, 2 * S, 2 * S};
+      c.gelu = 1;
+      hb_gemm(s, c, lens2, nb);
+    }
+    {
+      HbGemm c{&e->conv2, C1, W("model.encoder.conv2.bias"), e->pos, X, 2 * S, S};
+      c.stride = 2; c.gelu = 1; c.res_bs = 0;
+      hb_gemm(s, c, lens, nb);
+    }
+    float* St = X;
+    float* St2 = X2;
+    for (int i = 0; i < g.layers; ++i) {
+      const HbLayer& l = e->layers[i];
+      const std::string q = wh_enc_key(i);
+      ln_launch(St, q + "self_attn_layer_norm", X1, nullptr);
+      {
+        HbGemm c{&l.qkv, X1, l.qkv_b, nullptr, QKV, S, S};
+        c.nscale = H; c.scale = 1.f / sqrtf((float)d);
+        hb_gemm(s, c, lens, nb);
+      }
+      hb_attn(s, QKV, ATT, lens, 0, H, g.heads, d, S, nb, nullptr, nullptr, 0);
+      {
+        HbGemm c{&l.out, ATT, W(q + "self_attn.out_proj.bias"), St, Y, S, S};
+        hb_gemm(s, c, lens, nb);
+      }
+      ln_launch(Y, q + "final_layer_norm", X1, nullptr);
+      {
+        HbGemm c{&l.ff1, X1, W(q + "fc1.bias"), nullptr, FF, S, S};
+        c.gelu = 1;
+        hb_gemm(s, c, lens, nb);
+      }
+      {
+        HbGemm c{&l.ff2, FF, W(q + "fc2.bias"), Y, St2, S, S};
+        hb_gemm(s, c, lens, nb);
+      }
+      std::swap(St, St2);
+    }
+    ln_launch(St, "model.encoder.layer_norm", planar + b0 * sh, out ? out + b0 * sh : nullptr);
+  }
+  return hipGetLastError();
+}
+
+hipError_t wh_encoder_cross_kv(WhEncoder* e, WeightTable& t, const float* planar, int B, float* kv, hipStream_t s) {
+  const WhEncGeometry& g = e->g;
+  const size_t sh = (size_t)g.S * g.d_model;
+  const HbLens lens = wh_lens(g.S);
+  for (int i = 0; i < g.dec_layers; ++i)
+    for (int b0 = 0; b0 < B; b0 += kHbItems) {
+      const int nb = std::min(kHbItems, B - b0);
+      HbGemm c{&e->cross[i], planar + b0 * sh, e->cross_b[i], nullptr, kv + ((size_t)i * B + b0) * 2 * sh, g.S, g.S};
+      hb_gemm(s, c, lens, nb);
+    }
+  return hipGetLastError();
+}
+
 }  // namespace us
 
 extern "C" {

@@ -1,0 +1,651 @@
+// Whisper (transformers.WhisperForConditionalGeneration, eval mode): log-mel features [B][n_mels][2 S] -> encoder -> greedy decoder -> token
+// ids.  fp32 storage and exact-fp32 products (v_mfma_f32_16x16x4_f32 in the decoder's GEMMs) throughout.
+//
+// The encoder and the cross-attention keys / values run on hubert.hip's kernels (whisper_encoder.h).  This file is the decoder step: up to
+// kWhItems items of one launch group advance by one position per step, one row each.
+//  - wh_embed_kernel: x[m] = embed_tokens[token] + embed_positions[pos]; the token is the host's (prompt, teacher forcing) or the one the
+//    last wh_argmax_kernel chose.
+//  - wh_gemm_kernel: the skinny GEMM y[m][n] = post(sum_k pre(x)[m][k] W[n][k]) for M <= 16 rows, the rows padded to the 16 columns of the
+//    MFMA with zeros.  A workgroup is 16 outputs n; its four waves take the k range in interleaved slices of 16 and their partial sums meet in
+//    LDS in wave order, so the weights are read once and an element's summation order depends on K alone, not on M or on the row's place.
+//    pre: LayerNorm of the row (two-pass, fixed order, recomputed per workgroup: K floats per row).  post: + bias, * scale, GELU, + residual.
+//    Up to three weight matrices share one launch (q | k | v: blockIdx.y), each with its own output: k and v go straight into the self cache.
+//  - wh_self_attn_kernel: one query of an (item, head) over the item's self cache [layer][item][2][max_target_positions][d_model], one wave.
+//  - wh_cross_attn_kernel: one query over the item's planar cross keys / values [layer][item][2 d_model][S], sixteen waves.
+//  - wh_argmax_kernel: the suppression masks, then (value, index) argmax per item with the lower index on exact ties (torch.argmax), the end of
+//    an item (eos) and the count of items still running.
+// No kernel waits on a value another kernel writes; the host loop runs at most max_new steps and reads the running count back every
+// kWhPoll steps.  Every reduction has a fixed order and no launch depends on the batch: an item alone or in a batch, and repeated calls, give
+// the same bits.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/unitspeech_hip.h"
+#include "handle.h"
+#include "item_lens.h"
+#include "kernels.h"
+#include "whisper_encoder.h"
+
+namespace us {
+namespace {
+
+constexpr int kWhItems = 16;        // items (rows) per launch group: the columns of one 16x16x4 MFMA
+constexpr int kWhPoll = 8;          // generate: steps between two reads of the running count
+constexpr int kWhMaxKeys = 2048;    // keys one attention workgroup holds in LDS (S and max_target_positions)
+
+struct WhTokens {                   // the host's token of each row of the group, or -1: take the one argmax chose
+  int id[kWhItems];
+};
+
+__device__ __forceinline__ float wh_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+
+__global__ __launch_bounds__(256) void wh_embed_kernel(const float* __restrict__ emb, const float* __restrict__ pos, const int* __restrict__ cur,
+                                                       WhTokens forced, float* __restrict__ x, int H, int p) {
+  const int m = blockIdx.x;
+  const int tok = forced.id[m] >= 0 ? forced.id[m] : cur[m];
+  for (int c = threadIdx.x; c < H; c += 256) x[(size_t)m * H + c] = emb[(size_t)tok * H + c] + pos[(size_t)p * H + c];
+}
+
+struct WhSeg {
+  const float* w;             // [N][K], torch's Linear layout
+  const float* bias;          // [N] or null
+  float* y;                   // row m at y + m * ldy
+  long long ldy;
+  float scale;
+};
+struct WhGemmArgs {
+  const float* x;             // [M][K], rows ldx apart
+  const float* ln_g;          // LayerNorm of the row in front (eps 1e-5), or null
+  const float* ln_b;
+  const float* res;           // added last, indexed like segment 0's output; or null
+  WhSeg seg[3];
+  long long ldx;
+  int M, N, K, gelu;
+};
+
+__global__ __launch_bounds__(256) void wh_gemm_kernel(WhGemmArgs a) {
+  __shared__ float stat[kWhItems][2];
+  __shared__ float red[4][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const WhSeg sg = a.seg[blockIdx.y];
+  const int n0 = blockIdx.x * 16, K = a.K;
+  if (a.ln_g) {
+    for (int m = wave; m < kWhItems; m += 4) {
+      float mean = 0.f, rs = 0.f;
+      if (m < a.M) {
+        const float* xr = a.x + (size_t)m * a.ldx;
+        float s = 0.f;
+        for (int k = lane; k < K; k += 64) s += xr[k];
+        mean = wave_sum(s) / (float)K;
+        float v = 0.f;
+        for (int k = lane; k < K; k += 64) {
+          const float d = xr[k] - mean;
+          v = fmaf(d, d, v);
+        }
+        rs = 1.f / sqrtf(wave_sum(v) / (float)K + 1e-5f);
+      }
+      if (lane == 0) {
+        stat[m][0] = mean;
+        stat[m][1] = rs;
+      }
+    }
+    __syncthreads();
+  }
+  const bool row = li < a.M;
+  const float mean = a.ln_g && row ? stat[li][0] : 0.f, rs = a.ln_g && row ? stat[li][1] : 0.f;
+  const float* __restrict__ wr = sg.w + (size_t)min(n0 + li, a.N - 1) * K;       // a row past N is row N - 1 again: never stored
+  const float* __restrict__ xr = a.x + (size_t)(row ? li : 0) * a.ldx;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  // A = W (lane: output n0 + li, k + lg-th quarter), B = x (lane: row li, the same k): D[n = 4 lg + r][m = li]
+#pragma unroll 4
+  for (int k0 = wave * 16; k0 < K; k0 += 64) {
+    const int k = k0 + 4 * lg;
+    f32x4 w4 = {0.f, 0.f, 0.f, 0.f}, x4 = {0.f, 0.f, 0.f, 0.f};
+    if (k < K) {                                                                   // K is a multiple of 4
+      w4 = *reinterpret_cast<const f32x4*>(wr + k);
+      if (row) {
+        x4 = *reinterpret_cast<const f32x4*>(xr + k);
+        if (a.ln_g) {
+          const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.ln_g + k), b4 = *reinterpret_cast<const f32x4*>(a.ln_b + k);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) x4[j] = fmaf((x4[j] - mean) * rs, g4[j], b4[j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[j], x4[j], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[wave][4 * lg + r][li] = acc[r];
+  __syncthreads();
+  const int m = tid >> 4, nl = tid & 15, n = n0 + nl;
+  if (m >= a.M || n >= a.N) return;
+  float v = ((red[0][nl][m] + red[1][nl][m]) + red[2][nl][m]) + red[3][nl][m];
+  if (sg.bias) v += sg.bias[n];
+  v *= sg.scale;
+  if (a.gelu) v = wh_gelu(v);
+  if (a.res) v += a.res[(size_t)m * sg.ldy + n];
+  sg.y[(size_t)m * sg.ldy + n] = v;
+}
+
+// q [M][H] (scaled) against keys 0 .. n - 1 of the item's cache: kc [n][H] keys, vc the values; head h owns channels [h d, (h + 1) d).
+// grid: (heads, items), one wave.  Lane j takes keys j, j + 64, ...; the maximum and the sum meet by wave_max / wave_sum; lane c then adds up
+// channel c over the keys in order.
+__global__ __launch_bounds__(64) void wh_self_attn_kernel(const float* __restrict__ q, const float* __restrict__ cache, float* __restrict__ out,
+                                                          long long item_stride, int Tm, int H, int d, int n) {
+  __shared__ float qs[64];
+  __shared__ float ps[kWhMaxKeys];
+  const int lane = threadIdx.x, head = blockIdx.x, m = blockIdx.y, hd = head * d;
+  const float* __restrict__ kc = cache + (size_t)m * item_stride + hd;
+  const float* __restrict__ vc = kc + (size_t)Tm * H;
+  qs[lane] = lane < d ? q[(size_t)m * H + hd + lane] : 0.f;
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int j = lane; j < n; j += 64) {
+    const float* kr = kc + (size_t)j * H;
+    float s = 0.f;
+    for (int c = 0; c < d; c += 4) {
+      const f32x4 k4 = *reinterpret_cast<const f32x4*>(kr + c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s = fmaf(qs[c + i], k4[i], s);
+    }
+    ps[j] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = wave_max(mx);
+  float l = 0.f;
+  for (int j = lane; j < n; j += 64) {
+    const float e = expf(ps[j] - mx);
+    ps[j] = e;
+    l += e;
+  }
+  l = wave_sum(l);
+  __syncthreads();
+  if (lane < d) {
+    float o = 0.f;
+    for (int j = 0; j < n; ++j) o = fmaf(ps[j], vc[(size_t)j * H + lane], o);
+    out[(size_t)m * H + hd + lane] = o / l;
+  }
+}
+
+// q [M][H] (scaled) against the S encoder frames: kv [2 H][S] planar per item (keys, then values).  grid: (heads, items), kWhCrossWaves waves.
+// Thread t takes frames t, t + 64 kWhCrossWaves, ...; wave w then adds up channels w, w + kWhCrossWaves, ... of the head, a lane over frames
+// lane, lane + 64, ...  The loops are unrolled so that a thread has several loads in flight; the order of every sum is the loop's.
+constexpr int kWhCrossWaves = 16;
+
+__global__ __launch_bounds__(64 * kWhCrossWaves) void wh_cross_attn_kernel(const float* __restrict__ q, const float* __restrict__ kv,
+                                                                           float* __restrict__ out, long long item_stride, int S, int H, int d) {
+  constexpr int NT = 64 * kWhCrossWaves;
+  __shared__ float qs[64];
+  __shared__ float ps[kWhMaxKeys];
+  __shared__ float red[kWhCrossWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, head = blockIdx.x, m = blockIdx.y, hd = head * d;
+  const float* __restrict__ kp = kv + (size_t)m * item_stride + (size_t)hd * S;
+  const float* __restrict__ vp = kp + (size_t)H * S;
+  if (tid < 64) qs[tid] = tid < d ? q[(size_t)m * H + hd + tid] : 0.f;
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int j = tid; j < S; j += NT) {
+    float s = 0.f;
+#pragma unroll 16
+    for (int c = 0; c < d; ++c) s = fmaf(qs[c], kp[(size_t)c * S + j], s);
+    ps[j] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = red[0];
+#pragma unroll
+  for (int w = 1; w < kWhCrossWaves; ++w) mx = fmaxf(mx, red[w]);
+  float l = 0.f;
+  for (int j = tid; j < S; j += NT) {
+    const float e = expf(ps[j] - mx);
+    ps[j] = e;
+    l += e;
+  }
+  l = wave_sum(l);
+  __syncthreads();
+  if (lane == 0) red[wave] = l;
+  __syncthreads();
+  l = 0.f;
+#pragma unroll
+  for (int w = 0; w < kWhCrossWaves; ++w) l += red[w];
+  for (int c = wave; c < d; c += kWhCrossWaves) {
+    const float* vr = vp + (size_t)c * S;
+    float o = 0.f;
+#pragma unroll 8
+    for (int j = lane; j < S; j += 64) o = fmaf(ps[j], vr[j], o);
+    o = wave_sum(o);
+    if (lane == 0) out[(size_t)m * H + hd + c] = o / l;
+  }
+}
+
+struct WhGenState {             // a group's loop state in the workspace
+  int* cur;                     // [kWhItems] the token argmax chose last
+  int* done;                    // [kWhItems]
+  int* running;                 // items of the group that have not ended
+};
+
+__global__ __launch_bounds__(256) void wh_init_kernel(WhGenState st, long long* __restrict__ tokens, long long* __restrict__ n, int nb, int max_new,
+                                                      long long eos) {
+  const int tid = threadIdx.x;
+  if (tid < kWhItems) {
+    st.cur[tid] = 0;
+    st.done[tid] = 0;
+  }
+  if (tid < nb) n[tid] = 0;
+  if (tid == 0) *st.running = nb;
+  for (int i = tid; i < nb * max_new; i += 256) tokens[i] = eos;
+}
+
+// item m of the group: the largest logit that no mask suppresses, the lower index on a tie; tokens[m][step] and the item's end
+__global__ __launch_bounds__(256) void wh_argmax_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ suppress,
+                                                        const unsigned char* __restrict__ begin, WhGenState st, long long* __restrict__ tokens,
+                                                        long long* __restrict__ n, int V, int max_new, int step, int eos) {
+  __shared__ float rv[4];
+  __shared__ int ri[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = blockIdx.x;
+  const float* __restrict__ x = logits + (size_t)m * V;
+  float best = -INFINITY;
+  int idx = 0x7fffffff;
+  for (int v = tid; v < V; v += 256) {
+    if ((suppress && suppress[v]) || (begin && begin[v])) continue;
+    const float y = x[v];
+    if (y > best || (idx == 0x7fffffff && y == best)) {
+      best = y;
+      idx = v;
+    }
+  }
+  auto take = [&](float ov, int oi) {
+    if (ov > best || (ov == best && oi < idx)) {
+      best = ov;
+      idx = oi;
+    }
+  };
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) take(__shfl_xor(best, o), __shfl_xor(idx, o));
+  if (lane == 0) {
+    rv[wave] = best;
+    ri[wave] = idx;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 1; w < 4; ++w) take(rv[w], ri[w]);
+  if (st.done[m]) return;                               // tokens[m][step] holds eos already
+  const int tok = idx == 0x7fffffff ? eos : idx;        // every token suppressed: the item ends
+  st.cur[m] = tok;
+  tokens[(size_t)m * max_new + step] = tok;
+  if (tok == eos) {
+    st.done[m] = 1;
+    atomicSub(st.running, 1);
+  } else {
+    n[m] += 1;
+  }
+}
+
+struct WhLinear {
+  const float *w = nullptr, *b = nullptr;
+};
+struct WhDecLayer {
+  const float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b;
+  WhLinear q, k, v, o, cq, co, fc1, fc2;
+};
+
+}  // namespace
+}  // namespace us
+
+struct us_whisper : us::WeightTable {
+  us_whisper_config cfg{};
+  us::WhEncoder* enc = nullptr;
+  std::vector<us::WhDecLayer> dec;
+  bool allocated = false, dirty = true;
+};
+
+namespace us {
+namespace {
+
+void wh_keys(us_whisper* h) {
+  const auto& c = h->cfg;
+  const int H = c.d_model;
+  auto affine = [&](const std::string& p) {
+    h->add(p + ".weight", {H});
+    h->add(p + ".bias", {H});
+  };
+  auto linear = [&](const std::string& p, int out, int in, bool bias = true) {
+    h->add(p + ".weight", {out, in});
+    if (bias) h->add(p + ".bias", {out});
+  };
+  auto attn = [&](const std::string& p) {
+    linear(p + ".k_proj", H, H, false);
+    linear(p + ".v_proj", H, H);
+    linear(p + ".q_proj", H, H);
+    linear(p + ".out_proj", H, H);
+  };
+  h->add("model.encoder.conv1.weight", {H, c.n_mels, 3});
+  h->add("model.encoder.conv1.bias", {H});
+  h->add("model.encoder.conv2.weight", {H, H, 3});
+  h->add("model.encoder.conv2.bias", {H});
+  h->add("model.encoder.embed_positions.weight", {c.max_source_positions, H});
+  for (int i = 0; i < c.encoder_layers; ++i) {
+    const std::string p = "model.encoder.layers." + std::to_string(i);
+    attn(p + ".self_attn");
+    affine(p + ".self_attn_layer_norm");
+    linear(p + ".fc1", c.encoder_ffn, H);
+    linear(p + ".fc2", H, c.encoder_ffn);
+    affine(p + ".final_layer_norm");
+  }
+  affine("model.encoder.layer_norm");
+  h->add("model.decoder.embed_tokens.weight", {c.vocab_size, H});
+  h->add("model.decoder.embed_positions.weight", {c.max_target_positions, H});
+  for (int i = 0; i < c.decoder_layers; ++i) {
+    const std::string p = "model.decoder.layers." + std::to_string(i);
+    attn(p + ".self_attn");
+    affine(p + ".self_attn_layer_norm");
+    attn(p + ".encoder_attn");
+    affine(p + ".encoder_attn_layer_norm");
+    linear(p + ".fc1", c.decoder_ffn, H);
+    linear(p + ".fc2", H, c.decoder_ffn);
+    affine(p + ".final_layer_norm");
+  }
+  affine("model.decoder.layer_norm");
+}
+
+hipError_t wh_alloc(us_whisper* h) {
+  hipError_t e = hipSuccess;
+  for (auto& kv : h->w)
+    if (e == hipSuccess && !kv.second.dev) e = hipMalloc(&kv.second.dev, std::max<size_t>(kv.second.numel(), 1) * sizeof(float));
+  if (e == hipSuccess) e = wh_encoder_alloc(h->enc);
+  h->allocated = e == hipSuccess;
+  return e;
+}
+
+hipError_t wh_prepare(us_whisper* h, hipStream_t s) {
+  auto W = [&](const std::string& k) { return (const float*)h->w.at(k).dev; };
+  h->dec.resize(h->cfg.decoder_layers);
+  for (int i = 0; i < h->cfg.decoder_layers; ++i) {
+    const std::string p = "model.decoder.layers." + std::to_string(i) + ".";
+    WhDecLayer& l = h->dec[i];
+    l.ln1_g = W(p + "self_attn_layer_norm.weight"); l.ln1_b = W(p + "self_attn_layer_norm.bias");
+    l.ln2_g = W(p + "encoder_attn_layer_norm.weight"); l.ln2_b = W(p + "encoder_attn_layer_norm.bias");
+    l.ln3_g = W(p + "final_layer_norm.weight"); l.ln3_b = W(p + "final_layer_norm.bias");
+    l.q = {W(p + "self_attn.q_proj.weight"), W(p + "self_attn.q_proj.bias")};
+    l.k = {W(p + "self_attn.k_proj.weight"), nullptr};
+    l.v = {W(p + "self_attn.v_proj.weight"), W(p + "self_attn.v_proj.bias")};
+    l.o = {W(p + "self_attn.out_proj.weight"), W(p + "self_attn.out_proj.bias")};
+    l.cq = {W(p + "encoder_attn.q_proj.weight"), W(p + "encoder_attn.q_proj.bias")};
+    l.co = {W(p + "encoder_attn.out_proj.weight"), W(p + "encoder_attn.out_proj.bias")};
+    l.fc1 = {W(p + "fc1.weight"), W(p + "fc1.bias")};
+    l.fc2 = {W(p + "fc2.weight"), W(p + "fc2.bias")};
+  }
+  const hipError_t e = wh_encoder_prepare(h->enc, *h, s);
+  if (e == hipSuccess) h->dirty = false;
+  return e;
+}
+
+struct WhPlan {                 // float offsets into the aligned workspace
+  size_t enc, planar, kv, cache, x, q, att, ff, logits, state, total;
+};
+
+WhPlan wh_plan(const us_whisper* h, int B) {
+  const auto& c = h->cfg;
+  WhPlan p{};
+  WsTake take;
+  const size_t H = (size_t)c.d_model, S = (size_t)c.max_source_positions;
+  p.enc = take(wh_encoder_ws_floats(h->enc, B));
+  p.planar = take((size_t)B * H * S);
+  p.kv = take((size_t)c.decoder_layers * B * 2 * H * S);
+  p.cache = take((size_t)c.decoder_layers * B * 2 * c.max_target_positions * H);
+  p.x = take(kWhItems * H);
+  p.q = take(kWhItems * H);
+  p.att = take(kWhItems * H);
+  p.ff = take((size_t)kWhItems * c.decoder_ffn);
+  p.logits = take((size_t)kWhItems * c.vocab_size);
+  p.state = take(64);
+  p.total = take.total;
+  return p;
+}
+
+size_t wh_workspace_bytes(const us_whisper* h, int B) { return wh_plan(h, B).total * sizeof(float) + 256; }
+
+// the checks every computing entry point starts with, then the encoder: -> planar (and out), cross keys / values when `cross`
+int wh_begin(us_whisper* h, const std::string& what, const float* feats, int B, int T, float* out, bool cross, void* ws, size_t ws_bytes,
+             hipStream_t s) {
+  if (!h || !feats || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
+  const auto& c = h->cfg;
+  if (T != 2 * c.max_source_positions)
+    return h->fail(US_EINVAL, what + ": the features have " + std::to_string(T) + " frames, the model takes exactly 2 * max_source_positions = " +
+                                  std::to_string(2 * c.max_source_positions));
+  if (B > 65535) return h->fail(US_EINVAL, what + ": at most 65535 items");
+  const int rc = h->all_loaded(what.c_str());
+  if (rc != US_OK) return rc;
+  if (!ws || ws_bytes < wh_workspace_bytes(h, B)) return h->fail(US_EWORKSPACE, what + ": workspace too small (us_whisper_workspace_bytes)");
+  hipError_t e;
+  if (h->dirty && (e = wh_prepare(h, s)) != hipSuccess) return h->hip((what + ": preparing the weights").c_str(), e);
+  const WhPlan p = wh_plan(h, B);
+  float* base = ws_align(ws);
+  if ((e = wh_encoder_forward(h->enc, *h, feats, B, base + p.planar, out, base + p.enc, s)) != hipSuccess) return h->hip(what.c_str(), e);
+  if (cross && (e = wh_encoder_cross_kv(h->enc, *h, base + p.planar, B, base + p.kv, s)) != hipSuccess) return h->hip(what.c_str(), e);
+  return US_OK;
+}
+
+struct WhStep {                 // one group's buffers
+  us_whisper* h;
+  hipStream_t s;
+  float *X, *Q, *ATT, *FF, *cache, *kv;        // cache / kv: the group's first item of layer 0
+  int B, nb;
+};
+
+void wh_gemm(const WhStep& t, const float* x, int K, const float* ln_g, const float* ln_b, const float* res, int N, int gelu, int nseg, const WhSeg* seg) {
+  WhGemmArgs a{};
+  a.x = x; a.ldx = K; a.ln_g = ln_g; a.ln_b = ln_b; a.res = res; a.M = t.nb; a.N = N; a.K = K; a.gelu = gelu;
+  for (int i = 0; i < nseg; ++i) a.seg[i] = seg[i];
+  hipLaunchKernelGGL(wh_gemm_kernel, dim3((N + 15) / 16, nseg), dim3(256), 0, t.s, a);
+}
+
+// the decoder layers at position `pos`: X holds the embedded rows on entry and the last layer's stream on return
+void wh_layers(const WhStep& t, int pos) {
+  const auto& c = t.h->cfg;
+  const int H = c.d_model, I = c.decoder_ffn, Tm = c.max_target_positions, S = c.max_source_positions, d = H / c.decoder_heads;
+  const float qs = 1.f / sqrtf((float)d);
+  const long long cache_item = 2ll * Tm * H, kv_item = 2ll * H * S;
+  for (int i = 0; i < c.decoder_layers; ++i) {
+    const WhDecLayer& l = t.h->dec[i];
+    float* cache = t.cache + (size_t)i * t.B * cache_item;
+    const float* kv = t.kv + (size_t)i * t.B * kv_item;
+    const WhSeg qkv[3] = {{l.q.w, l.q.b, t.Q, H, qs},
+                          {l.k.w, nullptr, cache + (size_t)pos * H, cache_item, 1.f},
+                          {l.v.w, l.v.b, cache + (size_t)(Tm + pos) * H, cache_item, 1.f}};
+    wh_gemm(t, t.X, H, l.ln1_g, l.ln1_b, nullptr, H, 0, 3, qkv);
+    hipLaunchKernelGGL(wh_self_attn_kernel, dim3(c.decoder_heads, t.nb), dim3(64), 0, t.s, t.Q, cache, t.ATT, cache_item, Tm, H, d, pos + 1);
+    const WhSeg o{l.o.w, l.o.b, t.X, H, 1.f};
+    wh_gemm(t, t.ATT, H, nullptr, nullptr, t.X, H, 0, 1, &o);
+    const WhSeg cq{l.cq.w, l.cq.b, t.Q, H, qs};
+    wh_gemm(t, t.X, H, l.ln2_g, l.ln2_b, nullptr, H, 0, 1, &cq);
+    hipLaunchKernelGGL(wh_cross_attn_kernel, dim3(c.decoder_heads, t.nb), dim3(64 * kWhCrossWaves), 0, t.s, t.Q, kv, t.ATT, kv_item, S, H, d);
+    const WhSeg co{l.co.w, l.co.b, t.X, H, 1.f};
+    wh_gemm(t, t.ATT, H, nullptr, nullptr, t.X, H, 0, 1, &co);
+    const WhSeg f1{l.fc1.w, l.fc1.b, t.FF, I, 1.f};
+    wh_gemm(t, t.X, H, l.ln3_g, l.ln3_b, nullptr, I, 1, 1, &f1);
+    const WhSeg f2{l.fc2.w, l.fc2.b, t.X, H, 1.f};
+    wh_gemm(t, t.FF, I, nullptr, nullptr, t.X, H, 0, 1, &f2);
+  }
+}
+
+// logits of the rows in X: decoder.layer_norm, then the tied embedding; row m at y + m * ldy
+void wh_logits(const WhStep& t, float* y, long long ldy) {
+  auto W = [&](const char* k) { return (const float*)t.h->w.at(k).dev; };
+  const WhSeg sg{W("model.decoder.embed_tokens.weight"), nullptr, y, ldy, 1.f};
+  wh_gemm(t, t.X, t.h->cfg.d_model, W("model.decoder.layer_norm.weight"), W("model.decoder.layer_norm.bias"), nullptr, t.h->cfg.vocab_size, 0, 1, &sg);
+}
+
+void wh_embed(const WhStep& t, const WhTokens& forced, const int* cur, int pos) {
+  auto W = [&](const char* k) { return (const float*)t.h->w.at(k).dev; };
+  hipLaunchKernelGGL(wh_embed_kernel, dim3(t.nb), dim3(256), 0, t.s, W("model.decoder.embed_tokens.weight"), W("model.decoder.embed_positions.weight"),
+                     cur, forced, t.X, t.h->cfg.d_model, pos);
+}
+
+WhStep wh_group(us_whisper* h, const WhPlan& p, float* base, int B, int b0, int nb, hipStream_t s) {
+  const auto& c = h->cfg;
+  const size_t H = (size_t)c.d_model;
+  return WhStep{h, s, base + p.x, base + p.q, base + p.att, base + p.ff, base + p.cache + (size_t)b0 * 2 * c.max_target_positions * H,
+                base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions, B, nb};
+}
+
+std::string wh_bad_token(const std::string& what, const int64_t* ids, size_t n, int V) {
+  for (size_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= V)
+      return what + ": token " + std::to_string((long long)ids[i]) + " at index " + std::to_string(i) + " lies outside the vocabulary [0, " +
+             std::to_string(V) + ")";
+  return std::string();
+}
+
+}  // namespace
+}  // namespace us
+
+extern "C" {
+
+using namespace us;
+
+int us_whisper_create(us_whisper_handle* out, const us_whisper_config* cfg) {
+  if (!out || !cfg) return WeightTable::fail(nullptr, US_EINVAL, "us_whisper_create: null argument");
+  const auto& c = *cfg;
+  auto bad = [](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, "us_whisper_create: " + m); };
+  if (c.n_mels < 1 || c.n_mels > 1024 || c.d_model < 4 || c.d_model > 8192 || c.vocab_size < 1 || c.vocab_size > (1 << 24)) return bad("bad n_mels / d_model / vocab_size");
+  if (c.encoder_layers < 0 || c.encoder_layers > 64 || c.decoder_layers < 1 || c.decoder_layers > 64) return bad("0 to 64 encoder layers, 1 to 64 decoder layers");
+  if (c.encoder_ffn < 4 || c.decoder_ffn < 4 || c.encoder_ffn > 32768 || c.decoder_ffn > 32768 || c.decoder_ffn % 4 != 0)
+    return bad("the feed-forward sizes must lie in [4, 32768], the decoder's a multiple of 4");
+  if (c.max_source_positions < 1 || c.max_source_positions > kWhMaxKeys || c.max_target_positions < 1 || c.max_target_positions > kWhMaxKeys)
+    return bad("max_source_positions and max_target_positions must lie in [1, " + std::to_string(kWhMaxKeys) + "]");
+  for (int heads : {c.encoder_heads, c.decoder_heads}) {
+    if (heads < 1 || c.d_model % heads != 0) return bad("d_model must be divisible by the number of heads");
+    const int d = c.d_model / heads;
+    if (d > 64 || d % 4 != 0) return bad("the head dimension must be a multiple of 4, at most 64 (got " + std::to_string(d) + ")");
+  }
+  auto* h = new us_whisper();
+  h->cfg = c;
+  (void)hipGetDevice(&h->device);
+  h->enc = wh_encoder_new({c.n_mels, c.d_model, c.encoder_heads, c.encoder_ffn, c.encoder_layers, c.max_source_positions, c.decoder_layers});
+  wh_keys(h);
+  *out = h;
+  return US_OK;
+}
+
+int us_whisper_destroy(us_whisper_handle h) {
+  if (!h) return US_OK;
+  h->free_weights();
+  wh_encoder_free(h->enc);
+  delete h;
+  return US_OK;
+}
+
+int us_whisper_num_weights(us_whisper_handle h) { return h ? h->num() : 0; }
+const char* us_whisper_weight_key(us_whisper_handle h, int i) { return h ? h->key(i) : nullptr; }
+const char* us_whisper_last_error(us_whisper_handle h) { return h ? h->last_error() : us_last_error(nullptr); }
+
+int us_whisper_load_weight(us_whisper_handle h, const char* key, const float* data, const int64_t* shape, int ndim, us_stream stream) {
+  Weight* w;
+  int rc = WeightTable::find(h, "us_whisper_load_weight", key, data, shape, ndim, &w);
+  if (rc != US_OK) return rc;
+  hipError_t e;
+  if (!h->allocated && (e = wh_alloc(h)) != hipSuccess) return h->hip("us_whisper_load_weight: hipMalloc", e);
+  if ((rc = h->copy(*w, data, static_cast<hipStream_t>(stream))) != US_OK) return rc;
+  w->loaded = true;
+  h->dirty = true;
+  return US_OK;
+}
+
+size_t us_whisper_workspace_bytes(us_whisper_handle h, int B) { return h && B > 0 && B <= 65535 ? wh_workspace_bytes(h, B) : 0; }
+
+int us_whisper_encode(us_whisper_handle h, const float* features, int B, int T, float* out, void* workspace, size_t workspace_bytes, us_stream stream) {
+  if (!out) return WeightTable::fail(h, US_EINVAL, "us_whisper_encode: bad argument");
+  return wh_begin(h, "us_whisper_encode", features, B, T, out, false, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int us_whisper_decoder_logits(us_whisper_handle h, const float* features, int B, int T, const int64_t* ids, int N, float* logits, void* workspace,
+                              size_t workspace_bytes, us_stream stream) {
+  const std::string what = "us_whisper_decoder_logits";
+  if (!h || !ids || !logits || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
+  const auto& c = h->cfg;
+  if (N < 1 || N > c.max_target_positions)
+    return h->fail(US_EINVAL, what + ": " + std::to_string(N) + " positions, the model has max_target_positions = " + std::to_string(c.max_target_positions));
+  const std::string bad = wh_bad_token(what, ids, (size_t)B * N, c.vocab_size);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = wh_begin(h, what, features, B, T, nullptr, true, workspace, workspace_bytes, s);
+  if (rc != US_OK) return rc;
+  const WhPlan p = wh_plan(h, B);
+  float* base = ws_align(workspace);
+  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
+    const WhStep t = wh_group(h, p, base, B, b0, nb, s);
+    for (int pos = 0; pos < N; ++pos) {
+      WhTokens f;
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < nb ? (int)ids[(size_t)(b0 + m) * N + pos] : 0;
+      wh_embed(t, f, nullptr, pos);
+      wh_layers(t, pos);
+      wh_logits(t, logits + ((size_t)b0 * N + pos) * c.vocab_size, (long long)N * c.vocab_size);
+    }
+  });
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
+}
+
+int us_whisper_generate(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P, int max_new, int64_t eos,
+                        const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* tokens, int64_t* n, void* workspace,
+                        size_t workspace_bytes, us_stream stream) {
+  const std::string what = "us_whisper_generate";
+  if (!h || !prompt || !tokens || !n || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
+  const auto& c = h->cfg;
+  if (P < 1 || max_new < 1 || (long long)P + max_new > c.max_target_positions)
+    return h->fail(US_EINVAL, what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
+                                  " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(c.max_target_positions));
+  if (eos < 0 || eos >= c.vocab_size) return h->fail(US_EINVAL, what + ": eos lies outside the vocabulary");
+  const std::string bad = wh_bad_token(what, prompt, (size_t)B * P, c.vocab_size);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = wh_begin(h, what, features, B, T, nullptr, true, workspace, workspace_bytes, s);
+  if (rc != US_OK) return rc;
+  const WhPlan p = wh_plan(h, B);
+  float* base = ws_align(workspace);
+  int* ints = reinterpret_cast<int*>(base + p.state);
+  const WhGenState st{ints, ints + kWhItems, ints + 2 * kWhItems};
+  float* L = base + p.logits;
+  hipError_t e = hipSuccess;
+  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
+    if (e != hipSuccess) return;
+    const WhStep t = wh_group(h, p, base, B, b0, nb, s);
+    long long* tok = reinterpret_cast<long long*>(tokens) + (size_t)b0 * max_new;
+    long long* cnt = reinterpret_cast<long long*>(n) + b0;
+    hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(256), 0, s, st, tok, cnt, nb, max_new, (long long)eos);
+    WhTokens f;
+    for (int pos = 0; pos + 1 < P; ++pos) {             // the prompt but for its last token: keys and values only
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : 0;
+      wh_embed(t, f, st.cur, pos);
+      wh_layers(t, pos);
+    }
+    for (int step = 0; step < max_new; ++step) {
+      const int pos = P - 1 + step;
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = step == 0 && m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : step == 0 ? 0 : -1;
+      wh_embed(t, f, st.cur, pos);
+      wh_layers(t, pos);
+      wh_logits(t, L, c.vocab_size);
+      hipLaunchKernelGGL(wh_argmax_kernel, dim3(nb), dim3(256), 0, s, L, suppress, step == 0 ? begin_suppress : nullptr, st, tok, cnt, c.vocab_size,
+                         max_new, step, (int)eos);
+      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
+        int running = 1;
+        if ((e = hipMemcpyAsync(&running, st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return;
+        if (running <= 0) break;
+      }
+    }
+  });
+  if (e == hipSuccess) e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
+}
+
+}  // extern "C"

@@ -1,0 +1,391 @@
+"""Whisper on the HIP library (`csrc/whisper.hip`, the encoder schedule in `csrc/hubert.hip`): what the reference's evaluation notebook does
+with `whisper.load_model`, `pad_or_trim`, `log_mel_spectrogram` and `decode(model, mel, DecodingOptions())`.
+
+`WhisperForConditionalGeneration` takes transformers' configuration fields by keyword and its state_dict; `log_mel_spectrogram` is Whisper's
+feature extraction in torch ops; `WhisperVocabulary` turns ids into text.  Greedy decoding only: no timestamp rules (put `<|notimestamps|>` in
+the prompt), no beam search, no temperature fallback, no window beyond 30 s (a longer item is refused), fp32 weights.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._handle import HandleModule
+from ._wav_encoder import _set
+from .mel import mel_filterbank
+
+SAMPLE_RATE, N_FFT, HOP, N_SAMPLES = 16000, 400, 160, 480000
+_FIELDS = ("num_mel_bins", "d_model", "encoder_layers", "encoder_attention_heads", "encoder_ffn_dim", "decoder_layers", "decoder_attention_heads",
+           "decoder_ffn_dim", "max_source_positions", "max_target_positions", "vocab_size")
+_DEFAULTS = dict(num_mel_bins=80, d_model=384, encoder_layers=4, encoder_attention_heads=6, encoder_ffn_dim=1536, decoder_layers=4,
+                 decoder_attention_heads=6, decoder_ffn_dim=1536, max_source_positions=1500, max_target_positions=448, vocab_size=51865)
+MEDIUM = dict(num_mel_bins=80, d_model=1024, encoder_layers=24, encoder_attention_heads=16, encoder_ffn_dim=4096, decoder_layers=24,
+              decoder_attention_heads=16, decoder_ffn_dim=4096, max_source_positions=1500, max_target_positions=448, vocab_size=51865)
+
+
+def log_mel_spectrogram(wav16, lengths=None, n_mels: int = 80):
+    """16 kHz waveform [B, T] (or [T]) with per-item lengths -> Whisper's input features [B, n_mels, 3000] (fp32, on the waveform's device):
+    pad / trim to 480,000 samples (samples at and past an item's length count as silence), n_fft 400, hop 160, periodic Hann, reflect-centred
+    frames with the last one dropped, power spectrum, the Slaney mel bank, log10(max(x, 1e-10)), per-item max(x, x.max() - 8), (x + 4) / 4.
+    Computed in fp64 and rounded once: the stage is far below 1 % of a transcription."""
+    x = torch.as_tensor(wav16)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"log_mel_spectrogram: expected a waveform [B, T], got {tuple(x.shape)}")
+    B, T = x.shape
+    x = x.to(torch.float64)
+    if lengths is not None:
+        n = torch.as_tensor(lengths, device=x.device).to(torch.int64).view(B, 1)
+        x = torch.where(torch.arange(T, device=x.device)[None] < n, x, torch.zeros((), dtype=x.dtype, device=x.device))
+    x = x[:, :N_SAMPLES] if T >= N_SAMPLES else torch.nn.functional.pad(x, (0, N_SAMPLES - T))
+    window = torch.hann_window(N_FFT, periodic=True, dtype=torch.float64, device=x.device)
+    spec = torch.stft(x, N_FFT, HOP, window=window, center=True, pad_mode="reflect", return_complex=True)[..., :-1]
+    power = spec.real ** 2 + spec.imag ** 2
+    bank = torch.from_numpy(np.asarray(mel_filterbank(SAMPLE_RATE, N_FFT, n_mels), dtype=np.float64)).to(x.device)
+    mel = torch.log10(torch.clamp(bank @ power, min=1e-10))
+    mel = torch.maximum(mel, mel.amax(dim=(1, 2), keepdim=True) - 8.0)
+    return ((mel + 4.0) / 4.0).to(torch.float32)
+
+
+def _bytes_to_unicode():
+    """GPT-2's table: every byte as a printable character"""
+    bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("¡"), ord("¬") + 1)) + list(range(ord("®"), ord("ÿ") + 1))
+    cs, n = bs[:], 0
+    for b in range(256):
+        if b not in bs:
+            bs.append(b)
+            cs.append(256 + n)
+            n += 1
+    return dict(zip(bs, (chr(c) for c in cs)))
+
+
+class _ScoringAlphabet:
+    def __contains__(self, c):
+        return c in " '" or (c.isalnum() and c == c.lower())
+
+    def __iter__(self):                  # normalize_text looks at the letters' case: all lower
+        return iter("abcdefghijklmnopqrstuvwxyz '")
+
+
+class WhisperVocabulary:
+    """`vocab.json` (token -> id, tokens in GPT-2's byte alphabet) and optionally `added_tokens.json` (the special tokens) of a Whisper
+    tokenizer; either may be a path or a dict.  `decode(ids)` drops the special tokens (anything written `<|...|>`, every added token and
+    every id the vocabulary lacks) and turns the rest into text."""
+
+    def __init__(self, vocab, added_tokens=None):
+        def read(v):
+            if isinstance(v, (str, os.PathLike)):
+                with open(v, encoding="utf-8") as f:
+                    return json.load(f)
+            return dict(v or {})
+        vocab, added = read(vocab), read(added_tokens)
+        self.token_to_id = {**vocab, **added}
+        self.special = {i for t, i in self.token_to_id.items() if t in added or (t.startswith("<|") and t.endswith("|>"))}
+        self.id_to_token = {i: t for t, i in self.token_to_id.items()}
+        self._byte = {c: b for b, c in _bytes_to_unicode().items()}
+
+    def __len__(self):
+        return len(self.token_to_id)
+
+    def token_id(self, token: str) -> int:
+        if token not in self.token_to_id:
+            raise KeyError(f"WhisperVocabulary: no token {token!r}")
+        return self.token_to_id[token]
+
+    start_id = property(lambda self: self.token_id("<|startoftranscript|>"))
+    transcribe_id = property(lambda self: self.token_id("<|transcribe|>"))
+    notimestamps_id = property(lambda self: self.token_id("<|notimestamps|>"))
+    end_id = property(lambda self: self.token_id("<|endoftext|>"))
+
+    def language_id(self, language: str) -> int:
+        return self.token_id(f"<|{language}|>")
+
+    def language_ids(self):
+        """the ids of the two- and three-letter `<|xx|>` tokens"""
+        return sorted(i for t, i in self.token_to_id.items() if t.startswith("<|") and t.endswith("|>") and t[2:-2].isalpha() and t[2:-2].islower()
+                      and len(t) in (6, 7))
+
+    @property
+    def characters(self):
+        """what `asr.normalize_text` keeps of a transcript: a byte-level vocabulary can write any character, so the scoring alphabet is
+        chosen here: lower-case letters and digits of any script, the apostrophe and the space"""
+        return _ScoringAlphabet()
+
+    def decode(self, ids, n=None):
+        """ids: a sequence of ints -> str; or [B, L] with counts `n` [B] -> list of str"""
+        if n is not None:
+            return [self.decode(row[:int(k)]) for row, k in zip(torch.as_tensor(ids).tolist(), torch.as_tensor(n).tolist())]
+        raw = bytearray()
+        for i in (int(v) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)):
+            t = self.id_to_token.get(i)
+            if t is None or i in self.special:
+                continue
+            raw.extend(self._byte[c] for c in t)
+        return raw.decode("utf-8", errors="replace")
+
+
+class WhisperForConditionalGeneration(HandleModule):
+    """`transformers.WhisperForConditionalGeneration` in eval mode on the HIP library: the configuration's fields by keyword, the
+    state_dict's keys (`proj_out.weight` is the tied `model.decoder.embed_tokens.weight`: accepted when equal, refused when not)."""
+    _abi = "whisper"
+    _what = "Whisper recogniser"
+    _cache_sources = True
+
+    def __init__(self, **config):
+        super().__init__()
+        unknown = sorted(k for k in config if k not in _FIELDS)
+        self.config = c = {k: int(config.get(k, _DEFAULTS[k])) for k in _FIELDS}
+        self.extra_config = {k: config[k] for k in unknown}        # eos_token_id, suppress_tokens ...: kept for the caller, not used here
+        H = c["d_model"]
+        for side in ("encoder", "decoder"):
+            nh = c[side + "_attention_heads"]
+            if nh < 1 or H % nh:
+                raise ValueError(f"WhisperForConditionalGeneration: d_model = {H} must be divisible by the {side}'s {nh} heads")
+            if (H // nh) > 64 or (H // nh) % 4:
+                raise ValueError(f"WhisperForConditionalGeneration: the head dimension must be a multiple of 4, at most 64 (got {H // nh})")
+        self.prompt_ids = None           # transcribe_ids: [start, language or None, task, notimestamps]
+        self.language_ids = None         # transcribe_ids: the candidates of detect_language when the prompt's language is None
+        self.eos_token_id = self.extra_config.get("eos_token_id")
+        self.suppress_tokens = self.extra_config.get("suppress_tokens")
+        self.begin_suppress_tokens = self.extra_config.get("begin_suppress_tokens")
+        self._masks = {}
+
+        def affine(p):
+            _set(self, p + ".weight", torch.ones(H))
+            _set(self, p + ".bias", torch.zeros(H))
+
+        def linear(p, o, i, bias=True):
+            _set(self, p + ".weight", torch.zeros(o, i))
+            if bias:
+                _set(self, p + ".bias", torch.zeros(o))
+
+        def attention(p):
+            linear(p + ".k_proj", H, H, False)
+            linear(p + ".v_proj", H, H)
+            linear(p + ".q_proj", H, H)
+            linear(p + ".out_proj", H, H)
+
+        _set(self, "model.encoder.conv1.weight", torch.zeros(H, c["num_mel_bins"], 3))
+        _set(self, "model.encoder.conv1.bias", torch.zeros(H))
+        _set(self, "model.encoder.conv2.weight", torch.zeros(H, H, 3))
+        _set(self, "model.encoder.conv2.bias", torch.zeros(H))
+        _set(self, "model.encoder.embed_positions.weight", torch.zeros(c["max_source_positions"], H))
+        for i in range(c["encoder_layers"]):
+            p = f"model.encoder.layers.{i}"
+            attention(p + ".self_attn")
+            affine(p + ".self_attn_layer_norm")
+            linear(p + ".fc1", c["encoder_ffn_dim"], H)
+            linear(p + ".fc2", H, c["encoder_ffn_dim"])
+            affine(p + ".final_layer_norm")
+        affine("model.encoder.layer_norm")
+        _set(self, "model.decoder.embed_tokens.weight", torch.zeros(c["vocab_size"], H))
+        _set(self, "model.decoder.embed_positions.weight", torch.zeros(c["max_target_positions"], H))
+        for i in range(c["decoder_layers"]):
+            p = f"model.decoder.layers.{i}"
+            attention(p + ".self_attn")
+            affine(p + ".self_attn_layer_norm")
+            attention(p + ".encoder_attn")
+            affine(p + ".encoder_attn_layer_norm")
+            linear(p + ".fc1", c["decoder_ffn_dim"], H)
+            linear(p + ".fc2", H, c["decoder_ffn_dim"])
+            affine(p + ".final_layer_norm")
+        affine("model.decoder.layer_norm")
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        sd = dict(state_dict)
+        tied = sd.pop("proj_out.weight", None)
+        if tied is not None and "model.decoder.embed_tokens.weight" in sd and not torch.equal(tied, sd["model.decoder.embed_tokens.weight"]):
+            raise ValueError("WhisperForConditionalGeneration: proj_out.weight differs from model.decoder.embed_tokens.weight; only the tied "
+                             "projection is built")
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    # ---- engine ----------------------------------------------------------------------------------------------------------------
+
+    def _create(self, lib, device):
+        c, s = self.config, _lib.us_whisper_config()
+        s.n_mels, s.d_model, s.vocab_size = c["num_mel_bins"], c["d_model"], c["vocab_size"]
+        s.encoder_layers, s.encoder_heads, s.encoder_ffn = c["encoder_layers"], c["encoder_attention_heads"], c["encoder_ffn_dim"]
+        s.decoder_layers, s.decoder_heads, s.decoder_ffn = c["decoder_layers"], c["decoder_attention_heads"], c["decoder_ffn_dim"]
+        s.max_source_positions, s.max_target_positions = c["max_source_positions"], c["max_target_positions"]
+        _lib.check(lib.us_whisper_create(C.byref(self._h), C.byref(s)), None, "us_whisper_create")
+
+    def _precondition(self):
+        if self.training:
+            raise RuntimeError("WhisperForConditionalGeneration is inference-only: call .eval()")
+
+    def _features(self, input_features):
+        x = input_features
+        if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] != self.config["num_mel_bins"]:
+            raise ValueError(f"WhisperForConditionalGeneration: expected features [B, {self.config['num_mel_bins']}, T], got {tuple(x.shape)}")
+        lib, stream = self._sync(x.device)
+        x = x.detach().to(torch.float32).contiguous()
+        B, T = int(x.shape[0]), int(x.shape[2])
+        return lib, stream, x, B, T, self._workspace(lib, x.device, B)
+
+    def _ids(self, ids, B, name):
+        t = torch.as_tensor(ids).detach().to("cpu", torch.int64)
+        if t.dim() == 1:
+            t = t[None].expand(B, -1)
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1:
+            raise ValueError(f"WhisperForConditionalGeneration: {name} must be [B, N] (or [N] for every item) with N >= 1, got {tuple(t.shape)}")
+        t = t.contiguous()
+        return t, (C.c_int64 * t.numel())(*t.view(-1).tolist())
+
+    @torch.no_grad()
+    def encode(self, input_features):
+        """[B, n_mels, 2 S] -> the encoder's last hidden state [B, S, d_model]"""
+        lib, stream, x, B, T, ws = self._features(input_features)
+        out = torch.empty(B, self.config["max_source_positions"], self.config["d_model"], device=x.device)
+        self._call(lib, x.device, "encode", self._h, x.data_ptr(), B, T, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        return out
+
+    @torch.no_grad()
+    def logits(self, input_features, decoder_input_ids):
+        """teacher forcing: decoder_input_ids [B, N] -> [B, N, V]"""
+        lib, stream, x, B, T, ws = self._features(input_features)
+        t, ids = self._ids(decoder_input_ids, B, "decoder_input_ids")
+        out = torch.empty(B, t.shape[1], self.config["vocab_size"], device=x.device)
+        self._call(lib, x.device, "decoder_logits", self._h, x.data_ptr(), B, T, ids, int(t.shape[1]), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                   stream)
+        return out
+
+    def _mask(self, tokens, device):
+        if tokens is None or len(tokens) == 0:
+            return None
+        key = (tuple(int(t) for t in tokens), device)
+        if key not in self._masks:
+            V = self.config["vocab_size"]
+            if min(key[0]) < 0 or max(key[0]) >= V:
+                raise ValueError(f"WhisperForConditionalGeneration: a suppressed token lies outside the vocabulary [0, {V})")
+            m = torch.zeros(V, dtype=torch.uint8)
+            m[list(key[0])] = 1
+            self._masks = {key: m.to(device), **dict(list(self._masks.items())[-3:])}
+        return self._masks[key]
+
+    @torch.no_grad()
+    def generate(self, input_features, prompt_ids, max_new_tokens=None, suppress_tokens=None, begin_suppress_tokens=None, eos_token_id=None):
+        """greedy decoding after the teacher-forced prompt [B, P] (or [P]) -> (tokens [B, max_new_tokens] int64 with eos at and after an
+        item's end, lengths [B] int64: the tokens in front of it)"""
+        lib, stream, x, B, T, ws = self._features(input_features)
+        t, ids = self._ids(prompt_ids, B, "prompt_ids")
+        P = int(t.shape[1])
+        eos = self.eos_token_id if eos_token_id is None else eos_token_id
+        if eos is None:
+            raise ValueError("WhisperForConditionalGeneration.generate: no eos_token_id (give it here or in the configuration)")
+        max_new = self.config["max_target_positions"] - P if max_new_tokens is None else int(max_new_tokens)
+        sup, beg = self._mask(suppress_tokens, x.device), self._mask(begin_suppress_tokens, x.device)
+        tokens = torch.empty(B, max(max_new, 1), dtype=torch.int64, device=x.device)
+        n = torch.empty(B, dtype=torch.int64, device=x.device)
+        self._call(lib, x.device, "generate", self._h, x.data_ptr(), B, T, ids, P, max_new, int(eos), sup.data_ptr() if sup is not None else None,
+                   beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        return tokens, n
+
+    @torch.no_grad()
+    def detect_language(self, input_features, language_ids, start_id=None):
+        """One step from the start token, argmax over `language_ids` -> [B] int64 (on the device): the first thing `whisper.decode` does
+        when no language is set."""
+        start = self.extra_config.get("decoder_start_token_id") if start_id is None else start_id
+        if start is None:
+            start = self.prompt_ids[0] if self.prompt_ids else None
+        if start is None:
+            raise ValueError("detect_language: no start token (start_id, decoder_start_token_id or prompt_ids[0])")
+        cand = torch.as_tensor(list(language_ids), dtype=torch.int64, device=input_features.device)
+        lg = self.logits(input_features, torch.full((input_features.shape[0], 1), int(start), dtype=torch.int64))[:, 0]
+        return cand[lg[:, cand].argmax(-1)]
+
+    @torch.no_grad()
+    def transcribe_ids(self, wav16, lengths=None, language_id=None, prompt_ids=None, max_new_tokens=None):
+        """16 kHz waveforms [B, T] with per-item lengths -> (tokens [B, L], count [B]): log-mel features, the prompt (`prompt_ids`, default
+        `self.prompt_ids`: [start, language, task, notimestamps]; a language of None is `language_id`, or detected per item among
+        `self.language_ids`), greedy decoding with the configuration's suppression lists.  An item longer than 30 s is refused."""
+        x = torch.as_tensor(wav16)
+        if x.dim() == 1:
+            x = x[None]
+        B = x.shape[0]
+        n = [int(v) for v in (torch.as_tensor(lengths).tolist() if lengths is not None else [x.shape[1]] * B)]
+        if max(n) > N_SAMPLES:
+            raise ValueError(f"WhisperForConditionalGeneration.transcribe_ids: item {n.index(max(n))} has {max(n)} samples, more than one 30 s "
+                             f"window ({N_SAMPLES}); longer items are not cut")
+        feats = log_mel_spectrogram(x, n, self.config["num_mel_bins"])
+        prompt = list(self.prompt_ids if prompt_ids is None else prompt_ids)
+        if not prompt:
+            raise ValueError("WhisperForConditionalGeneration.transcribe_ids: no prompt_ids")
+        rows = torch.tensor([[0 if p is None else int(p) for p in prompt]] * B, dtype=torch.int64)
+        for j, p in enumerate(prompt):
+            if p is None:
+                if language_id is None and not self.language_ids:
+                    raise ValueError("WhisperForConditionalGeneration.transcribe_ids: no language_id and no language_ids to detect one among")
+                rows[:, j] = int(language_id) if language_id is not None else self.detect_language(feats, self.language_ids, prompt[0]).cpu()
+        return self.generate(feats, rows, max_new_tokens, self.suppress_tokens, self.begin_suppress_tokens)
+
+
+def detect_language(model, input_features, language_ids, start_id=None):
+    return model.detect_language(input_features, language_ids, start_id)
+
+
+def load_whisper_checkpoint(path):
+    """A `torch.save`d state dict (the `openai/whisper-medium` size unless the file is a dict with `config` and `state_dict`), or a directory
+    with `config.json` and `pytorch_model.bin` / `model.safetensors` (the latter only where `safetensors` imports) -> the model, with
+    eos_token_id and the suppression lists of `generation_config.json` (else `config.json`) set."""
+    config, extra = dict(MEDIUM), {}
+    if os.path.isdir(path):
+        with open(os.path.join(path, "config.json"), encoding="utf-8") as f:
+            config = json.load(f)
+        gen = os.path.join(path, "generation_config.json")
+        if os.path.exists(gen):
+            with open(gen, encoding="utf-8") as f:
+                extra = json.load(f)
+        if os.path.exists(os.path.join(path, "pytorch_model.bin")):
+            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
+        elif os.path.exists(os.path.join(path, "model.safetensors")):
+            try:
+                from safetensors.torch import load_file
+            except ImportError as e:
+                raise RuntimeError(f"{path} holds model.safetensors only and `safetensors` does not import: save it with torch.save") from e
+            sd = load_file(os.path.join(path, "model.safetensors"))
+        else:
+            raise FileNotFoundError(f"{path}: neither pytorch_model.bin nor model.safetensors")
+    else:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if "state_dict" in sd and "config" in sd:
+            config, sd = dict(sd["config"]), sd["state_dict"]
+    keep = {k: config[k] for k in _FIELDS if k in config}
+    for k in ("eos_token_id", "decoder_start_token_id", "suppress_tokens", "begin_suppress_tokens"):
+        v = extra.get(k, config.get(k))
+        if v is not None:
+            keep[k] = v
+    model = WhisperForConditionalGeneration(**keep)
+    model.load_state_dict({k: v.float() for k, v in sd.items()})
+    return model.eval()
+
+
+def synthetic_whisper_state_dict(config, seed: int = 0):
+    """Seeded weights under transformers' keys at scales where greedy decoding moves: embeddings std 0.03, decoder positions 0.7, the
+    encoder's sinusoids, matrices N(0, 1.7^2 / fan_in), LayerNorm weights 1 +- 0.1, biases 0.1."""
+    m = WhisperForConditionalGeneration(**config)
+    g = np.random.Generator(np.random.Philox(key=11000 + seed))
+    sd = {}
+    for k, p in m.state_dict().items():
+        r = torch.from_numpy(g.standard_normal(tuple(p.shape), dtype=np.float32))
+        if k == "model.encoder.embed_positions.weight":
+            S, H = p.shape
+            inc = np.log(10000.0) / (H // 2 - 1)
+            t = torch.arange(S)[:, None] * torch.exp(-inc * torch.arange(H // 2))[None]
+            sd[k] = torch.cat([t.sin(), t.cos()], dim=1).float()
+        elif k.endswith("embed_tokens.weight"):
+            sd[k] = 0.03 * r
+        elif k.endswith("embed_positions.weight"):
+            sd[k] = 0.7 * r
+        elif "layer_norm" in k:
+            sd[k] = (1.0 if k.endswith(".weight") else 0.0) + 0.1 * r
+        elif k.endswith(".bias"):
+            sd[k] = 0.1 * r
+        else:
+            sd[k] = r * (1.7 / float(np.sqrt(p[0].numel())))
+    return sd
