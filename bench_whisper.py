@@ -2,11 +2,15 @@
 """Whisper benchmark at whisper-medium's geometry (d 1024, 24 + 24 layers, 16 heads, V 51,865, S 1500; seeded weights).
 
     python bench_whisper.py [--runs 5] [--warmup 2] [--quick] [--json PATH]
+    python bench_whisper.py --decode [--runs 5] [--warmup 2] [--quick] [--json PATH]
 
   encoder       `encode` at B = 1 and 8
   decode        time per token at B = 1 and 8: greedy decoding of 65 tokens minus greedy decoding of 1 token (both hold the encoder and
                 the cross keys / values), over the 64 steps between them; eos is suppressed so every item runs them all
   transcribe    the whole `transcribe_ids` at B = 8 x 30 s (log-mel, encoder, 4 prompt tokens, 128 new tokens)
+  --decode      instead of the above: time per token of `decode` (the timestamp rules, `us_whisper_decode`) against `generate` (plain greedy,
+                `us_whisper_generate`) at B = 1 and 8, measured the same way, and one selection step alone (`us_whisper_select`: the host's
+                call and its three launches) at V tokens for B = 1, 8 and 16
 Two legs, alternating run by run on the same GPU after the warm-up, timed by device events; median [min, max]:
   hip           the library (unitspeech_amd.whisper.WhisperForConditionalGeneration)
   eager         the fp32 torch restatement with its key/value cache (tools/whisper_torch.py) on the device
@@ -30,7 +34,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from whisper_torch import WhisperTorch  # noqa: E402
-from unitspeech_amd.whisper import MEDIUM, WhisperForConditionalGeneration, log_mel_spectrogram, synthetic_whisper_state_dict  # noqa: E402
+from unitspeech_amd.whisper import (MEDIUM, WhisperForConditionalGeneration, log_mel_spectrogram, select_tokens,  # noqa: E402
+                                    synthetic_whisper_state_dict)
 
 QUICK = dict(d_model=64, encoder_attention_heads=2, decoder_attention_heads=2, encoder_layers=2, decoder_layers=2, encoder_ffn_dim=128,
              decoder_ffn_dim=128, num_mel_bins=80, max_source_positions=1500, max_target_positions=448, vocab_size=203)
@@ -82,17 +87,63 @@ def copy_rate(dev):
     return 2 * a.numel() * 4 / (ms * 1e-3)
 
 
+def decode_legs(a, c, dev):
+    """`decode` against `generate`, per token, and the selection step alone"""
+    V = c["vocab_size"]
+    eos, nt = (50257, 50363) if V == 51865 else (V - 25, V - 13)
+    hip = WhisperForConditionalGeneration(**c, eos_token_id=eos)
+    hip.load_state_dict(synthetic_whisper_state_dict(c, 0))
+    hip = hip.to(dev).eval()
+    rows, box = [], {}
+    for B in (1, 8):
+        x = features(B, c, dev, B)
+        legs = {"generate": lambda n: box.__setitem__("g", hip.generate(x, [1, 2, 3, nt], n, suppress_tokens=[eos])[0]),
+                "decode": lambda n: box.__setitem__("d", hip.decode(x, [1, 2, 3], no_timestamps_id=nt, no_speech_id=nt - 1, max_new_tokens=n,
+                                                                   suppress_tokens=[eos]).tokens)}
+        ts = alternate({f"{k}_{n}": (lambda k=k, n=n: legs[k](n)) for n in (1, STEPS + 1) for k in legs}, a.runs, a.warmup)
+        per = {k: [(n - o) / STEPS for n, o in zip(ts[f"{k}_{STEPS + 1}"], ts[f"{k}_1"])] for k in legs}
+        stamps = int((box["d"] > nt).sum())
+        rows.append(dict(stage="decode_per_token", B=B, steps=STEPS, **{k: stats(v) for k, v in per.items()},
+                         first_token={k: stats(ts[f"{k}_1"]) for k in legs}, timestamps_emitted=stamps, tokens=int(box["d"].numel())))
+        print(f"per token B={B}: decode {statistics.median(per['decode']):.4f} ms  generate {statistics.median(per['generate']):.4f} ms  "
+              f"({stamps} of {box['d'].numel()} tokens are timestamps)", flush=True)
+    g = torch.Generator().manual_seed(7)
+    reps = 50
+    for B in (1, 8, 16):
+        lg = (3 * torch.randn(B, V, generator=g)).to(dev)
+        hist = [(2, nt + 3, 5, nt + 3, 0)] * B
+
+        def sel():
+            for _ in range(reps):
+                select_tokens(lg, hist, eos_token_id=eos, no_timestamps_id=nt)
+
+        ts = alternate(dict(select=sel), a.runs, a.warmup)
+        rows.append(dict(stage="select_call", B=B, V=V, calls=reps, **{k: stats([t / reps for t in v]) for k, v in ts.items()}))
+        print(f"select B={B} V={V}: {statistics.median(ts['select']) / reps * 1e3:.1f} us per call (host call + 3 launches)", flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--quick", action="store_true", help="a tiny geometry: a functional check, not a measurement")
     ap.add_argument("--json", type=str, default=None)
+    ap.add_argument("--decode", action="store_true", help="only `decode` against `generate` and the selection step alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("CUDA/ROCm is not available: the recogniser has no CPU fallback")
     dev = torch.device("cuda", 0)
     c = dict(QUICK if a.quick else MEDIUM)
+    if a.decode:
+        out = {"bench": "whisper_decode", "geometry": "quick" if a.quick else "whisper-medium", "config": c, "runs": a.runs, "warmup": a.warmup,
+               "device": torch.cuda.get_device_name(0), "rows": decode_legs(a, c, dev)}
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+                f.write("\n")
+        print(json.dumps(out))
+        return
     V, eos = c["vocab_size"], c["vocab_size"] - 1
     sd = synthetic_whisper_state_dict(c, 0)
     hip = WhisperForConditionalGeneration(**c, eos_token_id=eos)

@@ -6,7 +6,7 @@ its text by character and word error rate, compare its speaker embedding with th
                        [--speaker_encoder_path EMBEDDER.pt] [--batch 16] [--timestamps] [--out RESULT.json]
     python evaluate.py --synthetic 12 --batch 4
     python evaluate.py --filelist LIST --recogniser whisper --whisper_checkpoint DIR [--language ro]
-    python evaluate.py --synthetic 6 --batch 4 --recogniser whisper
+    python evaluate.py --synthetic 6 --batch 4 --recogniser whisper [--whisper_timestamps]
 
 LIST holds one `wav|transcript[|reference_wav]` line per sample.  CTC.pt is a `torch.save`d state dict of `transformers.HubertForCTC` or
 `Wav2Vec2ForCTC` in the base form (the class is taken from the keys; nothing is fetched by name; the base size unless --config_path
@@ -23,10 +23,14 @@ out_int16=True)`), before the recogniser and the speaker encoder see it: the ref
 recordings of the third column are left as they are.
 
 --recogniser whisper transcribes with `unitspeech_amd.whisper.WhisperForConditionalGeneration` instead, as the reference's notebook does
-(`whisper.load_model("medium")`, `pad_or_trim`, `log_mel_spectrogram`, `decode` with default options: greedy, no timestamps).  DIR holds
+(`whisper.load_model("medium")`, `pad_or_trim`, `log_mel_spectrogram`, `decode`).  The notebook's `DecodingOptions()` are greedy decoding
+under the timestamp rules (`without_timestamps=False`): that is --whisper_timestamps; without the flag the decoding is plain greedy with
+<|notimestamps|> in the prompt, which can give another transcript.  DIR holds
 `config.json`, the weights (`pytorch_model.bin`, or `model.safetensors` where that package imports), `vocab.json` and `added_tokens.json`
 (and `generation_config.json` for the suppression lists).  The prompt is <|startoftranscript|>, the language, <|transcribe|>,
-<|notimestamps|>; without --language the language is detected per file.  The same length-sorted batches feed it; hypotheses and references are
+<|notimestamps|>; without --language the language is detected per file.  With --whisper_timestamps the prompt ends at <|transcribe|>, every
+step applies the timestamp rules (`WhisperForConditionalGeneration.decode`), and each file's record gains `avg_logprob`, `no_speech_prob`
+(where the vocabulary has <|nospeech|> or <|nocaptions|>) and `segments` ([start_s, end_s, text] from the timestamp pairs).  The same length-sorted batches feed it; hypotheses and references are
 brought to lower-case letters, digits, apostrophes and single spaces before scoring.  Files longer than 30 s are refused.
 
 --synthetic N runs without files: a seeded tiny CTC model, N seeded waveforms, and as transcripts the model's own decodings with a known
@@ -103,14 +107,26 @@ def padded_batch(wavs16, idx):
 
 
 @torch.no_grad()
-def transcribe_all(model, vocabulary, wavs16, max_batch):
-    """16 kHz waveforms [T_i] on the device -> their transcripts, in the order given; one read back per batch, of the tokens."""
+def transcribe_all(model, vocabulary, wavs16, max_batch, scores=None):
+    """16 kHz waveforms [T_i] on the device -> their transcripts, in the order given; one read back per batch, of the tokens.
+    scores: a list that makes Whisper decode under the timestamp rules and receives per file dict(avg_logprob, no_speech_prob, segments)."""
     texts = [None] * len(wavs16)
     batches = plan_batches([int(w.shape[0]) for w in wavs16], max_batch)
+    if scores is not None:
+        scores[:] = [None] * len(wavs16)
     for idx in batches:
         x, n = padded_batch(wavs16, idx)
-        tokens, count = model.transcribe_ids(x, n)
-        for i, t in zip(idx, vocabulary.decode(tokens.cpu(), count.cpu())):
+        if scores is None:
+            tokens, count = model.transcribe_ids(x, n)
+            tokens, count = tokens.cpu(), count.cpu()
+        else:
+            r = model.transcribe_ids(x, n, timestamps=True)
+            tokens, count, avg = r.tokens.cpu(), r.lengths.cpu(), r.avg_logprob.cpu().tolist()
+            ns = r.no_speech_prob.cpu().tolist() if r.no_speech_prob is not None else [None] * len(idx)
+            for b, i in enumerate(idx):
+                scores[i] = dict(avg_logprob=avg[b], no_speech_prob=ns[b],
+                                 segments=[list(sg) for sg in vocabulary.segments(tokens[b, :int(count[b])])])
+        for i, t in zip(idx, vocabulary.decode(tokens, count)):
             texts[i] = t
     return texts, batches
 
@@ -184,22 +200,38 @@ TINY_WHISPER = dict(d_model=64, encoder_attention_heads=2, decoder_attention_hea
                     decoder_ffn_dim=128, num_mel_bins=80, max_source_positions=1500, max_target_positions=32, vocab_size=36)
 
 
-def synthetic_whisper(device, seed: int = 0):
-    """A seeded tiny Whisper over the letters, the space and the special tokens, and its vocabulary."""
+SYNTHETIC_TIMESTAMPS = 8         # --whisper_timestamps: <|0.00|> ... <|0.14|> behind <|notimestamps|>
+
+
+def synthetic_whisper(device, seed: int = 0, timestamps: bool = False):
+    """A seeded tiny Whisper over the letters, the space and the special tokens, and its vocabulary.  timestamps: a vocabulary (and an
+    embedding) longer by <|nospeech|> in front of <|notimestamps|> and SYNTHETIC_TIMESTAMPS timestamp tokens behind it."""
     from unitspeech_amd.whisper import WhisperForConditionalGeneration, WhisperVocabulary, synthetic_whisper_state_dict
     vocab = {**{c: i for i, c in enumerate("abcdefghijklmnopqrstuvwxyz")}, "\u0120": 26}          # GPT-2's spelling of the space
-    added = {t: 27 + i for i, t in enumerate(("<|endoftext|>", "<|startoftranscript|>", "<|ro|>", "<|en|>", "<|transcribe|>", "<|notimestamps|>"))}
+    special = ("<|endoftext|>", "<|startoftranscript|>", "<|ro|>", "<|en|>", "<|transcribe|>", "<|notimestamps|>")
+    config = dict(TINY_WHISPER)
+    if timestamps:
+        special = special[:-1] + ("<|nospeech|>", "<|notimestamps|>") + tuple(f"<|{0.02 * i:.2f}|>" for i in range(SYNTHETIC_TIMESTAMPS))
+        config["vocab_size"] = 27 + len(special)
+    added = {t: 27 + i for i, t in enumerate(special)}
     vocabulary = WhisperVocabulary(vocab, added)
-    model = WhisperForConditionalGeneration(**TINY_WHISPER, eos_token_id=vocabulary.end_id, suppress_tokens=sorted(added.values())[1:])
-    model.load_state_dict(synthetic_whisper_state_dict(TINY_WHISPER, seed))
+    suppress = [i for t, i in sorted(added.items(), key=lambda kv: kv[1])[1:] if not t[2:-2].replace(".", "").isdigit()]
+    model = WhisperForConditionalGeneration(**config, eos_token_id=vocabulary.end_id, suppress_tokens=suppress)
+    model.load_state_dict(synthetic_whisper_state_dict(config, seed))
     return model.to(device).eval(), vocabulary
 
 
 def whisper_prompt(model, vocabulary, language):
-    """The notebook's default options: transcribe, no timestamps; the language given, or detected among the vocabulary's."""
+    """Transcribe, <|notimestamps|> last (`transcribe_ids(timestamps=True)`, the notebook's default options, leaves it out); the language
+    given, or detected among the vocabulary's."""
     model.prompt_ids = [vocabulary.start_id, vocabulary.language_id(language) if language else None, vocabulary.transcribe_id,
                         vocabulary.notimestamps_id]
     model.language_ids = vocabulary.language_ids()
+    model.no_timestamps_id = vocabulary.notimestamps_id
+    try:
+        model.no_speech_id = vocabulary.nospeech_id
+    except KeyError:
+        model.no_speech_id = None
     if model.eos_token_id is None:
         model.eos_token_id = vocabulary.end_id
 
@@ -222,6 +254,8 @@ def main(argv=None):
     ap.add_argument("--recogniser", choices=("ctc", "whisper"), default="ctc")
     ap.add_argument("--whisper_checkpoint", default=None, help="--recogniser whisper: directory with config.json, weights, vocab.json, added_tokens.json")
     ap.add_argument("--language", default=None, help="--recogniser whisper: the language token's name (ro); detected per file when absent")
+    ap.add_argument("--whisper_timestamps", action="store_true",
+                    help="--recogniser whisper: decode under the timestamp rules (whisper.decode's defaults); adds avg_logprob, no_speech_prob, segments")
     ap.add_argument("--blank", default="<pad>")
     ap.add_argument("--word_delimiter", default="|")
     ap.add_argument("--normalize", action="store_true", help="zero mean, unit variance per waveform (a feature extractor with do_normalize)")
@@ -235,6 +269,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+    if args.whisper_timestamps and args.recogniser != "whisper":
+        raise SystemExit("--whisper_timestamps belongs to --recogniser whisper")
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm device: the HIP recogniser has no CPU fallback")
     from unitspeech_amd.asr import CTCVocabulary, error_rates, load_ctc_checkpoint, normalize_text
@@ -244,7 +280,7 @@ def main(argv=None):
     if whisper and (args.timestamps or args.normalize):
         raise SystemExit("--timestamps and --normalize belong to the CTC recogniser")
     if args.synthetic:
-        model, vocabulary = synthetic_whisper(device, args.seed) if whisper else synthetic_model(device, args.seed)
+        model, vocabulary = synthetic_whisper(device, args.seed, args.whisper_timestamps) if whisper else synthetic_model(device, args.seed)
         items = synthetic_waves(args.synthetic, args.seed)
         transcripts, references = None, [None] * len(items)
     else:
@@ -290,7 +326,8 @@ def main(argv=None):
         model.pad_token_id = vocabulary.blank_id
     if args.normalize:
         wavs16 = [(w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7) for w in wavs16]
-    hyps, batches = transcribe_all(model, vocabulary, wavs16, args.batch)
+    scores = [] if args.whisper_timestamps else None
+    hyps, batches = transcribe_all(model, vocabulary, wavs16, args.batch, scores)
     if whisper:
         hyps = [normalize_text(h, vocabulary) for h in hyps]
     result = {}
@@ -310,6 +347,8 @@ def main(argv=None):
             rec["secs"] = s
         if words is not None:
             rec["word_times"] = words[k]
+        if scores is not None:
+            rec.update(scores[k])
         files.append(rec)
         print(f"{name}: CER {p['cer']:.4f} ({p['char_distance']}/{p['chars']})  WER {p['wer']:.4f} ({p['word_distance']}/{p['words']})"
               + (f"  SECS {s:.4f}" if s is not None else "") + f"  | {h!r} <- {t!r}")

@@ -743,7 +743,9 @@ int us_wavlm_forward(us_wavlm_handle h, const float* wav, const int64_t* lengths
  * (logits and tokens).
  * us_whisper_create returns US_EINVAL for a d_model the heads do not divide, a head dimension above 64 or not a multiple of 4, a decoder
  * feed-forward size that is no multiple of 4, and max_source_positions or max_target_positions above 2048.
- * Not built: the timestamp-token rules (callers put <|notimestamps|> in the prompt), beam search, temperature fallback, fp16 weights. */
+ * us_whisper_generate is plain greedy decoding (callers put <|notimestamps|> in the prompt); us_whisper_decode is greedy decoding under the
+ * timestamp rules, what openai's `whisper.decode(model, mel, DecodingOptions())` runs by default (without_timestamps=False).
+ * Not built: beam search, temperature fallback, fp16 weights. */
 typedef struct us_whisper* us_whisper_handle;
 typedef struct us_whisper_config {
   int32_t n_mels;
@@ -776,6 +778,51 @@ int us_whisper_decoder_logits(us_whisper_handle h, const float* features, int B,
 int us_whisper_generate(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P, int max_new, int64_t eos,
                         const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* tokens, int64_t* n, void* workspace,
                         size_t workspace_bytes, us_stream stream);
+
+/* Greedy decoding under the timestamp rules (openai's SuppressTokens, SuppressBlank, ApplyTimestampRules and GreedyDecoder.update at
+ * temperature 0; transformers' WhisperTimeStampLogitsProcessor is the same rule text).  With tb = no_timestamps + 1, the first timestamp token,
+ * and an item's sampled tokens so far:
+ *   no_timestamps is never chosen; last_ts: at least one token sampled and the last one >= tb; pen_ts: fewer than two sampled, or the
+ *   penultimate one >= tb.  last_ts && pen_ts: every token >= tb is masked.  last_ts && !pen_ts: every token < eos is masked (tokens in
+ *   [eos, tb) stay allowed).  After any timestamp, with `last` the last one sampled: [tb, last) is masked when last_ts && !pen_ts, else
+ *   [tb, last + 1).  At the first generated position every token < tb is masked, and with max_initial_timestamp_index >= 0 every token
+ *   > tb + index.  Then, if the log-sum-exp of the surviving timestamp logits is strictly greater than the largest surviving text logit,
+ *   all text is masked (equality keeps text; an empty side is -inf).  The token is the argmax of what survives, the lower index on an exact
+ *   tie; its log-probability is x[token] - logsumexp(surviving logits).  Where nothing survives the item ends with eos at log-probability 0.
+ * An item ends at eos; the log-probabilities of all its steps, the one that emits eos included, are summed into sum_logprobs.  The stage is
+ * two launches per step (partial sums over chunks of 512 logits, then one workgroup per item), without atomics on floats: an item has the
+ * same bits alone, in any batch and in repeated calls. */
+typedef struct us_whisper_decode_options {
+  int32_t eos;                          /* 0 <= eos < no_timestamps */
+  int32_t no_timestamps;                /* no_timestamps + 1 < vocab_size */
+  int32_t max_initial_timestamp_index;  /* -1: none */
+  int32_t no_speech;                    /* -1: none; else no_speech_prob is computed */
+  int32_t sot_index;                    /* the start token's place in the prompt, in [0, P): where no_speech_prob is read */
+  int32_t max_new;                      /* us_whisper_decode: P + max_new <= max_target_positions */
+} us_whisper_decode_options;
+/* As us_whisper_generate (prompt on the host, nothing allocated, the stream awaited every 8 steps), under the rules above.  -> tokens
+ * [B][max_new] int64 with eos at and after an item's end, n [B] int64, sum_logprobs [B] fp32 and, when options->no_speech >= 0,
+ * no_speech_prob [B] fp32 = softmax(unmasked logits after prompt[.][sot_index])[no_speech] (one more vocabulary GEMM); all on the device.
+ * US_EINVAL for eos >= no_timestamps, no_timestamps + 1 >= vocab_size, sot_index outside the prompt, P + max_new beyond
+ * max_target_positions.  The workspace is us_whisper_workspace_bytes(h, B), which includes the stage's state and partials. */
+int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P,
+                      const us_whisper_decode_options* options, const unsigned char* suppress, const unsigned char* begin_suppress,
+                      int64_t* tokens, int64_t* n, float* sum_logprobs, float* no_speech_prob, void* workspace, size_t workspace_bytes,
+                      us_stream stream);
+/* One selection step without a handle, through the same two kernels: logits [B][V] (device, any B >= 1, walked in groups of 16), the
+ * histories HOST [B], masks as above -> token [B] int64, logprob [B] fp32, decided_timestamp [B] int32 (1: the timestamps won the decision),
+ * on the device.  A done item returns eos, 0 and 0.  options->eos, no_timestamps and max_initial_timestamp_index are read.  scratch: device,
+ * us_whisper_select_scratch_bytes(V). */
+typedef struct us_whisper_history {
+  int32_t n_sampled;                    /* tokens sampled so far; 0: the first generated position */
+  int32_t last, penultimate;            /* read when n_sampled >= 1 / >= 2 */
+  int32_t last_timestamp;               /* the last sampled token >= tb, or -1 */
+  int32_t done;
+} us_whisper_history;
+size_t us_whisper_select_scratch_bytes(int V);
+int us_whisper_select(const float* logits, int B, int V, const us_whisper_history* history, const us_whisper_decode_options* options,
+                      const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* token, float* logprob,
+                      int32_t* decided_timestamp, void* scratch, size_t scratch_bytes, us_stream stream);
 
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102

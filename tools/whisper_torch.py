@@ -1,12 +1,20 @@
 """A torch restatement of `transformers.WhisperForConditionalGeneration` in eval mode, at a chosen dtype: the encoder, the decoder one
-position at a time over a key/value cache, and the greedy loop of `us_whisper_generate`.  In fp64 it is the yardstick the goldens are checked
+position at a time over a key/value cache, the greedy loop of `us_whisper_generate` and the loop under the timestamp rules of
+`us_whisper_decode` (`decode`; the rules are tools/whisper_decode_numpy.py's, at the same dtype).  In fp64 it is the yardstick the goldens are checked
 with (tests/test_whisper.py), in fp32 its distance to the golden sets the bar of the GPU tests, and on the device it is bench_whisper.py's
 eager leg.
 
 `sd`: the state_dict (keys `model.encoder.*`, `model.decoder.*`); `c`: transformers' configuration fields by name.
 """
+import os
+import sys
+
+import numpy as np
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import whisper_decode_numpy as rules  # noqa: E402
 
 
 def golden_state_dict(g):
@@ -126,3 +134,41 @@ class WhisperTorch:
             if stop_early and (i + 1) % 8 == 0 and bool(done.all()):
                 break
         return tokens, n
+
+    def decode(self, feats, prompt, max_new, layout, sot_index=0, trace=None):
+        """Greedy decoding under the timestamp rules (`layout`: see tools/whisper_decode_numpy.py), the selection in this object's dtype
+        -> dict(tokens [B, max_new] with eos at and after an item's end, lengths [B], logprobs [B, max_new] fp64 (0 after the end),
+        sum_logprob [B] fp64, no_speech_prob [B] fp64 or None).  trace: a list that receives every step's unmasked logits [B, V]."""
+        np_dtype = {torch.float64: np.float64, torch.float32: np.float32}[self.dtype]
+        state = self.start(self.encode(feats))
+        prompt = prompt.to(self.device)
+        B, P = prompt.shape
+        eos, ns = int(layout["eos"]), layout.get("no_speech")
+        sup, beg = rules.masks(layout, self.c["vocab_size"])
+        nsp = None
+        for t in range(P - 1):
+            lg = self.step(state, prompt[:, t], t, logits=ns is not None and t == sot_index)
+            if lg is not None:
+                nsp = np.asarray([rules.no_speech_prob(r, int(ns), np_dtype) for r in lg.cpu().numpy()])
+        tokens = np.full((B, max_new), eos, dtype=np.int64)
+        lps, lengths, sampled, done = np.zeros((B, max_new)), np.full(B, max_new, dtype=np.int64), [[] for _ in range(B)], [False] * B
+        cur = prompt[:, P - 1]
+        for i in range(max_new):
+            lg = self.step(state, cur, P - 1 + i)
+            if trace is not None:
+                trace.append(lg.clone())
+            rows = lg.cpu().numpy()
+            if i == 0 and ns is not None and sot_index == P - 1:
+                nsp = np.asarray([rules.no_speech_prob(r, int(ns), np_dtype) for r in rows])
+            for b in range(B):
+                if done[b]:
+                    continue
+                r = rules.select(rows[b], sampled[b], layout, sup, beg, np_dtype)
+                tokens[b, i], lps[b, i] = r["token"], r["logprob"]
+                sampled[b].append(r["token"])
+                if r["token"] == eos:
+                    done[b], lengths[b] = True, i
+            cur = torch.from_numpy(tokens[:, i]).to(self.device)
+            if all(done):
+                break
+        return dict(tokens=tokens, lengths=lengths, logprobs=lps, sum_logprob=lps.sum(1), no_speech_prob=nsp)

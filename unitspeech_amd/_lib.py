@@ -77,6 +77,14 @@ class us_whisper_config(C.Structure):
                                          "decoder_ffn", "max_source_positions", "max_target_positions", "vocab_size")]
 
 
+class us_whisper_decode_options(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("eos", "no_timestamps", "max_initial_timestamp_index", "no_speech", "sot_index", "max_new")]
+
+
+class us_whisper_history(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_sampled", "last", "penultimate", "last_timestamp", "done")]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/unitspeech_hip.h
 SIGNATURES = {
     "us_decoder_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(us_config)]),
@@ -196,6 +204,11 @@ SIGNATURES = {
                                             C.c_size_t, C.c_void_p]),
     "us_whisper_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_whisper_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(us_whisper_decode_options),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_whisper_select_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "us_whisper_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(us_whisper_history), C.POINTER(us_whisper_decode_options), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),

@@ -14,6 +14,14 @@
 //  - wh_cross_attn_kernel: one query over the item's planar cross keys / values [layer][item][2 d_model][S], sixteen waves.
 //  - wh_argmax_kernel: the suppression masks, then (value, index) argmax per item with the lower index on exact ties (torch.argmax), the end of
 //    an item (eos) and the count of items still running.
+//  - wh_select_partial_kernel + wh_select_close_kernel: the selection stage of us_whisper_decode and us_whisper_select.  SuppressTokens,
+//    begin-suppress, the timestamp rules and the greedy choice at temperature 0 from the step's logits and the item's history on the
+//    device (tokens sampled, last, penultimate, last timestamp, done).  The partial kernel runs on a (chunk of kWhChunk logits, item) grid
+//    and writes, for the text side [0, timestamp_begin) and the timestamp side separately, the largest surviving logit, its index (the
+//    lower one on a tie) and sum exp(x - max); the closing kernel, one workgroup per item, joins the partials by a tree fixed by the
+//    chunk index, decides (the log-sum-exp of the timestamps strictly above the best text logit: a timestamp), and writes the token, its
+//    log-probability and the new history.  No atomics on floats; an item's summation order depends on V alone.
+//  - wh_nospeech_kernel: softmax(unfiltered logits)[no_speech] at the start token's position, from the partial kernel's plain mode.
 // No kernel waits on a value another kernel writes; the host loop runs at most max_new steps and reads the running count back every
 // kWhPoll steps.  Every reduction has a fixed order and no launch depends on the batch: an item alone or in a batch, and repeated calls, give
 // the same bits.
@@ -289,6 +297,255 @@ __global__ __launch_bounds__(256) void wh_argmax_kernel(const float* __restrict_
   }
 }
 
+// ---- the selection stage under the timestamp rules ----------------------------------------------------------------------------------
+
+constexpr int kWhChunk = 512;       // logits per workgroup of the partial kernel: 102 chunks at V = 51,865
+
+struct WhRules {
+  int eos, tb, max_init;            // tb = no_timestamps + 1: the first timestamp token; max_init -1: no cap at the first position
+};
+struct WhPart {                     // one side of one chunk: the largest surviving logit (-inf: none), sum exp(x - m), the index of m
+  float m, s;
+  int bi, pad;
+};
+struct WhDecState {                 // a group's loop state in the workspace; cur / done / running as WhGenState
+  int *cur, *done, *running;
+  int *count, *last, *pen, *last_ts;        // [kWhItems] tokens sampled so far, the last two of them, the last timestamp (-1: none)
+  double* sum;                      // [kWhItems] the sum of the log-probabilities
+};
+struct WhHistory {                  // us_whisper_select: the group's histories, from the host
+  int count[kWhItems], last[kWhItems], pen[kWhItems], last_ts[kWhItems], done[kWhItems];
+};
+constexpr int kWhNone = 0x7fffffff;
+
+__device__ __forceinline__ void wh_take(float& bv, int& bi, float ov, int oi) {       // the larger value, the lower index on a tie
+  if (ov > bv || (ov == bv && oi < bi)) {
+    bv = ov;
+    bi = oi;
+  }
+}
+// (value, index) of every thread of a 256-thread workgroup -> the best of all in every thread; red: 4 slots each
+__device__ __forceinline__ void wh_block_best(float& bv, int& bi, float* rv, int* ri) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) wh_take(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
+  __syncthreads();
+  if (lane == 0) {
+    rv[wave] = bv;
+    ri[wave] = bi;
+  }
+  __syncthreads();
+  bv = rv[0];
+  bi = ri[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) wh_take(bv, bi, rv[w], ri[w]);
+}
+// one value per thread -> the workgroup's sum in every thread: the wave butterfly, then the four waves in order
+__device__ __forceinline__ float wh_block_sum(float v, float* rs) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  v = wave_sum(v);
+  __syncthreads();
+  if (lane == 0) rs[wave] = v;
+  __syncthreads();
+  return ((rs[0] + rs[1]) + rs[2]) + rs[3];
+}
+
+// grid: (chunks, items).  plain: every token survives and counts as text (the no-speech probability).
+__global__ __launch_bounds__(256) void wh_select_partial_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ suppress,
+                                                                const unsigned char* __restrict__ begin, WhDecState st, WhRules r,
+                                                                WhPart* __restrict__ part, int V, int nchunks, int plain) {
+  __shared__ float rv[4], rs[4];
+  __shared__ int ri[4];
+  const int tid = threadIdx.x, chunk = blockIdx.x, m = blockIdx.y;
+  // the surviving ranges of the two sides
+  int text_lo = 0, text_hi = r.tb, ts_lo = r.tb, ts_hi = V, first = 0, no_ts = r.tb - 1;
+  if (plain) {
+    text_hi = V;
+    ts_lo = V;
+    no_ts = -1;
+  } else {
+    const int count = st.count[m], last = st.last[m], pen = st.pen[m], lts = st.last_ts[m];
+    const bool last_is = count >= 1 && last >= r.tb, pen_is = count < 2 || pen >= r.tb;
+    first = count == 0;
+    if (last_is && pen_is) ts_hi = ts_lo;
+    if (last_is && !pen_is) text_lo = r.eos;
+    if (lts >= 0) ts_lo = max(ts_lo, last_is && !pen_is ? lts : lts + 1);
+    if (first) {
+      text_hi = 0;
+      if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init + 1);
+    }
+  }
+  const float* __restrict__ x = logits + (size_t)m * V;
+  float y[2];
+  int side[2];                      // 0 text, 1 timestamp, -1 masked
+  float tv = -INFINITY, sv = -INFINITY;
+  int ti = kWhNone, si = kWhNone;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int v = chunk * kWhChunk + j * 256 + tid;
+    side[j] = -1;
+    y[j] = -INFINITY;
+    if (v >= V || v == no_ts) continue;
+    if (!plain && ((suppress && suppress[v]) || (first && begin && begin[v]))) continue;
+    if (v >= text_lo && v < text_hi) side[j] = 0;
+    else if (v >= ts_lo && v < ts_hi) side[j] = 1;
+    else continue;
+    y[j] = x[v];
+    if (side[j] == 0) wh_take(tv, ti, y[j], v);
+    else wh_take(sv, si, y[j], v);
+  }
+  wh_block_best(tv, ti, rv, ri);
+  wh_block_best(sv, si, rv, ri);
+  float te = 0.f, se = 0.f;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (side[j] == 0 && tv > -INFINITY) te += expf(y[j] - tv);
+    if (side[j] == 1 && sv > -INFINITY) se += expf(y[j] - sv);
+  }
+  te = wh_block_sum(te, rs);
+  se = wh_block_sum(se, rs);
+  if (tid == 0) {
+    part[((size_t)m * 2 + 0) * nchunks + chunk] = WhPart{tv, te, ti, 0};
+    part[((size_t)m * 2 + 1) * nchunks + chunk] = WhPart{sv, se, si, 0};
+  }
+}
+
+// the partials of one side of item m -> (max, its index, sum exp(x - max)) in every thread
+__device__ __forceinline__ void wh_join(const WhPart* __restrict__ p, int nchunks, float& M, int& I, float& S, float* rv, int* ri, float* rs) {
+  M = -INFINITY;
+  I = kWhNone;
+  for (int c = threadIdx.x; c < nchunks; c += 256) wh_take(M, I, p[c].m, p[c].bi);
+  wh_block_best(M, I, rv, ri);
+  float s = 0.f;
+  if (M > -INFINITY)
+    for (int c = threadIdx.x; c < nchunks; c += 256)
+      if (p[c].m > -INFINITY) s += p[c].s * expf(p[c].m - M);
+  S = wh_block_sum(s, rs);
+}
+
+// grid: items.  tokens[m][step], n[m] and the running count as wh_argmax_kernel; sum_out[m] the item's summed log-probability so far;
+// step_lp / decided (or null): this step's log-probability and whether the timestamps won the decision.
+__global__ __launch_bounds__(256) void wh_select_close_kernel(const WhPart* __restrict__ part, WhDecState st, WhRules r, long long* __restrict__ tokens,
+                                                              long long* __restrict__ n, float* __restrict__ sum_out, float* __restrict__ step_lp,
+                                                              int* __restrict__ decided, int nchunks, int max_new, int step) {
+  __shared__ float rv[4], rs[4];
+  __shared__ int ri[4];
+  const int m = blockIdx.x;
+  float Mt, St, Ms, Ss;
+  int It, Is;
+  wh_join(part + ((size_t)m * 2 + 0) * nchunks, nchunks, Mt, It, St, rv, ri, rs);
+  wh_join(part + ((size_t)m * 2 + 1) * nchunks, nchunks, Ms, Is, Ss, rv, ri, rs);
+  if (threadIdx.x != 0 || st.done[m]) return;            // a done item: tokens[m][step] holds eos already
+  const float lse_ts = Ss > 0.f ? Ms + logf(Ss) : -INFINITY;
+  const bool ts_wins = lse_ts > Mt;
+  int tok = r.eos;                                      // nothing survives: the item ends, at no cost
+  float lp = 0.f;
+  if (ts_wins) {
+    tok = Is;
+    lp = Ms - lse_ts;
+  } else if (It != kWhNone) {
+    const float M = fmaxf(Mt, Ms);                      // Mt is finite or It the first of a side of -inf
+    const float S = (Mt > -INFINITY ? St * expf(Mt - M) : 0.f) + (Ms > -INFINITY ? Ss * expf(Ms - M) : 0.f);
+    tok = It;
+    lp = S > 0.f ? Mt - (M + logf(S)) : 0.f;
+  }
+  st.cur[m] = tok;
+  st.pen[m] = st.last[m];
+  st.last[m] = tok;
+  st.count[m] += 1;
+  if (tok >= r.tb) st.last_ts[m] = tok;
+  st.sum[m] += (double)lp;
+  tokens[(size_t)m * max_new + step] = tok;
+  if (sum_out) sum_out[m] = (float)st.sum[m];
+  if (step_lp) step_lp[m] = lp;
+  if (decided) decided[m] = ts_wins ? 1 : 0;
+  if (tok == r.eos) {
+    st.done[m] = 1;
+    atomicSub(st.running, 1);
+  } else {
+    n[m] += 1;
+  }
+}
+
+// grid: items.  out[m] = exp(x[no_speech] - logsumexp(x)) from the plain partials (the text side holds every token)
+__global__ __launch_bounds__(256) void wh_nospeech_kernel(const WhPart* __restrict__ part, const float* __restrict__ logits, float* __restrict__ out,
+                                                          int V, int nchunks, int no_speech) {
+  __shared__ float rv[4], rs[4];
+  __shared__ int ri[4];
+  const int m = blockIdx.x;
+  float M, S;
+  int I;
+  wh_join(part + ((size_t)m * 2 + 0) * nchunks, nchunks, M, I, S, rv, ri, rs);
+  if (threadIdx.x == 0) out[m] = S > 0.f ? expf(logits[(size_t)m * V + no_speech] - (M + logf(S))) : 0.f;
+}
+
+__global__ __launch_bounds__(256) void wh_decode_init_kernel(WhDecState st, long long* __restrict__ tokens, long long* __restrict__ n,
+                                                             float* __restrict__ sum_out, int nb, int max_new, long long eos) {
+  const int tid = threadIdx.x;
+  if (tid < kWhItems) {
+    st.cur[tid] = 0;
+    st.done[tid] = 0;
+    st.count[tid] = 0;
+    st.last[tid] = st.pen[tid] = st.last_ts[tid] = -1;
+    st.sum[tid] = 0.0;
+  }
+  if (tid < nb) {
+    n[tid] = 0;
+    sum_out[tid] = 0.f;
+  }
+  if (tid == 0) *st.running = nb;
+  for (int i = tid; i < nb * max_new; i += 256) tokens[i] = eos;
+}
+
+// us_whisper_select: the host's histories into the state, and what a done item returns
+__global__ __launch_bounds__(64) void wh_select_init_kernel(WhDecState st, WhHistory hist, long long* __restrict__ token, long long* __restrict__ n,
+                                                            float* __restrict__ logprob, int* __restrict__ decided, int nb, long long eos) {
+  const int tid = threadIdx.x;
+  if (tid < kWhItems) {
+    st.cur[tid] = 0;
+    st.done[tid] = hist.done[tid];
+    st.count[tid] = hist.count[tid];
+    st.last[tid] = hist.last[tid];
+    st.pen[tid] = hist.pen[tid];
+    st.last_ts[tid] = hist.last_ts[tid];
+    st.sum[tid] = 0.0;
+    n[tid] = 0;
+  }
+  if (tid < nb) {
+    token[tid] = eos;
+    logprob[tid] = 0.f;
+    decided[tid] = 0;
+  }
+  if (tid == 0) *st.running = nb;
+}
+
+inline int wh_chunks(int V) { return (V + kWhChunk - 1) / kWhChunk; }
+// floats of the selection stage's state and partials: 8 int arrays, the sums (doubles), n (long long), the partials of both sides
+inline size_t wh_select_floats(int V) { return pad64(8 * kWhItems) + pad64(2 * kWhItems) + pad64(2 * kWhItems) + pad64((size_t)kWhItems * 2 * wh_chunks(V) * 4); }
+
+struct WhSelect {                   // the stage's buffers in a scratch of wh_select_floats(V) floats
+  WhDecState st;
+  long long* n;
+  WhPart* part;
+};
+inline WhSelect wh_select_carve(float* base) {
+  int* ints = reinterpret_cast<int*>(base);
+  WhSelect c;
+  c.st = WhDecState{ints, ints + kWhItems, ints + 2 * kWhItems, ints + 3 * kWhItems, ints + 4 * kWhItems, ints + 5 * kWhItems, ints + 6 * kWhItems,
+                    reinterpret_cast<double*>(base + pad64(8 * kWhItems))};
+  c.n = reinterpret_cast<long long*>(base + pad64(8 * kWhItems) + pad64(2 * kWhItems));
+  c.part = reinterpret_cast<WhPart*>(base + pad64(8 * kWhItems) + 2 * pad64(2 * kWhItems));
+  return c;
+}
+
+// the two launches of one selection step of a group
+inline void wh_select_step(const float* L, const unsigned char* suppress, const unsigned char* begin, const WhSelect& c, const WhRules& r, long long* tokens,
+                           long long* n, float* sum_out, float* step_lp, int* decided, int V, int nb, int max_new, int step, hipStream_t s) {
+  const int nc = wh_chunks(V);
+  hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, nb), dim3(256), 0, s, L, suppress, begin, c.st, r, c.part, V, nc, 0);
+  hipLaunchKernelGGL(wh_select_close_kernel, dim3(nb), dim3(256), 0, s, c.part, c.st, r, tokens, n, sum_out, step_lp, decided, nc, max_new, step);
+}
+
 struct WhLinear {
   const float *w = nullptr, *b = nullptr;
 };
@@ -389,7 +646,7 @@ hipError_t wh_prepare(us_whisper* h, hipStream_t s) {
 }
 
 struct WhPlan {                 // float offsets into the aligned workspace
-  size_t enc, planar, kv, cache, x, q, att, ff, logits, state, total;
+  size_t enc, planar, kv, cache, x, q, att, ff, logits, state, select, total;
 };
 
 WhPlan wh_plan(const us_whisper* h, int B) {
@@ -407,6 +664,7 @@ WhPlan wh_plan(const us_whisper* h, int B) {
   p.ff = take((size_t)kWhItems * c.decoder_ffn);
   p.logits = take((size_t)kWhItems * c.vocab_size);
   p.state = take(64);
+  p.select = take(wh_select_floats(c.vocab_size));       // behind everything us_whisper_generate uses
   p.total = take.total;
   return p;
 }
@@ -639,6 +897,118 @@ int us_whisper_generate(us_whisper_handle h, const float* features, int B, int T
       if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
         int running = 1;
         if ((e = hipMemcpyAsync(&running, st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return;
+        if (running <= 0) break;
+      }
+    }
+  });
+  if (e == hipSuccess) e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
+}
+
+size_t us_whisper_select_scratch_bytes(int V) { return V >= 1 && V <= (1 << 24) ? wh_select_floats(V) * sizeof(float) + 256 : 0; }
+
+int us_whisper_select(const float* logits, int B, int V, const us_whisper_history* history, const us_whisper_decode_options* options,
+                      const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* token, float* logprob,
+                      int32_t* decided_timestamp, void* scratch, size_t scratch_bytes, us_stream stream) {
+  const std::string what = "us_whisper_select";
+  auto bad = [&](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, what + ": " + m); };
+  if (!logits || !history || !options || !token || !logprob || !decided_timestamp || B < 1) return bad("bad argument");
+  const auto& o = *options;
+  if (V < 1 || V > (1 << 24)) return bad("V must lie in [1, 2^24]");
+  if (o.eos < 0 || o.eos >= o.no_timestamps) return bad("eos must lie in [0, no_timestamps)");
+  if ((long long)o.no_timestamps + 1 >= V) return bad("no_timestamps + 1 >= V: the vocabulary has no timestamp token");
+  if (o.max_initial_timestamp_index < -1) return bad("max_initial_timestamp_index must be -1 (none) or an index");
+  if (!scratch || scratch_bytes < us_whisper_select_scratch_bytes(V))
+    return WeightTable::fail(nullptr, US_EWORKSPACE, what + ": scratch too small (us_whisper_select_scratch_bytes)");
+  for (int b = 0; b < B; ++b)
+    if (history[b].n_sampled < 0) return bad("history[" + std::to_string(b) + "].n_sampled is negative");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const WhSelect c = wh_select_carve(ws_align(scratch));
+  const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
+  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
+    WhHistory hist{};
+    for (int m = 0; m < kWhItems; ++m) {
+      const us_whisper_history& h = history[b0 + std::min(m, nb - 1)];
+      hist.count[m] = h.n_sampled;
+      hist.last[m] = h.n_sampled >= 1 ? h.last : -1;
+      hist.pen[m] = h.n_sampled >= 2 ? h.penultimate : -1;
+      hist.last_ts[m] = h.last_timestamp >= r.tb ? h.last_timestamp : -1;
+      hist.done[m] = h.done != 0;
+    }
+    long long* tok = reinterpret_cast<long long*>(token) + b0;
+    hipLaunchKernelGGL(wh_select_init_kernel, dim3(1), dim3(64), 0, s, c.st, hist, tok, c.n, logprob + b0, decided_timestamp + b0, nb, (long long)o.eos);
+    wh_select_step(logits + (size_t)b0 * V, suppress, begin_suppress, c, r, tok, c.n, nullptr, logprob + b0, decided_timestamp + b0, V, nb, 1, 0, s);
+  });
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : WeightTable::fail(nullptr, US_EHIP, what + ": " + hipGetErrorString(e));
+}
+
+int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P,
+                      const us_whisper_decode_options* options, const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* tokens,
+                      int64_t* n, float* sum_logprobs, float* no_speech_prob, void* workspace, size_t workspace_bytes, us_stream stream) {
+  const std::string what = "us_whisper_decode";
+  if (!h || !prompt || !options || !tokens || !n || !sum_logprobs || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
+  const auto& c = h->cfg;
+  const auto& o = *options;
+  const int V = c.vocab_size, max_new = o.max_new;
+  if (P < 1 || max_new < 1 || (long long)P + max_new > c.max_target_positions)
+    return h->fail(US_EINVAL, what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
+                                  " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(c.max_target_positions));
+  if (o.eos < 0 || o.eos >= o.no_timestamps)
+    return h->fail(US_EINVAL, what + ": eos = " + std::to_string(o.eos) + " must lie in [0, no_timestamps = " + std::to_string(o.no_timestamps) + ")");
+  if ((long long)o.no_timestamps + 1 >= V)
+    return h->fail(US_EINVAL, what + ": no_timestamps + 1 = " + std::to_string((long long)o.no_timestamps + 1) + " >= vocab_size = " + std::to_string(V) +
+                                  ": the vocabulary has no timestamp token");
+  if (o.max_initial_timestamp_index < -1) return h->fail(US_EINVAL, what + ": max_initial_timestamp_index must be -1 (none) or an index");
+  if (o.no_speech < -1 || o.no_speech >= V) return h->fail(US_EINVAL, what + ": no_speech lies outside the vocabulary (-1: none)");
+  if (o.no_speech >= 0 && !no_speech_prob) return h->fail(US_EINVAL, what + ": a no_speech token needs no_speech_prob");
+  if (o.sot_index < 0 || o.sot_index >= P)
+    return h->fail(US_EINVAL, what + ": sot_index = " + std::to_string(o.sot_index) + " lies outside the prompt of " + std::to_string(P));
+  const std::string badtok = wh_bad_token(what, prompt, (size_t)B * P, V);
+  if (!badtok.empty()) return h->fail(US_EINVAL, badtok);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = wh_begin(h, what, features, B, T, nullptr, true, workspace, workspace_bytes, s);
+  if (rc != US_OK) return rc;
+  const WhPlan p = wh_plan(h, B);
+  float* base = ws_align(workspace);
+  const WhSelect sel = wh_select_carve(base + p.select);
+  const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
+  const int nc = wh_chunks(V);
+  float* L = base + p.logits;
+  hipError_t e = hipSuccess;
+  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
+    if (e != hipSuccess) return;
+    const WhStep t = wh_group(h, p, base, B, b0, nb, s);
+    long long* tok = reinterpret_cast<long long*>(tokens) + (size_t)b0 * max_new;
+    long long* cnt = reinterpret_cast<long long*>(n) + b0;
+    hipLaunchKernelGGL(wh_decode_init_kernel, dim3(1), dim3(256), 0, s, sel.st, tok, cnt, sum_logprobs + b0, nb, max_new, (long long)o.eos);
+    auto no_speech = [&](int pos) {                     // L holds the logits of position `pos`
+      if (o.no_speech < 0 || pos != o.sot_index) return;
+      hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, nb), dim3(256), 0, s, L, nullptr, nullptr, sel.st, r, sel.part, V, nc, 1);
+      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(nb), dim3(256), 0, s, sel.part, L, no_speech_prob + b0, V, nc, o.no_speech);
+    };
+    WhTokens f;
+    for (int pos = 0; pos + 1 < P; ++pos) {             // the prompt but for its last token: keys and values, and the start token's logits
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : 0;
+      wh_embed(t, f, sel.st.cur, pos);
+      wh_layers(t, pos);
+      if (o.no_speech >= 0 && pos == o.sot_index) {
+        wh_logits(t, L, V);
+        no_speech(pos);
+      }
+    }
+    for (int step = 0; step < max_new; ++step) {
+      const int pos = P - 1 + step;
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = step == 0 && m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : step == 0 ? 0 : -1;
+      wh_embed(t, f, sel.st.cur, pos);
+      wh_layers(t, pos);
+      wh_logits(t, L, V);
+      if (step == 0) no_speech(pos);
+      wh_select_step(L, suppress, begin_suppress, sel, r, tok, cnt, sum_logprobs + b0, nullptr, nullptr, V, nb, max_new, step, s);
+      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
+        int running = 1;
+        if ((e = hipMemcpyAsync(&running, sel.st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return;
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return;
         if (running <= 0) break;
       }

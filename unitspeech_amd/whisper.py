@@ -2,14 +2,17 @@
 with `whisper.load_model`, `pad_or_trim`, `log_mel_spectrogram` and `decode(model, mel, DecodingOptions())`.
 
 `WhisperForConditionalGeneration` takes transformers' configuration fields by keyword and its state_dict; `log_mel_spectrogram` is Whisper's
-feature extraction in torch ops; `WhisperVocabulary` turns ids into text.  Greedy decoding only: no timestamp rules (put `<|notimestamps|>` in
-the prompt), no beam search, no temperature fallback, no window beyond 30 s (a longer item is refused), fp32 weights.
+feature extraction in torch ops; `WhisperVocabulary` turns ids into text.  `generate` is plain greedy decoding (no timestamp rules: put `<|notimestamps|>` in
+the prompt); `decode` is greedy decoding under the timestamp rules, with `avg_logprob` and `no_speech_prob`: what
+`whisper.decode(model, mel, DecodingOptions())` runs by default (`without_timestamps=False`).  No beam search, no temperature fallback, no
+window beyond 30 s (a longer item is refused), fp32 weights.
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -73,6 +76,24 @@ class _ScoringAlphabet:
         return iter("abcdefghijklmnopqrstuvwxyz '")
 
 
+TIME_PRECISION = 0.02           # seconds per timestamp index
+
+
+@dataclass
+class WhisperDecoding:
+    """what `WhisperForConditionalGeneration.decode` returns, on the device: tokens [B, L] int64 (eos at and after an item's end), lengths
+    [B] int64, sum_logprob [B] fp32 (every generated token, the closing eos included), no_speech_prob [B] fp32 or None"""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    sum_logprob: torch.Tensor
+    no_speech_prob: torch.Tensor | None
+
+    @property
+    def avg_logprob(self):
+        """openai's: sum_logprob / (length + 1)"""
+        return self.sum_logprob / (self.lengths + 1).to(self.sum_logprob.dtype)
+
+
 class WhisperVocabulary:
     """`vocab.json` (token -> id, tokens in GPT-2's byte alphabet) and optionally `added_tokens.json` (the special tokens) of a Whisper
     tokenizer; either may be a path or a dict.  `decode(ids)` drops the special tokens (anything written `<|...|>`, every added token and
@@ -102,6 +123,34 @@ class WhisperVocabulary:
     transcribe_id = property(lambda self: self.token_id("<|transcribe|>"))
     notimestamps_id = property(lambda self: self.token_id("<|notimestamps|>"))
     end_id = property(lambda self: self.token_id("<|endoftext|>"))
+    timestamp_begin = property(lambda self: self.notimestamps_id + 1)
+
+    @property
+    def nospeech_id(self) -> int:
+        for t in ("<|nospeech|>", "<|nocaptions|>"):     # the older vocabularies spell it the second way
+            if t in self.token_to_id:
+                return self.token_to_id[t]
+        raise KeyError("WhisperVocabulary: neither <|nospeech|> nor <|nocaptions|>")
+
+    def segments(self, ids):
+        """ids with timestamp tokens (>= timestamp_begin, 0.02 s per index) -> [(start_s, end_s, text)]: the text between a timestamp and
+        the next one.  Text in front of any timestamp starts at None; an unclosed last segment ends at None; of two timestamps in a
+        row the first closes a segment and the second opens the next."""
+        tb = self.timestamp_begin
+        out, start, text = [], None, []
+        for i in (int(v) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)):
+            if i >= tb:
+                t = round((i - tb) * TIME_PRECISION, 2)
+                if text:
+                    out.append((start, t, self.decode(text)))
+                    start, text = None, []
+                else:
+                    start = t
+            elif i not in self.special and i in self.id_to_token:
+                text.append(i)
+        if text:
+            out.append((start, None, self.decode(text)))
+        return out
 
     def language_id(self, language: str) -> int:
         return self.token_id(f"<|{language}|>")
@@ -151,6 +200,8 @@ class WhisperForConditionalGeneration(HandleModule):
                 raise ValueError(f"WhisperForConditionalGeneration: the head dimension must be a multiple of 4, at most 64 (got {H // nh})")
         self.prompt_ids = None           # transcribe_ids: [start, language or None, task, notimestamps]
         self.language_ids = None         # transcribe_ids: the candidates of detect_language when the prompt's language is None
+        self.no_timestamps_id = None     # transcribe_ids(timestamps=True): left out of the prompt; the token in front of the first timestamp
+        self.no_speech_id = None         # transcribe_ids(timestamps=True): when set, no_speech_prob is computed
         self.eos_token_id = self.extra_config.get("eos_token_id")
         self.suppress_tokens = self.extra_config.get("suppress_tokens")
         self.begin_suppress_tokens = self.extra_config.get("begin_suppress_tokens")
@@ -287,6 +338,41 @@ class WhisperForConditionalGeneration(HandleModule):
         return tokens, n
 
     @torch.no_grad()
+    def decode(self, input_features, prompt_ids, *, no_timestamps_id, max_initial_timestamp=1.0, no_speech_id=None, max_new_tokens=None,
+               suppress_tokens=None, begin_suppress_tokens=None, eos_token_id=None, sot_index=0):
+        """Greedy decoding under the timestamp rules after the teacher-forced prompt [B, P] (or [P]; no `<|notimestamps|>` in it): what
+        `whisper.decode(model, mel, DecodingOptions())` does.  `no_timestamps_id + 1` is the first timestamp token; the first generated token
+        is a timestamp of at most `max_initial_timestamp` seconds (None: any); `no_speech_id` asks for `no_speech_prob`, read after the
+        prompt's token `sot_index`; `max_new_tokens` defaults to max_target_positions // 2, openai's sample_len.  -> WhisperDecoding."""
+        what = "WhisperForConditionalGeneration.decode"
+        eos = self.eos_token_id if eos_token_id is None else eos_token_id
+        if eos is None:
+            raise ValueError(f"{what}: no eos_token_id (give it here or in the configuration)")
+        if max_initial_timestamp is not None and not max_initial_timestamp >= 0:
+            raise ValueError(f"{what}: max_initial_timestamp must be None or at least 0 seconds")
+        max_new = self.config["max_target_positions"] // 2 if max_new_tokens is None else int(max_new_tokens)
+        if max_new < 1:
+            raise ValueError(f"{what}: max_new_tokens must be at least 1")
+        lib, stream, x, B, T, ws = self._features(input_features)
+        t, ids = self._ids(prompt_ids, B, "prompt_ids")
+        P = int(t.shape[1])
+        o = _lib.us_whisper_decode_options()
+        o.eos, o.no_timestamps, o.sot_index, o.max_new = int(eos), int(no_timestamps_id), int(sot_index), max_new
+        o.max_initial_timestamp_index = -1 if max_initial_timestamp is None else int(round(max_initial_timestamp / TIME_PRECISION))
+        o.no_speech = -1 if no_speech_id is None else int(no_speech_id)
+        suppress_tokens = self.suppress_tokens if suppress_tokens is None else suppress_tokens
+        begin_suppress_tokens = self.begin_suppress_tokens if begin_suppress_tokens is None else begin_suppress_tokens
+        sup, beg = self._mask(suppress_tokens, x.device), self._mask(begin_suppress_tokens, x.device)
+        tokens = torch.empty(B, max(max_new, 1), dtype=torch.int64, device=x.device)
+        n = torch.empty(B, dtype=torch.int64, device=x.device)
+        lp = torch.empty(B, dtype=torch.float32, device=x.device)
+        ns = torch.empty(B, dtype=torch.float32, device=x.device) if no_speech_id is not None else None
+        self._call(lib, x.device, "decode", self._h, x.data_ptr(), B, T, ids, P, C.byref(o), sup.data_ptr() if sup is not None else None,
+                   beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(), lp.data_ptr(),
+                   ns.data_ptr() if ns is not None else None, ws.data_ptr(), ws.numel(), stream)
+        return WhisperDecoding(tokens, n, lp, ns)
+
+    @torch.no_grad()
     def detect_language(self, input_features, language_ids, start_id=None):
         """One step from the start token, argmax over `language_ids` -> [B] int64 (on the device): the first thing `whisper.decode` does
         when no language is set."""
@@ -300,10 +386,12 @@ class WhisperForConditionalGeneration(HandleModule):
         return cand[lg[:, cand].argmax(-1)]
 
     @torch.no_grad()
-    def transcribe_ids(self, wav16, lengths=None, language_id=None, prompt_ids=None, max_new_tokens=None):
+    def transcribe_ids(self, wav16, lengths=None, language_id=None, prompt_ids=None, max_new_tokens=None, timestamps=False):
         """16 kHz waveforms [B, T] with per-item lengths -> (tokens [B, L], count [B]): log-mel features, the prompt (`prompt_ids`, default
         `self.prompt_ids`: [start, language, task, notimestamps]; a language of None is `language_id`, or detected per item among
-        `self.language_ids`), greedy decoding with the configuration's suppression lists.  An item longer than 30 s is refused."""
+        `self.language_ids`), greedy decoding with the configuration's suppression lists.  An item longer than 30 s is refused.
+        timestamps=True: the three-token prompt (the prompt without `self.no_timestamps_id`) and `decode` under the timestamp rules, with
+        `no_speech_prob` when `self.no_speech_id` is set -> WhisperDecoding."""
         x = torch.as_tensor(wav16)
         if x.dim() == 1:
             x = x[None]
@@ -316,13 +404,54 @@ class WhisperForConditionalGeneration(HandleModule):
         prompt = list(self.prompt_ids if prompt_ids is None else prompt_ids)
         if not prompt:
             raise ValueError("WhisperForConditionalGeneration.transcribe_ids: no prompt_ids")
+        if timestamps:
+            if self.no_timestamps_id is None:
+                raise ValueError("WhisperForConditionalGeneration.transcribe_ids: timestamps=True needs no_timestamps_id")
+            prompt = [p for p in prompt if p is None or int(p) != int(self.no_timestamps_id)]
         rows = torch.tensor([[0 if p is None else int(p) for p in prompt]] * B, dtype=torch.int64)
         for j, p in enumerate(prompt):
             if p is None:
                 if language_id is None and not self.language_ids:
                     raise ValueError("WhisperForConditionalGeneration.transcribe_ids: no language_id and no language_ids to detect one among")
                 rows[:, j] = int(language_id) if language_id is not None else self.detect_language(feats, self.language_ids, prompt[0]).cpu()
+        if timestamps:
+            return self.decode(feats, rows, no_timestamps_id=int(self.no_timestamps_id), no_speech_id=self.no_speech_id, max_new_tokens=max_new_tokens)
         return self.generate(feats, rows, max_new_tokens, self.suppress_tokens, self.begin_suppress_tokens)
+
+
+_select_scratch = {}
+
+
+@torch.no_grad()
+def select_tokens(logits, history, *, eos_token_id, no_timestamps_id, max_initial_timestamp_index=-1, suppress=None, begin_suppress=None):
+    """One selection step of `decode` on its own (`us_whisper_select`): logits [B, V] fp32 on the device, history: per item (n_sampled, last,
+    penultimate, last_timestamp, done), suppress / begin_suppress: uint8 masks [V] on the device or None -> (token [B] int64, logprob [B]
+    fp32, decided_timestamp [B] int32) on the device."""
+    if logits.device.type != "cuda" or logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"select_tokens: expected fp32 logits [B, V] on a ROCm device, got {logits.dtype} {tuple(logits.shape)} on {logits.device}")
+    lib = _lib.load()
+    x = logits.contiguous()
+    B, V = int(x.shape[0]), int(x.shape[1])
+    if len(history) != B:
+        raise ValueError(f"select_tokens: {len(history)} histories for {B} items")
+    for m in (suppress, begin_suppress):
+        if m is not None and (m.dtype != torch.uint8 or m.numel() != V or m.device != x.device):
+            raise ValueError("select_tokens: a mask must be uint8 [V] on the logits' device")
+    hist = (_lib.us_whisper_history * B)(*[_lib.us_whisper_history(*[int(v) for v in h]) for h in history])
+    o = _lib.us_whisper_decode_options(int(eos_token_id), int(no_timestamps_id), int(max_initial_timestamp_index), -1, 0, 1)
+    n = int(lib.us_whisper_select_scratch_bytes(V))
+    ws = _select_scratch.get(x.device)
+    if ws is None or ws.numel() < n:
+        _select_scratch[x.device] = ws = torch.empty(max(n, 1), dtype=torch.uint8, device=x.device)
+    token = torch.empty(B, dtype=torch.int64, device=x.device)
+    logprob = torch.empty(B, dtype=torch.float32, device=x.device)
+    decided = torch.empty(B, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.us_whisper_select(x.data_ptr(), B, V, hist, C.byref(o), suppress.data_ptr() if suppress is not None else None,
+                                   begin_suppress.data_ptr() if begin_suppress is not None else None, token.data_ptr(), logprob.data_ptr(),
+                                   decided.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    _lib.check(rc, None, "us_whisper_select")
+    return token, logprob, decided
 
 
 def detect_language(model, input_features, language_ids, start_id=None):
