@@ -7,6 +7,8 @@ its text by character and word error rate, compare its speaker embedding with th
     python evaluate.py --synthetic 12 --batch 4
     python evaluate.py --filelist LIST --recogniser whisper --whisper_checkpoint DIR [--language ro]
     python evaluate.py --synthetic 6 --batch 4 --recogniser whisper [--whisper_timestamps]
+    python evaluate.py --filelist LIST ... --mos_path MOS.ckpt [--mos_upstream WAV2VEC2.pt] [--mos_clipping 0|1]
+    python evaluate.py --synthetic 12 --batch 4 --mos
 
 LIST holds one `wav|transcript[|reference_wav]` line per sample.  CTC.pt is a `torch.save`d state dict of `transformers.HubertForCTC` or
 `Wav2Vec2ForCTC` in the base form (the class is taken from the keys; nothing is fetched by name; the base size unless --config_path
@@ -32,6 +34,14 @@ under the timestamp rules (`without_timestamps=False`): that is --whisper_timest
 step applies the timestamp rules (`WhisperForConditionalGeneration.decode`), and each file's record gains `avg_logprob`, `no_speech_prob`
 (where the vocabulary has <|nospeech|> or <|nocaptions|>) and `segments` ([start_s, end_s, text] from the timestamp pairs).  The same length-sorted batches feed it; hypotheses and references are
 brought to lower-case letters, digits, apostrophes and single spaces before scoring.  Files longer than 30 s are refused.
+
+--mos_path adds the reference notebook's third figure, a predicted mean opinion score (`s3prl.hub.mos_wav2vec2()` applied to every file
+at 16 kHz): MOS.ckpt is s3prl's checkpoint (Featurizer, Downstream and their arguments), --mos_upstream the wav2vec2-base weights (a
+`transformers.Wav2Vec2Model` state dict or fairseq's `wav2vec_small.pt`); --mos_clipping says whether the score is 2 tanh(score) + 3 when the
+checkpoint does not.  Every file's 16 kHz waveform goes through `unitspeech_amd.mos.MOSPredictor` in the same length-sorted ragged batches as
+the recogniser (after --sv56 when that is given: the notebook's two rows differ in exactly that; --normalize does not touch it): each
+file's record gains `mos`, the corpus line `mos` (the mean), `mos_min` and `mos_max`.  With --synthetic N --mos and no path a seeded tiny
+predictor (the TINY geometry, a connector of 16) runs.
 
 --synthetic N runs without files: a seeded tiny CTC model, N seeded waveforms, and as transcripts the model's own decodings with a known
 number of edits applied (characters appended, or cut from the end): the distance of each pair is then exactly that number, so the CER
@@ -196,6 +206,34 @@ def synthetic_model(device, seed: int = 0):
     return model.to(device).eval(), CTCVocabulary(TINY_VOCAB)
 
 
+MOS_PROJECTOR = 16               # --synthetic N --mos: the tiny head's connector
+
+
+def synthetic_mos(device, seed: int = 0):
+    """A seeded tiny `MOSPredictor`: the TINY upstream (wav2vec2's base form is HuBERT's) and a head with a connector of MOS_PROJECTOR."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from hubert_torch import synthetic_hubert_state_dict
+    from mos_torch import synthetic_mos_weights
+    from unitspeech_amd.hubert import HubertModel
+    from unitspeech_amd.mos import MOSHead, MOSPredictor
+    upstream = HubertModel(**TINY)
+    upstream.load_state_dict(synthetic_hubert_state_dict(TINY, seed))
+    head = MOSHead(TINY["hidden_size"], TINY["num_hidden_layers"] + 1, MOS_PROJECTOR)
+    head.load_state_dict(synthetic_mos_weights(head.n_states, head.hidden_size, MOS_PROJECTOR, seed))
+    return MOSPredictor(upstream, head).to(device).eval()
+
+
+@torch.no_grad()
+def mos_all(predictor, wavs16, max_batch):
+    """16 kHz waveforms [T_i] on the device -> their predicted scores as floats, in the order given; one read back per batch."""
+    out = [None] * len(wavs16)
+    for idx in plan_batches([int(w.shape[0]) for w in wavs16], max_batch):
+        x, n = padded_batch(wavs16, idx)
+        for i, v in zip(idx, predictor(x, n).cpu().tolist()):
+            out[i] = v
+    return out
+
+
 TINY_WHISPER = dict(d_model=64, encoder_attention_heads=2, decoder_attention_heads=2, encoder_layers=2, decoder_layers=2, encoder_ffn_dim=128,
                     decoder_ffn_dim=128, num_mel_bins=80, max_source_positions=1500, max_target_positions=32, vocab_size=36)
 
@@ -265,12 +303,20 @@ def main(argv=None):
     ap.add_argument("--timestamps", action="store_true", help="per-word start and end times of the reference text (forced alignment)")
     ap.add_argument("--sv56", action="store_true", help="normalise every sample's active speech level before it is scored")
     ap.add_argument("--ndb", type=float, default=-26.0, help="--sv56: the target level in dB relative to full scale")
+    ap.add_argument("--mos_path", default=None, help="s3prl's mos_wav2vec2 checkpoint: adds a predicted mean opinion score per file")
+    ap.add_argument("--mos_upstream", default=None, help="--mos_path: the wav2vec2-base weights (transformers state dict or fairseq's wav2vec_small.pt)")
+    ap.add_argument("--mos_clipping", type=int, choices=(0, 1), default=None, help="--mos_path: 2 tanh(score) + 3, when the checkpoint does not say")
+    ap.add_argument("--mos", action="store_true", help="--synthetic N: a seeded tiny MOS predictor when no --mos_path is given")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded waveforms through a seeded tiny model")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     if args.whisper_timestamps and args.recogniser != "whisper":
         raise SystemExit("--whisper_timestamps belongs to --recogniser whisper")
+    if args.mos and not args.mos_path and not args.synthetic:
+        raise SystemExit("--mos without --mos_path belongs to --synthetic N: give --mos_path CKPT")
+    if (args.mos_upstream or args.mos_clipping is not None) and not args.mos_path:
+        raise SystemExit("--mos_upstream and --mos_clipping belong to --mos_path")
     if not torch.cuda.is_available():
         raise SystemExit("no ROCm device: the HIP recogniser has no CPU fallback")
     from unitspeech_amd.asr import CTCVocabulary, error_rates, load_ctc_checkpoint, normalize_text
@@ -324,6 +370,15 @@ def main(argv=None):
         whisper_prompt(model, vocabulary, args.language)
     else:
         model.pad_token_id = vocabulary.blank_id
+    mos = None
+    if args.mos_path or args.mos:
+        if args.mos_path:
+            from unitspeech_amd.mos import load_mos_checkpoint
+            extra = {} if args.mos_clipping is None else {"clipping": bool(args.mos_clipping)}
+            predictor = load_mos_checkpoint(args.mos_path, args.mos_upstream, **extra).to(device)
+        else:
+            predictor = synthetic_mos(device, args.seed)
+        mos = mos_all(predictor, wavs16, args.batch)
     if args.normalize:
         wavs16 = [(w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7) for w in wavs16]
     scores = [] if args.whisper_timestamps else None
@@ -349,13 +404,17 @@ def main(argv=None):
             rec["word_times"] = words[k]
         if scores is not None:
             rec.update(scores[k])
+        if mos is not None:
+            rec["mos"] = mos[k]
         files.append(rec)
         print(f"{name}: CER {p['cer']:.4f} ({p['char_distance']}/{p['chars']})  WER {p['wer']:.4f} ({p['word_distance']}/{p['words']})"
-              + (f"  SECS {s:.4f}" if s is not None else "") + f"  | {h!r} <- {t!r}")
+              + (f"  SECS {s:.4f}" if s is not None else "") + (f"  MOS {mos[k]:.4f}" if mos is not None else "") + f"  | {h!r} <- {t!r}")
     result.update(cer=rates["cer"], wer=rates["wer"], files=len(files), batches=len(batches), per_file=files)
     have = [s for s in secs if s is not None]
     if have:
         result["secs"] = float(np.mean(have))
+    if mos is not None:
+        result.update(mos=float(np.mean(mos)), mos_min=float(np.min(mos)), mos_max=float(np.max(mos)))
     print(json.dumps({k: v for k, v in result.items() if k != "per_file"}))
     if args.out:
         with open(args.out, "w", encoding="utf-8") as f:

@@ -993,6 +993,38 @@ int us_level_measure(const void* wav, int in_dtype, int quantize_input, const in
 int us_level_apply(const void* wav, int in_dtype, int quantize_input, const int64_t* lengths, int B, int Tmax, const double* stats, double ndb,
                    void* out, int out_dtype, double* gain, int64_t* clipped, void* workspace, size_t workspace_bytes, us_stream stream);
 
+/* ---- MOS predictor: the layer mix and the downstream head of s3prl's `mos_wav2vec2`, csrc/mos.hip -----------------------------------------
+ * Handle-free device calls like the ones above: they allocate nothing and only enqueue on `stream`.  n_states in [1, 32] hidden states of
+ * width H, a multiple of 4 in [4, 1024]; a connector of P in [1, 4096] rows; anything else: us_mos_packed_bytes returns 0 and the calls
+ * US_EINVAL.  With s = softmax(weights) over the states and hh[t] = sum_l s_l h_l[t]: z[t] = C hh[t] + c, e[t] = a . z[t] + a0, alpha =
+ * softmax_t(e) over the item's own frames, mu[t] = m . z[t] + m0, score = sum_t alpha_t mu[t]; without attention pooling alpha_t = 1 / F and
+ * the score is the mean of mu.  With `clipping` the score becomes 2 tanh(score) + 3.
+ * us_mos_pack_head: weights [n_states], connector_weight [P][H] and connector_bias [P] (C, c), attention_weight [P] and attention_bias [1]
+ *   (a, a0; attention_weight NULL: no attention pooling, attention_bias must then be NULL too), mean_weight [P] and mean_bias [1] (m, m0),
+ *   all on the device, a NULL bias standing for zeros -> `packed` (us_mos_packed_bytes, 16-byte aligned): s, v_e = C^T a, v_m = C^T m,
+ *   k_e = a . c + a0, k_m = m . c + m0 and the variant.  The softmax and every sum over p (ascending) run in fp64 and are rounded to fp32 once.
+ *   us_mos_unpack_head writes them back out (s [n_states], v_e [H], v_m [H], k [2] = k_e, k_m; each optional): NaN when n_states or H are
+ *   not the pack's.
+ * us_mos_score: hidden state l of item b is [Tmax][H] rows (H contiguous) at hidden + b * item_stride + l * state_stride (elements; both
+ *   strides non-negative multiples of 4, hidden 16-byte aligned): `us_hubert_forward`'s [B][L+1][F][H] and `us_wavlm_forward`'s
+ *   [L+1][B][F][H] are read in place.  lengths [B] device int64 (frames per item, clamped to [0, Tmax]; NULL: all Tmax); n_states and H as
+ *   packed (another head's pack gives NaN scores and is not read past its header) -> scores [B]; optionally frame_scores [B][Tmax] = mu and
+ *   attention [B][Tmax] = alpha (1 / F without attention pooling).  Rows at or past an item's length are never read; their frame_scores and
+ *   attention entries are written as 0; nothing is written past a row.  AN ITEM OF 0 FRAMES GETS A QUIET NaN, as the mean of nothing is in
+ *   torch.  The softmax is taken over e - k_e (it does not change when a constant is added to every e), so a large a0 costs no bits.
+ *   workspace: at least us_mos_workspace_bytes(B, Tmax) (0 for what the call refuses: B in [1, 65535], B * Tmax <= 2^24), 8-byte aligned.
+ *   No float atomics; every order of summation is a function of H, n_states and the item's own frames alone: an item has the same bits
+ *   alone, inside any batch, at any Tmax and from run to run. */
+size_t us_mos_packed_bytes(int n_states, int H, int P);
+int us_mos_pack_head(const float* weights, const float* connector_weight, const float* connector_bias, const float* attention_weight,
+                     const float* attention_bias, const float* mean_weight, const float* mean_bias, int n_states, int H, int P, void* packed,
+                     size_t packed_bytes, us_stream stream);
+int us_mos_unpack_head(const void* packed, int n_states, int H, float* s, float* v_e, float* v_m, float* k, us_stream stream);
+size_t us_mos_workspace_bytes(int B, int Tmax);
+int us_mos_score(const float* hidden, int64_t item_stride, int64_t state_stride, const int64_t* lengths, const void* packed, int B, int Tmax,
+                 int n_states, int H, int clipping, float* scores, float* frame_scores, float* attention, void* workspace, size_t workspace_bytes,
+                 us_stream stream);
+
 /* Last error message of this handle (or of the library when h == NULL). */
 const char* us_last_error(us_handle h);
 

@@ -237,6 +237,11 @@ SIGNATURES = {
     "us_ctc_head_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "us_ctc_align_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "us_ctc_forced_align": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "us_mos_packed_bytes": (C.c_size_t, [C.c_int] * 3),
+    "us_mos_pack_head": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_mos_unpack_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "us_mos_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "us_mos_score": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "us_level_chunk": (C.c_int, []),
     "us_level_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_level_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

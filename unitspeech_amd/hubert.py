@@ -8,6 +8,7 @@ arithmetic is `csrc/hubert.hip`; there is no CPU fallback and no training.
 """
 from __future__ import annotations
 
+import re
 from collections import OrderedDict
 
 import torch
@@ -113,6 +114,28 @@ def from_fairseq_state_dict(sd):
     and `final_proj.*` (masking and the pre-training heads, unused in eval) are dropped.  fairseq is not available where this library is
     developed: the mapping is tested on a hand-made dictionary of the right names and shapes only."""
     return rename_fairseq(sd, _FAIRSEQ)
+
+
+_W2V2_DROPPED = ("quantizer.", "project_q.")
+_W2V2_KNOWN = re.compile(r"^(feature_extractor\.conv_layers\.\d+\.conv\.weight"
+                         r"|feature_extractor\.conv_layers\.0\.layer_norm\.(weight|bias)"
+                         r"|feature_projection\.(layer_norm|projection)\.(weight|bias)"
+                         r"|encoder\.pos_conv_embed\.conv\.(bias|weight_g|weight_v)"
+                         r"|encoder\.layer_norm\.(weight|bias)"
+                         r"|encoder\.layers\.\d+\.(attention\.(k|v|q|out)_proj|layer_norm|final_layer_norm|feed_forward\.(intermediate|output)_dense)"
+                         r"\.(weight|bias))$")
+
+
+def from_fairseq_wav2vec2_state_dict(sd):
+    """A fairseq wav2vec 2.0 checkpoint's `model` dictionary (`wav2vec_small.pt`) under `HubertModel`'s key names: `from_fairseq_state_dict`'s
+    table.  Dropped, as unused in eval: `mask_emb`, `label_embs_concat` and `final_proj.*` (as there), and the pre-training's quantiser,
+    `quantizer.*` (`vars`, `weight_proj.*`) and `project_q.*`.  Any other key that is not one of the base form's is a ValueError naming it.
+    Tested on a hand-made dictionary of the right names only, as `from_fairseq_state_dict` is."""
+    out = rename_fairseq(OrderedDict((k, v) for k, v in sd.items() if not k.startswith(_W2V2_DROPPED)), _FAIRSEQ)
+    unknown = [k for k in out if not _W2V2_KNOWN.match(k)]
+    if unknown:
+        raise ValueError(f"from_fairseq_wav2vec2_state_dict: unknown keys {unknown[:4]}{' ...' if len(unknown) > 4 else ''}")
+    return out
 
 
 def load_hubert_checkpoint(path, **config):
