@@ -3,6 +3,7 @@
 
     python bench_whisper.py [--runs 5] [--warmup 2] [--quick] [--json PATH]
     python bench_whisper.py --decode [--runs 5] [--warmup 2] [--quick] [--json PATH]
+    python bench_whisper.py --beam 5 [--runs 5] [--warmup 2] [--quick] [--json PATH]
 
   encoder       `encode` at B = 1 and 8
   decode        time per token at B = 1 and 8: greedy decoding of 65 tokens minus greedy decoding of 1 token (both hold the encoder and
@@ -11,6 +12,10 @@
   --decode      instead of the above: time per token of `decode` (the timestamp rules, `us_whisper_decode`) against `generate` (plain greedy,
                 `us_whisper_generate`) at B = 1 and 8, measured the same way, and one selection step alone (`us_whisper_select`: the host's
                 call and its three launches) at V tokens for B = 1, 8 and 16
+  --beam N      instead of the above, at B = 1: time per step of `decode(beam_size=N)` (`us_whisper_decode_beam`, N rows in one launch group)
+                against `decode` on the same build, measured the same way, beside the weight-streaming floor and the launches of a step, and
+                one step of selection and bookkeeping alone (`us_whisper_beam_select`: the host's call and its four launches) as a share of
+                the beam step
 Two legs, alternating run by run on the same GPU after the warm-up, timed by device events; median [min, max]:
   hip           the library (unitspeech_amd.whisper.WhisperForConditionalGeneration)
   eager         the fp32 torch restatement with its key/value cache (tools/whisper_torch.py) on the device
@@ -34,7 +39,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from whisper_torch import WhisperTorch  # noqa: E402
-from unitspeech_amd.whisper import (MEDIUM, WhisperForConditionalGeneration, log_mel_spectrogram, select_tokens,  # noqa: E402
+from unitspeech_amd.whisper import (MEDIUM, WhisperForConditionalGeneration, log_mel_spectrogram, select_beams, select_tokens,  # noqa: E402
                                     synthetic_whisper_state_dict)
 
 QUICK = dict(d_model=64, encoder_attention_heads=2, decoder_attention_heads=2, encoder_layers=2, decoder_layers=2, encoder_ffn_dim=128,
@@ -123,6 +128,43 @@ def decode_legs(a, c, dev):
     return rows
 
 
+def beam_legs(a, c, dev):
+    """`decode(beam_size=n)` against `decode` per step at B = 1, and the beam's selection and bookkeeping alone"""
+    V, n = c["vocab_size"], a.beam
+    eos, nt = (50257, 50363) if V == 51865 else (V - 25, V - 13)
+    hip = WhisperForConditionalGeneration(**c, eos_token_id=eos)
+    hip.load_state_dict(synthetic_whisper_state_dict(c, 0))
+    hip = hip.to(dev).eval()
+    rate = copy_rate(dev)
+    floor_ms = decoder_bytes(c) / rate * 1e3
+    x, box = features(1, c, dev, 1), {}
+
+    def run(k, steps):                                  # eos suppressed: no entry finishes, every row stays live, every step runs
+        box[k] = hip.decode(x, [1, 2, 3], no_timestamps_id=nt, no_speech_id=nt - 1, max_new_tokens=steps, suppress_tokens=[eos],
+                            beam_size=n if k == "beam" else None)
+
+    ts = alternate({f"{k}_{s}": (lambda k=k, s=s: run(k, s)) for s in (1, STEPS + 1) for k in ("greedy", "beam")}, a.runs, a.warmup)
+    per = {k: [(m - o) / STEPS for m, o in zip(ts[f"{k}_{STEPS + 1}"], ts[f"{k}_1"])] for k in ("greedy", "beam")}
+    g = torch.Generator().manual_seed(7)
+    lg, reps = (3 * torch.randn(n, V, generator=g)).to(dev), 50
+    hist, scores = [(2, nt + 3, 5, nt + 3, 0)] * n, [-0.5 * j for j in range(n)]
+
+    def sel():
+        for _ in range(reps):
+            select_beams(lg, hist, scores, n, eos_token_id=eos, no_timestamps_id=nt)
+
+    sel_ms = [t / reps for t in alternate(dict(select=sel), a.runs, a.warmup)["select"]]
+    beam_ms, greedy_ms, s_ms = (statistics.median(v) for v in (per["beam"], per["greedy"], sel_ms))
+    launches = dict(greedy=1 + 8 * c["decoder_layers"] + 1 + 2, beam=1 + 8 * c["decoder_layers"] + 1 + 3)
+    row = dict(stage="beam_per_step", B=1, beam_size=n, steps=STEPS, beam=stats(per["beam"]), greedy=stats(per["greedy"]),
+               ratio=round(beam_ms / greedy_ms, 3), floor_ms=round(floor_ms, 4), launches_per_step=launches, select_call=stats(sel_ms),
+               select_share=round(s_ms / beam_ms, 4), beam_length=int(box["beam"].lengths[0]), greedy_length=int(box["greedy"].lengths[0]))
+    print(f"per step B=1: decode(beam_size={n}) {beam_ms:.4f} ms  decode {greedy_ms:.4f} ms  ratio {beam_ms / greedy_ms:.2f}  floor {floor_ms:.4f} ms  "
+          f"launches {launches['beam']} / {launches['greedy']}  selection + bookkeeping {s_ms * 1e3:.1f} us per call ({100 * s_ms / beam_ms:.1f} % of a step, "
+          f"the host's call and an init launch included)", flush=True)
+    return [row], rate
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
@@ -130,11 +172,22 @@ def main():
     ap.add_argument("--quick", action="store_true", help="a tiny geometry: a functional check, not a measurement")
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--decode", action="store_true", help="only `decode` against `generate` and the selection step alone")
+    ap.add_argument("--beam", type=int, default=None, metavar="N", help="only `decode(beam_size=N)` against `decode` at B = 1")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("CUDA/ROCm is not available: the recogniser has no CPU fallback")
     dev = torch.device("cuda", 0)
     c = dict(QUICK if a.quick else MEDIUM)
+    if a.beam is not None:
+        rows, rate = beam_legs(a, c, dev)
+        out = {"bench": "whisper_beam", "geometry": "quick" if a.quick else "whisper-medium", "config": c, "runs": a.runs, "warmup": a.warmup,
+               "device": torch.cuda.get_device_name(0), "copy_rate_GBps": round(rate / 1e9, 1), "decoder_weight_bytes": decoder_bytes(c), "rows": rows}
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+                f.write("\n")
+        print(json.dumps(out))
+        return
     if a.decode:
         out = {"bench": "whisper_decode", "geometry": "quick" if a.quick else "whisper-medium", "config": c, "runs": a.runs, "warmup": a.warmup,
                "device": torch.cuda.get_device_name(0), "rows": decode_legs(a, c, dev)}

@@ -6,7 +6,7 @@ its text by character and word error rate, compare its speaker embedding with th
                        [--speaker_encoder_path EMBEDDER.pt] [--batch 16] [--timestamps] [--out RESULT.json]
     python evaluate.py --synthetic 12 --batch 4
     python evaluate.py --filelist LIST --recogniser whisper --whisper_checkpoint DIR [--language ro]
-    python evaluate.py --synthetic 6 --batch 4 --recogniser whisper [--whisper_timestamps]
+    python evaluate.py --synthetic 6 --batch 4 --recogniser whisper [--whisper_timestamps [--whisper_beam_size 5 [--whisper_patience 1.0]]]
     python evaluate.py --filelist LIST ... --mos_path MOS.ckpt [--mos_upstream WAV2VEC2.pt] [--mos_clipping 0|1]
     python evaluate.py --synthetic 12 --batch 4 --mos
 
@@ -34,6 +34,9 @@ under the timestamp rules (`without_timestamps=False`): that is --whisper_timest
 step applies the timestamp rules (`WhisperForConditionalGeneration.decode`), and each file's record gains `avg_logprob`, `no_speech_prob`
 (where the vocabulary has <|nospeech|> or <|nocaptions|>) and `segments` ([start_s, end_s, text] from the timestamp pairs).  The same length-sorted batches feed it; hypotheses and references are
 brought to lower-case letters, digits, apostrophes and single spaces before scoring.  Files longer than 30 s are refused.
+--whisper_beam_size N (with --whisper_timestamps) decodes by beam search under the same rules, `DecodingOptions(beam_size=N, patience=P)` with
+--whisper_patience P (default 1.0): what the `whisper` command line runs with N = 5.  `avg_logprob` is then the winning sequence's; the values
+used go into the result as `whisper_beam_size` and `whisper_patience`.
 
 --mos_path adds the reference notebook's third figure, a predicted mean opinion score (`s3prl.hub.mos_wav2vec2()` applied to every file
 at 16 kHz): MOS.ckpt is s3prl's checkpoint (Featurizer, Downstream and their arguments), --mos_upstream the wav2vec2-base weights (a
@@ -117,9 +120,10 @@ def padded_batch(wavs16, idx):
 
 
 @torch.no_grad()
-def transcribe_all(model, vocabulary, wavs16, max_batch, scores=None):
+def transcribe_all(model, vocabulary, wavs16, max_batch, scores=None, beam=None):
     """16 kHz waveforms [T_i] on the device -> their transcripts, in the order given; one read back per batch, of the tokens.
-    scores: a list that makes Whisper decode under the timestamp rules and receives per file dict(avg_logprob, no_speech_prob, segments)."""
+    scores: a list that makes Whisper decode under the timestamp rules and receives per file dict(avg_logprob, no_speech_prob, segments);
+    beam: dict(beam_size, patience) for beam search under those rules."""
     texts = [None] * len(wavs16)
     batches = plan_batches([int(w.shape[0]) for w in wavs16], max_batch)
     if scores is not None:
@@ -130,7 +134,7 @@ def transcribe_all(model, vocabulary, wavs16, max_batch, scores=None):
             tokens, count = model.transcribe_ids(x, n)
             tokens, count = tokens.cpu(), count.cpu()
         else:
-            r = model.transcribe_ids(x, n, timestamps=True)
+            r = model.transcribe_ids(x, n, timestamps=True, **(beam or {}))
             tokens, count, avg = r.tokens.cpu(), r.lengths.cpu(), r.avg_logprob.cpu().tolist()
             ns = r.no_speech_prob.cpu().tolist() if r.no_speech_prob is not None else [None] * len(idx)
             for b, i in enumerate(idx):
@@ -294,6 +298,10 @@ def main(argv=None):
     ap.add_argument("--language", default=None, help="--recogniser whisper: the language token's name (ro); detected per file when absent")
     ap.add_argument("--whisper_timestamps", action="store_true",
                     help="--recogniser whisper: decode under the timestamp rules (whisper.decode's defaults); adds avg_logprob, no_speech_prob, segments")
+    ap.add_argument("--whisper_beam_size", type=int, default=None, metavar="N",
+                    help="--whisper_timestamps: beam search with N beams (whisper.decode's DecodingOptions(beam_size=N)), N in [1, 16]")
+    ap.add_argument("--whisper_patience", type=float, default=None, metavar="P",
+                    help="--whisper_beam_size: the search ends after round(N * P) finished candidates (default 1.0)")
     ap.add_argument("--blank", default="<pad>")
     ap.add_argument("--word_delimiter", default="|")
     ap.add_argument("--normalize", action="store_true", help="zero mean, unit variance per waveform (a feature extractor with do_normalize)")
@@ -313,6 +321,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.whisper_timestamps and args.recogniser != "whisper":
         raise SystemExit("--whisper_timestamps belongs to --recogniser whisper")
+    if args.whisper_beam_size is not None and not (args.recogniser == "whisper" and args.whisper_timestamps):
+        raise SystemExit("--whisper_beam_size needs --recogniser whisper --whisper_timestamps: beam search is built under the timestamp rules only")
+    if args.whisper_patience is not None and args.whisper_beam_size is None:
+        raise SystemExit("--whisper_patience belongs to --whisper_beam_size")
+    if args.whisper_beam_size is not None and not 1 <= args.whisper_beam_size <= 16:
+        raise SystemExit("--whisper_beam_size must lie in [1, 16]")
     if args.mos and not args.mos_path and not args.synthetic:
         raise SystemExit("--mos without --mos_path belongs to --synthetic N: give --mos_path CKPT")
     if (args.mos_upstream or args.mos_clipping is not None) and not args.mos_path:
@@ -382,10 +396,15 @@ def main(argv=None):
     if args.normalize:
         wavs16 = [(w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7) for w in wavs16]
     scores = [] if args.whisper_timestamps else None
-    hyps, batches = transcribe_all(model, vocabulary, wavs16, args.batch, scores)
+    beam = None
+    if args.whisper_beam_size is not None:
+        beam = dict(beam_size=args.whisper_beam_size, patience=args.whisper_patience)
+    hyps, batches = transcribe_all(model, vocabulary, wavs16, args.batch, scores, beam)
     if whisper:
         hyps = [normalize_text(h, vocabulary) for h in hyps]
     result = {}
+    if beam is not None:
+        result.update(whisper_beam_size=args.whisper_beam_size, whisper_patience=1.0 if args.whisper_patience is None else args.whisper_patience)
     if args.synthetic:
         transcripts = [apply_edits(h, SYNTHETIC_EDITS, cut=bool(i & 1)) for i, h in enumerate(hyps)]
         result["expected_cer"] = SYNTHETIC_EDITS * len(hyps) / sum(len(t) for t in transcripts)

@@ -745,7 +745,8 @@ int us_wavlm_forward(us_wavlm_handle h, const float* wav, const int64_t* lengths
  * feed-forward size that is no multiple of 4, and max_source_positions or max_target_positions above 2048.
  * us_whisper_generate is plain greedy decoding (callers put <|notimestamps|> in the prompt); us_whisper_decode is greedy decoding under the
  * timestamp rules, what openai's `whisper.decode(model, mel, DecodingOptions())` runs by default (without_timestamps=False).
- * Not built: beam search, temperature fallback, fp16 weights. */
+ * us_whisper_decode_beam is beam search under those rules (DecodingOptions(beam_size=n, patience=p)).
+ * Not built: temperature fallback, fp16 weights. */
 typedef struct us_whisper* us_whisper_handle;
 typedef struct us_whisper_config {
   int32_t n_mels;
@@ -823,6 +824,40 @@ size_t us_whisper_select_scratch_bytes(int V);
 int us_whisper_select(const float* logits, int B, int V, const us_whisper_history* history, const us_whisper_decode_options* options,
                       const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* token, float* logprob,
                       int32_t* decided_timestamp, void* scratch, size_t scratch_bytes, us_stream stream);
+
+/* Beam search under the same rules: openai-whisper's BeamSearchDecoder.update / finalize and MaximumLikelihoodRanker with length_penalty=None,
+ * what `whisper.decode(model, mel, DecodingOptions(beam_size=n, patience=p))` runs, with max_candidates C = round(n * patience).
+ * An item has n rows, each with a sampled sequence, a score (the sum of its log-probabilities, a double) and a live flag; row 0 alone is live at
+ * the start.  A pool holds finished (sequence, score) pairs.  At every step each live row offers its top n + 1 surviving tokens by
+ * log-probability under the rules above applied to its own sequence (the lower id first on equal values, a token at -inf never, (eos, 0) when
+ * nothing survives); the candidates, listed in (row, rank) order, are sorted descending by score + log-probability, equal totals keeping that
+ * order, and walked: an eos candidate finishes (the row's sequence without the eos, the total), any other becomes the next new row (parent,
+ * token, total), and the walk stops once n new rows exist; what lies behind the stop is ignored, rows not filled are dead.  The finished
+ * entries join the pool in walk order while it holds fewer than C.  An item ends when its pool holds C entries, when no row is live, or after
+ * max_new steps, whatever the other items of the batch do.  Then a pool of fewer than n entries takes the live rows in descending score (the
+ * lower row first), and the entry with the largest score / length wins (length 0 counts as -infinity; the earlier entry on a tie).
+ * n = 1 with C = 1 is us_whisper_decode.
+ * Rows are item-major; a launch group holds floor(16 / n) whole items, so a step streams the weights once for all their rows.  The cross keys
+ * and values are stored once per item; the self cache is stored once per row and never moved: a per-row table names, for every position, the
+ * row of the item that holds its key.  An item has the same bits alone, in any batch and in repeated calls.
+ * -> tokens [B][max_new] int64 (the winner's sequence, eos at and after its end), n [B] int64 its length, sum_logprobs [B] fp32 its score
+ * (the eos term included where it ended by eos), no_speech_prob [B] as us_whisper_decode (the item's first row).  US_EINVAL for beam_size outside
+ * [1, 16], max_candidates outside [1, 64], a workspace below us_whisper_beam_workspace_bytes(h, B, beam_size) (0 for arguments out of range),
+ * and everything us_whisper_decode refuses. */
+size_t us_whisper_beam_workspace_bytes(us_whisper_handle h, int B, int beam_size);
+int us_whisper_decode_beam(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P,
+                           const us_whisper_decode_options* options, int beam_size, int max_candidates, const unsigned char* suppress,
+                           const unsigned char* begin_suppress, int64_t* tokens, int64_t* n, float* sum_logprobs, float* no_speech_prob,
+                           void* workspace, size_t workspace_bytes, us_stream stream);
+/* One step of the beam stage without a handle, through the same kernels: logits [B * beam_size][V] (device, rows item-major), the rows'
+ * histories and scores HOST [B * beam_size] (history.done != 0: the row is dead) -> per item, on the device: the new rows parent / token /
+ * score [B][beam_size] (parent -1, token eos, score 0 for a dead row), n_live [B], and the newly finished entries in walk order fin_parent /
+ * fin_score [B][beam_size] (-1 / 0 behind n_fin [B]).  scratch: device, us_whisper_beam_select_scratch_bytes(V, beam_size). */
+size_t us_whisper_beam_select_scratch_bytes(int V, int beam_size);
+int us_whisper_beam_select(const float* logits, int B, int V, int beam_size, const us_whisper_history* history, const double* scores,
+                           const us_whisper_decode_options* options, const unsigned char* suppress, const unsigned char* begin_suppress,
+                           int32_t* parent, int64_t* token, double* score, int32_t* n_live, int32_t* fin_parent, double* fin_score, int32_t* n_fin,
+                           void* scratch, size_t scratch_bytes, us_stream stream);
 
 /* ---- unit extraction from the dense upstream features on, csrc/units.hip ------------------------------------------------------------
  * The reference's host path (finetune.py:112-128: scikit-learn `KMeans.predict`, `torch.unique_consecutive`, util.py:69-102

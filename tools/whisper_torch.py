@@ -1,6 +1,7 @@
 """A torch restatement of `transformers.WhisperForConditionalGeneration` in eval mode, at a chosen dtype: the encoder, the decoder one
 position at a time over a key/value cache, the greedy loop of `us_whisper_generate` and the loop under the timestamp rules of
-`us_whisper_decode` (`decode`; the rules are tools/whisper_decode_numpy.py's, at the same dtype).  In fp64 it is the yardstick the goldens are checked
+`us_whisper_decode` (`decode`; the rules are tools/whisper_decode_numpy.py's, at the same dtype) and beam search under them
+(`decode_beam`; tools/whisper_beam_numpy.py over this model, the cache gathered by parent).  In fp64 it is the yardstick the goldens are checked
 with (tests/test_whisper.py), in fp32 its distance to the golden sets the bar of the GPU tests, and on the device it is bench_whisper.py's
 eager leg.
 
@@ -172,3 +173,36 @@ class WhisperTorch:
             if all(done):
                 break
         return dict(tokens=tokens, lengths=lengths, logprobs=lps, sum_logprob=lps.sum(1), no_speech_prob=nsp)
+
+    def decode_beam(self, feats, prompt, max_new, layout, beam_size, max_candidates, sot_index=0):
+        """Beam search under the timestamp rules (tools/whisper_beam_numpy.py, the selection in this object's dtype), one item after the
+        other: its beam_size rows share the encoder output, and the self cache is gathered by parent after each step
+        -> dict(tokens [B, max_new], lengths [B], sum_logprob [B] fp64, no_speech_prob [B] fp64 or None, items: beam_search's dicts)."""
+        import whisper_beam_numpy as beam
+        np_dtype = {torch.float64: np.float64, torch.float32: np.float32}[self.dtype]
+        enc = self.encode(feats)
+        prompt = prompt.to(self.device)
+        B, P = prompt.shape
+        n, V, ns = int(beam_size), self.c["vocab_size"], layout.get("no_speech")
+        nsp, items = (np.zeros(B) if ns is not None else None), []
+        for b in range(B):
+            state = self.start(enc[b:b + 1].expand(n, -1, -1))
+            for t in range(P - 1):
+                lg = self.step(state, prompt[b, t].expand(n), t, logits=ns is not None and t == sot_index)
+                if lg is not None:
+                    nsp[b] = rules.no_speech_prob(lg[0].cpu().numpy(), int(ns), np_dtype)
+
+            def logits_fn(i, tokens, parents, b=b, state=state):
+                if i == 0:
+                    cur = prompt[b, P - 1].expand(n)
+                else:
+                    state["cache"] = state["cache"][:, :, torch.as_tensor(parents, device=self.device)]
+                    cur = torch.as_tensor(tokens, dtype=torch.long, device=self.device)
+                rows = self.step(state, cur, P - 1 + i).cpu().numpy()
+                if i == 0 and ns is not None and sot_index == P - 1:
+                    nsp[b] = rules.no_speech_prob(rows[0], int(ns), np_dtype)
+                return rows
+
+            items.append(beam.beam_search(logits_fn, n, int(max_candidates), max_new, layout, V, np_dtype))
+        return dict(tokens=np.stack([r["tokens"] for r in items]), lengths=np.asarray([r["length"] for r in items], dtype=np.int64),
+                    sum_logprob=np.asarray([r["sum_logprob"] for r in items]), no_speech_prob=nsp, items=items)

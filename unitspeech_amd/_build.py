@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libunitspeech_hip.so")
 SOURCES = ["conv_igemm.hip", "ops.hip", "attn.hip", "wino.hip", "wino4.hip", "train.hip", "optim.hip", "glue.hip", "frontend.hip", "encoder_train.hip", "duration_train.hip", "tts_train.hip", "decoder.hip", "vocoder.hip", "speaker.hip", "units.hip", "units_fit.hip", "ctc.hip", "ctc_train.hip", "level.hip", "mel.hip", "resample.hip", "hubert.hip", "whisper.hip", "mos.hip"]
 # every source includes kernels.h; decoder.hip also includes the two .inc files (one stale check for all: a header edit is rare)
-HEADERS = ["kernels.h", "mfma_layout.h", "f16x3_tile.h", "handle.h", "item_lens.h", "conv1d_planar.h", "whisper_encoder.h", "dense_tile.h", "ctc_limits.h", "frontend.h", "pack_f16.h", "wino4_coef.h", "units_fit_layout.h", "train_host.inc", "train_abi.inc", os.path.join("..", "..", "include", "unitspeech_hip.h")]
+HEADERS = ["kernels.h", "mfma_layout.h", "f16x3_tile.h", "handle.h", "item_lens.h", "conv1d_planar.h", "whisper_encoder.h", "whisper_beam.h", "dense_tile.h", "ctc_limits.h", "frontend.h", "pack_f16.h", "wino4_coef.h", "units_fit_layout.h", "train_host.inc", "train_abi.inc", os.path.join("..", "..", "include", "unitspeech_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # extra hipcc flags for one-off builds (e.g. -DUS_STAMP / -DUS_LIFE instrumentation): never set in production
 FLAGS += os.environ.get("UNITSPEECH_AMD_EXTRA_FLAGS", "").split()

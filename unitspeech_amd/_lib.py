@@ -209,6 +209,14 @@ SIGNATURES = {
     "us_whisper_select_scratch_bytes": (C.c_size_t, [C.c_int]),
     "us_whisper_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(us_whisper_history), C.POINTER(us_whisper_decode_options), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_whisper_beam_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "us_whisper_decode_beam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int,
+                                         C.POINTER(us_whisper_decode_options), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "us_whisper_beam_select_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "us_whisper_beam_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(us_whisper_history), C.POINTER(C.c_double),
+                                         C.POINTER(us_whisper_decode_options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "us_units_pack_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "us_units_workspace_bytes": (C.c_size_t, [C.c_int] * 5),

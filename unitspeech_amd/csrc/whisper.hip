@@ -22,6 +22,10 @@
 //    chunk index, decides (the log-sum-exp of the timestamps strictly above the best text logit: a timestamp), and writes the token, its
 //    log-probability and the new history.  No atomics on floats; an item's summation order depends on V alone.
 //  - wh_nospeech_kernel: softmax(unfiltered logits)[no_speech] at the start token's position, from the partial kernel's plain mode.
+//  - wh_beam_partial_kernel + wh_beam_row_kernel + wh_beam_book_kernel, wh_beam_final_kernel: beam search under the same rules
+//    (us_whisper_decode_beam, us_whisper_beam_select).  An item's n rows ride in one launch group; the cross keys / values stay per item
+//    (wh_cross_attn_kernel reads item m / rpi), the self cache stays where each row wrote it and wh_self_attn_kernel<true> finds every
+//    position's key through a per-row ancestry table.  See the section in front of the kernels.
 // No kernel waits on a value another kernel writes; the host loop runs at most max_new steps and reads the running count back every
 // kWhPoll steps.  Every reduction has a fixed order and no launch depends on the batch: an item alone or in a batch, and repeated calls, give
 // the same bits.
@@ -37,6 +41,7 @@
 #include "handle.h"
 #include "item_lens.h"
 #include "kernels.h"
+#include "whisper_beam.h"
 #include "whisper_encoder.h"
 
 namespace us {
@@ -144,18 +149,24 @@ __global__ __launch_bounds__(256) void wh_gemm_kernel(WhGemmArgs a) {
 // q [M][H] (scaled) against keys 0 .. n - 1 of the item's cache: kc [n][H] keys, vc the values; head h owns channels [h d, (h + 1) d).
 // grid: (heads, items), one wave.  Lane j takes keys j, j + 64, ...; the maximum and the sum meet by wave_max / wave_sum; lane c then adds up
 // channel c over the keys in order.
+// kAnc (beam search): row m's key and value of position j live in the cache of row anc[m][j] of the group (the row that computed them: an
+// ancestor of m, or m itself); the arithmetic and its order are the same.
+template <bool kAnc>
 __global__ __launch_bounds__(64) void wh_self_attn_kernel(const float* __restrict__ q, const float* __restrict__ cache, float* __restrict__ out,
-                                                          long long item_stride, int Tm, int H, int d, int n) {
+                                                          const int* __restrict__ anc, long long item_stride, int Tm, int H, int d, int n) {
   __shared__ float qs[64];
   __shared__ float ps[kWhMaxKeys];
+  __shared__ int rw[kAnc ? kWhMaxKeys : 1];
   const int lane = threadIdx.x, head = blockIdx.x, m = blockIdx.y, hd = head * d;
-  const float* __restrict__ kc = cache + (size_t)m * item_stride + hd;
+  const float* __restrict__ kc = cache + (kAnc ? (size_t)0 : (size_t)m * item_stride) + hd;
   const float* __restrict__ vc = kc + (size_t)Tm * H;
   qs[lane] = lane < d ? q[(size_t)m * H + hd + lane] : 0.f;
+  if (kAnc)
+    for (int j = lane; j < n; j += 64) rw[j] = anc[(size_t)m * Tm + j];
   __syncthreads();
   float mx = -INFINITY;
   for (int j = lane; j < n; j += 64) {
-    const float* kr = kc + (size_t)j * H;
+    const float* kr = kc + (kAnc ? (size_t)rw[j] * item_stride : (size_t)0) + (size_t)j * H;
     float s = 0.f;
     for (int c = 0; c < d; c += 4) {
       const f32x4 k4 = *reinterpret_cast<const f32x4*>(kr + c);
@@ -176,24 +187,26 @@ __global__ __launch_bounds__(64) void wh_self_attn_kernel(const float* __restric
   __syncthreads();
   if (lane < d) {
     float o = 0.f;
-    for (int j = 0; j < n; ++j) o = fmaf(ps[j], vc[(size_t)j * H + lane], o);
+    for (int j = 0; j < n; ++j) o = fmaf(ps[j], vc[(kAnc ? (size_t)rw[j] * item_stride : (size_t)0) + (size_t)j * H + lane], o);
     out[(size_t)m * H + hd + lane] = o / l;
   }
 }
 
-// q [M][H] (scaled) against the S encoder frames: kv [2 H][S] planar per item (keys, then values).  grid: (heads, items), kWhCrossWaves waves.
+// q [M][H] (scaled) against the S encoder frames: kv [2 H][S] planar per item (keys, then values).  grid: (heads, rows), kWhCrossWaves waves.
+// Row m reads item m / rpi: greedy decoding has one row per item (rpi = 1), a beam's rows share their item's keys and values.
 // Thread t takes frames t, t + 64 kWhCrossWaves, ...; wave w then adds up channels w, w + kWhCrossWaves, ... of the head, a lane over frames
 // lane, lane + 64, ...  The loops are unrolled so that a thread has several loads in flight; the order of every sum is the loop's.
 constexpr int kWhCrossWaves = 16;
 
 __global__ __launch_bounds__(64 * kWhCrossWaves) void wh_cross_attn_kernel(const float* __restrict__ q, const float* __restrict__ kv,
-                                                                           float* __restrict__ out, long long item_stride, int S, int H, int d) {
+                                                                           float* __restrict__ out, long long item_stride, int S, int H, int d,
+                                                                           int rpi) {
   constexpr int NT = 64 * kWhCrossWaves;
   __shared__ float qs[64];
   __shared__ float ps[kWhMaxKeys];
   __shared__ float red[kWhCrossWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, head = blockIdx.x, m = blockIdx.y, hd = head * d;
-  const float* __restrict__ kp = kv + (size_t)m * item_stride + (size_t)hd * S;
+  const float* __restrict__ kp = kv + (size_t)(m / rpi) * item_stride + (size_t)hd * S;
   const float* __restrict__ vp = kp + (size_t)H * S;
   if (tid < 64) qs[tid] = tid < d ? q[(size_t)m * H + hd + tid] : 0.f;
   __syncthreads();
@@ -351,6 +364,23 @@ __device__ __forceinline__ float wh_block_sum(float v, float* rs) {
 }
 
 // grid: (chunks, items).  plain: every token survives and counts as text (the no-speech probability).
+// the surviving ranges of the two sides, from a row's history: text [text_lo, text_hi), timestamps [ts_lo, ts_hi); first: no token sampled yet
+struct WhRanges {
+  int text_lo, text_hi, ts_lo, ts_hi, first;
+};
+__device__ __forceinline__ WhRanges wh_ranges(const WhRules& r, int V, int count, int last, int pen, int lts) {
+  WhRanges g{0, r.tb, r.tb, V, count == 0};
+  const bool last_is = count >= 1 && last >= r.tb, pen_is = count < 2 || pen >= r.tb;
+  if (last_is && pen_is) g.ts_hi = g.ts_lo;
+  if (last_is && !pen_is) g.text_lo = r.eos;
+  if (lts >= 0) g.ts_lo = max(g.ts_lo, last_is && !pen_is ? lts : lts + 1);
+  if (g.first) {
+    g.text_hi = 0;
+    if (r.max_init >= 0) g.ts_hi = min(g.ts_hi, r.tb + r.max_init + 1);
+  }
+  return g;
+}
+
 __global__ __launch_bounds__(256) void wh_select_partial_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ suppress,
                                                                 const unsigned char* __restrict__ begin, WhDecState st, WhRules r,
                                                                 WhPart* __restrict__ part, int V, int nchunks, int plain) {
@@ -364,16 +394,8 @@ __global__ __launch_bounds__(256) void wh_select_partial_kernel(const float* __r
     ts_lo = V;
     no_ts = -1;
   } else {
-    const int count = st.count[m], last = st.last[m], pen = st.pen[m], lts = st.last_ts[m];
-    const bool last_is = count >= 1 && last >= r.tb, pen_is = count < 2 || pen >= r.tb;
-    first = count == 0;
-    if (last_is && pen_is) ts_hi = ts_lo;
-    if (last_is && !pen_is) text_lo = r.eos;
-    if (lts >= 0) ts_lo = max(ts_lo, last_is && !pen_is ? lts : lts + 1);
-    if (first) {
-      text_hi = 0;
-      if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init + 1);
-    }
+    const WhRanges g = wh_ranges(r, V, st.count[m], st.last[m], st.pen[m], st.last_ts[m]);
+    text_lo = g.text_lo, text_hi = g.text_hi, ts_lo = g.ts_lo, ts_hi = g.ts_hi, first = g.first;
   }
   const float* __restrict__ x = logits + (size_t)m * V;
   float y[2];
@@ -467,16 +489,17 @@ __global__ __launch_bounds__(256) void wh_select_close_kernel(const WhPart* __re
   }
 }
 
-// grid: items.  out[m] = exp(x[no_speech] - logsumexp(x)) from the plain partials (the text side holds every token)
+// grid: items.  out[item] = exp(x[no_speech] - logsumexp(x)) of row m = item * rpi (a beam's first row) from the plain partials (the text
+// side holds every token)
 __global__ __launch_bounds__(256) void wh_nospeech_kernel(const WhPart* __restrict__ part, const float* __restrict__ logits, float* __restrict__ out,
-                                                          int V, int nchunks, int no_speech) {
+                                                          int V, int nchunks, int no_speech, int rpi) {
   __shared__ float rv[4], rs[4];
   __shared__ int ri[4];
-  const int m = blockIdx.x;
+  const int m = blockIdx.x * rpi;
   float M, S;
   int I;
   wh_join(part + ((size_t)m * 2 + 0) * nchunks, nchunks, M, I, S, rv, ri, rs);
-  if (threadIdx.x == 0) out[m] = S > 0.f ? expf(logits[(size_t)m * V + no_speech] - (M + logf(S))) : 0.f;
+  if (threadIdx.x == 0) out[blockIdx.x] = S > 0.f ? expf(logits[(size_t)m * V + no_speech] - (M + logf(S))) : 0.f;
 }
 
 __global__ __launch_bounds__(256) void wh_decode_init_kernel(WhDecState st, long long* __restrict__ tokens, long long* __restrict__ n,
@@ -544,6 +567,372 @@ inline void wh_select_step(const float* L, const unsigned char* suppress, const 
   const int nc = wh_chunks(V);
   hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, nb), dim3(256), 0, s, L, suppress, begin, c.st, r, c.part, V, nc, 0);
   hipLaunchKernelGGL(wh_select_close_kernel, dim3(nb), dim3(256), 0, s, c.part, c.st, r, tokens, n, sum_out, step_lp, decided, nc, max_new, step);
+}
+
+// ---- beam search under the timestamp rules ------------------------------------------------------------------------------------------
+// An item has n rows (beam_size), item-major in a launch group of floor(16 / n) whole items, so a group's step still streams every weight
+// once.  Four launches follow the step's logits:
+//  - wh_beam_partial_kernel, grid (chunks, rows): wh_select_partial_kernel's masks, maxima and sums, and beside them per side the chunk's top
+//    n + 1 finite survivors (value, index), placed by counting rank in LDS (the larger value, the lower index on a tie);
+//  - wh_beam_row_kernel, grid rows: joins the partials as wh_select_close_kernel does, decides text against timestamps, and picks the row's top
+//    n + 1 survivors out of the chunks' lists, one after the other in the strict order (value, index): the result does not depend on how the
+//    lists are visited.  -> the row's candidates (token, log-probability);
+//  - wh_beam_book_kernel, one workgroup per item: ranks the <= n (n + 1) candidates by counting in LDS, walks them (whisper_beam.h), and writes
+//    the new rows' scores, histories, sequences and ancestry, the pool and the item's end;
+//  - wh_beam_final_kernel, once per group: tops the pool up, ranks it, and writes the winner.
+// Sequences and ancestry are ping-pong tables indexed by the step's parity; scores are doubles, as us_whisper_decode's sums.
+
+constexpr int kWhTop = kWbMaxBeam + 1;      // candidates a row offers at most
+
+struct WhBeamState {                // a group's state: rows [kWhItems], items [kWhItems]
+  int *cur, *live, *count, *last, *pen, *last_ts;       // rows: the token to embed next, live, and the history as WhDecState
+  int *cand_n, *done, *pool_n, *nsteps, *running;       // rows: candidates offered; items: ended, pool entries, steps taken; the group's running items
+  double* score;                    // rows
+  int* cand_tok;                    // [rows][kWhTop]
+  float* cand_lp;
+  int *seq, *anc;                   // [2][rows][L] the sampled sequences, [2][rows][Tm] position -> group row that holds its key
+  double* pool_score;               // [items][kWbMaxPool]
+  int *pool_len, *pool_seq;         // [items][kWbMaxPool], [items][kWbMaxPool][L]
+  WhPart* part;                     // [rows][2][chunks]
+  float* topv;                      // [rows][2][chunks][kWhTop]
+  int *topi, *topn;                 // the same, and [rows][2][chunks] how many are valid
+};
+struct WhBeamHist {                 // us_whisper_beam_select: the group's rows, from the host
+  int count[kWhItems], last[kWhItems], pen[kWhItems], last_ts[kWhItems], live[kWhItems];
+  double score[kWhItems];
+};
+struct WhBeamOut {                  // us_whisper_beam_select's results per item, or nulls
+  int* parent;                      // [items][n], -1: the row is dead
+  long long* token;                 // [items][n]
+  double* score;                    // [items][n]
+  int* n_live;                      // [items]
+  int* fin_parent;                  // [items][n] in walk order
+  double* fin_score;
+  int* n_fin;                       // [items]
+};
+
+// hist: null (a decoding starts: row 0 of every item live, nothing sampled) or the host's rows.  L, Tm: the strides of seq and anc.
+__global__ __launch_bounds__(256) void wh_beam_init_kernel(WhBeamState st, WhBeamHist hist, int use_hist, int n, int items, int eos, int L, int Tm) {
+  const int tid = threadIdx.x;
+  if (tid < kWhItems) {
+    const bool row = tid < items * n;
+    st.cur[tid] = eos;
+    st.live[tid] = use_hist ? hist.live[tid] : (row && tid % n == 0 ? 1 : 0);
+    st.count[tid] = use_hist ? hist.count[tid] : 0;
+    st.last[tid] = use_hist ? hist.last[tid] : -1;
+    st.pen[tid] = use_hist ? hist.pen[tid] : -1;
+    st.last_ts[tid] = use_hist ? hist.last_ts[tid] : -1;
+    st.score[tid] = use_hist ? hist.score[tid] : 0.0;
+    st.cand_n[tid] = 0;
+    st.done[tid] = 0;
+    st.pool_n[tid] = 0;
+    st.nsteps[tid] = 0;
+  }
+  if (tid == 0) *st.running = items;
+  for (int i = tid; i < 2 * kWhItems * Tm; i += 256) st.anc[i] = (i / Tm) % kWhItems;
+  for (int i = tid; i < 2 * kWhItems * L; i += 256) st.seq[i] = eos;
+}
+
+// grid: (chunks, rows)
+__global__ __launch_bounds__(256) void wh_beam_partial_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ suppress,
+                                                              const unsigned char* __restrict__ begin, WhBeamState st, WhRules r, int V, int nchunks,
+                                                              int n) {
+  __shared__ float rv[4], rs[4];
+  __shared__ int ri[4];
+  __shared__ float yv[kWhChunk];
+  __shared__ int sd[kWhChunk];
+  const int tid = threadIdx.x, chunk = blockIdx.x, m = blockIdx.y, K = n + 1;
+  if (!st.live[m] || st.done[m / n]) return;            // the row offers nothing: its partials are not read
+  const WhRanges g = wh_ranges(r, V, st.count[m], st.last[m], st.pen[m], st.last_ts[m]);
+  const int no_ts = r.tb - 1;
+  const float* __restrict__ x = logits + (size_t)m * V;
+  float y[2];
+  int side[2];                      // 0 text, 1 timestamp, -1 masked
+  float tv = -INFINITY, sv = -INFINITY;
+  int ti = kWhNone, si = kWhNone;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int v = chunk * kWhChunk + j * 256 + tid;
+    side[j] = -1;
+    y[j] = -INFINITY;
+    if (v < V && v != no_ts && !((suppress && suppress[v]) || (g.first && begin && begin[v]))) {
+      if (v >= g.text_lo && v < g.text_hi) side[j] = 0;
+      else if (v >= g.ts_lo && v < g.ts_hi) side[j] = 1;
+      if (side[j] >= 0) {
+        y[j] = x[v];
+        if (side[j] == 0) wh_take(tv, ti, y[j], v);
+        else wh_take(sv, si, y[j], v);
+      }
+    }
+    yv[j * 256 + tid] = y[j];
+    sd[j * 256 + tid] = y[j] > -INFINITY ? side[j] : -1;        // a token at -inf is never a candidate
+  }
+  wh_block_best(tv, ti, rv, ri);
+  wh_block_best(sv, si, rv, ri);
+  float te = 0.f, se = 0.f, tc = 0.f, sc = 0.f;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (side[j] == 0 && tv > -INFINITY) te += expf(y[j] - tv);
+    if (side[j] == 1 && sv > -INFINITY) se += expf(y[j] - sv);
+    if (side[j] == 0 && y[j] > -INFINITY) tc += 1.f;
+    if (side[j] == 1 && y[j] > -INFINITY) sc += 1.f;
+  }
+  te = wh_block_sum(te, rs);
+  se = wh_block_sum(se, rs);
+  tc = wh_block_sum(tc, rs);        // counts up to 512: exact
+  sc = wh_block_sum(sc, rs);
+  const size_t p0 = ((size_t)m * 2 + 0) * nchunks + chunk, p1 = ((size_t)m * 2 + 1) * nchunks + chunk;
+  if (tid == 0) {
+    st.part[p0] = WhPart{tv, te, ti, 0};
+    st.part[p1] = WhPart{sv, se, si, 0};
+    st.topn[p0] = min((int)tc, K);
+    st.topn[p1] = min((int)sc, K);
+  }
+  // the place of each finite survivor among those of its side in this chunk: the larger value first, then the lower index
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int own = j * 256 + tid, sj = sd[own];
+    if (sj < 0) continue;
+    int rank = 0;
+    for (int u = 0; u < kWhChunk && rank < K; ++u) rank += sd[u] == sj && (yv[u] > y[j] || (yv[u] == y[j] && u < own)) ? 1 : 0;
+    if (rank < K) {
+      const size_t e = (sj == 0 ? p0 : p1) * kWhTop + rank;
+      st.topv[e] = y[j];
+      st.topi[e] = chunk * kWhChunk + own;
+    }
+  }
+}
+
+// grid: rows.  The row's candidates: its top n + 1 survivors (token, log-probability), or (eos, 0) when nothing survives.
+__global__ __launch_bounds__(256) void wh_beam_row_kernel(WhBeamState st, WhRules r, int nchunks, int n) {
+  __shared__ float rv[4], rs[4];
+  __shared__ int ri[4];
+  const int m = blockIdx.x, K = n + 1;
+  if (!st.live[m] || st.done[m / n]) {
+    if (threadIdx.x == 0) st.cand_n[m] = 0;
+    return;
+  }
+  const WhPart* pt = st.part + ((size_t)m * 2 + 0) * nchunks;
+  float Mt, St, Ms, Ss;
+  int It, Is;
+  wh_join(pt, nchunks, Mt, It, St, rv, ri, rs);
+  wh_join(pt + nchunks, nchunks, Ms, Is, Ss, rv, ri, rs);
+  const float lse_ts = Ss > 0.f ? Ms + logf(Ss) : -INFINITY;
+  const bool ts_wins = lse_ts > Mt;
+  float lse = lse_ts;
+  if (!ts_wins) {
+    const float M = fmaxf(Mt, Ms);
+    const float S = (Mt > -INFINITY ? St * expf(Mt - M) : 0.f) + (Ms > -INFINITY ? Ss * expf(Ms - M) : 0.f);
+    lse = S > 0.f ? M + logf(S) : -INFINITY;
+  }
+  // entries [side][chunk][k]; with the timestamps winning only side 1 counts
+  const int e0 = ts_wins ? nchunks * kWhTop : 0, e1 = 2 * nchunks * kWhTop;
+  const float* tv = st.topv + (size_t)m * 2 * nchunks * kWhTop;
+  const int* ti = st.topi + (size_t)m * 2 * nchunks * kWhTop;
+  const int* tn = st.topn + (size_t)m * 2 * nchunks;
+  float pv = INFINITY;
+  int pi = -1, got = 0;
+  for (int k = 0; k < K; ++k) {
+    float bv = -INFINITY;
+    int bi = kWhNone;
+    for (int e = e0 + threadIdx.x; e < e1; e += 256) {
+      if (e % kWhTop >= tn[e / kWhTop]) continue;
+      const float v = tv[e];
+      const int i = ti[e];
+      if (v < pv || (v == pv && i > pi)) wh_take(bv, bi, v, i);       // behind the last one taken
+    }
+    wh_block_best(bv, bi, rv, ri);
+    if (bi == kWhNone || !(lse > -INFINITY)) break;
+    if (threadIdx.x == 0) {
+      st.cand_tok[m * kWhTop + k] = bi;
+      st.cand_lp[m * kWhTop + k] = bv - lse;
+    }
+    pv = bv;
+    pi = bi;
+    ++got;
+  }
+  if (threadIdx.x == 0) {
+    if (got == 0) {
+      st.cand_tok[m * kWhTop] = r.eos;
+      st.cand_lp[m * kWhTop] = 0.f;
+      got = 1;
+    }
+    st.cand_n[m] = got;
+  }
+}
+
+// grid: items.  step: the sequences hold `step` tokens; pos: the position this step's rows wrote in the self cache.  tables: 0 leaves the
+// sequence, ancestry and pool tables alone (us_whisper_beam_select).
+__global__ __launch_bounds__(256) void wh_beam_book_kernel(WhBeamState st, WhRules r, WhBeamOut out, int n, int C, int step, int pos, int L, int Tm,
+                                                           int tables) {
+  __shared__ double tot[kWbMaxCands];
+  __shared__ int par[kWbMaxCands], tok[kWbMaxCands], ord[kWbMaxCands];
+  __shared__ int cbase[kWbMaxBeam + 1], hc[kWbMaxBeam], hl[kWbMaxBeam], hts[kWbMaxBeam];
+  __shared__ WbRow rows[kWbMaxBeam];
+  __shared__ WbFin fin[kWbMaxCands];
+  __shared__ WbWalk w;
+  const int tid = threadIdx.x, item = blockIdx.x, base = item * n;
+  if (st.done[item]) return;
+  if (tid == 0) {
+    int c = 0;
+    for (int j = 0; j < n; ++j) {
+      cbase[j] = c;
+      c += st.live[base + j] ? min(max(st.cand_n[base + j], 0), n + 1) : 0;
+    }
+    cbase[n] = c;
+  }
+  if (tid < n) {
+    hc[tid] = st.count[base + tid];
+    hl[tid] = st.last[base + tid];
+    hts[tid] = st.last_ts[base + tid];
+  }
+  __syncthreads();
+  const int count = cbase[n];
+  for (int c = tid; c < count; c += 256) {
+    int j = 0;
+    while (j + 1 < n && cbase[j + 1] <= c) ++j;
+    const int k = c - cbase[j];
+    par[c] = j;
+    tok[c] = st.cand_tok[(base + j) * kWhTop + k];
+    tot[c] = st.score[base + j] + (double)st.cand_lp[(base + j) * kWhTop + k];
+  }
+  __syncthreads();
+  for (int c = tid; c < count; c += 256) ord[wb_rank(tot, count, c)] = c;
+  __syncthreads();
+  // a row offers eos at most once, so at most n entries finish (fin holds one per candidate all the same)
+  if (tid == 0) w = wb_walk(ord, par, tok, tot, count, n, C, r.eos, st.pool_n[item], rows, fin);
+  __syncthreads();
+  const int ob = step & 1, nb = ob ^ 1, pool0 = st.pool_n[item];
+  if (tables) {
+    for (int a = 0; a < w.added; ++a) {
+      const int* src = st.seq + ((size_t)ob * kWhItems + base + fin[a].parent) * L;
+      int* dst = st.pool_seq + ((size_t)item * kWbMaxPool + pool0 + a) * L;
+      for (int t = tid; t < step; t += 256) dst[t] = src[t];
+    }
+    for (int k = 0; k < n; ++k) {
+      const int j = k < w.rows ? rows[k].parent : k;
+      if (k < w.rows) {
+        const int* src = st.seq + ((size_t)ob * kWhItems + base + j) * L;
+        int* dst = st.seq + ((size_t)nb * kWhItems + base + k) * L;
+        for (int t = tid; t < step; t += 256) dst[t] = src[t];
+        if (tid == 0 && step < L) dst[step] = rows[k].token;
+      }
+      const int* as = st.anc + ((size_t)ob * kWhItems + base + j) * Tm;
+      int* ad = st.anc + ((size_t)nb * kWhItems + base + k) * Tm;
+      for (int t = tid; t <= pos + 1 && t < Tm; t += 256) ad[t] = t <= pos && k < w.rows ? as[t] : base + k;
+    }
+  }
+  __syncthreads();                  // every read of the old rows lies in front of these writes
+  if (tid < n) {
+    const int k = tid, m = base + k;
+    if (k < w.rows) {
+      const int j = rows[k].parent, t = rows[k].token;
+      st.live[m] = 1;
+      st.cur[m] = t;
+      st.count[m] = hc[j] + 1;
+      st.pen[m] = hl[j];
+      st.last[m] = t;
+      st.last_ts[m] = t >= r.tb ? t : hts[j];
+      st.score[m] = rows[k].score;
+    } else {
+      st.live[m] = 0;
+      st.cur[m] = r.eos;
+    }
+    if (out.parent) {
+      out.parent[m] = k < w.rows ? rows[k].parent : -1;
+      out.token[m] = k < w.rows ? rows[k].token : r.eos;
+      out.score[m] = k < w.rows ? rows[k].score : 0.0;
+      out.fin_parent[m] = k < w.finished ? fin[k].parent : -1;
+      out.fin_score[m] = k < w.finished ? fin[k].score : 0.0;
+    }
+  }
+  if (tid == 0) {
+    for (int a = 0; a < w.added; ++a) {
+      st.pool_score[item * kWbMaxPool + pool0 + a] = fin[a].score;
+      st.pool_len[item * kWbMaxPool + pool0 + a] = step;
+    }
+    st.pool_n[item] = pool0 + w.added;
+    st.nsteps[item] = step + 1;
+    if (out.parent) {
+      out.n_live[item] = w.rows;
+      out.n_fin[item] = w.finished;
+    }
+    if (w.ended) {
+      st.done[item] = 1;
+      atomicSub(st.running, 1);
+    }
+  }
+}
+
+// grid: items.  finalise and rank: tokens[item][max_new] (eos at and after the end), cnt[item], sum_out[item]
+__global__ __launch_bounds__(256) void wh_beam_final_kernel(WhBeamState st, long long* __restrict__ tokens, long long* __restrict__ cnt,
+                                                            float* __restrict__ sum_out, int n, int L, int max_new, int eos) {
+  __shared__ double sc[kWbMaxPool + kWbMaxBeam];
+  __shared__ int len[kWbMaxPool + kWbMaxBeam], top[kWbMaxBeam];
+  __shared__ int win, total, pool;
+  const int tid = threadIdx.x, item = blockIdx.x, base = item * n;
+  if (tid == 0) {
+    pool = min(st.pool_n[item], kWbMaxPool);
+    for (int i = 0; i < pool; ++i) {
+      sc[i] = st.pool_score[item * kWbMaxPool + i];
+      len[i] = st.pool_len[item * kWbMaxPool + i];
+    }
+    const int k = wb_top_up(st.live + base, st.score + base, n, pool, top);
+    for (int u = 0; u < k; ++u) {
+      sc[pool + u] = st.score[base + top[u]];
+      len[pool + u] = st.count[base + top[u]];
+    }
+    total = pool + k;
+    win = total > 0 ? wb_winner(sc, len, total) : -1;
+  }
+  __syncthreads();
+  const int length = win < 0 ? 0 : min(len[win], max_new);
+  const int* src = win < 0 ? nullptr
+                   : win < pool ? st.pool_seq + ((size_t)item * kWbMaxPool + win) * L
+                                : st.seq + ((size_t)(st.nsteps[item] & 1) * kWhItems + base + top[win - pool]) * L;
+  for (int t = tid; t < max_new; t += 256) tokens[(size_t)item * max_new + t] = t < length ? src[t] : eos;
+  if (tid == 0) {
+    cnt[item] = length;
+    sum_out[item] = win < 0 ? 0.f : (float)sc[win];
+  }
+}
+
+// floats of a group's beam state with sequences of L tokens, ancestry over Tm positions and the partials of V logits
+inline size_t wh_beam_floats(int V, int L, int Tm) {
+  const size_t nc = (size_t)((V + kWhChunk - 1) / kWhChunk), R = kWhItems;
+  return pad64(11 * R) + pad64(2 * R) + 2 * pad64(R * kWhTop) + pad64(2 * R * L) + pad64(2 * R * Tm) + pad64(2 * R * kWbMaxPool) + pad64(R * kWbMaxPool) +
+         pad64(R * kWbMaxPool * L) + pad64(R * 2 * nc * 4) + 2 * pad64(R * 2 * nc * kWhTop) + pad64(R * 2 * nc);
+}
+inline WhBeamState wh_beam_carve(float* base, int V, int L, int Tm) {
+  const size_t nc = (size_t)((V + kWhChunk - 1) / kWhChunk), R = kWhItems;
+  WsTake take;
+  auto at = [&](size_t floats) { return base + take(floats); };
+  int* ints = reinterpret_cast<int*>(at(11 * R));
+  WhBeamState s{};
+  s.cur = ints; s.live = ints + R; s.count = ints + 2 * R; s.last = ints + 3 * R; s.pen = ints + 4 * R; s.last_ts = ints + 5 * R;
+  s.cand_n = ints + 6 * R; s.done = ints + 7 * R; s.pool_n = ints + 8 * R; s.nsteps = ints + 9 * R; s.running = ints + 10 * R;
+  s.score = reinterpret_cast<double*>(at(2 * R));
+  s.cand_tok = reinterpret_cast<int*>(at(R * kWhTop));
+  s.cand_lp = at(R * kWhTop);
+  s.seq = reinterpret_cast<int*>(at(2 * R * L));
+  s.anc = reinterpret_cast<int*>(at(2 * R * Tm));
+  s.pool_score = reinterpret_cast<double*>(at(2 * R * kWbMaxPool));
+  s.pool_len = reinterpret_cast<int*>(at(R * kWbMaxPool));
+  s.pool_seq = reinterpret_cast<int*>(at(R * kWbMaxPool * L));
+  s.part = reinterpret_cast<WhPart*>(at(R * 2 * nc * 4));
+  s.topv = at(R * 2 * nc * kWhTop);
+  s.topi = reinterpret_cast<int*>(at(R * 2 * nc * kWhTop));
+  s.topn = reinterpret_cast<int*>(at(R * 2 * nc));
+  return s;
+}
+
+// the three launches of one beam step of a group of `items` items behind its logits
+inline void wh_beam_step(const float* L, const unsigned char* suppress, const unsigned char* begin, const WhBeamState& st, const WhRules& r,
+                         const WhBeamOut& out, int V, int n, int C, int items, int step, int pos, int Ls, int Tm, int tables, hipStream_t s) {
+  const int nc = (V + kWhChunk - 1) / kWhChunk;
+  hipLaunchKernelGGL(wh_beam_partial_kernel, dim3(nc, items * n), dim3(256), 0, s, L, suppress, begin, st, r, V, nc, n);
+  hipLaunchKernelGGL(wh_beam_row_kernel, dim3(items * n), dim3(256), 0, s, st, r, nc, n);
+  hipLaunchKernelGGL(wh_beam_book_kernel, dim3(items), dim3(256), 0, s, st, r, out, n, C, step, pos, Ls, Tm, tables);
 }
 
 struct WhLinear {
@@ -695,8 +1084,10 @@ int wh_begin(us_whisper* h, const std::string& what, const float* feats, int B, 
 struct WhStep {                 // one group's buffers
   us_whisper* h;
   hipStream_t s;
-  float *X, *Q, *ATT, *FF, *cache, *kv;        // cache / kv: the group's first item of layer 0
-  int B, nb;
+  float *X, *Q, *ATT, *FF, *cache, *kv;        // cache / kv: the group's first row / item of layer 0
+  int B, nb;                    // the items of the call (a layer of kv is B items), the rows of the group
+  int cache_rows = 0, rpi = 1;  // rows of a layer of the self cache; rows per item: row m attends to the cross keys of item m / rpi
+  const int* anc = nullptr;     // beam search: [rows][max_target_positions], the group row that holds each position's key (else the row's own)
 };
 
 void wh_gemm(const WhStep& t, const float* x, int K, const float* ln_g, const float* ln_b, const float* res, int N, int gelu, int nseg, const WhSeg* seg) {
@@ -714,18 +1105,19 @@ void wh_layers(const WhStep& t, int pos) {
   const long long cache_item = 2ll * Tm * H, kv_item = 2ll * H * S;
   for (int i = 0; i < c.decoder_layers; ++i) {
     const WhDecLayer& l = t.h->dec[i];
-    float* cache = t.cache + (size_t)i * t.B * cache_item;
+    float* cache = t.cache + (size_t)i * t.cache_rows * cache_item;
     const float* kv = t.kv + (size_t)i * t.B * kv_item;
     const WhSeg qkv[3] = {{l.q.w, l.q.b, t.Q, H, qs},
                           {l.k.w, nullptr, cache + (size_t)pos * H, cache_item, 1.f},
                           {l.v.w, l.v.b, cache + (size_t)(Tm + pos) * H, cache_item, 1.f}};
     wh_gemm(t, t.X, H, l.ln1_g, l.ln1_b, nullptr, H, 0, 3, qkv);
-    hipLaunchKernelGGL(wh_self_attn_kernel, dim3(c.decoder_heads, t.nb), dim3(64), 0, t.s, t.Q, cache, t.ATT, cache_item, Tm, H, d, pos + 1);
+    if (t.anc) hipLaunchKernelGGL(wh_self_attn_kernel<true>, dim3(c.decoder_heads, t.nb), dim3(64), 0, t.s, t.Q, cache, t.ATT, t.anc, cache_item, Tm, H, d, pos + 1);
+    else hipLaunchKernelGGL(wh_self_attn_kernel<false>, dim3(c.decoder_heads, t.nb), dim3(64), 0, t.s, t.Q, cache, t.ATT, t.anc, cache_item, Tm, H, d, pos + 1);
     const WhSeg o{l.o.w, l.o.b, t.X, H, 1.f};
     wh_gemm(t, t.ATT, H, nullptr, nullptr, t.X, H, 0, 1, &o);
     const WhSeg cq{l.cq.w, l.cq.b, t.Q, H, qs};
     wh_gemm(t, t.X, H, l.ln2_g, l.ln2_b, nullptr, H, 0, 1, &cq);
-    hipLaunchKernelGGL(wh_cross_attn_kernel, dim3(c.decoder_heads, t.nb), dim3(64 * kWhCrossWaves), 0, t.s, t.Q, kv, t.ATT, kv_item, S, H, d);
+    hipLaunchKernelGGL(wh_cross_attn_kernel, dim3(c.decoder_heads, t.nb), dim3(64 * kWhCrossWaves), 0, t.s, t.Q, kv, t.ATT, kv_item, S, H, d, t.rpi);
     const WhSeg co{l.co.w, l.co.b, t.X, H, 1.f};
     wh_gemm(t, t.ATT, H, nullptr, nullptr, t.X, H, 0, 1, &co);
     const WhSeg f1{l.fc1.w, l.fc1.b, t.FF, I, 1.f};
@@ -752,7 +1144,7 @@ WhStep wh_group(us_whisper* h, const WhPlan& p, float* base, int B, int b0, int 
   const auto& c = h->cfg;
   const size_t H = (size_t)c.d_model;
   return WhStep{h, s, base + p.x, base + p.q, base + p.att, base + p.ff, base + p.cache + (size_t)b0 * 2 * c.max_target_positions * H,
-                base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions, B, nb};
+                base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions, B, nb, B, 1, nullptr};
 }
 
 std::string wh_bad_token(const std::string& what, const int64_t* ids, size_t n, int V) {
@@ -986,7 +1378,7 @@ int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, 
     auto no_speech = [&](int pos) {                     // L holds the logits of position `pos`
       if (o.no_speech < 0 || pos != o.sot_index) return;
       hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, nb), dim3(256), 0, s, L, nullptr, nullptr, sel.st, r, sel.part, V, nc, 1);
-      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(nb), dim3(256), 0, s, sel.part, L, no_speech_prob + b0, V, nc, o.no_speech);
+      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(nb), dim3(256), 0, s, sel.part, L, no_speech_prob + b0, V, nc, o.no_speech, 1);
     };
     WhTokens f;
     for (int pos = 0; pos + 1 < P; ++pos) {             // the prompt but for its last token: keys and values, and the start token's logits
@@ -1014,6 +1406,174 @@ int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, 
       }
     }
   });
+  if (e == hipSuccess) e = hipGetLastError();
+  return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
+}
+
+}  // extern "C"
+
+namespace us {
+namespace {
+
+// rows of the largest launch group of B items at beam size n: floor(16 / n) whole items
+inline int wh_beam_group_rows(int B, int n) { return std::min(B, kWhItems / n) * n; }
+
+struct WhBeamPlan {             // float offsets behind wh_plan(h, B): the self cache of one group's rows, the group's beam state
+  size_t cache, state, total;
+};
+WhBeamPlan wh_beam_plan(const us_whisper* h, int B, int n) {
+  const auto& c = h->cfg;
+  WhBeamPlan p{};
+  WsTake take;
+  take(wh_plan(h, B).total);
+  p.cache = take((size_t)c.decoder_layers * wh_beam_group_rows(B, n) * 2 * c.max_target_positions * c.d_model);
+  p.state = take(wh_beam_floats(c.vocab_size, c.max_target_positions, c.max_target_positions));
+  p.total = take.total;
+  return p;
+}
+
+}  // namespace
+}  // namespace us
+
+extern "C" {
+
+size_t us_whisper_beam_workspace_bytes(us_whisper_handle h, int B, int beam_size) {
+  return h && B > 0 && B <= 65535 && beam_size >= 1 && beam_size <= kWbMaxBeam ? wh_beam_plan(h, B, beam_size).total * sizeof(float) + 256 : 0;
+}
+
+size_t us_whisper_beam_select_scratch_bytes(int V, int beam_size) {
+  return V >= 1 && V <= (1 << 24) && beam_size >= 1 && beam_size <= kWbMaxBeam ? wh_beam_floats(V, 1, 2) * sizeof(float) + 256 : 0;
+}
+
+int us_whisper_beam_select(const float* logits, int B, int V, int beam_size, const us_whisper_history* history, const double* scores,
+                           const us_whisper_decode_options* options, const unsigned char* suppress, const unsigned char* begin_suppress,
+                           int32_t* parent, int64_t* token, double* score, int32_t* n_live, int32_t* fin_parent, double* fin_score, int32_t* n_fin,
+                           void* scratch, size_t scratch_bytes, us_stream stream) {
+  const std::string what = "us_whisper_beam_select";
+  auto bad = [&](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, what + ": " + m); };
+  if (!logits || !history || !scores || !options || !parent || !token || !score || !n_live || !fin_parent || !fin_score || !n_fin || B < 1)
+    return bad("bad argument");
+  const auto& o = *options;
+  const int n = beam_size;
+  if (n < 1 || n > kWbMaxBeam) return bad("beam_size must lie in [1, " + std::to_string(kWbMaxBeam) + "]");
+  if (V < 1 || V > (1 << 24)) return bad("V must lie in [1, 2^24]");
+  if (o.eos < 0 || o.eos >= o.no_timestamps) return bad("eos must lie in [0, no_timestamps)");
+  if ((long long)o.no_timestamps + 1 >= V) return bad("no_timestamps + 1 >= V: the vocabulary has no timestamp token");
+  if (o.max_initial_timestamp_index < -1) return bad("max_initial_timestamp_index must be -1 (none) or an index");
+  if (!scratch || scratch_bytes < us_whisper_beam_select_scratch_bytes(V, n))
+    return WeightTable::fail(nullptr, US_EWORKSPACE, what + ": scratch too small (us_whisper_beam_select_scratch_bytes)");
+  for (long long m = 0; m < (long long)B * n; ++m)
+    if (history[m].n_sampled < 0) return bad("history[" + std::to_string(m) + "].n_sampled is negative");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const WhBeamState st = wh_beam_carve(ws_align(scratch), V, 1, 2);
+  const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
+  const int ipg = kWhItems / n;
+  for (int b0 = 0; b0 < B; b0 += ipg) {
+    const int items = std::min(ipg, B - b0);
+    WhBeamHist hist{};
+    for (int m = 0; m < items * n; ++m) {
+      const us_whisper_history& hh = history[(size_t)b0 * n + m];
+      hist.count[m] = hh.n_sampled;
+      hist.last[m] = hh.n_sampled >= 1 ? hh.last : -1;
+      hist.pen[m] = hh.n_sampled >= 2 ? hh.penultimate : -1;
+      hist.last_ts[m] = hh.last_timestamp >= r.tb ? hh.last_timestamp : -1;
+      hist.live[m] = hh.done == 0;
+      hist.score[m] = scores[(size_t)b0 * n + m];
+    }
+    const WhBeamOut out{parent + (size_t)b0 * n,     reinterpret_cast<long long*>(token) + (size_t)b0 * n, score + (size_t)b0 * n, n_live + b0,
+                        fin_parent + (size_t)b0 * n, fin_score + (size_t)b0 * n,                           n_fin + b0};
+    hipLaunchKernelGGL(wh_beam_init_kernel, dim3(1), dim3(256), 0, s, st, hist, 1, n, items, o.eos, 1, 2);
+    wh_beam_step(logits + (size_t)b0 * n * V, suppress, begin_suppress, st, r, out, V, n, kWbMaxPool, items, 0, 0, 1, 2, 0, s);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? US_OK : WeightTable::fail(nullptr, US_EHIP, what + ": " + hipGetErrorString(e));
+}
+
+int us_whisper_decode_beam(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P,
+                           const us_whisper_decode_options* options, int beam_size, int max_candidates, const unsigned char* suppress,
+                           const unsigned char* begin_suppress, int64_t* tokens, int64_t* n, float* sum_logprobs, float* no_speech_prob,
+                           void* workspace, size_t workspace_bytes, us_stream stream) {
+  const std::string what = "us_whisper_decode_beam";
+  if (!h || !prompt || !options || !tokens || !n || !sum_logprobs || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
+  const auto& c = h->cfg;
+  const auto& o = *options;
+  const int V = c.vocab_size, max_new = o.max_new, nb = beam_size, C = max_candidates, Tm = c.max_target_positions;
+  if (nb < 1 || nb > kWbMaxBeam)
+    return h->fail(US_EINVAL, what + ": beam_size = " + std::to_string(nb) + " must lie in [1, " + std::to_string(kWbMaxBeam) + "]");
+  if (C < 1 || C > kWbMaxPool)
+    return h->fail(US_EINVAL, what + ": max_candidates = " + std::to_string(C) + " must lie in [1, " + std::to_string(kWbMaxPool) + "]");
+  if (P < 1 || max_new < 1 || (long long)P + max_new > Tm)
+    return h->fail(US_EINVAL, what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
+                                  " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(Tm));
+  if (o.eos < 0 || o.eos >= o.no_timestamps)
+    return h->fail(US_EINVAL, what + ": eos = " + std::to_string(o.eos) + " must lie in [0, no_timestamps = " + std::to_string(o.no_timestamps) + ")");
+  if ((long long)o.no_timestamps + 1 >= V)
+    return h->fail(US_EINVAL, what + ": no_timestamps + 1 = " + std::to_string((long long)o.no_timestamps + 1) + " >= vocab_size = " + std::to_string(V) +
+                                  ": the vocabulary has no timestamp token");
+  if (o.max_initial_timestamp_index < -1) return h->fail(US_EINVAL, what + ": max_initial_timestamp_index must be -1 (none) or an index");
+  if (o.no_speech < -1 || o.no_speech >= V) return h->fail(US_EINVAL, what + ": no_speech lies outside the vocabulary (-1: none)");
+  if (o.no_speech >= 0 && !no_speech_prob) return h->fail(US_EINVAL, what + ": a no_speech token needs no_speech_prob");
+  if (o.sot_index < 0 || o.sot_index >= P)
+    return h->fail(US_EINVAL, what + ": sot_index = " + std::to_string(o.sot_index) + " lies outside the prompt of " + std::to_string(P));
+  const std::string badtok = wh_bad_token(what, prompt, (size_t)B * P, V);
+  if (!badtok.empty()) return h->fail(US_EINVAL, badtok);
+  if (B > 65535) return h->fail(US_EINVAL, what + ": at most 65535 items");
+  if (!workspace || workspace_bytes < us_whisper_beam_workspace_bytes(h, B, nb))
+    return h->fail(US_EINVAL, what + ": workspace too small (us_whisper_beam_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = wh_begin(h, what, features, B, T, nullptr, true, workspace, workspace_bytes, s);
+  if (rc != US_OK) return rc;
+  const WhPlan p = wh_plan(h, B);
+  const WhBeamPlan bp = wh_beam_plan(h, B, nb);
+  float* base = ws_align(workspace);
+  const WhSelect sel = wh_select_carve(base + p.select);       // the plain partials of the no-speech probability
+  const WhBeamState st = wh_beam_carve(base + bp.state, V, Tm, Tm);
+  const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
+  const int nc = wh_chunks(V), ipg = kWhItems / nb, cache_rows = wh_beam_group_rows(B, nb);
+  const size_t H = (size_t)c.d_model;
+  float* L = base + p.logits;
+  hipError_t e = hipSuccess;
+  for (int b0 = 0; b0 < B && e == hipSuccess; b0 += ipg) {
+    const int items = std::min(ipg, B - b0), M = items * nb;
+    WhStep t{h, s, base + p.x, base + p.q, base + p.att, base + p.ff, base + bp.cache, base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions,
+             B, M, cache_rows, nb, st.anc};
+    long long* tok = reinterpret_cast<long long*>(tokens) + (size_t)b0 * max_new;
+    long long* cnt = reinterpret_cast<long long*>(n) + b0;
+    hipLaunchKernelGGL(wh_beam_init_kernel, dim3(1), dim3(256), 0, s, st, WhBeamHist{}, 0, nb, items, o.eos, Tm, Tm);
+    auto no_speech = [&](int pos) {                     // L holds the logits of position `pos`; the item's first row speaks for it
+      if (o.no_speech < 0 || pos != o.sot_index) return;
+      hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, M), dim3(256), 0, s, L, nullptr, nullptr, sel.st, r, sel.part, V, nc, 1);
+      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(items), dim3(256), 0, s, sel.part, L, no_speech_prob + b0, V, nc, o.no_speech, nb);
+    };
+    WhTokens f;
+    for (int pos = 0; pos + 1 < P; ++pos) {             // every row of an item walks the prompt: its own keys and values, identity ancestry
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < M ? (int)prompt[(size_t)(b0 + m / nb) * P + pos] : 0;
+      wh_embed(t, f, st.cur, pos);
+      wh_layers(t, pos);
+      if (o.no_speech >= 0 && pos == o.sot_index) {
+        wh_logits(t, L, V);
+        no_speech(pos);
+      }
+    }
+    for (int step = 0; step < max_new; ++step) {
+      const int pos = P - 1 + step;
+      for (int m = 0; m < kWhItems; ++m) f.id[m] = step == 0 && m < M ? (int)prompt[(size_t)(b0 + m / nb) * P + pos] : step == 0 ? 0 : -1;
+      t.anc = st.anc + (size_t)(step & 1) * kWhItems * Tm;
+      wh_embed(t, f, st.cur, pos);
+      wh_layers(t, pos);
+      wh_logits(t, L, V);
+      if (step == 0) no_speech(pos);
+      wh_beam_step(L, suppress, begin_suppress, st, r, WhBeamOut{}, V, nb, C, items, step, pos, Tm, Tm, 1, s);
+      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
+        int running = 1;
+        if ((e = hipMemcpyAsync(&running, st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) break;
+        if (running <= 0) break;
+      }
+    }
+    if (e == hipSuccess)
+      hipLaunchKernelGGL(wh_beam_final_kernel, dim3(items), dim3(256), 0, s, st, tok, cnt, sum_logprobs + b0, nb, Tm, max_new, o.eos);
+  }
   if (e == hipSuccess) e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
 }

@@ -4,8 +4,9 @@ with `whisper.load_model`, `pad_or_trim`, `log_mel_spectrogram` and `decode(mode
 `WhisperForConditionalGeneration` takes transformers' configuration fields by keyword and its state_dict; `log_mel_spectrogram` is Whisper's
 feature extraction in torch ops; `WhisperVocabulary` turns ids into text.  `generate` is plain greedy decoding (no timestamp rules: put `<|notimestamps|>` in
 the prompt); `decode` is greedy decoding under the timestamp rules, with `avg_logprob` and `no_speech_prob`: what
-`whisper.decode(model, mel, DecodingOptions())` runs by default (`without_timestamps=False`).  No beam search, no temperature fallback, no
-window beyond 30 s (a longer item is refused), fp32 weights.
+`whisper.decode(model, mel, DecodingOptions())` runs by default (`without_timestamps=False`); with `beam_size` (and `patience`) it is beam
+search under the same rules, `DecodingOptions(beam_size=n, patience=p)`, what the `whisper` command line runs with n = 5.  No temperature
+fallback, no window beyond 30 s (a longer item is refused), fp32 weights.
 """
 from __future__ import annotations
 
@@ -339,12 +340,16 @@ class WhisperForConditionalGeneration(HandleModule):
 
     @torch.no_grad()
     def decode(self, input_features, prompt_ids, *, no_timestamps_id, max_initial_timestamp=1.0, no_speech_id=None, max_new_tokens=None,
-               suppress_tokens=None, begin_suppress_tokens=None, eos_token_id=None, sot_index=0):
+               suppress_tokens=None, begin_suppress_tokens=None, eos_token_id=None, sot_index=0, beam_size=None, patience=None):
         """Greedy decoding under the timestamp rules after the teacher-forced prompt [B, P] (or [P]; no `<|notimestamps|>` in it): what
         `whisper.decode(model, mel, DecodingOptions())` does.  `no_timestamps_id + 1` is the first timestamp token; the first generated token
         is a timestamp of at most `max_initial_timestamp` seconds (None: any); `no_speech_id` asks for `no_speech_prob`, read after the
-        prompt's token `sot_index`; `max_new_tokens` defaults to max_target_positions // 2, openai's sample_len.  -> WhisperDecoding."""
+        prompt's token `sot_index`; `max_new_tokens` defaults to max_target_positions // 2, openai's sample_len.  -> WhisperDecoding.
+        `beam_size` n in [1, 16]: beam search under the same rules (`us_whisper_decode_beam`) with max_candidates = round(n * patience),
+        patience 1.0 by default; `sum_logprob` is the winning sequence's score.  `patience` alone is refused."""
         what = "WhisperForConditionalGeneration.decode"
+        if patience is not None and beam_size is None:
+            raise ValueError(f"{what}: patience belongs to beam search: give beam_size")
         eos = self.eos_token_id if eos_token_id is None else eos_token_id
         if eos is None:
             raise ValueError(f"{what}: no eos_token_id (give it here or in the configuration)")
@@ -367,10 +372,25 @@ class WhisperForConditionalGeneration(HandleModule):
         n = torch.empty(B, dtype=torch.int64, device=x.device)
         lp = torch.empty(B, dtype=torch.float32, device=x.device)
         ns = torch.empty(B, dtype=torch.float32, device=x.device) if no_speech_id is not None else None
+        if beam_size is not None:
+            nb, cand = int(beam_size), int(round(int(beam_size) * (1.0 if patience is None else float(patience))))
+            ws = self._beam_workspace(lib, x.device, B, nb)
+            self._call(lib, x.device, "decode_beam", self._h, x.data_ptr(), B, T, ids, P, C.byref(o), nb, cand,
+                       sup.data_ptr() if sup is not None else None, beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(),
+                       lp.data_ptr(), ns.data_ptr() if ns is not None else None, ws.data_ptr(), ws.numel(), stream)
+            return WhisperDecoding(tokens, n, lp, ns)
         self._call(lib, x.device, "decode", self._h, x.data_ptr(), B, T, ids, P, C.byref(o), sup.data_ptr() if sup is not None else None,
                    beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(), lp.data_ptr(),
                    ns.data_ptr() if ns is not None else None, ws.data_ptr(), ws.numel(), stream)
         return WhisperDecoding(tokens, n, lp, ns)
+
+    def _beam_workspace(self, lib, device, B, beam_size):
+        """the call's scratch grown to us_whisper_beam_workspace_bytes (0 for a beam size the library refuses: the call reports it)"""
+        n = int(lib.us_whisper_beam_workspace_bytes(self._h, B, beam_size))
+        if self._ws.numel() < n:
+            self._ws = None
+            self._ws = torch.empty(n, dtype=torch.uint8, device=device)
+        return self._ws
 
     @torch.no_grad()
     def detect_language(self, input_features, language_ids, start_id=None):
@@ -386,12 +406,17 @@ class WhisperForConditionalGeneration(HandleModule):
         return cand[lg[:, cand].argmax(-1)]
 
     @torch.no_grad()
-    def transcribe_ids(self, wav16, lengths=None, language_id=None, prompt_ids=None, max_new_tokens=None, timestamps=False):
+    def transcribe_ids(self, wav16, lengths=None, language_id=None, prompt_ids=None, max_new_tokens=None, timestamps=False, beam_size=None,
+                       patience=None):
         """16 kHz waveforms [B, T] with per-item lengths -> (tokens [B, L], count [B]): log-mel features, the prompt (`prompt_ids`, default
         `self.prompt_ids`: [start, language, task, notimestamps]; a language of None is `language_id`, or detected per item among
         `self.language_ids`), greedy decoding with the configuration's suppression lists.  An item longer than 30 s is refused.
         timestamps=True: the three-token prompt (the prompt without `self.no_timestamps_id`) and `decode` under the timestamp rules, with
-        `no_speech_prob` when `self.no_speech_id` is set -> WhisperDecoding."""
+        `no_speech_prob` when `self.no_speech_id` is set -> WhisperDecoding; `beam_size` / `patience` go to `decode` and need timestamps=True
+        (beam search is built under the timestamp rules only)."""
+        if (beam_size is not None or patience is not None) and not timestamps:
+            raise ValueError("WhisperForConditionalGeneration.transcribe_ids: beam_size / patience need timestamps=True: beam search is built "
+                             "under the timestamp rules only, not for the prompt with <|notimestamps|>")
         x = torch.as_tensor(wav16)
         if x.dim() == 1:
             x = x[None]
@@ -415,7 +440,8 @@ class WhisperForConditionalGeneration(HandleModule):
                     raise ValueError("WhisperForConditionalGeneration.transcribe_ids: no language_id and no language_ids to detect one among")
                 rows[:, j] = int(language_id) if language_id is not None else self.detect_language(feats, self.language_ids, prompt[0]).cpu()
         if timestamps:
-            return self.decode(feats, rows, no_timestamps_id=int(self.no_timestamps_id), no_speech_id=self.no_speech_id, max_new_tokens=max_new_tokens)
+            return self.decode(feats, rows, no_timestamps_id=int(self.no_timestamps_id), no_speech_id=self.no_speech_id, max_new_tokens=max_new_tokens,
+                               beam_size=beam_size, patience=patience)
         return self.generate(feats, rows, max_new_tokens, self.suppress_tokens, self.begin_suppress_tokens)
 
 
@@ -452,6 +478,42 @@ def select_tokens(logits, history, *, eos_token_id, no_timestamps_id, max_initia
                                    decided.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
     _lib.check(rc, None, "us_whisper_select")
     return token, logprob, decided
+
+
+@torch.no_grad()
+def select_beams(logits, history, scores, beam_size, *, eos_token_id, no_timestamps_id, max_initial_timestamp_index=-1, suppress=None,
+                 begin_suppress=None):
+    """One step of `decode(beam_size=n)`'s selection and bookkeeping on its own (`us_whisper_beam_select`): logits [B * n, V] fp32 on the device,
+    rows item-major; history: per row (n_sampled, last, penultimate, last_timestamp, dead); scores: per row, floats -> dict on the device:
+    parent [B, n] int32 (-1: dead), token [B, n] int64, score [B, n] fp64, n_live [B], fin_parent [B, n] int32 and fin_score [B, n] fp64 (the
+    newly finished entries in walk order), n_fin [B]."""
+    if logits.device.type != "cuda" or logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"select_beams: expected fp32 logits [B * n, V] on a ROCm device, got {logits.dtype} {tuple(logits.shape)} on {logits.device}")
+    lib = _lib.load()
+    x = logits.contiguous()
+    n, R, V = int(beam_size), int(x.shape[0]), int(x.shape[1])
+    if n < 1 or R % n or len(history) != R or len(scores) != R:
+        raise ValueError(f"select_beams: {R} rows of logits, {len(history)} histories and {len(scores)} scores do not make items of {n} rows")
+    B = R // n
+    for m in (suppress, begin_suppress):
+        if m is not None and (m.dtype != torch.uint8 or m.numel() != V or m.device != x.device):
+            raise ValueError("select_beams: a mask must be uint8 [V] on the logits' device")
+    hist = (_lib.us_whisper_history * R)(*[_lib.us_whisper_history(*[int(v) for v in h]) for h in history])
+    sc = (C.c_double * R)(*[float(v) for v in scores])
+    o = _lib.us_whisper_decode_options(int(eos_token_id), int(no_timestamps_id), int(max_initial_timestamp_index), -1, 0, 1)
+    nbytes = int(lib.us_whisper_beam_select_scratch_bytes(V, n))
+    ws = _select_scratch.get(x.device)
+    if ws is None or ws.numel() < nbytes:
+        _select_scratch[x.device] = ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=x.device)
+    out = dict(parent=new(torch.int32, B, n), token=new(torch.int64, B, n), score=new(torch.float64, B, n), n_live=new(torch.int32, B),
+               fin_parent=new(torch.int32, B, n), fin_score=new(torch.float64, B, n), n_fin=new(torch.int32, B))
+    with torch.cuda.device(x.device):
+        rc = lib.us_whisper_beam_select(x.data_ptr(), B, V, n, hist, sc, C.byref(o), suppress.data_ptr() if suppress is not None else None,
+                                        begin_suppress.data_ptr() if begin_suppress is not None else None, *[t.data_ptr() for t in out.values()],
+                                        ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    _lib.check(rc, None, "us_whisper_beam_select")
+    return out
 
 
 def detect_language(model, input_features, language_ids, start_id=None):
