@@ -1,6 +1,6 @@
 """Whisper's beam search under the timestamp rules as tools/whisper_beam_numpy.py states it (the yardstick of us_whisper_decode_beam), over toy
 logits; the walk / pool / ranking functions of csrc/whisper_beam.h, built into tools/whisper_beam_check.cpp under AddressSanitizer and UBSan,
-against that statement; and the goldens tests/golden/whisper_beam_{a,b}.npz against `WhisperTorch(float64).decode_beam`."""
+against that statement; and the goldens tests/golden/whisper_beam_{a,b,wide}.npz against `WhisperTorch(float64).decode_beam`."""
 import json
 import os
 import shutil
@@ -214,7 +214,7 @@ def test_the_header_under_sanitizers_agrees_with_numpy(tmp_path):
 # ---- the goldens ----------------------------------------------------------------------------------------------------------------------
 
 
-@pytest.mark.parametrize("name", ["a", "b"])
+@pytest.mark.parametrize("name", ["a", "b", "wide"])
 def test_goldens_are_what_the_fp64_restatement_decodes(name):
     with np.load(os.path.join(ROOT, "tests", "golden", f"whisper_{name}.npz")) as g:
         c, sd, feats, prompts = json.loads(str(g["config"])), golden_state_dict(g), g["features"], torch.from_numpy(g["prompt"])

@@ -1,5 +1,5 @@
 """Decoding under the timestamp rules without a GPU: the fp64 numpy statement of one selection step (tools/whisper_decode_numpy.py) against
-transformers' three processor classes, the torch restatement's `decode` against the goldens (tests/golden/whisper_decode_{a,b}.npz),
+transformers' three processor classes, the torch restatement's `decode` against the goldens (tests/golden/whisper_decode_{a,b,long,wide}.npz),
 `WhisperVocabulary.segments`, and the refusals that need no device."""
 import json
 import os
@@ -114,18 +114,24 @@ def golden(name):
     return _CACHE[name]
 
 
-@pytest.mark.parametrize("name", ["a", "b"])
+NAMES = ["a", "b", "long", "wide"]
+
+
+@pytest.mark.parametrize("name", NAMES)
 def test_goldens_keep_their_conditions(name):
     x, prompt, c, sd, d, lay = golden(name)
     free = np.isfinite(d["d"])
     assert float(np.abs(d["d"][free]).min()) >= 1e-2 and float(d["min_gap"]) >= 1e-3
     assert int((free & (d["decided"] == 1)).sum()) >= 5 and int((free & (d["decided"] == 0)).sum()) >= 5
     stops = [int(v) for v in d["lengths"] if v < int(d["max_new"])]
-    assert len(set(stops)) >= 2 and len(stops) < len(d["lengths"])
+    if name == "long":                                # two items: they end differently and one runs past step 70
+        assert int(d["max_new"]) == 132 and len(set(d["lengths"].tolist())) == 2 and int(d["lengths"].max()) > 70
+    else:
+        assert len(set(stops)) >= 2 and len(stops) < len(d["lengths"])
     assert os.path.getsize(os.path.join(ROOT, "tests", "golden", f"whisper_decode_{name}.npz")) < 16384
 
 
-@pytest.mark.parametrize("name", ["a", "b"])
+@pytest.mark.parametrize("name", NAMES)
 def test_torch_decode_reproduces_the_golden(name):
     x, prompt, c, sd, d, lay = golden(name)
     trace = []
@@ -135,7 +141,7 @@ def test_torch_decode_reproduces_the_golden(name):
     assert float(np.abs(r["no_speech_prob"] - d["no_speech_prob"]).max()) <= 1e-9
     assert float(np.abs(r["logprobs"] - d["logprobs"]).max()) <= 1e-9
     # the loop over the recorded logits (numpy alone) gives the same
-    for b in range(3):
+    for b in range(len(x)):
         n = rules.decode(np.stack([t[b].numpy() for t in trace]), lay)
         k = int(d["lengths"][b])
         assert n["length"] == min(k, len(trace)) and np.array_equal(n["tokens"][:k], d["tokens"][b, :k])

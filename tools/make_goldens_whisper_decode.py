@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/whisper_decode_{a,b}.npz: greedy decoding under the timestamp rules of the two tiny models of
-tests/golden/whisper_{a,b}.npz (their weights, features and prompts; nothing of those is stored again), from the installed
+"""Writes tests/golden/whisper_decode_{a,b,long,wide}.npz: greedy decoding under the timestamp rules of the tiny models of
+tests/golden/whisper_{a,b,long,wide}.npz (their weights, features and prompts; nothing of those is stored again), from the installed
 `transformers.WhisperForConditionalGeneration` in fp64 on the CPU (the whole prefix again at every step, no cache) and transformers'
 SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor and WhisperTimeStampLogitsProcessor, then argmax and log_softmax.
 
-    python tools/make_goldens_whisper_decode.py
+    python tools/make_goldens_whisper_decode.py [name ...]          # no name: all of them
 
 The token layout (eos, no_timestamps, the cap of the first timestamp, the suppressed ids) is searched, LAYOUTS first, and a file is written
 only when all of these hold:
@@ -13,11 +13,13 @@ only when all of these hold:
  3. both outcomes of a free decision occur at least 5 times each;
  4. some item returns to a timestamp after text by a free decision;
  5. two items have different timestamp patterns;
- 6. two items stop at different steps and one never stops.
+ 6. two items stop at different steps and one never stops (`long`, which has two items: their lengths differ and one of them runs past
+    step 70, so that the rules are applied over a cache of more than 64 positions).
+A layout is given up at the first step that misses condition 1 or 2.
 Every step is also computed by tools/whisper_decode_numpy.py and must give transformers' token and log-probability (1e-12).
 
 Each file holds `layout` (json: eos, no_timestamps, max_initial_timestamp_index, no_speech, suppress, begin_suppress), `sot_index`, `max_new`,
-`tokens` [3][max_new] (eos at and after an item's end), `lengths` [3], `logprobs` [3][max_new] fp64 (0 after the end), `sum_logprob` [3],
+`tokens` [items][max_new] (eos at and after an item's end), `lengths` [3], `logprobs` [3][max_new] fp64 (0 after the end), `sum_logprob` [3],
 `no_speech_prob` [3], `d` [3][max_new] (nan where the decision is not free), `decided` [3][max_new] (1: the timestamps won), `gap`
 [3][max_new], `min_abs_d`, `min_gap` (relative) and `max_logit`.
 """
@@ -34,7 +36,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import whisper_decode_numpy as rules  # noqa: E402
 from whisper_torch import golden_state_dict  # noqa: E402
 
-LAYOUTS = {"a": dict(no_timestamps=87, eos=35, max_initial_timestamp_index=2), "b": dict(no_timestamps=190, eos=178, max_initial_timestamp_index=2)}
+LAYOUTS = {"a": dict(no_timestamps=87, eos=35, max_initial_timestamp_index=2), "b": dict(no_timestamps=190, eos=178, max_initial_timestamp_index=2),
+           "long": dict(no_timestamps=60, eos=40, max_initial_timestamp_index=2),
+           "wide": dict(no_timestamps=520, eos=252, max_initial_timestamp_index=2, also_suppress=(526, 529))}
+LONG_PAST = 70
 
 
 def load(name):
@@ -49,11 +54,15 @@ def load(name):
     sd = dict(sd)
     sd["proj_out.weight"] = sd["model.decoder.embed_tokens.weight"]
     model.load_state_dict(sd)
-    return c, model.double(), x, prompt
+    model = model.double()
+    with torch.no_grad():                 # the encoder once per item, not once per step: the same numbers
+        enc = [model.model.encoder(x[b:b + 1]).last_hidden_state for b in range(x.shape[0])]
+    return c, model, enc, prompt
 
 
-def run(model, c, x, prompt, layout):
+def run(model, c, enc, prompt, layout, name=None):
     """-> (the file's arrays, None) or (None, why not)"""
+    from transformers.modeling_outputs import BaseModelOutput
     from transformers.generation.logits_process import (SuppressTokensAtBeginLogitsProcessor, SuppressTokensLogitsProcessor,
                                                         WhisperTimeStampLogitsProcessor)
     V, P = c["vocab_size"], prompt.shape[1]
@@ -64,7 +73,7 @@ def run(model, c, x, prompt, layout):
     procs = [SuppressTokensLogitsProcessor(layout["suppress"]), SuppressTokensAtBeginLogitsProcessor(layout["begin_suppress"], P),
              WhisperTimeStampLogitsProcessor(gen, begin_index=P)]
     sup, beg = rules.masks(layout, V)
-    B = x.shape[0]
+    B = len(enc)
     tokens, lps = np.full((B, max_new), eos, dtype=np.int64), np.zeros((B, max_new))
     d, decided, gap = np.full((B, max_new), np.nan), np.zeros((B, max_new), dtype=np.int8), np.full((B, max_new), np.inf)
     lengths, nsp, big = np.full(B, max_new, dtype=np.int64), np.zeros(B), 0.0
@@ -72,7 +81,7 @@ def run(model, c, x, prompt, layout):
         for b in range(B):
             seq = prompt[b:b + 1].clone()
             for i in range(max_new):
-                lg = model(input_features=x[b:b + 1], decoder_input_ids=seq, use_cache=False).logits[0]
+                lg = model(encoder_outputs=BaseModelOutput(last_hidden_state=enc[b]), decoder_input_ids=seq, use_cache=False).logits[0]
                 if i == 0:
                     nsp[b] = float(torch.softmax(lg[0], -1)[layout["no_speech"]])
                 row = lg[-1]
@@ -85,6 +94,8 @@ def run(model, c, x, prompt, layout):
                 r = rules.select(row.numpy(), seq[0, P:].tolist(), layout, sup, beg)
                 assert r["token"] == tok and abs(r["logprob"] - lp) <= 1e-12, (b, i, r, tok, lp)
                 tokens[b, i], lps[b, i], d[b, i], decided[b, i], gap[b, i] = tok, lp, r["d"], r["decided"], r["gap"]
+                if (r["free"] and abs(r["d"]) < 1e-2) or r["gap"] < 1e-3 * big:          # conditions 1 and 2: `big` only grows
+                    return None, f"item {b} step {i}: |d| {abs(r['d']):.1e}, gap {r['gap'] / big:.1e}"
                 seq = torch.cat([seq, torch.tensor([[tok]])], dim=1)
                 if tok == eos:
                     lengths[b] = i
@@ -105,7 +116,7 @@ def run(model, c, x, prompt, layout):
     if len(patterns) < 2:
         return None, "one timestamp pattern"
     stops = sorted(int(v) for v in lengths if v < max_new)
-    if len(set(stops)) < 2 or len(stops) == B:
+    if (len(set(lengths.tolist())) < 2 or int(lengths.max()) <= LONG_PAST) if name == "long" else (len(set(stops)) < 2 or len(stops) == B):
         return None, f"stops {lengths.tolist()}"
     out = dict(layout=json.dumps(layout), sot_index=np.int64(0), max_new=np.int64(max_new), tokens=tokens, lengths=lengths, logprobs=lps,
                sum_logprob=lps.sum(1), no_speech_prob=nsp, d=d, decided=decided, gap=gap, min_abs_d=np.float64(np.abs(d[free]).min()),
@@ -119,6 +130,9 @@ def candidates(name, V):
     then another cap or another no_timestamps (5 to 15 timestamp tokens)"""
     first = LAYOUTS[name]
     seen = set()
+    if name in SPREAD:
+        yield from spread(first, V)
+        return
     for nt in [first["no_timestamps"]] + list(range(V - 7, V - 17, -1)):
         for cap in (first["max_initial_timestamp_index"], -1):
             for extra in [None] + list(range(3, nt - 1)):
@@ -132,11 +146,34 @@ def candidates(name, V):
                                suppress=[eos + 1, nt - 1] + ([extra] if extra is not None else []), begin_suppress=[7, eos])
 
 
+SPREAD = ("long", "wide")
+
+
+def spread(first, V):
+    """The search of the models with more steps or more tokens than a and b: a run of many steps uses up a handful of timestamp tokens long
+    before it ends (they only grow), and the timestamps then never win again.  So the number of timestamp tokens is searched in front of
+    everything else, from the first layout's down to a third of the vocabulary; then eos, then one more suppressed text token.
+    whisper_wide's two largest timestamp logits are those of two of its last tokens, 526 and 529, at every step: chosen at the first free
+    decisions, they leave no timestamp for the rest of the run, whatever the other fields are.  Its first layout suppresses them
+    (`also_suppress`), as a real vocabulary's list suppresses single tokens."""
+    for extra in [tuple(first.get("also_suppress", ()))] + [(t,) for t in range(3, 12)]:
+        for eos in [first["eos"]] + list(range(3, V // 3)):
+            for cap in (first["max_initial_timestamp_index"], -1):
+                for nt in [first["no_timestamps"]] + list(range(V - 7, V // 3, -max(1, V // 50))):
+                    if eos in extra or eos >= nt - 2:
+                        continue
+                    yield dict(eos=eos, no_timestamps=nt, max_initial_timestamp_index=cap, no_speech=nt - 1,
+                               suppress=[eos + 1, nt - 1] + list(extra), begin_suppress=[7, eos])
+
+
 def main():
-    for name in ("a", "b"):
-        c, model, x, prompt = load(name)
+    names = sys.argv[1:] or list(LAYOUTS)
+    if set(names) - set(LAYOUTS):
+        raise SystemExit(f"unknown model among {names}: the tool knows {list(LAYOUTS)}")
+    for name in names:
+        c, model, enc, prompt = load(name)
         for layout in candidates(name, c["vocab_size"]):
-            out, msg = run(model, c, x, prompt, layout)
+            out, msg = run(model, c, enc, prompt, layout, name)
             print(name, {k: layout[k] for k in ("no_timestamps", "eos", "max_initial_timestamp_index", "suppress")}, msg, flush=True)
             if out is not None:
                 break
