@@ -405,8 +405,15 @@ int us_duration_predictor_mse_loss(const float* logw, const float* w, const floa
  * Output masking follows the library's producer-side convention (attention / Downsample / Upsample outputs are stored
  * masked): pass an all-ones mask to obtain the reference module's raw output.
  * US_DEBUG_TEMB (prefix ignored): x = t [B], out [B][2 * dim] = SinusoidalPosEmb(t) | mlp(SinusoidalPosEmb(t))
- * (unitspeech/unitspeech.py:109-121, 133-134, 165-166). */
-enum { US_DEBUG_BLOCK = 0, US_DEBUG_RESNET = 1, US_DEBUG_ATTENTION = 2, US_DEBUG_DOWN = 3, US_DEBUG_UP = 4, US_DEBUG_TEMB = 5 };
+ * (unitspeech/unitspeech.py:109-121, 133-134, 165-166).
+ * US_DEBUG_FIRST (prefix and level ignored): the first ResnetBlock, "estimator.downs.0.0", by the walk's own helper: x = mu [B][F][T]
+ * followed by the noisy input [B][F][T] (both are multiplied by the mask here, as the walk stacks them), temb as above;
+ * out [B][F][T][dim], stored masked.
+ * US_DEBUG_FINAL (prefix ignored): the final Block and the 1x1 projection (unitspeech/unitspeech.py:198-201): x [B][F][T][dim] already
+ * masked, out [B][F][T] (masked).  level selects where the Block's activation lives: 0 = not kept, GroupNorm + Mish run inside the
+ * projection (every inference evaluation); 1 = kept, the projection in its plain form (what a training forward runs). */
+enum { US_DEBUG_BLOCK = 0, US_DEBUG_RESNET = 1, US_DEBUG_ATTENTION = 2, US_DEBUG_DOWN = 3, US_DEBUG_UP = 4, US_DEBUG_TEMB = 5,
+       US_DEBUG_FIRST = 6, US_DEBUG_FINAL = 7 };
 int us_debug_block(us_handle h, int kind, const char* prefix, int level, const float* x, const float* mask,
                    const float* temb, float* out, int B, int T, void* workspace, size_t workspace_bytes, us_stream stream);
 

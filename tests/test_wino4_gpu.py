@@ -6,6 +6,7 @@ frames, the GroupNorm-fused input transform), every level combination against th
 mode of the weight store (the inference-only pack is skipped while training and refreshed by the first inference call afterwards)."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +14,9 @@ import torch
 
 from oracle import decoder_oracle as O
 from unitspeech_amd import DecoderConfig, UnitSpeech, _lib, synthetic_inputs, synthetic_state_dict
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import wino_torch as WT      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -29,9 +33,29 @@ def l1(a, b):
     return float((a.double().cpu() - b.double().cpu()).abs().mean())
 
 
+def elementwise(tag, got, r64, r32):
+    """The element-wise bar of tests/test_decoder_blocks_gpu.py beside the L1 one: max |library - fp64| <= max(10 x max |fp32 reference - fp64|,
+    1e-5 x max |fp64|); prints err, floor, bar and the worst element's place."""
+    d = (got.double().cpu() - r64).abs()
+    err, floor, top = float(d.max()), float((r32.double() - r64).abs().max()), float(r64.abs().max())
+    bar = max(10 * floor, 1e-5 * top)
+    at = tuple(int(v) for v in torch.unravel_index(d.argmax(), d.shape))
+    print(f"{tag}: max |library - fp64| {err:.3e}, floor {floor:.3e}, bar {bar:.3e}, worst element at {at}")
+    assert err <= bar, tag
+
+
 @pytest.fixture(scope="module")
 def sd_np():
     return synthetic_state_dict(FULL, 0)
+
+
+@pytest.fixture(scope="module")
+def sd64(sd_np):
+    return O.to_torch(sd_np, torch.float64)
+
+
+def estimator_fp64(sd64, inp, t):
+    return O.estimator_forward(sd64, inp["z"].double(), inp["mask"].double(), inp["cond"].double(), t.double(), inp["spk_emb"].double())
 
 
 def build(sd_np, monkeypatch, forms):
@@ -71,7 +95,7 @@ CASES = [
 
 
 @pytest.mark.parametrize("forms,level,prefix,cin,cout,T", CASES)
-def test_resnet_block_with_the_4_wide_winograd_forms_vs_oracle(sd_np, monkeypatch, forms, level, prefix, cin, cout, T):
+def test_resnet_block_with_the_4_wide_winograd_forms_vs_oracle(sd_np, sd64, monkeypatch, forms, level, prefix, cin, cout, T):
     """One whole `ResnetBlock` (:58-75) through us_debug_block: block1's 3x3 takes the plain input transform, block2's the one with
     block1's GroupNorm + Mish + time embedding evaluated on the fly; two items, one with padded frames; against the oracle module."""
     model = build(sd_np, monkeypatch, forms)
@@ -88,11 +112,20 @@ def test_resnet_block_with_the_4_wide_winograd_forms_vs_oracle(sd_np, monkeypatc
     e = l1(got, ref) / float(ref.abs().mean())
     print(f"\n{forms} level {level} {cin}->{cout} {H}x{W}: relative L1 vs the oracle ResnetBlock {e:.2e}")
     assert torch.isfinite(got).all() and e <= 2e-6
+    # element by element, against the fp64 oracle; the fp32 floor is the restatement of the forms the two convolutions run in
+    f4 = int(forms.split(",")[level])
+    f1, f2 = (f4 if cin >= 256 else 22), f4
+    ref64 = O.resnet_block(sd64, prefix, x.double(), mask.double(), temb.double())
+    elementwise(f"{forms} level {level} ResnetBlock, forms {f1} / {f2}", got, ref64,
+                WT.resnet_block_wino(sd, prefix, x, mask, temb, f1, f2, torch.float32, 22))
     # and the block on its own (Block :46-55, the plain input transform; an all-ones mask shows the padded columns too)
     ones = torch.ones(B, 1, T)
     got_b = debug_block(model, 0, prefix, level, x, ones, None, cout)
     ref_b = O.block(sd, f"{prefix}.block1", x, torch.ones(B, 1, 1, W))
     assert l1(got_b, ref_b) / float(ref_b.abs().mean()) <= 2e-6
+    ones4 = torch.ones(B, 1, 1, W)
+    elementwise(f"{forms} level {level} Block, form {f1}", got_b, O.block(sd64, f"{prefix}.block1", x.double(), ones4.double()),
+                WT.block_wino(sd, f"{prefix}.block1", x, ones4, f1, torch.float32, 22))
 
 
 @pytest.mark.parametrize("forms", ["0,44,44,24", "0,44,44,44", "0,24,24,24", "0,0,0,0"])
@@ -115,7 +148,7 @@ def test_evaluation_and_50_step_loop_vs_reference_goldens(sd_np, monkeypatch, fo
 
 
 @pytest.mark.parametrize("T", [8, 40])
-def test_short_utterances_vs_oracle(sd_np, monkeypatch, T):
+def test_short_utterances_vs_oracle(sd_np, sd64, monkeypatch, T):
     """T = 8: one column at level 3, two at level 2, four at level 1 -- a single, mostly empty tile column at every level of the 4-wide forms;
     T = 40: 5 / 10 / 20 columns (partial last tiles at levels 3 and 2).  Full-size weights, a padded item, against the oracle."""
     model = build(sd_np, monkeypatch, "0,44,44,24")
@@ -128,9 +161,10 @@ def test_short_utterances_vs_oracle(sd_np, monkeypatch, T):
     e = l1(out, ref)
     print(f"\nT={T} evaluation: L1 vs oracle {e:.2e} (mean |ref| {ref.abs().mean():.3f})")
     assert torch.isfinite(out).all() and e <= 2e-6
+    elementwise(f"T={T} evaluation", out, estimator_fp64(sd64, inp, t), ref)
 
 
-def test_ragged_evaluation_and_batch_independence(sd_np, monkeypatch):
+def test_ragged_evaluation_and_batch_independence(sd_np, sd64, monkeypatch):
     """T = 136 (17 / 34 / 68 columns at levels 3 / 2 / 1: partial tile columns everywhere) with a padded and a fully padded item, against the
     oracle; and an item's result must not depend on what it is batched with, bit for bit (the tile of a Winograd-domain GEMM follows the
     launch geometry, the order in which an output element is summed does not)."""
@@ -146,6 +180,7 @@ def test_ragged_evaluation_and_batch_independence(sd_np, monkeypatch):
     e = l1(out, ref)
     print(f"\nragged T=136 evaluation: L1 vs oracle {e:.2e} (mean |ref| {ref.abs().mean():.3f})")
     assert e <= 2e-6 and torch.equal(out[1:2], one)
+    elementwise("ragged T=136 evaluation", out, estimator_fp64(sd64, inp, t), ref)
 
 
 def test_training_mode_skips_the_inference_only_pack_and_inference_refreshes_it(sd_np, monkeypatch):

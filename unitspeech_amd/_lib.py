@@ -14,6 +14,8 @@ US_OK = 0
 US_CREATE_EXACT_FP32 = 1
 US_RANGE_ACT, US_RANGE_WEIGHT = 1, 2
 US_BACKWARD_GRADS_ZEROED, US_BACKWARD_KEEP_TAPE = 1, 2
+(US_DEBUG_BLOCK, US_DEBUG_RESNET, US_DEBUG_ATTENTION, US_DEBUG_DOWN, US_DEBUG_UP, US_DEBUG_TEMB, US_DEBUG_FIRST,
+ US_DEBUG_FINAL) = range(8)          # us_debug_block's kinds
 US_ENCODER_CONV_FWD, US_ENCODER_CONV_WGRAD, US_ENCODER_CONV_DGRAD = 0, 1, 2
 US_ENCODER_CONV_MASK_IN, US_ENCODER_CONV_RELU, US_ENCODER_CONV_MASK_OUT = 1, 2, 4
 ERRORS = {-1: "EINVAL", -2: "ENOKEY", -3: "ESHAPE", -4: "EWEIGHTS", -5: "EWORKSPACE", -6: "EHIP"}

@@ -1049,6 +1049,20 @@ hipError_t time_embedding(EvalCtx& e, const float* t, const float* spk) {
   });
 }
 
+// final Block + 1x1 projection (unitspeech/unitspeech.py:198-201); fin: [Bp][F][T][fin_ld], fin_split: in the two-plane fp16 form
+hipError_t final_block(EvalCtx& e, Places& p, const float* fin, int fin_ld, bool fin_split, float* out) {
+  us_decoder* h = e.h;
+  const int F = h->cfg.n_feats, T = e.T, c0 = h->C[0];
+  p.fin_x = fin; p.fin_ld = fin_ld;
+  CK(conv3x3(e, h->final_conv3, fin, fin_ld, 0, p.fin_y, c0, p.fin_st, fin_split));
+  // fin_h not kept: GroupNorm + Mish + mask inside the 1x1 projection, the normalised tensor is never stored
+  if (!p.fin_h)
+    return launch_final_conv(p.fin_y, c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s, p.fin_st,
+                             h->final_g->buf.p, h->final_b->buf.p);
+  CK(gn_apply(e, p.fin_y, 0, c0, p.fin_st, h->final_g, h->final_b, nullptr, nullptr, 0, false, false, p.fin_h, c0));
+  return launch_final_conv(p.fin_h, c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s);
+}
+
 // The U-Net of `GradLogPEstimator2d.forward` (unitspeech.py:170-201) over a placement table: every launch of an inference evaluation
 // and of a training forward between the time embedding and the result.
 // x: [Bx][F][T]; mu: [Bmu][F][T]; items b' < n_text_uncond use text_uncon instead of mu; out: [Bp][F][T]
@@ -1118,16 +1132,7 @@ hipError_t unet_forward(EvalCtx& e, Places& p, const float* x, int Bx, const flo
     CK(conv_up(e, *c.w, at.out, at.out_ld, l, c.out, c.out_ld, up_split[l], (l - 1 >= 1) ? hid_split[l - 1] != 0 : fin_split));
     fin = c.out; fin_ld = c.out_ld;
   }
-  // final Block + 1x1 projection (unitspeech/unitspeech.py:198-201)
-  const int c0 = h->C[0];
-  p.fin_x = fin; p.fin_ld = fin_ld;
-  CK(conv3x3(e, h->final_conv3, fin, fin_ld, 0, p.fin_y, c0, p.fin_st, fin_split));
-  // fin_h not kept: GroupNorm + Mish + mask inside the 1x1 projection, the normalised tensor is never stored
-  if (!p.fin_h)
-    return launch_final_conv(p.fin_y, c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s, p.fin_st,
-                             h->final_g->buf.p, h->final_b->buf.p);
-  CK(gn_apply(e, p.fin_y, 0, c0, p.fin_st, h->final_g, h->final_b, nullptr, nullptr, 0, false, false, p.fin_h, c0));
-  return launch_final_conv(p.fin_h, c0, h->final_w1->buf.p, h->final_b1->buf.p, e.mask, T, e.Bm, out, e.Bp, F, T, c0, e.s);
+  return final_block(e, p, fin, fin_ld, fin_split, out);
 }
 
 // One inference evaluation.  t: [Bp], spk: [Bp][S] (unused when the sampler has the time projections ready).
@@ -1912,6 +1917,26 @@ int us_debug_block(us_handle h, int kind, const char* prefix, int level, const f
         return US_OK;
       }
     return h->fail(US_ENOKEY, "no Upsample '%s'", prefix);
+  }
+  if (kind == US_DEBUG_FIRST) {
+    // x = mu [B][F][T] | x [B][F][T]; the stacked, masked input and the first ResnetBlock by the walk's own resnet_first()
+    if (!temb) return h->fail(US_EINVAL, "ResnetBlock needs temb");
+    const ResnetW& r = h->downs[0].r1;
+    ResT& t = pl.res[r.index];
+    const size_t item = (size_t)h->cfg.n_feats * T;
+    const int td = h->cfg.dim + h->cfg.spk_emb_dim;
+    US_HIP(h, launch_stack_inputs(x + (size_t)B * item, B, x, B, 0, h->text_uncon->buf.p, mask, B, b.in2, B, h->cfg.n_feats, T, s));
+    US_HIP(h, launch_linear(temb, td, r.mlp_w->buf.p, r.mlp_b->buf.p, b.tproj + b.tproj_off[r.index], r.cout, B, td, r.cout, true, s));
+    t.out = out; t.out_ld = r.cout;
+    US_HIP(h, resnet_first(e, t, nullptr));
+    return US_OK;
+  }
+  if (kind == US_DEBUG_FINAL) {
+    // level 1: the activation is kept, as a training plan places it (in the level's spare scratch here), so the projection runs in its plain form
+    if (level == 1) pl.fin_h = b.S2[0];
+    else if (level != 0) return h->fail(US_EINVAL, "final Block: level selects the form, 0 or 1");
+    US_HIP(h, final_block(e, pl, x, h->C[0], false, out));
+    return US_OK;
   }
   return h->fail(US_EINVAL, "unknown block kind %d", kind);
 }
