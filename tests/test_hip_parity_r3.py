@@ -10,6 +10,7 @@
 """
 import ctypes as C
 import os
+import sys
 import warnings
 
 import numpy as np
@@ -19,6 +20,9 @@ import torch
 from oracle import decoder_oracle as O
 from unitspeech_amd import DecoderConfig, UnitSpeech, _lib, synthetic_inputs, synthetic_state_dict
 from unitspeech_amd.unitspeech import RangeError
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+from grad_parity import ReplayRandn as _ReplayRandn, crops as _crops      # noqa: E402  (moved there unchanged; shared with test_decoder_grads*.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -265,39 +269,6 @@ def test_finetune_graph_reports_a_range_event_one_step_late(sd_np, backward):
 # ---------------------------------------------------------------------------------------------------------------
 # loss scaling inside us_estimator_backward
 # ---------------------------------------------------------------------------------------------------------------
-def _crops(B, T, key):
-    g = np.random.Generator(np.random.Philox(key=key))
-    x0 = torch.from_numpy(g.standard_normal((B, FULL.n_feats, T), dtype=np.float32)).clamp(-1, 1)
-    cond = torch.from_numpy(g.standard_normal((B, FULL.n_feats, T), dtype=np.float32) * 0.5)
-    lengths = [T - 8 * (b % 3) for b in range(B)]
-    mask = torch.zeros(B, 1, T)
-    for b, n in enumerate(lengths):
-        mask[b, 0, :n] = 1.0
-    spk = torch.from_numpy(g.standard_normal((B, 1, FULL.spk_emb_dim), dtype=np.float32))
-    spk = spk / spk.norm(dim=-1, keepdim=True)
-    t = torch.from_numpy(g.uniform(0.05, 0.95, size=(B,)).astype(np.float32))
-    z = torch.from_numpy(g.standard_normal((B, FULL.n_feats, T), dtype=np.float32))
-    return x0, mask, cond, spk, t, z
-
-
-class _ReplayRandn:
-    def __init__(self, draws):
-        self.draws, self.i = list(draws), 0
-
-    def __enter__(self):
-        self.orig = torch.randn
-        torch.randn = self
-        return self
-
-    def __exit__(self, *a):
-        torch.randn = self.orig
-
-    def __call__(self, *shape, **kw):
-        d = self.draws[self.i]
-        self.i += 1
-        return d.to(device=kw.get("device", d.device), dtype=kw.get("dtype", d.dtype))
-
-
 def _hip_grads(sd_np, x0, mask, cond, spk, t, z, exact=False, loss_factor=1.0, cfg=FULL):
     m = build(sd_np, exact=exact, train=True, cfg=cfg)
     with _ReplayRandn([z.to(DEV)]):
