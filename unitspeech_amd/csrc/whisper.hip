@@ -26,20 +26,24 @@
 //    (us_whisper_decode_beam, us_whisper_beam_select).  An item's n rows ride in one launch group; the cross keys / values stay per item
 //    (wh_cross_attn_kernel reads item m / rpi), the self cache stays where each row wrote it and wh_self_attn_kernel<true> finds every
 //    position's key through a per-row ancestry table.  See the section in front of the kernels.
-// No kernel waits on a value another kernel writes; the host loop runs at most max_new steps and reads the running count back every
-// kWhPoll steps.  Every reduction has a fixed order and no launch depends on the batch: an item alone or in a batch, and repeated calls, give
-// the same bits.
+// The host side of us_whisper_generate, us_whisper_decode and us_whisper_decode_beam is one function, wh_walk: per launch group it starts the
+// state, teacher-forces the prompt but for its last token, then runs at most max_new steps of embed, layers, logits and selection and reads
+// the running count back every kWhPoll steps.  A WhPolicy names the five places where the three differ: the rows per item (and with them
+// whose self cache a row writes), the state that holds cur / running, the launches that start the state and that select, the ancestry table
+// of the step's parity, and the launch behind the last step.  us_whisper_decoder_logits runs the same position step (wh_position) with
+// logits at every position.  No kernel waits on a value another kernel writes.  Every reduction has a fixed order and no launch depends on
+// the batch: an item alone or in a batch, and repeated calls, give the same bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/unitspeech_hip.h"
 #include "handle.h"
-#include "item_lens.h"
 #include "kernels.h"
 #include "whisper_beam.h"
 #include "whisper_encoder.h"
@@ -247,27 +251,15 @@ __global__ __launch_bounds__(64 * kWhCrossWaves) void wh_cross_attn_kernel(const
   }
 }
 
-struct WhGenState {             // a group's loop state in the workspace
-  int* cur;                     // [kWhItems] the token argmax chose last
-  int* done;                    // [kWhItems]
-  int* running;                 // items of the group that have not ended
+struct WhDecState {                 // a group's loop state in the workspace, one row per item
+  int *cur, *done, *running;        // [kWhItems] the token chosen last, the item has ended; the items of the group that have not
+  int *count, *last, *pen, *last_ts;        // [kWhItems] tokens sampled so far, the last two of them, the last timestamp (-1: none)
+  double* sum;                      // [kWhItems] the sum of the log-probabilities
 };
-
-__global__ __launch_bounds__(256) void wh_init_kernel(WhGenState st, long long* __restrict__ tokens, long long* __restrict__ n, int nb, int max_new,
-                                                      long long eos) {
-  const int tid = threadIdx.x;
-  if (tid < kWhItems) {
-    st.cur[tid] = 0;
-    st.done[tid] = 0;
-  }
-  if (tid < nb) n[tid] = 0;
-  if (tid == 0) *st.running = nb;
-  for (int i = tid; i < nb * max_new; i += 256) tokens[i] = eos;
-}
 
 // item m of the group: the largest logit that no mask suppresses, the lower index on a tie; tokens[m][step] and the item's end
 __global__ __launch_bounds__(256) void wh_argmax_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ suppress,
-                                                        const unsigned char* __restrict__ begin, WhGenState st, long long* __restrict__ tokens,
+                                                        const unsigned char* __restrict__ begin, WhDecState st, long long* __restrict__ tokens,
                                                         long long* __restrict__ n, int V, int max_new, int step, int eos) {
   __shared__ float rv[4];
   __shared__ int ri[4];
@@ -321,12 +313,7 @@ struct WhPart {                     // one side of one chunk: the largest surviv
   float m, s;
   int bi, pad;
 };
-struct WhDecState {                 // a group's loop state in the workspace; cur / done / running as WhGenState
-  int *cur, *done, *running;
-  int *count, *last, *pen, *last_ts;        // [kWhItems] tokens sampled so far, the last two of them, the last timestamp (-1: none)
-  double* sum;                      // [kWhItems] the sum of the log-probabilities
-};
-struct WhHistory {                  // us_whisper_select: the group's histories, from the host
+struct WhHistory {                  // us_whisper_select, us_whisper_beam_select: the histories of a group's rows, from the host
   int count[kWhItems], last[kWhItems], pen[kWhItems], last_ts[kWhItems], done[kWhItems];
 };
 constexpr int kWhNone = 0x7fffffff;
@@ -502,44 +489,29 @@ __global__ __launch_bounds__(256) void wh_nospeech_kernel(const WhPart* __restri
   if (threadIdx.x == 0) out[blockIdx.x] = S > 0.f ? expf(logits[(size_t)m * V + no_speech] - (M + logf(S))) : 0.f;
 }
 
-__global__ __launch_bounds__(256) void wh_decode_init_kernel(WhDecState st, long long* __restrict__ tokens, long long* __restrict__ n,
-                                                             float* __restrict__ sum_out, int nb, int max_new, long long eos) {
+// The state of a group of nb items as a decoding starts (hist null in effect: use_hist 0) or from the host's histories (us_whisper_select),
+// and what an item returns that never chooses a token: tokens = eos, n = 0, and zeros in whichever of sum_out / logprob / decided is given.
+__global__ __launch_bounds__(256) void wh_state_init_kernel(WhDecState st, WhHistory hist, int use_hist, long long* __restrict__ tokens,
+                                                            long long* __restrict__ n, float* __restrict__ sum_out, float* __restrict__ logprob,
+                                                            int* __restrict__ decided, int nb, int max_new, long long eos) {
   const int tid = threadIdx.x;
   if (tid < kWhItems) {
     st.cur[tid] = 0;
-    st.done[tid] = 0;
-    st.count[tid] = 0;
-    st.last[tid] = st.pen[tid] = st.last_ts[tid] = -1;
+    st.done[tid] = use_hist ? hist.done[tid] : 0;
+    st.count[tid] = use_hist ? hist.count[tid] : 0;
+    st.last[tid] = use_hist ? hist.last[tid] : -1;
+    st.pen[tid] = use_hist ? hist.pen[tid] : -1;
+    st.last_ts[tid] = use_hist ? hist.last_ts[tid] : -1;
     st.sum[tid] = 0.0;
   }
   if (tid < nb) {
     n[tid] = 0;
-    sum_out[tid] = 0.f;
+    if (sum_out) sum_out[tid] = 0.f;
+    if (logprob) logprob[tid] = 0.f;
+    if (decided) decided[tid] = 0;
   }
   if (tid == 0) *st.running = nb;
   for (int i = tid; i < nb * max_new; i += 256) tokens[i] = eos;
-}
-
-// us_whisper_select: the host's histories into the state, and what a done item returns
-__global__ __launch_bounds__(64) void wh_select_init_kernel(WhDecState st, WhHistory hist, long long* __restrict__ token, long long* __restrict__ n,
-                                                            float* __restrict__ logprob, int* __restrict__ decided, int nb, long long eos) {
-  const int tid = threadIdx.x;
-  if (tid < kWhItems) {
-    st.cur[tid] = 0;
-    st.done[tid] = hist.done[tid];
-    st.count[tid] = hist.count[tid];
-    st.last[tid] = hist.last[tid];
-    st.pen[tid] = hist.pen[tid];
-    st.last_ts[tid] = hist.last_ts[tid];
-    st.sum[tid] = 0.0;
-    n[tid] = 0;
-  }
-  if (tid < nb) {
-    token[tid] = eos;
-    logprob[tid] = 0.f;
-    decided[tid] = 0;
-  }
-  if (tid == 0) *st.running = nb;
 }
 
 inline int wh_chunks(int V) { return (V + kWhChunk - 1) / kWhChunk; }
@@ -597,8 +569,8 @@ struct WhBeamState {                // a group's state: rows [kWhItems], items [
   float* topv;                      // [rows][2][chunks][kWhTop]
   int *topi, *topn;                 // the same, and [rows][2][chunks] how many are valid
 };
-struct WhBeamHist {                 // us_whisper_beam_select: the group's rows, from the host
-  int count[kWhItems], last[kWhItems], pen[kWhItems], last_ts[kWhItems], live[kWhItems];
+struct WhBeamHist {                 // us_whisper_beam_select: the group's rows, from the host; a row that is not done is live
+  WhHistory h;
   double score[kWhItems];
 };
 struct WhBeamOut {                  // us_whisper_beam_select's results per item, or nulls
@@ -617,11 +589,11 @@ __global__ __launch_bounds__(256) void wh_beam_init_kernel(WhBeamState st, WhBea
   if (tid < kWhItems) {
     const bool row = tid < items * n;
     st.cur[tid] = eos;
-    st.live[tid] = use_hist ? hist.live[tid] : (row && tid % n == 0 ? 1 : 0);
-    st.count[tid] = use_hist ? hist.count[tid] : 0;
-    st.last[tid] = use_hist ? hist.last[tid] : -1;
-    st.pen[tid] = use_hist ? hist.pen[tid] : -1;
-    st.last_ts[tid] = use_hist ? hist.last_ts[tid] : -1;
+    st.live[tid] = row && (use_hist ? !hist.h.done[tid] : tid % n == 0) ? 1 : 0;
+    st.count[tid] = use_hist ? hist.h.count[tid] : 0;
+    st.last[tid] = use_hist ? hist.h.last[tid] : -1;
+    st.pen[tid] = use_hist ? hist.h.pen[tid] : -1;
+    st.last_ts[tid] = use_hist ? hist.h.last_ts[tid] : -1;
     st.score[tid] = use_hist ? hist.score[tid] : 0.0;
     st.cand_n[tid] = 0;
     st.done[tid] = 0;
@@ -899,12 +871,12 @@ __global__ __launch_bounds__(256) void wh_beam_final_kernel(WhBeamState st, long
 
 // floats of a group's beam state with sequences of L tokens, ancestry over Tm positions and the partials of V logits
 inline size_t wh_beam_floats(int V, int L, int Tm) {
-  const size_t nc = (size_t)((V + kWhChunk - 1) / kWhChunk), R = kWhItems;
+  const size_t nc = (size_t)wh_chunks(V), R = kWhItems;
   return pad64(11 * R) + pad64(2 * R) + 2 * pad64(R * kWhTop) + pad64(2 * R * L) + pad64(2 * R * Tm) + pad64(2 * R * kWbMaxPool) + pad64(R * kWbMaxPool) +
          pad64(R * kWbMaxPool * L) + pad64(R * 2 * nc * 4) + 2 * pad64(R * 2 * nc * kWhTop) + pad64(R * 2 * nc);
 }
 inline WhBeamState wh_beam_carve(float* base, int V, int L, int Tm) {
-  const size_t nc = (size_t)((V + kWhChunk - 1) / kWhChunk), R = kWhItems;
+  const size_t nc = (size_t)wh_chunks(V), R = kWhItems;
   WsTake take;
   auto at = [&](size_t floats) { return base + take(floats); };
   int* ints = reinterpret_cast<int*>(at(11 * R));
@@ -929,7 +901,7 @@ inline WhBeamState wh_beam_carve(float* base, int V, int L, int Tm) {
 // the three launches of one beam step of a group of `items` items behind its logits
 inline void wh_beam_step(const float* L, const unsigned char* suppress, const unsigned char* begin, const WhBeamState& st, const WhRules& r,
                          const WhBeamOut& out, int V, int n, int C, int items, int step, int pos, int Ls, int Tm, int tables, hipStream_t s) {
-  const int nc = (V + kWhChunk - 1) / kWhChunk;
+  const int nc = wh_chunks(V);
   hipLaunchKernelGGL(wh_beam_partial_kernel, dim3(nc, items * n), dim3(256), 0, s, L, suppress, begin, st, r, V, nc, n);
   hipLaunchKernelGGL(wh_beam_row_kernel, dim3(items * n), dim3(256), 0, s, st, r, nc, n);
   hipLaunchKernelGGL(wh_beam_book_kernel, dim3(items), dim3(256), 0, s, st, r, out, n, C, step, pos, Ls, Tm, tables);
@@ -950,6 +922,7 @@ struct us_whisper : us::WeightTable {
   us_whisper_config cfg{};
   us::WhEncoder* enc = nullptr;
   std::vector<us::WhDecLayer> dec;
+  const float *embed_tokens = nullptr, *embed_positions = nullptr, *ln_g = nullptr, *ln_b = nullptr;       // the decoder's embeddings and final LayerNorm
   bool allocated = false, dirty = true;
 };
 
@@ -1029,13 +1002,17 @@ hipError_t wh_prepare(us_whisper* h, hipStream_t s) {
     l.fc1 = {W(p + "fc1.weight"), W(p + "fc1.bias")};
     l.fc2 = {W(p + "fc2.weight"), W(p + "fc2.bias")};
   }
+  h->embed_tokens = W("model.decoder.embed_tokens.weight");
+  h->embed_positions = W("model.decoder.embed_positions.weight");
+  h->ln_g = W("model.decoder.layer_norm.weight");
+  h->ln_b = W("model.decoder.layer_norm.bias");
   const hipError_t e = wh_encoder_prepare(h->enc, *h, s);
   if (e == hipSuccess) h->dirty = false;
   return e;
 }
 
 struct WhPlan {                 // float offsets into the aligned workspace
-  size_t enc, planar, kv, cache, x, q, att, ff, logits, state, select, total;
+  size_t enc, planar, kv, cache, x, q, att, ff, logits, select, total;
 };
 
 WhPlan wh_plan(const us_whisper* h, int B) {
@@ -1052,8 +1029,7 @@ WhPlan wh_plan(const us_whisper* h, int B) {
   p.att = take(kWhItems * H);
   p.ff = take((size_t)kWhItems * c.decoder_ffn);
   p.logits = take((size_t)kWhItems * c.vocab_size);
-  p.state = take(64);
-  p.select = take(wh_select_floats(c.vocab_size));       // behind everything us_whisper_generate uses
+  p.select = take(wh_select_floats(c.vocab_size));       // the group's state, and the selection stage's partials
   p.total = take.total;
   return p;
 }
@@ -1127,25 +1103,111 @@ void wh_layers(const WhStep& t, int pos) {
   }
 }
 
+
 // logits of the rows in X: decoder.layer_norm, then the tied embedding; row m at y + m * ldy
 void wh_logits(const WhStep& t, float* y, long long ldy) {
-  auto W = [&](const char* k) { return (const float*)t.h->w.at(k).dev; };
-  const WhSeg sg{W("model.decoder.embed_tokens.weight"), nullptr, y, ldy, 1.f};
-  wh_gemm(t, t.X, t.h->cfg.d_model, W("model.decoder.layer_norm.weight"), W("model.decoder.layer_norm.bias"), nullptr, t.h->cfg.vocab_size, 0, 1, &sg);
+  const WhSeg sg{t.h->embed_tokens, nullptr, y, ldy, 1.f};
+  wh_gemm(t, t.X, t.h->cfg.d_model, t.h->ln_g, t.h->ln_b, nullptr, t.h->cfg.vocab_size, 0, 1, &sg);
 }
 
-void wh_embed(const WhStep& t, const WhTokens& forced, const int* cur, int pos) {
-  auto W = [&](const char* k) { return (const float*)t.h->w.at(k).dev; };
-  hipLaunchKernelGGL(wh_embed_kernel, dim3(t.nb), dim3(256), 0, t.s, W("model.decoder.embed_tokens.weight"), W("model.decoder.embed_positions.weight"),
-                     cur, forced, t.X, t.h->cfg.d_model, pos);
+// position `pos` of a group through the embedding and the layers.  host: row m takes ids[b0 + m / rpi][pos] of the host's [B][P]; else cur[m]
+void wh_position(const WhStep& t, const int64_t* ids, int P, int b0, int pos, const int* cur, bool host) {
+  WhTokens f;
+  for (int m = 0; m < kWhItems; ++m) f.id[m] = !host ? -1 : m < t.nb ? (int)ids[(size_t)(b0 + m / t.rpi) * P + pos] : 0;
+  hipLaunchKernelGGL(wh_embed_kernel, dim3(t.nb), dim3(256), 0, t.s, t.h->embed_tokens, t.h->embed_positions, cur, f, t.X, t.h->cfg.d_model, pos);
+  wh_layers(t, pos);
 }
 
-WhStep wh_group(us_whisper* h, const WhPlan& p, float* base, int B, int b0, int nb, hipStream_t s) {
+// the buffers of the group of nb rows, rpi per item, whose first item is b0.  cache: the group's rows of layer 0 in a self cache of cache_rows
+// rows a layer, or null: the items' own rows of the plan's
+WhStep wh_group(us_whisper* h, const WhPlan& p, float* base, float* cache, int cache_rows, int rpi, int B, int b0, int nb, hipStream_t s) {
   const auto& c = h->cfg;
   const size_t H = (size_t)c.d_model;
-  return WhStep{h, s, base + p.x, base + p.q, base + p.att, base + p.ff, base + p.cache + (size_t)b0 * 2 * c.max_target_positions * H,
-                base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions, B, nb, B, 1, nullptr};
+  return WhStep{h, s, base + p.x, base + p.q, base + p.att, base + p.ff, cache ? cache : base + p.cache + (size_t)b0 * 2 * c.max_target_positions * H,
+                base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions, B, nb, cache ? cache_rows : B, rpi, nullptr};
 }
+
+// rows of the largest launch group of B items at beam size n: floor(16 / n) whole items
+inline int wh_beam_group_rows(int B, int n) { return std::min(B, kWhItems / n) * n; }
+
+struct WhBeamPlan {             // float offsets behind wh_plan(h, B): the self cache of one group's rows, the group's beam state
+  size_t cache, state, total;
+};
+WhBeamPlan wh_beam_plan(const us_whisper* h, int B, int n) {
+  const auto& c = h->cfg;
+  WhBeamPlan p{};
+  WsTake take;
+  take(wh_plan(h, B).total);
+  p.cache = take((size_t)c.decoder_layers * wh_beam_group_rows(B, n) * 2 * c.max_target_positions * c.d_model);
+  p.state = take(wh_beam_floats(c.vocab_size, c.max_target_positions, c.max_target_positions));
+  p.total = take.total;
+  return p;
+}
+
+// ---- the decoding walk --------------------------------------------------------------------------------------------------------------
+// us_whisper_generate, us_whisper_decode and us_whisper_decode_beam are one walk over launch groups, prompt positions and steps; a policy
+// names the five places where they differ.
+
+struct WhPolicy {
+  int rpi;                      // rows per item: a launch group is kWhItems / rpi whole items
+  int *cur, *running;           // the state's [kWhItems] token each row embeds next, and its count of the group's items that have not ended
+  const int* anc;               // null, or the ancestry tables [2][kWhItems][max_target_positions]: a step reads the one of its parity
+  float* cache;                 // with anc: the self cache the groups' rows share, cache_rows rows a layer; null: every item has its own
+  int cache_rows;
+  std::function<void(int b0, int items)> init;         // the group's state, and what an item returns that chooses nothing
+  std::function<void(const float* L, int b0, int items, int step, int pos)> select;       // the step's logits -> tokens, cur, running
+  std::function<void(int b0, int items)> final;        // behind the group's last step, or empty
+};
+struct WhProbe {                // the no-speech probability: softmax(unfiltered logits)[token] behind the prompt's token sot -> out [B]; token < 0: none
+  int token, sot;
+  float* out;
+};
+
+// The prompt [B][P] but for its last token is teacher-forced (keys and values only); up to max_new steps follow, the first from the prompt's
+// last token, the others from the token the selection chose.  The running count is read back every kWhPoll steps: the first error of that
+// read stops the call with nothing launched behind it, else hipGetLastError() closes it.
+hipError_t wh_walk(us_whisper* h, const WhPlan& p, float* base, const int64_t* prompt, int B, int P, int max_new, const WhProbe& probe,
+                   const WhPolicy& pol, hipStream_t s) {
+  const int V = h->cfg.vocab_size, Tm = h->cfg.max_target_positions, nc = wh_chunks(V), ipg = kWhItems / pol.rpi;
+  const WhSelect sel = wh_select_carve(base + p.select);        // the probe's plain partials: they read neither the state nor the rules
+  float* L = base + p.logits;
+  for (int b0 = 0; b0 < B; b0 += ipg) {
+    const int items = std::min(ipg, B - b0), M = items * pol.rpi;
+    WhStep t = wh_group(h, p, base, pol.cache, pol.cache_rows, pol.rpi, B, b0, M, s);
+    t.anc = pol.anc;
+    pol.init(b0, items);
+    auto probe_here = [&]() {                           // L holds the logits behind sot; an item's first row speaks for it
+      hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, M), dim3(256), 0, s, L, nullptr, nullptr, sel.st, WhRules{}, sel.part, V, nc, 1);
+      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(items), dim3(256), 0, s, sel.part, L, probe.out + b0, V, nc, probe.token, pol.rpi);
+    };
+    for (int pos = 0; pos + 1 < P; ++pos) {
+      wh_position(t, prompt, P, b0, pos, pol.cur, true);
+      if (probe.token >= 0 && pos == probe.sot) {
+        wh_logits(t, L, V);
+        probe_here();
+      }
+    }
+    for (int step = 0; step < max_new; ++step) {
+      const int pos = P - 1 + step;
+      if (pol.anc) t.anc = pol.anc + (size_t)(step & 1) * kWhItems * Tm;
+      wh_position(t, prompt, P, b0, pos, pol.cur, step == 0);
+      wh_logits(t, L, V);
+      if (step == 0 && probe.token >= 0 && pos == probe.sot) probe_here();
+      pol.select(L, b0, items, step, pos);
+      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
+        int running = 1;
+        hipError_t e = hipMemcpyAsync(&running, pol.running, sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        if (running <= 0) break;
+      }
+    }
+    if (pol.final) pol.final(b0, items);
+  }
+  return hipGetLastError();
+}
+
+// ---- refusals: "" or the text -------------------------------------------------------------------------------------------------------
 
 std::string wh_bad_token(const std::string& what, const int64_t* ids, size_t n, int V) {
   for (size_t i = 0; i < n; ++i)
@@ -1153,6 +1215,56 @@ std::string wh_bad_token(const std::string& what, const int64_t* ids, size_t n, 
       return what + ": token " + std::to_string((long long)ids[i]) + " at index " + std::to_string(i) + " lies outside the vocabulary [0, " +
              std::to_string(V) + ")";
   return std::string();
+}
+
+std::string wh_bad_span(const std::string& what, int P, int max_new, int Tm) {
+  if (P >= 1 && max_new >= 1 && (long long)P + max_new <= Tm) return std::string();
+  return what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
+         " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(Tm);
+}
+
+// what the selection rules ask of the options and a vocabulary of V tokens
+std::string wh_bad_rules(const std::string& what, const us_whisper_decode_options& o, int V) {
+  if (V < 1 || V > (1 << 24)) return what + ": V must lie in [1, 2^24]";
+  if (o.eos < 0 || o.eos >= o.no_timestamps)
+    return what + ": eos = " + std::to_string(o.eos) + " must lie in [0, no_timestamps = " + std::to_string(o.no_timestamps) + ")";
+  if ((long long)o.no_timestamps + 1 >= V)
+    return what + ": no_timestamps + 1 = " + std::to_string((long long)o.no_timestamps + 1) + " >= vocab_size = " + std::to_string(V) +
+           ": the vocabulary has no timestamp token";
+  if (o.max_initial_timestamp_index < -1) return what + ": max_initial_timestamp_index must be -1 (none) or an index";
+  return std::string();
+}
+
+// the options and the prompt of us_whisper_decode and us_whisper_decode_beam
+std::string wh_bad_decode(const std::string& what, const us_whisper_config& c, const us_whisper_decode_options& o, const int64_t* prompt, int B, int P,
+                          const float* no_speech_prob) {
+  std::string bad = wh_bad_span(what, P, o.max_new, c.max_target_positions);
+  if (bad.empty()) bad = wh_bad_rules(what, o, c.vocab_size);
+  if (!bad.empty()) return bad;
+  if (o.no_speech < -1 || o.no_speech >= c.vocab_size) return what + ": no_speech lies outside the vocabulary (-1: none)";
+  if (o.no_speech >= 0 && !no_speech_prob) return what + ": a no_speech token needs no_speech_prob";
+  if (o.sot_index < 0 || o.sot_index >= P) return what + ": sot_index = " + std::to_string(o.sot_index) + " lies outside the prompt of " + std::to_string(P);
+  return wh_bad_token(what, prompt, (size_t)B * P, c.vocab_size);
+}
+
+std::string wh_bad_history(const std::string& what, const us_whisper_history* history, long long rows) {
+  for (long long m = 0; m < rows; ++m)
+    if (history[m].n_sampled < 0) return what + ": history[" + std::to_string(m) + "].n_sampled is negative";
+  return std::string();
+}
+
+// the host's histories of a group's `rows` rows as the kernels take them; a slot past the group repeats its last row
+WhHistory wh_history(const us_whisper_history* history, int rows, int tb) {
+  WhHistory g{};
+  for (int m = 0; m < kWhItems; ++m) {
+    const us_whisper_history& h = history[std::min(m, rows - 1)];
+    g.count[m] = h.n_sampled;
+    g.last[m] = h.n_sampled >= 1 ? h.last : -1;
+    g.pen[m] = h.n_sampled >= 2 ? h.penultimate : -1;
+    g.last_ts[m] = h.last_timestamp >= tb ? h.last_timestamp : -1;
+    g.done[m] = h.done != 0;
+  }
+  return g;
 }
 
 }  // namespace
@@ -1212,11 +1324,23 @@ int us_whisper_load_weight(us_whisper_handle h, const char* key, const float* da
 
 size_t us_whisper_workspace_bytes(us_whisper_handle h, int B) { return h && B > 0 && B <= 65535 ? wh_workspace_bytes(h, B) : 0; }
 
+size_t us_whisper_beam_workspace_bytes(us_whisper_handle h, int B, int beam_size) {
+  return h && B > 0 && B <= 65535 && beam_size >= 1 && beam_size <= kWbMaxBeam ? wh_beam_plan(h, B, beam_size).total * sizeof(float) + 256 : 0;
+}
+
+size_t us_whisper_select_scratch_bytes(int V) { return V >= 1 && V <= (1 << 24) ? wh_select_floats(V) * sizeof(float) + 256 : 0; }
+
+size_t us_whisper_beam_select_scratch_bytes(int V, int beam_size) {
+  return V >= 1 && V <= (1 << 24) && beam_size >= 1 && beam_size <= kWbMaxBeam ? wh_beam_floats(V, 1, 2) * sizeof(float) + 256 : 0;
+}
+
 int us_whisper_encode(us_whisper_handle h, const float* features, int B, int T, float* out, void* workspace, size_t workspace_bytes, us_stream stream) {
   if (!out) return WeightTable::fail(h, US_EINVAL, "us_whisper_encode: bad argument");
   return wh_begin(h, "us_whisper_encode", features, B, T, out, false, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+// Teacher forcing with the logits of every position and no step: not wh_walk, which takes logits inside the prompt for the probe alone and
+// into the group's one buffer.
 int us_whisper_decoder_logits(us_whisper_handle h, const float* features, int B, int T, const int64_t* ids, int N, float* logits, void* workspace,
                               size_t workspace_bytes, us_stream stream) {
   const std::string what = "us_whisper_decoder_logits";
@@ -1231,16 +1355,13 @@ int us_whisper_decoder_logits(us_whisper_handle h, const float* features, int B,
   if (rc != US_OK) return rc;
   const WhPlan p = wh_plan(h, B);
   float* base = ws_align(workspace);
-  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
-    const WhStep t = wh_group(h, p, base, B, b0, nb, s);
+  for (int b0 = 0; b0 < B; b0 += kWhItems) {
+    const WhStep t = wh_group(h, p, base, nullptr, 0, 1, B, b0, std::min(kWhItems, B - b0), s);
     for (int pos = 0; pos < N; ++pos) {
-      WhTokens f;
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < nb ? (int)ids[(size_t)(b0 + m) * N + pos] : 0;
-      wh_embed(t, f, nullptr, pos);
-      wh_layers(t, pos);
+      wh_position(t, ids, N, b0, pos, nullptr, true);
       wh_logits(t, logits + ((size_t)b0 * N + pos) * c.vocab_size, (long long)N * c.vocab_size);
     }
-  });
+  }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
 }
@@ -1250,90 +1371,54 @@ int us_whisper_generate(us_whisper_handle h, const float* features, int B, int T
                         size_t workspace_bytes, us_stream stream) {
   const std::string what = "us_whisper_generate";
   if (!h || !prompt || !tokens || !n || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
-  const auto& c = h->cfg;
-  if (P < 1 || max_new < 1 || (long long)P + max_new > c.max_target_positions)
-    return h->fail(US_EINVAL, what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
-                                  " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(c.max_target_positions));
-  if (eos < 0 || eos >= c.vocab_size) return h->fail(US_EINVAL, what + ": eos lies outside the vocabulary");
-  const std::string bad = wh_bad_token(what, prompt, (size_t)B * P, c.vocab_size);
+  const int V = h->cfg.vocab_size;
+  std::string bad = wh_bad_span(what, P, max_new, h->cfg.max_target_positions);
+  if (bad.empty() && (eos < 0 || eos >= V)) bad = what + ": eos lies outside the vocabulary";
+  if (bad.empty()) bad = wh_bad_token(what, prompt, (size_t)B * P, V);
   if (!bad.empty()) return h->fail(US_EINVAL, bad);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rc = wh_begin(h, what, features, B, T, nullptr, true, workspace, workspace_bytes, s);
   if (rc != US_OK) return rc;
   const WhPlan p = wh_plan(h, B);
   float* base = ws_align(workspace);
-  int* ints = reinterpret_cast<int*>(base + p.state);
-  const WhGenState st{ints, ints + kWhItems, ints + 2 * kWhItems};
-  float* L = base + p.logits;
-  hipError_t e = hipSuccess;
-  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
-    if (e != hipSuccess) return;
-    const WhStep t = wh_group(h, p, base, B, b0, nb, s);
-    long long* tok = reinterpret_cast<long long*>(tokens) + (size_t)b0 * max_new;
-    long long* cnt = reinterpret_cast<long long*>(n) + b0;
-    hipLaunchKernelGGL(wh_init_kernel, dim3(1), dim3(256), 0, s, st, tok, cnt, nb, max_new, (long long)eos);
-    WhTokens f;
-    for (int pos = 0; pos + 1 < P; ++pos) {             // the prompt but for its last token: keys and values only
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : 0;
-      wh_embed(t, f, st.cur, pos);
-      wh_layers(t, pos);
-    }
-    for (int step = 0; step < max_new; ++step) {
-      const int pos = P - 1 + step;
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = step == 0 && m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : step == 0 ? 0 : -1;
-      wh_embed(t, f, st.cur, pos);
-      wh_layers(t, pos);
-      wh_logits(t, L, c.vocab_size);
-      hipLaunchKernelGGL(wh_argmax_kernel, dim3(nb), dim3(256), 0, s, L, suppress, step == 0 ? begin_suppress : nullptr, st, tok, cnt, c.vocab_size,
-                         max_new, step, (int)eos);
-      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
-        int running = 1;
-        if ((e = hipMemcpyAsync(&running, st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return;
-        if (running <= 0) break;
-      }
-    }
-  });
-  if (e == hipSuccess) e = hipGetLastError();
+  const WhDecState st = wh_select_carve(base + p.select).st;
+  long long *tok = reinterpret_cast<long long*>(tokens), *cnt = reinterpret_cast<long long*>(n);
+  WhPolicy pol{1, st.cur, st.running, nullptr, nullptr, 0};
+  pol.init = [&](int b0, int items) {
+    hipLaunchKernelGGL(wh_state_init_kernel, dim3(1), dim3(256), 0, s, st, WhHistory{}, 0, tok + (size_t)b0 * max_new, cnt + b0, nullptr, nullptr, nullptr,
+                       items, max_new, (long long)eos);
+  };
+  pol.select = [&](const float* L, int b0, int items, int step, int) {
+    hipLaunchKernelGGL(wh_argmax_kernel, dim3(items), dim3(256), 0, s, L, suppress, step == 0 ? begin_suppress : nullptr, st, tok + (size_t)b0 * max_new,
+                       cnt + b0, V, max_new, step, (int)eos);
+  };
+  const hipError_t e = wh_walk(h, p, base, prompt, B, P, max_new, WhProbe{-1, 0, nullptr}, pol, s);
   return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
 }
-
-size_t us_whisper_select_scratch_bytes(int V) { return V >= 1 && V <= (1 << 24) ? wh_select_floats(V) * sizeof(float) + 256 : 0; }
 
 int us_whisper_select(const float* logits, int B, int V, const us_whisper_history* history, const us_whisper_decode_options* options,
                       const unsigned char* suppress, const unsigned char* begin_suppress, int64_t* token, float* logprob,
                       int32_t* decided_timestamp, void* scratch, size_t scratch_bytes, us_stream stream) {
   const std::string what = "us_whisper_select";
-  auto bad = [&](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, what + ": " + m); };
-  if (!logits || !history || !options || !token || !logprob || !decided_timestamp || B < 1) return bad("bad argument");
+  auto refuse = [&](int code, const std::string& m) { return WeightTable::fail(nullptr, code, m); };
+  if (!logits || !history || !options || !token || !logprob || !decided_timestamp || B < 1) return refuse(US_EINVAL, what + ": bad argument");
   const auto& o = *options;
-  if (V < 1 || V > (1 << 24)) return bad("V must lie in [1, 2^24]");
-  if (o.eos < 0 || o.eos >= o.no_timestamps) return bad("eos must lie in [0, no_timestamps)");
-  if ((long long)o.no_timestamps + 1 >= V) return bad("no_timestamps + 1 >= V: the vocabulary has no timestamp token");
-  if (o.max_initial_timestamp_index < -1) return bad("max_initial_timestamp_index must be -1 (none) or an index");
-  if (!scratch || scratch_bytes < us_whisper_select_scratch_bytes(V))
-    return WeightTable::fail(nullptr, US_EWORKSPACE, what + ": scratch too small (us_whisper_select_scratch_bytes)");
-  for (int b = 0; b < B; ++b)
-    if (history[b].n_sampled < 0) return bad("history[" + std::to_string(b) + "].n_sampled is negative");
+  std::string bad = wh_bad_rules(what, o, V);
+  if (!bad.empty()) return refuse(US_EINVAL, bad);
+  if (!scratch || scratch_bytes < us_whisper_select_scratch_bytes(V)) return refuse(US_EWORKSPACE, what + ": scratch too small (us_whisper_select_scratch_bytes)");
+  if (!(bad = wh_bad_history(what, history, B)).empty()) return refuse(US_EINVAL, bad);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const WhSelect c = wh_select_carve(ws_align(scratch));
   const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
-  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
-    WhHistory hist{};
-    for (int m = 0; m < kWhItems; ++m) {
-      const us_whisper_history& h = history[b0 + std::min(m, nb - 1)];
-      hist.count[m] = h.n_sampled;
-      hist.last[m] = h.n_sampled >= 1 ? h.last : -1;
-      hist.pen[m] = h.n_sampled >= 2 ? h.penultimate : -1;
-      hist.last_ts[m] = h.last_timestamp >= r.tb ? h.last_timestamp : -1;
-      hist.done[m] = h.done != 0;
-    }
+  for (int b0 = 0; b0 < B; b0 += kWhItems) {
+    const int nb = std::min(kWhItems, B - b0);
     long long* tok = reinterpret_cast<long long*>(token) + b0;
-    hipLaunchKernelGGL(wh_select_init_kernel, dim3(1), dim3(64), 0, s, c.st, hist, tok, c.n, logprob + b0, decided_timestamp + b0, nb, (long long)o.eos);
+    hipLaunchKernelGGL(wh_state_init_kernel, dim3(1), dim3(256), 0, s, c.st, wh_history(history + b0, nb, r.tb), 1, tok, c.n, nullptr, logprob + b0,
+                       decided_timestamp + b0, nb, 1, (long long)o.eos);
     wh_select_step(logits + (size_t)b0 * V, suppress, begin_suppress, c, r, tok, c.n, nullptr, logprob + b0, decided_timestamp + b0, V, nb, 1, 0, s);
-  });
+  }
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : WeightTable::fail(nullptr, US_EHIP, what + ": " + hipGetErrorString(e));
+  return e == hipSuccess ? US_OK : refuse(US_EHIP, what + ": " + hipGetErrorString(e));
 }
 
 int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P,
@@ -1341,24 +1426,10 @@ int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, 
                       int64_t* n, float* sum_logprobs, float* no_speech_prob, void* workspace, size_t workspace_bytes, us_stream stream) {
   const std::string what = "us_whisper_decode";
   if (!h || !prompt || !options || !tokens || !n || !sum_logprobs || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
-  const auto& c = h->cfg;
   const auto& o = *options;
-  const int V = c.vocab_size, max_new = o.max_new;
-  if (P < 1 || max_new < 1 || (long long)P + max_new > c.max_target_positions)
-    return h->fail(US_EINVAL, what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
-                                  " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(c.max_target_positions));
-  if (o.eos < 0 || o.eos >= o.no_timestamps)
-    return h->fail(US_EINVAL, what + ": eos = " + std::to_string(o.eos) + " must lie in [0, no_timestamps = " + std::to_string(o.no_timestamps) + ")");
-  if ((long long)o.no_timestamps + 1 >= V)
-    return h->fail(US_EINVAL, what + ": no_timestamps + 1 = " + std::to_string((long long)o.no_timestamps + 1) + " >= vocab_size = " + std::to_string(V) +
-                                  ": the vocabulary has no timestamp token");
-  if (o.max_initial_timestamp_index < -1) return h->fail(US_EINVAL, what + ": max_initial_timestamp_index must be -1 (none) or an index");
-  if (o.no_speech < -1 || o.no_speech >= V) return h->fail(US_EINVAL, what + ": no_speech lies outside the vocabulary (-1: none)");
-  if (o.no_speech >= 0 && !no_speech_prob) return h->fail(US_EINVAL, what + ": a no_speech token needs no_speech_prob");
-  if (o.sot_index < 0 || o.sot_index >= P)
-    return h->fail(US_EINVAL, what + ": sot_index = " + std::to_string(o.sot_index) + " lies outside the prompt of " + std::to_string(P));
-  const std::string badtok = wh_bad_token(what, prompt, (size_t)B * P, V);
-  if (!badtok.empty()) return h->fail(US_EINVAL, badtok);
+  const int V = h->cfg.vocab_size, max_new = o.max_new;
+  const std::string bad = wh_bad_decode(what, h->cfg, o, prompt, B, P, no_speech_prob);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rc = wh_begin(h, what, features, B, T, nullptr, true, workspace, workspace_bytes, s);
   if (rc != US_OK) return rc;
@@ -1366,83 +1437,17 @@ int us_whisper_decode(us_whisper_handle h, const float* features, int B, int T, 
   float* base = ws_align(workspace);
   const WhSelect sel = wh_select_carve(base + p.select);
   const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
-  const int nc = wh_chunks(V);
-  float* L = base + p.logits;
-  hipError_t e = hipSuccess;
-  for_item_groups<kWhItems>(B, [](int) { return 1; }, [&](int b0, int nb, const ItemLens<kWhItems>&, int) {
-    if (e != hipSuccess) return;
-    const WhStep t = wh_group(h, p, base, B, b0, nb, s);
-    long long* tok = reinterpret_cast<long long*>(tokens) + (size_t)b0 * max_new;
-    long long* cnt = reinterpret_cast<long long*>(n) + b0;
-    hipLaunchKernelGGL(wh_decode_init_kernel, dim3(1), dim3(256), 0, s, sel.st, tok, cnt, sum_logprobs + b0, nb, max_new, (long long)o.eos);
-    auto no_speech = [&](int pos) {                     // L holds the logits of position `pos`
-      if (o.no_speech < 0 || pos != o.sot_index) return;
-      hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, nb), dim3(256), 0, s, L, nullptr, nullptr, sel.st, r, sel.part, V, nc, 1);
-      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(nb), dim3(256), 0, s, sel.part, L, no_speech_prob + b0, V, nc, o.no_speech, 1);
-    };
-    WhTokens f;
-    for (int pos = 0; pos + 1 < P; ++pos) {             // the prompt but for its last token: keys and values, and the start token's logits
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : 0;
-      wh_embed(t, f, sel.st.cur, pos);
-      wh_layers(t, pos);
-      if (o.no_speech >= 0 && pos == o.sot_index) {
-        wh_logits(t, L, V);
-        no_speech(pos);
-      }
-    }
-    for (int step = 0; step < max_new; ++step) {
-      const int pos = P - 1 + step;
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = step == 0 && m < nb ? (int)prompt[(size_t)(b0 + m) * P + pos] : step == 0 ? 0 : -1;
-      wh_embed(t, f, sel.st.cur, pos);
-      wh_layers(t, pos);
-      wh_logits(t, L, V);
-      if (step == 0) no_speech(pos);
-      wh_select_step(L, suppress, begin_suppress, sel, r, tok, cnt, sum_logprobs + b0, nullptr, nullptr, V, nb, max_new, step, s);
-      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
-        int running = 1;
-        if ((e = hipMemcpyAsync(&running, sel.st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return;
-        if (running <= 0) break;
-      }
-    }
-  });
-  if (e == hipSuccess) e = hipGetLastError();
+  long long *tok = reinterpret_cast<long long*>(tokens), *cnt = reinterpret_cast<long long*>(n);
+  WhPolicy pol{1, sel.st.cur, sel.st.running, nullptr, nullptr, 0};
+  pol.init = [&](int b0, int items) {
+    hipLaunchKernelGGL(wh_state_init_kernel, dim3(1), dim3(256), 0, s, sel.st, WhHistory{}, 0, tok + (size_t)b0 * max_new, cnt + b0, sum_logprobs + b0,
+                       nullptr, nullptr, items, max_new, (long long)o.eos);
+  };
+  pol.select = [&](const float* L, int b0, int items, int step, int) {
+    wh_select_step(L, suppress, begin_suppress, sel, r, tok + (size_t)b0 * max_new, cnt + b0, sum_logprobs + b0, nullptr, nullptr, V, items, max_new, step, s);
+  };
+  const hipError_t e = wh_walk(h, p, base, prompt, B, P, max_new, WhProbe{o.no_speech, o.sot_index, no_speech_prob}, pol, s);
   return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
-}
-
-}  // extern "C"
-
-namespace us {
-namespace {
-
-// rows of the largest launch group of B items at beam size n: floor(16 / n) whole items
-inline int wh_beam_group_rows(int B, int n) { return std::min(B, kWhItems / n) * n; }
-
-struct WhBeamPlan {             // float offsets behind wh_plan(h, B): the self cache of one group's rows, the group's beam state
-  size_t cache, state, total;
-};
-WhBeamPlan wh_beam_plan(const us_whisper* h, int B, int n) {
-  const auto& c = h->cfg;
-  WhBeamPlan p{};
-  WsTake take;
-  take(wh_plan(h, B).total);
-  p.cache = take((size_t)c.decoder_layers * wh_beam_group_rows(B, n) * 2 * c.max_target_positions * c.d_model);
-  p.state = take(wh_beam_floats(c.vocab_size, c.max_target_positions, c.max_target_positions));
-  p.total = take.total;
-  return p;
-}
-
-}  // namespace
-}  // namespace us
-
-extern "C" {
-
-size_t us_whisper_beam_workspace_bytes(us_whisper_handle h, int B, int beam_size) {
-  return h && B > 0 && B <= 65535 && beam_size >= 1 && beam_size <= kWbMaxBeam ? wh_beam_plan(h, B, beam_size).total * sizeof(float) + 256 : 0;
-}
-
-size_t us_whisper_beam_select_scratch_bytes(int V, int beam_size) {
-  return V >= 1 && V <= (1 << 24) && beam_size >= 1 && beam_size <= kWbMaxBeam ? wh_beam_floats(V, 1, 2) * sizeof(float) + 256 : 0;
 }
 
 int us_whisper_beam_select(const float* logits, int B, int V, int beam_size, const us_whisper_history* history, const double* scores,
@@ -1450,43 +1455,31 @@ int us_whisper_beam_select(const float* logits, int B, int V, int beam_size, con
                            int32_t* parent, int64_t* token, double* score, int32_t* n_live, int32_t* fin_parent, double* fin_score, int32_t* n_fin,
                            void* scratch, size_t scratch_bytes, us_stream stream) {
   const std::string what = "us_whisper_beam_select";
-  auto bad = [&](const std::string& m) { return WeightTable::fail(nullptr, US_EINVAL, what + ": " + m); };
+  auto refuse = [&](int code, const std::string& m) { return WeightTable::fail(nullptr, code, m); };
   if (!logits || !history || !scores || !options || !parent || !token || !score || !n_live || !fin_parent || !fin_score || !n_fin || B < 1)
-    return bad("bad argument");
+    return refuse(US_EINVAL, what + ": bad argument");
   const auto& o = *options;
   const int n = beam_size;
-  if (n < 1 || n > kWbMaxBeam) return bad("beam_size must lie in [1, " + std::to_string(kWbMaxBeam) + "]");
-  if (V < 1 || V > (1 << 24)) return bad("V must lie in [1, 2^24]");
-  if (o.eos < 0 || o.eos >= o.no_timestamps) return bad("eos must lie in [0, no_timestamps)");
-  if ((long long)o.no_timestamps + 1 >= V) return bad("no_timestamps + 1 >= V: the vocabulary has no timestamp token");
-  if (o.max_initial_timestamp_index < -1) return bad("max_initial_timestamp_index must be -1 (none) or an index");
+  if (n < 1 || n > kWbMaxBeam) return refuse(US_EINVAL, what + ": beam_size must lie in [1, " + std::to_string(kWbMaxBeam) + "]");
+  std::string bad = wh_bad_rules(what, o, V);
+  if (!bad.empty()) return refuse(US_EINVAL, bad);
   if (!scratch || scratch_bytes < us_whisper_beam_select_scratch_bytes(V, n))
-    return WeightTable::fail(nullptr, US_EWORKSPACE, what + ": scratch too small (us_whisper_beam_select_scratch_bytes)");
-  for (long long m = 0; m < (long long)B * n; ++m)
-    if (history[m].n_sampled < 0) return bad("history[" + std::to_string(m) + "].n_sampled is negative");
+    return refuse(US_EWORKSPACE, what + ": scratch too small (us_whisper_beam_select_scratch_bytes)");
+  if (!(bad = wh_bad_history(what, history, (long long)B * n)).empty()) return refuse(US_EINVAL, bad);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const WhBeamState st = wh_beam_carve(ws_align(scratch), V, 1, 2);
   const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
-  const int ipg = kWhItems / n;
-  for (int b0 = 0; b0 < B; b0 += ipg) {
+  for (int b0 = 0, ipg = kWhItems / n; b0 < B; b0 += ipg) {
     const int items = std::min(ipg, B - b0);
-    WhBeamHist hist{};
-    for (int m = 0; m < items * n; ++m) {
-      const us_whisper_history& hh = history[(size_t)b0 * n + m];
-      hist.count[m] = hh.n_sampled;
-      hist.last[m] = hh.n_sampled >= 1 ? hh.last : -1;
-      hist.pen[m] = hh.n_sampled >= 2 ? hh.penultimate : -1;
-      hist.last_ts[m] = hh.last_timestamp >= r.tb ? hh.last_timestamp : -1;
-      hist.live[m] = hh.done == 0;
-      hist.score[m] = scores[(size_t)b0 * n + m];
-    }
-    const WhBeamOut out{parent + (size_t)b0 * n,     reinterpret_cast<long long*>(token) + (size_t)b0 * n, score + (size_t)b0 * n, n_live + b0,
-                        fin_parent + (size_t)b0 * n, fin_score + (size_t)b0 * n,                           n_fin + b0};
+    const size_t m0 = (size_t)b0 * n;
+    WhBeamHist hist{wh_history(history + m0, items * n, r.tb), {}};
+    for (int m = 0; m < items * n; ++m) hist.score[m] = scores[m0 + m];
+    const WhBeamOut out{parent + m0, reinterpret_cast<long long*>(token) + m0, score + m0, n_live + b0, fin_parent + m0, fin_score + m0, n_fin + b0};
     hipLaunchKernelGGL(wh_beam_init_kernel, dim3(1), dim3(256), 0, s, st, hist, 1, n, items, o.eos, 1, 2);
-    wh_beam_step(logits + (size_t)b0 * n * V, suppress, begin_suppress, st, r, out, V, n, kWbMaxPool, items, 0, 0, 1, 2, 0, s);
+    wh_beam_step(logits + m0 * V, suppress, begin_suppress, st, r, out, V, n, kWbMaxPool, items, 0, 0, 1, 2, 0, s);
   }
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? US_OK : WeightTable::fail(nullptr, US_EHIP, what + ": " + hipGetErrorString(e));
+  return e == hipSuccess ? US_OK : refuse(US_EHIP, what + ": " + hipGetErrorString(e));
 }
 
 int us_whisper_decode_beam(us_whisper_handle h, const float* features, int B, int T, const int64_t* prompt, int P,
@@ -1495,28 +1488,14 @@ int us_whisper_decode_beam(us_whisper_handle h, const float* features, int B, in
                            void* workspace, size_t workspace_bytes, us_stream stream) {
   const std::string what = "us_whisper_decode_beam";
   if (!h || !prompt || !options || !tokens || !n || !sum_logprobs || B <= 0) return WeightTable::fail(h, US_EINVAL, what + ": bad argument");
-  const auto& c = h->cfg;
   const auto& o = *options;
-  const int V = c.vocab_size, max_new = o.max_new, nb = beam_size, C = max_candidates, Tm = c.max_target_positions;
+  const int V = h->cfg.vocab_size, max_new = o.max_new, nb = beam_size, C = max_candidates, Tm = h->cfg.max_target_positions;
   if (nb < 1 || nb > kWbMaxBeam)
     return h->fail(US_EINVAL, what + ": beam_size = " + std::to_string(nb) + " must lie in [1, " + std::to_string(kWbMaxBeam) + "]");
   if (C < 1 || C > kWbMaxPool)
     return h->fail(US_EINVAL, what + ": max_candidates = " + std::to_string(C) + " must lie in [1, " + std::to_string(kWbMaxPool) + "]");
-  if (P < 1 || max_new < 1 || (long long)P + max_new > Tm)
-    return h->fail(US_EINVAL, what + ": a prompt of " + std::to_string(P) + " and " + std::to_string(max_new) +
-                                  " new tokens need P >= 1, max_new >= 1 and P + max_new <= max_target_positions = " + std::to_string(Tm));
-  if (o.eos < 0 || o.eos >= o.no_timestamps)
-    return h->fail(US_EINVAL, what + ": eos = " + std::to_string(o.eos) + " must lie in [0, no_timestamps = " + std::to_string(o.no_timestamps) + ")");
-  if ((long long)o.no_timestamps + 1 >= V)
-    return h->fail(US_EINVAL, what + ": no_timestamps + 1 = " + std::to_string((long long)o.no_timestamps + 1) + " >= vocab_size = " + std::to_string(V) +
-                                  ": the vocabulary has no timestamp token");
-  if (o.max_initial_timestamp_index < -1) return h->fail(US_EINVAL, what + ": max_initial_timestamp_index must be -1 (none) or an index");
-  if (o.no_speech < -1 || o.no_speech >= V) return h->fail(US_EINVAL, what + ": no_speech lies outside the vocabulary (-1: none)");
-  if (o.no_speech >= 0 && !no_speech_prob) return h->fail(US_EINVAL, what + ": a no_speech token needs no_speech_prob");
-  if (o.sot_index < 0 || o.sot_index >= P)
-    return h->fail(US_EINVAL, what + ": sot_index = " + std::to_string(o.sot_index) + " lies outside the prompt of " + std::to_string(P));
-  const std::string badtok = wh_bad_token(what, prompt, (size_t)B * P, V);
-  if (!badtok.empty()) return h->fail(US_EINVAL, badtok);
+  const std::string bad = wh_bad_decode(what, h->cfg, o, prompt, B, P, no_speech_prob);
+  if (!bad.empty()) return h->fail(US_EINVAL, bad);
   if (B > 65535) return h->fail(US_EINVAL, what + ": at most 65535 items");
   if (!workspace || workspace_bytes < us_whisper_beam_workspace_bytes(h, B, nb))
     return h->fail(US_EINVAL, what + ": workspace too small (us_whisper_beam_workspace_bytes)");
@@ -1526,55 +1505,18 @@ int us_whisper_decode_beam(us_whisper_handle h, const float* features, int B, in
   const WhPlan p = wh_plan(h, B);
   const WhBeamPlan bp = wh_beam_plan(h, B, nb);
   float* base = ws_align(workspace);
-  const WhSelect sel = wh_select_carve(base + p.select);       // the plain partials of the no-speech probability
   const WhBeamState st = wh_beam_carve(base + bp.state, V, Tm, Tm);
   const WhRules r{o.eos, o.no_timestamps + 1, o.max_initial_timestamp_index};
-  const int nc = wh_chunks(V), ipg = kWhItems / nb, cache_rows = wh_beam_group_rows(B, nb);
-  const size_t H = (size_t)c.d_model;
-  float* L = base + p.logits;
-  hipError_t e = hipSuccess;
-  for (int b0 = 0; b0 < B && e == hipSuccess; b0 += ipg) {
-    const int items = std::min(ipg, B - b0), M = items * nb;
-    WhStep t{h, s, base + p.x, base + p.q, base + p.att, base + p.ff, base + bp.cache, base + p.kv + (size_t)b0 * 2 * H * c.max_source_positions,
-             B, M, cache_rows, nb, st.anc};
-    long long* tok = reinterpret_cast<long long*>(tokens) + (size_t)b0 * max_new;
-    long long* cnt = reinterpret_cast<long long*>(n) + b0;
-    hipLaunchKernelGGL(wh_beam_init_kernel, dim3(1), dim3(256), 0, s, st, WhBeamHist{}, 0, nb, items, o.eos, Tm, Tm);
-    auto no_speech = [&](int pos) {                     // L holds the logits of position `pos`; the item's first row speaks for it
-      if (o.no_speech < 0 || pos != o.sot_index) return;
-      hipLaunchKernelGGL(wh_select_partial_kernel, dim3(nc, M), dim3(256), 0, s, L, nullptr, nullptr, sel.st, r, sel.part, V, nc, 1);
-      hipLaunchKernelGGL(wh_nospeech_kernel, dim3(items), dim3(256), 0, s, sel.part, L, no_speech_prob + b0, V, nc, o.no_speech, nb);
-    };
-    WhTokens f;
-    for (int pos = 0; pos + 1 < P; ++pos) {             // every row of an item walks the prompt: its own keys and values, identity ancestry
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = m < M ? (int)prompt[(size_t)(b0 + m / nb) * P + pos] : 0;
-      wh_embed(t, f, st.cur, pos);
-      wh_layers(t, pos);
-      if (o.no_speech >= 0 && pos == o.sot_index) {
-        wh_logits(t, L, V);
-        no_speech(pos);
-      }
-    }
-    for (int step = 0; step < max_new; ++step) {
-      const int pos = P - 1 + step;
-      for (int m = 0; m < kWhItems; ++m) f.id[m] = step == 0 && m < M ? (int)prompt[(size_t)(b0 + m / nb) * P + pos] : step == 0 ? 0 : -1;
-      t.anc = st.anc + (size_t)(step & 1) * kWhItems * Tm;
-      wh_embed(t, f, st.cur, pos);
-      wh_layers(t, pos);
-      wh_logits(t, L, V);
-      if (step == 0) no_speech(pos);
-      wh_beam_step(L, suppress, begin_suppress, st, r, WhBeamOut{}, V, nb, C, items, step, pos, Tm, Tm, 1, s);
-      if ((step + 1) % kWhPoll == 0 && step + 1 < max_new) {
-        int running = 1;
-        if ((e = hipMemcpyAsync(&running, st.running, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) break;
-        if (running <= 0) break;
-      }
-    }
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(wh_beam_final_kernel, dim3(items), dim3(256), 0, s, st, tok, cnt, sum_logprobs + b0, nb, Tm, max_new, o.eos);
-  }
-  if (e == hipSuccess) e = hipGetLastError();
+  long long *tok = reinterpret_cast<long long*>(tokens), *cnt = reinterpret_cast<long long*>(n);
+  WhPolicy pol{nb, st.cur, st.running, st.anc, base + bp.cache, wh_beam_group_rows(B, nb)};
+  pol.init = [&](int, int items) { hipLaunchKernelGGL(wh_beam_init_kernel, dim3(1), dim3(256), 0, s, st, WhBeamHist{}, 0, nb, items, o.eos, Tm, Tm); };
+  pol.select = [&](const float* L, int, int items, int step, int pos) {
+    wh_beam_step(L, suppress, begin_suppress, st, r, WhBeamOut{}, V, nb, C, items, step, pos, Tm, Tm, 1, s);
+  };
+  pol.final = [&](int b0, int items) {
+    hipLaunchKernelGGL(wh_beam_final_kernel, dim3(items), dim3(256), 0, s, st, tok + (size_t)b0 * max_new, cnt + b0, sum_logprobs + b0, nb, Tm, max_new, o.eos);
+  };
+  const hipError_t e = wh_walk(h, p, base, prompt, B, P, max_new, WhProbe{o.no_speech, o.sot_index, no_speech_prob}, pol, s);
   return e == hipSuccess ? US_OK : h->hip(what.c_str(), e);
 }
 

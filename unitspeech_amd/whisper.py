@@ -334,8 +334,8 @@ class WhisperForConditionalGeneration(HandleModule):
         sup, beg = self._mask(suppress_tokens, x.device), self._mask(begin_suppress_tokens, x.device)
         tokens = torch.empty(B, max(max_new, 1), dtype=torch.int64, device=x.device)
         n = torch.empty(B, dtype=torch.int64, device=x.device)
-        self._call(lib, x.device, "generate", self._h, x.data_ptr(), B, T, ids, P, max_new, int(eos), sup.data_ptr() if sup is not None else None,
-                   beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        self._call(lib, x.device, "generate", self._h, x.data_ptr(), B, T, ids, P, max_new, int(eos), _ptr(sup), _ptr(beg), tokens.data_ptr(),
+                   n.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         return tokens, n
 
     @torch.no_grad()
@@ -372,16 +372,13 @@ class WhisperForConditionalGeneration(HandleModule):
         n = torch.empty(B, dtype=torch.int64, device=x.device)
         lp = torch.empty(B, dtype=torch.float32, device=x.device)
         ns = torch.empty(B, dtype=torch.float32, device=x.device) if no_speech_id is not None else None
+        name, beam = "decode", ()
         if beam_size is not None:
-            nb, cand = int(beam_size), int(round(int(beam_size) * (1.0 if patience is None else float(patience))))
+            nb = int(beam_size)
+            name, beam = "decode_beam", (nb, int(round(nb * (1.0 if patience is None else float(patience)))))
             ws = self._beam_workspace(lib, x.device, B, nb)
-            self._call(lib, x.device, "decode_beam", self._h, x.data_ptr(), B, T, ids, P, C.byref(o), nb, cand,
-                       sup.data_ptr() if sup is not None else None, beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(),
-                       lp.data_ptr(), ns.data_ptr() if ns is not None else None, ws.data_ptr(), ws.numel(), stream)
-            return WhisperDecoding(tokens, n, lp, ns)
-        self._call(lib, x.device, "decode", self._h, x.data_ptr(), B, T, ids, P, C.byref(o), sup.data_ptr() if sup is not None else None,
-                   beg.data_ptr() if beg is not None else None, tokens.data_ptr(), n.data_ptr(), lp.data_ptr(),
-                   ns.data_ptr() if ns is not None else None, ws.data_ptr(), ws.numel(), stream)
+        self._call(lib, x.device, name, self._h, x.data_ptr(), B, T, ids, P, C.byref(o), *beam, _ptr(sup), _ptr(beg), tokens.data_ptr(), n.data_ptr(),
+                   lp.data_ptr(), _ptr(ns), ws.data_ptr(), ws.numel(), stream)
         return WhisperDecoding(tokens, n, lp, ns)
 
     def _beam_workspace(self, lib, device, B, beam_size):
@@ -448,34 +445,48 @@ class WhisperForConditionalGeneration(HandleModule):
 _select_scratch = {}
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _select_call(what, logits, history, options, suppress, begin_suppress, scores=None, n=1):
+    """What `select_tokens` and `select_beams` (scores, n rows per item) check and marshal alike -> (lib, x, R, V, `us_whisper_history[R]`, the
+    options struct of (eos, no_timestamps, max_initial_timestamp_index), the device's cached scratch, the stream)."""
+    if logits.device.type != "cuda" or logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"{what}: expected fp32 logits {'[B, V]' if scores is None else '[B * n, V]'} on a ROCm device, got {logits.dtype} "
+                         f"{tuple(logits.shape)} on {logits.device}")
+    lib = _lib.load()
+    x = logits.contiguous()
+    R, V = int(x.shape[0]), int(x.shape[1])
+    if scores is None and len(history) != R:
+        raise ValueError(f"{what}: {len(history)} histories for {R} items")
+    if scores is not None and (n < 1 or R % n or len(history) != R or len(scores) != R):
+        raise ValueError(f"{what}: {R} rows of logits, {len(history)} histories and {len(scores)} scores do not make items of {n} rows")
+    for m in (suppress, begin_suppress):
+        if m is not None and (m.dtype != torch.uint8 or m.numel() != V or m.device != x.device):
+            raise ValueError(f"{what}: a mask must be uint8 [V] on the logits' device")
+    hist = (_lib.us_whisper_history * R)(*[_lib.us_whisper_history(*[int(v) for v in h]) for h in history])
+    o = _lib.us_whisper_decode_options(*[int(v) for v in options], -1, 0, 1)
+    nbytes = int(lib.us_whisper_select_scratch_bytes(V) if scores is None else lib.us_whisper_beam_select_scratch_bytes(V, n))
+    ws = _select_scratch.get(x.device)
+    if ws is None or ws.numel() < nbytes:
+        _select_scratch[x.device] = ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    return lib, x, R, V, hist, o, ws, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
 @torch.no_grad()
 def select_tokens(logits, history, *, eos_token_id, no_timestamps_id, max_initial_timestamp_index=-1, suppress=None, begin_suppress=None):
     """One selection step of `decode` on its own (`us_whisper_select`): logits [B, V] fp32 on the device, history: per item (n_sampled, last,
     penultimate, last_timestamp, done), suppress / begin_suppress: uint8 masks [V] on the device or None -> (token [B] int64, logprob [B]
     fp32, decided_timestamp [B] int32) on the device."""
-    if logits.device.type != "cuda" or logits.dim() != 2 or logits.dtype != torch.float32:
-        raise ValueError(f"select_tokens: expected fp32 logits [B, V] on a ROCm device, got {logits.dtype} {tuple(logits.shape)} on {logits.device}")
-    lib = _lib.load()
-    x = logits.contiguous()
-    B, V = int(x.shape[0]), int(x.shape[1])
-    if len(history) != B:
-        raise ValueError(f"select_tokens: {len(history)} histories for {B} items")
-    for m in (suppress, begin_suppress):
-        if m is not None and (m.dtype != torch.uint8 or m.numel() != V or m.device != x.device):
-            raise ValueError("select_tokens: a mask must be uint8 [V] on the logits' device")
-    hist = (_lib.us_whisper_history * B)(*[_lib.us_whisper_history(*[int(v) for v in h]) for h in history])
-    o = _lib.us_whisper_decode_options(int(eos_token_id), int(no_timestamps_id), int(max_initial_timestamp_index), -1, 0, 1)
-    n = int(lib.us_whisper_select_scratch_bytes(V))
-    ws = _select_scratch.get(x.device)
-    if ws is None or ws.numel() < n:
-        _select_scratch[x.device] = ws = torch.empty(max(n, 1), dtype=torch.uint8, device=x.device)
+    lib, x, B, V, hist, o, ws, stream = _select_call("select_tokens", logits, history, (eos_token_id, no_timestamps_id, max_initial_timestamp_index),
+                                                     suppress, begin_suppress)
     token = torch.empty(B, dtype=torch.int64, device=x.device)
     logprob = torch.empty(B, dtype=torch.float32, device=x.device)
     decided = torch.empty(B, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        rc = lib.us_whisper_select(x.data_ptr(), B, V, hist, C.byref(o), suppress.data_ptr() if suppress is not None else None,
-                                   begin_suppress.data_ptr() if begin_suppress is not None else None, token.data_ptr(), logprob.data_ptr(),
-                                   decided.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        rc = lib.us_whisper_select(x.data_ptr(), B, V, hist, C.byref(o), _ptr(suppress), _ptr(begin_suppress), token.data_ptr(), logprob.data_ptr(),
+                                   decided.data_ptr(), ws.data_ptr(), ws.numel(), stream)
     _lib.check(rc, None, "us_whisper_select")
     return token, logprob, decided
 
@@ -487,31 +498,17 @@ def select_beams(logits, history, scores, beam_size, *, eos_token_id, no_timesta
     rows item-major; history: per row (n_sampled, last, penultimate, last_timestamp, dead); scores: per row, floats -> dict on the device:
     parent [B, n] int32 (-1: dead), token [B, n] int64, score [B, n] fp64, n_live [B], fin_parent [B, n] int32 and fin_score [B, n] fp64 (the
     newly finished entries in walk order), n_fin [B]."""
-    if logits.device.type != "cuda" or logits.dim() != 2 or logits.dtype != torch.float32:
-        raise ValueError(f"select_beams: expected fp32 logits [B * n, V] on a ROCm device, got {logits.dtype} {tuple(logits.shape)} on {logits.device}")
-    lib = _lib.load()
-    x = logits.contiguous()
-    n, R, V = int(beam_size), int(x.shape[0]), int(x.shape[1])
-    if n < 1 or R % n or len(history) != R or len(scores) != R:
-        raise ValueError(f"select_beams: {R} rows of logits, {len(history)} histories and {len(scores)} scores do not make items of {n} rows")
+    n = int(beam_size)
+    lib, x, R, V, hist, o, ws, stream = _select_call("select_beams", logits, history, (eos_token_id, no_timestamps_id, max_initial_timestamp_index),
+                                                     suppress, begin_suppress, scores, n)
     B = R // n
-    for m in (suppress, begin_suppress):
-        if m is not None and (m.dtype != torch.uint8 or m.numel() != V or m.device != x.device):
-            raise ValueError("select_beams: a mask must be uint8 [V] on the logits' device")
-    hist = (_lib.us_whisper_history * R)(*[_lib.us_whisper_history(*[int(v) for v in h]) for h in history])
     sc = (C.c_double * R)(*[float(v) for v in scores])
-    o = _lib.us_whisper_decode_options(int(eos_token_id), int(no_timestamps_id), int(max_initial_timestamp_index), -1, 0, 1)
-    nbytes = int(lib.us_whisper_beam_select_scratch_bytes(V, n))
-    ws = _select_scratch.get(x.device)
-    if ws is None or ws.numel() < nbytes:
-        _select_scratch[x.device] = ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
     new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=x.device)
     out = dict(parent=new(torch.int32, B, n), token=new(torch.int64, B, n), score=new(torch.float64, B, n), n_live=new(torch.int32, B),
                fin_parent=new(torch.int32, B, n), fin_score=new(torch.float64, B, n), n_fin=new(torch.int32, B))
     with torch.cuda.device(x.device):
-        rc = lib.us_whisper_beam_select(x.data_ptr(), B, V, n, hist, sc, C.byref(o), suppress.data_ptr() if suppress is not None else None,
-                                        begin_suppress.data_ptr() if begin_suppress is not None else None, *[t.data_ptr() for t in out.values()],
-                                        ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        rc = lib.us_whisper_beam_select(x.data_ptr(), B, V, n, hist, sc, C.byref(o), _ptr(suppress), _ptr(begin_suppress),
+                                        *[t.data_ptr() for t in out.values()], ws.data_ptr(), ws.numel(), stream)
     _lib.check(rc, None, "us_whisper_beam_select")
     return out
 
